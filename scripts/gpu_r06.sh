@@ -61,7 +61,7 @@ e)  # A/B: early touch of the next step's visited words (EHX_GW_WARM), same box,
   ;;
 f)  # EHX-MANIFOLD-1 on the device == the oracle; then the default bench run with the 10 M x 768 structured graph leg
   timeout 600 python -m pytest tests/test_datagen.py -x -q 2>&1 | tail -3
-  timeout 900 python bench.py > $O/r06_f_bench_line.json 2> $O/r06_f_bench.err; echo "bench rc=$?"
+  timeout 900 python bench.py --full > $O/r06_f_bench_line.json 2> $O/r06_f_bench.err; echo "bench rc=$?"
   cp $O/bench_detail.json $O/r06_f_bench_detail.json 2>/dev/null
   grep -E "leg done|structured|skipp" $O/r06_f_bench.err | tail -30
   python - <<PY
@@ -77,7 +77,7 @@ g)  # keyed rows after a generated base; configs[4] with the Set stream on the f
     # the headline and under concurrent Sets, same box
   timeout 600 python -m pytest tests/test_generated_base.py tests/test_concurrent_set.py -x -q 2>&1 | tail -3
   for sync in 0 2 0 2; do
-    EHX_I8_SYNC=$sync timeout 900 python bench.py --graph-rows 0 --structured-rows 0 --structured-big-rows 0 --single-query 0 \
+    EHX_I8_SYNC=$sync timeout 900 python bench.py --full --graph-rows 0 --structured-rows 0 --structured-big-rows 0 --single-query 0 \
       --reference-benchmark 0 --no-cpu-baseline --steps 20 --warmup 5 --detail-file $O/r06_g_sync${sync}_detail.json \
       > $O/r06_g_sync${sync}_line.json 2> $O/r06_g_sync${sync}.err; echo "sync=$sync rc=$?"
     python - <<PY
@@ -162,13 +162,13 @@ m)  # what the HALF kernel's parked cycles are made of (6.25 M x 128: SQ counter
   grep -h "ScanArgsI8E" $O/prof/r06_m_6250k128_i8_pmc_sq_summary.txt $O/prof/r06_m_6250k128_i8_pmc_sq2_summary.txt | grep -v "^#" | cut -c1-170
   cp $O/prof/r06_m_*summary.txt $O/ 2>/dev/null
   find $O/prof -name "*.db" -size +4M -delete
-  timeout 900 python bench.py > $O/r06_m_bench_line.json 2> $O/r06_m_bench.err; echo "bench rc=$?"
+  timeout 900 python bench.py --full > $O/r06_m_bench_line.json 2> $O/r06_m_bench.err; echo "bench rc=$?"
   cp $O/bench_detail.json $O/r06_m_bench_detail.json 2>/dev/null
   grep -E "leg done|structured|skipp" $O/r06_m_bench.err | tail -20
   ;;
 n)  # the configs[3]-shard graph leg alone (6.25 M x 128 L2 structured rows: strict / wide walk with its helper wave), then the
     # new sharded test
-  timeout 900 python bench.py --graph-rows 0 --structured-rows 0 --structured-big-rows 0 --single-query 0 --reference-benchmark 0 \
+  timeout 900 python bench.py --full --graph-rows 0 --structured-rows 0 --structured-big-rows 0 --single-query 0 --reference-benchmark 0 \
     --no-cpu-baseline --config-legs 0 --set-concurrent 0 --no-f32-engine --check-queries 0 --rows 1000000 \
     --detail-file $O/r06_n_detail.json > $O/r06_n_line.json 2> $O/r06_n.err; echo "bench rc=$?"
   python - <<PY
@@ -249,7 +249,7 @@ u)  # the round's final library: whole GPU suite, rocprofv3 trace + FETCH / WRIT
   find $O/prof -name "*.db" -size +4M -delete
   S=q bash scripts/gpu_r06.sh q 2>&1 | grep -v "^W2026" | grep "total\|^#"
   for f in $O/r06_q_*_timeline.txt; do cp $f $O/r06_u_$(basename $f | sed s/r06_q_//); done
-  timeout 1200 python bench.py > $O/r06_u_bench_line.json 2> $O/r06_u_bench.err; echo "bench rc=$?"
+  timeout 1200 python bench.py --full > $O/r06_u_bench_line.json 2> $O/r06_u_bench.err; echo "bench rc=$?"
   cp $O/bench_detail.json $O/r06_u_bench_detail.json 2>/dev/null
   grep -E "leg done|skipp" $O/r06_u_bench.err | tail -20 | cut -c1-220
   python - <<PY
@@ -263,7 +263,7 @@ PY
 v)  # the driver's own sequence on the final library: smoke(), then bench.py with the driver's arguments; and the SQ counters
     # of the headline's main pass (the wave-cycle split DESIGN quotes)
   timeout 600 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2
-  timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/r06_${VT:-v}_bench_line.json 2> $O/r06_${VT:-v}_bench.err; echo "bench rc=$?"
+  timeout 1200 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/r06_${VT:-v}_bench_line.json 2> $O/r06_${VT:-v}_bench.err; echo "bench rc=$?"
   cp $O/bench_detail.json $O/r06_${VT:-v}_bench_detail.json 2>/dev/null
   python - <<PY
 import json

@@ -33,11 +33,12 @@ def bench_on_stand_ins(monkeypatch, tmp_path):
     for var in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         monkeypatch.delenv(var, raising=False)
 
-    def run(argv):
-        """runs main(); returns the FULL record (the detail file).  The one stdout line — the compact record the driver
-        parses — is checked here for every run (size bound, contract fields) and kept as run.line"""
+    def run(argv, full=True):
+        """runs main() (with --full unless full=False); returns the FULL record (the detail file).  The one stdout line —
+        the compact record the driver parses — is checked here for every run (size bound, contract fields) and kept as
+        run.line"""
         detail = str(tmp_path / "bench_detail.json")
-        monkeypatch.setattr(sys, "argv", ["bench.py"] + argv + ["--detail-file", detail])
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + argv + ["--full"] * full + ["--detail-file", detail])
         buf = io.StringIO()
         with redirect_stdout(buf):
             bench.main()
@@ -99,6 +100,64 @@ def test_default_flow_prints_one_json_line_with_the_contract_fields(bench_on_sta
         assert set(("ef", "recall_at_10", "qps", "frac")) <= set(c[leg]) and "recall_vs_ef" not in c[leg]
     assert c["graph_path_structured"]["exact_flat_qps"] == r["graph_path_structured"]["exact_flat_engine_same_rows_queries_per_s"]
     assert not any(isinstance(v, str) and len(v) > 200 for v in json.dumps(c).split('"'))   # no prose
+
+
+def test_a_plain_run_times_the_headline_and_nothing_else(bench_on_stand_ins):
+    """without --full: set up, warm up, the timed steps, the line — no exactness block, no A/B legs, no CPU baseline, no
+    optional legs, even where their flags ask for them"""
+    r = bench_on_stand_ins(SMALL + ["--graph-rows", "1000", "--structured-rows", "600", "--steps", "5"], full=False)
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "config", "roofline"):
+        assert key in r, key
+    assert r["steps"] == 5 and r["higher_is_better"] is True and r["unit"] == "queries/s"
+    assert sum(c["calls"] for c in r["config"]["host_calls"]) == 5          # --steps timed calls, no more
+    for key in ("exactness", "recall_at_10", "device_resident_queries", "host_pointer_one_caller", "f32_scan_engine",
+                "configs", "cpu_baseline", "graph_path", "graph_path_structured", "optional_legs_skipped", "cpu_hnsw_offline",
+                "outputs_dumped"):
+        assert key not in r, key
+    c = bench_on_stand_ins.line
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert c[key] == r[key], key
+
+
+@pytest.mark.parametrize("full", [False, True])
+def test_dump_outputs_writes_the_last_timed_batchs_answer(bench_on_stand_ins, tmp_path, full):
+    """--dump-outputs DIR: ids / distances / counts the caller of the timed path received for its LAST timed batch (here
+    batch warmup + steps - 1 = 3), as float64 / float32 arrays — the same with or without --full, and run to run"""
+    import threading
+    dumps = []
+    for run in range(2):
+        bench_on_stand_ins.module._EMIT = threading.Lock()      # (emit() prints once per process: a fresh run)
+        d = tmp_path / ("dump%d" % run)
+        r = bench_on_stand_ins(SMALL + ["--graph-rows", "0", "--structured-rows", "0", "--no-cpu-baseline",
+                                        "--dump-outputs", str(d)], full=full)
+        assert r["outputs_dumped"]["arrays"] == ["counts", "distances", "ids"] and r["outputs_dumped"]["batch"] == 3
+        dumps.append({n: np.load(d / (n + ".npy")) for n in ("ids", "distances", "counts")})
+    a, b = dumps
+    assert a["ids"].dtype == np.float64 and a["distances"].dtype == np.float32 and a["counts"].dtype == np.float64
+    assert a["ids"].shape == (16, 10) and a["distances"].shape == (16, 10) and a["counts"].shape == (16,)
+    for n in a:
+        assert a[n].tobytes() == b[n].tobytes(), n
+    X = pyoracle.gen_rows(20250211, 0, 3000, 32, normalize=True)          # (SEED_CORPUS, SEED_QUERY)
+    Q = pyoracle.gen_rows(20250212, 3 * 16, 16, 32, normalize=True)
+    o_ids, o_dist, o_cnt = pyoracle.exhaustive(X, Q, 10, pyoracle.METRIC_COSINE)
+    assert np.array_equal(a["ids"], o_ids.astype(np.float64)) and a["distances"].tobytes() == o_dist.tobytes()
+    assert np.array_equal(a["counts"], o_cnt.astype(np.float64))
+
+
+def test_dump_outputs_samples_a_batch_too_large_for_the_limit(bench_on_stand_ins, tmp_path, monkeypatch):
+    bench = bench_on_stand_ins.module
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 2000)
+    ids = np.arange(400, dtype=np.uint64).reshape(40, 10)
+    dist = np.linspace(0, 1, 400, dtype=np.float32).reshape(40, 10)
+    names = bench.dump_outputs(str(tmp_path / "d"), ids, dist, np.full(40, 10, np.uint32))
+    assert names == ["counts", "distances", "ids", "query_rows"]
+    got = {n: np.load(tmp_path / "d" / (n + ".npy")) for n in names}
+    assert sum(a.nbytes for a in got.values()) <= 2000
+    rows = got["query_rows"].astype(np.int64)
+    assert len(rows) == 2000 // (10 * 8 + 10 * 4 + 8 + 8) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(got["ids"], ids[rows].astype(np.float64)) and np.array_equal(got["distances"], dist[rows])
+    again = bench.dump_outputs(str(tmp_path / "e"), ids, dist, np.full(40, 10, np.uint32))   # a fixed, seeded sample
+    assert np.array_equal(np.load(tmp_path / "e" / "query_rows.npy"), got["query_rows"]) and again == names
 
 
 def test_structured_10m_leg_reports_the_graph_path_at_the_metrics_recall_with_both_walks(bench_on_stand_ins):
@@ -327,6 +386,7 @@ def test_multi_rank_flow_rank0_prints_the_line(bench_on_stand_ins, monkeypatch):
 
 def _run_bench_subprocess(argv, devices, detail=None):
     import subprocess
+    argv = argv + ["--full"]
     if detail is not None:
         argv = argv + ["--detail-file", str(detail)]
     env = dict(os.environ, EHX_BENCH_STANDINS="1", EHX_STANDIN_DEVICES=str(devices),
