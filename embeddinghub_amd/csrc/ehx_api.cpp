@@ -361,7 +361,7 @@ int ehx_space_scan_engine(ehx_space* s, uint32_t* engine) {
   std::shared_lock<std::shared_mutex> rl(s->mu);
   if (s->dropped) return fail(EHX_ENOTFOUND, "Not found");
   if (is_parent(s)) return ehx_space_scan_engine(s->shards[0], engine);
-  *engine = (uint32_t)resolve_engine(s);
+  *engine = (uint32_t)resolve_engine(s, s->n.load(std::memory_order_acquire));
   return EHX_OK;
 }
 

@@ -6,6 +6,8 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <chrono>
+#include <thread>
 
 namespace ehx {
 
@@ -44,6 +46,9 @@ struct Env {
   bool graph_vislog = true;       // EHX_GRAPH_VISLOG=0: visited bitmaps cleared by a memset per batch, never by the visit log
   int graph_help = -1;            // EHX_GRAPH_HELP = 0 | 1: the wide walk's helper wave off / on whatever the shape (-1: by shape)
   uint32_t graph_width = 0;       // EHX_GRAPH_WIDTH = 1 | 2 | 4: expansions per step of every graph search (0: the space's search_width)
+  // ---- tests only ----
+  uint32_t test_pause_us = 0;     // EHX_TEST_PAUSE_US [0, 100000]: a search sleeps this long on the host at the points where a
+                                  // concurrent append could slip in (test_pause below) — widens those windows for the tests
 };
 
 inline const Env& env() {
@@ -119,9 +124,20 @@ inline const Env& env() {
       const long x = atol(g);
       if (x == 1 || x == 2 || x == 4) v.graph_width = (uint32_t)x;
     }
+    if (const char* g = str("EHX_TEST_PAUSE_US")) {
+      const long x = atol(g);
+      v.test_pause_us = (uint32_t)(x < 0 ? 0 : (x > 100000 ? 100000 : x));
+    }
     return v;
   }();
   return e;
+}
+
+// EHX_TEST_PAUSE_US: called by a search after it has resolved its engine and pass plan, between the pages of the exhaustive
+// pass and inside the one-launch path — where a Set published meanwhile must not change what the search answers for.
+// Unset: one branch.
+inline void test_pause() {
+  if (env().test_pause_us) std::this_thread::sleep_for(std::chrono::microseconds(env().test_pause_us));
 }
 
 }  // namespace ehx

@@ -31,7 +31,7 @@ ScanPlan plan_scan(uint32_t nq, uint32_t n_tiles, uint32_t k, int n_cus) {
 //   f16 = false: the fp32 MFMA scan (k_flat8.hip), exact on its own.
 //   f16 = true : the fp16 MFMA filter scan (k_flat16.hip); per-query certification flags land in
 //                s->dUflags and the caller re-runs the unflagged remainder through the fp32 scan.
-int flat_pass(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, uint64_t* d_ids,
+int flat_pass(ehx_space* s, uint64_t n_pub, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, uint64_t* d_ids,
               float* d_dist, uint32_t* d_count, bool f16, bool count_stats) {
   Engine& E = engine();
   // A cascade of scan passes over growing row ranges (one tile per workgroup, then x8 per pass): after
@@ -41,7 +41,7 @@ int flat_pass(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, u
   // tile epilogue stays on its branch-free fast path; a single pass would have every workgroup warm its
   // thresholds up from +inf (~k' ln(rows/k') appends per list).
   const uint32_t tile_rows = f16 ? kTileRows16 : kTileRows;
-  const uint32_t n_tiles = (uint32_t)((s->n + tile_rows - 1) / tile_rows);
+  const uint32_t n_tiles = (uint32_t)((n_pub + tile_rows - 1) / tile_rows);
   const uint32_t lpc = f16 ? 2u : scan_lists_per_chunk();
   struct Pass {
     uint32_t tile0;
@@ -76,6 +76,7 @@ int flat_pass(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, u
     passes.push_back({done, plan_scan((uint32_t)nq, n_tiles - done, k, E.n_cus)});
   }
   ScanPlan p = passes.back().plan;  // (q_tiles, q_rows, kprime are the same for every pass)
+  test_pause();
   if (f16) {
     // the filter keeps k' = k + 22 candidates (<= 56): the certification needs the k'-th lower bound to
     // clear the k-th exact distance by the fp16 error bound, so it wants more slack than the fp32 scan
@@ -129,7 +130,7 @@ int flat_pass(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, u
   if (f16)
     HIP_TRY(launch_prep_queries16(d_queries, (uint32_t)nq, s->dims, s->ld16, p.q_rows, s->metric, s->dQ16.p,
                                   s->dQgamma.p, s->dQuv.p, st));
-  if (s->n == 0) {
+  if (n_pub == 0) {
     // empty space: every query returns count 0
     HIP_TRY(hipMemsetAsync(s->dMerged.p, 0xFF, (size_t)p.q_rows * 64 * sizeof(uint64_t), st));
     HIP_TRY(hipEventRecord(s->ev[1], st));
@@ -142,7 +143,7 @@ int flat_pass(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, u
     a.rowp = s->dRowp;
     a.cand = s->dCand.p;
     a.part = s->dPart.p;
-    a.n = (uint32_t)s->n;
+    a.n = (uint32_t)n_pub;
     a.ld = s->ld;
     a.q_tiles = p.q_tiles;
     a.kprime = p.kprime;
@@ -221,7 +222,7 @@ int flat_pass(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, u
   r.nq = (uint32_t)nq;
   r.k = k;
   r.kprime = p.kprime;
-  r.n = (uint32_t)s->n;
+  r.n = (uint32_t)n_pub;
   r.dims = s->dims;
   r.ld = s->ld;
   r.metric = s->metric;
@@ -236,9 +237,9 @@ int flat_pass(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, u
   s->ev_seq = ++s->ev_counter;
   if (count_stats) {
     s->n_queries += nq;
-    s->n_dist += (uint64_t)nq * s->n;
+    s->n_dist += (uint64_t)nq * n_pub;
     // SURVEY §8d brute force bytes per batch: N*d*s + B*d*4 + B*k*12 (s = bytes per element the scan reads)
-    s->bytes_algo += s->n * s->dims * (uint64_t)(f16 ? 2 : s->esz) + (uint64_t)nq * s->dims * 4ull +
+    s->bytes_algo += n_pub * s->dims * (uint64_t)(f16 ? 2 : s->esz) + (uint64_t)nq * s->dims * 4ull +
                      (uint64_t)nq * k * 12ull;
   }
   s->n_rerank += (uint64_t)nq * p.kprime;
@@ -246,10 +247,12 @@ int flat_pass(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, u
 }
 
 // which scan engine answers first on this space right now: EHX_ENGINE_* (include/ehx.h)
-int resolve_engine(const ehx_space* s) {
-  if (s->params.mode != EHX_MODE_FLAT || s->scan_sel == EHX_SCAN_F32 || s->n == 0) return EHX_ENGINE_F32;
-  if (s->scan_sel == EHX_SCAN_AUTO && s->has8 && s->h_unsafe8 == 0 && s->n >= s->i8_min_rows) return EHX_ENGINE_I8;
-  if (s->has16 && s->h_unsafe == 0) return EHX_ENGINE_F16;
+// for the prefix of n_pub rows (the caller's snapshot: the unsafe-row counts are read after it, see ehx_space::h_unsafe)
+int resolve_engine(const ehx_space* s, uint64_t n_pub) {
+  if (s->params.mode != EHX_MODE_FLAT || s->scan_sel == EHX_SCAN_F32 || n_pub == 0) return EHX_ENGINE_F32;
+  if (s->scan_sel == EHX_SCAN_AUTO && s->has8 && s->h_unsafe8.load(std::memory_order_relaxed) == 0 && n_pub >= s->i8_min_rows)
+    return EHX_ENGINE_I8;
+  if (s->has16 && s->h_unsafe.load(std::memory_order_relaxed) == 0) return EHX_ENGINE_F16;
   return EHX_ENGINE_F32;
 }
 
@@ -258,11 +261,11 @@ int resolve_engine(const ehx_space* s) {
 // rerank256 (canonical distances of the k' = 128 best lower bounds, top-k, certificate).  Per-query verdicts land in
 // s->dUflags / s->dUncert16 like those of flat_pass.
 // `set`: which of the space's two scratch sets (ehx_space::I8Set) this batch runs in; the caller holds that set's mutex.
-int flat_pass8(ehx_space* s, int set, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, uint64_t* d_ids,
-               float* d_dist, uint32_t* d_count, bool count_stats, uint32_t* kprime_used) {
+int flat_pass8(ehx_space* s, uint64_t n_pub, int set, hipStream_t st, size_t nq, const float* d_queries, uint32_t k,
+               uint64_t* d_ids, float* d_dist, uint32_t* d_count, bool count_stats, uint32_t* kprime_used) {
   Engine& E = engine();
   ehx_space::I8Set& sc = s->i8set[set];
-  const uint32_t n_tiles = (uint32_t)((s->n + kTileRows16 - 1) / kTileRows16);
+  const uint32_t n_tiles = (uint32_t)((n_pub + kTileRows16 - 1) / kTileRows16);
   // The cascade's shape.  Shards of at least 2048 tiles (524 288 rows): a first pass of 128 tiles that aims for 64 keys
   // per query, then x8 in rows per pass; smaller ones: 512 tiles, min(512, 2 k') keys, x4 (one or two passes).  Round 5,
   // same box, 60 batches each (profiles/r05_i_ab_cascade.jsonl): 1.25 M x 768 1.190 -> 1.146 ms per batch, 10 M x 768
@@ -307,7 +310,7 @@ int flat_pass8(ehx_space* s, int set, hipStream_t st, size_t nq, const float* d_
   // d = 128).  Measured, 46 000 queries each, 0 fallbacks (profiles/r04_p_kprime_short_rows.jsonl): 6.25 M x 128 k' 256 /
   // 128 / 64 = 1.380 / 1.277 / 1.238 ms per batch, 1 M x 128 0.447 (128) / 0.414 (64); 4 M x 384 and 10 M x 256 are fine
   // with 128 (1.762 against 1.825, 2.620 against 2.722 ms) and lose queries by the hundred with 64.
-  uint32_t kp_auto = s->n >= 4000000 ? 256u : 128u;
+  uint32_t kp_auto = n_pub >= 4000000 ? 256u : 128u;
   if (s->dims <= 128) kp_auto = 64u;
   else if (s->dims < 512) kp_auto = 128u;
   if (s->dims >= 1024) kp_auto = width;
@@ -340,7 +343,7 @@ int flat_pass8(ehx_space* s, int set, hipStream_t st, size_t nq, const float* d_
   // applied, qparams.w).
   auto rank_after = [&](size_t i) -> uint32_t {
     if (i + 1 >= passes.size()) return kprime;
-    const double f = (double)((uint64_t)(passes[i + 1].tile0) * kTileRows16) / (double)s->n;
+    const double f = (double)((uint64_t)(passes[i + 1].tile0) * kTileRows16) / (double)n_pub;
     return (uint32_t)std::min<double>(kprime, std::max<double>(16.0, std::ceil(kprime * f * safety)));
   };
   // The first pass runs under a threshold taken from the sample at a LOW rank, chosen for the number of keys the pass
@@ -356,6 +359,7 @@ int flat_pass8(ehx_space* s, int set, hipStream_t st, size_t nq, const float* d_
   const uint32_t sample_rank =
       (uint32_t)std::min<uint64_t>(64, std::max<uint64_t>(8, first_keys * kSampleTiles * kTileRows16 / first_rows));
   const ScanPlan p = passes.back().plan;  // (q_tiles, q_rows are the same for every pass)
+  test_pause();
   uint32_t grid_max = 0, chunks_max = 0;
   for (auto& ps : passes) {
     grid_max = std::max(grid_max, ps.plan.grid);
@@ -411,13 +415,13 @@ int flat_pass8(ehx_space* s, int set, hipStream_t st, size_t nq, const float* d_
   a.pool_cnt = pool_cnt;
   a.ovf = ovf;
   a.pool_cap = kPoolCap;
-  a.n = (uint32_t)s->n;
+  a.n = (uint32_t)n_pub;
   a.ld = s->ld8;
   a.q_tiles = p.q_tiles;
   a.skew = env().i8_skew;
   // (cosine / inner product: B_r is one constant, every margin 0; L2^2 on normalised rows: no tile has a margin worth the
   // epilogue's extra permute and multiply-add per query block — 6.25 M x 128: 1.02 -> 1.07 ms per batch with them)
-  a.group_b = s->metric == EHX_METRIC_L2SQ && s->h_margin8 > 0 && env().i8_groupb ? 1u : 0u;
+  a.group_b = s->metric == EHX_METRIC_L2SQ && s->h_margin8.load(std::memory_order_relaxed) > 0 && env().i8_groupb ? 1u : 0u;
   auto scan = [&](const ScanPlan& pl, uint32_t tile0) -> hipError_t {
     a.tile0 = tile0;
     a.n_tiles = pl.n_tiles;
@@ -481,7 +485,7 @@ int flat_pass8(ehx_space* s, int set, hipStream_t st, size_t nq, const float* d_
   r.nq = (uint32_t)nq;
   r.k = k;
   r.kprime = kprime;
-  r.n = (uint32_t)s->n;
+  r.n = (uint32_t)n_pub;
   r.dims = s->dims;
   r.ld = s->ld;
   r.metric = s->metric;
@@ -524,9 +528,9 @@ int flat_pass8(ehx_space* s, int set, hipStream_t st, size_t nq, const float* d_
   }
   if (count_stats) {
     s->n_queries += nq;
-    s->n_dist += (uint64_t)nq * s->n;
+    s->n_dist += (uint64_t)nq * n_pub;
     // SURVEY §8d brute force bytes per batch: N*d*s + B*d*4 + B*k*12 (s = 1: the int8 scan copy)
-    s->bytes_algo += s->n * (uint64_t)s->dims + (uint64_t)nq * s->dims * 4ull + (uint64_t)nq * k * 12ull;
+    s->bytes_algo += n_pub * (uint64_t)s->dims + (uint64_t)nq * s->dims * 4ull + (uint64_t)nq * k * 12ull;
   }
   s->n_rerank += (uint64_t)nq * kprime;
   return EHX_OK;
@@ -536,13 +540,13 @@ int flat_pass8(ehx_space* s, int set, hipStream_t st, size_t nq, const float* d_
 // exhaustive_kernel), merged and emitted through the re-rank with the certification switched off (the keys
 // are exact).  Serves (a) queries no matrix-core scan can certify and (b) requests with k > EHX_MAX_K, which
 // it answers in pages of 64 results (each page keeps the keys strictly above the previous page's last).
-int exhaustive_pass(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, uint64_t* d_ids,
-                    float* d_dist, uint32_t* d_count) {
+int exhaustive_pass(ehx_space* s, uint64_t n_pub, hipStream_t st, size_t nq, const float* d_queries, uint32_t k,
+                    uint64_t* d_ids, float* d_dist, uint32_t* d_count) {
   // rows per workgroup: 8192 when there are queries enough to fill the chip; fewer queries get smaller blocks (down to
   // one 64-row step) so that about 2048 workgroups share the shard — the keys are exact whatever the partition
   const uint32_t kRowsPerBlock =
-      (uint32_t)std::min<uint64_t>(8192, std::max<uint64_t>(64, ((uint64_t)s->n * nq / 2048 + 63) / 64 * 64));
-  const uint32_t n_blocks = (uint32_t)((s->n + kRowsPerBlock - 1) / kRowsPerBlock);
+      (uint32_t)std::min<uint64_t>(8192, std::max<uint64_t>(64, ((uint64_t)n_pub * nq / 2048 + 63) / 64 * 64));
+  const uint32_t n_blocks = (uint32_t)((n_pub + kRowsPerBlock - 1) / kRowsPerBlock);
   const uint32_t pages = (k + 63) / 64;
   int rc;
   if ((rc = s->dQ.ensure(nq * s->ld))) return rc;
@@ -562,8 +566,9 @@ int exhaustive_pass(ehx_space* s, hipStream_t st, size_t nq, const float* d_quer
   HIP_TRY(launch_prep_queries(d_queries, (uint32_t)nq, s->dims, s->ld, (uint32_t)nq, s->metric, s->dQ.p, st));
   HIP_TRY(hipEventRecord(s->ev[1], st));
   for (uint32_t pg = 0; pg < pages; ++pg) {
+    if (pg) test_pause();
     const uint64_t* floor = pg ? s->dGthr.p : nullptr;
-    HIP_TRY(launch_exhaustive(s->dQ.p, s->dX, s->x_half, s->dInv, (uint32_t)s->n, s->dims, s->ld, s->metric,
+    HIP_TRY(launch_exhaustive(s->dQ.p, s->dX, s->x_half, s->dInv, (uint32_t)n_pub, s->dims, s->ld, s->metric,
                               kRowsPerBlock, n_blocks, (uint32_t)nq, floor, s->dPart.p, st));
     HIP_TRY(launch_flat_merge(s->dPart.p, (uint32_t)nq, n_blocks, 64, s->dMerged.p, st, n_blocks));
     if (pg + 1 < pages) HIP_TRY(launch_set_floor(s->dMerged.p, (uint32_t)nq, s->dGthr.p, st));
@@ -580,7 +585,7 @@ int exhaustive_pass(ehx_space* s, hipStream_t st, size_t nq, const float* d_quer
     r.nq = (uint32_t)nq;
     r.k = std::min<uint32_t>(64, k - pg * 64);
     r.kprime = 64;
-    r.n = (uint32_t)s->n;
+    r.n = (uint32_t)n_pub;
     r.dims = s->dims;
     r.ld = s->ld;
     r.metric = s->metric;
@@ -596,7 +601,7 @@ int exhaustive_pass(ehx_space* s, hipStream_t st, size_t nq, const float* d_quer
   s->end_sampled = false;
   s->ev_valid = true;
   s->ev_seq = ++s->ev_counter;
-  s->n_dist += (uint64_t)nq * s->n * pages;
+  s->n_dist += (uint64_t)nq * n_pub * pages;
   return EHX_OK;
 }
 
@@ -647,7 +652,7 @@ void i8_adapt(ehx_space* s, size_t nq, size_t n_failed, size_t n_short, uint32_t
 // (i8_short of them because their candidate list was too short) continue with the next engine.
 int knn_device_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k,
                       uint64_t* d_ids, float* d_dist, uint32_t* d_count, const std::vector<uint32_t>* i8_failed,
-                      size_t i8_short, uint32_t i8_kprime_in) {
+                      size_t i8_short, uint32_t i8_kprime_in, uint64_t n_pub) {
   if (k == 0 || nq == 0) return EHX_OK;
   if (nq > (1u << 24)) return fail(EHX_EINVAL, "too many queries in one call: %zu", nq);
   if (s->params.mode == EHX_MODE_GRAPH) {
@@ -655,15 +660,17 @@ int knn_device_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_qu
     if (k > EHX_MAX_K_PAGED) return fail(EHX_EUNSUPPORTED, "graph mode: k=%u exceeds %u", k, EHX_MAX_K_PAGED);
     return knn_graph_locked(s, st, nq, d_queries, k, d_ids, d_dist, d_count);
   }
+  // the ONE read of the row count in this search (a caller whose int8 stage already ran passes the snapshot it ran on)
+  if (n_pub == kNoSnapshot) n_pub = s->n.load(std::memory_order_acquire);
   if (k > EHX_MAX_K) {
     // beyond the candidate capacity of one scan pass: the exhaustive canonical pass, paged (exact, HBM-bound —
     // the whole shard is read once per page of 64 results and per query)
     if (k > EHX_MAX_K_PAGED) return fail(EHX_EUNSUPPORTED, "k=%u exceeds EHX_MAX_K_PAGED=%u", k, EHX_MAX_K_PAGED);
-    if (s->n == 0) {
+    if (n_pub == 0) {
       HIP_TRY(hipMemsetAsync(d_count, 0, nq * sizeof(uint32_t), st));
       return EHX_OK;
     }
-    int rc2 = exhaustive_pass(s, st, nq, d_queries, k, d_ids, d_dist, d_count);
+    int rc2 = exhaustive_pass(s, n_pub, st, nq, d_queries, k, d_ids, d_dist, d_count);
     if (rc2) return rc2;
     s->n_queries += nq;
     s->n_exhaustive += nq;
@@ -677,8 +684,8 @@ int knn_device_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_qu
   // oracle's arithmetic over every row, exact by construction, three launches — reads the rows once.  Concurrent single
   // queries never get here alone: ehx_knn coalesces them into device batches.  (EHX_SMALL_EXACT_BYTES=0 switches it off.)
   const uint64_t small_bytes = env().small_exact_bytes;
-  if (nq == 1 && s->scan_sel == EHX_SCAN_AUTO && s->n > 0 && (uint64_t)s->n * s->ld * s->esz <= small_bytes) {
-    int rc2 = exhaustive_pass(s, st, nq, d_queries, k, d_ids, d_dist, d_count);
+  if (nq == 1 && s->scan_sel == EHX_SCAN_AUTO && n_pub > 0 && n_pub * s->ld * s->esz <= small_bytes) {
+    int rc2 = exhaustive_pass(s, n_pub, st, nq, d_queries, k, d_ids, d_dist, d_count);
     if (rc2) return rc2;
     s->n_queries += nq;
     s->n_exhaustive += nq;
@@ -715,12 +722,12 @@ int knn_device_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_qu
     // through knn_host_direct's pipelined path at the same time)
     std::unique_lock<std::mutex> set_lock(s->i8set[0].mu, std::defer_lock);
     if (kind == kI8) set_lock.lock();
-    if (kind == kExhaustive) rc = exhaustive_pass(s, st, m, q, k, oi, od, oc);
+    if (kind == kExhaustive) rc = exhaustive_pass(s, n_pub, st, m, q, k, oi, od, oc);
     else if (kind == kI8) {   // (enqueued as one block, like a pipelined host batch's: per-batch scan windows stay clean)
       std::lock_guard<std::mutex> ql(s->i8_enqueue_mu);
-      rc = flat_pass8(s, 0, st, m, q, k, oi, od, oc, count_stats, &i8_kprime);
+      rc = flat_pass8(s, n_pub, 0, st, m, q, k, oi, od, oc, count_stats, &i8_kprime);
     }
-    else rc = flat_pass(s, st, m, q, k, oi, od, oc, kind == kFilter, count_stats);
+    else rc = flat_pass(s, n_pub, st, m, q, k, oi, od, oc, kind == kFilter, count_stats);
     if (rc) return rc;
     unsigned long long* d_unc = kind == kI8 ? s->i8set[0].dUncert : s->dUncert16;
     const uint32_t* d_flags = kind == kI8 ? s->i8set[0].dUflags.p : s->dUflags.p;
@@ -757,7 +764,8 @@ int knn_device_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_qu
   std::vector<uint32_t> todo, next;
   bool all = true;  // `todo` = every query
   bool counted = false;
-  const int eng = resolve_engine(s);
+  const int eng = resolve_engine(s, n_pub);
+  test_pause();
   if (eng == EHX_ENGINE_I8) {
     if (i8_failed) {
       next = *i8_failed;
@@ -773,7 +781,7 @@ int knn_device_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_qu
     todo.swap(next);
     all = todo.size() * 2 > nq;
   }
-  if ((eng == EHX_ENGINE_I8 || eng == EHX_ENGINE_F16) && s->has16 && s->h_unsafe == 0) {
+  if ((eng == EHX_ENGINE_I8 || eng == EHX_ENGINE_F16) && s->has16 && s->h_unsafe.load(std::memory_order_relaxed) == 0) {
     const size_t m = all ? nq : todo.size();
     if ((rc = stage(kFilter, all ? nullptr : &todo, !counted, &next))) return rc;
     counted = true;

@@ -227,8 +227,9 @@ struct ehx_space {
   // held SHARED — rows below the new count are resident and described before the store, the arrays do not move while any search
   // holds the lock shared — where it used to take the lock exclusively "for the length of one store": glibc's rwlock prefers
   // readers, two pipelined search callers overlap without a gap, and the writer waited ~4 batches per chunk (12.5 M x 1536
-  // under search: 63 ms per 8192-row chunk against 3 un-contended).  A search may read the count more than once; every use
-  // tolerates a later, larger value (more rows valid than tiles scanned: "a search sees a prefix of the completed Sets").
+  // under search: 63 ms per 8192-row chunk against 3 un-contended).
+  // A search loads it ONCE (acquire) and passes that snapshot down to every pass, page, launch and statistic of the call: two
+  // reads of it may differ, and a pass planned on one prefix and masked by another answers for no prefix at all.
   std::atomic<uint64_t> n{0};
   // fp16-MFMA filter scan (k_flat16.hip): unit-normalised binary16 scan copy of the rows
   bool has16 = false;          // the space keeps the fp16 scan copy (maintained on every write, whatever use16 says)
@@ -237,7 +238,9 @@ struct ehx_space {
   float2* dRowp16 = nullptr;   // [cap]
   uint32_t ld16 = 0;
   unsigned long long* dUnsafe = nullptr;  // rows the filter cannot bound (then every scan is the fp32 scan)
-  uint64_t h_unsafe = 0;
+  // (the three counters below are written by an appending Set while searches run: atomic, stored BEFORE the release store of n —
+  // a search reads them after its snapshot of n, so a prefix it scans never holds a row they do not count)
+  std::atomic<uint64_t> h_unsafe{0};
   // int8-MFMA filter scan (k_flati8.hip): per-row-scaled int8 scan copy of the unit-normalised rows
   bool has8 = false;           // the space keeps the int8 scan copy (flat spaces whose row length makes it pay)
   int8_t* dX8 = nullptr;       // [cap][ld8] in the stage-blocked scan8_index layout
@@ -248,8 +251,8 @@ struct ehx_space {
   DevBuf<uint64_t> dTileList;  // scratch of launch_make_scan8
   uint32_t ld8 = 0;
   unsigned long long* dUnsafe8 = nullptr;
-  uint64_t h_unsafe8 = 0;
-  uint64_t h_margin8 = 0;      // tiles written so far with a lane group whose min B lies > 0.1 % above the tile's (dUnsafe8[1])
+  std::atomic<uint64_t> h_unsafe8{0};
+  std::atomic<uint64_t> h_margin8{0};     // tiles written so far with a lane group whose min B lies > 0.1 % above the tile's (dUnsafe8[1])
   uint64_t i8_min_rows = 16384;  // below this the fp16 filter serves (sample pass + cascade need a few thousand rows)
   uint32_t scan_sel = EHX_SCAN_AUTO;  // EHX_SCAN_*: what ehx_space_set_scan selected
 
@@ -615,17 +618,19 @@ int knn_graph_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_que
                      float* d_dist, uint32_t* d_count, const GraphOneLaunch* one = nullptr);
 
 // ---- ehx_flat.cpp ----
-int flat_pass(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, uint64_t* d_ids,
+constexpr uint64_t kNoSnapshot = ~0ull;   // knn_device_locked: no snapshot of the row count yet, take one
+// n_pub: the search's one snapshot of the published row count (s->n.load(std::memory_order_acquire))
+int flat_pass(ehx_space* s, uint64_t n_pub, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, uint64_t* d_ids,
               float* d_dist, uint32_t* d_count, bool f16, bool count_stats);
-int resolve_engine(const ehx_space* s);
-int flat_pass8(ehx_space* s, int set, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, uint64_t* d_ids,
-               float* d_dist, uint32_t* d_count, bool count_stats, uint32_t* kprime_used = nullptr);
-int exhaustive_pass(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, uint64_t* d_ids,
-                    float* d_dist, uint32_t* d_count);
+int resolve_engine(const ehx_space* s, uint64_t n_pub);
+int flat_pass8(ehx_space* s, uint64_t n_pub, int set, hipStream_t st, size_t nq, const float* d_queries, uint32_t k,
+               uint64_t* d_ids, float* d_dist, uint32_t* d_count, bool count_stats, uint32_t* kprime_used = nullptr);
+int exhaustive_pass(ehx_space* s, uint64_t n_pub, hipStream_t st, size_t nq, const float* d_queries, uint32_t k,
+                    uint64_t* d_ids, float* d_dist, uint32_t* d_count);
 void i8_adapt(ehx_space* s, size_t nq, size_t n_failed, size_t n_short, uint32_t kprime);
 int knn_device_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k,
                       uint64_t* d_ids, float* d_dist, uint32_t* d_count, const std::vector<uint32_t>* i8_failed = nullptr,
-                      size_t i8_short = 0, uint32_t i8_kprime_in = 0);
+                      size_t i8_short = 0, uint32_t i8_kprime_in = 0, uint64_t n_pub = kNoSnapshot);
 
 // ---- ehx_write.cpp ----
 int sync_stream(ehx_space* s, hipStream_t st);

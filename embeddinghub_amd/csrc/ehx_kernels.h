@@ -93,6 +93,16 @@ __device__ __forceinline__ float cert_margin(int metric, uint32_t dims, float qn
   return base + 2e-6f * fmaxf(scale, fmaxf(qn, 1.0f));
 }
 
+// Int8 filter, L2^2: the B margin of a 32-row lane group over its tile — every row of the group has B_r >= bt + the
+// margin, given bg <= min B of the group's rows and bt <= min B of the tile's (tileg8[tile][8 + g], tilep8[tile].w,
+// k_misc.hip).  (bg - bt) rounded down, never negative: whichever writes of the two bounds a scan reads, bt + margin
+// <= max(bg, bt) (erring low), which bounds the rows both describe.  bt = +inf (a tile of padding rows): 0.
+__device__ __forceinline__ float i8_group_b_margin(float bg, float bt) {
+  float m = 0.0f;
+  if (bt < __builtin_inff()) m = bg < __builtin_inff() ? (bg - bt) * (1.0f - 1e-6f) : __builtin_inff();
+  return m > 0.0f ? m : 0.0f;
+}
+
 // Canonical distance between a prepared query and a stored row, in exactly the order of hnswlib's SSE
 // kernels (space_l2.h / space_ip.h; oracle/hnsw_oracle.hpp restates them): 4 strided partial sums
 // over the multiple-of-4 body (multiply and add NOT fused), horizontal sum t0+t1+t2+t3 left to

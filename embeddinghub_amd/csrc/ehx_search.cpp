@@ -53,8 +53,9 @@ static int knn_host_direct(ehx_space* s, size_t n_queries, const float* queries,
     // single_query_kernel).  10 k x 128: ~130 us through the three-launch path -> see DESIGN §e.
     const uint64_t one_bytes = env().small_exact_bytes;
     const bool one_on = env().one_launch;
-    if (one_on && n_queries == 1 && k <= 64 && s->params.mode == EHX_MODE_FLAT && s->scan_sel == EHX_SCAN_AUTO && s->n > 0 &&
-        s->ld <= 4096 && (uint64_t)s->n * s->ld * s->esz <= one_bytes) {
+    const uint64_t n_pub = s->n.load(std::memory_order_acquire);   // (this path's one read of the row count)
+    if (one_on && n_queries == 1 && k <= 64 && s->params.mode == EHX_MODE_FLAT && s->scan_sel == EHX_SCAN_AUTO && n_pub > 0 &&
+        s->ld <= 4096 && n_pub * s->ld * s->esz <= one_bytes) {
       constexpr size_t kOneQ = 16384;   // query slot (ld <= 4096 floats)
       if (!s->hOnePin) {
         HIP_TRY(hipHostMalloc((void**)&s->hOnePin, kOneQ + 2048, hipHostMallocCoherent | hipHostMallocMapped));
@@ -64,9 +65,10 @@ static int knn_host_direct(ehx_space* s, size_t n_queries, const float* queries,
         HIP_TRY(hipMalloc((void**)&s->dOneTicket, sizeof(uint32_t)));
         HIP_TRY(hipMemset(s->dOneTicket, 0, sizeof(uint32_t)));
       }
-      const uint32_t rpb = (uint32_t)std::max<uint64_t>(64, ((s->n + 1023) / 1024 + 63) / 64 * 64);  // <= 1024 workgroups
-      const uint32_t n_blocks = (uint32_t)((s->n + rpb - 1) / rpb);
+      const uint32_t rpb = (uint32_t)std::max<uint64_t>(64, ((n_pub + 1023) / 1024 + 63) / 64 * 64);  // <= 1024 workgroups
+      const uint32_t n_blocks = (uint32_t)((n_pub + rpb - 1) / rpb);
       if ((rc = s->dOnePart.ensure((size_t)n_blocks * 64))) return rc;
+      test_pause();
       if ((rc = wait_searches_in_flight(s, s->stream))) return rc;  // (device searches queued on other streams)
       char* h = s->hOnePin;
       memcpy(h, queries, qbytes);
@@ -82,7 +84,7 @@ static int knn_host_direct(ehx_space* s, size_t n_queries, const float* queries,
       a.done_flag = (uint32_t*)(h + kOneQ + 1024);
       a.seq = ++s->one_seq ? s->one_seq : ++s->one_seq;   // (never 0: the buffer starts zeroed)
       a.x_half = (uint32_t)s->x_half;
-      a.n = (uint32_t)s->n;
+      a.n = (uint32_t)n_pub;
       a.dims = s->dims;
       a.ld = s->ld;
       a.rows_per_block = rpb;
@@ -109,7 +111,7 @@ static int knn_host_direct(ehx_space* s, size_t n_queries, const float* queries,
       s->n_queries += 1;
       s->n_exhaustive += 1;
       s->n_one_launch += 1;
-      s->n_dist += s->n;
+      s->n_dist += n_pub;
       return EHX_OK;
     }
     // ... and in GRAPH mode (round 5; the reference's own index and request: HNSW, one query per NearestNeighbor RPC):
@@ -235,13 +237,17 @@ static int knn_host_direct(ehx_space* s, size_t n_queries, const float* queries,
   std::vector<uint32_t> failed;
   size_t n_short = 0;
   uint32_t kprime_used = 0;
-  if (pipe_on && s->params.mode == EHX_MODE_FLAT && k <= EHX_MAX_K && s->n > 0 && resolve_engine(s) == EHX_ENGINE_I8) {
+  // the ONE read of the row count in this call: the pipelined int8 stage and the rest of the chain (knn_device_locked) answer
+  // for the same prefix
+  const uint64_t n_pub = s->n.load(std::memory_order_acquire);
+  if (pipe_on && s->params.mode == EHX_MODE_FLAT && k <= EHX_MAX_K && n_pub > 0 && resolve_engine(s, n_pub) == EHX_ENGINE_I8) {
     const int set = (int)(s->i8_next_set.fetch_add(1, std::memory_order_relaxed) & 1u);   // consecutive batches alternate
     ehx_space::I8Set& sc = s->i8set[set];
+    test_pause();
     std::lock_guard<std::mutex> l(sc.mu);
     std::unique_lock<std::mutex> ql(s->i8_enqueue_mu);   // (this batch's launches go onto the stream as one block)
     HIP_TRY(hipStreamWaitEvent(s->stream, hs->in_ev, 0));
-    if ((rc = flat_pass8(s, set, s->stream, n_queries, hs->dq.p, k, d_ids, d_dist, d_cnt, false, &kprime_used))) return rc;
+    if ((rc = flat_pass8(s, n_pub, set, s->stream, n_queries, hs->dq.p, k, d_ids, d_dist, d_cnt, false, &kprime_used))) return rc;
     HIP_TRY(hipMemcpyAsync(sc.hUncertPin, sc.dUncert, sizeof(unsigned long long), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipEventRecord(sc.verdict, s->stream));
     ql.unlock();
@@ -255,8 +261,8 @@ static int knn_host_direct(ehx_space* s, size_t n_queries, const float* queries,
     copied_early = true;
     HIP_TRY(hipEventSynchronize(sc.verdict));
     s->n_queries += n_queries;
-    s->n_dist += (uint64_t)n_queries * s->n;
-    s->bytes_algo += s->n * (uint64_t)s->dims + (uint64_t)n_queries * s->dims * 4ull + (uint64_t)n_queries * k * 12ull;
+    s->n_dist += (uint64_t)n_queries * n_pub;
+    s->bytes_algo += n_pub * (uint64_t)s->dims + (uint64_t)n_queries * s->dims * 4ull + (uint64_t)n_queries * k * 12ull;
     if (*sc.hUncertPin == 0) {
       done = true;
       s->n_i8_queries += n_queries;
@@ -278,7 +284,7 @@ static int knn_host_direct(ehx_space* s, size_t n_queries, const float* queries,
     std::lock_guard<std::mutex> sl2(s->scratch_mu);
     HIP_TRY(hipStreamWaitEvent(s->stream, hs->in_ev, 0));
     if ((rc = knn_device_locked(s, s->stream, n_queries, hs->dq.p, k, d_ids, d_dist, d_cnt, have_failed ? &failed : nullptr,
-                                n_short, kprime_used)))
+                                n_short, kprime_used, n_pub)))
       return rc;
     HIP_TRY(hipEventRecord(hs->done_ev, s->stream));
   }

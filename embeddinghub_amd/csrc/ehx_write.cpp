@@ -156,9 +156,10 @@ int refresh_scan16(ehx_space* s, uint64_t row0, uint64_t n, hipStream_t st, bool
     int rcs = sync_stream(s, st);
     if (rcs) return rcs;
   }
-  s->h_unsafe = u;
-  s->h_unsafe8 = u8[0];
-  if (s->has8) s->h_margin8 = u8[1];   // (cumulative: only ever grows — using the margins is sound either way)
+  // (before the caller's release store of the row count: a search that sees these rows sees these counts)
+  s->h_unsafe.store(u, std::memory_order_relaxed);
+  s->h_unsafe8.store(u8[0], std::memory_order_relaxed);
+  if (s->has8) s->h_margin8.store(u8[1], std::memory_order_relaxed);   // (cumulative: only ever grows — using the margins is sound either way)
   return EHX_OK;
 }
 

@@ -422,7 +422,7 @@ __global__ __launch_bounds__(I8L<HALF>::kThreads, 2) void flat_scan_i8_kernel(co
   // max |A| of this wave's four 32-row lane groups (one per l >> 4) of the current tile: uniform, loaded a tile ahead
   const cf4p tgp = uniform_ptr(a.tileg + (size_t)tile_par * 16 + (size_t)wr * 4);
   float4 tg_cur = ldc(tgp, 0);
-  // ... and the B margins of the same four groups (tileg[tile][8 + g]: min B of the group - min B of the tile)
+  // ... and the min B of the same four groups (tileg[tile][8 + g]; the margin over the tile's min B: i8_group_b_margin)
   float4 tgb_cur = ldc(tgp, 2);
   // =============================== tile epilogue ===============================
   auto epilogue = [&](uint32_t t) {
@@ -498,7 +498,7 @@ __global__ __launch_bounds__(I8L<HALF>::kThreads, 2) void flat_scan_i8_kernel(co
     float g_own = 0.0f, dB = 0.0f;
     if (a.group_b) {
       const float4 tgb = tgb_cur;
-      dB = qd == 0 ? tgb.x : (qd == 1 ? tgb.y : (qd == 2 ? tgb.z : tgb.w));
+      dB = i8_group_b_margin(qd == 0 ? tgb.x : (qd == 1 ? tgb.y : (qd == 2 ? tgb.z : tgb.w)), tp.w);
       g_own = fmaxf(qp_lds[wc * 64 + lane_e].z, 0.0f) * qinv_lds[wc * 64 + lane_e] * (1.0f - 1e-4f);
     }
 #pragma unroll

@@ -518,7 +518,7 @@ __global__ __launch_bounds__(256) void rank_tiles8_kernel(const float* __restric
   tgtA[i] = gmax;
   perm8[tile * 256 + pos] = (uint8_t)tid;
   if (tid < 8) tileg8[tile * 16 + tid] = __uint_as_float(g_l[tid]);
-  else if (tid < 16) tileg8[tile * 16 + tid] = 0.0f;   // (the groups' B margins: ident_tiles8_kernel, from the rows as stored)
+  else if (tid < 16) tileg8[tile * 16 + tid] = 0.0f;   // (the groups' min B: ident_tiles8_kernel, from the rows as stored)
 }
 
 // tiles kept in row order: perm = identity, group maxima from the rows where they are
@@ -545,14 +545,16 @@ __global__ __launch_bounds__(256) void ident_tiles8_kernel(const float4* __restr
   __syncthreads();
   if (tid < 8) tileg8[tile * 16 + tid] = __uint_as_float(gm[tid]);
   else if (tid < 16) {
-    // tileg8[tile][8 + g] = (min B of group g) - (min B of the tile = tilep8[tile].w, tile_params8_kernel), ROUNDED DOWN:
-    // the scan's alarm level of the group may assume B_r >= min B of the tile + this margin for every row of the group
+    // tileg8[tile][8 + g] = min B of group g, ABSOLUTE: the scan derives the group's margin over the tile's min B
+    // (tilep8[tile].w) itself, i8_group_b_margin.  An append rewrites both arrays of the tile that straddles the published
+    // row count while scans read them with two loads; a margin stored RELATIVE to the tile's min B, read with the tile's
+    // older (higher) min B, raised a group's level above what its published rows allow.  Any mix of old and new values of
+    // two absolute bounds is sound (tests/test_i8_model.py).
     uint32_t tmin = bm[0];
     for (int j = 1; j < 8; ++j) tmin = bm[j] < tmin ? bm[j] : tmin;
     const float bt = __uint_as_float(tmin), bg = __uint_as_float(bm[tid - 8]);
-    float margin = 0.0f;
-    if (bt < __builtin_inff()) margin = bg < __builtin_inff() ? (bg - bt) * (1.0f - 1e-6f) : __builtin_inff();
-    tileg8[tile * 16 + tid] = margin > 0.0f ? margin : 0.0f;
+    tileg8[tile * 16 + tid] = bm[tid - 8] ? bg : -__builtin_inff();   // (0: a B never produced may hide there — no margin)
+    const float margin = i8_group_b_margin(bg, bt);
     // (n_margin[1]: tiles where a margin is worth having — the scan only spends instructions on them in spaces that have any)
     if (margin > 1e-3f * bt && margin < __builtin_inff()) atomicAdd(n_margin + 1, 1ull);
   }

@@ -133,6 +133,7 @@ class DurableSpace:
         self.dims = inner.dims
         self._mu = threading.Lock()
         self._freeze_waiting = 0   # FreezeSpace calls waiting for the space: writers stand back while it is > 0
+        self._freeze_cv = threading.Condition()   # guards _freeze_waiting; notified when it drops
 
     def set(self, key, vec):
         self.set_batch([key], [vec])
@@ -142,9 +143,10 @@ class DurableSpace:
         # freeze that only TRIES the lock (below) could miss it for ever.  A writer that finds a freeze waiting
         # steps aside until it is through — and is then refused by the engine ("Cannot write to immutable space"), as the
         # reference's mutex order would have it.
-        import time as _time
-        while self._freeze_waiting:
-            _time.sleep(0.001)
+        # (bounded: a freeze gives up after 120 s itself, so a longer wait here means the count went wrong)
+        with self._freeze_cv:
+            if not self._freeze_cv.wait_for(lambda: self._freeze_waiting <= 0, timeout=150.0):
+                raise TimeoutError("Set on %r: a FreezeSpace stayed pending for 150 s" % self._name)
         with self._mu:  # the log order is the apply order
             # log first, then apply: a write is never served without being persisted.  If the engine refuses the
             # rows (immutable space, allocation failure ...) the log is cut back, so a restart does not replay them.
@@ -166,7 +168,8 @@ class DurableSpace:
         # it away from everybody else for as long as the space stayed busy.
         import time as _time
         deadline = _time.monotonic() + 120.0
-        self._freeze_waiting += 1      # (under the GIL; writers poll it before they take the space's lock)
+        with self._freeze_cv:          # (writers wait on it before they take the space's lock)
+            self._freeze_waiting += 1
         try:
             while True:
                 with self._owner._mu:
@@ -182,7 +185,9 @@ class DurableSpace:
                     raise TimeoutError("FreezeSpace(%r): the space stayed busy for 120 s" % self._name)
                 _time.sleep(0.002)
         finally:
-            self._freeze_waiting -= 1
+            with self._freeze_cv:
+                self._freeze_waiting -= 1
+                self._freeze_cv.notify_all()
 
     def __getattr__(self, name):  # get / nearest / keys_sorted / __len__ ... : straight through
         return getattr(self._inner, name)

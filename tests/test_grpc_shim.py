@@ -371,3 +371,45 @@ def test_durable_freeze_and_delete_do_not_deadlock(tmp_path):
     sp2.set("still-writable", rng.standard_normal(8).astype(np.float32))   # not frozen by the stale handle's record
     assert sp2.keys_sorted() == ["fresh", "still-writable"]
     st2.close()
+
+
+def test_durable_concurrent_freezes_then_a_set_is_refused_promptly(tmp_path):
+    """Two FreezeSpace calls at once while a writer streams: the count of pending freezes is kept under a lock (an
+    unlocked += / -= from two threads can lose an update and leave writers waiting for ever); once both are through, a
+    Set gets "immutable space" at once instead of spinning."""
+    import time
+    from embeddinghub_amd.rpc.durable import DurableStore
+    from embeddinghub_amd.rpc.server import SpaceNotWritable
+    rng = np.random.default_rng(9)
+    st = DurableStore(OracleStore(), str(tmp_path))
+    for rnd in range(20):
+        sp = st.create_space("fz%d" % rnd, 8)
+        sp.set("k", rng.standard_normal(8).astype(np.float32))
+        refused, errs = [], []
+
+        def writer():
+            try:
+                for i in range(100000):
+                    sp.set("w%d" % i, rng.standard_normal(8).astype(np.float32))
+            except SpaceNotWritable:
+                refused.append(True)
+            except Exception as e:  # noqa: BLE001
+                errs.append(repr(e))
+        w = threading.Thread(target=writer)
+        w.start()
+        fs = [threading.Thread(target=sp.freeze) for _ in range(2)]
+        for t in fs:
+            t.start()
+        for t in fs:
+            t.join(timeout=30)
+            assert not t.is_alive(), "FreezeSpace hung"
+        w.join(timeout=30)
+        assert not w.is_alive(), "the writer kept waiting after both freezes were through"
+        assert not errs, errs
+        assert refused, "the writer was never refused"
+        assert sp._freeze_waiting == 0
+        t0 = time.monotonic()
+        with pytest.raises(SpaceNotWritable):
+            sp.set("late", rng.standard_normal(8).astype(np.float32))
+        assert time.monotonic() - t0 < 1.0, "a Set after the freezes did not fail promptly"
+    st.close()

@@ -285,3 +285,67 @@ def test_group_b_margin_is_sound_and_pays_on_rows_whose_norms_vary():
         rates[name] = (al_old / groups, al_new / groups)
     assert rates["raw gaussian"][0] > 0.9 and rates["raw gaussian"][1] < 0.5, rates
     assert abs(rates["normalised"][0] - rates["normalised"][1]) < 0.02, rates
+    _straddling_tile_margins_are_sound_under_any_mix(rng, d)
+
+
+def _group_b_margin(bg, bt):
+    """i8_group_b_margin (ehx_kernels.h): (bg - bt) rounded down, never negative; bt = +inf: 0"""
+    if not bt < np.inf:
+        return f32(0)
+    m = f32(f32(bg - bt) * f32(1.0 - 1e-6)) if bg < np.inf else f32(np.inf)
+    return m if m > 0 else f32(0)
+
+
+def _straddling_tile_margins_are_sound_under_any_mix(rng, d):
+    """The tile that straddles the published row count: an append writes rows of LOWER B (smaller norms) beyond the count
+    and rewrites the tile's min B (tilep8.w) and its groups' entries (tileg8[tile][8 + g]) while scans read the two with
+    independent loads — a scan may combine the old or the new value of either.  The published rows' alarms must hold under
+    all four mixes.  With the margin stored RELATIVE to the tile's min B (the old encoding) the mix "old tile B, new group
+    margin" raises a group's level by (old min B - new min B) and hides published rows: asserted here, it is why the
+    encoding changed.  With each group's ABSOLUTE min B stored and the margin derived in the scan, clamped at 0, every mix
+    is sound."""
+    n_pub = 168                                              # published rows of the tile; the rest is padding, then the append
+    X = rng.standard_normal((256, d)).astype(f32) * rng.uniform(0.9, 1.1, (256, 1)).astype(f32)
+    X[n_pub:] *= f32(0.4)                                    # the appended rows: B = |x|^2 about 6 x lower
+    Q = np.concatenate([X[:8] + f32(1e-2) * rng.standard_normal((8, d)).astype(f32), rng.standard_normal((8, d)).astype(f32)])
+    xi, A, B, C, D = _row_params(X, "l2", d)
+    qi, sq, eq, g, u, v = _query_params(Q, "l2", d)
+    I = xi @ qi.T
+    t = (sq[None, :] * I.astype(f32)).astype(f32)
+    S = (A[:, None] * t + (B[:, None] * g[None, :] + (C[:, None] * eq[None, :] + D[:, None]).astype(f32)).astype(f32)).astype(f32)
+    pos = np.arange(256)
+    grp = ((pos >> 7) << 2) | ((pos >> 2) & 3)              # i8_group_of_pos: a straddling tile keeps the row order
+    pub = pos < n_pub
+    B_old = np.where(pub, B, f32(np.inf)).astype(f32)       # before the append: padding rows beyond the count (B = +inf)
+    B_new = B
+    bt = {"old": B_old.min(), "new": B_new.min()}
+    bg = {w: np.array([Bw[grp == gi].min() for gi in range(8)], dtype=f32) for w, Bw in (("old", B_old), ("new", B_new))}
+    assert bt["new"] < bt["old"] * f32(0.5), "the append must lower the tile's min B"
+    rel = {w: np.array([_group_b_margin(bg[w][gi], bt[w]) for gi in range(8)], dtype=f32) for w in bt}
+    Cmax, Dmax = np.abs(C[pub]).max(), np.abs(D[pub]).max()
+    Ag = np.array([np.abs(A[pub & (grp == gi)]).max() for gi in range(8)], dtype=f32)   # published rows' steps
+
+    def hidden(margin_of):
+        """(tile B, group value) mixes -> the published rows some mix hides under its alarm level"""
+        out = []
+        for wt in ("old", "new"):
+            for wg in ("old", "new"):
+                for qj in range(Q.shape[0]):
+                    qinv = f32(f32(1.0 - 1e-5) / sq[qj]) if sq[qj] > 0 else f32(np.inf)
+                    gq = f32(f32(max(g[qj], f32(0)) * qinv) * f32(1.0 - 1e-4))
+                    for gi in range(8):
+                        rows = np.nonzero(pub & (grp == gi))[0]
+                        for thr in np.sort(S[rows, qj])[:3]:           # thresholds a published row of the group meets
+                            kq = _alarm_k(bt[wt], Cmax, Dmax, g[qj], eq[qj], sq[qj], thr)
+                            with np.errstate(invalid="ignore"):
+                                kg = f32(margin_of(wt, wg, gi) * gq + kq)
+                            level = -2.1e9 if np.isnan(kg) else float(
+                                np.clip(np.float64(kg) / np.float64(Ag[gi]) * (1 - 2e-6), -2.1e9, 2.1e9))
+                            if not (I[rows, qj] >= int(level)).any():
+                                out.append((wt, wg, qj, gi))
+        return out
+    old_enc = hidden(lambda wt, wg, gi: rel[wg][gi])                        # margin stored relative to the writer's tile B
+    new_enc = hidden(lambda wt, wg, gi: _group_b_margin(bg[wg][gi], bt[wt]))   # absolute group B, margin in the scan
+    assert old_enc, "the relative encoding should hide published rows under the mix (old tile B, new margins)"
+    assert {(m[0], m[1]) for m in old_enc} == {("old", "new")}, old_enc[:5]
+    assert not new_enc, new_enc[:5]
