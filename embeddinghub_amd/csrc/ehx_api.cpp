@@ -151,13 +151,13 @@ static int create_one(Engine& E, const std::string& nm, uint32_t dims, int metri
   HIP_TRY(hipStreamCreateWithFlags(&s->wstream, hipStreamNonBlocking));
   HIP_TRY(hipEventCreateWithFlags(&s->wev, hipEventBlockingSync | hipEventDisableTiming));
   for (auto& e : s->sev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventBlockingSync | hipEventDisableTiming));
+  for (BatchClock* c : {&s->clock, &s->i8set[0].clock, &s->i8set[1].clock}) {
+    c->own = s->stream;
+    c->counter = &s->ev_counter;
+  }
   if (!parent) {
     HIP_TRY(hipMalloc((void**)&s->dMaxSumsq, sizeof(float)));
     HIP_TRY(hipMemset(s->dMaxSumsq, 0, sizeof(float)));
-    for (auto& e : s->ev) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipEventCreate(&s->ev_end));
-    for (auto& pr : s->ring)
-      for (auto& e : pr) HIP_TRY(hipEventCreate(&e));
     uint64_t cap0 = s->params.initial_capacity ? s->params.initial_capacity : 128;  // index.h:21
     if ((rc = grow(s.get(), cap0))) return rc;
   }
@@ -685,49 +685,15 @@ int ehx_stats(ehx_space* s, ehx_stats_t* out) {
     if (u[1]) return fail(EHX_EINTERNAL, "scan kernel tripped its bounded-retry guard %llu times", u[1]);
   }
   {
-    // scan times: the space's own ring (graph, fp16 / fp32 engines) and the rings of the int8 pipeline's two scratch sets
+    // scan times: the space's own clock (graph, fp16 / fp32 engines, exhaustive pass) and the int8 scratch sets' clocks;
+    // last_scan_ms / last_total_ms of the clock that timed a batch LAST, scan_ms_mean over all three rings
     double sum = 0;
-    uint64_t got = 0;
-    float ms = 0;
-    uint64_t newest = 0;  // last_scan_ms / last_total_ms: of the event set that was recorded LAST
-    if (s->ev_valid) {
-      HIP_TRY(hipEventSynchronize(s->ev[3]));
-      newest = s->ev_seq;
-      if (s->end_sampled) {   // graph search: the last TIMED batch (batch 0 and every EHX_STATS_EVERY-th)
-        if (s->g_timed_valid) {
-          HIP_TRY(hipEventSynchronize(s->ev_end));
-          if (s->scan_ev[0] && s->scan_ev[1] && hipEventElapsedTime(&ms, s->scan_ev[0], s->scan_ev[1]) == hipSuccess)
-            out->last_scan_ms = ms;
-          if (hipEventElapsedTime(&ms, s->ev[0], s->ev_end) == hipSuccess) out->last_total_ms = ms;
-        }
-      } else {
-        if (hipEventElapsedTime(&ms, s->ev[1], s->ev[2]) == hipSuccess) out->last_scan_ms = ms;
-        if (hipEventElapsedTime(&ms, s->ev[0], s->ev[3]) == hipSuccess) out->last_total_ms = ms;
-      }
-      const uint64_t m = s->ring_count < (uint64_t)ehx_space::kRing ? s->ring_count : (uint64_t)ehx_space::kRing;
-      for (uint64_t i = 0; i < m; ++i)
-        if (hipEventElapsedTime(&ms, s->ring[i][0], s->ring[i][1]) == hipSuccess) {
-          sum += ms;
-          ++got;
-        }
-    }
+    uint64_t got = 0, newest = 0;
+    int rc;
+    if ((rc = s->clock.read(&newest, &out->last_scan_ms, &out->last_total_ms, &sum, &got))) return rc;
     for (auto& c : s->i8set) {
       std::lock_guard<std::mutex> cl(c.mu);
-      if (!c.ev_valid) continue;
-      HIP_TRY(hipEventSynchronize(c.ev[3]));
-      if (c.timed_valid) HIP_TRY(hipEventSynchronize(c.ev[2]));   // (recorded right behind ev[3] on timed batches)
-      if (c.timed_valid && c.ev_seq > newest) {   // (the set's last TIMED batch: every EHX_STATS_EVERY-th)
-        newest = c.ev_seq;
-        if (c.last_scan[0] && c.last_scan[1] && hipEventElapsedTime(&ms, c.last_scan[0], c.last_scan[1]) == hipSuccess)
-          out->last_scan_ms = ms;
-        if (hipEventElapsedTime(&ms, c.ev[0], c.ev[2]) == hipSuccess) out->last_total_ms = ms;
-      }
-      const uint64_t m = c.ring_count < 64 ? c.ring_count : 64;
-      for (uint64_t i = 0; i < m; ++i)
-        if (hipEventElapsedTime(&ms, c.ring[i][0], c.ring[i][1]) == hipSuccess) {
-          sum += ms;
-          ++got;
-        }
+      if ((rc = c.clock.read(&newest, &out->last_scan_ms, &out->last_total_ms, &sum, &got))) return rc;
     }
     if (got == 0 && out->last_scan_ms > 0.0) {   // (only first batches so far: the int8 chain keeps them out of its ring)
       sum = out->last_scan_ms;
@@ -787,12 +753,10 @@ int ehx_stats_reset(ehx_space* s) {
   s->n_uncertified_final = 0;
   s->n_i8_queries = 0;
   s->n_i8_fallback = 0;
-  s->ring_count = 0;
-  s->g_batches = 0;   // (the next graph batch is a timed one)
+  s->clock.reset();
   for (auto& c : s->i8set) {
     std::lock_guard<std::mutex> cl(c.mu);
-    c.ring_count = 0;
-    c.batches = 0;   // (the next batch of the set is a timed one)
+    c.clock.reset();
   }
   if (s->dUncert) HIP_TRY(hipMemset(s->dUncert, 0, 2 * sizeof(unsigned long long)));
   if (s->dGraphCounters) HIP_TRY(hipMemset(s->dGraphCounters, 0, kGraphCounters * sizeof(unsigned long long)));

@@ -125,7 +125,8 @@ int flat_pass(ehx_space* s, uint64_t n_pub, hipStream_t st, size_t nq, const flo
     int rcw = wait_searches_in_flight(s, st);
     if (rcw) return rcw;
   }
-  HIP_TRY(hipEventRecord(s->ev[0], st));
+  BatchClock& clock = s->clock;   // (every batch timed and in the ring; an empty space's outside it)
+  if ((rc = clock.begin(st, n_pub ? 1u : BatchClock::kOutOfRing))) return rc;
   HIP_TRY(launch_prep_queries(d_queries, (uint32_t)nq, s->dims, s->ld, p.q_rows, s->metric, s->dQ.p, st));
   if (f16)
     HIP_TRY(launch_prep_queries16(d_queries, (uint32_t)nq, s->dims, s->ld16, p.q_rows, s->metric, s->dQ16.p,
@@ -133,8 +134,7 @@ int flat_pass(ehx_space* s, uint64_t n_pub, hipStream_t st, size_t nq, const flo
   if (n_pub == 0) {
     // empty space: every query returns count 0
     HIP_TRY(hipMemsetAsync(s->dMerged.p, 0xFF, (size_t)p.q_rows * 64 * sizeof(uint64_t), st));
-    HIP_TRY(hipEventRecord(s->ev[1], st));
-    HIP_TRY(hipEventRecord(s->ev[2], st));
+    if ((rc = clock.scan_begin(st)) || (rc = clock.scan_end(st))) return rc;
   } else {
     ScanArgs a;
     a.Q = s->dQ.p;
@@ -185,9 +185,7 @@ int flat_pass(ehx_space* s, uint64_t n_pub, hipStream_t st, size_t nq, const flo
       return launch_flat_scan(a, st);
     };
     HIP_TRY(hipMemsetAsync(s->dGthr.p, 0xFF, (size_t)p.q_rows * sizeof(uint64_t), st));
-    hipEvent_t* pr = s->ring[s->ring_count % ehx_space::kRing];
-    HIP_TRY(hipEventRecord(s->ev[1], st));
-    HIP_TRY(hipEventRecord(pr[0], st));
+    if ((rc = clock.scan_begin(st))) return rc;
     if (sample) {
       ScanPlan sp = plan_scan((uint32_t)nq, kSampleTiles, k, E.n_cus);
       sp.kprime = p.kprime;
@@ -200,11 +198,7 @@ int flat_pass(ehx_space* s, uint64_t n_pub, hipStream_t st, size_t nq, const flo
     for (size_t i = 0; i < passes.size(); ++i) {
       const bool last = i + 1 == passes.size();
       HIP_TRY(scan(passes[i].plan, passes[i].tile0, 0));
-      if (last) {  // (the final merge is outside the timed scan phase)
-        HIP_TRY(hipEventRecord(pr[1], st));
-        HIP_TRY(hipEventRecord(s->ev[2], st));
-        s->ring_count++;
-      }
+      if (last && (rc = clock.scan_end(st))) return rc;   // (the final merge is outside the timed scan phase)
       HIP_TRY(launch_flat_merge(s->dPart.p, (uint32_t)nq, passes[i].plan.n_chunks * lpc, p.kprime, s->dMerged.p, st,
                                 lists_total, i > 0, last ? nullptr : (unsigned long long*)s->dGthr.p));
     }
@@ -230,18 +224,8 @@ int flat_pass(ehx_space* s, uint64_t n_pub, hipStream_t st, size_t nq, const flo
   r.max_sumsq = s->dMaxSumsq;
   r.uncert_flags = s->dUflags.p;
   HIP_TRY(launch_rerank(r, st));
-  HIP_TRY(hipEventRecord(s->ev[3], st));
-  s->ev3_stream = st;
-  s->end_sampled = false;
-  s->ev_valid = true;
-  s->ev_seq = ++s->ev_counter;
-  if (count_stats) {
-    s->n_queries += nq;
-    s->n_dist += (uint64_t)nq * n_pub;
-    // SURVEY §8d brute force bytes per batch: N*d*s + B*d*4 + B*k*12 (s = bytes per element the scan reads)
-    s->bytes_algo += n_pub * s->dims * (uint64_t)(f16 ? 2 : s->esz) + (uint64_t)nq * s->dims * 4ull +
-                     (uint64_t)nq * k * 12ull;
-  }
+  if ((rc = clock.finish(st))) return rc;
+  if (count_stats) count_scan_batch(s, nq, n_pub, k, f16 ? 2 : s->esz);
   s->n_rerank += (uint64_t)nq * p.kprime;
   return EHX_OK;
 }
@@ -386,19 +370,10 @@ int flat_pass8(ehx_space* s, uint64_t n_pub, int set, hipStream_t st, size_t nq,
   uint32_t* pool_cnt = sc.dI8Ctl.p;
   uint32_t* ovf = sc.dI8Ctl.p + p.q_rows;
   uint32_t* sync = sc.dI8Ctl.p + 2 * (size_t)p.q_rows;
-  if (!sc.ev[0]) {
-    for (auto& e : sc.ev) HIP_TRY(hipEventCreate(&e));
-    for (auto& pr2 : sc.ring)
-      for (auto& e : pr2) HIP_TRY(hipEventCreate(&e));
-    for (auto& e : sc.first_pair) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipEventCreateWithFlags(&sc.verdict, hipEventBlockingSync | hipEventDisableTiming));
-  }
+  if (!sc.verdict) HIP_TRY(hipEventCreateWithFlags(&sc.verdict, hipEventBlockingSync | hipEventDisableTiming));
   // (a caller's stream other than the space's own: searches already in flight there and here finish first)
   if ((rc = wait_searches_in_flight(s, st))) return rc;
-  const uint64_t batch_no = sc.batches++;
-  const bool in_ring = (batch_no % env().stats_every) == env().stats_every - 1u;
-  const bool timed = in_ring || batch_no == 0;   // (the first batch after a reset is a timed one, outside the ring's mean)
-  if (timed) HIP_TRY(hipEventRecord(sc.ev[0], st));
+  if ((rc = sc.clock.begin(st, env().stats_every))) return rc;
   HIP_TRY(launch_prep_queries_i8(d_queries, (uint32_t)nq, s->dims, s->ld, s->ld8, p.q_rows, s->metric, sc.dQ.p,
                                  sc.dQ8.p, sc.dQp8.p, sc.dQuv.p, sc.dThr8.p, sc.dI8Ctl.p, st));
   ScanArgsI8 a;
@@ -430,14 +405,7 @@ int flat_pass8(ehx_space* s, uint64_t n_pub, int set, hipStream_t st, size_t nq,
     a.xcd_map = pl.xcd_map;
     return launch_flat_scan_i8(a, st);
   };
-  hipEvent_t* pr = in_ring ? sc.ring[sc.ring_count % 64] : sc.first_pair;
-  // (one record per mark: sc.ev[1] / ev[2] — "scan start / end of the LAST batch" for ehx_stats — are the ring's own events
-  // of this batch; a second marker packet at the same place cost ~5 us of queue time each, twice per batch)
-  if (timed) {
-    HIP_TRY(hipEventRecord(pr[0], st));
-    sc.last_scan[0] = sc.last_scan[1] = nullptr;   // (a pass that fails half way leaves no half pair for ehx_stats)
-    sc.timed_valid = false;
-  }
+  if ((rc = sc.clock.scan_begin(st))) return rc;
   {  // sample pass: lower bounds of the first 2048 rows -> thr[q] = the k'-th best of them
     ScanPlan sp = plan_scan((uint32_t)nq, kSampleTiles, k, E.n_cus);
     a.dump = sc.dSample8.p;
@@ -457,12 +425,8 @@ int flat_pass8(ehx_space* s, uint64_t n_pub, int set, hipStream_t st, size_t nq,
       if (i > 0) HIP_TRY(hipMemsetAsync(sync, 0, kSyncWordsI8 * sizeof(uint32_t), st));
     }
     HIP_TRY(scan(passes[i].plan, passes[i].tile0));
-    if (last && timed) {  // (the last select and the re-rank are outside the timed scan phase, like flat_pass's final merge)
-      HIP_TRY(hipEventRecord(pr[1], st));
-      sc.last_scan[0] = pr[0];   // both marks of THIS batch, set together
-      sc.last_scan[1] = pr[1];
-      if (in_ring) sc.ring_count++;
-    }
+    // (the last select and the re-rank are outside the timed scan phase, like flat_pass's final merge)
+    if (last && (rc = sc.clock.scan_end(st))) return rc;
     HIP_TRY(launch_select256(sc.dPool.p, pool_cnt, kPoolCap, (uint32_t)nq, rank_after(i), sc.dMerged8.p, width, i > 0,
                              sc.dThr8.p, sc.dQp8.p, st));
   }
@@ -518,20 +482,8 @@ int flat_pass8(ehx_space* s, uint64_t n_pub, int set, hipStream_t st, size_t nq,
               qp[q].w, S(0), S(63), S(127), S(255), od[q * k + k - 1], uv[q].x, uv[q].y);
     }
   }
-  HIP_TRY(hipEventRecord(sc.ev[3], st));
-  sc.ev3_stream = st;
-  sc.ev_valid = true;
-  if (timed) {
-    HIP_TRY(hipEventRecord(sc.ev[2], st));
-    sc.timed_valid = true;
-    sc.ev_seq = ++s->ev_counter;
-  }
-  if (count_stats) {
-    s->n_queries += nq;
-    s->n_dist += (uint64_t)nq * n_pub;
-    // SURVEY §8d brute force bytes per batch: N*d*s + B*d*4 + B*k*12 (s = 1: the int8 scan copy)
-    s->bytes_algo += n_pub * (uint64_t)s->dims + (uint64_t)nq * s->dims * 4ull + (uint64_t)nq * k * 12ull;
-  }
+  if ((rc = sc.clock.finish(st))) return rc;
+  if (count_stats) count_scan_batch(s, nq, n_pub, k, 1);   // (the int8 scan copy)
   s->n_rerank += (uint64_t)nq * kprime;
   return EHX_OK;
 }
@@ -562,9 +514,9 @@ int exhaustive_pass(ehx_space* s, uint64_t n_pub, hipStream_t st, size_t nq, con
     int rcw = wait_searches_in_flight(s, st);
     if (rcw) return rcw;
   }
-  HIP_TRY(hipEventRecord(s->ev[0], st));
+  if ((rc = s->clock.begin(st, BatchClock::kOutOfRing))) return rc;
   HIP_TRY(launch_prep_queries(d_queries, (uint32_t)nq, s->dims, s->ld, (uint32_t)nq, s->metric, s->dQ.p, st));
-  HIP_TRY(hipEventRecord(s->ev[1], st));
+  if ((rc = s->clock.scan_begin(st))) return rc;
   for (uint32_t pg = 0; pg < pages; ++pg) {
     if (pg) test_pause();
     const uint64_t* floor = pg ? s->dGthr.p : nullptr;
@@ -594,13 +546,8 @@ int exhaustive_pass(ehx_space* s, uint64_t n_pub, hipStream_t st, size_t nq, con
     r.out_stride = k;
     r.out_offset = pg * 64;
     HIP_TRY(launch_rerank(r, st));
-    if (pg + 1 == pages) HIP_TRY(hipEventRecord(s->ev[2], st));
   }
-  HIP_TRY(hipEventRecord(s->ev[3], st));
-  s->ev3_stream = st;
-  s->end_sampled = false;
-  s->ev_valid = true;
-  s->ev_seq = ++s->ev_counter;
+  if ((rc = s->clock.scan_end(st)) || (rc = s->clock.finish(st))) return rc;
   s->n_dist += (uint64_t)nq * n_pub * pages;
   return EHX_OK;
 }
@@ -636,6 +583,28 @@ void i8_adapt(ehx_space* s, size_t nq, size_t n_failed, size_t n_short, uint32_t
   if (env().i8_trace)
     fprintf(stderr, "[ehx i8] %zu of %zu queries uncertified (%zu by a short list): candidate list now %u of %u\n", n_failed,
             nq, n_short, std::max(s->i8_kprime_min.load(), kprime), s->i8_width.load());
+}
+
+void count_scan_batch(ehx_space* s, size_t nq, uint64_t n_pub, uint32_t k, uint64_t elem_bytes) {
+  s->n_queries += nq;
+  s->n_dist += (uint64_t)nq * n_pub;
+  // SURVEY §8d brute force bytes per batch: N*d*s + B*d*4 + B*k*12 (s = bytes per element the scan reads)
+  s->bytes_algo += n_pub * s->dims * elem_bytes + (uint64_t)nq * s->dims * 4ull + (uint64_t)nq * k * 12ull;
+}
+
+int collect_uncertified(hipStream_t st, const uint32_t* d_flags, size_t m, const std::vector<uint32_t>* subset,
+                        std::vector<uint32_t>* out, size_t* n_short) {
+  std::vector<uint32_t> flags(m);
+  HIP_TRY(hipMemcpyAsync(flags.data(), d_flags, m * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  out->clear();
+  *n_short = 0;
+  for (size_t j = 0; j < m; ++j)
+    if (flags[j]) {
+      out->push_back(subset ? (*subset)[j] : (uint32_t)j);
+      *n_short += flags[j] == 2u;
+    }
+  return EHX_OK;
 }
 
 // Device pipeline of a flat space: up to three stages, each run only for the queries the previous one
@@ -733,9 +702,7 @@ int knn_device_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_qu
     const uint32_t* d_flags = kind == kI8 ? s->i8set[0].dUflags.p : s->dUflags.p;
     if (subset) {
       HIP_TRY(launch_scatter_results(oi, od, oc, s->dFbIdx.p, (uint32_t)m, k, d_ids, d_dist, d_count, st));
-      HIP_TRY(hipEventRecord(s->ev[3], st));
-      s->ev3_stream = st;
-  s->end_sampled = false;
+      if ((rc = s->clock.extend(st))) return rc;   // (the scatter is part of the pass's batch: writers wait for it too)
     }
     // verdict
     unc->clear();
@@ -749,16 +716,7 @@ int knn_device_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_qu
 #endif
     if (n_unc == 0) return EHX_OK;
     HIP_TRY(hipMemsetAsync(d_unc, 0, sizeof(unsigned long long), st));
-    std::vector<uint32_t> flags(m);
-    HIP_TRY(hipMemcpyAsync(flags.data(), d_flags, m * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    n_short = 0;
-    for (size_t j = 0; j < m; ++j)
-      if (flags[j]) {
-        unc->push_back(subset ? (*subset)[j] : (uint32_t)j);
-        n_short += flags[j] == 2u;
-      }
-    return EHX_OK;
+    return collect_uncertified(st, d_flags, m, subset, unc, &n_short);
   };
 
   std::vector<uint32_t> todo, next;

@@ -99,6 +99,49 @@ struct DevBuf {
   }
 };
 
+// The per-batch events of one search pipeline: the timing events behind ehx_stats (last_scan_ms / last_total_ms of the
+// last timed batch, the ring of scan windows behind scan_ms_mean) and the fence — "every launch of the last batch has run"
+// — that writers and searches on other streams wait for (wait_searches_in_flight).  A space has three: ehx_space::clock
+// (fp32 / fp16 scans, exhaustive pass, graph search — a space is flat or graph, never both) and one per int8 scratch set.
+// Sampling, begin(st, every): batch b since the last reset is timed when b == 0 or b % every == every - 1, and only the
+// latter go into the ring (every = 1: every batch, batch 0 included; with every > 1 the first batch behind a reset, which
+// starts on an idle queue and ran 5-10 % long in the bench's 10-step runs, stays out of the mean); every = kOutOfRing:
+// timed, never in the ring, not counted.  An event record between two kernels idles the queue ~6 us (round 6), so a timed
+// batch records four events — start, scan begin, scan end, end (which is also its fence) — and an untimed one its fence.
+// The owner's lock (scratch_mu / the set's mu) serialises a clock's batches and ehx_stats; fence_mu guards the fence, which
+// every other thread reads.
+struct BatchClock {
+  static constexpr int kRing = 64;
+  static constexpr uint32_t kOutOfRing = 0;
+  hipStream_t own = nullptr;                 // the space's search stream (create_one)
+  std::atomic<uint64_t>* counter = nullptr;  // ehx_space::ev_counter: which of a space's clocks timed a batch last
+
+  int begin(hipStream_t st, uint32_t every);
+  int scan_begin(hipStream_t st);  // the timed scan window of the batch
+  int scan_end(hipStream_t st);
+  int finish(hipStream_t st);      // every launch of the batch is enqueued: its fence (and end)
+  int extend(hipStream_t st);      // work enqueued behind the last batch belongs to it: re-records the event that closed it
+  int order(hipStream_t st);       // work enqueued on `st` from here on starts after the last batch
+  void reset() { batches = ring_count = 0; }   // (the next batch is a timed one)
+  // ehx_stats: waits for the last batch; the last timed batch's times if it is newer than *newest; the ring's windows
+  int read(uint64_t* newest, double* last_scan_ms, double* last_total_ms, double* sum, uint64_t* got);
+  void release();
+
+ private:
+  hipEvent_t start = nullptr, end = nullptr, fence_ev = nullptr;
+  hipEvent_t ring[kRing][2] = {};
+  hipEvent_t spare[2] = {};      // scan window of a timed batch outside the ring
+  hipEvent_t* last = nullptr;    // scan window of the last timed batch: a ring pair or the spare
+  hipEvent_t* pair = nullptr;    // ... of this batch
+  uint64_t batches = 0, ring_count = 0;
+  uint64_t seq = 0;              // *counter when the last timed batch finished
+  bool timed = false, in_ring = false;  // this batch
+  bool timed_valid = false;      // start / last / end hold the last timed batch, complete
+  std::mutex fence_mu;
+  hipEvent_t fence = nullptr;    // the event that closed the last batch (end or fence_ev); null before the first
+  bool fence_own = false;        // ... recorded on `own`
+};
+
 }  // namespace ehx_impl
 using namespace ehx_impl;
 
@@ -340,7 +383,7 @@ struct ehx_space {
   DevBuf<uint64_t> dFbIds;
   unsigned long long* dUncert16 = nullptr;  // queries the filter pass could not certify
   // int8 filter scratch: everything ONE in-flight batch of the int8 pipeline owns — prepared queries, query tiles +
-  // parameters, per-pass thresholds, sample scores, pools, running best list, verdict, timing events.  TWO sets: a host
+  // parameters, per-pass thresholds, sample scores, pools, running best list, verdict, batch clock.  TWO sets: a host
   // caller's batch can be enqueued behind another caller's on the space's stream while that one still waits for its
   // verdict (knn_host_direct), so the scan kernels of consecutive batches run back to back with no host in between.
   struct I8Set {
@@ -355,26 +398,12 @@ struct ehx_space {
     DevBuf<uint64_t> dCnt;    // [8] epilogue counters of diagnosis builds (EHX_I8_COUNT); the set's own: nothing shared
     unsigned long long* dUncert = nullptr;
     unsigned long long* hUncertPin = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // start of the last TIMED batch | (unused) | its end | all enqueued
-                                                              // work done (every batch: what writers and other streams wait for)
-    // Timing events are recorded on every EHX_STATS_EVERY-th batch of the set only (round 6: an event record between two
-    // kernels idles the queue ~6 us — start, scan start, scan end and end were 24 us of a 0.9-ms batch): batches N - 1, 2 N - 1
-    // ... go into the ring behind scan_ms_mean; batch 0 is timed too (a caller that runs one batch and asks) but stays out of
-    // the ring — the first batch behind a reset starts on an idle queue and ran 5-10 % long in the bench's 10-step runs
-    hipStream_t ev3_stream = nullptr;   // the stream ev[3] was last recorded on (work queued there later is behind it anyway)
-    uint64_t batches = 0;        // batches run in this set since the last ehx_stats_reset
-    bool timed_valid = false;    // ev[0] / ev[2] / last_scan[] hold a recorded batch
-    hipEvent_t last_scan[2] = {nullptr, nullptr};            // scan start / end of the last batch: two of ring[][]'s events
-    hipEvent_t verdict = nullptr;                            // blocking-sync: the verdict has landed in hUncertPin
-    std::atomic<bool> ev_valid{false};
-    uint64_t ev_seq = 0;     // value of ehx_space::ev_counter when ev[] was last recorded (ehx_stats: which set is newest)
-    hipEvent_t ring[64][2] = {};
-    uint64_t ring_count = 0;
-    hipEvent_t first_pair[2] = {nullptr, nullptr};   // scan start / end of the set's FIRST batch after a reset (not in the ring)
+    hipEvent_t verdict = nullptr;  // blocking-sync: the verdict has landed in hUncertPin
+    BatchClock clock;              // timed: batch 0 and every EHX_STATS_EVERY-th batch of the set
     std::mutex mu;
   };
   I8Set i8set[2];
-  std::atomic<uint64_t> ev_counter{0};
+  std::atomic<uint64_t> ev_counter{0};   // orders the timed batches of the space's three clocks (BatchClock::counter)
   std::atomic<uint32_t> i8_next_set{0};
   std::mutex i8_enqueue_mu;  // held while ONE host batch's int8 stage is enqueued on the space's stream (not while its
                              // verdict is awaited): two callers in different scratch sets must not interleave their
@@ -384,22 +413,10 @@ struct ehx_space {
   std::atomic<uint64_t> n_i8_queries{0}, n_i8_fallback{0};
   float* hStage = nullptr;  // pinned staging (Set / Get / query upload)
   size_t hStageBytes = 0;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  hipStream_t ev3_stream = nullptr;   // the stream ev[3] was last recorded on
-  // graph search (round 6): timing events on batch 0 and on every EHX_STATS_EVERY-th batch only — six event records per batch
-  // idled the queue ~36 us of a 0.35-ms batch.  scan_ev: the timed batch's scan window (a ring pair, or ev[1] / ev[2] for
-  // batch 0, which stays out of the ring); ev_end: recorded behind ev[3] on timed batches; end_sampled: the last batch was
-  // a graph search (the other engines record ev[0..3] on every batch and clear it)
-  hipEvent_t scan_ev[2] = {nullptr, nullptr};
-  hipEvent_t ev_end = nullptr;
-  bool end_sampled = false, g_timed_valid = false;
-  uint64_t g_batches = 0;
-  std::atomic<bool> ev_valid{false};
-  uint64_t ev_seq = 0;
-  // ring of (start, stop) event pairs around the scan kernel: per-launch durations for the roofline
-  static constexpr int kRing = 64;
-  hipEvent_t ring[kRing][2] = {};
-  uint64_t ring_count = 0;
+  // the batch clock of the passes under scratch_mu: fp32 / fp16 scans time every batch, the exhaustive pass every batch
+  // outside the ring, the graph search batch 0 and every EHX_STATS_EVERY-th batch (round 6: six event records per batch
+  // idled the queue ~36 us of a 0.35-ms batch)
+  BatchClock clock;
 
   // micro-batcher: concurrent small ehx_knn calls are coalesced into one device batch
   struct KnnReq {
@@ -473,22 +490,9 @@ struct ehx_space {
       fr(c.dUncert);
       if (c.hUncertPin) (void)hipHostFree(c.hUncertPin);
       c.hUncertPin = nullptr;
-      for (auto& e : c.ev) {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-      }
       if (c.verdict) (void)hipEventDestroy(c.verdict);
       c.verdict = nullptr;
-      c.ev_valid = false;
-      for (auto& pr : c.ring)
-        for (auto& e : pr) {
-          if (e) (void)hipEventDestroy(e);
-          e = nullptr;
-        }
-      for (auto& e : c.first_pair) {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-      }
+      c.clock.release();
     }
     dGPack.release();
     dOutPack.release();
@@ -557,22 +561,11 @@ struct ehx_space {
     if (hStage) (void)hipHostFree(hStage);
     hStage = nullptr;
     hStageBytes = 0;
-    for (auto& e : ev) {
-      if (e) (void)hipEventDestroy(e);
-      e = nullptr;
-    }
-    ev_valid = false;
-    for (auto& pr : ring)
-      for (auto& e : pr) {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-      }
+    clock.release();
     if (stream) (void)hipStreamDestroy(stream);
     stream = nullptr;
     if (wstream) (void)hipStreamDestroy(wstream);
     wstream = nullptr;
-    if (ev_end) (void)hipEventDestroy(ev_end);
-    ev_end = nullptr;
     if (wev) (void)hipEventDestroy(wev);
     wev = nullptr;
     for (auto& e : sev) {
@@ -596,7 +589,7 @@ inline bool valid_space(ehx_space* s) { return s != nullptr; }
 inline bool is_parent(const ehx_space* s) { return !s->shards.empty(); }
 
 // work enqueued on stream `st` from here on starts after every search of this space that is already in flight (whatever
-// stream it was given, whichever scratch set it runs in)
+// stream it was given, whichever scratch set it runs in): BatchClock::order of the space's three clocks
 int wait_searches_in_flight(ehx_space* s, hipStream_t st);
 int key_for_id(ehx_space* s, uint64_t id, std::string* out);
 int lookup_key(ehx_space* s, const char* key, size_t klen, uint64_t* id);
@@ -628,6 +621,12 @@ int flat_pass8(ehx_space* s, uint64_t n_pub, int set, hipStream_t st, size_t nq,
 int exhaustive_pass(ehx_space* s, uint64_t n_pub, hipStream_t st, size_t nq, const float* d_queries, uint32_t k,
                     uint64_t* d_ids, float* d_dist, uint32_t* d_count);
 void i8_adapt(ehx_space* s, size_t nq, size_t n_failed, size_t n_short, uint32_t kprime);
+// work counters of one scan batch of nq queries over n_pub rows; elem_bytes: bytes per element the scan reads
+void count_scan_batch(ehx_space* s, size_t nq, uint64_t n_pub, uint32_t k, uint64_t elem_bytes);
+// the uncertified queries of a batch of m (flags d_flags[0, m) on the device; subset: their global indices) -> *out, and
+// how many of them were flagged 2 (a candidate list too short) -> *n_short
+int collect_uncertified(hipStream_t st, const uint32_t* d_flags, size_t m, const std::vector<uint32_t>* subset,
+                        std::vector<uint32_t>* out, size_t* n_short);
 int knn_device_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k,
                       uint64_t* d_ids, float* d_dist, uint32_t* d_count, const std::vector<uint32_t>* i8_failed = nullptr,
                       size_t i8_short = 0, uint32_t i8_kprime_in = 0, uint64_t n_pub = kNoSnapshot);

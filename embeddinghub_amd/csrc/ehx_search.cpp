@@ -260,23 +260,14 @@ static int knn_host_direct(ehx_space* s, size_t n_queries, const float* queries,
     HIP_TRY(hipMemcpyAsync(hs->pin + qbytes, hs->dout.p, out_bytes, hipMemcpyDeviceToHost, hs->st));
     copied_early = true;
     HIP_TRY(hipEventSynchronize(sc.verdict));
-    s->n_queries += n_queries;
-    s->n_dist += (uint64_t)n_queries * n_pub;
-    s->bytes_algo += n_pub * (uint64_t)s->dims + (uint64_t)n_queries * s->dims * 4ull + (uint64_t)n_queries * k * 12ull;
+    count_scan_batch(s, n_queries, n_pub, k, 1);
     if (*sc.hUncertPin == 0) {
       done = true;
       s->n_i8_queries += n_queries;
       i8_adapt(s, n_queries, 0, 0, kprime_used);   // a clean batch: the score decays
     } else {  // which queries, and why: the engine chain continues with them (below, under the pipeline lock)
       HIP_TRY(hipMemsetAsync(sc.dUncert, 0, sizeof(unsigned long long), s->stream));
-      std::vector<uint32_t> flags(n_queries);
-      HIP_TRY(hipMemcpyAsync(flags.data(), sc.dUflags.p, n_queries * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
-      HIP_TRY(hipStreamSynchronize(s->stream));
-      for (size_t j = 0; j < n_queries; ++j)
-        if (flags[j]) {
-          failed.push_back((uint32_t)j);
-          n_short += flags[j] == 2u;
-        }
+      if ((rc = collect_uncertified(s->stream, sc.dUflags.p, n_queries, nullptr, &failed, &n_short))) return rc;
       have_failed = true;
     }
   }

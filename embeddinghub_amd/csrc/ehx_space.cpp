@@ -172,14 +172,114 @@ int ensure_rows(ehx_space* s, uint64_t rows) {
 }
 
 
-// work enqueued on stream `st` from here on starts after every search of this space that is already in flight (whatever
-// stream it was given, whichever scratch set it runs in)
+int BatchClock::begin(hipStream_t st, uint32_t every) {
+  if (!start) {  // (created on first use, on the space's device; `start` last: it marks the set complete)
+    for (hipEvent_t* e : {&end, &fence_ev, &spare[0], &spare[1]})
+      if (!*e) HIP_TRY(hipEventCreate(e));
+    for (auto& pr : ring)
+      for (auto& e : pr)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(hipEventCreate(&start));
+  }
+  const uint64_t b = every == kOutOfRing ? 0 : batches++;
+  in_ring = every != kOutOfRing && b % every == every - 1;
+  timed = in_ring || b == 0;
+  pair = in_ring ? ring[ring_count % kRing] : spare;
+  if (timed) {
+    timed_valid = false;   // (a pass that fails half way leaves no half-recorded batch for ehx_stats)
+    last = nullptr;
+    HIP_TRY(hipEventRecord(start, st));
+  }
+  return EHX_OK;
+}
+
+int BatchClock::scan_begin(hipStream_t st) {
+  if (timed) HIP_TRY(hipEventRecord(pair[0], st));
+  return EHX_OK;
+}
+
+int BatchClock::scan_end(hipStream_t st) {
+  if (!timed) return EHX_OK;
+  HIP_TRY(hipEventRecord(pair[1], st));
+  last = pair;
+  if (in_ring) ring_count++;
+  return EHX_OK;
+}
+
+int BatchClock::finish(hipStream_t st) {
+  {
+    std::lock_guard<std::mutex> l(fence_mu);
+    HIP_TRY(hipEventRecord(timed ? end : fence_ev, st));
+    fence = timed ? end : fence_ev;
+    fence_own = st == own;
+  }
+  if (timed) {
+    timed_valid = last != nullptr;
+    seq = ++*counter;
+  }
+  return EHX_OK;
+}
+
+int BatchClock::extend(hipStream_t st) {
+  std::lock_guard<std::mutex> l(fence_mu);
+  if (!fence) return EHX_OK;
+  HIP_TRY(hipEventRecord(fence, st));
+  fence_own = st == own;
+  return EHX_OK;
+}
+
+int BatchClock::order(hipStream_t st) {
+  // Only the space's own stream skips the wait for a fence recorded on it — the host pipeline's case: the stream's order
+  // already holds it, and the wait packets (three per batch) were ~10 us of queue time (round 6).  A caller's stream always
+  // waits: a stream destroyed and created again may come back with the handle of the one the fence was recorded on.
+  std::lock_guard<std::mutex> l(fence_mu);
+  if (fence && !(fence_own && st == own)) HIP_TRY(hipStreamWaitEvent(st, fence, 0));
+  return EHX_OK;
+}
+
+int BatchClock::read(uint64_t* newest, double* last_scan_ms, double* last_total_ms, double* sum, uint64_t* got) {
+  hipEvent_t f;   // (the caller holds the owner's lock: only the wait for it happens outside fence_mu)
+  {
+    std::lock_guard<std::mutex> l(fence_mu);
+    f = fence;
+  }
+  if (!f) return EHX_OK;
+  HIP_TRY(hipEventSynchronize(f));
+  float ms = 0;
+  if (timed_valid && seq > *newest) {
+    HIP_TRY(hipEventSynchronize(end));
+    *newest = seq;
+    if (hipEventElapsedTime(&ms, last[0], last[1]) == hipSuccess) *last_scan_ms = ms;
+    if (hipEventElapsedTime(&ms, start, end) == hipSuccess) *last_total_ms = ms;
+  }
+  for (uint64_t i = 0; i < std::min<uint64_t>(ring_count, kRing); ++i)
+    if (hipEventElapsedTime(&ms, ring[i][0], ring[i][1]) == hipSuccess) {
+      *sum += ms;
+      ++*got;
+    }
+  return EHX_OK;
+}
+
+void BatchClock::release() {
+  std::lock_guard<std::mutex> l(fence_mu);
+  auto destroy = [](hipEvent_t& e) {
+    if (e) (void)hipEventDestroy(e);
+    e = nullptr;
+  };
+  for (hipEvent_t* e : {&start, &end, &fence_ev, &spare[0], &spare[1]}) destroy(*e);
+  for (auto& pr : ring)
+    for (auto& e : pr) destroy(e);
+  fence = nullptr;
+  last = pair = nullptr;
+  timed_valid = false;
+  batches = ring_count = 0;
+}
+
 int wait_searches_in_flight(ehx_space* s, hipStream_t st) {
-  // (an event recorded on `st` itself orders nothing that the stream's own order does not: no wait packet — three of them per
-  // batch of the host pipeline, every batch on the space's stream, were ~10 us of queue time; round 6)
-  if (s->ev_valid && s->ev3_stream != st) HIP_TRY(hipStreamWaitEvent(st, s->ev[3], 0));
+  int rc;
+  if ((rc = s->clock.order(st))) return rc;
   for (auto& o : s->i8set)
-    if (o.ev_valid && o.ev3_stream != st) HIP_TRY(hipStreamWaitEvent(st, o.ev[3], 0));
+    if ((rc = o.clock.order(st))) return rc;
   return EHX_OK;
 }
 
