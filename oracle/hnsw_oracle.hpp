@@ -464,6 +464,112 @@ class HnswOracle {
 
   labeltype label_of(tableint id) const { return labels_[id]; }
 
+  // -----------------------------------------------------------------------------------------------
+  // Graph import: the state that addPoint would have left after building exactly this graph over `rows` (already
+  // prepared for the metric), label = row index.  The CSR is the engine's ehx_graph_import shape (include/ehx.h):
+  // level0 [n][1 + maxM0] (count, ids; padding ignored), levels [n], and one upper list per (node, level >= 1) in
+  // (upper_node, upper_level, upper_ids[upper_off[i], upper_off[i + 1])).  Only an EMPTY index imports.  Everything is
+  // validated before anything is written; a bad graph throws with the first violation and leaves the index empty.
+  // The level generator is advanced by n draws, as n addPoint calls would have advanced it.
+  // -----------------------------------------------------------------------------------------------
+  void importGraph(const float* rows, size_t n, const uint32_t* level0, const int32_t* levels, size_t n_upper,
+                   const uint32_t* upper_node, const int32_t* upper_level, const uint64_t* upper_off,
+                   size_t n_upper_ids, const uint32_t* upper_ids, uint32_t entry_point, int32_t max_level) {
+    if (cur_element_count_ != 0) throw std::runtime_error("import: the index is not empty");
+    if (n == 0) {
+      if (n_upper != 0) throw std::runtime_error("import: upper lists without rows");
+      return;
+    }
+    if (n >= (size_t)0xFFFFFFFFu) throw std::runtime_error("import: too many rows");
+    auto bad = [](const std::string& what) { throw std::runtime_error("import: " + what); };
+    auto at = [](size_t node, long level) {
+      return " (node " + std::to_string(node) + ", level " + std::to_string(level) + ")";
+    };
+    int32_t top = -1;
+    for (size_t i = 0; i < n; ++i) {
+      if (levels[i] < 0) bad("negative level" + at(i, levels[i]));
+      top = std::max(top, levels[i]);
+    }
+    if (max_level != top)
+      bad("max_level " + std::to_string(max_level) + " is not the highest level " + std::to_string(top));
+    if (entry_point >= n) bad("entry point " + std::to_string(entry_point) + " >= n");
+    if (levels[entry_point] != max_level)
+      bad("entry point " + std::to_string(entry_point) + " has level " + std::to_string(levels[entry_point]) +
+          ", not max_level " + std::to_string(max_level));
+    // one list: ids < n, not the node itself, distinct, each of them present at this level
+    std::vector<uint32_t> stamp(n, 0);
+    uint32_t list_no = 0;
+    auto check_list = [&](size_t node, long level, const uint32_t* ids, size_t c, size_t cmax) {
+      if (c > cmax) bad("list of " + std::to_string(c) + " > " + std::to_string(cmax) + " ids" + at(node, level));
+      ++list_no;
+      if (list_no == 0) {  // (wrapped: start the stamps over)
+        std::fill(stamp.begin(), stamp.end(), 0);
+        list_no = 1;
+      }
+      for (size_t j = 0; j < c; ++j) {
+        const uint32_t v = ids[j];
+        if (v >= n) bad("id " + std::to_string(v) + " >= n" + at(node, level));
+        if (v == node) bad("self-link" + at(node, level));
+        if (stamp[v] == list_no) bad("id " + std::to_string(v) + " twice in one list" + at(node, level));
+        stamp[v] = list_no;
+        if (levels[v] < level)
+          bad("neighbour " + std::to_string(v) + " of level " + std::to_string(levels[v]) + " linked" + at(node, level));
+      }
+    };
+    const size_t w0 = maxM0_ + 1;
+    for (size_t i = 0; i < n; ++i) check_list(i, 0, level0 + i * w0 + 1, level0[i * w0], maxM0_);
+    // upper lists: exactly one per (node, 1 <= level <= levels[node])
+    size_t want = 0;
+    for (size_t i = 0; i < n; ++i) want += (size_t)levels[i];
+    std::vector<uint64_t> first(n + 1, 0);  // slot of (node, level) = first[node] + level - 1
+    for (size_t i = 0; i < n; ++i) first[i + 1] = first[i] + (uint64_t)levels[i];
+    std::vector<size_t> which(want, (size_t)-1);
+    if (upper_off[0] != 0) bad("upper_off[0] is not 0");
+    for (size_t u = 0; u < n_upper; ++u) {
+      const uint32_t node = upper_node[u];
+      const int32_t level = upper_level[u];
+      if (node >= n) bad("upper list of node " + std::to_string(node) + " >= n");
+      if (level < 1 || level > levels[node])
+        bad("upper list for a level the node does not have" + at(node, level));
+      if (upper_off[u + 1] < upper_off[u] || upper_off[u + 1] > n_upper_ids) bad("upper_off out of order or range");
+      size_t& slot = which[first[node] + (uint64_t)level - 1];
+      if (slot != (size_t)-1) bad("two upper lists" + at(node, level));
+      slot = u;
+      check_list(node, level, upper_ids + upper_off[u], (size_t)(upper_off[u + 1] - upper_off[u]), maxM_);
+    }
+    for (size_t i = 0; i < n; ++i)
+      for (int32_t l = 1; l <= levels[i]; ++l)
+        if (which[first[i] + (uint64_t)l - 1] == (size_t)-1) bad("upper list missing" + at(i, l));
+    // ---- valid: write the state ----
+    if (n > max_elements_) resizeIndex(n);
+    labels_.resize(n);
+    label_lookup_.reserve(n);
+    for (size_t i = 0; i < n; ++i) {
+      const tableint id = (tableint)i;
+      (void)getRandomLevel(mult_);
+      label_lookup_[i] = id;
+      labels_[i] = i;
+      element_levels_[i] = levels[i];
+      std::memcpy(&data_[i * dim_], rows + i * dim_, sizeof(float) * dim_);
+      unsigned* ll0 = linklist0(id);
+      std::memset(ll0, 0, sizeof(unsigned) * w0);
+      const size_t c0 = level0[i * w0];
+      ll0[0] = (unsigned)c0;
+      std::memcpy(ll0 + 1, level0 + i * w0 + 1, sizeof(unsigned) * c0);
+      links_upper_[i].assign((size_t)levels[i] * (maxM_ + 1), 0);
+      for (int32_t l = 1; l <= levels[i]; ++l) {
+        const size_t u = which[first[i] + (uint64_t)l - 1];
+        const size_t c = (size_t)(upper_off[u + 1] - upper_off[u]);
+        unsigned* ll = linklist(id, l);
+        ll[0] = (unsigned)c;
+        std::memcpy(ll + 1, upper_ids + upper_off[u], sizeof(unsigned) * c);
+      }
+    }
+    cur_element_count_ = n;
+    enterpoint_node_ = entry_point;
+    maxlevel_ = max_level;
+  }
+
  private:
   CandQueue searchBaseLayer(tableint ep_id, const float* data_point, int layer) {
     ctx0_.next_tag(max_elements_);

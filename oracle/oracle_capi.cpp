@@ -262,6 +262,33 @@ uint32_t orc_hnsw_export_upper(void* p, uint32_t id, int level, uint32_t* out) {
   for (uint32_t j = 0; j < c; j++) out[j] = ll[1 + j];
   return c;
 }
+// Graph import into an EMPTY index (the inverse of the export above, in ehx_graph_import's CSR shape): X raw rows
+// [n][dim], label = row index; cosine rows are normalised as orc_hnsw_add normalises them.  Returns 0, or -1 with the
+// first violation in err (the index stays empty).
+int orc_hnsw_import(void* p, const float* X, size_t n, const uint32_t* level0, const int32_t* levels, size_t n_upper,
+                    const uint32_t* upper_node, const int32_t* upper_level, const uint64_t* upper_off,
+                    size_t n_upper_ids, const uint32_t* upper_ids, uint32_t entry_point, int32_t max_level,
+                    int threads, char* err, size_t err_cap) {
+  Handle* h = (Handle*)p;
+  try {
+    std::vector<float> t;
+    if (h->metric == METRIC_COSINE) {
+      t.resize(n * h->dim);
+      const size_t NB = 1024;
+      parallel_for((n + NB - 1) / NB, threads, [&](size_t b, int) {
+        const size_t i1 = std::min(n, (b + 1) * NB);
+        for (size_t i = b * NB; i < i1; i++) normalize_vector(X + i * h->dim, &t[i * h->dim], h->dim);
+      });
+      X = t.data();
+    }
+    h->hnsw->importGraph(X, n, level0, levels, n_upper, upper_node, upper_level, upper_off, n_upper_ids, upper_ids,
+                         entry_point, max_level);
+  } catch (const std::exception& e) {
+    if (err && err_cap) snprintf(err, err_cap, "%s", e.what());
+    return -1;
+  }
+  return 0;
+}
 void orc_hnsw_export_vectors(void* p, float* out) {
   Handle* h = (Handle*)p;
   for (size_t i = 0; i < h->hnsw->size(); i++)

@@ -64,6 +64,9 @@ def lib():
         L.orc_hnsw_export_upper.restype = C.c_uint32
         L.orc_hnsw_export_upper.argtypes = [C.c_void_p, C.c_uint32, C.c_int, u32p]
         L.orc_hnsw_export_vectors.argtypes = [C.c_void_p, f32p]
+        L.orc_hnsw_import.restype = C.c_int
+        L.orc_hnsw_import.argtypes = [C.c_void_p, f32p, C.c_size_t, u32p, i32p, C.c_size_t, u32p, i32p, u64p,
+                                      C.c_size_t, u32p, C.c_uint32, C.c_int32, C.c_int, C.c_char_p, C.c_size_t]
         L.orc_exhaustive.restype = C.c_double
         L.orc_exhaustive.argtypes = [f32p, C.c_size_t, C.c_size_t, C.c_int, f32p, C.c_size_t,
                                      C.c_size_t, u64p, f32p, u32p, C.c_int]
@@ -236,6 +239,35 @@ class Hnsw:
                 c = lib().orc_hnsw_export_upper(self._h, int(i), level, _ptr(buf, C.c_uint32))
                 upper[(int(i), level)] = buf[:c].copy()
         return l0, lv, upper
+
+    def import_graph(self, X, level0, levels, upper, entry_point, max_level, threads=None):
+        """Load a graph over the raw rows X into this EMPTY index, label = row index: the state addPoint would have left
+        after building exactly this graph (cosine rows normalised as add() normalises them).  level0 [n, 1+2M] u32 rows
+        (count, ids...), levels [n] i32, upper {(node, level >= 1): ids} — what export_graph() and Space.graph_export()
+        return.  The graph is validated first; a bad one raises RuntimeError and leaves the index empty."""
+        X, pX = _f32(X)
+        n = X.shape[0] if X.ndim == 2 else 0
+        assert X.size == n * self.dim, "rows must be [n, dim]"
+        l0 = np.ascontiguousarray(level0, dtype=np.uint32)
+        lv = np.ascontiguousarray(levels, dtype=np.int32)
+        if l0.shape != (n, 2 * self.M + 1) or lv.shape != (n,):
+            raise ValueError("level0 must be [%d, %d] and levels [%d]" % (n, 2 * self.M + 1, n))
+        keys = sorted(upper)
+        un = np.array([key[0] for key in keys], dtype=np.uint32)
+        ul = np.array([key[1] for key in keys], dtype=np.int32)
+        lists = [np.asarray(upper[key], dtype=np.uint32).ravel() for key in keys]
+        off = np.zeros(len(keys) + 1, dtype=np.uint64)
+        if keys:
+            np.cumsum([a.size for a in lists], out=off[1:])
+        ids = np.concatenate(lists) if lists else np.zeros(0, dtype=np.uint32)
+        ids = np.ascontiguousarray(ids if ids.size else np.zeros(1, dtype=np.uint32), dtype=np.uint32)
+        err = C.create_string_buffer(512)
+        rc = lib().orc_hnsw_import(self._h, pX, n, _ptr(l0, C.c_uint32), _ptr(lv, C.c_int32), len(keys),
+                                   _ptr(un, C.c_uint32), _ptr(ul, C.c_int32), _ptr(off, C.c_uint64), int(off[-1]),
+                                   _ptr(ids, C.c_uint32), int(entry_point) & 0xFFFFFFFF, int(max_level),
+                                   threads or os.cpu_count() or 1, err, 512)
+        if rc != 0:
+            raise RuntimeError(err.value.decode())
 
     def export_vectors(self):
         out = np.zeros((len(self), self.dim), dtype=np.float32)
