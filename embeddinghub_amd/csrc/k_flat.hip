@@ -218,8 +218,10 @@ __global__ __launch_bounds__(256) void rerank_kernel(const RerankArgs a) {
       const float margin = cert_margin(a.metric, a.dims, qn, a.max_sumsq ? *a.max_sumsq : __builtin_inff(),
                                        fmaxf(fabsf(kth), fabsf(worst)));
       uncert = !(worst - margin > kth);
-    } else if (a.quv && a.n > a.kprime && cnt < a.k) {
-      uncert = true;  // the filter lost candidates (overflowing gamma etc.): let the fp32 scan decide
+    } else if (a.n > a.kprime && cnt < a.k) {
+      // candidates were lost (NaN keys, an overflowing filter bound): rows outside the list may still be neighbours,
+      // so the next engine decides — the fp32 scan after a filter, the exhaustive pass after the fp32 scan
+      uncert = true;
     }
     if (tid == 0) {
       if (uncert) atomicAdd(a.n_uncertified, 1ull);

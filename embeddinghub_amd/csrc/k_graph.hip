@@ -112,6 +112,11 @@ __global__ __launch_bounds__(64) void graph_search_kernel(const GraphArgs a) {
   EHX_GSYNC();
   float curdist = __uint_as_float(EHX_UNIFORM(__float_as_uint(lane_dist(1))));
   n_dist += 1;
+  // A NaN distance is no neighbour: the descent treats it as +inf (never strictly smaller), and a NaN entry
+  // point the descent could not leave seeds level 0 with the largest key, where it is expanded once and never returned.
+  const bool nan_entry = curdist != curdist;
+  if (nan_entry) curdist = __builtin_inff();
+  bool nan_seed = nan_entry;
 
   // ---- upper levels: greedy descent ----
   for (int level = a.max_level; level >= 1; --level) {
@@ -133,6 +138,7 @@ __global__ __launch_bounds__(64) void graph_search_kernel(const GraphArgs a) {
       {
         // first strictly-smaller minimum in stored order
         float m = lane_dist(cnt);
+        if (m != m) m = __builtin_inff();
         uint32_t mi = (uint32_t)lane;
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
@@ -154,6 +160,7 @@ __global__ __launch_bounds__(64) void graph_search_kernel(const GraphArgs a) {
         curdist = best_d;
         cur = EHX_UNIFORM(ids_l[best_i]);
         changed = true;
+        nan_seed = false;
       }
       EHX_GSYNC();
     }
@@ -179,7 +186,7 @@ __global__ __launch_bounds__(64) void graph_search_kernel(const GraphArgs a) {
   const uint32_t ef = a.ef;
   uint32_t nR = 1;
   if (lane == 0) {
-    R[0] = ((uint64_t)f32_to_ordered(curdist) << 32) | ((uint64_t)cur << 1);
+    R[0] = ((uint64_t)(nan_seed ? kOrdNaN : f32_to_ordered(curdist)) << 32) | ((uint64_t)cur << 1);
     atomicOr(&vis[cur >> 5], 1u << (cur & 31));
     if (a.vislog_cap) vlog[0] = cur;
   }
@@ -257,12 +264,14 @@ __global__ __launch_bounds__(64) void graph_search_kernel(const GraphArgs a) {
     EHX_GSYNC();
     n_dist += nfresh;
     EHX_PROF(1)
-    // distances: lane p (< nfresh) owns fresh neighbour p
+    // distances: lane p (< nfresh) owns fresh neighbour p; a NaN distance keeps +inf and never enters R, so only the
+    // nin keys below +inf are merged (they rank 0..nin-1 among the fresh keys)
     uint64_t mykey = kKeyInf;
     if (nfresh) {
       const float d = lane_dist(nfresh);
-      if ((uint32_t)lane < nfresh) mykey = ((uint64_t)f32_to_ordered(d) << 32) | ((uint64_t)ids_l[lane] << 1);
+      if ((uint32_t)lane < nfresh && d == d) mykey = ((uint64_t)f32_to_ordered(d) << 32) | ((uint64_t)ids_l[lane] << 1);
     }
+    const uint32_t nin = (uint32_t)__builtin_popcountll(__ballot(mykey != kKeyInf));
     scan_from = idx2 != kNoNode ? idx2 : nR;  // entries before idx2 are all expanded now (positions only grow)
 #ifdef EHX_GRAPH_PROFILE
     if (__any(mykey == 1ull)) prof_[7] += 1;  // keeps the distances live: the timer below waits for them
@@ -270,7 +279,7 @@ __global__ __launch_bounds__(64) void graph_search_kernel(const GraphArgs a) {
     EHX_PROF(2)
     // Does any fresh key enter R?  If so rank the fresh keys among themselves by counting (keys are
     // distinct: the id is part of the key); the key of rank 0 is the closest fresh neighbour.
-    const bool do_merge = nfresh != 0 && (nR < ef || __any(mykey < R[ef - 1]));
+    const bool do_merge = nin != 0 && (nR < ef || __any(mykey < R[ef - 1]));
     uint64_t minkey = kKeyInf;
     uint32_t rank = 0;
     if (do_merge) {
@@ -285,7 +294,7 @@ __global__ __launch_bounds__(64) void graph_search_kernel(const GraphArgs a) {
 #pragma unroll
         for (int u = 0; u < 16; ++u) rank += kb[u] < mykey ? 1u : 0u;
       }
-      const uint64_t first = __ballot((uint32_t)lane < nfresh && rank == 0);
+      const uint64_t first = __ballot(mykey != kKeyInf && rank == 0);
       minkey = readlane64(mykey, (int)__builtin_ctzll(first));
     }
     EHX_PROF(3)
@@ -312,11 +321,11 @@ __global__ __launch_bounds__(64) void graph_search_kernel(const GraphArgs a) {
     }
     EHX_PROF(4)
     if (do_merge) {
-      if ((uint32_t)lane < nfresh) S[rank] = mykey;
+      if (mykey != kKeyInf) S[rank] = mykey;
       EHX_GSYNC();
       uint64_t skey = kKeyInf;
       uint32_t ps = kNoNode;
-      if ((uint32_t)lane < nfresh) {
+      if ((uint32_t)lane < nin) {
         skey = S[lane];  // the lane-th smallest fresh key
         ps = lower_bound_lds(R, nR, skey);
       }
@@ -330,9 +339,9 @@ __global__ __launch_bounds__(64) void graph_search_kernel(const GraphArgs a) {
         // slot minus the number of fresh keys landing below it.  F flags the landing slots, so per 64 slots
         // that number is one ballot + a lane-prefix popcount — no per-entry search.  Top down: a chunk
         // reads only slots at or below its own, which are still untouched.
-        const uint32_t new_nR = nR + nfresh < ef ? nR + nfresh : ef;
+        const uint32_t new_nR = nR + nin < ef ? nR + nin : ef;
         const uint32_t fpos = ps + (uint32_t)lane;
-        const bool lands = (uint32_t)lane < nfresh && fpos < ef;
+        const bool lands = (uint32_t)lane < nin && fpos < ef;
         if (lands) F[fpos] = 1;
         EHX_GSYNC();
         for (uint32_t dhi = new_nR; dhi > p0;) {
@@ -380,8 +389,9 @@ __global__ __launch_bounds__(64) void graph_search_kernel(const GraphArgs a) {
   } else {
     for (uint32_t i = lane; i < a.vis_words; i += 64) vis[i] = 0u;
   }
-  // ---- results: the k closest of R (already sorted by (dist, id)) ----
-  const uint32_t cnt = nR < a.k ? nR : a.k;
+  // ---- results: the k closest of R (already sorted by (dist, id)); a NaN seed, if still there, is R's last entry ----
+  uint32_t cnt = nR < a.k ? nR : a.k;
+  if (cnt && (uint32_t)(R[cnt - 1] >> 32) == kOrdNaN) cnt -= 1;
   for (uint32_t j = lane; j < a.k; j += 64) {
     const bool ok = j < cnt;
     a.out_ids[(size_t)qi * a.k + j] = ok ? (uint64_t)((uint32_t)(R[j] & 0xFFFFFFFFull) >> 1) : ~0ull;

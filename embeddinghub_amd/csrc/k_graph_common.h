@@ -9,6 +9,7 @@ namespace ehx {
 namespace {
 
 constexpr uint32_t kNoNode = 0xFFFFFFFFu;
+constexpr uint32_t kOrdNaN = 0xFFFFFFFFu;  // ordered key above +inf: a NaN entry point seeding level 0, never returned
 
 // -DEHX_GRAPH_PROFILE (ablation builds, scripts/gpu_graph_profile.sh): per-phase wall-clock ticks (100 MHz)
 // of the level-0 loop, summed over all query waves into counters[4..11]: pick next node | adjacency +

@@ -90,6 +90,10 @@ __global__ __launch_bounds__(HELP ? 128 : 64) void graph_search_wide_kernel(cons
   float curdist = __uint_as_float(
       EHX_UNIFORM(__float_as_uint(wave_group_dists<METRIC01>(qs, a.Xs, a.ld, a.dims, ids_l, 1, lane, a.xscale))));
   n_dist += 1;
+  // NaN distances (k_graph.hip): +inf to the descent, a NaN entry point it could not leave seeds R with the largest key
+  const bool nan_entry = curdist != curdist;
+  if (nan_entry) curdist = __builtin_inff();
+  bool nan_seed = nan_entry;
   for (int level = a.max_level; level >= 1; --level) {
     bool changed = true;
     while (changed) {
@@ -104,6 +108,7 @@ __global__ __launch_bounds__(HELP ? 128 : 64) void graph_search_wide_kernel(cons
       EHX_GSYNC();
       n_dist += cnt;
       float m = wave_group_dists<METRIC01>(qs, a.Xs, a.ld, a.dims, ids_l, cnt, lane, a.xscale);
+      if (m != m) m = __builtin_inff();
       uint32_t mi = (uint32_t)lane;
 #pragma unroll
       for (int o = 1; o < 64; o <<= 1) {  // first strictly-smaller minimum in stored order
@@ -120,6 +125,7 @@ __global__ __launch_bounds__(HELP ? 128 : 64) void graph_search_wide_kernel(cons
         curdist = m;
         cur = EHX_UNIFORM(ids_l[mi]);
         changed = true;
+        nan_seed = false;
       }
       EHX_GSYNC();
     }
@@ -129,7 +135,7 @@ __global__ __launch_bounds__(HELP ? 128 : 64) void graph_search_wide_kernel(cons
   const uint32_t ef = a.ef;
   uint32_t nR = 1;
   if (lane == 0) {
-    R[0] = ((uint64_t)f32_to_ordered(curdist) << 32) | ((uint64_t)cur << 1);
+    R[0] = ((uint64_t)(nan_seed ? kOrdNaN : f32_to_ordered(curdist)) << 32) | ((uint64_t)cur << 1);
     atomicOr(&vis[cur >> 5], 1u << (cur & 31));
     if (a.vislog_cap) vlog[0] = cur;
   }
@@ -290,7 +296,8 @@ __global__ __launch_bounds__(HELP ? 128 : 64) void graph_search_wide_kernel(cons
         } else {
           d = wave_group_dists<METRIC01, true>(qs, a.Xs, a.ld, a.dims, ids_l + f0, cnt, lane, a.xscale);
         }
-        if ((uint32_t)lane < cnt) key[c] = ((uint64_t)f32_to_ordered(d) << 32) | ((uint64_t)ids_l[f0 + lane] << 1);
+        // (a NaN distance keeps +inf: never below the bound, so it never enters R)
+        if ((uint32_t)lane < cnt && d == d) key[c] = ((uint64_t)f32_to_ordered(d) << 32) | ((uint64_t)ids_l[f0 + lane] << 1);
       }
     }
     EHX_PROF(2)
@@ -438,8 +445,9 @@ __global__ __launch_bounds__(HELP ? 128 : 64) void graph_search_wide_kernel(cons
   } else {
     for (uint32_t i = lane; i < a.vis_words; i += 64) vis[i] = 0u;
   }
-  // ---- results: the k closest of R ----
-  const uint32_t cnt = nR < a.k ? nR : a.k;
+  // ---- results: the k closest of R (without a NaN seed: R's last entry if it is still there) ----
+  uint32_t cnt = nR < a.k ? nR : a.k;
+  if (cnt && (uint32_t)(R[cnt - 1] >> 32) == kOrdNaN) cnt -= 1;
   for (uint32_t j = lane; j < a.k; j += 64) {
     const bool ok = j < cnt;
     a.out_ids[(size_t)qi * a.k + j] = ok ? (uint64_t)((uint32_t)(R[j] & 0xFFFFFFFFull) >> 1) : ~0ull;

@@ -199,8 +199,12 @@ int ehx_key_of(ehx_space* s, uint64_t id, char* out_key, size_t cap, size_t* kle
 /* ---- kNN: ANNIndex::approx_nearest (index.cc:39-52), NearestNeighbor RPC (server.cc:172-210),
  *      VectorStoreTable.Nearest (online.go:63), offlinehub.Index.nearest_neighbor (offlinehub.py:102-131).
  *      Batched: n_queries x dims row-major in, n_queries x k out, nearest first.
- *      out_count[i] <= k is the number of valid results of query i (fewer than k only when the
- *      space holds fewer than k rows — the reference has UB there, index.cc:46-50). ---- */
+ *      out_count[i] <= k is the number of valid results of query i (fewer than k when the space holds
+ *      fewer than k rows — the reference has UB there, index.cc:46-50 — or pairs are left out by the NaN rule).
+ *      Contract: the first k (query, row) pairs in (canonical distance, id) order; a pair whose distance is NaN
+ *      is no neighbour; +-Inf distances are.  The filter scans bound rows and queries with |x|^2 == 0 or in
+ *      (1e-24, 1e30); outside that band the fp32 scan / exhaustive pass answers.  DTYPE_F16 rows are stored
+ *      rounded to nearest-even binary16 (overflow to +-Inf), and searched as stored. ---- */
 int ehx_knn(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, uint64_t* out_ids,
             float* out_dist, uint32_t* out_count);
 /* as ehx_knn, plus keys: key j of query i is key_arena[key_off[i*k+j] .. key_off[i*k+j+1]) ;

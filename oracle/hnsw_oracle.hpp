@@ -1148,13 +1148,14 @@ class HnswOracle {
 
 // ---------------------------------------------------------------------------
 // Exhaustive search: ground truth for recall and the CPU comparator of the
-// brute-force path.  Same distance arithmetic as above; ordered by (dist, id).
+// brute-force path.  Same distance arithmetic as above; ordered by (dist, id); NaN-distance pairs are skipped.
 // ---------------------------------------------------------------------------
 static inline void exhaustive_knn(const float* X, size_t n, size_t dim, int metric, const float* q,
                                   size_t k, uint64_t* out_ids, float* out_dist, size_t* out_count) {
   std::priority_queue<std::pair<float, uint64_t>> heap;  // max-heap on (dist, id)
   for (size_t i = 0; i < n; i++) {
     float d = metric_dist(metric, q, X + i * dim, dim);
+    if (d != d) continue;
     if (heap.size() < k) {
       heap.emplace(d, (uint64_t)i);
     } else if (k > 0 && std::make_pair(d, (uint64_t)i) < heap.top()) {

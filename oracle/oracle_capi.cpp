@@ -317,7 +317,8 @@ double orc_exhaustive(const float* X, size_t n, size_t dim, int metric, const fl
   // Row-blocked scan: a thread takes a block of rows small enough to stay in its cache and runs every query over
   // it, keeping the best k of each query it has seen; the per-thread lists are merged at the end.  Same distances
   // (metric_dist) and the same total order (dist, id) as exhaustive_knn over the whole matrix, so the result is
-  // identical — only the rows are read from DRAM once instead of once per query.
+  // identical — only the rows are read from DRAM once instead of once per query.  A pair whose distance is NaN is no
+  // neighbour (counts may then be < k); +-Inf distances are ordinary keys.
   typedef std::pair<float, uint64_t> Ent;
   if (threads < 1) threads = 1;
   const size_t RB = std::max<size_t>(16, (size_t)(128 * 1024) / (dim ? dim : 1));
@@ -332,6 +333,7 @@ double orc_exhaustive(const float* X, size_t n, size_t dim, int metric, const fl
       const float* q = Q + qi * dim;
       for (size_t i = i0; i < i1; i++) {
         const Ent e(metric_dist(metric, q, X + i * dim, dim), (uint64_t)i);
+        if (e.first != e.first) continue;
         if (h.size() < k) {
           h.push_back(e);
           std::push_heap(h.begin(), h.end());
