@@ -233,6 +233,12 @@ struct ehx_space {
                                // between the raw upload and the permutation — those rows sit in raw order inside a
                                // permuted store; searches and Gets refuse (EHX_EINTERNAL) instead of answering wrongly
   std::shared_mutex mu;        // writers: set/drop/reserve ; readers: knn/get
+  // Exclusive writers of ehx_set_batch — ONLY those: growth of an appending Set, drop, reserve, freeze and graph import take
+  // `mu` exclusively without it — waiting for `mu`.  The lock prefers readers: two callers searching back to back never
+  // leave it free, and a batch that rewrites rows (or any graph write) waited tens of seconds for its turn
+  // (tests/test_rewrite_under_search.py: 3 of 12 batches in 60 s beside one knn and one knn_device caller on 8 000 rows).
+  // ehx_knn and ehx_knn_device let a waiting writer in first (yield_to_writer, ehx_search.cpp).
+  std::atomic<uint32_t> excl_waiting{0};
   std::mutex wmu;              // every mutator takes wmu first, then mu: writers are serialised among themselves, and
                                // a batch of fresh keys does its upload / statistics / scan copies holding wmu only —
                                // the rows land beyond the published row count — and takes mu just to publish

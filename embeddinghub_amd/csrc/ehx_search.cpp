@@ -2,6 +2,15 @@
 // lookups, top-k merge of shard lists.
 #include "ehx_internal.h"
 
+// A search that finds an exclusive writer waiting for the space's lock lets it in first: the caller holds no lock here, and
+// the wait is bounded (50 ms), so it can delay a search and never block one.  Once the writer has the lock the search
+// queues behind it on the lock itself.  (50 us per step, 50 ms in all: chosen, not measured.  With no writer waiting the
+// cost is one atomic load per call.)
+static void yield_to_writer(const ehx_space* s) {
+  for (int i = 0; i < 1000 && s->excl_waiting.load(std::memory_order_acquire) != 0; ++i)
+    std::this_thread::sleep_for(std::chrono::microseconds(50));
+}
+
 extern "C" {
 
 int ehx_knn_device(ehx_space* s, void* stream, size_t n_queries, const float* d_queries, uint32_t k,
@@ -9,6 +18,7 @@ int ehx_knn_device(ehx_space* s, void* stream, size_t n_queries, const float* d_
   if (!valid_space(s)) return fail(EHX_EINVAL, "space is NULL");
   if (n_queries && k && (!d_queries || !d_out_ids || !d_out_dist || !d_out_count))
     return fail(EHX_EINVAL, "NULL device pointer");
+  yield_to_writer(s);
   std::shared_lock<std::shared_mutex> rl(s->mu);
   if (s->dropped) return fail(EHX_ENOTFOUND, "Not found");
   if (is_parent(s)) {
@@ -33,6 +43,7 @@ static int knn_host_direct(ehx_space* s, size_t n_queries, const float* queries,
     return EHX_OK;
   }
   if (!queries || !out_ids || !out_dist) return fail(EHX_EINVAL, "NULL argument");
+  yield_to_writer(s);
   std::shared_lock<std::shared_mutex> rl(s->mu);
   if (s->dropped) return fail(EHX_ENOTFOUND, "Not found");
   if (is_parent(s)) return sharded_knn(s, n_queries, queries, nullptr, 0, k, out_ids, out_dist, out_count, false, nullptr);

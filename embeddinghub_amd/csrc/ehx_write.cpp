@@ -32,7 +32,9 @@ int ehx_set_batch(ehx_space* s, size_t n, const char* const* keys, const size_t*
     }
     if (fast) return write_rows_locked(s, n, ids, next, vecs, &new_keys, true);
   }
+  s->excl_waiting.fetch_add(1, std::memory_order_release);   // (searches that arrive from here on wait for this batch's turn)
   std::unique_lock<std::shared_mutex> wl(s->mu);
+  s->excl_waiting.fetch_sub(1, std::memory_order_release);
   if (s->dropped) return fail(EHX_ENOTFOUND, "Not found");
   if (s->keyless) return fail(EHX_EINVAL, "a shard is written through its parent space");
   auto write = [&](size_t cnt, const char* const* ks, const size_t* kl, const float* v) -> int {

@@ -130,20 +130,24 @@ def _stream(s, base_X, chunks, searchers, n_writers=1, pace=0.0):
     return X, bounds, records
 
 
-def _host_searcher(s, Q, k, tag):
+def _host_searcher(s, Q, k, tag, clock=None):
+    """clock: what lo / hi are read from (default: the published row count; test_rewrite_under_search.py counts batches)"""
+    clock = clock or (lambda: len(s))
+
     def fn(stop):
         out = []
         while not stop.is_set():
-            lo = len(s)
+            lo = clock()
             ans = s.knn(Q, k)
-            hi = len(s)
+            hi = clock()
             out.append((lo, ans, hi, tag))
         return out
     return fn
 
 
-def _device_searcher(s, Q, k, tag):
+def _device_searcher(s, Q, k, tag, clock=None):
     import torch
+    clock = clock or (lambda: len(s))
     st = torch.cuda.Stream()
     q = torch.from_numpy(Q).cuda()
     B = Q.shape[0]
@@ -154,10 +158,10 @@ def _device_searcher(s, Q, k, tag):
         dst = torch.empty((B, k), dtype=torch.float32, device="cuda")
         cnt = torch.empty((B,), dtype=torch.int32, device="cuda")
         while not stop.is_set():
-            lo = len(s)
+            lo = clock()
             s.knn_device(q, k, ids, dst, cnt, stream=st.cuda_stream)
             st.synchronize()
-            hi = len(s)
+            hi = clock()
             out.append((lo, (ids.cpu().numpy().astype(np.uint64), dst.cpu().numpy(), cnt.cpu().numpy().astype(np.uint32)),
                         hi, tag))
         return out
