@@ -149,9 +149,7 @@ int graph_insert(ehx_space* s, uint64_t id0, uint64_t count, uint32_t batch) {
   }
   HIP_TRY(hipMemsetAsync(s->dLinkCount.p, 0, n_rounds * sizeof(uint32_t), st));
   InsertArgs a{};  // (zeroed: a null link_head / sel switches those outputs off in the kernels)
-  a.X = (s->x_half || s->x_perm) ? nullptr : s->xf32();  // (graph kernels read the search copy; X: fp32 ablation builds only)
   a.Xs = s->dXs;
-  a.inv_norm = s->dInv;
   a.xscale = (s->x_perm && s->metric == EHX_METRIC_COSINE) ? s->dInv : nullptr;
   a.adj0 = s->dAdj0;
   a.up_start = s->dUpStart;
@@ -243,9 +241,7 @@ int graph_update(ehx_space* s, uint32_t id) {
   const int level = s->h_levels[id];
   int rc;
   InsertArgs a{};  // (zeroed: a null link_head / sel switches those outputs off in the kernels)
-  a.X = (s->x_half || s->x_perm) ? nullptr : s->xf32();  // (graph kernels read the search copy; X: fp32 ablation builds only)
   a.Xs = s->dXs;
-  a.inv_norm = s->dInv;
   a.xscale = (s->x_perm && s->metric == EHX_METRIC_COSINE) ? s->dInv : nullptr;
   a.adj0 = s->dAdj0;
   a.up_start = s->dUpStart;
@@ -424,9 +420,7 @@ int knn_graph_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_que
   }
   GraphArgs a;
   a.Q = s->dQ.p;
-  a.X = (s->x_half || s->x_perm) ? nullptr : s->xf32();  // (graph kernels read the search copy; X: fp32 ablation builds only)
   a.Xs = s->dXs;
-  a.inv_norm = s->dInv;
   a.xscale = (s->x_perm && s->metric == EHX_METRIC_COSINE) ? s->dInv : nullptr;
   a.adj0 = s->dAdj0;
   a.up_start = s->dUpStart;

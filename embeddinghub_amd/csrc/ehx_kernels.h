@@ -15,6 +15,7 @@ constexpr uint32_t kTileRows16 = 256; // corpus rows per tile of the fp16 filter
 constexpr uint32_t kBK = 32;          // k-depth of one LDS stage (floats)
 constexpr uint32_t kCandSlots = 64;   // per-(query, block) candidate slots = one wave row
 constexpr uint64_t kKeyInf = ~0ull;
+constexpr uint32_t kNoNode = 0xFFFFFFFFu;  // graph kernels: no node / padding of an adjacency list
 
 // (score, id) packed so that unsigned 64-bit order == (score asc, id asc).
 __host__ __device__ inline uint32_t f32_to_ordered(float f) {
@@ -56,6 +57,34 @@ __device__ __forceinline__ void wave_lds_sync() {
 __device__ __forceinline__ uint32_t wave_uniform(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
 __device__ __forceinline__ float wave_uniform(float x) {
   return __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(x)));
+}
+
+// ascending bitonic sort of one u64 per lane across the 64-lane wave
+__device__ __forceinline__ uint64_t wave_sort64(uint64_t key, int lane) {
+#pragma unroll
+  for (int k = 2; k <= 64; k <<= 1) {
+#pragma unroll
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      const uint64_t other = __shfl_xor(key, j, 64);
+      const bool up = (lane & k) == 0;
+      const bool lower = (lane & j) == 0;
+      const uint64_t mn = key < other ? key : other;
+      const uint64_t mx = key < other ? other : key;
+      key = (lower == up) ? mn : mx;
+    }
+  }
+  return key;
+}
+
+// number of entries of the ascending array a[0..n) (any n) that are < key
+__device__ __forceinline__ uint32_t lower_bound_lds(const uint64_t* a, uint32_t n, uint64_t key) {
+  uint32_t lo = 0, hi = n;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (a[mid] < key) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
 }
 
 __device__ __forceinline__ float ex_add(float a, float b) { return a + b; }
@@ -557,19 +586,6 @@ __device__ __forceinline__ float wave_group_dists(const float* __restrict__ qs, 
   return wave_group_dists_t<METRIC01, false, QUAD>(qs, Xs, ld, dims, ids_l, count, lane, nullptr);
 }
 
-// runtime-dispatch form (metric: 0 = L2^2, 1 = 1 - inner product; scale_x: cosine rows) used by the
-// insertion kernels (EHX_INSERT_RING: with or without the register ring — A/B switch)
-#ifndef EHX_INSERT_RING
-#define EHX_INSERT_RING 0
-#endif
-__device__ __forceinline__ float canon_dist_lane(int metric, const float* __restrict__ q,
-                                                 const float* __restrict__ x, float xscale, bool scale_x,
-                                                 uint32_t dims) {
-  if (metric == 0) return canon_dist_lane_t<0, false, EHX_INSERT_RING != 0>(q, x, xscale, dims);
-  if (scale_x) return canon_dist_lane_t<1, true, EHX_INSERT_RING != 0>(q, x, xscale, dims);
-  return canon_dist_lane_t<1, false, EHX_INSERT_RING != 0>(q, x, xscale, dims);
-}
-
 struct ScanArgs {
   const float* Q;        // [q_tiles*256][ld] prepared queries (zero padded)
   const void* X;         // [cap][ld] stored rows (fp32, or fp16 when x_half), cap % 256 == 0, pad columns zero
@@ -870,9 +886,7 @@ hipError_t launch_gen_rows(uint64_t seed, uint64_t row0, uint64_t n_rows, uint32
 constexpr uint32_t kGraphCounters = 12;  // n_dist, n_hops0, n_hops_up, n_prefetch_hit, [4..11] profile builds (wide walk: [4] = steps)
 struct GraphArgs {
   const float* Q;           // prepared queries [nq][ld]
-  const float* X;           // rows [cap][ld]
   const float* Xs;          // search copy [cap][ld] (launch_make_search_copy)
-  const float* inv_norm;    // cosine
   const float* xscale = nullptr;  // single-copy graph spaces, cosine: Xs holds RAW permuted rows, scaled by inv_norm on the fly
   const uint32_t* adj0;     // [n][M0], pad 0xFFFFFFFF, stored order
   const uint32_t* up_start; // [n]: first upper list of the node (levels 1..L consecutive) or ~0
@@ -906,7 +920,8 @@ hipError_t launch_graph_search(const GraphArgs& a, hipStream_t st);
 // largest size set so far is kept per device, atomically.  `fns`: the kernel's instantiations.
 struct DynLdsAttr {
   std::atomic<size_t> set[64] = {};
-  hipError_t ensure(const void* const* fns, int n_fns, size_t bytes) {
+  template <class Fn>
+  hipError_t ensure(const Fn* fns, int n_fns, size_t bytes) {
     if (bytes <= 64 * 1024) return hipSuccess;  // (within the default limit)
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
@@ -914,7 +929,7 @@ struct DynLdsAttr {
     std::atomic<size_t>& cur = set[dev & 63];
     if (cur.load(std::memory_order_acquire) >= bytes) return hipSuccess;
     for (int i = 0; i < n_fns; ++i) {
-      e = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+      e = hipFuncSetAttribute((const void*)fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
       if (e != hipSuccess) return e;
     }
     size_t seen = cur.load(std::memory_order_relaxed);
@@ -925,9 +940,7 @@ struct DynLdsAttr {
 };
 
 struct InsertArgs {
-  const float* X;
   const float* Xs;         // search copy (launch_make_search_copy)
-  const float* inv_norm;
   const float* xscale;     // single-copy graph spaces, cosine: Xs holds RAW permuted rows, scaled by inv_norm on the fly (else nullptr)
   uint32_t* adj0;          // [cap][M0]
   uint32_t* up_start;      // [cap]

@@ -20,23 +20,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
-// ascending bitonic sort of one u64 per lane across the 64-lane wave
-__device__ __forceinline__ uint64_t wave_sort64(uint64_t key, int lane) {
-#pragma unroll
-  for (int k = 2; k <= 64; k <<= 1) {
-#pragma unroll
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      const uint64_t other = __shfl_xor(key, j, 64);
-      const bool up = (lane & k) == 0;
-      const bool lower = (lane & j) == 0;
-      const uint64_t mn = key < other ? key : other;
-      const uint64_t mx = key < other ? other : key;
-      key = (lower == up) ? mn : mx;
-    }
-  }
-  return key;
-}
-
 // input: bitonic sequence across lanes; output ascending
 __device__ __forceinline__ uint64_t wave_bitonic_merge64(uint64_t key, int lane) {
 #pragma unroll

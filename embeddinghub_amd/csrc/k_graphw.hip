@@ -23,6 +23,10 @@
 //
 // Replaces hnswlib::HierarchicalNSW::searchKnn (call site embeddinghub/embeddingstore/index.cc:41) as a throughput mode;
 // layout, visited bitmaps, visit log and counters as k_graph.hip.
+//
+// The LDS layout, the query prologue, the greedy descent, the in-place merge of keys into R and the query epilogue are
+// k_graph_common.h's (shared with the strict walk).  This file is the wide level-0 loop — pick, ranking (its own copy of
+// rank_by_counting's loop: see merge_keys), prediction, request_next, the helper-wave protocol — and the launcher.
 #include "k_graph_common.h"
 
 namespace ehx {
@@ -41,30 +45,22 @@ __global__ __launch_bounds__(HELP ? 128 : 64) void graph_search_wide_kernel(cons
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const uint32_t qi = blockIdx.x;
-  float* qs = (float*)smem;
-  uint64_t* R = (uint64_t*)(smem + (size_t)a.ld * 4);
-  uint64_t* S = R + a.ef_cap;
-  uint64_t* batch = S + 64;
-  uint32_t* ids_l = (uint32_t*)(batch + 64);
-  uint8_t* F = (uint8_t*)(ids_l + 32 * P);
-  float* hd = (float*)(F + (((size_t)a.ef_cap + 15) & ~(size_t)15));   // HELP: the helper wave's distances [32]
-  volatile uint32_t* ctrl = (volatile uint32_t*)(hd + 32);               // HELP: (count, first slot) of the pass; ~0: done
+  GraphLds L;
+  L.carve(smem, a.ld, a.ef_cap, 32 * P);
+  float* qs = L.qs;
+  uint64_t* R = L.R;
+  uint64_t* S = L.S;
+  uint64_t* batch = L.batch;
+  uint32_t* ids_l = L.ids;
+  float* hd = L.hd;                    // HELP: the helper wave's distances [32]
+  volatile uint32_t* ctrl = L.ctrl;    // HELP: (count, first slot) of the pass; ~0: done
   uint32_t* pki = (uint32_t*)batch;  // indices of a step's picks (batch[] is free outside the rank phase)
   uint32_t* vis = a.visited + (size_t)qi * a.vis_words;
   uint32_t* vlog = a.vislog + (size_t)qi * a.vislog_cap;
   uint32_t n_logged = 0;
   if (wv == 0)
-    for (uint32_t i = lane; i < a.ef_cap; i += 64) F[i] = 0;
-
-  if (wv == 0 && a.q_raw) {  // one query per call in one launch (k_graph.hip)
-    prep_query_row(a.q_raw, 1u, a.dims, a.ld, a.metric, const_cast<float*>(a.Q), 0u, lane);
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-  }
-  if (HELP) __syncthreads();   // (the prepared query row is wave 0's work)
-  for (uint32_t i = threadIdx.x; i < a.ld; i += (HELP ? 128 : 64)) qs[search_copy_pos(i)] = a.Q[(size_t)qi * a.ld + i];
-  if (HELP) __syncthreads();
-  else EHX_GSYNC();
+    for (uint32_t i = lane; i < a.ef_cap; i += 64) L.F[i] = 0;
+  load_query<HELP ? 2 : 1>(a, qs, qi, wv, lane);
   if (HELP && wv == 1) {   // the helper wave: rows 32.. of every pass wave 0 publishes
     for (;;) {
       __syncthreads();  // A: (count, first slot) are published
@@ -80,67 +76,23 @@ __global__ __launch_bounds__(HELP ? 128 : 64) void graph_search_wide_kernel(cons
     return;
   }
 
-  unsigned long long n_dist = 0, n_hops0 = 0, n_hops_up = 0, n_steps = 0, n_pf_hit = 0;
+  WalkCounters ctr;
   const uint64_t lt_mask = (1ull << lane) - 1ull;
 
   // ---- entry point and upper levels: the strict walk's greedy descent ----
-  uint32_t cur = a.entry_point;
-  if (lane == 0) ids_l[0] = cur;
-  EHX_GSYNC();
-  float curdist = __uint_as_float(
-      EHX_UNIFORM(__float_as_uint(wave_group_dists<METRIC01>(qs, a.Xs, a.ld, a.dims, ids_l, 1, lane, a.xscale))));
-  n_dist += 1;
-  // NaN distances (k_graph.hip): +inf to the descent, a NaN entry point it could not leave seeds R with the largest key
-  const bool nan_entry = curdist != curdist;
-  if (nan_entry) curdist = __builtin_inff();
-  bool nan_seed = nan_entry;
-  for (int level = a.max_level; level >= 1; --level) {
-    bool changed = true;
-    while (changed) {
-      changed = false;
-      const uint32_t us = a.up_start[cur];
-      const uint32_t* lst = a.up_lists + ((size_t)us + (uint32_t)(level - 1)) * a.M;
-      uint32_t nb = kNoNode;
-      if (lane < (int)a.M) nb = lst[lane];
-      const uint32_t cnt = __builtin_popcountll(__ballot(nb != kNoNode));
-      n_hops_up += 1;
-      if (lane < (int)cnt) ids_l[lane] = nb;
-      EHX_GSYNC();
-      n_dist += cnt;
-      float m = wave_group_dists<METRIC01>(qs, a.Xs, a.ld, a.dims, ids_l, cnt, lane, a.xscale);
-      if (m != m) m = __builtin_inff();
-      uint32_t mi = (uint32_t)lane;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {  // first strictly-smaller minimum in stored order
-        const float od = __shfl_xor(m, o, 64);
-        const uint32_t oi = __shfl_xor(mi, o, 64);
-        if (od < m || (od == m && oi < mi)) {
-          m = od;
-          mi = oi;
-        }
-      }
-      m = __uint_as_float(EHX_UNIFORM(__float_as_uint(m)));
-      mi = EHX_UNIFORM(mi);
-      if (m < curdist) {
-        curdist = m;
-        cur = EHX_UNIFORM(ids_l[mi]);
-        changed = true;
-        nan_seed = false;
-      }
-      EHX_GSYNC();
-    }
-  }
+  const Descent top = greedy_descent<METRIC01>(a, L, lane, ctr);
+  const uint32_t cur = top.cur;
 
   // ---- level 0: best-first, ef bounded, P expansions per step ----
   const uint32_t ef = a.ef;
   uint32_t nR = 1;
   if (lane == 0) {
-    R[0] = ((uint64_t)(nan_seed ? kOrdNaN : f32_to_ordered(curdist)) << 32) | ((uint64_t)cur << 1);
+    R[0] = ((uint64_t)(top.nan_seed ? kOrdNaN : f32_to_ordered(top.curdist)) << 32) | ((uint64_t)cur << 1);
     atomicOr(&vis[cur >> 5], 1u << (cur & 31));
     if (a.vislog_cap) vlog[0] = cur;
   }
   n_logged = 1;
-  EHX_GSYNC();
+  wave_lds_sync();
   uint32_t scan_from = 0;  // every entry of R before this index is expanded
   uint32_t pf_node[P];     // nodes whose adjacency rows were requested at the end of the last step (wave-uniform)
   uint32_t pf_nb[NREG];    // ... and the rows, slot layout as above
@@ -153,9 +105,9 @@ __global__ __launch_bounds__(HELP ? 128 : 64) void graph_search_wide_kernel(cons
 
   // -DEHX_GRAPH_PROFILE builds: 100-MHz ticks per phase summed over all waves into counters[5..11]:
   // pick | adjacency + visited + compaction | row fetch + distances | rank + prediction | insertion points | move R | rest
-  EHX_PROF_DECL;
+  GraphProf prof;
   for (;;) {
-    EHX_PROF(6)
+    prof.mark(6);
     // (Measured and dropped: touching the visited words of the predicted nodes' neighbours here — an atomic OR of 0, nothing to
     // wait for — so that the test-and-set after the pick finds its lines in the L2.  6.25 M x 128, same box, ef 50 / 200 / 800:
     // +7 % time at either width (profiles/r06_e_graph_6250k128_{warm,nowarm}.jsonl): the extra atomic per neighbour costs
@@ -185,7 +137,7 @@ __global__ __launch_bounds__(HELP ? 128 : 64) void graph_search_wide_kernel(cons
       found += c0 + (uint32_t)__builtin_popcountll(m1);
     }
     if (found == 0) break;
-    EHX_GSYNC();
+    wave_lds_sync();
     const uint32_t npick = found < P ? found : P;
     const uint32_t nu = (found < 2 * P ? found : 2 * P) - npick;
     uint64_t pkv = kKeyInf;
@@ -203,10 +155,10 @@ __global__ __launch_bounds__(HELP ? 128 : 64) void graph_search_wide_kernel(cons
       ckey[j] = readlane64(pkv, P + j);  // (lanes >= npick + nu hold +inf)
     }
     scan_from = nu ? (uint32_t)__builtin_amdgcn_readlane((int)pkiv, P) : nR;
-    EHX_GSYNC();
-    n_hops0 += npick;
-    n_steps += 1;
-    EHX_PROF(0)
+    wave_lds_sync();
+    ctr.n_hops0 += npick;
+    ctr.n_steps += 1;
+    prof.mark(0);
 
     // ---- adjacency rows: from the registers requested a step ago where the prediction named the node, else loaded ----
     int mj[P];
@@ -216,7 +168,7 @@ __global__ __launch_bounds__(HELP ? 128 : 64) void graph_search_wide_kernel(cons
 #pragma unroll
       for (int jj = 0; jj < P; ++jj)
         if (pnode[j] != kNoNode && pnode[j] == pf_node[jj]) mj[j] = jj;
-      if (mj[j] >= 0) n_pf_hit += 1;
+      if (mj[j] >= 0) ctr.n_pf_hit += 1;
     }
     uint32_t nb[NREG];
 #pragma unroll
@@ -257,9 +209,9 @@ __global__ __launch_bounds__(HELP ? 128 : 64) void graph_search_wide_kernel(cons
       nfresh += (uint32_t)__builtin_popcountll(fm);
     }
     n_logged += nfresh;
-    n_dist += nfresh;
-    EHX_GSYNC();
-    EHX_PROF(1)
+    ctr.n_dist += nfresh;
+    wave_lds_sync();
+    prof.mark(1);
 
     // the adjacency rows of the nodes the next step is expected to pick (ckey), requested once the last fresh key is ranked
     auto request_next = [&]() {
@@ -300,7 +252,7 @@ __global__ __launch_bounds__(HELP ? 128 : 64) void graph_search_wide_kernel(cons
         if ((uint32_t)lane < cnt && d == d) key[c] = ((uint64_t)f32_to_ordered(d) << 32) | ((uint64_t)ids_l[f0 + lane] << 1);
       }
     }
-    EHX_PROF(2)
+    prof.mark(2);
     // one merge of up to 64 keys (lane p holds key p, +inf: none) into R; `last`: the step's last merge — the next step's
     // adjacency rows are requested inside it, once its keys are ranked
     auto merge_keys = [&](const uint64_t mykey, const bool last) {
@@ -317,8 +269,12 @@ __global__ __launch_bounds__(HELP ? 128 : 64) void graph_search_wide_kernel(cons
       const uint32_t ncan = (uint32_t)__builtin_popcountll(cmask);
       if ((uint32_t)lane >= ncan) batch[lane] = kKeyInf;
       if (can) batch[__builtin_popcountll(cmask & lt_mask)] = mykey;
-      EHX_GSYNC();
-      // rank of those keys among themselves by counting (k_graph.hip); a lane that holds none ranks nothing
+      wave_lds_sync();
+      // rank of those keys among themselves by counting; a lane that holds none ranks nothing.  The loop is
+      // rank_by_counting()'s (k_graph_common.h), kept in place here: with the call the P = 4 instantiations allocate
+      // differently (SGPR spills to lanes 79 / 112 / 87 / 86 -> 117 / 121 / 126 / 126; VGPRs, scratch, occupancy equal)
+      // and width 4 measured 0.6-0.9 % below the slowest run of the parent build at 6.25 M x 128, ef 200, two sessions
+      // ("Shared with the strict walk"; profiles/graph_shared_pieces_ab.jsonl, libs new_rank_call / parent).
       uint32_t rank = 0;
       for (uint32_t j = 0; j < ncan; j += 16) {
         uint64_t kb[16];
@@ -351,49 +307,8 @@ __global__ __launch_bounds__(HELP ? 128 : 64) void graph_search_wide_kernel(cons
         for (int t = 0; t < P; ++t) ckey[t] = nkey[t];
       }
       if (last) request_next();
-      EHX_PROF(3)
-      // merge into R in place, top down (k_graph.hip): the ncan keys, sorted through S
-      if (can) S[rank] = mykey;
-      EHX_GSYNC();
-      uint64_t skey = kKeyInf;
-      uint32_t ps = kNoNode;
-      if ((uint32_t)lane < ncan) {
-        skey = S[lane];
-        ps = lower_bound_lds(R, nR, skey);
-      }
-      const uint32_t p0 = EHX_UNIFORM(ps);
-      EHX_PROF(4)
-      if (p0 < ef) {
-        const uint32_t new_nR = nR + ncan < ef ? nR + ncan : ef;
-        const uint32_t fpos = ps + (uint32_t)lane;
-        const bool lands = (uint32_t)lane < ncan && fpos < ef;
-        if (lands) F[fpos] = 1;
-        EHX_GSYNC();
-        for (uint32_t dhi = new_nR; dhi > p0;) {
-          const uint32_t dlo = dhi - p0 > 64 ? dhi - 64 : p0;
-          const uint32_t dpos = dlo + (uint32_t)lane;
-          const bool in = dpos < dhi;
-          const bool taken = in && F[dpos] != 0;
-          const uint64_t occ = __ballot(taken);
-          const uint32_t below = (uint32_t)__builtin_popcountll(__ballot(lands && fpos < dlo));
-          const uint32_t cntb = below + (uint32_t)__builtin_popcountll(occ & lt_mask);
-          const bool mv = in && !taken;
-          uint64_t kj = 0;
-          if (mv) kj = R[dpos - cntb];
-          EHX_GSYNC();
-          if (mv) R[dpos] = kj;
-          EHX_GSYNC();
-          dhi = dlo;
-        }
-        if (lands) {
-          R[fpos] = skey;
-          F[fpos] = 0;
-        }
-        EHX_GSYNC();
-        nR = new_nR;
-        if (p0 < scan_from) scan_from = p0;
-      }
-      EHX_PROF(5)
+      prof.mark(3);
+      merge_sorted_into_R<4, 5>(L, ef, mykey, can, rank, ncan, nR, scan_from, lane, prof);
     };
     if (nfresh != 0) {
       if (NCH == 1) {
@@ -419,9 +334,9 @@ __global__ __launch_bounds__(HELP ? 128 : 64) void graph_search_wide_kernel(cons
             if (key[c] < bound0) batch[off + (uint32_t)__builtin_popcountll(cm[c] & lt_mask)] = key[c];
             off += (uint32_t)__builtin_popcountll(cm[c]);
           }
-          EHX_GSYNC();
+          wave_lds_sync();
           const uint64_t mk = (uint32_t)lane < ntot ? batch[lane] : kKeyInf;
-          EHX_GSYNC();
+          wave_lds_sync();
           merge_keys(mk, true);
         } else {
 #pragma unroll
@@ -436,51 +351,19 @@ __global__ __launch_bounds__(HELP ? 128 : 64) void graph_search_wide_kernel(cons
     if (lane == 0) ctrl[0] = 0xFFFFFFFFu;
     __syncthreads();
   }
-  // ---- leave the visited bitmap all-zero (k_graph.hip) ----
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-  if (a.vislog_cap == 0) {
-  } else if (n_logged <= a.vislog_cap) {
-    for (uint32_t i = lane; i < n_logged; i += 64) vis[vlog[i] >> 5] = 0u;
-  } else {
-    for (uint32_t i = lane; i < a.vis_words; i += 64) vis[i] = 0u;
-  }
-  // ---- results: the k closest of R (without a NaN seed: R's last entry if it is still there) ----
-  uint32_t cnt = nR < a.k ? nR : a.k;
-  if (cnt && (uint32_t)(R[cnt - 1] >> 32) == kOrdNaN) cnt -= 1;
-  for (uint32_t j = lane; j < a.k; j += 64) {
-    const bool ok = j < cnt;
-    a.out_ids[(size_t)qi * a.k + j] = ok ? (uint64_t)((uint32_t)(R[j] & 0xFFFFFFFFull) >> 1) : ~0ull;
-    a.out_dist[(size_t)qi * a.k + j] = ok ? ordered_to_f32((uint32_t)(R[j] >> 32)) : __builtin_inff();
-  }
-  if (lane == 0) {
-    a.out_count[qi] = cnt;
-    atomicAdd(&a.counters[0], n_dist);
-    atomicAdd(&a.counters[1], n_hops0);
-    atomicAdd(&a.counters[2], n_hops_up);
-    atomicAdd(&a.counters[3], n_pf_hit);
-    atomicAdd(&a.counters[4], n_steps);
-#ifdef EHX_GRAPH_PROFILE
-    for (int i = 0; i < 7; ++i) atomicAdd(&a.counters[5 + i], prof_[i]);
-#endif
-  }
-  if (a.done_flag) {
-    __threadfence_system();
-    __builtin_amdgcn_s_waitcnt(0);
-    if (lane == 0) __hip_atomic_store(a.done_flag, a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
+  finish_query<true>(a, R, nR, qi, lane, vis, vlog, n_logged, ctr, prof);
 }
 
 hipError_t launch_graph_search_wide(const GraphArgs& a, hipStream_t st) {
   const uint32_t P = a.width >= 4 ? 4 : 2;
   const size_t lds = graph_lds_bytes(a.ld, a.ef_cap, P);
   static DynLdsAttr attr;
-  const void* fns[8] = {(const void*)graph_search_wide_kernel<0, 2, false>, (const void*)graph_search_wide_kernel<1, 2, false>,
-                        (const void*)graph_search_wide_kernel<0, 4, false>, (const void*)graph_search_wide_kernel<1, 4, false>,
-                        (const void*)graph_search_wide_kernel<0, 2, true>,  (const void*)graph_search_wide_kernel<1, 2, true>,
-                        (const void*)graph_search_wide_kernel<0, 4, true>,  (const void*)graph_search_wide_kernel<1, 4, true>};
-  if (hipError_t e = attr.ensure(fns, 8, lds); e != hipSuccess) return e;
-  const bool l2 = a.metric == 0;
+  static const GraphKernel kWide[8] = {  // [4 * help + 2 * (P == 4) + (metric != L2)]
+      graph_search_wide_kernel<0, 2, false>, graph_search_wide_kernel<1, 2, false>,
+      graph_search_wide_kernel<0, 4, false>, graph_search_wide_kernel<1, 4, false>,
+      graph_search_wide_kernel<0, 2, true>,  graph_search_wide_kernel<1, 2, true>,
+      graph_search_wide_kernel<0, 4, true>,  graph_search_wide_kernel<1, 4, true>};
+  if (hipError_t e = attr.ensure(kWide, 8, lds); e != hipSuccess) return e;
   // The helper wave: rows of the lengths two share a 4-lane group (<= 256 dims: a pass of 32 rows per wave), batches of at most
   // one query per SIMD, and not the one-query form (its latency is launch + walk, not rows).
   // EHX_GRAPH_HELP=0 / 1 forces it off / on (A/B runs).
@@ -498,16 +381,7 @@ hipError_t launch_graph_search_wide(const GraphArgs& a, hipStream_t st) {
   }
   const int help_env = env().graph_help;
   const bool help = help_env >= 0 ? help_env != 0 : (short_rows && (int)a.nq <= n_simds.load(std::memory_order_relaxed) && !a.q_raw);
-#define EHX_LAUNCH_W(M, PP, H) \
-  hipLaunchKernelGGL((graph_search_wide_kernel<M, PP, H>), dim3(a.nq), dim3(H ? 128 : 64), lds, st, a)
-  if (help) {
-    if (P == 2) { if (l2) EHX_LAUNCH_W(0, 2, true); else EHX_LAUNCH_W(1, 2, true); }
-    else { if (l2) EHX_LAUNCH_W(0, 4, true); else EHX_LAUNCH_W(1, 4, true); }
-  } else {
-    if (P == 2) { if (l2) EHX_LAUNCH_W(0, 2, false); else EHX_LAUNCH_W(1, 2, false); }
-    else { if (l2) EHX_LAUNCH_W(0, 4, false); else EHX_LAUNCH_W(1, 4, false); }
-  }
-#undef EHX_LAUNCH_W
+  hipLaunchKernelGGL(kWide[4 * help + 2 * (P == 4) + (a.metric != 0)], dim3(a.nq), dim3(help ? 128 : 64), lds, st, a);
   return hipGetLastError();
 }
 

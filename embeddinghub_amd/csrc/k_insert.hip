@@ -20,48 +20,16 @@
 //
 // All distances use the canonical (oracle-order) arithmetic and read the SEARCH COPY only (cosine rows normalised
 // there: exactly the vectors hnswlib would have stored) — the raw rows may be fp32 or binary16.
+//
+// The 64-lane sort (wave_sort64), the binary search (lower_bound_lds) and kNoNode are ehx_kernels.h's, shared with the
+// flat and graph-search kernels.  The descent and level search here are NOT k_graph_common.h's: they stop at the node's
+// level, merge through a double buffer and have no NaN mapping (it would change the graph built from non-finite rows).
+// Every kernel here runs one wave per workgroup: LDS hand-overs are wave_lds_sync(), not barriers.
 #include "ehx_kernels.h"
 
 namespace ehx {
 
-#ifndef EHX_I_WSYNC
-#define EHX_I_WSYNC 1  // every kernel here runs one wave per workgroup: wave_lds_sync() instead of a barrier
-#endif
-#if EHX_I_WSYNC
-#define EHX_ISYNC() wave_lds_sync()
-#else
-#define EHX_ISYNC() __syncthreads()
-#endif
-
 namespace {
-
-constexpr uint32_t kNone = 0xFFFFFFFFu;
-
-__device__ __forceinline__ uint64_t wsort64(uint64_t key, int lane) {
-#pragma unroll
-  for (int k = 2; k <= 64; k <<= 1) {
-#pragma unroll
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      const uint64_t other = __shfl_xor(key, j, 64);
-      const bool up = (lane & k) == 0;
-      const bool lower = (lane & j) == 0;
-      const uint64_t mn = key < other ? key : other;
-      const uint64_t mx = key < other ? other : key;
-      key = (lower == up) ? mn : mx;
-    }
-  }
-  return key;
-}
-
-__device__ __forceinline__ uint32_t lb_lds(const uint64_t* a, uint32_t n, uint64_t key) {
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (a[mid] < key) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
 
 // canonical distance between two STORED rows, one lane, both read from the SEARCH COPY (k_misc.hip: cosine rows
 // already normalised — the product hnswlib stores — and every 16-float block permuted so that piece j holds the four
@@ -149,7 +117,7 @@ __device__ __forceinline__ uint32_t select_heuristic(const InsertArgs& a, const 
   const int metric01 = a.metric == 0 ? 0 : 1;
   if (nc < Msel) {
     for (uint32_t i = lane; i < nc; i += 64) kept[i] = cand[i];
-    EHX_ISYNC();
+    wave_lds_sync();
     return nc;
   }
   uint32_t nk = 0;
@@ -168,7 +136,7 @@ __device__ __forceinline__ uint32_t select_heuristic(const InsertArgs& a, const 
       if (lane == 0) kept[nk] = ck;
       nk += 1;
     }
-    EHX_ISYNC();
+    wave_lds_sync();
   }
   return nk;
 }
@@ -200,7 +168,7 @@ __global__ __launch_bounds__(64) void insert_search_kernel(const InsertArgs a) {
     const float qsc = a.xscale ? a.xscale[me] : 1.0f;   // (single-copy graph spaces: the stored row is raw)
     for (uint32_t i = lane; i < a.ld; i += 64) qs[i] = ex_mul(a.Xs[(size_t)me * a.ld + i], qsc);
   }
-  EHX_ISYNC();
+  wave_lds_sync();
 
   // canonical distances of rows ids_l[0..count) to the new row: 4-lane groups reading the search copy in coalesced
   // 64-byte pieces (wave_group_dists, as k_graph.hip); lane p gets row p
@@ -219,14 +187,14 @@ __global__ __launch_bounds__(64) void insert_search_kernel(const InsertArgs a) {
 
   uint32_t* out = a.sel ? a.sel + (size_t)p * (a.max_sel_levels * (1 + a.M)) : nullptr;
   if (out) {
-    for (uint32_t i = lane; i < a.max_sel_levels * (1 + a.M); i += 64) out[i] = (i % (1 + a.M)) == 0 ? 0u : kNone;
+    for (uint32_t i = lane; i < a.max_sel_levels * (1 + a.M); i += 64) out[i] = (i % (1 + a.M)) == 0 ? 0u : kNoNode;
     __syncthreads();  // (global memory handed between lanes — here: rewritten by other lanes later — keeps the real fence)
   }
 
   // ---- greedy descent through the levels above the node's level (hnswlib addPoint) ----
   uint32_t cur = a.entry_point;
   if (lane == 0) ids_l[0] = cur;
-  EHX_ISYNC();
+  wave_lds_sync();
   float curdist = 0.0f;
   if (my_level < a.max_level) {
     curdist = wave_uniform(lane_dist(1));
@@ -236,11 +204,11 @@ __global__ __launch_bounds__(64) void insert_search_kernel(const InsertArgs a) {
         changed = false;
         uint32_t width;
         const uint32_t* lst = list_of(cur, level, &width);
-        uint32_t nb = kNone;
+        uint32_t nb = kNoNode;
         if (lane < (int)width) nb = lst[lane];
-        const uint32_t cnt = __builtin_popcountll(__ballot(nb != kNone));
+        const uint32_t cnt = __builtin_popcountll(__ballot(nb != kNoNode));
         if (lane < (int)cnt) ids_l[lane] = nb;
-        EHX_ISYNC();
+        wave_lds_sync();
         float m = lane_dist(cnt);
         uint32_t mi = (uint32_t)lane;
 #pragma unroll
@@ -259,7 +227,7 @@ __global__ __launch_bounds__(64) void insert_search_kernel(const InsertArgs a) {
           cur = wave_uniform(ids_l[mi]);
           changed = true;
         }
-        EHX_ISYNC();
+        wave_lds_sync();
       }
     }
   }
@@ -270,7 +238,7 @@ __global__ __launch_bounds__(64) void insert_search_kernel(const InsertArgs a) {
   for (int level = top_level; level >= 0; --level) {
     uint32_t nlog = 0;
     if (lane == 0) ids_l[0] = cur;
-    EHX_ISYNC();
+    wave_lds_sync();
     const float d0 = wave_uniform(lane_dist(1));
     uint32_t nR = 1;
     if (lane == 0) {
@@ -279,25 +247,25 @@ __global__ __launch_bounds__(64) void insert_search_kernel(const InsertArgs a) {
       vlog[0] = cur;
     }
     nlog = 1;
-    EHX_ISYNC();
+    wave_lds_sync();
     for (;;) {
-      uint32_t idx = kNone;
-      for (uint32_t base = 0; base < nR && idx == kNone; base += 64) {
+      uint32_t idx = kNoNode;
+      for (uint32_t base = 0; base < nR && idx == kNoNode; base += 64) {
         const uint32_t i = base + lane;
         const bool un = i < nR && !(R[i] & 1ull);
         const uint64_t m = __ballot(un);
         if (m) idx = base + (uint32_t)__builtin_ctzll(m);
       }
-      if (idx == kNone) break;
+      if (idx == kNoNode) break;
       const uint32_t c = wave_uniform((uint32_t)(R[idx] & 0xFFFFFFFFull) >> 1);
-      EHX_ISYNC();
+      wave_lds_sync();
       if (lane == 0) R[idx] |= 1ull;
       uint32_t width;
       const uint32_t* lst = list_of(c, level, &width);
-      uint32_t nb = kNone;
+      uint32_t nb = kNoNode;
       if (lane < (int)width) nb = lst[lane];
       bool fresh = false;
-      if (nb != kNone) {
+      if (nb != kNoNode) {
         const uint32_t bit = 1u << (nb & 31);
         fresh = !(atomicOr(&vis[nb >> 5], bit) & bit);
       }
@@ -309,26 +277,26 @@ __global__ __launch_bounds__(64) void insert_search_kernel(const InsertArgs a) {
         if (nlog + slot < a.vislog_cap) vlog[nlog + slot] = nb;
       }
       nlog += nfresh;
-      EHX_ISYNC();
+      wave_lds_sync();
       if (nfresh == 0) continue;
       uint64_t mykey = kKeyInf;
       {
         const float d = lane_dist(nfresh);
         if ((uint32_t)lane < nfresh) mykey = ((uint64_t)f32_to_ordered(d) << 32) | ((uint64_t)ids_l[lane] << 1);
       }
-      mykey = wsort64(mykey, lane);
+      mykey = wave_sort64(mykey, lane);
       batch[lane] = mykey;
-      EHX_ISYNC();
+      wave_lds_sync();
       if ((uint32_t)lane < nfresh) {
-        const uint32_t pos = lb_lds(R, nR, mykey) + lane;
+        const uint32_t pos = lower_bound_lds(R, nR, mykey) + lane;
         if (pos < ef) R2[pos] = mykey;
       }
       for (uint32_t j = lane; j < nR; j += 64) {
         const uint64_t kj = R[j];
-        const uint32_t pos = j + lb_lds(batch, nfresh, kj);
+        const uint32_t pos = j + lower_bound_lds(batch, nfresh, kj);
         if (pos < ef) R2[pos] = kj;
       }
-      EHX_ISYNC();
+      wave_lds_sync();
       nR = nR + nfresh < ef ? nR + nfresh : ef;
       uint64_t* t = R;
       R = R2;
@@ -344,21 +312,21 @@ __global__ __launch_bounds__(64) void insert_search_kernel(const InsertArgs a) {
     } else {
       for (uint32_t i = lane; i < a.vis_words; i += 64) vis[i] = 0u;
     }
-    EHX_ISYNC();
+    wave_lds_sync();
     if (a.exclude_self) {
       // repairConnectionsForUpdate: the node being updated is part of the graph and finds itself;
       // hnswlib filters it out of the results (and skips the level if nothing else is left)
-      uint32_t pos = kNone;
-      for (uint32_t base = 0; base < nR && pos == kNone; base += 64) {
+      uint32_t pos = kNoNode;
+      for (uint32_t base = 0; base < nR && pos == kNoNode; base += 64) {
         const uint32_t i = base + lane;
         const uint64_t m = __ballot(i < nR && ((uint32_t)(R[i] & 0xFFFFFFFFull) >> 1) == me);
         if (m) pos = base + (uint32_t)__builtin_ctzll(m);
       }
-      if (pos != kNone) {
+      if (pos != kNoNode) {
         for (uint32_t i = lane; i < nR; i += 64) R2[i] = R[i];
-        EHX_ISYNC();
+        wave_lds_sync();
         for (uint32_t i = pos + lane; i + 1 < nR; i += 64) R[i] = R2[i + 1];
-        EHX_ISYNC();
+        wave_lds_sync();
         nR -= 1;
       }
       if (nR == 0) continue;  // level skipped: own list and entry for the next level unchanged
@@ -378,9 +346,9 @@ __global__ __launch_bounds__(64) void insert_search_kernel(const InsertArgs a) {
       // host-side regrouping.  The order pairs arrive in is arbitrary; the link kernel applies them by ascending id.
       uint32_t width;
       uint32_t* own = const_cast<uint32_t*>(list_of(me, level, &width));
-      const uint32_t t = (uint32_t)lane < nk ? (uint32_t)(kept[nk - 1 - lane] & 0xFFFFFFFFull) >> 1 : kNone;
+      const uint32_t t = (uint32_t)lane < nk ? (uint32_t)(kept[nk - 1 - lane] & 0xFFFFFFFFull) >> 1 : kNoNode;
       if ((uint32_t)lane < width) own[lane] = t;
-      if (t != kNone) {
+      if (t != kNoNode) {
         const uint32_t lid = level == 0 ? t : a.head_rows + a.up_start[t] + (uint32_t)(level - 1);
         const uint32_t pair = (p * a.max_sel_levels + (uint32_t)level) * a.M + (uint32_t)lane;
         const uint32_t old = atomicExch(&a.link_head[lid], pair + 1u);
@@ -389,7 +357,7 @@ __global__ __launch_bounds__(64) void insert_search_kernel(const InsertArgs a) {
       }
     }
     cur = (uint32_t)(kept[0] & 0xFFFFFFFFull) >> 1;
-    EHX_ISYNC();
+    wave_lds_sync();
   }
 }
 
@@ -402,15 +370,15 @@ hipError_t launch_insert_search(const InsertArgs& a, uint32_t n_new, hipStream_t
   return hipGetLastError();
 }
 
-// mutuallyConnectNewElement for ONE incoming id on one wave: the list `lst` (width entries, kNone-padded) of node s
+// mutuallyConnectNewElement for ONE incoming id on one wave: the list `lst` (width entries, kNoNode-padded) of node s
 // receives nid — appended while there is room, otherwise re-selected with the heuristic over {nid} u list.
 // is_update: hnswlib's isUpdate branch (a link that already exists is left alone).
 __device__ __forceinline__ void link_incoming(const InsertArgs& a, uint32_t* lst, uint32_t width, uint32_t s,
                                               uint32_t nid, bool is_update, uint64_t* cand, uint64_t* kept, int lane,
                                               int metric01) {
-  uint32_t nb = kNone;
+  uint32_t nb = kNoNode;
   if ((uint32_t)lane < width) nb = lst[lane];
-  const uint32_t cnt = __builtin_popcountll(__ballot(nb != kNone));
+  const uint32_t cnt = __builtin_popcountll(__ballot(nb != kNoNode));
   if (is_update && __any(nb == nid)) return;  // isUpdate: the link already exists
   if (cnt < width) {
     if (lane == 0) lst[cnt] = nid;
@@ -424,10 +392,10 @@ __device__ __forceinline__ void link_incoming(const InsertArgs& a, uint32_t* lst
     return ((uint64_t)f32_to_ordered(d) << 32) | ((uint64_t)id << 1);
   };
   if (cnt < 64) {
-    const uint32_t id = (uint32_t)lane < cnt ? nb : ((uint32_t)lane == cnt ? nid : kNone);
+    const uint32_t id = (uint32_t)lane < cnt ? nb : ((uint32_t)lane == cnt ? nid : kNoNode);
     uint64_t key = kKeyInf;
-    if (id != kNone) key = key_of(id);
-    key = wsort64(key, lane);
+    if (id != kNoNode) key = key_of(id);
+    key = wave_sort64(key, lane);
     cand[lane] = key;
   } else {
     // 64 list entries fill the wave: sort them, then slot the incoming key in at its rank (keys are distinct:
@@ -435,7 +403,7 @@ __device__ __forceinline__ void link_incoming(const InsertArgs& a, uint32_t* lst
     uint64_t nkey = 0;
     if (lane == 0) nkey = key_of(nid);
     nkey = ((uint64_t)__shfl((int)(nkey >> 32), 0, 64) << 32) | (uint32_t)__shfl((int)(uint32_t)nkey, 0, 64);
-    const uint64_t key = wsort64(key_of(nb), lane);
+    const uint64_t key = wave_sort64(key_of(nb), lane);
     const uint32_t rank = __builtin_popcountll(__ballot(key < nkey));
     cand[(uint32_t)lane + ((uint32_t)lane >= rank ? 1u : 0u)] = key;
     if (lane == 0) cand[rank] = nkey;
@@ -443,7 +411,7 @@ __device__ __forceinline__ void link_incoming(const InsertArgs& a, uint32_t* lst
   __syncthreads();
   const uint32_t nk = select_heuristic(a, cand, cnt + 1, width, kept, lane);
   // rewrite farthest first
-  if ((uint32_t)lane < width) lst[lane] = (uint32_t)lane < nk ? (uint32_t)(kept[nk - 1 - lane] & 0xFFFFFFFFull) >> 1 : kNone;
+  if ((uint32_t)lane < width) lst[lane] = (uint32_t)lane < nk ? (uint32_t)(kept[nk - 1 - lane] & 0xFFFFFFFFull) >> 1 : kNoNode;
   __syncthreads();
 }
 
@@ -467,7 +435,7 @@ __global__ __launch_bounds__(64) void insert_link_kernel(const InsertArgs a, con
                              : a.up_lists + ((size_t)a.up_start[s] + (uint32_t)(level - 1)) * a.M;
   const uint32_t b0 = inc_off[w], b1 = inc_off[w + 1];
   if (kind[w] == 1) {
-    if ((uint32_t)lane < width) lst[lane] = (b0 + lane < b1) ? inc_ids[b0 + lane] : kNone;
+    if ((uint32_t)lane < width) lst[lane] = (b0 + lane < b1) ? inc_ids[b0 + lane] : kNoNode;
     return;
   }
   const int metric01 = a.metric == 0 ? 0 : 1;
@@ -511,7 +479,7 @@ __global__ __launch_bounds__(64) void insert_link_dev_kernel(const InsertArgs a)
     uint32_t prev = 0;
     for (uint32_t b = 0; b < c; ++b) {
       // the smallest incoming id above the last one applied
-      uint32_t m = kNone;
+      uint32_t m = kNoNode;
       if (c <= kIncCap) {
         for (uint32_t i = lane; i < c; i += 64) {
           const uint32_t v = inc[i];
@@ -567,26 +535,26 @@ __global__ __launch_bounds__(64) void update_neigh_kernel(const InsertArgs a, co
                                    a.xscale ? a.xscale[s] : 1.0f, a.xscale ? a.xscale[id] : 1.0f);
       key = ((uint64_t)f32_to_ordered(d) << 32) | ((uint64_t)id << 1);
     }
-    key = wsort64(key, lane);
+    key = wave_sort64(key, lane);
     batch[lane] = key;
-    EHX_ISYNC();
+    wave_lds_sync();
     if ((uint32_t)lane < n_here) {
-      const uint32_t pos = lb_lds(R, nR, key) + lane;
+      const uint32_t pos = lower_bound_lds(R, nR, key) + lane;
       if (pos < keep) R2[pos] = key;
     }
     for (uint32_t j = lane; j < nR; j += 64) {
       const uint64_t kj = R[j];
-      const uint32_t pos = j + lb_lds(batch, n_here, kj);
+      const uint32_t pos = j + lower_bound_lds(batch, n_here, kj);
       if (pos < keep) R2[pos] = kj;
     }
-    EHX_ISYNC();
+    wave_lds_sync();
     nR = nR + n_here < keep ? nR + n_here : keep;
     uint64_t* t = R;
     R = R2;
     R2 = t;
   }
   const uint32_t nk = select_heuristic(a, R, nR, width, kept, lane);
-  if ((uint32_t)lane < width) lst[lane] = (uint32_t)lane < nk ? (uint32_t)(kept[nk - 1 - lane] & 0xFFFFFFFFull) >> 1 : kNone;
+  if ((uint32_t)lane < width) lst[lane] = (uint32_t)lane < nk ? (uint32_t)(kept[nk - 1 - lane] & 0xFFFFFFFFull) >> 1 : kNoNode;
 }
 
 hipError_t launch_update_neigh(const InsertArgs& a, uint32_t n_items, const uint32_t* neigh, int level,

@@ -177,7 +177,7 @@ hipError_t launch_sample_select256(const float* scores, uint32_t n_rows, uint32_
 // held (three to four launches per batch: a seventh of a 1.25 M-row shard's batch).
 // ---------------------------------------------------------------------------------------------
 namespace {
-__device__ __forceinline__ uint32_t lower_bound_lds(const uint64_t* a, uint32_t n, uint64_t key) {  // n a power of two
+__device__ __forceinline__ uint32_t lower_bound_pow2_lds(const uint64_t* a, uint32_t n, uint64_t key) {  // n a power of two
   uint32_t lo = 0;
   for (uint32_t step = n >> 1; step > 0; step >>= 1)
     if (a[lo + step - 1] < key) lo += step;
@@ -226,10 +226,10 @@ __global__ __launch_bounds__(256) void select256_kernel(const uint64_t* __restri
     __syncthreads();
     // the new key's place: its index in its own run + the keys below it in the other runs and in the list
     if (v != kKeyInf) {
-      uint32_t pos = (uint32_t)lane + lower_bound_lds(best[cur], width, v);
+      uint32_t pos = (uint32_t)lane + lower_bound_pow2_lds(best[cur], width, v);
 #pragma unroll
       for (int o = 0; o < 4; ++o)
-        if (o != w) pos += lower_bound_lds(runs[o], 64, v);
+        if (o != w) pos += lower_bound_pow2_lds(runs[o], 64, v);
       if (pos < width) best[nxt][pos] = v;
     }
     // the old keys' places
@@ -238,7 +238,7 @@ __global__ __launch_bounds__(256) void select256_kernel(const uint64_t* __restri
       if (old == kKeyInf) continue;
       uint32_t pos = e;
 #pragma unroll
-      for (int o = 0; o < 4; ++o) pos += lower_bound_lds(runs[o], 64, old);
+      for (int o = 0; o < 4; ++o) pos += lower_bound_pow2_lds(runs[o], 64, old);
       if (pos < width) best[nxt][pos] = old;
     }
     cur = nxt;
