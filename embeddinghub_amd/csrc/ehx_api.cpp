@@ -39,6 +39,7 @@ int ehx_init(const int* device_ids, int n_devices) {
   // links are down must not quietly run its exchange step through host memory (EHX_ALLOW_NO_PEER=1 accepts it: the
   // copies then stage through the host, correct but slow).
   const bool strict = !env().allow_no_peer;
+  bool peer_all = true;
   for (int a : devs)
     for (int b : devs) {
       if (a == b) continue;
@@ -52,6 +53,7 @@ int ehx_init(const int* device_ids, int n_devices) {
         pe = hipErrorPeerAccessUnsupported;
       }
       (void)hipGetLastError();
+      if (pe != hipSuccess) peer_all = false;
       if (pe != hipSuccess && strict)
         return fail(EHX_ENODEVICE, "device %d cannot open peer access to device %d (%s): the shards' exchange step needs "
                                    "it (EHX_ALLOW_NO_PEER=1 stages the copies through the host instead)",
@@ -59,6 +61,7 @@ int ehx_init(const int* device_ids, int n_devices) {
     }
   HIP_TRY(hipSetDevice(devs[0]));
   E.devices = devs;
+  E.peer_all = peer_all;
   E.device = devs[0];
   E.n_cus = n_cus > 0 ? n_cus : 256;
   E.inited = true;

@@ -66,6 +66,7 @@ struct Engine {
   bool inited = false;
   int device = 0;            // devices[0]: where unsharded spaces live
   std::vector<int> devices;  // ehx_init's device list: shard i of a sharded space lives on devices[i % size]
+  bool peer_all = true;      // every ordered pair of them has peer access open (false only under EHX_ALLOW_NO_PEER=1)
   int n_cus = 256;
   std::unordered_map<std::string, std::unique_ptr<ehx_space>> spaces;
   std::vector<std::unique_ptr<ehx_space>> graveyard;  // dropped spaces (tombstones), freed by ehx_shutdown
@@ -381,6 +382,13 @@ struct ehx_space {
   DevBuf<float> dOutDist;
   DevBuf<uint32_t> dOutCount;
   unsigned long long* dUncert = nullptr;
+  // neighbours of stored rows (ehx_knn_by_keys / ehx_knn_by_ids_device): the gathered query batch, the row ids of a host
+  // call, the (k + 1)-long lists | validity flags | a host call's k-long results; by_ev: the last call's launches have run
+  // (the next call's stream waits for it before it writes them again)
+  DevBuf<float> dByQ;
+  DevBuf<uint64_t> dByIds;
+  DevBuf<unsigned char> dByOut;
+  hipEvent_t by_ev = nullptr;
   // filter scratch: fp16 queries, per-query (gamma, u, v), per-query certification flags, re-run buffers
   DevBuf<__half> dQ16;
   DevBuf<float> dQgamma, dFbQ, dFbDist, dSample;
@@ -556,6 +564,11 @@ struct ehx_space {
     dLinkTouched.release();
     dQraw.release();
     dQ.release();
+    dByQ.release();
+    dByIds.release();
+    dByOut.release();
+    if (by_ev) (void)hipEventDestroy(by_ev);
+    by_ev = nullptr;
     dCand.release();
     dPart.release();
     dMerged.release();
@@ -651,5 +664,9 @@ int sharded_set_batch(ehx_space* p, size_t n, const char* const* keys, const siz
 int sharded_fill_synthetic(ehx_space* p, uint64_t seed, uint64_t row0, uint64_t n_rows, int normalize, uint32_t latent = 0);
 int sharded_knn(ehx_space* p, size_t nq, const float* h_queries, const float* d_queries, int qdev, uint32_t k,
                 uint64_t* out_ids, float* out_dist, uint32_t* out_count, bool out_on_device, hipStream_t caller_stream);
+// the same with the parent's scratch_mu already held by the caller
+int sharded_knn_locked(ehx_space* p, size_t nq, const float* h_queries, const float* d_queries, int qdev, uint32_t k,
+                       uint64_t* out_ids, float* out_dist, uint32_t* out_count, bool out_on_device,
+                       hipStream_t caller_stream);
 
 }  // namespace ehx_impl

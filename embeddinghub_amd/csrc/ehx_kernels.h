@@ -857,6 +857,36 @@ hipError_t launch_scatter_results(const uint64_t* ids, const float* dist, const 
                                   uint32_t m, uint32_t k, uint64_t* out_ids, float* out_dist, uint32_t* out_cnt,
                                   hipStream_t st);
 
+// neighbours of stored rows (k_bykey.hip): the query batch gathered from the rows themselves, and the row's own id
+// removed from its (k + 1)-long list
+constexpr uint32_t kMaxShardBases = 64;   // (ehx_space_create accepts up to 64 shards)
+struct ShardBases {
+  const void* p[kMaxShardBases];   // dX of shard i (an unsharded space: p[0])
+};
+struct GatherRowsArgs {
+  const uint64_t* row_ids;  // [n] global row ids
+  ShardBases bases;         // rows of shard g % G, local row g / G; peers are read over the access ehx_init opened
+  uint64_t n_rows;          // the search's snapshot of the row count: an id at or above it gives a zero row, valid = 0
+  float* out;               // [n][dims] what ehx_get_by_id returns for every row
+  uint32_t* valid;          // [n]
+  uint32_t n, dims, ld, G;
+  uint32_t x_half;          // rows stored as binary16
+  uint32_t x_perm;          // fp32 rows stored in the search copy's block order (single-copy graph spaces)
+};
+hipError_t launch_gather_rows(const GatherRowsArgs& a, hipStream_t st);
+struct DropSelfArgs {
+  const uint64_t* ids;      // [n][k + 1] result lists of the k + 1 search
+  const float* dist;        // [n][k + 1]
+  const uint32_t* count;    // [n]
+  const uint64_t* row_ids;  // [n] every query's own row id
+  const uint32_t* valid;    // [n] launch_gather_rows: 0 = the query's row id was out of range (count 0)
+  uint64_t* out_ids;        // [n][k]
+  float* out_dist;          // [n][k]
+  uint32_t* out_count;      // [n]
+  uint32_t n, k;
+};
+hipError_t launch_drop_self(const DropSelfArgs& a, hipStream_t st);
+
 // per-row statistics for rows [row0, row0+n): inv_norm (cosine), rowp (a,b) for the scan epilogue;
 // *max_sumsq (optional) is raised to the largest |x|^2 seen (the certification margin's norm bound)
 // perm: the fp32 rows are stored block-permuted (single-copy graph spaces); the sums keep the logical order

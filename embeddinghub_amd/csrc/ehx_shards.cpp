@@ -121,10 +121,17 @@ int sharded_fill_synthetic(ehx_space* p, uint64_t seed, uint64_t row0, uint64_t 
 int sharded_knn(ehx_space* p, size_t nq, const float* h_queries, const float* d_queries, int qdev, uint32_t k,
                 uint64_t* out_ids, float* out_dist, uint32_t* out_count, bool out_on_device, hipStream_t caller_stream) {
   if (k == 0 || nq == 0) return EHX_OK;
+  std::lock_guard<std::mutex> sl(p->scratch_mu);
+  return sharded_knn_locked(p, nq, h_queries, d_queries, qdev, k, out_ids, out_dist, out_count, out_on_device, caller_stream);
+}
+
+int sharded_knn_locked(ehx_space* p, size_t nq, const float* h_queries, const float* d_queries, int qdev, uint32_t k,
+                       uint64_t* out_ids, float* out_dist, uint32_t* out_count, bool out_on_device,
+                       hipStream_t caller_stream) {
+  if (k == 0 || nq == 0) return EHX_OK;
   if (k > 1024) return fail(EHX_EUNSUPPORTED, "k=%u exceeds 1024", k);
   const size_t G = p->shards.size();
   const int home = p->shards[0]->device;
-  std::lock_guard<std::mutex> sl(p->scratch_mu);
   int rc;
   HIP_TRY(hipSetDevice(home));
   const size_t o_dist = nq * k * sizeof(uint64_t), o_cnt = o_dist + nq * k * sizeof(float);

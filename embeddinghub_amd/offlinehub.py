@@ -63,6 +63,11 @@ class Index:
         keys = self._space.knn_keys(np.asarray(embedding, dtype=np.float32), num)[0]
         return [self._orig_key(k) for k in keys]
 
+    def nearest_neighbors(self, num, keys):
+        """nearest_neighbor(num, key=...) for many stored keys in ONE engine call -> one key list per key"""
+        lists = self._space.knn_by_keys_keys([str(key) for key in keys], num)
+        return [[self._orig_key(k) for k in lst] for lst in lists]
+
     def _orig_key(self, skey):
         # hand back the caller's original key object: one dict lookup per neighbour (it was a scan over every key
         # of the index for non-string keys — the reference's own tests use integer keys, offlinehub_test.py:68-86)

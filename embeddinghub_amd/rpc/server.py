@@ -41,7 +41,9 @@ class SpaceNotWritable(Exception):
 
 
 class KeyNotFound(Exception):
-    pass
+    def __init__(self, index=None):
+        super().__init__()
+        self.index = index  # nearest_many_by_key: position of the first unknown key in the batch
 
 
 class EngineSpace:
@@ -92,6 +94,17 @@ class EngineSpace:
     def nearest_many(self, num, embeddings):
         """by-embedding lookups of one stream window as ONE engine call (n x dims matrix -> n key lists)"""
         return self._s.knn_keys(np.asarray(embeddings, dtype=np.float32).reshape(-1, self.dims), num)
+
+    def nearest_many_by_key(self, num, keys):
+        """by-key lookups of one stream window as ONE engine call (n stored keys -> n key lists); an unknown key raises
+        KeyNotFound carrying its position"""
+        from .. import _lib
+        try:
+            return self._s.knn_by_keys_keys(keys, num)
+        except _lib.EhxError as e:
+            if e.code == _lib.ENOTFOUND:
+                raise KeyNotFound(getattr(e, "bad_index", None))
+            raise
 
     def drop(self):
         self._s.drop()
@@ -238,12 +251,34 @@ class EmbeddingHubService(pb_grpc.EmbeddingHubServicer):
             context.abort(grpc.StatusCode.INVALID_ARGUMENT, "num must not be negative")
         return sp, has_key
 
+    @staticmethod
+    def _nearest_by_keys(sp, num, keys):
+        """-> (answers of the keys in front of the first unknown one, its position or None): ONE engine call where the
+        store batches by key (`nearest_many_by_key`; a second one for the keys in front of an unknown key), else one call
+        per key"""
+        many = getattr(sp, "nearest_many_by_key", None)
+        if many is not None and len(keys) > 1:
+            try:
+                return many(num, keys), None
+            except KeyNotFound as e:
+                if e.index is None:
+                    raise
+                return (many(num, keys[:e.index]) if e.index else []), e.index
+        got = []
+        for i, key in enumerate(keys):
+            try:
+                got.append(sp.nearest(num, key=key))
+            except KeyNotFound:
+                return got, i
+        return got, None
+
     def MultiNearestNeighbor(self, request_iterator, context):
         """Additive RPC (embedding_store_pb2.ADDITIVE_METHODS): NearestNeighbor over a stream, answers in request
         order.  Requests are taken off the stream as they arrive — a reader thread feeds a queue, so a client that
         waits for an answer before sending its next request is served at once — and whatever has accumulated (up to
-        MULTI_NN_WINDOW) is answered together: by-embedding requests of one (space, num) go to the engine as ONE batch
-        (`nearest_many`), by-key requests one by one.  Every request gets the unary RPC's checks; the first failing one
+        MULTI_NN_WINDOW) is answered together: the by-embedding requests of one (space, num) go to the engine as ONE batch
+        (`nearest_many`), and so do its by-key requests (`nearest_many_by_key`); a store without these methods is asked
+        one by one.  Every request gets the unary RPC's checks; the first failing one
         ends the stream with the unary RPC's status, after the requests before it have been answered.  The reader
         thread ends with the handler (abort, cancelled client, normal end): it never blocks on a queue nobody drains."""
         inbox = queue.Queue(maxsize=4 * self.MULTI_NN_WINDOW)
@@ -293,16 +328,17 @@ class EmbeddingHubService(pb_grpc.EmbeddingHubServicer):
                 failed = None
                 answers = []
                 groups = {}  # (space name, num) -> (space, [positions], [vectors])
+                key_groups = {}  # (space name, num) -> (space, [positions], [keys])
                 for pos, req in enumerate(window):
                     try:
                         if isinstance(req, Exception):
                             raise _Failed(grpc.StatusCode.CANCELLED, "request stream failed: %r" % (req,))
                         sp, has_key = self._nn_validate(req, _Deferring)
                         if has_key:
-                            try:
-                                answers.append(sp.nearest(req.num, key=req.key))
-                            except KeyNotFound:
-                                raise _Failed(grpc.StatusCode.NOT_FOUND, "Not found")
+                            g = key_groups.setdefault((req.space, req.num), (sp, [], []))
+                            g[1].append(pos)
+                            g[2].append(req.key)
+                            answers.append(None)
                         else:
                             v = self._checked(sp, req.embedding, _Deferring)
                             g = groups.setdefault((req.space, req.num), (sp, [], []))
@@ -312,7 +348,21 @@ class EmbeddingHubService(pb_grpc.EmbeddingHubServicer):
                     except _Failed as f:  # the requests before the failing one are still answered, then the stream ends
                         failed = f
                         break
+                # an unknown key fails its request like any other check: the answers stop in front of the FIRST failing
+                # request of the window, whichever kind it is
+                cut = len(answers)
+                for (_, num), (sp, positions, keys) in key_groups.items():
+                    keys = [k for pos, k in zip(positions, keys) if pos < cut]
+                    got, bad = self._nearest_by_keys(sp, num, keys)
+                    for pos, res in zip(positions, got):
+                        answers[pos] = res
+                    if bad is not None:
+                        cut = positions[bad]
+                        failed = _Failed(grpc.StatusCode.NOT_FOUND, "Not found")
+                del answers[cut:]
                 for (_, num), (sp, positions, vecs) in groups.items():
+                    vecs = [v for pos, v in zip(positions, vecs) if pos < cut]
+                    positions = positions[:len(vecs)]
                     many = getattr(sp, "nearest_many", None)
                     if many is not None and len(vecs) > 1:
                         for pos, keys in zip(positions, many(num, np.stack(vecs))):

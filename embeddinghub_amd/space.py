@@ -264,6 +264,49 @@ class Space:
         o = off.tolist()
         return [raw[o[j]:o[j + 1]].decode() for j in range(cnt.value)]
 
+    def knn_by_keys(self, keys, k):
+        """knn_by_key for a batch of stored keys in ONE engine call: the rows are gathered into the query batch on the
+        device, searched with k + 1, and every key is dropped from its own list there.
+        -> ids [n,k] u64, dist [n,k] f32, count [n] u32.  An unknown key raises EhxError (ENOTFOUND) whose
+        `bad_index` is the position of the first one."""
+        n, arr, lens, keep = marshal_keys(keys)
+        ids = np.full((n, max(k, 1)), np.uint64(2**64 - 1), dtype=np.uint64)
+        dist = np.full((n, max(k, 1)), np.inf, dtype=np.float32)
+        cnt = np.zeros(n, dtype=np.uint32)
+        bad = C.c_size_t(0)
+        rc = self._L.ehx_knn_by_keys(self._h, n, arr, lens, k, ids.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                     dist.ctypes.data_as(C.POINTER(C.c_float)),
+                                     cnt.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(bad))
+        del keep
+        _check_bad(rc, bad)
+        return ids[:, :k], dist[:, :k], cnt
+
+    def knn_by_keys_keys(self, keys, k):
+        """-> list (per key) of neighbour key lists, nearest first (the NearestNeighbor RPC by key, batched)."""
+        n, arr, lens, keep = marshal_keys(keys)
+        ids = np.zeros((n, max(k, 1)), dtype=np.uint64)
+        dist = np.zeros((n, max(k, 1)), dtype=np.float32)
+        cnt = np.zeros(n, dtype=np.uint32)
+        off = np.zeros(n * k + 1, dtype=np.uint64)
+        bad = C.c_size_t(0)
+        cap = 1 << 16
+        while True:
+            arena = C.create_string_buffer(cap)
+            rc = self._L.ehx_knn_by_keys_keys(self._h, n, arr, lens, k, ids.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                              dist.ctypes.data_as(C.POINTER(C.c_float)),
+                                              cnt.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(bad), arena, cap,
+                                              off.ctypes.data_as(C.POINTER(C.c_uint64)))
+            if rc == _lib.ERANGE:
+                cap *= 4
+                continue
+            _check_bad(rc, bad)
+            break
+        del keep
+        raw = arena.raw
+        o = off.tolist()
+        c = cnt.tolist()
+        return [[raw[o[i * k + j]:o[i * k + j + 1]].decode() for j in range(c[i])] for i in range(n)]
+
     # ---- device-resident (torch tensors on the GPU) ----
     def knn_device(self, d_queries, k, d_ids, d_dist, d_count, stream=None):
         """All arguments are device pointers (ints) or torch CUDA tensors; enqueues on `stream`."""
@@ -274,6 +317,17 @@ class Space:
             raise ValueError("pass torch tensors (queries [nq, dims])")
         check(self._L.ehx_knn_device(self._h, C.c_void_p(stream or 0), nq, ptr(d_queries), k, ptr(d_ids),
                                      ptr(d_dist), ptr(d_count)))
+
+    def knn_by_ids_device(self, d_row_ids, k, d_ids, d_dist, d_count, stream=None):
+        """The neighbours of stored rows, by row id, without the rows leaving the device: d_row_ids [n] u64, outputs as
+        knn_device's (torch CUDA tensors); row i's own id is dropped from its list; an id >= len(self) gives count 0."""
+        def ptr(t):
+            return C.c_void_p(t.data_ptr() if hasattr(t, "data_ptr") else int(t))
+        n = d_row_ids.shape[0] if hasattr(d_row_ids, "shape") else None
+        if n is None:
+            raise ValueError("pass torch tensors (row ids [n])")
+        check(self._L.ehx_knn_by_ids_device(self._h, C.c_void_p(stream or 0), n, ptr(d_row_ids), k, ptr(d_ids),
+                                            ptr(d_dist), ptr(d_count)))
 
     def stats(self):
         st = Stats()
@@ -288,6 +342,15 @@ class Space:
         out = (C.c_uint64 * 12)()
         check(self._L.ehx_graph_counters(self._h, out, 12))
         return tuple(int(v) for v in out)  # [4:] phase timers of -DEHX_GRAPH_PROFILE builds, else zeros
+
+
+def _check_bad(rc, bad):
+    """check(rc) of a batched by-key call: an ENOTFOUND error carries the index of the first unknown key"""
+    try:
+        check(rc)
+    except EhxError as e:
+        e.bad_index = bad.value if e.code == _lib.ENOTFOUND else None
+        raise
 
 
 def marshal_keys(keys):

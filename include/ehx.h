@@ -222,6 +222,20 @@ int ehx_knn_by_key(ehx_space* s, const char* key, size_t klen, uint32_t k, uint6
  * out_ids / out_dist may be NULL. */
 int ehx_knn_by_key_keys(ehx_space* s, const char* key, size_t klen, uint32_t k, uint64_t* out_ids, float* out_dist,
                         uint32_t* out_count, char* key_arena, size_t arena_cap, uint64_t* key_off);
+/* ehx_knn_by_key for n stored keys in ONE call (the same key may appear several times): the rows are gathered into a query
+ * batch on the device (the bytes ehx_get returns), searched with k + 1 by the space's own pipeline, and every key is
+ * dropped from its own list on the device — the rule above, so row i equals ehx_knn_by_key(keys[i]).  Outputs laid out
+ * [n][k] as in ehx_knn.  Key lookup, gather and search see ONE state of the space.  An unknown key fails the whole call
+ * with EHX_ENOTFOUND, stores its index in *bad_index (may be NULL) and leaves the outputs unwritten; k > EHX_MAX_K_PAGED:
+ * EHX_EUNSUPPORTED.  Flat and graph spaces, F32 and F16, row-sharded spaces (whose shards must have peer access to shard
+ * 0's device: EHX_EUNSUPPORTED under EHX_ALLOW_NO_PEER when they do not). */
+int ehx_knn_by_keys(ehx_space* s, size_t n, const char* const* keys, const size_t* klens, uint32_t k,
+                    uint64_t* out_ids, float* out_dist, uint32_t* out_count, size_t* bad_index);
+/* as ehx_knn_by_keys, plus the neighbours' keys, laid out as ehx_knn_keys lays them out (key_off has n*k+1 entries);
+ * EHX_ERANGE if the arena is too small. */
+int ehx_knn_by_keys_keys(ehx_space* s, size_t n, const char* const* keys, const size_t* klens, uint32_t k,
+                         uint64_t* out_ids, float* out_dist, uint32_t* out_count, size_t* bad_index, char* key_arena,
+                         size_t arena_cap, uint64_t* key_off);
 
 /* ---- device-resident entry points (inputs/outputs already in HBM; `stream` is a hipStream_t
  *      passed as void*, NULL = default stream).  These are what a batching shim and bench.py
@@ -235,6 +249,12 @@ int ehx_knn_by_key_keys(ehx_space* s, const char* key, size_t klen, uint32_t k, 
  *      arrays takes the space exclusively and drains the device first). ---- */
 int ehx_knn_device(ehx_space* s, void* stream, size_t n_queries, const float* d_queries, uint32_t k,
                    uint64_t* d_out_ids, float* d_out_dist, uint32_t* d_out_count);
+/* The neighbours of rows the space holds, by row id, without the rows leaving HBM: query i is row d_row_ids[i] as stored
+ * (what ehx_get_by_id returns), searched with k + 1, the row itself dropped from its list (ehx_knn_by_key's rule).
+ * Completion as for ehx_knn_device.  An id at or above the row count gives d_out_count[i] = 0, not an error.
+ * k > EHX_MAX_K_PAGED and row-sharded spaces: EHX_EUNSUPPORTED. */
+int ehx_knn_by_ids_device(ehx_space* s, void* stream, size_t n, const uint64_t* d_row_ids, uint32_t k,
+                          uint64_t* d_out_ids, float* d_out_dist, uint32_t* d_out_count);
 /* k-way merge of per-shard results (RCCL all-gather output): lists laid out
  * [n_lists][n_queries][k]; ids must already be global.  Ordered by (dist, id). */
 int ehx_merge_topk_device(void* stream, size_t n_queries, uint32_t k, uint32_t n_lists,

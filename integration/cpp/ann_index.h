@@ -63,6 +63,41 @@ class ANNIndex {
     return keys;
   }
 
+  // Not part of the reference's class: the neighbours of many stored keys in ONE engine call (ehx_knn_by_keys_keys: the
+  // rows are gathered on the device, searched with num + 1, every key dropped from its own list) — what server.cc:193-207
+  // does per request.  Throws std::out_of_range naming the first key that is not stored.
+  std::vector<std::vector<std::string>> approx_nearest_by_keys(const std::vector<std::string>& keys, size_t num) const {
+    std::vector<std::vector<std::string>> out(keys.size());
+    if (num == 0 || keys.empty()) return out;
+    const size_t n = keys.size();
+    std::vector<const char*> kp(n);
+    std::vector<size_t> kl(n);
+    for (size_t i = 0; i < n; ++i) {
+      kp[i] = keys[i].data();
+      kl[i] = keys[i].size();
+    }
+    std::vector<uint64_t> ids(n * num), off(n * num + 1);
+    std::vector<float> dist(n * num);
+    std::vector<uint32_t> count(n);
+    std::vector<char> arena(64 * n * num + 4096);
+    size_t bad = 0;
+    for (;;) {
+      int rc = ehx_knn_by_keys_keys(space_, n, kp.data(), kl.data(), (uint32_t)num, ids.data(), dist.data(), count.data(),
+                                    &bad, arena.data(), arena.size(), off.data());
+      if (rc == EHX_ERANGE) {
+        arena.resize(arena.size() * 4);
+        continue;
+      }
+      if (rc == EHX_ENOTFOUND) throw std::out_of_range("ANNIndex::approx_nearest_by_keys: no such key: " + keys[bad]);
+      check(rc);
+      break;
+    }
+    for (size_t i = 0; i < n; ++i)
+      for (uint32_t j = 0; j < count[i]; ++j)
+        out[i].emplace_back(arena.data() + off[i * num + j], arena.data() + off[i * num + j + 1]);
+    return out;
+  }
+
  private:
   static void check(int rc) {
     if (rc != EHX_OK) throw std::runtime_error(std::string("ehx: ") + ehx_last_error());
