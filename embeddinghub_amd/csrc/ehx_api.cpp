@@ -121,9 +121,8 @@ static int create_one(Engine& E, const std::string& nm, uint32_t dims, int metri
   {
     const bool env_f32 = env().scan_f32;  // EHX_SCAN=f32: every space scans in fp32 (A/B runs, profiling)
     const bool env_f16 = env().scan_f16;  // EHX_SCAN=f16: no int8 scan copy (A/B runs)
-    s->use16 = s->params.mode == EHX_MODE_FLAT && s->params.scan != EHX_SCAN_F32 && !env_f32;
-    s->has16 = s->use16;
-    s->scan_sel = s->use16 ? s->params.scan : (uint32_t)EHX_SCAN_F32;
+    s->has16 = s->params.mode == EHX_MODE_FLAT && s->params.scan != EHX_SCAN_F32 && !env_f32;
+    s->scan_sel = s->has16 ? s->params.scan : (uint32_t)EHX_SCAN_F32;
     s->ld16 = (uint32_t)round_up(dims, 128);
     s->ld8 = (uint32_t)round_up(dims, 64);
     // the int8 scan copy pays when its rows are clearly shorter than the fp16 copy's (padded to whole 64-byte stages
@@ -140,27 +139,21 @@ static int create_one(Engine& E, const std::string& nm, uint32_t dims, int metri
     s->i8_width = dims >= 1536 ? 2 * kMerged8 : kMerged8;
     if (env().i8_width) s->i8_width = env().i8_width;
     if (env().i8_min_rows) s->i8_min_rows = env().i8_min_rows;
-    if (s->has16) {
-      HIP_TRY(hipMalloc((void**)&s->dUnsafe, sizeof(unsigned long long)));
-      HIP_TRY(hipMemset(s->dUnsafe, 0, sizeof(unsigned long long)));
-    }
-    if (s->has8) {
-      // [0] rows the int8 filter cannot bound, [1] tiles with a lane group whose B margin matters (L2^2 on rows whose norms vary)
-      HIP_TRY(hipMalloc((void**)&s->dUnsafe8, 2 * sizeof(unsigned long long)));
-      HIP_TRY(hipMemset(s->dUnsafe8, 0, 2 * sizeof(unsigned long long)));
-    }
+    if (s->has16 && (rc = s->f16.dUnsafe.ensure_zeroed_once(1))) return rc;
+    // [0] rows the int8 filter cannot bound, [1] tiles with a lane group whose B margin matters (L2^2 on rows whose norms vary)
+    if (s->has8 && (rc = s->i8.dUnsafe8.ensure_zeroed_once(2))) return rc;
   }
-  HIP_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-  HIP_TRY(hipStreamCreateWithFlags(&s->wstream, hipStreamNonBlocking));
-  HIP_TRY(hipEventCreateWithFlags(&s->wev, hipEventBlockingSync | hipEventDisableTiming));
-  for (auto& e : s->sev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventBlockingSync | hipEventDisableTiming));
+  if ((rc = s->stream.ensure(hipStreamNonBlocking))) return rc;
+  if ((rc = s->wr.wstream.ensure(hipStreamNonBlocking))) return rc;
+  if ((rc = s->wr.wev.ensure(hipEventBlockingSync | hipEventDisableTiming))) return rc;
+  for (auto& e : s->wr.sev)
+    if ((rc = e.ensure(hipEventBlockingSync | hipEventDisableTiming))) return rc;
   for (BatchClock* c : {&s->clock, &s->i8set[0].clock, &s->i8set[1].clock}) {
     c->own = s->stream;
     c->counter = &s->ev_counter;
   }
   if (!parent) {
-    HIP_TRY(hipMalloc((void**)&s->dMaxSumsq, sizeof(float)));
-    HIP_TRY(hipMemset(s->dMaxSumsq, 0, sizeof(float)));
+    if ((rc = s->rows.dMaxSumsq.ensure_zeroed_once(1))) return rc;
     uint64_t cap0 = s->params.initial_capacity ? s->params.initial_capacity : 128;  // index.h:21
     if ((rc = grow(s.get(), cap0))) return rc;
   }
@@ -355,7 +348,6 @@ int ehx_space_set_scan(ehx_space* s, uint32_t scan) {
     return fail(EHX_EUNSUPPORTED, "space '%s' was created without the filter scan copies", s->name.c_str());
   s->params.scan = scan;
   s->scan_sel = scan;
-  s->use16 = scan != EHX_SCAN_F32;
   return EHX_OK;
 }
 
@@ -458,15 +450,15 @@ int fill_synthetic_locked(ehx_space* s, uint64_t seed, uint64_t row0, uint64_t n
     for (uint64_t r0 = 0; r0 < n_rows; r0 += slab) {
       const uint64_t m = std::min<uint64_t>(slab, n_rows - r0);
       HIP_TRY(launch_gen_rows(seed, row0 + r0 * stride, m, s->dims, s->ld, normalize, tmp.p, s->stream, stride, latent));
-      HIP_TRY(launch_store_rows_f16(tmp.p, s->ld, nullptr, s->n + r0, m, s->dims, s->ld, (__half*)s->dX, s->stream));
+      HIP_TRY(launch_store_rows_f16(tmp.p, s->ld, nullptr, s->n + r0, m, s->dims, s->ld, (__half*)s->rows.dX.p, s->stream));
     }
     HIP_TRY(hipStreamSynchronize(s->stream));
     tmp.release();
   } else {
     HIP_TRY(launch_gen_rows(seed, row0, n_rows, s->dims, s->ld, normalize, (float*)s->xrow(s->n), s->stream, stride, latent));
-    if (s->x_perm) HIP_TRY(launch_permute_blocks((float*)s->dX, s->ld, s->n, n_rows, nullptr, s->stream));
+    if (s->x_perm) HIP_TRY(launch_permute_blocks((float*)s->rows.dX.p, s->ld, s->n, n_rows, nullptr, s->stream));
   }
-  HIP_TRY(launch_row_stats(s->dX, s->x_half, s->n, n_rows, s->dims, s->ld, s->metric, s->dInv, s->dRowp, s->dMaxSumsq,
+  HIP_TRY(launch_row_stats(s->rows.dX.p, s->x_half, s->n, n_rows, s->dims, s->ld, s->metric, s->rows.dInv.p, s->rows.dRowp.p, s->rows.dMaxSumsq.p,
                            s->stream, s->x_perm ? 1 : 0));
   HIP_TRY(hipStreamSynchronize(s->stream));
   if ((rc = refresh_scan16(s, s->n, n_rows, nullptr, true, s->n + n_rows))) return rc;
@@ -562,17 +554,15 @@ int ehx_graph_import(ehx_space* s, uint64_t n, const uint32_t* level0, const int
     }
   }
   HIP_TRY(hipDeviceSynchronize());
-  if (s->dAdj0) (void)hipFree(s->dAdj0);
-  if (s->dUpStart) (void)hipFree(s->dUpStart);
-  if (s->dUpLists) (void)hipFree(s->dUpLists);
-  s->dAdj0 = s->dUpStart = s->dUpLists = nullptr;
-  s->g_n = 0;
-  HIP_TRY(hipMalloc((void**)&s->dAdj0, adj.size() * 4));
-  HIP_TRY(hipMalloc((void**)&s->dUpStart, up_start.size() * 4));
-  HIP_TRY(hipMalloc((void**)&s->dUpLists, lists.size() * 4));
-  HIP_TRY(hipMemcpy(s->dAdj0, adj.data(), adj.size() * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(s->dUpStart, up_start.data(), up_start.size() * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(s->dUpLists, lists.data(), lists.size() * 4, hipMemcpyHostToDevice));
+  int rc;
+  DevBuf<uint32_t> na, nu, nl;   // (swapped in when all three are filled: a failure leaves the space's graph as it was)
+  if ((rc = na.fresh(adj.size())) || (rc = nu.fresh(up_start.size())) || (rc = nl.fresh(lists.size()))) return rc;
+  HIP_TRY(hipMemcpy(na.p, adj.data(), adj.size() * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(nu.p, up_start.data(), up_start.size() * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(nl.p, lists.data(), lists.size() * 4, hipMemcpyHostToDevice));
+  s->graph.dAdj0.swap(na);
+  s->graph.dUpStart.swap(nu);
+  s->graph.dUpLists.swap(nl);
   s->g_n = n;
   s->g_entry = entry_point;
   s->g_maxlevel = max_level;
@@ -607,7 +597,7 @@ int ehx_graph_export(ehx_space* s, uint32_t* level0, int32_t* levels, uint32_t* 
   HIP_TRY(hipDeviceSynchronize());
   if (level0) {
     std::vector<uint32_t> adj(n * M0);
-    HIP_TRY(hipMemcpy(adj.data(), s->dAdj0, adj.size() * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(adj.data(), s->graph.dAdj0.p, adj.size() * 4, hipMemcpyDeviceToHost));
     for (uint64_t i = 0; i < n; ++i) {
       uint32_t c = 0;
       for (uint32_t j = 0; j < M0; ++j) {
@@ -619,11 +609,11 @@ int ehx_graph_export(ehx_space* s, uint32_t* level0, int32_t* levels, uint32_t* 
     }
   }
   if (levels) memcpy(levels, s->h_levels.data(), n * sizeof(int32_t));
-  if (up_start) HIP_TRY(hipMemcpy(up_start, s->dUpStart, n * 4, hipMemcpyDeviceToHost));
+  if (up_start) HIP_TRY(hipMemcpy(up_start, s->graph.dUpStart.p, n * 4, hipMemcpyDeviceToHost));
   if (up_lists) {
     if (up_lists_cap < s->g_lists_used) return fail(EHX_ERANGE, "upper-list buffer too small");
     if (s->g_lists_used)
-      HIP_TRY(hipMemcpy(up_lists, s->dUpLists, s->g_lists_used * M * 4, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(up_lists, s->graph.dUpLists.p, s->g_lists_used * M * 4, hipMemcpyDeviceToHost));
   }
   return EHX_OK;
 }
@@ -673,17 +663,17 @@ int ehx_stats(ehx_space* s, ehx_stats_t* out) {
   out->n_uncertified = s->n_uncertified_final;
   out->n_i8_queries = s->n_i8_queries;
   out->n_i8_fallback = s->n_i8_fallback;
-  if (s->dGraphCounters) {
+  if (s->graph.dGraphCounters.p) {
     unsigned long long g[3] = {0, 0, 0};
-    HIP_TRY(hipMemcpy(g, s->dGraphCounters, sizeof(g), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(g, s->graph.dGraphCounters.p, sizeof(g), hipMemcpyDeviceToHost));
     out->n_dist += g[0];
     out->n_hops = g[1] + g[2];
     // n_dist*d*4 + n_hops0*(4+4*2M) + n_hops_up*(4+4*M)
     out->bytes_algorithmic += g[0] * s->dims * 4ull + g[1] * (4ull + 8ull * s->params.M) + g[2] * (4ull + 4ull * s->params.M);
   }
-  if (s->dUncert) {
+  if (s->scr.dUncert.p) {
     unsigned long long u[2] = {0, 0};
-    HIP_TRY(hipMemcpy(u, s->dUncert, sizeof(u), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(u, s->scr.dUncert.p, sizeof(u), hipMemcpyDeviceToHost));
     (void)u[0];
     if (u[1]) return fail(EHX_EINTERNAL, "scan kernel tripped its bounded-retry guard %llu times", u[1]);
   }
@@ -725,9 +715,9 @@ int ehx_graph_counters(ehx_space* s, uint64_t* out, uint32_t n_out) {
   std::lock_guard<std::mutex> sl(s->scratch_mu);
   if (s->dropped) return fail(EHX_ENOTFOUND, "Not found");
   unsigned long long g[kGraphCounters] = {};
-  if (s->dGraphCounters) {
+  if (s->graph.dGraphCounters.p) {
     HIP_TRY(hipSetDevice(s->device));
-    HIP_TRY(hipMemcpy(g, s->dGraphCounters, sizeof(g), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(g, s->graph.dGraphCounters.p, sizeof(g), hipMemcpyDeviceToHost));
   }
   for (uint32_t i = 0; i < n_out; ++i) out[i] = g[i];
   return EHX_OK;
@@ -761,8 +751,8 @@ int ehx_stats_reset(ehx_space* s) {
     std::lock_guard<std::mutex> cl(c.mu);
     c.clock.reset();
   }
-  if (s->dUncert) HIP_TRY(hipMemset(s->dUncert, 0, 2 * sizeof(unsigned long long)));
-  if (s->dGraphCounters) HIP_TRY(hipMemset(s->dGraphCounters, 0, kGraphCounters * sizeof(unsigned long long)));
+  if (s->scr.dUncert.p) HIP_TRY(hipMemset(s->scr.dUncert.p, 0, 2 * sizeof(unsigned long long)));
+  if (s->graph.dGraphCounters.p) HIP_TRY(hipMemset(s->graph.dGraphCounters.p, 0, kGraphCounters * sizeof(unsigned long long)));
   return EHX_OK;
 }
 

@@ -30,7 +30,7 @@ ScanPlan plan_scan(uint32_t nq, uint32_t n_tiles, uint32_t k, int n_cus) {
 // one flat pipeline: prepared queries -> scan -> merge -> canonical re-rank.
 //   f16 = false: the fp32 MFMA scan (k_flat8.hip), exact on its own.
 //   f16 = true : the fp16 MFMA filter scan (k_flat16.hip); per-query certification flags land in
-//                s->dUflags and the caller re-runs the unflagged remainder through the fp32 scan.
+//                s->scr.dUflags and the caller re-runs the unflagged remainder through the fp32 scan.
 int flat_pass(ehx_space* s, uint64_t n_pub, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, uint64_t* d_ids,
               float* d_dist, uint32_t* d_count, bool f16, bool count_stats) {
   Engine& E = engine();
@@ -99,25 +99,19 @@ int flat_pass(ehx_space* s, uint64_t n_pub, hipStream_t st, size_t nq, const flo
     grid_max = std::max(grid_max, ps.plan.grid);
   }
   int rc;
-  if ((rc = s->dQ.ensure((size_t)p.q_rows * s->ld))) return rc;
-  if ((rc = s->dCand.ensure((size_t)grid_max * 512 * kCandSlots))) return rc;
-  if ((rc = s->dPart.ensure((size_t)p.q_rows * lists_total * p.kprime))) return rc;
-  if ((rc = s->dMerged.ensure((size_t)p.q_rows * 64))) return rc;
-  if ((rc = s->dGthr.ensure((size_t)p.q_rows + 8))) return rc;  // +8: instrumentation slots of profiling builds
-  if (!s->dUncert) {
-    HIP_TRY(hipMalloc((void**)&s->dUncert, 2 * sizeof(unsigned long long)));  // [0] uncertified, [1] scan error
-    HIP_TRY(hipMemset(s->dUncert, 0, 2 * sizeof(unsigned long long)));
-  }
-  if ((rc = s->dUflags.ensure(p.q_rows))) return rc;
-  if (!s->dUncert16) {
-    HIP_TRY(hipMalloc((void**)&s->dUncert16, sizeof(unsigned long long)));
-    HIP_TRY(hipMemset(s->dUncert16, 0, sizeof(unsigned long long)));
-  }
+  if ((rc = s->scr.dQ.ensure((size_t)p.q_rows * s->ld))) return rc;
+  if ((rc = s->scr.dCand.ensure((size_t)grid_max * 512 * kCandSlots))) return rc;
+  if ((rc = s->scr.dPart.ensure((size_t)p.q_rows * lists_total * p.kprime))) return rc;
+  if ((rc = s->scr.dMerged.ensure((size_t)p.q_rows * 64))) return rc;
+  if ((rc = s->scr.dGthr.ensure((size_t)p.q_rows + 8))) return rc;  // +8: instrumentation slots of profiling builds
+  if ((rc = s->scr.dUncert.ensure_zeroed_once(2))) return rc;  // [0] uncertified, [1] scan error
+  if ((rc = s->scr.dUflags.ensure(p.q_rows))) return rc;
+  if ((rc = s->scr.dUncert16.ensure_zeroed_once(1))) return rc;
   if (f16) {
-    if ((rc = s->dQ16.ensure(scanq16_halves(p.q_rows, s->ld16)))) return rc;
-    if ((rc = s->dQgamma.ensure(p.q_rows))) return rc;
-    if ((rc = s->dQuv.ensure(p.q_rows))) return rc;
-    if (sample && (rc = s->dSample.ensure((size_t)kSampleTiles * kTileRows16 * p.q_rows))) return rc;
+    if ((rc = s->scr.dQ16.ensure(scanq16_halves(p.q_rows, s->ld16)))) return rc;
+    if ((rc = s->scr.dQgamma.ensure(p.q_rows))) return rc;
+    if ((rc = s->scr.dQuv.ensure(p.q_rows))) return rc;
+    if (sample && (rc = s->scr.dSample.ensure((size_t)kSampleTiles * kTileRows16 * p.q_rows))) return rc;
   }
   // scratch buffers are shared by all callers: order this pipeline after the previous one even
   // when it was enqueued on a different stream
@@ -127,34 +121,34 @@ int flat_pass(ehx_space* s, uint64_t n_pub, hipStream_t st, size_t nq, const flo
   }
   BatchClock& clock = s->clock;   // (every batch timed and in the ring; an empty space's outside it)
   if ((rc = clock.begin(st, n_pub ? 1u : BatchClock::kOutOfRing))) return rc;
-  HIP_TRY(launch_prep_queries(d_queries, (uint32_t)nq, s->dims, s->ld, p.q_rows, s->metric, s->dQ.p, st));
+  HIP_TRY(launch_prep_queries(d_queries, (uint32_t)nq, s->dims, s->ld, p.q_rows, s->metric, s->scr.dQ.p, st));
   if (f16)
-    HIP_TRY(launch_prep_queries16(d_queries, (uint32_t)nq, s->dims, s->ld16, p.q_rows, s->metric, s->dQ16.p,
-                                  s->dQgamma.p, s->dQuv.p, st));
+    HIP_TRY(launch_prep_queries16(d_queries, (uint32_t)nq, s->dims, s->ld16, p.q_rows, s->metric, s->scr.dQ16.p,
+                                  s->scr.dQgamma.p, s->scr.dQuv.p, st));
   if (n_pub == 0) {
     // empty space: every query returns count 0
-    HIP_TRY(hipMemsetAsync(s->dMerged.p, 0xFF, (size_t)p.q_rows * 64 * sizeof(uint64_t), st));
+    HIP_TRY(hipMemsetAsync(s->scr.dMerged.p, 0xFF, (size_t)p.q_rows * 64 * sizeof(uint64_t), st));
     if ((rc = clock.scan_begin(st)) || (rc = clock.scan_end(st))) return rc;
   } else {
     ScanArgs a;
-    a.Q = s->dQ.p;
-    a.X = s->dX;
+    a.Q = s->scr.dQ.p;
+    a.X = s->rows.dX.p;
     a.x_half = (uint32_t)s->x_half;
-    a.rowp = s->dRowp;
-    a.cand = s->dCand.p;
-    a.part = s->dPart.p;
+    a.rowp = s->rows.dRowp.p;
+    a.cand = s->scr.dCand.p;
+    a.part = s->scr.dPart.p;
     a.n = (uint32_t)n_pub;
     a.ld = s->ld;
     a.q_tiles = p.q_tiles;
     a.kprime = p.kprime;
     a.lists_total = lists_total;
-    a.err = (uint32_t*)(s->dUncert + 1);
-    a.gthr = (unsigned long long*)s->dGthr.p;
+    a.err = (uint32_t*)(s->scr.dUncert.p + 1);
+    a.gthr = (unsigned long long*)s->scr.dGthr.p;
     ScanArgs16 h;
-    h.Q = s->dQ16.p;
-    h.X = s->dX16;
-    h.rowp = s->dRowp16;
-    h.qgamma = s->dQgamma.p;
+    h.Q = s->scr.dQ16.p;
+    h.X = s->f16.dX16.p;
+    h.rowp = s->f16.dRowp16.p;
+    h.qgamma = s->scr.dQgamma.p;
     h.eps = scan16_eps(s->dims);
     h.cos = s->metric == EHX_METRIC_COSINE;
     h.cand = a.cand;
@@ -184,35 +178,35 @@ int flat_pass(ehx_space* s, uint64_t n_pub, hipStream_t st, size_t nq, const flo
       a.list0 = list0;
       return launch_flat_scan(a, st);
     };
-    HIP_TRY(hipMemsetAsync(s->dGthr.p, 0xFF, (size_t)p.q_rows * sizeof(uint64_t), st));
+    HIP_TRY(hipMemsetAsync(s->scr.dGthr.p, 0xFF, (size_t)p.q_rows * sizeof(uint64_t), st));
     if ((rc = clock.scan_begin(st))) return rc;
     if (sample) {
       ScanPlan sp = plan_scan((uint32_t)nq, kSampleTiles, k, E.n_cus);
       sp.kprime = p.kprime;
-      h.dump = s->dSample.p;
+      h.dump = s->scr.dSample.p;
       HIP_TRY(scan(sp, 0, 0));
       h.dump = nullptr;
-      HIP_TRY(launch_sample_select(s->dSample.p, kSampleTiles * kTileRows16, p.q_rows, (uint32_t)nq, p.kprime,
-                                   (unsigned long long*)s->dGthr.p, st));
+      HIP_TRY(launch_sample_select(s->scr.dSample.p, kSampleTiles * kTileRows16, p.q_rows, (uint32_t)nq, p.kprime,
+                                   (unsigned long long*)s->scr.dGthr.p, st));
     }
     for (size_t i = 0; i < passes.size(); ++i) {
       const bool last = i + 1 == passes.size();
       HIP_TRY(scan(passes[i].plan, passes[i].tile0, 0));
       if (last && (rc = clock.scan_end(st))) return rc;   // (the final merge is outside the timed scan phase)
-      HIP_TRY(launch_flat_merge(s->dPart.p, (uint32_t)nq, passes[i].plan.n_chunks * lpc, p.kprime, s->dMerged.p, st,
-                                lists_total, i > 0, last ? nullptr : (unsigned long long*)s->dGthr.p));
+      HIP_TRY(launch_flat_merge(s->scr.dPart.p, (uint32_t)nq, passes[i].plan.n_chunks * lpc, p.kprime, s->scr.dMerged.p, st,
+                                lists_total, i > 0, last ? nullptr : (unsigned long long*)s->scr.dGthr.p));
     }
   }
   RerankArgs r;
-  r.Q = s->dQ.p;
-  r.X = s->dX;
+  r.Q = s->scr.dQ.p;
+  r.X = s->rows.dX.p;
   r.x_half = (uint32_t)s->x_half;
-  r.inv_norm = s->dInv;
-  r.merged = s->dMerged.p;
+  r.inv_norm = s->rows.dInv.p;
+  r.merged = s->scr.dMerged.p;
   r.out_ids = d_ids;
   r.out_dist = d_dist;
   r.out_count = d_count;
-  r.n_uncertified = s->dUncert16;  // verdict counter of this pass (the caller reads and clears it)
+  r.n_uncertified = s->scr.dUncert16.p;  // verdict counter of this pass (the caller reads and clears it)
   r.nq = (uint32_t)nq;
   r.k = k;
   r.kprime = p.kprime;
@@ -220,9 +214,9 @@ int flat_pass(ehx_space* s, uint64_t n_pub, hipStream_t st, size_t nq, const flo
   r.dims = s->dims;
   r.ld = s->ld;
   r.metric = s->metric;
-  if (f16) r.quv = s->dQuv.p;
-  r.max_sumsq = s->dMaxSumsq;
-  r.uncert_flags = s->dUflags.p;
+  if (f16) r.quv = s->scr.dQuv.p;
+  r.max_sumsq = s->rows.dMaxSumsq.p;
+  r.uncert_flags = s->scr.dUflags.p;
   HIP_TRY(launch_rerank(r, st));
   if ((rc = clock.finish(st))) return rc;
   if (count_stats) count_scan_batch(s, nq, n_pub, k, f16 ? 2 : s->esz);
@@ -243,7 +237,7 @@ int resolve_engine(const ehx_space* s, uint64_t n_pub) {
 // The int8 filter pipeline (k_flati8.hip, k_select.hip): prepared queries -> sample pass (first thresholds) ->
 // cascade of collect passes, x4 in rows, each followed by select256 (running best 256 + the next threshold) ->
 // rerank256 (canonical distances of the k' = 128 best lower bounds, top-k, certificate).  Per-query verdicts land in
-// s->dUflags / s->dUncert16 like those of flat_pass.
+// s->scr.dUflags / s->scr.dUncert16.p like those of flat_pass.
 // `set`: which of the space's two scratch sets (ehx_space::I8Set) this batch runs in; the caller holds that set's mutex.
 int flat_pass8(ehx_space* s, uint64_t n_pub, int set, hipStream_t st, size_t nq, const float* d_queries, uint32_t k,
                uint64_t* d_ids, float* d_dist, uint32_t* d_count, bool count_stats, uint32_t* kprime_used) {
@@ -351,42 +345,39 @@ int flat_pass8(ehx_space* s, uint64_t n_pub, int set, hipStream_t st, size_t nq,
   }
   if (chunks_max > 256) return fail(EHX_EINTERNAL, "scan plan with %u chunks", chunks_max);
   int rc;
-  if ((rc = sc.dQ.ensure((size_t)p.q_rows * s->ld))) return rc;
-  if ((rc = sc.dQ8.ensure(scanq8_bytes(p.q_rows, s->ld8)))) return rc;
-  if ((rc = sc.dQp8.ensure(p.q_rows))) return rc;
-  if ((rc = sc.dQuv.ensure(p.q_rows))) return rc;
-  if ((rc = sc.dThr8.ensure(p.q_rows))) return rc;
-  if ((rc = sc.dSample8.ensure((size_t)kSampleTiles * kTileRows16 * p.q_rows))) return rc;
-  if ((rc = sc.dCnt.ensure(8, true))) return rc;   // (the set's own: this function runs outside the pipeline lock too)
-  if ((rc = sc.dPool.ensure((size_t)p.q_rows * kPoolCap))) return rc;
-  if ((rc = sc.dMerged8.ensure((size_t)p.q_rows * width))) return rc;
-  if ((rc = sc.dI8Ctl.ensure((size_t)p.q_rows * 2 + kSyncWordsI8))) return rc;
-  if ((rc = sc.dUflags.ensure(p.q_rows))) return rc;
-  if (!sc.dUncert) {
-    HIP_TRY(hipMalloc((void**)&sc.dUncert, sizeof(unsigned long long)));
-    HIP_TRY(hipMemset(sc.dUncert, 0, sizeof(unsigned long long)));
-    HIP_TRY(hipHostMalloc((void**)&sc.hUncertPin, sizeof(unsigned long long), hipHostMallocDefault));
-  }
-  uint32_t* pool_cnt = sc.dI8Ctl.p;
-  uint32_t* ovf = sc.dI8Ctl.p + p.q_rows;
-  uint32_t* sync = sc.dI8Ctl.p + 2 * (size_t)p.q_rows;
-  if (!sc.verdict) HIP_TRY(hipEventCreateWithFlags(&sc.verdict, hipEventBlockingSync | hipEventDisableTiming));
+  if ((rc = sc.buf.dQ.ensure((size_t)p.q_rows * s->ld))) return rc;
+  if ((rc = sc.buf.dQ8.ensure(scanq8_bytes(p.q_rows, s->ld8)))) return rc;
+  if ((rc = sc.buf.dQp8.ensure(p.q_rows))) return rc;
+  if ((rc = sc.buf.dQuv.ensure(p.q_rows))) return rc;
+  if ((rc = sc.buf.dThr8.ensure(p.q_rows))) return rc;
+  if ((rc = sc.buf.dSample8.ensure((size_t)kSampleTiles * kTileRows16 * p.q_rows))) return rc;
+  if ((rc = sc.buf.dCnt.ensure(8, true))) return rc;   // (the set's own: this function runs outside the pipeline lock too)
+  if ((rc = sc.buf.dPool.ensure((size_t)p.q_rows * kPoolCap))) return rc;
+  if ((rc = sc.buf.dMerged8.ensure((size_t)p.q_rows * width))) return rc;
+  if ((rc = sc.buf.dI8Ctl.ensure((size_t)p.q_rows * 2 + kSyncWordsI8))) return rc;
+  if ((rc = sc.buf.dUflags.ensure(p.q_rows))) return rc;
+  if ((rc = sc.buf.dUncert.ensure_zeroed_once(1))) return rc;
+  if ((rc = sc.buf.hUncertPin.ensure(1))) return rc;
+  uint32_t* pool_cnt = sc.buf.dI8Ctl.p;
+  uint32_t* ovf = sc.buf.dI8Ctl.p + p.q_rows;
+  uint32_t* sync = sc.buf.dI8Ctl.p + 2 * (size_t)p.q_rows;
+  if ((rc = sc.buf.verdict.ensure(hipEventBlockingSync | hipEventDisableTiming))) return rc;
   // (a caller's stream other than the space's own: searches already in flight there and here finish first)
   if ((rc = wait_searches_in_flight(s, st))) return rc;
   if ((rc = sc.clock.begin(st, env().stats_every))) return rc;
-  HIP_TRY(launch_prep_queries_i8(d_queries, (uint32_t)nq, s->dims, s->ld, s->ld8, p.q_rows, s->metric, sc.dQ.p,
-                                 sc.dQ8.p, sc.dQp8.p, sc.dQuv.p, sc.dThr8.p, sc.dI8Ctl.p, st));
+  HIP_TRY(launch_prep_queries_i8(d_queries, (uint32_t)nq, s->dims, s->ld, s->ld8, p.q_rows, s->metric, sc.buf.dQ.p,
+                                 sc.buf.dQ8.p, sc.buf.dQp8.p, sc.buf.dQuv.p, sc.buf.dThr8.p, sc.buf.dI8Ctl.p, st));
   ScanArgsI8 a;
-  a.Q = sc.dQ8.p;
-  a.X = s->dX8;
-  a.rowp = s->dRowp8;
-  a.tilep = s->dTilep8;
-  a.tileg = s->dTileg8;
-  a.perm = s->dPerm8;
-  a.qparams = sc.dQp8.p;
-  a.thr = sc.dThr8.p;
-  a.cand = sc.dCnt.p;
-  a.pool = sc.dPool.p;
+  a.Q = sc.buf.dQ8.p;
+  a.X = s->i8.dX8.p;
+  a.rowp = s->i8.dRowp8.p;
+  a.tilep = s->i8.dTilep8.p;
+  a.tileg = s->i8.dTileg8.p;
+  a.perm = s->i8.dPerm8.p;
+  a.qparams = sc.buf.dQp8.p;
+  a.thr = sc.buf.dThr8.p;
+  a.cand = sc.buf.dCnt.p;
+  a.pool = sc.buf.dPool.p;
   a.pool_cnt = pool_cnt;
   a.ovf = ovf;
   a.pool_cap = kPoolCap;
@@ -408,12 +399,12 @@ int flat_pass8(ehx_space* s, uint64_t n_pub, int set, hipStream_t st, size_t nq,
   if ((rc = sc.clock.scan_begin(st))) return rc;
   {  // sample pass: lower bounds of the first 2048 rows -> thr[q] = the k'-th best of them
     ScanPlan sp = plan_scan((uint32_t)nq, kSampleTiles, k, E.n_cus);
-    a.dump = sc.dSample8.p;
+    a.dump = sc.buf.dSample8.p;
     a.sync = nullptr;
     HIP_TRY(scan(sp, 0));
     a.dump = nullptr;
-    HIP_TRY(launch_sample_select256(sc.dSample8.p, kSampleTiles * kTileRows16, p.q_rows, (uint32_t)nq, sample_rank,
-                                    sc.dThr8.p, st));
+    HIP_TRY(launch_sample_select256(sc.buf.dSample8.p, kSampleTiles * kTileRows16, p.q_rows, (uint32_t)nq, sample_rank,
+                                    sc.buf.dThr8.p, st));
   }
   for (size_t i = 0; i < passes.size(); ++i) {
     const bool last = i + 1 == passes.size();
@@ -427,25 +418,25 @@ int flat_pass8(ehx_space* s, uint64_t n_pub, int set, hipStream_t st, size_t nq,
     HIP_TRY(scan(passes[i].plan, passes[i].tile0));
     // (the last select and the re-rank are outside the timed scan phase, like flat_pass's final merge)
     if (last && (rc = sc.clock.scan_end(st))) return rc;
-    HIP_TRY(launch_select256(sc.dPool.p, pool_cnt, kPoolCap, (uint32_t)nq, rank_after(i), sc.dMerged8.p, width, i > 0,
-                             sc.dThr8.p, sc.dQp8.p, st));
+    HIP_TRY(launch_select256(sc.buf.dPool.p, pool_cnt, kPoolCap, (uint32_t)nq, rank_after(i), sc.buf.dMerged8.p, width, i > 0,
+                             sc.buf.dThr8.p, sc.buf.dQp8.p, st));
   }
   Rerank256Args r;
-  r.Q = sc.dQ.p;
-  r.X = s->dX;
+  r.Q = sc.buf.dQ.p;
+  r.X = s->rows.dX.p;
   r.x_half = (uint32_t)s->x_half;
-  r.inv_norm = s->dInv;
-  r.merged = sc.dMerged8.p;
+  r.inv_norm = s->rows.dInv.p;
+  r.merged = sc.buf.dMerged8.p;
   r.width = width;
   r.ovf = ovf;
-  r.quv = sc.dQuv.p;
-  r.qparams = sc.dQp8.p;
-  r.max_sumsq = s->dMaxSumsq;
+  r.quv = sc.buf.dQuv.p;
+  r.qparams = sc.buf.dQp8.p;
+  r.max_sumsq = s->rows.dMaxSumsq.p;
   r.out_ids = d_ids;
   r.out_dist = d_dist;
   r.out_count = d_count;
-  r.n_uncertified = sc.dUncert;
-  r.uncert_flags = sc.dUflags.p;
+  r.n_uncertified = sc.buf.dUncert.p;
+  r.uncert_flags = sc.buf.dUflags.p;
   r.nq = (uint32_t)nq;
   r.k = k;
   r.kprime = kprime;
@@ -457,7 +448,7 @@ int flat_pass8(ehx_space* s, uint64_t n_pub, int set, hipStream_t st, size_t nq,
   if (env().i8_count) {  // diagnosis builds (-DEHX_I8_COUNT=1): the scan's epilogue counters of this batch
     unsigned long long c[8] = {0};
     HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipMemcpy(c, sc.dCnt.p, sizeof(c), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(c, sc.buf.dCnt.p, sizeof(c), hipMemcpyDeviceToHost));
     fprintf(stderr, "[i8 count] tests %llu alarms %llu row-block alarms %llu trips %llu (cumulative)\n", c[0], c[1], c[2], c[3]);
   }
   if (env().i8_debug) {  // diagnosis only: what the uncertified queries of this batch look like
@@ -467,11 +458,11 @@ int flat_pass8(ehx_space* s, uint64_t n_pub, int set, hipStream_t st, size_t nq,
     std::vector<float2> uv(nq);
     std::vector<uint64_t> mg(nq * width);
     std::vector<float> od(nq * k);
-    HIP_TRY(hipMemcpy(fl.data(), sc.dUflags.p, nq * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(fl.data(), sc.buf.dUflags.p, nq * 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(ov.data(), ovf, nq * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(qp.data(), sc.dQp8.p, nq * sizeof(float4), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(uv.data(), sc.dQuv.p, nq * sizeof(float2), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(mg.data(), sc.dMerged8.p, nq * width * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(qp.data(), sc.buf.dQp8.p, nq * sizeof(float4), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(uv.data(), sc.buf.dQuv.p, nq * sizeof(float2), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(mg.data(), sc.buf.dMerged8.p, nq * width * 8, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(od.data(), d_dist, nq * k * 4, hipMemcpyDeviceToHost));
     int shown = 0;
     for (size_t q = 0; q < nq && shown < 6; ++q) {
@@ -501,39 +492,36 @@ int exhaustive_pass(ehx_space* s, uint64_t n_pub, hipStream_t st, size_t nq, con
   const uint32_t n_blocks = (uint32_t)((n_pub + kRowsPerBlock - 1) / kRowsPerBlock);
   const uint32_t pages = (k + 63) / 64;
   int rc;
-  if ((rc = s->dQ.ensure(nq * s->ld))) return rc;
-  if ((rc = s->dPart.ensure(nq * n_blocks * 64))) return rc;
-  if ((rc = s->dMerged.ensure(nq * 64))) return rc;
-  if ((rc = s->dUflags.ensure(nq))) return rc;
-  if (pages > 1 && (rc = s->dGthr.ensure(nq + 8))) return rc;
-  if (!s->dUncert16) {
-    HIP_TRY(hipMalloc((void**)&s->dUncert16, sizeof(unsigned long long)));
-    HIP_TRY(hipMemset(s->dUncert16, 0, sizeof(unsigned long long)));
-  }
+  if ((rc = s->scr.dQ.ensure(nq * s->ld))) return rc;
+  if ((rc = s->scr.dPart.ensure(nq * n_blocks * 64))) return rc;
+  if ((rc = s->scr.dMerged.ensure(nq * 64))) return rc;
+  if ((rc = s->scr.dUflags.ensure(nq))) return rc;
+  if (pages > 1 && (rc = s->scr.dGthr.ensure(nq + 8))) return rc;
+  if ((rc = s->scr.dUncert16.ensure_zeroed_once(1))) return rc;
   {
     int rcw = wait_searches_in_flight(s, st);
     if (rcw) return rcw;
   }
   if ((rc = s->clock.begin(st, BatchClock::kOutOfRing))) return rc;
-  HIP_TRY(launch_prep_queries(d_queries, (uint32_t)nq, s->dims, s->ld, (uint32_t)nq, s->metric, s->dQ.p, st));
+  HIP_TRY(launch_prep_queries(d_queries, (uint32_t)nq, s->dims, s->ld, (uint32_t)nq, s->metric, s->scr.dQ.p, st));
   if ((rc = s->clock.scan_begin(st))) return rc;
   for (uint32_t pg = 0; pg < pages; ++pg) {
     if (pg) test_pause();
-    const uint64_t* floor = pg ? s->dGthr.p : nullptr;
-    HIP_TRY(launch_exhaustive(s->dQ.p, s->dX, s->x_half, s->dInv, (uint32_t)n_pub, s->dims, s->ld, s->metric,
-                              kRowsPerBlock, n_blocks, (uint32_t)nq, floor, s->dPart.p, st));
-    HIP_TRY(launch_flat_merge(s->dPart.p, (uint32_t)nq, n_blocks, 64, s->dMerged.p, st, n_blocks));
-    if (pg + 1 < pages) HIP_TRY(launch_set_floor(s->dMerged.p, (uint32_t)nq, s->dGthr.p, st));
+    const uint64_t* floor = pg ? s->scr.dGthr.p : nullptr;
+    HIP_TRY(launch_exhaustive(s->scr.dQ.p, s->rows.dX.p, s->x_half, s->rows.dInv.p, (uint32_t)n_pub, s->dims, s->ld, s->metric,
+                              kRowsPerBlock, n_blocks, (uint32_t)nq, floor, s->scr.dPart.p, st));
+    HIP_TRY(launch_flat_merge(s->scr.dPart.p, (uint32_t)nq, n_blocks, 64, s->scr.dMerged.p, st, n_blocks));
+    if (pg + 1 < pages) HIP_TRY(launch_set_floor(s->scr.dMerged.p, (uint32_t)nq, s->scr.dGthr.p, st));
     RerankArgs r;
-    r.Q = s->dQ.p;
-    r.X = s->dX;
+    r.Q = s->scr.dQ.p;
+    r.X = s->rows.dX.p;
     r.x_half = (uint32_t)s->x_half;
-    r.inv_norm = s->dInv;
-    r.merged = s->dMerged.p;
+    r.inv_norm = s->rows.dInv.p;
+    r.merged = s->scr.dMerged.p;
     r.out_ids = d_ids;
     r.out_dist = d_dist;
     r.out_count = d_count;
-    r.n_uncertified = s->dUncert16;
+    r.n_uncertified = s->scr.dUncert16.p;
     r.nq = (uint32_t)nq;
     r.k = std::min<uint32_t>(64, k - pg * 64);
     r.kprime = 64;
@@ -541,7 +529,7 @@ int exhaustive_pass(ehx_space* s, uint64_t n_pub, hipStream_t st, size_t nq, con
     r.dims = s->dims;
     r.ld = s->ld;
     r.metric = s->metric;
-    r.uncert_flags = s->dUflags.p;
+    r.uncert_flags = s->scr.dUflags.p;
     r.exact_keys = 1;
     r.out_stride = k;
     r.out_offset = pg * 64;
@@ -644,7 +632,7 @@ int knn_device_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_qu
     s->n_queries += nq;
     s->n_exhaustive += nq;
     HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipMemsetAsync(s->dUncert16, 0, sizeof(unsigned long long), st));
+    HIP_TRY(hipMemsetAsync(s->scr.dUncert16.p, 0, sizeof(unsigned long long), st));
     return EHX_OK;
   }
   // ONE query against a small shard — the reference's own usage: one NearestNeighbor RPC, one query (server.cc:172-210;
@@ -658,7 +646,7 @@ int knn_device_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_qu
     if (rc2) return rc2;
     s->n_queries += nq;
     s->n_exhaustive += nq;
-    if (s->dUncert16) HIP_TRY(hipMemsetAsync(s->dUncert16, 0, sizeof(unsigned long long), st));
+    if (s->scr.dUncert16.p) HIP_TRY(hipMemsetAsync(s->scr.dUncert16.p, 0, sizeof(unsigned long long), st));
     return EHX_OK;   // (no wait here: the caller's copy-back or stream order is the wait)
   }
   constexpr size_t kMaxExhaustive = 32;
@@ -674,18 +662,18 @@ int knn_device_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_qu
     float* od = d_dist;
     uint32_t* oc = d_count;
     if (subset) {
-      if ((rc = s->dFbQ.ensure(m * s->dims))) return rc;
-      if ((rc = s->dFbIds.ensure(m * k))) return rc;
-      if ((rc = s->dFbDist.ensure(m * k))) return rc;
-      if ((rc = s->dFbCnt.ensure(m))) return rc;
-      if ((rc = s->dFbIdx.ensure(m))) return rc;
+      if ((rc = s->scr.dFbQ.ensure(m * s->dims))) return rc;
+      if ((rc = s->scr.dFbIds.ensure(m * k))) return rc;
+      if ((rc = s->scr.dFbDist.ensure(m * k))) return rc;
+      if ((rc = s->scr.dFbCnt.ensure(m))) return rc;
+      if ((rc = s->scr.dFbIdx.ensure(m))) return rc;
       // (the index list comes from pageable host memory: the runtime stages it before the call returns)
-      HIP_TRY(hipMemcpyAsync(s->dFbIdx.p, subset->data(), m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-      HIP_TRY(launch_gather_queries(d_queries, s->dFbIdx.p, (uint32_t)m, s->dims, s->dFbQ.p, st));
-      q = s->dFbQ.p;
-      oi = s->dFbIds.p;
-      od = s->dFbDist.p;
-      oc = s->dFbCnt.p;
+      HIP_TRY(hipMemcpyAsync(s->scr.dFbIdx.p, subset->data(), m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+      HIP_TRY(launch_gather_queries(d_queries, s->scr.dFbIdx.p, (uint32_t)m, s->dims, s->scr.dFbQ.p, st));
+      q = s->scr.dFbQ.p;
+      oi = s->scr.dFbIds.p;
+      od = s->scr.dFbDist.p;
+      oc = s->scr.dFbCnt.p;
     }
     // (the int8 stage runs in scratch set 0 here, held for the stage and its verdict: host batches may be using both sets
     // through knn_host_direct's pipelined path at the same time)
@@ -698,19 +686,19 @@ int knn_device_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_qu
     }
     else rc = flat_pass(s, n_pub, st, m, q, k, oi, od, oc, kind == kFilter, count_stats);
     if (rc) return rc;
-    unsigned long long* d_unc = kind == kI8 ? s->i8set[0].dUncert : s->dUncert16;
-    const uint32_t* d_flags = kind == kI8 ? s->i8set[0].dUflags.p : s->dUflags.p;
+    unsigned long long* d_unc = kind == kI8 ? s->i8set[0].buf.dUncert.p : s->scr.dUncert16.p;
+    const uint32_t* d_flags = kind == kI8 ? s->i8set[0].buf.dUflags.p : s->scr.dUflags.p;
     if (subset) {
-      HIP_TRY(launch_scatter_results(oi, od, oc, s->dFbIdx.p, (uint32_t)m, k, d_ids, d_dist, d_count, st));
+      HIP_TRY(launch_scatter_results(oi, od, oc, s->scr.dFbIdx.p, (uint32_t)m, k, d_ids, d_dist, d_count, st));
       if ((rc = s->clock.extend(st))) return rc;   // (the scatter is part of the pass's batch: writers wait for it too)
     }
     // verdict
     unc->clear();
     // (into PINNED host memory: a copy to pageable memory goes through a staging buffer and a copy kernel)
-    if (!s->hUncertPin) HIP_TRY(hipHostMalloc((void**)&s->hUncertPin, sizeof(unsigned long long), hipHostMallocDefault));
-    HIP_TRY(hipMemcpyAsync(s->hUncertPin, d_unc, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    if ((rc = s->scr.hUncertPin.ensure(1))) return rc;
+    HIP_TRY(hipMemcpyAsync(s->scr.hUncertPin.p, d_unc, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    const unsigned long long n_unc = *s->hUncertPin;
+    const unsigned long long n_unc = *s->scr.hUncertPin.p;
 #if defined(EHX_ABL) && EHX_ABL
     return EHX_OK;  // profiling builds with ablated (wrong-by-construction) kernels: time the first stage only
 #endif

@@ -10,40 +10,38 @@ namespace ehx_impl {
 // the round (the analogue of hnswlib's multi-threaded add_items).
 int graph_ensure_arrays(ehx_space* s) {
   const uint32_t M0 = 2 * s->params.M;
-  if (s->g_cap_rows >= s->cap && s->dAdj0) return EHX_OK;
+  if (s->g_cap_rows >= s->cap && s->graph.dAdj0.p) return EHX_OK;
   HIP_TRY(hipDeviceSynchronize());
-  uint32_t* na = nullptr;
-  uint32_t* nu = nullptr;
-  HIP_TRY(hipMalloc((void**)&na, s->cap * M0 * sizeof(uint32_t)));
-  HIP_TRY(hipMalloc((void**)&nu, s->cap * sizeof(uint32_t)));
-  HIP_TRY(hipMemset(na, 0xFF, s->cap * M0 * sizeof(uint32_t)));
-  HIP_TRY(hipMemset(nu, 0xFF, s->cap * sizeof(uint32_t)));
-  if (s->dAdj0 && s->g_n) {
-    HIP_TRY(hipMemcpy(na, s->dAdj0, s->g_n * M0 * sizeof(uint32_t), hipMemcpyDeviceToDevice));
-    HIP_TRY(hipMemcpy(nu, s->dUpStart, s->g_n * sizeof(uint32_t), hipMemcpyDeviceToDevice));
+  DevBuf<uint32_t> na, nu;   // (built here, swapped in when everything has succeeded: the old arrays die with these)
+  int rc;
+  if ((rc = na.fresh(s->cap * M0))) return rc;
+  if ((rc = nu.fresh(s->cap))) return rc;
+  HIP_TRY(hipMemset(na.p, 0xFF, s->cap * M0 * sizeof(uint32_t)));
+  HIP_TRY(hipMemset(nu.p, 0xFF, s->cap * sizeof(uint32_t)));
+  if (s->graph.dAdj0.p && s->g_n) {
+    HIP_TRY(hipMemcpy(na.p, s->graph.dAdj0.p, s->g_n * M0 * sizeof(uint32_t), hipMemcpyDeviceToDevice));
+    HIP_TRY(hipMemcpy(nu.p, s->graph.dUpStart.p, s->g_n * sizeof(uint32_t), hipMemcpyDeviceToDevice));
   }
   HIP_TRY(hipStreamSynchronize(nullptr));  // (fills and copies above ran on the NULL stream; ours are non-blocking)
-  if (s->dAdj0) (void)hipFree(s->dAdj0);
-  if (s->dUpStart) (void)hipFree(s->dUpStart);
-  s->dAdj0 = na;
-  s->dUpStart = nu;
+  s->graph.dAdj0.swap(na);
+  s->graph.dUpStart.swap(nu);
   s->g_cap_rows = s->cap;
   return EHX_OK;
 }
 
 int graph_ensure_lists(ehx_space* s, uint64_t lists) {
-  if (lists <= s->g_lists_cap && s->dUpLists) return EHX_OK;
+  if (lists <= s->g_lists_cap && s->graph.dUpLists.p) return EHX_OK;
   uint64_t want = s->g_lists_cap ? s->g_lists_cap : 1024;
   while (want < lists) want *= 2;
   HIP_TRY(hipDeviceSynchronize());
-  uint32_t* nl = nullptr;
-  HIP_TRY(hipMalloc((void**)&nl, want * s->params.M * sizeof(uint32_t)));
-  HIP_TRY(hipMemset(nl, 0xFF, want * s->params.M * sizeof(uint32_t)));
-  if (s->dUpLists && s->g_lists_used)
-    HIP_TRY(hipMemcpy(nl, s->dUpLists, s->g_lists_used * s->params.M * sizeof(uint32_t), hipMemcpyDeviceToDevice));
+  DevBuf<uint32_t> nl;
+  int rc;
+  if ((rc = nl.fresh(want * s->params.M))) return rc;
+  HIP_TRY(hipMemset(nl.p, 0xFF, want * s->params.M * sizeof(uint32_t)));
+  if (s->graph.dUpLists.p && s->g_lists_used)
+    HIP_TRY(hipMemcpy(nl.p, s->graph.dUpLists.p, s->g_lists_used * s->params.M * sizeof(uint32_t), hipMemcpyDeviceToDevice));
   HIP_TRY(hipStreamSynchronize(nullptr));
-  if (s->dUpLists) (void)hipFree(s->dUpLists);
-  s->dUpLists = nl;
+  s->graph.dUpLists.swap(nl);
   s->g_lists_cap = want;
   return EHX_OK;
 }
@@ -94,7 +92,7 @@ int graph_insert(ehx_space* s, uint64_t id0, uint64_t count, uint32_t batch) {
     if (level > top) top = level;
   }
   if ((rc = graph_ensure_lists(s, s->g_lists_used + new_lists))) return undo(rc);
-  if ((rc = s->dInsLevels.ensure(count))) return undo(rc);
+  if ((rc = s->graph.dInsLevels.ensure(count))) return undo(rc);
   // ---- round schedule ----
   const uint64_t round_cap = batch > 1 ? batch : 4096;
   // Rows of one round do not see each other, so a round never exceeds a small share of the graph it joins: 1/128, at
@@ -130,32 +128,32 @@ int graph_insert(ehx_space* s, uint64_t id0, uint64_t count, uint32_t batch) {
   const uint64_t max_pairs = max_P * (uint64_t)(top + 1) * M;
   if (max_pairs >= 0xFFFFFFFFull) return undo(fail(EHX_EUNSUPPORTED, "graph build: round too large"));
   // (the bitmaps are zero when allocated and every search clears the bits it set: no per-round memset)
-  if ((rc = s->dVisited.ensure(max_P * vis_words, true))) return undo(rc);
-  if ((rc = s->dInsVislog.ensure(max_P * (uint64_t)vislog_cap))) return undo(rc);
-  if ((rc = s->dLinkHead.ensure(s->cap + s->g_lists_cap, true))) return undo(rc);  // all zero between rounds
-  if ((rc = s->dLinkNext.ensure(max_pairs))) return undo(rc);
-  if ((rc = s->dLinkTouched.ensure(max_pairs))) return undo(rc);
-  if ((rc = s->dLinkCount.ensure(n_rounds))) return undo(rc);
+  if ((rc = s->graph.dVisited.ensure(max_P * vis_words, true))) return undo(rc);
+  if ((rc = s->graph.dInsVislog.ensure(max_P * (uint64_t)vislog_cap))) return undo(rc);
+  if ((rc = s->graph.dLinkHead.ensure(s->cap + s->g_lists_cap, true))) return undo(rc);  // all zero between rounds
+  if ((rc = s->graph.dLinkNext.ensure(max_pairs))) return undo(rc);
+  if ((rc = s->graph.dLinkTouched.ensure(max_pairs))) return undo(rc);
+  if ((rc = s->graph.dLinkCount.ensure(n_rounds))) return undo(rc);
   // ---- commit: from here on the rows are on their way into the graph ----
   s->g_lists_used += new_lists;
   s->h_levels.insert(s->h_levels.end(), h_lv.begin(), h_lv.end());
   // the new nodes' up_start entries and levels (their adjacency rows are still all-0xFF; nothing reaches a node
   // before the round that links it)
-  HIP_TRY(hipMemcpyAsync(s->dUpStart + id0, h_upstart.data(), count * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(s->dInsLevels.p, h_lv.data(), count * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(s->graph.dUpStart.p + id0, h_upstart.data(), count * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(s->graph.dInsLevels.p, h_lv.data(), count * sizeof(int32_t), hipMemcpyHostToDevice, st));
   if (s->vis_dirty) {  // a search that clears its bitmaps before its kernel left them marked
-    HIP_TRY(hipMemsetAsync(s->dVisited.p, 0, s->dVisited.n * sizeof(uint32_t), st));
+    HIP_TRY(hipMemsetAsync(s->graph.dVisited.p, 0, s->graph.dVisited.n * sizeof(uint32_t), st));
     s->vis_dirty = false;
   }
-  HIP_TRY(hipMemsetAsync(s->dLinkCount.p, 0, n_rounds * sizeof(uint32_t), st));
+  HIP_TRY(hipMemsetAsync(s->graph.dLinkCount.p, 0, n_rounds * sizeof(uint32_t), st));
   InsertArgs a{};  // (zeroed: a null link_head / sel switches those outputs off in the kernels)
-  a.Xs = s->dXs;
-  a.xscale = (s->x_perm && s->metric == EHX_METRIC_COSINE) ? s->dInv : nullptr;
-  a.adj0 = s->dAdj0;
-  a.up_start = s->dUpStart;
-  a.up_lists = s->dUpLists;
-  a.visited = s->dVisited.p;
-  a.vislog = s->dInsVislog.p;
+  a.Xs = s->xs();
+  a.xscale = (s->x_perm && s->metric == EHX_METRIC_COSINE) ? s->rows.dInv.p : nullptr;
+  a.adj0 = s->graph.dAdj0.p;
+  a.up_start = s->graph.dUpStart.p;
+  a.up_lists = s->graph.dUpLists.p;
+  a.visited = s->graph.dVisited.p;
+  a.vislog = s->graph.dInsVislog.p;
   a.new_ids = nullptr;
   a.sel = nullptr;
   a.ef = efc;
@@ -168,9 +166,9 @@ int graph_insert(ehx_space* s, uint64_t id0, uint64_t count, uint32_t batch) {
   a.metric = s->metric;
   a.exclude_self = 0;
   a.head_rows = (uint32_t)s->cap;
-  a.link_head = s->dLinkHead.p;
-  a.link_next = s->dLinkNext.p;
-  a.link_touched = (uint2*)s->dLinkTouched.p;
+  a.link_head = s->graph.dLinkHead.p;
+  a.link_next = s->graph.dLinkNext.p;
+  a.link_touched = (uint2*)s->graph.dLinkTouched.p;
   // EHX_BUILD_TRACE=1: progress to stderr (costs a stream synchronisation every 128 rounds)
   const bool trace = env().build_trace;
   const auto t_build0 = std::chrono::steady_clock::now();
@@ -186,11 +184,11 @@ int graph_insert(ehx_space* s, uint64_t id0, uint64_t count, uint32_t batch) {
     }
     const uint64_t P = round_size(s->g_n, end - pos);
     a.id0 = (uint32_t)pos;
-    a.new_levels = s->dInsLevels.p + (pos - id0);
+    a.new_levels = s->graph.dInsLevels.p + (pos - id0);
     a.max_sel_levels = (uint32_t)s->g_maxlevel + 1;
     a.entry_point = s->g_entry;
     a.max_level = s->g_maxlevel;
-    a.link_count = s->dLinkCount.p + round;
+    a.link_count = s->graph.dLinkCount.p + round;
     HIP_TRY(launch_insert_search(a, (uint32_t)P, st));
     const uint64_t pairs = P * a.max_sel_levels * M;
     HIP_TRY(launch_insert_link_dev(a, (uint32_t)std::min<uint64_t>(pairs, 32768), st));
@@ -218,13 +216,13 @@ int graph_insert(ehx_space* s, uint64_t id0, uint64_t count, uint32_t batch) {
   // zeroed, at its first call: ~1 ms).  Streamed Sets (small calls) keep theirs.
   // (EHX_BUILD_SCRATCH_KEEP=<bytes>: what a build may keep, whatever its size — tests release at small sizes with 0)
   const long long keep_env = env().build_scratch_keep;
-  const bool give_back = keep_env >= 0 ? s->dVisited.n * sizeof(uint32_t) > (unsigned long long)keep_env
-                                       : (end - id0 >= 65536 && s->dVisited.n * sizeof(uint32_t) > (1ull << 30));
+  const bool give_back = keep_env >= 0 ? s->graph.dVisited.n * sizeof(uint32_t) > (unsigned long long)keep_env
+                                       : (end - id0 >= 65536 && s->graph.dVisited.n * sizeof(uint32_t) > (1ull << 30));
   if (give_back) {
-    s->dVisited.release();
-    s->dInsVislog.release();
-    s->dLinkNext.release();
-    s->dLinkTouched.release();
+    s->graph.dVisited.release();
+    s->graph.dInsVislog.release();
+    s->graph.dLinkNext.release();
+    s->graph.dLinkTouched.release();
     s->vis_dirty = false;
   }
   return EHX_OK;
@@ -241,11 +239,11 @@ int graph_update(ehx_space* s, uint32_t id) {
   const int level = s->h_levels[id];
   int rc;
   InsertArgs a{};  // (zeroed: a null link_head / sel switches those outputs off in the kernels)
-  a.Xs = s->dXs;
-  a.xscale = (s->x_perm && s->metric == EHX_METRIC_COSINE) ? s->dInv : nullptr;
-  a.adj0 = s->dAdj0;
-  a.up_start = s->dUpStart;
-  a.up_lists = s->dUpLists;
+  a.Xs = s->xs();
+  a.xscale = (s->x_perm && s->metric == EHX_METRIC_COSINE) ? s->rows.dInv.p : nullptr;
+  a.adj0 = s->graph.dAdj0.p;
+  a.up_start = s->graph.dUpStart.p;
+  a.up_lists = s->graph.dUpLists.p;
   a.ef = efc;
   a.dims = s->dims;
   a.ld = s->ld;
@@ -260,11 +258,11 @@ int graph_update(ehx_space* s, uint32_t id) {
     uint32_t buf[64];
     const uint32_t* src;
     if (layer == 0) {
-      src = s->dAdj0 + (size_t)node * M0;
+      src = s->graph.dAdj0.p + (size_t)node * M0;
     } else {
       uint32_t us = 0;
-      HIP_TRY(hipMemcpy(&us, s->dUpStart + node, 4, hipMemcpyDeviceToHost));
-      src = s->dUpLists + ((size_t)us + (uint32_t)(layer - 1)) * M;
+      HIP_TRY(hipMemcpy(&us, s->graph.dUpStart.p + node, 4, hipMemcpyDeviceToHost));
+      src = s->graph.dUpLists.p + ((size_t)us + (uint32_t)(layer - 1)) * M;
     }
     HIP_TRY(hipMemcpy(buf, src, width * 4, hipMemcpyDeviceToHost));
     out->clear();
@@ -295,14 +293,14 @@ int graph_update(ehx_space* s, uint32_t id) {
     }
     h_off.push_back((uint32_t)h_cand.size());
     const uint32_t n_items = (uint32_t)h_neigh.size();
-    if ((rc = s->dItemTgt.ensure(n_items))) return rc;
-    if ((rc = s->dItemOff.ensure(n_items + 1))) return rc;
-    if ((rc = s->dItemIds.ensure(h_cand.size() ? h_cand.size() : 1))) return rc;
-    HIP_TRY(hipMemcpyAsync(s->dItemTgt.p, h_neigh.data(), n_items * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(s->dItemOff.p, h_off.data(), (n_items + 1) * 4, hipMemcpyHostToDevice, st));
+    if ((rc = s->graph.dItemTgt.ensure(n_items))) return rc;
+    if ((rc = s->graph.dItemOff.ensure(n_items + 1))) return rc;
+    if ((rc = s->graph.dItemIds.ensure(h_cand.size() ? h_cand.size() : 1))) return rc;
+    HIP_TRY(hipMemcpyAsync(s->graph.dItemTgt.p, h_neigh.data(), n_items * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(s->graph.dItemOff.p, h_off.data(), (n_items + 1) * 4, hipMemcpyHostToDevice, st));
     if (!h_cand.empty())
-      HIP_TRY(hipMemcpyAsync(s->dItemIds.p, h_cand.data(), h_cand.size() * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(launch_update_neigh(a, n_items, s->dItemTgt.p, layer, s->dItemOff.p, s->dItemIds.p, st));
+      HIP_TRY(hipMemcpyAsync(s->graph.dItemIds.p, h_cand.data(), h_cand.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(launch_update_neigh(a, n_items, s->graph.dItemTgt.p, layer, s->graph.dItemOff.p, s->graph.dItemIds.p, st));
     HIP_TRY(hipStreamSynchronize(st));
   }
   // part 2: repairConnectionsForUpdate = search from the entry point with the new vector, drop the
@@ -310,26 +308,26 @@ int graph_update(ehx_space* s, uint32_t id) {
   const uint32_t vis_words = (uint32_t)((s->cap + 31) / 32);
   const uint32_t vislog_cap = 32768;
   const uint32_t max_sel_levels = (uint32_t)s->g_maxlevel + 1;
-  if ((rc = s->dInsIds.ensure(1))) return rc;
-  if ((rc = s->dInsLevels.ensure(1))) return rc;
-  if ((rc = s->dInsSel.ensure((size_t)max_sel_levels * (1 + M)))) return rc;
-  if ((rc = s->dVisited.ensure(vis_words, true))) return rc;
-  if ((rc = s->dInsVislog.ensure(vislog_cap))) return rc;
+  if ((rc = s->graph.dInsIds.ensure(1))) return rc;
+  if ((rc = s->graph.dInsLevels.ensure(1))) return rc;
+  if ((rc = s->graph.dInsSel.ensure((size_t)max_sel_levels * (1 + M)))) return rc;
+  if ((rc = s->graph.dVisited.ensure(vis_words, true))) return rc;
+  if ((rc = s->graph.dInsVislog.ensure(vislog_cap))) return rc;
   const int32_t lv32 = level;
-  HIP_TRY(hipMemcpyAsync(s->dInsIds.p, &id, 4, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(s->dInsLevels.p, &lv32, 4, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemsetAsync(s->dVisited.p, 0, vis_words * sizeof(uint32_t), st));
-  a.visited = s->dVisited.p;
-  a.vislog = s->dInsVislog.p;
-  a.new_ids = s->dInsIds.p;
-  a.new_levels = s->dInsLevels.p;
-  a.sel = s->dInsSel.p;
+  HIP_TRY(hipMemcpyAsync(s->graph.dInsIds.p, &id, 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(s->graph.dInsLevels.p, &lv32, 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemsetAsync(s->graph.dVisited.p, 0, vis_words * sizeof(uint32_t), st));
+  a.visited = s->graph.dVisited.p;
+  a.vislog = s->graph.dInsVislog.p;
+  a.new_ids = s->graph.dInsIds.p;
+  a.new_levels = s->graph.dInsLevels.p;
+  a.sel = s->graph.dInsSel.p;
   a.vis_words = vis_words;
   a.vislog_cap = vislog_cap;
   a.max_sel_levels = max_sel_levels;
   HIP_TRY(launch_insert_search(a, 1, st));
   std::vector<uint32_t> h_sel((size_t)max_sel_levels * (1 + M));
-  HIP_TRY(hipMemcpyAsync(h_sel.data(), s->dInsSel.p, h_sel.size() * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(h_sel.data(), s->graph.dInsSel.p, h_sel.size() * 4, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   std::vector<uint32_t> h_tgt, h_kind, h_ioff, h_inc;
   std::vector<int32_t> h_tlevel;
@@ -353,18 +351,18 @@ int graph_update(ehx_space* s, uint32_t id) {
   h_ioff.push_back((uint32_t)h_inc.size());
   const uint32_t n_items = (uint32_t)h_tgt.size();
   if (n_items) {
-    if ((rc = s->dItemTgt.ensure(n_items))) return rc;
-    if ((rc = s->dItemLevel.ensure(n_items))) return rc;
-    if ((rc = s->dItemKind.ensure(n_items))) return rc;
-    if ((rc = s->dItemOff.ensure(n_items + 1))) return rc;
-    if ((rc = s->dItemIds.ensure(h_inc.size()))) return rc;
-    HIP_TRY(hipMemcpyAsync(s->dItemTgt.p, h_tgt.data(), n_items * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(s->dItemLevel.p, h_tlevel.data(), n_items * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(s->dItemKind.p, h_kind.data(), n_items * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(s->dItemOff.p, h_ioff.data(), (n_items + 1) * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(s->dItemIds.p, h_inc.data(), h_inc.size() * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(launch_insert_link(a, n_items, s->dItemTgt.p, s->dItemLevel.p, s->dItemKind.p, s->dItemOff.p,
-                               s->dItemIds.p, st));
+    if ((rc = s->graph.dItemTgt.ensure(n_items))) return rc;
+    if ((rc = s->graph.dItemLevel.ensure(n_items))) return rc;
+    if ((rc = s->graph.dItemKind.ensure(n_items))) return rc;
+    if ((rc = s->graph.dItemOff.ensure(n_items + 1))) return rc;
+    if ((rc = s->graph.dItemIds.ensure(h_inc.size()))) return rc;
+    HIP_TRY(hipMemcpyAsync(s->graph.dItemTgt.p, h_tgt.data(), n_items * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(s->graph.dItemLevel.p, h_tlevel.data(), n_items * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(s->graph.dItemKind.p, h_kind.data(), n_items * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(s->graph.dItemOff.p, h_ioff.data(), (n_items + 1) * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(s->graph.dItemIds.p, h_inc.data(), h_inc.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(launch_insert_link(a, n_items, s->graph.dItemTgt.p, s->graph.dItemLevel.p, s->graph.dItemKind.p, s->graph.dItemOff.p,
+                               s->graph.dItemIds.p, st));
     HIP_TRY(hipStreamSynchronize(st));
   }
   return EHX_OK;
@@ -388,11 +386,11 @@ int knn_graph_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_que
   if (ef > 4096) return fail(EHX_EUNSUPPORTED, "ef=%u exceeds 4096", ef);
   const uint32_t q_rows = (uint32_t)nq;
   int rc;
-  if ((rc = s->dQ.ensure((size_t)q_rows * s->ld))) return rc;
+  if ((rc = s->scr.dQ.ensure((size_t)q_rows * s->ld))) return rc;
   const uint32_t vis_words = (uint32_t)((s->n + 31) / 32);
   // the bitmaps are all-zero between kernels (every kernel that marks rows clears them again): zeroed once, on
   // allocation
-  if ((rc = s->dVisited.ensure((size_t)nq * vis_words, true))) return rc;
+  if ((rc = s->graph.dVisited.ensure((size_t)nq * vis_words, true))) return rc;
   const bool use_vislog = env().graph_vislog;  // (EHX_GRAPH_VISLOG=0: per-batch memset of the bitmaps instead, A/B runs)
   // Measured (r02, batch 1024, memset inside the timed region; gpurun_out of scripts/gpu_session_n.sh): the memset
   // costs n/8 bytes per query, streamed; the log costs one store per visited row plus one RANDOM 4-byte store per row
@@ -404,11 +402,8 @@ int knn_graph_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_que
                            : use_vislog && (size_t)nq * vis_words * sizeof(uint32_t) >= (192u << 20) &&
                                  s->n >= (uint64_t)32000 * ef;
   const uint32_t vislog_cap = log_now ? 48u * ef + 256u : 0u;
-  if ((rc = s->dInsVislog.ensure((size_t)nq * (vislog_cap ? vislog_cap : 1u)))) return rc;
-  if (!s->dGraphCounters) {
-    HIP_TRY(hipMalloc((void**)&s->dGraphCounters, kGraphCounters * sizeof(unsigned long long)));
-    HIP_TRY(hipMemset(s->dGraphCounters, 0, kGraphCounters * sizeof(unsigned long long)));
-  }
+  if ((rc = s->graph.dInsVislog.ensure((size_t)nq * (vislog_cap ? vislog_cap : 1u)))) return rc;
+  if ((rc = s->graph.dGraphCounters.ensure_zeroed_once(kGraphCounters))) return rc;
   {
     int rcw = wait_searches_in_flight(s, st);
     if (rcw) return rcw;
@@ -416,22 +411,22 @@ int knn_graph_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_que
   // timing events: batch 0 after a reset (outside the ring's mean) and every EHX_STATS_EVERY-th batch (BatchClock)
   if (!one) {
     if ((rc = s->clock.begin(st, env().stats_every))) return rc;
-    HIP_TRY(launch_prep_queries(d_queries, (uint32_t)nq, s->dims, s->ld, q_rows, s->metric, s->dQ.p, st));
+    HIP_TRY(launch_prep_queries(d_queries, (uint32_t)nq, s->dims, s->ld, q_rows, s->metric, s->scr.dQ.p, st));
   }
   GraphArgs a;
-  a.Q = s->dQ.p;
-  a.Xs = s->dXs;
-  a.xscale = (s->x_perm && s->metric == EHX_METRIC_COSINE) ? s->dInv : nullptr;
-  a.adj0 = s->dAdj0;
-  a.up_start = s->dUpStart;
-  a.up_lists = s->dUpLists;
-  a.visited = s->dVisited.p;
-  a.vislog = s->dInsVislog.p;
+  a.Q = s->scr.dQ.p;
+  a.Xs = s->xs();
+  a.xscale = (s->x_perm && s->metric == EHX_METRIC_COSINE) ? s->rows.dInv.p : nullptr;
+  a.adj0 = s->graph.dAdj0.p;
+  a.up_start = s->graph.dUpStart.p;
+  a.up_lists = s->graph.dUpLists.p;
+  a.visited = s->graph.dVisited.p;
+  a.vislog = s->graph.dInsVislog.p;
   a.vislog_cap = vislog_cap;
   a.out_ids = d_ids;
   a.out_dist = d_dist;
   a.out_count = d_count;
-  a.counters = s->dGraphCounters;
+  a.counters = s->graph.dGraphCounters.p;
   a.nq = (uint32_t)nq;
   a.k = k;
   a.ef = ef;
@@ -458,7 +453,7 @@ int knn_graph_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_que
     a.q_raw = one->q_host;
     a.done_flag = one->done_flag;
     a.seq = one->seq;
-    if (s->vis_dirty) HIP_TRY(hipMemsetAsync(s->dVisited.p, 0, s->dVisited.n * sizeof(uint32_t), st));
+    if (s->vis_dirty) HIP_TRY(hipMemsetAsync(s->graph.dVisited.p, 0, s->graph.dVisited.n * sizeof(uint32_t), st));
     s->vis_dirty = false;
     HIP_TRY(launch_graph_search(a, st));
     s->n_queries += nq;
@@ -467,9 +462,9 @@ int knn_graph_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_que
   if ((rc = s->clock.scan_begin(st))) return rc;
   // (inside the timed kernel region: clearing the bitmaps is part of what a batch costs, log or memset)
   if (log_now && s->vis_dirty)  // (the whole buffer: an earlier, larger batch may have marked words beyond this one's)
-    HIP_TRY(hipMemsetAsync(s->dVisited.p, 0, s->dVisited.n * sizeof(uint32_t), st));
+    HIP_TRY(hipMemsetAsync(s->graph.dVisited.p, 0, s->graph.dVisited.n * sizeof(uint32_t), st));
   else if (!log_now)
-    HIP_TRY(hipMemsetAsync(s->dVisited.p, 0, (size_t)nq * vis_words * sizeof(uint32_t), st));
+    HIP_TRY(hipMemsetAsync(s->graph.dVisited.p, 0, (size_t)nq * vis_words * sizeof(uint32_t), st));
   s->vis_dirty = !log_now;
   HIP_TRY(launch_graph_search(a, st));
   if ((rc = s->clock.scan_end(st)) || (rc = s->clock.finish(st))) return rc;

@@ -75,30 +75,9 @@ Engine& engine();   // the process-global engine state (ehx_space.cpp)
 
 inline uint64_t round_up(uint64_t v, uint64_t m) { return (v + m - 1) / m * m; }
 
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  size_t n = 0;
-  int ensure(size_t want, bool zero = false) {
-    if (want <= n) return EHX_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-    HIP_TRY(hipMalloc((void**)&p, want * sizeof(T)));
-    if (zero) {
-      // (the fill runs on the NULL stream; the spaces' streams are non-blocking, i.e. not ordered with it: wait)
-      HIP_TRY(hipMemset(p, 0, want * sizeof(T)));
-      HIP_TRY(hipStreamSynchronize(nullptr));
-    }
-    n = want;
-    return EHX_OK;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-  }
-};
+}  // namespace ehx_impl
+#include "ehx_own.h"
+namespace ehx_impl {
 
 // The per-batch events of one search pipeline: the timing events behind ehx_stats (last_scan_ms / last_total_ms of the
 // last timed batch, the ring of scan windows behind scan_ms_mean) and the fence — "every launch of the last batch has run"
@@ -114,7 +93,7 @@ struct DevBuf {
 struct BatchClock {
   static constexpr int kRing = 64;
   static constexpr uint32_t kOutOfRing = 0;
-  hipStream_t own = nullptr;                 // the space's search stream (create_one)
+  hipStream_t own = nullptr;                 // the space's search stream (create_one; not owned)
   std::atomic<uint64_t>* counter = nullptr;  // ehx_space::ev_counter: which of a space's clocks timed a batch last
 
   int begin(hipStream_t st, uint32_t every);
@@ -129,11 +108,13 @@ struct BatchClock {
   void release();
 
  private:
-  hipEvent_t start = nullptr, end = nullptr, fence_ev = nullptr;
-  hipEvent_t ring[kRing][2] = {};
-  hipEvent_t spare[2] = {};      // scan window of a timed batch outside the ring
-  hipEvent_t* last = nullptr;    // scan window of the last timed batch: a ring pair or the spare
-  hipEvent_t* pair = nullptr;    // ... of this batch
+  struct Events {
+    Event start, end, fence_ev;
+    Event ring[kRing][2];
+    Event spare[2];              // scan window of a timed batch outside the ring
+  } ev;
+  Event* last = nullptr;         // scan window of the last timed batch: a ring pair or the spare
+  Event* pair = nullptr;         // ... of this batch
   uint64_t batches = 0, ring_count = 0;
   uint64_t seq = 0;              // *counter when the last timed batch finished
   bool timed = false, in_ring = false;  // this batch
@@ -243,10 +224,12 @@ struct ehx_space {
   std::mutex wmu;              // every mutator takes wmu first, then mu: writers are serialised among themselves, and
                                // a batch of fresh keys does its upload / statistics / scan copies holding wmu only —
                                // the rows land beyond the published row count — and takes mu just to publish
-  hipStream_t wstream = nullptr;  // the writers' stream (uploads, row statistics, derived copies)
-  hipEvent_t wev = nullptr;       // blocking-sync event: a writer waiting for its stream sleeps instead of spinning
-  hipEvent_t sev[2] = {nullptr, nullptr};  // "upload out of staging half i has finished" (ping-pong staging)
-                                  // inside the HIP runtime beside the threads that launch searches
+  struct Writer {              // what writers use (wmu), created by create_one
+    Stream wstream;            // the writers' stream (uploads, row statistics, derived copies)
+    Event wev;                 // blocking-sync event: a writer waiting for its stream sleeps instead of spinning
+    Event sev[2];              // "upload out of staging half i has finished" (ping-pong staging)
+    PinBuf<float> hStage;      // pinned staging (Set / Get / query upload), ensure_stage
+  } wr;
   int device = 0;              // HIP device of this space's HBM state
   // Row sharding behind the C ABI (ehx_params.shards > 1): the PARENT keeps the key maps and no rows; global row g
   // lives in shard g % G at local row g / G (streamed Sets stay balanced); the shards are ordinary
@@ -254,24 +237,30 @@ struct ehx_space {
   bool keyless = false;            // a shard: rows are addressed by local id only, hidden from ehx_space_open
   std::vector<ehx_space*> shards;  // parent only (the shards are owned by the registry under hidden names)
   std::unique_ptr<ShardWorkers> workers;  // parent only: one persistent host thread per shard beyond the first
-  hipEvent_t xev = nullptr;        // shard only: "my local top-k has reached the gather buffer" (the parent's stream waits)
-  DevBuf<unsigned char> dOutPack;  // shard only: ids | distances | counts of one batch, contiguous: ONE peer copy
-  DevBuf<unsigned char> dGPack;    // parent scratch on shards[0]'s device: the G packed results, one slot per shard
+  struct ShardExchange {
+    Event xev;                       // shard only: "my local top-k has reached the gather buffer" (the parent's stream waits)
+    DevBuf<unsigned char> dOutPack;  // shard only: ids | distances | counts of one batch, contiguous: ONE peer copy
+    DevBuf<unsigned char> dGPack;    // parent scratch on shards[0]'s device: the G packed results, one slot per shard
+  } xch;
 
-  // HBM-resident state
-  void* dX = nullptr;        // [cap][ld] rows, fp32 or fp16 (x_half)
+  // HBM-resident state.  Every device / pinned resource below is an owner (ehx_own.h) inside a group named after what
+  // guards and uses it; release_device resets the groups, so a buffer added to a group is freed with no further edit.
+  struct Rows {                // the stored rows (moved by grow under mu held exclusively)
+    DevBuf<char> dX;           // [cap][ld] rows, fp32 or fp16 (x_half)
+    DevBuf<float2> dRowp;      // [cap]
+    DevBuf<float> dInv;        // [cap] (cosine)
+    DevBuf<float> dMaxSumsq;   // device scalar: largest |x|^2 ever written (certification margin, cert_margin)
+    DevBuf<float> dXs;         // [cap][ld] two-copy graph spaces: the search copy (permuted blocks, cosine rows normalised)
+    DevBuf<uint64_t> dPermIds; // rows of a batch written in place (non-contiguous ids), for launch_permute_blocks
+  } rows;
   int x_half = 0;            // EHX_DTYPE_F16: rows stored as IEEE binary16 (flat mode only)
   size_t esz = sizeof(float);  // bytes per stored element
-  char* xrow(uint64_t id) const { return (char*)dX + id * ld * esz; }
-  const float* xf32() const { return (const float*)dX; }
-  float2* dRowp = nullptr;   // [cap]
-  float* dInv = nullptr;     // [cap] (cosine)
-  float* dMaxSumsq = nullptr;  // device scalar: largest |x|^2 ever written (certification margin, cert_margin)
-  float* dXs = nullptr;      // [cap][ld] graph mode: the search copy (permuted blocks, cosine rows normalised)
+  char* xrow(uint64_t id) const { return rows.dX.p + id * ld * esz; }
+  const float* xf32() const { return (const float*)rows.dX.p; }
   bool x_perm = false;       // graph mode, fp32 rows (round 4): the rows are stored ONCE — dX holds them in the search
-                             // copy's block order, RAW; dXs is the same pointer; cosine rows are scaled by inv_norm on
+                             // copy's block order, RAW, and rows.dXs stays empty; cosine rows are scaled by inv_norm on
                              // the fly in the kernels (GraphArgs / InsertArgs .xscale); Get undoes the permutation
-  DevBuf<uint64_t> dPermIds; // rows of a batch written in place (non-contiguous ids), for launch_permute_blocks
+  float* xs() const { return x_perm ? (float*)rows.dX.p : rows.dXs.p; }  // graph mode: the search copy
   uint64_t cap = 0;
   // published row count.  Atomic (round 6): an appending Set publishes its rows with ONE release store under the space's lock
   // held SHARED — rows below the new count are resident and described before the store, the arrays do not move while any search
@@ -282,59 +271,67 @@ struct ehx_space {
   // reads of it may differ, and a pass planned on one prefix and masked by another answers for no prefix at all.
   std::atomic<uint64_t> n{0};
   // fp16-MFMA filter scan (k_flat16.hip): unit-normalised binary16 scan copy of the rows
-  bool has16 = false;          // the space keeps the fp16 scan copy (maintained on every write, whatever use16 says)
-  bool use16 = false;          // ... and scans with the fp16 filter right now (ehx_space_set_scan switches it)
-  __half* dX16 = nullptr;      // [cap][ld16] in the stage-blocked scan16_index layout
-  float2* dRowp16 = nullptr;   // [cap]
+  bool has16 = false;          // the space keeps the fp16 scan copy (maintained on every write, whatever engine scans)
+  struct Scan16 {
+    DevBuf<__half> dX16;       // [cap][ld16] in the stage-blocked scan16_index layout
+    DevBuf<float2> dRowp16;    // [cap]
+    DevBuf<unsigned long long> dUnsafe;  // rows the filter cannot bound (then every scan is the fp32 scan)
+  } f16;
   uint32_t ld16 = 0;
-  unsigned long long* dUnsafe = nullptr;  // rows the filter cannot bound (then every scan is the fp32 scan)
   // (the three counters below are written by an appending Set while searches run: atomic, stored BEFORE the release store of n —
   // a search reads them after its snapshot of n, so a prefix it scans never holds a row they do not count)
   std::atomic<uint64_t> h_unsafe{0};
   // int8-MFMA filter scan (k_flati8.hip): per-row-scaled int8 scan copy of the unit-normalised rows
   bool has8 = false;           // the space keeps the int8 scan copy (flat spaces whose row length makes it pay)
-  int8_t* dX8 = nullptr;       // [cap][ld8] in the stage-blocked scan8_index layout
-  float4* dRowp8 = nullptr;    // [cap + 512] (A, B, C, D)
-  float4* dTilep8 = nullptr;   // [cap/256 + 2]
-  float* dTileg8 = nullptr;    // [cap/256 + 2][16] per-lane-group max |A| (k_misc.hip: rows of a tile ordered by step)
-  uint8_t* dPerm8 = nullptr;   // [cap] position -> row index inside the tile
-  DevBuf<uint64_t> dTileList;  // scratch of launch_make_scan8
+  struct Scan8 {
+    DevBuf<int8_t> dX8;        // [cap][ld8] in the stage-blocked scan8_index layout
+    DevBuf<float4> dRowp8;     // [cap + 512] (A, B, C, D)
+    DevBuf<float4> dTilep8;    // [cap/256 + 2]
+    DevBuf<float> dTileg8;     // [cap/256 + 2][16] per-lane-group max |A| (k_misc.hip: rows of a tile ordered by step)
+    DevBuf<uint8_t> dPerm8;    // [cap] position -> row index inside the tile
+    DevBuf<uint64_t> dTileList;  // scratch of launch_make_scan8
+    DevBuf<unsigned long long> dUnsafe8;
+  } i8;
   uint32_t ld8 = 0;
-  unsigned long long* dUnsafe8 = nullptr;
   std::atomic<uint64_t> h_unsafe8{0};
   std::atomic<uint64_t> h_margin8{0};     // tiles written so far with a lane group whose min B lies > 0.1 % above the tile's (dUnsafe8[1])
   uint64_t i8_min_rows = 16384;  // below this the fp16 filter serves (sample pass + cascade need a few thousand rows)
   uint32_t scan_sel = EHX_SCAN_AUTO;  // EHX_SCAN_*: what ehx_space_set_scan selected
 
-  // graph (graph mode): imported adjacency, re-laid-out for the GPU (k_graph.hip)
-  uint32_t* dAdj0 = nullptr;     // [g_n][2M]
-  uint32_t* dUpStart = nullptr;  // [g_n]
-  uint32_t* dUpLists = nullptr;  // [*][M]
+  // graph (graph mode): adjacency, re-laid-out for the GPU (k_graph.hip), and the GPU-side insertion's scratch
+  struct Graph {
+    DevBuf<uint32_t> dAdj0;      // [g_n][2M]
+    DevBuf<uint32_t> dUpStart;   // [g_n]
+    DevBuf<uint32_t> dUpLists;   // [*][M]
+    DevBuf<uint32_t> dVisited;
+    DevBuf<uint32_t> dInsIds, dInsSel, dInsVislog, dItemTgt, dItemKind, dItemOff, dItemIds;
+    DevBuf<uint32_t> dLinkHead, dLinkNext, dLinkCount;  // bulk build: device-side link work items (k_insert.hip)
+    DevBuf<uint64_t> dLinkTouched;
+    DevBuf<int32_t> dInsLevels, dItemLevel;
+    DevBuf<unsigned long long> dGraphCounters;  // n_dist, n_hops0, n_hops_up, n_prefetch_hit, [4..11] profile builds
+  } graph;
   uint64_t g_n = 0;              // rows covered by the graph (0 = no graph)
   uint32_t g_entry = 0;
   int g_maxlevel = -1;
-  DevBuf<uint32_t> dVisited;
-  unsigned long long* hUncertPin = nullptr;  // pinned landing place of a batch's verdict (uncertified-query count)
-  // one query per call against a small flat shard: one launch, host-visible in / out (knn_host_direct)
-  char* hOnePin = nullptr;                   // host-coherent pinned: query | ids[64] | dist[64] | count | flag
-  DevBuf<uint64_t> dOnePart;                 // [n_blocks][64] workgroup lists
-  uint32_t* dOneTicket = nullptr;
+  // one query per call in one launch, host-visible in / out (knn_host_direct; scratch_mu)
+  struct OneLaunch {
+    PinBuf<char> hOnePin;        // host-coherent pinned: query | ids[64] | dist[64] | count | flag
+    DevBuf<uint64_t> dOnePart;   // [n_blocks][64] workgroup lists
+    DevBuf<uint32_t> dOneTicket;
+  } one;
   uint32_t one_seq = 0;
   std::atomic<uint64_t> n_one_launch{0};
-  char* hSmallPin = nullptr;                 // pinned staging of small host calls: [queries | ids, distances, counts]
-  DevBuf<uint64_t> dSmallOut;                // their results, one block (one device-to-host copy)
   // Host-pointer batches (ehx_knn with more than a handful of queries): every call in flight owns a SLOT — pinned
   // staging for its queries and results, device buffers for both, a copy stream — so that the upload of call i + 1
   // and the download of call i - 1 run beside the scan of call i (which alone needs scratch_mu).  One caller sees its
   // own copies in series as before; two or more callers keep the scan kernels back to back.
   struct HostSlot {
-    hipStream_t st = nullptr;
-    hipEvent_t in_ev = nullptr, done_ev = nullptr;
-    char* pin = nullptr;
-    size_t pin_bytes = 0;
+    Stream st;
+    Event in_ev, done_ev;
+    PinBuf<char> pin;
     DevBuf<float> dq;
     DevBuf<unsigned char> dout;
-    bool busy = false;
+    bool busy = false;   // (hs_mu; a call holds the space's lock shared for as long as it holds a slot)
   };
   static constexpr int kHostSlots = 3;
   HostSlot hslot[kHostSlots];
@@ -359,11 +356,6 @@ struct ehx_space {
   std::default_random_engine level_rng;  // hnswlib: level_generator_ (libstdc++ minstd_rand0)
   bool level_rng_seeded = false;
   uint64_t g_stale_updates = 0;  // rows overwritten in place after their insertion (no graph repair)
-  DevBuf<uint32_t> dInsIds, dInsSel, dInsVislog, dItemTgt, dItemKind, dItemOff, dItemIds;
-  DevBuf<uint32_t> dLinkHead, dLinkNext, dLinkCount;  // bulk build: device-side link work items (k_insert.hip)
-  DevBuf<uint64_t> dLinkTouched;
-  DevBuf<int32_t> dInsLevels, dItemLevel;
-  unsigned long long* dGraphCounters = nullptr;  // n_dist, n_hops0, n_hops_up, n_prefetch_hit, [4..11] profile builds
 
   // key map (explicit keys only)
   // key <-> row id.  Their own lock (taken INSIDE mu when both are held, or alone): a streamed batch inserts its
@@ -376,43 +368,52 @@ struct ehx_space {
 
   // scratch for the kNN pipeline (serialised by scratch_mu)
   std::mutex scratch_mu;
-  hipStream_t stream = nullptr;
-  DevBuf<float> dQraw, dQ;
-  DevBuf<uint64_t> dCand, dPart, dMerged, dOutIds, dGthr;
-  DevBuf<float> dOutDist;
-  DevBuf<uint32_t> dOutCount;
-  unsigned long long* dUncert = nullptr;
+  Stream stream;               // the space's search stream (create_one)
+  struct Scratch {
+    DevBuf<float> dQraw, dQ;
+    DevBuf<uint64_t> dCand, dPart, dMerged, dOutIds, dGthr;
+    DevBuf<float> dOutDist;
+    DevBuf<uint32_t> dOutCount;
+    DevBuf<unsigned long long> dUncert;
+    // filter scratch: fp16 queries, per-query (gamma, u, v), per-query certification flags, re-run buffers
+    DevBuf<__half> dQ16;
+    DevBuf<float> dQgamma, dFbQ, dFbDist, dSample;
+    DevBuf<float2> dQuv;
+    DevBuf<uint32_t> dUflags, dFbCnt, dFbIdx;
+    DevBuf<uint64_t> dFbIds;
+    DevBuf<unsigned long long> dUncert16;      // queries the filter pass could not certify
+    PinBuf<unsigned long long> hUncertPin;     // pinned landing place of a batch's verdict (uncertified-query count)
+    PinBuf<char> hSmallPin;                    // pinned staging of small host calls: [queries | ids, distances, counts]
+    DevBuf<uint64_t> dSmallOut;                // their results, one block (one device-to-host copy)
+  } scr;
   // neighbours of stored rows (ehx_knn_by_keys / ehx_knn_by_ids_device): the gathered query batch, the row ids of a host
   // call, the (k + 1)-long lists | validity flags | a host call's k-long results; by_ev: the last call's launches have run
   // (the next call's stream waits for it before it writes them again)
-  DevBuf<float> dByQ;
-  DevBuf<uint64_t> dByIds;
-  DevBuf<unsigned char> dByOut;
-  hipEvent_t by_ev = nullptr;
-  // filter scratch: fp16 queries, per-query (gamma, u, v), per-query certification flags, re-run buffers
-  DevBuf<__half> dQ16;
-  DevBuf<float> dQgamma, dFbQ, dFbDist, dSample;
-  DevBuf<float2> dQuv;
-  DevBuf<uint32_t> dUflags, dFbCnt, dFbIdx;
-  DevBuf<uint64_t> dFbIds;
-  unsigned long long* dUncert16 = nullptr;  // queries the filter pass could not certify
+  struct ByKey {
+    DevBuf<float> dByQ;
+    DevBuf<uint64_t> dByIds;
+    DevBuf<unsigned char> dByOut;
+    Event by_ev;
+  } by;
   // int8 filter scratch: everything ONE in-flight batch of the int8 pipeline owns — prepared queries, query tiles +
   // parameters, per-pass thresholds, sample scores, pools, running best list, verdict, batch clock.  TWO sets: a host
   // caller's batch can be enqueued behind another caller's on the space's stream while that one still waits for its
   // verdict (knn_host_direct), so the scan kernels of consecutive batches run back to back with no host in between.
   struct I8Set {
-    DevBuf<float> dQ;
-    DevBuf<int8_t> dQ8;
-    DevBuf<float4> dQp8;
-    DevBuf<float2> dQuv;
-    DevBuf<float> dThr8, dSample8;
-    DevBuf<uint64_t> dPool, dMerged8;
-    DevBuf<uint32_t> dI8Ctl;  // [q_rows] pool counts | [q_rows] overflow flags | [kSyncWordsI8] lock-step progress words
-    DevBuf<uint32_t> dUflags;
-    DevBuf<uint64_t> dCnt;    // [8] epilogue counters of diagnosis builds (EHX_I8_COUNT); the set's own: nothing shared
-    unsigned long long* dUncert = nullptr;
-    unsigned long long* hUncertPin = nullptr;
-    hipEvent_t verdict = nullptr;  // blocking-sync: the verdict has landed in hUncertPin
+    struct Buffers {
+      DevBuf<float> dQ;
+      DevBuf<int8_t> dQ8;
+      DevBuf<float4> dQp8;
+      DevBuf<float2> dQuv;
+      DevBuf<float> dThr8, dSample8;
+      DevBuf<uint64_t> dPool, dMerged8;
+      DevBuf<uint32_t> dI8Ctl;  // [q_rows] pool counts | [q_rows] overflow flags | [kSyncWordsI8] lock-step progress words
+      DevBuf<uint32_t> dUflags;
+      DevBuf<uint64_t> dCnt;    // [8] epilogue counters of diagnosis builds (EHX_I8_COUNT); the set's own: nothing shared
+      DevBuf<unsigned long long> dUncert;
+      PinBuf<unsigned long long> hUncertPin;
+      Event verdict;            // blocking-sync: the verdict has landed in hUncertPin
+    } buf;
     BatchClock clock;              // timed: batch 0 and every EHX_STATS_EVERY-th batch of the set
     std::mutex mu;
   };
@@ -425,8 +426,6 @@ struct ehx_space {
                              // time (the timing ring, ehx_stats) would span both
   std::atomic<uint64_t> n_filter_queries{0}, n_filter_fallback{0}, n_exhaustive{0}, n_uncertified_final{0};
   std::atomic<uint64_t> n_i8_queries{0}, n_i8_fallback{0};
-  float* hStage = nullptr;  // pinned staging (Set / Get / query upload)
-  size_t hStageBytes = 0;
   // the batch clock of the passes under scratch_mu: fp32 / fp16 scans time every batch, the exhaustive pass every batch
   // outside the ring, the graph search batch 0 and every EHX_STATS_EVERY-th batch (round 6: six event records per batch
   // idled the queue ~36 us of a 0.35-ms batch)
@@ -469,128 +468,22 @@ struct ehx_space {
 
   // frees every device / pinned resource (idempotent); the host-side object stays usable as a tombstone
   void release_device() {
-    auto fr = [](auto*& p) {
-      if (p) (void)hipFree(p);
-      p = nullptr;
-    };
-    if (dXs == (float*)dX) dXs = nullptr;  // (single-copy graph spaces: the same allocation)
-    fr(dX);
-    fr(dXs);
-    dPermIds.release();
-    fr(dRowp);
-    fr(dInv);
-    fr(dMaxSumsq);
-    fr(dX16);
-    fr(dRowp16);
-    fr(dUnsafe);
-    fr(dX8);
-    fr(dRowp8);
-    fr(dTilep8);
-    fr(dTileg8);
-    fr(dPerm8);
-    dTileList.release();
-    fr(dUnsafe8);
+    rows = {};
+    f16 = {};
+    i8 = {};
+    graph = {};
+    scr = {};
+    by = {};
+    one = {};
+    xch = {};
+    wr = {};
     for (auto& c : i8set) {
-      c.dQ.release();
-      c.dQ8.release();
-      c.dQp8.release();
-      c.dQuv.release();
-      c.dThr8.release();
-      c.dSample8.release();
-      c.dPool.release();
-      c.dMerged8.release();
-      c.dI8Ctl.release();
-      c.dUflags.release();
-      fr(c.dUncert);
-      if (c.hUncertPin) (void)hipHostFree(c.hUncertPin);
-      c.hUncertPin = nullptr;
-      if (c.verdict) (void)hipEventDestroy(c.verdict);
-      c.verdict = nullptr;
+      c.buf = {};
       c.clock.release();
     }
-    dGPack.release();
-    dOutPack.release();
-    if (xev) (void)hipEventDestroy(xev);
-    xev = nullptr;
-    fr(dUncert16);
-    if (hUncertPin) (void)hipHostFree(hUncertPin);
-    hUncertPin = nullptr;
-    if (hSmallPin) (void)hipHostFree(hSmallPin);
-    hSmallPin = nullptr;
-    if (hOnePin) (void)hipHostFree(hOnePin);
-    hOnePin = nullptr;
-    dOnePart.release();
-    fr(dOneTicket);
-    for (auto& h : hslot) {
-      if (h.pin) (void)hipHostFree(h.pin);
-      h.pin = nullptr;
-      h.pin_bytes = 0;
-      h.dq.release();
-      h.dout.release();
-      if (h.in_ev) (void)hipEventDestroy(h.in_ev);
-      if (h.done_ev) (void)hipEventDestroy(h.done_ev);
-      if (h.st) (void)hipStreamDestroy(h.st);
-      h.in_ev = h.done_ev = nullptr;
-      h.st = nullptr;
-    }
-    fr(dAdj0);
-    fr(dUpStart);
-    fr(dUpLists);
-    fr(dGraphCounters);
-    fr(dUncert);
-    dQ16.release();
-    dQgamma.release();
-    dSample.release();
-    dFbQ.release();
-    dFbDist.release();
-    dQuv.release();
-    dUflags.release();
-    dFbCnt.release();
-    dFbIdx.release();
-    dFbIds.release();
-    dVisited.release();
-    dInsIds.release();
-    dInsSel.release();
-    dInsVislog.release();
-    dItemTgt.release();
-    dItemKind.release();
-    dItemOff.release();
-    dItemIds.release();
-    dInsLevels.release();
-    dItemLevel.release();
-    dLinkHead.release();
-    dLinkNext.release();
-    dLinkCount.release();
-    dLinkTouched.release();
-    dQraw.release();
-    dQ.release();
-    dByQ.release();
-    dByIds.release();
-    dByOut.release();
-    if (by_ev) (void)hipEventDestroy(by_ev);
-    by_ev = nullptr;
-    dCand.release();
-    dPart.release();
-    dMerged.release();
-    dGthr.release();
-    dOutIds.release();
-    dSmallOut.release();
-    dOutDist.release();
-    dOutCount.release();
-    if (hStage) (void)hipHostFree(hStage);
-    hStage = nullptr;
-    hStageBytes = 0;
+    for (auto& h : hslot) h = {};
     clock.release();
-    if (stream) (void)hipStreamDestroy(stream);
-    stream = nullptr;
-    if (wstream) (void)hipStreamDestroy(wstream);
-    wstream = nullptr;
-    if (wev) (void)hipEventDestroy(wev);
-    wev = nullptr;
-    for (auto& e : sev) {
-      if (e) (void)hipEventDestroy(e);
-      e = nullptr;
-    }
+    stream = {};
     cap = 0;
     n = 0;
     g_n = 0;

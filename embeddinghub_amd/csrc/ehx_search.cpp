@@ -31,10 +31,10 @@ static int by_scratch(ehx_space* s, size_t n, uint32_t k, bool host_out, ByKeySc
   const size_t o_oids = round_up(o_valid + n * sizeof(uint32_t), 8);
   const size_t o_odist = o_oids + n * k * sizeof(uint64_t), o_ocnt = o_odist + n * k * sizeof(float);
   int rc;
-  if ((rc = s->dByQ.ensure(n * s->dims))) return rc;
-  if ((rc = s->dByOut.ensure(host_out ? o_ocnt + n * sizeof(uint32_t) : o_oids))) return rc;
-  if (!s->by_ev) HIP_TRY(hipEventCreateWithFlags(&s->by_ev, hipEventDisableTiming));
-  unsigned char* p = s->dByOut.p;
+  if ((rc = s->by.dByQ.ensure(n * s->dims))) return rc;
+  if ((rc = s->by.dByOut.ensure(host_out ? o_ocnt + n * sizeof(uint32_t) : o_oids))) return rc;
+  if ((rc = s->by.by_ev.ensure(hipEventDisableTiming))) return rc;
+  unsigned char* p = s->by.dByOut.p;
   b->l_ids = (uint64_t*)p;
   b->l_dist = (float*)(p + o_ldist);
   b->l_cnt = (uint32_t*)(p + o_lcnt);
@@ -68,14 +68,14 @@ static int by_ids_locked(ehx_space* s, hipStream_t st, size_t n, const uint64_t*
   if (s->x_perm && s->poisoned.load())
     return fail(EHX_EINTERNAL, "graph space: an in-place overwrite failed half way (rows left in raw order); drop and rebuild it");
   // (the last call's launches — on whatever stream it was given — have read and written this scratch)
-  HIP_TRY(hipStreamWaitEvent(st, s->by_ev, 0));
+  HIP_TRY(hipStreamWaitEvent(st, s->by.by_ev, 0));
   // the ONE read of the row count: the gather's range check and the flat chain's passes answer for the same prefix
   const uint64_t n_pub = s->n.load(std::memory_order_acquire);
   GatherRowsArgs g = {};
   g.row_ids = d_row_ids;
-  g.bases.p[0] = s->dX;
+  g.bases.p[0] = s->rows.dX.p;
   g.n_rows = n_pub;
-  g.out = s->dByQ.p;
+  g.out = s->by.dByQ.p;
   g.valid = b.valid;
   g.n = (uint32_t)n;
   g.dims = s->dims;
@@ -86,9 +86,9 @@ static int by_ids_locked(ehx_space* s, hipStream_t st, size_t n, const uint64_t*
   HIP_TRY(launch_gather_rows(g, st));
   int rc = EHX_OK;
   if (n_pub > 0)   // (an empty space: every query is invalid, the lists are never read)
-    rc = knn_device_locked(s, st, n, s->dByQ.p, k + 1, b.l_ids, b.l_dist, b.l_cnt, nullptr, 0, 0, n_pub);
+    rc = knn_device_locked(s, st, n, s->by.dByQ.p, k + 1, b.l_ids, b.l_dist, b.l_cnt, nullptr, 0, 0, n_pub);
   if (!rc) rc = by_drop_self(b, st, n, d_row_ids, k, d_out_ids, d_out_dist, d_out_count);
-  (void)hipEventRecord(s->by_ev, st);
+  (void)hipEventRecord(s->by.by_ev, st);
   return rc;
 }
 
@@ -115,12 +115,12 @@ static int sharded_by_ids_locked(ehx_space* p, size_t n, const uint64_t* d_row_i
       if (c->dropped) return fail(EHX_ENOTFOUND, "Not found");
       if (c->x_perm && c->poisoned.load())
         return fail(EHX_EINTERNAL, "graph space: an in-place overwrite failed half way (rows left in raw order); drop and rebuild it");
-      g.bases.p[i] = c->dX;
+      g.bases.p[i] = c->rows.dX.p;
     }
     const ehx_space* c0 = p->shards[0];
     g.row_ids = d_row_ids;
     g.n_rows = n_pub;
-    g.out = p->dByQ.p;
+    g.out = p->by.dByQ.p;
     g.valid = b.valid;
     g.n = (uint32_t)n;
     g.dims = c0->dims;
@@ -131,7 +131,7 @@ static int sharded_by_ids_locked(ehx_space* p, size_t n, const uint64_t* d_row_i
     HIP_TRY(launch_gather_rows(g, p->stream));
     HIP_TRY(hipStreamSynchronize(p->stream));
   }
-  int rc = sharded_knn_locked(p, n, nullptr, p->dByQ.p, home, k + 1, b.l_ids, b.l_dist, b.l_cnt, true, p->stream);
+  int rc = sharded_knn_locked(p, n, nullptr, p->by.dByQ.p, home, k + 1, b.l_ids, b.l_dist, b.l_cnt, true, p->stream);
   if (rc) return rc;
   HIP_TRY(hipSetDevice(home));
   return by_drop_self(b, p->stream, n, d_row_ids, k, b.o_ids, b.o_dist, b.o_cnt);
@@ -143,6 +143,55 @@ static int by_copy_out(hipStream_t st, uint64_t* out_ids, const uint64_t* d_ids,
   HIP_TRY(hipMemcpyAsync(out_dist, d_dist, dist_b, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(out_count, d_cnt, cnt_b, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
+  return EHX_OK;
+}
+
+// ---- one query per call in one launch (knn_host_direct): the host-visible block and the wait for the kernel's flag ----
+constexpr size_t kOneQ = 16384;   // query slot (ld <= 4096 floats); behind it: ids[64] | dist[64] | count | flag
+
+// the host-coherent pinned block (zeroed: no flag value is ever 0), created on the space's device on first use
+static int one_launch_block(ehx_space* s, char** h) {
+  int rc = s->one.hOnePin.ensure(kOneQ + 2048, hipHostMallocCoherent | hipHostMallocMapped, true);
+  *h = s->one.hOnePin.p;
+  return rc;
+}
+
+// spins on the flag the kernel's last wave raises (~ tens of milliseconds at most), then asks the runtime
+static int one_launch_wait(ehx_space* s, const uint32_t* done_flag, uint32_t seq, const char* what) {
+  volatile const uint32_t* flag = done_flag;
+  bool seen = false;
+  for (uint32_t spin = 0; spin < 4000000u; ++spin) {
+    if (*flag == seq) {
+      seen = true;
+      break;
+    }
+    __builtin_ia32_pause();
+  }
+  if (!seen) {
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    if (*flag != seq) return fail(EHX_EINTERNAL, "%s finished without publishing its result", what);
+  }
+  std::atomic_thread_fence(std::memory_order_acquire);
+  return EHX_OK;
+}
+
+// keys of the rows a batch returned, packed into the caller's arena: key_off[i * k + j] .. key_off[i * k + j + 1] is the
+// key of result j of query i (empty beyond out_count[i], or for a row without a key)
+static int fill_key_arena(ehx_space* s, size_t n, uint32_t k, const uint64_t* out_ids, const uint32_t* out_count,
+                          char* key_arena, size_t arena_cap, uint64_t* key_off) {
+  uint64_t off = 0;
+  std::string key;
+  for (size_t i = 0; i < n; ++i) {
+    for (uint32_t j = 0; j < k; ++j) {
+      key_off[i * k + j] = off;
+      if (j < out_count[i] && key_for_id(s, out_ids[i * k + j], &key) == EHX_OK) {
+        if (off + key.size() > arena_cap) return fail(EHX_ERANGE, "key arena too small");
+        memcpy(key_arena + off, key.data(), key.size());
+        off += key.size();
+      }
+    }
+  }
+  key_off[n * k] = off;
   return EHX_OK;
 }
 
@@ -202,28 +251,21 @@ static int knn_host_direct(ehx_space* s, size_t n_queries, const float* queries,
     const uint64_t n_pub = s->n.load(std::memory_order_acquire);   // (this path's one read of the row count)
     if (one_on && n_queries == 1 && k <= 64 && s->params.mode == EHX_MODE_FLAT && s->scan_sel == EHX_SCAN_AUTO && n_pub > 0 &&
         s->ld <= 4096 && n_pub * s->ld * s->esz <= one_bytes) {
-      constexpr size_t kOneQ = 16384;   // query slot (ld <= 4096 floats)
-      if (!s->hOnePin) {
-        HIP_TRY(hipHostMalloc((void**)&s->hOnePin, kOneQ + 2048, hipHostMallocCoherent | hipHostMallocMapped));
-        memset(s->hOnePin, 0, kOneQ + 2048);
-      }
-      if (!s->dOneTicket) {
-        HIP_TRY(hipMalloc((void**)&s->dOneTicket, sizeof(uint32_t)));
-        HIP_TRY(hipMemset(s->dOneTicket, 0, sizeof(uint32_t)));
-      }
+      char* h;
+      if ((rc = one_launch_block(s, &h))) return rc;
+      if ((rc = s->one.dOneTicket.ensure_zeroed_once(1))) return rc;
       const uint32_t rpb = (uint32_t)std::max<uint64_t>(64, ((n_pub + 1023) / 1024 + 63) / 64 * 64);  // <= 1024 workgroups
       const uint32_t n_blocks = (uint32_t)((n_pub + rpb - 1) / rpb);
-      if ((rc = s->dOnePart.ensure((size_t)n_blocks * 64))) return rc;
+      if ((rc = s->one.dOnePart.ensure((size_t)n_blocks * 64))) return rc;
       test_pause();
       if ((rc = wait_searches_in_flight(s, s->stream))) return rc;  // (device searches queued on other streams)
-      char* h = s->hOnePin;
       memcpy(h, queries, qbytes);
       SingleQueryArgs a;
       a.q_in = (const float*)h;
-      a.X = s->dX;
-      a.inv_norm = s->dInv;
-      a.part = s->dOnePart.p;
-      a.ticket = s->dOneTicket;
+      a.X = s->rows.dX.p;
+      a.inv_norm = s->rows.dInv.p;
+      a.part = s->one.dOnePart.p;
+      a.ticket = s->one.dOneTicket.p;
       a.out_ids = (uint64_t*)(h + kOneQ);
       a.out_dist = (float*)(h + kOneQ + 512);
       a.out_count = (uint32_t*)(h + kOneQ + 768);
@@ -237,20 +279,7 @@ static int knn_host_direct(ehx_space* s, size_t n_queries, const float* queries,
       a.k = k;
       a.metric = s->metric;
       HIP_TRY(launch_single_query(a, n_blocks, s->stream));
-      volatile uint32_t* flag = (volatile uint32_t*)a.done_flag;
-      bool seen = false;
-      for (uint32_t spin = 0; spin < 4000000u; ++spin) {   // ~ tens of milliseconds at most, then ask the runtime
-        if (*flag == a.seq) {
-          seen = true;
-          break;
-        }
-        __builtin_ia32_pause();
-      }
-      if (!seen) {
-        HIP_TRY(hipStreamSynchronize(s->stream));
-        if (*flag != a.seq) return fail(EHX_EINTERNAL, "single-query kernel finished without publishing its result");
-      }
-      std::atomic_thread_fence(std::memory_order_acquire);
+      if ((rc = one_launch_wait(s, a.done_flag, a.seq, "single-query kernel"))) return rc;
       memcpy(out_ids, a.out_ids, k * sizeof(uint64_t));
       memcpy(out_dist, a.out_dist, k * sizeof(float));
       out_count[0] = *a.out_count;
@@ -264,12 +293,8 @@ static int knn_host_direct(ehx_space* s, size_t n_queries, const float* queries,
     // the graph search kernel reads the raw query from host-visible memory, prepares it itself, walks the graph (one
     // wave) and writes the answer into host-visible memory — one launch instead of prepare + search + two copies.
     if (one_on && n_queries == 1 && k <= 64 && s->params.mode == EHX_MODE_GRAPH && s->n > 0 && s->ld <= 4096) {
-      constexpr size_t kOneQ = 16384;
-      if (!s->hOnePin) {
-        HIP_TRY(hipHostMalloc((void**)&s->hOnePin, kOneQ + 2048, hipHostMallocCoherent | hipHostMallocMapped));
-        memset(s->hOnePin, 0, kOneQ + 2048);
-      }
-      char* h = s->hOnePin;
+      char* h;
+      if ((rc = one_launch_block(s, &h))) return rc;
       memcpy(h, queries, qbytes);
       GraphOneLaunch one;
       one.q_host = (const float*)h;
@@ -279,36 +304,23 @@ static int knn_host_direct(ehx_space* s, size_t n_queries, const float* queries,
       float* o_dist = (float*)(h + kOneQ + 512);
       uint32_t* o_cnt = (uint32_t*)(h + kOneQ + 768);
       if ((rc = knn_graph_locked(s, s->stream, 1, nullptr, k, o_ids, o_dist, o_cnt, &one))) return rc;
-      volatile uint32_t* flag = (volatile uint32_t*)one.done_flag;
-      bool seen = false;
-      for (uint32_t spin = 0; spin < 4000000u; ++spin) {
-        if (*flag == one.seq) {
-          seen = true;
-          break;
-        }
-        __builtin_ia32_pause();
-      }
-      if (!seen) {
-        HIP_TRY(hipStreamSynchronize(s->stream));
-        if (*flag != one.seq) return fail(EHX_EINTERNAL, "graph search kernel finished without publishing its result");
-      }
-      std::atomic_thread_fence(std::memory_order_acquire);
+      if ((rc = one_launch_wait(s, one.done_flag, one.seq, "graph search kernel"))) return rc;
       memcpy(out_ids, o_ids, k * sizeof(uint64_t));
       memcpy(out_dist, o_dist, k * sizeof(float));
       out_count[0] = *o_cnt;
       s->n_one_launch += 1;
       return EHX_OK;
     }
-    if ((rc = s->dQraw.ensure(n_queries * s->dims))) return rc;
-    if (!s->hSmallPin) HIP_TRY(hipHostMalloc((void**)&s->hSmallPin, 2 * kSmallCall, hipHostMallocDefault));
-    if ((rc = s->dSmallOut.ensure(kSmallCall / sizeof(uint64_t)))) return rc;
-    uint64_t* d_ids = s->dSmallOut.p;
+    if ((rc = s->scr.dQraw.ensure(n_queries * s->dims))) return rc;
+    if ((rc = s->scr.hSmallPin.ensure(2 * kSmallCall))) return rc;
+    if ((rc = s->scr.dSmallOut.ensure(kSmallCall / sizeof(uint64_t)))) return rc;
+    uint64_t* d_ids = s->scr.dSmallOut.p;
     float* d_dist = (float*)(d_ids + nk);
     uint32_t* d_cnt = (uint32_t*)(d_dist + nk);
-    memcpy(s->hSmallPin, queries, qbytes);
-    HIP_TRY(hipMemcpyAsync(s->dQraw.p, s->hSmallPin, qbytes, hipMemcpyHostToDevice, s->stream));
-    if ((rc = knn_device_locked(s, s->stream, n_queries, s->dQraw.p, k, d_ids, d_dist, d_cnt))) return rc;
-    char* h = s->hSmallPin + kSmallCall;
+    memcpy(s->scr.hSmallPin.p, queries, qbytes);
+    HIP_TRY(hipMemcpyAsync(s->scr.dQraw.p, s->scr.hSmallPin.p, qbytes, hipMemcpyHostToDevice, s->stream));
+    if ((rc = knn_device_locked(s, s->stream, n_queries, s->scr.dQraw.p, k, d_ids, d_dist, d_cnt))) return rc;
+    char* h = s->scr.hSmallPin.p + kSmallCall;
     HIP_TRY(hipMemcpyAsync(h, d_ids, out_bytes, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     memcpy(out_ids, h, nk * sizeof(uint64_t));
@@ -352,26 +364,20 @@ static int knn_host_direct(ehx_space* s, size_t n_queries, const float* queries,
   } release{s, hs};
   const size_t ids_b = nk * sizeof(uint64_t), dist_b = nk * sizeof(float);
   const size_t need = qbytes + out_bytes;
-  if (!hs->st) {
-    HIP_TRY(hipStreamCreateWithFlags(&hs->st, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreateWithFlags(&hs->in_ev, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&hs->done_ev, hipEventDisableTiming));
-  }
-  if (hs->pin_bytes < need) {
+  if ((rc = hs->st.ensure(hipStreamNonBlocking))) return rc;
+  if ((rc = hs->in_ev.ensure(hipEventDisableTiming))) return rc;
+  if ((rc = hs->done_ev.ensure(hipEventDisableTiming))) return rc;
+  if (hs->pin.n < need) {
     HIP_TRY(hipStreamSynchronize(hs->st));
-    if (hs->pin) (void)hipHostFree(hs->pin);
-    hs->pin = nullptr;
-    hs->pin_bytes = 0;
-    HIP_TRY(hipHostMalloc((void**)&hs->pin, need, hipHostMallocDefault));
-    hs->pin_bytes = need;
+    if ((rc = hs->pin.ensure(need))) return rc;
   }
   if ((rc = hs->dq.ensure(n_queries * s->dims))) return rc;
   if ((rc = hs->dout.ensure(out_bytes))) return rc;
   uint64_t* d_ids = (uint64_t*)hs->dout.p;
   float* d_dist = (float*)(hs->dout.p + ids_b);
   uint32_t* d_cnt = (uint32_t*)(hs->dout.p + ids_b + dist_b);
-  memcpy(hs->pin, queries, qbytes);
-  HIP_TRY(hipMemcpyAsync(hs->dq.p, hs->pin, qbytes, hipMemcpyHostToDevice, hs->st));
+  memcpy(hs->pin.p, queries, qbytes);
+  HIP_TRY(hipMemcpyAsync(hs->dq.p, hs->pin.p, qbytes, hipMemcpyHostToDevice, hs->st));
   HIP_TRY(hipEventRecord(hs->in_ev, hs->st));
   // The int8 engine's first stage — all of a batch unless queries lose their certificate — runs in one of the space's two
   // scratch sets WITHOUT the pipeline-wide lock: this call's launches queue up on the space's stream behind the other
@@ -394,26 +400,26 @@ static int knn_host_direct(ehx_space* s, size_t n_queries, const float* queries,
     std::unique_lock<std::mutex> ql(s->i8_enqueue_mu);   // (this batch's launches go onto the stream as one block)
     HIP_TRY(hipStreamWaitEvent(s->stream, hs->in_ev, 0));
     if ((rc = flat_pass8(s, n_pub, set, s->stream, n_queries, hs->dq.p, k, d_ids, d_dist, d_cnt, false, &kprime_used))) return rc;
-    HIP_TRY(hipMemcpyAsync(sc.hUncertPin, sc.dUncert, sizeof(unsigned long long), hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipEventRecord(sc.verdict, s->stream));
+    HIP_TRY(hipMemcpyAsync(sc.buf.hUncertPin.p, sc.buf.dUncert.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipEventRecord(sc.buf.verdict, s->stream));
     ql.unlock();
     // the results start their way back NOW, before the verdict is known (it is clean for all but a few batches in a
     // thousand): one host wait per batch instead of two in a row — verdict, then copy.  A batch that did lose queries runs
     // the rest of the chain below and copies again (same slot stream: in order, the later copy wins).
     // (it waits for the verdict's event — recorded right behind the re-rank and the 8-byte verdict copy; a marker of its own
     // cost the queue another ~6 us per batch)
-    HIP_TRY(hipStreamWaitEvent(hs->st, sc.verdict, 0));
-    HIP_TRY(hipMemcpyAsync(hs->pin + qbytes, hs->dout.p, out_bytes, hipMemcpyDeviceToHost, hs->st));
+    HIP_TRY(hipStreamWaitEvent(hs->st, sc.buf.verdict, 0));
+    HIP_TRY(hipMemcpyAsync(hs->pin.p + qbytes, hs->dout.p, out_bytes, hipMemcpyDeviceToHost, hs->st));
     copied_early = true;
-    HIP_TRY(hipEventSynchronize(sc.verdict));
+    HIP_TRY(hipEventSynchronize(sc.buf.verdict));
     count_scan_batch(s, n_queries, n_pub, k, 1);
-    if (*sc.hUncertPin == 0) {
+    if (*sc.buf.hUncertPin.p == 0) {
       done = true;
       s->n_i8_queries += n_queries;
       i8_adapt(s, n_queries, 0, 0, kprime_used);   // a clean batch: the score decays
     } else {  // which queries, and why: the engine chain continues with them (below, under the pipeline lock)
-      HIP_TRY(hipMemsetAsync(sc.dUncert, 0, sizeof(unsigned long long), s->stream));
-      if ((rc = collect_uncertified(s->stream, sc.dUflags.p, n_queries, nullptr, &failed, &n_short))) return rc;
+      HIP_TRY(hipMemsetAsync(sc.buf.dUncert.p, 0, sizeof(unsigned long long), s->stream));
+      if ((rc = collect_uncertified(s->stream, sc.buf.dUflags.p, n_queries, nullptr, &failed, &n_short))) return rc;
       have_failed = true;
     }
   }
@@ -425,7 +431,7 @@ static int knn_host_direct(ehx_space* s, size_t n_queries, const float* queries,
       return rc;
     HIP_TRY(hipEventRecord(hs->done_ev, s->stream));
   }
-  char* ho = hs->pin + qbytes;
+  char* ho = hs->pin.p + qbytes;
   if (!(done && copied_early)) {
     HIP_TRY(hipStreamWaitEvent(hs->st, hs->done_ev, 0));
     HIP_TRY(hipMemcpyAsync(ho, hs->dout.p, out_bytes, hipMemcpyDeviceToHost, hs->st));
@@ -538,20 +544,7 @@ int ehx_knn_keys(ehx_space* s, size_t n_queries, const float* queries, uint32_t 
   if (rc) return rc;
   std::shared_lock<std::shared_mutex> rl(s->mu);
   if (s->dropped) return fail(EHX_ENOTFOUND, "Not found");
-  uint64_t off = 0;
-  std::string key;
-  for (size_t i = 0; i < n_queries; ++i) {
-    for (uint32_t j = 0; j < k; ++j) {
-      key_off[i * k + j] = off;
-      if (j < out_count[i] && key_for_id(s, out_ids[i * k + j], &key) == EHX_OK) {
-        if (off + key.size() > arena_cap) return fail(EHX_ERANGE, "key arena too small");
-        memcpy(key_arena + off, key.data(), key.size());
-        off += key.size();
-      }
-    }
-  }
-  key_off[n_queries * k] = off;
-  return EHX_OK;
+  return fill_key_arena(s, n_queries, k, out_ids, out_count, key_arena, arena_cap, key_off);
 }
 
 int ehx_knn_by_key(ehx_space* s, const char* key, size_t klen, uint32_t k, uint64_t* out_ids, float* out_dist,
@@ -654,11 +647,11 @@ int ehx_knn_by_keys(ehx_space* s, size_t n, const char* const* keys, const size_
   HIP_TRY(hipSetDevice(home->device));
   ByKeyScratch b;
   if ((rc = by_scratch(s, n, k, true, &b))) return rc;
-  if ((rc = s->dByIds.ensure(n))) return rc;
+  if ((rc = s->by.dByIds.ensure(n))) return rc;
   // (pageable host memory: the runtime stages it before the call returns)
-  HIP_TRY(hipMemcpyAsync(s->dByIds.p, ids.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, s->stream));
-  if (is_parent(s)) rc = sharded_by_ids_locked(s, n, s->dByIds.p, k, b);
-  else rc = by_ids_locked(s, s->stream, n, s->dByIds.p, k, b, b.o_ids, b.o_dist, b.o_cnt);
+  HIP_TRY(hipMemcpyAsync(s->by.dByIds.p, ids.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, s->stream));
+  if (is_parent(s)) rc = sharded_by_ids_locked(s, n, s->by.dByIds.p, k, b);
+  else rc = by_ids_locked(s, s->stream, n, s->by.dByIds.p, k, b, b.o_ids, b.o_dist, b.o_cnt);
   if (!rc) rc = by_copy_out(s->stream, out_ids, b.o_ids, ids_b, out_dist, b.o_dist, dist_b, out_count, b.o_cnt, cnt_b);
   if (rc) {  // launches of this call may still be in flight: drain them before the scratch goes to the next caller
     (void)hipStreamSynchronize(s->stream);
@@ -675,20 +668,7 @@ int ehx_knn_by_keys_keys(ehx_space* s, size_t n, const char* const* keys, const 
   if (rc) return rc;
   std::shared_lock<std::shared_mutex> rl(s->mu);
   if (s->dropped) return fail(EHX_ENOTFOUND, "Not found");
-  uint64_t off = 0;
-  std::string key;
-  for (size_t i = 0; i < n; ++i) {
-    for (uint32_t j = 0; j < k; ++j) {
-      key_off[i * k + j] = off;
-      if (j < out_count[i] && key_for_id(s, out_ids[i * k + j], &key) == EHX_OK) {
-        if (off + key.size() > arena_cap) return fail(EHX_ERANGE, "key arena too small");
-        memcpy(key_arena + off, key.data(), key.size());
-        off += key.size();
-      }
-    }
-  }
-  key_off[n * k] = off;
-  return EHX_OK;
+  return fill_key_arena(s, n, k, out_ids, out_count, key_arena, arena_cap, key_off);
 }
 
 int ehx_knn_by_ids_device(ehx_space* s, void* stream, size_t n, const uint64_t* d_row_ids, uint32_t k,

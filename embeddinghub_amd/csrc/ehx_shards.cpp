@@ -136,10 +136,10 @@ int sharded_knn_locked(ehx_space* p, size_t nq, const float* h_queries, const fl
   HIP_TRY(hipSetDevice(home));
   const size_t o_dist = nq * k * sizeof(uint64_t), o_cnt = o_dist + nq * k * sizeof(float);
   const size_t P = (o_cnt + nq * sizeof(uint32_t) + 15) / 16 * 16;  // one shard's packed result
-  if ((rc = p->dGPack.ensure(G * P))) return rc;
-  if ((rc = p->dOutIds.ensure(nq * k))) return rc;
-  if ((rc = p->dOutDist.ensure(nq * k))) return rc;
-  if ((rc = p->dOutCount.ensure(nq))) return rc;
+  if ((rc = p->xch.dGPack.ensure(G * P))) return rc;
+  if ((rc = p->scr.dOutIds.ensure(nq * k))) return rc;
+  if ((rc = p->scr.dOutDist.ensure(nq * k))) return rc;
+  if ((rc = p->scr.dOutCount.ensure(nq))) return rc;
   if (d_queries) {  // the caller's stream produced the queries: they must be complete before the shards read them
     HIP_TRY(hipSetDevice(qdev));
     HIP_TRY(hipStreamSynchronize(caller_stream));
@@ -151,18 +151,18 @@ int sharded_knn_locked(ehx_space* p, size_t nq, const float* h_queries, const fl
     std::lock_guard<std::mutex> cl(c->scratch_mu);
     HIP_TRY(hipSetDevice(c->device));
     int r;
-    if ((r = c->dQraw.ensure(nq * c->dims))) return r;
-    if ((r = c->dOutPack.ensure(P))) return r;
-    if (!c->xev) HIP_TRY(hipEventCreateWithFlags(&c->xev, hipEventDisableTiming));
-    if (d_queries) HIP_TRY(hipMemcpyPeerAsync(c->dQraw.p, c->device, d_queries, qdev, qbytes, c->stream));
-    else HIP_TRY(hipMemcpyAsync(c->dQraw.p, h_queries, qbytes, hipMemcpyHostToDevice, c->stream));
-    unsigned char* pk = c->dOutPack.p;
-    if ((r = knn_device_locked(c, c->stream, nq, c->dQraw.p, k, (uint64_t*)pk, (float*)(pk + o_dist),
+    if ((r = c->scr.dQraw.ensure(nq * c->dims))) return r;
+    if ((r = c->xch.dOutPack.ensure(P))) return r;
+    if ((r = c->xch.xev.ensure(hipEventDisableTiming))) return r;
+    if (d_queries) HIP_TRY(hipMemcpyPeerAsync(c->scr.dQraw.p, c->device, d_queries, qdev, qbytes, c->stream));
+    else HIP_TRY(hipMemcpyAsync(c->scr.dQraw.p, h_queries, qbytes, hipMemcpyHostToDevice, c->stream));
+    unsigned char* pk = c->xch.dOutPack.p;
+    if ((r = knn_device_locked(c, c->stream, nq, c->scr.dQraw.p, k, (uint64_t*)pk, (float*)(pk + o_dist),
                                (uint32_t*)(pk + o_cnt))))
       return r;
     // the one exchange step
-    HIP_TRY(hipMemcpyPeerAsync(p->dGPack.p + i * P, home, pk, c->device, P, c->stream));
-    HIP_TRY(hipEventRecord(c->xev, c->stream));
+    HIP_TRY(hipMemcpyPeerAsync(p->xch.dGPack.p + i * P, home, pk, c->device, P, c->stream));
+    HIP_TRY(hipEventRecord(c->xch.xev, c->stream));
     return EHX_OK;
   });
   if (rc) {
@@ -174,19 +174,19 @@ int sharded_knn_locked(ehx_space* p, size_t nq, const float* h_queries, const fl
     return rc;
   }
   HIP_TRY(hipSetDevice(home));
-  for (size_t i = 0; i < G; ++i) HIP_TRY(hipStreamWaitEvent(p->stream, p->shards[i]->xev, 0));
-  const unsigned char* gp = p->dGPack.p;
+  for (size_t i = 0; i < G; ++i) HIP_TRY(hipStreamWaitEvent(p->stream, p->shards[i]->xch.xev, 0));
+  const unsigned char* gp = p->xch.dGPack.p;
   HIP_TRY(launch_merge_lists((const uint64_t*)gp, (const float*)(gp + o_dist), (const uint32_t*)(gp + o_cnt),
-                             (uint32_t)nq, k, (uint32_t)G, p->dOutIds.p, p->dOutDist.p, p->dOutCount.p, p->stream, P, P,
+                             (uint32_t)nq, k, (uint32_t)G, p->scr.dOutIds.p, p->scr.dOutDist.p, p->scr.dOutCount.p, p->stream, P, P,
                              P, (uint64_t)G, 1));
   if (out_on_device) {
-    HIP_TRY(hipMemcpyPeerAsync(out_ids, qdev, p->dOutIds.p, home, nq * k * sizeof(uint64_t), p->stream));
-    HIP_TRY(hipMemcpyPeerAsync(out_dist, qdev, p->dOutDist.p, home, nq * k * sizeof(float), p->stream));
-    HIP_TRY(hipMemcpyPeerAsync(out_count, qdev, p->dOutCount.p, home, nq * sizeof(uint32_t), p->stream));
+    HIP_TRY(hipMemcpyPeerAsync(out_ids, qdev, p->scr.dOutIds.p, home, nq * k * sizeof(uint64_t), p->stream));
+    HIP_TRY(hipMemcpyPeerAsync(out_dist, qdev, p->scr.dOutDist.p, home, nq * k * sizeof(float), p->stream));
+    HIP_TRY(hipMemcpyPeerAsync(out_count, qdev, p->scr.dOutCount.p, home, nq * sizeof(uint32_t), p->stream));
   } else {
-    HIP_TRY(hipMemcpyAsync(out_ids, p->dOutIds.p, nq * k * sizeof(uint64_t), hipMemcpyDeviceToHost, p->stream));
-    HIP_TRY(hipMemcpyAsync(out_dist, p->dOutDist.p, nq * k * sizeof(float), hipMemcpyDeviceToHost, p->stream));
-    HIP_TRY(hipMemcpyAsync(out_count, p->dOutCount.p, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipMemcpyAsync(out_ids, p->scr.dOutIds.p, nq * k * sizeof(uint64_t), hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipMemcpyAsync(out_dist, p->scr.dOutDist.p, nq * k * sizeof(float), hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipMemcpyAsync(out_count, p->scr.dOutCount.p, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, p->stream));
   }
   HIP_TRY(hipStreamSynchronize(p->stream));  // (the shards' scratch may be reused by the next call: all of it is done)
   p->n_queries += nq;

@@ -21,144 +21,115 @@ Engine& engine() {
 
 
 int ensure_stage(ehx_space* s, size_t bytes) {
-  if (bytes <= s->hStageBytes) return EHX_OK;
-  if (s->hStage) (void)hipHostFree(s->hStage);
-  s->hStage = nullptr;
-  s->hStageBytes = 0;
-  HIP_TRY(hipHostMalloc((void**)&s->hStage, bytes, hipHostMallocDefault));
-  s->hStageBytes = bytes;
+  return s->wr.hStage.ensure((bytes + sizeof(float) - 1) / sizeof(float));
+}
+
+// pieces of grow(): the first `count` elements of the old array, and zeroes from element `from` to the new array's end
+template <class T>
+static int keep_prefix(DevBuf<T>& to, const DevBuf<T>& old, size_t count, hipStream_t st) {
+  if (count) HIP_TRY(hipMemcpyAsync(to.p, old.p, count * sizeof(T), hipMemcpyDeviceToDevice, st));
+  return EHX_OK;
+}
+template <class T>
+static int zero_tail(DevBuf<T>& b, size_t from, hipStream_t st) {
+  HIP_TRY(hipMemsetAsync(b.p + from, 0, (b.n - from) * sizeof(T), st));
   return EHX_OK;
 }
 
-// grow HBM arrays to hold `rows` rows (multiple of 256, zero-initialised, rowp = pad).
+// the groups of grow(), each: new arrays in local owners, filled on `st`, swapped in behind the synchronisation
+static int grow_scan16(ehx_space* s, uint64_t want, uint64_t keep, hipStream_t st) {
+  int rc;
+  const char* nm = s->name.c_str();
+  const unsigned long long wantl = want;
+  const uint64_t keep_t = round_up(keep, kTileRows16);   // the copy is stored in whole 256-row tiles: those that hold rows
+  DevBuf<__half> nx16;
+  DevBuf<float2> nr16;
+  // (+ tail padding: the scan's DMA reads three stage blocks / two tiles of row parameters ahead)
+  if (nx16.fresh(want * s->ld16 + kScan16TailPadHalves) || nr16.fresh(want + 2 * kTileRows16))
+    return fail(EHX_ENOMEM, "hipMalloc failed growing the scan copy of space '%s' to %llu rows", nm, wantl);
+  if ((rc = keep_prefix(nx16, s->f16.dX16, keep_t * s->ld16, st)) ||
+      (rc = keep_prefix(nr16, s->f16.dRowp16, keep, st)) || (rc = zero_tail(nx16, keep_t * s->ld16, st)))
+    return rc;
+  HIP_TRY(launch_rowp_pad(nr16.p, keep, nr16.n - keep, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  s->f16.dX16.swap(nx16);
+  s->f16.dRowp16.swap(nr16);
+  return EHX_OK;
+}
+
+static int grow_scan8(ehx_space* s, uint64_t want, uint64_t keep, hipStream_t st) {
+  int rc;
+  const char* nm = s->name.c_str();
+  const unsigned long long wantl = want;
+  const uint64_t keep_t = round_up(keep, kTileRows16);   // the copy is stored in whole 256-row tiles: those that hold rows
+  DevBuf<int8_t> nx8;
+  DevBuf<float4> nr8, nt8;
+  DevBuf<float> ng8;
+  DevBuf<uint8_t> np8;
+  const uint64_t tiles = want / kTileRows16, keep_tiles = keep_t / kTileRows16;
+  if (nx8.fresh(want * s->ld8 + kScan8TailPadBytes) || nr8.fresh(want + 2 * kTileRows16) || nt8.fresh(tiles + 2) ||
+      ng8.fresh((tiles + 2) * 16) || np8.fresh(want))
+    return fail(EHX_ENOMEM, "hipMalloc failed growing the int8 scan copy of space '%s' to %llu rows", nm, wantl);
+  if ((rc = keep_prefix(nx8, s->i8.dX8, keep_t * s->ld8, st)) || (rc = keep_prefix(nr8, s->i8.dRowp8, keep_t, st)) ||
+      (rc = keep_prefix(nt8, s->i8.dTilep8, keep_tiles, st)) ||
+      (rc = keep_prefix(ng8, s->i8.dTileg8, keep_tiles * 16, st)) || (rc = keep_prefix(np8, s->i8.dPerm8, keep_t, st)) ||
+      (rc = zero_tail(ng8, keep_tiles * 16, st)))
+    return rc;
+  HIP_TRY(launch_perm8_pad(np8.p, keep_t, want - keep_t, st));
+  if ((rc = zero_tail(nx8, keep_t * s->ld8, st))) return rc;
+  HIP_TRY(launch_rowp8_pad(nr8.p, keep_t, nr8.n - keep_t, st));
+  HIP_TRY(launch_tilep8_pad(nt8.p, keep_tiles, nt8.n - keep_tiles, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  s->i8.dX8.swap(nx8);
+  s->i8.dRowp8.swap(nr8);
+  s->i8.dTilep8.swap(nt8);
+  s->i8.dTileg8.swap(ng8);
+  s->i8.dPerm8.swap(np8);
+  return EHX_OK;
+}
+
+static int grow_search_copy(ehx_space* s, uint64_t want, uint64_t keep, hipStream_t st) {
+  int rc;
+  const char* nm = s->name.c_str();
+  const unsigned long long wantl = want;
+  DevBuf<float> nxs;
+  if (nxs.fresh(want * s->ld))
+    return fail(EHX_ENOMEM, "hipMalloc failed growing the search copy of space '%s' to %llu rows", nm, wantl);
+  if ((rc = keep_prefix(nxs, s->rows.dXs, keep * s->ld, st)) || (rc = zero_tail(nxs, keep * s->ld, st))) return rc;
+  HIP_TRY(hipStreamSynchronize(st));
+  s->rows.dXs.swap(nxs);
+  return EHX_OK;
+}
+
+// grow HBM arrays to hold `rows` rows (multiple of 256, zero-initialised, rowp = pad).  Each group of arrays is built in
+// local owners, filled on the space's stream and swapped in behind the synchronisation that follows its copies: the old
+// arrays die with the locals, and an error return frees what it had allocated.  (Group by group, not all at the end: old
+// and new scan copies of every group at once would raise the peak; a group that has moved is larger than `cap` needs.)
 int grow(ehx_space* s, uint64_t rows) {
-  uint64_t want = round_up(rows < 256 ? 256 : rows, 256);
+  const uint64_t want = round_up(rows < 256 ? 256 : rows, 256);
   if (want <= s->cap) return EHX_OK;
   HIP_TRY(hipDeviceSynchronize());  // no search may still read the old arrays
-  char* nx = nullptr;
-  float2* nr = nullptr;
-  float* ni = nullptr;
-  HIP_TRY(hipMalloc((void**)&nx, want * s->ld * s->esz));
-  hipError_t e1 = hipMalloc((void**)&nr, want * sizeof(float2));
-  hipError_t e2 = hipMalloc((void**)&ni, want * sizeof(float));
-  if (e1 != hipSuccess || e2 != hipSuccess) {
-    (void)hipFree(nx);
-    if (nr) (void)hipFree(nr);
-    if (ni) (void)hipFree(ni);
-    return fail(EHX_ENOMEM, "hipMalloc failed growing space '%s' to %llu rows", s->name.c_str(),
-                (unsigned long long)want);
-  }
-  const uint64_t keep = s->n;
-  if (keep) {
-    HIP_TRY(hipMemcpyAsync(nx, s->dX, keep * s->ld * s->esz, hipMemcpyDeviceToDevice, s->stream));
-    HIP_TRY(hipMemcpyAsync(nr, s->dRowp, keep * sizeof(float2), hipMemcpyDeviceToDevice, s->stream));
-    HIP_TRY(hipMemcpyAsync(ni, s->dInv, keep * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
-  }
-  HIP_TRY(hipMemsetAsync(nx + keep * s->ld * s->esz, 0, (want - keep) * s->ld * s->esz, s->stream));
-  HIP_TRY(hipMemsetAsync(ni + keep, 0, (want - keep) * sizeof(float), s->stream));
-  HIP_TRY(launch_rowp_pad(nr, keep, want - keep, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  if (s->has16) {
-    __half* nx16 = nullptr;
-    float2* nr16 = nullptr;
-    // (+ tail padding: the scan's DMA reads three stage blocks / two tiles of row parameters ahead)
-    hipError_t e3 = hipMalloc((void**)&nx16, (want * s->ld16 + kScan16TailPadHalves) * sizeof(__half));
-    hipError_t e4 = hipMalloc((void**)&nr16, (want + 2 * kTileRows16) * sizeof(float2));
-    if (e3 != hipSuccess || e4 != hipSuccess) {
-      if (nx16) (void)hipFree(nx16);
-      if (nr16) (void)hipFree(nr16);
-      (void)hipFree(nx);
-      (void)hipFree(nr);
-      (void)hipFree(ni);
-      return fail(EHX_ENOMEM, "hipMalloc failed growing the scan copy of space '%s' to %llu rows", s->name.c_str(),
-                  (unsigned long long)want);
-    }
-    // the scan copy is stored in whole 256-row tiles (scan16_index): copy the tiles that hold rows
-    const uint64_t keep16 = round_up(keep, kTileRows16);
-    if (keep) {
-      HIP_TRY(hipMemcpyAsync(nx16, s->dX16, keep16 * s->ld16 * sizeof(__half), hipMemcpyDeviceToDevice, s->stream));
-      HIP_TRY(hipMemcpyAsync(nr16, s->dRowp16, keep * sizeof(float2), hipMemcpyDeviceToDevice, s->stream));
-    }
-    HIP_TRY(hipMemsetAsync(nx16 + keep16 * s->ld16, 0,
-                           ((want - keep16) * s->ld16 + kScan16TailPadHalves) * sizeof(__half), s->stream));
-    HIP_TRY(launch_rowp_pad(nr16, keep, want + 2 * kTileRows16 - keep, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    if (s->dX16) (void)hipFree(s->dX16);
-    if (s->dRowp16) (void)hipFree(s->dRowp16);
-    s->dX16 = nx16;
-    s->dRowp16 = nr16;
-  }
-  if (s->has8) {
-    int8_t* nx8 = nullptr;
-    float4* nr8 = nullptr;
-    float4* nt8 = nullptr;
-    const uint64_t tiles = want / kTileRows16;
-    hipError_t e5 = hipMalloc((void**)&nx8, want * s->ld8 + kScan8TailPadBytes);
-    hipError_t e6 = hipMalloc((void**)&nr8, (want + 2 * kTileRows16) * sizeof(float4));
-    hipError_t e7 = hipMalloc((void**)&nt8, (tiles + 2) * sizeof(float4));
-    float* ng8 = nullptr;
-    uint8_t* np8 = nullptr;
-    hipError_t e8 = hipMalloc((void**)&ng8, (tiles + 2) * 16 * sizeof(float));
-    hipError_t e9 = hipMalloc((void**)&np8, want);
-    if (e5 != hipSuccess || e6 != hipSuccess || e7 != hipSuccess || e8 != hipSuccess || e9 != hipSuccess) {
-      if (nx8) (void)hipFree(nx8);
-      if (nr8) (void)hipFree(nr8);
-      if (nt8) (void)hipFree(nt8);
-      if (ng8) (void)hipFree(ng8);
-      if (np8) (void)hipFree(np8);
-      (void)hipFree(nx);
-      (void)hipFree(nr);
-      (void)hipFree(ni);
-      return fail(EHX_ENOMEM, "hipMalloc failed growing the int8 scan copy of space '%s' to %llu rows", s->name.c_str(),
-                  (unsigned long long)want);
-    }
-    const uint64_t keep8 = round_up(keep, kTileRows16), keep_tiles = keep8 / kTileRows16;
-    if (keep) {
-      HIP_TRY(hipMemcpyAsync(nx8, s->dX8, keep8 * s->ld8, hipMemcpyDeviceToDevice, s->stream));
-      HIP_TRY(hipMemcpyAsync(nr8, s->dRowp8, keep8 * sizeof(float4), hipMemcpyDeviceToDevice, s->stream));
-      HIP_TRY(hipMemcpyAsync(nt8, s->dTilep8, keep_tiles * sizeof(float4), hipMemcpyDeviceToDevice, s->stream));
-      HIP_TRY(hipMemcpyAsync(ng8, s->dTileg8, keep_tiles * 16 * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
-      HIP_TRY(hipMemcpyAsync(np8, s->dPerm8, keep8, hipMemcpyDeviceToDevice, s->stream));
-    }
-    HIP_TRY(hipMemsetAsync(ng8 + keep_tiles * 16, 0, (tiles + 2 - keep_tiles) * 16 * sizeof(float), s->stream));
-    HIP_TRY(launch_perm8_pad(np8, keep8, want - keep8, s->stream));
-    HIP_TRY(hipMemsetAsync(nx8 + keep8 * s->ld8, 0, (want - keep8) * s->ld8 + kScan8TailPadBytes, s->stream));
-    HIP_TRY(launch_rowp8_pad(nr8, keep8, want + 2 * kTileRows16 - keep8, s->stream));
-    HIP_TRY(launch_tilep8_pad(nt8, keep_tiles, tiles + 2 - keep_tiles, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    if (s->dX8) (void)hipFree(s->dX8);
-    if (s->dRowp8) (void)hipFree(s->dRowp8);
-    if (s->dTilep8) (void)hipFree(s->dTilep8);
-    if (s->dTileg8) (void)hipFree(s->dTileg8);
-    if (s->dPerm8) (void)hipFree(s->dPerm8);
-    s->dTileg8 = ng8;
-    s->dPerm8 = np8;
-    s->dX8 = nx8;
-    s->dRowp8 = nr8;
-    s->dTilep8 = nt8;
-  }
-  if (s->params.mode == EHX_MODE_GRAPH && !s->x_perm) {
-    float* nxs = nullptr;
-    if (hipMalloc((void**)&nxs, want * s->ld * sizeof(float)) != hipSuccess) {
-      (void)hipFree(nx);
-      (void)hipFree(nr);
-      (void)hipFree(ni);
-      return fail(EHX_ENOMEM, "hipMalloc failed growing the search copy of space '%s' to %llu rows", s->name.c_str(),
-                  (unsigned long long)want);
-    }
-    if (keep) HIP_TRY(hipMemcpyAsync(nxs, s->dXs, keep * s->ld * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
-    HIP_TRY(hipMemsetAsync(nxs + keep * s->ld, 0, (want - keep) * s->ld * sizeof(float), s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    if (s->dXs) (void)hipFree(s->dXs);
-    s->dXs = nxs;
-  }
-  if (s->dX) (void)hipFree(s->dX);
-  if (s->dRowp) (void)hipFree(s->dRowp);
-  if (s->dInv) (void)hipFree(s->dInv);
-  s->dX = nx;
-  if (s->x_perm) s->dXs = (float*)nx;  // one allocation: the rows ARE the search copy
-  s->dRowp = nr;
-  s->dInv = ni;
+  const hipStream_t st = s->stream;
+  const char* nm = s->name.c_str();
+  const unsigned long long wantl = want;
+  const uint64_t keep = s->n, row_bytes = s->ld * s->esz;
+  DevBuf<char> nx;
+  DevBuf<float2> nr;
+  DevBuf<float> ni;
+  int rc;
+  if ((rc = nx.fresh(want * row_bytes))) return rc;
+  if (nr.fresh(want) || ni.fresh(want)) return fail(EHX_ENOMEM, "hipMalloc failed growing space '%s' to %llu rows", nm, wantl);
+  if ((rc = keep_prefix(nx, s->rows.dX, keep * row_bytes, st)) || (rc = keep_prefix(nr, s->rows.dRowp, keep, st)) ||
+      (rc = keep_prefix(ni, s->rows.dInv, keep, st)) || (rc = zero_tail(nx, keep * row_bytes, st)) || (rc = zero_tail(ni, keep, st)))
+    return rc;
+  HIP_TRY(launch_rowp_pad(nr.p, keep, want - keep, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (s->has16 && (rc = grow_scan16(s, want, keep, st))) return rc;
+  if (s->has8 && (rc = grow_scan8(s, want, keep, st))) return rc;
+  if (s->params.mode == EHX_MODE_GRAPH && !s->x_perm && (rc = grow_search_copy(s, want, keep, st))) return rc;
+  s->rows.dX.swap(nx);  // (single-copy graph spaces: the rows ARE the search copy, ehx_space::xs)
+  s->rows.dRowp.swap(nr);
+  s->rows.dInv.swap(ni);
   s->cap = want;
   return EHX_OK;
 }
@@ -173,22 +144,23 @@ int ensure_rows(ehx_space* s, uint64_t rows) {
 
 
 int BatchClock::begin(hipStream_t st, uint32_t every) {
-  if (!start) {  // (created on first use, on the space's device; `start` last: it marks the set complete)
-    for (hipEvent_t* e : {&end, &fence_ev, &spare[0], &spare[1]})
-      if (!*e) HIP_TRY(hipEventCreate(e));
-    for (auto& pr : ring)
+  if (!ev.start) {  // (created on first use, on the space's device; `start` last: it marks the set complete)
+    int rc;
+    for (Event* e : {&ev.end, &ev.fence_ev, &ev.spare[0], &ev.spare[1]})
+      if ((rc = e->ensure())) return rc;
+    for (auto& pr : ev.ring)
       for (auto& e : pr)
-        if (!e) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipEventCreate(&start));
+        if ((rc = e.ensure())) return rc;
+    if ((rc = ev.start.ensure())) return rc;
   }
   const uint64_t b = every == kOutOfRing ? 0 : batches++;
   in_ring = every != kOutOfRing && b % every == every - 1;
   timed = in_ring || b == 0;
-  pair = in_ring ? ring[ring_count % kRing] : spare;
+  pair = in_ring ? ev.ring[ring_count % kRing] : ev.spare;
   if (timed) {
     timed_valid = false;   // (a pass that fails half way leaves no half-recorded batch for ehx_stats)
     last = nullptr;
-    HIP_TRY(hipEventRecord(start, st));
+    HIP_TRY(hipEventRecord(ev.start, st));
   }
   return EHX_OK;
 }
@@ -209,8 +181,9 @@ int BatchClock::scan_end(hipStream_t st) {
 int BatchClock::finish(hipStream_t st) {
   {
     std::lock_guard<std::mutex> l(fence_mu);
-    HIP_TRY(hipEventRecord(timed ? end : fence_ev, st));
-    fence = timed ? end : fence_ev;
+    Event& closing = timed ? ev.end : ev.fence_ev;
+    HIP_TRY(hipEventRecord(closing, st));
+    fence = closing;
     fence_own = st == own;
   }
   if (timed) {
@@ -247,13 +220,13 @@ int BatchClock::read(uint64_t* newest, double* last_scan_ms, double* last_total_
   HIP_TRY(hipEventSynchronize(f));
   float ms = 0;
   if (timed_valid && seq > *newest) {
-    HIP_TRY(hipEventSynchronize(end));
+    HIP_TRY(hipEventSynchronize(ev.end));
     *newest = seq;
     if (hipEventElapsedTime(&ms, last[0], last[1]) == hipSuccess) *last_scan_ms = ms;
-    if (hipEventElapsedTime(&ms, start, end) == hipSuccess) *last_total_ms = ms;
+    if (hipEventElapsedTime(&ms, ev.start, ev.end) == hipSuccess) *last_total_ms = ms;
   }
   for (uint64_t i = 0; i < std::min<uint64_t>(ring_count, kRing); ++i)
-    if (hipEventElapsedTime(&ms, ring[i][0], ring[i][1]) == hipSuccess) {
+    if (hipEventElapsedTime(&ms, ev.ring[i][0], ev.ring[i][1]) == hipSuccess) {
       *sum += ms;
       ++*got;
     }
@@ -262,13 +235,7 @@ int BatchClock::read(uint64_t* newest, double* last_scan_ms, double* last_total_
 
 void BatchClock::release() {
   std::lock_guard<std::mutex> l(fence_mu);
-  auto destroy = [](hipEvent_t& e) {
-    if (e) (void)hipEventDestroy(e);
-    e = nullptr;
-  };
-  for (hipEvent_t* e : {&start, &end, &fence_ev, &spare[0], &spare[1]}) destroy(*e);
-  for (auto& pr : ring)
-    for (auto& e : pr) destroy(e);
+  ev = {};
   fence = nullptr;
   last = pair = nullptr;
   timed_valid = false;
@@ -353,3 +320,9 @@ void resolve_keys(ehx_space* s, size_t n, const char* const* keys, const size_t*
 }
 
 }  // namespace ehx_impl
+
+// Test hook (not in include/ehx.h, in the spirit of EHX_TEST_PAUSE_US): how many device allocations, pinned allocations,
+// events and streams the owners of ehx_own.h hold in this process right now.
+extern "C" void ehx_test_live_resources(uint64_t out[4]) {
+  for (int i = 0; i < 4; ++i) out[i] = g_live[i].load(std::memory_order_relaxed);
+}

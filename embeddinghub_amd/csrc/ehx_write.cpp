@@ -103,9 +103,9 @@ namespace ehx_impl {
 
 // wait for a stream of the space: the writers' stream through the blocking event, any other by hipStreamSynchronize
 int sync_stream(ehx_space* s, hipStream_t st) {
-  if (st == s->wstream && s->wev) {
-    HIP_TRY(hipEventRecord(s->wev, st));
-    HIP_TRY(hipEventSynchronize(s->wev));
+  if (st == s->wr.wstream && s->wr.wev) {
+    HIP_TRY(hipEventRecord(s->wr.wev, st));
+    HIP_TRY(hipEventSynchronize(s->wr.wev));
   } else {
     HIP_TRY(hipStreamSynchronize(st));
   }
@@ -119,14 +119,14 @@ int sync_stream(ehx_space* s, hipStream_t st) {
 // of [row0, row0 + n) lies beyond the published row count.  n_after: the row count once this write is published.
 int refresh_scan16(ehx_space* s, uint64_t row0, uint64_t n, hipStream_t st, bool exclusive, uint64_t n_after) {
   if (!st) st = s->stream;
-  if (s->dXs && !s->x_perm && n)
-    HIP_TRY(launch_make_search_copy(s->dX, s->x_half, s->dInv, row0, n, s->ld, s->metric, s->dXs, st));
+  if (s->xs() && !s->x_perm && n)
+    HIP_TRY(launch_make_search_copy(s->rows.dX.p, s->x_half, s->rows.dInv.p, row0, n, s->ld, s->metric, s->xs(), st));
   if ((!s->has16 && !s->has8) || n == 0) return EHX_OK;  // (kept current whatever engine is selected right now)
   unsigned long long u = 0, u8[2] = {0, 0};
   if (s->has16) {
-    HIP_TRY(launch_make_scan16(s->dX, s->x_half, row0, n, s->dims, s->ld, s->ld16, s->metric, s->dX16, s->dRowp16,
-                               s->dUnsafe, st));
-    HIP_TRY(hipMemcpyAsync(&u, s->dUnsafe, sizeof(u), hipMemcpyDeviceToHost, st));
+    HIP_TRY(launch_make_scan16(s->rows.dX.p, s->x_half, row0, n, s->dims, s->ld, s->ld16, s->metric, s->f16.dX16.p, s->f16.dRowp16.p,
+                               s->f16.dUnsafe.p, st));
+    HIP_TRY(hipMemcpyAsync(&u, s->f16.dUnsafe.p, sizeof(u), hipMemcpyDeviceToHost, st));
   }
   if (s->has8) {
     // Full tiles are stored ordered by quantisation step (k_misc.hip).  Re-ordering moves rows inside a tile, so it
@@ -145,14 +145,14 @@ int refresh_scan16(ehx_space* s, uint64_t row0, uint64_t n, hipStream_t st, bool
     }
     int rc8;
     const uint64_t slo = sort_tiles ? r8 : 0, shi = sort_tiles ? e8 : 0;
-    if ((rc8 = s->dTileList.ensure((make_scan8_scratch_bytes(r8, e8 - r8, slo, shi) + 7) / 8))) return rc8;
-    HIP_TRY(launch_make_scan8(s->dX, s->x_half, r8, e8 - r8, s->dims, s->ld, s->ld8, s->metric, s->dX8, s->dRowp8,
-                              s->dTilep8, s->dPerm8, s->dTileg8, slo, shi, s->dTileList.p, s->dUnsafe8, st));
-    if (s->dTileList.n > (64u << 20) / 8) {  // (a bulk load's scratch — 9 bytes per row — is not kept)
+    if ((rc8 = s->i8.dTileList.ensure((make_scan8_scratch_bytes(r8, e8 - r8, slo, shi) + 7) / 8))) return rc8;
+    HIP_TRY(launch_make_scan8(s->rows.dX.p, s->x_half, r8, e8 - r8, s->dims, s->ld, s->ld8, s->metric, s->i8.dX8.p, s->i8.dRowp8.p,
+                              s->i8.dTilep8.p, s->i8.dPerm8.p, s->i8.dTileg8.p, slo, shi, s->i8.dTileList.p, s->i8.dUnsafe8.p, st));
+    if (s->i8.dTileList.n > (64u << 20) / 8) {  // (a bulk load's scratch — 9 bytes per row — is not kept)
       HIP_TRY(hipStreamSynchronize(st));
-      s->dTileList.release();
+      s->i8.dTileList.release();
     }
-    HIP_TRY(hipMemcpyAsync(u8, s->dUnsafe8, sizeof(u8), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(u8, s->i8.dUnsafe8.p, sizeof(u8), hipMemcpyDeviceToHost, st));
   }
   {
     int rcs = sync_stream(s, st);
@@ -196,7 +196,7 @@ static int write_rows_locked(ehx_space* s, size_t n, const std::vector<uint64_t>
                              std::vector<std::string>* new_keys, bool append_only) {
   if (s->frozen) return fail(EHX_EIMMUTABLE, "Cannot write to immutable space");
   HIP_TRY(hipSetDevice(s->device));
-  hipStream_t ws = s->wstream ? s->wstream : s->stream;
+  hipStream_t ws = s->wr.wstream ? s->wr.wstream : s->stream;
   // rows rewritten in place: in-flight device searches (enqueued without the lock being held any more) finish first
   if (!append_only) {
     int rcw = wait_searches_in_flight(s, ws);
@@ -234,7 +234,7 @@ static int write_rows_locked(ehx_space* s, size_t n, const std::vector<uint64_t>
       perm_uniq.assign(ids.begin(), ids.begin() + n);
       std::sort(perm_uniq.begin(), perm_uniq.end());
       perm_uniq.erase(std::unique(perm_uniq.begin(), perm_uniq.end()), perm_uniq.end());
-      if ((rc = s->dPermIds.ensure(perm_uniq.size()))) return rc;
+      if ((rc = s->rows.dPermIds.ensure(perm_uniq.size()))) return rc;
     }
     for (size_t i = 0; i < n && !touches_committed; ++i) touches_committed = ids[i] < old_n;
   }
@@ -246,8 +246,8 @@ static int write_rows_locked(ehx_space* s, size_t n, const std::vector<uint64_t>
   for (size_t i0 = 0; i0 < n; i0 += slab_rows, ++slab) {
     if (touches_committed) poison.armed = true;
     const size_t m = std::min(slab_rows, n - i0);
-    char* stage = (char*)s->hStage + (slab & 1) * half_bytes;
-    if (slab >= 2) HIP_TRY(hipEventSynchronize(s->sev[slab & 1]));  // the upload that last used this half
+    char* stage = (char*)s->wr.hStage.p + (slab & 1) * half_bytes;
+    if (slab >= 2) HIP_TRY(hipEventSynchronize(s->wr.sev[slab & 1]));  // the upload that last used this half
     stage_rows(stage, vecs + i0 * s->dims, m * s->dims, s->x_half);
     // contiguous run of fresh ids -> one 2D copy; otherwise row by row
     bool contiguous = true;
@@ -261,7 +261,7 @@ static int write_rows_locked(ehx_space* s, size_t n, const std::vector<uint64_t>
         HIP_TRY(hipMemcpyAsync(s->xrow(ids[i0 + i]), stage + i * row_bytes, row_bytes,
                                hipMemcpyHostToDevice, ws));
     }
-    HIP_TRY(hipEventRecord(s->sev[slab & 1], ws));
+    HIP_TRY(hipEventRecord(s->wr.sev[slab & 1], ws));
     for (size_t i = 0; i < m; ++i) {
       min_id = std::min(min_id, ids[i0 + i]);
       max_id = std::max(max_id, ids[i0 + i]);
@@ -272,17 +272,17 @@ static int write_rows_locked(ehx_space* s, size_t n, const std::vector<uint64_t>
     // single-copy graph space: the rows just written go into the search copy's block order, in place, exactly once
     // each (the permutation is its own inverse: a row written twice in this batch is permuted once)
     if (perm_run) {
-      HIP_TRY(launch_permute_blocks((float*)s->dX, s->ld, ids[0], n, nullptr, ws));
+      HIP_TRY(launch_permute_blocks((float*)s->rows.dX.p, s->ld, ids[0], n, nullptr, ws));
     } else {
-      HIP_TRY(hipMemcpyAsync(s->dPermIds.p, perm_uniq.data(), perm_uniq.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ws));
-      HIP_TRY(launch_permute_blocks((float*)s->dX, s->ld, 0, perm_uniq.size(), s->dPermIds.p, ws));
+      HIP_TRY(hipMemcpyAsync(s->rows.dPermIds.p, perm_uniq.data(), perm_uniq.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ws));
+      HIP_TRY(launch_permute_blocks((float*)s->rows.dX.p, s->ld, 0, perm_uniq.size(), s->rows.dPermIds.p, ws));
     }
     HIP_TRY(hipStreamSynchronize(ws));  // (the list lives on this stack frame; the rows are in block order from here on)
     poison.armed = false;
   }
   // per-row statistics over the touched id range (idempotent for untouched rows in between)
-  HIP_TRY(launch_row_stats(s->dX, s->x_half, min_id, max_id - min_id + 1, s->dims, s->ld, s->metric, s->dInv,
-                           s->dRowp, s->dMaxSumsq, ws, s->x_perm ? 1 : 0));
+  HIP_TRY(launch_row_stats(s->rows.dX.p, s->x_half, min_id, max_id - min_id + 1, s->dims, s->ld, s->metric, s->rows.dInv.p,
+                           s->rows.dRowp.p, s->rows.dMaxSumsq.p, ws, s->x_perm ? 1 : 0));
   if ((rc = refresh_scan16(s, min_id, max_id - min_id + 1, ws, !append_only, next))) return rc;
   if ((rc = sync_stream(s, ws))) return rc;
   // commit: the rows are resident and described — publish the keys and the new row count
