@@ -1,0 +1,201 @@
+// Exact kNN restricted to a caller's lists of row ids: ehx_knn_among (host pointers), ehx_knn_among_device, and
+// ehx_knn_among_keys (one shared list given as stored keys).  The listed rows are scanned exhaustively in the oracle's
+// arithmetic (k_among.hip), whatever the space's mode: a graph space answers from its stored rows, its graph is not walked.
+#include "ehx_internal.h"
+
+namespace {
+
+constexpr uint32_t kAmongGridTarget = 4096;   // workgroups a launch aims for (16 per CU): chosen, not measured
+constexpr uint32_t kAmongMaxBlocks = 1024;    // ... and at most this many key lists per query for the merge
+
+int among_check(ehx_space* s, size_t nq, uint32_t k, const void* q, const void* o_ids, const void* o_dist, const void* o_cnt) {
+  if (!valid_space(s)) return fail(EHX_EINVAL, "space is NULL");
+  if (k == 0) return fail(EHX_EINVAL, "k is 0");
+  if (k > EHX_MAX_K_PAGED) return fail(EHX_EUNSUPPORTED, "k=%u exceeds %u", k, EHX_MAX_K_PAGED);
+  if (!o_ids || !o_dist || !o_cnt || (nq && !q)) return fail(EHX_EINVAL, "NULL argument");
+  if (nq > (1u << 24)) return fail(EHX_EINVAL, "too many queries in one call: %zu", nq);
+  return EHX_OK;
+}
+
+int among_unsharded(const ehx_space* s, const char* what) {
+  if (s->dropped) return fail(EHX_ENOTFOUND, "Not found");
+  if (is_parent(s))
+    return fail(EHX_EUNSUPPORTED, "%s: space '%s' is row-sharded (filtered search over shards is not built yet)", what,
+                s->name.c_str());
+  return EHX_OK;
+}
+
+// an unsharded space, locked shared, scratch_mu held, its device current; everything is enqueued on `st`.
+// d_off == nullptr: every query shares d_ids[0, n_cand).  max_list: an upper bound of one list's length (0: n_cand) — it
+// sizes the grid only.
+int among_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, const uint64_t* d_ids,
+                 const uint64_t* d_off, size_t n_cand, size_t max_list, uint64_t* d_out_ids, float* d_out_dist,
+                 uint32_t* d_out_count) {
+  if (s->x_perm && s->poisoned.load())
+    return fail(EHX_EINTERNAL, "graph space: an in-place overwrite failed half way (rows left in raw order); drop and rebuild it");
+  if (s->ld > among_max_ld())   // (before anything is enqueued)
+    return fail(EHX_EUNSUPPORTED, "filtered search keeps a prepared query in LDS: rows of %u floats exceed %u", s->ld,
+                among_max_ld());
+  // the ONE read of the row count: every page's range check answers for the same prefix
+  const uint64_t n_pub = s->n.load(std::memory_order_acquire);
+  AmongArgs a = {};
+  a.X = s->rows.dX.p;
+  a.inv_norm = s->rows.dInv.p;
+  a.cand_ids = d_ids;
+  a.cand_off = d_off;
+  a.n_cand = n_cand;
+  a.n_rows = n_pub;
+  a.nq = (uint32_t)nq;
+  a.dims = s->dims;
+  a.ld = s->ld;
+  a.x_half = (uint32_t)s->x_half;
+  a.x_perm = s->x_perm ? 1u : 0u;
+  a.metric = s->metric;
+  const uint64_t longest = std::max<uint64_t>(1, max_list && max_list < n_cand ? max_list : n_cand);
+  const uint32_t step = among_step_rows(a);
+  const uint64_t units = among_tiled(a) ? (nq + kAmongTileQ - 1) / kAmongTileQ : nq;
+  a.n_blocks = (uint32_t)std::min<uint64_t>(
+      std::min<uint64_t>((longest + step - 1) / step, kAmongMaxBlocks), std::max<uint64_t>(1, kAmongGridTarget / units));
+  const uint32_t pages = (k + 63) / 64;
+  int rc;
+  if ((rc = s->scr.dQ.ensure(nq * s->ld))) return rc;
+  if ((rc = s->scr.dPart.ensure(nq * a.n_blocks * 64))) return rc;
+  if ((rc = s->scr.dMerged.ensure(nq * 64))) return rc;
+  if (pages > 1 && (rc = s->scr.dGthr.ensure(nq + 8))) return rc;
+  // (searches on other streams have read and written this scratch; this call's fence, below, makes a Set that rewrites
+  // rows in place wait for it in turn)
+  if ((rc = wait_searches_in_flight(s, st))) return rc;
+  if ((rc = s->clock.begin(st, BatchClock::kOutOfRing))) return rc;
+  HIP_TRY(launch_prep_queries(d_queries, (uint32_t)nq, s->dims, s->ld, (uint32_t)nq, s->metric, s->scr.dQ.p, st));
+  a.Q = s->scr.dQ.p;
+  a.out = s->scr.dPart.p;
+  if ((rc = s->clock.scan_begin(st))) return rc;
+  for (uint32_t pg = 0; pg < pages; ++pg) {
+    a.floor = pg ? s->scr.dGthr.p : nullptr;
+    HIP_TRY(launch_among(a, st));
+    HIP_TRY(launch_flat_merge(s->scr.dPart.p, (uint32_t)nq, a.n_blocks, 64, s->scr.dMerged.p, st, a.n_blocks));
+    if (pg + 1 < pages) HIP_TRY(launch_set_floor(s->scr.dMerged.p, (uint32_t)nq, s->scr.dGthr.p, st));
+    // (the merged keys ARE the canonical distances: a page is written from them — launch_rerank would recompute them from
+    // rows in the plain layout, which a single-copy graph space does not have)
+    HIP_TRY(launch_among_emit(s->scr.dMerged.p, (uint32_t)nq, std::min<uint32_t>(64, k - pg * 64), k, pg * 64, d_out_ids,
+                              d_out_dist, d_out_count, st));
+  }
+  if ((rc = s->clock.scan_end(st)) || (rc = s->clock.finish(st))) return rc;
+  s->n_queries += nq;
+  s->n_dist += d_off ? (uint64_t)n_cand : (uint64_t)nq * n_cand;
+  return EHX_OK;
+}
+
+// host pointers in, host pointers out, on the space's stream (scratch_mu held): ids [| offsets] staged in among.dLists
+int among_host_locked(ehx_space* s, size_t nq, const float* queries, uint32_t k, const uint64_t* cand_ids,
+                      const uint64_t* cand_off, size_t n_cand, uint64_t* out_ids, float* out_dist, uint32_t* out_count) {
+  const size_t n_off = cand_off ? nq + 1 : 0;
+  const size_t ids_b = nq * k * sizeof(uint64_t), dist_b = nq * k * sizeof(float), cnt_b = nq * sizeof(uint32_t);
+  int rc;
+  HIP_TRY(hipSetDevice(s->device));
+  if ((rc = s->among.dLists.ensure(n_cand + n_off + 1))) return rc;
+  if ((rc = s->among.dQraw.ensure(nq * s->dims))) return rc;
+  if ((rc = s->among.dOut.ensure(ids_b + dist_b + cnt_b))) return rc;
+  uint64_t* d_ids = s->among.dLists.p;
+  uint64_t* d_off = cand_off ? d_ids + n_cand : nullptr;
+  uint64_t* o_ids = (uint64_t*)s->among.dOut.p;
+  float* o_dist = (float*)(s->among.dOut.p + ids_b);
+  uint32_t* o_cnt = (uint32_t*)(s->among.dOut.p + ids_b + dist_b);
+  rc = EHX_OK;
+  auto run = [&]() -> int {
+    // (pageable host memory: the runtime stages it before the call returns; the staging buffers are this path's alone and
+    // the space's stream orders their reuse)
+    if (n_cand) HIP_TRY(hipMemcpyAsync(d_ids, cand_ids, n_cand * sizeof(uint64_t), hipMemcpyHostToDevice, s->stream));
+    if (d_off) HIP_TRY(hipMemcpyAsync(d_off, cand_off, n_off * sizeof(uint64_t), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->among.dQraw.p, queries, nq * s->dims * sizeof(float), hipMemcpyHostToDevice, s->stream));
+    size_t longest = n_cand;
+    if (cand_off) {
+      longest = 0;
+      for (size_t i = 0; i < nq; ++i) longest = std::max<size_t>(longest, cand_off[i + 1] - cand_off[i]);
+    }
+    int r = among_locked(s, s->stream, nq, s->among.dQraw.p, k, d_ids, d_off, n_cand, longest, o_ids, o_dist, o_cnt);
+    if (r) return r;
+    HIP_TRY(hipMemcpyAsync(out_ids, o_ids, ids_b, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipMemcpyAsync(out_dist, o_dist, dist_b, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipMemcpyAsync(out_count, o_cnt, cnt_b, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return EHX_OK;
+  };
+  rc = run();
+  if (rc) {  // launches of this call may still be in flight: drain them before the scratch goes to the next caller
+    (void)hipStreamSynchronize(s->stream);
+    (void)hipGetLastError();
+  }
+  return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ehx_knn_among(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, const uint64_t* cand_ids,
+                  const uint64_t* cand_off, size_t n_cand, uint64_t* out_ids, float* out_dist, uint32_t* out_count) {
+  int rc = among_check(s, n_queries, k, queries, out_ids, out_dist, out_count);
+  if (rc) return rc;
+  if (n_cand && !cand_ids) return fail(EHX_EINVAL, "NULL argument");
+  if (cand_off) {
+    if (cand_off[0] > cand_off[n_queries]) return fail(EHX_EINVAL, "cand_off is not non-decreasing");
+    for (size_t i = 0; i < n_queries; ++i)
+      if (cand_off[i] > cand_off[i + 1]) return fail(EHX_EINVAL, "cand_off is not non-decreasing at query %zu", i);
+    if (cand_off[n_queries] != n_cand)
+      return fail(EHX_EINVAL, "cand_off ends at %llu, not at n_cand = %zu", (unsigned long long)cand_off[n_queries], n_cand);
+  }
+  yield_to_writer(s);
+  std::shared_lock<std::shared_mutex> rl(s->mu);
+  if ((rc = among_unsharded(s, "ehx_knn_among"))) return rc;
+  if (n_queries == 0) return EHX_OK;
+  std::lock_guard<std::mutex> sl(s->scratch_mu);
+  return among_host_locked(s, n_queries, queries, k, cand_ids, cand_off, n_cand, out_ids, out_dist, out_count);
+}
+
+int ehx_knn_among_device(ehx_space* s, void* stream, size_t n_queries, const float* d_queries, uint32_t k,
+                         const uint64_t* d_cand_ids, const uint64_t* d_cand_off, size_t n_cand, size_t max_list_hint,
+                         uint64_t* d_out_ids, float* d_out_dist, uint32_t* d_out_count) {
+  int rc = among_check(s, n_queries, k, d_queries, d_out_ids, d_out_dist, d_out_count);
+  if (rc) return rc;
+  if (n_cand && !d_cand_ids) return fail(EHX_EINVAL, "NULL device pointer");
+  yield_to_writer(s);
+  std::shared_lock<std::shared_mutex> rl(s->mu);
+  if ((rc = among_unsharded(s, "ehx_knn_among_device"))) return rc;
+  if (n_queries == 0) return EHX_OK;
+  std::lock_guard<std::mutex> sl(s->scratch_mu);
+  HIP_TRY(hipSetDevice(s->device));
+  return among_locked(s, (hipStream_t)stream, n_queries, d_queries, k, d_cand_ids, d_cand_off, n_cand, max_list_hint,
+                      d_out_ids, d_out_dist, d_out_count);
+}
+
+int ehx_knn_among_keys(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, size_t n_allowed,
+                       const char* const* keys, const size_t* klens, uint64_t* out_ids, float* out_dist,
+                       uint32_t* out_count, size_t* bad_index) {
+  int rc = among_check(s, n_queries, k, queries, out_ids, out_dist, out_count);
+  if (rc) return rc;
+  if (n_allowed && (!keys || !klens)) return fail(EHX_EINVAL, "NULL argument");
+  yield_to_writer(s);
+  // ONE shared hold for key lookup and search: the answer describes one state of the space
+  std::shared_lock<std::shared_mutex> rl(s->mu);
+  if ((rc = among_unsharded(s, "ehx_knn_among_keys"))) return rc;
+  std::vector<uint64_t> ids(n_allowed);
+  {
+    std::shared_lock<std::shared_mutex> kl(s->kmu);
+    for (size_t i = 0; i < n_allowed; ++i) {
+      if (!keys[i]) return fail(EHX_EINVAL, "NULL argument");
+      if (implicit_id(s, keys[i], klens[i], &ids[i])) continue;
+      auto it = s->key_to_id.find(std::string(keys[i], klens[i]));
+      if (it == s->key_to_id.end()) {
+        if (bad_index) *bad_index = i;
+        return fail(EHX_ENOTFOUND, "Not found");
+      }
+      ids[i] = it->second;
+    }
+  }
+  if (n_queries == 0) return EHX_OK;
+  std::lock_guard<std::mutex> sl(s->scratch_mu);
+  return among_host_locked(s, n_queries, queries, k, ids.data(), nullptr, n_allowed, out_ids, out_dist, out_count);
+}
+
+}  // extern "C"

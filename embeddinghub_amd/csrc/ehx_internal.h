@@ -395,6 +395,14 @@ struct ehx_space {
     DevBuf<unsigned char> dByOut;
     Event by_ev;
   } by;
+  // exact kNN among a caller's id lists (ehx_among.cpp; scratch_mu): a host call's staged ids | offsets and its results.
+  // The prepared queries, the workgroups' key lists, the merged keys and the page floor are the exhaustive pass's
+  // (scr.dQ / dPart / dMerged / dGthr); the space's batch clock fences all of them across streams.
+  struct Among {
+    DevBuf<uint64_t> dLists;
+    DevBuf<float> dQraw;
+    DevBuf<unsigned char> dOut;
+  } among;
   // int8 filter scratch: everything ONE in-flight batch of the int8 pipeline owns — prepared queries, query tiles +
   // parameters, per-pass thresholds, sample scores, pools, running best list, verdict, batch clock.  TWO sets: a host
   // caller's batch can be enqueued behind another caller's on the space's stream while that one still waits for its
@@ -474,6 +482,7 @@ struct ehx_space {
     graph = {};
     scr = {};
     by = {};
+    among = {};
     one = {};
     xch = {};
     wr = {};
@@ -542,6 +551,9 @@ int collect_uncertified(hipStream_t st, const uint32_t* d_flags, size_t m, const
 int knn_device_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k,
                       uint64_t* d_ids, float* d_dist, uint32_t* d_count, const std::vector<uint32_t>* i8_failed = nullptr,
                       size_t i8_short = 0, uint32_t i8_kprime_in = 0, uint64_t n_pub = kNoSnapshot);
+
+// ---- ehx_search.cpp ----
+void yield_to_writer(const ehx_space* s);   // a search lets an exclusive writer that waits for the space's lock in first
 
 // ---- ehx_write.cpp ----
 int sync_stream(ehx_space* s, hipStream_t st);

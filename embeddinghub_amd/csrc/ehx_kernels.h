@@ -76,6 +76,18 @@ __device__ __forceinline__ uint64_t wave_sort64(uint64_t key, int lane) {
   return key;
 }
 
+// input: bitonic sequence across lanes; output ascending
+__device__ __forceinline__ uint64_t wave_bitonic_merge64(uint64_t key, int lane) {
+#pragma unroll
+  for (int j = 32; j > 0; j >>= 1) {
+    const uint64_t other = __shfl_xor(key, j, 64);
+    const uint64_t mn = key < other ? key : other;
+    const uint64_t mx = key < other ? other : key;
+    key = (lane & j) == 0 ? mn : mx;
+  }
+  return key;
+}
+
 // number of entries of the ascending array a[0..n) (any n) that are < key
 __device__ __forceinline__ uint32_t lower_bound_lds(const uint64_t* a, uint32_t n, uint64_t key) {
   uint32_t lo = 0, hi = n;
@@ -886,6 +898,35 @@ struct DropSelfArgs {
   uint32_t n, k;
 };
 hipError_t launch_drop_self(const DropSelfArgs& a, hipStream_t st);
+
+// exact kNN among a caller's list of row ids (k_among.hip): the canonical distance of every listed row, best 64
+// (distance, id) keys per workgroup -> out[q][n_blocks][64] (launch_flat_merge's input)
+constexpr uint32_t kAmongTileQ = 8;     // shared list: queries a workgroup applies a staged tile of rows to
+constexpr uint32_t kAmongTileRows = 8;  // ... rows per staged tile
+struct AmongArgs {
+  const float* Q;            // prepared queries [nq][ld] (launch_prep_queries)
+  const void* X;             // stored rows
+  const float* inv_norm;     // [cap] (cosine)
+  const uint64_t* cand_ids;  // [n_cand] global row ids; an id at or above n_rows is ignored
+  const uint64_t* cand_off;  // nullptr: every query shares cand_ids[0, n_cand); else [nq + 1], query q owns [off[q], off[q + 1])
+  const uint64_t* floor;     // optional, per query: only keys strictly above floor[q] are kept (paging for k > 64)
+  uint64_t* out;             // [nq][n_blocks][64]
+  uint64_t n_cand;
+  uint64_t n_rows;           // the search's snapshot of the row count
+  uint32_t nq, dims, ld;
+  uint32_t n_blocks;         // workgroups per query (or query tile): each walks its steps of the list in a grid-stride loop
+  uint32_t x_half;           // rows stored as binary16
+  uint32_t x_perm;           // fp32 rows stored in the search copy's block order (single-copy graph spaces)
+  int metric;
+};
+bool among_tiled(const AmongArgs& a);          // the shared-list kernel serves (cand_off == nullptr and the tiles fit in LDS)
+uint32_t among_max_ld();                       // longest row stride (floats) the kernels take: a prepared query must fit in LDS
+uint32_t among_step_rows(const AmongArgs& a);  // list entries one workgroup takes per step of its loop
+hipError_t launch_among(const AmongArgs& a, hipStream_t st);
+// a page of results from merged keys that hold exact canonical distances ([nq][64] ascending, launch_flat_merge): columns
+// [out_offset, out_offset + k) of rows of out_stride entries, k <= 64; the counts of pages after the first add up
+hipError_t launch_among_emit(const uint64_t* merged, uint32_t nq, uint32_t k, uint32_t out_stride, uint32_t out_offset,
+                             uint64_t* out_ids, float* out_dist, uint32_t* out_count, hipStream_t st);
 
 // per-row statistics for rows [row0, row0+n): inv_norm (cosine), rowp (a,b) for the scan epilogue;
 // *max_sumsq (optional) is raised to the largest |x|^2 seen (the certification margin's norm bound)

@@ -6,7 +6,7 @@
 // the wait is bounded (50 ms), so it can delay a search and never block one.  Once the writer has the lock the search
 // queues behind it on the lock itself.  (50 us per step, 50 ms in all: chosen, not measured.  With no writer waiting the
 // cost is one atomic load per call.)
-static void yield_to_writer(const ehx_space* s) {
+void ehx_impl::yield_to_writer(const ehx_space* s) {
   for (int i = 0; i < 1000 && s->excl_waiting.load(std::memory_order_acquire) != 0; ++i)
     std::this_thread::sleep_for(std::chrono::microseconds(50));
 }

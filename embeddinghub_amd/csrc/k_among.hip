@@ -1,0 +1,279 @@
+// Exact kNN among a caller's list of row ids (ehx_knn_among*): the canonical (oracle-order) distance of every listed row,
+// the best 64 (distance, id) keys per workgroup — out[q][block][64], the layout launch_flat_merge reads — and the page
+// writer that turns a query's merged keys into ids / distances / count.
+//   among_list_kernel   one query per workgroup, the rows read straight from HBM: a gather, bound by what the memory
+//                       system delivers for random whole rows.  Serves the per-query lists.
+//   among_tile_kernel   ONE list shared by every query: a workgroup stages 8 gathered rows in LDS and applies them to a tile
+//                       of 8 queries before it moves on, so a row makes one trip through the memory system per 8 pairs
+//                       (and the workgroups of the other query tiles, resident together, find it in L2).
+// Every distance comes from canon_dist / canon_dist_lane_t / canon_dist_group_t (ehx_kernels.h); the row layouts are those
+// gather_rows_kernel (k_bykey.hip) reads: fp32 rows as stored, binary16 rows widened exactly, single-copy graph rows in the
+// search copy's block order.  Cosine rows are scaled by inv_norm — one rounding per element, hnswlib-python's stored
+// normalised row — on the fly (list kernel) or as they are staged (tile kernel).
+#include "ehx_kernels.h"
+
+namespace ehx {
+
+namespace {
+
+typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
+
+enum { kLayoutF32 = 0, kLayoutF16 = 1, kLayoutPerm = 2 };
+
+constexpr uint32_t kLdsPad = 4;   // floats behind every LDS row: the 8 rows a 32-lane group reads fall into 32 banks
+
+__device__ __forceinline__ uint64_t among_key(float d, uint32_t id, bool ok, bool paged, uint64_t fl) {
+  uint64_t key = (ok && d == d) ? (((uint64_t)f32_to_ordered(d) << 32) | id) : kKeyInf;   // NaN: not a neighbour
+  if (paged && key <= fl) key = kKeyInf;   // paging (k > 64): only keys strictly above the previous page's last
+  return key;
+}
+
+// the 64 smallest of (best, 64 unsorted keys), ascending across the wave
+__device__ __forceinline__ uint64_t keep_best64(uint64_t best, uint64_t key, int lane) {
+  key = wave_sort64(key, lane);
+  const uint64_t rv = __shfl(key, 63 - lane, 64);
+  return wave_bitonic_merge64(best < rv ? best : rv, lane);
+}
+
+}  // namespace
+
+// Grid (queries, blocks): block b of query q walks steps b, b + gridDim.y, ... of the query's list until its end, a step
+// being 256 rows (fp32 rows: one lane per row, canon_dist_lane_t, 16-byte loads) or 64 rows (binary16 rows: canon_dist;
+// block-permuted rows: canon_dist_group_t, 16-byte loads; a 4-lane group per row).  The grid is sized from a hint of the
+// longest list; a hint that is too small costs time, never rows.  The query sits in LDS (permuted like the rows for the
+// block-permuted layout).
+template <int LAYOUT, int METRIC>
+__global__ __launch_bounds__(256) void among_list_kernel(const AmongArgs a) {
+  constexpr uint32_t kStep = LAYOUT == kLayoutF32 ? 256u : 64u;
+  extern __shared__ float4 among_lds[];
+  __shared__ uint64_t keys[256];
+  float* qs = (float*)among_lds;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const uint32_t q = blockIdx.x;
+  uint64_t lo = 0, hi = a.n_cand;
+  if (a.cand_off) {
+    lo = a.cand_off[q];
+    hi = a.cand_off[q + 1];
+    hi = hi < a.n_cand ? hi : a.n_cand;   // (the device form cannot check its offsets: never read beyond the id array)
+  }
+  const float* qv = a.Q + (size_t)q * a.ld;
+  for (uint32_t m = tid; m < a.ld; m += 256) qs[LAYOUT == kLayoutPerm ? search_copy_pos(m) : m] = qv[m];
+  __syncthreads();
+  constexpr bool scale = METRIC == 2;
+  constexpr int metric01 = METRIC == 0 ? 0 : 1;
+  const uint64_t fl = a.floor ? a.floor[q] : 0ull;
+  const bool paged = a.floor != nullptr;
+  uint64_t best = kKeyInf;
+  for (uint64_t p0 = lo + (uint64_t)blockIdx.y * kStep; p0 < hi; p0 += (uint64_t)gridDim.y * kStep) {
+    if (LAYOUT == kLayoutF32) {
+      const uint64_t p = p0 + (uint64_t)tid;
+      const uint64_t id = p < hi ? a.cand_ids[p] : ~0ull;
+      const bool ok = id < a.n_rows;
+      float d = 0.0f;
+      if (ok) {
+        const float* x = (const float*)a.X + (size_t)id * a.ld;
+        d = canon_dist_lane_t<metric01, scale>(qs, x, scale ? a.inv_norm[id] : 1.0f, a.dims);
+      }
+      keys[tid] = among_key(d, (uint32_t)id, ok, paged, fl);
+    } else {
+      const int g = tid >> 2, sub = tid & 3;
+      const uint64_t p = p0 + (uint64_t)g;
+      const uint64_t id = p < hi ? a.cand_ids[p] : ~0ull;
+      const bool ok = id < a.n_rows;   // (the same in the four lanes of a group: they walk a row together)
+      float d = 0.0f;
+      if (ok) {
+        const float xs = scale ? a.inv_norm[id] : 1.0f;
+        if (LAYOUT == kLayoutF16) {
+          d = canon_dist(metric01, qs, (const __half*)a.X + (size_t)id * a.ld, xs, scale, a.dims, sub);
+        } else {
+          d = canon_dist_group_t<metric01, scale>(qs, (const float*)a.X + (size_t)id * a.ld, sub, a.dims, xs);
+        }
+      }
+      if (sub == 0) keys[g] = among_key(d, (uint32_t)id, ok, paged, fl);
+    }
+    __syncthreads();
+    if ((uint32_t)wave < kStep / 64u) best = keep_best64(best, keys[tid], lane);
+    __syncthreads();
+  }
+  if (kStep > 64u) {   // the four waves' lists -> wave 0
+    keys[tid] = best;
+    __syncthreads();
+    if (wave == 0)
+      for (int w = 1; w < 4; ++w) {
+        const uint64_t rv = keys[w * 64 + 63 - lane];
+        best = wave_bitonic_merge64(best < rv ? best : rv, lane);
+      }
+  }
+  if (wave == 0) a.out[((size_t)q * gridDim.y + blockIdx.y) * 64 + lane] = best;
+}
+
+// Grid (query tiles, blocks), the query tile fastest: the workgroups that read the same chunks of the shared list run
+// together.  Block b walks chunks b, b + gridDim.y, ... of 64 list entries; a chunk goes through LDS in 8 steps of
+// kAmongTileRows rows — 32 lanes stage a row with 16-byte loads into plain, scaled fp32 (whatever the stored layout), then
+// each of the 64 four-lane groups evaluates one (row, query) pair with canon_dist from LDS.  After the chunk every wave
+// merges the 64 new keys of its two queries into their best-64 lists (registers).
+template <int LAYOUT, int METRIC>
+__global__ __launch_bounds__(256) void among_tile_kernel(const AmongArgs a) {
+  constexpr uint32_t QT = kAmongTileQ, R = kAmongTileRows;
+  static_assert(QT * R == 64 && QT == 8, "one (row, query) pair per 4-lane group; two queries per wave");
+  extern __shared__ float4 among_lds[];
+  __shared__ uint32_t row_id[R], row_ok[R];
+  const uint32_t lds = a.ld + kLdsPad;
+  float* qs = (float*)among_lds;                  // [QT][lds] the tile's prepared queries
+  float* xs = qs + (size_t)QT * lds;              // [R][lds] this step's rows
+  uint64_t* keys = (uint64_t*)(xs + (size_t)R * lds);   // [QT][64] this chunk's keys
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const uint32_t q0 = blockIdx.x * QT;
+  const uint32_t nqt = a.nq - q0 < QT ? a.nq - q0 : QT;
+  const uint32_t ld4 = a.ld >> 2, lds4 = lds >> 2;
+  for (uint32_t i = tid; i < QT * ld4; i += 256) {
+    const uint32_t qi = i / ld4, c = i - qi * ld4;
+    ((float4*)qs)[qi * lds4 + c] =
+        qi < nqt ? ((const float4*)a.Q)[(size_t)(q0 + qi) * ld4 + c] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  }
+  constexpr bool scale = METRIC == 2;
+  constexpr int metric01 = METRIC == 0 ? 0 : 1;
+  const bool paged = a.floor != nullptr;
+  const int g = tid >> 2, sub = tid & 3;
+  const uint32_t pr = (uint32_t)g & (R - 1), pq = (uint32_t)g / R;   // this group's pair: row slot, query of the tile
+  const uint64_t fl = (paged && pq < nqt) ? a.floor[q0 + pq] : 0ull;
+  const uint32_t sr = (uint32_t)tid >> 5, sl = (uint32_t)tid & 31u;  // staging: row slot, lane within the row's 32
+  uint64_t best[2] = {kKeyInf, kKeyInf};          // queries wave and wave + 4 of the tile
+  for (uint64_t c0 = (uint64_t)blockIdx.y * 64u; c0 < a.n_cand; c0 += (uint64_t)gridDim.y * 64u) {
+    keys[tid] = kKeyInf;
+    keys[tid + 256] = kKeyInf;
+    for (uint32_t st = 0; st < 64u / R && c0 + st * R < a.n_cand; ++st) {
+      const uint64_t p = c0 + st * R + sr;
+      const uint64_t id = p < a.n_cand ? a.cand_ids[p] : ~0ull;
+      const bool ok = id < a.n_rows;
+      if (sl == 0) {
+        row_id[sr] = (uint32_t)id;
+        row_ok[sr] = ok ? 1u : 0u;
+      }
+      if (ok) {   // (a row that is not staged leaves stale floats behind: its pairs' keys are dropped)
+        const float inv = scale ? a.inv_norm[id] : 1.0f;
+        float4* dst = (float4*)xs + sr * lds4;
+        if (LAYOUT == kLayoutF16) {
+          const half8_t* x = (const half8_t*)((const _Float16*)a.X + (size_t)id * a.ld);
+          for (uint32_t c = sl; c < (a.dims + 7u) >> 3; c += 32) {
+            const half8_t h = x[c];
+            float4 v0 = make_float4((float)h[0], (float)h[1], (float)h[2], (float)h[3]);
+            float4 v1 = make_float4((float)h[4], (float)h[5], (float)h[6], (float)h[7]);
+            if (scale) {
+              v0 = scale_f4(v0, inv);
+              v1 = scale_f4(v1, inv);
+            }
+            dst[2 * c] = v0;
+            dst[2 * c + 1] = v1;
+          }
+        } else if (LAYOUT == kLayoutPerm) {
+          // a 16-float block of the search copy's order: four 16-byte loads, the 4 x 4 transpose undone (search_copy_pos)
+          const float4* x = (const float4*)((const float*)a.X + (size_t)id * a.ld);
+          for (uint32_t b = sl; b < (a.dims + 15u) >> 4; b += 32) {
+            float4 v0 = x[4 * b], v1 = x[4 * b + 1], v2 = x[4 * b + 2], v3 = x[4 * b + 3];
+            if (scale) {
+              v0 = scale_f4(v0, inv);
+              v1 = scale_f4(v1, inv);
+              v2 = scale_f4(v2, inv);
+              v3 = scale_f4(v3, inv);
+            }
+            dst[4 * b] = make_float4(v0.x, v1.x, v2.x, v3.x);
+            dst[4 * b + 1] = make_float4(v0.y, v1.y, v2.y, v3.y);
+            dst[4 * b + 2] = make_float4(v0.z, v1.z, v2.z, v3.z);
+            dst[4 * b + 3] = make_float4(v0.w, v1.w, v2.w, v3.w);
+          }
+        } else {
+          const float4* x = (const float4*)((const float*)a.X + (size_t)id * a.ld);
+          for (uint32_t c = sl; c < (a.dims + 3u) >> 2; c += 32) dst[c] = scale ? scale_f4(x[c], inv) : x[c];
+        }
+      }
+      __syncthreads();
+      const float d = canon_dist(metric01, qs + (size_t)pq * lds, xs + (size_t)pr * lds, 1.0f, false, a.dims, sub);
+      if (sub == 0) keys[pq * 64 + st * R + pr] = among_key(d, row_id[pr], row_ok[pr] != 0 && pq < nqt, paged, fl);
+      __syncthreads();
+    }
+#pragma unroll
+    for (int j = 0; j < 2; ++j) best[j] = keep_best64(best[j], keys[(wave + 4 * j) * 64 + lane], lane);
+    __syncthreads();
+  }
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const uint32_t qi = (uint32_t)wave + 4u * j;
+    if (qi < nqt) a.out[((size_t)(q0 + qi) * gridDim.y + blockIdx.y) * 64 + lane] = best[j];
+  }
+}
+
+// One wave per query: a page of results from the query's merged keys (ascending, exact canonical distances): columns
+// [out_offset, out_offset + k) of a row of out_stride entries; entries beyond the count are id ~0 / +Inf; the count of a
+// later page is added to the earlier pages'.
+__global__ __launch_bounds__(64) void among_emit_kernel(const uint64_t* __restrict__ merged, uint32_t k,
+                                                        uint32_t out_stride, uint32_t out_offset,
+                                                        uint64_t* __restrict__ out_ids, float* __restrict__ out_dist,
+                                                        uint32_t* __restrict__ out_count) {
+  const uint32_t lane = threadIdx.x, q = blockIdx.x;
+  const uint64_t key = merged[(size_t)q * 64 + lane];
+  const uint32_t nvalid = (uint32_t)__builtin_popcountll(__ballot(key != kKeyInf));
+  const uint32_t cnt = nvalid < k ? nvalid : k;
+  if (lane < k) {
+    const bool ok = lane < cnt;
+    out_ids[(size_t)q * out_stride + out_offset + lane] = ok ? (uint64_t)(uint32_t)key : ~0ull;
+    out_dist[(size_t)q * out_stride + out_offset + lane] = ok ? ordered_to_f32((uint32_t)(key >> 32)) : __builtin_inff();
+  }
+  if (lane == 0) out_count[q] = (out_offset ? out_count[q] : 0u) + cnt;
+}
+
+namespace {
+
+size_t among_tile_lds(uint32_t ld) {
+  return (size_t)(kAmongTileQ + kAmongTileRows) * (ld + kLdsPad) * sizeof(float) + (size_t)kAmongTileQ * 64 * sizeof(uint64_t);
+}
+
+typedef void (*AmongFn)(const AmongArgs);
+#define EHX_AMONG_FNS(K) \
+  {K<kLayoutF32, 0>, K<kLayoutF32, 1>, K<kLayoutF32, 2>, K<kLayoutF16, 0>, K<kLayoutF16, 1>, K<kLayoutF16, 2>, \
+   K<kLayoutPerm, 0>, K<kLayoutPerm, 1>, K<kLayoutPerm, 2>}
+const AmongFn kTileFns[9] = EHX_AMONG_FNS(among_tile_kernel);   // [layout * 3 + metric]
+const AmongFn kListFns[9] = EHX_AMONG_FNS(among_list_kernel);
+#undef EHX_AMONG_FNS
+DynLdsAttr g_tile_lds, g_list_lds;
+constexpr size_t kMaxLds = 160u * 1024u;   // LDS of one CU: the most one workgroup can have
+
+int among_layout(const AmongArgs& a) { return a.x_half ? kLayoutF16 : (a.x_perm ? kLayoutPerm : kLayoutF32); }
+
+}  // namespace
+
+bool among_tiled(const AmongArgs& a) { return a.cand_off == nullptr && among_tile_lds(a.ld) <= kMaxLds; }
+
+uint32_t among_max_ld() { return (uint32_t)(kMaxLds / sizeof(float)); }   // among_list_kernel keeps one prepared query in LDS
+
+uint32_t among_step_rows(const AmongArgs& a) { return among_tiled(a) ? 64u : (among_layout(a) == kLayoutF32 ? 256u : 64u); }
+
+hipError_t launch_among(const AmongArgs& a, hipStream_t st) {
+  if (a.nq == 0 || a.n_blocks == 0 || a.n_blocks > 65535u || (a.ld & 31u) || a.metric < 0 || a.metric > 2)
+    return hipErrorInvalidValue;
+  const int fn = among_layout(a) * 3 + a.metric;
+  if (among_tiled(a)) {
+    const size_t lds = among_tile_lds(a.ld);
+    hipError_t e = g_tile_lds.ensure(kTileFns, 9, lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kTileFns[fn], dim3((a.nq + kAmongTileQ - 1) / kAmongTileQ, a.n_blocks), dim3(256), lds, st, a);
+  } else {
+    const size_t lds = (size_t)a.ld * sizeof(float);
+    if (lds > kMaxLds) return hipErrorInvalidValue;
+    hipError_t e = g_list_lds.ensure(kListFns, 9, lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kListFns[fn], dim3(a.nq, a.n_blocks), dim3(256), lds, st, a);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_among_emit(const uint64_t* merged, uint32_t nq, uint32_t k, uint32_t out_stride, uint32_t out_offset,
+                             uint64_t* out_ids, float* out_dist, uint32_t* out_count, hipStream_t st) {
+  if (nq == 0) return hipSuccess;
+  if (k == 0 || k > 64) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(among_emit_kernel, dim3(nq), dim3(64), 0, st, merged, k, out_stride, out_offset, out_ids, out_dist,
+                     out_count);
+  return hipGetLastError();
+}
+
+}  // namespace ehx

@@ -18,22 +18,6 @@ namespace ehx {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-namespace {
-
-// input: bitonic sequence across lanes; output ascending
-__device__ __forceinline__ uint64_t wave_bitonic_merge64(uint64_t key, int lane) {
-#pragma unroll
-  for (int j = 32; j > 0; j >>= 1) {
-    const uint64_t other = __shfl_xor(key, j, 64);
-    const uint64_t mn = key < other ? key : other;
-    const uint64_t mx = key < other ? other : key;
-    key = (lane & j) == 0 ? mn : mx;
-  }
-  return key;
-}
-
-}  // namespace
-
 // the fp32 scan publishes two sorted key lists per (query, chunk): one per wave row of the 8-wave kernel (k_flat8.hip)
 uint32_t scan_lists_per_chunk() { return 2u; }
 

@@ -329,6 +329,59 @@ class Space:
         check(self._L.ehx_knn_by_ids_device(self._h, C.c_void_p(stream or 0), n, ptr(d_row_ids), k, ptr(d_ids),
                                             ptr(d_dist), ptr(d_count)))
 
+    # ---- kNN among lists of row ids (filtered search) ----
+    def knn_among(self, queries, k, cand_ids, cand_off=None):
+        """The k nearest rows of every query among a list of row ids, exact (ehx_knn_among).  cand_ids: ONE id sequence
+        shared by every query; or, with cand_off [nq + 1], the concatenated per-query lists; or a list of per-query id
+        sequences (the offsets are built here).  -> ids [nq,k] u64, dist [nq,k] f32, count [nq] u32."""
+        q, pq = _f32(queries)
+        q = q.reshape(-1, self.dims)
+        nq = q.shape[0]
+        ids_in, off_in = marshal_id_lists(cand_ids, cand_off)
+        if off_in is not None and off_in.shape[0] != nq + 1:
+            raise ValueError("expected %d per-query lists, got %d" % (nq, off_in.shape[0] - 1))
+        ids = np.full((nq, max(k, 1)), np.uint64(2**64 - 1), dtype=np.uint64)
+        dist = np.full((nq, max(k, 1)), np.inf, dtype=np.float32)
+        cnt = np.zeros(nq, dtype=np.uint32)
+        u64p = C.POINTER(C.c_uint64)
+        check(self._L.ehx_knn_among(self._h, nq, pq, k, ids_in.ctypes.data_as(u64p),
+                                    off_in.ctypes.data_as(u64p) if off_in is not None else None, ids_in.shape[0],
+                                    ids.ctypes.data_as(u64p), dist.ctypes.data_as(C.POINTER(C.c_float)),
+                                    cnt.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return ids[:, :k], dist[:, :k], cnt
+
+    def knn_among_keys(self, queries, k, keys):
+        """knn_among with the shared list given as stored keys, looked up under the same state of the space the search
+        sees.  An unknown key raises EhxError (ENOTFOUND) whose `bad_index` is the position of the first one."""
+        q, pq = _f32(queries)
+        q = q.reshape(-1, self.dims)
+        nq = q.shape[0]
+        n, arr, lens, keep = marshal_keys(keys)
+        ids = np.full((nq, max(k, 1)), np.uint64(2**64 - 1), dtype=np.uint64)
+        dist = np.full((nq, max(k, 1)), np.inf, dtype=np.float32)
+        cnt = np.zeros(nq, dtype=np.uint32)
+        bad = C.c_size_t(0)
+        rc = self._L.ehx_knn_among_keys(self._h, nq, pq, k, n, arr, lens, ids.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                        dist.ctypes.data_as(C.POINTER(C.c_float)),
+                                        cnt.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(bad))
+        del keep
+        _check_bad(rc, bad)
+        return ids[:, :k], dist[:, :k], cnt
+
+    def knn_among_device(self, d_queries, k, d_cand_ids, d_cand_off, d_ids, d_dist, d_count, max_list_hint=0, stream=None):
+        """knn_among without anything leaving the device: torch CUDA tensors — d_queries [nq, dims] f32, d_cand_ids
+        [n_cand] u64 (int64 storage), d_cand_off [nq + 1] or None (one shared list), outputs as knn_device's.
+        max_list_hint: an upper bound of one list's length (0 = unknown); it sizes the launch only."""
+        def ptr(t):
+            return C.c_void_p(0 if t is None else (t.data_ptr() if hasattr(t, "data_ptr") else int(t)))
+        nq = d_queries.shape[0] if hasattr(d_queries, "shape") else None
+        n_cand = d_cand_ids.shape[0] if hasattr(d_cand_ids, "shape") else None
+        if nq is None or n_cand is None:
+            raise ValueError("pass torch tensors (queries [nq, dims], candidate ids [n_cand])")
+        check(self._L.ehx_knn_among_device(self._h, C.c_void_p(stream or 0), nq, ptr(d_queries), k, ptr(d_cand_ids),
+                                           ptr(d_cand_off), n_cand, int(max_list_hint), ptr(d_ids), ptr(d_dist),
+                                           ptr(d_count)))
+
     def stats(self):
         st = Stats()
         check(self._L.ehx_stats(self._h, C.byref(st)))
@@ -351,6 +404,35 @@ def _check_bad(rc, bad):
     except EhxError as e:
         e.bad_index = bad.value if e.code == _lib.ENOTFOUND else None
         raise
+
+
+def marshal_id_lists(cand_ids, cand_off=None):
+    """The candidate lists of knn_among -> (ids u64 [n_cand], offsets u64 [nq + 1] or None).  cand_ids is a flat id
+    sequence (shared by every query when cand_off is None, else cut by cand_off), or a list / tuple of per-query id
+    sequences, from which the offsets are built (empty lists allowed).  Ids are coerced to uint64; negative ids and
+    non-integral values are refused."""
+    def as_u64(a):
+        a = np.asarray(a)
+        if a.size == 0:
+            return np.zeros(0, dtype=np.uint64)
+        if a.dtype.kind not in "ui":
+            raise ValueError("row ids must be integers, got dtype %s" % a.dtype)
+        if a.dtype.kind == "i" and (a < 0).any():
+            raise ValueError("row ids must not be negative")
+        return np.ascontiguousarray(a.reshape(-1), dtype=np.uint64)
+    nested = (cand_off is None and isinstance(cand_ids, (list, tuple))
+              and (len(cand_ids) == 0 or any(not np.isscalar(c) for c in cand_ids)))
+    if nested:
+        parts = [as_u64(c) for c in cand_ids]
+        off = np.zeros(len(parts) + 1, dtype=np.uint64)
+        if parts:
+            np.cumsum([p.shape[0] for p in parts], out=off[1:])
+        ids = np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint64)
+        return np.ascontiguousarray(ids, dtype=np.uint64), off
+    ids = as_u64(cand_ids)
+    if cand_off is None:
+        return ids, None
+    return ids, as_u64(cand_off)
 
 
 def marshal_keys(keys):

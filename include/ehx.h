@@ -236,6 +236,19 @@ int ehx_knn_by_keys(ehx_space* s, size_t n, const char* const* keys, const size_
 int ehx_knn_by_keys_keys(ehx_space* s, size_t n, const char* const* keys, const size_t* klens, uint32_t k,
                          uint64_t* out_ids, float* out_dist, uint32_t* out_count, size_t* bad_index, char* key_arena,
                          size_t arena_cap, uint64_t* key_off);
+/* ehx_knn among lists of row ids, from host pointers: ehx_knn_among_device (below: contract, duplicate rule, intended
+ * regime) plus the H2D / D2H copies.  cand_off == NULL: ONE list cand_ids[0, n_cand) shared by every query; else query i
+ * owns cand_ids[cand_off[i], cand_off[i+1]) and cand_off has n_queries + 1 entries — checked here: not non-decreasing, or
+ * not ending at n_cand: EHX_EINVAL.  Outputs laid out [n_queries][k] as in ehx_knn. */
+int ehx_knn_among(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, const uint64_t* cand_ids,
+                  const uint64_t* cand_off, size_t n_cand, uint64_t* out_ids, float* out_dist, uint32_t* out_count);
+/* ehx_knn_among with the shared list given as n_allowed stored keys, resolved under the same hold of the space's lock as
+ * the search: key lookup and search see ONE state of the space.  An unknown key fails the whole call with EHX_ENOTFOUND,
+ * stores its index in *bad_index (may be NULL) and leaves the outputs unwritten (ehx_knn_by_keys' rule).  A key given twice
+ * is a repeated id (the duplicate rule of ehx_knn_among_device). */
+int ehx_knn_among_keys(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, size_t n_allowed,
+                       const char* const* keys, const size_t* klens, uint64_t* out_ids, float* out_dist,
+                       uint32_t* out_count, size_t* bad_index);
 
 /* ---- device-resident entry points (inputs/outputs already in HBM; `stream` is a hipStream_t
  *      passed as void*, NULL = default stream).  These are what a batching shim and bench.py
@@ -255,6 +268,28 @@ int ehx_knn_device(ehx_space* s, void* stream, size_t n_queries, const float* d_
  * k > EHX_MAX_K_PAGED and row-sharded spaces: EHX_EUNSUPPORTED. */
 int ehx_knn_by_ids_device(ehx_space* s, void* stream, size_t n, const uint64_t* d_row_ids, uint32_t k,
                           uint64_t* d_out_ids, float* d_out_dist, uint32_t* d_out_count);
+/* Exact kNN restricted to lists of row ids (filtered search, re-ranking of candidates found elsewhere): query i has a
+ * candidate list L_i of global row ids and the answer is the first k (query, row) pairs over the rows of L_i in (canonical
+ * distance, id) order — ehx_knn's contract (NaN rule, +-Inf, cosine normalisation, F16 rows as stored, out_count[i] <= k,
+ * entries beyond the count id ~0 / +Inf) with "every row" replaced by "the rows of L_i".  The listed rows are scanned
+ * exhaustively in the oracle's arithmetic, in flat AND graph spaces (a graph space's graph is not walked).
+ * d_cand_off == NULL: ONE list d_cand_ids[0, n_cand) shared by every query; else query i owns
+ * d_cand_ids[d_cand_off[i], d_cand_off[i+1]), n_queries + 1 offsets, the last equal to n_cand.  The order of ids in a list
+ * does not matter; an id at or above the row count the call took its ONE snapshot of is ignored, not an error; an empty
+ * list gives count 0.  An id should appear at most once per list: a list that repeats one may get that row back more than
+ * once — nothing else (no id outside the list, distances canonical and non-decreasing).  k <= EHX_MAX_K_PAGED, served in
+ * pages of 64 as the exhaustive pass serves them; above: EHX_EUNSUPPORTED; k == 0 or NULL outputs: EHX_EINVAL; row-sharded
+ * spaces, and rows longer than 40 960 floats (a prepared query must fit in a CU's LDS): EHX_EUNSUPPORTED.  The offsets cannot be checked here: max_list_hint is an upper bound of any one list's length
+ * (0 = unknown: n_cand) and sizes the launch ONLY — a workgroup walks its list to the end whatever the hint, so a hint that
+ * is too small costs time and never rows.  Completion as for ehx_knn_device; a Set that rewrites rows in place waits for
+ * the call like for any search.
+ * Intended regime: selective filters and re-ranking — this is an exact scan in fp32 vector arithmetic, not a faster scan.
+ * A shared list is cheaper than ehx_knn_device on the whole space only while it names a small share of the rows (estimated,
+ * NOT measured: 1-2 % of the rows at batch 1024 on 1 M x 768), and per-query lists are a gather bound by the memory
+ * system: DESIGN.md §e.10 has the rooflines and says what scripts/bench_among.py will record. */
+int ehx_knn_among_device(ehx_space* s, void* stream, size_t n_queries, const float* d_queries, uint32_t k,
+                         const uint64_t* d_cand_ids, const uint64_t* d_cand_off, size_t n_cand, size_t max_list_hint,
+                         uint64_t* d_out_ids, float* d_out_dist, uint32_t* d_out_count);
 /* k-way merge of per-shard results (RCCL all-gather output): lists laid out
  * [n_lists][n_queries][k]; ids must already be global.  Ordered by (dist, id). */
 int ehx_merge_topk_device(void* stream, size_t n_queries, uint32_t k, uint32_t n_lists,
