@@ -25,12 +25,14 @@ int among_unsharded(const ehx_space* s, const char* what) {
   return EHX_OK;
 }
 
+}  // namespace
+
 // an unsharded space, locked shared, scratch_mu held, its device current; everything is enqueued on `st`.
 // d_off == nullptr: every query shares d_ids[0, n_cand).  max_list: an upper bound of one list's length (0: n_cand) — it
 // sizes the grid only.
-int among_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, const uint64_t* d_ids,
-                 const uint64_t* d_off, size_t n_cand, size_t max_list, uint64_t* d_out_ids, float* d_out_dist,
-                 uint32_t* d_out_count) {
+int ehx_impl::among_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k,
+                           const uint64_t* d_ids, const uint64_t* d_off, size_t n_cand, size_t max_list, uint64_t* d_out_ids, float* d_out_dist,
+                           uint32_t* d_out_count) {
   if (s->x_perm && s->poisoned.load())
     return fail(EHX_EINTERNAL, "graph space: an in-place overwrite failed half way (rows left in raw order); drop and rebuild it");
   if (s->ld > among_max_ld())   // (before anything is enqueued)
@@ -85,6 +87,8 @@ int among_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries
   s->n_dist += d_off ? (uint64_t)n_cand : (uint64_t)nq * n_cand;
   return EHX_OK;
 }
+
+namespace {
 
 // host pointers in, host pointers out, on the space's stream (scratch_mu held): ids [| offsets] staged in among.dLists
 int among_host_locked(ehx_space* s, size_t nq, const float* queries, uint32_t k, const uint64_t* cand_ids,

@@ -4,10 +4,6 @@
 
 namespace ehx_impl {
 
-struct ScanPlan {
-  uint32_t q_tiles, q_rows, n_tiles, n_chunks, tiles_per_chunk, kprime, xcd_map, grid;
-};
-
 // plan one scan pass over `n_tiles` row tiles
 ScanPlan plan_scan(uint32_t nq, uint32_t n_tiles, uint32_t k, int n_cus) {
   ScanPlan p;

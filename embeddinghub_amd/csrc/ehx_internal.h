@@ -403,6 +403,20 @@ struct ehx_space {
     DevBuf<float> dQraw;
     DevBuf<unsigned char> dOut;
   } among;
+  // exact range search (ehx_range.cpp; scratch_mu): the queries' pools and control words of the exact kernel, the list of
+  // queries a stage answers, the sub-batch an overflow sends through the exact kNN pipeline, and a host call's staged
+  // queries | radii and results.  The prepared queries are the exhaustive pass's (scr.dQ), fenced by the space's clock.
+  struct Range {
+    DevBuf<uint64_t> dPool;      // [slots][kPoolCap]
+    DevBuf<uint32_t> dCtl;       // [slots] pool counts (= totals) | [q_rows] members kept by the int8 path's re-rank
+    DevBuf<uint32_t> dSel;       // [slots] query of every slot
+    DevBuf<float> dFbQ, dFbDist;
+    DevBuf<uint64_t> dFbIds, dIota;
+    DevBuf<uint32_t> dFbCnt;
+    DevBuf<float> dQraw;         // host form: queries | radii
+    DevBuf<unsigned char> dOut;  // host form: ids | distances | counts | totals
+  } range;
+  std::atomic<uint64_t> range_ctr[4] = {};   // test hook: queries answered by the int8 path, by the exact path, pool overflows, truncated
   // int8 filter scratch: everything ONE in-flight batch of the int8 pipeline owns — prepared queries, query tiles +
   // parameters, per-pass thresholds, sample scores, pools, running best list, verdict, batch clock.  TWO sets: a host
   // caller's batch can be enqueued behind another caller's on the space's stream while that one still waits for its
@@ -483,6 +497,7 @@ struct ehx_space {
     scr = {};
     by = {};
     among = {};
+    range = {};
     one = {};
     xch = {};
     wr = {};
@@ -532,6 +547,10 @@ int knn_graph_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_que
                      float* d_dist, uint32_t* d_count, const GraphOneLaunch* one = nullptr);
 
 // ---- ehx_flat.cpp ----
+struct ScanPlan {
+  uint32_t q_tiles, q_rows, n_tiles, n_chunks, tiles_per_chunk, kprime, xcd_map, grid;
+};
+ScanPlan plan_scan(uint32_t nq, uint32_t n_tiles, uint32_t k, int n_cus);   // one scan pass over `n_tiles` row tiles
 constexpr uint64_t kNoSnapshot = ~0ull;   // knn_device_locked: no snapshot of the row count yet, take one
 // n_pub: the search's one snapshot of the published row count (s->n.load(std::memory_order_acquire))
 int flat_pass(ehx_space* s, uint64_t n_pub, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, uint64_t* d_ids,
@@ -554,6 +573,16 @@ int knn_device_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_qu
 
 // ---- ehx_search.cpp ----
 void yield_to_writer(const ehx_space* s);   // a search lets an exclusive writer that waits for the space's lock in first
+// the keys of result lists [n][k] (counts out_count) packed into key_arena, key_off[n * k + 1]: ehx_knn_keys' layout
+int fill_key_arena(ehx_space* s, size_t n, uint32_t k, const uint64_t* out_ids, const uint32_t* out_count, char* key_arena,
+                   size_t arena_cap, uint64_t* key_off);
+
+// ---- ehx_among.cpp ----
+// exact kNN among row ids on an unsharded space, locked shared, scratch_mu held, its device current (d_off == nullptr: one
+// list shared by every query; max_list: an upper bound of one list's length, 0 = n_cand)
+int among_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, const uint64_t* d_ids,
+                 const uint64_t* d_off, size_t n_cand, size_t max_list, uint64_t* d_out_ids, float* d_out_dist,
+                 uint32_t* d_out_count);
 
 // ---- ehx_write.cpp ----
 int sync_stream(ehx_space* s, hipStream_t st);

@@ -928,6 +928,55 @@ hipError_t launch_among(const AmongArgs& a, hipStream_t st);
 hipError_t launch_among_emit(const uint64_t* merged, uint32_t nq, uint32_t k, uint32_t out_stride, uint32_t out_offset,
                              uint64_t* out_ids, float* out_dist, uint32_t* out_count, hipStream_t st);
 
+// exact range search (k_range.hip): every row with canonical distance <= radius[q].  The control words are per query
+// SLOT j (slot j answers query sel[j], or j when sel == nullptr): pool_cnt[j] counts every member — stored in
+// pool[j][kPoolCap] only while a slot is free — so it is the exact total, and pool_cnt[j] > kPoolCap is the overflow verdict.
+struct RangeArgs {
+  const float* Q;            // prepared queries [*][ld] (launch_prep_queries), indexed by QUERY
+  const void* X;             // stored rows
+  const float* inv_norm;     // [cap] (cosine)
+  const float* radius;       // [*] indexed by query
+  const uint32_t* sel;       // optional [n_slots]: the queries this launch answers
+  uint64_t* pool;            // [n_slots][kPoolCap] (canonical distance, id) keys, unsorted
+  uint32_t* pool_cnt;        // [n_slots], zero before the launch
+  uint32_t n_rows;           // the search's snapshot of the row count
+  uint32_t dims, ld;
+  uint32_t n_blocks;         // workgroups per query: each walks its steps of the rows in a grid-stride loop
+  uint32_t x_half;           // rows stored as binary16
+  uint32_t x_perm;           // fp32 rows stored in the search copy's block order (single-copy graph spaces)
+  int metric;
+};
+uint32_t range_step_rows(const RangeArgs& a);   // rows one workgroup takes per step of its loop
+hipError_t launch_range_exact(const RangeArgs& a, uint32_t n_slots, hipStream_t st);
+// the pools sorted by (distance, id): the first min(total, max_results) pairs of every slot's query, sentinels behind
+// them, the count, and out_total (optional) = the counter; an overflowed slot gets its total only
+hipError_t launch_range_emit(const uint64_t* pool, const uint32_t* pool_cnt, const uint32_t* sel, uint32_t n_slots,
+                             uint32_t max_results, uint64_t* out_ids, float* out_dist, uint32_t* out_count,
+                             uint64_t* out_total, hipStream_t st);
+// int8 path: thr[q] = the score below which every row with D <= radius[q] must lie (k_range.hip's header); ovf[q] = 2
+// marks a query the bound does not serve (thr -inf)
+hipError_t launch_range_thr(const float* radius, const float2* quv, const float* max_sumsq, uint32_t nq, uint32_t dims,
+                            int metric, float* thr, uint32_t* ovf, hipStream_t st);
+struct RangeRerankArgs {
+  const float* Q;            // prepared queries [*][ld]
+  const void* X;             // stored rows, fp32 or binary16, plain layout
+  const float* inv_norm;
+  const float* radius;       // [nq]
+  const uint64_t* pool;      // [*][kPoolCap] the scan's (S_lower, id) keys
+  const uint32_t* pool_cnt;  // [*]
+  const uint32_t* ovf;       // [*] non-zero: the query is answered elsewhere, nothing is written for it
+  uint32_t* kept;            // [nq] members found = the exact total
+  uint64_t* out_ids;         // [nq][max_results]
+  float* out_dist;
+  uint32_t* out_count;       // [nq]
+  uint64_t* out_total;       // [nq] or nullptr
+  uint32_t nq, max_results, n_rows, dims, ld, x_half;
+  int metric;
+};
+uint32_t range_rerank_max_ld();   // longest row stride (floats): the pool and the prepared query share the LDS
+hipError_t launch_range_rerank(const RangeRerankArgs& a, hipStream_t st);
+hipError_t launch_range_iota(uint64_t* out, uint64_t n, hipStream_t st);   // out[i] = i
+
 // per-row statistics for rows [row0, row0+n): inv_norm (cosine), rowp (a,b) for the scan epilogue;
 // *max_sumsq (optional) is raised to the largest |x|^2 seen (the certification margin's norm bound)
 // perm: the fp32 rows are stored block-permuted (single-copy graph spaces); the sums keep the logical order

@@ -177,7 +177,7 @@ static int one_launch_wait(ehx_space* s, const uint32_t* done_flag, uint32_t seq
 
 // keys of the rows a batch returned, packed into the caller's arena: key_off[i * k + j] .. key_off[i * k + j + 1] is the
 // key of result j of query i (empty beyond out_count[i], or for a row without a key)
-static int fill_key_arena(ehx_space* s, size_t n, uint32_t k, const uint64_t* out_ids, const uint32_t* out_count,
+int ehx_impl::fill_key_arena(ehx_space* s, size_t n, uint32_t k, const uint64_t* out_ids, const uint32_t* out_count,
                           char* key_arena, size_t arena_cap, uint64_t* key_off) {
   uint64_t off = 0;
   std::string key;

@@ -382,6 +382,70 @@ class Space:
                                            ptr(d_cand_off), n_cand, int(max_list_hint), ptr(d_ids), ptr(d_dist),
                                            ptr(d_count)))
 
+    # ---- range search (every row within a radius) ----
+    def _range_args(self, queries, radius, max_results):
+        q, pq = _f32(queries)
+        q = q.reshape(-1, self.dims)
+        nq = q.shape[0]
+        r = marshal_radius(radius, nq)
+        k = max(int(max_results), 1)
+        ids = np.full((nq, k), np.uint64(2**64 - 1), dtype=np.uint64)
+        dist = np.full((nq, k), np.inf, dtype=np.float32)
+        cnt = np.zeros(nq, dtype=np.uint32)
+        total = np.zeros(nq, dtype=np.uint64)
+        return nq, pq, r, ids, dist, cnt, total, (q,)
+
+    def range_search(self, queries, radius, max_results):
+        """Every row whose distance to the query is <= radius, exact (ehx_range), nearest first: radius is one number for
+        every query or one per query.  -> ids [nq, max_results] u64, dist [nq, max_results] f32, count [nq] u32 (entries
+        written per query), total [nq] u64 (rows inside the radius: total > count means the answer was cut)."""
+        nq, pq, r, ids, dist, cnt, total, keep = self._range_args(queries, radius, max_results)
+        u64p = C.POINTER(C.c_uint64)
+        check(self._L.ehx_range(self._h, nq, pq, r.ctypes.data_as(C.POINTER(C.c_float)), max_results,
+                                ids.ctypes.data_as(u64p), dist.ctypes.data_as(C.POINTER(C.c_float)),
+                                cnt.ctypes.data_as(C.POINTER(C.c_uint32)), total.ctypes.data_as(u64p)))
+        del keep
+        return ids[:, :max_results], dist[:, :max_results], cnt, total
+
+    def range_search_keys(self, queries, radius, max_results):
+        """range_search with the members' keys -> (list per query of key lists, nearest first; dist; count; total)."""
+        nq, pq, r, ids, dist, cnt, total, keep = self._range_args(queries, radius, max_results)
+        k = max_results
+        off = np.zeros(nq * max(k, 1) + 1, dtype=np.uint64)
+        u64p = C.POINTER(C.c_uint64)
+        cap = 1 << 16
+        while True:
+            arena = C.create_string_buffer(cap)
+            rc = self._L.ehx_range_keys(self._h, nq, pq, r.ctypes.data_as(C.POINTER(C.c_float)), k,
+                                        ids.ctypes.data_as(u64p), dist.ctypes.data_as(C.POINTER(C.c_float)),
+                                        cnt.ctypes.data_as(C.POINTER(C.c_uint32)), total.ctypes.data_as(u64p), arena, cap,
+                                        off.ctypes.data_as(u64p))
+            if rc == _lib.ERANGE:
+                cap *= 4
+                continue
+            check(rc)
+            break
+        del keep
+        raw = arena.raw
+        o = off.tolist()
+        c = cnt.tolist()
+        keys = [[raw[o[i * k + j]:o[i * k + j + 1]].decode() for j in range(c[i])] for i in range(nq)]
+        return keys, dist[:, :k], cnt, total
+
+    def range_device(self, d_queries, d_radius, max_results, d_ids, d_dist, d_count, d_total=None, stream=None):
+        """range_search without anything leaving the device: torch CUDA tensors — d_queries [nq, dims] f32, d_radius [nq]
+        f32, d_ids [nq, max_results] u64 (int64 storage), d_dist [nq, max_results] f32, d_count [nq] u32 (int32 storage),
+        d_total [nq] u64 (int64 storage) or None."""
+        def ptr(t):
+            return C.c_void_p(0 if t is None else (t.data_ptr() if hasattr(t, "data_ptr") else int(t)))
+        nq = d_queries.shape[0] if hasattr(d_queries, "shape") else None
+        if nq is None:
+            raise ValueError("pass torch tensors (queries [nq, dims], radius [nq])")
+        if hasattr(d_radius, "shape") and tuple(d_radius.shape) != (nq,):
+            raise ValueError("expected %d radii, got shape %s" % (nq, tuple(d_radius.shape)))
+        check(self._L.ehx_range_device(self._h, C.c_void_p(stream or 0), nq, ptr(d_queries), ptr(d_radius), max_results,
+                                       ptr(d_ids), ptr(d_dist), ptr(d_count), ptr(d_total)))
+
     def stats(self):
         st = Stats()
         check(self._L.ehx_stats(self._h, C.byref(st)))
@@ -404,6 +468,18 @@ def _check_bad(rc, bad):
     except EhxError as e:
         e.bad_index = bad.value if e.code == _lib.ENOTFOUND else None
         raise
+
+
+def marshal_radius(radius, nq):
+    """The radii of range_search -> f32 [nq], C-contiguous: a scalar (or a 0-d / one-element array) is broadcast to every
+    query; otherwise one radius per query."""
+    r = np.asarray(radius, dtype=np.float32)
+    if r.ndim == 0 or r.size == 1:
+        return np.full(nq, r.reshape(-1)[0], dtype=np.float32)
+    r = np.ascontiguousarray(r.reshape(-1), dtype=np.float32)
+    if r.shape[0] != nq:
+        raise ValueError("expected %d radii, got %d" % (nq, r.shape[0]))
+    return r
 
 
 def marshal_id_lists(cand_ids, cand_off=None):

@@ -249,6 +249,15 @@ int ehx_knn_among(ehx_space* s, size_t n_queries, const float* queries, uint32_t
 int ehx_knn_among_keys(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, size_t n_allowed,
                        const char* const* keys, const size_t* klens, uint64_t* out_ids, float* out_dist,
                        uint32_t* out_count, size_t* bad_index);
+/* Exact range search from host pointers: ehx_range_device (below: the contract) plus the H2D / D2H copies.  radius has
+ * n_queries entries; out_total may be NULL. */
+int ehx_range(ehx_space* s, size_t n_queries, const float* queries, const float* radius, uint32_t max_results,
+              uint64_t* out_ids, float* out_dist, uint32_t* out_count, uint64_t* out_total);
+/* ehx_range plus the members' keys, laid out as ehx_knn_keys lays them out (key_off has n_queries * max_results + 1
+ * entries), looked up under the same hold of the space's lock as the search. */
+int ehx_range_keys(ehx_space* s, size_t n_queries, const float* queries, const float* radius, uint32_t max_results,
+                   uint64_t* out_ids, float* out_dist, uint32_t* out_count, uint64_t* out_total, char* key_arena,
+                   size_t arena_cap, uint64_t* key_off);
 
 /* ---- device-resident entry points (inputs/outputs already in HBM; `stream` is a hipStream_t
  *      passed as void*, NULL = default stream).  These are what a batching shim and bench.py
@@ -290,6 +299,24 @@ int ehx_knn_by_ids_device(ehx_space* s, void* stream, size_t n, const uint64_t* 
 int ehx_knn_among_device(ehx_space* s, void* stream, size_t n_queries, const float* d_queries, uint32_t k,
                          const uint64_t* d_cand_ids, const uint64_t* d_cand_off, size_t n_cand, size_t max_list_hint,
                          uint64_t* d_out_ids, float* d_out_dist, uint32_t* d_out_count);
+/* Exact range search: every row closer than a radius.  With D(q, x) the canonical distance ehx_knn reports (cosine, L2^2,
+ * inner product as there), row x belongs to query i's answer iff D is not NaN and D <= d_radius[i] as a float comparison
+ * (inclusive: a radius that equals a row's distance byte for byte includes that row; -Inf distances under inner product
+ * are ordinary members).  The answer is ordered by (distance, id); its first min(total, max_results) pairs are written,
+ * d_out_count[i] is that number, the rest of the row holds ehx_knn's sentinels (id 2^64 - 1, +Inf), and d_out_total[i]
+ * (may be NULL) is the EXACT number of rows inside the radius even beyond max_results: total > count is how a caller sees
+ * truncation.  Equivalently: ehx_knn(k = max_results) cut before the first distance above the radius, plus the count.
+ * A NaN radius gives count 0 and total 0; +Inf every row with a non-NaN distance.  The answer describes the prefix of ONE
+ * acquire load of the row count.  Outputs [n_queries][max_results].  1 <= max_results <= EHX_MAX_K_PAGED (0: EHX_EINVAL,
+ * above: EHX_EUNSUPPORTED); NULL arguments, more than 2^24 queries: EHX_EINVAL; a row-sharded space, and rows longer than
+ * 40 960 floats: EHX_EUNSUPPORTED; a dropped space: EHX_ENOTFOUND; no device: EHX_ENODEVICE.  Flat spaces whose first engine
+ * is the int8 filter are answered by ONE pass of its scan under a threshold mapped from the radius and an exact re-rank of
+ * the survivors; every other space, and the queries that scan cannot bound, by the canonical distance of every row — in
+ * graph spaces too: the graph is not walked.  The call waits for the device before it returns (it reads a verdict back);
+ * a Set that rewrites rows in place waits for it like for any search.  DESIGN.md §e.11. */
+int ehx_range_device(ehx_space* s, void* stream, size_t n_queries, const float* d_queries, const float* d_radius,
+                     uint32_t max_results, uint64_t* d_out_ids, float* d_out_dist, uint32_t* d_out_count,
+                     uint64_t* d_out_total);
 /* k-way merge of per-shard results (RCCL all-gather output): lists laid out
  * [n_lists][n_queries][k]; ids must already be global.  Ordered by (dist, id). */
 int ehx_merge_topk_device(void* stream, size_t n_queries, uint32_t k, uint32_t n_lists,
