@@ -680,7 +680,8 @@ struct ScanArgsI8 {
   const float4* rowp;     // [cap + 512] (A, B, C, D) per row; padding rows (0, +inf, 0, 0)
   const float4* tilep;    // [cap/256 + 2] (max|A|, max|C|, max|D|, min B) per 256-row tile
   const float* tileg;     // [cap/256 + 2][16]: [0..8) max |A| of each 32-row lane group of the tile (g = 4 wr + (l >> 4)),
-                          // [8..16) the group's B margin: min B of the group - min B of the tile (>= 0; round 6)
+                          // [8..16) min B of the group, ABSOLUTE (-inf: no margin); the scan derives the group's B margin over
+                          // tilep[tile].w itself (i8_group_b_margin; round 6)
   const uint8_t* perm;    // [cap] row index inside its tile of the row stored at each position (identity: unsorted tile)
   const float4* qparams;  // [q_tiles*256] (s_q, e_q, gamma_q, smallest threshold the query was scanned with so far)
   const float* thr;       // [q_tiles*256] score threshold of this pass per query (-inf: padding query)

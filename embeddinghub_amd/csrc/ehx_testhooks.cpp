@@ -1,0 +1,202 @@
+// Test hooks of the int8 filter scan (not in include/ehx.h, like ehx_test_range_counters and ehx_test_live_resources):
+//   ehx_test_i8_array   a slice of one array of the int8 scan copy, raw, as the writers left it
+//   ehx_test_i8_pass    ONE launch of flat_scan_i8_kernel over a window of tiles with the arguments a search would give
+//                       it: the sample form (every lower bound of the window) or a collect pass under the caller's
+//                       thresholds (the pools as the pass left them, before select256 and the re-rank reduce them)
+// tests/test_i8_device_bound.py checks the scan copy, the bound and the hit path on them.  No production path calls in here.
+#include "ehx_internal.h"
+
+namespace {
+
+enum { kArrX8, kArrRowp8, kArrTilep8, kArrTileg8, kArrPerm8, kArrUnsafe8, kArrLd8, kArrCap };
+constexpr uint32_t kSampleTiles = 8;   // the sample pass's window (flat_pass8)
+
+int hook_space(ehx_space* s, const char* what) {
+  int rc = ehx_init(nullptr, 0);
+  if (rc) return rc;
+  if (!valid_space(s)) return fail(EHX_EINVAL, "space is NULL");
+  if (s->dropped) return fail(EHX_ENOTFOUND, "Not found");
+  if (is_parent(s)) return fail(EHX_EUNSUPPORTED, "%s: space '%s' is row-sharded", what, s->name.c_str());
+  if (!s->has8) return fail(EHX_EUNSUPPORTED, "%s: space '%s' keeps no int8 scan copy", what, s->name.c_str());
+  return EHX_OK;
+}
+
+template <class T>
+int copy_slice(ehx_space* s, const ehx_impl::DevBuf<T>& b, uint64_t off, uint64_t n, void* out, hipStream_t st) {
+  if (off > b.n || n > b.n - off) return fail(EHX_EINVAL, "slice [%llu, +%llu) of an array of %llu elements",
+                                              (unsigned long long)off, (unsigned long long)n, (unsigned long long)b.n);
+  if (n == 0) return EHX_OK;
+  HIP_TRY(hipMemcpyAsync(out, b.p + off, n * sizeof(T), hipMemcpyDeviceToHost, st));
+  return sync_stream(s, st);
+}
+
+}  // namespace
+
+extern "C" {
+
+// which: 0 X8 (int8) | 1 rowp8 (float, four per row) | 2 tilep8 (float, four per tile) | 3 tileg8 (float, sixteen per tile)
+// | 4 perm8 (u8) | 5 the two counters of dUnsafe8 (u64) | 6 ld8 | 7 cap (one u64 each); offset and length in those elements
+int ehx_test_i8_array(ehx_space* s, int which, uint64_t elem_offset, uint64_t n_elems, void* out) {
+  int rc = hook_space(s, "ehx_test_i8_array");
+  if (rc) return rc;
+  if (!out && n_elems) return fail(EHX_EINVAL, "NULL argument");
+  // writers are serialised by wmu and enqueue on the writers' stream (grow: on the space's): with wmu held and both
+  // streams drained the arrays are what the last write left
+  std::lock_guard<std::mutex> wl(s->wmu);
+  std::shared_lock<std::shared_mutex> rl(s->mu);
+  if (s->dropped) return fail(EHX_ENOTFOUND, "Not found");
+  HIP_TRY(hipSetDevice(s->device));
+  const hipStream_t ws = s->wr.wstream ? (hipStream_t)s->wr.wstream : (hipStream_t)s->stream;
+  if ((rc = sync_stream(s, ws)) || (rc = sync_stream(s, s->stream))) return rc;
+  switch (which) {
+    case kArrX8: return copy_slice(s, s->i8.dX8, elem_offset, n_elems, out, ws);
+    case kArrPerm8: return copy_slice(s, s->i8.dPerm8, elem_offset, n_elems, out, ws);
+    case kArrTileg8: return copy_slice(s, s->i8.dTileg8, elem_offset, n_elems, out, ws);
+    case kArrUnsafe8: return copy_slice(s, s->i8.dUnsafe8, elem_offset, n_elems, out, ws);
+    case kArrRowp8:
+    case kArrTilep8: {
+      const DevBuf<float4>& b = which == kArrRowp8 ? s->i8.dRowp8 : s->i8.dTilep8;
+      if (elem_offset > b.n * 4 || n_elems > b.n * 4 - elem_offset) return fail(EHX_EINVAL, "slice beyond the array");
+      if (n_elems == 0) return EHX_OK;
+      HIP_TRY(hipMemcpyAsync(out, (const float*)b.p + elem_offset, n_elems * sizeof(float), hipMemcpyDeviceToHost, ws));
+      return sync_stream(s, ws);
+    }
+    case kArrLd8:
+    case kArrCap:
+      if (elem_offset != 0 || n_elems != 1) return fail(EHX_EINVAL, "a scalar: offset 0, one element");
+      *(uint64_t*)out = which == kArrLd8 ? (uint64_t)s->ld8 : s->cap;
+      return EHX_OK;
+  }
+  return fail(EHX_EINVAL, "unknown array %d", which);
+}
+
+// queries [nq][dims] and thr [nq] (or NULL) are host pointers, as are the outputs:
+//   thr == NULL (n_tiles must be 8): out_dump[q_rows * n_tiles * 256], scan8_dump_index layout, raw
+//   thr != NULL: out_cnt[nq] (the pool counter: it counts past the pool's end), out_ovf[nq], out_ids / out_scores
+//                [nq][kPoolCap], the first min(count, kPoolCap) of a query valid, in the pool's order
+//   both: out_qparams[nq][4], out_quv[nq][2], out_q8[scanq8_bytes(q_rows, ld8)] raw,
+//         out_info[8] = q_rows, ld8, group_b, n_chunks, tiles_per_chunk, xcd_map, published rows, lock-step on
+// (outputs of the other form may be NULL)
+int ehx_test_i8_pass(ehx_space* s, uint32_t nq, const float* queries, const float* thr, uint32_t tile0, uint32_t n_tiles,
+                     float* out_dump, uint32_t* out_cnt, uint32_t* out_ovf, uint32_t* out_ids, float* out_scores,
+                     float* out_qparams, float* out_quv, int8_t* out_q8, uint32_t* out_info) {
+  int rc = hook_space(s, "ehx_test_i8_pass");
+  if (rc) return rc;
+  if (!queries || !out_qparams || !out_quv || !out_q8 || !out_info) return fail(EHX_EINVAL, "NULL argument");
+  if (thr ? (!out_cnt || !out_ovf || !out_ids || !out_scores) : !out_dump) return fail(EHX_EINVAL, "NULL argument");
+  if (nq == 0 || nq > 4 * kTileQ) return fail(EHX_EINVAL, "nq=%u outside [1, %u]", nq, 4 * kTileQ);
+  if (!thr && n_tiles != kSampleTiles) return fail(EHX_EINVAL, "the sample form scans %u tiles", kSampleTiles);
+  yield_to_writer(s);
+  std::shared_lock<std::shared_mutex> rl(s->mu);
+  if (s->dropped) return fail(EHX_ENOTFOUND, "Not found");
+  // (the window may reach beyond the published rows, never beyond the arrays: the scan reads whole tiles)
+  if (n_tiles == 0 || (uint64_t)tile0 + n_tiles > s->cap / kTileRows16)
+    return fail(EHX_EINVAL, "tiles [%u, +%u) of a space of %llu", tile0, n_tiles, (unsigned long long)(s->cap / kTileRows16));
+  std::lock_guard<std::mutex> sl(s->scratch_mu);
+  HIP_TRY(hipSetDevice(s->device));
+  Engine& E = engine();
+  const hipStream_t st = s->stream;
+  const uint64_t n_pub = s->n.load(std::memory_order_acquire);
+  const ScanPlan p = plan_scan(nq, n_tiles, 1, E.n_cus);
+  if (p.n_chunks > 256) return fail(EHX_EINTERNAL, "scan plan with %u chunks", p.n_chunks);
+  // scratch of this call alone (owners: freed on every return)
+  DevBuf<float> dQraw, dQ, dThr, dDump;
+  DevBuf<int8_t> dQ8;
+  DevBuf<float4> dQp;
+  DevBuf<float2> dQuv;
+  DevBuf<uint64_t> dPool, dCnt;
+  DevBuf<uint32_t> dCtl;
+  const size_t q8_bytes = scanq8_bytes(p.q_rows, s->ld8);
+  const size_t dump_elems = (size_t)p.q_rows * n_tiles * kTileRows16;
+  if ((rc = dQraw.ensure((size_t)nq * s->dims)) || (rc = dQ.ensure((size_t)p.q_rows * s->ld)) || (rc = dThr.ensure(p.q_rows)) ||
+      (rc = dQ8.ensure(q8_bytes)) || (rc = dQp.ensure(p.q_rows)) || (rc = dQuv.ensure(p.q_rows)) || (rc = dCnt.ensure(8, true)) ||
+      (rc = dCtl.ensure((size_t)p.q_rows * 2 + kSyncWordsI8)))
+    return rc;
+  if (thr ? (rc = dPool.ensure((size_t)p.q_rows * kPoolCap)) : (rc = dDump.ensure(dump_elems))) return rc;
+  std::vector<uint64_t> pool(thr ? (size_t)nq * kPoolCap : 0);
+  uint32_t lockstep = 0;
+  auto run = [&]() -> int {
+    int r;
+    HIP_TRY(hipMemcpyAsync(dQraw.p, queries, (size_t)nq * s->dims * sizeof(float), hipMemcpyHostToDevice, st));
+    if ((r = wait_searches_in_flight(s, st))) return r;
+    if ((r = s->clock.begin(st, BatchClock::kOutOfRing))) return r;
+    // thr[q] = +inf (-inf for the padding queries), control words zero ...
+    HIP_TRY(launch_prep_queries_i8(dQraw.p, nq, s->dims, s->ld, s->ld8, p.q_rows, s->metric, dQ.p, dQ8.p, dQp.p, dQuv.p, dThr.p,
+                                   dCtl.p, st));
+    // ... then the caller's thresholds
+    if (thr) HIP_TRY(hipMemcpyAsync(dThr.p, thr, (size_t)nq * sizeof(float), hipMemcpyHostToDevice, st));
+    ScanArgsI8 a;   // filled as flat_pass8 fills it (ehx_flat.cpp)
+    a.Q = dQ8.p;
+    a.X = s->i8.dX8.p;
+    a.rowp = s->i8.dRowp8.p;
+    a.tilep = s->i8.dTilep8.p;
+    a.tileg = s->i8.dTileg8.p;
+    a.perm = s->i8.dPerm8.p;
+    a.qparams = dQp.p;
+    a.thr = dThr.p;
+    a.cand = dCnt.p;
+    a.pool = dPool.p;
+    a.pool_cnt = dCtl.p;
+    a.ovf = dCtl.p + p.q_rows;
+    a.pool_cap = kPoolCap;
+    a.n = (uint32_t)n_pub;
+    a.ld = s->ld8;
+    a.q_tiles = p.q_tiles;
+    a.skew = env().i8_skew;
+    a.group_b = s->metric == EHX_METRIC_L2SQ && s->h_margin8.load(std::memory_order_relaxed) > 0 && env().i8_groupb ? 1u : 0u;
+    a.tile0 = tile0;
+    a.n_tiles = p.n_tiles;
+    a.n_chunks = p.n_chunks;
+    a.tiles_per_chunk = p.tiles_per_chunk;
+    a.xcd_map = p.xcd_map;
+    a.dump = thr ? nullptr : dDump.p;
+    a.sync = nullptr;
+    if (thr && env().i8_sync > 0 && p.xcd_map && p.q_tiles > 1 && p.tiles_per_chunk >= 4 && p.n_chunks * 4u <= kSyncWordsI8) {
+      a.sync = dCtl.p + 2 * (size_t)p.q_rows;   // (zeroed by the query preparation)
+      a.sync_tol = (uint32_t)env().i8_sync;
+      lockstep = 1;
+    }
+    out_info[2] = a.group_b;
+    if ((r = s->clock.scan_begin(st))) return r;
+    HIP_TRY(launch_flat_scan_i8(a, st));
+    if ((r = s->clock.scan_end(st)) || (r = s->clock.finish(st))) return r;
+    if (thr) {
+      HIP_TRY(hipMemcpyAsync(out_cnt, dCtl.p, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipMemcpyAsync(out_ovf, dCtl.p + p.q_rows, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipMemcpyAsync(pool.data(), dPool.p, pool.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    } else {
+      HIP_TRY(hipMemcpyAsync(out_dump, dDump.p, dump_elems * sizeof(float), hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipMemcpyAsync(out_qparams, dQp.p, (size_t)nq * sizeof(float4), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(out_quv, dQuv.p, (size_t)nq * sizeof(float2), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(out_q8, dQ8.p, q8_bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return EHX_OK;
+  };
+  rc = run();
+  if (rc) {  // launches of this call may still be in flight: drain them before the scratch is freed
+    (void)hipStreamSynchronize(st);
+    (void)hipGetLastError();
+    return rc;
+  }
+  out_info[0] = p.q_rows;
+  out_info[1] = s->ld8;
+  out_info[3] = p.n_chunks;
+  out_info[4] = p.tiles_per_chunk;
+  out_info[5] = p.xcd_map;
+  out_info[6] = (uint32_t)n_pub;
+  out_info[7] = lockstep;
+  if (thr) {
+    for (size_t q = 0; q < nq; ++q) {
+      const size_t m = std::min<size_t>(out_cnt[q], kPoolCap);
+      for (size_t i = 0; i < kPoolCap; ++i) {
+        const uint64_t key = i < m ? pool[q * kPoolCap + i] : kKeyInf;
+        out_ids[q * kPoolCap + i] = (uint32_t)key;
+        out_scores[q * kPoolCap + i] = i < m ? ordered_to_f32((uint32_t)(key >> 32)) : __builtin_inff();
+      }
+    }
+  }
+  return EHX_OK;
+}
+
+}  // extern "C"

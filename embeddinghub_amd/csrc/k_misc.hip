@@ -374,7 +374,13 @@ __global__ __launch_bounds__(256) void make_scan8_kernel(const XT* __restrict__ 
         a_r = -nr;
         b_r = ss * (1.0f - 1e-6f - 7e-8f * ((float)(dims >> 6) + 8.0f));  // the parallel sum, rounded down
       }
-      p = make_float4(a_r * s, b_r * (1.0f - 1e-6f), a_r * (1.0001f + e), a_r * (1.0001f * e + i8_slack(dims)));
+      // A row of an ordered tile stores the group's |A| ITSELF: |a_r| * (tgt / |a_r|) lands an ulp beside tgt for most norms,
+      // and the scan's one level per lane group is exact only if every row of the group has the group's |A| to the last
+      // bit (tests/i8_checks.py, C4).  The real product |a_r| s lies within 2^-23 of tgt either way (s >= tgt / |a_r|
+      // rounded, and the row's own step gives at most tgt), which the slack in D covers like any rounding of A; a zero row
+      // (a_r = 0 under inner product / L2^2) has all-zero codes, so its A never meets a non-zero I.
+      const float A_r = tgtA ? -tgtA[r - base] : a_r * s;
+      p = make_float4(A_r, b_r * (1.0f - 1e-6f), a_r * (1.0001f + e), a_r * (1.0001f * e + i8_slack(dims)));
     }
     rowp8[pr] = p;
   }

@@ -6,96 +6,15 @@ numpy float32, checked against float64 distances on ordinary and adversarial dat
   * the alarm test (I * |A_r| against one threshold per tile and query) never hides a row whose S_lower is at or
     below the threshold.
 
-The constants below are the kernels' (a change there must be mirrored here)."""
+The restated quantities live in tests/i8_model.py (the constants are the kernels'); tests/test_i8_device_bound.py checks the
+same two properties on what the device itself stored and collected."""
 import numpy as np
 import pytest
 
+from i8_model import (_alarm_k, _datasets, _group_b_margin, _kernel_order, _query_params,  # noqa: F401
+                      _quantise, _row_params, _true_distance)
+
 f32 = np.float32
-
-
-def _slack(d):
-    return f32(4e-6) + f32(1.5e-7) * f32(d)          # i8_slack
-
-
-def _err_up(e2):
-    return np.sqrt(e2).astype(f32) * f32(1.0 + 1e-4) + f32(3e-7)   # i8_err_up
-
-
-def _quantise(V):
-    """rows V (fp32) -> (n_f, ss, xi, s, e) as make_scan8 / prep_queries8 compute them"""
-    ss = (V.astype(f32) ** 2).sum(axis=1, dtype=f32)
-    nr = np.sqrt(ss).astype(f32)
-    inv = np.where(nr > 0, f32(1) / np.where(nr > 0, nr, f32(1)), f32(0)).astype(f32)
-    xh = (V * inv[:, None]).astype(f32)
-    amax = np.abs(xh).max(axis=1).astype(f32)
-    s = (amax / f32(127)).astype(f32)
-    rs = np.where(amax > 0, f32(127) / np.where(amax > 0, amax, f32(1)), f32(0)).astype(f32)
-    qf = np.clip(np.rint((xh * rs[:, None]).astype(f32)), -127, 127).astype(f32)
-    res = (xh - (s[:, None] * qf).astype(f32)).astype(f32)
-    e = _err_up((res ** 2).sum(axis=1, dtype=f32))
-    return nr, ss, qf.astype(np.int32), s, e
-
-
-def _row_params(X, metric, d):
-    nr, ss, xi, s, e = _quantise(X)
-    a = -np.ones_like(nr)
-    b = np.ones_like(nr)
-    if metric in ("ip", "l2"):
-        a = -nr
-    if metric == "l2":
-        b = (ss * f32(1.0 - 1e-6 - 7e-8 * ((d >> 6) + 8.0))).astype(f32)
-    A = (a * s).astype(f32)
-    B = (b * f32(1.0 - 1e-6)).astype(f32)
-    C = (a * (f32(1.0001) + e)).astype(f32)
-    D = (a * (f32(1.0001) * e + _slack(d))).astype(f32)
-    return xi, A, B, C, D
-
-
-def _query_params(Q, metric, d):
-    beta, ss, qi, s, e = _quantise(Q)
-    g = np.ones_like(beta)
-    u = np.ones_like(beta)
-    v = np.zeros_like(beta)
-    pos = beta > 0
-    if metric == "ip":
-        g[pos] = f32(1) / beta[pos]
-        u[pos] = beta[pos]
-    elif metric == "l2":
-        g[pos] = f32(0.5) / beta[pos]
-        u[pos] = f32(2) * beta[pos]
-        v[pos] = (ss[pos] * f32(1.0 - 1e-6 - 7e-8 * ((d >> 6) + 8.0))).astype(f32)
-    return qi, s, e, g, u, v
-
-
-def _true_distance(X, Q, metric):
-    X64, Q64 = X.astype(np.float64), Q.astype(np.float64)
-    if metric == "cosine":
-        nx = np.maximum(np.linalg.norm(X64, axis=1), 1e-300)
-        nq = np.maximum(np.linalg.norm(Q64, axis=1), 1e-300)
-        return 1.0 - (X64 / nx[:, None]) @ (Q64 / nq[:, None]).T
-    if metric == "ip":
-        return 1.0 - X64 @ Q64.T
-    return ((X64[:, None, :] - Q64[None, :, :]) ** 2).sum(axis=2)
-
-
-def _datasets(rng, d, n=320):
-    g = rng.standard_normal((n, d)).astype(f32)
-    yield "gaussian", g
-    yield "scaled 1e3", g * f32(1e3)
-    yield "scaled 1e-3", g * f32(1e-3)
-    yield "near-duplicates", np.repeat(g[:16], n // 16, axis=0) + f32(1e-4) * rng.standard_normal((n, d)).astype(f32)
-    sparse = np.zeros((n, d), dtype=f32)
-    sparse[np.arange(n)[:, None], rng.integers(0, d, size=(n, 3))] = rng.standard_normal((n, 3)).astype(f32)
-    yield "3-sparse", sparse
-    yield "one-hot-ish", np.eye(d, dtype=f32)[rng.integers(0, d, n)] + f32(1e-3) * g
-    yield "constant", np.ones((n, d), dtype=f32) * rng.uniform(0.5, 2, size=(n, 1)).astype(f32)
-    heavy = g.copy()
-    heavy[:, 0] *= f32(50)
-    yield "dominant coordinate", heavy
-    mixed = g * (10.0 ** rng.uniform(-1, 1, size=(n, 1))).astype(f32)
-    mixed[:8] = 0
-    yield "mixed norms + zero rows", mixed
-    yield "all positive", np.abs(g)
 
 
 @pytest.mark.parametrize("d", [8, 100, 768, 2048])
@@ -141,17 +60,6 @@ def test_alarm_threshold_never_hides_a_hit(metric):
                 prod = (I[:, qj].astype(f32) * np.abs(A)).astype(f32)                         # (float)I * |A_r|
                 hits = S[:, qj] <= thr
                 assert (prod[hits] >= kq).all(), (name, metric, qj, float(thr))
-
-
-def _alarm_k(Bmin, Cmax, Dmax, g, eq, sq, thr):
-    bg, ce = f32(Bmin * g), f32(Cmax * eq)
-    num = f32(f32(f32(bg - Dmax) - ce) - thr)
-    num = f32(num - f32(1e-5) * f32(abs(bg) + Dmax + ce + abs(thr))) if np.isfinite(thr) else f32(-np.inf)
-    if not (num > 0):
-        return f32(-np.inf)
-    if not (sq > 0):
-        return f32(np.inf)
-    return f32(f32(num / sq) * f32(1.0 - 1e-5))
 
 
 def test_the_alarm_is_judged_per_row():
@@ -217,17 +125,6 @@ def test_block_integer_alarm_is_valid_and_pays_once_rows_are_ordered_by_step():
     assert rates[False] > 0.8 and rates[True] < 0.35, rates
 
 
-def _kernel_order(A, norms):
-    """rank_tiles8_kernel (k_misc.hip, round 6): the positions of a FULL tile's 256 rows — pure step order when the norms
-    spread by less than 0.1 %, else four norm bands of 64 rows, each by step; returns the rows in rank order (rank r sits in
-    lane group r // 32)"""
-    idx = np.arange(256)
-    if norms.max() <= norms.min() * f32(1.001):
-        return idx[np.argsort(np.abs(A), kind="stable")]
-    by_norm = idx[np.argsort(norms, kind="stable")]
-    return np.concatenate([b[np.argsort(np.abs(A[b]), kind="stable")] for b in (by_norm[i * 64:(i + 1) * 64] for i in range(4))])
-
-
 def test_group_b_margin_is_sound_and_pays_on_rows_whose_norms_vary():
     """Round 6 (L2^2 on raw rows — the reference's default metric on un-normalised data): every 32-row lane group's alarm
     level uses the group's own min B (tileg8[tile][8 + g] = min B of the group - min B of the tile, rounded down; the
@@ -286,14 +183,6 @@ def test_group_b_margin_is_sound_and_pays_on_rows_whose_norms_vary():
     assert rates["raw gaussian"][0] > 0.9 and rates["raw gaussian"][1] < 0.5, rates
     assert abs(rates["normalised"][0] - rates["normalised"][1]) < 0.02, rates
     _straddling_tile_margins_are_sound_under_any_mix(rng, d)
-
-
-def _group_b_margin(bg, bt):
-    """i8_group_b_margin (ehx_kernels.h): (bg - bt) rounded down, never negative; bt = +inf: 0"""
-    if not bt < np.inf:
-        return f32(0)
-    m = f32(f32(bg - bt) * f32(1.0 - 1e-6)) if bg < np.inf else f32(np.inf)
-    return m if m > 0 else f32(0)
 
 
 def _straddling_tile_margins_are_sound_under_any_mix(rng, d):
