@@ -8,21 +8,12 @@ namespace {
 constexpr uint32_t kAmongGridTarget = 4096;   // workgroups a launch aims for (16 per CU): chosen, not measured
 constexpr uint32_t kAmongMaxBlocks = 1024;    // ... and at most this many key lists per query for the merge
 
-int among_check(ehx_space* s, size_t nq, uint32_t k, const void* q, const void* o_ids, const void* o_dist, const void* o_cnt) {
-  if (!valid_space(s)) return fail(EHX_EINVAL, "space is NULL");
-  if (k == 0) return fail(EHX_EINVAL, "k is 0");
-  if (k > EHX_MAX_K_PAGED) return fail(EHX_EUNSUPPORTED, "k=%u exceeds %u", k, EHX_MAX_K_PAGED);
-  if (!o_ids || !o_dist || !o_cnt || (nq && !q)) return fail(EHX_EINVAL, "NULL argument");
-  if (nq > (1u << 24)) return fail(EHX_EINVAL, "too many queries in one call: %zu", nq);
-  return EHX_OK;
+// the checks every entry point starts with, and the gate behind the space's lock
+int among_check(const ehx_space* s, size_t nq, uint32_t k, const void* q, const void* o_ids, const void* o_dist, const void* o_cnt) {
+  return check_batch_call(s, nq, k, "k", false, o_ids && o_dist && o_cnt && (!nq || q));
 }
-
 int among_unsharded(const ehx_space* s, const char* what) {
-  if (s->dropped) return fail(EHX_ENOTFOUND, "Not found");
-  if (is_parent(s))
-    return fail(EHX_EUNSUPPORTED, "%s: space '%s' is row-sharded (filtered search over shards is not built yet)", what,
-                s->name.c_str());
-  return EHX_OK;
+  return check_unsharded(s, what, "filtered search over shards is not built yet");
 }
 
 }  // namespace
@@ -33,33 +24,25 @@ int among_unsharded(const ehx_space* s, const char* what) {
 int ehx_impl::among_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k,
                            const uint64_t* d_ids, const uint64_t* d_off, size_t n_cand, size_t max_list, uint64_t* d_out_ids, float* d_out_dist,
                            uint32_t* d_out_count) {
-  if (s->x_perm && s->poisoned.load())
-    return fail(EHX_EINTERNAL, "graph space: an in-place overwrite failed half way (rows left in raw order); drop and rebuild it");
+  int rc;
+  if ((rc = check_not_poisoned(s))) return rc;
   if (s->ld > among_max_ld())   // (before anything is enqueued)
     return fail(EHX_EUNSUPPORTED, "filtered search keeps a prepared query in LDS: rows of %u floats exceed %u", s->ld,
                 among_max_ld());
   // the ONE read of the row count: every page's range check answers for the same prefix
   const uint64_t n_pub = s->n.load(std::memory_order_acquire);
   AmongArgs a = {};
-  a.X = s->rows.dX.p;
-  a.inv_norm = s->rows.dInv.p;
+  a.rows = rows_view(s, n_pub);
   a.cand_ids = d_ids;
   a.cand_off = d_off;
   a.n_cand = n_cand;
-  a.n_rows = n_pub;
   a.nq = (uint32_t)nq;
-  a.dims = s->dims;
-  a.ld = s->ld;
-  a.x_half = (uint32_t)s->x_half;
-  a.x_perm = s->x_perm ? 1u : 0u;
-  a.metric = s->metric;
   const uint64_t longest = std::max<uint64_t>(1, max_list && max_list < n_cand ? max_list : n_cand);
   const uint32_t step = among_step_rows(a);
   const uint64_t units = among_tiled(a) ? (nq + kAmongTileQ - 1) / kAmongTileQ : nq;
   a.n_blocks = (uint32_t)std::min<uint64_t>(
       std::min<uint64_t>((longest + step - 1) / step, kAmongMaxBlocks), std::max<uint64_t>(1, kAmongGridTarget / units));
   const uint32_t pages = (k + 63) / 64;
-  int rc;
   if ((rc = s->scr.dQ.ensure(nq * s->ld))) return rc;
   if ((rc = s->scr.dPart.ensure(nq * a.n_blocks * 64))) return rc;
   if ((rc = s->scr.dMerged.ensure(nq * 64))) return rc;
@@ -94,43 +77,27 @@ namespace {
 int among_host_locked(ehx_space* s, size_t nq, const float* queries, uint32_t k, const uint64_t* cand_ids,
                       const uint64_t* cand_off, size_t n_cand, uint64_t* out_ids, float* out_dist, uint32_t* out_count) {
   const size_t n_off = cand_off ? nq + 1 : 0;
-  const size_t ids_b = nq * k * sizeof(uint64_t), dist_b = nq * k * sizeof(float), cnt_b = nq * sizeof(uint32_t);
   int rc;
   HIP_TRY(hipSetDevice(s->device));
   if ((rc = s->among.dLists.ensure(n_cand + n_off + 1))) return rc;
   if ((rc = s->among.dQraw.ensure(nq * s->dims))) return rc;
-  if ((rc = s->among.dOut.ensure(ids_b + dist_b + cnt_b))) return rc;
+  if ((rc = s->among.dOut.ensure(ResultBlock::bytes(nq, k, false)))) return rc;
   uint64_t* d_ids = s->among.dLists.p;
   uint64_t* d_off = cand_off ? d_ids + n_cand : nullptr;
-  uint64_t* o_ids = (uint64_t*)s->among.dOut.p;
-  float* o_dist = (float*)(s->among.dOut.p + ids_b);
-  uint32_t* o_cnt = (uint32_t*)(s->among.dOut.p + ids_b + dist_b);
-  rc = EHX_OK;
-  auto run = [&]() -> int {
-    // (pageable host memory: the runtime stages it before the call returns; the staging buffers are this path's alone and
-    // the space's stream orders their reuse)
-    if (n_cand) HIP_TRY(hipMemcpyAsync(d_ids, cand_ids, n_cand * sizeof(uint64_t), hipMemcpyHostToDevice, s->stream));
-    if (d_off) HIP_TRY(hipMemcpyAsync(d_off, cand_off, n_off * sizeof(uint64_t), hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(hipMemcpyAsync(s->among.dQraw.p, queries, nq * s->dims * sizeof(float), hipMemcpyHostToDevice, s->stream));
-    size_t longest = n_cand;
-    if (cand_off) {
-      longest = 0;
-      for (size_t i = 0; i < nq; ++i) longest = std::max<size_t>(longest, cand_off[i + 1] - cand_off[i]);
-    }
-    int r = among_locked(s, s->stream, nq, s->among.dQraw.p, k, d_ids, d_off, n_cand, longest, o_ids, o_dist, o_cnt);
-    if (r) return r;
-    HIP_TRY(hipMemcpyAsync(out_ids, o_ids, ids_b, hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipMemcpyAsync(out_dist, o_dist, dist_b, hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipMemcpyAsync(out_count, o_cnt, cnt_b, hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return EHX_OK;
-  };
-  rc = run();
-  if (rc) {  // launches of this call may still be in flight: drain them before the scratch goes to the next caller
-    (void)hipStreamSynchronize(s->stream);
-    (void)hipGetLastError();
+  const ResultBlock o = ResultBlock::at(s->among.dOut.p, nq, k, false);
+  DrainUnlessOk drain{s->stream};
+  // (pageable host memory: the runtime stages it before the call returns; the staging buffers are this path's alone and
+  // the space's stream orders their reuse)
+  if (n_cand) HIP_TRY(hipMemcpyAsync(d_ids, cand_ids, n_cand * sizeof(uint64_t), hipMemcpyHostToDevice, s->stream));
+  if (d_off) HIP_TRY(hipMemcpyAsync(d_off, cand_off, n_off * sizeof(uint64_t), hipMemcpyHostToDevice, s->stream));
+  HIP_TRY(hipMemcpyAsync(s->among.dQraw.p, queries, nq * s->dims * sizeof(float), hipMemcpyHostToDevice, s->stream));
+  size_t longest = n_cand;
+  if (cand_off) {
+    longest = 0;
+    for (size_t i = 0; i < nq; ++i) longest = std::max<size_t>(longest, cand_off[i + 1] - cand_off[i]);
   }
-  return rc;
+  if ((rc = among_locked(s, s->stream, nq, s->among.dQraw.p, k, d_ids, d_off, n_cand, longest, o.ids, o.dist, o.cnt))) return rc;
+  return drain.done(o.copy_out(s->stream, out_ids, out_dist, out_count, nullptr));
 }
 
 }  // namespace
@@ -183,20 +150,8 @@ int ehx_knn_among_keys(ehx_space* s, size_t n_queries, const float* queries, uin
   // ONE shared hold for key lookup and search: the answer describes one state of the space
   std::shared_lock<std::shared_mutex> rl(s->mu);
   if ((rc = among_unsharded(s, "ehx_knn_among_keys"))) return rc;
-  std::vector<uint64_t> ids(n_allowed);
-  {
-    std::shared_lock<std::shared_mutex> kl(s->kmu);
-    for (size_t i = 0; i < n_allowed; ++i) {
-      if (!keys[i]) return fail(EHX_EINVAL, "NULL argument");
-      if (implicit_id(s, keys[i], klens[i], &ids[i])) continue;
-      auto it = s->key_to_id.find(std::string(keys[i], klens[i]));
-      if (it == s->key_to_id.end()) {
-        if (bad_index) *bad_index = i;
-        return fail(EHX_ENOTFOUND, "Not found");
-      }
-      ids[i] = it->second;
-    }
-  }
+  std::vector<uint64_t> ids;
+  if ((rc = lookup_keys(s, n_allowed, keys, klens, &ids, bad_index))) return rc;
   if (n_queries == 0) return EHX_OK;
   std::lock_guard<std::mutex> sl(s->scratch_mu);
   return among_host_locked(s, n_queries, queries, k, ids.data(), nullptr, n_allowed, out_ids, out_dist, out_count);

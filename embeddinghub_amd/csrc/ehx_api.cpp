@@ -374,8 +374,7 @@ int ehx_get_by_id(ehx_space* s, uint64_t id, float* out_vec) {
     return EHX_OK;
   }
   if (s->x_perm) {  // single-copy graph space: the row is stored in the search copy's block order — undo it here
-    if (s->poisoned.load())
-      return fail(EHX_EINTERNAL, "graph space: an in-place overwrite failed half way (rows left in raw order); drop and rebuild it");
+    if (int rcp = check_not_poisoned(s)) return rcp;
     std::vector<float> h(s->ld);
     HIP_TRY(hipMemcpy(h.data(), s->xrow(id), (size_t)s->ld * sizeof(float), hipMemcpyDeviceToHost));
     for (uint32_t c = 0; c < s->dims; ++c) out_vec[c] = h[search_copy_pos(c)];

@@ -1,0 +1,147 @@
+// What the batched entry points (ehx_knn_among*, ehx_range*, ehx_knn_by_keys / _by_ids_device) and the flat chain share
+// around their kernels: argument checks, the poisoned / dropped / sharded gates, key lookup, where the rows are, the
+// result block of a host call, sub-batches, and the int8 scan's arguments.
+#include "ehx_internal.h"
+
+namespace ehx_impl {
+
+int check_not_poisoned(const ehx_space* s) {   // (only a single-copy graph space, x_perm, is ever poisoned: ehx_write.cpp)
+  if (s->poisoned.load())
+    return fail(EHX_EINTERNAL, "graph space: an in-place overwrite failed half way (rows left in raw order); drop and rebuild it");
+  return EHX_OK;
+}
+
+int check_space_and_k(const ehx_space* s, uint32_t k, const char* k_name, bool zero_k_ok) {
+  if (!s) return fail(EHX_EINVAL, "space is NULL");
+  if (k == 0 && !zero_k_ok) return fail(EHX_EINVAL, "%s is 0", k_name);
+  if (k > EHX_MAX_K_PAGED) return fail(EHX_EUNSUPPORTED, "%s=%u exceeds %u", k_name, k, EHX_MAX_K_PAGED);
+  return EHX_OK;
+}
+
+int check_batch_size(size_t nq) {
+  if (nq > (1u << 24)) return fail(EHX_EINVAL, "too many queries in one call: %zu", nq);
+  return EHX_OK;
+}
+
+int check_batch_call(const ehx_space* s, size_t nq, uint32_t k, const char* k_name, bool zero_k_ok, bool ptrs_ok,
+                     const char* null_text) {
+  int rc = check_space_and_k(s, k, k_name, zero_k_ok);
+  if (rc) return rc;
+  if (!ptrs_ok) return fail(EHX_EINVAL, "%s", null_text);
+  return check_batch_size(nq);
+}
+
+int check_unsharded(const ehx_space* s, const char* what, const char* why) {
+  if (s->dropped) return fail(EHX_ENOTFOUND, "Not found");
+  if (is_parent(s)) return fail(EHX_EUNSUPPORTED, "%s: space '%s' is row-sharded (%s)", what, s->name.c_str(), why);
+  return EHX_OK;
+}
+
+int lookup_keys(ehx_space* s, size_t n, const char* const* keys, const size_t* klens, std::vector<uint64_t>* ids,
+                size_t* bad_index) {
+  ids->resize(n);
+  std::shared_lock<std::shared_mutex> kl(s->kmu);
+  for (size_t i = 0; i < n; ++i) {
+    if (!keys[i]) return fail(EHX_EINVAL, "NULL argument");
+    if (implicit_id(s, keys[i], klens[i], &(*ids)[i])) continue;
+    auto it = s->key_to_id.find(std::string(keys[i], klens[i]));
+    if (it == s->key_to_id.end()) {
+      if (bad_index) *bad_index = i;
+      return fail(EHX_ENOTFOUND, "Not found");
+    }
+    (*ids)[i] = it->second;
+  }
+  return EHX_OK;
+}
+
+RowsView rows_view(const ehx_space* s, uint64_t n_pub) {
+  RowsView v;
+  v.X = s->rows.dX.p;
+  v.inv_norm = s->rows.dInv.p;
+  v.n_rows = n_pub;
+  v.dims = s->dims;
+  v.ld = s->ld;
+  v.x_half = (uint32_t)s->x_half;
+  v.x_perm = s->x_perm ? 1u : 0u;
+  v.metric = s->metric;
+  return v;
+}
+
+}  // namespace ehx_impl
+
+size_t ResultBlock::bytes(size_t nq, uint32_t k, bool with_total) {
+  return nq * k * (sizeof(uint64_t) + sizeof(float)) + nq * sizeof(uint32_t) + (with_total ? nq * sizeof(uint64_t) : 0);
+}
+
+ResultBlock ResultBlock::at(unsigned char* p, size_t nq, uint32_t k, bool with_total) {
+  const size_t ids_b = nq * k * sizeof(uint64_t), tot_b = with_total ? nq * sizeof(uint64_t) : 0, dist_b = nq * k * sizeof(float);
+  return {(uint64_t*)p, (float*)(p + ids_b + tot_b), (uint32_t*)(p + ids_b + tot_b + dist_b),
+          with_total ? (uint64_t*)(p + ids_b) : nullptr, nq, k};
+}
+
+int ResultBlock::copy_out(hipStream_t st, uint64_t* h_ids, float* h_dist, uint32_t* h_cnt, uint64_t* h_total) const {
+  HIP_TRY(hipMemcpyAsync(h_ids, ids, nq * k * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(h_dist, dist, nq * k * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(h_cnt, cnt, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  if (h_total && total) HIP_TRY(hipMemcpyAsync(h_total, total, nq * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return EHX_OK;
+}
+
+int SubsetBufs::gather(const float* d_queries, const std::vector<uint32_t>& idx, uint32_t dims, uint32_t k_, hipStream_t st) {
+  m = idx.size();
+  k = k_;
+  int rc;
+  if ((rc = dFbQ.ensure(m * dims))) return rc;
+  if ((rc = dFbIds.ensure(m * k))) return rc;
+  if ((rc = dFbDist.ensure(m * k))) return rc;
+  if ((rc = dFbCnt.ensure(m))) return rc;
+  if ((rc = dFbIdx.ensure(m))) return rc;
+  // (the index list comes from pageable host memory: the runtime stages it before the call returns)
+  HIP_TRY(hipMemcpyAsync(dFbIdx.p, idx.data(), m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  HIP_TRY(launch_gather_queries(d_queries, dFbIdx.p, (uint32_t)m, dims, dFbQ.p, st));
+  return EHX_OK;
+}
+
+int SubsetBufs::scatter(uint64_t* d_ids, float* d_dist, uint32_t* d_count, hipStream_t st) const {
+  HIP_TRY(launch_scatter_results(dFbIds.p, dFbDist.p, dFbCnt.p, dFbIdx.p, (uint32_t)m, k, d_ids, d_dist, d_count, st));
+  return EHX_OK;
+}
+
+namespace ehx_impl {
+
+int i8_scan_args(ehx_space* s, ehx_space::I8Set::Buffers& b, const ScanPlan& p, uint64_t n_pub, ScanArgsI8* a) {
+  int rc;
+  if ((rc = b.dQ.ensure((size_t)p.q_rows * s->ld))) return rc;
+  if ((rc = b.dQ8.ensure(scanq8_bytes(p.q_rows, s->ld8)))) return rc;
+  if ((rc = b.dQp8.ensure(p.q_rows))) return rc;
+  if ((rc = b.dQuv.ensure(p.q_rows))) return rc;
+  if ((rc = b.dThr8.ensure(p.q_rows))) return rc;
+  if ((rc = b.dCnt.ensure(8, true))) return rc;   // (the set's own: a batch may run outside the pipeline lock)
+  if ((rc = b.dPool.ensure((size_t)p.q_rows * kPoolCap))) return rc;
+  if ((rc = b.dI8Ctl.ensure((size_t)p.q_rows * 2 + kSyncWordsI8))) return rc;
+  *a = ScanArgsI8();
+  a->Q = b.dQ8.p;
+  a->X = s->i8.dX8.p;
+  a->rowp = s->i8.dRowp8.p;
+  a->tilep = s->i8.dTilep8.p;
+  a->tileg = s->i8.dTileg8.p;
+  a->perm = s->i8.dPerm8.p;
+  a->qparams = b.dQp8.p;
+  a->thr = b.dThr8.p;
+  a->cand = b.dCnt.p;
+  a->pool = b.dPool.p;
+  a->pool_cnt = b.dI8Ctl.p;
+  a->ovf = b.dI8Ctl.p + p.q_rows;
+  a->pool_cap = kPoolCap;
+  a->n = (uint32_t)n_pub;
+  a->ld = s->ld8;
+  a->q_tiles = p.q_tiles;
+  a->skew = env().i8_skew;
+  // (cosine / inner product: B_r is one constant, every margin 0; L2^2 on normalised rows: no tile has a margin worth the
+  // epilogue's extra permute and multiply-add per query block — 6.25 M x 128: 1.02 -> 1.07 ms per batch with them)
+  a->group_b = s->metric == EHX_METRIC_L2SQ && s->h_margin8.load(std::memory_order_relaxed) > 0 && env().i8_groupb ? 1u : 0u;
+  return EHX_OK;
+}
+
+}  // namespace ehx_impl

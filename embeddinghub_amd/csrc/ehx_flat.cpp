@@ -195,9 +195,7 @@ int flat_pass(ehx_space* s, uint64_t n_pub, hipStream_t st, size_t nq, const flo
   }
   RerankArgs r;
   r.Q = s->scr.dQ.p;
-  r.X = s->rows.dX.p;
-  r.x_half = (uint32_t)s->x_half;
-  r.inv_norm = s->rows.dInv.p;
+  r.rows = rows_view(s, n_pub);
   r.merged = s->scr.dMerged.p;
   r.out_ids = d_ids;
   r.out_dist = d_dist;
@@ -206,10 +204,6 @@ int flat_pass(ehx_space* s, uint64_t n_pub, hipStream_t st, size_t nq, const flo
   r.nq = (uint32_t)nq;
   r.k = k;
   r.kprime = p.kprime;
-  r.n = (uint32_t)n_pub;
-  r.dims = s->dims;
-  r.ld = s->ld;
-  r.metric = s->metric;
   if (f16) r.quv = s->scr.dQuv.p;
   r.max_sumsq = s->rows.dMaxSumsq.p;
   r.uncert_flags = s->scr.dUflags.p;
@@ -341,21 +335,15 @@ int flat_pass8(ehx_space* s, uint64_t n_pub, int set, hipStream_t st, size_t nq,
   }
   if (chunks_max > 256) return fail(EHX_EINTERNAL, "scan plan with %u chunks", chunks_max);
   int rc;
-  if ((rc = sc.buf.dQ.ensure((size_t)p.q_rows * s->ld))) return rc;
-  if ((rc = sc.buf.dQ8.ensure(scanq8_bytes(p.q_rows, s->ld8)))) return rc;
-  if ((rc = sc.buf.dQp8.ensure(p.q_rows))) return rc;
-  if ((rc = sc.buf.dQuv.ensure(p.q_rows))) return rc;
-  if ((rc = sc.buf.dThr8.ensure(p.q_rows))) return rc;
+  ScanArgsI8 a;
+  if ((rc = i8_scan_args(s, sc.buf, p, n_pub, &a))) return rc;
   if ((rc = sc.buf.dSample8.ensure((size_t)kSampleTiles * kTileRows16 * p.q_rows))) return rc;
-  if ((rc = sc.buf.dCnt.ensure(8, true))) return rc;   // (the set's own: this function runs outside the pipeline lock too)
-  if ((rc = sc.buf.dPool.ensure((size_t)p.q_rows * kPoolCap))) return rc;
   if ((rc = sc.buf.dMerged8.ensure((size_t)p.q_rows * width))) return rc;
-  if ((rc = sc.buf.dI8Ctl.ensure((size_t)p.q_rows * 2 + kSyncWordsI8))) return rc;
   if ((rc = sc.buf.dUflags.ensure(p.q_rows))) return rc;
   if ((rc = sc.buf.dUncert.ensure_zeroed_once(1))) return rc;
   if ((rc = sc.buf.hUncertPin.ensure(1))) return rc;
-  uint32_t* pool_cnt = sc.buf.dI8Ctl.p;
-  uint32_t* ovf = sc.buf.dI8Ctl.p + p.q_rows;
+  uint32_t* const pool_cnt = a.pool_cnt;
+  uint32_t* const ovf = a.ovf;
   uint32_t* sync = sc.buf.dI8Ctl.p + 2 * (size_t)p.q_rows;
   if ((rc = sc.buf.verdict.ensure(hipEventBlockingSync | hipEventDisableTiming))) return rc;
   // (a caller's stream other than the space's own: searches already in flight there and here finish first)
@@ -363,33 +351,8 @@ int flat_pass8(ehx_space* s, uint64_t n_pub, int set, hipStream_t st, size_t nq,
   if ((rc = sc.clock.begin(st, env().stats_every))) return rc;
   HIP_TRY(launch_prep_queries_i8(d_queries, (uint32_t)nq, s->dims, s->ld, s->ld8, p.q_rows, s->metric, sc.buf.dQ.p,
                                  sc.buf.dQ8.p, sc.buf.dQp8.p, sc.buf.dQuv.p, sc.buf.dThr8.p, sc.buf.dI8Ctl.p, st));
-  ScanArgsI8 a;
-  a.Q = sc.buf.dQ8.p;
-  a.X = s->i8.dX8.p;
-  a.rowp = s->i8.dRowp8.p;
-  a.tilep = s->i8.dTilep8.p;
-  a.tileg = s->i8.dTileg8.p;
-  a.perm = s->i8.dPerm8.p;
-  a.qparams = sc.buf.dQp8.p;
-  a.thr = sc.buf.dThr8.p;
-  a.cand = sc.buf.dCnt.p;
-  a.pool = sc.buf.dPool.p;
-  a.pool_cnt = pool_cnt;
-  a.ovf = ovf;
-  a.pool_cap = kPoolCap;
-  a.n = (uint32_t)n_pub;
-  a.ld = s->ld8;
-  a.q_tiles = p.q_tiles;
-  a.skew = env().i8_skew;
-  // (cosine / inner product: B_r is one constant, every margin 0; L2^2 on normalised rows: no tile has a margin worth the
-  // epilogue's extra permute and multiply-add per query block — 6.25 M x 128: 1.02 -> 1.07 ms per batch with them)
-  a.group_b = s->metric == EHX_METRIC_L2SQ && s->h_margin8.load(std::memory_order_relaxed) > 0 && env().i8_groupb ? 1u : 0u;
   auto scan = [&](const ScanPlan& pl, uint32_t tile0) -> hipError_t {
-    a.tile0 = tile0;
-    a.n_tiles = pl.n_tiles;
-    a.n_chunks = pl.n_chunks;
-    a.tiles_per_chunk = pl.tiles_per_chunk;
-    a.xcd_map = pl.xcd_map;
+    i8_scan_pass(a, pl, tile0);
     return launch_flat_scan_i8(a, st);
   };
   if ((rc = sc.clock.scan_begin(st))) return rc;
@@ -487,6 +450,7 @@ int exhaustive_pass(ehx_space* s, uint64_t n_pub, hipStream_t st, size_t nq, con
       (uint32_t)std::min<uint64_t>(8192, std::max<uint64_t>(64, ((uint64_t)n_pub * nq / 2048 + 63) / 64 * 64));
   const uint32_t n_blocks = (uint32_t)((n_pub + kRowsPerBlock - 1) / kRowsPerBlock);
   const uint32_t pages = (k + 63) / 64;
+  const RowsView rows = rows_view(s, n_pub);
   int rc;
   if ((rc = s->scr.dQ.ensure(nq * s->ld))) return rc;
   if ((rc = s->scr.dPart.ensure(nq * n_blocks * 64))) return rc;
@@ -504,15 +468,12 @@ int exhaustive_pass(ehx_space* s, uint64_t n_pub, hipStream_t st, size_t nq, con
   for (uint32_t pg = 0; pg < pages; ++pg) {
     if (pg) test_pause();
     const uint64_t* floor = pg ? s->scr.dGthr.p : nullptr;
-    HIP_TRY(launch_exhaustive(s->scr.dQ.p, s->rows.dX.p, s->x_half, s->rows.dInv.p, (uint32_t)n_pub, s->dims, s->ld, s->metric,
-                              kRowsPerBlock, n_blocks, (uint32_t)nq, floor, s->scr.dPart.p, st));
+    HIP_TRY(launch_exhaustive(s->scr.dQ.p, rows, kRowsPerBlock, n_blocks, (uint32_t)nq, floor, s->scr.dPart.p, st));
     HIP_TRY(launch_flat_merge(s->scr.dPart.p, (uint32_t)nq, n_blocks, 64, s->scr.dMerged.p, st, n_blocks));
     if (pg + 1 < pages) HIP_TRY(launch_set_floor(s->scr.dMerged.p, (uint32_t)nq, s->scr.dGthr.p, st));
     RerankArgs r;
     r.Q = s->scr.dQ.p;
-    r.X = s->rows.dX.p;
-    r.x_half = (uint32_t)s->x_half;
-    r.inv_norm = s->rows.dInv.p;
+    r.rows = rows;
     r.merged = s->scr.dMerged.p;
     r.out_ids = d_ids;
     r.out_dist = d_dist;
@@ -521,10 +482,6 @@ int exhaustive_pass(ehx_space* s, uint64_t n_pub, hipStream_t st, size_t nq, con
     r.nq = (uint32_t)nq;
     r.k = std::min<uint32_t>(64, k - pg * 64);
     r.kprime = 64;
-    r.n = (uint32_t)n_pub;
-    r.dims = s->dims;
-    r.ld = s->ld;
-    r.metric = s->metric;
     r.uncert_flags = s->scr.dUflags.p;
     r.exact_keys = 1;
     r.out_stride = k;
@@ -657,19 +614,13 @@ int knn_device_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_qu
     uint64_t* oi = d_ids;
     float* od = d_dist;
     uint32_t* oc = d_count;
+    SubsetBufs& sub = s->scr.sub;
     if (subset) {
-      if ((rc = s->scr.dFbQ.ensure(m * s->dims))) return rc;
-      if ((rc = s->scr.dFbIds.ensure(m * k))) return rc;
-      if ((rc = s->scr.dFbDist.ensure(m * k))) return rc;
-      if ((rc = s->scr.dFbCnt.ensure(m))) return rc;
-      if ((rc = s->scr.dFbIdx.ensure(m))) return rc;
-      // (the index list comes from pageable host memory: the runtime stages it before the call returns)
-      HIP_TRY(hipMemcpyAsync(s->scr.dFbIdx.p, subset->data(), m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-      HIP_TRY(launch_gather_queries(d_queries, s->scr.dFbIdx.p, (uint32_t)m, s->dims, s->scr.dFbQ.p, st));
-      q = s->scr.dFbQ.p;
-      oi = s->scr.dFbIds.p;
-      od = s->scr.dFbDist.p;
-      oc = s->scr.dFbCnt.p;
+      if ((rc = sub.gather(d_queries, *subset, s->dims, k, st))) return rc;
+      q = sub.dFbQ.p;
+      oi = sub.dFbIds.p;
+      od = sub.dFbDist.p;
+      oc = sub.dFbCnt.p;
     }
     // (the int8 stage runs in scratch set 0 here, held for the stage and its verdict: host batches may be using both sets
     // through knn_host_direct's pipelined path at the same time)
@@ -685,7 +636,7 @@ int knn_device_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_qu
     unsigned long long* d_unc = kind == kI8 ? s->i8set[0].buf.dUncert.p : s->scr.dUncert16.p;
     const uint32_t* d_flags = kind == kI8 ? s->i8set[0].buf.dUflags.p : s->scr.dUflags.p;
     if (subset) {
-      HIP_TRY(launch_scatter_results(oi, od, oc, s->scr.dFbIdx.p, (uint32_t)m, k, d_ids, d_dist, d_count, st));
+      if ((rc = sub.scatter(d_ids, d_dist, d_count, st))) return rc;
       if ((rc = s->clock.extend(st))) return rc;   // (the scatter is part of the pass's batch: writers wait for it too)
     }
     // verdict

@@ -375,8 +375,7 @@ int graph_update(ehx_space* s, uint32_t id) {
 // launch and the wave's first instruction but the runtime).
 int knn_graph_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, uint64_t* d_ids,
                      float* d_dist, uint32_t* d_count, const GraphOneLaunch* one) {
-  if (s->poisoned.load())
-    return fail(EHX_EINTERNAL, "graph space: an in-place overwrite failed half way (rows left in raw order); drop and rebuild it");
+  if (int rcp = check_not_poisoned(s)) return rcp;
   if (s->g_n != s->n)
     return fail(EHX_EUNSUPPORTED,
                 "graph mode: the graph covers %llu of %llu rows (rows were written while graph building was "

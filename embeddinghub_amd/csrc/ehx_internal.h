@@ -5,6 +5,7 @@
 //   ehx_shards.cpp  row-sharded spaces inside one process (ehx_params.shards)
 //   ehx_write.cpp   Set / BatchSet: staging, upload, row statistics, scan copies, write combiner
 //   ehx_search.cpp  ehx_knn_device / ehx_knn (host pointers, micro-batcher) / keys / merge
+//   ehx_call.cpp    what the batched entry points share: argument checks, key lookup, result blocks, sub-batches
 //   ehx_api.cpp     init, registry, Get, synthetic fill, graph import / export, statistics
 #pragma once
 // (was the head of ehx_api.cpp) C-ABI of the engine (include/ehx.h): process-global space registry, key <-> dense id map
@@ -126,6 +127,52 @@ struct BatchClock {
 
 }  // namespace ehx_impl
 using namespace ehx_impl;
+
+// A sub-batch of a call's queries: rows idx[0, m) of the batch gathered into a dense matrix, answered on their own into
+// [m][k] lists, and those written back to the rows they belong to (ehx_call.cpp).  Two instances per space — the engine
+// chain's (ehx_space::Scratch) and the range search's, whose overflow runs the engine chain while its own is in use.
+struct SubsetBufs {
+  DevBuf<float> dFbQ, dFbDist;
+  DevBuf<uint64_t> dFbIds;
+  DevBuf<uint32_t> dFbCnt, dFbIdx;
+  size_t m = 0;
+  uint32_t k = 0;
+  int gather(const float* d_queries, const std::vector<uint32_t>& idx, uint32_t dims, uint32_t k_, hipStream_t st);
+  int scatter(uint64_t* d_ids, float* d_dist, uint32_t* d_count, hipStream_t st) const;
+};
+
+// The result arrays of one batched call, [nq][k] ids | [nq] totals (range search; may be absent) | [nq][k] distances |
+// [nq] counts: the caller's device arrays, or carved from one staging buffer of a host call (ehx_call.cpp).
+struct ResultBlock {
+  uint64_t* ids;
+  float* dist;
+  uint32_t* cnt;
+  uint64_t* total;   // may be nullptr
+  size_t nq;
+  uint32_t k;
+  static size_t bytes(size_t nq, uint32_t k, bool with_total);
+  static ResultBlock at(unsigned char* p, size_t nq, uint32_t k, bool with_total);   // p: 8-byte aligned
+  ResultBlock from(size_t q0, size_t m) const {   // queries [q0, q0 + m)
+    return {ids + q0 * k, dist + q0 * k, cnt + q0, total ? total + q0 : nullptr, m, k};
+  }
+  int copy_out(hipStream_t st, uint64_t* h_ids, float* h_dist, uint32_t* h_cnt, uint64_t* h_total) const;  // ... and waits
+};
+
+// Launches of a call that failed may still be in flight: unless the call succeeded they are drained — and the runtime's
+// error cleared — before the call's scratch goes to the next caller.  `return drain.done(rc);` ends the guarded scope.
+struct DrainUnlessOk {
+  hipStream_t st;
+  bool ok = false;
+  int done(int rc) {
+    ok = rc == EHX_OK;
+    return rc;
+  }
+  ~DrainUnlessOk() {
+    if (ok) return;
+    (void)hipStreamSynchronize(st);
+    (void)hipGetLastError();
+  }
+};
 
 // Persistent host threads of a sharded space: worker i drives shard i + 1 (the caller's thread drives shard 0).  Round 2
 // started G - 1 std::threads per CALL; these live as long as the space and sleep on a condition variable between jobs.
@@ -377,10 +424,10 @@ struct ehx_space {
     DevBuf<unsigned long long> dUncert;
     // filter scratch: fp16 queries, per-query (gamma, u, v), per-query certification flags, re-run buffers
     DevBuf<__half> dQ16;
-    DevBuf<float> dQgamma, dFbQ, dFbDist, dSample;
+    DevBuf<float> dQgamma, dSample;
     DevBuf<float2> dQuv;
-    DevBuf<uint32_t> dUflags, dFbCnt, dFbIdx;
-    DevBuf<uint64_t> dFbIds;
+    DevBuf<uint32_t> dUflags;
+    SubsetBufs sub;                            // the queries a stage of the engine chain re-runs
     DevBuf<unsigned long long> dUncert16;      // queries the filter pass could not certify
     PinBuf<unsigned long long> hUncertPin;     // pinned landing place of a batch's verdict (uncertified-query count)
     PinBuf<char> hSmallPin;                    // pinned staging of small host calls: [queries | ids, distances, counts]
@@ -410,9 +457,8 @@ struct ehx_space {
     DevBuf<uint64_t> dPool;      // [slots][kPoolCap]
     DevBuf<uint32_t> dCtl;       // [slots] pool counts (= totals) | [q_rows] members kept by the int8 path's re-rank
     DevBuf<uint32_t> dSel;       // [slots] query of every slot
-    DevBuf<float> dFbQ, dFbDist;
-    DevBuf<uint64_t> dFbIds, dIota;
-    DevBuf<uint32_t> dFbCnt;
+    SubsetBufs sub;              // the overflowed queries, answered by the exact kNN pipeline
+    DevBuf<uint64_t> dIota;
     DevBuf<float> dQraw;         // host form: queries | radii
     DevBuf<unsigned char> dOut;  // host form: ids | distances | counts | totals
   } range;
@@ -576,6 +622,31 @@ void yield_to_writer(const ehx_space* s);   // a search lets an exclusive writer
 // the keys of result lists [n][k] (counts out_count) packed into key_arena, key_off[n * k + 1]: ehx_knn_keys' layout
 int fill_key_arena(ehx_space* s, size_t n, uint32_t k, const uint64_t* out_ids, const uint32_t* out_count, char* key_arena,
                    size_t arena_cap, uint64_t* key_off);
+
+// ---- ehx_call.cpp ----
+int check_not_poisoned(const ehx_space* s);   // a single-copy graph space whose rows an aborted overwrite left in raw order
+// a NULL space; k (or max_results: k_name) of 0 unless zero_k_ok, or above EHX_MAX_K_PAGED
+int check_space_and_k(const ehx_space* s, uint32_t k, const char* k_name, bool zero_k_ok);
+int check_batch_size(size_t nq);
+// the two around "a pointer the call needs is NULL" (ptrs_ok false: EHX_EINVAL with null_text)
+int check_batch_call(const ehx_space* s, size_t nq, uint32_t k, const char* k_name, bool zero_k_ok, bool ptrs_ok,
+                     const char* null_text = "NULL argument");
+// (space locked) dropped: EHX_ENOTFOUND; a row-sharded parent: EHX_EUNSUPPORTED "<what>: space '<name>' is row-sharded (<why>)"
+int check_unsharded(const ehx_space* s, const char* what, const char* why);
+// ids of n stored keys (space locked shared; takes kmu shared); an unknown key: EHX_ENOTFOUND, its index in *bad_index
+int lookup_keys(ehx_space* s, size_t n, const char* const* keys, const size_t* klens, std::vector<uint64_t>* ids,
+                size_t* bad_index);
+RowsView rows_view(const ehx_space* s, uint64_t n_pub);   // where the rows are, for a search on the prefix of n_pub rows
+// The int8 scan's arguments for a batch planned as `p` in the buffers `b` (grown as needed), all but the pass's own fields
+// (i8_scan_pass; dump, sync).  The control words are b.dI8Ctl: [q_rows] pool counts | [q_rows] overflow flags | lock-step.
+int i8_scan_args(ehx_space* s, ehx_space::I8Set::Buffers& b, const ScanPlan& p, uint64_t n_pub, ScanArgsI8* a);
+inline void i8_scan_pass(ScanArgsI8& a, const ScanPlan& pl, uint32_t tile0) {
+  a.tile0 = tile0;
+  a.n_tiles = pl.n_tiles;
+  a.n_chunks = pl.n_chunks;
+  a.tiles_per_chunk = pl.tiles_per_chunk;
+  a.xcd_map = pl.xcd_map;
+}
 
 // ---- ehx_among.cpp ----
 // exact kNN among row ids on an unsharded space, locked shared, scratch_mu held, its device current (d_off == nullptr: one

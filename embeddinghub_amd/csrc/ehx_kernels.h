@@ -598,6 +598,10 @@ __device__ __forceinline__ float wave_group_dists(const float* __restrict__ qs, 
   return wave_group_dists_t<METRIC01, false, QUAD>(qs, Xs, ld, dims, ids_l, count, lane, nullptr);
 }
 
+}  // namespace ehx
+#include "k_exact_common.h"   // RowsView, the row layouts and the exact paths' walk, built on the walkers above
+namespace ehx {
+
 struct ScanArgs {
   const float* Q;        // [q_tiles*256][ld] prepared queries (zero padded)
   const void* X;         // [cap][ld] stored rows (fp32, or fp16 when x_half), cap % 256 == 0, pad columns zero
@@ -817,16 +821,13 @@ hipError_t launch_flat_merge(const uint64_t* part, uint32_t nq, uint32_t n_chunk
 // canonical (oracle-order) distances of the merged candidates, sort by (dist, id), emit top-k.
 struct RerankArgs {
   const float* Q;          // prepared queries [*][ld]
-  const void* X;           // fp32 or fp16 rows
-  uint32_t x_half;
-  const float* inv_norm;   // [cap] (cosine) or nullptr
+  RowsView rows;           // fp32 or fp16 rows, plain layout
   const uint64_t* merged;  // [nq][64] keys (approx score, id)
   uint64_t* out_ids;       // [nq][k]
   float* out_dist;         // [nq][k]
   uint32_t* out_count;     // [nq]
   unsigned long long* n_uncertified;  // device counter
-  uint32_t nq, k, kprime, n, dims, ld;
-  int metric;
+  uint32_t nq, k, kprime;
   // fp16-filter scans: the keys hold S_lower; D = u*S + v maps the worst candidate back to a distance.
   // nullptr for the fp32 scan.
   const float2* quv = nullptr;
@@ -838,23 +839,20 @@ struct RerankArgs {
 hipError_t launch_rerank(const RerankArgs& a, hipStream_t st);
 // canonical distance of every row for each of nq prepared queries: out[q][block][64] best (distance, id) keys
 // (floor, optional: per query, only keys strictly above floor[q] are kept — paging for k > 64)
-hipError_t launch_exhaustive(const float* Q, const void* X, int x_half, const float* inv_norm, uint32_t n, uint32_t dims,
-                             uint32_t ld, int metric, uint32_t rows_per_block, uint32_t n_blocks, uint32_t nq,
+hipError_t launch_exhaustive(const float* Q, const RowsView& rows, uint32_t rows_per_block, uint32_t n_blocks, uint32_t nq,
                              const uint64_t* floor, uint64_t* out, hipStream_t st);
 hipError_t launch_set_floor(const uint64_t* merged, uint32_t nq, uint64_t* floor, hipStream_t st);
 // one query from host-visible memory against a small shard in one launch (k_flat.hip: single_query_kernel)
 struct SingleQueryArgs {
   const float* q_in;        // [dims] raw query (host-visible pinned memory, or device memory)
-  const void* X;            // rows, fp32 or fp16 (x_half)
-  const float* inv_norm;    // [cap] (cosine)
+  RowsView rows;            // fp32 or fp16 rows, plain layout
   uint64_t* part;           // [n_blocks][64] scratch: every workgroup's best keys
   uint32_t* ticket;         // device counter, 0 between calls
   uint64_t* out_ids;        // [k]  host-visible
   float* out_dist;          // [k]  host-visible
   uint32_t* out_count;      // [1]  host-visible
   uint32_t* done_flag;      // host-visible: set to `seq` when the results are in place
-  uint32_t seq, x_half, n, dims, ld, rows_per_block, k;
-  int metric;
+  uint32_t seq, rows_per_block, k;
 };
 hipError_t launch_single_query(const SingleQueryArgs& a, uint32_t n_blocks, hipStream_t st);
 
@@ -878,13 +876,11 @@ struct ShardBases {
 };
 struct GatherRowsArgs {
   const uint64_t* row_ids;  // [n] global row ids
+  RowsView rows;            // shape, layout and row count (an id at or above it gives a zero row, valid = 0); X: see bases
   ShardBases bases;         // rows of shard g % G, local row g / G; peers are read over the access ehx_init opened
-  uint64_t n_rows;          // the search's snapshot of the row count: an id at or above it gives a zero row, valid = 0
   float* out;               // [n][dims] what ehx_get_by_id returns for every row
   uint32_t* valid;          // [n]
-  uint32_t n, dims, ld, G;
-  uint32_t x_half;          // rows stored as binary16
-  uint32_t x_perm;          // fp32 rows stored in the search copy's block order (single-copy graph spaces)
+  uint32_t n, G;
 };
 hipError_t launch_gather_rows(const GatherRowsArgs& a, hipStream_t st);
 struct DropSelfArgs {
@@ -906,19 +902,14 @@ constexpr uint32_t kAmongTileQ = 8;     // shared list: queries a workgroup appl
 constexpr uint32_t kAmongTileRows = 8;  // ... rows per staged tile
 struct AmongArgs {
   const float* Q;            // prepared queries [nq][ld] (launch_prep_queries)
-  const void* X;             // stored rows
-  const float* inv_norm;     // [cap] (cosine)
-  const uint64_t* cand_ids;  // [n_cand] global row ids; an id at or above n_rows is ignored
+  RowsView rows;             // stored rows, any layout
+  const uint64_t* cand_ids;  // [n_cand] global row ids; an id at or above rows.n_rows is ignored
   const uint64_t* cand_off;  // nullptr: every query shares cand_ids[0, n_cand); else [nq + 1], query q owns [off[q], off[q + 1])
   const uint64_t* floor;     // optional, per query: only keys strictly above floor[q] are kept (paging for k > 64)
   uint64_t* out;             // [nq][n_blocks][64]
   uint64_t n_cand;
-  uint64_t n_rows;           // the search's snapshot of the row count
-  uint32_t nq, dims, ld;
+  uint32_t nq;
   uint32_t n_blocks;         // workgroups per query (or query tile): each walks its steps of the list in a grid-stride loop
-  uint32_t x_half;           // rows stored as binary16
-  uint32_t x_perm;           // fp32 rows stored in the search copy's block order (single-copy graph spaces)
-  int metric;
 };
 bool among_tiled(const AmongArgs& a);          // the shared-list kernel serves (cand_off == nullptr and the tiles fit in LDS)
 uint32_t among_max_ld();                       // longest row stride (floats) the kernels take: a prepared query must fit in LDS
@@ -934,18 +925,12 @@ hipError_t launch_among_emit(const uint64_t* merged, uint32_t nq, uint32_t k, ui
 // pool[j][kPoolCap] only while a slot is free — so it is the exact total, and pool_cnt[j] > kPoolCap is the overflow verdict.
 struct RangeArgs {
   const float* Q;            // prepared queries [*][ld] (launch_prep_queries), indexed by QUERY
-  const void* X;             // stored rows
-  const float* inv_norm;     // [cap] (cosine)
+  RowsView rows;             // stored rows, any layout
   const float* radius;       // [*] indexed by query
   const uint32_t* sel;       // optional [n_slots]: the queries this launch answers
   uint64_t* pool;            // [n_slots][kPoolCap] (canonical distance, id) keys, unsorted
   uint32_t* pool_cnt;        // [n_slots], zero before the launch
-  uint32_t n_rows;           // the search's snapshot of the row count
-  uint32_t dims, ld;
   uint32_t n_blocks;         // workgroups per query: each walks its steps of the rows in a grid-stride loop
-  uint32_t x_half;           // rows stored as binary16
-  uint32_t x_perm;           // fp32 rows stored in the search copy's block order (single-copy graph spaces)
-  int metric;
 };
 uint32_t range_step_rows(const RangeArgs& a);   // rows one workgroup takes per step of its loop
 hipError_t launch_range_exact(const RangeArgs& a, uint32_t n_slots, hipStream_t st);
@@ -960,8 +945,7 @@ hipError_t launch_range_thr(const float* radius, const float2* quv, const float*
                             int metric, float* thr, uint32_t* ovf, hipStream_t st);
 struct RangeRerankArgs {
   const float* Q;            // prepared queries [*][ld]
-  const void* X;             // stored rows, fp32 or binary16, plain layout
-  const float* inv_norm;
+  RowsView rows;             // stored rows, fp32 or binary16, plain layout
   const float* radius;       // [nq]
   const uint64_t* pool;      // [*][kPoolCap] the scan's (S_lower, id) keys
   const uint32_t* pool_cnt;  // [*]
@@ -971,8 +955,7 @@ struct RangeRerankArgs {
   float* out_dist;
   uint32_t* out_count;       // [nq]
   uint64_t* out_total;       // [nq] or nullptr
-  uint32_t nq, max_results, n_rows, dims, ld, x_half;
-  int metric;
+  uint32_t nq, max_results;
 };
 uint32_t range_rerank_max_ld();   // longest row stride (floats): the pool and the prepared query share the LDS
 hipError_t launch_range_rerank(const RangeRerankArgs& a, hipStream_t st);

@@ -12,31 +12,16 @@ namespace {
 constexpr size_t kRangeChunk = 2048;          // queries per device batch: their pools are 64 MiB
 constexpr uint32_t kRangeGridTarget = 4096;   // workgroups the exact kernel's launch aims for (16 per CU): chosen, not measured
 
-struct RangeOut {
-  uint64_t* ids;
-  float* dist;
-  uint32_t* cnt;
-  uint64_t* total;   // may be nullptr
-};
+typedef ResultBlock RangeOut;   // the caller's arrays, or a host call's staging block; total may be nullptr
 
-int range_check(ehx_space* s, size_t nq, uint32_t max_results, const void* q, const void* radius, const void* o_ids,
+int range_check(const ehx_space* s, size_t nq, uint32_t max_results, const void* q, const void* radius, const void* o_ids,
                 const void* o_dist, const void* o_cnt) {
   int rc = ehx_init(nullptr, 0);   // (no device: EHX_ENODEVICE, whatever else is wrong with the call)
   if (rc) return rc;
-  if (!valid_space(s)) return fail(EHX_EINVAL, "space is NULL");
-  if (max_results == 0) return fail(EHX_EINVAL, "max_results is 0");
-  if (max_results > EHX_MAX_K_PAGED) return fail(EHX_EUNSUPPORTED, "max_results=%u exceeds %u", max_results, EHX_MAX_K_PAGED);
-  if (!o_ids || !o_dist || !o_cnt || (nq && (!q || !radius))) return fail(EHX_EINVAL, "NULL argument");
-  if (nq > (1u << 24)) return fail(EHX_EINVAL, "too many queries in one call: %zu", nq);
-  return EHX_OK;
+  return check_batch_call(s, nq, max_results, "max_results", false, o_ids && o_dist && o_cnt && (!nq || (q && radius)));
 }
-
 int range_unsharded(const ehx_space* s, const char* what) {
-  if (s->dropped) return fail(EHX_ENOTFOUND, "Not found");
-  if (is_parent(s))
-    return fail(EHX_EUNSUPPORTED, "%s: space '%s' is row-sharded (range search over shards is not built yet)", what,
-                s->name.c_str());
-  return EHX_OK;
+  return check_unsharded(s, what, "range search over shards is not built yet");
 }
 
 // Queries whose pool overflowed (idx: their indices in the batch) have more than kPoolCap >= max_results members: their
@@ -44,28 +29,18 @@ int range_unsharded(const ehx_space* s, const char* what) {
 // its row ids, its graph is not walked).  The totals are already written.
 int range_overflow(ehx_space* s, hipStream_t st, uint64_t n_pub, const float* d_queries, const std::vector<uint32_t>& idx,
                    uint32_t k, const RangeOut& o) {
-  const size_t m = idx.size();
+  SubsetBufs& sub = s->range.sub;   // (its own: knn_device_locked's stages use the engine chain's)
   int rc;
-  if ((rc = s->range.dSel.ensure(m))) return rc;
-  if ((rc = s->range.dFbQ.ensure(m * s->dims))) return rc;
-  if ((rc = s->range.dFbIds.ensure(m * k))) return rc;
-  if ((rc = s->range.dFbDist.ensure(m * k))) return rc;
-  if ((rc = s->range.dFbCnt.ensure(m))) return rc;
-  // (the index list comes from pageable host memory: the runtime stages it before the call returns)
-  HIP_TRY(hipMemcpyAsync(s->range.dSel.p, idx.data(), m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-  HIP_TRY(launch_gather_queries(d_queries, s->range.dSel.p, (uint32_t)m, s->dims, s->range.dFbQ.p, st));
+  if ((rc = sub.gather(d_queries, idx, s->dims, k, st))) return rc;
   if (s->params.mode == EHX_MODE_GRAPH) {
     if ((rc = s->range.dIota.ensure(n_pub))) return rc;
     HIP_TRY(launch_range_iota(s->range.dIota.p, n_pub, st));
-    rc = among_locked(s, st, m, s->range.dFbQ.p, k, s->range.dIota.p, nullptr, n_pub, 0, s->range.dFbIds.p,
-                      s->range.dFbDist.p, s->range.dFbCnt.p);
+    rc = among_locked(s, st, sub.m, sub.dFbQ.p, k, s->range.dIota.p, nullptr, n_pub, 0, sub.dFbIds.p, sub.dFbDist.p, sub.dFbCnt.p);
   } else {
-    rc = knn_device_locked(s, st, m, s->range.dFbQ.p, k, s->range.dFbIds.p, s->range.dFbDist.p, s->range.dFbCnt.p, nullptr, 0,
-                           0, n_pub);
+    rc = knn_device_locked(s, st, sub.m, sub.dFbQ.p, k, sub.dFbIds.p, sub.dFbDist.p, sub.dFbCnt.p, nullptr, 0, 0, n_pub);
   }
   if (rc) return rc;
-  HIP_TRY(launch_scatter_results(s->range.dFbIds.p, s->range.dFbDist.p, s->range.dFbCnt.p, s->range.dSel.p, (uint32_t)m, k,
-                                 o.ids, o.dist, o.cnt, st));
+  if ((rc = sub.scatter(o.ids, o.dist, o.cnt, st))) return rc;
   return s->clock.extend(st);   // (the scatter belongs to the last batch: writers wait for it too)
 }
 
@@ -89,18 +64,11 @@ int range_exact_stage(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, c
   HIP_TRY(launch_prep_queries(d_queries, (uint32_t)nq, s->dims, s->ld, (uint32_t)nq, s->metric, s->scr.dQ.p, st));
   RangeArgs a = {};
   a.Q = s->scr.dQ.p;
-  a.X = s->rows.dX.p;
-  a.inv_norm = s->rows.dInv.p;
+  a.rows = rows_view(s, n_pub);
   a.radius = d_radius;
   a.sel = sel ? s->range.dSel.p : nullptr;
   a.pool = s->range.dPool.p;
   a.pool_cnt = s->range.dCtl.p;
-  a.n_rows = (uint32_t)n_pub;
-  a.dims = s->dims;
-  a.ld = s->ld;
-  a.x_half = (uint32_t)s->x_half;
-  a.x_perm = s->x_perm ? 1u : 0u;
-  a.metric = s->metric;
   const uint32_t step = range_step_rows(a);
   a.n_blocks = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(1, (n_pub + step - 1) / step),
                                             std::max<uint64_t>(1, kRangeGridTarget / m));
@@ -143,17 +111,9 @@ int range_i8_stage(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, cons
   const ScanPlan p = plan_scan((uint32_t)nq, n_tiles, 1, E.n_cus);   // ONE pass over all tiles
   if (p.n_chunks > 256) return fail(EHX_EINTERNAL, "scan plan with %u chunks", p.n_chunks);
   int rc;
-  if ((rc = sc.buf.dQ.ensure((size_t)p.q_rows * s->ld))) return rc;
-  if ((rc = sc.buf.dQ8.ensure(scanq8_bytes(p.q_rows, s->ld8)))) return rc;
-  if ((rc = sc.buf.dQp8.ensure(p.q_rows))) return rc;
-  if ((rc = sc.buf.dQuv.ensure(p.q_rows))) return rc;
-  if ((rc = sc.buf.dThr8.ensure(p.q_rows))) return rc;
-  if ((rc = sc.buf.dCnt.ensure(8, true))) return rc;
-  if ((rc = sc.buf.dPool.ensure((size_t)p.q_rows * kPoolCap))) return rc;
-  if ((rc = sc.buf.dI8Ctl.ensure((size_t)p.q_rows * 2 + kSyncWordsI8))) return rc;
+  ScanArgsI8 a;
+  if ((rc = i8_scan_args(s, sc.buf, p, n_pub, &a))) return rc;
   if ((rc = s->range.dCtl.ensure(p.q_rows))) return rc;
-  uint32_t* pool_cnt = sc.buf.dI8Ctl.p;
-  uint32_t* ovf = sc.buf.dI8Ctl.p + p.q_rows;
   {
     std::lock_guard<std::mutex> ql(s->i8_enqueue_mu);   // (this batch's launches go onto the stream as one block)
     if ((rc = wait_searches_in_flight(s, st))) return rc;
@@ -162,43 +122,19 @@ int range_i8_stage(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, cons
     HIP_TRY(launch_prep_queries_i8(d_queries, (uint32_t)nq, s->dims, s->ld, s->ld8, p.q_rows, s->metric, sc.buf.dQ.p,
                                    sc.buf.dQ8.p, sc.buf.dQp8.p, sc.buf.dQuv.p, sc.buf.dThr8.p, sc.buf.dI8Ctl.p, st));
     // ... then the radius' threshold, and the marks of the queries the bound does not serve
-    HIP_TRY(launch_range_thr(d_radius, sc.buf.dQuv.p, s->rows.dMaxSumsq.p, (uint32_t)nq, s->dims, s->metric, sc.buf.dThr8.p, ovf,
+    HIP_TRY(launch_range_thr(d_radius, sc.buf.dQuv.p, s->rows.dMaxSumsq.p, (uint32_t)nq, s->dims, s->metric, sc.buf.dThr8.p, a.ovf,
                              st));
-    ScanArgsI8 a;
-    a.Q = sc.buf.dQ8.p;
-    a.X = s->i8.dX8.p;
-    a.rowp = s->i8.dRowp8.p;
-    a.tilep = s->i8.dTilep8.p;
-    a.tileg = s->i8.dTileg8.p;
-    a.perm = s->i8.dPerm8.p;
-    a.qparams = sc.buf.dQp8.p;
-    a.thr = sc.buf.dThr8.p;
-    a.cand = sc.buf.dCnt.p;
-    a.pool = sc.buf.dPool.p;
-    a.pool_cnt = pool_cnt;
-    a.ovf = ovf;
-    a.pool_cap = kPoolCap;
-    a.n = (uint32_t)n_pub;
-    a.ld = s->ld8;
-    a.q_tiles = p.q_tiles;
-    a.skew = env().i8_skew;
-    a.group_b = s->metric == EHX_METRIC_L2SQ && s->h_margin8.load(std::memory_order_relaxed) > 0 && env().i8_groupb ? 1u : 0u;
-    a.tile0 = 0;
-    a.n_tiles = p.n_tiles;
-    a.n_chunks = p.n_chunks;
-    a.tiles_per_chunk = p.tiles_per_chunk;
-    a.xcd_map = p.xcd_map;
+    i8_scan_pass(a, p, 0);   // ONE pass over all tiles
     if ((rc = sc.clock.scan_begin(st))) return rc;
     HIP_TRY(launch_flat_scan_i8(a, st));
     if ((rc = sc.clock.scan_end(st))) return rc;
     RangeRerankArgs r = {};
     r.Q = sc.buf.dQ.p;
-    r.X = s->rows.dX.p;
-    r.inv_norm = s->rows.dInv.p;
+    r.rows = rows_view(s, n_pub);
     r.radius = d_radius;
     r.pool = sc.buf.dPool.p;
-    r.pool_cnt = pool_cnt;
-    r.ovf = ovf;
+    r.pool_cnt = a.pool_cnt;
+    r.ovf = a.ovf;
     r.kept = s->range.dCtl.p;
     r.out_ids = o.ids;
     r.out_dist = o.dist;
@@ -206,11 +142,6 @@ int range_i8_stage(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, cons
     r.out_total = o.total;
     r.nq = (uint32_t)nq;
     r.max_results = max_results;
-    r.n_rows = (uint32_t)n_pub;
-    r.dims = s->dims;
-    r.ld = s->ld;
-    r.x_half = (uint32_t)s->x_half;
-    r.metric = s->metric;
     HIP_TRY(launch_range_rerank(r, st));
     if ((rc = sc.clock.finish(st))) return rc;
   }
@@ -244,8 +175,8 @@ int range_i8_stage(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, cons
 // an unsharded space, locked shared, scratch_mu held, its device current; everything is enqueued on `st`
 int range_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, const float* d_radius, uint32_t max_results,
                  const RangeOut& out) {
-  if (s->x_perm && s->poisoned.load())
-    return fail(EHX_EINTERNAL, "graph space: an in-place overwrite failed half way (rows left in raw order); drop and rebuild it");
+  int rc;
+  if ((rc = check_not_poisoned(s))) return rc;
   if (s->ld > among_max_ld())   // (before anything is enqueued)
     return fail(EHX_EUNSUPPORTED, "range search keeps a prepared query in LDS: rows of %u floats exceed %u", s->ld,
                 among_max_ld());
@@ -258,9 +189,7 @@ int range_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries
     const size_t m = std::min(kRangeChunk, nq - q0);
     const float* q = d_queries + q0 * s->dims;
     const float* r = d_radius + q0;
-    const RangeOut o = {out.ids + q0 * max_results, out.dist + q0 * max_results, out.cnt + q0,
-                        out.total ? out.total + q0 : nullptr};
-    int rc;
+    const RangeOut o = out.from(q0, m);
     if (i8) {
       if ((rc = range_i8_stage(s, st, n_pub, m, q, r, max_results, o, &todo, &counted))) return rc;
       if (todo.empty()) continue;
@@ -275,36 +204,20 @@ int range_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries
 // host pointers in, host pointers out, on the space's stream (scratch_mu held): queries | radii staged in range.dQraw
 int range_host_locked(ehx_space* s, size_t nq, const float* queries, const float* radius, uint32_t k, uint64_t* out_ids,
                       float* out_dist, uint32_t* out_count, uint64_t* out_total) {
-  const size_t ids_b = nq * k * sizeof(uint64_t), tot_b = nq * sizeof(uint64_t), dist_b = nq * k * sizeof(float),
-               cnt_b = nq * sizeof(uint32_t);
   int rc;
   HIP_TRY(hipSetDevice(s->device));
   if ((rc = s->range.dQraw.ensure(nq * s->dims + nq))) return rc;
-  if ((rc = s->range.dOut.ensure(ids_b + tot_b + dist_b + cnt_b))) return rc;
+  if ((rc = s->range.dOut.ensure(ResultBlock::bytes(nq, k, true)))) return rc;
   float* d_q = s->range.dQraw.p;
   float* d_r = d_q + nq * s->dims;
-  const RangeOut o = {(uint64_t*)s->range.dOut.p, (float*)(s->range.dOut.p + ids_b + tot_b),
-                      (uint32_t*)(s->range.dOut.p + ids_b + tot_b + dist_b), (uint64_t*)(s->range.dOut.p + ids_b)};
-  auto run = [&]() -> int {
-    // (pageable host memory: the runtime stages it before the call returns; the staging buffers are this path's alone and
-    // the space's stream orders their reuse)
-    HIP_TRY(hipMemcpyAsync(d_q, queries, nq * s->dims * sizeof(float), hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(hipMemcpyAsync(d_r, radius, nq * sizeof(float), hipMemcpyHostToDevice, s->stream));
-    int r = range_locked(s, s->stream, nq, d_q, d_r, k, o);
-    if (r) return r;
-    HIP_TRY(hipMemcpyAsync(out_ids, o.ids, ids_b, hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipMemcpyAsync(out_dist, o.dist, dist_b, hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipMemcpyAsync(out_count, o.cnt, cnt_b, hipMemcpyDeviceToHost, s->stream));
-    if (out_total) HIP_TRY(hipMemcpyAsync(out_total, o.total, tot_b, hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return EHX_OK;
-  };
-  rc = run();
-  if (rc) {  // launches of this call may still be in flight: drain them before the scratch goes to the next caller
-    (void)hipStreamSynchronize(s->stream);
-    (void)hipGetLastError();
-  }
-  return rc;
+  const RangeOut o = ResultBlock::at(s->range.dOut.p, nq, k, true);
+  DrainUnlessOk drain{s->stream};
+  // (pageable host memory: the runtime stages it before the call returns; the staging buffers are this path's alone and
+  // the space's stream orders their reuse)
+  HIP_TRY(hipMemcpyAsync(d_q, queries, nq * s->dims * sizeof(float), hipMemcpyHostToDevice, s->stream));
+  HIP_TRY(hipMemcpyAsync(d_r, radius, nq * sizeof(float), hipMemcpyHostToDevice, s->stream));
+  if ((rc = range_locked(s, s->stream, nq, d_q, d_r, k, o))) return rc;
+  return drain.done(o.copy_out(s->stream, out_ids, out_dist, out_count, out_total));
 }
 
 }  // namespace
@@ -352,13 +265,9 @@ int ehx_range_device(ehx_space* s, void* stream, size_t n_queries, const float* 
   if (n_queries == 0) return EHX_OK;
   std::lock_guard<std::mutex> sl(s->scratch_mu);
   HIP_TRY(hipSetDevice(s->device));
-  rc = range_locked(s, (hipStream_t)stream, n_queries, d_queries, d_radius, max_results,
-                    RangeOut{d_out_ids, d_out_dist, d_out_count, d_out_total});
-  if (rc) {  // launches of this call may still be in flight: drain them before the scratch goes to the next caller
-    (void)hipStreamSynchronize((hipStream_t)stream);
-    (void)hipGetLastError();
-  }
-  return rc;
+  DrainUnlessOk drain{(hipStream_t)stream};
+  return drain.done(range_locked(s, (hipStream_t)stream, n_queries, d_queries, d_radius, max_results,
+                                 RangeOut{d_out_ids, d_out_dist, d_out_count, d_out_total, n_queries, max_results}));
 }
 
 // test hook, not part of the ABI: queries answered by the int8 path, by the exact path, pool overflows, truncated answers

@@ -19,29 +19,24 @@ struct ByKeyScratch {   // carved from ehx_space::dByOut (scratch_mu)
   float* l_dist;
   uint32_t* l_cnt;      // [n]
   uint32_t* valid;      // [n]
-  uint64_t* o_ids;      // [n][k] a host call's results (host_out)
-  float* o_dist;
-  uint32_t* o_cnt;
+  ResultBlock out;      // [n][k] a host call's results (host_out)
 };
 
 static int by_scratch(ehx_space* s, size_t n, uint32_t k, bool host_out, ByKeyScratch* b) {
   const size_t kk = (size_t)k + 1;
   const size_t o_ldist = n * kk * sizeof(uint64_t), o_lcnt = o_ldist + n * kk * sizeof(float);
   const size_t o_valid = o_lcnt + n * sizeof(uint32_t);
-  const size_t o_oids = round_up(o_valid + n * sizeof(uint32_t), 8);
-  const size_t o_odist = o_oids + n * k * sizeof(uint64_t), o_ocnt = o_odist + n * k * sizeof(float);
+  const size_t o_out = round_up(o_valid + n * sizeof(uint32_t), 8);
   int rc;
   if ((rc = s->by.dByQ.ensure(n * s->dims))) return rc;
-  if ((rc = s->by.dByOut.ensure(host_out ? o_ocnt + n * sizeof(uint32_t) : o_oids))) return rc;
+  if ((rc = s->by.dByOut.ensure(o_out + (host_out ? ResultBlock::bytes(n, k, false) : 0)))) return rc;
   if ((rc = s->by.by_ev.ensure(hipEventDisableTiming))) return rc;
   unsigned char* p = s->by.dByOut.p;
   b->l_ids = (uint64_t*)p;
   b->l_dist = (float*)(p + o_ldist);
   b->l_cnt = (uint32_t*)(p + o_lcnt);
   b->valid = (uint32_t*)(p + o_valid);
-  b->o_ids = host_out ? (uint64_t*)(p + o_oids) : nullptr;
-  b->o_dist = host_out ? (float*)(p + o_odist) : nullptr;
-  b->o_cnt = host_out ? (uint32_t*)(p + o_ocnt) : nullptr;
+  b->out = host_out ? ResultBlock::at(p + o_out, n, k, false) : ResultBlock{};
   return EHX_OK;
 }
 
@@ -65,26 +60,21 @@ static int by_drop_self(const ByKeyScratch& b, hipStream_t st, size_t n, const u
 // an unsharded space, locked shared, scratch_mu held, its device current; everything is enqueued on `st`
 static int by_ids_locked(ehx_space* s, hipStream_t st, size_t n, const uint64_t* d_row_ids, uint32_t k,
                          const ByKeyScratch& b, uint64_t* d_out_ids, float* d_out_dist, uint32_t* d_out_count) {
-  if (s->x_perm && s->poisoned.load())
-    return fail(EHX_EINTERNAL, "graph space: an in-place overwrite failed half way (rows left in raw order); drop and rebuild it");
+  int rc;
+  if ((rc = check_not_poisoned(s))) return rc;
   // (the last call's launches — on whatever stream it was given — have read and written this scratch)
   HIP_TRY(hipStreamWaitEvent(st, s->by.by_ev, 0));
   // the ONE read of the row count: the gather's range check and the flat chain's passes answer for the same prefix
   const uint64_t n_pub = s->n.load(std::memory_order_acquire);
   GatherRowsArgs g = {};
   g.row_ids = d_row_ids;
-  g.bases.p[0] = s->rows.dX.p;
-  g.n_rows = n_pub;
+  g.rows = rows_view(s, n_pub);
+  g.bases.p[0] = g.rows.X;
   g.out = s->by.dByQ.p;
   g.valid = b.valid;
   g.n = (uint32_t)n;
-  g.dims = s->dims;
-  g.ld = s->ld;
   g.G = 1;
-  g.x_half = (uint32_t)s->x_half;
-  g.x_perm = s->x_perm ? 1u : 0u;
   HIP_TRY(launch_gather_rows(g, st));
-  int rc = EHX_OK;
   if (n_pub > 0)   // (an empty space: every query is invalid, the lists are never read)
     rc = knn_device_locked(s, st, n, s->by.dByQ.p, k + 1, b.l_ids, b.l_dist, b.l_cnt, nullptr, 0, 0, n_pub);
   if (!rc) rc = by_drop_self(b, st, n, d_row_ids, k, d_out_ids, d_out_dist, d_out_count);
@@ -113,37 +103,22 @@ static int sharded_by_ids_locked(ehx_space* p, size_t n, const uint64_t* d_row_i
       ehx_space* c = p->shards[i];
       held.emplace_back(c->mu);
       if (c->dropped) return fail(EHX_ENOTFOUND, "Not found");
-      if (c->x_perm && c->poisoned.load())
-        return fail(EHX_EINTERNAL, "graph space: an in-place overwrite failed half way (rows left in raw order); drop and rebuild it");
+      if (int rcp = check_not_poisoned(c)) return rcp;
       g.bases.p[i] = c->rows.dX.p;
     }
-    const ehx_space* c0 = p->shards[0];
     g.row_ids = d_row_ids;
-    g.n_rows = n_pub;
+    g.rows = rows_view(p->shards[0], n_pub);   // (shape and layout are the shards'; the rows: bases)
     g.out = p->by.dByQ.p;
     g.valid = b.valid;
     g.n = (uint32_t)n;
-    g.dims = c0->dims;
-    g.ld = c0->ld;
     g.G = (uint32_t)G;
-    g.x_half = (uint32_t)c0->x_half;
-    g.x_perm = c0->x_perm ? 1u : 0u;
     HIP_TRY(launch_gather_rows(g, p->stream));
     HIP_TRY(hipStreamSynchronize(p->stream));
   }
   int rc = sharded_knn_locked(p, n, nullptr, p->by.dByQ.p, home, k + 1, b.l_ids, b.l_dist, b.l_cnt, true, p->stream);
   if (rc) return rc;
   HIP_TRY(hipSetDevice(home));
-  return by_drop_self(b, p->stream, n, d_row_ids, k, b.o_ids, b.o_dist, b.o_cnt);
-}
-
-static int by_copy_out(hipStream_t st, uint64_t* out_ids, const uint64_t* d_ids, size_t ids_b, float* out_dist,
-                       const float* d_dist, size_t dist_b, uint32_t* out_count, const uint32_t* d_cnt, size_t cnt_b) {
-  HIP_TRY(hipMemcpyAsync(out_ids, d_ids, ids_b, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(out_dist, d_dist, dist_b, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(out_count, d_cnt, cnt_b, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return EHX_OK;
+  return by_drop_self(b, p->stream, n, d_row_ids, k, b.out.ids, b.out.dist, b.out.cnt);
 }
 
 // ---- one query per call in one launch (knn_host_direct): the host-visible block and the wait for the kernel's flag ----
@@ -262,8 +237,7 @@ static int knn_host_direct(ehx_space* s, size_t n_queries, const float* queries,
       memcpy(h, queries, qbytes);
       SingleQueryArgs a;
       a.q_in = (const float*)h;
-      a.X = s->rows.dX.p;
-      a.inv_norm = s->rows.dInv.p;
+      a.rows = rows_view(s, n_pub);
       a.part = s->one.dOnePart.p;
       a.ticket = s->one.dOneTicket.p;
       a.out_ids = (uint64_t*)(h + kOneQ);
@@ -271,13 +245,8 @@ static int knn_host_direct(ehx_space* s, size_t n_queries, const float* queries,
       a.out_count = (uint32_t*)(h + kOneQ + 768);
       a.done_flag = (uint32_t*)(h + kOneQ + 1024);
       a.seq = ++s->one_seq ? s->one_seq : ++s->one_seq;   // (never 0: the buffer starts zeroed)
-      a.x_half = (uint32_t)s->x_half;
-      a.n = (uint32_t)n_pub;
-      a.dims = s->dims;
-      a.ld = s->ld;
       a.rows_per_block = rpb;
       a.k = k;
-      a.metric = s->metric;
       HIP_TRY(launch_single_query(a, n_blocks, s->stream));
       if ((rc = one_launch_wait(s, a.done_flag, a.seq, "single-query kernel"))) return rc;
       memcpy(out_ids, a.out_ids, k * sizeof(uint64_t));
@@ -612,8 +581,8 @@ int ehx_knn_by_key_keys(ehx_space* s, const char* key, size_t klen, uint32_t k, 
 
 int ehx_knn_by_keys(ehx_space* s, size_t n, const char* const* keys, const size_t* klens, uint32_t k, uint64_t* out_ids,
                     float* out_dist, uint32_t* out_count, size_t* bad_index) {
-  if (!valid_space(s)) return fail(EHX_EINVAL, "space is NULL");
-  if (k > EHX_MAX_K_PAGED) return fail(EHX_EUNSUPPORTED, "k=%u exceeds %u", k, EHX_MAX_K_PAGED);  // (before k + 1, before any allocation)
+  int rc = check_space_and_k(s, k, "k", true);   // (before k + 1, before any allocation)
+  if (rc) return rc;
   if (n == 0) return EHX_OK;
   if (!out_count) return fail(EHX_EINVAL, "out_count is NULL");
   if (k == 0) {
@@ -621,43 +590,26 @@ int ehx_knn_by_keys(ehx_space* s, size_t n, const char* const* keys, const size_
     return EHX_OK;
   }
   if (!keys || !klens || !out_ids || !out_dist) return fail(EHX_EINVAL, "NULL argument");
-  if (n > (1u << 24)) return fail(EHX_EINVAL, "too many queries in one call: %zu", n);
+  if ((rc = check_batch_size(n))) return rc;
   yield_to_writer(s);
   // ONE shared hold for key lookup, gather and search: the answer describes one state of the space
   std::shared_lock<std::shared_mutex> rl(s->mu);
   if (s->dropped) return fail(EHX_ENOTFOUND, "Not found");
-  std::vector<uint64_t> ids(n);
-  {
-    std::shared_lock<std::shared_mutex> kl(s->kmu);
-    for (size_t i = 0; i < n; ++i) {
-      if (!keys[i]) return fail(EHX_EINVAL, "NULL argument");
-      if (implicit_id(s, keys[i], klens[i], &ids[i])) continue;
-      auto it = s->key_to_id.find(std::string(keys[i], klens[i]));
-      if (it == s->key_to_id.end()) {
-        if (bad_index) *bad_index = i;
-        return fail(EHX_ENOTFOUND, "Not found");
-      }
-      ids[i] = it->second;
-    }
-  }
-  const size_t ids_b = n * k * sizeof(uint64_t), dist_b = n * k * sizeof(float), cnt_b = n * sizeof(uint32_t);
-  int rc;
+  std::vector<uint64_t> ids;
+  if ((rc = lookup_keys(s, n, keys, klens, &ids, bad_index))) return rc;
   ehx_space* home = is_parent(s) ? s->shards[0] : s;   // the device the batch is gathered, merged and trimmed on
   std::lock_guard<std::mutex> sl(s->scratch_mu);
   HIP_TRY(hipSetDevice(home->device));
   ByKeyScratch b;
   if ((rc = by_scratch(s, n, k, true, &b))) return rc;
   if ((rc = s->by.dByIds.ensure(n))) return rc;
+  DrainUnlessOk drain{s->stream};
   // (pageable host memory: the runtime stages it before the call returns)
   HIP_TRY(hipMemcpyAsync(s->by.dByIds.p, ids.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, s->stream));
   if (is_parent(s)) rc = sharded_by_ids_locked(s, n, s->by.dByIds.p, k, b);
-  else rc = by_ids_locked(s, s->stream, n, s->by.dByIds.p, k, b, b.o_ids, b.o_dist, b.o_cnt);
-  if (!rc) rc = by_copy_out(s->stream, out_ids, b.o_ids, ids_b, out_dist, b.o_dist, dist_b, out_count, b.o_cnt, cnt_b);
-  if (rc) {  // launches of this call may still be in flight: drain them before the scratch goes to the next caller
-    (void)hipStreamSynchronize(s->stream);
-    (void)hipGetLastError();
-  }
-  return rc;
+  else rc = by_ids_locked(s, s->stream, n, s->by.dByIds.p, k, b, b.out.ids, b.out.dist, b.out.cnt);
+  if (rc) return rc;
+  return drain.done(b.out.copy_out(s->stream, out_ids, out_dist, out_count, nullptr));
 }
 
 int ehx_knn_by_keys_keys(ehx_space* s, size_t n, const char* const* keys, const size_t* klens, uint32_t k,
@@ -673,19 +625,15 @@ int ehx_knn_by_keys_keys(ehx_space* s, size_t n, const char* const* keys, const 
 
 int ehx_knn_by_ids_device(ehx_space* s, void* stream, size_t n, const uint64_t* d_row_ids, uint32_t k,
                           uint64_t* d_out_ids, float* d_out_dist, uint32_t* d_out_count) {
-  if (!valid_space(s)) return fail(EHX_EINVAL, "space is NULL");
-  if (k > EHX_MAX_K_PAGED) return fail(EHX_EUNSUPPORTED, "k=%u exceeds %u", k, EHX_MAX_K_PAGED);
-  if (n && k && (!d_row_ids || !d_out_ids || !d_out_dist || !d_out_count)) return fail(EHX_EINVAL, "NULL device pointer");
-  if (n > (1u << 24)) return fail(EHX_EINVAL, "too many queries in one call: %zu", n);
+  int rc = check_batch_call(s, n, k, "k", true, !(n && k) || (d_row_ids && d_out_ids && d_out_dist && d_out_count),
+                            "NULL device pointer");
+  if (rc) return rc;
   yield_to_writer(s);
   std::shared_lock<std::shared_mutex> rl(s->mu);
-  if (s->dropped) return fail(EHX_ENOTFOUND, "Not found");
-  if (is_parent(s))
-    return fail(EHX_EUNSUPPORTED, "ehx_knn_by_ids_device: space '%s' is row-sharded (use ehx_knn_by_keys)", s->name.c_str());
+  if ((rc = check_unsharded(s, "ehx_knn_by_ids_device", "use ehx_knn_by_keys"))) return rc;
   if (n == 0 || k == 0) return EHX_OK;
   std::lock_guard<std::mutex> sl(s->scratch_mu);
   HIP_TRY(hipSetDevice(s->device));
-  int rc;
   ByKeyScratch b;
   if ((rc = by_scratch(s, n, k, false, &b))) return rc;
   return by_ids_locked(s, (hipStream_t)stream, n, d_row_ids, k, b, d_out_ids, d_out_dist, d_out_count);

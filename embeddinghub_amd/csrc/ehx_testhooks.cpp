@@ -100,19 +100,19 @@ int ehx_test_i8_pass(ehx_space* s, uint32_t nq, const float* queries, const floa
   const ScanPlan p = plan_scan(nq, n_tiles, 1, E.n_cus);
   if (p.n_chunks > 256) return fail(EHX_EINTERNAL, "scan plan with %u chunks", p.n_chunks);
   // scratch of this call alone (owners: freed on every return)
-  DevBuf<float> dQraw, dQ, dThr, dDump;
-  DevBuf<int8_t> dQ8;
-  DevBuf<float4> dQp;
-  DevBuf<float2> dQuv;
-  DevBuf<uint64_t> dPool, dCnt;
-  DevBuf<uint32_t> dCtl;
+  ehx_space::I8Set::Buffers b;
+  DevBuf<float> dQraw, dDump;
   const size_t q8_bytes = scanq8_bytes(p.q_rows, s->ld8);
   const size_t dump_elems = (size_t)p.q_rows * n_tiles * kTileRows16;
-  if ((rc = dQraw.ensure((size_t)nq * s->dims)) || (rc = dQ.ensure((size_t)p.q_rows * s->ld)) || (rc = dThr.ensure(p.q_rows)) ||
-      (rc = dQ8.ensure(q8_bytes)) || (rc = dQp.ensure(p.q_rows)) || (rc = dQuv.ensure(p.q_rows)) || (rc = dCnt.ensure(8, true)) ||
-      (rc = dCtl.ensure((size_t)p.q_rows * 2 + kSyncWordsI8)))
-    return rc;
-  if (thr ? (rc = dPool.ensure((size_t)p.q_rows * kPoolCap)) : (rc = dDump.ensure(dump_elems))) return rc;
+  ScanArgsI8 a;   // filled as flat_pass8 fills it
+  if ((rc = dQraw.ensure((size_t)nq * s->dims)) || (rc = i8_scan_args(s, b, p, n_pub, &a))) return rc;
+  if (!thr && (rc = dDump.ensure(dump_elems))) return rc;
+  DevBuf<float>&dQ = b.dQ, &dThr = b.dThr8;
+  DevBuf<int8_t>& dQ8 = b.dQ8;
+  DevBuf<float4>& dQp = b.dQp8;
+  DevBuf<float2>& dQuv = b.dQuv;
+  DevBuf<uint64_t>& dPool = b.dPool;
+  DevBuf<uint32_t>& dCtl = b.dI8Ctl;
   std::vector<uint64_t> pool(thr ? (size_t)nq * kPoolCap : 0);
   uint32_t lockstep = 0;
   auto run = [&]() -> int {
@@ -125,30 +125,7 @@ int ehx_test_i8_pass(ehx_space* s, uint32_t nq, const float* queries, const floa
                                    dCtl.p, st));
     // ... then the caller's thresholds
     if (thr) HIP_TRY(hipMemcpyAsync(dThr.p, thr, (size_t)nq * sizeof(float), hipMemcpyHostToDevice, st));
-    ScanArgsI8 a;   // filled as flat_pass8 fills it (ehx_flat.cpp)
-    a.Q = dQ8.p;
-    a.X = s->i8.dX8.p;
-    a.rowp = s->i8.dRowp8.p;
-    a.tilep = s->i8.dTilep8.p;
-    a.tileg = s->i8.dTileg8.p;
-    a.perm = s->i8.dPerm8.p;
-    a.qparams = dQp.p;
-    a.thr = dThr.p;
-    a.cand = dCnt.p;
-    a.pool = dPool.p;
-    a.pool_cnt = dCtl.p;
-    a.ovf = dCtl.p + p.q_rows;
-    a.pool_cap = kPoolCap;
-    a.n = (uint32_t)n_pub;
-    a.ld = s->ld8;
-    a.q_tiles = p.q_tiles;
-    a.skew = env().i8_skew;
-    a.group_b = s->metric == EHX_METRIC_L2SQ && s->h_margin8.load(std::memory_order_relaxed) > 0 && env().i8_groupb ? 1u : 0u;
-    a.tile0 = tile0;
-    a.n_tiles = p.n_tiles;
-    a.n_chunks = p.n_chunks;
-    a.tiles_per_chunk = p.tiles_per_chunk;
-    a.xcd_map = p.xcd_map;
+    i8_scan_pass(a, p, tile0);
     a.dump = thr ? nullptr : dDump.p;
     a.sync = nullptr;
     if (thr && env().i8_sync > 0 && p.xcd_map && p.q_tiles > 1 && p.tiles_per_chunk >= 4 && p.n_chunks * 4u <= kSyncWordsI8) {
@@ -198,5 +175,8 @@ int ehx_test_i8_pass(ehx_space* s, uint32_t nq, const float* queries, const floa
   }
   return EHX_OK;
 }
+
+// how many ehx_knn calls the one-launch kernels answered (single_query_kernel, the graph search's one-launch form)
+uint64_t ehx_test_one_launch_count(ehx_space* s) { return s ? s->n_one_launch.load(std::memory_order_relaxed) : 0; }
 
 }  // extern "C"

@@ -6,10 +6,11 @@
 //   among_tile_kernel   ONE list shared by every query: a workgroup stages 8 gathered rows in LDS and applies them to a tile
 //                       of 8 queries before it moves on, so a row makes one trip through the memory system per 8 pairs
 //                       (and the workgroups of the other query tiles, resident together, find it in L2).
-// Every distance comes from canon_dist / canon_dist_lane_t / canon_dist_group_t (ehx_kernels.h); the row layouts are those
-// gather_rows_kernel (k_bykey.hip) reads: fp32 rows as stored, binary16 rows widened exactly, single-copy graph rows in the
-// search copy's block order.  Cosine rows are scaled by inv_norm — one rounding per element, hnswlib-python's stored
-// normalised row — on the fly (list kernel) or as they are staged (tile kernel).
+// The list kernel takes every distance from the exact paths' one row walk (walk_row, k_exact_common.h), the tile kernel
+// from canon_dist over the rows it staged; keys, best-64 lists and the page come from the same header.  The row layouts
+// are those gather_rows_kernel (k_bykey.hip) reads: fp32 rows as stored, binary16 rows widened exactly, single-copy graph
+// rows in the search copy's block order.  Cosine rows are scaled by inv_norm — one rounding per element, hnswlib-python's
+// stored normalised row — on the fly (list kernel) or as they are staged (tile kernel).
 #include "ehx_kernels.h"
 
 namespace ehx {
@@ -18,33 +19,17 @@ namespace {
 
 typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
 
-enum { kLayoutF32 = 0, kLayoutF16 = 1, kLayoutPerm = 2 };
-
 constexpr uint32_t kLdsPad = 4;   // floats behind every LDS row: the 8 rows a 32-lane group reads fall into 32 banks
-
-__device__ __forceinline__ uint64_t among_key(float d, uint32_t id, bool ok, bool paged, uint64_t fl) {
-  uint64_t key = (ok && d == d) ? (((uint64_t)f32_to_ordered(d) << 32) | id) : kKeyInf;   // NaN: not a neighbour
-  if (paged && key <= fl) key = kKeyInf;   // paging (k > 64): only keys strictly above the previous page's last
-  return key;
-}
-
-// the 64 smallest of (best, 64 unsorted keys), ascending across the wave
-__device__ __forceinline__ uint64_t keep_best64(uint64_t best, uint64_t key, int lane) {
-  key = wave_sort64(key, lane);
-  const uint64_t rv = __shfl(key, 63 - lane, 64);
-  return wave_bitonic_merge64(best < rv ? best : rv, lane);
-}
 
 }  // namespace
 
 // Grid (queries, blocks): block b of query q walks steps b, b + gridDim.y, ... of the query's list until its end, a step
-// being 256 rows (fp32 rows: one lane per row, canon_dist_lane_t, 16-byte loads) or 64 rows (binary16 rows: canon_dist;
-// block-permuted rows: canon_dist_group_t, 16-byte loads; a 4-lane group per row).  The grid is sized from a hint of the
-// longest list; a hint that is too small costs time, never rows.  The query sits in LDS (permuted like the rows for the
-// block-permuted layout).
+// being 256 rows (fp32 rows: one lane per row) or 64 rows (binary16 and block-permuted rows: a 4-lane group per row) of
+// walk_row.  The grid is sized from a hint of the longest list; a hint that is too small costs time, never rows.  The
+// query sits in LDS (permuted like the rows for the block-permuted layout).
 template <int LAYOUT, int METRIC>
 __global__ __launch_bounds__(256) void among_list_kernel(const AmongArgs a) {
-  constexpr uint32_t kStep = LAYOUT == kLayoutF32 ? 256u : 64u;
+  constexpr uint32_t kStep = walk_rows<LAYOUT, true>(256);
   extern __shared__ float4 among_lds[];
   __shared__ uint64_t keys[256];
   float* qs = (float*)among_lds;
@@ -56,41 +41,19 @@ __global__ __launch_bounds__(256) void among_list_kernel(const AmongArgs a) {
     hi = a.cand_off[q + 1];
     hi = hi < a.n_cand ? hi : a.n_cand;   // (the device form cannot check its offsets: never read beyond the id array)
   }
-  const float* qv = a.Q + (size_t)q * a.ld;
-  for (uint32_t m = tid; m < a.ld; m += 256) qs[LAYOUT == kLayoutPerm ? search_copy_pos(m) : m] = qv[m];
+  stage_query_lds<LAYOUT>(qs, a.Q + (size_t)q * a.rows.ld, a.rows.ld, tid, 256);
   __syncthreads();
-  constexpr bool scale = METRIC == 2;
-  constexpr int metric01 = METRIC == 0 ? 0 : 1;
   const uint64_t fl = a.floor ? a.floor[q] : 0ull;
   const bool paged = a.floor != nullptr;
+  const uint32_t slot = walk_slot<LAYOUT, true>(tid);
+  const bool writer = walk_by_lane<LAYOUT, true>() || (tid & 3) == 0;   // this lane files its slot's key
   uint64_t best = kKeyInf;
   for (uint64_t p0 = lo + (uint64_t)blockIdx.y * kStep; p0 < hi; p0 += (uint64_t)gridDim.y * kStep) {
-    if (LAYOUT == kLayoutF32) {
-      const uint64_t p = p0 + (uint64_t)tid;
-      const uint64_t id = p < hi ? a.cand_ids[p] : ~0ull;
-      const bool ok = id < a.n_rows;
-      float d = 0.0f;
-      if (ok) {
-        const float* x = (const float*)a.X + (size_t)id * a.ld;
-        d = canon_dist_lane_t<metric01, scale>(qs, x, scale ? a.inv_norm[id] : 1.0f, a.dims);
-      }
-      keys[tid] = among_key(d, (uint32_t)id, ok, paged, fl);
-    } else {
-      const int g = tid >> 2, sub = tid & 3;
-      const uint64_t p = p0 + (uint64_t)g;
-      const uint64_t id = p < hi ? a.cand_ids[p] : ~0ull;
-      const bool ok = id < a.n_rows;   // (the same in the four lanes of a group: they walk a row together)
-      float d = 0.0f;
-      if (ok) {
-        const float xs = scale ? a.inv_norm[id] : 1.0f;
-        if (LAYOUT == kLayoutF16) {
-          d = canon_dist(metric01, qs, (const __half*)a.X + (size_t)id * a.ld, xs, scale, a.dims, sub);
-        } else {
-          d = canon_dist_group_t<metric01, scale>(qs, (const float*)a.X + (size_t)id * a.ld, sub, a.dims, xs);
-        }
-      }
-      if (sub == 0) keys[g] = among_key(d, (uint32_t)id, ok, paged, fl);
-    }
+    const uint64_t p = p0 + (uint64_t)slot;
+    const uint64_t id = p < hi ? a.cand_ids[p] : ~0ull;
+    bool mine;
+    const float d = walk_row<LAYOUT, METRIC, true>(a.rows, qs, id, id < a.rows.n_rows, tid, &mine);
+    if (writer) keys[slot] = dist_key_paged(d, (uint32_t)id, mine, paged, fl);
     __syncthreads();
     if ((uint32_t)wave < kStep / 64u) best = keep_best64(best, keys[tid], lane);
     __syncthreads();
@@ -118,14 +81,14 @@ __global__ __launch_bounds__(256) void among_tile_kernel(const AmongArgs a) {
   static_assert(QT * R == 64 && QT == 8, "one (row, query) pair per 4-lane group; two queries per wave");
   extern __shared__ float4 among_lds[];
   __shared__ uint32_t row_id[R], row_ok[R];
-  const uint32_t lds = a.ld + kLdsPad;
+  const uint32_t lds = a.rows.ld + kLdsPad;
   float* qs = (float*)among_lds;                  // [QT][lds] the tile's prepared queries
   float* xs = qs + (size_t)QT * lds;              // [R][lds] this step's rows
   uint64_t* keys = (uint64_t*)(xs + (size_t)R * lds);   // [QT][64] this chunk's keys
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const uint32_t q0 = blockIdx.x * QT;
   const uint32_t nqt = a.nq - q0 < QT ? a.nq - q0 : QT;
-  const uint32_t ld4 = a.ld >> 2, lds4 = lds >> 2;
+  const uint32_t ld4 = a.rows.ld >> 2, lds4 = lds >> 2;
   for (uint32_t i = tid; i < QT * ld4; i += 256) {
     const uint32_t qi = i / ld4, c = i - qi * ld4;
     ((float4*)qs)[qi * lds4 + c] =
@@ -145,17 +108,17 @@ __global__ __launch_bounds__(256) void among_tile_kernel(const AmongArgs a) {
     for (uint32_t st = 0; st < 64u / R && c0 + st * R < a.n_cand; ++st) {
       const uint64_t p = c0 + st * R + sr;
       const uint64_t id = p < a.n_cand ? a.cand_ids[p] : ~0ull;
-      const bool ok = id < a.n_rows;
+      const bool ok = id < a.rows.n_rows;
       if (sl == 0) {
         row_id[sr] = (uint32_t)id;
         row_ok[sr] = ok ? 1u : 0u;
       }
       if (ok) {   // (a row that is not staged leaves stale floats behind: its pairs' keys are dropped)
-        const float inv = scale ? a.inv_norm[id] : 1.0f;
+        const float inv = scale ? a.rows.inv_norm[id] : 1.0f;
         float4* dst = (float4*)xs + sr * lds4;
         if (LAYOUT == kLayoutF16) {
-          const half8_t* x = (const half8_t*)((const _Float16*)a.X + (size_t)id * a.ld);
-          for (uint32_t c = sl; c < (a.dims + 7u) >> 3; c += 32) {
+          const half8_t* x = (const half8_t*)((const _Float16*)a.rows.X + (size_t)id * a.rows.ld);
+          for (uint32_t c = sl; c < (a.rows.dims + 7u) >> 3; c += 32) {
             const half8_t h = x[c];
             float4 v0 = make_float4((float)h[0], (float)h[1], (float)h[2], (float)h[3]);
             float4 v1 = make_float4((float)h[4], (float)h[5], (float)h[6], (float)h[7]);
@@ -168,8 +131,8 @@ __global__ __launch_bounds__(256) void among_tile_kernel(const AmongArgs a) {
           }
         } else if (LAYOUT == kLayoutPerm) {
           // a 16-float block of the search copy's order: four 16-byte loads, the 4 x 4 transpose undone (search_copy_pos)
-          const float4* x = (const float4*)((const float*)a.X + (size_t)id * a.ld);
-          for (uint32_t b = sl; b < (a.dims + 15u) >> 4; b += 32) {
+          const float4* x = (const float4*)((const float*)a.rows.X + (size_t)id * a.rows.ld);
+          for (uint32_t b = sl; b < (a.rows.dims + 15u) >> 4; b += 32) {
             float4 v0 = x[4 * b], v1 = x[4 * b + 1], v2 = x[4 * b + 2], v3 = x[4 * b + 3];
             if (scale) {
               v0 = scale_f4(v0, inv);
@@ -183,13 +146,13 @@ __global__ __launch_bounds__(256) void among_tile_kernel(const AmongArgs a) {
             dst[4 * b + 3] = make_float4(v0.w, v1.w, v2.w, v3.w);
           }
         } else {
-          const float4* x = (const float4*)((const float*)a.X + (size_t)id * a.ld);
-          for (uint32_t c = sl; c < (a.dims + 3u) >> 2; c += 32) dst[c] = scale ? scale_f4(x[c], inv) : x[c];
+          const float4* x = (const float4*)((const float*)a.rows.X + (size_t)id * a.rows.ld);
+          for (uint32_t c = sl; c < (a.rows.dims + 3u) >> 2; c += 32) dst[c] = scale ? scale_f4(x[c], inv) : x[c];
         }
       }
       __syncthreads();
-      const float d = canon_dist(metric01, qs + (size_t)pq * lds, xs + (size_t)pr * lds, 1.0f, false, a.dims, sub);
-      if (sub == 0) keys[pq * 64 + st * R + pr] = among_key(d, row_id[pr], row_ok[pr] != 0 && pq < nqt, paged, fl);
+      const float d = canon_dist(metric01, qs + (size_t)pq * lds, xs + (size_t)pr * lds, 1.0f, false, a.rows.dims, sub);
+      if (sub == 0) keys[pq * 64 + st * R + pr] = dist_key_paged(d, row_id[pr], row_ok[pr] != 0 && pq < nqt, paged, fl);
       __syncthreads();
     }
 #pragma unroll
@@ -204,8 +167,7 @@ __global__ __launch_bounds__(256) void among_tile_kernel(const AmongArgs a) {
 }
 
 // One wave per query: a page of results from the query's merged keys (ascending, exact canonical distances): columns
-// [out_offset, out_offset + k) of a row of out_stride entries; entries beyond the count are id ~0 / +Inf; the count of a
-// later page is added to the earlier pages'.
+// [out_offset, out_offset + k) of a row of out_stride entries (emit_page).
 __global__ __launch_bounds__(64) void among_emit_kernel(const uint64_t* __restrict__ merged, uint32_t k,
                                                         uint32_t out_stride, uint32_t out_offset,
                                                         uint64_t* __restrict__ out_ids, float* __restrict__ out_dist,
@@ -213,13 +175,8 @@ __global__ __launch_bounds__(64) void among_emit_kernel(const uint64_t* __restri
   const uint32_t lane = threadIdx.x, q = blockIdx.x;
   const uint64_t key = merged[(size_t)q * 64 + lane];
   const uint32_t nvalid = (uint32_t)__builtin_popcountll(__ballot(key != kKeyInf));
-  const uint32_t cnt = nvalid < k ? nvalid : k;
-  if (lane < k) {
-    const bool ok = lane < cnt;
-    out_ids[(size_t)q * out_stride + out_offset + lane] = ok ? (uint64_t)(uint32_t)key : ~0ull;
-    out_dist[(size_t)q * out_stride + out_offset + lane] = ok ? ordered_to_f32((uint32_t)(key >> 32)) : __builtin_inff();
-  }
-  if (lane == 0) out_count[q] = (out_offset ? out_count[q] : 0u) + cnt;
+  emit_page([&](uint32_t) { return key; }, nvalid, k, out_ids + (size_t)q * out_stride, out_dist + (size_t)q * out_stride,
+            out_count + q, out_offset, lane, 64);
 }
 
 namespace {
@@ -236,29 +193,28 @@ const AmongFn kTileFns[9] = EHX_AMONG_FNS(among_tile_kernel);   // [layout * 3 +
 const AmongFn kListFns[9] = EHX_AMONG_FNS(among_list_kernel);
 #undef EHX_AMONG_FNS
 DynLdsAttr g_tile_lds, g_list_lds;
-constexpr size_t kMaxLds = 160u * 1024u;   // LDS of one CU: the most one workgroup can have
 
-int among_layout(const AmongArgs& a) { return a.x_half ? kLayoutF16 : (a.x_perm ? kLayoutPerm : kLayoutF32); }
+int among_layout(const AmongArgs& a) { return row_layout(a.rows.x_half, a.rows.x_perm); }
 
 }  // namespace
 
-bool among_tiled(const AmongArgs& a) { return a.cand_off == nullptr && among_tile_lds(a.ld) <= kMaxLds; }
+bool among_tiled(const AmongArgs& a) { return a.cand_off == nullptr && among_tile_lds(a.rows.ld) <= kMaxLds; }
 
 uint32_t among_max_ld() { return (uint32_t)(kMaxLds / sizeof(float)); }   // among_list_kernel keeps one prepared query in LDS
 
 uint32_t among_step_rows(const AmongArgs& a) { return among_tiled(a) ? 64u : (among_layout(a) == kLayoutF32 ? 256u : 64u); }
 
 hipError_t launch_among(const AmongArgs& a, hipStream_t st) {
-  if (a.nq == 0 || a.n_blocks == 0 || a.n_blocks > 65535u || (a.ld & 31u) || a.metric < 0 || a.metric > 2)
+  if (a.nq == 0 || a.n_blocks == 0 || a.n_blocks > 65535u || (a.rows.ld & 31u) || a.rows.metric < 0 || a.rows.metric > 2)
     return hipErrorInvalidValue;
-  const int fn = among_layout(a) * 3 + a.metric;
+  const int fn = among_layout(a) * 3 + a.rows.metric;
   if (among_tiled(a)) {
-    const size_t lds = among_tile_lds(a.ld);
+    const size_t lds = among_tile_lds(a.rows.ld);
     hipError_t e = g_tile_lds.ensure(kTileFns, 9, lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kTileFns[fn], dim3((a.nq + kAmongTileQ - 1) / kAmongTileQ, a.n_blocks), dim3(256), lds, st, a);
   } else {
-    const size_t lds = (size_t)a.ld * sizeof(float);
+    const size_t lds = (size_t)a.rows.ld * sizeof(float);
     if (lds > kMaxLds) return hipErrorInvalidValue;
     hipError_t e = g_list_lds.ensure(kListFns, 9, lds);
     if (e != hipSuccess) return e;

@@ -20,30 +20,30 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void gather_rows_kernel(Gather
   const uint32_t q = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
   if (q >= a.n) return;
   const uint64_t g = a.row_ids[q];
-  float* __restrict__ out = a.out + (size_t)q * a.dims;
-  const bool ok = g < a.n_rows;
+  float* __restrict__ out = a.out + (size_t)q * a.rows.dims;
+  const bool ok = g < a.rows.n_rows;
   if (lane == 0) a.valid[q] = ok ? 1u : 0u;
   if (!ok) {
-    for (uint32_t c = lane; c < a.dims; c += 64) out[c] = 0.0f;
+    for (uint32_t c = lane; c < a.rows.dims; c += 64) out[c] = 0.0f;
     return;
   }
   const uint32_t g32 = (uint32_t)g, shard = a.G > 1 ? g32 % a.G : 0u, local = a.G > 1 ? g32 / a.G : g32;
   const char* __restrict__ base = (const char*)a.bases.p[shard];
-  const bool vec = (a.dims & 3u) == 0;
-  if (a.x_half) {
-    const _Float16* __restrict__ x = (const _Float16*)base + (size_t)local * a.ld;
-    const uint32_t n8 = vec ? a.dims >> 3 : 0;
+  const bool vec = (a.rows.dims & 3u) == 0;
+  if (a.rows.x_half) {
+    const _Float16* __restrict__ x = (const _Float16*)base + (size_t)local * a.rows.ld;
+    const uint32_t n8 = vec ? a.rows.dims >> 3 : 0;
     for (uint32_t c = lane; c < n8; c += 64) {
       const half8_t h = ((const half8_t*)x)[c];
       ((float4*)out)[2 * c] = make_float4((float)h[0], (float)h[1], (float)h[2], (float)h[3]);
       ((float4*)out)[2 * c + 1] = make_float4((float)h[4], (float)h[5], (float)h[6], (float)h[7]);
     }
-    for (uint32_t c = n8 * 8 + lane; c < a.dims; c += 64) out[c] = (float)x[c];
+    for (uint32_t c = n8 * 8 + lane; c < a.rows.dims; c += 64) out[c] = (float)x[c];
     return;
   }
-  const float* __restrict__ x = (const float*)base + (size_t)local * a.ld;
-  if (a.x_perm) {
-    const uint32_t n16 = vec ? a.dims >> 4 : 0;   // whole 16-float blocks: four 16-byte loads, a transpose, four stores
+  const float* __restrict__ x = (const float*)base + (size_t)local * a.rows.ld;
+  if (a.rows.x_perm) {
+    const uint32_t n16 = vec ? a.rows.dims >> 4 : 0;   // whole 16-float blocks: four 16-byte loads, a transpose, four stores
     for (uint32_t b = lane; b < n16; b += 64) {
       const float4* s = (const float4*)(x + (size_t)b * 16);
       const float4 v0 = s[0], v1 = s[1], v2 = s[2], v3 = s[3];
@@ -53,12 +53,12 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void gather_rows_kernel(Gather
       d[2] = make_float4(v0.z, v1.z, v2.z, v3.z);
       d[3] = make_float4(v0.w, v1.w, v2.w, v3.w);
     }
-    for (uint32_t c = n16 * 16 + lane; c < a.dims; c += 64) out[c] = x[search_copy_pos(c)];
+    for (uint32_t c = n16 * 16 + lane; c < a.rows.dims; c += 64) out[c] = x[search_copy_pos(c)];
     return;
   }
-  const uint32_t n4 = vec ? a.dims >> 2 : 0;
+  const uint32_t n4 = vec ? a.rows.dims >> 2 : 0;
   for (uint32_t c = lane; c < n4; c += 64) ((float4*)out)[c] = ((const float4*)x)[c];
-  for (uint32_t c = n4 * 4 + lane; c < a.dims; c += 64) out[c] = x[c];
+  for (uint32_t c = n4 * 4 + lane; c < a.rows.dims; c += 64) out[c] = x[c];
 }
 
 hipError_t launch_gather_rows(const GatherRowsArgs& a, hipStream_t st) {

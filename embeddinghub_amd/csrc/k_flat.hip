@@ -74,10 +74,7 @@ __global__ __launch_bounds__(64) void sample_select_kernel(const float* __restri
       const float sc = scores[(size_t)r * q_rows + q];
       if (sc == sc) key = ((uint64_t)f32_to_ordered(sc) << 32) | 0xFFFFFFFFull;
     }
-    key = wave_sort64(key, lane);
-    const uint64_t rv = __shfl(key, 63 - lane, 64);
-    const uint64_t m = best < rv ? best : rv;
-    best = wave_bitonic_merge64(m, lane);
+    best = keep_best64(best, key, lane);
   }
   if (lane == (int)kprime - 1) gthr[q] = best;
 }
@@ -114,29 +111,24 @@ hipError_t launch_flat_merge(const uint64_t* part, uint32_t nq, uint32_t n_chunk
 // (space_l2.h / space_ip.h; dispatch in L2Space / InnerProductSpace constructors), which is what
 // oracle/hnsw_oracle.hpp restates: 4 strided partial sums over the multiple-of-4 body (multiply
 // and add NOT fused), horizontal sum t0+t1+t2+t3 left to right, scalar tail added afterwards.
-// One 4-lane group per candidate; lane j of the group plays SSE lane j.
+// One 4-lane group per candidate; lane j of the group plays SSE lane j (walk_row, k_exact_common.h).
 // ---------------------------------------------------------------------------------------------
-template <typename XT>
+template <int LAYOUT>
 __global__ __launch_bounds__(256) void rerank_kernel(const RerankArgs a) {
   __shared__ uint64_t keys[64];
   __shared__ float approx[64];
   const int tid = threadIdx.x;
   const uint32_t q = blockIdx.x;
   const int g = tid >> 2, sub = tid & 3;
+  const uint32_t n = (uint32_t)a.rows.n_rows, dims = a.rows.dims, ld = a.rows.ld;
+  const int metric = a.rows.metric;
   const uint64_t mk = a.merged[(size_t)q * 64 + g];
   const uint32_t id = (uint32_t)mk;
-  const bool valid = (g < (int)a.kprime) && (mk != kKeyInf) && (id < a.n);
-  float d = __builtin_inff();
-  if (valid) {
-    const float* qv = a.Q + (size_t)q * a.ld;
-    const XT* xv = (const XT*)a.X + (size_t)id * a.ld;
-    const bool scale_x = a.metric == 2;
-    const float xs = scale_x ? a.inv_norm[id] : 1.0f;
-    d = canon_dist(a.metric == 0 ? 0 : 1, qv, xv, xs, scale_x, a.dims, sub);
-  }
+  const bool valid = (g < (int)a.kprime) && (mk != kKeyInf) && (id < n);
+  bool mine;
+  const float d = walk_row<LAYOUT, kMetricRt, false>(a.rows, a.Q + (size_t)q * ld, id, valid, tid, &mine);
   if (sub == 0) {
-    // (a NaN distance — a row or query holding NaN — is never a neighbour: the key is dropped)
-    keys[g] = (valid && d == d) ? (((uint64_t)f32_to_ordered(d) << 32) | id) : kKeyInf;
+    keys[g] = dist_key(d, id, valid);
     approx[g] = valid ? ordered_to_f32((uint32_t)(mk >> 32)) : __builtin_inff();
   }
   __syncthreads();
@@ -148,12 +140,8 @@ __global__ __launch_bounds__(256) void rerank_kernel(const RerankArgs a) {
     // results go to columns [out_offset, out_offset + k) of a row of out_stride entries (paged large-k
     // requests write one page per call; out_stride == 0: the plain [nq][k] layout)
     const size_t ostride = a.out_stride ? a.out_stride : a.k;
-    if (tid < (int)a.k) {
-      const bool ok = (uint32_t)tid < cnt;
-      a.out_ids[(size_t)q * ostride + a.out_offset + tid] = ok ? (uint64_t)(uint32_t)key : ~0ull;
-      a.out_dist[(size_t)q * ostride + a.out_offset + tid] = ok ? ordered_to_f32((uint32_t)(key >> 32)) : __builtin_inff();
-    }
-    if (tid == 0) a.out_count[q] = (a.out_offset ? a.out_count[q] : 0u) + cnt;
+    emit_page([&](uint32_t) { return key; }, nvalid, a.k, a.out_ids + (size_t)q * ostride, a.out_dist + (size_t)q * ostride,
+              a.out_count + q, a.out_offset, (uint32_t)tid, 64);
     // certification: every row that is NOT a candidate has approx score >= the worst candidate's
     // approx score A_last (for L2 the scan's score omits |q|^2, added back here).  If
     // A_last - margin > exact k-th distance, no outsider can beat the k-th result, so the top-k is
@@ -163,7 +151,7 @@ __global__ __launch_bounds__(256) void rerank_kernel(const RerankArgs a) {
     bool uncert = false;
     if (a.exact_keys) {
       // the keys are canonical distances of every row (exhaustive pass): nothing to certify
-    } else if (a.n > a.kprime && cnt == a.k && a.k > 0) {
+    } else if (n > a.kprime && cnt == a.k && a.k > 0) {
       float worst = -__builtin_inff();
       for (int j = 0; j < 64; ++j)
         if (approx[j] != __builtin_inff() && approx[j] > worst) worst = approx[j];
@@ -173,19 +161,19 @@ __global__ __launch_bounds__(256) void rerank_kernel(const RerankArgs a) {
         // (NaN u marks a query the filter could not bound: the comparison below fails)
         const float2 uv = a.quv[q];
         worst = __builtin_fmaf(uv.x, worst, uv.y);
-        qn = a.metric == 0 ? uv.y : (a.metric == 1 ? uv.x * uv.x : 1.0f);
+        qn = metric == 0 ? uv.y : (metric == 1 ? uv.x * uv.x : 1.0f);
       } else {
-        const float* qv = a.Q + (size_t)q * a.ld;
+        const float* qv = a.Q + (size_t)q * ld;
         qn = 0.0f;
-        for (uint32_t m = tid; m < a.dims; m += 64) qn += qv[m] * qv[m];
+        for (uint32_t m = tid; m < dims; m += 64) qn += qv[m] * qv[m];
         for (int o = 32; o > 0; o >>= 1) qn += __shfl_xor(qn, o, 64);
-        if (a.metric == 0) worst += qn;
+        if (metric == 0) worst += qn;
       }
       const float kth = ordered_to_f32((uint32_t)(__shfl(key, (int)a.k - 1, 64) >> 32));
-      const float margin = cert_margin(a.metric, a.dims, qn, a.max_sumsq ? *a.max_sumsq : __builtin_inff(),
+      const float margin = cert_margin(metric, dims, qn, a.max_sumsq ? *a.max_sumsq : __builtin_inff(),
                                        fmaxf(fabsf(kth), fabsf(worst)));
       uncert = !(worst - margin > kth);
-    } else if (a.n > a.kprime && cnt < a.k) {
+    } else if (n > a.kprime && cnt < a.k) {
       // candidates were lost (NaN keys, an overflowing filter bound): rows outside the list may still be neighbours,
       // so the next engine decides — the fp32 scan after a filter, the exhaustive pass after the fp32 scan
       uncert = true;
@@ -204,18 +192,16 @@ __global__ __launch_bounds__(256) void rerank_kernel(const RerankArgs a) {
 // (the whole shard per query) — the engine runs it for a handful of queries per batch at most.
 // Grid (n_blocks, n_queries); the keys are exact, so their merge + re-rank needs no certification.
 // ---------------------------------------------------------------------------------------------
-template <typename XT>
-__global__ __launch_bounds__(256) void exhaustive_kernel(const float* __restrict__ Q, const XT* __restrict__ X,
-                                                         const float* __restrict__ inv_norm, uint32_t n, uint32_t dims,
-                                                         uint32_t ld, int metric, uint32_t rows_per_block,
-                                                         const uint64_t* __restrict__ floor,
+template <int LAYOUT>
+__global__ __launch_bounds__(256) void exhaustive_kernel(const float* __restrict__ Q, const RowsView rows,
+                                                         uint32_t rows_per_block, const uint64_t* __restrict__ floor,
                                                          uint64_t* __restrict__ out) {
   __shared__ uint64_t keys[64];
   const int tid = threadIdx.x;
   const uint32_t b = blockIdx.x, j = blockIdx.y;
   const int g = tid >> 2, sub = tid & 3;
-  const float* qv = Q + (size_t)j * ld;
-  const bool scale_x = metric == 2;
+  const float* qv = Q + (size_t)j * rows.ld;
+  const uint32_t n = (uint32_t)rows.n_rows;
   const uint32_t r0 = b * rows_per_block;
   const uint32_t r1 = r0 + rows_per_block < n ? r0 + rows_per_block : n;
   // paging (k > 64): only keys strictly above the last key of the previous page count
@@ -224,23 +210,11 @@ __global__ __launch_bounds__(256) void exhaustive_kernel(const float* __restrict
   uint64_t best = kKeyInf;
   for (uint32_t base = r0; base < r1; base += 64) {
     const uint32_t id = base + (uint32_t)g;
-    float d = __builtin_inff();
-    if (id < r1) {
-      const float xs = scale_x ? inv_norm[id] : 1.0f;
-      d = canon_dist(metric == 0 ? 0 : 1, qv, X + (size_t)id * ld, xs, scale_x, dims, sub);
-    }
-    if (sub == 0) {
-      uint64_t key = (id < r1 && d == d) ? (((uint64_t)f32_to_ordered(d) << 32) | id) : kKeyInf;  // NaN: not a neighbour
-      if (paged && key <= fl) key = kKeyInf;
-      keys[g] = key;
-    }
+    bool mine;
+    const float d = walk_row<LAYOUT, kMetricRt, false>(rows, qv, id, id < r1, tid, &mine);
+    if (sub == 0) keys[g] = dist_key_paged(d, id, mine, paged, fl);
     __syncthreads();
-    if (tid < 64) {
-      const uint64_t key = wave_sort64(keys[tid], tid);
-      const uint64_t rv = __shfl(key, 63 - tid, 64);
-      const uint64_t m = best < rv ? best : rv;
-      best = wave_bitonic_merge64(m, tid);
-    }
+    if (tid < 64) best = keep_best64(best, keys[tid], tid);
     __syncthreads();
   }
   if (tid < 64) out[((size_t)j * gridDim.x + b) * 64 + tid] = best;
@@ -255,54 +229,46 @@ __global__ __launch_bounds__(256) void exhaustive_kernel(const float* __restrict
 // keys; the LAST workgroup to finish (a ticket) merges the lists and writes ids, distances and the count straight into
 // host-visible memory, then raises a flag the host is spinning on: no copy, no synchronisation call.
 // ---------------------------------------------------------------------------------------------
-template <typename XT>
+template <int LAYOUT>
 __global__ __launch_bounds__(256) void single_query_kernel(const SingleQueryArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem1[];
+  const uint32_t n = (uint32_t)a.rows.n_rows, dims = a.rows.dims, ld = a.rows.ld;
+  const int metric = a.rows.metric;
   float* qs = (float*)smem1;                       // [ld] prepared query
-  float* sq = qs + a.ld;                           // [ld] squares (cosine norm)
+  float* sq = qs + ld;                             // [ld] squares (cosine norm)
   __shared__ uint64_t keys[64];
   __shared__ uint64_t wbest[4][64];
   __shared__ uint32_t last_s;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const uint32_t b = blockIdx.x;
-  for (uint32_t i = tid; i < a.ld; i += 256) {
-    const float v = i < a.dims ? a.q_in[i] : 0.0f;
+  for (uint32_t i = tid; i < ld; i += 256) {
+    const float v = i < dims ? a.q_in[i] : 0.0f;
     qs[i] = v;
     sq[i] = ex_mul(v, v);
   }
   __syncthreads();
-  if (a.metric == 2) {
+  if (metric == 2) {
     if (tid == 0) {  // ONE sequential sum, hnswlib-python's order (prep_query_row's arithmetic)
-      const float sum = seq_sum_lds(sq, a.dims);
+      const float sum = seq_sum_lds(sq, dims);
       sq[0] = ex_div(1.0f, ex_add(ex_sqrt(sum), 1e-30f));
     }
     __syncthreads();
     const float inv = sq[0];
     __syncthreads();
-    for (uint32_t i = tid; i < a.dims; i += 256) qs[i] = ex_mul(qs[i], inv);
+    for (uint32_t i = tid; i < dims; i += 256) qs[i] = ex_mul(qs[i], inv);
     __syncthreads();
   }
-  const XT* X = (const XT*)a.X;
   const int g = tid >> 2, sub = tid & 3;
-  const bool scale_x = a.metric == 2;
   const uint32_t r0 = b * a.rows_per_block;
-  const uint32_t r1 = r0 + a.rows_per_block < a.n ? r0 + a.rows_per_block : a.n;
+  const uint32_t r1 = r0 + a.rows_per_block < n ? r0 + a.rows_per_block : n;
   uint64_t best = kKeyInf;
   for (uint32_t base = r0; base < r1; base += 64) {
     const uint32_t id = base + (uint32_t)g;
-    float d = __builtin_inff();
-    if (id < r1) {
-      const float xs = scale_x ? a.inv_norm[id] : 1.0f;
-      d = canon_dist(a.metric == 0 ? 0 : 1, qs, X + (size_t)id * a.ld, xs, scale_x, a.dims, sub);
-    }
-    if (sub == 0) keys[g] = (id < r1 && d == d) ? (((uint64_t)f32_to_ordered(d) << 32) | id) : kKeyInf;  // NaN: no neighbour
+    bool mine;
+    const float d = walk_row<LAYOUT, kMetricRt, false>(a.rows, qs, id, id < r1, tid, &mine);
+    if (sub == 0) keys[g] = dist_key(d, id, mine);
     __syncthreads();
-    if (tid < 64) {
-      const uint64_t key = wave_sort64(keys[tid], tid);
-      const uint64_t rv = __shfl(key, 63 - tid, 64);
-      const uint64_t m = best < rv ? best : rv;
-      best = wave_bitonic_merge64(m, tid);
-    }
+    if (tid < 64) best = keep_best64(best, keys[tid], tid);
     __syncthreads();
   }
   if (tid < 64) a.part[(size_t)b * 64 + tid] = best;
@@ -336,14 +302,8 @@ __global__ __launch_bounds__(256) void single_query_kernel(const SingleQueryArgs
       fin = wave_bitonic_merge64(m, lane);
     }
     const uint32_t nvalid = (uint32_t)__builtin_popcountll(__ballot(fin != kKeyInf));
-    const uint32_t cnt = nvalid < a.k ? nvalid : a.k;
-    if ((uint32_t)lane < a.k) {
-      const bool ok = (uint32_t)lane < cnt;
-      a.out_ids[lane] = ok ? (uint64_t)(uint32_t)fin : ~0ull;
-      a.out_dist[lane] = ok ? ordered_to_f32((uint32_t)(fin >> 32)) : __builtin_inff();
-    }
+    emit_page([&](uint32_t) { return fin; }, nvalid, a.k, a.out_ids, a.out_dist, a.out_count, 0, (uint32_t)lane, 64);
     if (lane == 0) {
-      a.out_count[0] = cnt;
       __hip_atomic_store(a.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next call
     }
     __threadfence_system();
@@ -353,12 +313,12 @@ __global__ __launch_bounds__(256) void single_query_kernel(const SingleQueryArgs
 }
 
 hipError_t launch_single_query(const SingleQueryArgs& a, uint32_t n_blocks, hipStream_t st) {
-  const size_t lds = (size_t)a.ld * 8;
+  const size_t lds = (size_t)a.rows.ld * 8;
   static DynLdsAttr attr;
-  const void* fns[2] = {(const void*)single_query_kernel<float>, (const void*)single_query_kernel<__half>};
+  const void* fns[2] = {(const void*)single_query_kernel<kLayoutF32>, (const void*)single_query_kernel<kLayoutF16>};
   if (hipError_t e = attr.ensure(fns, 2, lds + 4096); e != hipSuccess) return e;
-  if (a.x_half) hipLaunchKernelGGL(single_query_kernel<__half>, dim3(n_blocks), dim3(256), lds, st, a);
-  else hipLaunchKernelGGL(single_query_kernel<float>, dim3(n_blocks), dim3(256), lds, st, a);
+  if (a.rows.x_half) hipLaunchKernelGGL(single_query_kernel<kLayoutF16>, dim3(n_blocks), dim3(256), lds, st, a);
+  else hipLaunchKernelGGL(single_query_kernel<kLayoutF32>, dim3(n_blocks), dim3(256), lds, st, a);
   return hipGetLastError();
 }
 
@@ -374,22 +334,17 @@ hipError_t launch_set_floor(const uint64_t* merged, uint32_t nq, uint64_t* floor
   return hipGetLastError();
 }
 
-hipError_t launch_exhaustive(const float* Q, const void* X, int x_half, const float* inv_norm, uint32_t n, uint32_t dims,
-                             uint32_t ld, int metric, uint32_t rows_per_block, uint32_t n_blocks, uint32_t nq,
+hipError_t launch_exhaustive(const float* Q, const RowsView& rows, uint32_t rows_per_block, uint32_t n_blocks, uint32_t nq,
                              const uint64_t* floor, uint64_t* out, hipStream_t st) {
   const dim3 grid(n_blocks, nq);
-  if (x_half)
-    hipLaunchKernelGGL(exhaustive_kernel<__half>, grid, dim3(256), 0, st, Q, (const __half*)X, inv_norm, n, dims, ld,
-                       metric, rows_per_block, floor, out);
-  else
-    hipLaunchKernelGGL(exhaustive_kernel<float>, grid, dim3(256), 0, st, Q, (const float*)X, inv_norm, n, dims, ld,
-                       metric, rows_per_block, floor, out);
+  if (rows.x_half) hipLaunchKernelGGL(exhaustive_kernel<kLayoutF16>, grid, dim3(256), 0, st, Q, rows, rows_per_block, floor, out);
+  else hipLaunchKernelGGL(exhaustive_kernel<kLayoutF32>, grid, dim3(256), 0, st, Q, rows, rows_per_block, floor, out);
   return hipGetLastError();
 }
 
 hipError_t launch_rerank(const RerankArgs& a, hipStream_t st) {
-  if (a.x_half) hipLaunchKernelGGL(rerank_kernel<__half>, dim3(a.nq), dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(rerank_kernel<float>, dim3(a.nq), dim3(256), 0, st, a);
+  if (a.rows.x_half) hipLaunchKernelGGL(rerank_kernel<kLayoutF16>, dim3(a.nq), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(rerank_kernel<kLayoutF32>, dim3(a.nq), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 

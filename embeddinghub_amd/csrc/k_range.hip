@@ -6,8 +6,8 @@
 //   range_thr_kernel      int8 path: the caller's radius -> the int8 filter scan's score threshold (derivation below)
 //   range_rerank_kernel   int8 path: canonical distances of the scan's survivors, cut at the radius, sorted, emitted
 //   range_iota_kernel     0, 1, 2, ... (a graph space's overflow fall-back lists every row for launch_among)
-// Every distance comes from the canonical walkers of ehx_kernels.h (canon_dist, canon_dist_lane_t, canon_dist_group_t);
-// the row layouts and the on-the-fly cosine scaling are those of k_among.hip.
+// Every distance comes from the exact paths' one row walk (walk_row, k_exact_common.h), which also holds the row layouts,
+// the on-the-fly cosine scaling, the keys and the page writer.
 //
 // One counter serves as pool fill, overflow flag and total: a row inside the radius ALWAYS adds 1 to pool_cnt[q] and is
 // stored only while its slot is below kPoolCap, so pool_cnt[q] is the exact number of rows inside the radius whatever
@@ -42,8 +42,6 @@ namespace ehx {
 
 namespace {
 
-enum { kLayoutF32 = 0, kLayoutF16 = 1, kLayoutPerm = 2 };
-
 constexpr uint32_t kEmitThreads = 256;
 
 // ascending bitonic sort of keys[0, m) in LDS, m a power of two >= 2, by the whole workgroup
@@ -74,25 +72,19 @@ __device__ __forceinline__ void sort_and_emit(uint64_t* keys, uint32_t n, uint32
   for (uint32_t i = n + tid; i < m; i += kEmitThreads) keys[i] = kKeyInf;
   __syncthreads();
   block_sort_lds(keys, m, tid);
-  const uint32_t cnt = kept < max_results ? kept : max_results;
-  for (uint32_t i = tid; i < max_results; i += kEmitThreads) {
-    const bool ok = i < cnt;
-    const uint64_t key = ok ? keys[i] : kKeyInf;
-    out_ids[(size_t)q * max_results + i] = ok ? (uint64_t)(uint32_t)key : ~0ull;
-    out_dist[(size_t)q * max_results + i] = ok ? ordered_to_f32((uint32_t)(key >> 32)) : __builtin_inff();
-  }
-  if (tid == 0) out_count[q] = cnt;
+  emit_page([&](uint32_t i) { return keys[i]; }, kept, max_results, out_ids + (size_t)q * max_results,
+            out_dist + (size_t)q * max_results, out_count + q, 0, tid, kEmitThreads);
 }
 
 }  // namespace
 
 // Grid (query slots, blocks): slot j answers query sel[j] (sel == nullptr: j); block b walks steps b, b + gridDim.y, ...
-// of the rows [0, n_rows), a step being 256 rows (fp32 rows: one lane per row, canon_dist_lane_t, 16-byte loads) or 64 rows
-// (binary16 rows: canon_dist; block-permuted rows: canon_dist_group_t; a 4-lane group per row).  The prepared query sits in
-// LDS (permuted like the rows for the block-permuted layout).  A wave reserves the slots of its members with one atomic.
+// of the rows [0, n_rows), a step being 256 rows (fp32 rows: one lane per row) or 64 rows (binary16 and block-permuted rows: a
+// 4-lane group per row) of walk_row.  The prepared query sits in LDS (permuted like the rows for the block-permuted layout).
+// A wave reserves the slots of its members with one atomic.
 template <int LAYOUT, int METRIC>
 __global__ __launch_bounds__(256) void range_exact_kernel(const RangeArgs a) {
-  constexpr uint32_t kStep = LAYOUT == kLayoutF32 ? 256u : 64u;
+  constexpr uint32_t kStep = walk_rows<LAYOUT, true>(256);
   extern __shared__ float4 range_lds[];
   float* qs = (float*)range_lds;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -100,37 +92,14 @@ __global__ __launch_bounds__(256) void range_exact_kernel(const RangeArgs a) {
   const uint32_t q = a.sel ? a.sel[j] : j;
   const float r = a.radius[q];
   if (!(r == r)) return;   // a NaN radius has no members (the same in every lane: the whole workgroup leaves)
-  const float* qv = a.Q + (size_t)q * a.ld;
-  for (uint32_t m = tid; m < a.ld; m += 256) qs[LAYOUT == kLayoutPerm ? search_copy_pos(m) : m] = qv[m];
+  stage_query_lds<LAYOUT>(qs, a.Q + (size_t)q * a.rows.ld, a.rows.ld, tid, 256);
   __syncthreads();
-  constexpr bool scale = METRIC == 2;
-  constexpr int metric01 = METRIC == 0 ? 0 : 1;
   uint64_t* pool = a.pool + (size_t)j * kPoolCap;
-  for (uint64_t p0 = (uint64_t)blockIdx.y * kStep; p0 < a.n_rows; p0 += (uint64_t)gridDim.y * kStep) {
-    uint64_t id;
-    bool mine;   // this lane reports the row's result
-    float d = 0.0f;
-    if (LAYOUT == kLayoutF32) {
-      id = p0 + (uint64_t)tid;
-      mine = id < a.n_rows;
-      if (mine) {
-        const float* x = (const float*)a.X + (size_t)id * a.ld;
-        d = canon_dist_lane_t<metric01, scale>(qs, x, scale ? a.inv_norm[id] : 1.0f, a.dims);
-      }
-    } else {
-      const int sub = tid & 3;
-      id = p0 + (uint64_t)(tid >> 2);
-      const bool ok = id < a.n_rows;   // (the same in the four lanes of a group: they walk a row together)
-      if (ok) {
-        const float xs = scale ? a.inv_norm[id] : 1.0f;
-        if (LAYOUT == kLayoutF16) {
-          d = canon_dist(metric01, qs, (const __half*)a.X + (size_t)id * a.ld, xs, scale, a.dims, sub);
-        } else {
-          d = canon_dist_group_t<metric01, scale>(qs, (const float*)a.X + (size_t)id * a.ld, sub, a.dims, xs);
-        }
-      }
-      mine = ok && sub == 0;
-    }
+  const uint32_t slot0 = walk_slot<LAYOUT, true>(tid);
+  for (uint64_t p0 = (uint64_t)blockIdx.y * kStep; p0 < a.rows.n_rows; p0 += (uint64_t)gridDim.y * kStep) {
+    const uint64_t id = p0 + (uint64_t)slot0;
+    bool mine;
+    const float d = walk_row<LAYOUT, METRIC, true>(a.rows, qs, id, id < a.rows.n_rows, tid, &mine);
     const bool in = mine && d <= r;   // (a NaN distance compares false: never a member)
     const unsigned long long mask = __ballot(in);
     if (mask) {
@@ -139,7 +108,7 @@ __global__ __launch_bounds__(256) void range_exact_kernel(const RangeArgs a) {
       if (lane == (int)__builtin_ctzll(mask)) base = atomicAdd(&a.pool_cnt[j], n_in);
       base = (uint32_t)__shfl((int)base, (int)__builtin_ctzll(mask), 64);
       const uint32_t slot = base + (uint32_t)__builtin_popcountll(mask & ((1ull << lane) - 1ull));
-      if (in && slot < kPoolCap) pool[slot] = ((uint64_t)f32_to_ordered(d) << 32) | (uint32_t)id;
+      if (in && slot < kPoolCap) pool[slot] = dist_key(d, (uint32_t)id, true);
     }
   }
 }
@@ -194,58 +163,35 @@ __global__ __launch_bounds__(256) void range_thr_kernel(const float* __restrict_
 }
 
 // One workgroup per query: the survivors of the int8 scan — pool keys (S_lower, id), unsorted, each row at most once —
-// get their canonical distances from the stored rows (fp32: one lane per row, 16-byte loads through canon_dist_lane_t's
-// register ring; binary16: a 4-lane group per row, canon_dist widens the halves exactly), those above the radius are
-// dropped, the rest sorted by (distance, id) and emitted; kept[q] = how many stayed = the exact total (every member is in
+// get their canonical distances from the stored rows (walk_row; fp32: one lane per row, binary16: a 4-lane group per
+// row), those above the radius are dropped, the rest sorted by (distance, id) and emitted; kept[q] = how many stayed = the exact total (every member is in
 // the pool: header).  A query that is flagged (pool overflow, or marked by range_thr_kernel) writes nothing here.
 template <bool HALFX, int METRIC>
 __global__ __launch_bounds__(kEmitThreads) void range_rerank_kernel(const RangeRerankArgs a) {
   extern __shared__ float4 range_lds[];
   uint64_t* keys = (uint64_t*)range_lds;              // [kPoolCap]
   float* qs = (float*)(keys + kPoolCap);              // [ld]
-  uint32_t& kept_s = *(uint32_t*)(qs + a.ld);         // (dynamic too: the launch's size is the workgroup's whole LDS)
+  uint32_t& kept_s = *(uint32_t*)(qs + a.rows.ld);         // (dynamic too: the launch's size is the workgroup's whole LDS)
   const uint32_t tid = threadIdx.x, q = blockIdx.x;
   const int lane = (int)(tid & 63u);
   if (a.ovf[q]) return;
   const uint32_t cnt = a.pool_cnt[q] < kPoolCap ? a.pool_cnt[q] : kPoolCap;
   const float r = a.radius[q];
-  const float* qv = a.Q + (size_t)q * a.ld;
-  for (uint32_t m = tid; m < a.ld; m += kEmitThreads) qs[m] = qv[m];
+  constexpr int LAYOUT = HALFX ? kLayoutF16 : kLayoutF32;
+  stage_query_lds<LAYOUT>(qs, a.Q + (size_t)q * a.rows.ld, a.rows.ld, tid, kEmitThreads);
   if (tid == 0) kept_s = 0;
   __syncthreads();
-  constexpr bool scale = METRIC == 2;
-  constexpr int metric01 = METRIC == 0 ? 0 : 1;
   const uint64_t* pq = a.pool + (size_t)q * kPoolCap;
+  const bool writer = walk_by_lane<LAYOUT, true>() || (tid & 3u) == 0;   // this lane files its slot's key
   uint32_t kept = 0;
-  if (!HALFX) {
-    for (uint32_t i0 = 0; i0 < cnt; i0 += kEmitThreads) {
-      const uint32_t i = i0 + tid;
-      const uint32_t id = i < cnt ? (uint32_t)pq[i] : ~0u;
-      bool in = false;
-      float d = 0.0f;
-      if (id < a.n_rows) {
-        const float* x = (const float*)a.X + (size_t)id * a.ld;
-        d = canon_dist_lane_t<metric01, scale>(qs, x, scale ? a.inv_norm[id] : 1.0f, a.dims);
-        in = d <= r;
-      }
-      if (i < cnt) keys[i] = in ? (((uint64_t)f32_to_ordered(d) << 32) | id) : kKeyInf;
-      kept += (uint32_t)__builtin_popcountll(__ballot(in));
-    }
-  } else {
-    const int sub = (int)(tid & 3u);
-    for (uint32_t i0 = 0; i0 < cnt; i0 += kEmitThreads / 4) {
-      const uint32_t i = i0 + (tid >> 2);
-      const uint32_t id = i < cnt ? (uint32_t)pq[i] : ~0u;   // (the same in the four lanes of a group)
-      bool in = false;
-      float d = 0.0f;
-      if (id < a.n_rows) {
-        d = canon_dist(metric01, qs, (const __half*)a.X + (size_t)id * a.ld, scale ? a.inv_norm[id] : 1.0f, scale, a.dims,
-                       sub);
-        in = sub == 0 && d <= r;
-      }
-      if (i < cnt && sub == 0) keys[i] = in ? (((uint64_t)f32_to_ordered(d) << 32) | id) : kKeyInf;
-      kept += (uint32_t)__builtin_popcountll(__ballot(in));
-    }
+  for (uint32_t i0 = 0; i0 < cnt; i0 += walk_rows<LAYOUT, true>(kEmitThreads)) {
+    const uint32_t i = i0 + walk_slot<LAYOUT, true>(tid);
+    const uint32_t id = i < cnt ? (uint32_t)pq[i] : ~0u;   // (the same in the four lanes of a group)
+    bool mine;
+    const float d = walk_row<LAYOUT, METRIC, true>(a.rows, qs, id, id < a.rows.n_rows, tid, &mine);
+    const bool in = mine && d <= r;
+    if (i < cnt && writer) keys[i] = dist_key(d, id, in);
+    kept += (uint32_t)__builtin_popcountll(__ballot(in));
   }
   if (lane == 0 && kept) atomicAdd(&kept_s, kept);
   __syncthreads();
@@ -274,22 +220,21 @@ const RerankFn kRerankFns[6] = {   // [half * 3 + metric]
     range_rerank_kernel<false, 0>, range_rerank_kernel<false, 1>, range_rerank_kernel<false, 2>,
     range_rerank_kernel<true, 0>,  range_rerank_kernel<true, 1>,  range_rerank_kernel<true, 2>};
 DynLdsAttr g_exact_lds, g_rerank_lds;
-constexpr size_t kMaxLds = 160u * 1024u;   // LDS of one CU: the most one workgroup can have
 
 }  // namespace
 
-uint32_t range_step_rows(const RangeArgs& a) { return (a.x_half || a.x_perm) ? 64u : 256u; }
+uint32_t range_step_rows(const RangeArgs& a) { return row_layout(a.rows.x_half, a.rows.x_perm) == kLayoutF32 ? 256u : 64u; }
 
 uint32_t range_rerank_max_ld() { return (uint32_t)((kMaxLds - kPoolCap * sizeof(uint64_t) - 16u) / sizeof(float)) & ~31u; }
 
 hipError_t launch_range_exact(const RangeArgs& a, uint32_t n_slots, hipStream_t st) {
-  if (n_slots == 0 || a.n_rows == 0) return hipSuccess;
-  if (a.n_blocks == 0 || a.n_blocks > 65535u || (a.ld & 31u) || a.metric < 0 || a.metric > 2) return hipErrorInvalidValue;
-  const size_t lds = (size_t)a.ld * sizeof(float);
+  if (n_slots == 0 || a.rows.n_rows == 0) return hipSuccess;
+  if (a.n_blocks == 0 || a.n_blocks > 65535u || (a.rows.ld & 31u) || a.rows.metric < 0 || a.rows.metric > 2) return hipErrorInvalidValue;
+  const size_t lds = (size_t)a.rows.ld * sizeof(float);
   if (lds > kMaxLds) return hipErrorInvalidValue;
   hipError_t e = g_exact_lds.ensure(kExactFns, 9, lds);
   if (e != hipSuccess) return e;
-  const int fn = (a.x_half ? kLayoutF16 : (a.x_perm ? kLayoutPerm : kLayoutF32)) * 3 + a.metric;
+  const int fn = row_layout(a.rows.x_half, a.rows.x_perm) * 3 + a.rows.metric;
   hipLaunchKernelGGL(kExactFns[fn], dim3(n_slots, a.n_blocks), dim3(256), lds, st, a);
   return hipGetLastError();
 }
@@ -314,12 +259,12 @@ hipError_t launch_range_thr(const float* radius, const float2* quv, const float*
 
 hipError_t launch_range_rerank(const RangeRerankArgs& a, hipStream_t st) {
   if (a.nq == 0) return hipSuccess;
-  if (a.max_results == 0 || (a.ld & 3u) || a.ld > range_rerank_max_ld() || a.metric < 0 || a.metric > 2)
+  if (a.max_results == 0 || (a.rows.ld & 3u) || a.rows.ld > range_rerank_max_ld() || a.rows.metric < 0 || a.rows.metric > 2)
     return hipErrorInvalidValue;
-  const size_t lds = kPoolCap * sizeof(uint64_t) + (size_t)a.ld * sizeof(float) + 16u;
+  const size_t lds = kPoolCap * sizeof(uint64_t) + (size_t)a.rows.ld * sizeof(float) + 16u;
   hipError_t e = g_rerank_lds.ensure(kRerankFns, 6, lds);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kRerankFns[(a.x_half ? 3 : 0) + a.metric], dim3(a.nq), dim3(kEmitThreads), lds, st, a);
+  hipLaunchKernelGGL(kRerankFns[(a.rows.x_half ? 3 : 0) + a.rows.metric], dim3(a.nq), dim3(kEmitThreads), lds, st, a);
   return hipGetLastError();
 }
 
