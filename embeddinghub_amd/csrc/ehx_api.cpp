@@ -670,11 +670,10 @@ int ehx_stats(ehx_space* s, ehx_stats_t* out) {
     // n_dist*d*4 + n_hops0*(4+4*2M) + n_hops_up*(4+4*M)
     out->bytes_algorithmic += g[0] * s->dims * 4ull + g[1] * (4ull + 8ull * s->params.M) + g[2] * (4ull + 4ull * s->params.M);
   }
-  if (s->scr.dUncert.p) {
-    unsigned long long u[2] = {0, 0};
-    HIP_TRY(hipMemcpy(u, s->scr.dUncert.p, sizeof(u), hipMemcpyDeviceToHost));
-    (void)u[0];
-    if (u[1]) return fail(EHX_EINTERNAL, "scan kernel tripped its bounded-retry guard %llu times", u[1]);
+  if (s->scr.dScanErr.p) {
+    uint32_t err = 0;
+    HIP_TRY(hipMemcpy(&err, s->scr.dScanErr.p, sizeof(err), hipMemcpyDeviceToHost));
+    if (err) return fail(EHX_EINTERNAL, "scan kernel tripped its bounded-retry guard %u times", err);
   }
   {
     // scan times: the space's own clock (graph, fp16 / fp32 engines, exhaustive pass) and the int8 scratch sets' clocks;
@@ -750,7 +749,7 @@ int ehx_stats_reset(ehx_space* s) {
     std::lock_guard<std::mutex> cl(c.mu);
     c.clock.reset();
   }
-  if (s->scr.dUncert.p) HIP_TRY(hipMemset(s->scr.dUncert.p, 0, 2 * sizeof(unsigned long long)));
+  if (s->scr.dScanErr.p) HIP_TRY(hipMemset(s->scr.dScanErr.p, 0, sizeof(uint32_t)));
   if (s->graph.dGraphCounters.p) HIP_TRY(hipMemset(s->graph.dGraphCounters.p, 0, kGraphCounters * sizeof(unsigned long long)));
   return EHX_OK;
 }

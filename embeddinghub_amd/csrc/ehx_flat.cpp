@@ -23,12 +23,38 @@ ScanPlan plan_scan(uint32_t nq, uint32_t n_tiles, uint32_t k, int n_cus) {
   return p;
 }
 
+std::vector<ScanPass> plan_cascade(uint32_t nq, uint32_t n_tiles, uint32_t k, int n_cus, uint64_t first_tiles, uint64_t growth) {
+  std::vector<ScanPass> passes;
+  uint64_t done = 0;
+  for (uint64_t cum = first_tiles; cum * 2 < n_tiles; cum *= growth) {
+    passes.push_back({(uint32_t)done, plan_scan(nq, (uint32_t)(cum - done), k, n_cus)});
+    done = cum;
+  }
+  passes.push_back({(uint32_t)done, plan_scan(nq, (uint32_t)(n_tiles - done), k, n_cus)});
+  return passes;
+}
+
+// what the fp32 and the fp16 scan's arguments share: the candidate slots and list slots of the batch, its error word and
+// thresholds (every pass writes its lists from slot 0)
+template <class Args>
+static void scan_args_shared(Args& a, ehx_space* s, const ScanPlan& p, uint32_t lists_total, uint64_t n_pub) {
+  a.cand = s->scr.dCand.p;
+  a.part = s->scr.dPart.p;
+  a.n = (uint32_t)n_pub;
+  a.q_tiles = p.q_tiles;
+  a.kprime = p.kprime;
+  a.list0 = 0;
+  a.lists_total = lists_total;
+  a.err = s->scr.dScanErr.p;
+  a.gthr = (unsigned long long*)s->scr.dGthr.p;
+}
+
 // one flat pipeline: prepared queries -> scan -> merge -> canonical re-rank.
 //   f16 = false: the fp32 MFMA scan (k_flat8.hip), exact on its own.
 //   f16 = true : the fp16 MFMA filter scan (k_flat16.hip); per-query certification flags land in
-//                s->scr.dUflags and the caller re-runs the unflagged remainder through the fp32 scan.
-int flat_pass(ehx_space* s, uint64_t n_pub, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, uint64_t* d_ids,
-              float* d_dist, uint32_t* d_count, bool f16, bool count_stats) {
+//                s->scr.verdict and the caller re-runs the flagged remainder through the fp32 scan.
+static int flat_pass(ehx_space* s, uint64_t n_pub, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, uint64_t* d_ids,
+                     float* d_dist, uint32_t* d_count, bool f16) {
   Engine& E = engine();
   // A cascade of scan passes over growing row ranges (one tile per workgroup, then x8 per pass): after
   // every pass the per-workgroup candidate lists are merged into the query's running best-64 and its
@@ -38,39 +64,19 @@ int flat_pass(ehx_space* s, uint64_t n_pub, hipStream_t st, size_t nq, const flo
   // thresholds up from +inf (~k' ln(rows/k') appends per list).
   const uint32_t tile_rows = f16 ? kTileRows16 : kTileRows;
   const uint32_t n_tiles = (uint32_t)((n_pub + tile_rows - 1) / tile_rows);
-  const uint32_t lpc = f16 ? 2u : scan_lists_per_chunk();
-  struct Pass {
-    uint32_t tile0;
-    ScanPlan plan;
-  };
+  constexpr uint32_t lpc = kScanListsPerChunk;
   // Filter scan: a SAMPLE pass first — the first 8 tiles (2048 rows) are scanned in dump mode (all scores to
   // HBM, no candidate lists) and sample_select turns them into the k'-th best score per query, so not even
   // the first real pass has to warm its lists up from +inf (which costs ~3 list compactions per list).
   constexpr uint32_t kSampleTiles = 8;
   const bool sample = f16 && n_tiles >= 256;
-  std::vector<Pass> passes;
-  {
-    const ScanPlan whole = plan_scan((uint32_t)nq, n_tiles, k, E.n_cus);
-    uint32_t done = 0;
-    if (sample) {
-      // the filter scan gets its first thresholds from the sample pass below, so its cascade can start
-      // wide (128 tiles) and grow x16: three scan launches at 10 M rows
-      uint32_t cum = 128;
-      while (cum * 2 < n_tiles) {
-        passes.push_back({done, plan_scan((uint32_t)nq, cum - done, k, E.n_cus)});
-        done = cum;
-        cum *= 16;
-      }
-    } else if (lpc == 2 && n_tiles >= 16 * whole.n_chunks) {
-      uint32_t cum = whole.n_chunks;  // pass 0: one tile per workgroup
-      while (cum * 2 < n_tiles) {
-        passes.push_back({done, plan_scan((uint32_t)nq, cum - done, k, E.n_cus)});
-        done = cum;
-        cum *= 8;
-      }
-    }
-    passes.push_back({done, plan_scan((uint32_t)nq, n_tiles - done, k, E.n_cus)});
-  }
+  // the filter scan gets its first thresholds from the sample pass below, so its cascade can start wide (128 tiles) and
+  // grow x16: three scan launches at 10 M rows; without one, pass 0 is one tile per workgroup and the passes grow x8, on
+  // spaces of at least 16 such passes; everything smaller is one pass
+  const uint32_t whole_chunks = plan_scan((uint32_t)nq, n_tiles, k, E.n_cus).n_chunks;
+  const bool x8 = !sample && n_tiles >= 16 * whole_chunks;
+  std::vector<ScanPass> passes =
+      plan_cascade((uint32_t)nq, n_tiles, k, E.n_cus, sample ? 128 : x8 ? whole_chunks : n_tiles, sample ? 16 : 8);
   ScanPlan p = passes.back().plan;  // (q_tiles, q_rows, kprime are the same for every pass)
   test_pause();
   if (f16) {
@@ -100,9 +106,8 @@ int flat_pass(ehx_space* s, uint64_t n_pub, hipStream_t st, size_t nq, const flo
   if ((rc = s->scr.dPart.ensure((size_t)p.q_rows * lists_total * p.kprime))) return rc;
   if ((rc = s->scr.dMerged.ensure((size_t)p.q_rows * 64))) return rc;
   if ((rc = s->scr.dGthr.ensure((size_t)p.q_rows + 8))) return rc;  // +8: instrumentation slots of profiling builds
-  if ((rc = s->scr.dUncert.ensure_zeroed_once(2))) return rc;  // [0] uncertified, [1] scan error
-  if ((rc = s->scr.dUflags.ensure(p.q_rows))) return rc;
-  if ((rc = s->scr.dUncert16.ensure_zeroed_once(1))) return rc;
+  if ((rc = s->scr.dScanErr.ensure_zeroed_once(1))) return rc;
+  if ((rc = s->scr.verdict.ensure(p.q_rows))) return rc;
   if (f16) {
     if ((rc = s->scr.dQ16.ensure(scanq16_halves(p.q_rows, s->ld16)))) return rc;
     if ((rc = s->scr.dQgamma.ensure(p.q_rows))) return rc;
@@ -126,71 +131,49 @@ int flat_pass(ehx_space* s, uint64_t n_pub, hipStream_t st, size_t nq, const flo
     HIP_TRY(hipMemsetAsync(s->scr.dMerged.p, 0xFF, (size_t)p.q_rows * 64 * sizeof(uint64_t), st));
     if ((rc = clock.scan_begin(st)) || (rc = clock.scan_end(st))) return rc;
   } else {
-    ScanArgs a;
-    a.Q = s->scr.dQ.p;
-    a.X = s->rows.dX.p;
-    a.x_half = (uint32_t)s->x_half;
-    a.rowp = s->rows.dRowp.p;
-    a.cand = s->scr.dCand.p;
-    a.part = s->scr.dPart.p;
-    a.n = (uint32_t)n_pub;
-    a.ld = s->ld;
-    a.q_tiles = p.q_tiles;
-    a.kprime = p.kprime;
-    a.lists_total = lists_total;
-    a.err = (uint32_t*)(s->scr.dUncert.p + 1);
-    a.gthr = (unsigned long long*)s->scr.dGthr.p;
-    ScanArgs16 h;
-    h.Q = s->scr.dQ16.p;
-    h.X = s->f16.dX16.p;
-    h.rowp = s->f16.dRowp16.p;
-    h.qgamma = s->scr.dQgamma.p;
-    h.eps = scan16_eps(s->dims);
-    h.cos = s->metric == EHX_METRIC_COSINE;
-    h.cand = a.cand;
-    h.part = a.part;
-    h.n = a.n;
-    h.ld = s->ld16;
-    h.q_tiles = a.q_tiles;
-    h.kprime = a.kprime;
-    h.lists_total = lists_total;
-    h.err = a.err;
-    h.gthr = a.gthr;
-    auto scan = [&](const ScanPlan& pl, uint32_t tile0, uint32_t list0) -> hipError_t {
-      if (f16) {
-        h.tile0 = tile0;
-        h.n_tiles = pl.n_tiles;
-        h.n_chunks = pl.n_chunks;
-        h.tiles_per_chunk = pl.tiles_per_chunk;
-        h.xcd_map = pl.xcd_map;
-        h.list0 = list0;
-        return launch_flat_scan16(h, st);
+    // the cascade's passes through the engine's kernel, each followed by its merge
+    auto cascade = [&](auto& a, auto launch) -> int {
+      for (size_t i = 0; i < passes.size(); ++i) {
+        const bool last = i + 1 == passes.size();
+        set_scan_pass(a, passes[i].plan, passes[i].tile0);
+        HIP_TRY(launch(a, st));
+        if (last && (rc = clock.scan_end(st))) return rc;   // (the final merge is outside the timed scan phase)
+        HIP_TRY(launch_flat_merge(s->scr.dPart.p, (uint32_t)nq, passes[i].plan.n_chunks * lpc, p.kprime, s->scr.dMerged.p, st,
+                                  lists_total, i > 0, last ? nullptr : (unsigned long long*)s->scr.dGthr.p));
       }
-      a.tile0 = tile0;
-      a.n_tiles = pl.n_tiles;
-      a.n_chunks = pl.n_chunks;
-      a.tiles_per_chunk = pl.tiles_per_chunk;
-      a.xcd_map = pl.xcd_map;
-      a.list0 = list0;
-      return launch_flat_scan(a, st);
+      return EHX_OK;
     };
     HIP_TRY(hipMemsetAsync(s->scr.dGthr.p, 0xFF, (size_t)p.q_rows * sizeof(uint64_t), st));
     if ((rc = clock.scan_begin(st))) return rc;
-    if (sample) {
-      ScanPlan sp = plan_scan((uint32_t)nq, kSampleTiles, k, E.n_cus);
-      sp.kprime = p.kprime;
-      h.dump = s->scr.dSample.p;
-      HIP_TRY(scan(sp, 0, 0));
-      h.dump = nullptr;
-      HIP_TRY(launch_sample_select(s->scr.dSample.p, kSampleTiles * kTileRows16, p.q_rows, (uint32_t)nq, p.kprime,
-                                   (unsigned long long*)s->scr.dGthr.p, st));
-    }
-    for (size_t i = 0; i < passes.size(); ++i) {
-      const bool last = i + 1 == passes.size();
-      HIP_TRY(scan(passes[i].plan, passes[i].tile0, 0));
-      if (last && (rc = clock.scan_end(st))) return rc;   // (the final merge is outside the timed scan phase)
-      HIP_TRY(launch_flat_merge(s->scr.dPart.p, (uint32_t)nq, passes[i].plan.n_chunks * lpc, p.kprime, s->scr.dMerged.p, st,
-                                lists_total, i > 0, last ? nullptr : (unsigned long long*)s->scr.dGthr.p));
+    if (f16) {
+      ScanArgs16 h;
+      scan_args_shared(h, s, p, lists_total, n_pub);
+      h.Q = s->scr.dQ16.p;
+      h.X = s->f16.dX16.p;
+      h.rowp = s->f16.dRowp16.p;
+      h.qgamma = s->scr.dQgamma.p;
+      h.eps = scan16_eps(s->dims);
+      h.cos = s->metric == EHX_METRIC_COSINE;
+      h.ld = s->ld16;
+      if (sample) {
+        ScanPlan sp = plan_scan((uint32_t)nq, kSampleTiles, k, E.n_cus);
+        set_scan_pass(h, sp, 0);
+        h.dump = s->scr.dSample.p;
+        HIP_TRY(launch_flat_scan16(h, st));
+        h.dump = nullptr;
+        HIP_TRY(launch_sample_select(s->scr.dSample.p, kSampleTiles * kTileRows16, p.q_rows, (uint32_t)nq, p.kprime,
+                                     (unsigned long long*)s->scr.dGthr.p, st));
+      }
+      if ((rc = cascade(h, launch_flat_scan16))) return rc;
+    } else {
+      ScanArgs a;
+      scan_args_shared(a, s, p, lists_total, n_pub);
+      a.Q = s->scr.dQ.p;
+      a.X = s->rows.dX.p;
+      a.x_half = (uint32_t)s->x_half;
+      a.rowp = s->rows.dRowp.p;
+      a.ld = s->ld;
+      if ((rc = cascade(a, launch_flat_scan8))) return rc;
     }
   }
   RerankArgs r;
@@ -200,16 +183,15 @@ int flat_pass(ehx_space* s, uint64_t n_pub, hipStream_t st, size_t nq, const flo
   r.out_ids = d_ids;
   r.out_dist = d_dist;
   r.out_count = d_count;
-  r.n_uncertified = s->scr.dUncert16.p;  // verdict counter of this pass (the caller reads and clears it)
+  r.n_uncertified = s->scr.verdict.count.p;  // (the caller reads and clears it)
   r.nq = (uint32_t)nq;
   r.k = k;
   r.kprime = p.kprime;
   if (f16) r.quv = s->scr.dQuv.p;
   r.max_sumsq = s->rows.dMaxSumsq.p;
-  r.uncert_flags = s->scr.dUflags.p;
+  r.uncert_flags = s->scr.verdict.flags.p;
   HIP_TRY(launch_rerank(r, st));
   if ((rc = clock.finish(st))) return rc;
-  if (count_stats) count_scan_batch(s, nq, n_pub, k, f16 ? 2 : s->esz);
   s->n_rerank += (uint64_t)nq * p.kprime;
   return EHX_OK;
 }
@@ -224,13 +206,48 @@ int resolve_engine(const ehx_space* s, uint64_t n_pub) {
   return EHX_ENGINE_F32;
 }
 
+// EHX_I8_COUNT / EHX_I8_DEBUG, diagnosis only: the scan's epilogue counters of this batch (builds with -DEHX_I8_COUNT=1) and
+// what its uncertified queries look like, on stderr.  Waits for the stream.
+static int i8_diagnose(ehx_space::I8Set::Buffers& b, hipStream_t st, size_t nq, uint32_t k, uint32_t width,
+                       const uint32_t* d_ovf, const float* d_dist) {
+  HIP_TRY(hipStreamSynchronize(st));
+  if (env().i8_count) {
+    unsigned long long c[8] = {0};
+    HIP_TRY(hipMemcpy(c, b.dCnt.p, sizeof(c), hipMemcpyDeviceToHost));
+    fprintf(stderr, "[i8 count] tests %llu alarms %llu row-block alarms %llu trips %llu (cumulative)\n", c[0], c[1], c[2], c[3]);
+  }
+  if (env().i8_debug) {
+    std::vector<uint32_t> fl(nq), ov(nq);
+    std::vector<float4> qp(nq);
+    std::vector<float2> uv(nq);
+    std::vector<uint64_t> mg(nq * width);
+    std::vector<float> od(nq * k);
+    HIP_TRY(hipMemcpy(fl.data(), b.verdict.flags.p, nq * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(ov.data(), d_ovf, nq * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(qp.data(), b.dQp8.p, nq * sizeof(float4), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(uv.data(), b.dQuv.p, nq * sizeof(float2), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(mg.data(), b.dMerged8.p, nq * width * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(od.data(), d_dist, nq * k * 4, hipMemcpyDeviceToHost));
+    int shown = 0;
+    for (size_t q = 0; q < nq && shown < 6; ++q) {
+      if (!fl[q]) continue;
+      ++shown;
+      auto S = [&](int i) { return mg[q * width + i] == ~0ull ? INFINITY : ordered_to_f32((uint32_t)(mg[q * width + i] >> 32)); };
+      fprintf(stderr, "[i8 debug] q=%zu ovf=%u tmin=%g S[0]=%g S[63]=%g S[127]=%g S[255]=%g kth_dist=%g u=%g v=%g\n", q, ov[q],
+              qp[q].w, S(0), S(63), S(127), S(255), od[q * k + k - 1], uv[q].x, uv[q].y);
+    }
+  }
+  return EHX_OK;
+}
+
 // The int8 filter pipeline (k_flati8.hip, k_select.hip): prepared queries -> sample pass (first thresholds) ->
 // cascade of collect passes, x4 in rows, each followed by select256 (running best 256 + the next threshold) ->
 // rerank256 (canonical distances of the k' = 128 best lower bounds, top-k, certificate).  Per-query verdicts land in
-// s->scr.dUflags / s->scr.dUncert16.p like those of flat_pass.
+// the set's own Verdict, like those of flat_pass in the space's.
 // `set`: which of the space's two scratch sets (ehx_space::I8Set) this batch runs in; the caller holds that set's mutex.
-int flat_pass8(ehx_space* s, uint64_t n_pub, int set, hipStream_t st, size_t nq, const float* d_queries, uint32_t k,
-               uint64_t* d_ids, float* d_dist, uint32_t* d_count, bool count_stats, uint32_t* kprime_used) {
+// *kprime_used: the logical length of the candidate list the batch ran with.
+static int flat_pass8(ehx_space* s, uint64_t n_pub, int set, hipStream_t st, size_t nq, const float* d_queries, uint32_t k,
+                      uint64_t* d_ids, float* d_dist, uint32_t* d_count, uint32_t* kprime_used) {
   Engine& E = engine();
   ehx_space::I8Set& sc = s->i8set[set];
   const uint32_t n_tiles = (uint32_t)((n_pub + kTileRows16 - 1) / kTileRows16);
@@ -262,7 +279,7 @@ int flat_pass8(ehx_space* s, uint64_t n_pub, int set, hipStream_t st, size_t nq,
   // The list is 256 keys wide to begin with.  Longer rows leave more survivors (the bound is ~0.02 in dot units whatever
   // the dimension, while the spread of the dot products shrinks like 1/sqrt(d)): at 12.5 M x 1536 a fifth of the
   // queries needed more than 256 candidates and went to the next engine, which doubled the batch time.  A space whose
-  // batches keep losing queries that way doubles its list (knn_device_locked), up to kMerged8Max.
+  // batches keep losing queries that way doubles its list (i8_adapt), up to kMerged8Max.
   const uint32_t width = s->i8_width.load(std::memory_order_relaxed);  // (read once: another batch may widen it meanwhile)
   const long kprime_env = env().i8_kprime;
   // How many candidates a query keeps is what the scan's epilogue pays for (every key collected is a trip through its
@@ -272,7 +289,7 @@ int flat_pass8(ehx_space* s, uint64_t n_pub, int set, hipStream_t st, size_t nq,
   // else the full width (64 was tried: no query lost at 1 - 1.25 M x 768 in 50 batches, 3 of 256 at 100 k x 768); rows
   // of 1024 dims and more always get the full width (the bound is ~1.3e-2 in dot units whatever d while the scores'
   // spread shrinks like 1/sqrt(d): 18 000 x 2048 needs its 256) — and, like the width, doubles when queries lose their
-  // certificate because the list was too short (knn_device_locked).
+  // certificate because the list was too short (i8_adapt).
   // Short rows need fewer still: the bound is a smaller share of the scores' spread (0.15 sigma at d = 128 against 0.36
   // at d = 768), and on short rows the hit path is what a tile's time is made of (two stages of matrix work per tile at
   // d = 128).  Measured, 46 000 queries each, 0 fallbacks (profiles/r04_p_kprime_short_rows.jsonl): 6.25 M x 128 k' 256 /
@@ -285,25 +302,12 @@ int flat_pass8(ehx_space* s, uint64_t n_pub, int set, hipStream_t st, size_t nq,
   const uint32_t kp_want = std::max(kp_auto, s->i8_kprime_min.load(std::memory_order_relaxed));
   const uint32_t kprime = kprime_env >= 64 ? (uint32_t)std::min<long>(kprime_env, (long)width) : std::min(kp_want, width);
   s->i8_kprime_last.store(kprime, std::memory_order_relaxed);
-  if (kprime_used) *kprime_used = kprime;
-  struct Pass {
-    uint32_t tile0;
-    ScanPlan plan;
-  };
+  *kprime_used = kprime;
   // First pass: up to 512 tiles (131 072 rows) under a threshold taken from the sample at a LOW rank, chosen so that
   // the pass collects ~1000 keys per query (any threshold is sound, see sample_select256_kernel); then x4 in rows per
   // pass under the 256th best so far.
   const uint32_t kFirstTiles = env().i8_first_tiles ? env().i8_first_tiles : (big ? 128u : 512u);
-  std::vector<Pass> passes;
-  {
-    uint32_t done = 0, cum = kFirstTiles;
-    while ((uint64_t)cum * 2 < n_tiles) {
-      passes.push_back({done, plan_scan((uint32_t)nq, cum - done, k, E.n_cus)});
-      done = cum;
-      cum *= growth;
-    }
-    passes.push_back({done, plan_scan((uint32_t)nq, n_tiles - done, k, E.n_cus)});
-  }
+  const std::vector<ScanPass> passes = plan_cascade((uint32_t)nq, n_tiles, k, E.n_cus, kFirstTiles, growth);
   // rank of the threshold the select after pass i publishes for pass i + 1: the kprime-th best is always valid; while
   // only a share f of the rows has been seen, the final kprime-th best is expected near rank kprime * f of the prefix, so
   // rank kprime * f * safety (>= 16) is a much tighter threshold that is still above it — fewer keys collected, fewer
@@ -339,20 +343,17 @@ int flat_pass8(ehx_space* s, uint64_t n_pub, int set, hipStream_t st, size_t nq,
   if ((rc = i8_scan_args(s, sc.buf, p, n_pub, &a))) return rc;
   if ((rc = sc.buf.dSample8.ensure((size_t)kSampleTiles * kTileRows16 * p.q_rows))) return rc;
   if ((rc = sc.buf.dMerged8.ensure((size_t)p.q_rows * width))) return rc;
-  if ((rc = sc.buf.dUflags.ensure(p.q_rows))) return rc;
-  if ((rc = sc.buf.dUncert.ensure_zeroed_once(1))) return rc;
-  if ((rc = sc.buf.hUncertPin.ensure(1))) return rc;
+  if ((rc = sc.buf.verdict.ensure(p.q_rows))) return rc;
   uint32_t* const pool_cnt = a.pool_cnt;
   uint32_t* const ovf = a.ovf;
   uint32_t* sync = sc.buf.dI8Ctl.p + 2 * (size_t)p.q_rows;
-  if ((rc = sc.buf.verdict.ensure(hipEventBlockingSync | hipEventDisableTiming))) return rc;
   // (a caller's stream other than the space's own: searches already in flight there and here finish first)
   if ((rc = wait_searches_in_flight(s, st))) return rc;
   if ((rc = sc.clock.begin(st, env().stats_every))) return rc;
   HIP_TRY(launch_prep_queries_i8(d_queries, (uint32_t)nq, s->dims, s->ld, s->ld8, p.q_rows, s->metric, sc.buf.dQ.p,
                                  sc.buf.dQ8.p, sc.buf.dQp8.p, sc.buf.dQuv.p, sc.buf.dThr8.p, sc.buf.dI8Ctl.p, st));
   auto scan = [&](const ScanPlan& pl, uint32_t tile0) -> hipError_t {
-    i8_scan_pass(a, pl, tile0);
+    set_scan_pass(a, pl, tile0);
     return launch_flat_scan_i8(a, st);
   };
   if ((rc = sc.clock.scan_begin(st))) return rc;
@@ -394,8 +395,8 @@ int flat_pass8(ehx_space* s, uint64_t n_pub, int set, hipStream_t st, size_t nq,
   r.out_ids = d_ids;
   r.out_dist = d_dist;
   r.out_count = d_count;
-  r.n_uncertified = sc.buf.dUncert.p;
-  r.uncert_flags = sc.buf.dUflags.p;
+  r.n_uncertified = sc.buf.verdict.count.p;
+  r.uncert_flags = sc.buf.verdict.flags.p;
   r.nq = (uint32_t)nq;
   r.k = k;
   r.kprime = kprime;
@@ -404,36 +405,8 @@ int flat_pass8(ehx_space* s, uint64_t n_pub, int set, hipStream_t st, size_t nq,
   r.ld = s->ld;
   r.metric = s->metric;
   HIP_TRY(launch_rerank256(r, st));
-  if (env().i8_count) {  // diagnosis builds (-DEHX_I8_COUNT=1): the scan's epilogue counters of this batch
-    unsigned long long c[8] = {0};
-    HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipMemcpy(c, sc.buf.dCnt.p, sizeof(c), hipMemcpyDeviceToHost));
-    fprintf(stderr, "[i8 count] tests %llu alarms %llu row-block alarms %llu trips %llu (cumulative)\n", c[0], c[1], c[2], c[3]);
-  }
-  if (env().i8_debug) {  // diagnosis only: what the uncertified queries of this batch look like
-    HIP_TRY(hipStreamSynchronize(st));
-    std::vector<uint32_t> fl(nq), ov(nq);
-    std::vector<float4> qp(nq);
-    std::vector<float2> uv(nq);
-    std::vector<uint64_t> mg(nq * width);
-    std::vector<float> od(nq * k);
-    HIP_TRY(hipMemcpy(fl.data(), sc.buf.dUflags.p, nq * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(ov.data(), ovf, nq * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(qp.data(), sc.buf.dQp8.p, nq * sizeof(float4), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(uv.data(), sc.buf.dQuv.p, nq * sizeof(float2), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(mg.data(), sc.buf.dMerged8.p, nq * width * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(od.data(), d_dist, nq * k * 4, hipMemcpyDeviceToHost));
-    int shown = 0;
-    for (size_t q = 0; q < nq && shown < 6; ++q) {
-      if (!fl[q]) continue;
-      ++shown;
-      auto S = [&](int i) { return mg[q * width + i] == ~0ull ? INFINITY : ordered_to_f32((uint32_t)(mg[q * width + i] >> 32)); };
-      fprintf(stderr, "[i8 debug] q=%zu ovf=%u tmin=%g S[0]=%g S[63]=%g S[127]=%g S[255]=%g kth_dist=%g u=%g v=%g\n", q, ov[q],
-              qp[q].w, S(0), S(63), S(127), S(255), od[q * k + k - 1], uv[q].x, uv[q].y);
-    }
-  }
+  if ((env().i8_count || env().i8_debug) && (rc = i8_diagnose(sc.buf, st, nq, k, width, ovf, d_dist))) return rc;
   if ((rc = sc.clock.finish(st))) return rc;
-  if (count_stats) count_scan_batch(s, nq, n_pub, k, 1);   // (the int8 scan copy)
   s->n_rerank += (uint64_t)nq * kprime;
   return EHX_OK;
 }
@@ -455,9 +428,8 @@ int exhaustive_pass(ehx_space* s, uint64_t n_pub, hipStream_t st, size_t nq, con
   if ((rc = s->scr.dQ.ensure(nq * s->ld))) return rc;
   if ((rc = s->scr.dPart.ensure(nq * n_blocks * 64))) return rc;
   if ((rc = s->scr.dMerged.ensure(nq * 64))) return rc;
-  if ((rc = s->scr.dUflags.ensure(nq))) return rc;
+  if ((rc = s->scr.verdict.ensure(nq))) return rc;
   if (pages > 1 && (rc = s->scr.dGthr.ensure(nq + 8))) return rc;
-  if ((rc = s->scr.dUncert16.ensure_zeroed_once(1))) return rc;
   {
     int rcw = wait_searches_in_flight(s, st);
     if (rcw) return rcw;
@@ -478,11 +450,11 @@ int exhaustive_pass(ehx_space* s, uint64_t n_pub, hipStream_t st, size_t nq, con
     r.out_ids = d_ids;
     r.out_dist = d_dist;
     r.out_count = d_count;
-    r.n_uncertified = s->scr.dUncert16.p;
+    r.n_uncertified = s->scr.verdict.count.p;   // (never raised: exact keys are never flagged)
     r.nq = (uint32_t)nq;
     r.k = std::min<uint32_t>(64, k - pg * 64);
     r.kprime = 64;
-    r.uncert_flags = s->scr.dUflags.p;
+    r.uncert_flags = s->scr.verdict.flags.p;
     r.exact_keys = 1;
     r.out_stride = k;
     r.out_offset = pg * 64;
@@ -495,15 +467,15 @@ int exhaustive_pass(ehx_space* s, uint64_t n_pub, hipStream_t st, size_t nq, con
 
 // Adaptation of the int8 list after a batch of `nq` queries that ran with logical length `kprime`, lost `n_failed`
 // queries to the next engine, `n_short` of them because their candidate LIST was too short.  Called for EVERY int8
-// batch, clean ones included, from both paths (knn_device_locked; knn_host_direct's pipelined stage, which used to
-// skip it for clean batches: its score never decayed, and two losing batches any distance apart widened the list).
+// batch, clean ones included, whichever path ran it (i8_stage_outcome; the pipelined path once skipped it for clean
+// batches: its score never decayed, and two losing batches any distance apart widened the list).
 // The list is too short for this data when batches keep losing queries to the next engine — which re-reads every
 // row for them, nearly a batch's worth of time however few they are (12.5 M x 1536: 13 queries in 10 batches cost
 // 45 % of the run).  Only queries whose LIST was the failing part count (the re-rank flags them 2: a pool overflow,
 // exact ties at the threshold or lost candidates are not cured by width, and a width, once raised, stays).  A batch of
 // at least 64 queries that loses more than 2 % of them that way widens the list at once; otherwise every losing
 // batch adds 4 to a score that decays by 1 per clean batch, and 8 widens (two losing batches close together).
-void i8_adapt(ehx_space* s, size_t nq, size_t n_failed, size_t n_short, uint32_t kprime) {
+static void i8_adapt(ehx_space* s, size_t nq, size_t n_failed, size_t n_short, uint32_t kprime) {
   std::lock_guard<std::mutex> l(s->i8_adapt_mu);
   if (n_short == 0) s->i8_fb_score = s->i8_fb_score ? s->i8_fb_score - 1 : 0;
   else s->i8_fb_score += 4;
@@ -526,25 +498,34 @@ void i8_adapt(ehx_space* s, size_t nq, size_t n_failed, size_t n_short, uint32_t
             nq, n_short, std::max(s->i8_kprime_min.load(), kprime), s->i8_width.load());
 }
 
-void count_scan_batch(ehx_space* s, size_t nq, uint64_t n_pub, uint32_t k, uint64_t elem_bytes) {
+static void count_scan_batch(ehx_space* s, size_t nq, uint64_t n_pub, uint32_t k, uint64_t elem_bytes) {
   s->n_queries += nq;
   s->n_dist += (uint64_t)nq * n_pub;
   // SURVEY §8d brute force bytes per batch: N*d*s + B*d*4 + B*k*12 (s = bytes per element the scan reads)
   s->bytes_algo += n_pub * s->dims * elem_bytes + (uint64_t)nq * s->dims * 4ull + (uint64_t)nq * k * 12ull;
 }
 
-int collect_uncertified(hipStream_t st, const uint32_t* d_flags, size_t m, const std::vector<uint32_t>* subset,
-                        std::vector<uint32_t>* out, size_t* n_short) {
-  std::vector<uint32_t> flags(m);
-  HIP_TRY(hipMemcpyAsync(flags.data(), d_flags, m * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  out->clear();
-  *n_short = 0;
-  for (size_t j = 0; j < m; ++j)
-    if (flags[j]) {
-      out->push_back(subset ? (*subset)[j] : (uint32_t)j);
-      *n_short += flags[j] == 2u;
-    }
+int i8_stage_enqueue(ehx_space* s, uint64_t n_pub, int set, hipStream_t st, hipEvent_t after, bool pipelined, size_t nq,
+                     const float* d_queries, uint32_t k, uint64_t* d_ids, float* d_dist, uint32_t* d_count, I8Outcome* o) {
+  // (this batch's launches go onto the stream as one block: per-batch scan windows stay clean)
+  std::lock_guard<std::mutex> ql(s->i8_enqueue_mu);
+  if (after) HIP_TRY(hipStreamWaitEvent(st, after, 0));
+  int rc = flat_pass8(s, n_pub, set, st, nq, d_queries, k, d_ids, d_dist, d_count, &o->kprime);
+  if (rc) return rc;
+  Verdict& v = s->i8set[set].buf.verdict;
+  return pipelined ? v.post_and_record(st) : v.post(st);
+}
+
+int i8_stage_outcome(ehx_space* s, uint64_t n_pub, int set, hipStream_t st, size_t nq, uint32_t k, I8Outcome* o) {
+  Verdict& v = s->i8set[set].buf.verdict;
+  o->failed.clear();
+  o->n_short = 0;
+  int rc;
+  if (v.read() && (rc = v.collect(st, nq, nullptr, &o->failed, &o->n_short))) return rc;
+  count_scan_batch(s, nq, n_pub, k, 1);   // (the int8 scan copy)
+  s->n_i8_queries += nq;
+  s->n_i8_fallback += o->failed.size();
+  i8_adapt(s, nq, o->failed.size(), o->n_short, o->kprime);
   return EHX_OK;
 }
 
@@ -556,13 +537,10 @@ int collect_uncertified(hipStream_t st, const uint32_t* d_flags, size_t m, const
 //   3. canonical distance of every row                        (what stage 2 could not certify: near-ties finer
 //                                                              than the certification margin; kMaxExhaustive
 //                                                              queries per launch group, as many groups as needed)
-// One host round trip (8 bytes) per stage to read its verdict.
-// i8_failed (optional): the int8 stage of this very batch has already run — in one of the scratch sets, outside the
-// pipeline lock (knn_host_direct) — and left the answers of every other query in the output arrays; these queries
-// (i8_short of them because their candidate list was too short) continue with the next engine.
+// One host round trip (8 bytes) per stage to read its verdict (Verdict, ehx_own.h).
+// knn_device_locked: the gates in front of the chain and stage 0; flat_chain_rest: stages 1 to 3.
 int knn_device_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k,
-                      uint64_t* d_ids, float* d_dist, uint32_t* d_count, const std::vector<uint32_t>* i8_failed,
-                      size_t i8_short, uint32_t i8_kprime_in, uint64_t n_pub) {
+                      uint64_t* d_ids, float* d_dist, uint32_t* d_count, uint64_t n_pub) {
   if (k == 0 || nq == 0) return EHX_OK;
   if (nq > (1u << 24)) return fail(EHX_EINVAL, "too many queries in one call: %zu", nq);
   if (s->params.mode == EHX_MODE_GRAPH) {
@@ -570,7 +548,7 @@ int knn_device_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_qu
     if (k > EHX_MAX_K_PAGED) return fail(EHX_EUNSUPPORTED, "graph mode: k=%u exceeds %u", k, EHX_MAX_K_PAGED);
     return knn_graph_locked(s, st, nq, d_queries, k, d_ids, d_dist, d_count);
   }
-  // the ONE read of the row count in this search (a caller whose int8 stage already ran passes the snapshot it ran on)
+  // the ONE read of the row count in this search (a caller that has a snapshot already passes it)
   if (n_pub == kNoSnapshot) n_pub = s->n.load(std::memory_order_acquire);
   if (k > EHX_MAX_K) {
     // beyond the candidate capacity of one scan pass: the exhaustive canonical pass, paged (exact, HBM-bound —
@@ -584,8 +562,7 @@ int knn_device_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_qu
     if (rc2) return rc2;
     s->n_queries += nq;
     s->n_exhaustive += nq;
-    HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipMemsetAsync(s->scr.dUncert16.p, 0, sizeof(unsigned long long), st));
+    HIP_TRY(hipStreamSynchronize(st));   // (callers rely on it)
     return EHX_OK;
   }
   // ONE query against a small shard — the reference's own usage: one NearestNeighbor RPC, one query (server.cc:172-210;
@@ -599,16 +576,33 @@ int knn_device_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_qu
     if (rc2) return rc2;
     s->n_queries += nq;
     s->n_exhaustive += nq;
-    if (s->scr.dUncert16.p) HIP_TRY(hipMemsetAsync(s->scr.dUncert16.p, 0, sizeof(unsigned long long), st));
     return EHX_OK;   // (no wait here: the caller's copy-back or stream order is the wait)
   }
+  const int eng = resolve_engine(s, n_pub);
+  test_pause();
+  if (eng != EHX_ENGINE_I8) return flat_chain_rest(s, st, n_pub, nq, d_queries, k, d_ids, d_dist, d_count, eng, nullptr);
+  I8Outcome o;
+  {
+    // (scratch set 0, held for the stage and its verdict: host batches may be using both sets through knn_host_direct's
+    // pipelined path at the same time)
+    std::lock_guard<std::mutex> set_lock(s->i8set[0].mu);
+    int rc = i8_stage_enqueue(s, n_pub, 0, st, nullptr, false, nq, d_queries, k, d_ids, d_dist, d_count, &o);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(st));
+    if ((rc = i8_stage_outcome(s, n_pub, 0, st, nq, k, &o))) return rc;
+  }
+  if (o.failed.empty()) return EHX_OK;
+  return flat_chain_rest(s, st, n_pub, nq, d_queries, k, d_ids, d_dist, d_count, eng, &o);
+}
+
+int flat_chain_rest(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, const float* d_queries, uint32_t k,
+                    uint64_t* d_ids, float* d_dist, uint32_t* d_count, int eng, const I8Outcome* i8) {
   constexpr size_t kMaxExhaustive = 32;
-  enum { kI8, kFilter, kF32, kExhaustive };
+  enum { kFilter, kF32, kExhaustive };
   int rc;
-  size_t n_short = 0;  // of the last stage's uncertified queries: those whose candidate LIST was too short (flag 2)
-  uint32_t i8_kprime = i8_kprime_in;  // the k' this batch's int8 stage ran with
+  Verdict& v = s->scr.verdict;
   // run one stage on `subset` (nullptr = every query); *unc = global indices it could not certify
-  auto stage = [&](int kind, const std::vector<uint32_t>* subset, bool count_stats, std::vector<uint32_t>* unc) -> int {
+  auto stage = [&](int kind, const std::vector<uint32_t>* subset, std::vector<uint32_t>* unc) -> int {
     const size_t m = subset ? subset->size() : nq;
     const float* q = d_queries;
     uint64_t* oi = d_ids;
@@ -622,69 +616,39 @@ int knn_device_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_qu
       od = sub.dFbDist.p;
       oc = sub.dFbCnt.p;
     }
-    // (the int8 stage runs in scratch set 0 here, held for the stage and its verdict: host batches may be using both sets
-    // through knn_host_direct's pipelined path at the same time)
-    std::unique_lock<std::mutex> set_lock(s->i8set[0].mu, std::defer_lock);
-    if (kind == kI8) set_lock.lock();
     if (kind == kExhaustive) rc = exhaustive_pass(s, n_pub, st, m, q, k, oi, od, oc);
-    else if (kind == kI8) {   // (enqueued as one block, like a pipelined host batch's: per-batch scan windows stay clean)
-      std::lock_guard<std::mutex> ql(s->i8_enqueue_mu);
-      rc = flat_pass8(s, n_pub, 0, st, m, q, k, oi, od, oc, count_stats, &i8_kprime);
-    }
-    else rc = flat_pass(s, n_pub, st, m, q, k, oi, od, oc, kind == kFilter, count_stats);
+    else rc = flat_pass(s, n_pub, st, m, q, k, oi, od, oc, kind == kFilter);
     if (rc) return rc;
-    unsigned long long* d_unc = kind == kI8 ? s->i8set[0].buf.dUncert.p : s->scr.dUncert16.p;
-    const uint32_t* d_flags = kind == kI8 ? s->i8set[0].buf.dUflags.p : s->scr.dUflags.p;
     if (subset) {
       if ((rc = sub.scatter(d_ids, d_dist, d_count, st))) return rc;
       if ((rc = s->clock.extend(st))) return rc;   // (the scatter is part of the pass's batch: writers wait for it too)
     }
-    // verdict
     unc->clear();
-    // (into PINNED host memory: a copy to pageable memory goes through a staging buffer and a copy kernel)
-    if ((rc = s->scr.hUncertPin.ensure(1))) return rc;
-    HIP_TRY(hipMemcpyAsync(s->scr.hUncertPin.p, d_unc, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    if ((rc = v.post(st))) return rc;
     HIP_TRY(hipStreamSynchronize(st));
-    const unsigned long long n_unc = *s->scr.hUncertPin.p;
-#if defined(EHX_ABL) && EHX_ABL
-    return EHX_OK;  // profiling builds with ablated (wrong-by-construction) kernels: time the first stage only
-#endif
-    if (n_unc == 0) return EHX_OK;
-    HIP_TRY(hipMemsetAsync(d_unc, 0, sizeof(unsigned long long), st));
-    return collect_uncertified(st, d_flags, m, subset, unc, &n_short);
+    size_t n_short;   // (only the int8 list adapts to it)
+    return v.read() ? v.collect(st, m, subset, unc, &n_short) : EHX_OK;
   };
 
   std::vector<uint32_t> todo, next;
   bool all = true;  // `todo` = every query
-  bool counted = false;
-  const int eng = resolve_engine(s, n_pub);
-  test_pause();
-  if (eng == EHX_ENGINE_I8) {
-    if (i8_failed) {
-      next = *i8_failed;
-      n_short = i8_short;
-    } else if ((rc = stage(kI8, nullptr, true, &next))) {
-      return rc;
-    }
-    counted = true;
-    s->n_i8_queries += nq;
-    s->n_i8_fallback += next.size();
-    i8_adapt(s, nq, next.size(), n_short, i8_kprime);
-    if (next.empty()) return EHX_OK;
-    todo.swap(next);
+  const bool filter = (eng == EHX_ENGINE_I8 || eng == EHX_ENGINE_F16) && s->has16 && s->h_unsafe.load(std::memory_order_relaxed) == 0;
+  if (i8) {
+    todo = i8->failed;
     all = todo.size() * 2 > nq;
+  } else {  // (a batch's work counters are those of its first engine)
+    count_scan_batch(s, nq, n_pub, k, filter ? 2 : s->esz);
   }
-  if ((eng == EHX_ENGINE_I8 || eng == EHX_ENGINE_F16) && s->has16 && s->h_unsafe.load(std::memory_order_relaxed) == 0) {
+  if (filter) {
     const size_t m = all ? nq : todo.size();
-    if ((rc = stage(kFilter, all ? nullptr : &todo, !counted, &next))) return rc;
-    counted = true;
+    if ((rc = stage(kFilter, all ? nullptr : &todo, &next))) return rc;
     s->n_filter_queries += m;
     s->n_filter_fallback += next.size();
     if (next.empty()) return EHX_OK;
     todo.swap(next);
     all = todo.size() * 2 > nq;  // most of the batch: just run it all through the fp32 scan
   }
-  if ((rc = stage(kF32, all ? nullptr : &todo, !counted, &next))) return rc;
+  if ((rc = stage(kF32, all ? nullptr : &todo, &next))) return rc;
   if (next.empty()) return EHX_OK;
   todo.swap(next);
   // Whatever the matrix-core scans could not certify is answered by the exhaustive canonical pass, kMaxExhaustive
@@ -692,7 +656,7 @@ int knn_device_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_qu
   std::vector<uint32_t> chunk;
   for (size_t i0 = 0; i0 < todo.size(); i0 += kMaxExhaustive) {
     chunk.assign(todo.begin() + i0, todo.begin() + std::min(todo.size(), i0 + kMaxExhaustive));
-    if ((rc = stage(kExhaustive, &chunk, false, &next))) return rc;
+    if ((rc = stage(kExhaustive, &chunk, &next))) return rc;
     s->n_exhaustive += chunk.size();
     if (!next.empty()) {  // cannot happen: exact keys are never flagged
       s->n_uncertified_final += next.size();

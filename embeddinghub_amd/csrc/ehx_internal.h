@@ -421,15 +421,13 @@ struct ehx_space {
     DevBuf<uint64_t> dCand, dPart, dMerged, dOutIds, dGthr;
     DevBuf<float> dOutDist;
     DevBuf<uint32_t> dOutCount;
-    DevBuf<unsigned long long> dUncert;
-    // filter scratch: fp16 queries, per-query (gamma, u, v), per-query certification flags, re-run buffers
+    DevBuf<uint32_t> dScanErr;                 // one word: times a scan kernel tripped its bounded-retry guard (ehx_stats)
+    // filter scratch: fp16 queries, per-query (gamma, u, v), re-run buffers
     DevBuf<__half> dQ16;
     DevBuf<float> dQgamma, dSample;
     DevBuf<float2> dQuv;
-    DevBuf<uint32_t> dUflags;
     SubsetBufs sub;                            // the queries a stage of the engine chain re-runs
-    DevBuf<unsigned long long> dUncert16;      // queries the filter pass could not certify
-    PinBuf<unsigned long long> hUncertPin;     // pinned landing place of a batch's verdict (uncertified-query count)
+    Verdict verdict;                           // of the fp16 / fp32 / exhaustive stage that ran last
     PinBuf<char> hSmallPin;                    // pinned staging of small host calls: [queries | ids, distances, counts]
     DevBuf<uint64_t> dSmallOut;                // their results, one block (one device-to-host copy)
   } scr;
@@ -476,11 +474,8 @@ struct ehx_space {
       DevBuf<float> dThr8, dSample8;
       DevBuf<uint64_t> dPool, dMerged8;
       DevBuf<uint32_t> dI8Ctl;  // [q_rows] pool counts | [q_rows] overflow flags | [kSyncWordsI8] lock-step progress words
-      DevBuf<uint32_t> dUflags;
       DevBuf<uint64_t> dCnt;    // [8] epilogue counters of diagnosis builds (EHX_I8_COUNT); the set's own: nothing shared
-      DevBuf<unsigned long long> dUncert;
-      PinBuf<unsigned long long> hUncertPin;
-      Event verdict;            // blocking-sync: the verdict has landed in hUncertPin
+      Verdict verdict;          // of the set's int8 stage, on the device path and the pipelined one
     } buf;
     BatchClock clock;              // timed: batch 0 and every EHX_STATS_EVERY-th batch of the set
     std::mutex mu;
@@ -597,25 +592,48 @@ struct ScanPlan {
   uint32_t q_tiles, q_rows, n_tiles, n_chunks, tiles_per_chunk, kprime, xcd_map, grid;
 };
 ScanPlan plan_scan(uint32_t nq, uint32_t n_tiles, uint32_t k, int n_cus);   // one scan pass over `n_tiles` row tiles
+struct ScanPass {
+  uint32_t tile0;
+  ScanPlan plan;
+};
+// the passes of a scan cascade over n_tiles row tiles: the first `first_tiles`, then x `growth` in tiles seen per pass while
+// less than half of them are, then the rest (first_tiles >= n_tiles / 2: one pass)
+std::vector<ScanPass> plan_cascade(uint32_t nq, uint32_t n_tiles, uint32_t k, int n_cus, uint64_t first_tiles, uint64_t growth);
+// the fields of one pass in the arguments of any of the three scans (ScanArgs, ScanArgs16, ScanArgsI8)
+template <class Args>
+inline void set_scan_pass(Args& a, const ScanPlan& pl, uint32_t tile0) {
+  a.tile0 = tile0;
+  a.n_tiles = pl.n_tiles;
+  a.n_chunks = pl.n_chunks;
+  a.tiles_per_chunk = pl.tiles_per_chunk;
+  a.xcd_map = pl.xcd_map;
+}
 constexpr uint64_t kNoSnapshot = ~0ull;   // knn_device_locked: no snapshot of the row count yet, take one
-// n_pub: the search's one snapshot of the published row count (s->n.load(std::memory_order_acquire))
-int flat_pass(ehx_space* s, uint64_t n_pub, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, uint64_t* d_ids,
-              float* d_dist, uint32_t* d_count, bool f16, bool count_stats);
 int resolve_engine(const ehx_space* s, uint64_t n_pub);
-int flat_pass8(ehx_space* s, uint64_t n_pub, int set, hipStream_t st, size_t nq, const float* d_queries, uint32_t k,
-               uint64_t* d_ids, float* d_dist, uint32_t* d_count, bool count_stats, uint32_t* kprime_used = nullptr);
+// n_pub: the search's one snapshot of the published row count (s->n.load(std::memory_order_acquire))
 int exhaustive_pass(ehx_space* s, uint64_t n_pub, hipStream_t st, size_t nq, const float* d_queries, uint32_t k,
                     uint64_t* d_ids, float* d_dist, uint32_t* d_count);
-void i8_adapt(ehx_space* s, size_t nq, size_t n_failed, size_t n_short, uint32_t kprime);
-// work counters of one scan batch of nq queries over n_pub rows; elem_bytes: bytes per element the scan reads
-void count_scan_batch(ehx_space* s, size_t nq, uint64_t n_pub, uint32_t k, uint64_t elem_bytes);
-// the uncertified queries of a batch of m (flags d_flags[0, m) on the device; subset: their global indices) -> *out, and
-// how many of them were flagged 2 (a candidate list too short) -> *n_short
-int collect_uncertified(hipStream_t st, const uint32_t* d_flags, size_t m, const std::vector<uint32_t>* subset,
-                        std::vector<uint32_t>* out, size_t* n_short);
+// The int8 stage of a batch, for both of its callers (knn_device_locked; knn_host_direct's pipelined stage).  The caller
+// holds the scratch set's mutex from the enqueue to the outcome and waits in between in its own way.
+struct I8Outcome {
+  std::vector<uint32_t> failed;   // queries the stage could not certify: the next engine's
+  size_t n_short = 0;             // ... of them because their candidate LIST was too short
+  uint32_t kprime = 0;            // the list's logical length the stage ran with
+};
+// enqueues the stage on `st` as one block (i8_enqueue_mu), behind `after` if given, and posts its verdict: with the verdict's
+// event recorded (pipelined: Verdict::post_and_record) or without
+int i8_stage_enqueue(ehx_space* s, uint64_t n_pub, int set, hipStream_t st, hipEvent_t after, bool pipelined, size_t nq,
+                     const float* d_queries, uint32_t k, uint64_t* d_ids, float* d_dist, uint32_t* d_count, I8Outcome* o);
+// after the caller's wait: the landed verdict -> *o, and ALL of the stage's accounting (work counters, n_i8_queries,
+// n_i8_fallback, the list's adaptation)
+int i8_stage_outcome(ehx_space* s, uint64_t n_pub, int set, hipStream_t st, size_t nq, uint32_t k, I8Outcome* o);
 int knn_device_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k,
-                      uint64_t* d_ids, float* d_dist, uint32_t* d_count, const std::vector<uint32_t>* i8_failed = nullptr,
-                      size_t i8_short = 0, uint32_t i8_kprime_in = 0, uint64_t n_pub = kNoSnapshot);
+                      uint64_t* d_ids, float* d_dist, uint32_t* d_count, uint64_t n_pub = kNoSnapshot);
+// the rest of the chain after the int8 stage: fp16 filter, fp32 scan, exhaustive pass, each for what the one before left.
+// eng: what resolve_engine gave for the batch; i8: the outcome of its int8 stage when that is EHX_ENGINE_I8 (the failed
+// queries continue), else nullptr
+int flat_chain_rest(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, const float* d_queries, uint32_t k,
+                    uint64_t* d_ids, float* d_dist, uint32_t* d_count, int eng, const I8Outcome* i8);
 
 // ---- ehx_search.cpp ----
 void yield_to_writer(const ehx_space* s);   // a search lets an exclusive writer that waits for the space's lock in first
@@ -638,15 +656,8 @@ int lookup_keys(ehx_space* s, size_t n, const char* const* keys, const size_t* k
                 size_t* bad_index);
 RowsView rows_view(const ehx_space* s, uint64_t n_pub);   // where the rows are, for a search on the prefix of n_pub rows
 // The int8 scan's arguments for a batch planned as `p` in the buffers `b` (grown as needed), all but the pass's own fields
-// (i8_scan_pass; dump, sync).  The control words are b.dI8Ctl: [q_rows] pool counts | [q_rows] overflow flags | lock-step.
+// (set_scan_pass; dump, sync).  The control words are b.dI8Ctl: [q_rows] pool counts | [q_rows] overflow flags | lock-step.
 int i8_scan_args(ehx_space* s, ehx_space::I8Set::Buffers& b, const ScanPlan& p, uint64_t n_pub, ScanArgsI8* a);
-inline void i8_scan_pass(ScanArgsI8& a, const ScanPlan& pl, uint32_t tile0) {
-  a.tile0 = tile0;
-  a.n_tiles = pl.n_tiles;
-  a.n_chunks = pl.n_chunks;
-  a.tiles_per_chunk = pl.tiles_per_chunk;
-  a.xcd_map = pl.xcd_map;
-}
 
 // ---- ehx_among.cpp ----
 // exact kNN among row ids on an unsharded space, locked shared, scratch_mu held, its device current (d_off == nullptr: one

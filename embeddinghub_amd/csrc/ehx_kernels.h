@@ -624,9 +624,8 @@ struct ScanArgs {
   uint32_t xcd_map;      // 1: blocks of one chunk share an XCD (grid % 8 == 0, n_chunks % 8 == 0)
 };
 
-uint32_t scan_lists_per_chunk();  // sorted key lists each (query, chunk) publishes: 2 (one per wave row)
-hipError_t launch_flat_scan(const ScanArgs& a, hipStream_t st);   // the fp32 matrix-core scan
-hipError_t launch_flat_scan8(const ScanArgs& a, hipStream_t st);  // k_flat8.hip: 8 waves, two per SIMD
+constexpr uint32_t kScanListsPerChunk = 2;  // sorted key lists each (query, chunk) publishes: one per wave row of the 8-wave kernels
+hipError_t launch_flat_scan8(const ScanArgs& a, hipStream_t st);  // the fp32 matrix-core scan (k_flat8.hip: 8 waves, two per SIMD)
 
 // ---- fp16-MFMA filter scan (k_flat16.hip) ----
 struct ScanArgs16 {
@@ -808,8 +807,6 @@ hipError_t launch_make_scan16(const void* X, int x_half, uint64_t row0, uint64_t
 // D = u*S + v.  Queries the filter cannot bound get u = NaN (never certified -> fp32 re-run).
 hipError_t launch_prep_queries16(const float* q_in, uint32_t nq, uint32_t dims, uint32_t ld16, uint32_t q_rows,
                                  int metric, __half* Q16, float* qgamma, float2* quv, hipStream_t st);
-
-hipError_t launch_set_gthr(const uint64_t* merged, uint32_t nq, uint32_t kprime, unsigned long long* gthr, hipStream_t st);
 
 // one wave per query: k-way merge of the per-chunk sorted key lists -> top-kprime keys
 // (merges `n_chunks` consecutive lists of each query; a query's lists are `lists_stride` apart)

@@ -150,4 +150,56 @@ struct Stream {
   }
 };
 
+// The verdict of one stage of the exact flat chain: how many of its queries the re-rank could not certify, and which.
+// The re-rank kernels count into `count` and flag the queries in `flags` (1: uncertified; 2: because the candidate LIST was
+// too short).  The stage's caller posts the copy of the count behind its launches, waits in its own way — the device path
+// on the stream, the pipelined host path on `ev` (blocking-sync: the thread sleeps) — reads it, and only when it is not
+// zero collects the flags: 8 bytes and one wait per stage of a clean batch.
+struct Verdict {
+  DevBuf<unsigned long long> count;    // zeroed once; collect() clears it again
+  DevBuf<uint32_t> flags;              // [q_rows]
+  PinBuf<unsigned long long> landed;   // (PINNED: a copy to pageable memory goes through a staging buffer and a copy kernel)
+  Event ev;                            // post_and_record: the count has landed
+
+  int ensure(size_t q_rows) {
+    int rc;
+    if ((rc = count.ensure_zeroed_once(1)) || (rc = flags.ensure(q_rows))) return rc;
+    return landed.ensure(1);
+  }
+  int post(hipStream_t st) {
+    HIP_TRY(hipMemcpyAsync(landed.p, count.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    return EHX_OK;
+  }
+  // (the one event of a pipelined batch: a marker of its own costs the queue another ~6 us per batch)
+  int post_and_record(hipStream_t st) {
+    int rc;
+    if ((rc = ev.ensure(hipEventBlockingSync | hipEventDisableTiming)) || (rc = post(st))) return rc;
+    HIP_TRY(hipEventRecord(ev, st));
+    return EHX_OK;
+  }
+  // after the caller's wait: queries of the stage left uncertified
+  unsigned long long read() const {
+#if defined(EHX_ABL) && EHX_ABL
+    return 0;  // profiling builds with ablated (wrong-by-construction) kernels: time the first stage only
+#endif
+    return *landed.p;
+  }
+  // the uncertified queries of a stage of m (subset: their indices in the whole batch) -> *out, those flagged 2 counted in
+  // *n_short; clears the count for the next stage.  Waits for the stream.
+  int collect(hipStream_t st, size_t m, const std::vector<uint32_t>* subset, std::vector<uint32_t>* out, size_t* n_short) {
+    std::vector<uint32_t> f(m);
+    HIP_TRY(hipMemsetAsync(count.p, 0, sizeof(unsigned long long), st));
+    HIP_TRY(hipMemcpyAsync(f.data(), flags.p, m * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    out->clear();
+    *n_short = 0;
+    for (size_t j = 0; j < m; ++j)
+      if (f[j]) {
+        out->push_back(subset ? (*subset)[j] : (uint32_t)j);
+        *n_short += f[j] == 2u;
+      }
+    return EHX_OK;
+  }
+};
+
 }  // namespace ehx_impl

@@ -37,7 +37,7 @@ int range_overflow(ehx_space* s, hipStream_t st, uint64_t n_pub, const float* d_
     HIP_TRY(launch_range_iota(s->range.dIota.p, n_pub, st));
     rc = among_locked(s, st, sub.m, sub.dFbQ.p, k, s->range.dIota.p, nullptr, n_pub, 0, sub.dFbIds.p, sub.dFbDist.p, sub.dFbCnt.p);
   } else {
-    rc = knn_device_locked(s, st, sub.m, sub.dFbQ.p, k, sub.dFbIds.p, sub.dFbDist.p, sub.dFbCnt.p, nullptr, 0, 0, n_pub);
+    rc = knn_device_locked(s, st, sub.m, sub.dFbQ.p, k, sub.dFbIds.p, sub.dFbDist.p, sub.dFbCnt.p, n_pub);
   }
   if (rc) return rc;
   if ((rc = sub.scatter(o.ids, o.dist, o.cnt, st))) return rc;
@@ -124,7 +124,7 @@ int range_i8_stage(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, cons
     // ... then the radius' threshold, and the marks of the queries the bound does not serve
     HIP_TRY(launch_range_thr(d_radius, sc.buf.dQuv.p, s->rows.dMaxSumsq.p, (uint32_t)nq, s->dims, s->metric, sc.buf.dThr8.p, a.ovf,
                              st));
-    i8_scan_pass(a, p, 0);   // ONE pass over all tiles
+    set_scan_pass(a, p, 0);   // ONE pass over all tiles
     if ((rc = sc.clock.scan_begin(st))) return rc;
     HIP_TRY(launch_flat_scan_i8(a, st));
     if ((rc = sc.clock.scan_end(st))) return rc;

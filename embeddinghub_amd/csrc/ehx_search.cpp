@@ -76,7 +76,7 @@ static int by_ids_locked(ehx_space* s, hipStream_t st, size_t n, const uint64_t*
   g.G = 1;
   HIP_TRY(launch_gather_rows(g, st));
   if (n_pub > 0)   // (an empty space: every query is invalid, the lists are never read)
-    rc = knn_device_locked(s, st, n, s->by.dByQ.p, k + 1, b.l_ids, b.l_dist, b.l_cnt, nullptr, 0, 0, n_pub);
+    rc = knn_device_locked(s, st, n, s->by.dByQ.p, k + 1, b.l_ids, b.l_dist, b.l_cnt, n_pub);
   if (!rc) rc = by_drop_self(b, st, n, d_row_ids, k, d_out_ids, d_out_dist, d_out_count);
   (void)hipEventRecord(s->by.by_ev, st);
   return rc;
@@ -351,57 +351,42 @@ static int knn_host_direct(ehx_space* s, size_t n_queries, const float* queries,
   // The int8 engine's first stage — all of a batch unless queries lose their certificate — runs in one of the space's two
   // scratch sets WITHOUT the pipeline-wide lock: this call's launches queue up on the space's stream behind the other
   // caller's while that one still waits for its verdict, so the scan kernels of consecutive batches run back to back with
-  // no host round trip (launches, verdict copy, thread wake-up: ~0.1 ms per batch) between them.  A batch that does lose
-  // queries is re-run through the full engine chain under the lock (rare; the chain also adapts the list's length).
+  // no host round trip (launches, verdict copy, thread wake-up: ~0.1 ms per batch) between them.  The queries a batch does
+  // lose continue through the rest of the chain under the lock (rare).
   const bool pipe_on = env().host_pipeline;
-  bool done = false, have_failed = false, copied_early = false;
-  std::vector<uint32_t> failed;
-  size_t n_short = 0;
-  uint32_t kprime_used = 0;
-  // the ONE read of the row count in this call: the pipelined int8 stage and the rest of the chain (knn_device_locked) answer
-  // for the same prefix
+  bool done = false;   // answered by the pipelined stage alone, the results on their way back
+  I8Outcome o;
+  // the ONE read of the row count in this call: the pipelined int8 stage and the rest of the chain answer for the same prefix
   const uint64_t n_pub = s->n.load(std::memory_order_acquire);
-  if (pipe_on && s->params.mode == EHX_MODE_FLAT && k <= EHX_MAX_K && n_pub > 0 && resolve_engine(s, n_pub) == EHX_ENGINE_I8) {
+  const bool pipelined =
+      pipe_on && s->params.mode == EHX_MODE_FLAT && k <= EHX_MAX_K && n_pub > 0 && resolve_engine(s, n_pub) == EHX_ENGINE_I8;
+  if (pipelined) {
     const int set = (int)(s->i8_next_set.fetch_add(1, std::memory_order_relaxed) & 1u);   // consecutive batches alternate
     ehx_space::I8Set& sc = s->i8set[set];
     test_pause();
     std::lock_guard<std::mutex> l(sc.mu);
-    std::unique_lock<std::mutex> ql(s->i8_enqueue_mu);   // (this batch's launches go onto the stream as one block)
-    HIP_TRY(hipStreamWaitEvent(s->stream, hs->in_ev, 0));
-    if ((rc = flat_pass8(s, n_pub, set, s->stream, n_queries, hs->dq.p, k, d_ids, d_dist, d_cnt, false, &kprime_used))) return rc;
-    HIP_TRY(hipMemcpyAsync(sc.buf.hUncertPin.p, sc.buf.dUncert.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipEventRecord(sc.buf.verdict, s->stream));
-    ql.unlock();
+    if ((rc = i8_stage_enqueue(s, n_pub, set, s->stream, hs->in_ev, true, n_queries, hs->dq.p, k, d_ids, d_dist, d_cnt, &o))) return rc;
     // the results start their way back NOW, before the verdict is known (it is clean for all but a few batches in a
     // thousand): one host wait per batch instead of two in a row — verdict, then copy.  A batch that did lose queries runs
     // the rest of the chain below and copies again (same slot stream: in order, the later copy wins).
     // (it waits for the verdict's event — recorded right behind the re-rank and the 8-byte verdict copy; a marker of its own
     // cost the queue another ~6 us per batch)
-    HIP_TRY(hipStreamWaitEvent(hs->st, sc.buf.verdict, 0));
+    HIP_TRY(hipStreamWaitEvent(hs->st, sc.buf.verdict.ev, 0));
     HIP_TRY(hipMemcpyAsync(hs->pin.p + qbytes, hs->dout.p, out_bytes, hipMemcpyDeviceToHost, hs->st));
-    copied_early = true;
-    HIP_TRY(hipEventSynchronize(sc.buf.verdict));
-    count_scan_batch(s, n_queries, n_pub, k, 1);
-    if (*sc.buf.hUncertPin.p == 0) {
-      done = true;
-      s->n_i8_queries += n_queries;
-      i8_adapt(s, n_queries, 0, 0, kprime_used);   // a clean batch: the score decays
-    } else {  // which queries, and why: the engine chain continues with them (below, under the pipeline lock)
-      HIP_TRY(hipMemsetAsync(sc.buf.dUncert.p, 0, sizeof(unsigned long long), s->stream));
-      if ((rc = collect_uncertified(s->stream, sc.buf.dUflags.p, n_queries, nullptr, &failed, &n_short))) return rc;
-      have_failed = true;
-    }
+    HIP_TRY(hipEventSynchronize(sc.buf.verdict.ev));
+    if ((rc = i8_stage_outcome(s, n_pub, set, s->stream, n_queries, k, &o))) return rc;
+    done = o.failed.empty();
   }
-  if (!done) {
+  if (!done) {  // the whole chain, or what is left of it for the queries the stage above lost: under the pipeline lock
     std::lock_guard<std::mutex> sl2(s->scratch_mu);
     HIP_TRY(hipStreamWaitEvent(s->stream, hs->in_ev, 0));
-    if ((rc = knn_device_locked(s, s->stream, n_queries, hs->dq.p, k, d_ids, d_dist, d_cnt, have_failed ? &failed : nullptr,
-                                n_short, kprime_used, n_pub)))
-      return rc;
+    if (pipelined) rc = flat_chain_rest(s, s->stream, n_pub, n_queries, hs->dq.p, k, d_ids, d_dist, d_cnt, EHX_ENGINE_I8, &o);
+    else rc = knn_device_locked(s, s->stream, n_queries, hs->dq.p, k, d_ids, d_dist, d_cnt, n_pub);
+    if (rc) return rc;
     HIP_TRY(hipEventRecord(hs->done_ev, s->stream));
   }
   char* ho = hs->pin.p + qbytes;
-  if (!(done && copied_early)) {
+  if (!done) {
     HIP_TRY(hipStreamWaitEvent(hs->st, hs->done_ev, 0));
     HIP_TRY(hipMemcpyAsync(ho, hs->dout.p, out_bytes, hipMemcpyDeviceToHost, hs->st));
   }

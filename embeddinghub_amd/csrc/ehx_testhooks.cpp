@@ -125,7 +125,7 @@ int ehx_test_i8_pass(ehx_space* s, uint32_t nq, const float* queries, const floa
                                    dCtl.p, st));
     // ... then the caller's thresholds
     if (thr) HIP_TRY(hipMemcpyAsync(dThr.p, thr, (size_t)nq * sizeof(float), hipMemcpyHostToDevice, st));
-    i8_scan_pass(a, p, tile0);
+    set_scan_pass(a, p, tile0);
     a.dump = thr ? nullptr : dDump.p;
     a.sync = nullptr;
     if (thr && env().i8_sync > 0 && p.xcd_map && p.q_tiles > 1 && p.tiles_per_chunk >= 4 && p.n_chunks * 4u <= kSyncWordsI8) {

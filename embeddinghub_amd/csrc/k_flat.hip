@@ -18,11 +18,6 @@ namespace ehx {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// the fp32 scan publishes two sorted key lists per (query, chunk): one per wave row of the 8-wave kernel (k_flat8.hip)
-uint32_t scan_lists_per_chunk() { return 2u; }
-
-hipError_t launch_flat_scan(const ScanArgs& a, hipStream_t st) { return launch_flat_scan8(a, st); }
-
 // ---------------------------------------------------------------------------------------------
 // merge of the per-chunk sorted key lists: one wave per query
 // ---------------------------------------------------------------------------------------------
@@ -82,19 +77,6 @@ __global__ __launch_bounds__(64) void sample_select_kernel(const float* __restri
 hipError_t launch_sample_select(const float* scores, uint32_t n_rows, uint32_t q_rows, uint32_t nq, uint32_t kprime,
                                 unsigned long long* gthr, hipStream_t st) {
   hipLaunchKernelGGL(sample_select_kernel, dim3(nq), dim3(64), 0, st, scores, n_rows, q_rows, kprime, gthr);
-  return hipGetLastError();
-}
-
-// after the sample pass: the k'-th best key of the merged sample lists is an upper bound of the
-// query's global k'-th best -> initial threshold of the main pass
-__global__ __launch_bounds__(256) void set_gthr_kernel(const uint64_t* __restrict__ merged, uint32_t nq, uint32_t kprime,
-                                                       unsigned long long* __restrict__ gthr) {
-  const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
-  if (q < nq) gthr[q] = merged[(size_t)q * 64 + kprime - 1];
-}
-
-hipError_t launch_set_gthr(const uint64_t* merged, uint32_t nq, uint32_t kprime, unsigned long long* gthr, hipStream_t st) {
-  hipLaunchKernelGGL(set_gthr_kernel, dim3((nq + 255) / 256), dim3(256), 0, st, merged, nq, kprime, gthr);
   return hipGetLastError();
 }
 

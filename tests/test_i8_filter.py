@@ -97,12 +97,9 @@ def test_i8_heterogeneous_rows(em, om):
     s.drop()
 
 
-@pytest.mark.parametrize("em,om", [METRICS[0], METRICS[2]])
-def test_i8_adversarial_row_order_overflows_the_pool_and_stays_exact(em, om):
-    """rows ordered from far to near for a group of queries: every row beats the threshold the earlier rows left, the
-    pools of those queries overflow, and the next engine answers them — exactly"""
+def _far_to_near(n, d):
+    """n rows that lie closer and closer to a point c, and 40 queries, the first 20 of them at c"""
     rng = np.random.default_rng(9)
-    n, d, k = 60000, 256, 10
     c = rng.standard_normal(d).astype(np.float32)
     c /= np.linalg.norm(c)
     noise = rng.standard_normal((n, d)).astype(np.float32)
@@ -111,6 +108,15 @@ def test_i8_adversarial_row_order_overflows_the_pool_and_stays_exact(em, om):
     X = (w * c[None, :] + (1 - w) * noise).astype(np.float32)
     Q = rng.standard_normal((40, d)).astype(np.float32)
     Q[:20] = c[None, :] + np.float32(0.01) * rng.standard_normal((20, d)).astype(np.float32)
+    return X, Q
+
+
+@pytest.mark.parametrize("em,om", [METRICS[0], METRICS[2]])
+def test_i8_adversarial_row_order_overflows_the_pool_and_stays_exact(em, om):
+    """rows ordered from far to near for a group of queries: every row beats the threshold the earlier rows left, the
+    pools of those queries overflow, and the next engine answers them — exactly"""
+    n, d, k = 60000, 256, 10
+    X, Q = _far_to_near(n, d)
     s = _space(d, em, n)
     for i0 in range(0, n, 16384):
         s.set_batch(_keys(n)[i0:i0 + 16384], X[i0:i0 + 16384])
@@ -121,6 +127,55 @@ def test_i8_adversarial_row_order_overflows_the_pool_and_stays_exact(em, om):
     assert st["n_i8_queries"] == 40
     assert st["n_i8_fallback"] >= 20, "the adversarial queries were expected to overflow their pools: %r" % (st,)
     s.drop()
+
+
+CHAIN_COUNTERS = ("n_queries", "n_i8_queries", "n_i8_fallback", "n_filter_queries", "n_filter_fallback", "n_exhaustive",
+                  "n_rerank")
+
+
+@pytest.mark.parametrize("em,om", [METRICS[0], METRICS[2]])
+def test_host_and_device_calls_run_one_chain(em, om):
+    """ehx_knn's pipelined int8 stage and ehx_knn_device are one engine chain: a batch that loses queries to the next
+    engines (the far-to-near rows above, at a row count just over the int8 engine's floor) gets the same bytes and
+    leaves the same counters behind, whichever entry point ran it"""
+    import torch
+    n, d, k = 20000, 256, 10
+    X, Q = _far_to_near(n, d)
+    oids, odist, ocnt = pyoracle.exhaustive(X, Q, k, om)
+    assert (ocnt == k).all()
+
+    def fresh():
+        s = _space(d, em, n)
+        for i0 in range(0, n, 16384):
+            s.set_batch(_keys(n)[i0:i0 + 16384], X[i0:i0 + 16384])
+        assert s.scan_engine() == "i8"
+        s.stats_reset()
+        return s
+
+    host = fresh()
+    h_ids, h_dist, h_cnt = host.knn(Q, k)       # 40 queries x 256 floats: a host slot, the pipelined int8 stage
+    h_st = host.stats()
+    host.drop()
+    dev = fresh()
+    ids = torch.empty((40, k), dtype=torch.int64, device="cuda")
+    dst = torch.empty((40, k), dtype=torch.float32, device="cuda")
+    cnt = torch.empty((40,), dtype=torch.int32, device="cuda")
+    dev.knn_device(torch.from_numpy(Q).cuda(), k, ids, dst, cnt, stream=torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    d_st = dev.stats()
+    dev.drop()
+    d_ids, d_dist, d_cnt = ids.cpu().numpy().astype(np.uint64), dst.cpu().numpy(), cnt.cpu().numpy().astype(np.uint32)
+    print("host  ", {c: h_st[c] for c in CHAIN_COUNTERS})
+    print("device", {c: d_st[c] for c in CHAIN_COUNTERS})
+    for got_ids, got_dist, got_cnt in ((h_ids, h_dist, h_cnt), (d_ids, d_dist, d_cnt)):
+        np.testing.assert_array_equal(got_cnt, ocnt)
+        np.testing.assert_array_equal(got_ids, oids)
+        assert got_dist.tobytes() == odist.tobytes()
+    assert h_ids.tobytes() == d_ids.tobytes() and h_dist.tobytes() == d_dist.tobytes()
+    for c in CHAIN_COUNTERS:
+        assert h_st[c] == d_st[c], (c, h_st, d_st)
+    assert h_st["n_uncertified"] == 0 and d_st["n_uncertified"] == 0
+    assert h_st["n_i8_fallback"] >= 20, "the adversarial queries were expected to overflow their pools: %r" % (h_st,)
 
 
 def test_i8_growth_updates_and_fp16_rows():
