@@ -34,21 +34,6 @@ std::vector<ScanPass> plan_cascade(uint32_t nq, uint32_t n_tiles, uint32_t k, in
   return passes;
 }
 
-// what the fp32 and the fp16 scan's arguments share: the candidate slots and list slots of the batch, its error word and
-// thresholds (every pass writes its lists from slot 0)
-template <class Args>
-static void scan_args_shared(Args& a, ehx_space* s, const ScanPlan& p, uint32_t lists_total, uint64_t n_pub) {
-  a.cand = s->scr.dCand.p;
-  a.part = s->scr.dPart.p;
-  a.n = (uint32_t)n_pub;
-  a.q_tiles = p.q_tiles;
-  a.kprime = p.kprime;
-  a.list0 = 0;
-  a.lists_total = lists_total;
-  a.err = s->scr.dScanErr.p;
-  a.gthr = (unsigned long long*)s->scr.dGthr.p;
-}
-
 // one flat pipeline: prepared queries -> scan -> merge -> canonical re-rank.
 //   f16 = false: the fp32 MFMA scan (k_flat8.hip), exact on its own.
 //   f16 = true : the fp16 MFMA filter scan (k_flat16.hip); per-query certification flags land in
@@ -147,7 +132,7 @@ static int flat_pass(ehx_space* s, uint64_t n_pub, hipStream_t st, size_t nq, co
     if ((rc = clock.scan_begin(st))) return rc;
     if (f16) {
       ScanArgs16 h;
-      scan_args_shared(h, s, p, lists_total, n_pub);
+      scan_args_shared(h, s->scr.dCand.p, s->scr.dPart.p, s->scr.dScanErr.p, s->scr.dGthr.p, p, lists_total, n_pub);
       h.Q = s->scr.dQ16.p;
       h.X = s->f16.dX16.p;
       h.rowp = s->f16.dRowp16.p;
@@ -167,7 +152,7 @@ static int flat_pass(ehx_space* s, uint64_t n_pub, hipStream_t st, size_t nq, co
       if ((rc = cascade(h, launch_flat_scan16))) return rc;
     } else {
       ScanArgs a;
-      scan_args_shared(a, s, p, lists_total, n_pub);
+      scan_args_shared(a, s->scr.dCand.p, s->scr.dPart.p, s->scr.dScanErr.p, s->scr.dGthr.p, p, lists_total, n_pub);
       a.Q = s->scr.dQ.p;
       a.X = s->rows.dX.p;
       a.x_half = (uint32_t)s->x_half;

@@ -321,7 +321,7 @@ struct ehx_space {
   bool has16 = false;          // the space keeps the fp16 scan copy (maintained on every write, whatever engine scans)
   struct Scan16 {
     DevBuf<__half> dX16;       // [cap][ld16] in the stage-blocked scan16_index layout
-    DevBuf<float2> dRowp16;    // [cap]
+    DevBuf<float2> dRowp16;    // [cap + 512] (two tiles of tail padding: the scan's row parameters are fetched two tiles ahead)
     DevBuf<unsigned long long> dUnsafe;  // rows the filter cannot bound (then every scan is the fp32 scan)
   } f16;
   uint32_t ld16 = 0;
@@ -607,6 +607,21 @@ inline void set_scan_pass(Args& a, const ScanPlan& pl, uint32_t tile0) {
   a.n_chunks = pl.n_chunks;
   a.tiles_per_chunk = pl.tiles_per_chunk;
   a.xcd_map = pl.xcd_map;
+}
+// what the fp32 and the fp16 scan's arguments share: the candidate slots and list slots of the batch, its error word and
+// thresholds (every pass writes its lists from slot 0)
+template <class Args>
+inline void scan_args_shared(Args& a, uint64_t* cand, uint64_t* part, uint32_t* err, uint64_t* gthr, const ScanPlan& p,
+                             uint32_t lists_total, uint64_t n_pub) {
+  a.cand = cand;
+  a.part = part;
+  a.n = (uint32_t)n_pub;
+  a.q_tiles = p.q_tiles;
+  a.kprime = p.kprime;
+  a.list0 = 0;
+  a.lists_total = lists_total;
+  a.err = err;
+  a.gthr = (unsigned long long*)gthr;
 }
 constexpr uint64_t kNoSnapshot = ~0ull;   // knn_device_locked: no snapshot of the row count yet, take one
 int resolve_engine(const ehx_space* s, uint64_t n_pub);

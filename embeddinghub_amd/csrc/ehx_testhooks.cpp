@@ -3,7 +3,14 @@
 //   ehx_test_i8_pass    ONE launch of flat_scan_i8_kernel over a window of tiles with the arguments a search would give
 //                       it: the sample form (every lower bound of the window) or a collect pass under the caller's
 //                       thresholds (the pools as the pass left them, before select256 and the re-rank reduce them)
-// tests/test_i8_device_bound.py checks the scan copy, the bound and the hit path on them.  No production path calls in here.
+// tests/test_i8_device_bound.py checks the scan copy, the bound and the hit path on them.
+// ... and of the fp16 filter scan and the fp32 scan, which share the candidate-list path (k_scan_common.h):
+//   ehx_test_f16_array  a slice of one array of the fp16 scan copy, raw
+//   ehx_test_f16_pass   ONE launch of flat_scan16_kernel: the sample form (the dump, and what sample_select makes of it) or a
+//                       collect pass under the caller's 64-bit threshold keys (the lists as the pass published them, then
+//                       flat_merge_kernel's view of them)
+//   ehx_test_f32_pass   the collect form for flat_scan8_kernel
+// tests/test_f16_device_bound.py checks them.  No production path calls in here.
 #include "ehx_internal.h"
 
 namespace {
@@ -11,13 +18,14 @@ namespace {
 enum { kArrX8, kArrRowp8, kArrTilep8, kArrTileg8, kArrPerm8, kArrUnsafe8, kArrLd8, kArrCap };
 constexpr uint32_t kSampleTiles = 8;   // the sample pass's window (flat_pass8)
 
-int hook_space(ehx_space* s, const char* what) {
+int hook_space(ehx_space* s, const char* what, int need = 8) {
   int rc = ehx_init(nullptr, 0);
   if (rc) return rc;
   if (!valid_space(s)) return fail(EHX_EINVAL, "space is NULL");
   if (s->dropped) return fail(EHX_ENOTFOUND, "Not found");
   if (is_parent(s)) return fail(EHX_EUNSUPPORTED, "%s: space '%s' is row-sharded", what, s->name.c_str());
-  if (!s->has8) return fail(EHX_EUNSUPPORTED, "%s: space '%s' keeps no int8 scan copy", what, s->name.c_str());
+  if (need == 8 && !s->has8) return fail(EHX_EUNSUPPORTED, "%s: space '%s' keeps no int8 scan copy", what, s->name.c_str());
+  if (need == 16 && !s->has16) return fail(EHX_EUNSUPPORTED, "%s: space '%s' keeps no fp16 scan copy", what, s->name.c_str());
   return EHX_OK;
 }
 
@@ -28,6 +36,131 @@ int copy_slice(ehx_space* s, const ehx_impl::DevBuf<T>& b, uint64_t off, uint64_
   if (n == 0) return EHX_OK;
   HIP_TRY(hipMemcpyAsync(out, b.p + off, n * sizeof(T), hipMemcpyDeviceToHost, st));
   return sync_stream(s, st);
+}
+
+enum { kArrX16, kArrRowp16, kArrUnsafe16, kArrLd16, kArrCap16 };
+
+// ONE launch of flat_scan16_kernel (F16) or flat_scan8_kernel over tiles [tile0, +n_tiles), arguments as flat_pass fills them,
+// on scratch of this call alone.  keys == NULL (F16 only): the sample form.
+template <bool F16>
+int list_pass(ehx_space* s, const char* what, uint32_t nq, const float* queries, uint32_t kprime, const uint64_t* keys,
+              uint32_t tile0, uint32_t n_tiles, float* out_dump, uint64_t* out_gthr, uint64_t* out_part, uint32_t* out_err,
+              uint64_t* out_merged, uint16_t* out_q16, float* out_qgamma, float* out_quv, uint32_t* out_info) {
+  int rc = hook_space(s, what, F16 ? 16 : 0);
+  if (rc) return rc;
+  if (s->params.mode != EHX_MODE_FLAT) return fail(EHX_EUNSUPPORTED, "%s: space '%s' is not a flat space", what, s->name.c_str());
+  if (!queries || !out_gthr || !out_info) return fail(EHX_EINVAL, "NULL argument");
+  if (F16 && (!out_q16 || !out_qgamma || !out_quv)) return fail(EHX_EINVAL, "NULL argument");
+  if (keys ? (!out_part || !out_err || !out_merged) : !out_dump) return fail(EHX_EINVAL, "NULL argument");
+  if (nq == 0 || nq > 4 * kTileQ) return fail(EHX_EINVAL, "nq=%u outside [1, %u]", nq, 4 * kTileQ);
+  if (kprime == 0 || kprime > 56) return fail(EHX_EINVAL, "k'=%u outside [1, 56]", kprime);
+  if (!keys && n_tiles != kSampleTiles) return fail(EHX_EINVAL, "the sample form scans %u tiles", kSampleTiles);
+  constexpr uint32_t tile_rows = F16 ? kTileRows16 : kTileRows;
+  yield_to_writer(s);
+  std::shared_lock<std::shared_mutex> rl(s->mu);
+  if (s->dropped) return fail(EHX_ENOTFOUND, "Not found");
+  // (the window may reach beyond the published rows, never beyond the arrays: the scan reads whole tiles)
+  if (n_tiles == 0 || (uint64_t)tile0 + n_tiles > s->cap / tile_rows)
+    return fail(EHX_EINVAL, "tiles [%u, +%u) of a space of %llu", tile0, n_tiles, (unsigned long long)(s->cap / tile_rows));
+  std::lock_guard<std::mutex> sl(s->scratch_mu);
+  HIP_TRY(hipSetDevice(s->device));
+  Engine& E = engine();
+  const hipStream_t st = s->stream;
+  const uint64_t n_pub = s->n.load(std::memory_order_acquire);
+  ScanPlan p = plan_scan(nq, n_tiles, 1, E.n_cus);
+  p.kprime = kprime;
+  constexpr uint32_t lpc = kScanListsPerChunk;
+  const uint32_t lists_total = p.n_chunks * lpc;
+  // scratch of this call alone (owners: freed on every return)
+  DevBuf<float> dQraw, dQ, dQgamma, dDump;
+  DevBuf<__half> dQ16;
+  DevBuf<float2> dQuv;
+  DevBuf<uint64_t> dCand, dPart, dMerged, dGthr;
+  DevBuf<uint32_t> dErr;
+  const size_t q16_halves = F16 ? scanq16_halves(p.q_rows, s->ld16) : 0;
+  const size_t dump_elems = (size_t)kSampleTiles * kTileRows16 * p.q_rows;
+  const size_t part_elems = (size_t)p.q_rows * lists_total * kprime;
+  if ((rc = dQraw.ensure((size_t)nq * s->dims)) || (rc = dCand.ensure((size_t)p.grid * 512 * kCandSlots)) ||
+      (rc = dPart.ensure(part_elems)) || (rc = dMerged.ensure((size_t)p.q_rows * 64)) ||
+      (rc = dGthr.ensure((size_t)p.q_rows + 8)) || (rc = dErr.ensure(1)))
+    return rc;
+  if (F16 ? ((rc = dQ16.ensure(q16_halves)) || (rc = dQgamma.ensure(p.q_rows)) || (rc = dQuv.ensure(p.q_rows)))
+          : (rc = dQ.ensure((size_t)p.q_rows * s->ld)))
+    return rc;
+  if (!keys && (rc = dDump.ensure(dump_elems))) return rc;
+  const float eps = scan16_eps(s->dims);
+  auto run = [&]() -> int {
+    int r;
+    HIP_TRY(hipMemcpyAsync(dQraw.p, queries, (size_t)nq * s->dims * sizeof(float), hipMemcpyHostToDevice, st));
+    if ((r = wait_searches_in_flight(s, st))) return r;
+    if ((r = s->clock.begin(st, BatchClock::kOutOfRing))) return r;
+    HIP_TRY(hipMemsetAsync(dErr.p, 0, sizeof(uint32_t), st));
+    HIP_TRY(hipMemsetAsync(dPart.p, 0xFF, part_elems * sizeof(uint64_t), st));   // (chunks with no tiles publish empty lists)
+    HIP_TRY(hipMemsetAsync(dGthr.p, 0xFF, ((size_t)p.q_rows + 8) * sizeof(uint64_t), st));
+    if (keys) HIP_TRY(hipMemcpyAsync(dGthr.p, keys, (size_t)nq * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    if ((r = s->clock.scan_begin(st))) return r;
+    if constexpr (F16) {
+      HIP_TRY(launch_prep_queries16(dQraw.p, nq, s->dims, s->ld16, p.q_rows, s->metric, dQ16.p, dQgamma.p, dQuv.p, st));
+      ScanArgs16 h;
+      scan_args_shared(h, dCand.p, dPart.p, dErr.p, dGthr.p, p, lists_total, n_pub);
+      h.Q = dQ16.p;
+      h.X = s->f16.dX16.p;
+      h.rowp = s->f16.dRowp16.p;
+      h.qgamma = dQgamma.p;
+      h.eps = eps;
+      h.cos = s->metric == EHX_METRIC_COSINE;
+      h.ld = s->ld16;
+      set_scan_pass(h, p, tile0);
+      h.dump = keys ? nullptr : dDump.p;
+      HIP_TRY(launch_flat_scan16(h, st));
+      if (!keys)
+        HIP_TRY(launch_sample_select(dDump.p, kSampleTiles * kTileRows16, p.q_rows, nq, kprime, (unsigned long long*)dGthr.p, st));
+    } else {
+      HIP_TRY(launch_prep_queries(dQraw.p, nq, s->dims, s->ld, p.q_rows, s->metric, dQ.p, st));
+      ScanArgs a;
+      scan_args_shared(a, dCand.p, dPart.p, dErr.p, dGthr.p, p, lists_total, n_pub);
+      a.Q = dQ.p;
+      a.X = s->rows.dX.p;
+      a.x_half = (uint32_t)s->x_half;
+      a.rowp = s->rows.dRowp.p;
+      a.ld = s->ld;
+      set_scan_pass(a, p, tile0);
+      HIP_TRY(launch_flat_scan8(a, st));
+    }
+    if ((r = s->clock.scan_end(st))) return r;
+    if (keys) {
+      HIP_TRY(hipMemcpyAsync(out_err, dErr.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipMemcpyAsync(out_part, dPart.p, (size_t)nq * lists_total * kprime * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+      HIP_TRY(launch_flat_merge(dPart.p, nq, lists_total, kprime, dMerged.p, st, lists_total, false, (unsigned long long*)dGthr.p));
+      HIP_TRY(hipMemcpyAsync(out_merged, dMerged.p, (size_t)nq * 64 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    } else {
+      HIP_TRY(hipMemcpyAsync(out_dump, dDump.p, dump_elems * sizeof(float), hipMemcpyDeviceToHost, st));
+    }
+    if ((r = s->clock.finish(st))) return r;
+    HIP_TRY(hipMemcpyAsync(out_gthr, dGthr.p, (size_t)nq * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    if (F16) {
+      HIP_TRY(hipMemcpyAsync(out_q16, dQ16.p, q16_halves * sizeof(__half), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipMemcpyAsync(out_qgamma, dQgamma.p, (size_t)p.q_rows * sizeof(float), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipMemcpyAsync(out_quv, dQuv.p, (size_t)p.q_rows * sizeof(float2), hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    return EHX_OK;
+  };
+  rc = run();
+  if (rc) {  // launches of this call may still be in flight: drain them before the scratch is freed
+    (void)hipStreamSynchronize(st);
+    (void)hipGetLastError();
+    return rc;
+  }
+  out_info[0] = p.q_rows;
+  out_info[1] = F16 ? s->ld16 : s->ld;
+  out_info[2] = p.n_chunks;
+  out_info[3] = p.tiles_per_chunk;
+  out_info[4] = p.xcd_map;
+  out_info[5] = (uint32_t)n_pub;
+  memcpy(&out_info[6], &eps, sizeof(float));
+  out_info[7] = lists_total;
+  return EHX_OK;
 }
 
 }  // namespace
@@ -174,6 +307,62 @@ int ehx_test_i8_pass(ehx_space* s, uint32_t nq, const float* queries, const floa
     }
   }
   return EHX_OK;
+}
+
+// which: 0 X16 (binary16 as u16, the three blocks of tail padding included) | 1 rowp16 (float, two per row, cap + 512 rows)
+// | 2 the unsafe-row counter (u64) | 3 ld16 | 4 cap (one u64 each); offset and length in those elements
+int ehx_test_f16_array(ehx_space* s, int which, uint64_t elem_offset, uint64_t n_elems, void* out) {
+  int rc = hook_space(s, "ehx_test_f16_array", 16);
+  if (rc) return rc;
+  if (!out && n_elems) return fail(EHX_EINVAL, "NULL argument");
+  std::lock_guard<std::mutex> wl(s->wmu);   // (as ehx_test_i8_array)
+  std::shared_lock<std::shared_mutex> rl(s->mu);
+  if (s->dropped) return fail(EHX_ENOTFOUND, "Not found");
+  HIP_TRY(hipSetDevice(s->device));
+  const hipStream_t ws = s->wr.wstream ? (hipStream_t)s->wr.wstream : (hipStream_t)s->stream;
+  if ((rc = sync_stream(s, ws)) || (rc = sync_stream(s, s->stream))) return rc;
+  switch (which) {
+    case kArrX16: return copy_slice(s, s->f16.dX16, elem_offset, n_elems, out, ws);
+    case kArrUnsafe16: return copy_slice(s, s->f16.dUnsafe, elem_offset, n_elems, out, ws);
+    case kArrRowp16: {
+      const DevBuf<float2>& b = s->f16.dRowp16;
+      if (elem_offset > b.n * 2 || n_elems > b.n * 2 - elem_offset) return fail(EHX_EINVAL, "slice beyond the array");
+      if (n_elems == 0) return EHX_OK;
+      HIP_TRY(hipMemcpyAsync(out, (const float*)b.p + elem_offset, n_elems * sizeof(float), hipMemcpyDeviceToHost, ws));
+      return sync_stream(s, ws);
+    }
+    case kArrLd16:
+    case kArrCap16:
+      if (elem_offset != 0 || n_elems != 1) return fail(EHX_EINVAL, "a scalar: offset 0, one element");
+      *(uint64_t*)out = which == kArrLd16 ? (uint64_t)s->ld16 : s->cap;
+      return EHX_OK;
+  }
+  return fail(EHX_EINVAL, "unknown array %d", which);
+}
+
+// queries [nq][dims] and gthr_keys [nq] (or NULL) are host pointers, as are the outputs (those of the other form may be NULL):
+//   gthr_keys == NULL (n_tiles must be 8): out_dump[8 * 256][q_rows], out_gthr[nq] = what sample_select makes of it for k'
+//   gthr_keys != NULL: out_part[nq][lists][k'] as the pass published them (lists = 2 n_chunks = info[7], list = 2 chunk + wr;
+//                      lists <= 2 n_tiles), out_err[1]; then, after flat_merge_kernel on the same stream: out_merged[nq][64]
+//                      and out_gthr[nq], the threshold the merge hands to the next pass
+//   both: out_q16[scanq16_halves(q_rows, ld16)] raw, out_qgamma[q_rows], out_quv[q_rows][2] (the padding queries included),
+//         out_info[8] = q_rows, ld16, n_chunks, tiles_per_chunk, xcd_map, published rows, eps (float bits), lists
+int ehx_test_f16_pass(ehx_space* s, uint32_t nq, const float* queries, uint32_t kprime, const uint64_t* gthr_keys,
+                      uint32_t tile0, uint32_t n_tiles, float* out_dump, uint64_t* out_gthr, uint64_t* out_part,
+                      uint32_t* out_err, uint64_t* out_merged, uint16_t* out_q16, float* out_qgamma, float* out_quv,
+                      uint32_t* out_info) {
+  return list_pass<true>(s, "ehx_test_f16_pass", nq, queries, kprime, gthr_keys, tile0, n_tiles, out_dump, out_gthr, out_part,
+                         out_err, out_merged, out_q16, out_qgamma, out_quv, out_info);
+}
+
+// the collect form for flat_scan8_kernel, arguments as flat_pass sets them for the fp32 scan; tiles of kTileRows = 128 rows,
+// list = 2 chunk + wr covers rows wr * 64 .. wr * 64 + 63 of each of the chunk's tiles; info[1] = ld, info[6] unused
+int ehx_test_f32_pass(ehx_space* s, uint32_t nq, const float* queries, uint32_t kprime, const uint64_t* gthr_keys,
+                      uint32_t tile0, uint32_t n_tiles, uint64_t* out_gthr, uint64_t* out_part, uint32_t* out_err,
+                      uint64_t* out_merged, uint32_t* out_info) {
+  if (!gthr_keys) return fail(EHX_EINVAL, "NULL argument");
+  return list_pass<false>(s, "ehx_test_f32_pass", nq, queries, kprime, gthr_keys, tile0, n_tiles, nullptr, out_gthr, out_part,
+                          out_err, out_merged, nullptr, nullptr, nullptr, out_info);
 }
 
 // how many ehx_knn calls the one-launch kernels answered (single_query_kernel, the graph search's one-launch form)

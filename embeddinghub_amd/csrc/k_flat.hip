@@ -23,7 +23,9 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // ---------------------------------------------------------------------------------------------
 // seed != 0: `merged` already holds the 64 best keys of earlier passes and is merged with the new lists.
 // gthr != nullptr: also publish the k'-th best key so far (an upper bound of the query's final k'-th
-// best) as the threshold the next scan pass starts from.
+// best) as the threshold the next scan pass starts from; while fewer than k' keys are known the threshold
+// stays what it was (the value the pass ran under, or what its lists lowered it to: either bounds the final
+// k'-th best from above, "no bound" would only be looser).
 __global__ __launch_bounds__(64) void flat_merge_kernel(const uint64_t* __restrict__ part, uint32_t n_chunks,
                                                         uint32_t kprime, uint64_t* __restrict__ merged,
                                                         uint32_t lists_stride, uint32_t seed,
@@ -50,7 +52,7 @@ __global__ __launch_bounds__(64) void flat_merge_kernel(const uint64_t* __restri
     }
   }
   merged[(size_t)q * 64 + lane] = best;
-  if (gthr && lane == (int)kprime - 1) gthr[q] = best;
+  if (gthr && lane == (int)kprime - 1 && best != kKeyInf) gthr[q] = best;
 }
 
 // sample pass of the fp16 filter scan: scores[row][q] of the first n_rows rows -> gthr[q] = the kprime-th
