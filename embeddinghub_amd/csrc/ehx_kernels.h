@@ -38,10 +38,6 @@ __host__ __device__ inline float ordered_to_f32(uint32_t o) {
 #endif
 }
 
-// Exactly-rounded single operations for the canonical (oracle-order) arithmetic.  HIP's
-// __fmul_rn/__fadd_rn are plain * and + (contractible) and __fsqrt_rn is the approximate native
-// sqrt, so they are NOT used; the library is built with -ffp-contract=off and relies on hipcc's
-// default -fhip-fp32-correctly-rounded-divide-sqrt for / and sqrt.
 // LDS hand-over between the lanes of ONE wave (kernels launched with 64 threads per workgroup): the LDS accesses of
 // a wave execute in program order, so a compiler-level fence is all a write -> read across lanes needs — no
 // s_barrier and no drain of the LDS queue, which __syncthreads() would put on the dependent chain
@@ -99,12 +95,6 @@ __device__ __forceinline__ uint32_t lower_bound_lds(const uint64_t* a, uint32_t 
   return lo;
 }
 
-__device__ __forceinline__ float ex_add(float a, float b) { return a + b; }
-__device__ __forceinline__ float ex_sub(float a, float b) { return a - b; }
-__device__ __forceinline__ float ex_mul(float a, float b) { return a * b; }
-__device__ __forceinline__ float ex_div(float a, float b) { return a / b; }
-__device__ __forceinline__ float ex_sqrt(float a) { return __builtin_sqrtf(a); }
-
 // Certification margin of the re-rank (rerank_kernel*): an upper bound of
 //     | scan score of a row  -  that row's canonical (oracle-order) distance |
 // for EVERY row of the space, so that  "worst kept score - margin > exact k-th distance"  proves that no
@@ -144,462 +134,9 @@ __device__ __forceinline__ float i8_group_b_margin(float bg, float bt) {
   return m > 0.0f ? m : 0.0f;
 }
 
-// Canonical distance between a prepared query and a stored row, in exactly the order of hnswlib's SSE
-// kernels (space_l2.h / space_ip.h; oracle/hnsw_oracle.hpp restates them): 4 strided partial sums
-// over the multiple-of-4 body (multiply and add NOT fused), horizontal sum t0+t1+t2+t3 left to
-// right, scalar tail added afterwards.  Executed by a 4-lane group: lane `sub` plays SSE lane `sub`;
-// all 4 lanes of the group must be active.  metric01: 0 = L2^2, 1 = 1 - inner product.  For cosine
-// the stored row is normalised on the fly (x * inv_norm, one rounding — hnswlib-python's
-// normalize_vector) and the query arrives normalised.  Result valid in sub-lane 0.
-// row element load: fp32 rows as stored, fp16 rows widened exactly (every half is a float)
-__device__ __forceinline__ float ld_row(const float* x, uint32_t m) { return x[m]; }
-__device__ __forceinline__ float ld_row(const __half* x, uint32_t m) { return __half2float(x[m]); }
-
-template <typename XT>
-__device__ __forceinline__ float canon_dist(int metric, const float* __restrict__ q,
-                                            const XT* __restrict__ x, float xscale, bool scale_x,
-                                            uint32_t dims, int sub) {
-  uint32_t body;
-  if ((dims & 15u) == 0 || (dims & 3u) == 0) body = dims;
-  else if (dims > 16) body = dims & ~15u;
-  else if (dims > 4) body = dims & ~3u;
-  else body = 0;
-  float part = 0.0f;
-  if (metric == 0) {
-    for (uint32_t m = sub; m < body; m += 4) {
-      const float xv = scale_x ? ex_mul(ld_row(x, m), xscale) : ld_row(x, m);
-      const float diff = ex_sub(q[m], xv);
-      part = ex_add(part, ex_mul(diff, diff));
-    }
-  } else {
-    for (uint32_t m = sub; m < body; m += 4) {
-      const float xv = scale_x ? ex_mul(ld_row(x, m), xscale) : ld_row(x, m);
-      part = ex_add(part, ex_mul(q[m], xv));
-    }
-  }
-  // horizontal sum in lane order within the 4-lane group
-  const float t1 = __shfl_down(part, 1, 4), t2 = __shfl_down(part, 2, 4), t3 = __shfl_down(part, 3, 4);
-  float res = ex_add(ex_add(ex_add(part, t1), t2), t3);
-  if (body != dims) {
-    float tail = 0.0f;
-    if (metric == 0) {
-      for (uint32_t m = body; m < dims; ++m) {
-        const float xv = scale_x ? ex_mul(ld_row(x, m), xscale) : ld_row(x, m);
-        const float diff = ex_sub(q[m], xv);
-        tail = ex_add(tail, ex_mul(diff, diff));
-      }
-    } else {
-      for (uint32_t m = body; m < dims; ++m) {
-        const float xv = scale_x ? ex_mul(ld_row(x, m), xscale) : ld_row(x, m);
-        tail = ex_add(tail, ex_mul(q[m], xv));
-      }
-    }
-    if (metric != 0 && body) {
-      // hnswlib 0.5.x residual variants of the inner product: both halves are already distances (1 - sum) and are
-      // combined as  res + res_tail - 1.0f  (space_ip.h; oracle/hnsw_oracle.hpp:ip_dist)
-      return ex_sub(ex_add(ex_sub(1.0f, res), ex_sub(1.0f, tail)), 1.0f);
-    }
-    res = body ? ex_add(res, tail) : tail;
-  }
-  if (metric != 0) res = ex_sub(1.0f, res);
-  return res;  // valid in sub-lane 0
-}
-
-// Same canonical arithmetic executed by ONE lane: the lane keeps the 4 SSE partial sums itself and
-// walks its row with 16-byte loads (q may live in LDS).  Used by the graph search and the graph
-// insertion, where every lane owns one neighbour row.  Requires 16-byte aligned q and x (row stride
-// ld % 4 == 0).
-//
-// The walk is HBM-latency bound unless many loads are in flight per lane (a row is ld*4 contiguous
-// bytes = ld/32 cache lines that nobody else touches; the plain loop compiles to ONE 16-byte load in
-// flight per lane): the body is cut into blocks of kLaneBlk 16-byte loads and a ring of three
-// register blocks keeps two blocks in flight ahead of the block being accumulated.  Measured on the
-// graph bench (profiles/r01_m_*): 16-24 loads in flight per lane are enough — kLaneBlk 8 and 16 are
-// within 3 % of each other, 4 is 6 % slower at d=768 — because past that point the random row gathers
-// are bound by what the memory system delivers for this pattern (scripts/ubench/gather_rows.hip:
-// 27 lanes x private rows, 4 waves per CU: 4.2-4.5 TB/s; deeper queues thrash the 32-KiB L1).
-// The accumulation order is unchanged (block after block, 16 bytes after 16 bytes), so the result is
-// bit-identical to the plain loop.
-#ifndef EHX_LANE_BLK
-#define EHX_LANE_BLK 8
-#endif
-constexpr int kLaneBlk = EHX_LANE_BLK;  // 16-byte loads per ring block (8: 128 B = one cache line per lane)
-
-template <int METRIC01, bool SCALE>
-__device__ __forceinline__ void canon_lane_step(float4 xv, const float4 qv, float xscale, float& p0, float& p1,
-                                                float& p2, float& p3) {
-  if (SCALE) {
-    xv.x = ex_mul(xv.x, xscale);
-    xv.y = ex_mul(xv.y, xscale);
-    xv.z = ex_mul(xv.z, xscale);
-    xv.w = ex_mul(xv.w, xscale);
-  }
-  if (METRIC01 == 0) {
-    const float d0 = ex_sub(qv.x, xv.x), d1 = ex_sub(qv.y, xv.y), d2 = ex_sub(qv.z, xv.z), d3 = ex_sub(qv.w, xv.w);
-    p0 = ex_add(p0, ex_mul(d0, d0));
-    p1 = ex_add(p1, ex_mul(d1, d1));
-    p2 = ex_add(p2, ex_mul(d2, d2));
-    p3 = ex_add(p3, ex_mul(d3, d3));
-  } else {
-    p0 = ex_add(p0, ex_mul(qv.x, xv.x));
-    p1 = ex_add(p1, ex_mul(qv.y, xv.y));
-    p2 = ex_add(p2, ex_mul(qv.z, xv.z));
-    p3 = ex_add(p3, ex_mul(qv.w, xv.w));
-  }
-}
-
-template <int METRIC01, bool SCALE, bool RING = true>
-__device__ __forceinline__ float canon_dist_lane_t(const float* __restrict__ q, const float* __restrict__ x,
-                                                   float xscale, uint32_t dims) {
-  uint32_t body;
-  if ((dims & 15u) == 0 || (dims & 3u) == 0) body = dims;
-  else if (dims > 16) body = dims & ~15u;
-  else if (dims > 4) body = dims & ~3u;
-  else body = 0;
-  float p0 = 0.0f, p1 = 0.0f, p2 = 0.0f, p3 = 0.0f;
-  constexpr int BL = kLaneBlk;
-  const uint32_t nblk = RING ? body / (4u * BL) : 0u;  // !RING: few registers, four loads in flight
-  float4 r0[BL], r1[BL], r2[BL];
-  const float4* x4 = (const float4*)x;
-  const float4* q4 = (const float4*)q;
-#define EHX_LANE_LOAD(R, B)                                        \
-  _Pragma("unroll") for (int i_ = 0; i_ < BL; ++i_) R[i_] = x4[(size_t)(B) * BL + i_];
-#define EHX_LANE_ACC(R, B)                                         \
-  _Pragma("unroll") for (int i_ = 0; i_ < BL; ++i_)                \
-      canon_lane_step<METRIC01, SCALE>(R[i_], q4[(size_t)(B) * BL + i_], xscale, p0, p1, p2, p3);
-  uint32_t b = 0;
-  if (nblk >= 2) {
-    EHX_LANE_LOAD(r0, 0)
-    EHX_LANE_LOAD(r1, 1)
-    // steady state: three blocks accumulated per trip, every load two blocks ahead of its use, no branches
-    for (; b + 5 <= nblk; b += 3) {
-      EHX_LANE_LOAD(r2, b + 2)
-      EHX_LANE_ACC(r0, b)
-      EHX_LANE_LOAD(r0, b + 3)
-      EHX_LANE_ACC(r1, b + 1)
-      EHX_LANE_LOAD(r1, b + 4)
-      EHX_LANE_ACC(r2, b + 2)
-    }
-    const uint32_t rem = nblk - b;  // 2, 3 or 4 blocks left; r0 / r1 hold blocks b / b+1
-    if (rem >= 3) { EHX_LANE_LOAD(r2, b + 2) }
-    EHX_LANE_ACC(r0, b)
-    if (rem == 4) { EHX_LANE_LOAD(r0, b + 3) }
-    EHX_LANE_ACC(r1, b + 1)
-    if (rem >= 3) { EHX_LANE_ACC(r2, b + 2) }
-    if (rem == 4) { EHX_LANE_ACC(r0, b + 3) }
-  } else if (nblk == 1) {
-    EHX_LANE_LOAD(r0, 0)
-    EHX_LANE_ACC(r0, 0)
-  }
-#undef EHX_LANE_LOAD
-#undef EHX_LANE_ACC
-  // the 16-byte pieces after the last full block (fewer than kLaneBlk), four loads at a time
-  {
-    uint32_t m = nblk * BL;
-    const uint32_t m1 = body / 4u;
-    for (; m + 4 <= m1; m += 4) {
-      const float4 t0 = x4[m], t1 = x4[m + 1], t2 = x4[m + 2], t3 = x4[m + 3];
-      canon_lane_step<METRIC01, SCALE>(t0, q4[m], xscale, p0, p1, p2, p3);
-      canon_lane_step<METRIC01, SCALE>(t1, q4[m + 1], xscale, p0, p1, p2, p3);
-      canon_lane_step<METRIC01, SCALE>(t2, q4[m + 2], xscale, p0, p1, p2, p3);
-      canon_lane_step<METRIC01, SCALE>(t3, q4[m + 3], xscale, p0, p1, p2, p3);
-    }
-    for (; m < m1; ++m) canon_lane_step<METRIC01, SCALE>(x4[m], q4[m], xscale, p0, p1, p2, p3);
-  }
-  float res = ex_add(ex_add(ex_add(p0, p1), p2), p3);
-  if (body != dims) {
-    float tail = 0.0f;
-    for (uint32_t m = body; m < dims; ++m) {
-      const float xv = SCALE ? ex_mul(x[m], xscale) : x[m];
-      if (METRIC01 == 0) {
-        const float diff = ex_sub(q[m], xv);
-        tail = ex_add(tail, ex_mul(diff, diff));
-      } else {
-        tail = ex_add(tail, ex_mul(q[m], xv));
-      }
-    }
-    if (METRIC01 != 0 && body) return ex_sub(ex_add(ex_sub(1.0f, res), ex_sub(1.0f, tail)), 1.0f);  // see canon_dist
-    res = body ? ex_add(res, tail) : tail;
-  }
-  if (METRIC01 != 0) res = ex_sub(1.0f, res);
-  return res;
-}
-
-// The same canonical arithmetic executed by a 4-LANE GROUP over a row of the graph-mode SEARCH COPY
-// (launch_make_search_copy: inside every 16-float block the four inputs of SSE partial sum j are 16
-// contiguous bytes; cosine rows are stored normalised).  Lane `sub` of the group plays SSE lane `sub`:
-// per block it loads ONE float4 — the group reads the block as one coalesced 64-byte piece — and adds
-// its four products to its partial sum in order.  q is the query permuted the same way (LDS).  All four
-// lanes of the group must be active; every lane returns the full result.  Same register ring as above.
-// SCALE (round 4, single-copy graph spaces: the rows are stored raw and permuted, not normalised): every element of
-// the row is multiplied by xs first — hnswlib-python's stored normalised row x * inv_norm, one rounding per element,
-// formed on the fly; the products with the query then see exactly the values the normalised copy held.
-// x * xs per element as two packed multiplies (v_pk_mul_f32: IEEE, one rounding per element like the scalar form)
-__device__ __forceinline__ float4 scale_f4(float4 xv, float xs) {
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-  const f32x2 sc = {xs, xs};
-  f32x2 lo = {xv.x, xv.y}, hi = {xv.z, xv.w};
-  lo = lo * sc;
-  hi = hi * sc;
-  return make_float4(lo.x, lo.y, hi.x, hi.y);
-}
-
-template <int METRIC01, bool SCALE = false>
-__device__ __forceinline__ void canon_group_step(float4 xv, const float4 qv, float& p, int ncomp = 4, float xs = 1.0f) {
-  if (SCALE) xv = scale_f4(xv, xs);
-  if (METRIC01 == 0) {
-    const float d0 = ex_sub(qv.x, xv.x), d1 = ex_sub(qv.y, xv.y), d2 = ex_sub(qv.z, xv.z), d3 = ex_sub(qv.w, xv.w);
-    p = ex_add(p, ex_mul(d0, d0));
-    if (ncomp > 1) p = ex_add(p, ex_mul(d1, d1));
-    if (ncomp > 2) p = ex_add(p, ex_mul(d2, d2));
-    if (ncomp > 3) p = ex_add(p, ex_mul(d3, d3));
-  } else {
-    p = ex_add(p, ex_mul(qv.x, xv.x));
-    if (ncomp > 1) p = ex_add(p, ex_mul(qv.y, xv.y));
-    if (ncomp > 2) p = ex_add(p, ex_mul(qv.z, xv.z));
-    if (ncomp > 3) p = ex_add(p, ex_mul(qv.w, xv.w));
-  }
-}
-
-// position of element m of a row inside the search copy / the permuted query
-__host__ __device__ inline uint32_t search_copy_pos(uint32_t m) { return (m & ~15u) + ((m & 3u) << 2) + ((m >> 2) & 3u); }
-
-template <int METRIC01, bool SCALE = false>
-__device__ __forceinline__ float canon_dist_group_t(const float* __restrict__ qp, const float* __restrict__ xs, int sub,
-                                                    uint32_t dims, float xscale = 1.0f) {
-  uint32_t body;
-  if ((dims & 15u) == 0 || (dims & 3u) == 0) body = dims;
-  else if (dims > 16) body = dims & ~15u;
-  else if (dims > 4) body = dims & ~3u;
-  else body = 0;
-  float p = 0.0f;
-  constexpr int BL = kLaneBlk;
-  const uint32_t n16 = body / 16u;       // full 16-float blocks: one float4 per lane each
-  const uint32_t nblk = n16 / BL;        // ring blocks
-  float4 r0[BL], r1[BL], r2[BL];
-  const float4* x4 = (const float4*)xs + sub;  // block t of this lane: x4[4 t]
-  const float4* q4 = (const float4*)qp + sub;
-#define EHX_GRP_LOAD(R, B)                                        \
-  _Pragma("unroll") for (int i_ = 0; i_ < BL; ++i_) R[i_] = x4[((size_t)(B) * BL + i_) * 4];
-  // (SCALE: the ring block's query pieces are read from LDS together, ahead of its products — left to the scheduler,
-  // the scaled walk reads one piece, waits for it, multiplies, and pays the LDS latency once per 16-float block)
-#define EHX_GRP_ACC(R, B)                                                                                            \
-  if (SCALE) {                                                                                                       \
-    float4 qv_[BL];                                                                                                  \
-    _Pragma("unroll") for (int i_ = 0; i_ < BL; ++i_) qv_[i_] = q4[((size_t)(B) * BL + i_) * 4];                      \
-    _Pragma("unroll") for (int i_ = 0; i_ < BL; ++i_) R[i_] = scale_f4(R[i_], xscale);                               \
-    _Pragma("unroll") for (int i_ = 0; i_ < BL; ++i_) canon_group_step<METRIC01, false>(R[i_], qv_[i_], p, 4, 1.0f); \
-  } else {                                                                                                           \
-    _Pragma("unroll") for (int i_ = 0; i_ < BL; ++i_)                                                                \
-      canon_group_step<METRIC01, false>(R[i_], q4[((size_t)(B) * BL + i_) * 4], p, 4, 1.0f);                         \
-  }
-  uint32_t b = 0;
-  if (nblk >= 2) {
-    EHX_GRP_LOAD(r0, 0)
-    EHX_GRP_LOAD(r1, 1)
-    for (; b + 5 <= nblk; b += 3) {
-      EHX_GRP_LOAD(r2, b + 2)
-      EHX_GRP_ACC(r0, b)
-      EHX_GRP_LOAD(r0, b + 3)
-      EHX_GRP_ACC(r1, b + 1)
-      EHX_GRP_LOAD(r1, b + 4)
-      EHX_GRP_ACC(r2, b + 2)
-    }
-    const uint32_t rem = nblk - b;  // 2, 3 or 4 ring blocks left; r0 / r1 hold blocks b / b+1
-    if (rem >= 3) { EHX_GRP_LOAD(r2, b + 2) }
-    EHX_GRP_ACC(r0, b)
-    if (rem == 4) { EHX_GRP_LOAD(r0, b + 3) }
-    EHX_GRP_ACC(r1, b + 1)
-    if (rem >= 3) { EHX_GRP_ACC(r2, b + 2) }
-    if (rem == 4) { EHX_GRP_ACC(r0, b + 3) }
-  } else if (nblk == 1) {
-    EHX_GRP_LOAD(r0, 0)
-    EHX_GRP_ACC(r0, 0)
-  }
-#undef EHX_GRP_LOAD
-#undef EHX_GRP_ACC
-  {
-    uint32_t t = nblk * BL;  // 16-float blocks after the last full ring block (fewer than kLaneBlk), four at a time
-    for (; t + 4 <= n16; t += 4) {
-      const float4 t0 = x4[t * 4], t1 = x4[(t + 1) * 4], t2 = x4[(t + 2) * 4], t3 = x4[(t + 3) * 4];
-      canon_group_step<METRIC01, SCALE>(t0, q4[t * 4], p, 4, xscale);
-      canon_group_step<METRIC01, SCALE>(t1, q4[(t + 1) * 4], p, 4, xscale);
-      canon_group_step<METRIC01, SCALE>(t2, q4[(t + 2) * 4], p, 4, xscale);
-      canon_group_step<METRIC01, SCALE>(t3, q4[(t + 3) * 4], p, 4, xscale);
-    }
-    for (; t < n16; ++t) canon_group_step<METRIC01, SCALE>(x4[t * 4], q4[t * 4], p, 4, xscale);
-    // the 4-float pieces of a last, partial block (body % 16 / 4 of them): components 0..rem4-1
-    const int rem4 = (int)((body & 15u) >> 2);
-    if (rem4) canon_group_step<METRIC01, SCALE>(x4[n16 * 4], q4[n16 * 4], p, rem4, xscale);
-  }
-  // horizontal sum in SSE-lane order: ((p0 + p1) + p2) + p3, formed by every lane of the group
-  const float t0 = __shfl(p, 0, 4), t1 = __shfl(p, 1, 4), t2 = __shfl(p, 2, 4), t3 = __shfl(p, 3, 4);
-  float res = ex_add(ex_add(ex_add(t0, t1), t2), t3);
-  if (body != dims) {
-    float tail = 0.0f;
-    for (uint32_t m = body; m < dims; ++m) {
-      const uint32_t pos = search_copy_pos(m);
-      const float xv = SCALE ? ex_mul(xs[pos], xscale) : xs[pos];
-      if (METRIC01 == 0) {
-        const float diff = ex_sub(qp[pos], xv);
-        tail = ex_add(tail, ex_mul(diff, diff));
-      } else {
-        tail = ex_add(tail, ex_mul(qp[pos], xv));
-      }
-    }
-    if (METRIC01 != 0 && body) return ex_sub(ex_add(ex_sub(1.0f, res), ex_sub(1.0f, tail)), 1.0f);  // see canon_dist
-    res = body ? ex_add(res, tail) : tail;
-  }
-  if (METRIC01 != 0) res = ex_sub(1.0f, res);
-  return res;
-}
-
-// Two rows of exactly 16 * N16 floats by one 4-lane group, all 2 * N16 loads of the lane in flight before the first
-// product (a 128-dim row is ONE ring block of canon_dist_group_t: with more than 16 fresh neighbours the second pass
-// would wait a second memory round trip).  Same arithmetic and order per row as canon_dist_group_t.
-template <int METRIC01, int N16, bool SCALE = false>
-__device__ __forceinline__ void canon_dist_group_pair(const float* __restrict__ qp, const float* __restrict__ xa,
-                                                      const float* __restrict__ xb, int sub, float& res_a, float& res_b,
-                                                      float sa = 1.0f, float sb = 1.0f) {
-  const float4* a4 = (const float4*)xa + sub;
-  const float4* b4 = (const float4*)xb + sub;
-  const float4* q4 = (const float4*)qp + sub;
-  float4 ra[N16], rb[N16];
-#pragma unroll
-  for (int i = 0; i < N16; ++i) ra[i] = a4[i * 4];
-#pragma unroll
-  for (int i = 0; i < N16; ++i) rb[i] = b4[i * 4];
-  float pa = 0.0f, pb = 0.0f;
-#pragma unroll
-  for (int i = 0; i < N16; ++i) canon_group_step<METRIC01, SCALE>(ra[i], q4[i * 4], pa, 4, sa);
-#pragma unroll
-  for (int i = 0; i < N16; ++i) canon_group_step<METRIC01, SCALE>(rb[i], q4[i * 4], pb, 4, sb);
-  const float a0 = __shfl(pa, 0, 4), a1 = __shfl(pa, 1, 4), a2 = __shfl(pa, 2, 4), a3 = __shfl(pa, 3, 4);
-  const float b0 = __shfl(pb, 0, 4), b1 = __shfl(pb, 1, 4), b2 = __shfl(pb, 2, 4), b3 = __shfl(pb, 3, 4);
-  res_a = ex_add(ex_add(ex_add(a0, a1), a2), a3);
-  res_b = ex_add(ex_add(ex_add(b0, b1), b2), b3);
-  if (METRIC01 != 0) {
-    res_a = ex_sub(1.0f, res_a);
-    res_b = ex_sub(1.0f, res_b);
-  }
-}
-
-// Four rows of exactly 16 * N16 floats (N16 <= 8: rows of up to 128 dims) by one 4-lane group, all 4 * N16 loads of the lane
-// in flight before the first product: 64 rows per pass of a wave (the wide graph walk, k_graphw.hip, evaluates up to 64
-// fresh rows per merge — one memory round trip instead of two).  Same arithmetic and order per row as canon_dist_group_t.
-template <int METRIC01, int N16, bool SCALE = false>
-__device__ __forceinline__ void canon_dist_group_quad(const float* __restrict__ qp, const float* const (&x)[4], int sub,
-                                                      float (&res)[4], const float (&sc)[4]) {
-  const float4* q4 = (const float4*)qp + sub;
-  float4 r[4][N16];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float4* x4 = (const float4*)x[j] + sub;
-#pragma unroll
-    for (int i = 0; i < N16; ++i) r[j][i] = x4[i * 4];
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    float p = 0.0f;
-#pragma unroll
-    for (int i = 0; i < N16; ++i) canon_group_step<METRIC01, SCALE>(r[j][i], q4[i * 4], p, 4, sc[j]);
-    const float t0 = __shfl(p, 0, 4), t1 = __shfl(p, 1, 4), t2 = __shfl(p, 2, 4), t3 = __shfl(p, 3, 4);
-    res[j] = ex_add(ex_add(ex_add(t0, t1), t2), t3);
-    if (METRIC01 != 0) res[j] = ex_sub(1.0f, res[j]);
-  }
-}
-
-// Canonical distances of the search-copy rows ids_l[0..count) (LDS) to the permuted query qs (LDS), by one wave:
-// lane p (< count) returns the distance of row p, other lanes +inf.  16 rows per pass, one 4-lane group per row
-// (canon_dist_group_t); rows of 32 / 64 / 96 / 128 / 192 / 256 dims go 32 per pass, two per group, with the loads
-// of both rows in flight together (canon_dist_group_pair) — at 128 dims and 27 fresh neighbours per expansion that is
-// one memory round trip per expansion instead of two (6.25 M x 128-class workloads: -20 % kernel time).
-// xscale (optional): per-row scale applied to the row's elements on the fly (single-copy graph spaces, cosine:
-// inv_norm) — nullptr: the rows are used as stored.
-// QUAD (the wide graph walk): more than 32 rows of 32 / 64 / 96 / 128 dims go 64 per pass, four per group.
-template <int METRIC01, bool SCALE, bool QUAD = false>
-__device__ __forceinline__ float wave_group_dists_t(const float* __restrict__ qs, const float* __restrict__ Xs, uint32_t ld,
-                                                    uint32_t dims, const uint32_t* ids_l, uint32_t count, int lane,
-                                                    const float* __restrict__ xscale) {
-  float mine = __builtin_inff();
-  const bool pairable = dims <= 256 && (dims == 32 || dims == 64 || dims == 96 || dims == 128 || dims == 192 || dims == 256);
-  if (QUAD && pairable && dims <= 128 && count > 32) {   // (count <= 64: one pass)
-    const uint32_t r0 = (uint32_t)lane >> 2;
-    const float* x[4];
-    float sc[4], res[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const uint32_t rj = r0 + 16u * (uint32_t)j;
-      const uint32_t id = ids_l[rj < count ? rj : r0];   // a missing row: the group's first one again, result dropped
-      sc[j] = SCALE ? __hip_atomic_load(xscale + id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT) : 1.0f;
-      x[j] = Xs + (size_t)id * ld;
-    }
-    const int sub = lane & 3;
-    switch (dims) {
-      case 32: canon_dist_group_quad<METRIC01, 2, SCALE>(qs, x, sub, res, sc); break;
-      case 64: canon_dist_group_quad<METRIC01, 4, SCALE>(qs, x, sub, res, sc); break;
-      case 96: canon_dist_group_quad<METRIC01, 6, SCALE>(qs, x, sub, res, sc); break;
-      default: canon_dist_group_quad<METRIC01, 8, SCALE>(qs, x, sub, res, sc); break;
-    }
-    const int src = (lane & 15) << 2;
-    const float g0 = __shfl(res[0], src, 64), g1 = __shfl(res[1], src, 64), g2 = __shfl(res[2], src, 64),
-                g3 = __shfl(res[3], src, 64);
-    if ((uint32_t)lane < count) mine = (lane & 32) ? ((lane & 16) ? g3 : g2) : ((lane & 16) ? g1 : g0);
-    return mine;
-  }
-  if (pairable && count > 16) {
-    for (uint32_t base = 0; base < count; base += 32) {
-      const uint32_t ra = base + ((uint32_t)lane >> 2), rb = ra + 16;
-      float res_a = __builtin_inff(), res_b = __builtin_inff();
-      if (ra < count) {
-        const bool have_b = rb < count;  // a missing second row: the first one again, result dropped
-        const uint32_t ia = ids_l[ra], ib = ids_l[have_b ? rb : ra];
-        const float sa = SCALE ? __hip_atomic_load(xscale + ia, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT) : 1.0f;
-        const float sb = SCALE ? __hip_atomic_load(xscale + ib, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT) : 1.0f;
-        const float* xa = Xs + (size_t)ia * ld;
-        const float* xb = Xs + (size_t)ib * ld;
-        const int sub = lane & 3;
-        switch (dims) {
-          case 32: canon_dist_group_pair<METRIC01, 2, SCALE>(qs, xa, xb, sub, res_a, res_b, sa, sb); break;
-          case 64: canon_dist_group_pair<METRIC01, 4, SCALE>(qs, xa, xb, sub, res_a, res_b, sa, sb); break;
-          case 96: canon_dist_group_pair<METRIC01, 6, SCALE>(qs, xa, xb, sub, res_a, res_b, sa, sb); break;
-          case 128: canon_dist_group_pair<METRIC01, 8, SCALE>(qs, xa, xb, sub, res_a, res_b, sa, sb); break;
-          case 192: canon_dist_group_pair<METRIC01, 12, SCALE>(qs, xa, xb, sub, res_a, res_b, sa, sb); break;
-          default: canon_dist_group_pair<METRIC01, 16, SCALE>(qs, xa, xb, sub, res_a, res_b, sa, sb); break;
-        }
-        if (!have_b) res_b = __builtin_inff();
-      }
-      const float got_a = __shfl(res_a, (lane & 15) << 2, 64), got_b = __shfl(res_b, (lane & 15) << 2, 64);
-      if (((uint32_t)lane & ~31u) == base && (uint32_t)lane < count) mine = (lane & 16) ? got_b : got_a;
-    }
-    return mine;
-  }
-  for (uint32_t base = 0; base < count; base += 16) {
-    const uint32_t r = base + ((uint32_t)lane >> 2);
-    float res = __builtin_inff();
-    if (r < count) {
-      const uint32_t id = ids_l[r];
-      // (the scale is requested FIRST, as an ordered load: it is the oldest entry of the load queue when the first
-      // product needs it — sunk below the row's ring loads it would be the youngest, and waiting for it would drain
-      // the ring)
-      const float xsc = SCALE ? __hip_atomic_load(xscale + id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT) : 1.0f;
-      res = canon_dist_group_t<METRIC01, SCALE>(qs, Xs + (size_t)id * ld, lane & 3, dims, xsc);
-    }
-    const float got = __shfl(res, (lane & 15) << 2, 64);
-    if (((uint32_t)lane & ~15u) == base && (uint32_t)lane < count) mine = got;
-  }
-  return mine;
-}
-template <int METRIC01, bool QUAD = false>
-__device__ __forceinline__ float wave_group_dists(const float* __restrict__ qs, const float* __restrict__ Xs, uint32_t ld,
-                                                  uint32_t dims, const uint32_t* ids_l, uint32_t count, int lane,
-                                                  const float* __restrict__ xscale = nullptr) {
-  if (METRIC01 == 1 && xscale) return wave_group_dists_t<METRIC01, true, QUAD>(qs, Xs, ld, dims, ids_l, count, lane, xscale);
-  return wave_group_dists_t<METRIC01, false, QUAD>(qs, Xs, ld, dims, ids_l, count, lane, nullptr);
-}
-
 }  // namespace ehx
-#include "k_exact_common.h"   // RowsView, the row layouts and the exact paths' walk, built on the walkers above
+#include "k_canon.h"          // the canonical distance arithmetic and every walker built on it: the ONE statement of the order
+#include "k_exact_common.h"   // RowsView, the row layouts and the exact paths' walk, built on those walkers
 namespace ehx {
 
 struct ScanArgs {

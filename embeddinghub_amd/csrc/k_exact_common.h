@@ -1,8 +1,9 @@
 // What the exact paths share (k_flat.hip: rerank / exhaustive / single-query kernels; k_among.hip; k_range.hip): where the
 // stored rows are (RowsView), their three layouts, the ONE walk from a prepared query to a stored row in the oracle's
 // arithmetic, the (distance, id) key with its NaN rule, the running best-64 list, and the page writer with its sentinel
-// rule.  Included by ehx_kernels.h behind the canonical walkers it is built on (canon_dist, canon_dist_lane_t,
-// canon_dist_group_t), ahead of the launch arguments that embed a RowsView.
+// rule.  Included by ehx_kernels.h behind k_canon.h — the one statement of that arithmetic, whose walkers (canon_dist,
+// canon_dist_lane_t, canon_dist_group_t) the walk here calls and never restates — ahead of the launch arguments that embed
+// a RowsView.
 #pragma once
 
 namespace ehx {

@@ -430,7 +430,7 @@ __global__ __launch_bounds__(kThreads8, 2) void flat_scan8_kernel(const ScanArgs
     const int cq = cnt[list];
     const int nv = cq < (int)kCandSlots ? cq : (int)kCandSlots;
     uint64_t key = lane < nv ? cand[list * kCandSlots + lane] : kKeyInf;
-    key = wave_sort64_8(key, lane);
+    key = wave_sort64(key, lane);
     if (lane < (int)a.kprime)
       a.part[((size_t)(qt * kTileQ + wc * 64 + ql) * a.lists_total + a.list0 + chunk * 2 + wr) * a.kprime + lane] = key;
   }

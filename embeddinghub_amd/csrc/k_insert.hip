@@ -18,7 +18,8 @@
 // nodes of one batch do not see each other, the result depends on the batch size, and parity is
 // recall parity, not graph identity.
 //
-// All distances use the canonical (oracle-order) arithmetic and read the SEARCH COPY only (cosine rows normalised
+// All distances use the canonical (oracle-order) arithmetic, which k_canon.h alone states — row_row_dist between two stored
+// rows, canon_dist_lane_t / wave_group_dists from the new row — and read the SEARCH COPY only (cosine rows normalised
 // there: exactly the vectors hnswlib would have stored) — the raw rows may be fp32 or binary16.
 //
 // The 64-lane sort (wave_sort64), the binary search (lower_bound_lds) and kNoNode are ehx_kernels.h's, shared with the
@@ -30,83 +31,6 @@
 namespace ehx {
 
 namespace {
-
-// canonical distance between two STORED rows, one lane, both read from the SEARCH COPY (k_misc.hip: cosine rows
-// already normalised — the product hnswlib stores — and every 16-float block permuted so that piece j holds the four
-// inputs of SSE partial sum j in order).  Piece j of a block therefore feeds partial sum j with its four products one
-// after the other: the same additions in the same order as walking the raw rows 16 bytes at a time, and the kernels
-// here need neither the raw rows nor their norms (fp16 row storage: the search copy is made from the rounded rows).
-// sa / sb: per-row scales applied to the elements on the fly (single-copy graph spaces, cosine: the rows are stored
-// raw; x * inv_norm is the normalised row hnswlib-python stores, one rounding per element).  1.0f: the rows as stored
-// (a multiplication by one is exact).
-__device__ __forceinline__ float row_row_dist(int metric01, const float* __restrict__ xa, const float* __restrict__ xb,
-                                              uint32_t dims, float sa = 1.0f, float sb = 1.0f) {
-  uint32_t body;
-  if ((dims & 15u) == 0 || (dims & 3u) == 0) body = dims;
-  else if (dims > 16) body = dims & ~15u;
-  else if (dims > 4) body = dims & ~3u;
-  else body = 0;
-  float p[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  auto step = [&](float4 a, float4 b, float& acc, int ncomp) {
-    a.x = ex_mul(a.x, sa); a.y = ex_mul(a.y, sa); a.z = ex_mul(a.z, sa); a.w = ex_mul(a.w, sa);
-    b.x = ex_mul(b.x, sb); b.y = ex_mul(b.y, sb); b.z = ex_mul(b.z, sb); b.w = ex_mul(b.w, sb);
-    if (metric01 == 0) {
-      const float d0 = ex_sub(a.x, b.x), d1 = ex_sub(a.y, b.y), d2 = ex_sub(a.z, b.z), d3 = ex_sub(a.w, b.w);
-      acc = ex_add(acc, ex_mul(d0, d0));
-      if (ncomp > 1) acc = ex_add(acc, ex_mul(d1, d1));
-      if (ncomp > 2) acc = ex_add(acc, ex_mul(d2, d2));
-      if (ncomp > 3) acc = ex_add(acc, ex_mul(d3, d3));
-    } else {
-      acc = ex_add(acc, ex_mul(a.x, b.x));
-      if (ncomp > 1) acc = ex_add(acc, ex_mul(a.y, b.y));
-      if (ncomp > 2) acc = ex_add(acc, ex_mul(a.z, b.z));
-      if (ncomp > 3) acc = ex_add(acc, ex_mul(a.w, b.w));
-    }
-  };
-  const float4* a4 = (const float4*)xa;
-  const float4* b4 = (const float4*)xb;
-  const uint32_t n16 = body / 16u;
-  // two blocks (sixteen 16-byte pieces of both rows) requested before the first is used: a one-piece-per-trip
-  // loop keeps ONE load in flight and pays the cache latency dims/4 times
-  uint32_t t = 0;
-  for (; t + 2 <= n16; t += 2) {
-    float4 ra[8], rb[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      ra[i] = a4[t * 4 + i];
-      rb[i] = b4[t * 4 + i];
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) step(ra[i], rb[i], p[i & 3], 4);
-  }
-  for (; t < n16; ++t) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) step(a4[t * 4 + j], b4[t * 4 + j], p[j], 4);
-  }
-  const int rem4 = (int)((body & 15u) >> 2);  // 4-float pieces of a last, partial block: components 0..rem4-1
-  if (rem4) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) step(a4[n16 * 4 + j], b4[n16 * 4 + j], p[j], rem4);
-  }
-  float res = ex_add(ex_add(ex_add(p[0], p[1]), p[2]), p[3]);
-  if (body != dims) {
-    float tail = 0.0f;
-    for (uint32_t m = body; m < dims; ++m) {
-      const uint32_t pos = search_copy_pos(m);
-      const float va = ex_mul(xa[pos], sa), vb = ex_mul(xb[pos], sb);
-      if (metric01 == 0) {
-        const float d = ex_sub(va, vb);
-        tail = ex_add(tail, ex_mul(d, d));
-      } else {
-        tail = ex_add(tail, ex_mul(va, vb));
-      }
-    }
-    if (metric01 != 0 && body) return ex_sub(ex_add(ex_sub(1.0f, res), ex_sub(1.0f, tail)), 1.0f);  // see canon_dist
-    res = body ? ex_add(res, tail) : tail;
-  }
-  if (metric01 != 0) res = ex_sub(1.0f, res);
-  return res;
-}
 
 // hnswlib getNeighborsByHeuristic2 on one wave.  cand[0..nc): (dist-to-base, id<<1|flag) keys sorted
 // ascending; if nc < Msel all are kept.  Otherwise candidates are visited closest first and kept iff

@@ -18,22 +18,6 @@ __device__ __forceinline__ void glds16_8(const void* gsrc, void* lds_dst_uniform
                                    (__attribute__((address_space(3))) void*)lds_dst_uniform, 16, 0, 0);
 }
 
-__device__ __forceinline__ uint64_t wave_sort64_8(uint64_t key, int lane) {
-#pragma unroll
-  for (int k = 2; k <= 64; k <<= 1) {
-#pragma unroll
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      const uint64_t other = __shfl_xor(key, j, 64);
-      const bool up = (lane & k) == 0;
-      const bool lower = (lane & j) == 0;
-      const uint64_t mn = key < other ? key : other;
-      const uint64_t mx = key < other ? other : key;
-      key = (lower == up) ? mn : mx;
-    }
-  }
-  return key;
-}
-
 // hot-path barrier: LDS traffic only, the DMA queue keeps flowing
 __device__ __forceinline__ void hot_barrier() {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -80,7 +64,7 @@ __device__ __attribute__((noinline)) void scan8_compact(int w, int wc, int lane,
     const int cq = cnt[list];
     const int nv = cq < (int)kCandSlots ? cq : (int)kCandSlots;
     uint64_t key = lane < nv ? cand[list * kCandSlots + lane] : kKeyInf;
-    key = wave_sort64_8(key, lane);
+    key = wave_sort64(key, lane);
     if (lane < kprime) cand[list * kCandSlots + lane] = key;
     const uint64_t kth = __shfl(key, kprime - 1, 64);
     if (lane == 0) {

@@ -362,7 +362,7 @@ __device__ __forceinline__ float rerank_floor(const Rerank256Args& a, uint32_t q
 }  // namespace
 
 // Canonical distances of 64 rows (one per lane: row `id`, garbage allowed when !valid) to the query q, for rows whose
-// length is a multiple of 32 floats.  The arithmetic is the lane-private walk's (canon_lane_step, piece after piece);
+// length is a multiple of 32 floats.  The arithmetic is the lane-private walk's (k_canon.h: canon_lane_step, piece after piece, and canon_finish);
 // what changes is how the rows reach the lane.  A lane that loads its own row 16 bytes at a time makes every wave
 // load touch 64 different 128-byte lines, each needed eight times: with three ring blocks in flight per lane and four
 // waves on a CU that is 768 lines against a 256-line L1, and most of them are evicted before their eighth use
@@ -442,9 +442,8 @@ __device__ __forceinline__ float wave_rows_dist_staged(const float* __restrict__
   }
 #undef EHX_CONSUME
 #undef EHX_FETCH
-  float res = ex_add(ex_add(ex_add(p0, p1), p2), p3);
-  if (METRIC01 != 0) res = ex_sub(1.0f, res);
-  return res;
+  float res = canon_hsum(p0, p1, p2, p3);
+  EHX_CANON_FINISH_WHOLE(METRIC01, res)
 }
 
 // fp32 rows: one wave per query, one candidate per lane; rows of a multiple of 32 floats are loaded by the wave
@@ -483,8 +482,7 @@ __global__ __launch_bounds__(64) void rerank256_lane_kernel(const Rerank256Args 
       d = q_in_lds ? canon_dist_lane_t<METRIC01, SCALE>(qs, xv, xs, a.dims)
                    : canon_dist_lane_t<METRIC01, SCALE>(qv, xv, xs, a.dims);
     }
-    // (a NaN distance — a row or query holding NaN — is never a neighbour: the key is dropped)
-    const uint64_t key = (valid && d == d) ? (((uint64_t)f32_to_ordered(d) << 32) | id) : kKeyInf;
+    const uint64_t key = dist_key(d, id, valid);  // (a NaN distance is never a neighbour: the key is dropped)
     st.certified = rerank_round(a, mq, key, c0 + 64, floor_s, uv, qn, maxss, lane, st);
     if (st.certified) break;
   }
@@ -520,7 +518,7 @@ __global__ __launch_bounds__(256) void rerank256_kernel(const Rerank256Args a) {
       const float xs = scale_x ? a.inv_norm[id] : 1.0f;
       d = canon_dist(a.metric == 0 ? 0 : 1, qv, xv, xs, scale_x, a.dims, sub);
     }
-    if (sub == 0) keys[g] = (valid && d == d) ? (((uint64_t)f32_to_ordered(d) << 32) | id) : kKeyInf;
+    if (sub == 0) keys[g] = dist_key(d, id, valid);
     __syncthreads();
     if (tid < 64) {
       st.certified = rerank_round(a, mq, keys[tid], c0 + 64, floor_s, uv, qn, maxss, tid, st);

@@ -39,7 +39,9 @@ def _same(got, oids, odist, k, what):
 
 @pytest.mark.parametrize("kind", ["flat_f32", "flat_f16", "graph_f32"])
 @pytest.mark.parametrize("metric", ["l2", "ip", "cosine"])
-@pytest.mark.parametrize("d", [3, 7, 30, 100, 129])
+# 160 .. 896: the register ring of the lane walk (blocks of 32 floats) and of the group walk (blocks of 128) — the steady
+# state left with 2, 3 and 4 blocks, the four-at-a-time and single leftovers, and at 650 the residual join behind a full ring
+@pytest.mark.parametrize("d", [3, 7, 30, 100, 129, 160, 192, 231, 640, 650, 896])
 def test_every_exact_path_is_one_walk(d, metric, kind):
     em, om = METRICS[metric]
     rng = np.random.default_rng(9000 + d)

@@ -139,7 +139,9 @@ def _same_graph(s, h):
 
 
 @pytest.mark.parametrize("em,om", METRICS)
-@pytest.mark.parametrize("n,d", [(700, 32), (1500, 64), (400, 20)])
+# d = 3, 19, 44, 51: the row-to-row distance's scalar path, its tail with the residual join, a partial block, and the
+# paired loop with its odd leftover
+@pytest.mark.parametrize("n,d", [(700, 32), (1500, 64), (400, 20), (300, 3), (300, 19), (300, 44), (300, 51)])
 def test_sequential_gpu_build_is_the_oracles_graph(n, d, em, om):
     rng = np.random.default_rng(n * 7 + d)
     X = rng.standard_normal((n, d)).astype(np.float32)

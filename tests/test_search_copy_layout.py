@@ -1,5 +1,5 @@
 """Host-side check of the graph-mode SEARCH COPY layout (k_misc.hip::make_search_copy_kernel,
-ehx_kernels.h::search_copy_pos / canon_dist_group_t): restated in numpy float32 — every 16-float block
+k_canon.h::search_copy_pos / canon_dist_group_t): restated in numpy float32 — every 16-float block
 permuted so that the four inputs of SSE partial sum j are contiguous, lane j of a 4-lane group adding its
 four products per block in order, ((p0+p1)+p2)+p3, scalar tail last — it must reproduce the oracle's
 (hnswlib SSE-order) distance bit for bit for every distance-function variant hnswlib dispatches on
