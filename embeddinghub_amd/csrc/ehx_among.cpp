@@ -23,7 +23,7 @@ int among_unsharded(const ehx_space* s, const char* what) {
 // sizes the grid only.
 int ehx_impl::among_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k,
                            const uint64_t* d_ids, const uint64_t* d_off, size_t n_cand, size_t max_list, uint64_t* d_out_ids, float* d_out_dist,
-                           uint32_t* d_out_count) {
+                           uint32_t* d_out_count, bool count_queries) {
   int rc;
   if ((rc = check_not_poisoned(s))) return rc;
   if (s->ld > among_max_ld())   // (before anything is enqueued)
@@ -66,7 +66,7 @@ int ehx_impl::among_locked(ehx_space* s, hipStream_t st, size_t nq, const float*
                               d_out_dist, d_out_count, st));
   }
   if ((rc = s->clock.scan_end(st)) || (rc = s->clock.finish(st))) return rc;
-  s->n_queries += nq;
+  if (count_queries) s->n_queries += nq;
   s->n_dist += d_off ? (uint64_t)n_cand : (uint64_t)nq * n_cand;
   return EHX_OK;
 }

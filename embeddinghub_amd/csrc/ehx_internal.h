@@ -461,6 +461,23 @@ struct ehx_space {
     DevBuf<unsigned char> dOut;  // host form: ids | distances | counts | totals
   } range;
   std::atomic<uint64_t> range_ctr[4] = {};   // test hook: queries answered by the int8 path, by the exact path, pool overflows, truncated
+  // exact kNN under a row bitmap (ehx_masked.cpp; scratch_mu): the bitmap's compaction — allowed rows before every
+  // 256-row tile, the ascending list of allowed ids, the sample of it — the queries' radii and re-rank work counts, the
+  // sub-batch of flagged queries (answered by the exact kNN among the whole list), and a host call's staged bitmap,
+  // queries and results.  The scan route runs in one of the int8 scratch sets.
+  struct Masked {
+    DevBuf<uint32_t> dCum;       // [n_tiles + 1]
+    DevBuf<uint64_t> dList;      // [rows the bitmap covers]
+    DevBuf<uint64_t> dSample;    // [256]
+    DevBuf<float> dRadius;       // [queries of a device batch]
+    DevBuf<uint32_t> dWork;      // [queries of a device batch]
+    SubsetBufs sub;
+    DevBuf<uint32_t> dMaskRaw;   // host form: the bitmap
+    DevBuf<float> dQraw;         // host form: queries
+    DevBuf<unsigned char> dOut;  // host form: ids | distances | counts
+  } masked;
+  // test hook: queries answered on the scan route, on the exact route, queries that overflowed, scan passes launched, calls
+  std::atomic<uint64_t> masked_ctr[5] = {};
   // int8 filter scratch: everything ONE in-flight batch of the int8 pipeline owns — prepared queries, query tiles +
   // parameters, per-pass thresholds, sample scores, pools, running best list, verdict, batch clock.  TWO sets: a host
   // caller's batch can be enqueued behind another caller's on the space's stream while that one still waits for its
@@ -539,6 +556,7 @@ struct ehx_space {
     by = {};
     among = {};
     range = {};
+    masked = {};
     one = {};
     xch = {};
     wr = {};
@@ -677,9 +695,10 @@ int i8_scan_args(ehx_space* s, ehx_space::I8Set::Buffers& b, const ScanPlan& p, 
 // ---- ehx_among.cpp ----
 // exact kNN among row ids on an unsharded space, locked shared, scratch_mu held, its device current (d_off == nullptr: one
 // list shared by every query; max_list: an upper bound of one list's length, 0 = n_cand)
+// count_queries = false: a stage of a larger search (the masked kNN's sample) — its pairs are counted, its queries are not
 int among_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, const uint64_t* d_ids,
                  const uint64_t* d_off, size_t n_cand, size_t max_list, uint64_t* d_out_ids, float* d_out_dist,
-                 uint32_t* d_out_count);
+                 uint32_t* d_out_count, bool count_queries = true);
 
 // ---- ehx_write.cpp ----
 int sync_stream(ehx_space* s, hipStream_t st);

@@ -241,6 +241,8 @@ struct ScanArgsI8 {
   uint32_t sync_tol = 0;     // > 0: a workgroup does not run more than this many TILES ahead of its slowest sibling
   uint32_t skew = 0;         // half-tile workgroups: the second-resident wave of a SIMD starts skew x 64 cycles late
   uint32_t group_b = 0;      // 1: the alarm level of a lane group uses the group's B margin (L2^2: B_r = |x_r|^2 varies)
+  const uint32_t* allow = nullptr;  // optional row bitmap (masked kNN, k_masked.hip): bit id & 31 of word id >> 5; a hit whose
+  uint32_t allow_bits = 0;          // row id is >= allow_bits or whose bit is clear is dropped before it takes a pool slot
 };
 // Stage-blocked layout of the int8 scan copy / query tiles: tiles of 256 rows, stages of 64 columns (bytes); one
 // (tile, stage) block is 256 rows x 64 B = 16 KiB in exactly the LDS image of the kernel (16-byte chunk c of row r
@@ -494,6 +496,31 @@ struct RangeRerankArgs {
 uint32_t range_rerank_max_ld();   // longest row stride (floats): the pool and the prepared query share the LDS
 hipError_t launch_range_rerank(const RangeRerankArgs& a, hipStream_t st);
 hipError_t launch_range_iota(uint64_t* out, uint64_t n, hipStream_t st);   // out[i] = i
+
+// exact kNN under a row bitmap (k_masked.hip).  Compaction of the bitmap's first n_bits bits (n_tiles = ceil(n_bits / 256)
+// tiles of 8 words; words and bits beyond n_bits are not read): cum[0 .. n_tiles] = allowed rows before every tile, the
+// last entry their number; list = the allowed row ids, ascending
+hipError_t launch_masked_compact(const uint32_t* mask, uint64_t n_bits, uint32_t n_tiles, uint32_t* cum, uint64_t* list,
+                                 hipStream_t st);
+// sample[i] = list[i * stride] while i * stride < n_allowed (at most 256 entries)
+hipError_t launch_masked_sample(const uint64_t* list, uint64_t n_allowed, uint64_t stride, uint64_t* sample, hipStream_t st);
+// radius[q] = dist[q][k - 1] when cnt[q] >= k (result lists [nq][k]), else +Inf
+hipError_t launch_masked_radius(const float* dist, const uint32_t* cnt, uint32_t nq, uint32_t k, float* radius, hipStream_t st);
+struct MaskedRerankArgs {
+  const float* Q;            // prepared queries [*][ld]
+  RowsView rows;             // stored rows, fp32 or binary16, plain layout
+  float* radius;             // [nq] in: the radius the pass ran under; out: lowered to the k-th kept distance (NaN: overflowed)
+  uint64_t* pool;            // [*][kPoolCap] in: <= k carried keys, then the pass's hits; out: the best <= k (distance, id) keys
+  uint32_t* pool_cnt;        // [*] in: keys in the pool; out: keys carried
+  const uint32_t* ovf;       // [*] non-zero: the query is answered elsewhere, nothing is written for it
+  uint32_t* work;            // [nq] += rows re-ranked (statistics)
+  uint64_t* out_ids;         // [nq][k]  written behind the last pass
+  float* out_dist;
+  uint32_t* out_count;       // [nq]
+  uint32_t nq, k;
+  uint32_t last;             // 1: the last pass — write the page instead of carrying the keys
+};
+hipError_t launch_masked_rerank(const MaskedRerankArgs& a, hipStream_t st);   // rows.ld <= range_rerank_max_ld()
 
 // per-row statistics for rows [row0, row0+n): inv_norm (cosine), rowp (a,b) for the scan epilogue;
 // *max_sumsq (optional) is raised to the largest |x|^2 seen (the certification margin's norm bound)

@@ -1,6 +1,6 @@
 // What the exact paths share (k_flat.hip: rerank / exhaustive / single-query kernels; k_among.hip; k_range.hip): where the
 // stored rows are (RowsView), their three layouts, the ONE walk from a prepared query to a stored row in the oracle's
-// arithmetic, the (distance, id) key with its NaN rule, the running best-64 list, and the page writer with its sentinel
+// arithmetic, the (distance, id) key with its NaN rule, the running best-64 list, the re-rank of a pool and its sort, and the page writer with its sentinel
 // rule.  Included by ehx_kernels.h behind k_canon.h — the one statement of that arithmetic, whose walkers (canon_dist,
 // canon_dist_lane_t, canon_dist_group_t) the walk here calls and never restates — ahead of the launch arguments that embed
 // a RowsView.
@@ -95,6 +95,46 @@ __device__ __forceinline__ uint64_t keep_best64(uint64_t best, uint64_t key, int
   key = wave_sort64(key, lane);
   const uint64_t rv = __shfl(key, 63 - lane, 64);
   return wave_bitonic_merge64(best < rv ? best : rv, lane);
+}
+
+// ---- a pool of candidates, re-ranked (k_range.hip, k_masked.hip) ----
+// Canonical distances of the pool's rows for a workgroup of T threads: pool[0, cnt) are keys whose low halves are row ids
+// (each row at most once), qs the prepared query in LDS; keys[i] = the (distance, id) key of entry i, kKeyInf where the
+// distance lies above r or is NaN.  Returns, in every lane of a wave, how many entries that wave's lanes kept.
+template <int LAYOUT, int METRIC, uint32_t T>
+__device__ __forceinline__ uint32_t rerank_pool_cut(const RowsView& rows, const float* qs, const uint64_t* __restrict__ pool,
+                                                    uint32_t cnt, float r, uint64_t* keys, uint32_t tid) {
+  const bool writer = walk_by_lane<LAYOUT, true>() || (tid & 3u) == 0;   // this lane files its slot's key
+  uint32_t kept = 0;
+  for (uint32_t i0 = 0; i0 < cnt; i0 += walk_rows<LAYOUT, true>(T)) {
+    const uint32_t i = i0 + walk_slot<LAYOUT, true>(tid);
+    const uint32_t id = i < cnt ? (uint32_t)pool[i] : ~0u;   // (the same in the four lanes of a group)
+    bool mine;
+    const float d = walk_row<LAYOUT, METRIC, true>(rows, qs, id, id < rows.n_rows, tid, &mine);
+    const bool in = mine && d <= r;   // (a NaN distance compares false: never a member)
+    if (i < cnt && writer) keys[i] = dist_key(d, id, in);
+    kept += (uint32_t)__builtin_popcountll(__ballot(in));
+  }
+  return kept;
+}
+
+// ascending bitonic sort of keys[0, m) in LDS, m a power of two >= 2, by a whole workgroup of T threads
+template <uint32_t T>
+__device__ __forceinline__ void block_sort_lds(uint64_t* keys, uint32_t m, uint32_t tid) {
+  for (uint32_t k = 2; k <= m; k <<= 1) {
+    for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+      for (uint32_t t = tid; t < (m >> 1); t += T) {
+        const uint32_t i = ((t & ~(j - 1)) << 1) | (t & (j - 1));   // the pair (i, i + j)
+        const uint64_t a = keys[i], b = keys[i + j];
+        const bool up = (i & k) == 0;
+        if ((a > b) == up) {
+          keys[i] = b;
+          keys[i + j] = a;
+        }
+      }
+      __syncthreads();
+    }
+  }
 }
 
 // ---- a page of results ----

@@ -165,7 +165,8 @@ struct I8Ctx {
   uint32_t pool_cap;
   uint32_t n;            // valid rows
   uint32_t q_tile0;      // global index of this workgroup's query 0 (q_tile * 256)
-  uint32_t pad;
+  uint32_t allow_bits;   // row ids the bitmap covers
+  const uint32_t* allow; // optional row bitmap (masked kNN): a hit whose row's bit is clear is no candidate
 };
 static_assert(sizeof(I8Ctx) <= 64, "I8Ctx slot");
 
@@ -177,7 +178,9 @@ static_assert(sizeof(I8Ctx) <= 64, "I8Ctx slot");
 // waited at the next stage barrier — a quarter of the scan time at 6.25 M x 128, profiles/r06_s_*.)  The row parameters come
 // from HBM here (the tile's LDS copy is long gone); the vmcnt queue is drained before returning, so the caller's counted
 // waits see DMA pieces only.
-template <bool HALF>
+// MASKED: the masked kNN's scans (k_masked.hip) — a hit whose row the bitmap does not allow is dropped before it takes a pool
+// slot.  A flag of the template, so the scans of every other caller run the flush they always ran.
+template <bool HALF, bool MASKED>
 __device__ __attribute__((noinline)) void i8_flush_staging() {
   using L = I8L<HALF>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -199,7 +202,11 @@ __device__ __attribute__((noinline)) void i8_flush_staging() {
     const float4 qq = qp_lds[qloc];
     const float S = i8_score(ctx->rowp[posn], qq, v);
     if (!(S <= qq.w) || posn >= ctx->n) continue;
-    const uint64_t key = ((uint64_t)f32_to_ordered(S) << 32) | (uint64_t)((posn & 0xFFFFFF00u) | (uint32_t)ctx->perm[posn]);
+    const uint32_t id = (posn & 0xFFFFFF00u) | (uint32_t)ctx->perm[posn];
+    if constexpr (MASKED) {
+      if (id >= ctx->allow_bits || !((ctx->allow[id >> 5] >> (id & 31u)) & 1u)) continue;
+    }
+    const uint64_t key = ((uint64_t)f32_to_ordered(S) << 32) | (uint64_t)id;
     const uint32_t q = ctx->q_tile0 + qloc;
     const uint32_t pos = atomicAdd(&ctx->pool_cnt[q], 1u);
     if (pos < cap) ctx->pool[(size_t)q * cap + pos] = key;
@@ -214,7 +221,7 @@ __device__ __attribute__((noinline)) void i8_flush_staging() {
 // stage (value, position, query) for the flush, which judges it.  No read, no wait: the staging buffer belongs to this wave
 // alone, so its fill count lives in a wave-uniform register (stg_n) and the slots are handed out by a ballot and a lane
 // prefix count.
-template <bool HALF>
+template <bool HALF, bool MASKED>
 __device__ __forceinline__ void i8_hit(int v, bool hi, uint32_t r_local, uint32_t tile_row0, int ql, int w, uint32_t& stg_n) {
   using L = I8L<HALF>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -225,7 +232,7 @@ __device__ __forceinline__ void i8_hit(int v, bool hi, uint32_t r_local, uint32_
   if (stg_n + k > L::kStgCap) {  // (64 lanes, at least 64 entries: an emptied buffer takes them all)
     if ((threadIdx.x & 63) == 0) *cnt = stg_n;
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    i8_flush_staging<HALF>();
+    i8_flush_staging<HALF, MASKED>();
     stg_n = 0u;
   }
   if (hi) {
@@ -252,11 +259,12 @@ size_t scan_i8_lds_bytes() { return I8L<false>::kLdsBytes; }
 // registers each; a stage row's 64 bytes are ONE k-step: lane l holds bytes [16 (l >> 4), +16) of row / query l & 15 of
 // its block — one ds_read_b128 per block and stage, twelve per stage as before.  Every block gets exactly one MFMA
 // per stage.  An accumulator block holds, per lane, rows 4 (l >> 4) + 0..3 of its 16 rows for query l & 15.
-template <bool DUMP, bool REV, bool QRES = false, bool HALF = false, bool PAIR = false>
+template <bool DUMP, bool REV, bool QRES = false, bool HALF = false, bool PAIR = false, bool MASKED = false>
 __global__ __launch_bounds__(I8L<HALF>::kThreads, 2) void flat_scan_i8_kernel(const ScanArgsI8 a) {
   static_assert(!QRES || (!REV && !DUMP), "QRES: the run-time-slot loop of the plain scan only");
   static_assert(!PAIR || (!REV && !DUMP && !QRES && !HALF), "PAIR: the run-time-slot loop of the plain scan, stages in pairs");
   static_assert(!HALF || QRES, "HALF: short rows, the query tile resident in LDS");
+  static_assert(!MASKED || !DUMP, "MASKED: the flush of a collecting scan");
   using L = I8L<HALF>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
@@ -318,7 +326,8 @@ __global__ __launch_bounds__(I8L<HALF>::kThreads, 2) void flat_scan_i8_kernel(co
     ctx->pool_cap = a.pool_cap;
     ctx->n = a.n;
     ctx->q_tile0 = qt * kTileQ;
-    ctx->pad = 0u;
+    ctx->allow_bits = MASKED ? a.allow_bits : 0u;
+    if constexpr (MASKED) ctx->allow = a.allow;
   }
 
   const uint32_t tile_begin = a.tile0 + chunk * a.tiles_per_chunk;
@@ -563,7 +572,7 @@ __global__ __launch_bounds__(I8L<HALF>::kThreads, 2) void flat_scan_i8_kernel(co
           v = r == 0 ? c4[0] : (r == 1 ? c4[1] : (r == 2 ? c4[2] : c4[3]));
           r_local = rbase + 16u * (uint32_t)(b >> 2) + (uint32_t)r;
         }
-        i8_hit<HALF>(v, hi, r_local, tile_row0, ql, w, stg_n);
+        i8_hit<HALF, MASKED>(v, hi, r_local, tile_row0, ql, w, stg_n);
       }
     }
   };
@@ -983,7 +992,7 @@ __global__ __launch_bounds__(I8L<HALF>::kThreads, 2) void flat_scan_i8_kernel(co
   if (DUMP) return;
   if (lane == 0) ((uint32_t*)(smem + L::kStgCntOff))[w] = stg_n;
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  i8_flush_staging<HALF>();
+  i8_flush_staging<HALF, MASKED>();
 }
 
 hipError_t launch_flat_scan_i8(const ScanArgsI8& a, hipStream_t st) {
@@ -992,7 +1001,13 @@ hipError_t launch_flat_scan_i8(const ScanArgsI8& a, hipStream_t st) {
                        (const void*)flat_scan_i8_kernel<true, true>, (const void*)flat_scan_i8_kernel<true, false>,
                        (const void*)flat_scan_i8_kernel<false, false, true>,
                        (const void*)flat_scan_i8_kernel<false, false, true, true>,
-                       (const void*)flat_scan_i8_kernel<false, false, false, false, true>};
+                       (const void*)flat_scan_i8_kernel<false, false, false, false, true>,
+                       // the masked kNN's scans: the collecting instantiations once more, their flush testing the bitmap
+                       (const void*)flat_scan_i8_kernel<false, true, false, false, false, true>,
+                       (const void*)flat_scan_i8_kernel<false, false, false, false, false, true>,
+                       (const void*)flat_scan_i8_kernel<false, false, true, false, false, true>,
+                       (const void*)flat_scan_i8_kernel<false, false, true, true, false, true>,
+                       (const void*)flat_scan_i8_kernel<false, false, false, false, true, true>};
   if (hipError_t e = attr.ensure(fns, (int)(sizeof(fns) / sizeof(fns[0])), I8L<false>::kLdsBytes); e != hipSuccess) return e;
   if (a.ld == 0 || a.ld % kRowBI8) return hipErrorInvalidValue;
   const uint32_t grid = a.q_tiles * a.n_chunks;
@@ -1001,7 +1016,24 @@ hipError_t launch_flat_scan_i8(const ScanArgsI8& a, hipStream_t st) {
   hipLaunchKernelGGL((flat_scan_i8_kernel<D, R>), dim3(grid), dim3(I8L<false>::kThreads), I8L<false>::kLdsBytes, st, a)
   // short rows (a tile of at most four stages): the query tile resident in LDS (QRES in the kernel); EHX_I8_QRES=0: off
   const bool qres_on = env().i8_qres;
-  if (a.dump) {
+  if (a.allow) {   // the same choice of instantiation as below, MASKED
+    if (a.dump) return hipErrorInvalidValue;
+    if (rev)
+      hipLaunchKernelGGL((flat_scan_i8_kernel<false, true, false, false, false, true>), dim3(grid), dim3(I8L<false>::kThreads),
+                         I8L<false>::kLdsBytes, st, a);
+    else if (qres_on && env().i8_half && a.ld <= 2 * kRowBI8)
+      hipLaunchKernelGGL((flat_scan_i8_kernel<false, false, true, true, false, true>), dim3(2 * grid), dim3(I8L<true>::kThreads),
+                         I8L<true>::kLdsBytes, st, a);
+    else if (qres_on && a.ld <= 4 * kRowBI8)
+      hipLaunchKernelGGL((flat_scan_i8_kernel<false, false, true, false, false, true>), dim3(grid), dim3(I8L<false>::kThreads),
+                         I8L<false>::kLdsBytes, st, a);
+    else if ((a.ld / kRowBI8) % 2u == 0u)
+      hipLaunchKernelGGL((flat_scan_i8_kernel<false, false, false, false, true, true>), dim3(grid), dim3(I8L<false>::kThreads),
+                         I8L<false>::kLdsBytes, st, a);
+    else
+      hipLaunchKernelGGL((flat_scan_i8_kernel<false, false, false, false, false, true>), dim3(grid), dim3(I8L<false>::kThreads),
+                         I8L<false>::kLdsBytes, st, a);
+  } else if (a.dump) {
     if (rev) EHX_LAUNCH_I8(true, true);
     else EHX_LAUNCH_I8(true, false);
   } else {

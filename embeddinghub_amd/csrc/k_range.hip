@@ -44,24 +44,6 @@ namespace {
 
 constexpr uint32_t kEmitThreads = 256;
 
-// ascending bitonic sort of keys[0, m) in LDS, m a power of two >= 2, by the whole workgroup
-__device__ __forceinline__ void block_sort_lds(uint64_t* keys, uint32_t m, uint32_t tid) {
-  for (uint32_t k = 2; k <= m; k <<= 1) {
-    for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-      for (uint32_t t = tid; t < (m >> 1); t += kEmitThreads) {
-        const uint32_t i = ((t & ~(j - 1)) << 1) | (t & (j - 1));   // the pair (i, i + j)
-        const uint64_t a = keys[i], b = keys[i + j];
-        const bool up = (i & k) == 0;
-        if ((a > b) == up) {
-          keys[i] = b;
-          keys[i + j] = a;
-        }
-      }
-      __syncthreads();
-    }
-  }
-}
-
 // keys[0, n) hold (ordered distance, id) keys, kKeyInf = dropped; keys[n, m) are padded here, m the power of two the sort
 // runs over.  Sorts and writes query q's row: the first min(kept, max_results) pairs, then the sentinels.
 __device__ __forceinline__ void sort_and_emit(uint64_t* keys, uint32_t n, uint32_t kept, uint32_t q, uint32_t max_results,
@@ -71,7 +53,7 @@ __device__ __forceinline__ void sort_and_emit(uint64_t* keys, uint32_t n, uint32
   while (m < n) m <<= 1;
   for (uint32_t i = n + tid; i < m; i += kEmitThreads) keys[i] = kKeyInf;
   __syncthreads();
-  block_sort_lds(keys, m, tid);
+  block_sort_lds<kEmitThreads>(keys, m, tid);
   emit_page([&](uint32_t i) { return keys[i]; }, kept, max_results, out_ids + (size_t)q * max_results,
             out_dist + (size_t)q * max_results, out_count + q, 0, tid, kEmitThreads);
 }
@@ -182,17 +164,7 @@ __global__ __launch_bounds__(kEmitThreads) void range_rerank_kernel(const RangeR
   if (tid == 0) kept_s = 0;
   __syncthreads();
   const uint64_t* pq = a.pool + (size_t)q * kPoolCap;
-  const bool writer = walk_by_lane<LAYOUT, true>() || (tid & 3u) == 0;   // this lane files its slot's key
-  uint32_t kept = 0;
-  for (uint32_t i0 = 0; i0 < cnt; i0 += walk_rows<LAYOUT, true>(kEmitThreads)) {
-    const uint32_t i = i0 + walk_slot<LAYOUT, true>(tid);
-    const uint32_t id = i < cnt ? (uint32_t)pq[i] : ~0u;   // (the same in the four lanes of a group)
-    bool mine;
-    const float d = walk_row<LAYOUT, METRIC, true>(a.rows, qs, id, id < a.rows.n_rows, tid, &mine);
-    const bool in = mine && d <= r;
-    if (i < cnt && writer) keys[i] = dist_key(d, id, in);
-    kept += (uint32_t)__builtin_popcountll(__ballot(in));
-  }
+  const uint32_t kept = rerank_pool_cut<LAYOUT, METRIC, kEmitThreads>(a.rows, qs, pq, cnt, r, keys, tid);
   if (lane == 0 && kept) atomicAdd(&kept_s, kept);
   __syncthreads();
   const uint32_t total = kept_s;

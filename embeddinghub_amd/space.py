@@ -382,6 +382,36 @@ class Space:
                                            ptr(d_cand_off), n_cand, int(max_list_hint), ptr(d_ids), ptr(d_dist),
                                            ptr(d_count)))
 
+    # ---- kNN under a row bitmap (filtered search at ordinary selectivity) ----
+    def knn_masked(self, queries, k, allow, n_bits=None):
+        """The k nearest ALLOWED rows of every query, exact (ehx_knn_masked): the answer of knn_among on the ascending list
+        of allowed rows.  allow: a bool array, entry r allows row r; or packed uint32 words (bit r & 31 of word r >> 5) with
+        n_bits.  Rows at or above n_bits or len(self) are not allowed.  -> ids [nq,k] u64, dist [nq,k] f32, count [nq] u32."""
+        q, pq = _f32(queries)
+        q = q.reshape(-1, self.dims)
+        nq = q.shape[0]
+        words, n_bits = marshal_mask(allow, n_bits)
+        ids = np.full((nq, max(k, 1)), np.uint64(2**64 - 1), dtype=np.uint64)
+        dist = np.full((nq, max(k, 1)), np.inf, dtype=np.float32)
+        cnt = np.zeros(nq, dtype=np.uint32)
+        check(self._L.ehx_knn_masked(self._h, nq, pq, k, words.ctypes.data_as(C.POINTER(C.c_uint32)) if n_bits else None,
+                                     n_bits, ids.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                     dist.ctypes.data_as(C.POINTER(C.c_float)), cnt.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return ids[:, :k], dist[:, :k], cnt
+
+    def knn_masked_device(self, d_queries, k, d_mask, n_bits, d_ids, d_dist, d_count, stream=None):
+        """knn_masked without anything leaving the device: torch CUDA tensors — d_queries [nq, dims] f32, d_mask
+        [ceil(n_bits / 32)] packed u32 words (int32 storage), outputs as knn_device's."""
+        def ptr(t):
+            return C.c_void_p(0 if t is None else (t.data_ptr() if hasattr(t, "data_ptr") else int(t)))
+        nq = d_queries.shape[0] if hasattr(d_queries, "shape") else None
+        if nq is None:
+            raise ValueError("pass torch tensors (queries [nq, dims], mask words)")
+        if hasattr(d_mask, "numel") and d_mask.numel() * 32 < n_bits:
+            raise ValueError("%d mask words hold fewer than n_bits = %d bits" % (d_mask.numel(), n_bits))
+        check(self._L.ehx_knn_masked_device(self._h, C.c_void_p(stream or 0), nq, ptr(d_queries), k, ptr(d_mask), int(n_bits),
+                                            ptr(d_ids), ptr(d_dist), ptr(d_count)))
+
     # ---- range search (every row within a radius) ----
     def _range_args(self, queries, radius, max_results):
         q, pq = _f32(queries)
@@ -480,6 +510,31 @@ def marshal_radius(radius, nq):
     if r.shape[0] != nq:
         raise ValueError("expected %d radii, got %d" % (nq, r.shape[0]))
     return r
+
+
+def marshal_mask(allow, n_bits=None):
+    """The row bitmap of knn_masked -> (packed u32 words [ceil(n_bits / 32)], C-contiguous; n_bits).  allow is a 1-d bool
+    array (entry r allows row r: packed here, bit r & 31 of word r >> 5, n_bits = its length unless a smaller one is given),
+    or 1-d uint32 words already packed, passed through, with n_bits (at most 32 bits per word given)."""
+    a = np.asarray(allow)
+    if a.ndim != 1:
+        raise ValueError("expected a 1-d mask, got shape %s" % (a.shape,))
+    if a.dtype == np.bool_:
+        n = a.shape[0] if n_bits is None else int(n_bits)
+        if n < 0 or n > a.shape[0]:
+            raise ValueError("n_bits = %d outside a bool mask of %d entries" % (n, a.shape[0]))
+        bits = np.zeros((n + 31) // 32 * 32, dtype=np.uint8)
+        bits[:n] = a[:n]
+        words = np.packbits(bits.reshape(-1, 8), axis=1, bitorder="little").reshape(-1).view("<u4")
+        return np.ascontiguousarray(words, dtype=np.uint32), n
+    if a.dtype != np.uint32:
+        raise ValueError("a mask is a bool array or packed uint32 words, got dtype %s" % a.dtype)
+    if n_bits is None:
+        raise ValueError("packed mask words need n_bits")
+    n = int(n_bits)
+    if n < 0 or n > a.shape[0] * 32:
+        raise ValueError("n_bits = %d outside %d mask words" % (n, a.shape[0]))
+    return np.ascontiguousarray(a), n
 
 
 def marshal_id_lists(cand_ids, cand_off=None):

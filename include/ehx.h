@@ -249,6 +249,10 @@ int ehx_knn_among(ehx_space* s, size_t n_queries, const float* queries, uint32_t
 int ehx_knn_among_keys(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, size_t n_allowed,
                        const char* const* keys, const size_t* klens, uint64_t* out_ids, float* out_dist,
                        uint32_t* out_count, size_t* bad_index);
+/* Exact kNN under a row bitmap from host pointers: ehx_knn_masked_device (below: the contract) plus the H2D / D2H copies.
+ * mask has ceil(n_bits / 32) words. */
+int ehx_knn_masked(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, const uint32_t* mask, uint64_t n_bits,
+                   uint64_t* out_ids, float* out_dist, uint32_t* out_count);
 /* Exact range search from host pointers: ehx_range_device (below: the contract) plus the H2D / D2H copies.  radius has
  * n_queries entries; out_total may be NULL. */
 int ehx_range(ehx_space* s, size_t n_queries, const float* queries, const float* radius, uint32_t max_results,
@@ -299,6 +303,25 @@ int ehx_knn_by_ids_device(ehx_space* s, void* stream, size_t n, const uint64_t* 
 int ehx_knn_among_device(ehx_space* s, void* stream, size_t n_queries, const float* d_queries, uint32_t k,
                          const uint64_t* d_cand_ids, const uint64_t* d_cand_off, size_t n_cand, size_t max_list_hint,
                          uint64_t* d_out_ids, float* d_out_dist, uint32_t* d_out_count);
+/* Exact kNN under a row bitmap (filters of ordinary selectivity: a predicate resolved to one bit per row).  Row r is allowed
+ * iff r < n_bits, r is below the call's ONE acquire-load snapshot of the row count, and bit r & 31 of word r >> 5 of d_mask
+ * is set; d_mask has ceil(n_bits / 32) words, bits of the last word beyond n_bits are ignored.  The answer is, byte for
+ * byte, that of ehx_knn_among_device with the one shared list of allowed rows: the first k (query, row) pairs over the
+ * allowed rows in (canonical distance, id) order, with ehx_knn's NaN rule, +-Inf, cosine normalisation, F16 rows as stored
+ * and sentinels (id 2^64 - 1, +Inf) beyond d_out_count[i].  Every space kind ehx_knn_among serves is served; a graph space
+ * answers from its stored rows, its graph is not walked.  n_bits == 0 or a bitmap with no bit set: count 0 for every query.
+ * Errors as ehx_knn_among_device (k == 0 or NULL outputs: EHX_EINVAL; k > EHX_MAX_K_PAGED, row-sharded spaces, rows longer
+ * than 40 960 floats: EHX_EUNSUPPORTED; a dropped space: EHX_ENOTFOUND; no device: EHX_ENODEVICE), and a NULL mask with
+ * n_bits > 0: EHX_EINVAL.  The bitmap is compacted on the device to the ascending list of allowed ids; flat spaces whose
+ * first engine is the int8 filter, at k <= 48 and more than max(1024, rows / 128) allowed rows, are then answered by passes
+ * of that filter's scan under a threshold mapped from a radius — the exact k-th distance among the allowed rows seen so
+ * far, first of a sample of 256 of them — with the bitmap applied where the scan collects its hits and an exact re-rank of
+ * the survivors behind every pass; everything else, and the queries that scan cannot bound or whose pool overflowed, by
+ * the exact scan of the listed rows (ehx_knn_among_device).  The call waits for the device before it returns (it reads the
+ * tiles' allowed counts back); a Set that rewrites rows in place waits for it like for any search.  DESIGN.md §e.12. */
+int ehx_knn_masked_device(ehx_space* s, void* stream, size_t n_queries, const float* d_queries, uint32_t k,
+                          const uint32_t* d_mask, uint64_t n_bits, uint64_t* d_out_ids, float* d_out_dist,
+                          uint32_t* d_out_count);
 /* Exact range search: every row closer than a radius.  With D(q, x) the canonical distance ehx_knn reports (cosine, L2^2,
  * inner product as there), row x belongs to query i's answer iff D is not NaN and D <= d_radius[i] as a float comparison
  * (inclusive: a radius that equals a row's distance byte for byte includes that row; -Inf distances under inner product
