@@ -1,6 +1,7 @@
 // Exact kNN restricted to a caller's lists of row ids: ehx_knn_among (host pointers), ehx_knn_among_device, and
 // ehx_knn_among_keys (one shared list given as stored keys).  The listed rows are scanned exhaustively in the oracle's
 // arithmetic (k_among.hip), whatever the space's mode: a graph space answers from its stored rows, its graph is not walked.
+// Entry scaffold, host staging and the row-length gate are ehx_call.cpp's (search_shared / on_device, HostStage).
 #include "ehx_internal.h"
 
 namespace {
@@ -8,13 +9,11 @@ namespace {
 constexpr uint32_t kAmongGridTarget = 4096;   // workgroups a launch aims for (16 per CU): chosen, not measured
 constexpr uint32_t kAmongMaxBlocks = 1024;    // ... and at most this many key lists per query for the merge
 
-// the checks every entry point starts with, and the gate behind the space's lock
+// the checks every entry point starts with, and why the gate behind the space's lock refuses a row-sharded space
 int among_check(const ehx_space* s, size_t nq, uint32_t k, const void* q, const void* o_ids, const void* o_dist, const void* o_cnt) {
   return check_batch_call(s, nq, k, "k", false, o_ids && o_dist && o_cnt && (!nq || q));
 }
-int among_unsharded(const ehx_space* s, const char* what) {
-  return check_unsharded(s, what, "filtered search over shards is not built yet");
-}
+constexpr const char* kAmongWhy = "filtered search over shards is not built yet";
 
 }  // namespace
 
@@ -26,9 +25,7 @@ int ehx_impl::among_locked(ehx_space* s, hipStream_t st, size_t nq, const float*
                            uint32_t* d_out_count, bool count_queries) {
   int rc;
   if ((rc = check_not_poisoned(s))) return rc;
-  if (s->ld > among_max_ld())   // (before anything is enqueued)
-    return fail(EHX_EUNSUPPORTED, "filtered search keeps a prepared query in LDS: rows of %u floats exceed %u", s->ld,
-                among_max_ld());
+  if ((rc = check_rows_fit_lds(s, "filtered search"))) return rc;   // (before anything is enqueued)
   // the ONE read of the row count: every page's range check answers for the same prefix
   const uint64_t n_pub = s->n.load(std::memory_order_acquire);
   AmongArgs a = {};
@@ -73,31 +70,24 @@ int ehx_impl::among_locked(ehx_space* s, hipStream_t st, size_t nq, const float*
 
 namespace {
 
-// host pointers in, host pointers out, on the space's stream (scratch_mu held): ids [| offsets] staged in among.dLists
+// host pointers in, host pointers out, on the space's stream (on_device): ids [| offsets] staged in among.dLists
 int among_host_locked(ehx_space* s, size_t nq, const float* queries, uint32_t k, const uint64_t* cand_ids,
                       const uint64_t* cand_off, size_t n_cand, uint64_t* out_ids, float* out_dist, uint32_t* out_count) {
   const size_t n_off = cand_off ? nq + 1 : 0;
   int rc;
-  HIP_TRY(hipSetDevice(s->device));
-  if ((rc = s->among.dLists.ensure(n_cand + n_off + 1))) return rc;
-  if ((rc = s->among.dQraw.ensure(nq * s->dims))) return rc;
-  if ((rc = s->among.dOut.ensure(ResultBlock::bytes(nq, k, false)))) return rc;
+  HostStage& h = s->among.host;
+  if ((rc = s->among.dLists.ensure(n_cand + n_off + 1)) || (rc = h.up(s->stream, queries, nq, s->dims, k, false))) return rc;
   uint64_t* d_ids = s->among.dLists.p;
   uint64_t* d_off = cand_off ? d_ids + n_cand : nullptr;
-  const ResultBlock o = ResultBlock::at(s->among.dOut.p, nq, k, false);
-  DrainUnlessOk drain{s->stream};
-  // (pageable host memory: the runtime stages it before the call returns; the staging buffers are this path's alone and
-  // the space's stream orders their reuse)
   if (n_cand) HIP_TRY(hipMemcpyAsync(d_ids, cand_ids, n_cand * sizeof(uint64_t), hipMemcpyHostToDevice, s->stream));
   if (d_off) HIP_TRY(hipMemcpyAsync(d_off, cand_off, n_off * sizeof(uint64_t), hipMemcpyHostToDevice, s->stream));
-  HIP_TRY(hipMemcpyAsync(s->among.dQraw.p, queries, nq * s->dims * sizeof(float), hipMemcpyHostToDevice, s->stream));
   size_t longest = n_cand;
   if (cand_off) {
     longest = 0;
     for (size_t i = 0; i < nq; ++i) longest = std::max<size_t>(longest, cand_off[i + 1] - cand_off[i]);
   }
-  if ((rc = among_locked(s, s->stream, nq, s->among.dQraw.p, k, d_ids, d_off, n_cand, longest, o.ids, o.dist, o.cnt))) return rc;
-  return drain.done(o.copy_out(s->stream, out_ids, out_dist, out_count, nullptr));
+  if ((rc = among_locked(s, s->stream, nq, h.q, k, d_ids, d_off, n_cand, longest, h.out.ids, h.out.dist, h.out.cnt))) return rc;
+  return h.out.copy_out(s->stream, out_ids, out_dist, out_count, nullptr);
 }
 
 }  // namespace
@@ -106,8 +96,7 @@ extern "C" {
 
 int ehx_knn_among(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, const uint64_t* cand_ids,
                   const uint64_t* cand_off, size_t n_cand, uint64_t* out_ids, float* out_dist, uint32_t* out_count) {
-  int rc = among_check(s, n_queries, k, queries, out_ids, out_dist, out_count);
-  if (rc) return rc;
+  if (int rc = among_check(s, n_queries, k, queries, out_ids, out_dist, out_count)) return rc;
   if (n_cand && !cand_ids) return fail(EHX_EINVAL, "NULL argument");
   if (cand_off) {
     if (cand_off[0] > cand_off[n_queries]) return fail(EHX_EINVAL, "cand_off is not non-decreasing");
@@ -116,45 +105,36 @@ int ehx_knn_among(ehx_space* s, size_t n_queries, const float* queries, uint32_t
     if (cand_off[n_queries] != n_cand)
       return fail(EHX_EINVAL, "cand_off ends at %llu, not at n_cand = %zu", (unsigned long long)cand_off[n_queries], n_cand);
   }
-  yield_to_writer(s);
-  std::shared_lock<std::shared_mutex> rl(s->mu);
-  if ((rc = among_unsharded(s, "ehx_knn_among"))) return rc;
-  if (n_queries == 0) return EHX_OK;
-  std::lock_guard<std::mutex> sl(s->scratch_mu);
-  return among_host_locked(s, n_queries, queries, k, cand_ids, cand_off, n_cand, out_ids, out_dist, out_count);
+  return search_on_device(s, "ehx_knn_among", kAmongWhy, n_queries, nullptr, [&] {
+    return among_host_locked(s, n_queries, queries, k, cand_ids, cand_off, n_cand, out_ids, out_dist, out_count);
+  });
 }
 
 int ehx_knn_among_device(ehx_space* s, void* stream, size_t n_queries, const float* d_queries, uint32_t k,
                          const uint64_t* d_cand_ids, const uint64_t* d_cand_off, size_t n_cand, size_t max_list_hint,
                          uint64_t* d_out_ids, float* d_out_dist, uint32_t* d_out_count) {
-  int rc = among_check(s, n_queries, k, d_queries, d_out_ids, d_out_dist, d_out_count);
-  if (rc) return rc;
+  if (int rc = among_check(s, n_queries, k, d_queries, d_out_ids, d_out_dist, d_out_count)) return rc;
   if (n_cand && !d_cand_ids) return fail(EHX_EINVAL, "NULL device pointer");
-  yield_to_writer(s);
-  std::shared_lock<std::shared_mutex> rl(s->mu);
-  if ((rc = among_unsharded(s, "ehx_knn_among_device"))) return rc;
-  if (n_queries == 0) return EHX_OK;
-  std::lock_guard<std::mutex> sl(s->scratch_mu);
-  HIP_TRY(hipSetDevice(s->device));
-  return among_locked(s, (hipStream_t)stream, n_queries, d_queries, k, d_cand_ids, d_cand_off, n_cand, max_list_hint,
-                      d_out_ids, d_out_dist, d_out_count);
+  const hipStream_t st = (hipStream_t)stream;
+  return search_on_device(s, "ehx_knn_among_device", kAmongWhy, n_queries, &st, [&] {
+    return among_locked(s, st, n_queries, d_queries, k, d_cand_ids, d_cand_off, n_cand, max_list_hint,
+                        d_out_ids, d_out_dist, d_out_count);
+  });
 }
 
 int ehx_knn_among_keys(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, size_t n_allowed,
                        const char* const* keys, const size_t* klens, uint64_t* out_ids, float* out_dist,
                        uint32_t* out_count, size_t* bad_index) {
-  int rc = among_check(s, n_queries, k, queries, out_ids, out_dist, out_count);
-  if (rc) return rc;
+  if (int rc = among_check(s, n_queries, k, queries, out_ids, out_dist, out_count)) return rc;
   if (n_allowed && (!keys || !klens)) return fail(EHX_EINVAL, "NULL argument");
-  yield_to_writer(s);
   // ONE shared hold for key lookup and search: the answer describes one state of the space
-  std::shared_lock<std::shared_mutex> rl(s->mu);
-  if ((rc = among_unsharded(s, "ehx_knn_among_keys"))) return rc;
-  std::vector<uint64_t> ids;
-  if ((rc = lookup_keys(s, n_allowed, keys, klens, &ids, bad_index))) return rc;
-  if (n_queries == 0) return EHX_OK;
-  std::lock_guard<std::mutex> sl(s->scratch_mu);
-  return among_host_locked(s, n_queries, queries, k, ids.data(), nullptr, n_allowed, out_ids, out_dist, out_count);
+  return search_shared(s, "ehx_knn_among_keys", kAmongWhy, [&]() -> int {
+    std::vector<uint64_t> ids;
+    if (int rc2 = lookup_keys(s, n_allowed, keys, klens, &ids, bad_index)) return rc2;
+    return on_device(s, n_queries, s->stream, [&] {
+      return among_host_locked(s, n_queries, queries, k, ids.data(), nullptr, n_allowed, out_ids, out_dist, out_count);
+    });
+  });
 }
 
 }  // extern "C"

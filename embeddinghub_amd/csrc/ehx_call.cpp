@@ -1,6 +1,8 @@
-// What the batched entry points (ehx_knn_among*, ehx_range*, ehx_knn_by_keys / _by_ids_device) and the flat chain share
-// around their kernels: argument checks, the poisoned / dropped / sharded gates, key lookup, where the rows are, the
-// result block of a host call, sub-batches, and the int8 scan's arguments.
+// What the batched entry points (ehx_knn_among*, ehx_range*, ehx_knn_masked*, ehx_knn_by_keys / _by_ids_device) and the flat
+// chain share around their kernels: argument checks, the poisoned / dropped / sharded / row-length gates (the entry scaffold
+// that runs them, search_shared / on_device, is ehx_internal.h's), key lookup, where the rows are, the result block and the
+// staging of a host call, the re-run of a sub-batch by another path, the int8 scan's arguments, and the int8 radius scan
+// that serves the range search (one pass) and the bitmap search (several, under a falling radius).
 #include "ehx_internal.h"
 
 namespace ehx_impl {
@@ -35,6 +37,11 @@ int check_unsharded(const ehx_space* s, const char* what, const char* why) {
   if (s->dropped) return fail(EHX_ENOTFOUND, "Not found");
   if (is_parent(s)) return fail(EHX_EUNSUPPORTED, "%s: space '%s' is row-sharded (%s)", what, s->name.c_str(), why);
   return EHX_OK;
+}
+
+int check_rows_fit_lds(const ehx_space* s, const char* subject) {
+  if (s->ld <= among_max_ld()) return EHX_OK;
+  return fail(EHX_EUNSUPPORTED, "%s keeps a prepared query in LDS: rows of %u floats exceed %u", subject, s->ld, among_max_ld());
 }
 
 int lookup_keys(ehx_space* s, size_t n, const char* const* keys, const size_t* klens, std::vector<uint64_t>* ids,
@@ -88,24 +95,30 @@ int ResultBlock::copy_out(hipStream_t st, uint64_t* h_ids, float* h_dist, uint32
   return EHX_OK;
 }
 
-int SubsetBufs::gather(const float* d_queries, const std::vector<uint32_t>& idx, uint32_t dims, uint32_t k_, hipStream_t st) {
-  m = idx.size();
-  k = k_;
+int HostStage::up(hipStream_t st, const float* queries, size_t nq, uint32_t dims, uint32_t k, bool with_total, size_t n_tail) {
   int rc;
-  if ((rc = dFbQ.ensure(m * dims))) return rc;
-  if ((rc = dFbIds.ensure(m * k))) return rc;
-  if ((rc = dFbDist.ensure(m * k))) return rc;
-  if ((rc = dFbCnt.ensure(m))) return rc;
-  if ((rc = dFbIdx.ensure(m))) return rc;
-  // (the index list comes from pageable host memory: the runtime stages it before the call returns)
-  HIP_TRY(hipMemcpyAsync(dFbIdx.p, idx.data(), m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-  HIP_TRY(launch_gather_queries(d_queries, dFbIdx.p, (uint32_t)m, dims, dFbQ.p, st));
+  if ((rc = dQraw.ensure(nq * dims + n_tail)) || (rc = dOut.ensure(ResultBlock::bytes(nq, k, with_total)))) return rc;
+  q = dQraw.p;
+  out = ResultBlock::at(dOut.p, nq, k, with_total);
+  // (pageable host memory: the runtime stages it before the call returns; the staging buffers are their path's alone and
+  // the path's stream orders their reuse)
+  HIP_TRY(hipMemcpyAsync(q, queries, nq * dims * sizeof(float), hipMemcpyHostToDevice, st));
   return EHX_OK;
 }
 
-int SubsetBufs::scatter(uint64_t* d_ids, float* d_dist, uint32_t* d_count, hipStream_t st) const {
+int SubsetBufs::rerun(ehx_space* s, hipStream_t st, const float* d_queries, const std::vector<uint32_t>& idx, uint32_t k,
+                      const Answer& answer, uint64_t* d_ids, float* d_dist, uint32_t* d_count) {
+  const size_t m = idx.size();
+  int rc;
+  if ((rc = dFbQ.ensure(m * s->dims)) || (rc = dFbIds.ensure(m * k)) || (rc = dFbDist.ensure(m * k)) ||
+      (rc = dFbCnt.ensure(m)) || (rc = dFbIdx.ensure(m)))
+    return rc;
+  // (the index list comes from pageable host memory: the runtime stages it before the call returns)
+  HIP_TRY(hipMemcpyAsync(dFbIdx.p, idx.data(), m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  HIP_TRY(launch_gather_queries(d_queries, dFbIdx.p, (uint32_t)m, s->dims, dFbQ.p, st));
+  if ((rc = answer(m, dFbQ.p, dFbIds.p, dFbDist.p, dFbCnt.p))) return rc;
   HIP_TRY(launch_scatter_results(dFbIds.p, dFbDist.p, dFbCnt.p, dFbIdx.p, (uint32_t)m, k, d_ids, d_dist, d_count, st));
-  return EHX_OK;
+  return s->clock.extend(st);
 }
 
 namespace ehx_impl {
@@ -141,6 +154,51 @@ int i8_scan_args(ehx_space* s, ehx_space::I8Set::Buffers& b, const ScanPlan& p, 
   // (cosine / inner product: B_r is one constant, every margin 0; L2^2 on normalised rows: no tile has a margin worth the
   // epilogue's extra permute and multiply-add per query block — 6.25 M x 128: 1.02 -> 1.07 ms per batch with them)
   a->group_b = s->metric == EHX_METRIC_L2SQ && s->h_margin8.load(std::memory_order_relaxed) > 0 && env().i8_groupb ? 1u : 0u;
+  return EHX_OK;
+}
+
+int i8_radius_scan(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, const float* d_queries, const float* d_radius,
+                   const std::vector<TileRange>& passes, const uint32_t* allow, uint32_t allow_bits, bool time_thr,
+                   const PassRerank& rerank, const uint32_t* d_word, RadiusScanOut* out) {
+  ehx_space::I8Set& sc = s->i8set[s->i8_next_set.fetch_add(1, std::memory_order_relaxed) & 1u];
+  std::lock_guard<std::mutex> l(sc.mu);
+  std::vector<ScanPlan> plans;
+  for (auto& ps : passes) {
+    plans.push_back(plan_scan((uint32_t)nq, ps.second, 1, engine().n_cus));
+    if (plans.back().n_chunks > 256) return fail(EHX_EINTERNAL, "scan plan with %u chunks", plans.back().n_chunks);
+  }
+  const ScanPlan& p = plans.back();   // (q_tiles, q_rows are the same for every pass)
+  int rc;
+  ScanArgsI8 a;
+  if ((rc = i8_scan_args(s, sc.buf, p, n_pub, &a))) return rc;
+  a.allow = allow;
+  a.allow_bits = allow_bits;
+  {
+    std::lock_guard<std::mutex> ql(s->i8_enqueue_mu);   // (this batch's launches go onto the stream as one block)
+    if ((rc = wait_searches_in_flight(s, st))) return rc;
+    if ((rc = sc.clock.begin(st, BatchClock::kOutOfRing))) return rc;   // (timed, but not a kNN batch: outside the ring)
+    // thr[q] = +inf, control words zero; every pass then maps the radius as it stands to its threshold (and its marks)
+    HIP_TRY(launch_prep_queries_i8(d_queries, (uint32_t)nq, s->dims, s->ld, s->ld8, p.q_rows, s->metric, sc.buf.dQ.p,
+                                   sc.buf.dQ8.p, sc.buf.dQp8.p, sc.buf.dQuv.p, sc.buf.dThr8.p, sc.buf.dI8Ctl.p, st));
+    for (size_t i = 0; i < passes.size(); ++i) {
+      if (i == 0 && time_thr && (rc = sc.clock.scan_begin(st))) return rc;
+      HIP_TRY(launch_range_thr(d_radius, sc.buf.dQuv.p, s->rows.dMaxSumsq.p, (uint32_t)nq, s->dims, s->metric, sc.buf.dThr8.p,
+                               a.ovf, st));
+      set_scan_pass(a, plans[i], passes[i].first);
+      if (i == 0 && !time_thr && (rc = sc.clock.scan_begin(st))) return rc;
+      HIP_TRY(launch_flat_scan_i8(a, st));
+      if ((rc = rerank(i, i + 1 == passes.size(), a, sc))) return rc;
+    }
+    if ((rc = sc.clock.finish(st))) return rc;
+  }
+  // the verdict: pool counts, overflow flags and marks, and the caller's words (read once per batch, one wait)
+  out->ctl.resize(2 * (size_t)p.q_rows);
+  out->word.resize(nq);
+  out->pool_cnt = out->ctl.data();
+  out->flag = out->ctl.data() + p.q_rows;
+  HIP_TRY(hipMemcpyAsync(out->ctl.data(), sc.buf.dI8Ctl.p, out->ctl.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(out->word.data(), d_word, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
   return EHX_OK;
 }
 

@@ -589,25 +589,13 @@ int flat_chain_rest(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, con
   // run one stage on `subset` (nullptr = every query); *unc = global indices it could not certify
   auto stage = [&](int kind, const std::vector<uint32_t>* subset, std::vector<uint32_t>* unc) -> int {
     const size_t m = subset ? subset->size() : nq;
-    const float* q = d_queries;
-    uint64_t* oi = d_ids;
-    float* od = d_dist;
-    uint32_t* oc = d_count;
-    SubsetBufs& sub = s->scr.sub;
-    if (subset) {
-      if ((rc = sub.gather(d_queries, *subset, s->dims, k, st))) return rc;
-      q = sub.dFbQ.p;
-      oi = sub.dFbIds.p;
-      od = sub.dFbDist.p;
-      oc = sub.dFbCnt.p;
-    }
-    if (kind == kExhaustive) rc = exhaustive_pass(s, n_pub, st, m, q, k, oi, od, oc);
-    else rc = flat_pass(s, n_pub, st, m, q, k, oi, od, oc, kind == kFilter);
+    auto pass = [&](size_t n, const float* q, uint64_t* oi, float* od, uint32_t* oc) {
+      return kind == kExhaustive ? exhaustive_pass(s, n_pub, st, n, q, k, oi, od, oc)
+                                 : flat_pass(s, n_pub, st, n, q, k, oi, od, oc, kind == kFilter);
+    };
+    rc = subset ? s->scr.sub.rerun(s, st, d_queries, *subset, k, pass, d_ids, d_dist, d_count)
+                : pass(nq, d_queries, d_ids, d_dist, d_count);
     if (rc) return rc;
-    if (subset) {
-      if ((rc = sub.scatter(d_ids, d_dist, d_count, st))) return rc;
-      if ((rc = s->clock.extend(st))) return rc;   // (the scatter is part of the pass's batch: writers wait for it too)
-    }
     unc->clear();
     if ((rc = v.post(st))) return rc;
     HIP_TRY(hipStreamSynchronize(st));

@@ -5,7 +5,8 @@
 //   ehx_shards.cpp  row-sharded spaces inside one process (ehx_params.shards)
 //   ehx_write.cpp   Set / BatchSet: staging, upload, row statistics, scan copies, write combiner
 //   ehx_search.cpp  ehx_knn_device / ehx_knn (host pointers, micro-batcher) / keys / merge
-//   ehx_call.cpp    what the batched entry points share: argument checks, key lookup, result blocks, sub-batches
+//   ehx_call.cpp    what the batched entry points share: argument checks, the entry scaffold, key lookup, result blocks, host
+//                   staging, sub-batches, the int8 radius scan
 //   ehx_api.cpp     init, registry, Get, synthetic fill, graph import / export, statistics
 #pragma once
 // (was the head of ehx_api.cpp) C-ABI of the engine (include/ehx.h): process-global space registry, key <-> dense id map
@@ -129,16 +130,17 @@ struct BatchClock {
 using namespace ehx_impl;
 
 // A sub-batch of a call's queries: rows idx[0, m) of the batch gathered into a dense matrix, answered on their own into
-// [m][k] lists, and those written back to the rows they belong to (ehx_call.cpp).  Two instances per space — the engine
-// chain's (ehx_space::Scratch) and the range search's, whose overflow runs the engine chain while its own is in use.
+// [m][k] lists, and those written back to the rows they belong to (ehx_call.cpp).  Three instances per space — the engine
+// chain's (ehx_space::Scratch) and the range and bitmap searches', whose re-runs may go through the engine chain themselves.
 struct SubsetBufs {
   DevBuf<float> dFbQ, dFbDist;
   DevBuf<uint64_t> dFbIds;
   DevBuf<uint32_t> dFbCnt, dFbIdx;
-  size_t m = 0;
-  uint32_t k = 0;
-  int gather(const float* d_queries, const std::vector<uint32_t>& idx, uint32_t dims, uint32_t k_, hipStream_t st);
-  int scatter(uint64_t* d_ids, float* d_dist, uint32_t* d_count, hipStream_t st) const;
+  typedef std::function<int(size_t, const float*, uint64_t*, float*, uint32_t*)> Answer;   // (m, d_q, d_ids, d_dist, d_cnt)
+  // queries idx of the batch d_queries: gathered, answered by another path (on `st`), scattered into the batch's arrays;
+  // the scatter belongs to the last batch of the space's clock (BatchClock::extend: writers wait for it too)
+  int rerun(ehx_space* s, hipStream_t st, const float* d_queries, const std::vector<uint32_t>& idx, uint32_t k,
+            const Answer& answer, uint64_t* d_ids, float* d_dist, uint32_t* d_count);
 };
 
 // The result arrays of one batched call, [nq][k] ids | [nq] totals (range search; may be absent) | [nq][k] distances |
@@ -172,6 +174,16 @@ struct DrainUnlessOk {
     (void)hipStreamSynchronize(st);
     (void)hipGetLastError();
   }
+};
+
+// What a host form of a side search stages on the device, one per path (scratch_mu): the queries, n_tail more floats behind
+// them (the range search's radii) and the results.  up: both sized, the queries copied up on `st`; then q and out are set.
+struct HostStage {
+  DevBuf<float> dQraw;
+  DevBuf<unsigned char> dOut;
+  float* q = nullptr;   // the device queries [nq][dims] | the caller's tail
+  ResultBlock out{};
+  int up(hipStream_t st, const float* queries, size_t nq, uint32_t dims, uint32_t k, bool with_total, size_t n_tail = 0);
 };
 
 // Persistent host threads of a sharded space: worker i drives shard i + 1 (the caller's thread drives shard 0).  Round 2
@@ -440,25 +452,23 @@ struct ehx_space {
     DevBuf<unsigned char> dByOut;
     Event by_ev;
   } by;
-  // exact kNN among a caller's id lists (ehx_among.cpp; scratch_mu): a host call's staged ids | offsets and its results.
-  // The prepared queries, the workgroups' key lists, the merged keys and the page floor are the exhaustive pass's
+  // exact kNN among a caller's id lists (ehx_among.cpp; scratch_mu): a host call's staged ids | offsets, queries and
+  // results.  The prepared queries, the workgroups' key lists, the merged keys and the page floor are the exhaustive pass's
   // (scr.dQ / dPart / dMerged / dGthr); the space's batch clock fences all of them across streams.
   struct Among {
     DevBuf<uint64_t> dLists;
-    DevBuf<float> dQraw;
-    DevBuf<unsigned char> dOut;
+    HostStage host;
   } among;
   // exact range search (ehx_range.cpp; scratch_mu): the queries' pools and control words of the exact kernel, the list of
   // queries a stage answers, the sub-batch an overflow sends through the exact kNN pipeline, and a host call's staged
   // queries | radii and results.  The prepared queries are the exhaustive pass's (scr.dQ), fenced by the space's clock.
   struct Range {
     DevBuf<uint64_t> dPool;      // [slots][kPoolCap]
-    DevBuf<uint32_t> dCtl;       // [slots] pool counts (= totals) | [q_rows] members kept by the int8 path's re-rank
+    DevBuf<uint32_t> dCtl;       // [slots] pool counts (= totals) | [queries] members kept by the int8 path's re-rank
     DevBuf<uint32_t> dSel;       // [slots] query of every slot
     SubsetBufs sub;              // the overflowed queries, answered by the exact kNN pipeline
     DevBuf<uint64_t> dIota;
-    DevBuf<float> dQraw;         // host form: queries | radii
-    DevBuf<unsigned char> dOut;  // host form: ids | distances | counts | totals
+    HostStage host;              // host form: queries | radii, and ids | totals | distances | counts
   } range;
   std::atomic<uint64_t> range_ctr[4] = {};   // test hook: queries answered by the int8 path, by the exact path, pool overflows, truncated
   // exact kNN under a row bitmap (ehx_masked.cpp; scratch_mu): the bitmap's compaction — allowed rows before every
@@ -473,8 +483,7 @@ struct ehx_space {
     DevBuf<uint32_t> dWork;      // [queries of a device batch]
     SubsetBufs sub;
     DevBuf<uint32_t> dMaskRaw;   // host form: the bitmap
-    DevBuf<float> dQraw;         // host form: queries
-    DevBuf<unsigned char> dOut;  // host form: ids | distances | counts
+    HostStage host;              // host form: queries, and ids | distances | counts
   } masked;
   // test hook: queries answered on the scan route, on the exact route, queries that overflowed, scan passes launched, calls
   std::atomic<uint64_t> masked_ctr[5] = {};
@@ -691,6 +700,51 @@ RowsView rows_view(const ehx_space* s, uint64_t n_pub);   // where the rows are,
 // The int8 scan's arguments for a batch planned as `p` in the buffers `b` (grown as needed), all but the pass's own fields
 // (set_scan_pass; dump, sync).  The control words are b.dI8Ctl: [q_rows] pool counts | [q_rows] overflow flags | lock-step.
 int i8_scan_args(ehx_space* s, ehx_space::I8Set::Buffers& b, const ScanPlan& p, uint64_t n_pub, ScanArgsI8* a);
+// The entry scaffold of the list, range and bitmap searches, behind a path's own argument checks.  search_shared: a waiting
+// writer goes first, the space locked shared, a dropped or row-sharded one refused ("<what>: ... (<why>)"), body() under that
+// ONE hold.  on_device, inside it, for nq > 0 queries: scratch_mu, the space's device current, body(); unless that gives
+// EHX_OK, what it left on `st` (the caller's stream; the space's own for a host form) is drained.  search_on_device: both,
+// for an entry point with nothing in between (caller: the caller's stream; nullptr: a host form, on the space's own).
+template <class Body>
+int search_shared(ehx_space* s, const char* what, const char* why, Body&& body) {
+  yield_to_writer(s);
+  std::shared_lock<std::shared_mutex> rl(s->mu);
+  const int rc = check_unsharded(s, what, why);
+  return rc ? rc : body();
+}
+template <class Body>
+int on_device(ehx_space* s, size_t nq, hipStream_t st, Body&& body) {
+  if (nq == 0) return EHX_OK;
+  std::lock_guard<std::mutex> sl(s->scratch_mu);
+  HIP_TRY(hipSetDevice(s->device));
+  DrainUnlessOk drain{st};
+  return drain.done(body());
+}
+template <class Body>
+int search_on_device(ehx_space* s, const char* what, const char* why, size_t nq, const hipStream_t* caller, Body&& body) {
+  return search_shared(s, what, why, [&] { return on_device(s, nq, caller ? *caller : (hipStream_t)s->stream, body); });
+}
+constexpr size_t kSideChunk = 2048;   // queries per device batch of the range and bitmap searches: their pools are 64 MiB
+// "<subject> keeps a prepared query in LDS": rows longer than among_max_ld() are refused before anything is enqueued
+int check_rows_fit_lds(const ehx_space* s, const char* subject);
+// this space's int8 scan serves a radius (range search; the bitmap search's scan route) on the prefix of n_pub rows
+inline bool i8_serves_radius(const ehx_space* s, uint64_t n_pub) {
+  return resolve_engine(s, n_pub) == EHX_ENGINE_I8 && s->ld <= range_rerank_max_ld();
+}
+// Passes of the int8 scan over the tile ranges `passes` (tile0, n_tiles) in one int8 scratch set, nq <= kSideChunk queries:
+// each under the threshold mapped from d_radius[q] as it stands then, the bitmap allow[0, allow_bits) in its flush if given,
+// each followed by rerank(i, last, a, sc), which enqueues the pass's re-rank and records sc.clock.scan_end where its path's
+// timed scan phase ends; that phase opens in front of the first threshold kernel (time_thr) or behind it.  The set's mutex,
+// then i8_enqueue_mu around the launches; ONE wait, then *out (word: d_word[0, nq)).
+struct RadiusScanOut {
+  std::vector<uint32_t> ctl, word;
+  const uint32_t *pool_cnt, *flag;   // [nq] inside ctl; flag 1: the pool overflowed, else non-zero: the bound does not serve
+};
+typedef std::pair<uint32_t, uint32_t> TileRange;
+typedef std::function<int(size_t, bool, const ScanArgsI8&, ehx_space::I8Set&)> PassRerank;
+int i8_radius_scan(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, const float* d_queries, const float* d_radius,
+                   const std::vector<TileRange>& passes, const uint32_t* allow, uint32_t allow_bits, bool time_thr,
+                   const PassRerank& rerank, const uint32_t* d_word, RadiusScanOut* out);
 
 // ---- ehx_among.cpp ----
 // exact kNN among row ids on an unsharded space, locked shared, scratch_mu held, its device current (d_off == nullptr: one

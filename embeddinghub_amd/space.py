@@ -20,6 +20,38 @@ def _f32(a):
     return a, a.ctypes.data_as(C.POINTER(C.c_float))
 
 
+def _ptr(t):
+    """a device pointer for the C call: a torch CUDA tensor, an address (int), or None (NULL)"""
+    return C.c_void_p(0 if t is None else (t.data_ptr() if hasattr(t, "data_ptr") else int(t)))
+
+
+def _results(nq, k, with_total=False):
+    """The result arrays of a batched call, filled as "nothing written": ids [nq, max(k, 1)] u64 (2**64 - 1), dist (same
+    shape) f32 (inf), count [nq] u32 and, with_total, total [nq] u64 -> (the arrays, their C pointers in the same order)"""
+    out = [np.full((nq, max(k, 1)), np.uint64(2**64 - 1), dtype=np.uint64),
+           np.full((nq, max(k, 1)), np.inf, dtype=np.float32), np.zeros(nq, dtype=np.uint32)]
+    if with_total:
+        out.append(np.zeros(nq, dtype=np.uint64))
+    return out, [a.ctypes.data_as(C.POINTER(t)) for a, t in zip(out, (C.c_uint64, C.c_float, C.c_uint32, C.c_uint64))]
+
+
+def _with_arena(call, n_off, cap=1 << 16, grow=4):
+    """rc = call(arena, cap, key_off) with a key arena of `cap` bytes, made `grow` times larger for as long as the call
+    answers ERANGE -> (rc, the arena's bytes, the n_off offsets as a list)"""
+    off = np.zeros(n_off, dtype=np.uint64)
+    while True:
+        arena = C.create_string_buffer(cap)
+        rc = call(arena, cap, off.ctypes.data_as(C.POINTER(C.c_uint64)))
+        if rc != _lib.ERANGE:
+            return rc, arena.raw, off.tolist()
+        cap *= grow
+
+
+def _key_lists(raw, off, cnt, k):
+    """the keys of result lists [n][k] packed in an arena -> list per query of key lists, nearest first"""
+    return [[raw[off[i * k + j]:off[i * k + j + 1]].decode() for j in range(c)] for i, c in enumerate(cnt.tolist())]
+
+
 class Space:
     def __init__(self, name, dims, metric=_lib.METRIC_L2SQ, mode=_lib.MODE_FLAT, M=0, ef_construction=0,
                  ef=0, seed=0, initial_capacity=0, build_batch=0, dtype=_lib.DTYPE_F32, scan=_lib.SCAN_AUTO, shards=0,
@@ -188,12 +220,8 @@ class Space:
         q, pq = _f32(queries)
         q = q.reshape(-1, self.dims)
         nq = q.shape[0]
-        ids = np.full((nq, max(k, 1)), np.uint64(2**64 - 1), dtype=np.uint64)
-        dist = np.full((nq, max(k, 1)), np.inf, dtype=np.float32)
-        cnt = np.zeros(nq, dtype=np.uint32)
-        check(self._L.ehx_knn(self._h, nq, pq, k, ids.ctypes.data_as(C.POINTER(C.c_uint64)),
-                              dist.ctypes.data_as(C.POINTER(C.c_float)),
-                              cnt.ctypes.data_as(C.POINTER(C.c_uint32))))
+        (ids, dist, cnt), out = _results(nq, k)
+        check(self._L.ehx_knn(self._h, nq, pq, k, *out))
         return ids[:, :k], dist[:, :k], cnt
 
     def knn_into(self, queries, k, ids, dist, cnt):
@@ -214,27 +242,10 @@ class Space:
         q, pq = _f32(queries)
         q = q.reshape(-1, self.dims)
         nq = q.shape[0]
-        ids = np.zeros((nq, max(k, 1)), dtype=np.uint64)
-        dist = np.zeros((nq, max(k, 1)), dtype=np.float32)
-        cnt = np.zeros(nq, dtype=np.uint32)
-        off = np.zeros(nq * k + 1, dtype=np.uint64)
-        cap = 1 << 16
-        while True:
-            arena = C.create_string_buffer(cap)
-            rc = self._L.ehx_knn_keys(self._h, nq, pq, k, ids.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                      dist.ctypes.data_as(C.POINTER(C.c_float)),
-                                      cnt.ctypes.data_as(C.POINTER(C.c_uint32)), arena, cap,
-                                      off.ctypes.data_as(C.POINTER(C.c_uint64)))
-            if rc == _lib.ERANGE:
-                cap *= 4
-                continue
-            check(rc)
-            break
-        raw = arena.raw
-        out = []
-        for i in range(nq):
-            out.append([raw[int(off[i * k + j]):int(off[i * k + j + 1])].decode() for j in range(int(cnt[i]))])
-        return out
+        (_, _, cnt), out = _results(nq, k)
+        rc, raw, off = _with_arena(lambda *arena: self._L.ehx_knn_keys(self._h, nq, pq, k, *out, *arena), nq * k + 1)
+        check(rc)
+        return _key_lists(raw, off, cnt, k)
 
     def knn_by_key(self, key, k):
         kb = key.encode() if isinstance(key, str) else bytes(key)
@@ -249,19 +260,10 @@ class Space:
         """the NearestNeighbor RPC by key in ONE engine call -> list of neighbour keys, nearest first"""
         kb = key.encode() if isinstance(key, str) else bytes(key)
         cnt = C.c_uint32()
-        off = np.zeros(k + 1, dtype=np.uint64)
-        cap = 1 << 12
-        while True:
-            arena = C.create_string_buffer(cap)
-            rc = self._L.ehx_knn_by_key_keys(self._h, kb, len(kb), k, None, None, C.byref(cnt), arena, cap,
-                                             off.ctypes.data_as(C.POINTER(C.c_uint64)))
-            if rc == _lib.ERANGE:
-                cap *= 8
-                continue
-            check(rc)
-            break
-        raw = arena.raw
-        o = off.tolist()
+        rc, raw, o = _with_arena(lambda *arena: self._L.ehx_knn_by_key_keys(self._h, kb, len(kb), k, None, None,
+                                                                            C.byref(cnt), *arena),
+                                 k + 1, cap=1 << 12, grow=8)
+        check(rc)
         return [raw[o[j]:o[j + 1]].decode() for j in range(cnt.value)]
 
     def knn_by_keys(self, keys, k):
@@ -270,13 +272,9 @@ class Space:
         -> ids [n,k] u64, dist [n,k] f32, count [n] u32.  An unknown key raises EhxError (ENOTFOUND) whose
         `bad_index` is the position of the first one."""
         n, arr, lens, keep = marshal_keys(keys)
-        ids = np.full((n, max(k, 1)), np.uint64(2**64 - 1), dtype=np.uint64)
-        dist = np.full((n, max(k, 1)), np.inf, dtype=np.float32)
-        cnt = np.zeros(n, dtype=np.uint32)
+        (ids, dist, cnt), out = _results(n, k)
         bad = C.c_size_t(0)
-        rc = self._L.ehx_knn_by_keys(self._h, n, arr, lens, k, ids.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                     dist.ctypes.data_as(C.POINTER(C.c_float)),
-                                     cnt.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(bad))
+        rc = self._L.ehx_knn_by_keys(self._h, n, arr, lens, k, *out, C.byref(bad))
         del keep
         _check_bad(rc, bad)
         return ids[:, :k], dist[:, :k], cnt
@@ -284,50 +282,31 @@ class Space:
     def knn_by_keys_keys(self, keys, k):
         """-> list (per key) of neighbour key lists, nearest first (the NearestNeighbor RPC by key, batched)."""
         n, arr, lens, keep = marshal_keys(keys)
-        ids = np.zeros((n, max(k, 1)), dtype=np.uint64)
-        dist = np.zeros((n, max(k, 1)), dtype=np.float32)
-        cnt = np.zeros(n, dtype=np.uint32)
-        off = np.zeros(n * k + 1, dtype=np.uint64)
+        (_, _, cnt), out = _results(n, k)
         bad = C.c_size_t(0)
-        cap = 1 << 16
-        while True:
-            arena = C.create_string_buffer(cap)
-            rc = self._L.ehx_knn_by_keys_keys(self._h, n, arr, lens, k, ids.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                              dist.ctypes.data_as(C.POINTER(C.c_float)),
-                                              cnt.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(bad), arena, cap,
-                                              off.ctypes.data_as(C.POINTER(C.c_uint64)))
-            if rc == _lib.ERANGE:
-                cap *= 4
-                continue
-            _check_bad(rc, bad)
-            break
+        rc, raw, off = _with_arena(lambda *arena: self._L.ehx_knn_by_keys_keys(self._h, n, arr, lens, k, *out, C.byref(bad),
+                                                                               *arena), n * k + 1)
         del keep
-        raw = arena.raw
-        o = off.tolist()
-        c = cnt.tolist()
-        return [[raw[o[i * k + j]:o[i * k + j + 1]].decode() for j in range(c[i])] for i in range(n)]
+        _check_bad(rc, bad)
+        return _key_lists(raw, off, cnt, k)
 
     # ---- device-resident (torch tensors on the GPU) ----
     def knn_device(self, d_queries, k, d_ids, d_dist, d_count, stream=None):
         """All arguments are device pointers (ints) or torch CUDA tensors; enqueues on `stream`."""
-        def ptr(t):
-            return C.c_void_p(t.data_ptr() if hasattr(t, "data_ptr") else int(t))
         nq = d_queries.shape[0] if hasattr(d_queries, "shape") else None
         if nq is None:
             raise ValueError("pass torch tensors (queries [nq, dims])")
-        check(self._L.ehx_knn_device(self._h, C.c_void_p(stream or 0), nq, ptr(d_queries), k, ptr(d_ids),
-                                     ptr(d_dist), ptr(d_count)))
+        check(self._L.ehx_knn_device(self._h, C.c_void_p(stream or 0), nq, _ptr(d_queries), k, _ptr(d_ids),
+                                     _ptr(d_dist), _ptr(d_count)))
 
     def knn_by_ids_device(self, d_row_ids, k, d_ids, d_dist, d_count, stream=None):
         """The neighbours of stored rows, by row id, without the rows leaving the device: d_row_ids [n] u64, outputs as
         knn_device's (torch CUDA tensors); row i's own id is dropped from its list; an id >= len(self) gives count 0."""
-        def ptr(t):
-            return C.c_void_p(t.data_ptr() if hasattr(t, "data_ptr") else int(t))
         n = d_row_ids.shape[0] if hasattr(d_row_ids, "shape") else None
         if n is None:
             raise ValueError("pass torch tensors (row ids [n])")
-        check(self._L.ehx_knn_by_ids_device(self._h, C.c_void_p(stream or 0), n, ptr(d_row_ids), k, ptr(d_ids),
-                                            ptr(d_dist), ptr(d_count)))
+        check(self._L.ehx_knn_by_ids_device(self._h, C.c_void_p(stream or 0), n, _ptr(d_row_ids), k, _ptr(d_ids),
+                                            _ptr(d_dist), _ptr(d_count)))
 
     # ---- kNN among lists of row ids (filtered search) ----
     def knn_among(self, queries, k, cand_ids, cand_off=None):
@@ -340,14 +319,10 @@ class Space:
         ids_in, off_in = marshal_id_lists(cand_ids, cand_off)
         if off_in is not None and off_in.shape[0] != nq + 1:
             raise ValueError("expected %d per-query lists, got %d" % (nq, off_in.shape[0] - 1))
-        ids = np.full((nq, max(k, 1)), np.uint64(2**64 - 1), dtype=np.uint64)
-        dist = np.full((nq, max(k, 1)), np.inf, dtype=np.float32)
-        cnt = np.zeros(nq, dtype=np.uint32)
+        (ids, dist, cnt), out = _results(nq, k)
         u64p = C.POINTER(C.c_uint64)
         check(self._L.ehx_knn_among(self._h, nq, pq, k, ids_in.ctypes.data_as(u64p),
-                                    off_in.ctypes.data_as(u64p) if off_in is not None else None, ids_in.shape[0],
-                                    ids.ctypes.data_as(u64p), dist.ctypes.data_as(C.POINTER(C.c_float)),
-                                    cnt.ctypes.data_as(C.POINTER(C.c_uint32))))
+                                    off_in.ctypes.data_as(u64p) if off_in is not None else None, ids_in.shape[0], *out))
         return ids[:, :k], dist[:, :k], cnt
 
     def knn_among_keys(self, queries, k, keys):
@@ -357,13 +332,9 @@ class Space:
         q = q.reshape(-1, self.dims)
         nq = q.shape[0]
         n, arr, lens, keep = marshal_keys(keys)
-        ids = np.full((nq, max(k, 1)), np.uint64(2**64 - 1), dtype=np.uint64)
-        dist = np.full((nq, max(k, 1)), np.inf, dtype=np.float32)
-        cnt = np.zeros(nq, dtype=np.uint32)
+        (ids, dist, cnt), out = _results(nq, k)
         bad = C.c_size_t(0)
-        rc = self._L.ehx_knn_among_keys(self._h, nq, pq, k, n, arr, lens, ids.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                        dist.ctypes.data_as(C.POINTER(C.c_float)),
-                                        cnt.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(bad))
+        rc = self._L.ehx_knn_among_keys(self._h, nq, pq, k, n, arr, lens, *out, C.byref(bad))
         del keep
         _check_bad(rc, bad)
         return ids[:, :k], dist[:, :k], cnt
@@ -372,15 +343,13 @@ class Space:
         """knn_among without anything leaving the device: torch CUDA tensors — d_queries [nq, dims] f32, d_cand_ids
         [n_cand] u64 (int64 storage), d_cand_off [nq + 1] or None (one shared list), outputs as knn_device's.
         max_list_hint: an upper bound of one list's length (0 = unknown); it sizes the launch only."""
-        def ptr(t):
-            return C.c_void_p(0 if t is None else (t.data_ptr() if hasattr(t, "data_ptr") else int(t)))
         nq = d_queries.shape[0] if hasattr(d_queries, "shape") else None
         n_cand = d_cand_ids.shape[0] if hasattr(d_cand_ids, "shape") else None
         if nq is None or n_cand is None:
             raise ValueError("pass torch tensors (queries [nq, dims], candidate ids [n_cand])")
-        check(self._L.ehx_knn_among_device(self._h, C.c_void_p(stream or 0), nq, ptr(d_queries), k, ptr(d_cand_ids),
-                                           ptr(d_cand_off), n_cand, int(max_list_hint), ptr(d_ids), ptr(d_dist),
-                                           ptr(d_count)))
+        check(self._L.ehx_knn_among_device(self._h, C.c_void_p(stream or 0), nq, _ptr(d_queries), k, _ptr(d_cand_ids),
+                                           _ptr(d_cand_off), n_cand, int(max_list_hint), _ptr(d_ids), _ptr(d_dist),
+                                           _ptr(d_count)))
 
     # ---- kNN under a row bitmap (filtered search at ordinary selectivity) ----
     def knn_masked(self, queries, k, allow, n_bits=None):
@@ -391,26 +360,21 @@ class Space:
         q = q.reshape(-1, self.dims)
         nq = q.shape[0]
         words, n_bits = marshal_mask(allow, n_bits)
-        ids = np.full((nq, max(k, 1)), np.uint64(2**64 - 1), dtype=np.uint64)
-        dist = np.full((nq, max(k, 1)), np.inf, dtype=np.float32)
-        cnt = np.zeros(nq, dtype=np.uint32)
+        (ids, dist, cnt), out = _results(nq, k)
         check(self._L.ehx_knn_masked(self._h, nq, pq, k, words.ctypes.data_as(C.POINTER(C.c_uint32)) if n_bits else None,
-                                     n_bits, ids.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                     dist.ctypes.data_as(C.POINTER(C.c_float)), cnt.ctypes.data_as(C.POINTER(C.c_uint32))))
+                                     n_bits, *out))
         return ids[:, :k], dist[:, :k], cnt
 
     def knn_masked_device(self, d_queries, k, d_mask, n_bits, d_ids, d_dist, d_count, stream=None):
         """knn_masked without anything leaving the device: torch CUDA tensors — d_queries [nq, dims] f32, d_mask
         [ceil(n_bits / 32)] packed u32 words (int32 storage), outputs as knn_device's."""
-        def ptr(t):
-            return C.c_void_p(0 if t is None else (t.data_ptr() if hasattr(t, "data_ptr") else int(t)))
         nq = d_queries.shape[0] if hasattr(d_queries, "shape") else None
         if nq is None:
             raise ValueError("pass torch tensors (queries [nq, dims], mask words)")
         if hasattr(d_mask, "numel") and d_mask.numel() * 32 < n_bits:
             raise ValueError("%d mask words hold fewer than n_bits = %d bits" % (d_mask.numel(), n_bits))
-        check(self._L.ehx_knn_masked_device(self._h, C.c_void_p(stream or 0), nq, ptr(d_queries), k, ptr(d_mask), int(n_bits),
-                                            ptr(d_ids), ptr(d_dist), ptr(d_count)))
+        check(self._L.ehx_knn_masked_device(self._h, C.c_void_p(stream or 0), nq, _ptr(d_queries), k, _ptr(d_mask), int(n_bits),
+                                            _ptr(d_ids), _ptr(d_dist), _ptr(d_count)))
 
     # ---- range search (every row within a radius) ----
     def _range_args(self, queries, radius, max_results):
@@ -418,63 +382,39 @@ class Space:
         q = q.reshape(-1, self.dims)
         nq = q.shape[0]
         r = marshal_radius(radius, nq)
-        k = max(int(max_results), 1)
-        ids = np.full((nq, k), np.uint64(2**64 - 1), dtype=np.uint64)
-        dist = np.full((nq, k), np.inf, dtype=np.float32)
-        cnt = np.zeros(nq, dtype=np.uint32)
-        total = np.zeros(nq, dtype=np.uint64)
-        return nq, pq, r, ids, dist, cnt, total, (q,)
+        arrays, out = _results(nq, int(max_results), with_total=True)
+        return nq, pq, r, arrays, out, (q,)
 
     def range_search(self, queries, radius, max_results):
         """Every row whose distance to the query is <= radius, exact (ehx_range), nearest first: radius is one number for
         every query or one per query.  -> ids [nq, max_results] u64, dist [nq, max_results] f32, count [nq] u32 (entries
         written per query), total [nq] u64 (rows inside the radius: total > count means the answer was cut)."""
-        nq, pq, r, ids, dist, cnt, total, keep = self._range_args(queries, radius, max_results)
-        u64p = C.POINTER(C.c_uint64)
-        check(self._L.ehx_range(self._h, nq, pq, r.ctypes.data_as(C.POINTER(C.c_float)), max_results,
-                                ids.ctypes.data_as(u64p), dist.ctypes.data_as(C.POINTER(C.c_float)),
-                                cnt.ctypes.data_as(C.POINTER(C.c_uint32)), total.ctypes.data_as(u64p)))
+        nq, pq, r, (ids, dist, cnt, total), out, keep = self._range_args(queries, radius, max_results)
+        check(self._L.ehx_range(self._h, nq, pq, r.ctypes.data_as(C.POINTER(C.c_float)), max_results, *out))
         del keep
         return ids[:, :max_results], dist[:, :max_results], cnt, total
 
     def range_search_keys(self, queries, radius, max_results):
         """range_search with the members' keys -> (list per query of key lists, nearest first; dist; count; total)."""
-        nq, pq, r, ids, dist, cnt, total, keep = self._range_args(queries, radius, max_results)
+        nq, pq, r, (_, dist, cnt, total), out, keep = self._range_args(queries, radius, max_results)
         k = max_results
-        off = np.zeros(nq * max(k, 1) + 1, dtype=np.uint64)
-        u64p = C.POINTER(C.c_uint64)
-        cap = 1 << 16
-        while True:
-            arena = C.create_string_buffer(cap)
-            rc = self._L.ehx_range_keys(self._h, nq, pq, r.ctypes.data_as(C.POINTER(C.c_float)), k,
-                                        ids.ctypes.data_as(u64p), dist.ctypes.data_as(C.POINTER(C.c_float)),
-                                        cnt.ctypes.data_as(C.POINTER(C.c_uint32)), total.ctypes.data_as(u64p), arena, cap,
-                                        off.ctypes.data_as(u64p))
-            if rc == _lib.ERANGE:
-                cap *= 4
-                continue
-            check(rc)
-            break
+        rc, raw, off = _with_arena(lambda *arena: self._L.ehx_range_keys(self._h, nq, pq, r.ctypes.data_as(C.POINTER(C.c_float)),
+                                                                        k, *out, *arena), nq * max(k, 1) + 1)
         del keep
-        raw = arena.raw
-        o = off.tolist()
-        c = cnt.tolist()
-        keys = [[raw[o[i * k + j]:o[i * k + j + 1]].decode() for j in range(c[i])] for i in range(nq)]
-        return keys, dist[:, :k], cnt, total
+        check(rc)
+        return _key_lists(raw, off, cnt, k), dist[:, :k], cnt, total
 
     def range_device(self, d_queries, d_radius, max_results, d_ids, d_dist, d_count, d_total=None, stream=None):
         """range_search without anything leaving the device: torch CUDA tensors — d_queries [nq, dims] f32, d_radius [nq]
         f32, d_ids [nq, max_results] u64 (int64 storage), d_dist [nq, max_results] f32, d_count [nq] u32 (int32 storage),
         d_total [nq] u64 (int64 storage) or None."""
-        def ptr(t):
-            return C.c_void_p(0 if t is None else (t.data_ptr() if hasattr(t, "data_ptr") else int(t)))
         nq = d_queries.shape[0] if hasattr(d_queries, "shape") else None
         if nq is None:
             raise ValueError("pass torch tensors (queries [nq, dims], radius [nq])")
         if hasattr(d_radius, "shape") and tuple(d_radius.shape) != (nq,):
             raise ValueError("expected %d radii, got shape %s" % (nq, tuple(d_radius.shape)))
-        check(self._L.ehx_range_device(self._h, C.c_void_p(stream or 0), nq, ptr(d_queries), ptr(d_radius), max_results,
-                                       ptr(d_ids), ptr(d_dist), ptr(d_count), ptr(d_total)))
+        check(self._L.ehx_range_device(self._h, C.c_void_p(stream or 0), nq, _ptr(d_queries), _ptr(d_radius), max_results,
+                                       _ptr(d_ids), _ptr(d_dist), _ptr(d_count), _ptr(d_total)))
 
     def stats(self):
         st = Stats()
