@@ -2,7 +2,7 @@
 // chain share around their kernels: argument checks, the poisoned / dropped / sharded / row-length gates (the entry scaffold
 // that runs them, search_shared / on_device, is ehx_internal.h's), key lookup, where the rows are, the result block and the
 // staging of a host call, the re-run of a sub-batch by another path, the int8 scan's arguments, and the int8 radius scan
-// that serves the range search (one pass) and the bitmap search (several, under a falling radius).
+// that serves the range search (one pass), the bitmap search and the large-k route (several, under a falling radius).
 #include "ehx_internal.h"
 
 namespace ehx_impl {
@@ -159,7 +159,7 @@ int i8_scan_args(ehx_space* s, ehx_space::I8Set::Buffers& b, const ScanPlan& p, 
 
 int i8_radius_scan(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, const float* d_queries, const float* d_radius,
                    const std::vector<TileRange>& passes, const uint32_t* allow, uint32_t allow_bits, bool time_thr,
-                   const PassRerank& rerank, const uint32_t* d_word, RadiusScanOut* out) {
+                   const PassRerank& rerank, const uint32_t* d_word, RadiusScanOut* out, const ScanSeed& seed) {
   ehx_space::I8Set& sc = s->i8set[s->i8_next_set.fetch_add(1, std::memory_order_relaxed) & 1u];
   std::lock_guard<std::mutex> l(sc.mu);
   std::vector<ScanPlan> plans;
@@ -180,12 +180,15 @@ int i8_radius_scan(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, cons
     // thr[q] = +inf, control words zero; every pass then maps the radius as it stands to its threshold (and its marks)
     HIP_TRY(launch_prep_queries_i8(d_queries, (uint32_t)nq, s->dims, s->ld, s->ld8, p.q_rows, s->metric, sc.buf.dQ.p,
                                    sc.buf.dQ8.p, sc.buf.dQp8.p, sc.buf.dQuv.p, sc.buf.dThr8.p, sc.buf.dI8Ctl.p, st));
+    if (seed) {   // (the first radii: part of the timed scan phase, which then opens here)
+      if ((rc = sc.clock.scan_begin(st)) || (rc = seed(a, sc))) return rc;
+    }
     for (size_t i = 0; i < passes.size(); ++i) {
-      if (i == 0 && time_thr && (rc = sc.clock.scan_begin(st))) return rc;
+      if (i == 0 && time_thr && !seed && (rc = sc.clock.scan_begin(st))) return rc;
       HIP_TRY(launch_range_thr(d_radius, sc.buf.dQuv.p, s->rows.dMaxSumsq.p, (uint32_t)nq, s->dims, s->metric, sc.buf.dThr8.p,
                                a.ovf, st));
       set_scan_pass(a, plans[i], passes[i].first);
-      if (i == 0 && !time_thr && (rc = sc.clock.scan_begin(st))) return rc;
+      if (i == 0 && !time_thr && !seed && (rc = sc.clock.scan_begin(st))) return rc;
       HIP_TRY(launch_flat_scan_i8(a, st));
       if ((rc = rerank(i, i + 1 == passes.size(), a, sc))) return rc;
     }

@@ -38,6 +38,10 @@ struct Env {
   uint32_t stats_every = 2;       // EHX_STATS_EVERY [1, 1024]: the int8 chain brackets the scan phase of every N-th batch of a scratch set with timing events
   bool i8_groupb = true;          // EHX_I8_GROUPB=0: L2^2 spaces scan under one min B per tile (no per-group B margins)
   uint32_t i8_skew = 64;          // EHX_I8_SKEW: half-tile workgroups: start skew of a SIMD's second wave, x 64 cycles (0: none)
+  bool largek = true;             // EHX_LARGEK=0: 48 < k <= 256 stays on the paged exhaustive pass whatever the batch (A/B)
+  uint32_t largek_growth = 4;     // EHX_LARGEK_GROWTH [2, 16]: rows seen by pass j + 1 / rows seen by pass j of the large-k route
+  uint32_t largek_min_queries = 0;  // EHX_LARGEK_MIN_QUERIES [1, 2^24]: the route's batch-size gate, for measuring where the
+                                  // crossover lies (0: kLargeKMinQueries = 64, ehx_internal.h)
   bool rerank_staged = true;      // EHX_RERANK_STAGED=0: every lane of the re-rank walks its own row
   // ---- graph mode ----
   uint64_t build_div = 0;         // EHX_BUILD_DIV >= 2: a bulk-build round is at most 1/DIV of the graph it joins
@@ -110,6 +114,15 @@ inline const Env& env() {
     if (const char* g = str("EHX_I8_SKEW")) {
       const long x = atol(g);
       v.i8_skew = (uint32_t)(x < 0 ? 0 : (x > 4096 ? 4096 : x));
+    }
+    v.largek = flag("EHX_LARGEK", true);
+    if (const char* g = str("EHX_LARGEK_GROWTH")) {
+      const long x = atol(g);
+      v.largek_growth = (uint32_t)(x < 2 ? 2 : (x > 16 ? 16 : x));
+    }
+    if (const char* g = str("EHX_LARGEK_MIN_QUERIES")) {
+      const long x = atol(g);
+      v.largek_min_queries = (uint32_t)(x < 1 ? 1 : (x > (1l << 24) ? (1l << 24) : x));
     }
     v.rerank_staged = flag("EHX_RERANK_STAGED", true);
     if (const char* g = str("EHX_BUILD_DIV")) {

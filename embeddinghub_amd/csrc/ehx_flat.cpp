@@ -483,7 +483,7 @@ static void i8_adapt(ehx_space* s, size_t nq, size_t n_failed, size_t n_short, u
             nq, n_short, std::max(s->i8_kprime_min.load(), kprime), s->i8_width.load());
 }
 
-static void count_scan_batch(ehx_space* s, size_t nq, uint64_t n_pub, uint32_t k, uint64_t elem_bytes) {
+void count_scan_batch(ehx_space* s, size_t nq, uint64_t n_pub, uint32_t k, uint64_t elem_bytes) {
   s->n_queries += nq;
   s->n_dist += (uint64_t)nq * n_pub;
   // SURVEY §8d brute force bytes per batch: N*d*s + B*d*4 + B*k*12 (s = bytes per element the scan reads)
@@ -536,13 +536,16 @@ int knn_device_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_qu
   // the ONE read of the row count in this search (a caller that has a snapshot already passes it)
   if (n_pub == kNoSnapshot) n_pub = s->n.load(std::memory_order_acquire);
   if (k > EHX_MAX_K) {
-    // beyond the candidate capacity of one scan pass: the exhaustive canonical pass, paged (exact, HBM-bound —
-    // the whole shard is read once per page of 64 results and per query)
+    // beyond the candidate capacity of one scan pass: a batch of k <= kLargeKScanMax on an int8 space takes the large-k scan
+    // route (ehx_largek.cpp); everything else the exhaustive canonical pass, paged (exact, HBM-bound — the whole shard is
+    // read once per page of 64 results and per query)
     if (k > EHX_MAX_K_PAGED) return fail(EHX_EUNSUPPORTED, "k=%u exceeds EHX_MAX_K_PAGED=%u", k, EHX_MAX_K_PAGED);
     if (n_pub == 0) {
       HIP_TRY(hipMemsetAsync(d_count, 0, nq * sizeof(uint32_t), st));
       return EHX_OK;
     }
+    // (no int8 scratch set is held here: stage 0's lock is taken further down, the route takes its own)
+    if (largek_serves(s, nq, k, n_pub)) return largek_locked(s, st, n_pub, nq, d_queries, k, d_ids, d_dist, d_count);
     int rc2 = exhaustive_pass(s, n_pub, st, nq, d_queries, k, d_ids, d_dist, d_count);
     if (rc2) return rc2;
     s->n_queries += nq;

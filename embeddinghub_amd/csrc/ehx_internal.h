@@ -487,6 +487,18 @@ struct ehx_space {
   } masked;
   // test hook: queries answered on the scan route, on the exact route, queries that overflowed, scan passes launched, calls
   std::atomic<uint64_t> masked_ctr[5] = {};
+  // exact kNN for EHX_MAX_K < k <= kLargeKScanMax on the int8 radius scan (ehx_largek.cpp; scratch_mu): the queries' carried
+  // exact keys and their number, radii and re-rank work counts, and the sub-batch of flagged queries (answered by the
+  // exhaustive pass).  The route runs in one of the int8 scratch sets.
+  struct LargeK {
+    DevBuf<uint64_t> dTop;       // [queries of a device batch][kLargeKMax]
+    DevBuf<uint32_t> dTopCnt;    // [queries of a device batch]
+    DevBuf<float> dRadius;       // [queries of a device batch]
+    DevBuf<uint32_t> dWork;      // [queries of a device batch]
+    SubsetBufs sub;
+  } largek;
+  // test hook: queries answered on the route, handed to the exhaustive pass, of those the overflowed, scan passes launched, calls
+  std::atomic<uint64_t> largek_ctr[5] = {};
   // int8 filter scratch: everything ONE in-flight batch of the int8 pipeline owns — prepared queries, query tiles +
   // parameters, per-pass thresholds, sample scores, pools, running best list, verdict, batch clock.  TWO sets: a host
   // caller's batch can be enqueued behind another caller's on the space's stream while that one still waits for its
@@ -566,6 +578,7 @@ struct ehx_space {
     among = {};
     range = {};
     masked = {};
+    largek = {};
     one = {};
     xch = {};
     wr = {};
@@ -671,6 +684,8 @@ int i8_stage_enqueue(ehx_space* s, uint64_t n_pub, int set, hipStream_t st, hipE
 int i8_stage_outcome(ehx_space* s, uint64_t n_pub, int set, hipStream_t st, size_t nq, uint32_t k, I8Outcome* o);
 int knn_device_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k,
                       uint64_t* d_ids, float* d_dist, uint32_t* d_count, uint64_t n_pub = kNoSnapshot);
+// the work counters of a batch of nq queries whose first engine scanned n_pub rows of elem_bytes-wide elements
+void count_scan_batch(ehx_space* s, size_t nq, uint64_t n_pub, uint32_t k, uint64_t elem_bytes);
 // the rest of the chain after the int8 stage: fp16 filter, fp32 scan, exhaustive pass, each for what the one before left.
 // eng: what resolve_engine gave for the batch; i8: the outcome of its int8 stage when that is EHX_ENGINE_I8 (the failed
 // queries continue), else nullptr
@@ -742,9 +757,25 @@ struct RadiusScanOut {
 };
 typedef std::pair<uint32_t, uint32_t> TileRange;
 typedef std::function<int(size_t, bool, const ScanArgsI8&, ehx_space::I8Set&)> PassRerank;
+// seed (optional): enqueued behind the query preparation and in front of the first pass, inside the timed scan phase — what
+// writes the first radii from the set's prepared queries (the large-k route's sample, ehx_largek.cpp)
+typedef std::function<int(const ScanArgsI8&, ehx_space::I8Set&)> ScanSeed;
 int i8_radius_scan(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, const float* d_queries, const float* d_radius,
                    const std::vector<TileRange>& passes, const uint32_t* allow, uint32_t allow_bits, bool time_thr,
-                   const PassRerank& rerank, const uint32_t* d_word, RadiusScanOut* out);
+                   const PassRerank& rerank, const uint32_t* d_word, RadiusScanOut* out, const ScanSeed& seed = nullptr);
+
+// ---- ehx_largek.cpp ----
+constexpr uint32_t kLargeKScanMax = kLargeKMax;   // the large-k scan route serves EHX_MAX_K < k <= this
+constexpr size_t kLargeKMinQueries = 64;          // ... for batches of at least one query tile of the int8 wave tile (128 x 64)
+// tile ranges of the route's passes over n_rows rows: pass j (j = 1, 2, ...; the seed is stage 0) ends at the first tile
+// boundary at or beyond kLargeKSample * growth^j rows, the last pass takes the rest (n_rows <= kLargeKSample * growth: one pass)
+std::vector<TileRange> largek_passes(uint64_t n_rows, uint32_t growth);
+// knn_device_locked's gate: this flat-space batch takes the route (i8_serves_radius is part of it)
+bool largek_serves(const ehx_space* s, size_t nq, uint32_t k, uint64_t n_pub);
+// the route, for a batch largek_serves accepts: scratch_mu held, NO int8 scratch set's mutex held (i8_radius_scan takes one);
+// returns with the stream drained
+int largek_locked(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, const float* d_queries, uint32_t k,
+                  uint64_t* d_ids, float* d_dist, uint32_t* d_count);
 
 // ---- ehx_among.cpp ----
 // exact kNN among row ids on an unsharded space, locked shared, scratch_mu held, its device current (d_off == nullptr: one

@@ -522,6 +522,31 @@ struct MaskedRerankArgs {
 };
 hipError_t launch_masked_rerank(const MaskedRerankArgs& a, hipStream_t st);   // rows.ld <= range_rerank_max_ld()
 
+// exact kNN for EHX_MAX_K < k <= kLargeKMax on the int8 radius scan (k_largek.hip)
+constexpr uint32_t kLargeKMax = 256;      // longest carried list: one key per thread of the re-rank's workgroup
+constexpr uint32_t kLargeKSample = 1024;  // rows of the seed's strided sample, at most (>= 4 k for every served k)
+enum { kLargeKPass = 0, kLargeKLast = 1, kLargeKSeed = 2 };   // LargeKRerankArgs::mode
+// pool[q][i] = i * stride for i < n_sample <= kLargeKSample, pool_cnt[q] = n_sample; (n_sample - 1) * stride < n_rows
+hipError_t launch_largek_seed(uint64_t* pool, uint32_t* pool_cnt, uint32_t nq, uint64_t n_rows, uint64_t stride,
+                              uint32_t n_sample, hipStream_t st);
+struct LargeKRerankArgs {
+  const float* Q;            // prepared queries [*][ld]
+  RowsView rows;             // stored rows, fp32 or binary16, plain layout
+  float* radius;             // [nq] in: the radius the pass ran under; out: lowered to the k-th held distance (NaN: overflowed)
+  const uint64_t* pool;      // [*][kPoolCap] the pass's hits (the seed: the sample), keys whose low halves are row ids
+  uint32_t* pool_cnt;        // [*] in: keys in the pool; out: 0
+  const uint32_t* ovf;       // [*] non-zero: the query is answered elsewhere, nothing is written for it (not read by the seed)
+  uint64_t* top;             // [nq][kLargeKMax] the carried exact (distance, id) keys, ascending
+  uint32_t* top_cnt;         // [nq] keys carried (the seed: set to 0)
+  uint32_t* work;            // [nq] rows re-ranked (the seed: set; a pass: +=)
+  uint64_t* out_ids;         // [nq][k]  written behind the last pass
+  float* out_dist;
+  uint32_t* out_count;       // [nq]
+  uint32_t nq, k;
+  uint32_t mode;             // kLargeKPass | kLargeKLast (write the page instead of carrying) | kLargeKSeed (the radius only)
+};
+hipError_t launch_largek_rerank(const LargeKRerankArgs& a, hipStream_t st);   // k <= kLargeKMax, rows.ld <= range_rerank_max_ld()
+
 // per-row statistics for rows [row0, row0+n): inv_norm (cosine), rowp (a,b) for the scan epilogue;
 // *max_sumsq (optional) is raised to the largest |x|^2 seen (the certification margin's norm bound)
 // perm: the fp32 rows are stored block-permuted (single-copy graph spaces); the sums keep the logical order

@@ -10,7 +10,11 @@
 //                       collect pass under the caller's 64-bit threshold keys (the lists as the pass published them, then
 //                       flat_merge_kernel's view of them)
 //   ehx_test_f32_pass   the collect form for flat_scan8_kernel
-// tests/test_f16_device_bound.py checks them.  No production path calls in here.
+// tests/test_f16_device_bound.py checks them.
+// ... and of the large-k scan route (ehx_largek.cpp):
+//   ehx_test_largek_counters   what the route did so far on a space
+//   ehx_test_largek_plan       the route's pass planner, host arithmetic only (no device, no space)
+// No production path calls in here.
 #include "ehx_internal.h"
 
 namespace {
@@ -363,6 +367,29 @@ int ehx_test_f32_pass(ehx_space* s, uint32_t nq, const float* queries, uint32_t 
   if (!gthr_keys) return fail(EHX_EINVAL, "NULL argument");
   return list_pass<false>(s, "ehx_test_f32_pass", nq, queries, kprime, gthr_keys, tile0, n_tiles, nullptr, out_gthr, out_part,
                           out_err, out_merged, nullptr, nullptr, nullptr, out_info);
+}
+
+// queries answered on the large-k scan route, queries it handed to the exhaustive pass, of those the overflowed ones, scan
+// passes launched, calls
+void ehx_test_largek_counters(ehx_space* s, uint64_t out[5]) {
+  for (int i = 0; i < 5; ++i) out[i] = s ? s->largek_ctr[i].load(std::memory_order_relaxed) : 0;
+}
+
+// largek_passes(n_rows, growth) as (tile0, n_tiles) pairs into out_pairs[2 * cap]; returns the number of passes (the first
+// `cap` of them are written); out_consts[4] (optional) = sample rows, smallest k above the certified engines', largest k, fewest queries
+uint32_t ehx_test_largek_plan(uint64_t n_rows, uint32_t growth, uint32_t* out_pairs, uint32_t cap, uint32_t* out_consts) {
+  const std::vector<TileRange> p = largek_passes(n_rows, growth);
+  for (size_t i = 0; i < p.size() && i < cap; ++i) {
+    out_pairs[2 * i] = p[i].first;
+    out_pairs[2 * i + 1] = p[i].second;
+  }
+  if (out_consts) {
+    out_consts[0] = kLargeKSample;
+    out_consts[1] = EHX_MAX_K + 1;
+    out_consts[2] = kLargeKScanMax;
+    out_consts[3] = (uint32_t)kLargeKMinQueries;
+  }
+  return (uint32_t)p.size();
 }
 
 // how many ehx_knn calls the one-launch kernels answered (single_query_kernel, the graph search's one-launch form)

@@ -81,11 +81,19 @@ enum {
 /* what ehx_space_scan_engine reports: the engine that answers first right now */
 enum { EHX_ENGINE_F32 = 0, EHX_ENGINE_F16 = 1, EHX_ENGINE_I8 = 2 };
 
-#define EHX_MAX_K 48u /* largest k served by one scan pass (k + 8 slack < 64 candidate slots) */
-#define EHX_MAX_K_PAGED 1024u /* flat mode serves EHX_MAX_K < k <= this exactly too, by the exhaustive canonical pass in
-                                  pages of 64 results: the whole shard is read once per page and query — fine for the
-                                  occasional large request, not a batch path; graph mode serves any k <= this from its
-                                  result list of max(ef, k) entries, as hnswlib's searchKnn does */
+#define EHX_MAX_K 48u /* largest k served by the certified engine chain: one scan pass holds k + 8 slack < 64 candidate
+                         slots per query */
+#define EHX_MAX_K_PAGED 1024u /* flat mode serves EHX_MAX_K < k <= this exactly too.  Which k is served how:
+                                  48 < k <= 256, at least 64 queries in the device batch, a space whose first engine is
+                                  the int8 filter: the large-k scan route — passes of that filter's scan under a radius
+                                  that falls, an exact re-rank behind every pass; a batch path, the
+                                  exhaustive pass's answer byte for byte.
+                                  Everything else (k > 256, fewer than 64 queries, spaces below the int8 engine's row
+                                  count, EHX_SCAN_F32 / EHX_SCAN_F16): the exhaustive canonical pass in pages of 64
+                                  results — the whole shard is read once per page and query; fine for the occasional
+                                  large request, not a batch path.
+                                  Graph mode serves any k <= this from its result list of max(ef, k) entries, as
+                                  hnswlib's searchKnn does */
 
 typedef struct ehx_space ehx_space; /* opaque; owned by the process-global registry */
 
