@@ -1,8 +1,9 @@
 // What the batched entry points (ehx_knn_among*, ehx_range*, ehx_knn_masked*, ehx_knn_by_keys / _by_ids_device) and the flat
 // chain share around their kernels: argument checks, the poisoned / dropped / sharded / row-length gates (the entry scaffold
 // that runs them, search_shared / on_device, is ehx_internal.h's), key lookup, where the rows are, the result block and the
-// staging of a host call, the re-run of a sub-batch by another path, the int8 scan's arguments, and the int8 radius scan
-// that serves the range search (one pass), the bitmap search and the large-k route (several, under a falling radius).
+// staging of a host call, the re-run of a sub-batch by another path, the int8 scan's arguments, the int8 radius scan that
+// serves the range search (one pass), and the falling-radius kNN on it (radius_knn: several passes) that serves the bitmap
+// search and the large-k route.
 #include "ehx_internal.h"
 
 namespace ehx_impl {
@@ -158,8 +159,8 @@ int i8_scan_args(ehx_space* s, ehx_space::I8Set::Buffers& b, const ScanPlan& p, 
 }
 
 int i8_radius_scan(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, const float* d_queries, const float* d_radius,
-                   const std::vector<TileRange>& passes, const uint32_t* allow, uint32_t allow_bits, bool time_thr,
-                   const PassRerank& rerank, const uint32_t* d_word, RadiusScanOut* out, const ScanSeed& seed) {
+                   const RadiusScan& c, RadiusScanOut* out) {
+  const std::vector<TileRange>& passes = *c.passes;
   ehx_space::I8Set& sc = s->i8set[s->i8_next_set.fetch_add(1, std::memory_order_relaxed) & 1u];
   std::lock_guard<std::mutex> l(sc.mu);
   std::vector<ScanPlan> plans;
@@ -171,8 +172,8 @@ int i8_radius_scan(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, cons
   int rc;
   ScanArgsI8 a;
   if ((rc = i8_scan_args(s, sc.buf, p, n_pub, &a))) return rc;
-  a.allow = allow;
-  a.allow_bits = allow_bits;
+  a.allow = c.allow;
+  a.allow_bits = c.allow_bits;
   {
     std::lock_guard<std::mutex> ql(s->i8_enqueue_mu);   // (this batch's launches go onto the stream as one block)
     if ((rc = wait_searches_in_flight(s, st))) return rc;
@@ -180,17 +181,17 @@ int i8_radius_scan(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, cons
     // thr[q] = +inf, control words zero; every pass then maps the radius as it stands to its threshold (and its marks)
     HIP_TRY(launch_prep_queries_i8(d_queries, (uint32_t)nq, s->dims, s->ld, s->ld8, p.q_rows, s->metric, sc.buf.dQ.p,
                                    sc.buf.dQ8.p, sc.buf.dQp8.p, sc.buf.dQuv.p, sc.buf.dThr8.p, sc.buf.dI8Ctl.p, st));
-    if (seed) {   // (the first radii: part of the timed scan phase, which then opens here)
-      if ((rc = sc.clock.scan_begin(st)) || (rc = seed(a, sc))) return rc;
+    if (c.seed) {   // (the first radii: part of the timed scan phase, which then opens here)
+      if ((rc = sc.clock.scan_begin(st)) || (rc = c.seed(a, sc))) return rc;
     }
     for (size_t i = 0; i < passes.size(); ++i) {
-      if (i == 0 && time_thr && !seed && (rc = sc.clock.scan_begin(st))) return rc;
+      if (i == 0 && c.time_thr && !c.seed && (rc = sc.clock.scan_begin(st))) return rc;
       HIP_TRY(launch_range_thr(d_radius, sc.buf.dQuv.p, s->rows.dMaxSumsq.p, (uint32_t)nq, s->dims, s->metric, sc.buf.dThr8.p,
                                a.ovf, st));
       set_scan_pass(a, plans[i], passes[i].first);
-      if (i == 0 && !time_thr && !seed && (rc = sc.clock.scan_begin(st))) return rc;
+      if (i == 0 && !c.time_thr && !c.seed && (rc = sc.clock.scan_begin(st))) return rc;
       HIP_TRY(launch_flat_scan_i8(a, st));
-      if ((rc = rerank(i, i + 1 == passes.size(), a, sc))) return rc;
+      if ((rc = c.rerank(i, i + 1 == passes.size(), a, sc))) return rc;
     }
     if ((rc = sc.clock.finish(st))) return rc;
   }
@@ -200,8 +201,86 @@ int i8_radius_scan(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, cons
   out->pool_cnt = out->ctl.data();
   out->flag = out->ctl.data() + p.q_rows;
   HIP_TRY(hipMemcpyAsync(out->ctl.data(), sc.buf.dI8Ctl.p, out->ctl.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(out->word.data(), d_word, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(out->word.data(), c.d_word, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
+  return EHX_OK;
+}
+
+int radius_knn(ehx_space* s, hipStream_t st, RadiusKnnBufs& w, uint64_t n_pub, const float* d_queries, const RadiusKnn& c,
+               RadiusKnnTally* t) {
+  const size_t nq = c.out.nq, cap = std::min(kSideChunk, nq);
+  const uint32_t k = c.out.k;
+  int rc;
+  if ((rc = w.dTop.ensure(cap * kLargeKMax)) || (rc = w.dTopCnt.ensure(cap)) || (rc = w.dRadius.ensure(cap)) ||
+      (rc = w.dWork.ensure(cap)))
+    return rc;
+  size_t m = 0;    // the batch in hand: its queries and its rows of the output
+  ResultBlock o{};
+  auto rerank = [&](uint32_t mode, const ScanArgsI8& a, ehx_space::I8Set& sc) -> int {
+    RadiusRerankArgs r = {};
+    r.Q = sc.buf.dQ.p;
+    r.rows = rows_view(s, n_pub);
+    r.radius = w.dRadius.p;
+    r.pool = sc.buf.dPool.p;
+    r.pool_cnt = a.pool_cnt;
+    r.ovf = a.ovf;
+    r.top = w.dTop.p;
+    r.top_cnt = w.dTopCnt.p;
+    r.work = w.dWork.p;
+    r.out_ids = o.ids;
+    r.out_dist = o.dist;
+    r.out_count = o.cnt;
+    r.nq = (uint32_t)m;
+    r.k = k;
+    r.mode = mode;
+    HIP_TRY(launch_radius_rerank(r, st));
+    return EHX_OK;
+  };
+  RadiusScan scan;
+  scan.passes = &c.passes;
+  scan.allow = c.allow;
+  scan.allow_bits = c.allow_bits;
+  scan.time_thr = true;
+  scan.d_word = w.dWork.p;   // the rows re-ranked (the seed's sample included)
+  if (!c.first_radius) {
+    scan.seed = [&](const ScanArgsI8& a, ehx_space::I8Set& sc) -> int {
+      // (the control words are zero, the prepared queries in place): the sample -> the first radii, nothing carried
+      HIP_TRY(launch_radius_seed(sc.buf.dPool.p, a.pool_cnt, (uint32_t)m, n_pub, c.seed_stride, c.n_sample, st));
+      return rerank(kRadiusSeed, a, sc);
+    };
+  }
+  scan.rerank = [&](size_t, bool last, const ScanArgsI8& a, ehx_space::I8Set& sc) -> int {
+    if (int r = rerank(last ? kRadiusLast : kRadiusPass, a, sc)) return r;
+    return last ? sc.clock.scan_end(st) : (int)EHX_OK;   // (the timed scan phase: the seed and every pass with its re-rank)
+  };
+  std::vector<uint32_t> todo;
+  for (size_t q0 = 0; q0 < nq; q0 += kSideChunk) {
+    m = std::min(kSideChunk, nq - q0);
+    o = c.out.from(q0, m);
+    const float* q = d_queries + q0 * s->dims;
+    if (c.first_radius) {   // (and what the seed-mode re-rank does besides: nothing carried, nothing re-ranked yet)
+      if ((rc = c.first_radius(m, q, o, w.dRadius.p))) return rc;
+      HIP_TRY(hipMemsetAsync(w.dTopCnt.p, 0, m * sizeof(uint32_t), st));
+      HIP_TRY(hipMemsetAsync(w.dWork.p, 0, m * sizeof(uint32_t), st));
+    }
+    RadiusScanOut v;
+    if ((rc = i8_radius_scan(s, st, n_pub, m, q, w.dRadius.p, scan, &v))) return rc;
+    todo.clear();
+    uint64_t n_pairs = 0;
+    for (size_t j = 0; j < m; ++j) {
+      n_pairs += v.word[j];
+      if (v.flag[j]) {
+        todo.push_back((uint32_t)j);
+        t->overflowed += v.flag[j] == 1u;
+      }
+    }
+    s->n_dist += n_pairs;
+    t->batches += 1;
+    t->queries += m;
+    t->handed += todo.size();
+    if (todo.empty()) continue;
+    if ((rc = w.sub.rerun(s, st, q, todo, k, c.exact, o.ids, o.dist, o.cnt))) return rc;
+  }
   return EHX_OK;
 }
 

@@ -143,6 +143,16 @@ struct SubsetBufs {
             const Answer& answer, uint64_t* d_ids, float* d_dist, uint32_t* d_count);
 };
 
+// What a falling-radius kNN (radius_knn, ehx_call.cpp) keeps per query of a device batch besides its int8 scratch set, and the
+// sub-batch of the queries it hands on.
+struct RadiusKnnBufs {
+  DevBuf<uint64_t> dTop;       // [queries][kLargeKMax] carried exact keys
+  DevBuf<uint32_t> dTopCnt;    // [queries] their number
+  DevBuf<float> dRadius;       // [queries]
+  DevBuf<uint32_t> dWork;      // [queries] rows re-ranked
+  SubsetBufs sub;
+};
+
 // The result arrays of one batched call, [nq][k] ids | [nq] totals (range search; may be absent) | [nq][k] distances |
 // [nq] counts: the caller's device arrays, or carved from one staging buffer of a host call (ehx_call.cpp).
 struct ResultBlock {
@@ -472,31 +482,21 @@ struct ehx_space {
   } range;
   std::atomic<uint64_t> range_ctr[4] = {};   // test hook: queries answered by the int8 path, by the exact path, pool overflows, truncated
   // exact kNN under a row bitmap (ehx_masked.cpp; scratch_mu): the bitmap's compaction — allowed rows before every
-  // 256-row tile, the ascending list of allowed ids, the sample of it — the queries' radii and re-rank work counts, the
-  // sub-batch of flagged queries (answered by the exact kNN among the whole list), and a host call's staged bitmap,
-  // queries and results.  The scan route runs in one of the int8 scratch sets.
+  // 256-row tile, the ascending list of allowed ids, the sample of it — the scan route's buffers (RadiusKnnBufs; flagged
+  // queries are answered by the exact kNN among the whole list), and a host call's staged bitmap, queries and results.
   struct Masked {
     DevBuf<uint32_t> dCum;       // [n_tiles + 1]
     DevBuf<uint64_t> dList;      // [rows the bitmap covers]
     DevBuf<uint64_t> dSample;    // [256]
-    DevBuf<float> dRadius;       // [queries of a device batch]
-    DevBuf<uint32_t> dWork;      // [queries of a device batch]
-    SubsetBufs sub;
+    RadiusKnnBufs scan;
     DevBuf<uint32_t> dMaskRaw;   // host form: the bitmap
     HostStage host;              // host form: queries, and ids | distances | counts
   } masked;
   // test hook: queries answered on the scan route, on the exact route, queries that overflowed, scan passes launched, calls
   std::atomic<uint64_t> masked_ctr[5] = {};
-  // exact kNN for EHX_MAX_K < k <= kLargeKScanMax on the int8 radius scan (ehx_largek.cpp; scratch_mu): the queries' carried
-  // exact keys and their number, radii and re-rank work counts, and the sub-batch of flagged queries (answered by the
-  // exhaustive pass).  The route runs in one of the int8 scratch sets.
-  struct LargeK {
-    DevBuf<uint64_t> dTop;       // [queries of a device batch][kLargeKMax]
-    DevBuf<uint32_t> dTopCnt;    // [queries of a device batch]
-    DevBuf<float> dRadius;       // [queries of a device batch]
-    DevBuf<uint32_t> dWork;      // [queries of a device batch]
-    SubsetBufs sub;
-  } largek;
+  // exact kNN for EHX_MAX_K < k <= kLargeKScanMax on the int8 radius scan (ehx_largek.cpp; scratch_mu): flagged queries are
+  // answered by the exhaustive pass
+  RadiusKnnBufs largek;
   // test hook: queries answered on the route, handed to the exhaustive pass, of those the overflowed, scan passes launched, calls
   std::atomic<uint64_t> largek_ctr[5] = {};
   // int8 filter scratch: everything ONE in-flight batch of the int8 pipeline owns — prepared queries, query tiles +
@@ -746,23 +746,54 @@ int check_rows_fit_lds(const ehx_space* s, const char* subject);
 inline bool i8_serves_radius(const ehx_space* s, uint64_t n_pub) {
   return resolve_engine(s, n_pub) == EHX_ENGINE_I8 && s->ld <= range_rerank_max_ld();
 }
-// Passes of the int8 scan over the tile ranges `passes` (tile0, n_tiles) in one int8 scratch set, nq <= kSideChunk queries:
-// each under the threshold mapped from d_radius[q] as it stands then, the bitmap allow[0, allow_bits) in its flush if given,
-// each followed by rerank(i, last, a, sc), which enqueues the pass's re-rank and records sc.clock.scan_end where its path's
-// timed scan phase ends; that phase opens in front of the first threshold kernel (time_thr) or behind it.  The set's mutex,
-// then i8_enqueue_mu around the launches; ONE wait, then *out (word: d_word[0, nq)).
+// Passes of the int8 scan over disjoint tile ranges in one int8 scratch set, nq <= kSideChunk queries: each under the
+// threshold mapped from d_radius[q] as it stands then, each followed by its re-rank.  The set's mutex, then i8_enqueue_mu
+// around the launches; ONE wait, then *out (word: d_word[0, nq)).
 struct RadiusScanOut {
   std::vector<uint32_t> ctl, word;
   const uint32_t *pool_cnt, *flag;   // [nq] inside ctl; flag 1: the pool overflowed, else non-zero: the bound does not serve
 };
-typedef std::pair<uint32_t, uint32_t> TileRange;
-typedef std::function<int(size_t, bool, const ScanArgsI8&, ehx_space::I8Set&)> PassRerank;
-// seed (optional): enqueued behind the query preparation and in front of the first pass, inside the timed scan phase — what
-// writes the first radii from the set's prepared queries (the large-k route's sample, ehx_largek.cpp)
-typedef std::function<int(const ScanArgsI8&, ehx_space::I8Set&)> ScanSeed;
+typedef std::pair<uint32_t, uint32_t> TileRange;   // (tile0, n_tiles)
+struct RadiusScan {
+  const std::vector<TileRange>* passes = nullptr;
+  const uint32_t* allow = nullptr;   // optional row bitmap allow[0, allow_bits) in the scan's flush
+  uint32_t allow_bits = 0;
+  bool time_thr = false;             // the timed scan phase opens in front of the first threshold kernel, not behind it
+  // rerank(i, last, a, sc) enqueues pass i's re-rank and records sc.clock.scan_end where its path's timed scan phase ends
+  std::function<int(size_t, bool, const ScanArgsI8&, ehx_space::I8Set&)> rerank;
+  const uint32_t* d_word = nullptr;  // [nq] the caller's words of the verdict
+  // optional: enqueued behind the query preparation and in front of the first pass, inside the timed scan phase (which then
+  // opens here) — what writes the first radii from the set's prepared queries
+  std::function<int(const ScanArgsI8&, ehx_space::I8Set&)> seed;
+};
 int i8_radius_scan(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, const float* d_queries, const float* d_radius,
-                   const std::vector<TileRange>& passes, const uint32_t* allow, uint32_t allow_bits, bool time_thr,
-                   const PassRerank& rerank, const uint32_t* d_word, RadiusScanOut* out, const ScanSeed& seed = nullptr);
+                   const RadiusScan& c, RadiusScanOut* out);
+
+// Exact kNN by the radius scan under a radius that falls (k_radius.hip's header has the algorithm and why it is exact), for
+// every query of c.out in device batches of kSideChunk: stage 0 gives the first radii, every pass's re-rank merges its hits
+// into the carried keys and lowers the radius, ONE verdict is read behind the last pass, and the queries it flags (pool
+// overflow, or the bound does not serve them) are gathered, answered by c.exact and scattered back.  Adds the rows
+// re-ranked to n_dist; the caller's own counters take *t, which holds the batches whose verdict was read whatever is returned.
+struct RadiusKnn {
+  std::vector<TileRange> passes;
+  const uint32_t* allow = nullptr;     // optional row bitmap, as RadiusScan's
+  uint32_t allow_bits = 0;
+  // stage 0, one of two.  first_radius(m, d_q, o, d_radius): enqueued in front of a batch's scan, writes the exact k-th
+  // distance over ANY k rows the search may return (+Inf: none known) for its m queries; it may use o's rows, which are
+  // written again behind it.  Or, without it, the seed inside the scan's timed phase: the strided sample of rows 0, stride,
+  // 2 stride, ... (n_sample <= kLargeKSample of them) re-ranked in every query's pool
+  std::function<int(size_t, const float*, const ResultBlock&, float*)> first_radius;
+  uint64_t seed_stride = 0;
+  uint32_t n_sample = 0;
+  ResultBlock out;                     // out.k <= kLargeKMax
+  SubsetBufs::Answer exact;
+};
+struct RadiusKnnTally {
+  uint64_t batches = 0, queries = 0;     // device batches whose verdict was read, and their queries
+  uint64_t handed = 0, overflowed = 0;   // of those: queries left to c.exact; of these, the ones whose pool overflowed
+};
+int radius_knn(ehx_space* s, hipStream_t st, RadiusKnnBufs& w, uint64_t n_pub, const float* d_queries, const RadiusKnn& c,
+               RadiusKnnTally* t);
 
 // ---- ehx_largek.cpp ----
 constexpr uint32_t kLargeKScanMax = kLargeKMax;   // the large-k scan route serves EHX_MAX_K < k <= this
@@ -772,7 +803,7 @@ constexpr size_t kLargeKMinQueries = 64;          // ... for batches of at least
 std::vector<TileRange> largek_passes(uint64_t n_rows, uint32_t growth);
 // knn_device_locked's gate: this flat-space batch takes the route (i8_serves_radius is part of it)
 bool largek_serves(const ehx_space* s, size_t nq, uint32_t k, uint64_t n_pub);
-// the route, for a batch largek_serves accepts: scratch_mu held, NO int8 scratch set's mutex held (i8_radius_scan takes one);
+// the route, for a batch largek_serves accepts: scratch_mu held, NO int8 scratch set's mutex held (radius_knn takes one);
 // returns with the stream drained
 int largek_locked(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, const float* d_queries, uint32_t k,
                   uint64_t* d_ids, float* d_dist, uint32_t* d_count);

@@ -210,7 +210,7 @@ hipError_t launch_flat_scan16(const ScanArgs16& a, hipStream_t st);
 inline float scan16_eps(uint32_t dims) { return 1.0e-3f + 2.0e-7f * (float)dims; }
 
 // ---- int8-MFMA filter scan (k_flati8.hip) ----
-constexpr uint32_t kPoolCap = 4096;    // candidate keys one query can collect in one pass (overflow: query flagged)
+// (kPoolCap, the candidate keys one query can collect in one pass, is k_exact_common.h's: the pool re-rank carves LDS by it)
 constexpr uint32_t kSyncWordsI8 = 1024; // lock-step progress words of the int8 scan: [n_chunks <= 256][4 query tiles]
 constexpr uint32_t kMerged8 = 256;     // default width of the running best list of the int8 pipeline
 constexpr uint32_t kMerged8Max = 1024; // widest list (a space widens its list when queries go uncertified: ehx_flat.cpp)
@@ -506,30 +506,16 @@ hipError_t launch_masked_compact(const uint32_t* mask, uint64_t n_bits, uint32_t
 hipError_t launch_masked_sample(const uint64_t* list, uint64_t n_allowed, uint64_t stride, uint64_t* sample, hipStream_t st);
 // radius[q] = dist[q][k - 1] when cnt[q] >= k (result lists [nq][k]), else +Inf
 hipError_t launch_masked_radius(const float* dist, const uint32_t* cnt, uint32_t nq, uint32_t k, float* radius, hipStream_t st);
-struct MaskedRerankArgs {
-  const float* Q;            // prepared queries [*][ld]
-  RowsView rows;             // stored rows, fp32 or binary16, plain layout
-  float* radius;             // [nq] in: the radius the pass ran under; out: lowered to the k-th kept distance (NaN: overflowed)
-  uint64_t* pool;            // [*][kPoolCap] in: <= k carried keys, then the pass's hits; out: the best <= k (distance, id) keys
-  uint32_t* pool_cnt;        // [*] in: keys in the pool; out: keys carried
-  const uint32_t* ovf;       // [*] non-zero: the query is answered elsewhere, nothing is written for it
-  uint32_t* work;            // [nq] += rows re-ranked (statistics)
-  uint64_t* out_ids;         // [nq][k]  written behind the last pass
-  float* out_dist;
-  uint32_t* out_count;       // [nq]
-  uint32_t nq, k;
-  uint32_t last;             // 1: the last pass — write the page instead of carrying the keys
-};
-hipError_t launch_masked_rerank(const MaskedRerankArgs& a, hipStream_t st);   // rows.ld <= range_rerank_max_ld()
 
-// exact kNN for EHX_MAX_K < k <= kLargeKMax on the int8 radius scan (k_largek.hip)
+// exact kNN on the int8 radius scan under a radius that falls (k_radius.hip): the bitmap search's scan route (k <= 48) and
+// the flat chain's route for EHX_MAX_K < k <= kLargeKMax
 constexpr uint32_t kLargeKMax = 256;      // longest carried list: one key per thread of the re-rank's workgroup
-constexpr uint32_t kLargeKSample = 1024;  // rows of the seed's strided sample, at most (>= 4 k for every served k)
-enum { kLargeKPass = 0, kLargeKLast = 1, kLargeKSeed = 2 };   // LargeKRerankArgs::mode
+constexpr uint32_t kLargeKSample = 1024;  // rows of a seed's sample, at most (>= 4 k for every served k)
+enum { kRadiusPass = 0, kRadiusLast = 1, kRadiusSeed = 2 };   // RadiusRerankArgs::mode
 // pool[q][i] = i * stride for i < n_sample <= kLargeKSample, pool_cnt[q] = n_sample; (n_sample - 1) * stride < n_rows
-hipError_t launch_largek_seed(uint64_t* pool, uint32_t* pool_cnt, uint32_t nq, uint64_t n_rows, uint64_t stride,
+hipError_t launch_radius_seed(uint64_t* pool, uint32_t* pool_cnt, uint32_t nq, uint64_t n_rows, uint64_t stride,
                               uint32_t n_sample, hipStream_t st);
-struct LargeKRerankArgs {
+struct RadiusRerankArgs {
   const float* Q;            // prepared queries [*][ld]
   RowsView rows;             // stored rows, fp32 or binary16, plain layout
   float* radius;             // [nq] in: the radius the pass ran under; out: lowered to the k-th held distance (NaN: overflowed)
@@ -537,15 +523,15 @@ struct LargeKRerankArgs {
   uint32_t* pool_cnt;        // [*] in: keys in the pool; out: 0
   const uint32_t* ovf;       // [*] non-zero: the query is answered elsewhere, nothing is written for it (not read by the seed)
   uint64_t* top;             // [nq][kLargeKMax] the carried exact (distance, id) keys, ascending
-  uint32_t* top_cnt;         // [nq] keys carried (the seed: set to 0)
-  uint32_t* work;            // [nq] rows re-ranked (the seed: set; a pass: +=)
+  uint32_t* top_cnt;         // [nq] keys carried (the seed: set to 0; without a seed: zero before the first pass)
+  uint32_t* work;            // [nq] rows re-ranked (the seed: set; a pass: +=; without a seed: zero before the first pass)
   uint64_t* out_ids;         // [nq][k]  written behind the last pass
   float* out_dist;
   uint32_t* out_count;       // [nq]
   uint32_t nq, k;
-  uint32_t mode;             // kLargeKPass | kLargeKLast (write the page instead of carrying) | kLargeKSeed (the radius only)
+  uint32_t mode;             // kRadiusPass | kRadiusLast (write the page instead of carrying) | kRadiusSeed (the radius only)
 };
-hipError_t launch_largek_rerank(const LargeKRerankArgs& a, hipStream_t st);   // k <= kLargeKMax, rows.ld <= range_rerank_max_ld()
+hipError_t launch_radius_rerank(const RadiusRerankArgs& a, hipStream_t st);   // k <= kLargeKMax, rows.ld <= range_rerank_max_ld()
 
 // per-row statistics for rows [row0, row0+n): inv_norm (cosine), rowp (a,b) for the scan epilogue;
 // *max_sumsq (optional) is raised to the largest |x|^2 seen (the certification margin's norm bound)
@@ -628,6 +614,21 @@ struct DynLdsAttr {
     return hipSuccess;
   }
 };
+
+// The launch of a pool re-rank (pool_rerank_sorted: range_rerank_kernel, radius_rerank_kernel), one workgroup of `threads`
+// per query: fns[half * 3 + metric], the kernel's instantiations; args_ok: what the kernel's own arguments must satisfy.
+template <class Args>
+hipError_t launch_pool_rerank(void (*const (&fns)[6])(const Args), DynLdsAttr& attr, const Args& a, bool args_ok,
+                              uint32_t threads, hipStream_t st) {
+  if (a.nq == 0) return hipSuccess;
+  if (!args_ok || (a.rows.ld & 3u) || a.rows.ld > range_rerank_max_ld() || a.rows.metric < 0 || a.rows.metric > 2)
+    return hipErrorInvalidValue;
+  const size_t lds = pool_rerank_lds_bytes(a.rows.ld);
+  hipError_t e = attr.ensure(fns, 6, lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(fns[(a.rows.x_half ? 3 : 0) + a.rows.metric], dim3(a.nq), dim3(threads), lds, st, a);
+  return hipGetLastError();
+}
 
 struct InsertArgs {
   const float* Xs;         // search copy (launch_make_search_copy)

@@ -1,16 +1,15 @@
 // Exact kNN under a row bitmap: ehx_knn_masked (host pointers) and ehx_knn_masked_device.  Row r is allowed iff r < n_bits,
 // r is below the call's ONE snapshot of the row count and bit r & 31 of word r >> 5 is set; the answer is ehx_knn_among's
-// with the ascending list of allowed rows, byte for byte (k_masked.hip's header has the argument).
+// with the ascending list of allowed rows, byte for byte (k_radius.hip's header has the argument).
 //   compaction   the bitmap -> allowed rows before every 256-row tile (read back once: the host plans the passes from
 //                them) and the ascending list of allowed ids
 //   exact route  among_locked over that list: spaces the range search's int8 path does not serve, k > 48, lists of at
 //                most max(1024, rows / 128) rows
-//   scan route   the exact k-th distance of a sample of <= 256 allowed rows is the first radius; then the radius scan
-//                (i8_radius_scan, ehx_call.cpp — the range search's, with several passes and a radius that falls): passes
-//                of flat_scan_i8_kernel over disjoint tile ranges, cut by ALLOWED rows seen (4096, 65536, ...: sound
-//                wherever the bitmap's rows cluster), each under the threshold of the radius so far with the bitmap in its
-//                flush, each followed by masked_rerank_kernel; no host wait between passes.  Queries whose pool overflowed
-//                or which the bound does not serve take the exact route afterwards (SubsetBufs::rerun).
+//   scan route   the falling-radius kNN (radius_knn, ehx_call.cpp; k_radius.hip's header has the kernels and the argument)
+//                with the bitmap in the int8 scan's flush: the first radius is the exact k-th distance of a sample of <= 256
+//                allowed rows, taken by the list scan (its tiles share the sample's rows between queries), the passes are cut
+//                by ALLOWED rows seen (4096, 65536, ...: sound wherever the bitmap's rows cluster), and the queries it
+//                hands on — pool overflow, or the bound does not serve them — take the exact route
 // Entry scaffold and host staging are ehx_call.cpp's (search_shared / on_device, HostStage).
 #include "ehx_internal.h"
 
@@ -50,58 +49,6 @@ std::vector<TileRange> masked_passes(const std::vector<uint32_t>& cum, uint32_t 
   return out;
 }
 
-// The scan route for a batch of nq <= kSideChunk queries; *todo = the queries it leaves to the exact route.
-int masked_scan_stage(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, const float* d_queries, uint32_t k,
-                      const uint32_t* d_mask, uint64_t n_eff, uint64_t n_sample, const std::vector<TileRange>& passes,
-                      const ResultBlock& o, std::vector<uint32_t>* todo) {
-  int rc;
-  if ((rc = s->masked.dRadius.ensure(nq)) || (rc = s->masked.dWork.ensure(nq))) return rc;
-  // stage 0: the exact k nearest of the sample, into the caller's arrays (every query's row is written again below, by the
-  // last pass or by the exact route); their k-th distance is the first radius
-  // (its queries are not counted there: the stage's verdict counts every query once)
-  if ((rc = among_locked(s, st, nq, d_queries, k, s->masked.dSample.p, nullptr, n_sample, 0, o.ids, o.dist, o.cnt, false)))
-    return rc;
-  HIP_TRY(launch_masked_radius(o.dist, o.cnt, (uint32_t)nq, k, s->masked.dRadius.p, st));
-  HIP_TRY(hipMemsetAsync(s->masked.dWork.p, 0, nq * sizeof(uint32_t), st));
-  // the passes: the radius scan with the bitmap in its flush, each pass's re-rank lowering the radius for the next
-  RadiusScanOut v;   // word[q]: the rows re-ranked
-  rc = i8_radius_scan(s, st, n_pub, nq, d_queries, s->masked.dRadius.p, passes, d_mask, (uint32_t)n_eff, true,
-                      [&](size_t, bool last, const ScanArgsI8& a, ehx_space::I8Set& sc) {
-    MaskedRerankArgs r = {};
-    r.Q = sc.buf.dQ.p;
-    r.rows = rows_view(s, n_pub);
-    r.radius = s->masked.dRadius.p;
-    r.pool = sc.buf.dPool.p;
-    r.pool_cnt = a.pool_cnt;
-    r.ovf = a.ovf;
-    r.work = s->masked.dWork.p;
-    r.out_ids = o.ids;
-    r.out_dist = o.dist;
-    r.out_count = o.cnt;
-    r.nq = (uint32_t)nq;
-    r.k = k;
-    r.last = last ? 1u : 0u;
-    HIP_TRY(launch_masked_rerank(r, st));
-    return last ? sc.clock.scan_end(st) : (int)EHX_OK;   // (the timed scan phase is every pass with its re-rank)
-  }, s->masked.dWork.p, &v);
-  if (rc) return rc;
-  todo->clear();
-  uint64_t n_pairs = 0, n_over = 0;
-  for (size_t q = 0; q < nq; ++q) {
-    n_pairs += v.word[q];
-    if (v.flag[q]) {
-      todo->push_back((uint32_t)q);
-      n_over += v.flag[q] == 1u;
-    }
-  }
-  s->n_dist += n_pairs;
-  s->n_queries += nq - todo->size();
-  s->masked_ctr[0] += nq - todo->size();
-  s->masked_ctr[2] += n_over;
-  s->masked_ctr[3] += passes.size();
-  return EHX_OK;
-}
-
 // an unsharded space, locked shared, scratch_mu held, its device current; everything is enqueued on `st`
 int masked_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, const uint32_t* d_mask,
                   uint64_t n_bits, const ResultBlock& out) {
@@ -131,24 +78,32 @@ int masked_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_querie
     return among_locked(s, st, nq, d_queries, k, s->masked.dList.p, nullptr, n_allowed, 0, out.ids, out.dist, out.cnt);
   }
   const uint64_t stride = (n_allowed + kMaskedSample - 1) / kMaskedSample;
+  RadiusKnn c;
+  c.passes = masked_passes(cum, n_tiles);
+  c.allow = d_mask;
+  c.allow_bits = (uint32_t)n_eff;
+  c.out = out;
+  // stage 0: the exact k nearest of the sample, by the list scan, into the caller's arrays (every query's row is written
+  // again, by the last pass or by the exact route; its queries are not counted there: the verdict counts every query once);
+  // their k-th distance is the first radius, +Inf while the sample gives fewer than k
   const uint64_t n_sample = (n_allowed + stride - 1) / stride;
+  c.first_radius = [&](size_t m, const float* q, const ResultBlock& o, float* d_radius) -> int {
+    if (int r = among_locked(s, st, m, q, k, s->masked.dSample.p, nullptr, n_sample, 0, o.ids, o.dist, o.cnt, false)) return r;
+    HIP_TRY(launch_masked_radius(o.dist, o.cnt, (uint32_t)m, k, d_radius, st));
+    return EHX_OK;
+  };
+  c.exact = [&](size_t n, const float* sq, uint64_t* ids, float* dist, uint32_t* cnt) {
+    return among_locked(s, st, n, sq, k, s->masked.dList.p, nullptr, n_allowed, 0, ids, dist, cnt);
+  };
   HIP_TRY(launch_masked_sample(s->masked.dList.p, n_allowed, stride, s->masked.dSample.p, st));
-  const std::vector<TileRange> passes = masked_passes(cum, n_tiles);
-  std::vector<uint32_t> todo;
-  for (size_t q0 = 0; q0 < nq; q0 += kSideChunk) {
-    const size_t m = std::min(kSideChunk, nq - q0);
-    const float* q = d_queries + q0 * s->dims;
-    const ResultBlock o = out.from(q0, m);
-    if ((rc = masked_scan_stage(s, st, n_pub, m, q, k, d_mask, n_eff, n_sample, passes, o, &todo))) return rc;
-    if (todo.empty()) continue;
-    // flagged queries: gathered, answered by the exact kNN among the whole list, scattered back
-    rc = s->masked.sub.rerun(s, st, q, todo, k, [&](size_t n, const float* sq, uint64_t* ids, float* dist, uint32_t* cnt) {
-      return among_locked(s, st, n, sq, k, s->masked.dList.p, nullptr, n_allowed, 0, ids, dist, cnt);
-    }, o.ids, o.dist, o.cnt);
-    if (rc) return rc;
-    s->masked_ctr[1] += todo.size();
-  }
-  return EHX_OK;
+  RadiusKnnTally t;
+  rc = radius_knn(s, st, s->masked.scan, n_pub, d_queries, c, &t);
+  s->n_queries += t.queries - t.handed;   // (among_locked counts the rest)
+  s->masked_ctr[0] += t.queries - t.handed;
+  s->masked_ctr[1] += t.handed;
+  s->masked_ctr[2] += t.overflowed;
+  s->masked_ctr[3] += t.batches * c.passes.size();
+  return rc;
 }
 
 // host pointers in, host pointers out, on the space's stream (on_device): the bitmap staged in masked.dMaskRaw

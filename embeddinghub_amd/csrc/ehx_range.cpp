@@ -98,9 +98,11 @@ int range_i8_stage(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, cons
                    uint32_t max_results, const ResultBlock& o, std::vector<uint32_t>* todo, std::vector<uint8_t>* counted) {
   int rc;
   if ((rc = s->range.dCtl.ensure(nq))) return rc;
-  RadiusScanOut v;   // word[q]: what the re-rank kept
   const std::vector<TileRange> all = {{0u, (uint32_t)((n_pub + kTileRows16 - 1) / kTileRows16)}};
-  rc = i8_radius_scan(s, st, n_pub, nq, d_queries, d_radius, all, nullptr, 0, false, [&](size_t, bool, const ScanArgsI8& a, ehx_space::I8Set& sc) {
+  RadiusScan scan;
+  scan.passes = &all;
+  scan.d_word = s->range.dCtl.p;   // what the re-rank kept
+  scan.rerank = [&](size_t, bool, const ScanArgsI8& a, ehx_space::I8Set& sc) {
     if (int rc2 = sc.clock.scan_end(st)) return rc2;   // (the timed scan phase is the scan alone)
     RangeRerankArgs r = {};
     r.Q = sc.buf.dQ.p;
@@ -118,8 +120,9 @@ int range_i8_stage(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, cons
     r.max_results = max_results;
     HIP_TRY(launch_range_rerank(r, st));
     return (int)EHX_OK;
-  }, s->range.dCtl.p, &v);
-  if (rc) return rc;
+  };
+  RadiusScanOut v;
+  if ((rc = i8_radius_scan(s, st, n_pub, nq, d_queries, d_radius, scan, &v))) return rc;
   todo->clear();
   counted->clear();
   uint64_t n_pairs = 0, n_trunc = 0, n_over = 0;

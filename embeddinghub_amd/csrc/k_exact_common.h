@@ -16,6 +16,7 @@ __host__ __device__ inline int row_layout(uint32_t x_half, uint32_t x_perm) {
 }
 
 constexpr size_t kMaxLds = 160u * 1024u;   // LDS of one CU: the most one workgroup can have
+constexpr uint32_t kPoolCap = 4096;        // candidate keys one query can collect in one pass (overflow: query flagged)
 
 // where the rows of a space are, for one search (host: rows_view, ehx_call.cpp)
 struct RowsView {
@@ -97,7 +98,7 @@ __device__ __forceinline__ uint64_t keep_best64(uint64_t best, uint64_t key, int
   return wave_bitonic_merge64(best < rv ? best : rv, lane);
 }
 
-// ---- a pool of candidates, re-ranked (k_range.hip, k_masked.hip) ----
+// ---- a pool of candidates, re-ranked (k_range.hip, k_radius.hip) ----
 // Canonical distances of the pool's rows for a workgroup of T threads: pool[0, cnt) are keys whose low halves are row ids
 // (each row at most once), qs the prepared query in LDS; keys[i] = the (distance, id) key of entry i, kKeyInf where the
 // distance lies above r or is NaN.  Returns, in every lane of a wave, how many entries that wave's lanes kept.
@@ -135,6 +136,37 @@ __device__ __forceinline__ void block_sort_lds(uint64_t* keys, uint32_t m, uint3
       __syncthreads();
     }
   }
+}
+
+// keys[0, n) padded with kKeyInf to the power of two the sort runs over, and sorted
+template <uint32_t T>
+__device__ __forceinline__ void pad_and_sort_lds(uint64_t* keys, uint32_t n, uint32_t tid) {
+  uint32_t m = 2;
+  while (m < n) m <<= 1;
+  for (uint32_t i = n + tid; i < m; i += T) keys[i] = kKeyInf;
+  __syncthreads();
+  block_sort_lds<T>(keys, m, tid);
+}
+
+// One query's pool re-ranked by its workgroup of T threads, whose whole LDS is the launch's pool_rerank_lds_bytes(rows.ld):
+// the keys [kPoolCap] | the prepared query q_row, staged here, [ld] | a counter.  Behind it (uint64_t*)lds holds the
+// (distance, id) keys of the entries within r, ascending, kKeyInf behind them; returns how many there are.
+__host__ __device__ constexpr size_t pool_rerank_lds_bytes(uint32_t ld) {
+  return kPoolCap * sizeof(uint64_t) + (size_t)ld * sizeof(float) + 16u;
+}
+template <int LAYOUT, int METRIC, uint32_t T>
+__device__ __forceinline__ uint32_t pool_rerank_sorted(float4* lds, const RowsView& rows, const float* __restrict__ q_row,
+                                                       const uint64_t* __restrict__ pool, uint32_t cnt, float r, uint32_t tid) {
+  uint64_t* keys = (uint64_t*)lds;
+  float* qs = (float*)(keys + kPoolCap);
+  uint32_t& kept_s = *(uint32_t*)(qs + rows.ld);
+  stage_query_lds<LAYOUT>(qs, q_row, rows.ld, tid, T);
+  if (tid == 0) kept_s = 0;
+  __syncthreads();
+  const uint32_t kept = rerank_pool_cut<LAYOUT, METRIC, T>(rows, qs, pool, cnt, r, keys, tid);
+  if ((tid & 63u) == 0 && kept) atomicAdd(&kept_s, kept);
+  pad_and_sort_lds<T>(keys, cnt, tid);   // (at least one barrier: every wave's count has landed)
+  return kept_s;
 }
 
 // ---- a page of results ----

@@ -1,42 +1,19 @@
 // Exact kNN under a row bitmap (ehx_knn_masked*): the first k of the ALLOWED rows in (canonical distance, id) order — the
-// answer of ehx_knn_among with the ascending list of allowed rows, byte for byte.
+// answer of ehx_knn_among with the ascending list of allowed rows, byte for byte.  This file compacts the bitmap:
 //   masked_count_kernel    allowed rows of every 256-row tile (8 words of the bitmap)
 //   masked_prefix_kernel   their exclusive prefix, cum[0 .. n_tiles] (cum[n_tiles] = the number of allowed rows)
 //   masked_fill_kernel     the ascending list of allowed row ids
 //   masked_sample_kernel   every stride-th allowed id by rank: the sample whose exact k-th distance is the first radius
-//   masked_radius_kernel   radius[q] = the sample's k-th distance (+Inf while the sample gave fewer than k)
-//   masked_rerank_kernel   scan route, once per pass: the pool's canonical distances, cut at the radius, sorted; the best
-//                          <= k carried into the next pass, the radius lowered; behind the last pass the output page
-// Every distance comes from the exact paths' one row walk (walk_row, k_exact_common.h) through the pool re-rank it shares
-// with the range search (rerank_pool_cut, block_sort_lds), the keys from dist_key and the page from emit_page.
-//
-// The scan route (ehx_masked.cpp).  A search that knows a radius r with "the masked k-th distance is <= r" needs no
-// certificate: flat_scan_i8_kernel under the threshold range_thr_kernel maps r to keeps every row with D <= r (k_range.hip's
-// header), and its flush drops the rows the bitmap does not allow before they take a pool slot.  The k-th exact distance
-// over ANY subset of the allowed rows is such an r: the subset's k nearest are k allowed rows within r.  The first r is the
-// k-th distance of a sample of <= 256 allowed rows; the rows are then scanned in passes over disjoint tile ranges, and
-// behind every pass this file's re-rank computes the canonical distances of the pool — the <= k keys carried from earlier
-// passes and the pass's hits — drops what lies above r (or is NaN), sorts the rest by (distance, id), keeps the best <= k
-// at the head of the pool and lowers r to their k-th distance when k are held.  The radius only ever falls.
-//
-// Why the answer is exact and nothing is collected twice.
-//   * Passes cover disjoint tiles and a tile's rows are hit at most once per pass, so a row enters a pool at most once; the
-//     sample's rows give the radius only and enter a pool through their own pass like every other row.
-//   * Let m be a true member of the answer and r* the radius behind the last pass.  Every radius is the k-th distance of k
-//     allowed rows, hence >= the true masked k-th distance >= D(m); the radius r_j its own pass j ran under is >= r*
-//     >= D(m), so the scan keeps it (soundness of the threshold) and the re-rank does not cut it at the radius.  It leaves a
-//     pool only when k allowed rows precede it in (distance, id) order — then it is no member.  By induction over the
-//     passes the pool behind the last pass holds every member, in order.
-//   * A query whose pool overflowed (ovf = 1, sticky: its radius becomes NaN, so later passes collect nothing for it) or
-//     which the bound does not serve (ovf = 2, range_thr_kernel) writes nothing here: the host answers it with the exact
-//     kNN among the whole list.
+//   masked_radius_kernel   radius[q] = that distance, from the list scan's answer over the sample (+Inf while it gave fewer
+//                          than k)
+// The list serves the exact route (k_among.hip) and the host's pass plan; the scan route (ehx_masked.cpp) is the falling-
+// radius kNN of k_radius.hip with the bitmap in the int8 scan's flush and this first radius — that file's header has the
+// re-rank kernel and the argument why the answer is exact, "allowed rows" being its rows.
 #include "ehx_kernels.h"
 
 namespace ehx {
 
 namespace {
-
-constexpr uint32_t kMaskedThreads = 256;
 
 // word w of the bitmap cut at n_bits (bits of the last word beyond n_bits and words beyond it read as 0)
 __device__ __forceinline__ uint32_t mask_word(const uint32_t* __restrict__ mask, uint64_t w, uint64_t n_bits) {
@@ -117,64 +94,6 @@ __global__ __launch_bounds__(256) void masked_radius_kernel(const float* __restr
   radius[q] = cnt[q] >= k ? dist[(size_t)q * k + (k - 1)] : __builtin_inff();
 }
 
-// One workgroup per query (file header).  The pool holds keys whose low halves are row ids: (distance, id) of the rows
-// carried, (S_lower, id) of this pass's hits.
-template <bool HALFX, int METRIC>
-__global__ __launch_bounds__(kMaskedThreads) void masked_rerank_kernel(const MaskedRerankArgs a) {
-  extern __shared__ float4 masked_lds[];
-  uint64_t* keys = (uint64_t*)masked_lds;             // [kPoolCap]
-  float* qs = (float*)(keys + kPoolCap);              // [ld]
-  uint32_t& kept_s = *(uint32_t*)(qs + a.rows.ld);
-  const uint32_t tid = threadIdx.x, q = blockIdx.x;
-  const int lane = (int)(tid & 63u);
-  const uint32_t flag = a.ovf[q];
-  if (flag) {
-    // (an overflowed pool: a NaN radius maps to -inf, the later passes collect nothing for the query)
-    if (flag == 1u && tid == 0) a.radius[q] = __builtin_nanf("");
-    return;
-  }
-  const uint32_t have = a.pool_cnt[q];
-  if (have > kPoolCap) return;   // (the scan's flag is about to land or has: the host reads it behind the last pass)
-  const uint32_t cnt = have;
-  const float r = a.radius[q];
-  constexpr int LAYOUT = HALFX ? kLayoutF16 : kLayoutF32;
-  stage_query_lds<LAYOUT>(qs, a.Q + (size_t)q * a.rows.ld, a.rows.ld, tid, kMaskedThreads);
-  if (tid == 0) kept_s = 0;
-  __syncthreads();
-  uint64_t* pq = a.pool + (size_t)q * kPoolCap;
-  const uint32_t kept = rerank_pool_cut<LAYOUT, METRIC, kMaskedThreads>(a.rows, qs, pq, cnt, r, keys, tid);
-  if (lane == 0 && kept) atomicAdd(&kept_s, kept);
-  uint32_t m = 2;
-  while (m < cnt) m <<= 1;
-  for (uint32_t i = cnt + tid; i < m; i += kMaskedThreads) keys[i] = kKeyInf;
-  __syncthreads();
-  block_sort_lds<kMaskedThreads>(keys, m, tid);
-  const uint32_t total = kept_s;
-  const uint32_t keep = total < a.k ? total : a.k;
-  if (a.last) {
-    emit_page([&](uint32_t i) { return keys[i]; }, keep, a.k, a.out_ids + (size_t)q * a.k, a.out_dist + (size_t)q * a.k,
-              a.out_count + q, 0, tid, kMaskedThreads);
-  } else {
-    for (uint32_t i = tid; i < keep; i += kMaskedThreads) pq[i] = keys[i];
-    if (tid == 0) {
-      a.pool_cnt[q] = keep;
-      // (every kept distance is <= r: the k-th of them is the new, smaller or equal, radius)
-      if (total >= a.k) a.radius[q] = ordered_to_f32((uint32_t)(keys[a.k - 1] >> 32));
-    }
-  }
-  if (tid == 0) a.work[q] += cnt;
-}
-
-namespace {
-
-typedef void (*MaskedRerankFn)(const MaskedRerankArgs);
-const MaskedRerankFn kMaskedRerankFns[6] = {   // [half * 3 + metric]
-    masked_rerank_kernel<false, 0>, masked_rerank_kernel<false, 1>, masked_rerank_kernel<false, 2>,
-    masked_rerank_kernel<true, 0>,  masked_rerank_kernel<true, 1>,  masked_rerank_kernel<true, 2>};
-DynLdsAttr g_masked_lds;
-
-}  // namespace
-
 hipError_t launch_masked_compact(const uint32_t* mask, uint64_t n_bits, uint32_t n_tiles, uint32_t* cum, uint64_t* list,
                                  hipStream_t st) {
   if (n_tiles == 0) return hipSuccess;
@@ -196,18 +115,6 @@ hipError_t launch_masked_radius(const float* dist, const uint32_t* cnt, uint32_t
   if (nq == 0) return hipSuccess;
   if (k == 0) return hipErrorInvalidValue;
   hipLaunchKernelGGL(masked_radius_kernel, dim3((nq + 255u) / 256u), dim3(256), 0, st, dist, cnt, nq, k, radius);
-  return hipGetLastError();
-}
-
-hipError_t launch_masked_rerank(const MaskedRerankArgs& a, hipStream_t st) {
-  if (a.nq == 0) return hipSuccess;
-  if (a.k == 0 || a.k > kPoolCap || (a.rows.ld & 3u) || a.rows.ld > range_rerank_max_ld() || a.rows.x_perm || a.rows.metric < 0 ||
-      a.rows.metric > 2)
-    return hipErrorInvalidValue;
-  const size_t lds = kPoolCap * sizeof(uint64_t) + (size_t)a.rows.ld * sizeof(float) + 16u;
-  hipError_t e = g_masked_lds.ensure(kMaskedRerankFns, 6, lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kMaskedRerankFns[(a.rows.x_half ? 3 : 0) + a.rows.metric], dim3(a.nq), dim3(kMaskedThreads), lds, st, a);
   return hipGetLastError();
 }
 

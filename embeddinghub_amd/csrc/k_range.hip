@@ -44,20 +44,6 @@ namespace {
 
 constexpr uint32_t kEmitThreads = 256;
 
-// keys[0, n) hold (ordered distance, id) keys, kKeyInf = dropped; keys[n, m) are padded here, m the power of two the sort
-// runs over.  Sorts and writes query q's row: the first min(kept, max_results) pairs, then the sentinels.
-__device__ __forceinline__ void sort_and_emit(uint64_t* keys, uint32_t n, uint32_t kept, uint32_t q, uint32_t max_results,
-                                              uint64_t* __restrict__ out_ids, float* __restrict__ out_dist,
-                                              uint32_t* __restrict__ out_count, uint32_t tid) {
-  uint32_t m = 2;
-  while (m < n) m <<= 1;
-  for (uint32_t i = n + tid; i < m; i += kEmitThreads) keys[i] = kKeyInf;
-  __syncthreads();
-  block_sort_lds<kEmitThreads>(keys, m, tid);
-  emit_page([&](uint32_t i) { return keys[i]; }, kept, max_results, out_ids + (size_t)q * max_results,
-            out_dist + (size_t)q * max_results, out_count + q, 0, tid, kEmitThreads);
-}
-
 }  // namespace
 
 // Grid (query slots, blocks): slot j answers query sel[j] (sel == nullptr: j); block b walks steps b, b + gridDim.y, ...
@@ -111,7 +97,9 @@ __global__ __launch_bounds__(kEmitThreads) void range_emit_kernel(const uint64_t
   if (tid == 0 && out_total) out_total[q] = cnt;
   if (cnt > kPoolCap) return;
   for (uint32_t i = tid; i < cnt; i += kEmitThreads) keys[i] = pool[(size_t)j * kPoolCap + i];
-  sort_and_emit(keys, cnt, cnt, q, max_results, out_ids, out_dist, out_count, tid);
+  pad_and_sort_lds<kEmitThreads>(keys, cnt, tid);
+  emit_page([&](uint32_t i) { return keys[i]; }, cnt, max_results, out_ids + (size_t)q * max_results,
+            out_dist + (size_t)q * max_results, out_count + q, 0, tid, kEmitThreads);
 }
 
 // One lane per query: the threshold of the file header.  ovf[q] = 2 marks a query the bound does not serve.
@@ -151,28 +139,18 @@ __global__ __launch_bounds__(256) void range_thr_kernel(const float* __restrict_
 template <bool HALFX, int METRIC>
 __global__ __launch_bounds__(kEmitThreads) void range_rerank_kernel(const RangeRerankArgs a) {
   extern __shared__ float4 range_lds[];
-  uint64_t* keys = (uint64_t*)range_lds;              // [kPoolCap]
-  float* qs = (float*)(keys + kPoolCap);              // [ld]
-  uint32_t& kept_s = *(uint32_t*)(qs + a.rows.ld);         // (dynamic too: the launch's size is the workgroup's whole LDS)
+  uint64_t* keys = (uint64_t*)range_lds;   // (pool_rerank_sorted's image: the sorted keys at its head)
   const uint32_t tid = threadIdx.x, q = blockIdx.x;
-  const int lane = (int)(tid & 63u);
   if (a.ovf[q]) return;
   const uint32_t cnt = a.pool_cnt[q] < kPoolCap ? a.pool_cnt[q] : kPoolCap;
-  const float r = a.radius[q];
-  constexpr int LAYOUT = HALFX ? kLayoutF16 : kLayoutF32;
-  stage_query_lds<LAYOUT>(qs, a.Q + (size_t)q * a.rows.ld, a.rows.ld, tid, kEmitThreads);
-  if (tid == 0) kept_s = 0;
-  __syncthreads();
-  const uint64_t* pq = a.pool + (size_t)q * kPoolCap;
-  const uint32_t kept = rerank_pool_cut<LAYOUT, METRIC, kEmitThreads>(a.rows, qs, pq, cnt, r, keys, tid);
-  if (lane == 0 && kept) atomicAdd(&kept_s, kept);
-  __syncthreads();
-  const uint32_t total = kept_s;
+  const uint32_t total = pool_rerank_sorted<HALFX ? kLayoutF16 : kLayoutF32, METRIC, kEmitThreads>(
+      range_lds, a.rows, a.Q + (size_t)q * a.rows.ld, a.pool + (size_t)q * kPoolCap, cnt, a.radius[q], tid);
   if (tid == 0) {
     a.kept[q] = total;
     if (a.out_total) a.out_total[q] = total;
   }
-  sort_and_emit(keys, cnt, total, q, a.max_results, a.out_ids, a.out_dist, a.out_count, tid);
+  emit_page([&](uint32_t i) { return keys[i]; }, total, a.max_results, a.out_ids + (size_t)q * a.max_results,
+            a.out_dist + (size_t)q * a.max_results, a.out_count + q, 0, tid, kEmitThreads);
 }
 
 __global__ __launch_bounds__(256) void range_iota_kernel(uint64_t* __restrict__ out, uint64_t n) {
@@ -187,8 +165,7 @@ const RangeFn kExactFns[9] = {   // [layout * 3 + metric]
     range_exact_kernel<kLayoutF32, 0>,  range_exact_kernel<kLayoutF32, 1>,  range_exact_kernel<kLayoutF32, 2>,
     range_exact_kernel<kLayoutF16, 0>,  range_exact_kernel<kLayoutF16, 1>,  range_exact_kernel<kLayoutF16, 2>,
     range_exact_kernel<kLayoutPerm, 0>, range_exact_kernel<kLayoutPerm, 1>, range_exact_kernel<kLayoutPerm, 2>};
-typedef void (*RerankFn)(const RangeRerankArgs);
-const RerankFn kRerankFns[6] = {   // [half * 3 + metric]
+const decltype(&range_rerank_kernel<false, 0>) kRerankFns[6] = {   // [half * 3 + metric]
     range_rerank_kernel<false, 0>, range_rerank_kernel<false, 1>, range_rerank_kernel<false, 2>,
     range_rerank_kernel<true, 0>,  range_rerank_kernel<true, 1>,  range_rerank_kernel<true, 2>};
 DynLdsAttr g_exact_lds, g_rerank_lds;
@@ -197,7 +174,7 @@ DynLdsAttr g_exact_lds, g_rerank_lds;
 
 uint32_t range_step_rows(const RangeArgs& a) { return row_layout(a.rows.x_half, a.rows.x_perm) == kLayoutF32 ? 256u : 64u; }
 
-uint32_t range_rerank_max_ld() { return (uint32_t)((kMaxLds - kPoolCap * sizeof(uint64_t) - 16u) / sizeof(float)) & ~31u; }
+uint32_t range_rerank_max_ld() { return (uint32_t)((kMaxLds - pool_rerank_lds_bytes(0)) / sizeof(float)) & ~31u; }
 
 hipError_t launch_range_exact(const RangeArgs& a, uint32_t n_slots, hipStream_t st) {
   if (n_slots == 0 || a.rows.n_rows == 0) return hipSuccess;
@@ -230,14 +207,7 @@ hipError_t launch_range_thr(const float* radius, const float2* quv, const float*
 }
 
 hipError_t launch_range_rerank(const RangeRerankArgs& a, hipStream_t st) {
-  if (a.nq == 0) return hipSuccess;
-  if (a.max_results == 0 || (a.rows.ld & 3u) || a.rows.ld > range_rerank_max_ld() || a.rows.metric < 0 || a.rows.metric > 2)
-    return hipErrorInvalidValue;
-  const size_t lds = kPoolCap * sizeof(uint64_t) + (size_t)a.rows.ld * sizeof(float) + 16u;
-  hipError_t e = g_rerank_lds.ensure(kRerankFns, 6, lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kRerankFns[(a.rows.x_half ? 3 : 0) + a.rows.metric], dim3(a.nq), dim3(kEmitThreads), lds, st, a);
-  return hipGetLastError();
+  return launch_pool_rerank(kRerankFns, g_rerank_lds, a, a.max_results != 0, kEmitThreads, st);
 }
 
 hipError_t launch_range_iota(uint64_t* out, uint64_t n, hipStream_t st) {

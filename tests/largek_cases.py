@@ -138,7 +138,7 @@ def cascade(X, Q, metric, ks, growth=GROWTH, depth=8000, block=256):
                 member = D[lo:hi] <= radius[None, :]
                 assert not (member & ~through).any(), "the threshold hides a row within the radius"
                 out[k][1][j] = max(out[k][1][j], int(through.sum(axis=0).max()))
-                for q in range(nq):                                   # largek_rerank_kernel
+                for q in range(nq):                                   # radius_rerank_kernel
                     hits = lo + np.nonzero(through[:, q])[0]
                     hits = hits[D[hits, q] <= radius[q]]
                     pool = np.concatenate([carried[q], hits])

@@ -1,5 +1,5 @@
 """GPU tests of the large-k scan route: flat searches with 48 < k <= 256 and at least 64 queries on a space whose first
-engine is the int8 filter (ehx_largek.cpp, k_largek.hip).  Nothing but knn_device_locked decides the route, so the tests
+engine is the int8 filter (ehx_largek.cpp, k_radius.hip).  Nothing but knn_device_locked decides the route, so the tests
 call the ordinary entry points and read what happened from ehx_test_largek_counters and ehx_stats.
 
 Expected answers come from the oracle only (pyoracle.exhaustive): ids equal, distance BYTES equal, sentinels behind the

@@ -3,13 +3,14 @@
 Expected answers come from the oracle only: with L the ascending list of allowed rows (below n_bits and the row count),
 pyoracle.exhaustive(X[L], Q, k, metric) answers and its local ids are mapped back through L — tie order by local id is tie
 order by global id.  Ids must be equal and distance BYTES equal, tails the sentinels.  F16 spaces use the oracle on
-X.astype(float16).astype(float32).  The int8 cases (data: tests/range_cases.py, bitmaps: tests/masked_cases.py) are the ones
-tests/test_masked_model.py shows to stay within half a pool."""
+X.astype(float16).astype(float32).  The int8 cases (data: tests/range_cases.py, bitmaps: tests/masked_cases.py; the merge
+cases: masked_cases.merge_cases) are the ones tests/test_masked_model.py shows to stay within half a pool."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import largek_cases as lc
 import masked_cases as mc
 import range_cases as rc
 from oracle import pyoracle
@@ -88,8 +89,8 @@ def _same_bytes(a, b):
     return all(np.ascontiguousarray(x).tobytes() == np.ascontiguousarray(y).tobytes() for x, y in zip(a, b))
 
 
-def _i8_space(name, d, metric, X, cap=None):
-    s = ehx.Space.unique(name, d, metric=METRICS[metric][0], initial_capacity=cap or len(X))
+def _i8_space(name, d, metric, X, cap=None, **kw):
+    s = ehx.Space.unique(name, d, metric=METRICS[metric][0], initial_capacity=cap or len(X), **kw)
     s.set_batch(_keys(len(X)), X)
     assert s.scan_engine() == "i8"
     return s
@@ -178,6 +179,67 @@ def test_pool_overflow_falls_to_the_exact_route(metric, where):
     assert _same_bytes(got, _device_form(s, Q, k, allowed))
     assert s.stats()["n_uncertified"] == 0
     s.drop()
+
+
+# ---- the merge of a pass's hits into the carried keys ----
+
+def _merge_case(name, check=None, **kw):
+    """every bitmap and k of masked_cases.merge_cases()[name]: the oracle's answer, ehx_knn_among's bytes, both forms, every
+    query served by the two passes of the scan route (tests/test_masked_model.py: no pool overflows)"""
+    X, Q, metric, bitmaps, ks = mc.merge_cases()[name]
+    om = METRICS[metric][1]
+    s = _i8_space("masked-" + name, X.shape[1], metric, X, **kw)
+    for bname, allowed in bitmaps.items():
+        L = np.nonzero(allowed)[0].astype(np.uint64)
+        for k in ks:
+            what = "%s %s k=%d" % (name, bname, k)
+            want = _expected(X, Q, k, om, allowed)
+            c0 = _counters(s)
+            got = s.knn_masked(Q, k, allowed)
+            dc = _counters(s) - c0
+            _assert_rows(got, want, what)
+            assert dc.tolist() == [len(Q), 0, 0, 2, 1], (what, dc)
+            assert _same_bytes(got, s.knn_among(Q, k, L)), what + ": knn_among on the list differs"
+            assert _same_bytes(got, _device_form(s, Q, k, allowed)), what + ": host and device forms differ"
+            if check:
+                check(allowed, k, want)
+    assert s.stats()["n_uncertified"] == 0
+    s.drop()
+
+
+def test_ties_across_passes_come_back_in_id_order():
+    """300 copies of one row over the ids of both passes, the query that row: a pass's hits and the carried keys lie at ONE
+    distance, and the rank merge must order them by id.  Where the bitmap clears a copy, the answer simply lacks it."""
+    at = lc.ties()[2]
+
+    def check(allowed, k, want):
+        copies = at[allowed[at]]
+        first_pass_rows = mc.passes(allowed)[0][1] * mc.TILE
+        assert (copies < first_pass_rows).sum() > 0 and (copies >= first_pass_rows).sum() > 0
+        assert want[0][0] == [int(v) for v in copies[:k]] and (want[0][1] == want[0][1][0]).all()
+
+    _merge_case("ties", check)
+
+
+def test_fewer_than_k_keys_carried_out_of_the_first_pass():
+    """masked_cases.far_then_near: the first pass finds fewer than k rows within query 0's first radius — nothing, in fact —
+    so fewer than k keys are carried, the radius stays where the sample put it, and the second pass brings the whole answer"""
+    X, Q, metric, bitmaps, ks = mc.merge_cases()["short"]
+    allowed, k = bitmaps["far_then_near"], ks[0]
+    plan = mc.passes(allowed)
+    assert len(plan) == 2 and k == mc.SCAN_MAX_K
+    L = np.nonzero(allowed)[0]
+    oi, od, oc = pyoracle.exhaustive(np.ascontiguousarray(X[L]), Q[:1], len(L), METRICS[metric][1])
+    D0 = np.empty(len(X), dtype=f32)
+    D0[L[oi[0].astype(np.int64)]] = od[0]
+    r0 = np.sort(D0[mc.sample_ids(allowed)])[k - 1]
+    first = L[L < plan[0][1] * mc.TILE]
+    assert len(first) >= 4096 and (D0[first] <= r0).sum() < k
+    _merge_case("short")
+
+
+def test_binary16_rows_on_the_scan_route():
+    _merge_case("f16", dtype=ehx.DTYPE_F16)
 
 
 # ---- exact route ----

@@ -86,10 +86,10 @@ def test_masked_kernels_use_no_scratch_and_spill_no_vector_registers(tmp_path):
                                                     str(tmp_path / "k_masked.o")], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     names = re.findall(r"Function Name: (\S+)", r.stderr)
-    for kern, count in (("masked_rerank_kernel", 6), ("masked_count_kernel", 1), ("masked_prefix_kernel", 1),
-                        ("masked_fill_kernel", 1), ("masked_sample_kernel", 1), ("masked_radius_kernel", 1)):
-        assert sum(kern in n for n in names) == count, names
-    assert len(names) == 11
+    for kern in ("masked_count_kernel", "masked_prefix_kernel", "masked_fill_kernel", "masked_sample_kernel",
+                 "masked_radius_kernel"):
+        assert sum(kern in n for n in names) == 1, names
+    assert len(names) == 5
     for what in ("ScratchSize \\[bytes/lane\\]", "VGPRs Spill"):
         vals = re.findall(what + r": (\d+)", r.stderr)
         assert len(vals) == len(names) and all(v == "0" for v in vals), (what, vals)

@@ -1,5 +1,5 @@
 """CPU-side checks of the large-k scan route: the pass planner (largek_passes through its test hook, against the Python
-mirror of tests/largek_cases.py), the hooks that stay outside the ABI, the knobs, and the resource usage of k_largek.hip
+mirror of tests/largek_cases.py), the hooks that stay outside the ABI, the knobs, and the resource usage of k_radius.hip
 built for gfx950."""
 import ctypes as C
 import os
@@ -31,7 +31,7 @@ def test_the_hooks_are_exported_and_not_part_of_the_abi():
     raw = C.CDLL(_lib.LIB_PATH)
     for h in HOOKS:
         assert h not in header and h not in _lib.SYMBOLS and hasattr(raw, h)
-    assert "k_largek.hip" in ehx_build.SOURCES and "ehx_largek.cpp" in ehx_build.SOURCES
+    assert "k_radius.hip" in ehx_build.SOURCES and "ehx_largek.cpp" in ehx_build.SOURCES
     assert re.search(r"#define EHX_ABI_VERSION 5\b", header)   # no symbol or struct of the ABI changed
     assert re.search(r"#define EHX_MAX_K 48u\b", header) and re.search(r"#define EHX_MAX_K_PAGED 1024u\b", header)
 
@@ -80,13 +80,13 @@ def test_the_knobs_are_read_in_one_place_and_documented():
 
 
 def test_largek_kernels_use_no_scratch_and_spill_no_vector_registers(tmp_path):
-    src = os.path.join(ehx_build.CSRC, "k_largek.hip")
+    src = os.path.join(ehx_build.CSRC, "k_radius.hip")
     flags = [f for f in ehx_build.FLAGS if f != "-shared"]
     r = subprocess.run([ehx_build.HIPCC] + flags + ["-Rpass-analysis=kernel-resource-usage", "-x", "hip", "-c", src, "-o",
-                                                    str(tmp_path / "k_largek.o")], capture_output=True, text=True)
+                                                    str(tmp_path / "k_radius.o")], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     names = re.findall(r"Function Name: (\S+)", r.stderr)
-    for kern, count in (("largek_rerank_kernel", 6), ("largek_seed_kernel", 1)):
+    for kern, count in (("radius_rerank_kernel", 6), ("radius_seed_kernel", 1)):
         assert sum(kern in n for n in names) == count, names
     assert len(names) == 7
     for what in ("ScratchSize \\[bytes/lane\\]", "VGPRs Spill"):

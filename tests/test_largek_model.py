@@ -1,4 +1,4 @@
-"""CPU model of the large-k scan route (host logic, no GPU): the cascade of ehx_largek.cpp / k_largek.hip restated in numpy
+"""CPU model of the large-k scan route (host logic, no GPU): the cascade of ehx_largek.cpp / k_radius.hip restated in numpy
 (tests/largek_cases.py) on the lower-bound model of tests/i8_model.py and range_thr (tests/range_cases.py), for every case
 tests/test_knn_largek.py asserts "no query handed on" for.  At every pass of every case:
 
