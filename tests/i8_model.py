@@ -73,7 +73,21 @@ def _row_params_raised(X, metric, d, tgtA=None):
     return qf.astype(np.int32), A, B, C, D, e
 
 
-def _query_params(Q, metric, d):
+def _norm_ok(ss):
+    """norm_ok (k_misc.hip): the norms the filter's error analysis covers (a NaN sumsq compares false)"""
+    with np.errstate(invalid="ignore"):
+        return (ss == 0) | ((ss > f32(1e-24)) & (ss < f32(1e30)))
+
+
+def _query_params(Q, metric, d, band=False):
+    """band=True restates what prep_queries8 does besides: a query whose sumsq fails norm_ok takes beta = 0 (its codes
+    are then whatever 0 * x gives; the model stores zeros) and u = NaN, the value that makes range_thr_kernel hand it to an
+    exact path; a zero query passes norm_ok and keeps (g, u, v) = (1, 1, 0) under every metric."""
+    if band:
+        with np.errstate(all="ignore"):
+            ok = _norm_ok((Q.astype(f32) ** 2).sum(axis=1, dtype=f32))
+        qi, s, e, g, u, v = _query_params(np.where(ok[:, None], Q, f32(0)).astype(f32), metric, d)
+        return qi, s, e, g, np.where(ok, u, f32(np.nan)).astype(f32), v
     beta, ss, qi, s, e = _quantise(Q)
     g = np.ones_like(beta)
     u = np.ones_like(beta)

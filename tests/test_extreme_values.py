@@ -17,6 +17,8 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 from oracle import pyoracle  # noqa: E402
+from extreme_cases import (F16_EDGE, KINDS, N_I8, NEG_NAN, ODD_AT, POS_NAN, SAFE, _kind_rows, _ladder, _odd_queries,  # noqa: E402
+                           _scaled)
 
 pytestmark = pytest.mark.gpu
 
@@ -24,9 +26,7 @@ ehx = pytest.importorskip("embeddinghub_amd")
 
 METRICS = [(ehx.METRIC_L2SQ, pyoracle.METRIC_L2), (ehx.METRIC_IP, pyoracle.METRIC_IP),
            (ehx.METRIC_COSINE, pyoracle.METRIC_COSINE)]
-POS_NAN = np.array([0x7FC00000], dtype=np.uint32).view(np.float32)[0]
-NEG_NAN = np.array([0xFFC00000], dtype=np.uint32).view(np.float32)[0]
-N_I8, N_SMALL, BLOCK0, NBLOCK = 16384, 4000, 1000, 256
+N_SMALL = 4000
 
 
 def _keys(n):
@@ -43,55 +43,6 @@ def _check(space, X, Q, k, om, what=""):
         assert dist[i, :c].tobytes() == odist[i, :c].tobytes(), "%s query %d distances differ" % (what, i)
     assert space.stats()["n_uncertified"] == 0, what
     return ids, dist, cnt
-
-
-def _scaled(rng, n, d, sumsq_lo, sumsq_hi):
-    """n random directions with |x|^2 log-uniform in [sumsq_lo, sumsq_hi]"""
-    g = rng.standard_normal((n, d))
-    g /= np.linalg.norm(g, axis=1, keepdims=True)
-    s2 = np.exp(rng.uniform(np.log(sumsq_lo), np.log(sumsq_hi), n))
-    return (g * np.sqrt(s2)[:, None]).astype(np.float32)
-
-
-def _kind_rows(kind, rng, n, d):
-    if kind == "a_lo":
-        return _scaled(rng, n, d, 2e-24, 4e-24)      # just inside the band's low edge
-    if kind == "a_hi":
-        return _scaled(rng, n, d, 2.5e29, 5e29)      # just inside the high edge
-    if kind == "b_lo":
-        return _scaled(rng, n, d, 2e-25, 5e-25)      # just outside
-    if kind == "b_hi":
-        return _scaled(rng, n, d, 2e30, 4e30)
-    if kind == "c":                                  # products and sums are fp32 subnormals
-        return (rng.standard_normal((n, d)) * 1e-21).astype(np.float32)
-    if kind == "d":                                  # finite rows whose L2 distances overflow to +Inf
-        return (rng.standard_normal((n, d)) * 1e19).astype(np.float32)
-    if kind == "e":                                  # sumsq overflows, every component finite (cosine: a zero row)
-        return (np.sign(rng.standard_normal((n, d))) * rng.uniform(1e37, 3e37, (n, d))).astype(np.float32)
-    if kind == "f":
-        return np.zeros((n, d), np.float32)
-    if kind == "g":                                  # one non-finite component: +NaN, -NaN, +Inf, -Inf
-        X = rng.standard_normal((n, d)).astype(np.float32)
-        for i in range(n):
-            X[i, (i * 7) % d] = (POS_NAN, NEG_NAN, np.inf, -np.inf)[i % 4]
-        return X
-    raise ValueError(kind)
-
-
-KINDS = ["a_lo", "a_hi", "b_lo", "b_hi", "c", "d", "e", "f", "g"]
-SAFE = {"a_lo", "a_hi", "f"}   # rows the filters still bound
-
-
-def _ladder(kind, d, seed, n=N_I8):
-    rng = np.random.default_rng(seed)
-    X = rng.standard_normal((n, d)).astype(np.float32)
-    B = _kind_rows(kind, rng, NBLOCK, d)
-    X[BLOCK0:BLOCK0 + NBLOCK] = B
-    Q = rng.standard_normal((20, d)).astype(np.float32)
-    near = B[[0, 1, 2, 3, 5]].copy()
-    near[4] *= np.float32(1.0001)
-    Q = np.concatenate([Q, near, np.zeros((1, d), np.float32)])
-    return X, Q
 
 
 def _assert_engine(space, kind, fast):
@@ -186,26 +137,6 @@ def test_non_finite_rows_when_k_exceeds_the_finite_rows(em, om):
 
 
 # ---- B. odd queries inside ordinary batches -----------------------------------------------------------------------
-def _odd_queries(rng, d):
-    def band(s2):
-        g = rng.standard_normal(d)
-        return (g / np.linalg.norm(g) * np.sqrt(s2)).astype(np.float32)
-    out = [np.zeros(d, np.float32)]
-    for v in (POS_NAN, NEG_NAN, np.inf, -np.inf):
-        q = rng.standard_normal(d).astype(np.float32)
-        q[3] = v
-        out.append(q)
-    out += [band(2e-24), band(5e-25), band(5e29), band(2e30)]
-    q = rng.standard_normal(d).astype(np.float32)
-    q[0] = 1e15
-    out.append(q)
-    out.append((rng.standard_normal(d) * 1e-21).astype(np.float32))
-    return out
-
-
-ODD_AT = [0, 1, 2, 63, 64, 127, 128, 129, 200, 255, 256]
-
-
 @pytest.mark.parametrize("em,om", METRICS)
 @pytest.mark.parametrize("engine", ["i8", "f16", "f32"])
 def test_odd_queries_inside_ordinary_batches(engine, em, om):
@@ -277,10 +208,6 @@ def test_garbage_queries_do_not_widen_the_int8_candidate_list():
 
 
 # ---- E. fp16 storage at the binary16 boundaries; fp32 Get is bit-exact ---------------------------------------------
-F16_EDGE = np.array([65504.0, 65519.996, 65520.0, -65520.0, 2.0 ** -24, 2.0 ** -25, 3 * 2.0 ** -26, 1e-8, -0.0],
-                    dtype=np.float32)
-
-
 @pytest.mark.parametrize("em,om", METRICS)
 @pytest.mark.parametrize("n,engine", [(N_I8 + 64, "i8"), (N_SMALL, "f16")])
 def test_fp16_storage_boundaries(n, engine, em, om):
