@@ -69,7 +69,10 @@ SYMBOLS = {
     "ehx_space_scan_engine": (C.c_int, [_vp, _u32p]),
     "ehx_set": (C.c_int, [_vp, C.c_char_p, C.c_size_t, _f32p]),
     "ehx_set_batch": (C.c_int, [_vp, C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), _f32p]),
+    "ehx_set_batch_device": (C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), _vp, C.c_int]),
     "ehx_get": (C.c_int, [_vp, C.c_char_p, C.c_size_t, _f32p]),
+    "ehx_get_batch": (C.c_int, [_vp, C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), _f32p, C.POINTER(C.c_size_t)]),
+    "ehx_get_by_ids_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp, _vp]),
     "ehx_get_by_id": (C.c_int, [_vp, C.c_uint64, _f32p]),
     "ehx_key_of": (C.c_int, [_vp, C.c_uint64, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "ehx_knn": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_uint32, _u64p, _f32p, _u32p]),

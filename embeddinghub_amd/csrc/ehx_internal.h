@@ -4,6 +4,7 @@
 //   ehx_graph.cpp   graph mode: GPU-side insertion, update-in-place repair, the graph search pipeline
 //   ehx_shards.cpp  row-sharded spaces inside one process (ehx_params.shards)
 //   ehx_write.cpp   Set / BatchSet: staging, upload, row statistics, scan copies, write combiner
+//   ehx_rowio.cpp   rows in and out without staging: Set from device memory, batched Get, Get by row ids on the device
 //   ehx_search.cpp  ehx_knn_device / ehx_knn (host pointers, micro-batcher) / keys / merge
 //   ehx_call.cpp    what the batched entry points share: argument checks, the entry scaffold, key lookup, result blocks, host
 //                   staging, sub-batches, the int8 radius scan
@@ -298,6 +299,10 @@ struct ehx_space {
     Event wev;                 // blocking-sync event: a writer waiting for its stream sleeps instead of spinning
     Event sev[2];              // "upload out of staging half i has finished" (ping-pong staging)
     PinBuf<float> hStage;      // pinned staging (Set / Get / query upload), ensure_stage
+    DevBuf<uint64_t> dDstRows; // a Set from device memory: the stored row of every source row (~0: not written)
+    DevBuf<uint32_t> dSrcIdx;  // ... a shard's: the batch positions of its rows
+    Event tev[3];              // test hook ehx_test_write_times: rows in flight | rows landed | derived copies made, of the
+    bool timed = false;        // last write (recorded only once the hook has asked for them)
   } wr;
   int device = 0;              // HIP device of this space's HBM state
   // Row sharding behind the C ABI (ehx_params.shards > 1): the PARENT keeps the key maps and no rows; global row g
@@ -693,6 +698,11 @@ int flat_chain_rest(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, con
                     uint64_t* d_ids, float* d_dist, uint32_t* d_count, int eng, const I8Outcome* i8);
 
 // ---- ehx_search.cpp ----
+// The gather's view of a row-sharded parent (locked shared) on the prefix of n_pub rows: every shard locked shared into
+// *held (parent, then shards, as ehx_get_by_id takes them; hold them until the gather has read the rows), its rows' base in
+// g->bases, shape and layout in g->rows, g->G.  A dropped or poisoned shard, more than kMaxShardBases shards, or a shard
+// without peer access to shard 0's device (EHX_ALLOW_NO_PEER) is refused.
+int parent_gather_view(ehx_space* p, uint64_t n_pub, std::vector<std::shared_lock<std::shared_mutex>>* held, GatherRowsArgs* g);
 void yield_to_writer(const ehx_space* s);   // a search lets an exclusive writer that waits for the space's lock in first
 // the keys of result lists [n][k] (counts out_count) packed into key_arena, key_off[n * k + 1]: ehx_knn_keys' layout
 int fill_key_arena(ehx_space* s, size_t n, uint32_t k, const uint64_t* out_ids, const uint32_t* out_count, char* key_arena,
@@ -819,14 +829,36 @@ int among_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries
 // ---- ehx_write.cpp ----
 int sync_stream(ehx_space* s, hipStream_t st);
 int refresh_scan16(ehx_space* s, uint64_t row0, uint64_t n, hipStream_t st, bool exclusive, uint64_t n_after);
-int write_rows_locked_fwd(ehx_space* s, size_t n, const std::vector<uint64_t>& ids, uint64_t next, const float* vecs);
+// Where the rows of a Set come from: host floats [n][dims], staged and uploaded (ehx_set_batch), or a dense [*][dims] matrix
+// in device memory, scattered by scatter_rows_kernel (ehx_set_batch_device).
+struct RowSource {
+  const float* host = nullptr;
+  const void* dev = nullptr;       // device rows, EHX_DTYPE_F32 or EHX_DTYPE_F16 (dtype), on `device`
+  int dtype = EHX_DTYPE_F32;
+  int device = 0;
+  hipEvent_t ready = nullptr;      // recorded behind the work that produced them: the writers' stream waits for it
+  const uint32_t* idx = nullptr;   // device rows of a shard: the positions of its rows in the batch (nullptr: 0, 1, ...)
+  size_t elem_bytes() const { return dtype == EHX_DTYPE_F16 ? sizeof(_Float16) : sizeof(float); }
+  RowSource from(size_t i, uint32_t dims) const {   // the batch without its first i rows
+    RowSource r = *this;
+    if (host) r.host = host + i * dims;
+    else r.dev = (const char*)dev + i * dims * elem_bytes();
+    return r;
+  }
+};
+// the body of ehx_set_batch and ehx_set_batch_device: locking, the append-only fast path, graph batches that rewrite keys
+int set_batch_from(ehx_space* s, size_t n, const char* const* keys, const size_t* klens, const RowSource& src);
+int write_rows_locked_fwd(ehx_space* s, size_t n, const std::vector<uint64_t>& ids, uint64_t next, const RowSource& src);
+// The duplicate rule of a parallel scatter: out[i] = ids[i] for the LAST occurrence of every id, ~0 for the ones before it —
+// a key given twice in one batch keeps its last row, as the host path's in-order copies leave it.
+void last_writers(const uint64_t* ids, size_t n, uint64_t* out);
 
 // ---- ehx_api.cpp ----
 int fill_synthetic_locked(ehx_space* s, uint64_t seed, uint64_t row0, uint64_t n_rows, int normalize, uint64_t stride,
                           uint32_t latent = 0);
 
 // ---- ehx_shards.cpp ----
-int sharded_set_batch(ehx_space* p, size_t n, const char* const* keys, const size_t* klens, const float* vecs);
+int sharded_set_batch(ehx_space* p, size_t n, const char* const* keys, const size_t* klens, const RowSource& src);
 int sharded_fill_synthetic(ehx_space* p, uint64_t seed, uint64_t row0, uint64_t n_rows, int normalize, uint32_t latent = 0);
 int sharded_knn(ehx_space* p, size_t nq, const float* h_queries, const float* d_queries, int qdev, uint32_t k,
                 uint64_t* out_ids, float* out_dist, uint32_t* out_count, bool out_on_device, hipStream_t caller_stream);

@@ -432,6 +432,18 @@ struct DropSelfArgs {
 };
 hipError_t launch_drop_self(const DropSelfArgs& a, hipStream_t st);
 
+// rows written from device memory (k_rowio.hip): the gather's mirror, one wave per source row
+struct ScatterRowsArgs {
+  const void* src;          // dense [*][dims] source rows, fp32 or binary16 (src_half); element-aligned
+  const uint32_t* src_idx;  // [n] source row of work item i, or nullptr: i (a shard passes the batch positions of its rows)
+  const uint64_t* dst_row;  // [n] stored row of work item i, ~0 = not written; or nullptr: row0 + i (a contiguous append)
+  uint64_t row0;
+  void* X;                  // the stored rows [*][ld], fp32 or binary16 (x_half); columns [dims, ld) are not touched
+  uint32_t ld, dims, x_half, src_half;
+  uint32_t n;
+};
+hipError_t launch_scatter_rows(const ScatterRowsArgs& a, hipStream_t st);
+
 // exact kNN among a caller's list of row ids (k_among.hip): the canonical distance of every listed row, best 64
 // (distance, id) keys per workgroup -> out[q][n_blocks][64] (launch_flat_merge's input)
 constexpr uint32_t kAmongTileQ = 8;     // shared list: queries a workgroup applies a staged tile of rows to

@@ -82,9 +82,8 @@ static int by_ids_locked(ehx_space* s, hipStream_t st, size_t n, const uint64_t*
   return rc;
 }
 
-// a row-sharded parent, locked shared, its scratch_mu held, shard 0's device current: gathered over peer access into the
-// parent's scratch, searched by every shard, merged and trimmed on shard 0's device (on the parent's stream)
-static int sharded_by_ids_locked(ehx_space* p, size_t n, const uint64_t* d_row_ids, uint32_t k, const ByKeyScratch& b) {
+int ehx_impl::parent_gather_view(ehx_space* p, uint64_t n_pub, std::vector<std::shared_lock<std::shared_mutex>>* held,
+                                 GatherRowsArgs* g) {
   const size_t G = p->shards.size();
   const int home = p->shards[0]->device;
   if (G > kMaxShardBases) return fail(EHX_EUNSUPPORTED, "%zu shards exceed %u", G, kMaxShardBases);
@@ -93,25 +92,33 @@ static int sharded_by_ids_locked(ehx_space* p, size_t n, const uint64_t* d_row_i
       if (c->device != home)
         return fail(EHX_EUNSUPPORTED, "space '%s': device %d has no peer access to device %d (EHX_ALLOW_NO_PEER): the rows "
                                       "of a key batch are gathered over it", p->name.c_str(), home, c->device);
+  held->reserve(G);
+  for (size_t i = 0; i < G; ++i) {
+    ehx_space* c = p->shards[i];
+    held->emplace_back(c->mu);
+    if (c->dropped) return fail(EHX_ENOTFOUND, "Not found");
+    if (int rcp = check_not_poisoned(c)) return rcp;
+    g->bases.p[i] = c->rows.dX.p;
+  }
+  g->rows = rows_view(p->shards[0], n_pub);   // (shape and layout are the shards'; the rows: bases)
+  g->G = (uint32_t)G;
+  return EHX_OK;
+}
+
+// a row-sharded parent, locked shared, its scratch_mu held, shard 0's device current: gathered over peer access into the
+// parent's scratch, searched by every shard, merged and trimmed on shard 0's device (on the parent's stream)
+static int sharded_by_ids_locked(ehx_space* p, size_t n, const uint64_t* d_row_ids, uint32_t k, const ByKeyScratch& b) {
+  const int home = p->shards[0]->device;
   const uint64_t n_pub = p->n.load(std::memory_order_acquire);
   {
-    // parent, then shards, as ehx_get_by_id and sharded_knn take them; held until the gather has read the rows
+    // held until the gather has read the rows
     std::vector<std::shared_lock<std::shared_mutex>> held;
-    held.reserve(G);
     GatherRowsArgs g = {};
-    for (size_t i = 0; i < G; ++i) {
-      ehx_space* c = p->shards[i];
-      held.emplace_back(c->mu);
-      if (c->dropped) return fail(EHX_ENOTFOUND, "Not found");
-      if (int rcp = check_not_poisoned(c)) return rcp;
-      g.bases.p[i] = c->rows.dX.p;
-    }
+    if (int rcv = parent_gather_view(p, n_pub, &held, &g)) return rcv;
     g.row_ids = d_row_ids;
-    g.rows = rows_view(p->shards[0], n_pub);   // (shape and layout are the shards'; the rows: bases)
     g.out = p->by.dByQ.p;
     g.valid = b.valid;
     g.n = (uint32_t)n;
-    g.G = (uint32_t)G;
     HIP_TRY(launch_gather_rows(g, p->stream));
     HIP_TRY(hipStreamSynchronize(p->stream));
   }

@@ -23,20 +23,32 @@ int for_each_shard(ehx_space* p, const std::function<int(size_t)>& f) {
 }
 
 // parent locked exclusively by the caller
-int sharded_set_batch(ehx_space* p, size_t n, const char* const* keys, const size_t* klens, const float* vecs) {
+// src: host rows, copied into one matrix per shard; or device rows, which every shard reads where they are (over peer access
+// when they are on another device), each its own by their positions in the batch
+int sharded_set_batch(ehx_space* p, size_t n, const char* const* keys, const size_t* klens, const RowSource& src) {
   if (p->frozen) return fail(EHX_EIMMUTABLE, "Cannot write to immutable space");
   if (p->implicit_keys) return fail(EHX_EINVAL, "space '%s' holds synthetic rows with implicit keys", p->name.c_str());
   const uint64_t G = p->shards.size();
+  if (src.dev) {
+    if (n > 0xFFFFFFFFull) return fail(EHX_EINVAL, "too many rows in one call: %zu", n);
+    if (!engine().peer_all)
+      for (ehx_space* c : p->shards)
+        if (c->device != src.device)
+          return fail(EHX_EUNSUPPORTED, "space '%s': device %d has no peer access to device %d (EHX_ALLOW_NO_PEER): the shards "
+                                        "read the rows of a device batch over it", p->name.c_str(), c->device, src.device);
+  }
   std::vector<uint64_t> ids;
   std::vector<std::string> new_keys;
   uint64_t next = 0;
   resolve_keys(p, n, keys, klens, &ids, &next, &new_keys);
   std::vector<std::vector<uint64_t>> lids(G);
   std::vector<std::vector<float>> rows(G);
+  std::vector<std::vector<uint32_t>> pos(G);
   for (size_t i = 0; i < n; ++i) {
     const uint64_t sh = ids[i] % G;
     lids[sh].push_back(ids[i] / G);
-    rows[sh].insert(rows[sh].end(), vecs + i * p->dims, vecs + (i + 1) * p->dims);
+    if (src.dev) pos[sh].push_back((uint32_t)i);
+    else rows[sh].insert(rows[sh].end(), src.host + i * p->dims, src.host + (i + 1) * p->dims);
   }
   std::vector<uint64_t> before(G);
   for (size_t i = 0; i < G; ++i) before[i] = p->shards[i]->n;
@@ -61,7 +73,10 @@ int sharded_set_batch(ehx_space* p, size_t n, const char* const* keys, const siz
     std::lock_guard<std::mutex> cg(c->wmu);
     std::unique_lock<std::shared_mutex> wl(c->mu);
     const uint64_t next_local = (next + G - 1 - i) / G;  // globals below `next` that belong to shard i
-    return write_rows_locked_fwd(c, lids[i].size(), lids[i], next_local, rows[i].data());
+    RowSource mine = src;
+    if (src.dev) mine.idx = pos[i].data();
+    else mine.host = rows[i].data();
+    return write_rows_locked_fwd(c, lids[i].size(), lids[i], next_local, mine);
   });
   if (rc) {
     // A failing shard (e.g. out of memory while growing) must not leave the others ahead of the parent: their published

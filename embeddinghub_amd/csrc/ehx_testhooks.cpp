@@ -14,6 +14,10 @@
 // ... and of the large-k scan route (ehx_largek.cpp):
 //   ehx_test_largek_counters   what the route did so far on a space
 //   ehx_test_largek_plan       the route's pass planner, host arithmetic only (no device, no space)
+// ... and of the Set from device memory (ehx_rowio.cpp, ehx_write.cpp):
+//   ehx_test_last_writers      the duplicate rule of its scatter, host arithmetic only (no device, no space)
+//   ehx_test_write_times       device time of the last write's upload (or scatter) and of its derived copies (scripts/bench_rowio.py)
+//   ehx_test_shard             the handle of one shard of a row-sharded space (what a caller that kept one would hold)
 // No production path calls in here.
 #include "ehx_internal.h"
 
@@ -391,6 +395,35 @@ uint32_t ehx_test_largek_plan(uint64_t n_rows, uint32_t growth, uint32_t* out_pa
   }
   return (uint32_t)p.size();
 }
+
+// last_writers(ids[0, n)) into out[0, n): every id's last occurrence keeps it, the ones before it become 2^64 - 1
+void ehx_test_last_writers(const uint64_t* ids, size_t n, uint64_t* out) { last_writers(ids, n, out); }
+
+// The writers' stream's time of the last ehx_set_batch / ehx_set_batch_device on an unsharded space, in ms: out[0] the rows
+// (staging copies and uploads, or the wait for the producer and the scatter), out[1] what follows up to the publish (block
+// permutation, row statistics, scan copies).  The first call arms the events and answers EHX_ENOTFOUND: time the writes after it.
+int ehx_test_write_times(ehx_space* s, float out[2]) {
+  int rc = hook_space(s, "ehx_test_write_times", 0);
+  if (rc) return rc;
+  if (!out) return fail(EHX_EINVAL, "NULL argument");
+  std::lock_guard<std::mutex> wl(s->wmu);
+  HIP_TRY(hipSetDevice(s->device));
+  if (!s->wr.timed) {
+    for (Event& e : s->wr.tev)
+      if ((rc = e.ensure())) return rc;
+    s->wr.timed = true;
+    return fail(EHX_ENOTFOUND, "no write timed yet");
+  }
+  if (hipEventElapsedTime(&out[0], s->wr.tev[0], s->wr.tev[1]) != hipSuccess ||
+      hipEventElapsedTime(&out[1], s->wr.tev[1], s->wr.tev[2]) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(EHX_ENOTFOUND, "no write timed yet");
+  }
+  return EHX_OK;
+}
+
+// shard i of a row-sharded space, NULL for any other space or index
+ehx_space* ehx_test_shard(ehx_space* s, uint32_t i) { return s && i < s->shards.size() ? s->shards[i] : nullptr; }
 
 // how many ehx_knn calls the one-launch kernels answered (single_query_kernel, the graph search's one-launch form)
 uint64_t ehx_test_one_launch_count(ehx_space* s) { return s ? s->n_one_launch.load(std::memory_order_relaxed) : 0; }

@@ -2,10 +2,12 @@
 // scan copies, graph insertion, and the write combiner of concurrent single-row Sets.
 #include "ehx_internal.h"
 
+#include <unordered_set>
+
 extern "C" {
 
-static int set_batch_locked(ehx_space* s, size_t n, const char* const* keys, const size_t* klens, const float* vecs);
-static int write_rows_locked(ehx_space* s, size_t n, const std::vector<uint64_t>& ids, uint64_t next, const float* vecs,
+static int set_batch_locked(ehx_space* s, size_t n, const char* const* keys, const size_t* klens, const RowSource& src);
+static int write_rows_locked(ehx_space* s, size_t n, const std::vector<uint64_t>& ids, uint64_t next, const RowSource& src,
                              std::vector<std::string>* new_keys, bool append_only = false);
 static bool all_fresh_keys(const ehx_space* s, size_t n, const std::vector<uint64_t>& ids);
 
@@ -13,6 +15,14 @@ int ehx_set_batch(ehx_space* s, size_t n, const char* const* keys, const size_t*
   if (!valid_space(s)) return fail(EHX_EINVAL, "space is NULL");
   if (n == 0) return EHX_OK;
   if (!keys || !klens || !vecs) return fail(EHX_EINVAL, "NULL argument");
+  RowSource src;
+  src.host = vecs;
+  return set_batch_from(s, n, keys, klens, src);
+}
+
+}  // extern "C"
+
+int ehx_impl::set_batch_from(ehx_space* s, size_t n, const char* const* keys, const size_t* klens, const RowSource& src) {
   std::lock_guard<std::mutex> wg(s->wmu);
   if (!is_parent(s) && s->params.mode == EHX_MODE_FLAT) {
     // Streaming fast path (copy.go's BatchSet chunks, MultiSet): a batch made only of fresh keys is a pure append.
@@ -30,14 +40,14 @@ int ehx_set_batch(ehx_space* s, size_t n, const char* const* keys, const size_t*
         fast = new_keys.size() == n && all_fresh_keys(s, n, ids);
       }
     }
-    if (fast) return write_rows_locked(s, n, ids, next, vecs, &new_keys, true);
+    if (fast) return write_rows_locked(s, n, ids, next, src, &new_keys, true);
   }
   s->excl_waiting.fetch_add(1, std::memory_order_release);   // (searches that arrive from here on wait for this batch's turn)
   std::unique_lock<std::shared_mutex> wl(s->mu);
   s->excl_waiting.fetch_sub(1, std::memory_order_release);
   if (s->dropped) return fail(EHX_ENOTFOUND, "Not found");
   if (s->keyless) return fail(EHX_EINVAL, "a shard is written through its parent space");
-  auto write = [&](size_t cnt, const char* const* ks, const size_t* kl, const float* v) -> int {
+  auto write = [&](size_t cnt, const char* const* ks, const size_t* kl, const RowSource& v) -> int {
     return is_parent(s) ? sharded_set_batch(s, cnt, ks, kl, v) : set_batch_locked(s, cnt, ks, kl, v);
   };
   if (s->params.mode == EHX_MODE_GRAPH && n > 1 && s->params.build_batch != 0xFFFFFFFFu) {
@@ -55,14 +65,16 @@ int ehx_set_batch(ehx_space* s, size_t n, const char* const* keys, const size_t*
     }
     if (rewrite) {
       for (size_t i = 0; i < n; ++i) {
-        int rc = write(1, keys + i, klens + i, vecs + i * s->dims);
+        int rc = write(1, keys + i, klens + i, src.from(i, s->dims));
         if (rc) return rc;
       }
       return EHX_OK;
     }
   }
-  return write(n, keys, klens, vecs);
+  return write(n, keys, klens, src);
 }
+
+extern "C" {
 
 // rows -> pinned staging (fp16 spaces: rounded to binary16, round-to-nearest-even, on the way); large slabs are split
 // over four threads
@@ -170,13 +182,13 @@ int refresh_scan16(ehx_space* s, uint64_t row0, uint64_t n, hipStream_t st, bool
 
 extern "C" {
 
-static int set_batch_locked(ehx_space* s, size_t n, const char* const* keys, const size_t* klens, const float* vecs) {
+static int set_batch_locked(ehx_space* s, size_t n, const char* const* keys, const size_t* klens, const RowSource& src) {
   if (s->frozen) return fail(EHX_EIMMUTABLE, "Cannot write to immutable space");
   std::vector<uint64_t> ids;
   std::vector<std::string> new_keys;
   uint64_t next = 0;
   resolve_keys(s, n, keys, klens, &ids, &next, &new_keys);
-  return write_rows_locked(s, n, ids, next, vecs, &new_keys);
+  return write_rows_locked(s, n, ids, next, src, &new_keys);
 }
 
 // every key of the batch is new and distinct: the rows are a pure append
@@ -186,13 +198,13 @@ static bool all_fresh_keys(const ehx_space* s, size_t n, const std::vector<uint6
   return true;
 }
 
-// rows `vecs[i]` -> row ids[i] of the space (ids < next; ids >= s->n are appended, dense), then statistics, derived
+// rows `src[i]` -> row ids[i] of the space (ids < next; ids >= s->n are appended, dense), then statistics, derived
 // copies, graph; finally publishes the keys (new_keys, in id order from s->n) and the new row count `next`.
 //   append_only = false: the caller holds s->mu exclusively (rows may be rewritten in place, graphs change).
 //   append_only = true : flat spaces, every id >= s->n.  The caller holds s->wmu only: searches keep running while
 //     the rows are uploaded, described and copied BEYOND the published row count (every kernel masks rows >= n),
 //     on the writers' stream; s->mu is taken exclusively just to grow the arrays (rare) and to publish.
-static int write_rows_locked(ehx_space* s, size_t n, const std::vector<uint64_t>& ids, uint64_t next, const float* vecs,
+static int write_rows_locked(ehx_space* s, size_t n, const std::vector<uint64_t>& ids, uint64_t next, const RowSource& src,
                              std::vector<std::string>* new_keys, bool append_only) {
   if (s->frozen) return fail(EHX_EIMMUTABLE, "Cannot write to immutable space");
   HIP_TRY(hipSetDevice(s->device));
@@ -201,6 +213,8 @@ static int write_rows_locked(ehx_space* s, size_t n, const std::vector<uint64_t>
   if (!append_only) {
     int rcw = wait_searches_in_flight(s, ws);
     if (rcw) return rcw;
+    // (... and the gathers of ehx_get_by_ids_device, which read the rows on their callers' streams)
+    if (s->by.by_ev) HIP_TRY(hipStreamWaitEvent(ws, s->by.by_ev, 0));
   }
   const uint64_t old_n = s->n;
   int rc;
@@ -219,7 +233,7 @@ static int write_rows_locked(ehx_space* s, size_t n, const std::vector<uint64_t>
   const size_t row_bytes = (size_t)s->dims * s->esz;
   const size_t slab_rows = std::max<size_t>(1, std::min<size_t>(n, (8u << 20) / row_bytes));
   const size_t half_bytes = (slab_rows * row_bytes + 255) & ~(size_t)255;
-  if ((rc = ensure_stage(s, 2 * half_bytes))) return rc;
+  if (src.host && (rc = ensure_stage(s, 2 * half_bytes))) return rc;
   uint64_t min_id = ~0ull, max_id = 0;
   size_t slab = 0;
   // single-copy graph space: everything fallible that does not depend on the upload happens BEFORE the first row lands
@@ -243,12 +257,51 @@ static int write_rows_locked(ehx_space* s, size_t n, const std::vector<uint64_t>
     bool armed = false;
     ~Poison() { if (armed) s->poisoned.store(true); }
   } poison{s};
-  for (size_t i0 = 0; i0 < n; i0 += slab_rows, ++slab) {
+  if (s->wr.timed) HIP_TRY(hipEventRecord(s->wr.tev[0], ws));
+  // A device source: the id list (and a shard's batch positions) before the first row lands, like the lists above; what is
+  // enqueued is drained unless the call succeeds (the lists are uploaded from this frame)
+  bool dev_run = true;
+  std::vector<uint64_t> dst_rows;
+  DrainUnlessOk dev_drain{ws};
+  dev_drain.ok = src.host != nullptr;
+  if (src.dev) {
+    if (n > 0xFFFFFFFFull) return fail(EHX_EINVAL, "too many rows in one call: %zu", n);
+    for (size_t i = 1; i < n && dev_run; ++i) dev_run = ids[i] == ids[0] + i;
+    if (!dev_run) {
+      dst_rows.resize(n);
+      last_writers(ids.data(), n, dst_rows.data());
+      if ((rc = s->wr.dDstRows.ensure(n))) return rc;
+    }
+    if (src.idx && (rc = s->wr.dSrcIdx.ensure(n))) return rc;
+    if (touches_committed) poison.armed = true;
+    // the rows are complete when `ready` is: the writers' stream waits for the event, the producer's is not drained
+    HIP_TRY(hipStreamWaitEvent(ws, src.ready, 0));
+    // (pageable host memory: the runtime stages it before the call returns)
+    if (!dev_run) HIP_TRY(hipMemcpyAsync(s->wr.dDstRows.p, dst_rows.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, ws));
+    if (src.idx) HIP_TRY(hipMemcpyAsync(s->wr.dSrcIdx.p, src.idx, n * sizeof(uint32_t), hipMemcpyHostToDevice, ws));
+    ScatterRowsArgs a = {};
+    a.src = src.dev;
+    a.src_half = src.dtype == EHX_DTYPE_F16;
+    a.src_idx = src.idx ? s->wr.dSrcIdx.p : nullptr;
+    a.dst_row = dev_run ? nullptr : s->wr.dDstRows.p;
+    a.row0 = ids[0];
+    a.X = s->rows.dX.p;
+    a.ld = s->ld;
+    a.dims = s->dims;
+    a.x_half = (uint32_t)s->x_half;
+    a.n = (uint32_t)n;
+    HIP_TRY(launch_scatter_rows(a, ws));
+    for (size_t i = 0; i < n; ++i) {
+      min_id = std::min(min_id, ids[i]);
+      max_id = std::max(max_id, ids[i]);
+    }
+  }
+  for (size_t i0 = 0; src.host && i0 < n; i0 += slab_rows, ++slab) {
     if (touches_committed) poison.armed = true;
     const size_t m = std::min(slab_rows, n - i0);
     char* stage = (char*)s->wr.hStage.p + (slab & 1) * half_bytes;
     if (slab >= 2) HIP_TRY(hipEventSynchronize(s->wr.sev[slab & 1]));  // the upload that last used this half
-    stage_rows(stage, vecs + i0 * s->dims, m * s->dims, s->x_half);
+    stage_rows(stage, src.host + i0 * s->dims, m * s->dims, s->x_half);
     // contiguous run of fresh ids -> one 2D copy; otherwise row by row
     bool contiguous = true;
     for (size_t i = 1; i < m; ++i)
@@ -268,6 +321,7 @@ static int write_rows_locked(ehx_space* s, size_t n, const std::vector<uint64_t>
     }
   }
   // (the stream is waited for below, before the commit: both halves are free again when this call returns)
+  if (s->wr.timed) HIP_TRY(hipEventRecord(s->wr.tev[1], ws));
   if (s->x_perm) {
     // single-copy graph space: the rows just written go into the search copy's block order, in place, exactly once
     // each (the permutation is its own inverse: a row written twice in this batch is permuted once)
@@ -284,7 +338,9 @@ static int write_rows_locked(ehx_space* s, size_t n, const std::vector<uint64_t>
   HIP_TRY(launch_row_stats(s->rows.dX.p, s->x_half, min_id, max_id - min_id + 1, s->dims, s->ld, s->metric, s->rows.dInv.p,
                            s->rows.dRowp.p, s->rows.dMaxSumsq.p, ws, s->x_perm ? 1 : 0));
   if ((rc = refresh_scan16(s, min_id, max_id - min_id + 1, ws, !append_only, next))) return rc;
+  if (s->wr.timed) HIP_TRY(hipEventRecord(s->wr.tev[2], ws));
   if ((rc = sync_stream(s, ws))) return rc;
+  dev_drain.ok = true;   // (nothing of this call is in flight any more)
   // commit: the rows are resident and described — publish the keys and the new row count
   // (the keys first, under their own lock — searches keep running — then the row count: one release store)
   if (new_keys) {
@@ -307,9 +363,8 @@ static int write_rows_locked(ehx_space* s, size_t n, const std::vector<uint64_t>
     s->n.store(next, std::memory_order_release);   // (the caller holds the space's lock exclusively)
   }
   if (s->params.mode == EHX_MODE_GRAPH) {
-    // new rows join the graph one at a time, in id order (ANNIndex::set -> addPoint, index.cc:36);
-    // rows overwritten in place keep their links (hnswlib's updatePoint repair is not built yet)
-    // in call order: a fresh key is an insertion, a known key hnswlib's update-in-place
+    // the rows join the graph one at a time, in call order (ANNIndex::set -> addPoint, index.cc:36): a fresh key is an
+    // insertion, a known key hnswlib's update-in-place (graph_update: updatePoint's repair of the row's links)
     if (s->g_n == old_n && s->params.build_batch != 0xFFFFFFFFu) {
       if ((rc = graph_ensure_arrays(s))) return rc;
       // Opt-in bulk write (ehx_params.build_batch > 1 given explicitly): a batch made only of fresh keys
@@ -335,8 +390,14 @@ static int write_rows_locked(ehx_space* s, size_t n, const std::vector<uint64_t>
 }  // extern "C"
 
 namespace ehx_impl {
-int write_rows_locked_fwd(ehx_space* s, size_t n, const std::vector<uint64_t>& ids, uint64_t next, const float* vecs) {
-  return write_rows_locked(s, n, ids, next, vecs, nullptr);
+int write_rows_locked_fwd(ehx_space* s, size_t n, const std::vector<uint64_t>& ids, uint64_t next, const RowSource& src) {
+  return write_rows_locked(s, n, ids, next, src, nullptr);
+}
+
+void last_writers(const uint64_t* ids, size_t n, uint64_t* out) {
+  std::unordered_set<uint64_t> seen;
+  seen.reserve(n);
+  for (size_t i = n; i-- > 0;) out[i] = seen.insert(ids[i]).second ? ids[i] : ~0ull;
 }
 }  // namespace ehx_impl
 

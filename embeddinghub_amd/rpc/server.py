@@ -74,6 +74,17 @@ class EngineSpace:
                 return None
             raise
 
+    def get_many(self, keys):
+        """the rows of stored keys as ONE engine call (n keys -> n x dims matrix); an unknown key raises KeyNotFound carrying
+        its position"""
+        from .. import _lib
+        try:
+            return self._s.get_batch(keys)
+        except _lib.EhxError as e:
+            if e.code == _lib.ENOTFOUND:
+                raise KeyNotFound(getattr(e, "bad_index", None))
+            raise
+
     def freeze(self):
         self._s.freeze()
 
@@ -377,12 +388,28 @@ class EmbeddingHubService(pb_grpc.EmbeddingHubServicer):
         finally:
             stop.set()
 
+    DOWNLOAD_CHUNK = 1024  # sorted keys whose rows one engine call fetches while a Download streams
+
     def Download(self, request, context):
+        """streams (key, embedding) in key order.  A store that fetches rows in batches (`get_many`) is asked for
+        DOWNLOAD_CHUNK keys at a time; a key that went missing meanwhile sends its chunk, and any other store every key,
+        through the per-key Get"""
         sp = self._space(request.space, context)
-        for key in sp.keys_sorted():
-            v = sp.get(key)
-            if v is not None:
-                yield pb.DownloadResponse(key=key, embedding=pb.Embedding(values=v.tolist()))
+        keys = sp.keys_sorted()
+        many = getattr(sp, "get_many", None)
+        for i in range(0, len(keys), self.DOWNLOAD_CHUNK):
+            chunk = keys[i:i + self.DOWNLOAD_CHUNK]
+            rows = None
+            if many is not None:
+                try:
+                    rows = many(chunk)
+                except KeyNotFound:
+                    rows = None
+            if rows is None:
+                rows = [sp.get(key) for key in chunk]
+            for key, v in zip(chunk, rows):
+                if v is not None:
+                    yield pb.DownloadResponse(key=key, embedding=pb.Embedding(values=v.tolist()))
 
 
 def make_server(store, address, max_workers=64):

@@ -131,6 +131,18 @@ class Space:
     def set_prepared(self, prep):
         check(self._L.ehx_set_batch(self._h, prep[0], prep[1], prep[2], prep[3]))
 
+    def set_batch_device(self, keys, d_vecs, stream=None):
+        """set_batch with the rows read from device memory (ehx_set_batch_device): d_vecs is a contiguous torch CUDA tensor
+        [n, dims] of float32 or float16 — what a model on the same GPU produced; nothing is copied to the host.  stream:
+        the stream (its address) whose work produced the tensor, None = the default stream.  Returns after the rows are
+        published, as set_batch does."""
+        n, dtype = _device_rows(d_vecs, self.dims)
+        nk, arr, lens, keep = marshal_keys(keys)
+        if nk != n:
+            raise ValueError("keys/vecs length mismatch")
+        check(self._L.ehx_set_batch_device(self._h, C.c_void_p(stream or 0), n, arr, lens, _ptr(d_vecs), dtype))
+        del keep
+
     def graph_import(self, level0, levels, upper, entry_point, max_level):
         """Attach an HNSW graph over the rows already Set (graph mode).
 
@@ -207,6 +219,25 @@ class Space:
         out = np.empty(self.dims, dtype=np.float32)
         check(self._L.ehx_get_by_id(self._h, int(i), out.ctypes.data_as(C.POINTER(C.c_float))))
         return out
+
+    def get_batch(self, keys):
+        """get for a batch of stored keys in ONE engine call (one gather on the device, one copy back) -> f32 [n, dims],
+        row i what get(keys[i]) returns.  An unknown key raises EhxError (ENOTFOUND) whose `bad_index` is its position."""
+        n, arr, lens, keep = marshal_keys(keys)
+        out = np.empty((n, self.dims), dtype=np.float32)
+        bad = C.c_size_t(0)
+        rc = self._L.ehx_get_batch(self._h, n, arr, lens, out.ctypes.data_as(C.POINTER(C.c_float)), C.byref(bad))
+        del keep
+        _check_bad(rc, bad)
+        return out
+
+    def get_by_ids_device(self, d_row_ids, d_out, d_valid, stream=None):
+        """The stored rows by row id without leaving the device (torch CUDA tensors): d_row_ids [n] u64 (int64 storage),
+        d_out [n, dims] f32, d_valid [n] u32 (int32 storage); an id >= len(self) gives a zero row and valid 0."""
+        n = d_row_ids.shape[0] if hasattr(d_row_ids, "shape") else None
+        if n is None:
+            raise ValueError("pass torch tensors (row ids [n])")
+        check(self._L.ehx_get_by_ids_device(self._h, C.c_void_p(stream or 0), n, _ptr(d_row_ids), _ptr(d_out), _ptr(d_valid)))
 
     def key_of(self, i):
         n = C.c_size_t()
@@ -429,6 +460,23 @@ class Space:
         out = (C.c_uint64 * 12)()
         check(self._L.ehx_graph_counters(self._h, out, 12))
         return tuple(int(v) for v in out)  # [4:] phase timers of -DEHX_GRAPH_PROFILE builds, else zeros
+
+
+def _device_rows(t, dims):
+    """The checks of set_batch_device, in front of the C call: a contiguous CUDA tensor [n, dims] of float32 or float16
+    -> (n, EHX_DTYPE_* of the source)"""
+    if isinstance(t, np.ndarray) or not (hasattr(t, "data_ptr") and hasattr(t, "dtype") and hasattr(t, "shape")):
+        raise ValueError("pass a torch CUDA tensor [n, dims]; rows in host memory go through set_batch")
+    dtype = {"torch.float32": _lib.DTYPE_F32, "torch.float16": _lib.DTYPE_F16}.get(str(t.dtype))
+    if dtype is None:
+        raise ValueError("rows must be float32 or float16, got %s" % (t.dtype,))
+    if len(t.shape) != 2 or int(t.shape[1]) != dims:
+        raise ValueError("expected rows of shape [n, %d], got %s" % (dims, tuple(t.shape)))
+    if not getattr(t, "is_cuda", True):
+        raise ValueError("the rows are not on a GPU; rows in host memory go through set_batch")
+    if not t.is_contiguous():
+        raise ValueError("the rows must be contiguous (dense, row-major)")
+    return int(t.shape[0]), dtype
 
 
 def _check_bad(rc, bad):

@@ -197,10 +197,31 @@ int ehx_space_scan_engine(ehx_space* s, uint32_t* engine);
 int ehx_set(ehx_space* s, const char* key, size_t klen, const float* vec /* dims floats */);
 int ehx_set_batch(ehx_space* s, size_t n, const char* const* keys, const size_t* klens,
                   const float* vecs /* n x dims, row-major */);
+/* ehx_set_batch with the rows read from device memory (embeddings that a model on the same GPU just produced): d_vecs is
+ * n x dims, dense and row-major, of float (src_dtype EHX_DTYPE_F32) or IEEE binary16 (EHX_DTYPE_F16) — any other src_dtype:
+ * EHX_EINVAL; element-aligned is enough (a tensor view).  The keys stay on the host.  For the same values the call does what
+ * ehx_set_batch does — row ids, stored bytes, statistics, scan copies, graph insertion and update in call order, the
+ * append-only path that leaves searches running, every error code — except that no row passes through host memory: one
+ * kernel scatters them into the stored rows.  fp32 into an F16 space: rounded to nearest-even binary16
+ * on the device, overflow to +-Inf; binary16 into an F16 space: bit for bit; binary16 into an F32 space: widened exactly.
+ * A key given twice in one batch keeps the row of its last occurrence.  `stream` (a hipStream_t as void*, NULL = default
+ * stream) is the stream whose work produced d_vecs: the writers' stream waits for it through an event, it is not drained.
+ * The call returns after the rows are published, as ehx_set_batch does: d_vecs may be reused at once.  d_vecs must be device
+ * memory (a host pointer: EHX_EINVAL) on the space's device; for a row-sharded space on any device of ehx_init's list — the
+ * shards read it over peer access (EHX_EUNSUPPORTED under EHX_ALLOW_NO_PEER when they have none).  n == 0: EHX_OK. */
+int ehx_set_batch_device(ehx_space* s, void* stream, size_t n, const char* const* keys, const size_t* klens,
+                         const void* d_vecs /* n x dims, row-major, in HBM */, int src_dtype);
 
 /* ---- reads: Get (server.cc:95-111), OnlineStoreTable.Get (online.go:52) ---- */
 int ehx_get(ehx_space* s, const char* key, size_t klen, float* out_vec /* dims floats */);
 int ehx_get_by_id(ehx_space* s, uint64_t id, float* out_vec);
+/* ehx_get for n keys in ONE call (MultiGet / Download, embedding_store.proto:15-18; the same key may appear several times):
+ * all keys are looked up under one hold of the space's lock, the rows gathered on the device and copied back once; row i
+ * equals what ehx_get(keys[i]) returns.  An unknown key fails the whole call with EHX_ENOTFOUND, stores its index in
+ * *bad_index (may be NULL) and leaves out_vecs unwritten (ehx_knn_by_keys' rule).  Flat and graph spaces, F32 and F16,
+ * row-sharded spaces (peer access as for ehx_knn_by_keys).  n == 0: EHX_OK. */
+int ehx_get_batch(ehx_space* s, size_t n, const char* const* keys, const size_t* klens,
+                  float* out_vecs /* n x dims */, size_t* bad_index /* may be NULL */);
 /* key of a row id: copies up to cap bytes, stores the full length in *klen */
 int ehx_key_of(ehx_space* s, uint64_t id, char* out_key, size_t cap, size_t* klen);
 
@@ -289,6 +310,13 @@ int ehx_knn_device(ehx_space* s, void* stream, size_t n_queries, const float* d_
  * k > EHX_MAX_K_PAGED and row-sharded spaces: EHX_EUNSUPPORTED. */
 int ehx_knn_by_ids_device(ehx_space* s, void* stream, size_t n, const uint64_t* d_row_ids, uint32_t k,
                           uint64_t* d_out_ids, float* d_out_dist, uint32_t* d_out_count);
+/* The stored rows themselves, by row id, without leaving HBM: d_out[i] = what ehx_get_by_id(d_row_ids[i]) returns (F16 rows
+ * widened, a single-copy graph space's block order undone), d_valid[i] = 1.  An id at or above the row count — ONE acquire
+ * load of it per call — gives a zero row and d_valid[i] = 0, not an error.  Completion as for ehx_knn_device; on a
+ * row-sharded space (served too: the buffers on shard 0's device, or one with peer access to it) the call waits for the
+ * gather itself.  A Set that rewrites rows in place waits for the call like for any search.  n == 0: EHX_OK. */
+int ehx_get_by_ids_device(ehx_space* s, void* stream, size_t n, const uint64_t* d_row_ids,
+                          float* d_out /* n x dims */, uint32_t* d_valid /* n */);
 /* Exact kNN restricted to lists of row ids (filtered search, re-ranking of candidates found elsewhere): query i has a
  * candidate list L_i of global row ids and the answer is the first k (query, row) pairs over the rows of L_i in (canonical
  * distance, id) order — ehx_knn's contract (NaN rule, +-Inf, cosine normalisation, F16 rows as stored, out_count[i] <= k,
