@@ -369,13 +369,16 @@ int graph_update(ehx_space* s, uint32_t id) {
 }
 
 // graph pipeline: prepared queries -> zero visited bitmaps -> one-wave-per-query search
+// `mask` (optional, batch form only): the strict walk under a row bitmap (k_graphm.hip) — the same arguments, the same
+// wait, clock and refusals; its list is graph_walk_cap(ef) long and the visit log is sized from that.
 // `one` (optional): ONE query per call in ONE launch — the raw query sits in host-visible memory (one->q_host), the
 // kernel prepares it itself, writes ids / distances / count into host-visible memory (d_ids / d_dist / d_count then point
 // there) and publishes one->seq in one->done_flag; no prepare launch, no timing events (nothing between the host's
 // launch and the wave's first instruction but the runtime).
 int knn_graph_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, uint64_t* d_ids,
-                     float* d_dist, uint32_t* d_count, const GraphOneLaunch* one) {
+                     float* d_dist, uint32_t* d_count, const GraphOneLaunch* one, const GraphMask* mask) {
   if (int rcp = check_not_poisoned(s)) return rcp;
+  if (mask && one) return fail(EHX_EINTERNAL, "graph search: a bitmap with the one-launch form");
   if (s->g_n != s->n)
     return fail(EHX_EUNSUPPORTED,
                 "graph mode: the graph covers %llu of %llu rows (rows were written while graph building was "
@@ -383,6 +386,10 @@ int knn_graph_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_que
                 (unsigned long long)s->g_n, (unsigned long long)s->n);
   uint32_t ef = s->params.ef > k ? s->params.ef : k;  // searchKnn: max(ef_, k)
   if (ef > 4096) return fail(EHX_EUNSUPPORTED, "ef=%u exceeds 4096", ef);
+  // (the bitmap walk keeps the row id in 30 bits of its keys)
+  if (mask && s->n > (1ull << 30))
+    return fail(EHX_EUNSUPPORTED, "graph search under a bitmap: %llu rows exceed 2^30", (unsigned long long)s->n);
+  const uint32_t ef_cap = mask ? graph_walk_cap(ef) : ef;   // length of the walk's list
   const uint32_t q_rows = (uint32_t)nq;
   int rc;
   if ((rc = s->scr.dQ.ensure((size_t)q_rows * s->ld))) return rc;
@@ -400,7 +407,7 @@ int knn_graph_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_que
   const bool log_now = one ? true
                            : use_vislog && (size_t)nq * vis_words * sizeof(uint32_t) >= (192u << 20) &&
                                  s->n >= (uint64_t)32000 * ef;
-  const uint32_t vislog_cap = log_now ? 48u * ef + 256u : 0u;
+  const uint32_t vislog_cap = log_now ? 48u * ef_cap + 256u : 0u;
   if ((rc = s->graph.dInsVislog.ensure((size_t)nq * (vislog_cap ? vislog_cap : 1u)))) return rc;
   if ((rc = s->graph.dGraphCounters.ensure_zeroed_once(kGraphCounters))) return rc;
   {
@@ -429,7 +436,7 @@ int knn_graph_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_que
   a.nq = (uint32_t)nq;
   a.k = k;
   a.ef = ef;
-  a.ef_cap = ef;
+  a.ef_cap = ef_cap;
   a.n = (uint32_t)s->n;
   a.dims = s->dims;
   a.ld = s->ld;
@@ -448,6 +455,12 @@ int knn_graph_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_que
   a.width = env().graph_width ? env().graph_width : (s->params.search_width > 1 ? s->params.search_width : 1);
   if (a.width >= 4 && ef < 64) a.width = 2;
   if (a.width >= 2 && ef < 16) a.width = 1;
+  if (mask) {
+    a.width = 1;
+    a.allow = mask->allow;
+    a.allow_bits = (uint32_t)std::min<uint64_t>(mask->n_bits, s->n);
+    a.cap_hits = mask->cap_hits;
+  }
   if (one) {
     a.q_raw = one->q_host;
     a.done_flag = one->done_flag;
@@ -465,7 +478,7 @@ int knn_graph_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_que
   else if (!log_now)
     HIP_TRY(hipMemsetAsync(s->graph.dVisited.p, 0, (size_t)nq * vis_words * sizeof(uint32_t), st));
   s->vis_dirty = !log_now;
-  HIP_TRY(launch_graph_search(a, st));
+  HIP_TRY(mask ? launch_graph_search_masked(a, st) : launch_graph_search(a, st));
   if ((rc = s->clock.scan_end(st)) || (rc = s->clock.finish(st))) return rc;
   s->n_queries += nq;
   return EHX_OK;

@@ -496,9 +496,12 @@ struct ehx_space {
     RadiusKnnBufs scan;
     DevBuf<uint32_t> dMaskRaw;   // host form: the bitmap
     HostStage host;              // host form: queries, and ids | distances | counts
+    DevBuf<unsigned long long> dCapHits;   // [1] the graph walk under a bitmap: queries whose list reached its cap
   } masked;
   // test hook: queries answered on the scan route, on the exact route, queries that overflowed, scan passes launched, calls
   std::atomic<uint64_t> masked_ctr[5] = {};
+  // test hook of the graph walk under a bitmap (ehx_graph_knn_masked*): queries walked, queries answered exactly, calls
+  std::atomic<uint64_t> graphm_ctr[3] = {};
   // exact kNN for EHX_MAX_K < k <= kLargeKScanMax on the int8 radius scan (ehx_largek.cpp; scratch_mu): flagged queries are
   // answered by the exhaustive pass
   RadiusKnnBufs largek;
@@ -629,8 +632,17 @@ struct GraphOneLaunch {   // one query per call in one launch (knn_graph_locked)
   uint32_t* done_flag;     // host-visible; the kernel stores `seq` there when the results are written
   uint32_t seq;
 };
+struct GraphMask {        // the walk under a row bitmap (k_graphm.hip): always the batch form, always the strict order
+  const uint32_t* allow;   // device words; row r is allowed iff r < n_bits and bit r & 31 of word r >> 5 is set
+  uint64_t n_bits;         // already cut at the call's snapshot of the row count
+  unsigned long long* cap_hits;   // device counter: queries whose list reached its cap
+};
+// the walk list's length under a bitmap, a function of ef alone: max(ef, min(EHX_WALK_LIST_FACTOR * ef, EHX_WALK_LIST_MAX))
+inline uint32_t graph_walk_cap(uint32_t ef) {
+  return std::max<uint32_t>(ef, std::min<uint32_t>(EHX_WALK_LIST_FACTOR * ef, EHX_WALK_LIST_MAX));
+}
 int knn_graph_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, uint64_t* d_ids,
-                     float* d_dist, uint32_t* d_count, const GraphOneLaunch* one = nullptr);
+                     float* d_dist, uint32_t* d_count, const GraphOneLaunch* one = nullptr, const GraphMask* mask = nullptr);
 
 // ---- ehx_flat.cpp ----
 struct ScanPlan {

@@ -598,9 +598,17 @@ struct GraphArgs {
   // a time: graph_search_kernel); 2 / 4 = the wide walk (k_graphw.hip: the `width` closest unexpanded entries of the
   // result list are expanded together — same ef bound and termination, fewer dependent memory round trips per query).
   uint32_t width = 1;
+  // The walk under a row bitmap (k_graphm.hip; launch_graph_search_masked only): row r is allowed iff r < allow_bits and
+  // bit r & 31 of allow[r >> 5] is set (allow_bits already cut at the call's row count); ef_cap is then the walk list's
+  // length cap >= ef, and *cap_hits counts the queries whose list reached it.
+  const uint32_t* allow = nullptr;
+  uint32_t allow_bits = 0;
+  unsigned long long* cap_hits = nullptr;
 };
 size_t graph_lds_bytes(uint32_t ld, uint32_t ef_cap, uint32_t width = 1);
 hipError_t launch_graph_search(const GraphArgs& a, hipStream_t st);
+// the strict walk that carries a row bitmap: keys hold the row id in 30 bits (a.n <= 2^30), width is ignored
+hipError_t launch_graph_search_masked(const GraphArgs& a, hipStream_t st);
 
 // graph-mode insertion (k_insert.hip)
 // hipFuncAttributeMaxDynamicSharedMemorySize is set per function AND per device (every device has its own loaded code

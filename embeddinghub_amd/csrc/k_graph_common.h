@@ -1,5 +1,5 @@
-// The pieces the two graph walks share (k_graph.hip: the strict, hnswlib-order-identical walk; k_graphw.hip: the wide
-// walk, several expansions per step) — one copy of each:
+// The pieces the graph walks share (k_graph.hip: the strict, hnswlib-order-identical walk; k_graphw.hip: the wide
+// walk, several expansions per step; k_graphm.hip: the strict walk under a row bitmap) — one copy of each:
 //   GraphLds            the LDS layout: carve() in the kernels, bytes() for the launchers
 //   load_query          one-query form's preparation of the raw query, query row -> LDS in search-copy order
 //   greedy_descent      entry point + upper levels maxlevel..1, with the NaN rule
@@ -248,19 +248,25 @@ __device__ __forceinline__ void merge_sorted_into_R(const GraphLds& L, uint32_t 
 // before every launch).  Writes the k closest of R (already sorted by (dist, id); a NaN seed, if still there, is R's last
 // entry and is not returned), adds the work counters — WIDE: n_steps at [4]; profile builds: the phase ticks behind them —
 // and, in the one-launch form, tells the spinning host thread.
+// (the first half of it, for a walk with an epilogue of its own: k_graphm.hip)
+__device__ __forceinline__ void clear_visited(uint32_t vislog_cap, uint32_t vis_words, int lane, uint32_t* vis,
+                                              const uint32_t* vlog, uint32_t n_logged) {
+  // (the log was written by other lanes, through global memory: a real fence, once per query)
+  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+  if (vislog_cap == 0) {
+  } else if (n_logged <= vislog_cap) {
+    for (uint32_t i = lane; i < n_logged; i += 64) vis[vlog[i] >> 5] = 0u;
+  } else {
+    for (uint32_t i = lane; i < vis_words; i += 64) vis[i] = 0u;
+  }
+}
+
 template <bool WIDE>
 __device__ __forceinline__ void finish_query(const GraphArgs& a, const uint64_t* R, uint32_t nR, uint32_t qi, int lane,
                                              uint32_t* vis, const uint32_t* vlog, uint32_t n_logged, const WalkCounters& c,
                                              const GraphProf& prof) {
-  // (the log was written by other lanes, through global memory: a real fence, once per query)
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-  if (a.vislog_cap == 0) {
-  } else if (n_logged <= a.vislog_cap) {
-    for (uint32_t i = lane; i < n_logged; i += 64) vis[vlog[i] >> 5] = 0u;
-  } else {
-    for (uint32_t i = lane; i < a.vis_words; i += 64) vis[i] = 0u;
-  }
+  clear_visited(a.vislog_cap, a.vis_words, lane, vis, vlog, n_logged);
   uint32_t cnt = nR < a.k ? nR : a.k;
   if (cnt && (uint32_t)(R[cnt - 1] >> 32) == kOrdNaN) cnt -= 1;
   for (uint32_t j = lane; j < a.k; j += 64) {

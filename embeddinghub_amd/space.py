@@ -407,6 +407,30 @@ class Space:
         check(self._L.ehx_knn_masked_device(self._h, C.c_void_p(stream or 0), nq, _ptr(d_queries), k, _ptr(d_mask), int(n_bits),
                                             _ptr(d_ids), _ptr(d_dist), _ptr(d_count)))
 
+    # ---- kNN under a row bitmap on the graph path ----
+    def graph_knn_masked(self, queries, k, allow, n_bits=None, route=_lib.WALK_AUTO):
+        """The k nearest ALLOWED rows the graph walk finds (ehx_graph_knn_masked): approximate when walked, possibly fewer
+        than k entries; route WALK_EXACT (and WALK_AUTO below an allowed share of 1 / WALK_LIST_FACTOR, and every flat
+        space) gives knn_masked's answer.  allow / n_bits as knn_masked.  -> ids [nq,k] u64, dist [nq,k] f32, count [nq] u32."""
+        q, pq = _f32(queries)
+        q = q.reshape(-1, self.dims)
+        nq = q.shape[0]
+        words, n_bits = marshal_mask(allow, n_bits)
+        (ids, dist, cnt), out = _results(nq, k)
+        check(self._L.ehx_graph_knn_masked(self._h, nq, pq, k, words.ctypes.data_as(C.POINTER(C.c_uint32)) if n_bits else None,
+                                           n_bits, int(route), *out))
+        return ids[:, :k], dist[:, :k], cnt
+
+    def graph_knn_masked_device(self, d_queries, k, d_mask, n_bits, d_ids, d_dist, d_count, route=_lib.WALK_AUTO, stream=None):
+        """graph_knn_masked without anything leaving the device: tensors as knn_masked_device's."""
+        nq = d_queries.shape[0] if hasattr(d_queries, "shape") else None
+        if nq is None:
+            raise ValueError("pass torch tensors (queries [nq, dims], mask words)")
+        if hasattr(d_mask, "numel") and d_mask.numel() * 32 < n_bits:
+            raise ValueError("%d mask words hold fewer than n_bits = %d bits" % (d_mask.numel(), n_bits))
+        check(self._L.ehx_graph_knn_masked_device(self._h, C.c_void_p(stream or 0), nq, _ptr(d_queries), k, _ptr(d_mask),
+                                                  int(n_bits), int(route), _ptr(d_ids), _ptr(d_dist), _ptr(d_count)))
+
     # ---- range search (every row within a radius) ----
     def _range_args(self, queries, radius, max_results):
         q, pq = _f32(queries)

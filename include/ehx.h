@@ -95,6 +95,23 @@ enum { EHX_ENGINE_F32 = 0, EHX_ENGINE_F16 = 1, EHX_ENGINE_I8 = 2 };
                                   Graph mode serves any k <= this from its result list of max(ef, k) entries, as
                                   hnswlib's searchKnn does */
 
+/* The graph walk under a row bitmap (ehx_graph_knn_masked*) keeps ONE list of walked nodes, allowed or not, of at most
+ * cap = max(ef, min(EHX_WALK_LIST_FACTOR * ef, EHX_WALK_LIST_MAX)) entries.  The factor is the reciprocal of the smallest
+ * allowed share at which the list can still hold ef allowed entries — below it a walk stops paying, which is where
+ * EHX_WALK_AUTO hands the request to the exact route — and the maximum is the list the kernel keeps in LDS.
+ * The factor was 16 as a choice and is 12 as MEASURED (scripts/bench_graph_masked.py, profiles/graph_masked_bench.jsonl,
+ * batch 1024, k 10, ef 60, one MI355X): with a list of 16 ef the exact route costs what the walk costs at an allowed share
+ * of 1 / 14 on 1 M x 128 L2 rows and of 1 / 11 on 200 k x 768 cosine rows, and at 1 / 16 the walk was 1.14 and 1.66 times
+ * slower than the exact route.  DESIGN.md §e.15 has the table. */
+#define EHX_WALK_LIST_FACTOR 12u
+#define EHX_WALK_LIST_MAX 4096u
+/* route of ehx_graph_knn_masked* (A/B and diagnosis, as ehx_space_set_scan) */
+enum {
+  EHX_WALK_AUTO = 0,  /* walk iff allowed rows * EHX_WALK_LIST_FACTOR >= rows the bitmap covers, else the exact route */
+  EHX_WALK_GRAPH = 1, /* always walk the graph */
+  EHX_WALK_EXACT = 2  /* always the exact route: ehx_knn_masked_device's answer */
+};
+
 typedef struct ehx_space ehx_space; /* opaque; owned by the process-global registry */
 
 /* Index parameters.  Zero-initialise and set what you need; 0 means "reference default"
@@ -282,6 +299,10 @@ int ehx_knn_among_keys(ehx_space* s, size_t n_queries, const float* queries, uin
  * mask has ceil(n_bits / 32) words. */
 int ehx_knn_masked(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, const uint32_t* mask, uint64_t n_bits,
                    uint64_t* out_ids, float* out_dist, uint32_t* out_count);
+/* Graph search under a row bitmap from host pointers: ehx_graph_knn_masked_device (below: the contract) plus the H2D / D2H
+ * copies.  mask has ceil(n_bits / 32) words. */
+int ehx_graph_knn_masked(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, const uint32_t* mask,
+                         uint64_t n_bits, uint32_t route, uint64_t* out_ids, float* out_dist, uint32_t* out_count);
 /* Exact range search from host pointers: ehx_range_device (below: the contract) plus the H2D / D2H copies.  radius has
  * n_queries entries; out_total may be NULL. */
 int ehx_range(ehx_space* s, size_t n_queries, const float* queries, const float* radius, uint32_t max_results,
@@ -358,6 +379,33 @@ int ehx_knn_among_device(ehx_space* s, void* stream, size_t n_queries, const flo
 int ehx_knn_masked_device(ehx_space* s, void* stream, size_t n_queries, const float* d_queries, uint32_t k,
                           const uint32_t* d_mask, uint64_t n_bits, uint64_t* d_out_ids, float* d_out_dist,
                           uint32_t* d_out_count);
+/* Filtered search on the graph path: the k nearest ALLOWED rows found by walking a graph space's HNSW graph under a row
+ * bitmap (allowed as ehx_knn_masked_device defines it: r < n_bits, r below the call's ONE snapshot of the row count, bit
+ * r & 31 of word r >> 5 of d_mask set).  The walk, in words (tests/filtered_walk_model.py states it as code, DESIGN.md
+ * §e.15 has the argument): the upper levels are descended greedily as in ehx_knn_device, the bitmap ignored; at level 0
+ * there is one list of (distance, id) entries sorted by (distance, id), each expanded or not, starting with the descent's
+ * end node whether or not it is allowed.  A step expands the closest unexpanded entry — rows that are not allowed are walked
+ * through, never returned — and merges its unvisited level-0 neighbours into the list (NaN distances dropped); then, if the
+ * list holds at least ef allowed entries, everything behind the ef-th allowed one is deleted, and everything behind position
+ * cap (above, at EHX_WALK_LIST_FACTOR).  The walk ends when no entry is unexpanded; the answer is the first k allowed
+ * entries.  ef = max(the space's ef, k).  This is the rule hnswlib >= 0.7 applies to a filter (isIdAllowed) plus the cap;
+ * with every row allowed it is ehx_knn_device's strict walk, bit for bit.  ehx_params.search_width is ignored: this walk
+ * always expands one node per step.  One query per call takes this batch form too.
+ * route: EHX_WALK_GRAPH walks; EHX_WALK_EXACT gives ehx_knn_masked_device's answer, byte for byte; EHX_WALK_AUTO walks iff
+ * allowed rows * EHX_WALK_LIST_FACTOR >= the rows the bitmap covers (min(n_bits, row count)) and is exact below; any other
+ * value: EHX_EINVAL.  A flat space takes the exact route whatever a valid route says.
+ * A walked answer is APPROXIMATE (recall as a graph search's, falling with the allowed share); the exact route has recall 1.
+ * A walked answer may hold FEWER than k entries although k rows are allowed (the walk ended, or its list was cut at cap,
+ * before it met k of them); n_bits == 0 or no bit set: count 0 on every route.  Sentinels (id 2^64 - 1, +Inf) beyond
+ * d_out_count[i].  Errors as ehx_knn_masked_device: k == 0, NULL outputs, a NULL mask with n_bits > 0: EHX_EINVAL;
+ * k > EHX_MAX_K_PAGED, row-sharded spaces, an effective ef above 4096, a walk over more than 2^30 rows, and on the exact
+ * route rows longer than 40 960 floats: EHX_EUNSUPPORTED; a dropped space: EHX_ENOTFOUND; no device: EHX_ENODEVICE.
+ * Completion as for ehx_knn_device (a walk returns with the kernel queued on `stream`; AUTO and EXACT have waited for the
+ * device to read the allowed count back); a Set that rewrites rows in place waits for the call like for any search.
+ * ehx_graph_counters accumulates the walk's rows fetched and expansions, ehx_stats its queries. */
+int ehx_graph_knn_masked_device(ehx_space* s, void* stream, size_t n_queries, const float* d_queries, uint32_t k,
+                                const uint32_t* d_mask, uint64_t n_bits, uint32_t route, uint64_t* d_out_ids,
+                                float* d_out_dist, uint32_t* d_out_count);
 /* Exact range search: every row closer than a radius.  With D(q, x) the canonical distance ehx_knn reports (cosine, L2^2,
  * inner product as there), row x belongs to query i's answer iff D is not NaN and D <= d_radius[i] as a float comparison
  * (inclusive: a radius that equals a row's distance byte for byte includes that row; -Inf distances under inner product
