@@ -96,6 +96,18 @@ int ResultBlock::copy_out(hipStream_t st, uint64_t* h_ids, float* h_dist, uint32
   return EHX_OK;
 }
 
+int ResultBlock::copy_block_out(hipStream_t st, void* h_pin) const {
+  HIP_TRY(hipMemcpyAsync(h_pin, ids, bytes(nq, k, false), hipMemcpyDeviceToHost, st));
+  return EHX_OK;
+}
+
+void ResultBlock::unpack(const void* h_pin, uint64_t* h_ids, float* h_dist, uint32_t* h_cnt) const {
+  const char* h = (const char*)h_pin;   // (laid out as the device block is; any alignment)
+  memcpy(h_ids, h, nq * k * sizeof(uint64_t));
+  memcpy(h_dist, h + ((const char*)dist - (const char*)ids), nq * k * sizeof(float));
+  memcpy(h_cnt, h + ((const char*)cnt - (const char*)ids), nq * sizeof(uint32_t));
+}
+
 int HostStage::up(hipStream_t st, const float* queries, size_t nq, uint32_t dims, uint32_t k, bool with_total, size_t n_tail) {
   int rc;
   if ((rc = dQraw.ensure(nq * dims + n_tail)) || (rc = dOut.ensure(ResultBlock::bytes(nq, k, with_total)))) return rc;

@@ -5,7 +5,7 @@
 //   ehx_shards.cpp  row-sharded spaces inside one process (ehx_params.shards)
 //   ehx_write.cpp   Set / BatchSet: staging, upload, row statistics, scan copies, write combiner
 //   ehx_rowio.cpp   rows in and out without staging: Set from device memory, batched Get, Get by row ids on the device
-//   ehx_search.cpp  ehx_knn_device / ehx_knn (host pointers, micro-batcher) / keys / merge
+//   ehx_search.cpp  ehx_knn_device / ehx_knn (host pointers: four routes behind the request combiner, ehx_combine.h) / keys / merge
 //   ehx_call.cpp    what the batched entry points share: argument checks, the entry scaffold, key lookup, result blocks, host
 //                   staging, sub-batches, the int8 radius scan
 //   ehx_api.cpp     init, registry, Get, synthetic fill, graph import / export, statistics
@@ -40,6 +40,7 @@
 #include <vector>
 
 #include "../../include/ehx.h"
+#include "ehx_combine.h"
 #include "ehx_env.h"
 #include "ehx_kernels.h"
 
@@ -169,6 +170,10 @@ struct ResultBlock {
     return {ids + q0 * k, dist + q0 * k, cnt + q0, total ? total + q0 : nullptr, m, k};
   }
   int copy_out(hipStream_t st, uint64_t* h_ids, float* h_dist, uint32_t* h_cnt, uint64_t* h_total) const;  // ... and waits
+  // A block `at` carved from one buffer, without totals: ONE copy of all of it into pinned memory, enqueued on `st` and not
+  // waited for; and, once the caller has waited, the host block unpacked into the caller's arrays.
+  int copy_block_out(hipStream_t st, void* h_pin) const;
+  void unpack(const void* h_pin, uint64_t* h_ids, float* h_dist, uint32_t* h_cnt) const;
 };
 
 // Launches of a call that failed may still be in flight: unless the call succeeded they are drained — and the runtime's
@@ -315,6 +320,7 @@ struct ehx_space {
     Event xev;                       // shard only: "my local top-k has reached the gather buffer" (the parent's stream waits)
     DevBuf<unsigned char> dOutPack;  // shard only: ids | distances | counts of one batch, contiguous: ONE peer copy
     DevBuf<unsigned char> dGPack;    // parent scratch on shards[0]'s device: the G packed results, one slot per shard
+    DevBuf<unsigned char> dMergedOut;  // ... and the merged result, one block
   } xch;
 
   // HBM-resident state.  Every device / pinned resource below is an owner (ehx_own.h) inside a group named after what
@@ -445,9 +451,7 @@ struct ehx_space {
   Stream stream;               // the space's search stream (create_one)
   struct Scratch {
     DevBuf<float> dQraw, dQ;
-    DevBuf<uint64_t> dCand, dPart, dMerged, dOutIds, dGthr;
-    DevBuf<float> dOutDist;
-    DevBuf<uint32_t> dOutCount;
+    DevBuf<uint64_t> dCand, dPart, dMerged, dGthr;
     DevBuf<uint32_t> dScanErr;                 // one word: times a scan kernel tripped its bounded-retry guard (ehx_stats)
     // filter scratch: fp16 queries, per-query (gamma, u, v), re-run buffers
     DevBuf<__half> dQ16;
@@ -540,36 +544,24 @@ struct ehx_space {
   // idled the queue ~36 us of a 0.35-ms batch)
   BatchClock clock;
 
-  // micro-batcher: concurrent small ehx_knn calls are coalesced into one device batch
-  struct KnnReq {
+  // micro-batcher: concurrent small ehx_knn calls are coalesced into one device batch (ehx_search.cpp)
+  struct KnnReq : CombineReq {
     const float* q;
     size_t nq;
     uint32_t k;
-    uint64_t* ids;
+    uint64_t* ids;   // the caller's [nq][k] ids, [nq][k] distances, [nq] counts
     float* dist;
     uint32_t* cnt;
-    int rc = 0;
-    bool done = false;
-    char err[256] = "";
   };
-  std::mutex bq_mu;
-  std::condition_variable bq_cv;
-  std::vector<KnnReq*> bq;
-  bool bq_leader = false;
+  Combiner<KnnReq> knn_combiner;
   std::atomic<uint64_t> n_coalesced_batches{0}, n_coalesced_queries{0};
   // write-combiner: concurrent single-row ehx_set calls (runner/copy.go: 500 goroutines per chunk) become one batch
-  struct SetReq {
+  struct SetReq : CombineReq {
     const char* key;
     size_t klen;
     const float* vec;
-    int rc = 0;
-    bool done = false;
-    char err[256] = "";
   };
-  std::mutex wq_mu;
-  std::condition_variable wq_cv;
-  std::vector<SetReq*> wq;
-  bool wq_leader = false;
+  Combiner<SetReq> set_combiner;
   std::atomic<uint64_t> n_combined_sets{0}, n_combined_batches{0};
 
   // stats

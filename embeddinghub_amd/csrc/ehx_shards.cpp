@@ -149,12 +149,9 @@ int sharded_knn_locked(ehx_space* p, size_t nq, const float* h_queries, const fl
   const int home = p->shards[0]->device;
   int rc;
   HIP_TRY(hipSetDevice(home));
-  const size_t o_dist = nq * k * sizeof(uint64_t), o_cnt = o_dist + nq * k * sizeof(float);
-  const size_t P = (o_cnt + nq * sizeof(uint32_t) + 15) / 16 * 16;  // one shard's packed result
-  if ((rc = p->xch.dGPack.ensure(G * P))) return rc;
-  if ((rc = p->scr.dOutIds.ensure(nq * k))) return rc;
-  if ((rc = p->scr.dOutDist.ensure(nq * k))) return rc;
-  if ((rc = p->scr.dOutCount.ensure(nq))) return rc;
+  const size_t P = round_up(ResultBlock::bytes(nq, k, false), 16);  // one shard's packed result
+  if ((rc = p->xch.dGPack.ensure(G * P)) || (rc = p->xch.dMergedOut.ensure(ResultBlock::bytes(nq, k, false)))) return rc;
+  const ResultBlock merged = ResultBlock::at(p->xch.dMergedOut.p, nq, k, false);
   if (d_queries) {  // the caller's stream produced the queries: they must be complete before the shards read them
     HIP_TRY(hipSetDevice(qdev));
     HIP_TRY(hipStreamSynchronize(caller_stream));
@@ -171,12 +168,10 @@ int sharded_knn_locked(ehx_space* p, size_t nq, const float* h_queries, const fl
     if ((r = c->xch.xev.ensure(hipEventDisableTiming))) return r;
     if (d_queries) HIP_TRY(hipMemcpyPeerAsync(c->scr.dQraw.p, c->device, d_queries, qdev, qbytes, c->stream));
     else HIP_TRY(hipMemcpyAsync(c->scr.dQraw.p, h_queries, qbytes, hipMemcpyHostToDevice, c->stream));
-    unsigned char* pk = c->xch.dOutPack.p;
-    if ((r = knn_device_locked(c, c->stream, nq, c->scr.dQraw.p, k, (uint64_t*)pk, (float*)(pk + o_dist),
-                               (uint32_t*)(pk + o_cnt))))
-      return r;
+    const ResultBlock pk = ResultBlock::at(c->xch.dOutPack.p, nq, k, false);
+    if ((r = knn_device_locked(c, c->stream, nq, c->scr.dQraw.p, k, pk.ids, pk.dist, pk.cnt))) return r;
     // the one exchange step
-    HIP_TRY(hipMemcpyPeerAsync(p->xch.dGPack.p + i * P, home, pk, c->device, P, c->stream));
+    HIP_TRY(hipMemcpyPeerAsync(p->xch.dGPack.p + i * P, home, c->xch.dOutPack.p, c->device, P, c->stream));
     HIP_TRY(hipEventRecord(c->xch.xev, c->stream));
     return EHX_OK;
   });
@@ -190,20 +185,18 @@ int sharded_knn_locked(ehx_space* p, size_t nq, const float* h_queries, const fl
   }
   HIP_TRY(hipSetDevice(home));
   for (size_t i = 0; i < G; ++i) HIP_TRY(hipStreamWaitEvent(p->stream, p->shards[i]->xch.xev, 0));
-  const unsigned char* gp = p->xch.dGPack.p;
-  HIP_TRY(launch_merge_lists((const uint64_t*)gp, (const float*)(gp + o_dist), (const uint32_t*)(gp + o_cnt),
-                             (uint32_t)nq, k, (uint32_t)G, p->scr.dOutIds.p, p->scr.dOutDist.p, p->scr.dOutCount.p, p->stream, P, P,
-                             P, (uint64_t)G, 1));
+  const ResultBlock g0 = ResultBlock::at(p->xch.dGPack.p, nq, k, false);   // shard 0's slot; shard i's: P bytes further each
+  HIP_TRY(launch_merge_lists(g0.ids, g0.dist, g0.cnt, (uint32_t)nq, k, (uint32_t)G, merged.ids, merged.dist, merged.cnt,
+                             p->stream, P, P, P, (uint64_t)G, 1));
+  // (either way the stream is waited for: the shards' scratch may be reused by the next call, all of it is done)
   if (out_on_device) {
-    HIP_TRY(hipMemcpyPeerAsync(out_ids, qdev, p->scr.dOutIds.p, home, nq * k * sizeof(uint64_t), p->stream));
-    HIP_TRY(hipMemcpyPeerAsync(out_dist, qdev, p->scr.dOutDist.p, home, nq * k * sizeof(float), p->stream));
-    HIP_TRY(hipMemcpyPeerAsync(out_count, qdev, p->scr.dOutCount.p, home, nq * sizeof(uint32_t), p->stream));
-  } else {
-    HIP_TRY(hipMemcpyAsync(out_ids, p->scr.dOutIds.p, nq * k * sizeof(uint64_t), hipMemcpyDeviceToHost, p->stream));
-    HIP_TRY(hipMemcpyAsync(out_dist, p->scr.dOutDist.p, nq * k * sizeof(float), hipMemcpyDeviceToHost, p->stream));
-    HIP_TRY(hipMemcpyAsync(out_count, p->scr.dOutCount.p, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipMemcpyPeerAsync(out_ids, qdev, merged.ids, home, nq * k * sizeof(uint64_t), p->stream));
+    HIP_TRY(hipMemcpyPeerAsync(out_dist, qdev, merged.dist, home, nq * k * sizeof(float), p->stream));
+    HIP_TRY(hipMemcpyPeerAsync(out_count, qdev, merged.cnt, home, nq * sizeof(uint32_t), p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+  } else if ((rc = merged.copy_out(p->stream, out_ids, out_dist, out_count, nullptr))) {
+    return rc;
   }
-  HIP_TRY(hipStreamSynchronize(p->stream));  // (the shards' scratch may be reused by the next call: all of it is done)
   p->n_queries += nq;
   return EHX_OK;
 }

@@ -401,70 +401,40 @@ void last_writers(const uint64_t* ids, size_t n, uint64_t* out) {
 }
 }  // namespace ehx_impl
 
-extern "C" {
-
-// Single-row Sets (the reference's usage: one Set per RPC / per goroutine, runner/copy.go:146-161 runs 500 at a time)
-// are combined like the single-query searches are: the first caller becomes the leader, takes every request that
-// queued up meanwhile (up to 4096) and writes them as ONE batch; under load the batch size grows by itself.  A call
-// returns after its row is published, so a following ehx_knn from the same thread sees it (index_test.cc:39-49).
+// Single-row Sets (the reference's usage: one Set per RPC / per goroutine, runner/copy.go:146-161 runs 500 at a time) are
+// combined like the single-query searches are, by the space's request combiner (ehx_combine.h): the leader takes every
+// request that queued up meanwhile (up to 4096) and writes them as ONE batch; under load the batch size grows by itself.  A
+// call returns after its row is published, so a following ehx_knn from the same thread sees it (index_test.cc:39-49).
 constexpr size_t kCombineMaxBatch = 4096;
+typedef Combiner<ehx_space::SetReq>::Group SetGroup;
 
-int ehx_set(ehx_space* s, const char* key, size_t klen, const float* vec) {
-  if (!valid_space(s)) return fail(EHX_EINVAL, "space is NULL");
-  if (!key || !vec) return fail(EHX_EINVAL, "key / vector is NULL");
-  ehx_space::SetReq me;
-  me.key = key;
-  me.klen = klen;
-  me.vec = vec;
-  std::unique_lock<std::mutex> lk(s->wq_mu);
-  s->wq.push_back(&me);
-  std::vector<ehx_space::SetReq*> group;
-  std::vector<const char*> ks;
-  std::vector<size_t> kl;
-  std::vector<float> rows;
-  while (!me.done) {
-    if (s->wq_leader) {
-      s->wq_cv.wait(lk, [&] { return me.done || !s->wq_leader; });
-      continue;
-    }
-    s->wq_leader = true;
-    while (!me.done && !s->wq.empty()) {
-      const size_t m = std::min(s->wq.size(), kCombineMaxBatch);
-      group.assign(s->wq.begin(), s->wq.begin() + m);
-      s->wq.erase(s->wq.begin(), s->wq.begin() + m);
-      lk.unlock();
-      int rc;
-      if (m == 1) {
-        const char* k1[1] = {group[0]->key};
-        size_t l1[1] = {group[0]->klen};
-        rc = ehx_set_batch(s, 1, k1, l1, group[0]->vec);
-      } else {
-        ks.resize(m);
-        kl.resize(m);
-        rows.resize(m * s->dims);
-        for (size_t i = 0; i < m; ++i) {
-          ks[i] = group[i]->key;
-          kl[i] = group[i]->klen;
-          memcpy(rows.data() + i * s->dims, group[i]->vec, s->dims * sizeof(float));
-        }
-        rc = ehx_set_batch(s, m, ks.data(), kl.data(), rows.data());
-        s->n_combined_batches += 1;
-        s->n_combined_sets += m;
-      }
-      lk.lock();
-      for (auto* r : group) {
-        r->rc = rc;
-        if (rc) snprintf(r->err, sizeof(r->err), "%s", g_err);
-        r->done = true;
-      }
-      s->wq_cv.notify_all();
-    }
-    s->wq_leader = false;
-    s->wq_cv.notify_all();
-  }
-  lk.unlock();
-  if (me.rc) snprintf(g_err, sizeof(g_err), "%s", me.err);
-  return me.rc;
+static SetGroup set_take(SetGroup& queue) {
+  const size_t m = std::min(queue.size(), kCombineMaxBatch);
+  SetGroup group(queue.begin(), queue.begin() + m);
+  queue.erase(queue.begin(), queue.begin() + m);
+  return group;
 }
 
-}  // extern "C"
+static int set_serve(ehx_space* s, const SetGroup& group) {   // (a group of one: straight through, no copy)
+  const size_t m = group.size();
+  if (m == 1) return ehx_set_batch(s, 1, &group[0]->key, &group[0]->klen, group[0]->vec);
+  std::vector<const char*> ks(m);
+  std::vector<size_t> kl(m);
+  std::vector<float> rows(m * s->dims);
+  for (size_t i = 0; i < m; ++i) {
+    ks[i] = group[i]->key;
+    kl[i] = group[i]->klen;
+    memcpy(rows.data() + i * s->dims, group[i]->vec, s->dims * sizeof(float));
+  }
+  const int rc = ehx_set_batch(s, m, ks.data(), kl.data(), rows.data());
+  s->n_combined_batches += 1;
+  s->n_combined_sets += m;
+  return rc;
+}
+
+extern "C" int ehx_set(ehx_space* s, const char* key, size_t klen, const float* vec) {
+  if (!valid_space(s)) return fail(EHX_EINVAL, "space is NULL");
+  if (!key || !vec) return fail(EHX_EINVAL, "key / vector is NULL");
+  ehx_space::SetReq me{{}, key, klen, vec};
+  return s->set_combiner.submit(me, set_take, [s](const SetGroup& g) { return set_serve(s, g); }, g_err, sizeof(g_err));
+}
