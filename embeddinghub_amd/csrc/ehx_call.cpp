@@ -186,6 +186,7 @@ int i8_radius_scan(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, cons
   if ((rc = i8_scan_args(s, sc.buf, p, n_pub, &a))) return rc;
   a.allow = c.allow;
   a.allow_bits = c.allow_bits;
+  a.allow_per_query = c.allow_per_query ? 1u : 0u;
   {
     std::lock_guard<std::mutex> ql(s->i8_enqueue_mu);   // (this batch's launches go onto the stream as one block)
     if ((rc = wait_searches_in_flight(s, st))) return rc;
@@ -252,6 +253,7 @@ int radius_knn(ehx_space* s, hipStream_t st, RadiusKnnBufs& w, uint64_t n_pub, c
   scan.passes = &c.passes;
   scan.allow = c.allow;
   scan.allow_bits = c.allow_bits;
+  scan.allow_per_query = c.allow_per_query;
   scan.time_thr = true;
   scan.d_word = w.dWork.p;   // the rows re-ranked (the seed's sample included)
   if (!c.first_radius) {
@@ -291,6 +293,10 @@ int radius_knn(ehx_space* s, hipStream_t st, RadiusKnnBufs& w, uint64_t n_pub, c
     t->queries += m;
     t->handed += todo.size();
     if (todo.empty()) continue;
+    if (c.handed) {
+      if ((rc = c.handed(q0, todo, q, o))) return rc;
+      continue;
+    }
     if ((rc = w.sub.rerun(s, st, q, todo, k, c.exact, o.ids, o.dist, o.cnt))) return rc;
   }
   return EHX_OK;

@@ -502,7 +502,19 @@ struct ehx_space {
     HostStage host;              // host form: queries, and ids | distances | counts
     DevBuf<unsigned long long> dCapHits;   // [1] the graph walk under a bitmap: queries whose list reached its cap
   } masked;
+  // exact kNN under a table of bitmaps, one per query (ehx_maskedq.cpp; scratch_mu)
+  struct MaskedMulti {
+    DevBuf<uint32_t> dBlock;     // [kSideChunk] word offset of the bitmap of every query of a device batch | the bitmaps,
+                                 // [n_masks][words below the row count]: ONE block, the int8 scan's flush reads both
+    DevBuf<uint32_t> dCum;       // [n_masks][n_tiles + 1]
+    DevBuf<uint64_t> dList;      // the masks' ascending lists of allowed ids, back to back
+    DevBuf<uint64_t> dSample;    // [n_masks][256]
+    RadiusKnnBufs scan;          // (its sub-batch: the flagged queries of one mask)
+    SubsetBufs group;            // the call's queries ordered by route and mask
+    HostStage host;              // host form: queries, and ids | distances | counts
+  } maskedq;
   // test hook: queries answered on the scan route, on the exact route, queries that overflowed, scan passes launched, calls
+  // (ehx_knn_masked* and ehx_knn_masked_multi* both count here)
   std::atomic<uint64_t> masked_ctr[5] = {};
   // test hook of the graph walk under a bitmap (ehx_graph_knn_masked*): queries walked, queries answered exactly, calls
   std::atomic<uint64_t> graphm_ctr[3] = {};
@@ -772,6 +784,7 @@ struct RadiusScan {
   const std::vector<TileRange>* passes = nullptr;
   const uint32_t* allow = nullptr;   // optional row bitmap allow[0, allow_bits) in the scan's flush
   uint32_t allow_bits = 0;
+  bool allow_per_query = false;      // allow is the block of ScanArgsI8::allow_per_query: a bitmap per query
   bool time_thr = false;             // the timed scan phase opens in front of the first threshold kernel, not behind it
   // rerank(i, last, a, sc) enqueues pass i's re-rank and records sc.clock.scan_end where its path's timed scan phase ends
   std::function<int(size_t, bool, const ScanArgsI8&, ehx_space::I8Set&)> rerank;
@@ -792,6 +805,7 @@ struct RadiusKnn {
   std::vector<TileRange> passes;
   const uint32_t* allow = nullptr;     // optional row bitmap, as RadiusScan's
   uint32_t allow_bits = 0;
+  bool allow_per_query = false;        // ... or the block of a bitmap per query, as RadiusScan's
   // stage 0, one of two.  first_radius(m, d_q, o, d_radius): enqueued in front of a batch's scan, writes the exact k-th
   // distance over ANY k rows the search may return (+Inf: none known) for its m queries; it may use o's rows, which are
   // written again behind it.  Or, without it, the seed inside the scan's timed phase: the strided sample of rows 0, stride,
@@ -801,6 +815,10 @@ struct RadiusKnn {
   uint32_t n_sample = 0;
   ResultBlock out;                     // out.k <= kLargeKMax
   SubsetBufs::Answer exact;
+  // optional, instead of exact, where the exact answer depends on which query it is (a bitmap per query):
+  // handed(q0, todo, d_q, o) answers the flagged queries todo (ascending, inside the device batch that starts at query q0
+  // of the call, whose queries are d_q and whose rows of the output are o) and writes their rows of o
+  std::function<int(size_t, const std::vector<uint32_t>&, const float*, const ResultBlock&)> handed;
 };
 struct RadiusKnnTally {
   uint64_t batches = 0, queries = 0;     // device batches whose verdict was read, and their queries
@@ -829,6 +847,17 @@ int largek_locked(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, const
 int among_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, const uint64_t* d_ids,
                  const uint64_t* d_off, size_t n_cand, size_t max_list, uint64_t* d_out_ids, float* d_out_dist,
                  uint32_t* d_out_count, bool count_queries = true);
+
+// ---- ehx_masked.cpp (what ehx_maskedq.cpp, a bitmap per query, shares with it) ----
+constexpr uint32_t kMaskedScanMaxK = 48;    // the scan route carries <= k keys per query between passes: the certified engines' k
+constexpr uint64_t kMaskedSample = 256;     // allowed rows in the sample, at most
+constexpr uint64_t kMaskedPassGrowth = 16;  // pass j ends where kMaskedSample * 16^j allowed rows have been seen
+constexpr const char* kMaskedWhy = "filtered search over shards is not built yet";
+uint64_t masked_exact_cut(uint64_t n_pub);  // at most this many allowed rows: the exact route
+int masked_check(const ehx_space* s, size_t nq, uint32_t k, const void* q, const void* mask, uint64_t n_bits, const void* o_ids,
+                 const void* o_dist, const void* o_cnt);
+// tile ranges of the scan passes from cum[t] = allowed rows in tiles [0, t), non-decreasing, cum[n_tiles] their number
+std::vector<TileRange> masked_passes(const std::vector<uint32_t>& cum, uint32_t n_tiles);
 
 // ---- ehx_write.cpp ----
 int sync_stream(ehx_space* s, hipStream_t st);

@@ -14,29 +14,24 @@
 // Entry scaffold and host staging are ehx_call.cpp's (search_shared / on_device, HostStage).
 #include "ehx_internal.h"
 
-namespace {
-
-constexpr uint32_t kMaskedScanMaxK = 48;    // the scan route carries <= k keys per query between passes: the certified engines' k
-constexpr uint64_t kMaskedSample = 256;     // allowed rows in the sample, at most
-constexpr uint64_t kMaskedPassGrowth = 16;  // pass j ends where kMaskedSample * 16^j allowed rows have been seen
+// (the constants of the routes are ehx_internal.h's: ehx_maskedq.cpp routes every query of a table of bitmaps by them)
 // At most this many allowed rows: the exact route.  max(1024, rows / 128), MEASURED (scripts/bench_masked.py, 1 M x 768
 // cosine, batch 1024, k = 10: the list scan costs what the scan route costs at 7 697 allowed rows, 0.77 % of the space;
 // profiles/masked_bench.jsonl).
-uint64_t masked_exact_cut(uint64_t n_pub) { return std::max<uint64_t>(1024, n_pub / 128); }
+uint64_t ehx_impl::masked_exact_cut(uint64_t n_pub) { return std::max<uint64_t>(1024, n_pub / 128); }
 
-int masked_check(const ehx_space* s, size_t nq, uint32_t k, const void* q, const void* mask, uint64_t n_bits, const void* o_ids,
-                 const void* o_dist, const void* o_cnt) {
+int ehx_impl::masked_check(const ehx_space* s, size_t nq, uint32_t k, const void* q, const void* mask, uint64_t n_bits,
+                           const void* o_ids, const void* o_dist, const void* o_cnt) {
   int rc = ehx_init(nullptr, 0);   // (no device: EHX_ENODEVICE, whatever else is wrong with the call)
   if (rc) return rc;
   if ((rc = check_batch_call(s, nq, k, "k", false, o_ids && o_dist && o_cnt && (!nq || q)))) return rc;
   if (n_bits && !mask) return fail(EHX_EINVAL, "NULL mask with n_bits = %llu", (unsigned long long)n_bits);
   return EHX_OK;
 }
-constexpr const char* kMaskedWhy = "filtered search over shards is not built yet";
 
 // tile ranges of the scan passes: pass j (j = 1, 2, ...; the sample is stage 0) ends at the first tile where the allowed
 // rows seen reach kMaskedSample * 16^j, the last pass takes the rest.  cum[t] = allowed rows in tiles [0, t).
-std::vector<TileRange> masked_passes(const std::vector<uint32_t>& cum, uint32_t n_tiles) {
+std::vector<TileRange> ehx_impl::masked_passes(const std::vector<uint32_t>& cum, uint32_t n_tiles) {
   std::vector<TileRange> out;
   uint32_t t0 = 0;
   for (uint64_t want = kMaskedSample * kMaskedPassGrowth; t0 < n_tiles; want *= kMaskedPassGrowth) {
@@ -49,6 +44,8 @@ std::vector<TileRange> masked_passes(const std::vector<uint32_t>& cum, uint32_t 
   }
   return out;
 }
+
+namespace {
 
 // The bitmap of one call, compacted: the call's ONE read of the row count, the rows the bitmap covers below it, the allowed
 // rows before every tile (read back) and, in masked.dList, the ascending list of allowed ids.

@@ -166,7 +166,8 @@ struct I8Ctx {
   uint32_t n;            // valid rows
   uint32_t q_tile0;      // global index of this workgroup's query 0 (q_tile * 256)
   uint32_t allow_bits;   // row ids the bitmap covers
-  const uint32_t* allow; // optional row bitmap (masked kNN): a hit whose row's bit is clear is no candidate
+  const uint32_t* allow; // optional row bitmap (masked kNN): a hit whose row's bit is clear is no candidate; kMaskPerQuery:
+                         // the block [q_rows] word offsets | bitmaps (ScanArgsI8::allow_per_query)
 };
 static_assert(sizeof(I8Ctx) <= 64, "I8Ctx slot");
 
@@ -179,8 +180,12 @@ static_assert(sizeof(I8Ctx) <= 64, "I8Ctx slot");
 // from HBM here (the tile's LDS copy is long gone); the vmcnt queue is drained before returning, so the caller's counted
 // waits see DMA pieces only.
 // MASKED: the masked kNN's scans (k_masked.hip) — a hit whose row the bitmap does not allow is dropped before it takes a pool
-// slot.  A flag of the template, so the scans of every other caller run the flush they always ran.
-template <bool HALF, bool MASKED>
+// slot.  A flag of the template, so the scans of every other caller run the flush they always ran.  Three forms: kMaskNone,
+// kMaskOne (the batch's ONE bitmap) and kMaskPerQuery (ehx_knn_masked_multi*, k_maskedq.hip): ctx->allow is ONE block, the
+// word offset of every query's bitmap inside it ([q_rows], padding queries included) followed by the bitmaps, and the bit
+// tested is that of the bitmap of the hit's own query.
+constexpr int kMaskNone = 0, kMaskOne = 1, kMaskPerQuery = 2;
+template <bool HALF, int MASKED>
 __device__ __attribute__((noinline)) void i8_flush_staging() {
   using L = I8L<HALF>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -203,8 +208,13 @@ __device__ __attribute__((noinline)) void i8_flush_staging() {
     const float S = i8_score(ctx->rowp[posn], qq, v);
     if (!(S <= qq.w) || posn >= ctx->n) continue;
     const uint32_t id = (posn & 0xFFFFFF00u) | (uint32_t)ctx->perm[posn];
-    if constexpr (MASKED) {
+    if constexpr (MASKED == kMaskOne) {
       if (id >= ctx->allow_bits || !((ctx->allow[id >> 5] >> (id & 31u)) & 1u)) continue;
+    }
+    if constexpr (MASKED == kMaskPerQuery) {
+      if (id >= ctx->allow_bits) continue;
+      const uint32_t* block = ctx->allow;
+      if (!((block[(size_t)block[ctx->q_tile0 + qloc] + (id >> 5)] >> (id & 31u)) & 1u)) continue;
     }
     const uint64_t key = ((uint64_t)f32_to_ordered(S) << 32) | (uint64_t)id;
     const uint32_t q = ctx->q_tile0 + qloc;
@@ -221,7 +231,7 @@ __device__ __attribute__((noinline)) void i8_flush_staging() {
 // stage (value, position, query) for the flush, which judges it.  No read, no wait: the staging buffer belongs to this wave
 // alone, so its fill count lives in a wave-uniform register (stg_n) and the slots are handed out by a ballot and a lane
 // prefix count.
-template <bool HALF, bool MASKED>
+template <bool HALF, int MASKED>
 __device__ __forceinline__ void i8_hit(int v, bool hi, uint32_t r_local, uint32_t tile_row0, int ql, int w, uint32_t& stg_n) {
   using L = I8L<HALF>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -259,7 +269,7 @@ size_t scan_i8_lds_bytes() { return I8L<false>::kLdsBytes; }
 // registers each; a stage row's 64 bytes are ONE k-step: lane l holds bytes [16 (l >> 4), +16) of row / query l & 15 of
 // its block — one ds_read_b128 per block and stage, twelve per stage as before.  Every block gets exactly one MFMA
 // per stage.  An accumulator block holds, per lane, rows 4 (l >> 4) + 0..3 of its 16 rows for query l & 15.
-template <bool DUMP, bool REV, bool QRES = false, bool HALF = false, bool PAIR = false, bool MASKED = false>
+template <bool DUMP, bool REV, bool QRES = false, bool HALF = false, bool PAIR = false, int MASKED = kMaskNone>
 __global__ __launch_bounds__(I8L<HALF>::kThreads, 2) void flat_scan_i8_kernel(const ScanArgsI8 a) {
   static_assert(!QRES || (!REV && !DUMP), "QRES: the run-time-slot loop of the plain scan only");
   static_assert(!PAIR || (!REV && !DUMP && !QRES && !HALF), "PAIR: the run-time-slot loop of the plain scan, stages in pairs");
@@ -1007,7 +1017,13 @@ hipError_t launch_flat_scan_i8(const ScanArgsI8& a, hipStream_t st) {
                        (const void*)flat_scan_i8_kernel<false, false, false, false, false, true>,
                        (const void*)flat_scan_i8_kernel<false, false, true, false, false, true>,
                        (const void*)flat_scan_i8_kernel<false, false, true, true, false, true>,
-                       (const void*)flat_scan_i8_kernel<false, false, false, false, true, true>};
+                       (const void*)flat_scan_i8_kernel<false, false, false, false, true, true>,
+                       // ... and once more for a bitmap per query (ehx_knn_masked_multi*)
+                       (const void*)flat_scan_i8_kernel<false, true, false, false, false, kMaskPerQuery>,
+                       (const void*)flat_scan_i8_kernel<false, false, false, false, false, kMaskPerQuery>,
+                       (const void*)flat_scan_i8_kernel<false, false, true, false, false, kMaskPerQuery>,
+                       (const void*)flat_scan_i8_kernel<false, false, true, true, false, kMaskPerQuery>,
+                       (const void*)flat_scan_i8_kernel<false, false, false, false, true, kMaskPerQuery>};
   if (hipError_t e = attr.ensure(fns, (int)(sizeof(fns) / sizeof(fns[0])), I8L<false>::kLdsBytes); e != hipSuccess) return e;
   if (a.ld == 0 || a.ld % kRowBI8) return hipErrorInvalidValue;
   const uint32_t grid = a.q_tiles * a.n_chunks;
@@ -1016,23 +1032,29 @@ hipError_t launch_flat_scan_i8(const ScanArgsI8& a, hipStream_t st) {
   hipLaunchKernelGGL((flat_scan_i8_kernel<D, R>), dim3(grid), dim3(I8L<false>::kThreads), I8L<false>::kLdsBytes, st, a)
   // short rows (a tile of at most four stages): the query tile resident in LDS (QRES in the kernel); EHX_I8_QRES=0: off
   const bool qres_on = env().i8_qres;
-  if (a.allow) {   // the same choice of instantiation as below, MASKED
+  if (a.allow) {   // the same choice of instantiation as below, MASKED: the batch's one bitmap, or one per query
     if (a.dump) return hipErrorInvalidValue;
-    if (rev)
-      hipLaunchKernelGGL((flat_scan_i8_kernel<false, true, false, false, false, true>), dim3(grid), dim3(I8L<false>::kThreads),
-                         I8L<false>::kLdsBytes, st, a);
-    else if (qres_on && env().i8_half && a.ld <= 2 * kRowBI8)
-      hipLaunchKernelGGL((flat_scan_i8_kernel<false, false, true, true, false, true>), dim3(2 * grid), dim3(I8L<true>::kThreads),
-                         I8L<true>::kLdsBytes, st, a);
-    else if (qres_on && a.ld <= 4 * kRowBI8)
-      hipLaunchKernelGGL((flat_scan_i8_kernel<false, false, true, false, false, true>), dim3(grid), dim3(I8L<false>::kThreads),
-                         I8L<false>::kLdsBytes, st, a);
-    else if ((a.ld / kRowBI8) % 2u == 0u)
-      hipLaunchKernelGGL((flat_scan_i8_kernel<false, false, false, false, true, true>), dim3(grid), dim3(I8L<false>::kThreads),
-                         I8L<false>::kLdsBytes, st, a);
-    else
-      hipLaunchKernelGGL((flat_scan_i8_kernel<false, false, false, false, false, true>), dim3(grid), dim3(I8L<false>::kThreads),
-                         I8L<false>::kLdsBytes, st, a);
+#define EHX_LAUNCH_I8_MASKED(M)                                                                                              \
+  do {                                                                                                                       \
+    if (rev)                                                                                                                 \
+      hipLaunchKernelGGL((flat_scan_i8_kernel<false, true, false, false, false, M>), dim3(grid), dim3(I8L<false>::kThreads), \
+                         I8L<false>::kLdsBytes, st, a);                                                                      \
+    else if (qres_on && env().i8_half && a.ld <= 2 * kRowBI8)                                                                \
+      hipLaunchKernelGGL((flat_scan_i8_kernel<false, false, true, true, false, M>), dim3(2 * grid),                          \
+                         dim3(I8L<true>::kThreads), I8L<true>::kLdsBytes, st, a);                                            \
+    else if (qres_on && a.ld <= 4 * kRowBI8)                                                                                 \
+      hipLaunchKernelGGL((flat_scan_i8_kernel<false, false, true, false, false, M>), dim3(grid), dim3(I8L<false>::kThreads), \
+                         I8L<false>::kLdsBytes, st, a);                                                                      \
+    else if ((a.ld / kRowBI8) % 2u == 0u)                                                                                    \
+      hipLaunchKernelGGL((flat_scan_i8_kernel<false, false, false, false, true, M>), dim3(grid), dim3(I8L<false>::kThreads), \
+                         I8L<false>::kLdsBytes, st, a);                                                                      \
+    else                                                                                                                     \
+      hipLaunchKernelGGL((flat_scan_i8_kernel<false, false, false, false, false, M>), dim3(grid),                            \
+                         dim3(I8L<false>::kThreads), I8L<false>::kLdsBytes, st, a);                                          \
+  } while (0)
+    if (a.allow_per_query) EHX_LAUNCH_I8_MASKED(kMaskPerQuery);
+    else EHX_LAUNCH_I8_MASKED(kMaskOne);
+#undef EHX_LAUNCH_I8_MASKED
   } else if (a.dump) {
     if (rev) EHX_LAUNCH_I8(true, true);
     else EHX_LAUNCH_I8(true, false);

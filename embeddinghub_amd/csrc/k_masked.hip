@@ -13,20 +13,6 @@
 
 namespace ehx {
 
-namespace {
-
-// word w of the bitmap cut at n_bits (bits of the last word beyond n_bits and words beyond it read as 0)
-__device__ __forceinline__ uint32_t mask_word(const uint32_t* __restrict__ mask, uint64_t w, uint64_t n_bits) {
-  const uint64_t lo = w << 5;
-  if (lo >= n_bits) return 0u;
-  uint32_t v = mask[w];
-  const uint64_t left = n_bits - lo;
-  if (left < 32) v &= (1u << (uint32_t)left) - 1u;
-  return v;
-}
-
-}  // namespace
-
 // one lane per tile
 __global__ __launch_bounds__(256) void masked_count_kernel(const uint32_t* __restrict__ mask, uint64_t n_bits, uint32_t n_tiles,
                                                            uint32_t* __restrict__ cum) {

@@ -1,0 +1,102 @@
+// Exact kNN under a table of row bitmaps, one per query (ehx_knn_masked_multi*): k_masked.hip's compaction for every bitmap
+// of the table in one set of launches, the mask a grid dimension.
+//   maskedq_count_kernel    allowed rows of every 256-row tile of every mask
+//   maskedq_prefix_kernel   their exclusive prefix per mask, cum[m][0 .. n_tiles] (cum[m][n_tiles] = mask m's allowed rows)
+//   maskedq_fill_kernel     the ascending lists of allowed row ids, mask m's at list + off[m] (the host places them back to
+//                           back from the counts it read)
+//   maskedq_sample_kernel   every mask's sample: every ceil(allowed / 256)-th allowed id by rank
+// The bit test itself, per query, is the int8 scan's (i8_flush_staging, kMaskPerQuery, k_flati8.hip); the first radius is
+// k_masked.hip's masked_radius_kernel over the list scan's answer on the sample of each query's own mask.
+#include "ehx_kernels.h"
+
+namespace ehx {
+
+// one lane per tile, blockIdx.y = mask
+__global__ __launch_bounds__(256) void maskedq_count_kernel(const uint32_t* __restrict__ maps, uint64_t words, uint64_t n_bits,
+                                                            uint32_t n_tiles, uint32_t* __restrict__ cum) {
+  const uint32_t t = blockIdx.x * 256u + threadIdx.x, m = blockIdx.y;
+  if (t >= n_tiles) return;
+  const uint32_t* mask = maps + (size_t)m * words;
+  uint32_t c = 0;
+  for (uint32_t w = 0; w < 8; ++w) c += (uint32_t)__builtin_popcount(mask_word(mask, (uint64_t)t * 8u + w, n_bits));
+  cum[(size_t)m * (n_tiles + 1u) + t] = c;
+}
+
+// ONE workgroup per mask: masked_prefix_kernel's scan (blocks of 1024 tiles, a running carry between them)
+__global__ __launch_bounds__(1024) void maskedq_prefix_kernel(uint32_t* __restrict__ cum_all, uint32_t n_tiles) {
+  __shared__ uint32_t wave_sum[16];
+  __shared__ uint32_t carry_s;
+  uint32_t* cum = cum_all + (size_t)blockIdx.x * (n_tiles + 1u);
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
+  if (tid == 0) carry_s = 0;
+  __syncthreads();
+  for (uint32_t t0 = 0; t0 < n_tiles; t0 += 1024u) {
+    const uint32_t t = t0 + tid;
+    const uint32_t c = t < n_tiles ? cum[t] : 0u;
+    uint32_t incl = c;   // inclusive scan across the wave
+    for (int d = 1; d < 64; d <<= 1) {
+      const uint32_t o = (uint32_t)__shfl_up((int)incl, d, 64);
+      if ((int)lane >= d) incl += o;
+    }
+    if (lane == 63u) wave_sum[w] = incl;
+    __syncthreads();
+    uint32_t before = carry_s;
+    for (uint32_t i = 0; i < w; ++i) before += wave_sum[i];
+    if (t < n_tiles) cum[t] = before + incl - c;
+    __syncthreads();
+    if (tid == 1023u) carry_s = before + incl;
+    __syncthreads();
+  }
+  if (tid == 0) cum[n_tiles] = carry_s;
+}
+
+// one workgroup per (tile, mask), one lane per row: list[off[mask] + cum[mask][tile] + rank inside the tile] = row id
+__global__ __launch_bounds__(256) void maskedq_fill_kernel(const uint32_t* __restrict__ maps, uint64_t words, uint64_t n_bits,
+                                                           uint32_t n_tiles, const uint32_t* __restrict__ cum,
+                                                           const MaskedqOffsets off, uint64_t* __restrict__ list) {
+  const uint32_t tile = blockIdx.x, m = blockIdx.y, tid = threadIdx.x;
+  const uint32_t* mask = maps + (size_t)m * words;
+  const uint32_t wi = tid >> 5, bit = tid & 31u;
+  uint32_t before = 0, mine = 0;
+  for (uint32_t w = 0; w < 8; ++w) {   // (the tile's 8 words: 32 bytes, the same for every lane)
+    const uint32_t v = mask_word(mask, (uint64_t)tile * 8u + w, n_bits);
+    if (w < wi) before += (uint32_t)__builtin_popcount(v);
+    if (w == wi) mine = v;
+  }
+  if (!((mine >> bit) & 1u)) return;
+  const uint32_t rank = before + (uint32_t)__builtin_popcount(mine & ((1u << bit) - 1u));
+  list[off.off[m] + cum[(size_t)m * (n_tiles + 1u) + tile] + rank] = (uint64_t)tile * 256u + tid;
+}
+
+// one workgroup per mask: sample[256 m + i] = mask m's list[i * stride] while i * stride < allowed, stride = ceil(allowed / 256)
+__global__ __launch_bounds__(256) void maskedq_sample_kernel(const uint64_t* __restrict__ list, const MaskedqOffsets off,
+                                                             const uint32_t* __restrict__ cum, uint32_t n_tiles,
+                                                             uint64_t* __restrict__ sample) {
+  const uint32_t m = blockIdx.x;
+  const uint64_t n_allowed = cum[(size_t)m * (n_tiles + 1u) + n_tiles];
+  const uint64_t stride = (n_allowed + 255u) / 256u, i = threadIdx.x;
+  if (i * stride < n_allowed) sample[(size_t)m * 256u + i] = list[off.off[m] + i * stride];
+}
+
+hipError_t launch_maskedq_count(const uint32_t* maps, uint32_t n_masks, uint64_t n_bits, uint32_t n_tiles, uint32_t* cum,
+                                hipStream_t st) {
+  if (n_tiles == 0 || n_masks == 0) return hipSuccess;
+  if (n_masks > kMaskedqMaxMasks) return hipErrorInvalidValue;
+  const uint64_t words = (n_bits + 31) / 32;
+  hipLaunchKernelGGL(maskedq_count_kernel, dim3((n_tiles + 255u) / 256u, n_masks), dim3(256), 0, st, maps, words, n_bits, n_tiles,
+                     cum);
+  hipLaunchKernelGGL(maskedq_prefix_kernel, dim3(n_masks), dim3(1024), 0, st, cum, n_tiles);
+  return hipGetLastError();
+}
+
+hipError_t launch_maskedq_fill(const uint32_t* maps, uint32_t n_masks, uint64_t n_bits, uint32_t n_tiles, const uint32_t* cum,
+                               const MaskedqOffsets& off, uint64_t* list, uint64_t* sample, hipStream_t st) {
+  if (n_tiles == 0 || n_masks == 0) return hipSuccess;
+  if (n_masks > kMaskedqMaxMasks) return hipErrorInvalidValue;
+  const uint64_t words = (n_bits + 31) / 32;
+  hipLaunchKernelGGL(maskedq_fill_kernel, dim3(n_tiles, n_masks), dim3(256), 0, st, maps, words, n_bits, n_tiles, cum, off, list);
+  hipLaunchKernelGGL(maskedq_sample_kernel, dim3(n_masks), dim3(256), 0, st, list, off, cum, n_tiles, sample);
+  return hipGetLastError();
+}
+
+}  // namespace ehx

@@ -407,6 +407,39 @@ class Space:
         check(self._L.ehx_knn_masked_device(self._h, C.c_void_p(stream or 0), nq, _ptr(d_queries), k, _ptr(d_mask), int(n_bits),
                                             _ptr(d_ids), _ptr(d_dist), _ptr(d_count)))
 
+    # ---- kNN under a table of row bitmaps, one per query (a micro-batch of requests with different filters) ----
+    def knn_masked_multi(self, queries, k, allows, mask_of, n_bits=None):
+        """knn_masked with a bitmap per query (ehx_knn_masked_multi): query i is searched under allows[mask_of[i]], and row i
+        of the answer is knn_masked's for that query and bitmap.  allows: a 2-d bool array [n_masks, rows], or packed uint32
+        words [n_masks, words] with n_bits; at most 64 bitmaps.  mask_of: [nq] indices into allows.
+        -> ids [nq,k] u64, dist [nq,k] f32, count [nq] u32."""
+        q, pq = _f32(queries)
+        q = q.reshape(-1, self.dims)
+        nq = q.shape[0]
+        words, n_masks, n_bits = marshal_mask_table(allows, n_bits)
+        of = np.ascontiguousarray(np.asarray(mask_of).reshape(-1), dtype=np.uint32)
+        if of.shape[0] != nq:
+            raise ValueError("expected %d mask_of entries, got %d" % (nq, of.shape[0]))
+        (ids, dist, cnt), out = _results(nq, k)
+        check(self._L.ehx_knn_masked_multi(self._h, nq, pq, k, words.ctypes.data_as(C.POINTER(C.c_uint32)) if n_bits else None,
+                                           n_masks, n_bits, of.ctypes.data_as(C.POINTER(C.c_uint32)), *out))
+        return ids[:, :k], dist[:, :k], cnt
+
+    def knn_masked_multi_device(self, d_queries, k, d_masks, n_masks, n_bits, d_mask_of, d_ids, d_dist, d_count, stream=None):
+        """knn_masked_multi without anything leaving the device: torch CUDA tensors — d_queries [nq, dims] f32, d_masks
+        [n_masks, ceil(n_bits / 32)] packed u32 words (int32 storage), d_mask_of [nq] u32 (int32 storage), outputs as
+        knn_device's."""
+        nq = d_queries.shape[0] if hasattr(d_queries, "shape") else None
+        if nq is None:
+            raise ValueError("pass torch tensors (queries [nq, dims], mask words, mask_of)")
+        if hasattr(d_masks, "numel") and d_masks.numel() < int(n_masks) * ((int(n_bits) + 31) // 32):
+            raise ValueError("%d mask words hold fewer than %d bitmaps of n_bits = %d bits" % (d_masks.numel(), n_masks, n_bits))
+        if hasattr(d_mask_of, "numel") and d_mask_of.numel() < nq:
+            raise ValueError("%d mask_of entries for %d queries" % (d_mask_of.numel(), nq))
+        check(self._L.ehx_knn_masked_multi_device(self._h, C.c_void_p(stream or 0), nq, _ptr(d_queries), k, _ptr(d_masks),
+                                                  int(n_masks), int(n_bits), _ptr(d_mask_of), _ptr(d_ids), _ptr(d_dist),
+                                                  _ptr(d_count)))
+
     # ---- kNN under a row bitmap on the graph path ----
     def graph_knn_masked(self, queries, k, allow, n_bits=None, route=_lib.WALK_AUTO):
         """The k nearest ALLOWED rows the graph walk finds (ehx_graph_knn_masked): approximate when walked, possibly fewer
@@ -547,6 +580,34 @@ def marshal_mask(allow, n_bits=None):
     if n < 0 or n > a.shape[0] * 32:
         raise ValueError("n_bits = %d outside %d mask words" % (n, a.shape[0]))
     return np.ascontiguousarray(a), n
+
+
+def marshal_mask_table(allows, n_bits=None):
+    """The bitmaps of knn_masked_multi -> (packed u32 words [n_masks, ceil(n_bits / 32)], C-contiguous; n_masks; n_bits).
+    allows is a 2-d bool array [n_masks, rows] (every row packed as marshal_mask packs it, n_bits = rows unless a smaller
+    one is given), or 2-d uint32 words [n_masks, words] already packed, passed through, with n_bits."""
+    a = np.asarray(allows)
+    if a.ndim != 2:
+        raise ValueError("expected a 2-d table of masks, got shape %s" % (a.shape,))
+    if a.dtype == np.bool_:
+        n = a.shape[1] if n_bits is None else int(n_bits)
+        if n < 0 or n > a.shape[1]:
+            raise ValueError("n_bits = %d outside bool masks of %d entries" % (n, a.shape[1]))
+        n_words = (n + 31) // 32
+        bits = np.zeros((a.shape[0], n_words * 32), dtype=np.uint8)
+        bits[:, :n] = a[:, :n]
+        packed = np.packbits(bits.reshape(a.shape[0], n_words * 4, 8), axis=2, bitorder="little")
+        words = np.ascontiguousarray(packed.reshape(a.shape[0], n_words * 4)).view("<u4").reshape(a.shape[0], n_words)
+        return np.ascontiguousarray(words, dtype=np.uint32), a.shape[0], n
+    if a.dtype != np.uint32:
+        raise ValueError("a mask is a bool array or packed uint32 words, got dtype %s" % a.dtype)
+    if n_bits is None:
+        raise ValueError("packed mask words need n_bits")
+    n = int(n_bits)
+    if n < 0 or n > a.shape[1] * 32:
+        raise ValueError("n_bits = %d outside %d mask words" % (n, a.shape[1]))
+    # (the table is dense at ceil(n_bits / 32) words per bitmap: words beyond them are cut)
+    return np.ascontiguousarray(a[:, :(n + 31) // 32]), a.shape[0], n
 
 
 def marshal_id_lists(cand_ids, cand_off=None):

@@ -299,6 +299,12 @@ int ehx_knn_among_keys(ehx_space* s, size_t n_queries, const float* queries, uin
  * mask has ceil(n_bits / 32) words. */
 int ehx_knn_masked(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, const uint32_t* mask, uint64_t n_bits,
                    uint64_t* out_ids, float* out_dist, uint32_t* out_count);
+/* Exact kNN under a table of row bitmaps, one per query, from host pointers: ehx_knn_masked_multi_device (below: the
+ * contract) plus the H2D / D2H copies.  masks has n_masks * ceil(n_bits / 32) words, mask_of n_queries entries; mask_of is
+ * checked here, before anything is enqueued. */
+int ehx_knn_masked_multi(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, const uint32_t* masks,
+                         uint32_t n_masks, uint64_t n_bits, const uint32_t* mask_of, uint64_t* out_ids, float* out_dist,
+                         uint32_t* out_count);
 /* Graph search under a row bitmap from host pointers: ehx_graph_knn_masked_device (below: the contract) plus the H2D / D2H
  * copies.  mask has ceil(n_bits / 32) words. */
 int ehx_graph_knn_masked(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, const uint32_t* mask,
@@ -379,6 +385,34 @@ int ehx_knn_among_device(ehx_space* s, void* stream, size_t n_queries, const flo
 int ehx_knn_masked_device(ehx_space* s, void* stream, size_t n_queries, const float* d_queries, uint32_t k,
                           const uint32_t* d_mask, uint64_t n_bits, uint64_t* d_out_ids, float* d_out_dist,
                           uint32_t* d_out_count);
+/* Exact kNN under a TABLE of row bitmaps, one per query: what a serving process needs when one micro-batch carries requests
+ * of several tenants, ACL groups or categories — one call and one set of scan passes instead of one ehx_knn_masked_device
+ * call per filter.  d_masks holds n_masks bitmaps, dense, [n_masks][ceil(n_bits / 32)] words, each laid out as
+ * ehx_knn_masked_device's; query i is searched under bitmap d_mask_of[i].  Row i of the answer is, byte for byte, what
+ * ehx_knn_masked_device returns for query i alone under that bitmap: the same definition of an allowed row with ONE
+ * acquire-load snapshot of the row count for the whole call, (canonical distance, id) order, the NaN rule, +-Inf, cosine
+ * normalisation, F16 rows as stored, the sentinels beyond d_out_count[i]; a bitmap with no bit set gives count 0 for ITS
+ * queries only.  With n_masks == 1 (d_mask_of all zero) the call equals ehx_knn_masked_device byte for byte.  Every space
+ * kind ehx_knn_masked serves is served; a graph space answers from its stored rows.
+ * Errors as ehx_knn_masked_device, and: n_masks == 0 with n_queries > 0, a NULL d_mask_of, an entry of d_mask_of at or above
+ * n_masks: EHX_EINVAL, the outputs unwritten (the device form reads d_mask_of back together with the tiles' allowed counts:
+ * the one wait ehx_knn_masked_device has too); n_masks > 64: EHX_EUNSUPPORTED; n_queries == 0: EHX_OK.  A NULL space is
+ * refused (EHX_EINVAL) before the device is looked for.
+ * The limit of 64 bitmaps is a CHOICE, not a measured bound and not a knob: the offsets of the masks' lists travel as one
+ * kernel argument (512 bytes), a call stages n_masks * rows / 8 bytes of bitmaps (8 MB at 64 x 1 M rows), and 64 covers a
+ * micro-batch of 1024 requests at 16 per filter, below which the scan's query tiles stop being shared.
+ * Served as ehx_knn_masked_device serves it, query by query through its own bitmap (exact route: k > 48, spaces the int8
+ * filter does not serve first, bitmaps of at most max(1024, rows / 128) allowed rows; else the scan route), with every
+ * bitmap compacted in one set of launches, ONE plan of scan passes for the batch and the bit of the hit's own query's
+ * bitmap tested where the scan collects its hits.  The plan is the batch's: a pass ends where the bitmap that has shown most
+ * allowed rows reaches its quota (4096, 65 536, ...).  A bitmap whose rows CLUSTER late in the id space, behind rows the
+ * other bitmaps of the batch allow, therefore meets its rows in one late pass under its sample's radius; when more than
+ * about 4096 * 256 / k of them lie there (105 000 rows at k = 10, 22 000 at k = 48) its queries' pools overflow and they
+ * are answered by the exact scan of the bitmap's list — the same answer, at that scan's cost (ehx_knn_among_device's
+ * regime).  Bitmaps spread over the ids do not meet this.  DESIGN.md §e.16. */
+int ehx_knn_masked_multi_device(ehx_space* s, void* stream, size_t n_queries, const float* d_queries, uint32_t k,
+                                const uint32_t* d_masks, uint32_t n_masks, uint64_t n_bits, const uint32_t* d_mask_of,
+                                uint64_t* d_out_ids, float* d_out_dist, uint32_t* d_out_count);
 /* Filtered search on the graph path: the k nearest ALLOWED rows found by walking a graph space's HNSW graph under a row
  * bitmap (allowed as ehx_knn_masked_device defines it: r < n_bits, r below the call's ONE snapshot of the row count, bit
  * r & 31 of word r >> 5 of d_mask set).  The walk, in words (tests/filtered_walk_model.py states it as code, DESIGN.md
