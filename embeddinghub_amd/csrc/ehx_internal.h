@@ -490,29 +490,22 @@ struct ehx_space {
     HostStage host;              // host form: queries | radii, and ids | totals | distances | counts
   } range;
   std::atomic<uint64_t> range_ctr[4] = {};   // test hook: queries answered by the int8 path, by the exact path, pool overflows, truncated
-  // exact kNN under a row bitmap (ehx_masked.cpp; scratch_mu): the bitmap's compaction — allowed rows before every
-  // 256-row tile, the ascending list of allowed ids, the sample of it — the scan route's buffers (RadiusKnnBufs; flagged
-  // queries are answered by the exact kNN among the whole list), and a host call's staged bitmap, queries and results.
+  // exact kNN under row bitmaps, one for the call or a table with one per query (ehx_masked.cpp; scratch_mu): the bitmaps'
+  // compaction — allowed rows before every 256-row tile, the ascending lists of allowed ids, a sample of each — the scan
+  // route's buffers (RadiusKnnBufs; flagged queries are answered by the exact kNN among their mask's whole list), and a
+  // host call's staged queries and results.
   struct Masked {
-    DevBuf<uint32_t> dCum;       // [n_tiles + 1]
-    DevBuf<uint64_t> dList;      // [rows the bitmap covers]
-    DevBuf<uint64_t> dSample;    // [256]
-    RadiusKnnBufs scan;
-    DevBuf<uint32_t> dMaskRaw;   // host form: the bitmap
-    HostStage host;              // host form: queries, and ids | distances | counts
-    DevBuf<unsigned long long> dCapHits;   // [1] the graph walk under a bitmap: queries whose list reached its cap
-  } masked;
-  // exact kNN under a table of bitmaps, one per query (ehx_maskedq.cpp; scratch_mu)
-  struct MaskedMulti {
     DevBuf<uint32_t> dBlock;     // [kSideChunk] word offset of the bitmap of every query of a device batch | the bitmaps,
-                                 // [n_masks][words below the row count]: ONE block, the int8 scan's flush reads both
+                                 // [n_masks][words below the row count]: ONE block, the int8 scan's flush reads both.
+                                 // Host bitmaps and tables are staged here; ONE device bitmap is used where it lies
     DevBuf<uint32_t> dCum;       // [n_masks][n_tiles + 1]
     DevBuf<uint64_t> dList;      // the masks' ascending lists of allowed ids, back to back
     DevBuf<uint64_t> dSample;    // [n_masks][256]
     RadiusKnnBufs scan;          // (its sub-batch: the flagged queries of one mask)
     SubsetBufs group;            // the call's queries ordered by route and mask
     HostStage host;              // host form: queries, and ids | distances | counts
-  } maskedq;
+    DevBuf<unsigned long long> dCapHits;   // [1] the graph walk under a bitmap: queries whose list reached its cap
+  } masked;
   // test hook: queries answered on the scan route, on the exact route, queries that overflowed, scan passes launched, calls
   // (ehx_knn_masked* and ehx_knn_masked_multi* both count here)
   std::atomic<uint64_t> masked_ctr[5] = {};
@@ -847,17 +840,6 @@ int largek_locked(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, const
 int among_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, const uint64_t* d_ids,
                  const uint64_t* d_off, size_t n_cand, size_t max_list, uint64_t* d_out_ids, float* d_out_dist,
                  uint32_t* d_out_count, bool count_queries = true);
-
-// ---- ehx_masked.cpp (what ehx_maskedq.cpp, a bitmap per query, shares with it) ----
-constexpr uint32_t kMaskedScanMaxK = 48;    // the scan route carries <= k keys per query between passes: the certified engines' k
-constexpr uint64_t kMaskedSample = 256;     // allowed rows in the sample, at most
-constexpr uint64_t kMaskedPassGrowth = 16;  // pass j ends where kMaskedSample * 16^j allowed rows have been seen
-constexpr const char* kMaskedWhy = "filtered search over shards is not built yet";
-uint64_t masked_exact_cut(uint64_t n_pub);  // at most this many allowed rows: the exact route
-int masked_check(const ehx_space* s, size_t nq, uint32_t k, const void* q, const void* mask, uint64_t n_bits, const void* o_ids,
-                 const void* o_dist, const void* o_cnt);
-// tile ranges of the scan passes from cum[t] = allowed rows in tiles [0, t), non-decreasing, cum[n_tiles] their number
-std::vector<TileRange> masked_passes(const std::vector<uint32_t>& cum, uint32_t n_tiles);
 
 // ---- ehx_write.cpp ----
 int sync_stream(ehx_space* s, hipStream_t st);

@@ -241,9 +241,9 @@ struct ScanArgsI8 {
   uint32_t sync_tol = 0;     // > 0: a workgroup does not run more than this many TILES ahead of its slowest sibling
   uint32_t skew = 0;         // half-tile workgroups: the second-resident wave of a SIMD starts skew x 64 cycles late
   uint32_t group_b = 0;      // 1: the alarm level of a lane group uses the group's B margin (L2^2: B_r = |x_r|^2 varies)
-  const uint32_t* allow = nullptr;  // optional row bitmap (masked kNN, k_masked.hip): bit id & 31 of word id >> 5; a hit whose
+  const uint32_t* allow = nullptr;  // optional row bitmap (masked kNN, ehx_masked.cpp): bit id & 31 of word id >> 5; a hit whose
   uint32_t allow_bits = 0;          // row id is >= allow_bits or whose bit is clear is dropped before it takes a pool slot
-  uint32_t allow_per_query = 0;     // 1: a bitmap per query (ehx_knn_masked_multi*, k_maskedq.hip) — allow is ONE block,
+  uint32_t allow_per_query = 0;     // 1: a bitmap per query (ehx_knn_masked_multi*, several masks) — allow is ONE block,
                                     // [q_tiles * 256] word offsets from its start (query q: allow[q]) | the bitmaps
 };
 // Stage-blocked layout of the int8 scan copy / query tiles: tiles of 256 rows, stages of 64 columns (bytes); one
@@ -511,13 +511,24 @@ uint32_t range_rerank_max_ld();   // longest row stride (floats): the pool and t
 hipError_t launch_range_rerank(const RangeRerankArgs& a, hipStream_t st);
 hipError_t launch_range_iota(uint64_t* out, uint64_t n, hipStream_t st);   // out[i] = i
 
-// exact kNN under a row bitmap (k_masked.hip).  Compaction of the bitmap's first n_bits bits (n_tiles = ceil(n_bits / 256)
-// tiles of 8 words; words and bits beyond n_bits are not read): cum[0 .. n_tiles] = allowed rows before every tile, the
-// last entry their number; list = the allowed row ids, ascending
-hipError_t launch_masked_compact(const uint32_t* mask, uint64_t n_bits, uint32_t n_tiles, uint32_t* cum, uint64_t* list,
-                                 hipStream_t st);
-// sample[i] = list[i * stride] while i * stride < n_allowed (at most 256 entries)
-hipError_t launch_masked_sample(const uint64_t* list, uint64_t n_allowed, uint64_t stride, uint64_t* sample, hipStream_t st);
+// exact kNN under row bitmaps (k_masked.hip): one bitmap (ehx_knn_masked*, the graph walk's exact route) or a table, one per
+// query (ehx_knn_masked_multi*).  Compaction of the first n_bits bits of n_masks <= kMaskedMaxMasks bitmaps at once, the
+// mask a grid dimension (n_tiles = ceil(n_bits / 256) tiles of 8 words; words and bits beyond n_bits are not read).  maps:
+// bitmap m starts at maps + m * stride words, stride >= ceil(n_bits / 32); ONE bitmap is used where it lies, the stride
+// never applied.  cum: [n_masks][n_tiles + 1], allowed rows before every tile, the last entry their number.  Counts and
+// prefixes first (the host reads them back and places the lists), then the ascending lists of allowed row ids — mask m's at
+// list + off[m].  launch_masked_samples, for the scan route: every mask's sample of at most 256 ids by rank, stride
+// ceil(allowed / 256), at sample + 256 m.
+constexpr uint32_t kMaskedMaxMasks = 64;
+struct MaskedOffsets {
+  uint64_t off[kMaskedMaxMasks];
+};
+hipError_t launch_masked_count(const uint32_t* maps, uint64_t stride, uint32_t n_masks, uint64_t n_bits, uint32_t n_tiles,
+                               uint32_t* cum, hipStream_t st);
+hipError_t launch_masked_fill(const uint32_t* maps, uint64_t stride, uint32_t n_masks, uint64_t n_bits, uint32_t n_tiles,
+                              const uint32_t* cum, const MaskedOffsets& off, uint64_t* list, hipStream_t st);
+hipError_t launch_masked_samples(const uint64_t* list, const MaskedOffsets& off, const uint32_t* cum, uint32_t n_masks,
+                                 uint32_t n_tiles, uint64_t* sample, hipStream_t st);
 // radius[q] = dist[q][k - 1] when cnt[q] >= k (result lists [nq][k]), else +Inf
 hipError_t launch_masked_radius(const float* dist, const uint32_t* cnt, uint32_t nq, uint32_t k, float* radius, hipStream_t st);
 // word w of a bitmap cut at n_bits (bits of the last word beyond n_bits and words beyond it read as 0)
@@ -529,20 +540,6 @@ __device__ __forceinline__ uint32_t mask_word(const uint32_t* __restrict__ mask,
   if (left < 32) v &= (1u << (uint32_t)left) - 1u;
   return v;
 }
-
-// exact kNN under a TABLE of row bitmaps, one per query (ehx_knn_masked_multi*, k_maskedq.hip): the compaction above for
-// n_masks <= kMaskedqMaxMasks bitmaps at once, the mask a grid dimension.  maps: [n_masks][ceil(n_bits / 32)] words, dense;
-// cum: [n_masks][n_tiles + 1].  Counts and prefixes first (the host reads them back and places the lists), then the lists
-// — mask m's at list + off[m] — and every mask's sample of at most 256 ids by rank, stride ceil(allowed / 256), at
-// sample + 256 m.
-constexpr uint32_t kMaskedqMaxMasks = 64;
-struct MaskedqOffsets {
-  uint64_t off[kMaskedqMaxMasks];
-};
-hipError_t launch_maskedq_count(const uint32_t* maps, uint32_t n_masks, uint64_t n_bits, uint32_t n_tiles, uint32_t* cum,
-                                hipStream_t st);
-hipError_t launch_maskedq_fill(const uint32_t* maps, uint32_t n_masks, uint64_t n_bits, uint32_t n_tiles, const uint32_t* cum,
-                               const MaskedqOffsets& off, uint64_t* list, uint64_t* sample, hipStream_t st);
 
 // exact kNN on the int8 radius scan under a radius that falls (k_radius.hip): the bitmap search's scan route (k <= 48) and
 // the flat chain's route for EHX_MAX_K < k <= kLargeKMax

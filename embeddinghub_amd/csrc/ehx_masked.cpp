@@ -1,27 +1,49 @@
-// kNN under a row bitmap.  Exact: ehx_knn_masked (host pointers) and ehx_knn_masked_device; on the graph path:
-// ehx_graph_knn_masked* (the section at the end).  Row r is allowed iff r < n_bits,
-// r is below the call's ONE snapshot of the row count and bit r & 31 of word r >> 5 is set; the answer is ehx_knn_among's
-// with the ascending list of allowed rows, byte for byte (k_radius.hip's header has the argument).
-//   compaction   the bitmap -> allowed rows before every 256-row tile (read back once: the host plans the passes from
-//                them) and the ascending list of allowed ids
-//   exact route  among_locked over that list: spaces the range search's int8 path does not serve, k > 48, lists of at
-//                most max(1024, rows / 128) rows
+// kNN under row bitmaps.  Exact: ehx_knn_masked (host pointers) and ehx_knn_masked_device under ONE bitmap,
+// ehx_knn_masked_multi and ehx_knn_masked_multi_device under a TABLE of bitmaps, query i under bitmap mask_of[i]; on the
+// graph path: ehx_graph_knn_masked* (the section at the end).  Row r is allowed iff r < n_bits, r is below the call's ONE
+// snapshot of the row count and bit r & 31 of word r >> 5 is set; the answer is ehx_knn_among's with the ascending list of
+// allowed rows, byte for byte (k_radius.hip's header has the argument), and row i of a table's answer is the one-bitmap
+// answer for query i alone under its bitmap.  One bitmap is a table of one: ONE plan (masked_plan) and ONE answer over it
+// (masked_answer) serve every entry point, the graph walk's exact route included.
+//   compaction   every bitmap in one set of launches (k_masked.hip): allowed rows before every 256-row tile per mask, read
+//                back ONCE (the host plans the passes from them) together with mask_of (a table's device form), and the
+//                ascending lists, back to back (one mask: filled in front of that wait; several: behind it, placed by
+//                the counts); where a mask takes the scan route, a sample of <= 256 ids per mask
+//   routing      per query through its mask: the exact route for spaces the range search's int8 path does not serve,
+//                k > 48, and masks of at most max(1024, rows / 128) allowed rows; the scan route else
+//   grouping     the queries are ordered scan route first, then by mask (SubsetBufs: gathered, answered, scattered back;
+//                skipped when they come in that order, as one mask always does), so the queries of one mask are ONE range
+//                of the batch: the exact route and the first radius are one shared-list among_locked per mask over its range
+//   exact route  among_locked over the mask's list
 //   scan route   the falling-radius kNN (radius_knn, ehx_call.cpp; k_radius.hip's header has the kernels and the argument)
-//                with the bitmap in the int8 scan's flush: the first radius is the exact k-th distance of a sample of <= 256
-//                allowed rows, taken by the list scan (its tiles share the sample's rows between queries), the passes are cut
-//                by ALLOWED rows seen (4096, 65536, ...: sound wherever the bitmap's rows cluster), and the queries it
-//                hands on — pool overflow, or the bound does not serve them — take the exact route
+//                with the bitmap in the int8 scan's flush — the batch's one bitmap, or with several a bitmap per query
+//                (kMaskPerQuery, k_flati8.hip): ONE block, the word offset of every query's bitmap followed by the bitmaps.
+//                First radius: the exact k-th distance over the sample of the query's OWN mask, taken by the list scan (its
+//                tiles share the sample's rows between queries).  ONE pass plan, cut by ALLOWED rows seen (4096, 65536,
+//                ...: sound wherever the bitmap's rows cluster): pass j ends at the first tile where some scanned mask has
+//                seen 256 * 16^j allowed rows (the pointwise maximum of the scanned masks' counts), so no mask sees more
+//                allowed rows in a pass than it would alone.  The queries it hands on — pool overflow, or the bound does
+//                not serve them — take the exact route under their own mask.
+// n_masks <= kMaskedMaxMasks = 64: a choice (include/ehx.h says why), not a knob.
 // Entry scaffold and host staging are ehx_call.cpp's (search_shared / on_device, HostStage).
 #include "ehx_internal.h"
 
-// (the constants of the routes are ehx_internal.h's: ehx_maskedq.cpp routes every query of a table of bitmaps by them)
+namespace {
+
+constexpr uint32_t kMaskedScanMaxK = 48;    // the scan route carries <= k keys per query between passes: the certified engines' k
+constexpr uint64_t kMaskedSample = 256;     // allowed rows in the sample, at most
+constexpr uint64_t kMaskedPassGrowth = 16;  // pass j ends where kMaskedSample * 16^j allowed rows have been seen
+constexpr const char* kMaskedWhy = "filtered search over shards is not built yet";
+static_assert(kSideChunk % 256 == 0, "the offset table covers the padded query rows of one device batch");
+constexpr size_t kTabWords = kSideChunk;    // word offsets in front of the bitmaps of ehx_space::Masked::dBlock
+
 // At most this many allowed rows: the exact route.  max(1024, rows / 128), MEASURED (scripts/bench_masked.py, 1 M x 768
 // cosine, batch 1024, k = 10: the list scan costs what the scan route costs at 7 697 allowed rows, 0.77 % of the space;
 // profiles/masked_bench.jsonl).
-uint64_t ehx_impl::masked_exact_cut(uint64_t n_pub) { return std::max<uint64_t>(1024, n_pub / 128); }
+uint64_t masked_exact_cut(uint64_t n_pub) { return std::max<uint64_t>(1024, n_pub / 128); }
 
-int ehx_impl::masked_check(const ehx_space* s, size_t nq, uint32_t k, const void* q, const void* mask, uint64_t n_bits,
-                           const void* o_ids, const void* o_dist, const void* o_cnt) {
+int masked_check(const ehx_space* s, size_t nq, uint32_t k, const void* q, const void* mask, uint64_t n_bits,
+                 const void* o_ids, const void* o_dist, const void* o_cnt) {
   int rc = ehx_init(nullptr, 0);   // (no device: EHX_ENODEVICE, whatever else is wrong with the call)
   if (rc) return rc;
   if ((rc = check_batch_call(s, nq, k, "k", false, o_ids && o_dist && o_cnt && (!nq || q)))) return rc;
@@ -29,13 +51,30 @@ int ehx_impl::masked_check(const ehx_space* s, size_t nq, uint32_t k, const void
   return EHX_OK;
 }
 
+int masked_table_check(const ehx_space* s, size_t nq, uint32_t k, const void* q, const void* masks, uint32_t n_masks,
+                       uint64_t n_bits, const void* mask_of, const void* o_ids, const void* o_dist, const void* o_cnt) {
+  if (!s) return fail(EHX_EINVAL, "space is NULL");
+  if (int rc = masked_check(s, nq, k, q, masks, n_bits, o_ids, o_dist, o_cnt)) return rc;
+  if (nq == 0) return EHX_OK;
+  if (n_masks == 0) return fail(EHX_EINVAL, "n_masks is 0 with %zu queries", nq);
+  if (n_masks > kMaskedMaxMasks) return fail(EHX_EUNSUPPORTED, "n_masks=%u exceeds %u", n_masks, kMaskedMaxMasks);
+  if (!mask_of) return fail(EHX_EINVAL, "NULL mask_of");
+  return EHX_OK;
+}
+
+int check_mask_of(const uint32_t* mask_of, size_t nq, uint32_t n_masks) {
+  for (size_t i = 0; i < nq; ++i)
+    if (mask_of[i] >= n_masks) return fail(EHX_EINVAL, "mask_of[%zu] = %u is not below n_masks = %u", i, mask_of[i], n_masks);
+  return EHX_OK;
+}
+
 // tile ranges of the scan passes: pass j (j = 1, 2, ...; the sample is stage 0) ends at the first tile where the allowed
-// rows seen reach kMaskedSample * 16^j, the last pass takes the rest.  cum[t] = allowed rows in tiles [0, t).
-std::vector<TileRange> ehx_impl::masked_passes(const std::vector<uint32_t>& cum, uint32_t n_tiles) {
+// rows seen reach kMaskedSample * 16^j, the last pass takes the rest.  cum[t] = allowed rows in tiles [0, t), non-decreasing.
+std::vector<TileRange> masked_passes(const std::vector<uint32_t>& cum, uint32_t n_tiles) {
   std::vector<TileRange> out;
   uint32_t t0 = 0;
   for (uint64_t want = kMaskedSample * kMaskedPassGrowth; t0 < n_tiles; want *= kMaskedPassGrowth) {
-    // (cum is non-decreasing: the first t with cum[t] >= want)
+    // (the first t with cum[t] >= want)
     uint32_t t1 = (uint32_t)(std::lower_bound(cum.begin() + t0 + 1, cum.begin() + n_tiles + 1, want,
                                               [](uint32_t c, uint64_t w) { return (uint64_t)c < w; }) - cum.begin());
     if (t1 > n_tiles || cum[n_tiles] <= want) t1 = n_tiles;
@@ -45,113 +84,238 @@ std::vector<TileRange> ehx_impl::masked_passes(const std::vector<uint32_t>& cum,
   return out;
 }
 
-namespace {
-
-// The bitmap of one call, compacted: the call's ONE read of the row count, the rows the bitmap covers below it, the allowed
-// rows before every tile (read back) and, in masked.dList, the ascending list of allowed ids.
-struct MaskedList {
-  uint64_t n_pub = 0, n_eff = 0, n_allowed = 0;
-  uint32_t n_tiles = 0;
-  std::vector<uint32_t> cum;
+// Where a call's bitmaps come from: n_masks >= 1 bitmaps of `stride` words each, in host or device memory.
+struct MaskTable {
+  const uint32_t* p;
+  uint64_t stride;
+  uint32_t n_masks;
+  bool host;
 };
-int masked_compact_locked(ehx_space* s, hipStream_t st, const uint32_t* d_mask, uint64_t n_bits, MaskedList* m) {
+
+// The bitmaps of a call on the device, bitmap m at *d_maps + m * words (words: those of the n_eff rows below the row count):
+// ONE device bitmap where it lies; host words and every table dense in masked.dBlock behind the offset words.  (Host words
+// are pageable memory: the runtime stages them before the call returns.)
+int masked_maps(ehx_space* s, hipStream_t st, const MaskTable& tab, uint64_t n_eff, const uint32_t** d_maps) {
   int rc;
-  // the ONE read of the row count: the list names rows below it only, and every later stage sees at least this prefix
-  m->n_pub = s->n.load(std::memory_order_acquire);
-  m->n_eff = std::min<uint64_t>(n_bits, m->n_pub);   // (row ids are 32 bits wide: n_pub < 2^32)
-  m->n_tiles = (uint32_t)((m->n_eff + kTileRows16 - 1) / kTileRows16);
-  const uint32_t n_tiles = m->n_tiles;
-  if ((rc = s->masked.dCum.ensure((size_t)n_tiles + 1)) || (rc = s->masked.dList.ensure(std::max<uint64_t>(m->n_eff, 1))) ||
-      (rc = s->masked.dSample.ensure(kMaskedSample)))
-    return rc;
-  m->cum.assign((size_t)n_tiles + 1, 0u);
-  if (n_tiles) {
-    // (earlier calls' launches on other streams may still read the list and the sample)
-    if ((rc = wait_searches_in_flight(s, st))) return rc;
-    HIP_TRY(launch_masked_compact(d_mask, m->n_eff, n_tiles, s->masked.dCum.p, s->masked.dList.p, st));
-    HIP_TRY(hipMemcpyAsync(m->cum.data(), s->masked.dCum.p, m->cum.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-  }
-  m->n_allowed = m->cum[n_tiles];
+  const bool in_place = tab.n_masks == 1 && !tab.host;
+  const uint64_t words = (n_eff + 31) / 32;
+  if (kTabWords + (uint64_t)tab.n_masks * words > 0xFFFFFFFFull)
+    return fail(EHX_EUNSUPPORTED, "%u bitmaps of %llu rows exceed the 2^32 words of one table", tab.n_masks,
+                (unsigned long long)n_eff);
+  ehx_space::Masked& w = s->masked;
+  if (!in_place && (rc = w.dBlock.ensure(kTabWords + std::max<size_t>((size_t)tab.n_masks * words, 1)))) return rc;
+  // (earlier calls' launches on other streams may still read the block, the lists and the samples)
+  if ((rc = wait_searches_in_flight(s, st))) return rc;
+  *d_maps = in_place ? tab.p : w.dBlock.p + kTabWords;
+  for (uint32_t m = 0; !in_place && words && m < tab.n_masks; ++m)
+    HIP_TRY(hipMemcpyAsync(w.dBlock.p + kTabWords + (size_t)m * words, tab.p + (size_t)m * tab.stride, words * sizeof(uint32_t),
+                           tab.host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
   return EHX_OK;
 }
 
-// the exact answer over a compacted bitmap: the scan route where it serves, else the list scan
-int masked_answer_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, const uint32_t* d_mask,
-                         const MaskedList& m, const ResultBlock& out) {
+// The bitmaps of one call, compacted: the call's ONE read of the row count, the rows the bitmaps cover below it, per mask the
+// allowed rows before every tile (read back), their number and where its ascending list of allowed ids starts in
+// masked.dList, and which mask every query is searched under.
+struct MaskedPlan {
+  uint64_t n_pub = 0, n_eff = 0, words = 0;   // words: of one bitmap below the row count, and the stride between two
+  uint32_t n_tiles = 0, n_masks = 0;
+  const uint32_t* d_maps = nullptr;           // where the bitmaps live on the device (masked_maps)
+  std::vector<uint32_t> cum;                  // [n_masks][n_tiles + 1]
+  std::vector<uint64_t> n_allowed;            // [n_masks]
+  MaskedOffsets off = {};                     // list of mask m: masked.dList.p + off.off[m]
+  const uint32_t* mask_of = nullptr;          // [queries], host memory, checked; nullptr: every query is mask 0
+  std::vector<uint32_t> mask_of_read;         // ... of a table's device form
+  const uint32_t* cum_of(uint32_t m) const { return cum.data() + (size_t)m * (n_tiles + 1); }
+};
+
+// an unsharded space, locked shared, scratch_mu held, its device current; everything is enqueued on `st`.  mask_of: in host
+// memory and checked; or d_mask_of (a table's device form): read back with the allowed counts — the ONE wait of the
+// compaction — and checked then, the outputs unwritten; or neither: every query is mask 0 and nothing is read back for it.
+int masked_plan(ehx_space* s, hipStream_t st, const MaskTable& tab, uint64_t n_bits, size_t nq, const uint32_t* mask_of,
+                const uint32_t* d_mask_of, MaskedPlan* p) {
   int rc;
-  const uint64_t n_pub = m.n_pub, n_eff = m.n_eff, n_allowed = m.n_allowed;
-  const uint32_t n_tiles = m.n_tiles;
-  const std::vector<uint32_t>& cum = m.cum;
-  const bool scan = n_allowed > masked_exact_cut(n_pub) && k <= kMaskedScanMaxK && i8_serves_radius(s, n_pub);
-  if (!scan) {
-    s->masked_ctr[1] += nq;
-    return among_locked(s, st, nq, d_queries, k, s->masked.dList.p, nullptr, n_allowed, 0, out.ids, out.dist, out.cnt);
-  }
-  const uint64_t stride = (n_allowed + kMaskedSample - 1) / kMaskedSample;
-  RadiusKnn c;
-  c.passes = masked_passes(cum, n_tiles);
-  c.allow = d_mask;
-  c.allow_bits = (uint32_t)n_eff;
-  c.out = out;
-  // stage 0: the exact k nearest of the sample, by the list scan, into the caller's arrays (every query's row is written
-  // again, by the last pass or by the exact route; its queries are not counted there: the verdict counts every query once);
-  // their k-th distance is the first radius, +Inf while the sample gives fewer than k
-  const uint64_t n_sample = (n_allowed + stride - 1) / stride;
-  c.first_radius = [&](size_t m, const float* q, const ResultBlock& o, float* d_radius) -> int {
-    if (int r = among_locked(s, st, m, q, k, s->masked.dSample.p, nullptr, n_sample, 0, o.ids, o.dist, o.cnt, false)) return r;
-    HIP_TRY(launch_masked_radius(o.dist, o.cnt, (uint32_t)m, k, d_radius, st));
+  ehx_space::Masked& w = s->masked;
+  // the ONE read of the row count: the lists name rows below it only, and every later stage sees at least this prefix
+  p->n_pub = s->n.load(std::memory_order_acquire);
+  p->n_eff = std::min<uint64_t>(n_bits, p->n_pub);   // (row ids are 32 bits wide: n_pub < 2^32)
+  p->words = (p->n_eff + 31) / 32;
+  p->n_tiles = (uint32_t)((p->n_eff + kTileRows16 - 1) / kTileRows16);
+  p->n_masks = tab.n_masks;
+  p->mask_of = mask_of;
+  const uint32_t n_masks = tab.n_masks, n_tiles = p->n_tiles;
+  if ((rc = masked_maps(s, st, tab, p->n_eff, &p->d_maps))) return rc;
+  if ((rc = w.dCum.ensure((size_t)n_masks * (n_tiles + 1)))) return rc;
+  p->cum.assign((size_t)n_masks * (n_tiles + 1), 0u);
+  // the lists (list_rows: what they hold together, at most), behind the counts
+  auto fill = [&](uint64_t list_rows) -> int {
+    if (int r = w.dList.ensure(std::max<uint64_t>(list_rows, 1))) return r;
+    HIP_TRY(launch_masked_fill(p->d_maps, p->words, n_masks, p->n_eff, n_tiles, w.dCum.p, p->off, w.dList.p, st));
     return EHX_OK;
   };
-  c.exact = [&](size_t n, const float* sq, uint64_t* ids, float* dist, uint32_t* cnt) {
-    return among_locked(s, st, n, sq, k, s->masked.dList.p, nullptr, n_allowed, 0, ids, dist, cnt);
-  };
-  HIP_TRY(launch_masked_sample(s->masked.dList.p, n_allowed, stride, s->masked.dSample.p, st));
-  RadiusKnnTally t;
-  rc = radius_knn(s, st, s->masked.scan, n_pub, d_queries, c, &t);
-  s->n_queries += t.queries - t.handed;   // (among_locked counts the rest)
-  s->masked_ctr[0] += t.queries - t.handed;
-  s->masked_ctr[1] += t.handed;
-  s->masked_ctr[2] += t.overflowed;
-  s->masked_ctr[3] += t.batches * c.passes.size();
-  return rc;
+  // Several masks: the lists' offsets come from the counts, so they are filled behind the wait.  ONE mask: its list starts
+  // at 0 and holds at most n_eff ids — both known now — so it is filled in front of the wait, the order the one-bitmap call
+  // had before it was folded into this function.  HOISTED AFTER A MEASUREMENT (profiles/masked_unify_ab.jsonl, DESIGN §e.16
+  // "One masked path"; 1 M x 768 cosine, batch 1024, k = 10, the one-bitmap call on the exact route at density 0.005,
+  // median of three medians against the range of the library before the fold): count, wait, fill for every n_masks
+  // 1.3844 ms against 1.3772..1.3793; hoisted 1.3765 in 1.3688..1.3781 and, a session later, 1.3780 against
+  // 1.3699..1.3767.  Code the fold did not touch (the graph walk) missed its own range by as much in those sessions: the
+  // figures allow the parent's order, they do not prove it the faster one.
+  const bool fill_early = n_masks == 1;
+  if (n_tiles) {
+    HIP_TRY(launch_masked_count(p->d_maps, p->words, n_masks, p->n_eff, n_tiles, w.dCum.p, st));
+    if (fill_early && (rc = fill(p->n_eff))) return rc;
+    HIP_TRY(hipMemcpyAsync(p->cum.data(), w.dCum.p, p->cum.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  }
+  if (d_mask_of) {
+    p->mask_of_read.resize(nq);
+    HIP_TRY(hipMemcpyAsync(p->mask_of_read.data(), d_mask_of, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    p->mask_of = p->mask_of_read.data();
+  }
+  if (n_tiles || d_mask_of) HIP_TRY(hipStreamSynchronize(st));
+  if (d_mask_of && (rc = check_mask_of(p->mask_of, nq, n_masks))) return rc;
+  // where the lists start, back to back
+  p->n_allowed.resize(n_masks);
+  uint64_t total = 0;
+  for (uint32_t m = 0; m < n_masks; ++m) {
+    p->off.off[m] = total;
+    p->n_allowed[m] = p->cum_of(m)[n_tiles];
+    total += p->n_allowed[m];
+  }
+  return fill_early && n_tiles ? (int)EHX_OK : fill(total);   // (no tile: nothing is launched, the list is one spare entry)
 }
 
-// an unsharded space, locked shared, scratch_mu held, its device current; everything is enqueued on `st`
-int masked_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, const uint32_t* d_mask,
-                  uint64_t n_bits, const ResultBlock& out) {
+// the exact answer over a plan: per mask the scan route where it serves, else the list scan
+int masked_answer(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, const MaskedPlan& p,
+                  const ResultBlock& out) {
+  ehx_space::Masked& w = s->masked;
+  const uint32_t n_masks = p.n_masks, n_tiles = p.n_tiles;
+  const bool per_query = n_masks > 1;   // one mask: the batch's ONE bitmap in the flush, nothing grouped, no offsets
+  // routing, and the order the queries are answered in: the scan route's first, then by mask
+  const bool scan_serves = k <= kMaskedScanMaxK && i8_serves_radius(s, p.n_pub);
+  std::vector<char> scans(n_masks);
+  for (uint32_t m = 0; m < n_masks; ++m) scans[m] = scan_serves && p.n_allowed[m] > masked_exact_cut(p.n_pub);
+  auto place = [&](uint32_t i) {
+    const uint32_t m = p.mask_of ? p.mask_of[i] : 0u;
+    return (scans[m] ? 0u : kMaskedMaxMasks) + m;
+  };
+  std::vector<uint32_t> idx(nq), gm(nq);   // gm: the mask of every query in that order
+  for (size_t i = 0; i < nq; ++i) idx[i] = (uint32_t)i;
+  auto before = [&](uint32_t a, uint32_t b) { return place(a) < place(b); };
+  const bool in_order = std::is_sorted(idx.begin(), idx.end(), before);   // (one mask: always)
+  if (!in_order) std::stable_sort(idx.begin(), idx.end(), before);
+  size_t n_scan = 0;
+  for (size_t i = 0; i < nq; ++i) {
+    gm[i] = p.mask_of ? p.mask_of[idx[i]] : 0u;
+    n_scan += scans[gm[i]];
+  }
+  // [b, e): the next run of queries of one mask in [b, end)
+  auto run_end = [&](size_t b, size_t end) {
+    size_t e = b + 1;
+    while (e < end && gm[e] == gm[b]) ++e;
+    return e;
+  };
+  auto exact = [&](uint32_t m, size_t n, const float* q, uint64_t* ids, float* dist, uint32_t* cnt) {
+    return among_locked(s, st, n, q, k, w.dList.p + p.off.off[m], nullptr, p.n_allowed[m], 0, ids, dist, cnt);
+  };
+
+  auto answer = [&](size_t, const float* gq, uint64_t* ids, float* dist, uint32_t* cnt) -> int {
+    if (n_scan) {
+      // ONE pass plan: the allowed rows seen are, tile by tile, those of whichever scanned mask has seen most
+      std::vector<uint32_t> seen((size_t)n_tiles + 1, 0u);
+      for (size_t b = 0; b < n_scan; b = run_end(b, n_scan)) {
+        const uint32_t* c = p.cum_of(gm[b]);
+        for (size_t t = 0; t <= n_tiles; ++t) seen[t] = std::max(seen[t], c[t]);
+      }
+      RadiusKnn c;
+      c.passes = masked_passes(seen, n_tiles);
+      c.allow = per_query ? w.dBlock.p : p.d_maps;
+      c.allow_bits = (uint32_t)p.n_eff;
+      c.allow_per_query = per_query;
+      c.out = ResultBlock{ids, dist, cnt, nullptr, n_scan, k};
+      std::vector<uint32_t> offs(per_query ? kTabWords : 0);
+      // stage 0 of a device batch [q0, q0 + m): with several masks its queries' word offsets into the block; per mask the
+      // exact k nearest of the mask's sample by the list scan, into the batch's rows of the output (every query's row is
+      // written again, by the last pass or by the exact route; its queries are not counted there: the verdict counts every
+      // query once): their k-th distance is the first radius, +Inf while the sample gives fewer than k
+      c.first_radius = [&](size_t m, const float* q, const ResultBlock& o, float* d_radius) -> int {
+        const size_t q0 = (size_t)(q - gq) / s->dims;
+        if (per_query) {
+          for (size_t j = 0; j < kTabWords; ++j)   // (padding queries: any bitmap, they collect nothing)
+            offs[j] = (uint32_t)(kTabWords + (uint64_t)gm[q0 + std::min(j, m - 1)] * p.words);
+          HIP_TRY(hipMemcpyAsync(w.dBlock.p, offs.data(), kTabWords * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        }
+        for (size_t b = q0; b < q0 + m;) {
+          const size_t e = run_end(b, q0 + m), j = b - q0;
+          const uint64_t a = p.n_allowed[gm[b]], stride = (a + kMaskedSample - 1) / kMaskedSample;
+          if (int r = among_locked(s, st, e - b, q + j * s->dims, k, w.dSample.p + (size_t)gm[b] * kMaskedSample, nullptr,
+                                   (size_t)((a + stride - 1) / stride), 0, o.ids + j * k, o.dist + j * k, o.cnt + j, false))
+            return r;
+          b = e;
+        }
+        HIP_TRY(launch_masked_radius(o.dist, o.cnt, (uint32_t)m, k, d_radius, st));
+        return EHX_OK;
+      };
+      // the flagged queries of a device batch, mask by mask
+      c.handed = [&](size_t q0, const std::vector<uint32_t>& todo, const float* q, const ResultBlock& o) -> int {
+        for (size_t b = 0; b < todo.size();) {
+          const uint32_t m = gm[q0 + todo[b]];
+          size_t e = b + 1;
+          while (e < todo.size() && gm[q0 + todo[e]] == m) ++e;
+          const std::vector<uint32_t> part(todo.begin() + b, todo.begin() + e);
+          if (int r = w.scan.sub.rerun(
+                  s, st, q, part, k,
+                  [&](size_t n, const float* sq, uint64_t* i2, float* d2, uint32_t* c2) { return exact(m, n, sq, i2, d2, c2); },
+                  o.ids, o.dist, o.cnt))
+            return r;
+          b = e;
+        }
+        return EHX_OK;
+      };
+      // (the masks' samples: stage 0 of the scan route alone, so the exact route does not pay for them)
+      if (int r = w.dSample.ensure((size_t)n_masks * kMaskedSample)) return r;
+      HIP_TRY(launch_masked_samples(w.dList.p, p.off, w.dCum.p, n_masks, n_tiles, w.dSample.p, st));
+      RadiusKnnTally t;
+      const int r = radius_knn(s, st, w.scan, p.n_pub, gq, c, &t);
+      s->n_queries += t.queries - t.handed;   // (among_locked counts the rest)
+      s->masked_ctr[0] += t.queries - t.handed;
+      s->masked_ctr[1] += t.handed;
+      s->masked_ctr[2] += t.overflowed;
+      s->masked_ctr[3] += t.batches * c.passes.size();
+      if (r) return r;
+    }
+    for (size_t b = n_scan; b < nq;) {   // the exact route: one shared list per mask
+      const size_t e = run_end(b, nq);
+      s->masked_ctr[1] += e - b;
+      if (int r = exact(gm[b], e - b, gq + b * s->dims, ids + b * k, dist + b * k, cnt + b)) return r;
+      b = e;
+    }
+    return EHX_OK;
+  };
+  if (in_order) return answer(nq, d_queries, out.ids, out.dist, out.cnt);
+  return w.group.rerun(s, st, d_queries, idx, k, answer, out.ids, out.dist, out.cnt);
+}
+
+// an unsharded space, locked shared, scratch_mu held, its device current; everything is enqueued on `st` (mask_of /
+// d_mask_of: masked_plan's)
+int masked_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, const MaskTable& tab,
+                  uint64_t n_bits, const uint32_t* mask_of, const uint32_t* d_mask_of, const ResultBlock& out) {
   int rc;
   if ((rc = check_not_poisoned(s))) return rc;
   if ((rc = check_rows_fit_lds(s, "filtered search"))) return rc;   // (before anything is enqueued)
   s->masked_ctr[4] += 1;
-  MaskedList m;
-  if ((rc = masked_compact_locked(s, st, d_mask, n_bits, &m))) return rc;
-  return masked_answer_locked(s, st, nq, d_queries, k, d_mask, m, out);
+  MaskedPlan p;
+  if ((rc = masked_plan(s, st, tab, n_bits, nq, mask_of, d_mask_of, &p))) return rc;
+  return masked_answer(s, st, nq, d_queries, k, p, out);
 }
 
-// what a host form stages in front of its device form: the queries, room for the results (h) and the bitmap's words below
-// the row count (masked.dMaskRaw); *n_eff = the bits that may be looked at
-int masked_stage_host(ehx_space* s, HostStage& h, size_t nq, const float* queries, uint32_t k, const uint32_t* mask,
-                      uint64_t n_bits, uint64_t* n_eff) {
-  // (bits at or above the row count are never looked at: only the words below it are staged.  This load of the row count
-  // is the call's snapshot: the device form's own, later, load can only be larger, and the bits it may look at end at n_eff)
-  *n_eff = std::min<uint64_t>(n_bits, s->n.load(std::memory_order_acquire));
-  const size_t n_words = (size_t)((*n_eff + 31) / 32);
+// host pointers in, host pointers out, on the space's stream (on_device)
+int masked_host_locked(ehx_space* s, size_t nq, const float* queries, uint32_t k, const uint32_t* masks, uint32_t n_masks,
+                       uint64_t n_bits, const uint32_t* mask_of, uint64_t* out_ids, float* out_dist, uint32_t* out_count) {
   int rc;
-  if ((rc = s->masked.dMaskRaw.ensure(std::max<size_t>(n_words, 1)))) return rc;
-  if ((rc = h.up(s->stream, queries, nq, s->dims, k, false))) return rc;
-  if (n_words) HIP_TRY(hipMemcpyAsync(s->masked.dMaskRaw.p, mask, n_words * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
-  return EHX_OK;
-}
-
-// host pointers in, host pointers out, on the space's stream (on_device): the bitmap staged in masked.dMaskRaw
-int masked_host_locked(ehx_space* s, size_t nq, const float* queries, uint32_t k, const uint32_t* mask, uint64_t n_bits,
-                       uint64_t* out_ids, float* out_dist, uint32_t* out_count) {
-  int rc;
-  uint64_t n_eff;
   HostStage& h = s->masked.host;
-  if ((rc = masked_stage_host(s, h, nq, queries, k, mask, n_bits, &n_eff))) return rc;
-  if ((rc = masked_locked(s, s->stream, nq, h.q, k, s->masked.dMaskRaw.p, n_eff, h.out))) return rc;
+  if ((rc = h.up(s->stream, queries, nq, s->dims, k, false))) return rc;
+  const MaskTable tab = {masks, (n_bits + 31) / 32, n_masks, true};
+  if ((rc = masked_locked(s, s->stream, nq, h.q, k, tab, n_bits, mask_of, nullptr, h.out))) return rc;
   return h.out.copy_out(s->stream, out_ids, out_dist, out_count, nullptr);
 }
 
@@ -176,16 +340,17 @@ int graphm_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_querie
   if ((rc = check_not_poisoned(s))) return rc;
   s->graphm_ctr[2] += 1;
   if (s->params.mode != EHX_MODE_GRAPH) route = EHX_WALK_EXACT;
-  MaskedList m;
+  MaskedPlan p;
   if (route != EHX_WALK_GRAPH) {
     if (route == EHX_WALK_EXACT && (rc = check_rows_fit_lds(s, "filtered search"))) return rc;   // (before anything is enqueued)
-    if ((rc = masked_compact_locked(s, st, d_mask, n_bits, &m))) return rc;
-    if (route == EHX_WALK_AUTO) route = m.n_allowed * EHX_WALK_LIST_FACTOR >= m.n_eff ? EHX_WALK_GRAPH : EHX_WALK_EXACT;
+    const MaskTable tab = {d_mask, (n_bits + 31) / 32, 1, false};
+    if ((rc = masked_plan(s, st, tab, n_bits, nq, nullptr, nullptr, &p))) return rc;
+    if (route == EHX_WALK_AUTO) route = p.n_allowed[0] * EHX_WALK_LIST_FACTOR >= p.n_eff ? EHX_WALK_GRAPH : EHX_WALK_EXACT;
   }
   if (route == EHX_WALK_EXACT) {
     if ((rc = check_rows_fit_lds(s, "filtered search"))) return rc;   // (EHX_WALK_AUTO: known only now)
     s->graphm_ctr[1] += nq;
-    return masked_answer_locked(s, st, nq, d_queries, k, d_mask, m, out);
+    return masked_answer(s, st, nq, d_queries, k, p, out);
   }
   if ((rc = s->masked.dCapHits.ensure(1, true))) return rc;
   // (the walk takes its own snapshot of the row count behind the refusal g_n != n; a bitmap cut at an earlier, smaller
@@ -196,13 +361,20 @@ int graphm_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_querie
   return EHX_OK;
 }
 
+// host pointers in, host pointers out, on the space's stream: the bitmap's words below the row count staged in front of the
+// device form, which every route reads them from
 int graphm_host_locked(ehx_space* s, size_t nq, const float* queries, uint32_t k, const uint32_t* mask, uint64_t n_bits,
                        uint32_t route, uint64_t* out_ids, float* out_dist, uint32_t* out_count) {
   int rc;
-  uint64_t n_eff;
   HostStage& h = s->masked.host;
-  if ((rc = masked_stage_host(s, h, nq, queries, k, mask, n_bits, &n_eff))) return rc;
-  if ((rc = graphm_locked(s, s->stream, nq, h.q, k, s->masked.dMaskRaw.p, n_eff, route, h.out))) return rc;
+  // (bits at or above the row count are never looked at: only the words below it are staged.  This load of the row count
+  // is the call's snapshot: the device form's own, later, load can only be larger, and the bits it may look at end at n_eff)
+  const uint64_t n_eff = std::min<uint64_t>(n_bits, s->n.load(std::memory_order_acquire));
+  const MaskTable tab = {mask, (n_eff + 31) / 32, 1, true};
+  const uint32_t* d_mask;
+  if ((rc = h.up(s->stream, queries, nq, s->dims, k, false))) return rc;
+  if ((rc = masked_maps(s, s->stream, tab, n_eff, &d_mask))) return rc;
+  if ((rc = graphm_locked(s, s->stream, nq, h.q, k, d_mask, n_eff, route, h.out))) return rc;
   return h.out.copy_out(s->stream, out_ids, out_dist, out_count, nullptr);
 }
 
@@ -216,7 +388,8 @@ int ehx_knn_masked_device(ehx_space* s, void* stream, size_t n_queries, const fl
   if (int rc = masked_check(s, n_queries, k, d_queries, d_mask, n_bits, d_out_ids, d_out_dist, d_out_count)) return rc;
   const hipStream_t st = (hipStream_t)stream;
   return search_on_device(s, "ehx_knn_masked_device", kMaskedWhy, n_queries, &st, [&] {
-    return masked_locked(s, st, n_queries, d_queries, k, d_mask, n_bits,
+    const MaskTable tab = {d_mask, (n_bits + 31) / 32, 1, false};
+    return masked_locked(s, st, n_queries, d_queries, k, tab, n_bits, nullptr, nullptr,
                          ResultBlock{d_out_ids, d_out_dist, d_out_count, nullptr, n_queries, k});
   });
 }
@@ -225,7 +398,32 @@ int ehx_knn_masked(ehx_space* s, size_t n_queries, const float* queries, uint32_
                    uint64_t* out_ids, float* out_dist, uint32_t* out_count) {
   if (int rc = masked_check(s, n_queries, k, queries, mask, n_bits, out_ids, out_dist, out_count)) return rc;
   return search_on_device(s, "ehx_knn_masked", kMaskedWhy, n_queries, nullptr, [&] {
-    return masked_host_locked(s, n_queries, queries, k, mask, n_bits, out_ids, out_dist, out_count);
+    return masked_host_locked(s, n_queries, queries, k, mask, 1, n_bits, nullptr, out_ids, out_dist, out_count);
+  });
+}
+
+int ehx_knn_masked_multi_device(ehx_space* s, void* stream, size_t n_queries, const float* d_queries, uint32_t k,
+                                const uint32_t* d_masks, uint32_t n_masks, uint64_t n_bits, const uint32_t* d_mask_of,
+                                uint64_t* d_out_ids, float* d_out_dist, uint32_t* d_out_count) {
+  if (int rc = masked_table_check(s, n_queries, k, d_queries, d_masks, n_masks, n_bits, d_mask_of, d_out_ids, d_out_dist,
+                                  d_out_count))
+    return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  return search_on_device(s, "ehx_knn_masked_multi_device", kMaskedWhy, n_queries, &st, [&] {
+    const MaskTable tab = {d_masks, (n_bits + 31) / 32, n_masks, false};
+    return masked_locked(s, st, n_queries, d_queries, k, tab, n_bits, nullptr, d_mask_of,
+                         ResultBlock{d_out_ids, d_out_dist, d_out_count, nullptr, n_queries, k});
+  });
+}
+
+int ehx_knn_masked_multi(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, const uint32_t* masks,
+                         uint32_t n_masks, uint64_t n_bits, const uint32_t* mask_of, uint64_t* out_ids, float* out_dist,
+                         uint32_t* out_count) {
+  if (int rc = masked_table_check(s, n_queries, k, queries, masks, n_masks, n_bits, mask_of, out_ids, out_dist, out_count))
+    return rc;
+  if (int rc = check_mask_of(mask_of, n_queries, n_masks)) return rc;   // (before anything is enqueued)
+  return search_on_device(s, "ehx_knn_masked_multi", kMaskedWhy, n_queries, nullptr, [&] {
+    return masked_host_locked(s, n_queries, queries, k, masks, n_masks, n_bits, mask_of, out_ids, out_dist, out_count);
   });
 }
 
@@ -263,7 +461,7 @@ int ehx_test_graph_masked_counters(ehx_space* s, uint64_t out[4]) {
 }
 
 // test hook, not part of the ABI: queries answered on the scan route, on the exact route, queries that overflowed, scan
-// passes launched, calls
+// passes launched, calls (ehx_knn_masked* and ehx_knn_masked_multi* both count here)
 void ehx_test_masked_counters(ehx_space* s, uint64_t out[5]) {
   for (int i = 0; i < 5; ++i) out[i] = s ? s->masked_ctr[i].load(std::memory_order_relaxed) : 0;
 }

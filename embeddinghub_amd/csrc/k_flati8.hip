@@ -181,7 +181,7 @@ static_assert(sizeof(I8Ctx) <= 64, "I8Ctx slot");
 // waits see DMA pieces only.
 // MASKED: the masked kNN's scans (k_masked.hip) — a hit whose row the bitmap does not allow is dropped before it takes a pool
 // slot.  A flag of the template, so the scans of every other caller run the flush they always ran.  Three forms: kMaskNone,
-// kMaskOne (the batch's ONE bitmap) and kMaskPerQuery (ehx_knn_masked_multi*, k_maskedq.hip): ctx->allow is ONE block, the
+// kMaskOne (the batch's ONE bitmap) and kMaskPerQuery (ehx_knn_masked_multi*, several masks): ctx->allow is ONE block, the
 // word offset of every query's bitmap inside it ([q_rows], padding queries included) followed by the bitmaps, and the bit
 // tested is that of the bitmap of the hit's own query.
 constexpr int kMaskNone = 0, kMaskOne = 1, kMaskPerQuery = 2;

@@ -1,33 +1,40 @@
-// Exact kNN under a row bitmap (ehx_knn_masked*): the first k of the ALLOWED rows in (canonical distance, id) order — the
-// answer of ehx_knn_among with the ascending list of allowed rows, byte for byte.  This file compacts the bitmap:
-//   masked_count_kernel    allowed rows of every 256-row tile (8 words of the bitmap)
-//   masked_prefix_kernel   their exclusive prefix, cum[0 .. n_tiles] (cum[n_tiles] = the number of allowed rows)
-//   masked_fill_kernel     the ascending list of allowed row ids
-//   masked_sample_kernel   every stride-th allowed id by rank: the sample whose exact k-th distance is the first radius
-//   masked_radius_kernel   radius[q] = that distance, from the list scan's answer over the sample (+Inf while it gave fewer
-//                          than k)
-// The list serves the exact route (k_among.hip) and the host's pass plan; the scan route (ehx_masked.cpp) is the falling-
-// radius kNN of k_radius.hip with the bitmap in the int8 scan's flush and this first radius — that file's header has the
-// re-rank kernel and the argument why the answer is exact, "allowed rows" being its rows.
+// Exact kNN under row bitmaps (ehx_knn_masked*: one bitmap; ehx_knn_masked_multi*: a table, one per query): the first k of
+// the ALLOWED rows in (canonical distance, id) order — the answer of ehx_knn_among with the ascending list of allowed rows,
+// byte for byte.  This file compacts the bitmaps, every one of a table in one set of launches, the mask a grid dimension
+// (one bitmap: a table of one, used where it lies — the row stride is never applied):
+//   masked_count_kernel    allowed rows of every 256-row tile (8 words of the bitmap) of every mask
+//   masked_prefix_kernel   their exclusive prefix per mask, cum[m][0 .. n_tiles] (cum[m][n_tiles] = mask m's allowed rows)
+//   masked_fill_kernel     the ascending lists of allowed row ids, mask m's at list + off[m] (the host places them back to
+//                          back from the counts it read)
+//   masked_sample_kernel   every mask's sample, every ceil(allowed / 256)-th allowed id by rank: its exact k-th distance is
+//                          the first radius (launched for the scan route only)
+//   masked_radius_kernel   radius[q] = that distance, from the list scan's answer over the sample of the query's own mask
+//                          (+Inf while it gave fewer than k)
+// The lists serve the exact route (k_among.hip) and the host's pass plan; the scan route (ehx_masked.cpp) is the falling-
+// radius kNN of k_radius.hip with the bitmap in the int8 scan's flush (one for the batch, or one per query: k_flati8.hip)
+// and this first radius — that file's header has the re-rank kernel and the argument why the answer is exact, "allowed
+// rows" being its rows.
 #include "ehx_kernels.h"
 
 namespace ehx {
 
-// one lane per tile
-__global__ __launch_bounds__(256) void masked_count_kernel(const uint32_t* __restrict__ mask, uint64_t n_bits, uint32_t n_tiles,
-                                                           uint32_t* __restrict__ cum) {
-  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+// one lane per tile, blockIdx.y = mask
+__global__ __launch_bounds__(256) void masked_count_kernel(const uint32_t* __restrict__ maps, uint64_t stride, uint64_t n_bits,
+                                                           uint32_t n_tiles, uint32_t* __restrict__ cum) {
+  const uint32_t t = blockIdx.x * 256u + threadIdx.x, m = blockIdx.y;
   if (t >= n_tiles) return;
+  const uint32_t* mask = maps + (size_t)m * stride;
   uint32_t c = 0;
   for (uint32_t w = 0; w < 8; ++w) c += (uint32_t)__builtin_popcount(mask_word(mask, (uint64_t)t * 8u + w, n_bits));
-  cum[t] = c;
+  cum[(size_t)m * (n_tiles + 1u) + t] = c;
 }
 
-// ONE workgroup: cum[0 .. n_tiles) counts -> exclusive prefix in place, cum[n_tiles] = the total.  Blocks of 1024 tiles,
-// a running carry between them (n_tiles <= 2^24: at most 16 384 steps of a kernel that runs once per call).
-__global__ __launch_bounds__(1024) void masked_prefix_kernel(uint32_t* __restrict__ cum, uint32_t n_tiles) {
+// ONE workgroup per mask: cum[m][0 .. n_tiles) counts -> exclusive prefix in place, cum[m][n_tiles] = the total.  Blocks of
+// 1024 tiles, a running carry between them (n_tiles <= 2^24: at most 16 384 steps of a kernel that runs once per call).
+__global__ __launch_bounds__(1024) void masked_prefix_kernel(uint32_t* __restrict__ cum_all, uint32_t n_tiles) {
   __shared__ uint32_t wave_sum[16];
   __shared__ uint32_t carry_s;
+  uint32_t* cum = cum_all + (size_t)blockIdx.x * (n_tiles + 1u);
   const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
   if (tid == 0) carry_s = 0;
   __syncthreads();
@@ -51,10 +58,12 @@ __global__ __launch_bounds__(1024) void masked_prefix_kernel(uint32_t* __restric
   if (tid == 0) cum[n_tiles] = carry_s;
 }
 
-// one workgroup per tile, one lane per row: list[cum[tile] + rank inside the tile] = row id
-__global__ __launch_bounds__(256) void masked_fill_kernel(const uint32_t* __restrict__ mask, uint64_t n_bits,
-                                                          const uint32_t* __restrict__ cum, uint64_t* __restrict__ list) {
-  const uint32_t tile = blockIdx.x, tid = threadIdx.x;
+// one workgroup per (tile, mask), one lane per row: list[off[mask] + cum[mask][tile] + rank inside the tile] = row id
+__global__ __launch_bounds__(256) void masked_fill_kernel(const uint32_t* __restrict__ maps, uint64_t stride, uint64_t n_bits,
+                                                          uint32_t n_tiles, const uint32_t* __restrict__ cum,
+                                                          const MaskedOffsets off, uint64_t* __restrict__ list) {
+  const uint32_t tile = blockIdx.x, m = blockIdx.y, tid = threadIdx.x;
+  const uint32_t* mask = maps + (size_t)m * stride;
   const uint32_t wi = tid >> 5, bit = tid & 31u;
   uint32_t before = 0, mine = 0;
   for (uint32_t w = 0; w < 8; ++w) {   // (the tile's 8 words: 32 bytes, the same for every lane)
@@ -64,13 +73,17 @@ __global__ __launch_bounds__(256) void masked_fill_kernel(const uint32_t* __rest
   }
   if (!((mine >> bit) & 1u)) return;
   const uint32_t rank = before + (uint32_t)__builtin_popcount(mine & ((1u << bit) - 1u));
-  list[(uint64_t)cum[tile] + rank] = (uint64_t)tile * 256u + tid;
+  list[off.off[m] + cum[(size_t)m * (n_tiles + 1u) + tile] + rank] = (uint64_t)tile * 256u + tid;
 }
 
-__global__ __launch_bounds__(256) void masked_sample_kernel(const uint64_t* __restrict__ list, uint64_t n_allowed,
-                                                            uint64_t stride, uint64_t* __restrict__ sample) {
-  const uint64_t i = threadIdx.x;
-  if (i * stride < n_allowed) sample[i] = list[i * stride];
+// one workgroup per mask: sample[256 m + i] = mask m's list[i * stride] while i * stride < allowed, stride = ceil(allowed / 256)
+__global__ __launch_bounds__(256) void masked_sample_kernel(const uint64_t* __restrict__ list, const MaskedOffsets off,
+                                                            const uint32_t* __restrict__ cum, uint32_t n_tiles,
+                                                            uint64_t* __restrict__ sample) {
+  const uint32_t m = blockIdx.x;
+  const uint64_t n_allowed = cum[(size_t)m * (n_tiles + 1u) + n_tiles];
+  const uint64_t stride = (n_allowed + 255u) / 256u, i = threadIdx.x;
+  if (i * stride < n_allowed) sample[(size_t)m * 256u + i] = list[off.off[m] + i * stride];
 }
 
 __global__ __launch_bounds__(256) void masked_radius_kernel(const float* __restrict__ dist, const uint32_t* __restrict__ cnt,
@@ -80,19 +93,29 @@ __global__ __launch_bounds__(256) void masked_radius_kernel(const float* __restr
   radius[q] = cnt[q] >= k ? dist[(size_t)q * k + (k - 1)] : __builtin_inff();
 }
 
-hipError_t launch_masked_compact(const uint32_t* mask, uint64_t n_bits, uint32_t n_tiles, uint32_t* cum, uint64_t* list,
-                                 hipStream_t st) {
-  if (n_tiles == 0) return hipSuccess;
-  hipLaunchKernelGGL(masked_count_kernel, dim3((n_tiles + 255u) / 256u), dim3(256), 0, st, mask, n_bits, n_tiles, cum);
-  hipLaunchKernelGGL(masked_prefix_kernel, dim3(1), dim3(1024), 0, st, cum, n_tiles);
-  hipLaunchKernelGGL(masked_fill_kernel, dim3(n_tiles), dim3(256), 0, st, mask, n_bits, cum, list);
+hipError_t launch_masked_count(const uint32_t* maps, uint64_t stride, uint32_t n_masks, uint64_t n_bits, uint32_t n_tiles,
+                               uint32_t* cum, hipStream_t st) {
+  if (n_tiles == 0 || n_masks == 0) return hipSuccess;
+  if (n_masks > kMaskedMaxMasks || (n_masks > 1 && stride < (n_bits + 31) / 32)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(masked_count_kernel, dim3((n_tiles + 255u) / 256u, n_masks), dim3(256), 0, st, maps, stride, n_bits,
+                     n_tiles, cum);
+  hipLaunchKernelGGL(masked_prefix_kernel, dim3(n_masks), dim3(1024), 0, st, cum, n_tiles);
   return hipGetLastError();
 }
 
-hipError_t launch_masked_sample(const uint64_t* list, uint64_t n_allowed, uint64_t stride, uint64_t* sample, hipStream_t st) {
-  if (n_allowed == 0) return hipSuccess;
-  if (stride == 0 || (n_allowed + stride - 1) / stride > 256) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(masked_sample_kernel, dim3(1), dim3(256), 0, st, list, n_allowed, stride, sample);
+hipError_t launch_masked_fill(const uint32_t* maps, uint64_t stride, uint32_t n_masks, uint64_t n_bits, uint32_t n_tiles,
+                              const uint32_t* cum, const MaskedOffsets& off, uint64_t* list, hipStream_t st) {
+  if (n_tiles == 0 || n_masks == 0) return hipSuccess;
+  if (n_masks > kMaskedMaxMasks || (n_masks > 1 && stride < (n_bits + 31) / 32)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(masked_fill_kernel, dim3(n_tiles, n_masks), dim3(256), 0, st, maps, stride, n_bits, n_tiles, cum, off, list);
+  return hipGetLastError();
+}
+
+hipError_t launch_masked_samples(const uint64_t* list, const MaskedOffsets& off, const uint32_t* cum, uint32_t n_masks,
+                                 uint32_t n_tiles, uint64_t* sample, hipStream_t st) {
+  if (n_tiles == 0 || n_masks == 0) return hipSuccess;
+  if (n_masks > kMaskedMaxMasks) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(masked_sample_kernel, dim3(n_masks), dim3(256), 0, st, list, off, cum, n_tiles, sample);
   return hipGetLastError();
 }
 

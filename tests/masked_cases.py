@@ -39,13 +39,19 @@ def sample_ids(allowed):
     return L[::stride]
 
 
-def passes(allowed):
-    """[(first tile, tiles)] of the scan passes (masked_passes, ehx_masked.cpp)"""
+def running(allowed):
+    """int64 [tiles + 1]: the allowed rows before every 256-row tile, the last entry their number"""
     n = len(allowed)
     n_tiles = (n + TILE - 1) // TILE
     pad = np.zeros(n_tiles * TILE, dtype=np.int64)
     pad[:n] = allowed
-    cum = np.concatenate([[0], np.cumsum(pad.reshape(n_tiles, TILE).sum(axis=1))])
+    return np.concatenate([[0], np.cumsum(pad.reshape(n_tiles, TILE).sum(axis=1))])
+
+
+def passes_over(cum):
+    """[(first tile, tiles)] of the scan passes over a running count (masked_passes, ehx_masked.cpp): THE statement of the
+    pass cut — one bitmap passes its own counts, a table the pointwise maximum of its scanned masks'"""
+    n_tiles = len(cum) - 1
     out, t0, want = [], 0, SAMPLE * GROWTH
     while t0 < n_tiles:
         reach = np.nonzero(cum[t0 + 1:] >= want)[0]
@@ -53,6 +59,11 @@ def passes(allowed):
         out.append((t0, t1 - t0))
         t0, want = t1, want * GROWTH
     return out
+
+
+def passes(allowed):
+    """[(first tile, tiles)] of the scan passes under one bitmap"""
+    return passes_over(running(allowed))
 
 
 def far_then_near(X, q, n_far=4096, n_near=1500):

@@ -1,7 +1,7 @@
 """Helper of the tests of the kNN under a table of bitmaps, one per query (no test here): the table and the queries' masks of
 the int8 cases, shared by the CPU model (tests/test_masked_multi_model.py) and the GPU tests (tests/test_knn_masked_multi.py),
-and a restatement of how ehx_maskedq.cpp routes the queries, orders them and cuts the ONE scan of a batch into passes.
-Sample, exact cut and the single-mask plan are tests/masked_cases.py's."""
+and a restatement of how ehx_masked.cpp routes the queries, orders them and cuts the ONE scan of a batch into passes.
+Sample, exact cut and the pass cut are tests/masked_cases.py's."""
 import functools
 
 import numpy as np
@@ -46,7 +46,7 @@ def scans(tab, n_rows=None):
 
 
 def order(tab, mask_of):
-    """the order ehx_maskedq.cpp answers the queries in: the scan route's first, then by mask; stable"""
+    """the order ehx_masked.cpp answers the queries in: the scan route's first, then by mask; stable"""
     s = scans(tab)
     place = np.where(s[mask_of], 0, MAX_MASKS) + mask_of
     return np.argsort(place, kind="stable")
@@ -54,22 +54,10 @@ def order(tab, mask_of):
 
 def passes(tab, mask_of):
     """[(first tile, tiles)] of the batch's ONE scan: pass j ends at the first tile where some scanned mask has seen
-    256 * 16^j allowed rows — masked_passes over the pointwise maximum of the scanned masks' running counts"""
-    n = tab.shape[1]
-    n_tiles = (n + mc.TILE - 1) // mc.TILE
+    256 * 16^j allowed rows — the pass cut of masked_cases over the pointwise maximum of the scanned masks' running counts"""
     used = [m for m in np.unique(mask_of) if scans(tab)[m]]
     assert used
-    pad = np.zeros((len(used), n_tiles * mc.TILE), dtype=np.int64)
-    pad[:, :n] = tab[used]
-    cum = np.concatenate([np.zeros((len(used), 1), dtype=np.int64),
-                          np.cumsum(pad.reshape(len(used), n_tiles, mc.TILE).sum(axis=2), axis=1)], axis=1).max(axis=0)
-    out, t0, want = [], 0, mc.SAMPLE * mc.GROWTH
-    while t0 < n_tiles:
-        reach = np.nonzero(cum[t0 + 1:] >= want)[0]
-        t1 = n_tiles if len(reach) == 0 or cum[n_tiles] <= want else t0 + 1 + int(reach[0])
-        out.append((t0, t1 - t0))
-        t0, want = t1, want * mc.GROWTH
-    return out
+    return mc.passes_over(np.max([mc.running(tab[m]) for m in used], axis=0))
 
 
 def parity():

@@ -80,6 +80,7 @@ def test_mask_marshalling():
 
 
 def test_masked_kernels_use_no_scratch_and_spill_no_vector_registers(tmp_path):
+    """ONE kernel file serves one bitmap and a table of them: exactly five functions, each once"""
     src = os.path.join(ehx_build.CSRC, "k_masked.hip")
     flags = [f for f in ehx_build.FLAGS if f != "-shared"]
     r = subprocess.run([ehx_build.HIPCC] + flags + ["-Rpass-analysis=kernel-resource-usage", "-x", "hip", "-c", src, "-o",

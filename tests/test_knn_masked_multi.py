@@ -145,6 +145,32 @@ def test_one_mask_equals_knn_masked_byte_for_byte(d):
     s.drop()
 
 
+def test_two_identical_bitmaps_equal_knn_masked_byte_for_byte():
+    """One mask runs the flush with the batch's ONE bitmap on both sides of the test above; a table of TWO identical bitmaps,
+    the queries' masks interleaved, runs the flush with a bitmap per query (and the grouping by mask) against it.  Identical
+    bitmaps give the identical pointwise maximum, so the passes — and every other counter — are knn_masked's too."""
+    d = 128
+    X, Q = rc.i8_data(d)
+    Q = Q[:mmc.NQ]
+    s = _i8_space("masked-twins", d, "cosine", X)
+    of = mmc.interleaved(mmc.NQ, 2)
+    for name in ("half", "few", "empty"):
+        allowed = mmc.table()[mmc.NAMES.index(name)]
+        twins = np.stack([allowed, allowed])
+        for k in (10, 48, mmc.EXACT_K):
+            c0 = _counters(s)
+            one = s.knn_masked(Q, k, allowed)
+            c1 = _counters(s)
+            multi = s.knn_masked_multi(Q, k, twins, of)
+            c2 = _counters(s)
+            assert _same_bytes(one, multi), (name, k)
+            assert (c1 - c0).tolist() == (c2 - c1).tolist(), (name, k)
+            dev = _device_form(s, Q, k, twins, of)
+            assert _same_bytes(one, dev), (name, k)
+            assert (_counters(s) - c2).tolist() == (c1 - c0).tolist(), (name, k)
+    s.drop()
+
+
 # ---- rows the bitmaps do not cover ----
 
 def test_n_bits_below_the_row_count_and_not_a_multiple_of_32():

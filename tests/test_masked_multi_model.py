@@ -1,5 +1,5 @@
 """CPU model of the scan route of the kNN under a table of bitmaps, one per query (host logic, no GPU): the pass plan and the
-cascade of ehx_maskedq.cpp / k_radius.hip for several masks in one batch, restated in numpy on range_thr
+cascade of ehx_masked.cpp / k_radius.hip for several masks in one batch, restated in numpy on range_thr
 (tests/range_cases.py) over the int8 bound of tests/i8_model.py (through test_range_model._s_lower), as
 tests/test_masked_model.py does it for one bitmap.  Every query draws its first radius from the sample of its OWN mask and
 collects the rows its OWN mask allows; the passes are the batch's (masked_multi_cases.passes).
