@@ -427,55 +427,6 @@ int ehx_gen_manifold_rows_device(void* stream, uint64_t seed, uint64_t row0, uin
   return EHX_OK;
 }
 
-}  // extern "C"
-
-namespace ehx_impl {
-// rows row0, row0 + stride, ... of dataset `seed` appended to the space (locked exclusively by the caller)
-int fill_synthetic_locked(ehx_space* s, uint64_t seed, uint64_t row0, uint64_t n_rows, int normalize, uint64_t stride,
-                          uint32_t latent) {
-  if (s->frozen) return fail(EHX_EIMMUTABLE, "Cannot write to immutable space");
-  if (s->implicit_n != s->n)   // (generated rows form the head of a space: their keys are their decimal row ids)
-    return fail(EHX_EINVAL, "space '%s' already holds keyed rows", s->name.c_str());
-  HIP_TRY(hipSetDevice(s->device));
-  if (s->n + n_rows >= (1ull << 32)) return fail(EHX_EUNSUPPORTED, "a shard holds at most 2^32-1 rows");
-  int rc = grow(s, s->n + n_rows);
-  if (rc) return rc;
-  s->implicit_keys = true;
-  if (s->x_half) {
-    // generate fp32 slabs, round them into the fp16 rows
-    const uint64_t slab = 1u << 16;
-    DevBuf<float> tmp;
-    if ((rc = tmp.ensure(std::min<uint64_t>(slab, n_rows) * s->ld))) return rc;
-    for (uint64_t r0 = 0; r0 < n_rows; r0 += slab) {
-      const uint64_t m = std::min<uint64_t>(slab, n_rows - r0);
-      HIP_TRY(launch_gen_rows(seed, row0 + r0 * stride, m, s->dims, s->ld, normalize, tmp.p, s->stream, stride, latent));
-      HIP_TRY(launch_store_rows_f16(tmp.p, s->ld, nullptr, s->n + r0, m, s->dims, s->ld, (__half*)s->rows.dX.p, s->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    tmp.release();
-  } else {
-    HIP_TRY(launch_gen_rows(seed, row0, n_rows, s->dims, s->ld, normalize, (float*)s->xrow(s->n), s->stream, stride, latent));
-    if (s->x_perm) HIP_TRY(launch_permute_blocks((float*)s->rows.dX.p, s->ld, s->n, n_rows, nullptr, s->stream));
-  }
-  HIP_TRY(launch_row_stats(s->rows.dX.p, s->x_half, s->n, n_rows, s->dims, s->ld, s->metric, s->rows.dInv.p, s->rows.dRowp.p, s->rows.dMaxSumsq.p,
-                           s->stream, s->x_perm ? 1 : 0));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  if ((rc = refresh_scan16(s, s->n, n_rows, nullptr, true, s->n + n_rows))) return rc;
-  const uint64_t old_n = s->n;
-  s->n += n_rows;
-  {
-    std::unique_lock<std::shared_mutex> kl(s->kmu);
-    s->implicit_n = s->n;
-  }
-  if (s->params.mode == EHX_MODE_GRAPH && s->g_n == old_n && s->params.build_batch != 0xFFFFFFFFu) {
-    if ((rc = graph_insert(s, old_n, n_rows, s->params.build_batch))) return rc;
-  }
-  return EHX_OK;
-}
-}  // namespace ehx_impl
-
-extern "C" {
-
 static int fill_generated(ehx_space* s, uint64_t seed, uint64_t row0, uint64_t n_rows, int normalize, uint32_t latent) {
   if (!valid_space(s)) return fail(EHX_EINVAL, "space is NULL");
   if (n_rows == 0) return EHX_OK;

@@ -3,7 +3,7 @@
 //   ehx_flat.cpp    the exact flat chain: scan plans, fp32 / fp16 / int8 pipelines, exhaustive pass, engine fall-through
 //   ehx_graph.cpp   graph mode: GPU-side insertion, update-in-place repair, the graph search pipeline
 //   ehx_shards.cpp  row-sharded spaces inside one process (ehx_params.shards)
-//   ehx_write.cpp   Set / BatchSet: staging, upload, row statistics, scan copies, write combiner
+//   ehx_write.cpp   the write path (Set / BatchSet, the generator): landers, row statistics, derived copies, publish, write combiner
 //   ehx_rowio.cpp   rows in and out without staging: Set from device memory, batched Get, Get by row ids on the device
 //   ehx_search.cpp  ehx_knn_device / ehx_knn (host pointers: four routes behind the request combiner, ehx_combine.h) / keys / merge
 //   ehx_call.cpp    what the batched entry points share: argument checks, the entry scaffold, key lookup, result blocks, host
@@ -843,7 +843,7 @@ int among_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries
 
 // ---- ehx_write.cpp ----
 int sync_stream(ehx_space* s, hipStream_t st);
-int refresh_scan16(ehx_space* s, uint64_t row0, uint64_t n, hipStream_t st, bool exclusive, uint64_t n_after);
+int refresh_derived_copies(ehx_space* s, uint64_t row0, uint64_t n, hipStream_t st, bool exclusive, uint64_t n_after);
 // Where the rows of a Set come from: host floats [n][dims], staged and uploaded (ehx_set_batch), or a dense [*][dims] matrix
 // in device memory, scattered by scatter_rows_kernel (ehx_set_batch_device).
 struct RowSource {
@@ -863,12 +863,27 @@ struct RowSource {
 };
 // the body of ehx_set_batch and ehx_set_batch_device: locking, the append-only fast path, graph batches that rewrite keys
 int set_batch_from(ehx_space* s, size_t n, const char* const* keys, const size_t* klens, const RowSource& src);
-int write_rows_locked_fwd(ehx_space* s, size_t n, const std::vector<uint64_t>& ids, uint64_t next, const RowSource& src);
+bool is_dense_run(const uint64_t* ids, size_t n);   // ids[i] == ids[0] + i for every i
+// What a batch of row ids touches, host arithmetic only, computed once per batch by write_batch from the ids and the published
+// row count `old_n` (ids == nullptr: the generator's rows old_n, old_n + 1, ...).
+struct WriteBatch {
+  const uint64_t* ids = nullptr;
+  size_t n = 0;
+  uint64_t lo = ~0ull, hi = 0;      // the touched id range (an empty batch: the identities of min and max)
+  bool dense_run = true;            // one run of ids
+  bool touches_committed = false;   // some id < old_n: a published row is rewritten in place
+  bool all_appended = false;        // the run old_n, old_n + 1, ...: a pure append of fresh, distinct keys
+};
+WriteBatch write_batch(const uint64_t* ids, size_t n, uint64_t old_n);
+// the write path behind every Set (new_keys == nullptr: a shard's rows, whose parent publishes the keys); invariants at its head
+int write_rows(ehx_space* s, const WriteBatch& b, uint64_t next, const RowSource& src, std::vector<std::string>* new_keys,
+               bool append_only);
+// new_keys (moved from) become the keys of rows old_n, old_n + 1, ...; under kmu
+void publish_keys(ehx_space* s, uint64_t old_n, std::vector<std::string>& new_keys);
 // The duplicate rule of a parallel scatter: out[i] = ids[i] for the LAST occurrence of every id, ~0 for the ones before it —
 // a key given twice in one batch keeps its last row, as the host path's in-order copies leave it.
 void last_writers(const uint64_t* ids, size_t n, uint64_t* out);
-
-// ---- ehx_api.cpp ----
+// the generator's rows through the same tail (the space locked exclusively by the caller)
 int fill_synthetic_locked(ehx_space* s, uint64_t seed, uint64_t row0, uint64_t n_rows, int normalize, uint64_t stride,
                           uint32_t latent = 0);
 

@@ -9,7 +9,7 @@ namespace {
 // rows d_row_ids[0, n) of the space (locked shared, scratch_mu held, the gathering device current) -> d_out [n][dims],
 // d_valid [n], enqueued on `st`; wait: the stream is waited for before the shards' locks are released.  The ONE read of the
 // row count is taken here.  by_ev orders the call behind the last one that used the by-key scratch (d_out may be it) and is
-// what a writer that rewrites rows in place waits for (write_rows_locked).
+// what a writer that rewrites rows in place waits for (write_rows).
 int gather_locked(ehx_space* s, hipStream_t st, size_t n, const uint64_t* d_row_ids, float* d_out, uint32_t* d_valid, bool wait) {
   int rc;
   if ((rc = s->by.by_ev.ensure(hipEventDisableTiming))) return rc;

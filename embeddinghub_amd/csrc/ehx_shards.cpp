@@ -76,7 +76,7 @@ int sharded_set_batch(ehx_space* p, size_t n, const char* const* keys, const siz
     RowSource mine = src;
     if (src.dev) mine.idx = pos[i].data();
     else mine.host = rows[i].data();
-    return write_rows_locked_fwd(c, lids[i].size(), lids[i], next_local, mine);
+    return write_rows(c, write_batch(lids[i].data(), lids[i].size(), c->n), next_local, mine, nullptr, false);
   });
   if (rc) {
     // A failing shard (e.g. out of memory while growing) must not leave the others ahead of the parent: their published
@@ -93,12 +93,7 @@ int sharded_set_batch(ehx_space* p, size_t n, const char* const* keys, const siz
     snprintf(g_err, sizeof(g_err), "%s", msg.c_str());
     return rc;
   }
-  const uint64_t old_n = p->n;
-  {
-    std::unique_lock<std::shared_mutex> kl(p->kmu);
-    for (size_t i = 0; i < new_keys.size(); ++i) p->key_to_id.emplace(new_keys[i], old_n + i);
-    for (auto& k : new_keys) p->id_to_key.push_back(std::move(k));
-  }
+  publish_keys(p, p->n, new_keys);
   p->n = next;
   return EHX_OK;
 }

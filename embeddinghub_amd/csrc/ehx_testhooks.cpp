@@ -16,6 +16,7 @@
 //   ehx_test_largek_plan       the route's pass planner, host arithmetic only (no device, no space)
 // ... and of the Set from device memory (ehx_rowio.cpp, ehx_write.cpp):
 //   ehx_test_last_writers      the duplicate rule of its scatter, host arithmetic only (no device, no space)
+//   ehx_test_write_batch       what a batch of row ids touches (WriteBatch), host arithmetic only (no device, no space)
 //   ehx_test_write_times       device time of the last write's upload (or scatter) and of its derived copies (scripts/bench_rowio.py)
 //   ehx_test_shard             the handle of one shard of a row-sharded space (what a caller that kept one would hold)
 // No production path calls in here.
@@ -398,6 +399,13 @@ uint32_t ehx_test_largek_plan(uint64_t n_rows, uint32_t growth, uint32_t* out_pa
 
 // last_writers(ids[0, n)) into out[0, n): every id's last occurrence keeps it, the ones before it become 2^64 - 1
 void ehx_test_last_writers(const uint64_t* ids, size_t n, uint64_t* out) { last_writers(ids, n, out); }
+
+// write_batch(ids[0, n), old_n): out = {lo, hi, dense_run, touches_committed, all_appended}
+void ehx_test_write_batch(const uint64_t* ids, size_t n, uint64_t old_n, uint64_t out[5]) {
+  const WriteBatch b = write_batch(ids, n, old_n);
+  const uint64_t v[5] = {b.lo, b.hi, b.dense_run, b.touches_committed, b.all_appended};
+  std::copy(v, v + 5, out);
+}
 
 // The writers' stream's time of the last ehx_set_batch / ehx_set_batch_device on an unsharded space, in ms: out[0] the rows
 // (staging copies and uploads, or the wait for the producer and the scatter), out[1] what follows up to the publish (block

@@ -1,17 +1,10 @@
-// Set / BatchSet (ANNIndex::set, index.cc:20-37; Go BatchSet): key resolution, pinned staging, upload, row statistics,
-// scan copies, graph insertion, and the write combiner of concurrent single-row Sets.
+// The write path (ANNIndex::set, index.cc:20-37; Go BatchSet; the generator): three ways to land rows, one finish, one publish,
+// one graph join — and the write combiner of concurrent single-row Sets.
 #include "ehx_internal.h"
 
 #include <unordered_set>
 
-extern "C" {
-
-static int set_batch_locked(ehx_space* s, size_t n, const char* const* keys, const size_t* klens, const RowSource& src);
-static int write_rows_locked(ehx_space* s, size_t n, const std::vector<uint64_t>& ids, uint64_t next, const RowSource& src,
-                             std::vector<std::string>* new_keys, bool append_only = false);
-static bool all_fresh_keys(const ehx_space* s, size_t n, const std::vector<uint64_t>& ids);
-
-int ehx_set_batch(ehx_space* s, size_t n, const char* const* keys, const size_t* klens, const float* vecs) {
+extern "C" int ehx_set_batch(ehx_space* s, size_t n, const char* const* keys, const size_t* klens, const float* vecs) {
   if (!valid_space(s)) return fail(EHX_EINVAL, "space is NULL");
   if (n == 0) return EHX_OK;
   if (!keys || !klens || !vecs) return fail(EHX_EINVAL, "NULL argument");
@@ -20,61 +13,26 @@ int ehx_set_batch(ehx_space* s, size_t n, const char* const* keys, const size_t*
   return set_batch_from(s, n, keys, klens, src);
 }
 
-}  // extern "C"
+namespace ehx_impl {
 
-int ehx_impl::set_batch_from(ehx_space* s, size_t n, const char* const* keys, const size_t* klens, const RowSource& src) {
-  std::lock_guard<std::mutex> wg(s->wmu);
-  if (!is_parent(s) && s->params.mode == EHX_MODE_FLAT) {
-    // Streaming fast path (copy.go's BatchSet chunks, MultiSet): a batch made only of fresh keys is a pure append.
-    // The key lookup needs the lock shared only, and the upload runs with no lock on the space at all.
-    std::vector<uint64_t> ids;
-    std::vector<std::string> new_keys;
-    uint64_t next = 0;
-    bool fast = false;
-    {
-      std::shared_lock<std::shared_mutex> rl(s->mu);
-      if (s->dropped) return fail(EHX_ENOTFOUND, "Not found");
-      if (s->keyless) return fail(EHX_EINVAL, "a shard is written through its parent space");
-      if (!s->frozen) {
-        resolve_keys(s, n, keys, klens, &ids, &next, &new_keys);
-        fast = new_keys.size() == n && all_fresh_keys(s, n, ids);
-      }
-    }
-    if (fast) return write_rows_locked(s, n, ids, next, src, &new_keys, true);
-  }
-  s->excl_waiting.fetch_add(1, std::memory_order_release);   // (searches that arrive from here on wait for this batch's turn)
-  std::unique_lock<std::shared_mutex> wl(s->mu);
-  s->excl_waiting.fetch_sub(1, std::memory_order_release);
-  if (s->dropped) return fail(EHX_ENOTFOUND, "Not found");
-  if (s->keyless) return fail(EHX_EINVAL, "a shard is written through its parent space");
-  auto write = [&](size_t cnt, const char* const* ks, const size_t* kl, const RowSource& v) -> int {
-    return is_parent(s) ? sharded_set_batch(s, cnt, ks, kl, v) : set_batch_locked(s, cnt, ks, kl, v);
-  };
-  if (s->params.mode == EHX_MODE_GRAPH && n > 1 && s->params.build_batch != 0xFFFFFFFFu) {
-    // graph mode replays a batch in call order; when it re-writes keys (known ones, or the same key
-    // twice) every row must be in HBM exactly when its turn comes, so such batches go row by row
-    bool rewrite = false;
-    {
-      std::set<std::string> seen;
-      std::shared_lock<std::shared_mutex> kl(s->kmu);
-      for (size_t i = 0; i < n && !rewrite; ++i) {
-        std::string k(keys[i], klens[i]);
-        uint64_t known = 0;
-        rewrite = implicit_id(s, keys[i], klens[i], &known) || s->key_to_id.count(k) != 0 || !seen.insert(std::move(k)).second;
-      }
-    }
-    if (rewrite) {
-      for (size_t i = 0; i < n; ++i) {
-        int rc = write(1, keys + i, klens + i, src.from(i, s->dims));
-        if (rc) return rc;
-      }
-      return EHX_OK;
-    }
-  }
-  return write(n, keys, klens, src);
+bool is_dense_run(const uint64_t* ids, size_t n) {
+  for (size_t i = 1; i < n; ++i)
+    if (ids[i] != ids[0] + i) return false;
+  return true;
 }
 
-extern "C" {
+WriteBatch write_batch(const uint64_t* ids, size_t n, uint64_t old_n) {
+  WriteBatch b{ids, n};
+  for (size_t i = 0; ids && i < n; ++i) {
+    b.lo = std::min(b.lo, ids[i]);
+    b.hi = std::max(b.hi, ids[i]);
+  }
+  if (!ids && n) b = {nullptr, n, old_n, old_n + n - 1};   // (the generator's rows)
+  b.dense_run = !ids || is_dense_run(ids, n);
+  b.touches_committed = b.lo < old_n;
+  b.all_appended = b.dense_run && (n == 0 || b.lo == old_n);   // (every id fresh and distinct: `next` is old_n + n)
+  return b;
+}
 
 // rows -> pinned staging (fp16 spaces: rounded to binary16, round-to-nearest-even, on the way); large slabs are split
 // over four threads
@@ -109,10 +67,6 @@ static void stage_rows(char* dst, const float* src, size_t elems, bool half) {
   if (done_to < elems) work(done_to, elems);
 }
 
-}  // extern "C"
-
-namespace ehx_impl {
-
 // wait for a stream of the space: the writers' stream through the blocking event, any other by hipStreamSynchronize
 int sync_stream(ehx_space* s, hipStream_t st) {
   if (st == s->wr.wstream && s->wr.wev) {
@@ -125,12 +79,12 @@ int sync_stream(ehx_space* s, hipStream_t st) {
 }
 
 // (re)build the derived copies of rows [row0, row0+n) after they were written; must follow row_stats:
-// graph mode: the search copy; flat fp32 spaces: the fp16 scan copy
+// graph mode: the search copy; flat fp32 spaces: the fp16 scan copy and the int8 scan copy, with their unsafe-row and margin
+// flags
 // exclusive: no search can be reading the space (the caller holds s->mu exclusively and the writer's stream has waited
 // for the searches in flight) — rows below the published count may then move inside their tiles; otherwise every row
 // of [row0, row0 + n) lies beyond the published row count.  n_after: the row count once this write is published.
-int refresh_scan16(ehx_space* s, uint64_t row0, uint64_t n, hipStream_t st, bool exclusive, uint64_t n_after) {
-  if (!st) st = s->stream;
+int refresh_derived_copies(ehx_space* s, uint64_t row0, uint64_t n, hipStream_t st, bool exclusive, uint64_t n_after) {
   if (s->xs() && !s->x_perm && n)
     HIP_TRY(launch_make_search_copy(s->rows.dX.p, s->x_half, s->rows.dInv.p, row0, n, s->ld, s->metric, s->xs(), st));
   if ((!s->has16 && !s->has8) || n == 0) return EHX_OK;  // (kept current whatever engine is selected right now)
@@ -148,16 +102,12 @@ int refresh_scan16(ehx_space* s, uint64_t row0, uint64_t n, hipStream_t st, bool
     uint64_t r8 = row0, e8 = row0 + n;
     const bool sort_tiles = env().i8_sort;
     if (exclusive) {
-      {  // searches still in flight on other streams
-        int rcw = wait_searches_in_flight(s, st);
-        if (rcw) return rcw;
-      }
+      if (int rcw = wait_searches_in_flight(s, st)) return rcw;   // searches still in flight on other streams
       r8 = row0 & ~(uint64_t)255;
       e8 = std::min<uint64_t>(round_up(row0 + n, 256), std::max<uint64_t>(n_after, row0 + n));
     }
-    int rc8;
     const uint64_t slo = sort_tiles ? r8 : 0, shi = sort_tiles ? e8 : 0;
-    if ((rc8 = s->i8.dTileList.ensure((make_scan8_scratch_bytes(r8, e8 - r8, slo, shi) + 7) / 8))) return rc8;
+    if (int rc8 = s->i8.dTileList.ensure((make_scan8_scratch_bytes(r8, e8 - r8, slo, shi) + 7) / 8)) return rc8;
     HIP_TRY(launch_make_scan8(s->rows.dX.p, s->x_half, r8, e8 - r8, s->dims, s->ld, s->ld8, s->metric, s->i8.dX8.p, s->i8.dRowp8.p,
                               s->i8.dTilep8.p, s->i8.dPerm8.p, s->i8.dTileg8.p, slo, shi, s->i8.dTileList.p, s->i8.dUnsafe8.p, st));
     if (s->i8.dTileList.n > (64u << 20) / 8) {  // (a bulk load's scratch — 9 bytes per row — is not kept)
@@ -166,10 +116,7 @@ int refresh_scan16(ehx_space* s, uint64_t row0, uint64_t n, hipStream_t st, bool
     }
     HIP_TRY(hipMemcpyAsync(u8, s->i8.dUnsafe8.p, sizeof(u8), hipMemcpyDeviceToHost, st));
   }
-  {
-    int rcs = sync_stream(s, st);
-    if (rcs) return rcs;
-  }
+  if (int rcs = sync_stream(s, st)) return rcs;
   // (before the caller's release store of the row count: a search that sees these rows sees these counts)
   s->h_unsafe.store(u, std::memory_order_relaxed);
   s->h_unsafe8.store(u8[0], std::memory_order_relaxed);
@@ -177,221 +124,300 @@ int refresh_scan16(ehx_space* s, uint64_t row0, uint64_t n, hipStream_t st, bool
   return EHX_OK;
 }
 
+// ---- the three landers: each puts rows into dX on stream `st` and does nothing else.  The prepare half of each (and
+// prepare_permutation) does every allocation and every fallible step that does not depend on the rows; a caller runs all
+// prepare halves before the first row lands. ----
 
-}  // namespace ehx_impl
+// Host rows go up through pinned staging in slabs (fp16 spaces: rounded to binary16 while they are staged).  Two staging
+// halves, ping-pong: slab i is copied into its half (by up to four host threads — one core moves ~8 GB/s, a 25-MB chunk
+// of copy.go's 8192 x 768 rows would spend 3 ms there) while slab i-1 is on the wire.
+static size_t host_slab_rows(const ehx_space* s, size_t n) { return std::max<size_t>(1, std::min<size_t>(n, (8u << 20) / ((size_t)s->dims * s->esz))); }
+static size_t host_half_bytes(const ehx_space* s, size_t n) { return (host_slab_rows(s, n) * s->dims * s->esz + 255) & ~(size_t)255; }
 
-extern "C" {
+static int land_host(ehx_space* s, hipStream_t st, const WriteBatch& b, const float* rows) {
+  const size_t row_bytes = (size_t)s->dims * s->esz, slab_rows = host_slab_rows(s, b.n), half_bytes = host_half_bytes(s, b.n);
+  size_t slab = 0;
+  for (size_t i0 = 0; i0 < b.n; i0 += slab_rows, ++slab) {
+    const size_t m = std::min(slab_rows, b.n - i0);
+    const uint64_t* ids = b.ids + i0;
+    char* stage = (char*)s->wr.hStage.p + (slab & 1) * half_bytes;
+    if (slab >= 2) HIP_TRY(hipEventSynchronize(s->wr.sev[slab & 1]));  // the upload that last used this half
+    stage_rows(stage, rows + i0 * s->dims, m * s->dims, s->x_half);
+    // a slab that is one run of ids (it can be, inside a batch that is not) -> one 2D copy; otherwise row by row
+    if (is_dense_run(ids, m)) {
+      HIP_TRY(hipMemcpy2DAsync(s->xrow(ids[0]), (size_t)s->ld * s->esz, stage, row_bytes, row_bytes, m, hipMemcpyHostToDevice, st));
+    } else {
+      for (size_t i = 0; i < m; ++i)
+        HIP_TRY(hipMemcpyAsync(s->xrow(ids[i]), stage + i * row_bytes, row_bytes, hipMemcpyHostToDevice, st));
+    }
+    HIP_TRY(hipEventRecord(s->wr.sev[slab & 1], st));
+  }
+  return EHX_OK;   // (the caller waits for the stream before it returns: both halves are free again then)
+}
+
+// Device rows are scattered by one kernel.  A batch that is not a run needs the duplicate rule (last_writers) in a list
+// on the device; `dst_rows` lives in the caller's frame until the stream is drained (DrainUnlessOk).
+static int prepare_device(ehx_space* s, const WriteBatch& b, const RowSource& src, std::vector<uint64_t>* dst_rows) {
+  if (b.n > 0xFFFFFFFFull) return fail(EHX_EINVAL, "too many rows in one call: %zu", b.n);
+  if (!b.dense_run) {
+    dst_rows->resize(b.n);
+    last_writers(b.ids, b.n, dst_rows->data());
+    if (int rc = s->wr.dDstRows.ensure(b.n)) return rc;
+  }
+  return src.idx ? s->wr.dSrcIdx.ensure(b.n) : EHX_OK;
+}
+
+static int land_device(ehx_space* s, hipStream_t st, const WriteBatch& b, const RowSource& src, const std::vector<uint64_t>& dst_rows) {
+  // the rows are complete when `ready` is: the writers' stream waits for the event, the producer's is not drained
+  HIP_TRY(hipStreamWaitEvent(st, src.ready, 0));
+  // (pageable host memory: the runtime stages it before the call returns)
+  if (!b.dense_run) HIP_TRY(hipMemcpyAsync(s->wr.dDstRows.p, dst_rows.data(), b.n * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+  if (src.idx) HIP_TRY(hipMemcpyAsync(s->wr.dSrcIdx.p, src.idx, b.n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  ScatterRowsArgs a = {};
+  a.src = src.dev;
+  a.src_half = src.dtype == EHX_DTYPE_F16;
+  a.src_idx = src.idx ? s->wr.dSrcIdx.p : nullptr;
+  a.dst_row = b.dense_run ? nullptr : s->wr.dDstRows.p;
+  a.row0 = b.ids[0];
+  a.X = s->rows.dX.p;
+  a.ld = s->ld;
+  a.dims = s->dims;
+  a.x_half = (uint32_t)s->x_half;
+  a.n = (uint32_t)b.n;
+  HIP_TRY(launch_scatter_rows(a, st));
+  return EHX_OK;
+}
+
+// Rows row0, row0 + stride, ... of dataset `seed` into rows [old_n, old_n + n) of a space grown for them.  Order: the one
+// allocation first (binary16 spaces generate fp32 slabs of 65 536 rows and round them into the rows), then the launches.
+static int land_generated(ehx_space* s, hipStream_t st, uint64_t old_n, uint64_t n, uint64_t seed, uint64_t row0, int normalize,
+                          uint64_t stride, uint32_t latent) {
+  if (!s->x_half) {
+    HIP_TRY(launch_gen_rows(seed, row0, n, s->dims, s->ld, normalize, (float*)s->xrow(old_n), st, stride, latent));
+    return EHX_OK;
+  }
+  const uint64_t slab = 1u << 16;
+  DevBuf<float> tmp;
+  if (int rc = tmp.ensure(std::min<uint64_t>(slab, n) * s->ld)) return rc;
+  for (uint64_t r0 = 0; r0 < n; r0 += slab) {
+    const uint64_t m = std::min<uint64_t>(slab, n - r0);
+    HIP_TRY(launch_gen_rows(seed, row0 + r0 * stride, m, s->dims, s->ld, normalize, tmp.p, st, stride, latent));
+    HIP_TRY(launch_store_rows_f16(tmp.p, s->ld, nullptr, old_n + r0, m, s->dims, s->ld, (__half*)s->rows.dX.p, st));
+  }
+  HIP_TRY(hipStreamSynchronize(st));   // (the slab is released with this frame)
+  return EHX_OK;
+}
+
+// ---- the one tail behind the landers ----
+
+// A single-copy graph space (x_perm) keeps its rows in the search copy's block order: rows land raw and are permuted in
+// place.  While committed rows sit there raw the space must not be left to searches: a failure inside this guard's life —
+// from "the first row may land" to "permutation complete" — poisons the space.
+struct RawRowsGuard {
+  ehx_space* s;
+  bool armed;
+  RawRowsGuard(ehx_space* s_, const WriteBatch& b) : s(s_), armed(s_->x_perm && b.touches_committed) {}
+  ~RawRowsGuard() { if (armed) s->poisoned.store(true); }
+};
+
+// the id list of the permutation of a batch that is not a run: sorted, unique (the permutation is its own inverse: a row
+// written twice in a batch is permuted once), and its device buffer
+static int prepare_permutation(ehx_space* s, const WriteBatch& b, std::vector<uint64_t>* perm_ids) {
+  if (!s->x_perm || b.dense_run) return EHX_OK;
+  perm_ids->assign(b.ids, b.ids + b.n);
+  std::sort(perm_ids->begin(), perm_ids->end());
+  perm_ids->erase(std::unique(perm_ids->begin(), perm_ids->end()), perm_ids->end());
+  return s->rows.dPermIds.ensure(perm_ids->size());
+}
+
+// The rows of `b` have been enqueued on `st`: block order (single-copy graph spaces), row statistics over [lo, hi]
+// (idempotent for untouched rows in between), the derived copies with their flags, and the stream wait.  `copies_made`
+// (optional) is recorded between the last two.
+static int finish_rows(ehx_space* s, hipStream_t st, const WriteBatch& b, const std::vector<uint64_t>& perm_ids, RawRowsGuard& raw,
+                       bool exclusive, uint64_t next, hipEvent_t copies_made) {
+  if (s->x_perm) {
+    if (b.dense_run) {
+      HIP_TRY(launch_permute_blocks((float*)s->rows.dX.p, s->ld, b.lo, b.n, nullptr, st));
+    } else {
+      HIP_TRY(hipMemcpyAsync(s->rows.dPermIds.p, perm_ids.data(), perm_ids.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+      HIP_TRY(launch_permute_blocks((float*)s->rows.dX.p, s->ld, 0, perm_ids.size(), s->rows.dPermIds.p, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));  // (the list lives on the caller's frame; the rows are in block order from here on)
+    raw.armed = false;
+  }
+  HIP_TRY(launch_row_stats(s->rows.dX.p, s->x_half, b.lo, b.hi - b.lo + 1, s->dims, s->ld, s->metric, s->rows.dInv.p, s->rows.dRowp.p,
+                           s->rows.dMaxSumsq.p, st, s->x_perm ? 1 : 0));
+  if (int rc = refresh_derived_copies(s, b.lo, b.hi - b.lo + 1, st, exclusive, next)) return rc;
+  if (copies_made) HIP_TRY(hipEventRecord(copies_made, st));
+  return sync_stream(s, st);
+}
+
+void publish_keys(ehx_space* s, uint64_t old_n, std::vector<std::string>& new_keys) {
+  std::unique_lock<std::shared_mutex> kl(s->kmu);
+  for (size_t i = 0; i < new_keys.size(); ++i) s->key_to_id.emplace(new_keys[i], old_n + i);
+  for (auto& k : new_keys) s->id_to_key.push_back(std::move(k));
+}
+
+// the new row count, one release store.  An append-only writer holds no lock on the space: s->mu shared keeps a drop and a
+// re-allocation out, not the searches — the count is atomic, see ehx_internal.h (the exclusive lock this used to take starved
+// behind two pipelined search callers: 63 ms per chunk at 12.5 M x 1536 under search).  Else s->mu is held exclusively.
+static int publish_rows(ehx_space* s, uint64_t next, bool append_only) {
+  std::shared_lock<std::shared_mutex> pl(s->mu, std::defer_lock);
+  if (append_only) pl.lock();
+  if (append_only && s->dropped) return fail(EHX_ENOTFOUND, "Not found");
+  s->n.store(next, std::memory_order_release);
+  return EHX_OK;
+}
+
+// The published rows of `b` join the graph in call order (ANNIndex::set -> addPoint, index.cc:36): a fresh id is an
+// insertion, a known id hnswlib's update-in-place (graph_update: updatePoint's repair of the row's links).  Rows that are
+// all appended join in graph_insert's concurrent rounds instead — hnswlib's multi-threaded add_items (SURVEY A.7;
+// offlinehub.py:89): the generator's always, a Set's when ehx_params.build_batch > 1 was given explicitly.
+static int join_graph(ehx_space* s, const WriteBatch& b, uint64_t old_n, uint64_t next) {
+  if (s->params.mode != EHX_MODE_GRAPH) return EHX_OK;
+  if (s->g_n != old_n || s->params.build_batch == 0xFFFFFFFFu) {
+    s->g_stale_updates += b.n - (next - old_n);
+    return EHX_OK;
+  }
+  if (int rc = graph_ensure_arrays(s)) return rc;
+  if (b.all_appended && (!b.ids || s->params.build_batch > 1)) return graph_insert(s, old_n, b.n, s->params.build_batch);
+  for (size_t i = 0; i < b.n; ++i)
+    if (int rc = b.ids[i] >= s->g_n ? graph_insert(s, b.ids[i], 1, 1) : graph_update(s, (uint32_t)b.ids[i])) return rc;
+  return EHX_OK;
+}
+
+// ---- the callers ----
+
+// rows `src[i]` -> row b.ids[i] of the space (ids < next; ids >= s->n are appended, dense), then the tail; finally publishes
+// the keys (new_keys, in id order from s->n; nullptr: a shard, whose parent keeps them) and the new row count `next`.
+//   append_only = false: the caller holds s->mu exclusively (rows may be rewritten in place, graphs change).
+//   append_only = true : flat spaces, b.all_appended.  The caller holds s->wmu only: searches keep running while the rows
+//     are landed, described and copied BEYOND the published row count (every kernel masks rows >= n), on the writers' stream.
+// What holds on this path, each in one place:
+//   1. A batch that rewrites in place first makes the writers' stream wait for the searches in flight and for the gathers of
+//      ehx_get_by_ids_device (by_ev); an append-only batch and the generator wait for neither.  refresh_derived_copies
+//      (exclusive) keeps its own wait before it re-makes straddling int8 tiles.
+//   2. An append-only batch takes s->mu exclusively only to grow, re-checking `dropped`; it publishes keys under kmu with
+//      s->mu shared, then the row count by a release store under s->mu shared after a `dropped` check.  Keys before count.
+//   3. Nothing fallible that is independent of the rows happens after the first row may have landed: every prepare half
+//      runs first.  (A failure after committed rows landed raw in a permuted store poisons the space: RawRowsGuard.)
+//   4. The unsafe-row and margin flags are stored (refresh_derived_copies) before the release store of the row count.
+//   5. DrainUnlessOk on the writers' stream covers a device source from the first enqueue to the final stream wait (its
+//      lists are uploaded from this frame).
+//   6. tev[0..2] are recorded before the rows, behind the rows, and behind the derived copies; the generator records none.
+//   7. Graph rows join in call order (join_graph), after the row count is published.
+int write_rows(ehx_space* s, const WriteBatch& b, uint64_t next, const RowSource& src, std::vector<std::string>* new_keys,
+               bool append_only) {
+  if (s->frozen) return fail(EHX_EIMMUTABLE, "Cannot write to immutable space");
+  HIP_TRY(hipSetDevice(s->device));
+  hipStream_t ws = s->wr.wstream ? s->wr.wstream : s->stream;
+  int rc;
+  if (!append_only) {
+    if ((rc = wait_searches_in_flight(s, ws))) return rc;
+    if (s->by.by_ev) HIP_TRY(hipStreamWaitEvent(ws, s->by.by_ev, 0));
+  }
+  const uint64_t old_n = s->n;
+  {
+    std::unique_lock<std::shared_mutex> gl(s->mu, std::defer_lock);
+    if (append_only && next >= s->cap) gl.lock();  // the arrays move: no search may be running
+    if (gl && s->dropped) return fail(EHX_ENOTFOUND, "Not found");
+    if ((rc = ensure_rows(s, next))) return rc;
+  }
+  std::vector<uint64_t> perm_ids, dst_rows;
+  if (src.host && (rc = ensure_stage(s, 2 * host_half_bytes(s, b.n)))) return rc;
+  if ((rc = prepare_permutation(s, b, &perm_ids))) return rc;
+  if (s->wr.timed) HIP_TRY(hipEventRecord(s->wr.tev[0], ws));
+  DrainUnlessOk drain{ws, src.host != nullptr};
+  if (src.dev && (rc = prepare_device(s, b, src, &dst_rows))) return rc;
+  {
+    RawRowsGuard raw(s, b);
+    if ((rc = src.host ? land_host(s, ws, b, src.host) : land_device(s, ws, b, src, dst_rows))) return rc;
+    if (s->wr.timed) HIP_TRY(hipEventRecord(s->wr.tev[1], ws));
+    if ((rc = finish_rows(s, ws, b, perm_ids, raw, !append_only, next, s->wr.timed ? s->wr.tev[2] : nullptr))) return rc;
+  }
+  drain.ok = true;   // (nothing of this call is in flight any more)
+  // commit: the rows are resident and described — the keys first, under their own lock, then the row count
+  if (new_keys) {
+    std::shared_lock<std::shared_mutex> rl(s->mu, std::defer_lock);
+    if (append_only) rl.lock();  // (shared: keeps a drop out, not the searches)
+    if (append_only && s->dropped) return fail(EHX_ENOTFOUND, "Not found");
+    publish_keys(s, old_n, *new_keys);
+  }
+  if ((rc = publish_rows(s, next, append_only))) return rc;
+  return join_graph(s, b, old_n, next);
+}
 
 static int set_batch_locked(ehx_space* s, size_t n, const char* const* keys, const size_t* klens, const RowSource& src) {
+  if (is_parent(s)) return sharded_set_batch(s, n, keys, klens, src);
   if (s->frozen) return fail(EHX_EIMMUTABLE, "Cannot write to immutable space");
   std::vector<uint64_t> ids;
   std::vector<std::string> new_keys;
   uint64_t next = 0;
   resolve_keys(s, n, keys, klens, &ids, &next, &new_keys);
-  return write_rows_locked(s, n, ids, next, src, &new_keys);
+  return write_rows(s, write_batch(ids.data(), n, s->n), next, src, &new_keys, false);
 }
 
-// every key of the batch is new and distinct: the rows are a pure append
-static bool all_fresh_keys(const ehx_space* s, size_t n, const std::vector<uint64_t>& ids) {
-  for (size_t i = 0; i < n; ++i)
-    if (ids[i] != s->n + i) return false;
-  return true;
-}
-
-// rows `src[i]` -> row ids[i] of the space (ids < next; ids >= s->n are appended, dense), then statistics, derived
-// copies, graph; finally publishes the keys (new_keys, in id order from s->n) and the new row count `next`.
-//   append_only = false: the caller holds s->mu exclusively (rows may be rewritten in place, graphs change).
-//   append_only = true : flat spaces, every id >= s->n.  The caller holds s->wmu only: searches keep running while
-//     the rows are uploaded, described and copied BEYOND the published row count (every kernel masks rows >= n),
-//     on the writers' stream; s->mu is taken exclusively just to grow the arrays (rare) and to publish.
-static int write_rows_locked(ehx_space* s, size_t n, const std::vector<uint64_t>& ids, uint64_t next, const RowSource& src,
-                             std::vector<std::string>* new_keys, bool append_only) {
-  if (s->frozen) return fail(EHX_EIMMUTABLE, "Cannot write to immutable space");
-  HIP_TRY(hipSetDevice(s->device));
-  hipStream_t ws = s->wr.wstream ? s->wr.wstream : s->stream;
-  // rows rewritten in place: in-flight device searches (enqueued without the lock being held any more) finish first
-  if (!append_only) {
-    int rcw = wait_searches_in_flight(s, ws);
-    if (rcw) return rcw;
-    // (... and the gathers of ehx_get_by_ids_device, which read the rows on their callers' streams)
-    if (s->by.by_ev) HIP_TRY(hipStreamWaitEvent(ws, s->by.by_ev, 0));
-  }
-  const uint64_t old_n = s->n;
-  int rc;
-  if (append_only && next >= s->cap) {
-    std::unique_lock<std::shared_mutex> gl(s->mu);  // the arrays move: no search may be running
-    if (s->dropped) return fail(EHX_ENOTFOUND, "Not found");
-    rc = ensure_rows(s, next);
-  } else {
-    rc = ensure_rows(s, next);
-  }
-  if (rc) return rc;
-  // upload through pinned staging in slabs; rows may be non-contiguous (updates) so copy per row
-  // (fp16 spaces: rows are rounded to binary16, round-to-nearest-even, while they are staged)
-  // Two staging halves, ping-pong: slab i is copied into its half (by up to four host threads — one core moves
-  // ~8 GB/s, a 25-MB chunk of copy.go's 8192 x 768 rows would spend 3 ms there) while slab i-1 is on the wire.
-  const size_t row_bytes = (size_t)s->dims * s->esz;
-  const size_t slab_rows = std::max<size_t>(1, std::min<size_t>(n, (8u << 20) / row_bytes));
-  const size_t half_bytes = (slab_rows * row_bytes + 255) & ~(size_t)255;
-  if (src.host && (rc = ensure_stage(s, 2 * half_bytes))) return rc;
-  uint64_t min_id = ~0ull, max_id = 0;
-  size_t slab = 0;
-  // single-copy graph space: everything fallible that does not depend on the upload happens BEFORE the first row lands
-  // (the id list of a non-contiguous batch and its device buffer); a failure after an in-place upload of committed rows
-  // poisons the space (the rows would stay in raw order inside a permuted store)
-  bool perm_run = true;
-  std::vector<uint64_t> perm_uniq;
-  bool touches_committed = false;
-  if (s->x_perm) {
-    for (size_t i = 1; i < n && perm_run; ++i) perm_run = ids[i] == ids[0] + i;
-    if (!perm_run) {
-      perm_uniq.assign(ids.begin(), ids.begin() + n);
-      std::sort(perm_uniq.begin(), perm_uniq.end());
-      perm_uniq.erase(std::unique(perm_uniq.begin(), perm_uniq.end()), perm_uniq.end());
-      if ((rc = s->rows.dPermIds.ensure(perm_uniq.size()))) return rc;
-    }
-    for (size_t i = 0; i < n && !touches_committed; ++i) touches_committed = ids[i] < old_n;
-  }
-  struct Poison {   // armed while raw rows may sit in a permuted store
-    ehx_space* s;
-    bool armed = false;
-    ~Poison() { if (armed) s->poisoned.store(true); }
-  } poison{s};
-  if (s->wr.timed) HIP_TRY(hipEventRecord(s->wr.tev[0], ws));
-  // A device source: the id list (and a shard's batch positions) before the first row lands, like the lists above; what is
-  // enqueued is drained unless the call succeeds (the lists are uploaded from this frame)
-  bool dev_run = true;
-  std::vector<uint64_t> dst_rows;
-  DrainUnlessOk dev_drain{ws};
-  dev_drain.ok = src.host != nullptr;
-  if (src.dev) {
-    if (n > 0xFFFFFFFFull) return fail(EHX_EINVAL, "too many rows in one call: %zu", n);
-    for (size_t i = 1; i < n && dev_run; ++i) dev_run = ids[i] == ids[0] + i;
-    if (!dev_run) {
-      dst_rows.resize(n);
-      last_writers(ids.data(), n, dst_rows.data());
-      if ((rc = s->wr.dDstRows.ensure(n))) return rc;
-    }
-    if (src.idx && (rc = s->wr.dSrcIdx.ensure(n))) return rc;
-    if (touches_committed) poison.armed = true;
-    // the rows are complete when `ready` is: the writers' stream waits for the event, the producer's is not drained
-    HIP_TRY(hipStreamWaitEvent(ws, src.ready, 0));
-    // (pageable host memory: the runtime stages it before the call returns)
-    if (!dev_run) HIP_TRY(hipMemcpyAsync(s->wr.dDstRows.p, dst_rows.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, ws));
-    if (src.idx) HIP_TRY(hipMemcpyAsync(s->wr.dSrcIdx.p, src.idx, n * sizeof(uint32_t), hipMemcpyHostToDevice, ws));
-    ScatterRowsArgs a = {};
-    a.src = src.dev;
-    a.src_half = src.dtype == EHX_DTYPE_F16;
-    a.src_idx = src.idx ? s->wr.dSrcIdx.p : nullptr;
-    a.dst_row = dev_run ? nullptr : s->wr.dDstRows.p;
-    a.row0 = ids[0];
-    a.X = s->rows.dX.p;
-    a.ld = s->ld;
-    a.dims = s->dims;
-    a.x_half = (uint32_t)s->x_half;
-    a.n = (uint32_t)n;
-    HIP_TRY(launch_scatter_rows(a, ws));
-    for (size_t i = 0; i < n; ++i) {
-      min_id = std::min(min_id, ids[i]);
-      max_id = std::max(max_id, ids[i]);
-    }
-  }
-  for (size_t i0 = 0; src.host && i0 < n; i0 += slab_rows, ++slab) {
-    if (touches_committed) poison.armed = true;
-    const size_t m = std::min(slab_rows, n - i0);
-    char* stage = (char*)s->wr.hStage.p + (slab & 1) * half_bytes;
-    if (slab >= 2) HIP_TRY(hipEventSynchronize(s->wr.sev[slab & 1]));  // the upload that last used this half
-    stage_rows(stage, src.host + i0 * s->dims, m * s->dims, s->x_half);
-    // contiguous run of fresh ids -> one 2D copy; otherwise row by row
-    bool contiguous = true;
-    for (size_t i = 1; i < m; ++i)
-      if (ids[i0 + i] != ids[i0] + i) { contiguous = false; break; }
-    if (contiguous) {
-      HIP_TRY(hipMemcpy2DAsync(s->xrow(ids[i0]), (size_t)s->ld * s->esz, stage, row_bytes,
-                               row_bytes, m, hipMemcpyHostToDevice, ws));
-    } else {
-      for (size_t i = 0; i < m; ++i)
-        HIP_TRY(hipMemcpyAsync(s->xrow(ids[i0 + i]), stage + i * row_bytes, row_bytes,
-                               hipMemcpyHostToDevice, ws));
-    }
-    HIP_TRY(hipEventRecord(s->wr.sev[slab & 1], ws));
-    for (size_t i = 0; i < m; ++i) {
-      min_id = std::min(min_id, ids[i0 + i]);
-      max_id = std::max(max_id, ids[i0 + i]);
-    }
-  }
-  // (the stream is waited for below, before the commit: both halves are free again when this call returns)
-  if (s->wr.timed) HIP_TRY(hipEventRecord(s->wr.tev[1], ws));
-  if (s->x_perm) {
-    // single-copy graph space: the rows just written go into the search copy's block order, in place, exactly once
-    // each (the permutation is its own inverse: a row written twice in this batch is permuted once)
-    if (perm_run) {
-      HIP_TRY(launch_permute_blocks((float*)s->rows.dX.p, s->ld, ids[0], n, nullptr, ws));
-    } else {
-      HIP_TRY(hipMemcpyAsync(s->rows.dPermIds.p, perm_uniq.data(), perm_uniq.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ws));
-      HIP_TRY(launch_permute_blocks((float*)s->rows.dX.p, s->ld, 0, perm_uniq.size(), s->rows.dPermIds.p, ws));
-    }
-    HIP_TRY(hipStreamSynchronize(ws));  // (the list lives on this stack frame; the rows are in block order from here on)
-    poison.armed = false;
-  }
-  // per-row statistics over the touched id range (idempotent for untouched rows in between)
-  HIP_TRY(launch_row_stats(s->rows.dX.p, s->x_half, min_id, max_id - min_id + 1, s->dims, s->ld, s->metric, s->rows.dInv.p,
-                           s->rows.dRowp.p, s->rows.dMaxSumsq.p, ws, s->x_perm ? 1 : 0));
-  if ((rc = refresh_scan16(s, min_id, max_id - min_id + 1, ws, !append_only, next))) return rc;
-  if (s->wr.timed) HIP_TRY(hipEventRecord(s->wr.tev[2], ws));
-  if ((rc = sync_stream(s, ws))) return rc;
-  dev_drain.ok = true;   // (nothing of this call is in flight any more)
-  // commit: the rows are resident and described — publish the keys and the new row count
-  // (the keys first, under their own lock — searches keep running — then the row count: one release store)
-  if (new_keys) {
-    std::shared_lock<std::shared_mutex> rl(s->mu, std::defer_lock);
-    if (append_only) {
-      rl.lock();  // (shared: keeps a drop out, not the searches)
+int set_batch_from(ehx_space* s, size_t n, const char* const* keys, const size_t* klens, const RowSource& src) {
+  std::lock_guard<std::mutex> wg(s->wmu);
+  std::vector<uint64_t> ids;
+  std::vector<std::string> new_keys;
+  uint64_t next = 0;
+  if (!is_parent(s) && s->params.mode == EHX_MODE_FLAT) {
+    // Streaming fast path (copy.go's BatchSet chunks, MultiSet): a batch made only of fresh keys is a pure append.
+    // The key lookup needs the lock shared only, and the upload runs with no lock on the space at all.
+    WriteBatch b;
+    {
+      std::shared_lock<std::shared_mutex> rl(s->mu);
       if (s->dropped) return fail(EHX_ENOTFOUND, "Not found");
-    }
-    std::unique_lock<std::shared_mutex> kl(s->kmu);
-    for (size_t i = 0; i < new_keys->size(); ++i) s->key_to_id.emplace((*new_keys)[i], old_n + i);
-    for (auto& k : *new_keys) s->id_to_key.push_back(std::move(k));
-  }
-  if (append_only) {
-    // (shared: keeps a drop and a re-allocation out, not the searches — the count is atomic, see ehx_internal.h; the exclusive
-    // lock this used to take starved behind two pipelined search callers: 63 ms per chunk at 12.5 M x 1536 under search)
-    std::shared_lock<std::shared_mutex> pl(s->mu);
-    if (s->dropped) return fail(EHX_ENOTFOUND, "Not found");
-    s->n.store(next, std::memory_order_release);
-  } else {
-    s->n.store(next, std::memory_order_release);   // (the caller holds the space's lock exclusively)
-  }
-  if (s->params.mode == EHX_MODE_GRAPH) {
-    // the rows join the graph one at a time, in call order (ANNIndex::set -> addPoint, index.cc:36): a fresh key is an
-    // insertion, a known key hnswlib's update-in-place (graph_update: updatePoint's repair of the row's links)
-    if (s->g_n == old_n && s->params.build_batch != 0xFFFFFFFFu) {
-      if ((rc = graph_ensure_arrays(s))) return rc;
-      // Opt-in bulk write (ehx_params.build_batch > 1 given explicitly): a batch made only of fresh keys
-      // joins the graph in concurrent rounds of up to build_batch rows — hnswlib's multi-threaded
-      // add_items (offlinehub.py:89) — instead of one row per round.
-      bool all_fresh = s->params.build_batch > 1 && next - old_n == n;
-      for (size_t i = 0; i < n && all_fresh; ++i) all_fresh = ids[i] == old_n + i;
-      if (all_fresh) return graph_insert(s, old_n, n, s->params.build_batch);
-      for (size_t i = 0; i < n; ++i) {
-        if (ids[i] >= s->g_n) {
-          if ((rc = graph_insert(s, ids[i], 1, 1))) return rc;
-        } else {
-          if ((rc = graph_update(s, (uint32_t)ids[i]))) return rc;
-        }
+      if (s->keyless) return fail(EHX_EINVAL, "a shard is written through its parent space");
+      if (!s->frozen) {
+        resolve_keys(s, n, keys, klens, &ids, &next, &new_keys);
+        b = write_batch(ids.data(), n, s->n);
       }
-    } else {
-      s->g_stale_updates += n - (next - old_n);
+    }
+    if (b.all_appended) return write_rows(s, b, next, src, &new_keys, true);
+  }
+  s->excl_waiting.fetch_add(1, std::memory_order_release);   // (searches that arrive from here on wait for this batch's turn)
+  std::unique_lock<std::shared_mutex> wl(s->mu);
+  s->excl_waiting.fetch_sub(1, std::memory_order_release);
+  if (s->dropped) return fail(EHX_ENOTFOUND, "Not found");
+  if (s->keyless) return fail(EHX_EINVAL, "a shard is written through its parent space");
+  if (s->params.mode == EHX_MODE_GRAPH && n > 1 && s->params.build_batch != 0xFFFFFFFFu) {
+    // graph mode replays a batch in call order; when it re-writes keys (known ones, or the same key
+    // twice) every row must be in HBM exactly when its turn comes, so such batches go row by row
+    resolve_keys(s, n, keys, klens, &ids, &next, &new_keys);
+    if (!write_batch(ids.data(), n, s->n).all_appended) {
+      for (size_t i = 0; i < n; ++i)
+        if (int rc = set_batch_locked(s, 1, keys + i, klens + i, src.from(i, s->dims))) return rc;
+      return EHX_OK;
     }
   }
-  return EHX_OK;
+  return set_batch_locked(s, n, keys, klens, src);
 }
 
-}  // extern "C"
-
-namespace ehx_impl {
-int write_rows_locked_fwd(ehx_space* s, size_t n, const std::vector<uint64_t>& ids, uint64_t next, const RowSource& src) {
-  return write_rows_locked(s, n, ids, next, src, nullptr);
+// rows row0, row0 + stride, ... of dataset `seed` appended to the space (locked exclusively by the caller) by the tail of
+// write_rows; the reservation is exact (grow), not ensure_rows' doubling
+int fill_synthetic_locked(ehx_space* s, uint64_t seed, uint64_t row0, uint64_t n_rows, int normalize, uint64_t stride,
+                          uint32_t latent) {
+  if (s->frozen) return fail(EHX_EIMMUTABLE, "Cannot write to immutable space");
+  if (s->implicit_n != s->n)   // (generated rows form the head of a space: their keys are their decimal row ids)
+    return fail(EHX_EINVAL, "space '%s' already holds keyed rows", s->name.c_str());
+  HIP_TRY(hipSetDevice(s->device));
+  const uint64_t old_n = s->n, next = old_n + n_rows;
+  if (next >= (1ull << 32)) return fail(EHX_EUNSUPPORTED, "a shard holds at most 2^32-1 rows");
+  int rc = grow(s, next);
+  if (rc) return rc;
+  s->implicit_keys = true;
+  const WriteBatch b = write_batch(nullptr, n_rows, old_n);
+  RawRowsGuard raw(s, b);   // (never armed: nothing committed is touched)
+  if ((rc = land_generated(s, s->stream, old_n, n_rows, seed, row0, normalize, stride, latent))) return rc;
+  if ((rc = finish_rows(s, s->stream, b, {}, raw, true, next, nullptr))) return rc;
+  if ((rc = publish_rows(s, next, false))) return rc;
+  {
+    std::unique_lock<std::shared_mutex> kl(s->kmu);
+    s->implicit_n = next;
+  }
+  return join_graph(s, b, old_n, next);
 }
 
 void last_writers(const uint64_t* ids, size_t n, uint64_t* out) {
@@ -399,6 +425,7 @@ void last_writers(const uint64_t* ids, size_t n, uint64_t* out) {
   seen.reserve(n);
   for (size_t i = n; i-- > 0;) out[i] = seen.insert(ids[i]).second ? ids[i] : ~0ull;
 }
+
 }  // namespace ehx_impl
 
 // Single-row Sets (the reference's usage: one Set per RPC / per goroutine, runner/copy.go:146-161 runs 500 at a time) are

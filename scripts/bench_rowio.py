@@ -8,6 +8,8 @@
           around one call, which returns after the rows are published), and the writers' stream's time per chunk split into
           the rows (staging + upload, or wait + scatter) and what follows (row statistics, scan copies): the test hook
           ehx_test_write_times.
+  fill    wall time of ONE fill_synthetic of --fill-rows x --dims rows into a space reserved for them, F32 and F16, on a fresh
+          space per repeat (--fill-repeats): the generator's lander and the tail it shares with the Sets.
   get     --get-rows rows of the last F32 space by a loop of get, by ONE get_batch, and by get_by_ids_device (HIP events
           around one call, median of --steps after --warmup): bytes read + written over time, beside 8 TB/s.
 
@@ -32,6 +34,8 @@ def main():
     ap.add_argument("--dims", type=int, default=768)
     ap.add_argument("--chunk", type=int, default=8192)
     ap.add_argument("--repeats", type=int, default=2)
+    ap.add_argument("--fill-rows", type=int, default=1048576)
+    ap.add_argument("--fill-repeats", type=int, default=3)
     ap.add_argument("--get-rows", type=int, default=65536)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--steps", type=int, default=20)
@@ -102,6 +106,20 @@ def main():
                     kept = sp
                 else:
                     sp.drop()
+
+    # ---- fill ----
+    for dtype, name in ((ehx.DTYPE_F32, "F32"), (ehx.DTYPE_F16, "F16")):
+        secs = []
+        for _ in range(a.fill_repeats):
+            sp = ehx.Space.unique("bench-fill", a.dims, metric=ehx.METRIC_COSINE, dtype=dtype, initial_capacity=a.fill_rows)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            sp.fill_synthetic(ehx.SEED_CORPUS, 0, a.fill_rows, True)
+            secs.append(time.perf_counter() - t0)
+            assert len(sp) == a.fill_rows
+            sp.drop()
+        emit(leg="fill", space=name, rows=a.fill_rows, dims=a.dims, metric="cosine", fill_s_median=round(statistics.median(secs), 5),
+             fill_s_min=round(min(secs), 5), fill_s_max=round(max(secs), 5), rows_per_s_median=round(a.fill_rows / statistics.median(secs)))
 
     # ---- Gets ----
     sp = kept

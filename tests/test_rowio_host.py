@@ -1,7 +1,8 @@
 """CPU-side checks of the device-resident Set and the batched Gets (ehx_set_batch_device, ehx_get_batch,
 ehx_get_by_ids_device): the declarations, the ABI that stays as it was, what the entry points answer without a device, the
-duplicate rule of the scatter (a host function behind a test hook), the resource usage of k_rowio.hip built for gfx950, and
-the argument checks of Space.set_batch_device, which run in front of the C call."""
+duplicate rule of the scatter and what a batch of row ids touches (WriteBatch; host functions behind test hooks), the
+resource usage of k_rowio.hip built for gfx950, and the argument checks of Space.set_batch_device, which run in front of
+the C call."""
 import ctypes as C
 import os
 import re
@@ -17,6 +18,7 @@ from embeddinghub_amd.space import Space
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("ehx_set_batch_device", "ehx_get_batch", "ehx_get_by_ids_device")
 HOOK = "ehx_test_last_writers"
+HOOKS = (HOOK, "ehx_test_write_batch")
 NONE = 2**64 - 1
 
 
@@ -33,8 +35,9 @@ def test_entry_points_are_declared_bound_and_exported():
 
 def test_the_duplicate_rule_hook_is_not_part_of_the_abi():
     header = open(os.path.join(ROOT, "include", "ehx.h")).read()
-    assert HOOK not in header and HOOK not in _lib.SYMBOLS
-    assert hasattr(C.CDLL(_lib.LIB_PATH), HOOK)
+    for hook in HOOKS:
+        assert hook not in header and hook not in _lib.SYMBOLS
+        assert hasattr(C.CDLL(_lib.LIB_PATH), hook)
 
 
 def test_the_entry_points_without_a_device():
@@ -77,6 +80,53 @@ def test_last_writers():
     ids = rng.integers(0, 50, 400).tolist()
     last = {v: i for i, v in enumerate(ids)}
     assert _last_writers(ids) == [v if last[v] == i else NONE for i, v in enumerate(ids)]
+
+
+def _write_batch(ids, old_n):
+    fn = C.CDLL(_lib.LIB_PATH).ehx_test_write_batch
+    fn.restype = None
+    fn.argtypes = [C.POINTER(C.c_uint64), C.c_size_t, C.c_uint64, C.POINTER(C.c_uint64)]
+    a = np.asarray(ids, dtype=np.uint64)
+    out = np.full(6, 12345, dtype=np.uint64)
+    fn(a.ctypes.data_as(C.POINTER(C.c_uint64)), len(a), old_n, out.ctypes.data_as(C.POINTER(C.c_uint64)))
+    assert out[-1] == 12345
+    return tuple(int(v) for v in out[:5])
+
+
+def _write_batch_numpy(ids, old_n):
+    """(lo, hi, dense_run, touches_committed, all_appended) restated; an empty batch: the identities of min and max, a run,
+    nothing touched, all of its (no) rows appended"""
+    a = np.asarray(ids, dtype=np.uint64)
+    if a.size == 0:
+        return (NONE, 0, 1, 0, 1)
+    dense = bool((a == a[0] + np.arange(a.size, dtype=np.uint64)).all())
+    return (int(a.min()), int(a.max()), int(dense), int((a < old_n).any()), int(dense and int(a[0]) == old_n))
+
+
+@pytest.mark.parametrize("name, ids, old_n, expect", [
+    ("empty", [], 7, (NONE, 0, 1, 0, 1)),
+    ("one id, appended", [7], 7, (7, 7, 1, 0, 1)),
+    ("one id, rewritten", [3], 7, (3, 3, 1, 1, 0)),
+    ("a dense append", list(range(100, 108)), 100, (100, 107, 1, 0, 1)),
+    ("a dense run starting below old_n", list(range(96, 104)), 100, (96, 103, 1, 1, 0)),
+    ("a run with one repeat", [100, 101, 102, 102, 103], 100, (100, 103, 0, 0, 0)),
+    ("a permuted run", [100, 102, 101, 103], 100, (100, 103, 0, 0, 0)),
+    ("ids all below old_n", [5, 9, 2, 9], 100, (2, 9, 0, 1, 0)),
+    ("a mix with lo < old_n <= hi", [100, 4, 101, 102], 100, (4, 102, 0, 1, 0)),
+    ("ids beyond 2^32", [2**40, 2**40 + 1], 2**40, (2**40, 2**40 + 1, 1, 0, 1)),
+])
+def test_write_batch(name, ids, old_n, expect):
+    assert _write_batch_numpy(ids, old_n) == expect, "the restatement itself"
+    assert _write_batch(ids, old_n) == expect
+
+
+def test_write_batch_against_its_restatement():
+    rng = np.random.default_rng(5)
+    for _ in range(200):
+        old_n = int(rng.integers(0, 40))
+        n = int(rng.integers(0, 12))
+        ids = (np.arange(n) + rng.integers(0, 45)).tolist() if rng.random() < 0.5 else rng.integers(0, 60, n).tolist()
+        assert _write_batch(ids, old_n) == _write_batch_numpy(ids, old_n), (ids, old_n)
 
 
 def test_scatter_kernel_uses_no_scratch_and_spills_no_vector_registers(tmp_path):
