@@ -102,6 +102,10 @@ SYMBOLS = {
     "ehx_graph_knn_masked": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_uint32, _u32p, C.c_uint64, C.c_uint32, _u64p, _f32p, _u32p]),
     "ehx_graph_knn_masked_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint32, _vp, C.c_uint64, C.c_uint32, _vp, _vp,
                                               _vp]),
+    "ehx_graph_knn_masked_multi": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_uint32, _u32p, C.c_uint32, C.c_uint64, _u32p, C.c_uint32,
+                                             _u64p, _f32p, _u32p]),
+    "ehx_graph_knn_masked_multi_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint32, _vp, C.c_uint32, C.c_uint64, _vp,
+                                                    C.c_uint32, _vp, _vp, _vp]),
     "ehx_range": (C.c_int, [_vp, C.c_size_t, _f32p, _f32p, C.c_uint32, _u64p, _f32p, _u32p, _u64p]),
     "ehx_range_keys": (C.c_int, [_vp, C.c_size_t, _f32p, _f32p, C.c_uint32, _u64p, _f32p, _u32p, _u64p, C.c_char_p,
                                  C.c_size_t, _u64p]),

@@ -369,8 +369,8 @@ int graph_update(ehx_space* s, uint32_t id) {
 }
 
 // graph pipeline: prepared queries -> zero visited bitmaps -> one-wave-per-query search
-// `mask` (optional, batch form only): the strict walk under a row bitmap (k_graphm.hip) — the same arguments, the same
-// wait, clock and refusals; its list is graph_walk_cap(ef) long and the visit log is sized from that.
+// `mask` (optional, batch form only): the strict walk under a row bitmap, or under one per query (k_graphm.hip) — the same
+// arguments, the same wait, clock and refusals; its list is graph_walk_cap(ef) long and the visit log is sized from that.
 // `one` (optional): ONE query per call in ONE launch — the raw query sits in host-visible memory (one->q_host), the
 // kernel prepares it itself, writes ids / distances / count into host-visible memory (d_ids / d_dist / d_count then point
 // there) and publishes one->seq in one->done_flag; no prepare launch, no timing events (nothing between the host's
@@ -460,6 +460,7 @@ int knn_graph_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_que
     a.allow = mask->allow;
     a.allow_bits = (uint32_t)std::min<uint64_t>(mask->n_bits, s->n);
     a.cap_hits = mask->cap_hits;
+    a.allow_of = mask->allow_of;
   }
   if (one) {
     a.q_raw = one->q_host;

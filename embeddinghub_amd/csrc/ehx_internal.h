@@ -132,8 +132,9 @@ struct BatchClock {
 using namespace ehx_impl;
 
 // A sub-batch of a call's queries: rows idx[0, m) of the batch gathered into a dense matrix, answered on their own into
-// [m][k] lists, and those written back to the rows they belong to (ehx_call.cpp).  Three instances per space — the engine
-// chain's (ehx_space::Scratch) and the range and bitmap searches', whose re-runs may go through the engine chain themselves.
+// [m][k] lists, and those written back to the rows they belong to (ehx_call.cpp).  An instance per nesting level — the
+// engine chain's (ehx_space::Scratch), the range and bitmap searches', whose re-runs may go through the engine chain
+// themselves, and the graph walk's under a table of bitmaps, whose exact part goes through the bitmap search's.
 struct SubsetBufs {
   DevBuf<float> dFbQ, dFbDist;
   DevBuf<uint64_t> dFbIds;
@@ -505,11 +506,18 @@ struct ehx_space {
     SubsetBufs group;            // the call's queries ordered by route and mask
     HostStage host;              // host form: queries, and ids | distances | counts
     DevBuf<unsigned long long> dCapHits;   // [1] the graph walk under a bitmap: queries whose list reached its cap
+    // the graph walk under a TABLE of bitmaps (ehx_graph_knn_masked_multi*): per walked query the word offset of its bitmap
+    // from the first (GraphArgs::allow_of; its own buffer: the head of dBlock is the scan route's, rewritten per device
+    // batch), and the walked / exact parts of a batch that EHX_WALK_AUTO splits (their own: masked_answer re-runs through
+    // `group` and scan.sub)
+    DevBuf<uint32_t> dWalkOf;
+    SubsetBufs split;
   } masked;
   // test hook: queries answered on the scan route, on the exact route, queries that overflowed, scan passes launched, calls
   // (ehx_knn_masked* and ehx_knn_masked_multi* both count here)
   std::atomic<uint64_t> masked_ctr[5] = {};
-  // test hook of the graph walk under a bitmap (ehx_graph_knn_masked*): queries walked, queries answered exactly, calls
+  // test hook of the graph walk under a bitmap (ehx_graph_knn_masked*, ehx_graph_knn_masked_multi*): queries walked, queries
+  // answered exactly, calls
   std::atomic<uint64_t> graphm_ctr[3] = {};
   // exact kNN for EHX_MAX_K < k <= kLargeKScanMax on the int8 radius scan (ehx_largek.cpp; scratch_mu): flagged queries are
   // answered by the exhaustive pass
@@ -633,6 +641,7 @@ struct GraphMask {        // the walk under a row bitmap (k_graphm.hip): always 
   const uint32_t* allow;   // device words; row r is allowed iff r < n_bits and bit r & 31 of word r >> 5 is set
   uint64_t n_bits;         // already cut at the call's snapshot of the row count
   unsigned long long* cap_hits;   // device counter: queries whose list reached its cap
+  const uint32_t* allow_of;       // nullptr: ONE bitmap; else device [nq]: query i's bitmap begins allow_of[i] words into allow
 };
 // the walk list's length under a bitmap, a function of ef alone: max(ef, min(EHX_WALK_LIST_FACTOR * ef, EHX_WALK_LIST_MAX))
 inline uint32_t graph_walk_cap(uint32_t ef) {

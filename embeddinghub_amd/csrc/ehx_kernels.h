@@ -622,14 +622,17 @@ struct GraphArgs {
   uint32_t width = 1;
   // The walk under a row bitmap (k_graphm.hip; launch_graph_search_masked only): row r is allowed iff r < allow_bits and
   // bit r & 31 of allow[r >> 5] is set (allow_bits already cut at the call's row count); ef_cap is then the walk list's
-  // length cap >= ef, and *cap_hits counts the queries whose list reached it.
+  // length cap >= ef, and *cap_hits counts the queries whose list reached it.  allow_of != nullptr: a bitmap PER QUERY —
+  // allow is a table of bitmaps, query i's begins allow_of[i] words into it (every bitmap covers allow_bits rows).
   const uint32_t* allow = nullptr;
   uint32_t allow_bits = 0;
   unsigned long long* cap_hits = nullptr;
+  const uint32_t* allow_of = nullptr;   // [nq] word offsets, or nullptr: ONE bitmap for the batch
 };
 size_t graph_lds_bytes(uint32_t ld, uint32_t ef_cap, uint32_t width = 1);
 hipError_t launch_graph_search(const GraphArgs& a, hipStream_t st);
-// the strict walk that carries a row bitmap: keys hold the row id in 30 bits (a.n <= 2^30), width is ignored
+// the strict walk that carries a row bitmap, or with a.allow_of one per query: keys hold the row id in 30 bits
+// (a.n <= 2^30), width is ignored
 hipError_t launch_graph_search_masked(const GraphArgs& a, hipStream_t st);
 
 // graph-mode insertion (k_insert.hip)

@@ -1,6 +1,6 @@
 // kNN under row bitmaps.  Exact: ehx_knn_masked (host pointers) and ehx_knn_masked_device under ONE bitmap,
 // ehx_knn_masked_multi and ehx_knn_masked_multi_device under a TABLE of bitmaps, query i under bitmap mask_of[i]; on the
-// graph path: ehx_graph_knn_masked* (the section at the end).  Row r is allowed iff r < n_bits, r is below the call's ONE
+// graph path: ehx_graph_knn_masked* and ehx_graph_knn_masked_multi* (the section at the end).  Row r is allowed iff r < n_bits, r is below the call's ONE
 // snapshot of the row count and bit r & 31 of word r >> 5 is set; the answer is ehx_knn_among's with the ascending list of
 // allowed rows, byte for byte (k_radius.hip's header has the argument), and row i of a table's answer is the one-bitmap
 // answer for query i alone under its bitmap.  One bitmap is a table of one: ONE plan (masked_plan) and ONE answer over it
@@ -319,62 +319,128 @@ int masked_host_locked(ehx_space* s, size_t nq, const float* queries, uint32_t k
   return h.out.copy_out(s->stream, out_ids, out_dist, out_count, nullptr);
 }
 
-// ---- the graph walk under the bitmap (ehx_graph_knn_masked*; k_graphm.hip has the walk, tests/filtered_walk_model.py its
-// model).  Routes: the walk — knn_graph_locked with the bitmap: the same arguments, wait, clock and refusals as an
-// unfiltered graph search; or the exact answer above, byte for byte ehx_knn_masked_device's.  EHX_WALK_AUTO compacts the
-// bitmap first (one wait) and walks iff allowed rows * EHX_WALK_LIST_FACTOR >= the rows the bitmap covers: below that share
-// a list of cap = FACTOR * ef entries cannot hold ef allowed ones and the walk degenerates (MEASURED: the exact route
-// overtakes the walk between shares 1 / 11 and 1 / 14, scripts/bench_graph_masked.py, profiles/graph_masked_bench.jsonl;
-// include/ehx.h has the figures beside the constant).  A flat space has no graph: the exact route. ----
-int graphm_check(const ehx_space* s, size_t nq, uint32_t k, const void* q, const void* mask, uint64_t n_bits, uint32_t route,
-                 const void* o_ids, const void* o_dist, const void* o_cnt) {
-  if (int rc = masked_check(s, nq, k, q, mask, n_bits, o_ids, o_dist, o_cnt)) return rc;
+// ---- the graph walk under bitmaps (ehx_graph_knn_masked*: ONE bitmap; ehx_graph_knn_masked_multi*: a table, query i under
+// bitmap mask_of[i]; k_graphm.hip has the walk, tests/filtered_walk_model.py its model).  One bitmap is a table of one: ONE
+// function (graphm_locked) serves both.  Routes: the walk — knn_graph_locked with the bitmaps: the same arguments, wait,
+// clock and refusals as an unfiltered graph search; or the exact answer above, byte for byte ehx_knn_masked_multi_device's.
+// EHX_WALK_AUTO compacts the bitmaps first (one wait) and decides PER MASK: its queries are walked iff its allowed rows *
+// EHX_WALK_LIST_FACTOR >= the rows the bitmaps cover: below that share a list of cap = FACTOR * ef entries cannot hold ef
+// allowed ones and the walk degenerates (MEASURED: the exact route overtakes the walk between shares 1 / 11 and 1 / 14,
+// scripts/bench_graph_masked.py, profiles/graph_masked_bench.jsonl; include/ehx.h has the figures beside the constant).
+// A batch of a table may therefore be mixed: its walked queries take ONE walk launch, the others ONE masked_answer over the
+// same plan, each part gathered and scattered back (masked.split); a batch that is all walk or all exact is answered in
+// place.  A flat space has no graph: the exact route. ----
+int check_route(uint32_t route) {
   if (route != EHX_WALK_AUTO && route != EHX_WALK_GRAPH && route != EHX_WALK_EXACT)
     return fail(EHX_EINVAL, "route %u is none of EHX_WALK_AUTO, EHX_WALK_GRAPH, EHX_WALK_EXACT", route);
   return EHX_OK;
 }
 
-int graphm_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, const uint32_t* d_mask,
-                  uint64_t n_bits, uint32_t route, const ResultBlock& out) {
+int graphm_check(const ehx_space* s, size_t nq, uint32_t k, const void* q, const void* mask, uint64_t n_bits, uint32_t route,
+                 const void* o_ids, const void* o_dist, const void* o_cnt) {
+  if (int rc = masked_check(s, nq, k, q, mask, n_bits, o_ids, o_dist, o_cnt)) return rc;
+  return check_route(route);
+}
+
+int graphm_table_check(const ehx_space* s, size_t nq, uint32_t k, const void* q, const void* masks, uint32_t n_masks,
+                       uint64_t n_bits, const void* mask_of, uint32_t route, const void* o_ids, const void* o_dist,
+                       const void* o_cnt) {
+  if (int rc = masked_table_check(s, nq, k, q, masks, n_masks, n_bits, mask_of, o_ids, o_dist, o_cnt)) return rc;
+  return check_route(route);
+}
+
+// an unsharded space, locked shared, scratch_mu held, its device current; everything is enqueued on `st`.  mask_of /
+// d_mask_of: masked_plan's; neither: ONE bitmap (tab.n_masks == 1), every query under it.
+int graphm_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, const MaskTable& tab,
+                  uint64_t n_bits, const uint32_t* mask_of, const uint32_t* d_mask_of, uint32_t route, const ResultBlock& out) {
   int rc;
   if ((rc = check_not_poisoned(s))) return rc;
+  ehx_space::Masked& w = s->masked;
   s->graphm_ctr[2] += 1;
   if (s->params.mode != EHX_MODE_GRAPH) route = EHX_WALK_EXACT;
   MaskedPlan p;
   if (route != EHX_WALK_GRAPH) {
     if (route == EHX_WALK_EXACT && (rc = check_rows_fit_lds(s, "filtered search"))) return rc;   // (before anything is enqueued)
-    const MaskTable tab = {d_mask, (n_bits + 31) / 32, 1, false};
-    if ((rc = masked_plan(s, st, tab, n_bits, nq, nullptr, nullptr, &p))) return rc;
-    if (route == EHX_WALK_AUTO) route = p.n_allowed[0] * EHX_WALK_LIST_FACTOR >= p.n_eff ? EHX_WALK_GRAPH : EHX_WALK_EXACT;
+    if ((rc = masked_plan(s, st, tab, n_bits, nq, mask_of, d_mask_of, &p))) return rc;
+  } else {
+    // every query is walked: nothing is compacted.  The plan is the call's snapshot of the row count (the walk takes its own
+    // behind the refusal g_n != n; bitmaps cut at an earlier, smaller count only allow fewer rows), the bitmaps where the
+    // kernel reads them (ONE device bitmap: where it lies) and a table's mask_of on the host, checked
+    p.n_pub = s->n.load(std::memory_order_acquire);
+    p.n_eff = std::min<uint64_t>(n_bits, p.n_pub);
+    p.words = (p.n_eff + 31) / 32;
+    p.n_masks = tab.n_masks;
+    p.mask_of = mask_of;
+    p.d_maps = tab.p;
+    if ((tab.host || tab.n_masks > 1) && (rc = masked_maps(s, st, tab, p.n_eff, &p.d_maps))) return rc;
+    if (d_mask_of) {
+      p.mask_of_read.resize(nq);
+      HIP_TRY(hipMemcpyAsync(p.mask_of_read.data(), d_mask_of, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      p.mask_of = p.mask_of_read.data();
+      if ((rc = check_mask_of(p.mask_of, nq, tab.n_masks))) return rc;
+    }
   }
-  if (route == EHX_WALK_EXACT) {
-    if ((rc = check_rows_fit_lds(s, "filtered search"))) return rc;   // (EHX_WALK_AUTO: known only now)
-    s->graphm_ctr[1] += nq;
-    return masked_answer(s, st, nq, d_queries, k, p, out);
+  // the route of every mask, and of every query through its mask
+  bool walks[kMaskedMaxMasks];
+  for (uint32_t m = 0; m < tab.n_masks; ++m)
+    walks[m] = route == EHX_WALK_GRAPH || (route == EHX_WALK_AUTO && p.n_allowed[m] * EHX_WALK_LIST_FACTOR >= p.n_eff);
+  size_t n_walk = p.mask_of ? 0 : (walks[0] ? nq : 0);   // (one bitmap: nothing per query on the host's clock)
+  for (size_t i = 0; p.mask_of && i < nq; ++i) n_walk += walks[p.mask_of[i]];
+  if (n_walk < nq && (rc = check_rows_fit_lds(s, "filtered search"))) return rc;   // (EHX_WALK_AUTO: known only now)
+
+  // n queries under the masks of[0, n) (nullptr: mask 0), walked in ONE launch
+  auto walk = [&](size_t n, const float* q, const uint32_t* of, uint64_t* ids, float* dist, uint32_t* cnt) -> int {
+    if (int r = w.dCapHits.ensure(1, true)) return r;
+    const uint32_t* d_of = nullptr;
+    if (tab.n_masks > 1) {   // (one bitmap: the kernel that reads no offsets)
+      std::vector<uint32_t> offs(n);
+      for (size_t i = 0; i < n; ++i) offs[i] = (uint32_t)((uint64_t)of[i] * p.words);   // (masked_maps: below 2^32)
+      if (int r = w.dWalkOf.ensure(n)) return r;
+      // (pageable host memory: the runtime stages it before the call returns; masked_maps has ordered `st` behind the
+      // earlier calls that may still read the buffer)
+      HIP_TRY(hipMemcpyAsync(w.dWalkOf.p, offs.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+      d_of = w.dWalkOf.p;
+    }
+    const GraphMask gm = {p.d_maps, p.n_eff, w.dCapHits.p, d_of};
+    if (int r = knn_graph_locked(s, st, n, q, k, ids, dist, cnt, nullptr, &gm)) return r;
+    s->graphm_ctr[0] += n;
+    return EHX_OK;
+  };
+  // n queries under p.mask_of[0, n), answered exactly
+  auto exact = [&](size_t n, const float* q, uint64_t* ids, float* dist, uint32_t* cnt) -> int {
+    s->graphm_ctr[1] += n;
+    return masked_answer(s, st, n, q, k, p, ResultBlock{ids, dist, cnt, nullptr, n, k});
+  };
+  if (n_walk == nq) return walk(nq, d_queries, p.mask_of, out.ids, out.dist, out.cnt);
+  if (n_walk == 0) return exact(nq, d_queries, out.ids, out.dist, out.cnt);
+  // a mixed batch: each part gathered with its slice of mask_of, answered, scattered into its own rows — the walk first
+  // (what it refuses, it refuses before a row is written)
+  std::vector<uint32_t> iw, ix, mw, mx;   // the walked queries and the others, and their masks
+  for (size_t i = 0; i < nq; ++i) {
+    const bool wk = walks[p.mask_of[i]];
+    (wk ? iw : ix).push_back((uint32_t)i);
+    (wk ? mw : mx).push_back(p.mask_of[i]);
   }
-  if ((rc = s->masked.dCapHits.ensure(1, true))) return rc;
-  // (the walk takes its own snapshot of the row count behind the refusal g_n != n; a bitmap cut at an earlier, smaller
-  // count only allows fewer rows)
-  const GraphMask gm = {d_mask, std::min<uint64_t>(n_bits, s->n.load(std::memory_order_acquire)), s->masked.dCapHits.p};
-  if ((rc = knn_graph_locked(s, st, nq, d_queries, k, out.ids, out.dist, out.cnt, nullptr, &gm))) return rc;
-  s->graphm_ctr[0] += nq;
-  return EHX_OK;
+  if ((rc = w.split.rerun(
+           s, st, d_queries, iw, k,
+           [&](size_t n, const float* q, uint64_t* ids, float* dist, uint32_t* cnt) { return walk(n, q, mw.data(), ids, dist, cnt); },
+           out.ids, out.dist, out.cnt)))
+    return rc;
+  p.mask_of = mx.data();
+  return w.split.rerun(s, st, d_queries, ix, k, exact, out.ids, out.dist, out.cnt);
 }
 
-// host pointers in, host pointers out, on the space's stream: the bitmap's words below the row count staged in front of the
-// device form, which every route reads them from
-int graphm_host_locked(ehx_space* s, size_t nq, const float* queries, uint32_t k, const uint32_t* mask, uint64_t n_bits,
-                       uint32_t route, uint64_t* out_ids, float* out_dist, uint32_t* out_count) {
+// host pointers in, host pointers out, on the space's stream: the bitmaps' words below the row count are staged by whichever
+// route is taken (bits at or above the call's snapshot of the row count are never looked at: they are not even copied)
+int graphm_host_locked(ehx_space* s, size_t nq, const float* queries, uint32_t k, const uint32_t* masks, uint32_t n_masks,
+                       uint64_t n_bits, const uint32_t* mask_of, uint32_t route, uint64_t* out_ids, float* out_dist,
+                       uint32_t* out_count) {
   int rc;
   HostStage& h = s->masked.host;
-  // (bits at or above the row count are never looked at: only the words below it are staged.  This load of the row count
-  // is the call's snapshot: the device form's own, later, load can only be larger, and the bits it may look at end at n_eff)
-  const uint64_t n_eff = std::min<uint64_t>(n_bits, s->n.load(std::memory_order_acquire));
-  const MaskTable tab = {mask, (n_eff + 31) / 32, 1, true};
-  const uint32_t* d_mask;
   if ((rc = h.up(s->stream, queries, nq, s->dims, k, false))) return rc;
-  if ((rc = masked_maps(s, s->stream, tab, n_eff, &d_mask))) return rc;
-  if ((rc = graphm_locked(s, s->stream, nq, h.q, k, d_mask, n_eff, route, h.out))) return rc;
+  const MaskTable tab = {masks, (n_bits + 31) / 32, n_masks, true};
+  if ((rc = graphm_locked(s, s->stream, nq, h.q, k, tab, n_bits, mask_of, nullptr, route, h.out))) return rc;
   return h.out.copy_out(s->stream, out_ids, out_dist, out_count, nullptr);
 }
 
@@ -433,7 +499,8 @@ int ehx_graph_knn_masked_device(ehx_space* s, void* stream, size_t n_queries, co
   if (int rc = graphm_check(s, n_queries, k, d_queries, d_mask, n_bits, route, d_out_ids, d_out_dist, d_out_count)) return rc;
   const hipStream_t st = (hipStream_t)stream;
   return search_on_device(s, "ehx_graph_knn_masked_device", kMaskedWhy, n_queries, &st, [&] {
-    return graphm_locked(s, st, n_queries, d_queries, k, d_mask, n_bits, route,
+    const MaskTable tab = {d_mask, (n_bits + 31) / 32, 1, false};
+    return graphm_locked(s, st, n_queries, d_queries, k, tab, n_bits, nullptr, nullptr, route,
                          ResultBlock{d_out_ids, d_out_dist, d_out_count, nullptr, n_queries, k});
   });
 }
@@ -442,12 +509,37 @@ int ehx_graph_knn_masked(ehx_space* s, size_t n_queries, const float* queries, u
                          uint64_t n_bits, uint32_t route, uint64_t* out_ids, float* out_dist, uint32_t* out_count) {
   if (int rc = graphm_check(s, n_queries, k, queries, mask, n_bits, route, out_ids, out_dist, out_count)) return rc;
   return search_on_device(s, "ehx_graph_knn_masked", kMaskedWhy, n_queries, nullptr, [&] {
-    return graphm_host_locked(s, n_queries, queries, k, mask, n_bits, route, out_ids, out_dist, out_count);
+    return graphm_host_locked(s, n_queries, queries, k, mask, 1, n_bits, nullptr, route, out_ids, out_dist, out_count);
+  });
+}
+
+int ehx_graph_knn_masked_multi_device(ehx_space* s, void* stream, size_t n_queries, const float* d_queries, uint32_t k,
+                                      const uint32_t* d_masks, uint32_t n_masks, uint64_t n_bits, const uint32_t* d_mask_of,
+                                      uint32_t route, uint64_t* d_out_ids, float* d_out_dist, uint32_t* d_out_count) {
+  if (int rc = graphm_table_check(s, n_queries, k, d_queries, d_masks, n_masks, n_bits, d_mask_of, route, d_out_ids, d_out_dist,
+                                  d_out_count))
+    return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  return search_on_device(s, "ehx_graph_knn_masked_multi_device", kMaskedWhy, n_queries, &st, [&] {
+    const MaskTable tab = {d_masks, (n_bits + 31) / 32, n_masks, false};
+    return graphm_locked(s, st, n_queries, d_queries, k, tab, n_bits, nullptr, d_mask_of, route,
+                         ResultBlock{d_out_ids, d_out_dist, d_out_count, nullptr, n_queries, k});
+  });
+}
+
+int ehx_graph_knn_masked_multi(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, const uint32_t* masks,
+                               uint32_t n_masks, uint64_t n_bits, const uint32_t* mask_of, uint32_t route, uint64_t* out_ids,
+                               float* out_dist, uint32_t* out_count) {
+  if (int rc = graphm_table_check(s, n_queries, k, queries, masks, n_masks, n_bits, mask_of, route, out_ids, out_dist, out_count))
+    return rc;
+  if (int rc = check_mask_of(mask_of, n_queries, n_masks)) return rc;   // (before anything is enqueued)
+  return search_on_device(s, "ehx_graph_knn_masked_multi", kMaskedWhy, n_queries, nullptr, [&] {
+    return graphm_host_locked(s, n_queries, queries, k, masks, n_masks, n_bits, mask_of, route, out_ids, out_dist, out_count);
   });
 }
 
 // test hook, not part of the ABI: queries walked, queries answered exactly, calls, walked queries whose list reached its
-// cap (read from the device behind whatever is queued)
+// cap (read from the device behind whatever is queued); ehx_graph_knn_masked* and ehx_graph_knn_masked_multi* both count here
 int ehx_test_graph_masked_counters(ehx_space* s, uint64_t out[4]) {
   for (int i = 0; i < 3; ++i) out[i] = s ? s->graphm_ctr[i].load(std::memory_order_relaxed) : 0;
   out[3] = 0;

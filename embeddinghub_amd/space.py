@@ -464,6 +464,39 @@ class Space:
         check(self._L.ehx_graph_knn_masked_device(self._h, C.c_void_p(stream or 0), nq, _ptr(d_queries), k, _ptr(d_mask),
                                                   int(n_bits), int(route), _ptr(d_ids), _ptr(d_dist), _ptr(d_count)))
 
+    # ---- ... under a table of row bitmaps, one per query ----
+    def graph_knn_masked_multi(self, queries, k, allows, mask_of, n_bits=None, route=_lib.WALK_AUTO):
+        """graph_knn_masked with a bitmap per query (ehx_graph_knn_masked_multi): query i is searched under
+        allows[mask_of[i]] in one walk launch, and row i of the answer is graph_knn_masked's for that query, bitmap and route.
+        WALK_AUTO decides per bitmap, so one batch may hold walked (approximate) and exact rows.  allows / mask_of / n_bits as
+        knn_masked_multi.  -> ids [nq,k] u64, dist [nq,k] f32, count [nq] u32."""
+        q, pq = _f32(queries)
+        q = q.reshape(-1, self.dims)
+        nq = q.shape[0]
+        words, n_masks, n_bits = marshal_mask_table(allows, n_bits)
+        of = np.ascontiguousarray(np.asarray(mask_of).reshape(-1), dtype=np.uint32)
+        if of.shape[0] != nq:
+            raise ValueError("expected %d mask_of entries, got %d" % (nq, of.shape[0]))
+        (ids, dist, cnt), out = _results(nq, k)
+        check(self._L.ehx_graph_knn_masked_multi(self._h, nq, pq, k,
+                                                 words.ctypes.data_as(C.POINTER(C.c_uint32)) if n_bits else None, n_masks,
+                                                 n_bits, of.ctypes.data_as(C.POINTER(C.c_uint32)), int(route), *out))
+        return ids[:, :k], dist[:, :k], cnt
+
+    def graph_knn_masked_multi_device(self, d_queries, k, d_masks, n_masks, n_bits, d_mask_of, d_ids, d_dist, d_count,
+                                      route=_lib.WALK_AUTO, stream=None):
+        """graph_knn_masked_multi without anything leaving the device: tensors as knn_masked_multi_device's."""
+        nq = d_queries.shape[0] if hasattr(d_queries, "shape") else None
+        if nq is None:
+            raise ValueError("pass torch tensors (queries [nq, dims], mask words, mask_of)")
+        if hasattr(d_masks, "numel") and d_masks.numel() < int(n_masks) * ((int(n_bits) + 31) // 32):
+            raise ValueError("%d mask words hold fewer than %d bitmaps of n_bits = %d bits" % (d_masks.numel(), n_masks, n_bits))
+        if hasattr(d_mask_of, "numel") and d_mask_of.numel() < nq:
+            raise ValueError("%d mask_of entries for %d queries" % (d_mask_of.numel(), nq))
+        check(self._L.ehx_graph_knn_masked_multi_device(self._h, C.c_void_p(stream or 0), nq, _ptr(d_queries), k, _ptr(d_masks),
+                                                        int(n_masks), int(n_bits), _ptr(d_mask_of), int(route), _ptr(d_ids),
+                                                        _ptr(d_dist), _ptr(d_count)))
+
     # ---- range search (every row within a radius) ----
     def _range_args(self, queries, radius, max_results):
         q, pq = _f32(queries)

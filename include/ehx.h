@@ -309,6 +309,12 @@ int ehx_knn_masked_multi(ehx_space* s, size_t n_queries, const float* queries, u
  * copies.  mask has ceil(n_bits / 32) words. */
 int ehx_graph_knn_masked(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, const uint32_t* mask,
                          uint64_t n_bits, uint32_t route, uint64_t* out_ids, float* out_dist, uint32_t* out_count);
+/* Graph search under a table of row bitmaps, one per query, from host pointers: ehx_graph_knn_masked_multi_device (below:
+ * the contract) plus the H2D / D2H copies.  masks has n_masks * ceil(n_bits / 32) words, mask_of n_queries entries; mask_of
+ * is checked here, before anything is enqueued. */
+int ehx_graph_knn_masked_multi(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, const uint32_t* masks,
+                               uint32_t n_masks, uint64_t n_bits, const uint32_t* mask_of, uint32_t route, uint64_t* out_ids,
+                               float* out_dist, uint32_t* out_count);
 /* Exact range search from host pointers: ehx_range_device (below: the contract) plus the H2D / D2H copies.  radius has
  * n_queries entries; out_total may be NULL. */
 int ehx_range(ehx_space* s, size_t n_queries, const float* queries, const float* radius, uint32_t max_results,
@@ -440,6 +446,31 @@ int ehx_knn_masked_multi_device(ehx_space* s, void* stream, size_t n_queries, co
 int ehx_graph_knn_masked_device(ehx_space* s, void* stream, size_t n_queries, const float* d_queries, uint32_t k,
                                 const uint32_t* d_mask, uint64_t n_bits, uint32_t route, uint64_t* d_out_ids,
                                 float* d_out_dist, uint32_t* d_out_count);
+/* ehx_graph_knn_masked_device under a TABLE of row bitmaps, one per query: a micro-batch whose requests carry different
+ * tenant, ACL or category filters, walked in ONE launch — one wavefront per query, each under its own bitmap — instead of
+ * one ehx_graph_knn_masked_device call per distinct filter.  The table is ehx_knn_masked_multi_device's: d_masks holds
+ * n_masks <= 64 bitmaps, dense, [n_masks][ceil(n_bits / 32)] words; query i is searched under bitmap d_mask_of[i].
+ * Row i of the answer is, byte for byte (ids, distance bytes, count, the sentinels beyond it), what
+ * ehx_graph_knn_masked_device returns for query i alone under bitmap d_mask_of[i] with the same route; the call takes ONE
+ * snapshot of the row count, and bits at or above it are never looked at.  With n_masks == 1 the call equals
+ * ehx_graph_knn_masked_device.
+ * route: EHX_WALK_GRAPH walks every query; EHX_WALK_EXACT, and any valid route on a flat space, gives
+ * ehx_knn_masked_multi_device's answer; EHX_WALK_AUTO decides PER BITMAP by ehx_graph_knn_masked_device's rule (allowed
+ * rows of that bitmap * EHX_WALK_LIST_FACTOR >= the rows the bitmaps cover), so a batch may be MIXED: the queries of the
+ * walked bitmaps go through one walk launch, the queries of the others through one exact answer
+ * (ehx_knn_masked_multi_device's, over the same compaction), and every answer lands in its own row — approximate where
+ * walked, exact elsewhere, as the one-bitmap call states.
+ * Errors as ehx_graph_knn_masked_device and ehx_knn_masked_multi_device, with their codes: n_masks == 0 with
+ * n_queries > 0, a NULL d_mask_of, an invalid route: EHX_EINVAL; n_masks > 64: EHX_EUNSUPPORTED; an entry of d_mask_of at
+ * or above n_masks: EHX_EINVAL with the outputs unwritten, on every route (d_mask_of is read back — the call's one wait,
+ * shared with the allowed counts where a route needs them — and checked before anything writes the outputs);
+ * n_queries == 0: EHX_OK.  A NULL space is refused (EHX_EINVAL) before the device is looked for.
+ * Completion as for ehx_graph_knn_masked_device, except that every route has waited once (for d_mask_of).
+ * ehx_stats counts every query once; ehx_graph_counters the walked queries' work only.  DESIGN.md §e.17. */
+int ehx_graph_knn_masked_multi_device(ehx_space* s, void* stream, size_t n_queries, const float* d_queries, uint32_t k,
+                                      const uint32_t* d_masks, uint32_t n_masks, uint64_t n_bits,
+                                      const uint32_t* d_mask_of, uint32_t route, uint64_t* d_out_ids, float* d_out_dist,
+                                      uint32_t* d_out_count);
 /* Exact range search: every row closer than a radius.  With D(q, x) the canonical distance ehx_knn reports (cosine, L2^2,
  * inner product as there), row x belongs to query i's answer iff D is not NaN and D <= d_radius[i] as a float comparison
  * (inclusive: a radius that equals a row's distance byte for byte includes that row; -Inf distances under inner product
