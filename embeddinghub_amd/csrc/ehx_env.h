@@ -38,6 +38,8 @@ struct Env {
   uint32_t stats_every = 2;       // EHX_STATS_EVERY [1, 1024]: the int8 chain brackets the scan phase of every N-th batch of a scratch set with timing events
   bool i8_groupb = true;          // EHX_I8_GROUPB=0: L2^2 spaces scan under one min B per tile (no per-group B margins)
   uint32_t i8_skew = 64;          // EHX_I8_SKEW: half-tile workgroups: start skew of a SIMD's second wave, x 64 cycles (0: none)
+  bool i8_balance = true;         // EHX_I8_BALANCE=0: the long passes split their tiles evenly over the XCDs (no share table;
+                                  // the start / finish stamps stay on), for A/B runs
   bool largek = true;             // EHX_LARGEK=0: 48 < k <= 256 stays on the paged exhaustive pass whatever the batch (A/B)
   uint32_t largek_growth = 4;     // EHX_LARGEK_GROWTH [2, 16]: rows seen by pass j + 1 / rows seen by pass j of the large-k route
   uint32_t largek_min_queries = 0;  // EHX_LARGEK_MIN_QUERIES [1, 2^24]: the route's batch-size gate, for measuring where the
@@ -115,6 +117,7 @@ inline const Env& env() {
       const long x = atol(g);
       v.i8_skew = (uint32_t)(x < 0 ? 0 : (x > 4096 ? 4096 : x));
     }
+    v.i8_balance = flag("EHX_I8_BALANCE", true);
     v.largek = flag("EHX_LARGEK", true);
     if (const char* g = str("EHX_LARGEK_GROWTH")) {
       const long x = atol(g);

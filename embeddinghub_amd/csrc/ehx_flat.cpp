@@ -328,7 +328,45 @@ static int flat_pass8(ehx_space* s, uint64_t n_pub, int set, hipStream_t st, siz
   if ((rc = i8_scan_args(s, sc.buf, p, n_pub, &a))) return rc;
   if ((rc = sc.buf.dSample8.ensure((size_t)kSampleTiles * kTileRows16 * p.q_rows))) return rc;
   if ((rc = sc.buf.dMerged8.ensure((size_t)p.q_rows * width))) return rc;
-  if ((rc = sc.buf.verdict.ensure(p.q_rows))) return rc;
+  if ((rc = sc.buf.verdict.ensure(p.q_rows, ehx_space::I8Set::kStampWords))) return rc;
+  // The LONG passes (the compile-time-slot loop, chunks of at least 64 tiles, mapped to XCDs; at 10 M x 768: pass 3 and the
+  // last) are stamped — every workgroup's start and finish, riding home behind the verdict's count — and read their tile
+  // ranges from the share planner's table (ehx_balance.h): a power-limited pass ends with its slowest XCD, so the XCDs get
+  // shares in proportion to the rates the stamps of earlier batches showed.  EHX_I8_BALANCE=0: stamps only, uniform split.
+  constexpr uint32_t kTable = kBalanceMaxChunks + 1;
+  std::vector<int> stamp_slot(passes.size(), -1);
+  sc.n_stamped = 0;
+  // (the shards of a row-sharded space keep the plain passes: G devices, G sets of XCDs, not measured)
+  if (s->ld8 % 256u == 0u && !s->keyless) {
+    const uint32_t min_tpc = s->i8_balance_min_tpc.load(std::memory_order_relaxed);
+    uint32_t off = 0;
+    for (size_t i = passes.size(); i-- > 0 && sc.n_stamped < ehx_space::I8Set::kStampedPasses;) {
+      const ScanPlan& pl = passes[i].plan;
+      if (!pl.xcd_map || pl.tiles_per_chunk < min_tpc || pl.grid > ehx_space::I8Set::kStampGrid || pl.n_chunks > kBalanceMaxChunks)
+        continue;
+      ehx_space::I8Set::StampedPass& sp = sc.stamped[sc.n_stamped];
+      sp.key = BalanceState::key_of(pl.q_tiles, pl.n_chunks, pl.tiles_per_chunk);
+      sp.grid = pl.grid;
+      sp.q_tiles = pl.q_tiles;
+      sp.n_tiles = pl.n_tiles;
+      sp.n_chunks = pl.n_chunks;
+      sp.tile0 = passes[i].tile0;
+      sp.stamp_off = off;
+      off += 2 * pl.grid;
+      double f[kXcds];
+      s->i8_balance.factors(sp.key, f);
+      // (a table the planner could not validate is not used: the kernel's own arithmetic, which sp.bounds then restates)
+      sp.table = env().i8_balance && balance_bounds(f, pl.n_tiles, pl.n_chunks, sp.bounds);
+      if (!sp.table) balance_uniform(pl.n_tiles, pl.n_chunks, sp.bounds);
+      stamp_slot[i] = (int)sc.n_stamped++;
+    }
+    if (sc.n_stamped &&
+        (rc = sc.buf.hBounds.ensure((size_t)ehx_space::I8Set::kStampedPasses * kTable, hipHostMallocCoherent | hipHostMallocMapped, true)))
+      return rc;
+    sc.buf.verdict.riding = off;
+  } else {
+    sc.buf.verdict.riding = 0;
+  }
   uint32_t* const pool_cnt = a.pool_cnt;
   uint32_t* const ovf = a.ovf;
   uint32_t* sync = sc.buf.dI8Ctl.p + 2 * (size_t)p.q_rows;
@@ -359,6 +397,17 @@ static int flat_pass8(ehx_space* s, uint64_t n_pub, int set, hipStream_t st, siz
       a.sync = sync;
       a.sync_tol = (uint32_t)sync_mode;
       if (i > 0) HIP_TRY(hipMemsetAsync(sync, 0, kSyncWordsI8 * sizeof(uint32_t), st));
+    }
+    a.bounds = nullptr;
+    a.stamps = nullptr;
+    if (stamp_slot[i] >= 0) {
+      const ehx_space::I8Set::StampedPass& sp = sc.stamped[stamp_slot[i]];
+      a.stamps = (uint64_t*)sc.buf.verdict.extra_dev() + sp.stamp_off;
+      if (sp.table) {   // (the set's batch before this one has long read its tables: the set's mutex, enqueue to outcome)
+        uint32_t* const tab = sc.buf.hBounds.p + (size_t)stamp_slot[i] * kTable;
+        std::copy(sp.bounds, sp.bounds + sp.n_chunks + 1, tab);
+        a.bounds = tab;
+      }
     }
     HIP_TRY(scan(passes[i].plan, passes[i].tile0));
     // (the last select and the re-rank are outside the timed scan phase, like flat_pass's final merge)
@@ -501,10 +550,42 @@ int i8_stage_enqueue(ehx_space* s, uint64_t n_pub, int set, hipStream_t st, hipE
   return pipelined ? v.post_and_record(st) : v.post(st);
 }
 
+// The stamps of the batch's long passes have landed with its verdict: every pass's relative XCD rates go into the space's
+// factors for its shape (the next batch planned uses them), and the final pass is kept for the test hooks.
+static void i8_balance_outcome(ehx_space* s, ehx_space::I8Set& sc) {
+  const uint64_t* const words = (const uint64_t*)sc.buf.verdict.extra_landed();
+  for (uint32_t j = sc.n_stamped; j-- > 0;) {   // (in the cascade's order: slot 0 is its final pass)
+    const ehx_space::I8Set::StampedPass& sp = sc.stamped[j];
+    const uint64_t* const stamps = words + sp.stamp_off;
+    uint32_t tiles[kXcds];
+    double rate[kXcds];
+    balance_xcd_tiles(sp.bounds, sp.n_chunks, tiles);
+    const bool ok = balance_rates(stamps, sp.grid, tiles, rate);
+    if (ok) s->i8_balance.update(sp.key, rate);
+    if (j == 0) {
+      ehx_space::I8BalanceLast& l = s->i8_balance_last;
+      std::lock_guard<std::mutex> g(l.mu);
+      ++l.batches;
+      l.grid = sp.grid;
+      l.q_tiles = sp.q_tiles;
+      l.n_tiles = sp.n_tiles;
+      l.n_chunks = sp.n_chunks;
+      l.tile0 = sp.tile0;
+      l.table = sp.table ? 1u : 0u;
+      std::copy(sp.bounds, sp.bounds + sp.n_chunks + 1, l.bounds);
+      l.stamps.assign(stamps, stamps + 2 * (size_t)sp.grid);
+      s->i8_balance.factors(sp.key, l.factors);
+      std::copy(rate, rate + kXcds, l.rate);
+    }
+  }
+  sc.n_stamped = 0;
+}
+
 int i8_stage_outcome(ehx_space* s, uint64_t n_pub, int set, hipStream_t st, size_t nq, uint32_t k, I8Outcome* o) {
   Verdict& v = s->i8set[set].buf.verdict;
   o->failed.clear();
   o->n_short = 0;
+  i8_balance_outcome(s, s->i8set[set]);
   int rc;
   if (v.read() && (rc = v.collect(st, nq, nullptr, &o->failed, &o->n_short))) return rc;
   count_scan_batch(s, nq, n_pub, k, 1);   // (the int8 scan copy)

@@ -40,6 +40,7 @@
 #include <vector>
 
 #include "../../include/ehx.h"
+#include "ehx_balance.h"
 #include "ehx_combine.h"
 #include "ehx_env.h"
 #include "ehx_kernels.h"
@@ -538,12 +539,39 @@ struct ehx_space {
       DevBuf<uint64_t> dPool, dMerged8;
       DevBuf<uint32_t> dI8Ctl;  // [q_rows] pool counts | [q_rows] overflow flags | [kSyncWordsI8] lock-step progress words
       DevBuf<uint64_t> dCnt;    // [8] epilogue counters of diagnosis builds (EHX_I8_COUNT); the set's own: nothing shared
-      Verdict verdict;          // of the set's int8 stage, on the device path and the pipelined one
+      Verdict verdict;          // of the set's int8 stage, on the device path and the pipelined one; the stamps of the
+                                // batch's long passes ride behind its count (kStampWords)
+      PinBuf<uint32_t> hBounds; // host-mapped: [kStampedPasses][kBalanceMaxChunks + 1] the share planner's tables the
+                                // batch's long passes read (ScanArgsI8::bounds); written at the enqueue, under the set's mutex
     } buf;
     BatchClock clock;              // timed: batch 0 and every EHX_STATS_EVERY-th batch of the set
     std::mutex mu;
+    // The long passes of the batch in flight (flat_pass8 -> i8_stage_outcome; the set's mutex): what each was planned with
+    // and where its stamps ride.  At most the last kStampedPasses of a cascade, each of at most kStampGrid workgroups.
+    static constexpr uint32_t kStampedPasses = 2, kStampGrid = 512;
+    static constexpr size_t kStampWords = (size_t)kStampedPasses * 2 * kStampGrid;
+    struct StampedPass {
+      uint64_t key;                // BalanceState::key_of
+      uint32_t grid, q_tiles, n_tiles, n_chunks, tile0;
+      uint32_t stamp_off;          // words into the verdict's extra block
+      bool table;                  // the kernel read `bounds` (else it computed the uniform split itself)
+      uint32_t bounds[kBalanceMaxChunks + 1];
+    } stamped[kStampedPasses];
+    uint32_t n_stamped = 0;
   };
   I8Set i8set[2];
+  // The share of every XCD in the int8 scan's long passes (ehx_balance.h): the factors per pass shape, and what the last
+  // measured batch's final pass looked like (test hooks, scripts/i8_xcd_skew.py).
+  BalanceState i8_balance;
+  std::atomic<uint32_t> i8_balance_min_tpc{64};   // a pass is stamped (and balanced) from this many tiles per chunk
+  struct I8BalanceLast {
+    std::mutex mu;
+    uint64_t batches = 0;          // measured batches so far
+    uint32_t grid = 0, q_tiles = 0, n_tiles = 0, n_chunks = 0, tile0 = 0, table = 0;
+    uint32_t bounds[kBalanceMaxChunks + 1] = {};
+    std::vector<uint64_t> stamps;  // [2 * grid]
+    double factors[kXcds] = {}, rate[kXcds] = {};   // the factors after the update; the batch's own relative rates
+  } i8_balance_last;
   std::atomic<uint64_t> ev_counter{0};   // orders the timed batches of the space's three clocks (BatchClock::counter)
   std::atomic<uint32_t> i8_next_set{0};
   std::mutex i8_enqueue_mu;  // held while ONE host batch's int8 stage is enqueued on the space's stream (not while its

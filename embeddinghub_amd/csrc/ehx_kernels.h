@@ -245,6 +245,11 @@ struct ScanArgsI8 {
   uint32_t allow_bits = 0;          // row id is >= allow_bits or whose bit is clear is dropped before it takes a pool slot
   uint32_t allow_per_query = 0;     // 1: a bitmap per query (ehx_knn_masked_multi*, several masks) — allow is ONE block,
                                     // [q_tiles * 256] word offsets from its start (query q: allow[q]) | the bitmaps
+  // The flat int8 chain's long passes only (ehx_flat.cpp; the compile-time-slot loop without a bitmap): every other caller
+  // leaves both null and launches the kernels it always launched.
+  const uint32_t* bounds = nullptr;  // [n_chunks + 1] tile range of every chunk, relative to tile0 (the share planner's table,
+                                     // ehx_balance.h; host-mapped or device memory); nullptr: chunk * tiles_per_chunk
+  uint64_t* stamps = nullptr;        // [2 * grid] wall_clock64() of every workgroup before its prologue | after its last flush
 };
 // Stage-blocked layout of the int8 scan copy / query tiles: tiles of 256 rows, stages of 64 columns (bytes); one
 // (tile, stage) block is 256 rows x 64 B = 16 KiB in exactly the LDS image of the kernel (16-byte chunk c of row r

@@ -155,19 +155,26 @@ struct Stream {
 // too short).  The stage's caller posts the copy of the count behind its launches, waits in its own way — the device path
 // on the stream, the pipelined host path on `ev` (blocking-sync: the thread sleeps) — reads it, and only when it is not
 // zero collects the flags: 8 bytes and one wait per stage of a clean batch.
+// `extra` words may ride behind the count (the int8 sets' start / finish stamps, ehx_flat.cpp): the stage's kernels write
+// them, and the first `riding` of them land with the count in the ONE copy the host waits for anyway.
 struct Verdict {
-  DevBuf<unsigned long long> count;    // zeroed once; collect() clears it again
+  DevBuf<unsigned long long> count;    // [1 + extra] zeroed once; collect() clears the count again
   DevBuf<uint32_t> flags;              // [q_rows]
   PinBuf<unsigned long long> landed;   // (PINNED: a copy to pageable memory goes through a staging buffer and a copy kernel)
   Event ev;                            // post_and_record: the count has landed
+  size_t riding = 0;                   // words behind the count the next post() takes along (<= extra; the stage's caller sets it)
 
-  int ensure(size_t q_rows) {
+  // (a verdict is always ensured with the same `extra`: the words are created once and kept)
+  int ensure(size_t q_rows, size_t extra = 0) {
     int rc;
-    if ((rc = count.ensure_zeroed_once(1)) || (rc = flags.ensure(q_rows))) return rc;
-    return landed.ensure(1);
+    if ((rc = count.ensure_zeroed_once(1 + extra)) || (rc = flags.ensure(q_rows))) return rc;
+    return landed.ensure(1 + extra);
   }
+  unsigned long long* extra_dev() const { return count.p + 1; }
+  const unsigned long long* extra_landed() const { return landed.p + 1; }
   int post(hipStream_t st) {
-    HIP_TRY(hipMemcpyAsync(landed.p, count.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    const size_t words = 1 + std::min(riding, count.n ? count.n - 1 : 0);
+    HIP_TRY(hipMemcpyAsync(landed.p, count.p, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     return EHX_OK;
   }
   // (the one event of a pipelined batch: a marker of its own costs the queue another ~6 us per batch)

@@ -4,6 +4,8 @@
 //                       it: the sample form (every lower bound of the window) or a collect pass under the caller's
 //                       thresholds (the pools as the pass left them, before select256 and the re-rank reduce them)
 // tests/test_i8_device_bound.py checks the scan copy, the bound and the hit path on them.
+//   ehx_test_i8_balance_force / ehx_test_i8_balance_read   the share planner of the flat chain's long passes: forced factors,
+//                       and the bounds, stamps and factors of the last batch (tests/test_i8_balance.py)
 // ... and of the fp16 filter scan and the fp32 scan, which share the candidate-list path (k_scan_common.h):
 //   ehx_test_f16_array  a slice of one array of the fp16 scan copy, raw
 //   ehx_test_f16_pass   ONE launch of flat_scan16_kernel: the sample form (the dump, and what sample_select makes of it) or a
@@ -315,6 +317,53 @@ int ehx_test_i8_pass(ehx_space* s, uint32_t nq, const float* queries, const floa
       }
     }
   }
+  return EHX_OK;
+}
+
+// The share planner of the flat int8 chain's long passes (ehx_balance.h, flat_pass8).
+// f8 != NULL: eight factors of any non-negative size, used as they are (no clamp, no averaging) for every stamped pass of
+// the space until released; f8 == NULL: released, and the learnt factors forgotten.  min_tiles_per_chunk: from how many
+// tiles per chunk a pass is stamped and balanced (0: the default, 64) — the tests' spaces have chunks of a few tiles.
+int ehx_test_i8_balance_force(ehx_space* s, const double* f8, uint32_t min_tiles_per_chunk) {
+  int rc = hook_space(s, "ehx_test_i8_balance_force");
+  if (rc) return rc;
+  if (f8) {
+    double sum = 0.0;
+    for (uint32_t x = 0; x < kXcds; ++x) {
+      if (!(f8[x] >= 0.0) || !std::isfinite(f8[x])) return fail(EHX_EINVAL, "factor %u is not a non-negative number", x);
+      sum += f8[x];
+    }
+    if (!(sum > 0.0)) return fail(EHX_EINVAL, "all factors are zero");
+    s->i8_balance.force(f8);
+  } else {
+    s->i8_balance.reset();
+  }
+  s->i8_balance_min_tpc.store(min_tiles_per_chunk ? min_tiles_per_chunk : 64u, std::memory_order_relaxed);
+  return EHX_OK;
+}
+
+// The final pass of the last int8 batch that had a stamped pass (EHX_ENOTFOUND: none yet):
+//   out_info[8] = measured batches so far, grid, q_tiles, n_tiles, n_chunks, tile0, 1 if the kernel read the table (0: it
+//                 computed the uniform split, which out_bounds then restates), wall_clock64 ticks per millisecond
+//   out_bounds[n_chunks + 1 <= 257] tile range of every chunk, relative to tile0
+//   out_stamps[2 * grid <= 1024]    start | finish of every workgroup (workgroup b ran on XCD b & 7)
+//   out_factors[8], out_rates[8]    the shape's factors after that batch; the batch's own relative XCD rates (0: no tiles)
+int ehx_test_i8_balance_read(ehx_space* s, uint64_t* out_info, uint32_t* out_bounds, uint64_t* out_stamps, double* out_factors,
+                             double* out_rates) {
+  int rc = hook_space(s, "ehx_test_i8_balance_read");
+  if (rc) return rc;
+  if (!out_info || !out_bounds || !out_stamps || !out_factors || !out_rates) return fail(EHX_EINVAL, "NULL argument");
+  int khz = 0;
+  HIP_TRY(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, s->device));
+  ehx_space::I8BalanceLast& l = s->i8_balance_last;
+  std::lock_guard<std::mutex> g(l.mu);
+  if (l.batches == 0) return fail(EHX_ENOTFOUND, "no stamped pass yet");
+  const uint64_t info[8] = {l.batches, l.grid, l.q_tiles, l.n_tiles, l.n_chunks, l.tile0, l.table, (uint64_t)khz};
+  std::copy(info, info + 8, out_info);
+  std::copy(l.bounds, l.bounds + l.n_chunks + 1, out_bounds);
+  std::copy(l.stamps.begin(), l.stamps.end(), out_stamps);
+  std::copy(l.factors, l.factors + kXcds, out_factors);
+  std::copy(l.rate, l.rate + kXcds, out_rates);
   return EHX_OK;
 }
 

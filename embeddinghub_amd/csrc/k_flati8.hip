@@ -269,8 +269,12 @@ size_t scan_i8_lds_bytes() { return I8L<false>::kLdsBytes; }
 // registers each; a stage row's 64 bytes are ONE k-step: lane l holds bytes [16 (l >> 4), +16) of row / query l & 15 of
 // its block — one ds_read_b128 per block and stage, twelve per stage as before.  Every block gets exactly one MFMA
 // per stage.  An accumulator block holds, per lane, rows 4 (l >> 4) + 0..3 of its 16 rows for query l & 15.
-template <bool DUMP, bool REV, bool QRES = false, bool HALF = false, bool PAIR = false, int MASKED = kMaskNone>
+// TAB (the flat chain's long passes: ScanArgsI8::bounds / stamps, ehx_balance.h): the chunk's tile range comes from the share
+// planner's table — two scalar loads — and lane 0 of wave 0 stamps wall_clock64() before the prologue and after the last
+// flush.  A flag of the template, so every other caller's scans are the code they always were; nothing of it is in the tile loop.
+template <bool DUMP, bool REV, bool QRES = false, bool HALF = false, bool PAIR = false, int MASKED = kMaskNone, bool TAB = false>
 __global__ __launch_bounds__(I8L<HALF>::kThreads, 2) void flat_scan_i8_kernel(const ScanArgsI8 a) {
+  static_assert(!TAB || (REV && !DUMP && !QRES && !HALF && !PAIR && !MASKED), "TAB: the plain compile-time-slot scan only");
   static_assert(!QRES || (!REV && !DUMP), "QRES: the run-time-slot loop of the plain scan only");
   static_assert(!PAIR || (!REV && !DUMP && !QRES && !HALF), "PAIR: the run-time-slot loop of the plain scan, stages in pairs");
   static_assert(!HALF || QRES, "HALF: short rows, the query tile resident in LDS");
@@ -340,9 +344,24 @@ __global__ __launch_bounds__(I8L<HALF>::kThreads, 2) void flat_scan_i8_kernel(co
     if constexpr (MASKED) ctx->allow = a.allow;
   }
 
-  const uint32_t tile_begin = a.tile0 + chunk * a.tiles_per_chunk;
+  uint32_t tile_begin = a.tile0 + chunk * a.tiles_per_chunk;
   uint32_t tile_end = tile_begin + a.tiles_per_chunk;
   if (tile_end > a.tile0 + a.n_tiles) tile_end = a.tile0 + a.n_tiles;
+  if constexpr (TAB) {
+    if (a.bounds) {
+      // (through the CONSTANT address space, the address said to be uniform: two scalar loads, as tilep and tileg below.  The
+      // host validated the table — whole tiles, monotone, [0, n_tiles] — so an empty range is begin == end: my_tiles == 0)
+      typedef const __attribute__((address_space(4))) uint32_t* cu32p;
+      const uint64_t bv = (uint64_t)(a.bounds + chunk);
+      const uint32_t blo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)bv);
+      const uint32_t bhi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(bv >> 32));
+      const cu32p bp = (cu32p)(((uint64_t)bhi << 32) | blo);
+      tile_begin = a.tile0 + bp[0];
+      tile_end = a.tile0 + bp[1];
+      if (tile_end > a.tile0 + a.n_tiles) tile_end = a.tile0 + a.n_tiles;   // (never past the pass, whatever the table holds)
+      if (tile_begin > tile_end) tile_begin = tile_end;
+    }
+  }
   // (uniform by construction; said so, or the loop bound lives in a vector register — and, this kernel being out of
   // them, in scratch, reloaded behind an s_waitcnt vmcnt(0) once per tile)
   const uint32_t my_tiles =
@@ -619,6 +638,13 @@ __global__ __launch_bounds__(I8L<HALF>::kThreads, 2) void flat_scan_i8_kernel(co
         for (uint32_t i = 32; i <= a.skew; i += 32) __builtin_amdgcn_s_sleep(32);
         for (uint32_t i = 0; i < (a.skew & 31u); ++i) __builtin_amdgcn_s_sleep(1);
       }
+    }
+  }
+  if constexpr (TAB) {
+    // the start stamp, drained before the first DMA piece is issued: the counted waits of the stage loop see DMA pieces only
+    if (a.stamps) {
+      if (tid == 0) a.stamps[2u * blockIdx.x] = wall_clock64();
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
   }
   if (my_tiles > 0) {  // (a chunk past the end of the pass has nothing to scan and must not touch memory)
@@ -1003,6 +1029,13 @@ __global__ __launch_bounds__(I8L<HALF>::kThreads, 2) void flat_scan_i8_kernel(co
   if (lane == 0) ((uint32_t*)(smem + L::kStgCntOff))[w] = stg_n;
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   i8_flush_staging<HALF, MASKED>();
+  if constexpr (TAB) {
+    // the finish stamp: every wave of the workgroup has drained its last flush (the flush returns behind vmcnt(0))
+    if (a.stamps) {
+      __syncthreads();
+      if (tid == 0) a.stamps[2u * blockIdx.x + 1u] = wall_clock64();
+    }
+  }
 }
 
 hipError_t launch_flat_scan_i8(const ScanArgsI8& a, hipStream_t st) {
@@ -1023,7 +1056,9 @@ hipError_t launch_flat_scan_i8(const ScanArgsI8& a, hipStream_t st) {
                        (const void*)flat_scan_i8_kernel<false, false, false, false, false, kMaskPerQuery>,
                        (const void*)flat_scan_i8_kernel<false, false, true, false, false, kMaskPerQuery>,
                        (const void*)flat_scan_i8_kernel<false, false, true, true, false, kMaskPerQuery>,
-                       (const void*)flat_scan_i8_kernel<false, false, false, false, true, kMaskPerQuery>};
+                       (const void*)flat_scan_i8_kernel<false, false, false, false, true, kMaskPerQuery>,
+                       // the flat chain's long passes: tile ranges from the share planner's table, start / finish stamps
+                       (const void*)flat_scan_i8_kernel<false, true, false, false, false, kMaskNone, true>};
   if (hipError_t e = attr.ensure(fns, (int)(sizeof(fns) / sizeof(fns[0])), I8L<false>::kLdsBytes); e != hipSuccess) return e;
   if (a.ld == 0 || a.ld % kRowBI8) return hipErrorInvalidValue;
   const uint32_t grid = a.q_tiles * a.n_chunks;
@@ -1061,7 +1096,11 @@ hipError_t launch_flat_scan_i8(const ScanArgsI8& a, hipStream_t st) {
   } else {
     // short rows of at most two stages: two half-tile workgroups per CU (HALF in the kernel); EHX_I8_HALF=0: off
     const bool half_on = env().i8_half;
-    if (rev) EHX_LAUNCH_I8(false, true);
+    if (rev && (a.bounds || a.stamps))
+      hipLaunchKernelGGL((flat_scan_i8_kernel<false, true, false, false, false, kMaskNone, true>), dim3(grid),
+                         dim3(I8L<false>::kThreads), I8L<false>::kLdsBytes, st, a);
+    else if (a.bounds || a.stamps) return hipErrorInvalidValue;   // (the caller asks for them on these shapes only)
+    else if (rev) EHX_LAUNCH_I8(false, true);
     else if (qres_on && half_on && a.ld <= 2 * kRowBI8)
       hipLaunchKernelGGL((flat_scan_i8_kernel<false, false, true, true>), dim3(2 * grid), dim3(I8L<true>::kThreads),
                          I8L<true>::kLdsBytes, st, a);
