@@ -110,6 +110,10 @@ SYMBOLS = {
     "ehx_range_keys": (C.c_int, [_vp, C.c_size_t, _f32p, _f32p, C.c_uint32, _u64p, _f32p, _u32p, _u64p, C.c_char_p,
                                  C.c_size_t, _u64p]),
     "ehx_range_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp]),
+    "ehx_range_masked": (C.c_int, [_vp, C.c_size_t, _f32p, _f32p, C.c_uint32, _u32p, C.c_uint32, C.c_uint64, _u32p, _u64p, _f32p,
+                                   _u32p, _u64p]),
+    "ehx_range_masked_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp, C.c_uint32, _vp, C.c_uint32, C.c_uint64, _vp, _vp, _vp,
+                                          _vp, _vp]),
     "ehx_knn_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint32, _vp, _vp, _vp]),
     "ehx_merge_topk_device": (C.c_int, [_vp, C.c_size_t, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ehx_merge_topk_strided_device": (C.c_int, [_vp, C.c_size_t, C.c_uint32, C.c_uint32, _vp, C.c_size_t, _vp,

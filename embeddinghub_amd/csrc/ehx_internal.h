@@ -517,6 +517,23 @@ struct ehx_space {
   // test hook: queries answered on the scan route, on the exact route, queries that overflowed, scan passes launched, calls
   // (ehx_knn_masked* and ehx_knn_masked_multi* both count here)
   std::atomic<uint64_t> masked_ctr[5] = {};
+  // exact range search under row bitmaps (ehx_rangem.cpp; scratch_mu): the compaction is the bitmap search's (masked), the
+  // pools, control words and slot queries the range search's (range.dPool / dCtl / dSel); its own are the scan route's radii
+  // (NaN for the queries of a device batch the scan does not answer), every list-route slot's list, the sub-batch of the
+  // queries whose pool overflowed, and a host call's staged queries | radii and results
+  struct RangeMasked {
+    DevBuf<float> dRadius;       // [queries of a device batch]
+    DevBuf<uint32_t> dScans;     // [queries of a device batch] non-zero: the scan answers the query
+    DevBuf<uint64_t> dListOff;   // [slots] where the slot's list starts in masked.dList
+    DevBuf<uint32_t> dListLen;   // [slots] its length
+    SubsetBufs sub;
+    HostStage host;
+  } rangem;
+  // test hook: queries answered on the scan route, on the list route, queries whose pool overflowed, truncated answers, calls
+  std::atomic<uint64_t> rangem_ctr[5] = {};
+  // test hook (scripts/bench_range_masked.py's crossover sweep): 0 the cut decides; 1 every non-empty mask takes the scan
+  // route where the int8 scan serves a radius; 2 every mask takes the list route
+  std::atomic<uint32_t> rangem_route{0};
   // test hook of the graph walk under a bitmap (ehx_graph_knn_masked*, ehx_graph_knn_masked_multi*): queries walked, queries
   // answered exactly, calls
   std::atomic<uint64_t> graphm_ctr[3] = {};
@@ -869,6 +886,59 @@ bool largek_serves(const ehx_space* s, size_t nq, uint32_t k, uint64_t n_pub);
 // returns with the stream drained
 int largek_locked(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, const float* d_queries, uint32_t k,
                   uint64_t* d_ids, float* d_dist, uint32_t* d_count);
+
+// ---- ehx_range.cpp ----
+constexpr uint32_t kRangeGridTarget = 4096;   // workgroups an exact range kernel's launch aims for (16 per CU): chosen, not measured
+// The bitmaps of a filtered range search in the int8 scan's flush (RadiusScan's allow fields) and the tiles below their n_bits
+struct RangeAllow {
+  const uint32_t* allow;
+  uint32_t allow_bits;
+  bool per_query;
+  uint32_t n_tiles;
+};
+// What the int8 range stage found for a device batch: the queries it leaves to an exact path (counted[j] = 1: todo[j]'s pool
+// overflowed; else the bound does not serve it), and of the queries it answered the rows re-ranked and the truncated answers
+struct RangeI8Verdict {
+  std::vector<uint32_t> todo;
+  std::vector<uint8_t> counted;
+  uint64_t n_pairs = 0, n_trunc = 0, n_over = 0;
+};
+// ONE pass of the int8 radius scan over all tiles (allow: over the tiles its bitmaps cover, the bitmaps tested in the flush)
+// under the threshold mapped from d_radius, the survivors re-ranked, cut at the radius and emitted into o; nq <= kSideChunk
+int range_i8_stage(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, const float* d_queries, const float* d_radius,
+                   uint32_t max_results, const ResultBlock& o, const RangeAllow* allow, RangeI8Verdict* out);
+
+// ---- ehx_masked.cpp ----
+constexpr size_t kTabWords = kSideChunk;    // word offsets in front of the bitmaps of ehx_space::Masked::dBlock
+// At most this many allowed rows: the exact route of the bitmap searches
+uint64_t masked_exact_cut(uint64_t n_pub);
+int check_mask_of(const uint32_t* mask_of, size_t nq, uint32_t n_masks);   // an entry at or above n_masks: EHX_EINVAL
+// Where a call's bitmaps come from: n_masks >= 1 bitmaps of `stride` words each, in host or device memory.
+struct MaskTable {
+  const uint32_t* p;
+  uint64_t stride;
+  uint32_t n_masks;
+  bool host;
+};
+// The bitmaps of one call, compacted: the call's ONE read of the row count, the rows the bitmaps cover below it, per mask the
+// allowed rows before every tile (read back), their number and where its ascending list of allowed ids starts in
+// masked.dList, and which mask every query is searched under.
+struct MaskedPlan {
+  uint64_t n_pub = 0, n_eff = 0, words = 0;   // words: of one bitmap below the row count, and the stride between two
+  uint32_t n_tiles = 0, n_masks = 0;
+  const uint32_t* d_maps = nullptr;           // where the bitmaps live on the device (masked_maps)
+  std::vector<uint32_t> cum;                  // [n_masks][n_tiles + 1]
+  std::vector<uint64_t> n_allowed;            // [n_masks]
+  MaskedOffsets off = {};                     // list of mask m: masked.dList.p + off.off[m]
+  const uint32_t* mask_of = nullptr;          // [queries], host memory, checked; nullptr: every query is mask 0
+  std::vector<uint32_t> mask_of_read;         // ... of a table's device form
+  const uint32_t* cum_of(uint32_t m) const { return cum.data() + (size_t)m * (n_tiles + 1); }
+};
+// an unsharded space, locked shared, scratch_mu held, its device current; everything is enqueued on `st`.  mask_of: in host
+// memory and checked; or d_mask_of (a table's device form): read back with the allowed counts — the ONE wait of the
+// compaction — and checked then, the outputs unwritten; or neither: every query is mask 0 and nothing is read back for it.
+int masked_plan(ehx_space* s, hipStream_t st, const MaskTable& tab, uint64_t n_bits, size_t nq, const uint32_t* mask_of,
+                const uint32_t* d_mask_of, MaskedPlan* p);
 
 // ---- ehx_among.cpp ----
 // exact kNN among row ids on an unsharded space, locked shared, scratch_mu held, its device current (d_off == nullptr: one

@@ -516,6 +516,26 @@ uint32_t range_rerank_max_ld();   // longest row stride (floats): the pool and t
 hipError_t launch_range_rerank(const RangeRerankArgs& a, hipStream_t st);
 hipError_t launch_range_iota(uint64_t* out, uint64_t n, hipStream_t st);   // out[i] = i
 
+// exact range search under row bitmaps, the list route (k_rangem.hip): RangeArgs' slots, pools and counters, but slot j walks
+// its OWN list of row ids, ids[list_off[j] .. list_off[j] + list_len[j]) (a mask's ascending list of allowed rows), not
+// every row.  launch_range_emit then sorts and writes as it does for the unfiltered search.
+struct RangeListArgs {
+  const float* Q;            // prepared queries [*][ld] (launch_prep_queries), indexed by QUERY
+  RowsView rows;             // stored rows, any layout
+  const float* radius;       // [*] indexed by query
+  const uint32_t* sel;       // optional [n_slots]: the queries this launch answers
+  const uint64_t* ids;       // the lists' row ids; an id at or above rows.n_rows is no row and is not read
+  const uint64_t* list_off;  // [n_slots]
+  const uint32_t* list_len;  // [n_slots]
+  uint64_t* pool;            // [n_slots][kPoolCap] (canonical distance, id) keys, unsorted
+  uint32_t* pool_cnt;        // [n_slots], zero before the launch
+  uint32_t n_blocks;         // workgroups per slot, sized from the longest list: each walks its steps of the slot's list
+};
+uint32_t range_list_step_rows(const RangeListArgs& a);   // list entries one workgroup takes per step of its loop
+hipError_t launch_range_list(const RangeListArgs& a, uint32_t n_slots, hipStream_t st);
+// out[q] = scans[q] ? radius[q] : NaN — the radii the int8 scan of a device batch runs under: a NaN radius collects nothing
+hipError_t launch_range_scan_radii(const float* radius, const uint32_t* scans, uint32_t nq, float* out, hipStream_t st);
+
 // exact kNN under row bitmaps (k_masked.hip): one bitmap (ehx_knn_masked*, the graph walk's exact route) or a table, one per
 // query (ehx_knn_masked_multi*).  Compaction of the first n_bits bits of n_masks <= kMaskedMaxMasks bitmaps at once, the
 // mask a grid dimension (n_tiles = ceil(n_bits / 256) tiles of 8 words; words and bits beyond n_bits are not read).  maps:

@@ -24,6 +24,8 @@
 //                seen 256 * 16^j allowed rows (the pointwise maximum of the scanned masks' counts), so no mask sees more
 //                allowed rows in a pass than it would alone.  The queries it hands on — pool overflow, or the bound does
 //                not serve them — take the exact route under their own mask.
+// The plan, the cut between the routes and the check of mask_of are declared in ehx_internal.h: the range search under row
+// bitmaps (ehx_rangem.cpp) compacts its table with the same masked_plan.
 // n_masks <= kMaskedMaxMasks = 64: a choice (include/ehx.h says why), not a knob.
 // Entry scaffold and host staging are ehx_call.cpp's (search_shared / on_device, HostStage).
 #include "ehx_internal.h"
@@ -35,12 +37,6 @@ constexpr uint64_t kMaskedSample = 256;     // allowed rows in the sample, at mo
 constexpr uint64_t kMaskedPassGrowth = 16;  // pass j ends where kMaskedSample * 16^j allowed rows have been seen
 constexpr const char* kMaskedWhy = "filtered search over shards is not built yet";
 static_assert(kSideChunk % 256 == 0, "the offset table covers the padded query rows of one device batch");
-constexpr size_t kTabWords = kSideChunk;    // word offsets in front of the bitmaps of ehx_space::Masked::dBlock
-
-// At most this many allowed rows: the exact route.  max(1024, rows / 128), MEASURED (scripts/bench_masked.py, 1 M x 768
-// cosine, batch 1024, k = 10: the list scan costs what the scan route costs at 7 697 allowed rows, 0.77 % of the space;
-// profiles/masked_bench.jsonl, DESIGN §e.12).
-uint64_t masked_exact_cut(uint64_t n_pub) { return std::max<uint64_t>(1024, n_pub / 128); }
 
 int masked_check(const ehx_space* s, size_t nq, uint32_t k, const void* q, const void* mask, uint64_t n_bits,
                  const void* o_ids, const void* o_dist, const void* o_cnt) {
@@ -62,12 +58,6 @@ int masked_table_check(const ehx_space* s, size_t nq, uint32_t k, const void* q,
   return EHX_OK;
 }
 
-int check_mask_of(const uint32_t* mask_of, size_t nq, uint32_t n_masks) {
-  for (size_t i = 0; i < nq; ++i)
-    if (mask_of[i] >= n_masks) return fail(EHX_EINVAL, "mask_of[%zu] = %u is not below n_masks = %u", i, mask_of[i], n_masks);
-  return EHX_OK;
-}
-
 // tile ranges of the scan passes: pass j (j = 1, 2, ...; the sample is stage 0) ends at the first tile where the allowed
 // rows seen reach kMaskedSample * 16^j, the last pass takes the rest.  cum[t] = allowed rows in tiles [0, t), non-decreasing.
 std::vector<TileRange> masked_passes(const std::vector<uint32_t>& cum, uint32_t n_tiles) {
@@ -83,14 +73,6 @@ std::vector<TileRange> masked_passes(const std::vector<uint32_t>& cum, uint32_t 
   }
   return out;
 }
-
-// Where a call's bitmaps come from: n_masks >= 1 bitmaps of `stride` words each, in host or device memory.
-struct MaskTable {
-  const uint32_t* p;
-  uint64_t stride;
-  uint32_t n_masks;
-  bool host;
-};
 
 // The bitmaps of a call on the device, bitmap m at *d_maps + m * words (words: those of the n_eff rows below the row count):
 // ONE device bitmap where it lies; host words and every table dense in masked.dBlock behind the offset words.  (Host words
@@ -113,20 +95,20 @@ int masked_maps(ehx_space* s, hipStream_t st, const MaskTable& tab, uint64_t n_e
   return EHX_OK;
 }
 
-// The bitmaps of one call, compacted: the call's ONE read of the row count, the rows the bitmaps cover below it, per mask the
-// allowed rows before every tile (read back), their number and where its ascending list of allowed ids starts in
-// masked.dList, and which mask every query is searched under.
-struct MaskedPlan {
-  uint64_t n_pub = 0, n_eff = 0, words = 0;   // words: of one bitmap below the row count, and the stride between two
-  uint32_t n_tiles = 0, n_masks = 0;
-  const uint32_t* d_maps = nullptr;           // where the bitmaps live on the device (masked_maps)
-  std::vector<uint32_t> cum;                  // [n_masks][n_tiles + 1]
-  std::vector<uint64_t> n_allowed;            // [n_masks]
-  MaskedOffsets off = {};                     // list of mask m: masked.dList.p + off.off[m]
-  const uint32_t* mask_of = nullptr;          // [queries], host memory, checked; nullptr: every query is mask 0
-  std::vector<uint32_t> mask_of_read;         // ... of a table's device form
-  const uint32_t* cum_of(uint32_t m) const { return cum.data() + (size_t)m * (n_tiles + 1); }
-};
+}  // namespace
+
+namespace ehx_impl {
+
+// At most this many allowed rows: the exact route.  max(1024, rows / 128), MEASURED (scripts/bench_masked.py, 1 M x 768
+// cosine, batch 1024, k = 10: the list scan costs what the scan route costs at 7 697 allowed rows, 0.77 % of the space;
+// profiles/masked_bench.jsonl, DESIGN §e.12).
+uint64_t masked_exact_cut(uint64_t n_pub) { return std::max<uint64_t>(1024, n_pub / 128); }
+
+int check_mask_of(const uint32_t* mask_of, size_t nq, uint32_t n_masks) {
+  for (size_t i = 0; i < nq; ++i)
+    if (mask_of[i] >= n_masks) return fail(EHX_EINVAL, "mask_of[%zu] = %u is not below n_masks = %u", i, mask_of[i], n_masks);
+  return EHX_OK;
+}
 
 // an unsharded space, locked shared, scratch_mu held, its device current; everything is enqueued on `st`.  mask_of: in host
 // memory and checked; or d_mask_of (a table's device form): read back with the allowed counts — the ONE wait of the
@@ -183,6 +165,10 @@ int masked_plan(ehx_space* s, hipStream_t st, const MaskTable& tab, uint64_t n_b
   }
   return fill_early && n_tiles ? (int)EHX_OK : fill(total);   // (no tile: nothing is launched, the list is one spare entry)
 }
+
+}  // namespace ehx_impl
+
+namespace {
 
 // the exact answer over a plan: per mask the scan route where it serves, else the list scan
 int masked_answer(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, const MaskedPlan& p,

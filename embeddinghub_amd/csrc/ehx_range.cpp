@@ -6,12 +6,12 @@
 //               overflowed go on to
 //   exact path  every space: the canonical distance of every row (a graph space answers from its stored rows, its graph is
 //               not walked); a query with more than kPoolCap members is answered by the exact kNN pipeline at k = max_results.
+// The int8 path's stage (range_i8_stage) also serves the range search under row bitmaps (ehx_rangem.cpp), which hands it the
+// bitmaps for the scan's flush.
 // Entry scaffold, host staging, sub-batch re-runs: ehx_call.cpp's (search_shared / on_device, HostStage, SubsetBufs::rerun).
 #include "ehx_internal.h"
 
 namespace {
-
-constexpr uint32_t kRangeGridTarget = 4096;   // workgroups the exact kernel's launch aims for (16 per CU): chosen, not measured
 
 int range_check(const ehx_space* s, size_t nq, uint32_t max_results, const void* q, const void* radius, const void* o_ids,
                 const void* o_dist, const void* o_cnt) {
@@ -91,16 +91,26 @@ int range_exact_stage(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, c
   return range_overflow(s, st, n_pub, d_queries, over, max_results, o);
 }
 
-// The int8 path for a batch of nq queries — ONE pass of the radius scan over all tiles, the radius fixed: *todo = the
-// queries it leaves to the exact path (the bound does not serve them, or their pool overflowed: (*counted)[j] = 1 for the
-// latter).
+}  // namespace
+
+namespace ehx_impl {
+
+// The int8 path for a batch of nq queries — ONE pass of the radius scan over all tiles, the radius fixed: out->todo = the
+// queries it leaves to the exact path (the bound does not serve them, or their pool overflowed: out->counted[j] = 1 for the
+// latter).  allow (the filtered range search, ehx_rangem.cpp): the bitmaps of the scan's flush, and the tiles below their
+// n_bits — the only ones that hold a member.  The caller adds the verdict's figures to its own counters.
 int range_i8_stage(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, const float* d_queries, const float* d_radius,
-                   uint32_t max_results, const ResultBlock& o, std::vector<uint32_t>* todo, std::vector<uint8_t>* counted) {
+                   uint32_t max_results, const ResultBlock& o, const RangeAllow* allow, RangeI8Verdict* out) {
   int rc;
   if ((rc = s->range.dCtl.ensure(nq))) return rc;
-  const std::vector<TileRange> all = {{0u, (uint32_t)((n_pub + kTileRows16 - 1) / kTileRows16)}};
+  const std::vector<TileRange> all = {{0u, allow ? allow->n_tiles : (uint32_t)((n_pub + kTileRows16 - 1) / kTileRows16)}};
   RadiusScan scan;
   scan.passes = &all;
+  if (allow) {
+    scan.allow = allow->allow;
+    scan.allow_bits = allow->allow_bits;
+    scan.allow_per_query = allow->per_query;
+  }
   scan.d_word = s->range.dCtl.p;   // what the re-rank kept
   scan.rerank = [&](size_t, bool, const ScanArgsI8& a, ehx_space::I8Set& sc) {
     if (int rc2 = sc.clock.scan_end(st)) return rc2;   // (the timed scan phase is the scan alone)
@@ -123,26 +133,23 @@ int range_i8_stage(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, cons
   };
   RadiusScanOut v;
   if ((rc = i8_radius_scan(s, st, n_pub, nq, d_queries, d_radius, scan, &v))) return rc;
-  todo->clear();
-  counted->clear();
-  uint64_t n_pairs = 0, n_trunc = 0, n_over = 0;
+  *out = RangeI8Verdict();
   for (size_t q = 0; q < nq; ++q) {
     if (const uint32_t flag = v.flag[q]) {
-      todo->push_back((uint32_t)q);
-      counted->push_back(flag == 1u);
-      n_over += flag == 1u;
+      out->todo.push_back((uint32_t)q);
+      out->counted.push_back(flag == 1u);
+      out->n_over += flag == 1u;
     } else {
-      n_pairs += v.pool_cnt[q];
-      n_trunc += v.word[q] > max_results;
+      out->n_pairs += v.pool_cnt[q];
+      out->n_trunc += v.word[q] > max_results;
     }
   }
-  s->n_dist += n_pairs;
-  s->n_queries += nq - todo->size();
-  s->range_ctr[0] += nq - todo->size();
-  s->range_ctr[2] += n_over;
-  s->range_ctr[3] += n_trunc;
   return EHX_OK;
 }
+
+}  // namespace ehx_impl
+
+namespace {
 
 // an unsharded space, locked shared, scratch_mu held, its device current; everything is enqueued on `st`
 int range_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, const float* d_radius, uint32_t max_results,
@@ -153,17 +160,21 @@ int range_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries
   // the ONE read of the row count: every stage of the call answers for the same prefix
   const uint64_t n_pub = s->n.load(std::memory_order_acquire);
   const bool i8 = i8_serves_radius(s, n_pub);
-  std::vector<uint32_t> todo;
-  std::vector<uint8_t> counted;
+  RangeI8Verdict v;
   for (size_t q0 = 0; q0 < nq; q0 += kSideChunk) {
     const size_t m = std::min(kSideChunk, nq - q0);
     const float* q = d_queries + q0 * s->dims;
     const float* r = d_radius + q0;
     const ResultBlock o = out.from(q0, m);
     if (i8) {
-      if ((rc = range_i8_stage(s, st, n_pub, m, q, r, max_results, o, &todo, &counted))) return rc;
-      if (todo.empty()) continue;
-      if ((rc = range_exact_stage(s, st, n_pub, m, q, r, &todo, &counted, max_results, o))) return rc;
+      if ((rc = range_i8_stage(s, st, n_pub, m, q, r, max_results, o, nullptr, &v))) return rc;
+      s->n_dist += v.n_pairs;
+      s->n_queries += m - v.todo.size();
+      s->range_ctr[0] += m - v.todo.size();
+      s->range_ctr[2] += v.n_over;
+      s->range_ctr[3] += v.n_trunc;
+      if (v.todo.empty()) continue;
+      if ((rc = range_exact_stage(s, st, n_pub, m, q, r, &v.todo, &v.counted, max_results, o))) return rc;
     } else if ((rc = range_exact_stage(s, st, n_pub, m, q, r, nullptr, nullptr, max_results, o))) {
       return rc;
     }

@@ -537,6 +537,46 @@ class Space:
         check(self._L.ehx_range_device(self._h, C.c_void_p(stream or 0), nq, _ptr(d_queries), _ptr(d_radius), max_results,
                                        _ptr(d_ids), _ptr(d_dist), _ptr(d_count), _ptr(d_total)))
 
+    # ---- range search under row bitmaps (every ALLOWED row within a radius) ----
+    def range_masked(self, queries, radius, max_results, allows, mask_of=None, n_bits=None):
+        """range_search over the allowed rows alone (ehx_range_masked): query i is answered under allows[mask_of[i]], and
+        total counts allowed rows only.  allows: a 2-d bool array [n_masks, rows] or packed uint32 words [n_masks, words] with
+        n_bits, at most 64 bitmaps; or ONE 1-d bitmap (a table of one), under which every query is answered when mask_of is
+        None.  -> ids [nq, max_results] u64, dist [nq, max_results] f32, count [nq] u32, total [nq] u64."""
+        nq, pq, r, (ids, dist, cnt, total), out, keep = self._range_args(queries, radius, max_results)
+        a = np.asarray(allows)
+        words, n_masks, n_bits = marshal_mask_table(a[None] if a.ndim == 1 else a, n_bits)
+        of = None
+        if mask_of is not None:
+            of = np.ascontiguousarray(np.asarray(mask_of).reshape(-1), dtype=np.uint32)
+            if of.shape[0] != nq:
+                raise ValueError("expected %d mask_of entries, got %d" % (nq, of.shape[0]))
+        elif n_masks != 1:
+            raise ValueError("a table of %d bitmaps needs mask_of" % n_masks)
+        check(self._L.ehx_range_masked(self._h, nq, pq, r.ctypes.data_as(C.POINTER(C.c_float)), max_results,
+                                       words.ctypes.data_as(C.POINTER(C.c_uint32)) if n_bits else None, n_masks, n_bits,
+                                       of.ctypes.data_as(C.POINTER(C.c_uint32)) if of is not None else None, *out))
+        del keep
+        return ids[:, :max_results], dist[:, :max_results], cnt, total
+
+    def range_masked_device(self, d_queries, d_radius, max_results, d_masks, n_masks, n_bits, d_mask_of, d_ids, d_dist, d_count,
+                            d_total=None, stream=None):
+        """range_masked without anything leaving the device: torch CUDA tensors — d_queries, d_radius and the outputs as
+        range_device's, d_masks [n_masks, ceil(n_bits / 32)] packed u32 words (int32 storage), d_mask_of [nq] u32 (int32
+        storage) or None with n_masks == 1."""
+        nq = d_queries.shape[0] if hasattr(d_queries, "shape") else None
+        if nq is None:
+            raise ValueError("pass torch tensors (queries [nq, dims], radius [nq], mask words, mask_of)")
+        if hasattr(d_radius, "shape") and tuple(d_radius.shape) != (nq,):
+            raise ValueError("expected %d radii, got shape %s" % (nq, tuple(d_radius.shape)))
+        if hasattr(d_masks, "numel") and d_masks.numel() < int(n_masks) * ((int(n_bits) + 31) // 32):
+            raise ValueError("%d mask words hold fewer than %d bitmaps of n_bits = %d bits" % (d_masks.numel(), n_masks, n_bits))
+        if hasattr(d_mask_of, "numel") and d_mask_of.numel() < nq:
+            raise ValueError("%d mask_of entries for %d queries" % (d_mask_of.numel(), nq))
+        check(self._L.ehx_range_masked_device(self._h, C.c_void_p(stream or 0), nq, _ptr(d_queries), _ptr(d_radius), max_results,
+                                              _ptr(d_masks), int(n_masks), int(n_bits), _ptr(d_mask_of), _ptr(d_ids),
+                                              _ptr(d_dist), _ptr(d_count), _ptr(d_total)))
+
     def stats(self):
         st = Stats()
         check(self._L.ehx_stats(self._h, C.byref(st)))

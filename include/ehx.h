@@ -324,6 +324,13 @@ int ehx_range(ehx_space* s, size_t n_queries, const float* queries, const float*
 int ehx_range_keys(ehx_space* s, size_t n_queries, const float* queries, const float* radius, uint32_t max_results,
                    uint64_t* out_ids, float* out_dist, uint32_t* out_count, uint64_t* out_total, char* key_arena,
                    size_t arena_cap, uint64_t* key_off);
+/* Exact range search under a table of row bitmaps, one per query, from host pointers: ehx_range_masked_device (below: the
+ * contract) plus the H2D / D2H copies.  masks has n_masks * ceil(n_bits / 32) words, radius n_queries entries, mask_of
+ * n_queries entries (may be NULL with n_masks == 1: every query is under bitmap 0); mask_of is checked here, before anything
+ * is enqueued.  out_total may be NULL. */
+int ehx_range_masked(ehx_space* s, size_t n_queries, const float* queries, const float* radius, uint32_t max_results,
+                     const uint32_t* masks, uint32_t n_masks, uint64_t n_bits, const uint32_t* mask_of, uint64_t* out_ids,
+                     float* out_dist, uint32_t* out_count, uint64_t* out_total);
 
 /* ---- device-resident entry points (inputs/outputs already in HBM; `stream` is a hipStream_t
  *      passed as void*, NULL = default stream).  These are what a batching shim and bench.py
@@ -489,6 +496,28 @@ int ehx_graph_knn_masked_multi_device(ehx_space* s, void* stream, size_t n_queri
 int ehx_range_device(ehx_space* s, void* stream, size_t n_queries, const float* d_queries, const float* d_radius,
                      uint32_t max_results, uint64_t* d_out_ids, float* d_out_dist, uint32_t* d_out_count,
                      uint64_t* d_out_total);
+/* Filtered range search: every ALLOWED row closer than a radius, query i under bitmap d_mask_of[i] of a table laid out as
+ * ehx_knn_masked_multi_device's (n_masks <= 64 bitmaps of ceil(n_bits / 32) words, back to back).  One bitmap is a table of
+ * one: with n_masks == 1, d_mask_of may be NULL and every query is under bitmap 0.  Row r is allowed for query i iff
+ * r < n_bits, r is below the call's ONE acquire load of the row count and bit r & 31 of word r >> 5 of its bitmap is set.
+ * The answer is ehx_range_device's over the allowed rows alone: ordered by (distance, id), the first min(total, max_results)
+ * pairs written, d_out_count[i] that number, ehx_knn's sentinels behind them, and d_out_total[i] (may be NULL) the EXACT
+ * number of allowed rows inside the radius, whatever was cut — rows the filter excludes are never counted.  Radii and
+ * queries behave as in ehx_range_device (a NaN radius: count 0, total 0; +-Inf and non-finite queries are served).  An empty
+ * bitmap, or n_bits == 0 (d_masks may then be NULL): count 0 and total 0.  Errors: max_results 0, n_masks 0 with queries,
+ * NULL d_masks with n_bits > 0, NULL d_mask_of with n_masks > 1, other NULL arguments: EHX_EINVAL; d_mask_of[i] >= n_masks:
+ * EHX_EINVAL with the outputs unwritten (d_mask_of is read back in the compaction's one wait); max_results >
+ * EHX_MAX_K_PAGED, n_masks > 64, a row-sharded space, rows longer than 40 960 floats: EHX_EUNSUPPORTED; a dropped space:
+ * EHX_ENOTFOUND; no device: EHX_ENODEVICE.  Routes, per query through its bitmap: a bitmap that allows more than
+ * max(1024, rows / 128) rows of a flat space whose first engine is the int8 filter takes ONE pass of that scan with the
+ * bitmap tested as candidates are collected, and an exact re-rank; every other query — sparse bitmaps, other engines, graph
+ * spaces (the graph is not walked), radii the scan cannot bound — the canonical distance of every row of its bitmap's list.
+ * The call waits for the device more than once (the compaction's counts, then a verdict per batch of 2048 queries).
+ * DESIGN.md §e.18. */
+int ehx_range_masked_device(ehx_space* s, void* stream, size_t n_queries, const float* d_queries, const float* d_radius,
+                            uint32_t max_results, const uint32_t* d_masks, uint32_t n_masks, uint64_t n_bits,
+                            const uint32_t* d_mask_of, uint64_t* d_out_ids, float* d_out_dist, uint32_t* d_out_count,
+                            uint64_t* d_out_total);
 /* k-way merge of per-shard results (RCCL all-gather output): lists laid out
  * [n_lists][n_queries][k]; ids must already be global.  Ordered by (dist, id). */
 int ehx_merge_topk_device(void* stream, size_t n_queries, uint32_t k, uint32_t n_lists,
