@@ -19,6 +19,7 @@ ENGINE_F32, ENGINE_F16, ENGINE_I8 = 0, 1, 2
 MAX_K = 48
 WALK_AUTO, WALK_GRAPH, WALK_EXACT = 0, 1, 2   # route of graph_knn_masked
 WALK_LIST_FACTOR, WALK_LIST_MAX = 12, 4096     # EHX_WALK_LIST_FACTOR / _MAX: the walk list holds max(ef, min(12 ef, 4096))
+GROUP_NONE, MAX_K_GROUPED = 0xFFFFFFFF, 256     # EHX_GROUP_NONE (a row that is a group of its own), EHX_MAX_K_GROUPED
 SEED_CORPUS, SEED_QUERY = 20250211, 20250212
 
 
@@ -99,6 +100,8 @@ SYMBOLS = {
                                        _u32p]),
     "ehx_knn_masked_multi_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint32, _vp, C.c_uint32, C.c_uint64, _vp, _vp, _vp,
                                               _vp]),
+    "ehx_knn_grouped": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_uint32, C.c_uint32, _u32p, C.c_uint64, _u64p, _f32p, _u32p]),
+    "ehx_knn_grouped_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint32, C.c_uint32, _vp, C.c_uint64, _vp, _vp, _vp]),
     "ehx_graph_knn_masked": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_uint32, _u32p, C.c_uint64, C.c_uint32, _u64p, _f32p, _u32p]),
     "ehx_graph_knn_masked_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint32, _vp, C.c_uint64, C.c_uint32, _vp, _vp,
                                               _vp]),

@@ -246,7 +246,7 @@ int radius_knn(ehx_space* s, hipStream_t st, RadiusKnnBufs& w, uint64_t n_pub, c
     r.nq = (uint32_t)m;
     r.k = k;
     r.mode = mode;
-    HIP_TRY(launch_radius_rerank(r, st));
+    HIP_TRY(c.rerank ? c.rerank(r, st) : launch_radius_rerank(r, st));
     return EHX_OK;
   };
   RadiusScan scan;

@@ -542,6 +542,19 @@ struct ehx_space {
   RadiusKnnBufs largek;
   // test hook: queries answered on the route, handed to the exhaustive pass, of those the overflowed, scan passes launched, calls
   std::atomic<uint64_t> largek_ctr[5] = {};
+  // grouped kNN (ehx_grouped.cpp; scratch_mu): the scan route's buffers (RadiusKnnBufs; flagged queries go to the exact
+  // route), the exact route's own — carried keys, radii, every query's slab of row ids and its control words — and a host
+  // call's staged labels, queries and results
+  struct Grouped {
+    RadiusKnnBufs scan;
+    RadiusKnnBufs exact;         // (its sub-batch is not used: the exact route hands nothing on)
+    DevBuf<uint64_t> dPool;      // [queries of a device batch][kPoolCap]
+    DevBuf<uint32_t> dCtl;       // [queries] pool counts | [queries] flags, all zero
+    DevBuf<uint32_t> dLabels;    // host form: the labels of the prefix searched
+    HostStage host;
+  } grouped;
+  // test hook: queries answered on the scan route, handed to the exact route, of those the overflowed, scan passes launched, calls
+  std::atomic<uint64_t> grouped_ctr[5] = {};
   // int8 filter scratch: everything ONE in-flight batch of the int8 pipeline owns — prepared queries, query tiles +
   // parameters, per-pass thresholds, sample scores, pools, running best list, verdict, batch clock.  TWO sets: a host
   // caller's batch can be enqueued behind another caller's on the space's stream while that one still waits for its
@@ -637,6 +650,7 @@ struct ehx_space {
     range = {};
     masked = {};
     largek = {};
+    grouped = {};
     one = {};
     xch = {};
     wr = {};
@@ -866,6 +880,9 @@ struct RadiusKnn {
   // handed(q0, todo, d_q, o) answers the flagged queries todo (ascending, inside the device batch that starts at query q0
   // of the call, whose queries are d_q and whose rows of the output are o) and writes their rows of o
   std::function<int(size_t, const std::vector<uint32_t>&, const float*, const ResultBlock&)> handed;
+  // optional, instead of launch_radius_rerank: the re-rank of the seed and of every pass (the grouped kNN's, which caps the
+  // keys per label: k_grouped.hip)
+  std::function<hipError_t(const RadiusRerankArgs&, hipStream_t)> rerank;
 };
 struct RadiusKnnTally {
   uint64_t batches = 0, queries = 0;     // device batches whose verdict was read, and their queries
@@ -886,6 +903,12 @@ bool largek_serves(const ehx_space* s, size_t nq, uint32_t k, uint64_t n_pub);
 // returns with the stream drained
 int largek_locked(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, const float* d_queries, uint32_t k,
                   uint64_t* d_ids, float* d_dist, uint32_t* d_count);
+
+// ---- ehx_grouped.cpp ----
+// the exact route of the grouped kNN over the prefix of n_eff rows: every row in slabs of kPoolCap, any space kind
+// (count_queries: its queries are not in n_queries yet)
+int grouped_exact(ehx_space* s, hipStream_t st, uint64_t n_eff, size_t nq, const float* d_queries, uint32_t k, uint32_t per_group,
+                  const uint32_t* d_group_of, uint64_t* d_ids, float* d_dist, uint32_t* d_count, bool count_queries = true);
 
 // ---- ehx_range.cpp ----
 constexpr uint32_t kRangeGridTarget = 4096;   // workgroups an exact range kernel's launch aims for (16 per CU): chosen, not measured

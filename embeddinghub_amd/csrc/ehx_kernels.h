@@ -592,6 +592,21 @@ struct RadiusRerankArgs {
 };
 hipError_t launch_radius_rerank(const RadiusRerankArgs& a, hipStream_t st);   // k <= kLargeKMax, rows.ld <= range_rerank_max_ld()
 
+// grouped kNN (k_grouped.hip): the falling-radius re-rank with at most per_group rows of one label among the keys it carries,
+// hands on and writes; every layout of stored rows
+constexpr uint32_t kGroupNone = 0xFFFFFFFFu;   // EHX_GROUP_NONE: a row that is a group of its own
+struct GroupedRerankArgs {
+  RadiusRerankArgs r;        // (rows: any layout)
+  const uint32_t* group_of;  // [>= r.rows.n_rows] the rows' labels
+  uint32_t per_group;        // >= 1
+};
+uint32_t grouped_rerank_max_ld();   // longest row stride (floats): the pool, the cap's images and the prepared query share the LDS
+hipError_t launch_grouped_rerank(const GroupedRerankArgs& g, hipStream_t st);   // r.k <= kLargeKMax, rows.ld <= grouped_rerank_max_ld()
+// pool[q][i] = row0 + i for i < kPoolCap and pool_cnt[q] = n <= kPoolCap, for every query; first: radius[q] = +Inf,
+// top_cnt[q] = work[q] = 0 besides (the state in front of the first slab)
+hipError_t launch_grouped_slab(uint64_t* pool, uint32_t* pool_cnt, uint32_t nq, uint64_t row0, uint32_t n, bool first,
+                               float* radius, uint32_t* top_cnt, uint32_t* work, hipStream_t st);
+
 // per-row statistics for rows [row0, row0+n): inv_norm (cosine), rowp (a,b) for the scan epilogue;
 // *max_sumsq (optional) is raised to the largest |x|^2 seen (the certification margin's norm bound)
 // perm: the fp32 rows are stored block-permuted (single-copy graph spaces); the sums keep the logical order

@@ -440,6 +440,32 @@ class Space:
                                                   int(n_masks), int(n_bits), _ptr(d_mask_of), _ptr(d_ids), _ptr(d_dist),
                                                   _ptr(d_count)))
 
+    # ---- grouped kNN: at most per_group rows per group label ----
+    def knn_grouped(self, queries, k, group_of, per_group=1):
+        """The k nearest ELIGIBLE rows of every query, exact (ehx_knn_grouped): rows in (distance, id) order, a row eligible
+        iff its label is GROUP_NONE or fewer than per_group rows of its label precede it.  group_of: one integer label per
+        row (marshal_groups: -1 is GROUP_NONE); rows at or above len(group_of) or len(self) are not searched.  per_group = 1
+        is "collapse".  k <= 256.  -> ids [nq,k] u64, dist [nq,k] f32, count [nq] u32."""
+        q, pq = _f32(queries)
+        q = q.reshape(-1, self.dims)
+        nq = q.shape[0]
+        labels, n_labels = marshal_groups(group_of)
+        (ids, dist, cnt), out = _results(nq, k)
+        check(self._L.ehx_knn_grouped(self._h, nq, pq, k, int(per_group),
+                                      labels.ctypes.data_as(C.POINTER(C.c_uint32)) if n_labels else None, n_labels, *out))
+        return ids[:, :k], dist[:, :k], cnt
+
+    def knn_grouped_device(self, d_queries, k, d_group_of, n_labels, d_ids, d_dist, d_count, per_group=1, stream=None):
+        """knn_grouped without anything leaving the device (the serving path: the labels stay resident): torch CUDA tensors —
+        d_queries [nq, dims] f32, d_group_of [n_labels] u32 (int32 storage), outputs as knn_device's."""
+        nq = d_queries.shape[0] if hasattr(d_queries, "shape") else None
+        if nq is None:
+            raise ValueError("pass torch tensors (queries [nq, dims], group labels)")
+        if hasattr(d_group_of, "numel") and d_group_of.numel() < int(n_labels):
+            raise ValueError("%d group labels are fewer than n_labels = %d" % (d_group_of.numel(), n_labels))
+        check(self._L.ehx_knn_grouped_device(self._h, C.c_void_p(stream or 0), nq, _ptr(d_queries), k, int(per_group),
+                                             _ptr(d_group_of), int(n_labels), _ptr(d_ids), _ptr(d_dist), _ptr(d_count)))
+
     # ---- kNN under a row bitmap on the graph path ----
     def graph_knn_masked(self, queries, k, allow, n_bits=None, route=_lib.WALK_AUTO):
         """The k nearest ALLOWED rows the graph walk finds (ehx_graph_knn_masked): approximate when walked, possibly fewer
@@ -653,6 +679,27 @@ def marshal_mask(allow, n_bits=None):
     if n < 0 or n > a.shape[0] * 32:
         raise ValueError("n_bits = %d outside %d mask words" % (n, a.shape[0]))
     return np.ascontiguousarray(a), n
+
+
+def marshal_groups(group_of):
+    """The group labels of knn_grouped -> (u32 labels [n_labels], C-contiguous; n_labels).  group_of is a 1-d integer
+    sequence, one label per row; -1 (signed dtypes) and 0xFFFFFFFF both mean GROUP_NONE, a row that is a group of its own.
+    Other negative labels, labels above 0xFFFFFFFF and non-integral dtypes are refused."""
+    a = np.asarray(group_of)
+    if a.size == 0:
+        return np.zeros(0, dtype=np.uint32), 0
+    if a.ndim != 1:
+        raise ValueError("expected 1-d group labels, got shape %s" % (a.shape,))
+    if a.dtype.kind not in "ui":
+        raise ValueError("group labels must be integers, got dtype %s" % a.dtype)
+    if a.dtype != np.uint32:
+        if a.dtype.kind == "i":
+            if (a < -1).any():
+                raise ValueError("group labels must not be negative (-1 alone means GROUP_NONE)")
+            a = np.where(a == -1, _lib.GROUP_NONE, a.astype(np.int64) if a.dtype.itemsize < 8 else a)
+        if a.max() > _lib.GROUP_NONE:
+            raise ValueError("group labels must fit 32 bits")
+    return np.ascontiguousarray(a, dtype=np.uint32), int(a.shape[0])
 
 
 def marshal_mask_table(allows, n_bits=None):

@@ -315,6 +315,11 @@ int ehx_graph_knn_masked(ehx_space* s, size_t n_queries, const float* queries, u
 int ehx_graph_knn_masked_multi(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, const uint32_t* masks,
                                uint32_t n_masks, uint64_t n_bits, const uint32_t* mask_of, uint32_t route, uint64_t* out_ids,
                                float* out_dist, uint32_t* out_count);
+/* Grouped kNN from host pointers: ehx_knn_grouped_device (below: the contract) plus the H2D / D2H copies.  group_of has
+ * n_labels entries; the labels of the prefix searched are staged on EVERY call — 4 bytes per row, 4 MB at 1 M rows: the
+ * device form, with the labels resident, is the serving path. */
+int ehx_knn_grouped(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, uint32_t per_group,
+                    const uint32_t* group_of, uint64_t n_labels, uint64_t* out_ids, float* out_dist, uint32_t* out_count);
 /* Exact range search from host pointers: ehx_range_device (below: the contract) plus the H2D / D2H copies.  radius has
  * n_queries entries; out_total may be NULL. */
 int ehx_range(ehx_space* s, size_t n_queries, const float* queries, const float* radius, uint32_t max_results,
@@ -478,6 +483,32 @@ int ehx_graph_knn_masked_multi_device(ehx_space* s, void* stream, size_t n_queri
                                       const uint32_t* d_masks, uint32_t n_masks, uint64_t n_bits,
                                       const uint32_t* d_mask_of, uint32_t route, uint64_t* d_out_ids, float* d_out_dist,
                                       uint32_t* d_out_count);
+/* Grouped kNN: exact top-k with at most per_group rows per group label — the k nearest ENTITIES of a caller who stores
+ * several rows per entity (chunks of a document, frames of a video, variants of a product), without over-fetching.
+ * d_group_of holds one label per row, d_group_of[0, n_labels); EHX_GROUP_NONE marks a row that is a group of its own.  The
+ * call takes ONE acquire-load snapshot of the row count and searches the prefix n_eff = min(snapshot, n_labels); rows at or
+ * above it are not searched, as with n_bits of a bitmap (n_labels above the row count is fine; rows appended after the
+ * labels were built are not returned).  For query i, order the prefix rows by (canonical distance, id) under ehx_knn's
+ * rules: NaN is never a neighbour, +-Inf are ordered, cosine is normalised, F16 rows are read as stored.  A row is
+ * ELIGIBLE iff its label is EHX_GROUP_NONE, or fewer than per_group rows of the same label precede it in that order.  The
+ * answer is the first k eligible rows in that order, with sentinels (id 2^64 - 1, +Inf) behind d_out_count[i].
+ * Consequences: per_group >= k, or every label EHX_GROUP_NONE, gives ehx_knn's answer over the prefix, byte for byte;
+ * per_group == 1 is "collapse": the best row of each of the k nearest groups.  (NOT served: the per_group nearest rows of
+ * every winning group regardless of their distance — no radius bounds that.)
+ * Errors: a NULL space: EHX_EINVAL, before the device is looked for; k == 0, per_group == 0, NULL outputs, a NULL d_group_of
+ * with n_labels > 0: EHX_EINVAL; k > EHX_MAX_K_GROUPED, a row-sharded space, rows longer than 21 728 floats:
+ * EHX_EUNSUPPORTED; a dropped space: EHX_ENOTFOUND.  n_labels == 0: count 0 for every query; n_queries == 0: EHX_OK.
+ * Served by the falling-radius scan of the int8 filter where ehx_knn_device's large-k route would serve the prefix (flat
+ * spaces whose first engine is the int8 filter, at least 64 queries; any k here) with a cap per label in its exact re-rank;
+ * everything else — graph spaces (from their stored rows: the graph is not walked), small spaces, EHX_SCAN_F32 / _F16, small
+ * batches, and the queries that scan hands on — by an exact pass over every prefix row in slabs of 4096, which costs what
+ * the exhaustive pass costs plus a sort per slab.  A Set that rewrites rows in place waits for the call like for any
+ * search.  Not combined with a bitmap, not on the graph walk.  DESIGN.md §e.19. */
+#define EHX_GROUP_NONE 0xFFFFFFFFu
+#define EHX_MAX_K_GROUPED 256u
+int ehx_knn_grouped_device(ehx_space* s, void* stream, size_t n_queries, const float* d_queries, uint32_t k,
+                           uint32_t per_group, const uint32_t* d_group_of, uint64_t n_labels, uint64_t* d_out_ids,
+                           float* d_out_dist, uint32_t* d_out_count);
 /* Exact range search: every row closer than a radius.  With D(q, x) the canonical distance ehx_knn reports (cosine, L2^2,
  * inner product as there), row x belongs to query i's answer iff D is not NaN and D <= d_radius[i] as a float comparison
  * (inclusive: a radius that equals a row's distance byte for byte includes that row; -Inf distances under inner product
