@@ -62,12 +62,13 @@ def _key(dist):
     return lambda r: (dist[r], r)
 
 
-def passes_model(dist, labels, k, m, ranges, sample=None, through=None):
+def passes_model(dist, labels, k, m, ranges, sample=None, through=None, carried_at=None):
     """grouped_rerank_kernel over the row ranges [(lo, hi)] for one query.  dist: [rows] canonical distances (NaN: never a
     neighbour).  sample: row ids re-ranked in seed mode (their capped k-th distance is the first radius, +Inf below k
     capped rows; nothing is carried), or None: the exact route, radius +Inf first.  through(j, lo, hi, radius) -> bool
-    [hi - lo]: the rows the scan of pass j lets through (None: all).  -> (answer, radius in front of every pass, rows
-    within the radius at every pass)."""
+    [hi - lo]: the rows the scan of pass j lets through (None: all).  carried_at: a list that receives the number of keys
+    carried into every pass, before `through` is asked about it.  -> (answer, radius in front of every pass, rows within the
+    radius at every pass)."""
     key = _key(dist)
     ok = ~np.isnan(dist)
     radius = np.inf
@@ -78,6 +79,8 @@ def passes_model(dist, labels, k, m, ranges, sample=None, through=None):
     carried, radii, within = [], [], []
     for j, (lo, hi) in enumerate(ranges):
         radii.append(radius)
+        if carried_at is not None:
+            carried_at.append(len(carried))
         sel = ok[lo:hi] & (dist[lo:hi] <= radius)
         within.append(int(sel.sum()))
         if through is not None:

@@ -24,10 +24,13 @@ import functools
 import numpy as np
 
 import extreme_cases as xc
+import grouped_model as gm
 import i8_model as m8
 import largek_cases as lc
 import masked_cases as mc
+import masked_multi_cases as mmc
 import range_cases as rc
+import range_masked_cases as rmc
 from oracle import pyoracle
 
 f32 = np.float32
@@ -44,6 +47,9 @@ LARGE_K = 100
 BYKEYS_K = 48
 POOL_CAP = lc.POOL_CAP
 SERVED, MARKED, OVERFLOWED, UNDECIDED = "served", "marked", "overflowed", "undecided"
+EXACT = "exact"         # under a table of bitmaps: the query's mask takes the exact / list route outright, no verdict
+GROUPED_KM = ((10, 1), (100, 3))          # grouped kNN: (k, per_group)
+MASK_NAMES = ("half", "few", "block", "no_block", "empty", "ones")
 
 
 def _frozen(*arrays):
@@ -193,14 +199,21 @@ class Model:
     def _thr(self, radius):
         return rc.range_thr(radius, self.u, self.v, self.metric, self.d, self.max_sumsq)
 
-    def range(self, radius):
+    def range(self, radius, allow=None):
         """the range search's ONE pass over every tile -> (verdict [nq], fill [nq]); asserts that the threshold hides no
-        member of a query it does not mark"""
+        member of a query it does not mark.  allow: bool [rows, queries] or [rows] — the rows every query's bitmap allows
+        (the range search under row bitmaps: the flush drops the others, so only allowed rows fill the pool and only
+        allowed rows are members).  The verdict is the SCAN route's: masked_multi_cases.scans says which queries take the
+        list route outright."""
         radius = np.asarray(radius, dtype=f32)
         thr, marked = self._thr(radius)
         with np.errstate(invalid="ignore"):
             through = self.S <= thr[None, :]
             member = self.Dm <= radius[None, :]
+        if allow is not None:
+            allow = np.asarray(allow, dtype=bool)
+            allow = allow[:, None] if allow.ndim == 1 else allow
+            through, member = through & allow, member & allow
         hidden = member & ~through & ~marked[None, :]
         assert not hidden.any(), "the threshold hides %d members (queries %s)" % (
             int(hidden.sum()), np.nonzero(hidden.any(axis=0))[0][:8].tolist())
@@ -213,27 +226,50 @@ class Model:
         """the falling-radius kNN: allowed None: the large-k route (a strided sample seeds the radius), else the bitmap
         search's scan route.  -> (verdict [nq], fills [passes][nq] (-1: not scanned any more), answers: the ids of every served
         query, None for the others).  Asserts, at every pass, that no allowed row within the radius lies above the threshold."""
-        n, nq, Dm = self.n, self.nq, self.Dm
+        n = self.n
         if allowed is None:
             plan, smp, allow = lc.passes(n), lc.sample_ids(n), np.ones(n, dtype=bool)
         else:
             plan, smp, allow = mc.passes(allowed), mc.sample_ids(allowed), allowed
-        valid = ~np.isnan(Dm[smp])
-        kth = np.sort(np.where(valid, Dm[smp], f32(np.inf)), axis=0)[min(k, len(smp)) - 1]
-        radius = np.where(valid.sum(axis=0) >= k, kth, f32(np.inf)).astype(f32)   # fewer than k: +Inf, the query is marked
-        verdict = np.full(nq, SERVED, dtype=object)
-        live = np.ones(nq, dtype=bool)
+        return self._falling(k, plan, [allow] * self.nq, [smp] * self.nq)
+
+    def knn_table(self, k, tab, mask_of):
+        """the bitmap-table scan route (ehx_masked.cpp, masked_answer): ONE pass plan for the batch —
+        masked_multi_cases.passes(tab, mask_of), cut by the pointwise maximum of the scanned masks' running counts — every
+        scan-route query under its OWN bitmap, its first radius the exact k-th distance over its OWN mask's sample
+        (masked_cases.sample_ids of that mask: every ceil(allowed / 256)-th allowed id by rank, +Inf while the sample gives
+        fewer than k).  -> knn's triple; a query whose mask takes the exact route outright has the verdict EXACT, fills -1
+        and no answer."""
+        tab, mask_of = np.asarray(tab, dtype=bool), np.asarray(mask_of)
+        scans = mmc.scans(tab)
+        smp = [mc.sample_ids(tab[m]) if scans[m] else None for m in range(len(tab))]
+        return self._falling(k, mmc.passes(tab, mask_of), [tab[m] if scans[m] else None for m in mask_of],
+                             [smp[m] for m in mask_of])
+
+    def _falling(self, k, plan, allow_of, sample_of):
+        """the falling-radius cascade of knn / knn_table: query q under the rows allow_of[q] (None: not on the route), its
+        first radius from the rows sample_of[q]"""
+        n, nq, Dm = self.n, self.nq, self.Dm
+        live = np.array([a is not None for a in allow_of])
+        radius = np.full(nq, np.inf, dtype=f32)
+        for q in np.nonzero(live)[0]:
+            dq = Dm[sample_of[q], q]
+            dq = np.sort(dq[~np.isnan(dq)])
+            if len(dq) >= k:                # fewer than k: +Inf, the query is marked
+                radius[q] = dq[k - 1]
+        verdict = np.where(live, SERVED, EXACT).astype(object)
         carried = [np.zeros(0, dtype=np.int64) for _ in range(nq)]
         fills = []
         for t0, nt in plan:
             lo, hi = t0 * lc.TILE, min((t0 + nt) * lc.TILE, n)
             thr, marked = self._thr(radius)
             fill = np.full(nq, -1, dtype=np.int64)
-            in_pass = int(allow[lo:hi].sum())   # (a pass of at most POOL_CAP rows cannot overflow, however loose the bound)
             for q in np.nonzero(live)[0]:
                 if marked[q]:
                     verdict[q], live[q] = MARKED, False
                     continue
+                allow = allow_of[q]
+                in_pass = int(allow[lo:hi].sum())   # (a pass of at most POOL_CAP rows cannot overflow, however loose the bound)
                 with np.errstate(invalid="ignore"):
                     through = (self.S[lo:hi, q] <= thr[q]) & allow[lo:hi]
                     member = allow[lo:hi] & (Dm[lo:hi, q] <= radius[q])
@@ -260,6 +296,53 @@ class Model:
         ids, dist, cnt = self.oracle
         L = ids[q, :int(cnt[q])].astype(np.int64)
         return (L if allowed is None else L[allowed[L]])[:k]
+
+    def knn_grouped(self, k, m, labels):
+        """the grouped kNN's scan route (ehx_grouped.cpp): grouped_model.passes_model — the large-k route's strided sample
+        capped and cut at k for the first radius, then per pass: hits capped, merged with the carried keys, capped again, the
+        radius falling — over largek_cases' passes, the rows let through being S_lower <= range_thr(radius).
+        -> (verdict [nq], fills [passes][nq], answers, short: bool [nq], the capped sample holds fewer than k rows — the radius
+        stays +Inf and the query is marked through the seed).  Verdicts as knn's; asserts that no row within a radius is hidden
+        (passes_model does) and that a served query's answer is the capped greedy over the oracle's order."""
+        n, nq, Dm = self.n, self.nq, self.Dm
+        ranges, smp = gm.scan_ranges(n), lc.sample_ids(n)
+        verdict = np.full(nq, SERVED, dtype=object)
+        fills = [np.full(nq, -1, dtype=np.int64) for _ in ranges]
+        answers, short = [None] * nq, np.zeros(nq, dtype=bool)
+        for q in range(nq):
+            dist = Dm[:, q]
+            ok = smp[~np.isnan(dist[smp])]
+            capped = gm._cap(ok[np.lexsort((ok, dist[ok]))].tolist(), labels, m)
+            short[q] = len(capped) < k
+            carried_at = []
+
+            def through(j, lo, hi, radius, q=q, carried_at=carried_at):
+                thr, marked = rc.range_thr(np.array([radius], dtype=f32), self.u[q:q + 1], self.v[q:q + 1], self.metric,
+                                           self.d, self.max_sumsq)
+                if marked[0]:
+                    raise _Handed(MARKED)
+                with np.errstate(invalid="ignore"):
+                    t = self.S[lo:hi, q] <= thr[0]
+                fills[j][q] = int(t.sum())
+                if fills[j][q] > POOL_CAP:
+                    raise _Handed(OVERFLOWED)
+                if fills[j][q] + carried_at[j] > POOL_CAP // 2 and hi - lo > POOL_CAP:
+                    raise _Handed(UNDECIDED)
+                return t
+            try:
+                ans, _, _ = gm.passes_model(dist, labels, k, m, ranges, sample=smp, through=through, carried_at=carried_at)
+            except _Handed as e:
+                verdict[q] = e.args[0]
+                continue
+            order = self.oracle[0][q, :int(self.oracle[2][q])].astype(np.int64)
+            assert ans == gm.capped_greedy(order.tolist(), labels, k, m), "query %d: not the capped greedy" % q
+            answers[q] = np.asarray(ans, dtype=np.int64)
+        assert not (short & (verdict == SERVED)).any()   # (+Inf is never served)
+        return verdict, fills, answers, short
+
+
+class _Handed(Exception):
+    pass
 
 
 def tally(verdict):
@@ -364,6 +447,93 @@ def case_verdicts(name):
     v = route_verdicts(c["X"], c["Q"], c["metric"], half, c["key_rows"], radii)
     v["radii"] = radii
     return c, half, v
+
+
+# ---- the filtered searches: range under a table of bitmaps, kNN under it, grouped kNN ---------------------------------------
+
+def mask_table(n, seed=1):
+    """bool [6, n], MASK_NAMES: bitmaps(n, seed)'s half (on an int8 space: a first pass that cannot overflow) and few (<= 1024
+    rows, 100 of the block: the list / exact route in the same batch as scan-route queries); only the block's 256 rows (a
+    list made wholly of the extreme kind); every row but the block; none; all"""
+    half, few = bitmaps(n, seed)
+    block = np.zeros(n, dtype=bool)
+    block[xc.BLOCK0:xc.BLOCK0 + xc.NBLOCK] = True
+    tab = np.stack([half, few, block, ~block, np.zeros(n, dtype=bool), np.ones(n, dtype=bool)])
+    tab.setflags(write=False)
+    return tab
+
+
+BIG_LABEL = 0xFFFFFFFE   # the largest real label: beside NONE, and beside the padding key of the cap's sort
+BIG_LABEL_ROWS = (3, 4003, 8003, 12003, 16003)
+
+
+def group_labels(n, few_in_sample=False):
+    """uint32 [n]: row % 97, every 11th row a group of its own; the block's rows {5, 6, 7, NONE} in turn, so that extreme rows
+    compete with ordinary rows of the same label for a quota; BIG_LABEL on BIG_LABEL_ROWS (those below n).
+    few_in_sample (the spaces of one kind): row % 100 and every 13th row NONE instead — the large-k sample of 20 000 rows, the
+    ids 0, 20, 40, ..., then carries six labels and 76 NONE rows: 82 capped rows at per_group 1, 94 at per_group 3.  At
+    (k, per_group) = (100, 3) the cap leaves the seed fewer than k rows, the radius stays +Inf and EVERY query is marked
+    through the seed; at (10, 1) the seed is whole.  (Whether the capped sample reaches k does not depend on the query, NaN
+    distances aside: no one labeling gives a batch both.)"""
+    g = (np.arange(n, dtype=np.int64) % (100 if few_in_sample else 97)).astype(np.uint32)
+    g[::13 if few_in_sample else 11] = gm.NONE
+    g[xc.BLOCK0:xc.BLOCK0 + xc.NBLOCK] = np.array([5, 6, 7, gm.NONE], dtype=np.uint32)[np.arange(xc.NBLOCK) % 4]
+    for r in BIG_LABEL_ROWS:
+        if r < n:
+            g[r] = BIG_LABEL
+    g.setflags(write=False)
+    return g
+
+
+def for_counters(verdict):
+    """a table's verdicts as expect_counters reads them: a query whose mask takes the exact / list route outright is handed on
+    and is no overflow, as a marked one is"""
+    v = np.asarray(verdict).copy()
+    v[v == EXACT] = MARKED
+    return v
+
+
+FILTERED_ROUTES = ([("rangem", rank) for rank in RANKS] + [("table", k) for k in MASKED_KS]
+                   + [("grouped", k, per) for k, per in GROUPED_KM])
+
+
+class _Routes(dict):
+    """filtered_routes' result: a route's verdicts are worked out when they are first asked for"""
+
+    def __missing__(self, key):
+        m, tab, mask_of, scans = self["model"], self["tab"], self["mask_of"], self["scans"]
+        if key[0] == "radii":
+            value = rmc.radii_at(self["lists"], m.nq, key[1])
+        elif key[0] == "rangem":
+            verdict, fill = m.range(self["radii", key[1]], tab[mask_of].T)
+            value = (np.where(scans, verdict, EXACT), np.where(scans, fill, -1))
+        elif key[0] == "table":
+            value = m.knn_table(key[1], tab, mask_of)
+        elif key[0] == "grouped":
+            value = m.knn_grouped(key[1], key[2], self["labels"])
+        else:
+            raise KeyError(key)
+        self[key] = value
+        return value
+
+
+def filtered_routes(X, Q, metric, few_in_sample=False):
+    """what the three filtered searches' int8 routes do with the batch Q on the space X under mask_table / group_labels:
+    {"model", "tab", "mask_of", "labels", "lists" (range_masked_cases.lists_under: the oracle under every mask), "scans" (bool
+    [nq]: the query's mask is on the scan route), and per route of FILTERED_ROUTES, worked out at its first use: ("radii",
+    rank): the rank-th allowed distance of every query, ("rangem", rank): (verdict, fill), ("table", k): knn's triple,
+    ("grouped", k, m): knn_grouped's four}.  few_in_sample: group_labels'."""
+    n, nq = len(X), len(Q)
+    tab, mask_of = mask_table(n), mmc.interleaved(nq, len(MASK_NAMES))
+    return _Routes(model=Model(X, Q, metric), tab=tab, mask_of=mask_of, labels=group_labels(n, few_in_sample),
+                   lists=rmc.lists_under(X, Q, rc.OM[metric], tab, mask_of), scans=mmc.scans(tab)[mask_of])
+
+
+@functools.lru_cache(maxsize=2)
+def filtered_verdicts(name):
+    """-> (case, filtered_routes of it); the spaces of one kind under group_labels' few_in_sample"""
+    c = int8_case(name)
+    return c, filtered_routes(c["X"], c["Q"], c["metric"], few_in_sample=name.startswith("one-"))
 
 
 @functools.lru_cache(maxsize=None)
