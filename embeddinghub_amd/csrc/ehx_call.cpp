@@ -227,7 +227,7 @@ int radius_knn(ehx_space* s, hipStream_t st, RadiusKnnBufs& w, uint64_t n_pub, c
   if ((rc = w.dTop.ensure(cap * kLargeKMax)) || (rc = w.dTopCnt.ensure(cap)) || (rc = w.dRadius.ensure(cap)) ||
       (rc = w.dWork.ensure(cap)))
     return rc;
-  size_t m = 0;    // the batch in hand: its queries and its rows of the output
+  size_t q0 = 0, m = 0;    // the batch in hand: its first query, its queries and its rows of the output
   ResultBlock o{};
   auto rerank = [&](uint32_t mode, const ScanArgsI8& a, ehx_space::I8Set& sc) -> int {
     RadiusRerankArgs r = {};
@@ -259,7 +259,11 @@ int radius_knn(ehx_space* s, hipStream_t st, RadiusKnnBufs& w, uint64_t n_pub, c
   if (!c.first_radius) {
     scan.seed = [&](const ScanArgsI8& a, ehx_space::I8Set& sc) -> int {
       // (the control words are zero, the prepared queries in place): the sample -> the first radii, nothing carried
-      HIP_TRY(launch_radius_seed(sc.buf.dPool.p, a.pool_cnt, (uint32_t)m, n_pub, c.seed_stride, c.n_sample, st));
+      if (c.fill_pool) {
+        if (int r = c.fill_pool(q0, m, sc.buf.dPool.p, a.pool_cnt)) return r;
+      } else {
+        HIP_TRY(launch_radius_seed(sc.buf.dPool.p, a.pool_cnt, (uint32_t)m, n_pub, c.seed_stride, c.n_sample, st));
+      }
       return rerank(kRadiusSeed, a, sc);
     };
   }
@@ -268,7 +272,7 @@ int radius_knn(ehx_space* s, hipStream_t st, RadiusKnnBufs& w, uint64_t n_pub, c
     return last ? sc.clock.scan_end(st) : (int)EHX_OK;   // (the timed scan phase: the seed and every pass with its re-rank)
   };
   std::vector<uint32_t> todo;
-  for (size_t q0 = 0; q0 < nq; q0 += kSideChunk) {
+  for (q0 = 0; q0 < nq; q0 += kSideChunk) {
     m = std::min(kSideChunk, nq - q0);
     o = c.out.from(q0, m);
     const float* q = d_queries + q0 * s->dims;

@@ -555,6 +555,20 @@ struct ehx_space {
   } grouped;
   // test hook: queries answered on the scan route, handed to the exact route, of those the overflowed, scan passes launched, calls
   std::atomic<uint64_t> grouped_ctr[5] = {};
+  // grouped kNN under row bitmaps (ehx_groupedm.cpp; scratch_mu): the compaction is the bitmap search's (masked), the list
+  // route's pools, control words, carried keys and a host call's staged labels the grouped kNN's (grouped.dPool / dCtl /
+  // exact / dLabels); its own are the scan route's buffers (its sub-batch: the queries the scan hands on), the call's
+  // queries ordered by route and bitmap, the bitmap of every query of a device batch, and a host call's staged queries and
+  // results
+  struct GroupedMasked {
+    RadiusKnnBufs scan;
+    SubsetBufs group;
+    DevBuf<uint32_t> dMaskAt;    // [queries of a device batch]
+    HostStage host;
+  } groupedm;
+  // test hook: queries answered on the scan route, on the list route (by the gate or handed on by the scan), of those the
+  // overflowed, scan passes launched, calls
+  std::atomic<uint64_t> groupedm_ctr[5] = {};
   // int8 filter scratch: everything ONE in-flight batch of the int8 pipeline owns — prepared queries, query tiles +
   // parameters, per-pass thresholds, sample scores, pools, running best list, verdict, batch clock.  TWO sets: a host
   // caller's batch can be enqueued behind another caller's on the space's stream while that one still waits for its
@@ -651,6 +665,7 @@ struct ehx_space {
     masked = {};
     largek = {};
     grouped = {};
+    groupedm = {};
     one = {};
     xch = {};
     wr = {};
@@ -874,6 +889,10 @@ struct RadiusKnn {
   std::function<int(size_t, const float*, const ResultBlock&, float*)> first_radius;
   uint64_t seed_stride = 0;
   uint32_t n_sample = 0;
+  // optional, instead of that strided sample (seed_stride and n_sample are then unused): fill_pool(q0, m, pool, pool_cnt)
+  // enqueues what writes the sample of every query of the device batch [q0, q0 + m) of the call — pool[j][0, pool_cnt[j]),
+  // at most kLargeKSample row ids each, any rows the search may return — where launch_radius_seed would be
+  std::function<int(size_t, size_t, uint64_t*, uint32_t*)> fill_pool;
   ResultBlock out;                     // out.k <= kLargeKMax
   SubsetBufs::Answer exact;
   // optional, instead of exact, where the exact answer depends on which query it is (a bitmap per query):

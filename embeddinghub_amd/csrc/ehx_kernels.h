@@ -607,6 +607,17 @@ hipError_t launch_grouped_rerank(const GroupedRerankArgs& g, hipStream_t st);   
 hipError_t launch_grouped_slab(uint64_t* pool, uint32_t* pool_cnt, uint32_t nq, uint64_t row0, uint32_t n, bool first,
                                float* radius, uint32_t* top_cnt, uint32_t* work, hipStream_t st);
 
+// grouped kNN under row bitmaps (k_groupedm.hip): every query's pool filled from the compacted list of ITS OWN bitmap —
+// list, off, cum, n_tiles: launch_masked_fill's (n_tiles >= 1); mask_at[q] < n_masks: the bitmap of query q of the batch.
+// seed: pool[q][i] = mask's list[i * stride] for i * stride < allowed, stride = ceil(allowed / kLargeKSample), pool_cnt[q]
+// the number written.  slab: pool[q][0, n) = entries [slab * kPoolCap, ...) of the mask's list, pool_cnt[q] = n = as many as
+// remain, at most kPoolCap, possibly 0; first: radius[q] = +Inf, top_cnt[q] = work[q] = 0 besides, as launch_grouped_slab
+hipError_t launch_grouped_list_seed(const uint64_t* list, const MaskedOffsets& off, const uint32_t* cum, uint32_t n_tiles,
+                                    const uint32_t* mask_at, uint64_t* pool, uint32_t* pool_cnt, uint32_t nq, hipStream_t st);
+hipError_t launch_grouped_list_slab(const uint64_t* list, const MaskedOffsets& off, const uint32_t* cum, uint32_t n_tiles,
+                                    const uint32_t* mask_at, uint64_t slab, bool first, uint64_t* pool, uint32_t* pool_cnt,
+                                    float* radius, uint32_t* top_cnt, uint32_t* work, uint32_t nq, hipStream_t st);
+
 // per-row statistics for rows [row0, row0+n): inv_norm (cosine), rowp (a,b) for the scan epilogue;
 // *max_sumsq (optional) is raised to the largest |x|^2 seen (the certification margin's norm bound)
 // perm: the fp32 rows are stored block-permuted (single-copy graph spaces); the sums keep the logical order

@@ -466,6 +466,56 @@ class Space:
         check(self._L.ehx_knn_grouped_device(self._h, C.c_void_p(stream or 0), nq, _ptr(d_queries), k, int(per_group),
                                              _ptr(d_group_of), int(n_labels), _ptr(d_ids), _ptr(d_dist), _ptr(d_count)))
 
+    # ---- grouped kNN under row bitmaps: filter first, then at most per_group rows per group label ----
+    def knn_grouped_masked(self, queries, k, group_of, allows, mask_of=None, per_group=1, n_bits=None):
+        """knn_grouped over the allowed rows alone (ehx_knn_grouped_masked): query i is answered under allows[mask_of[i]];
+        rows that are not allowed neither appear nor count toward a group's cap.  group_of as knn_grouped's.  allows: a 2-d
+        bool array [n_masks, rows] or packed uint32 words [n_masks, words] with n_bits, at most 64 bitmaps; or ONE 1-d bitmap
+        (a table of one), under which every query is answered when mask_of is None.  Rows at or above len(group_of), n_bits
+        or len(self) are not searched.  k <= 256.  -> ids [nq,k] u64, dist [nq,k] f32, count [nq] u32."""
+        q, pq = _f32(queries)
+        q = q.reshape(-1, self.dims)
+        nq = q.shape[0]
+        labels, n_labels = marshal_groups(group_of)
+        a = np.asarray(allows)
+        if a.ndim == 1:
+            words, n_bits = marshal_mask(a, n_bits)
+            words, n_masks = words[None], 1
+        else:
+            words, n_masks, n_bits = marshal_mask_table(a, n_bits)
+        of = None
+        if mask_of is not None:
+            of = np.ascontiguousarray(np.asarray(mask_of).reshape(-1), dtype=np.uint32)
+            if of.shape[0] != nq:
+                raise ValueError("expected %d mask_of entries, got %d" % (nq, of.shape[0]))
+        elif n_masks != 1:
+            raise ValueError("a table of %d bitmaps needs mask_of" % n_masks)
+        (ids, dist, cnt), out = _results(nq, k)
+        check(self._L.ehx_knn_grouped_masked(self._h, nq, pq, k, int(per_group),
+                                             labels.ctypes.data_as(C.POINTER(C.c_uint32)) if n_labels else None, n_labels,
+                                             words.ctypes.data_as(C.POINTER(C.c_uint32)) if n_bits else None, n_masks, n_bits,
+                                             of.ctypes.data_as(C.POINTER(C.c_uint32)) if of is not None else None, *out))
+        return ids[:, :k], dist[:, :k], cnt
+
+    def knn_grouped_masked_device(self, d_queries, k, d_group_of, n_labels, d_masks, n_masks, n_bits, d_mask_of, d_ids, d_dist,
+                                  d_count, per_group=1, stream=None):
+        """knn_grouped_masked without anything leaving the device (the serving path: labels and bitmaps stay resident): torch
+        CUDA tensors — d_queries [nq, dims] f32, d_group_of [n_labels] u32 (int32 storage), d_masks [n_masks,
+        ceil(n_bits / 32)] packed u32 words (int32 storage), d_mask_of [nq] u32 (int32 storage) or None with n_masks == 1,
+        outputs as knn_device's."""
+        nq = d_queries.shape[0] if hasattr(d_queries, "shape") else None
+        if nq is None:
+            raise ValueError("pass torch tensors (queries [nq, dims], group labels, mask words, mask_of)")
+        if hasattr(d_group_of, "numel") and d_group_of.numel() < int(n_labels):
+            raise ValueError("%d group labels are fewer than n_labels = %d" % (d_group_of.numel(), n_labels))
+        if hasattr(d_masks, "numel") and d_masks.numel() < int(n_masks) * ((int(n_bits) + 31) // 32):
+            raise ValueError("%d mask words hold fewer than %d bitmaps of n_bits = %d bits" % (d_masks.numel(), n_masks, n_bits))
+        if hasattr(d_mask_of, "numel") and d_mask_of.numel() < nq:
+            raise ValueError("%d mask_of entries for %d queries" % (d_mask_of.numel(), nq))
+        check(self._L.ehx_knn_grouped_masked_device(self._h, C.c_void_p(stream or 0), nq, _ptr(d_queries), k, int(per_group),
+                                                    _ptr(d_group_of), int(n_labels), _ptr(d_masks), int(n_masks), int(n_bits),
+                                                    _ptr(d_mask_of), _ptr(d_ids), _ptr(d_dist), _ptr(d_count)))
+
     # ---- kNN under a row bitmap on the graph path ----
     def graph_knn_masked(self, queries, k, allow, n_bits=None, route=_lib.WALK_AUTO):
         """The k nearest ALLOWED rows the graph walk finds (ehx_graph_knn_masked): approximate when walked, possibly fewer

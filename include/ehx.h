@@ -320,6 +320,13 @@ int ehx_graph_knn_masked_multi(ehx_space* s, size_t n_queries, const float* quer
  * device form, with the labels resident, is the serving path. */
 int ehx_knn_grouped(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, uint32_t per_group,
                     const uint32_t* group_of, uint64_t n_labels, uint64_t* out_ids, float* out_dist, uint32_t* out_count);
+/* Grouped kNN under a table of row bitmaps from host pointers: ehx_knn_grouped_masked_device (below: the contract) plus the
+ * H2D / D2H copies.  group_of has n_labels entries, masks n_masks * ceil(n_bits / 32) words, mask_of n_queries entries (it may
+ * be NULL with n_masks == 1); mask_of is checked here, before anything is enqueued.  The labels and the bitmaps' words of the
+ * prefix searched are staged on EVERY call: the device form, with both resident, is the serving path. */
+int ehx_knn_grouped_masked(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, uint32_t per_group,
+                           const uint32_t* group_of, uint64_t n_labels, const uint32_t* masks, uint32_t n_masks,
+                           uint64_t n_bits, const uint32_t* mask_of, uint64_t* out_ids, float* out_dist, uint32_t* out_count);
 /* Exact range search from host pointers: ehx_range_device (below: the contract) plus the H2D / D2H copies.  radius has
  * n_queries entries; out_total may be NULL. */
 int ehx_range(ehx_space* s, size_t n_queries, const float* queries, const float* radius, uint32_t max_results,
@@ -503,12 +510,48 @@ int ehx_graph_knn_masked_multi_device(ehx_space* s, void* stream, size_t n_queri
  * everything else — graph spaces (from their stored rows: the graph is not walked), small spaces, EHX_SCAN_F32 / _F16, small
  * batches, and the queries that scan hands on — by an exact pass over every prefix row in slabs of 4096, which costs what
  * the exhaustive pass costs plus a sort per slab.  A Set that rewrites rows in place waits for the call like for any
- * search.  Not combined with a bitmap, not on the graph walk.  DESIGN.md §e.19. */
+ * search.  Under row bitmaps: ehx_knn_grouped_masked_device; not on the graph walk.  DESIGN.md §e.19. */
 #define EHX_GROUP_NONE 0xFFFFFFFFu
 #define EHX_MAX_K_GROUPED 256u
 int ehx_knn_grouped_device(ehx_space* s, void* stream, size_t n_queries, const float* d_queries, uint32_t k,
                            uint32_t per_group, const uint32_t* d_group_of, uint64_t n_labels, uint64_t* d_out_ids,
                            float* d_out_dist, uint32_t* d_out_count);
+/* Grouped kNN under row bitmaps: "the k nearest documents this user may see, at most per_group chunks each" in one request —
+ * ehx_knn_grouped_device's cap per label over the rows ehx_knn_masked_multi_device's filter allows.  Query i is answered
+ * under bitmap d_mask_of[i] of a table laid out as ehx_knn_masked_multi_device's (n_masks <= 64 bitmaps of ceil(n_bits / 32)
+ * words, back to back).  One bitmap is a table of one: with n_masks == 1, d_mask_of may be NULL and every query is under
+ * bitmap 0.  d_group_of holds one label per row, as for ehx_knn_grouped_device.
+ * The call takes ONE acquire-load snapshot of the row count and searches the prefix n_eff = min(snapshot, n_labels, n_bits).
+ * Row r is ALLOWED for query i iff r < n_eff and bit r & 31 of word r >> 5 of its bitmap is set: a row at or above any of the
+ * three limits is not allowed.
+ * The rule is FILTER FIRST, THEN CAP.  Order the ALLOWED rows of query i by (canonical distance, id) under
+ * ehx_knn_grouped_device's rules (NaN is never a neighbour, +-Inf are ordered, cosine is normalised, F16 rows are read as
+ * stored).  An allowed row is ELIGIBLE iff its label is EHX_GROUP_NONE, or fewer than per_group ALLOWED rows of the same label
+ * precede it in that order.  The answer is the first k eligible rows, with sentinels (id 2^64 - 1, +Inf) behind
+ * d_out_count[i].  Rows that are not allowed neither appear nor count toward a cap: a group whose nearest row is forbidden is
+ * represented by its nearest ALLOWED row — which ehx_knn_grouped_device followed by a filter on the host gets wrong.
+ * Equivalences, byte for byte: with every bit set the call equals ehx_knn_grouped_device (at n_labels = min(n_labels,
+ * n_bits)); with every label EHX_GROUP_NONE, or per_group at least the size of the largest group, it equals
+ * ehx_knn_masked_multi_device (at n_bits = min(n_bits, n_labels)); a bitmap with no bit set gives count 0 for ITS queries
+ * only.  n_bits == 0 (d_masks may then be NULL) or n_labels == 0: count 0 for every query.
+ * Errors, the union of the two parents': a NULL space: EHX_EINVAL, before the device is looked for; k == 0, per_group == 0,
+ * NULL outputs, a NULL d_group_of with n_labels > 0, a NULL d_masks with n_bits > 0, n_masks == 0 with n_queries > 0, a NULL
+ * d_mask_of with n_masks > 1: EHX_EINVAL; d_mask_of[i] >= n_masks: EHX_EINVAL with the outputs unwritten (d_mask_of is read
+ * back with the allowed counts and checked before anything writes the outputs); k > EHX_MAX_K_GROUPED, n_masks > 64, a
+ * row-sharded space, rows longer than 21 728 floats: EHX_EUNSUPPORTED; a dropped space: EHX_ENOTFOUND; no device:
+ * EHX_ENODEVICE.  n_queries == 0: EHX_OK.
+ * Served per bitmap.  The falling-radius scan of the int8 filter, the bitmaps tested in its flush (one per query) and a cap
+ * per label in its exact re-rank, where ehx_knn_grouped_device's scan would serve the prefix (flat spaces whose first engine
+ * is the int8 filter), for bitmaps that allow more than max(1024, rows / 128) rows, given at least 64 such queries; its
+ * first radius comes from a sample of at most 1024 allowed rows of the query's own bitmap.  Everything else — graph spaces
+ * (from their stored rows: the graph is not walked), small spaces, EHX_SCAN_F32 / _F16, small batches, sparse bitmaps, and the
+ * queries that scan hands on — by an exact pass over the bitmap's ALLOWED rows in slabs of 4096: the cost falls with the
+ * allowed share.  The call waits for the device once (it reads the allowed counts back); a Set that rewrites rows in place
+ * waits for the call like for any search.  Not on the graph walk.  DESIGN.md §e.20. */
+int ehx_knn_grouped_masked_device(ehx_space* s, void* stream, size_t n_queries, const float* d_queries, uint32_t k,
+                                  uint32_t per_group, const uint32_t* d_group_of, uint64_t n_labels, const uint32_t* d_masks,
+                                  uint32_t n_masks, uint64_t n_bits, const uint32_t* d_mask_of, uint64_t* d_out_ids,
+                                  float* d_out_dist, uint32_t* d_out_count);
 /* Exact range search: every row closer than a radius.  With D(q, x) the canonical distance ehx_knn reports (cosine, L2^2,
  * inner product as there), row x belongs to query i's answer iff D is not NaN and D <= d_radius[i] as a float comparison
  * (inclusive: a radius that equals a row's distance byte for byte includes that row; -Inf distances under inner product
