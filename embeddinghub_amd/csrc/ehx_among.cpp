@@ -19,10 +19,12 @@ constexpr const char* kAmongWhy = "filtered search over shards is not built yet"
 
 // an unsharded space, locked shared, scratch_mu held, its device current; everything is enqueued on `st`.
 // d_off == nullptr: every query shares d_ids[0, n_cand).  max_list: an upper bound of one list's length (0: n_cand) — it
-// sizes the grid only.
+// sizes the grid only.  d_end (with d_off; ehx_labeled.cpp): query q's list is d_ids[d_off[q], d_end[q]), so queries may share
+// a list inside ONE per-query launch; end_pairs: the lengths of those lists together (n_dist takes it; n_cand is then the
+// length of the id array the lists lie in).
 int ehx_impl::among_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k,
                            const uint64_t* d_ids, const uint64_t* d_off, size_t n_cand, size_t max_list, uint64_t* d_out_ids, float* d_out_dist,
-                           uint32_t* d_out_count, bool count_queries) {
+                           uint32_t* d_out_count, bool count_queries, const uint64_t* d_end, uint64_t end_pairs) {
   int rc;
   if ((rc = check_not_poisoned(s))) return rc;
   if ((rc = check_rows_fit_lds(s, "filtered search"))) return rc;   // (before anything is enqueued)
@@ -32,6 +34,7 @@ int ehx_impl::among_locked(ehx_space* s, hipStream_t st, size_t nq, const float*
   a.rows = rows_view(s, n_pub);
   a.cand_ids = d_ids;
   a.cand_off = d_off;
+  a.cand_end = d_off ? d_end : nullptr;
   a.n_cand = n_cand;
   a.nq = (uint32_t)nq;
   const uint64_t longest = std::max<uint64_t>(1, max_list && max_list < n_cand ? max_list : n_cand);
@@ -64,7 +67,7 @@ int ehx_impl::among_locked(ehx_space* s, hipStream_t st, size_t nq, const float*
   }
   if ((rc = s->clock.scan_end(st)) || (rc = s->clock.finish(st))) return rc;
   if (count_queries) s->n_queries += nq;
-  s->n_dist += d_off ? (uint64_t)n_cand : (uint64_t)nq * n_cand;
+  s->n_dist += a.cand_end ? end_pairs : d_off ? (uint64_t)n_cand : (uint64_t)nq * n_cand;
   return EHX_OK;
 }
 

@@ -187,6 +187,7 @@ int i8_radius_scan(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, cons
   a.allow = c.allow;
   a.allow_bits = c.allow_bits;
   a.allow_per_query = c.allow_per_query ? 1u : 0u;
+  a.allow_label = c.allow_label ? 1u : 0u;
   {
     std::lock_guard<std::mutex> ql(s->i8_enqueue_mu);   // (this batch's launches go onto the stream as one block)
     if ((rc = wait_searches_in_flight(s, st))) return rc;
@@ -254,6 +255,7 @@ int radius_knn(ehx_space* s, hipStream_t st, RadiusKnnBufs& w, uint64_t n_pub, c
   scan.allow = c.allow;
   scan.allow_bits = c.allow_bits;
   scan.allow_per_query = c.allow_per_query;
+  scan.allow_label = c.allow_label;
   scan.time_thr = true;
   scan.d_word = w.dWork.p;   // the rows re-ranked (the seed's sample included)
   if (!c.first_radius) {

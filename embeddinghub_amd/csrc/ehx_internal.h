@@ -517,6 +517,24 @@ struct ehx_space {
   // test hook: queries answered on the scan route, on the exact route, queries that overflowed, scan passes launched, calls
   // (ehx_knn_masked* and ehx_knn_masked_multi* both count here)
   std::atomic<uint64_t> masked_ctr[5] = {};
+  // exact kNN under a label column (ehx_labeled.cpp; scratch_mu): per device batch the compaction of the column for the
+  // batch's distinct wanted labels ("slots").  The lists, the scanning slots' tile prefixes and samples, the scan route's
+  // buffers and the grouping are the bitmap search's (masked.dList / dCum / dSample / scan / group: one answer serves both).
+  struct Labeled {
+    DevBuf<uint32_t> dBlock;     // [kLabelHead] wanted label of every query of a device batch | a copy of label_of[0, n_eff):
+                                 // ONE block, the int8 scan's flush reads both
+    DevBuf<uint32_t> dSlots;     // [slots] the ascending table | [slots] row counts | [slots] scanning index | [slots] cursors
+    DevBuf<uint16_t> dSlotOf;    // [n_eff] the slot of every row's label
+    DevBuf<uint64_t> dOff;       // [slots] where every slot's list starts in masked.dList | [scanning slots] the same by index
+    DevBuf<uint64_t> dRange;     // [queries] start | [queries] end of every query's list in the ONE per-query launch
+    DevBuf<uint32_t> dCol;       // a host call's staged label column, the rows below the row count
+    HostStage host;              // host form: queries, and ids | distances | counts
+  } labeled;
+  // test hook: queries answered on the scan route, on the list route, queries that overflowed, scan passes launched, calls
+  std::atomic<uint64_t> labeled_ctr[5] = {};
+  // test hook (scripts/bench_labeled.py's crossover sweep): 0 the cut decides; 1 every non-empty label takes the scan route
+  // where the int8 scan serves (a batch may then name at most 127 of them); 2 every label takes the list route
+  std::atomic<uint32_t> labeled_route{0};
   // exact range search under row bitmaps (ehx_rangem.cpp; scratch_mu): the compaction is the bitmap search's (masked), the
   // pools, control words and slot queries the range search's (range.dPool / dCtl / dSel); its own are the scan route's radii
   // (NaN for the queries of a device batch the scan does not answer), every list-route slot's list, the sub-batch of the
@@ -861,7 +879,8 @@ struct RadiusScan {
   const uint32_t* allow = nullptr;   // optional row bitmap allow[0, allow_bits) in the scan's flush
   uint32_t allow_bits = 0;
   bool allow_per_query = false;      // allow is the block of ScanArgsI8::allow_per_query: a bitmap per query
-  bool time_thr = false;             // the timed scan phase opens in front of the first threshold kernel, not behind it
+  bool allow_label = false;          // allow is the block of ScanArgsI8::allow_label: wanted labels | the label column
+  bool time_thr = false;            // the timed scan phase opens in front of the first threshold kernel, not behind it
   // rerank(i, last, a, sc) enqueues pass i's re-rank and records sc.clock.scan_end where its path's timed scan phase ends
   std::function<int(size_t, bool, const ScanArgsI8&, ehx_space::I8Set&)> rerank;
   const uint32_t* d_word = nullptr;  // [nq] the caller's words of the verdict
@@ -882,6 +901,7 @@ struct RadiusKnn {
   const uint32_t* allow = nullptr;     // optional row bitmap, as RadiusScan's
   uint32_t allow_bits = 0;
   bool allow_per_query = false;        // ... or the block of a bitmap per query, as RadiusScan's
+  bool allow_label = false;            // ... or the block of a label column, as RadiusScan's
   // stage 0, one of two.  first_radius(m, d_q, o, d_radius): enqueued in front of a batch's scan, writes the exact k-th
   // distance over ANY k rows the search may return (+Inf: none known) for its m queries; it may use o's rows, which are
   // written again behind it.  Or, without it, the seed inside the scan's timed phase: the strided sample of rows 0, stride,
@@ -981,14 +1001,45 @@ struct MaskedPlan {
 // compaction — and checked then, the outputs unwritten; or neither: every query is mask 0 and nothing is read back for it.
 int masked_plan(ehx_space* s, hipStream_t st, const MaskTable& tab, uint64_t n_bits, size_t nq, const uint32_t* mask_of,
                 const uint32_t* d_mask_of, MaskedPlan* p);
+// What the exact answer needs of compacted per-query row filters, whatever they were compacted from: a table of bitmaps
+// (masked_answer, ehx_masked.cpp) or the wanted labels of a label column (ehx_labeled.cpp).  Host arrays unless named d_.
+struct FilterView {
+  uint64_t n_pub = 0, n_eff = 0, list_rows = 0;   // list_rows: entries of d_list the filters' lists hold together
+  uint32_t n_tiles = 0, n_filters = 0;
+  const uint64_t* n_allowed = nullptr;   // [n_filters] rows the filter allows
+  const uint64_t* off = nullptr;         // [n_filters] its list: d_list + off[f] (ascending where the filter scans)
+  const uint32_t* filter_of = nullptr;   // [queries] checked; nullptr: every query is filter 0
+  const char* scans = nullptr;           // [n_filters] the filter takes the scan route (filter_scan_serves and the cut)
+  const uint32_t* cum = nullptr;         // [rows][n_tiles + 1] allowed rows before every tile, of the filters that scan
+  const uint32_t* scan_of = nullptr;     // [n_filters] the filter's row of cum and of the samples; nullptr: f itself
+  const uint64_t* d_list = nullptr;
+  const DevBuf<uint64_t>* sample = nullptr;   // [rows][256], filled by samples()
+  std::function<int()> samples;          // enqueues the scanning filters' samples (the scan route's stage 0 alone pays)
+  // the row test in the int8 scan's flush (RadiusKnn's allow fields); where it is per query, d_head is the head of the
+  // block — kTabWords words, rewritten for every device batch — and head_of[f] the word of a query under filter f
+  const uint32_t* allow = nullptr;
+  bool allow_per_query = false, allow_label = false;
+  uint32_t* d_head = nullptr;
+  const uint32_t* head_of = nullptr;
+  // the list route: a filter that at least shared_min queries of the batch name takes the shared-list kernel over their
+  // range; the others go through ONE per-query launch together, their [start | end) in d_range.  1: every filter shares.
+  uint32_t shared_min = 1;
+  DevBuf<uint64_t>* d_range = nullptr;
+  std::atomic<uint64_t>* ctr = nullptr;  // [5] scan route, list route, overflowed, scan passes, calls (the caller counts calls)
+};
+bool filter_scan_serves(const ehx_space* s, uint32_t k, uint64_t n_pub);   // the scan route serves this k on this prefix
+int filtered_answer(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, const FilterView& v,
+                    const ResultBlock& out);
 
 // ---- ehx_among.cpp ----
 // exact kNN among row ids on an unsharded space, locked shared, scratch_mu held, its device current (d_off == nullptr: one
 // list shared by every query; max_list: an upper bound of one list's length, 0 = n_cand)
 // count_queries = false: a stage of a larger search (the masked kNN's sample) — its pairs are counted, its queries are not
+// d_end (with d_off): query q's list is d_ids[d_off[q], d_end[q]) — queries may share a list — and end_pairs those lists'
+// lengths together; the public among entry points never pass it
 int among_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, const uint64_t* d_ids,
                  const uint64_t* d_off, size_t n_cand, size_t max_list, uint64_t* d_out_ids, float* d_out_dist,
-                 uint32_t* d_out_count, bool count_queries = true);
+                 uint32_t* d_out_count, bool count_queries = true, const uint64_t* d_end = nullptr, uint64_t end_pairs = 0);
 
 // ---- ehx_write.cpp ----
 int sync_stream(ehx_space* s, hipStream_t st);

@@ -214,6 +214,7 @@ inline float scan16_eps(uint32_t dims) { return 1.0e-3f + 2.0e-7f * (float)dims;
 constexpr uint32_t kSyncWordsI8 = 1024; // lock-step progress words of the int8 scan: [n_chunks <= 256][4 query tiles]
 constexpr uint32_t kMerged8 = 256;     // default width of the running best list of the int8 pipeline
 constexpr uint32_t kMerged8Max = 1024; // widest list (a space widens its list when queries go uncertified: ehx_flat.cpp)
+constexpr uint32_t kLabelHead = 2048;  // wanted labels in front of the label column of ScanArgsI8::allow_label's block
 struct ScanArgsI8 {
   const int8_t* Q;        // [q_tiles][ld/64 + 3][256][64] int8 query tiles, scan8 stage-blocked layout
   const int8_t* X;        // scan copy, scan8_index layout; cap % 256 == 0
@@ -245,6 +246,9 @@ struct ScanArgsI8 {
   uint32_t allow_bits = 0;          // row id is >= allow_bits or whose bit is clear is dropped before it takes a pool slot
   uint32_t allow_per_query = 0;     // 1: a bitmap per query (ehx_knn_masked_multi*, several masks) — allow is ONE block,
                                     // [q_tiles * 256] word offsets from its start (query q: allow[q]) | the bitmaps
+  uint32_t allow_label = 0;         // 1: a label column instead of bitmaps (ehx_knn_labeled*) — allow is ONE block,
+                                    // [kLabelHead >= q_tiles * 256] wanted labels (query q: allow[q]) | label_of[0,
+                                    // allow_bits); a hit survives iff its row's label is its query's
   // The flat int8 chain's long passes only (ehx_flat.cpp; the compile-time-slot loop without a bitmap): every other caller
   // leaves both null and launches the kernels it always launched.
   const uint32_t* bounds = nullptr;  // [n_chunks + 1] tile range of every chunk, relative to tile0 (the share planner's table,
@@ -465,6 +469,8 @@ struct AmongArgs {
   uint64_t n_cand;
   uint32_t nq;
   uint32_t n_blocks;         // workgroups per query (or query tile): each walks its steps of the list in a grid-stride loop
+  const uint64_t* cand_end;  // optional, with cand_off: [nq], query q owns [off[q], end[q]) — queries may then share a list;
+                             // nullptr: off + 1
 };
 bool among_tiled(const AmongArgs& a);          // the shared-list kernel serves (cand_off == nullptr and the tiles fit in LDS)
 uint32_t among_max_ld();                       // longest row stride (floats) the kernels take: a prepared query must fit in LDS
@@ -554,6 +560,30 @@ hipError_t launch_masked_fill(const uint32_t* maps, uint64_t stride, uint32_t n_
                               const uint32_t* cum, const MaskedOffsets& off, uint64_t* list, hipStream_t st);
 hipError_t launch_masked_samples(const uint64_t* list, const MaskedOffsets& off, const uint32_t* cum, uint32_t n_masks,
                                  uint32_t n_tiles, uint64_t* sample, hipStream_t st);
+// exact kNN under a label column (k_labeled.hip; ehx_knn_labeled*): compaction of the rows [0, n_rows) by label, for the
+// n_slots <= kLabeledMaxSlots distinct wanted labels of one device batch (table: ascending, in device memory).
+//   launch_labeled_count   slot_of[r] = the slot of row r's label (kLabeledNoSlot: nobody wants it), count[slot] += 1
+//                          (count: zero before the launch is enqueued — the launch clears it itself)
+//   launch_labeled_tiles   for the slots that scan (scan_of[slot] < n_scan <= kLabeledMaxScan, else kLabeledNoScan):
+//                          cum[scan][0 .. n_tiles] = the slot's rows before every 256-row tile, the last entry their number
+//                          (the layout masked_passes reads)
+//   launch_labeled_fill    every slot's list of row ids at list + off[slot]: ascending for the slots that scan (placed by
+//                          cum), in any order for the others (placed by a cursor per slot: cursor[n_slots], cleared here)
+//   launch_labeled_samples sample[256 scan + i] = the i-th of every ceil(rows / 256)-th id of a scanning slot's list by rank
+//                          (scan_off[scan]: where its list starts)
+constexpr uint32_t kLabeledMaxSlots = 2048;   // the queries of one device batch (kSideChunk)
+constexpr uint32_t kLabeledMaxScan = 127;     // labels of more than max(1024, n / 128) rows: n / max(1024, n / 128) <= 128, strictly below
+constexpr uint16_t kLabeledNoSlot = 0xFFFFu;
+constexpr uint32_t kLabeledNoScan = 0xFFFFFFFFu;
+hipError_t launch_labeled_count(const uint32_t* label_of, uint64_t n_rows, const uint32_t* table, uint32_t n_slots,
+                                uint16_t* slot_of, uint32_t* count, hipStream_t st);
+hipError_t launch_labeled_tiles(const uint16_t* slot_of, uint64_t n_rows, uint32_t n_tiles, const uint32_t* scan_of,
+                                uint32_t n_scan, uint32_t* cum, hipStream_t st);
+hipError_t launch_labeled_fill(const uint16_t* slot_of, uint64_t n_rows, uint32_t n_tiles, uint32_t n_slots,
+                               const uint64_t* off, const uint32_t* scan_of, uint32_t n_scan, const uint32_t* cum,
+                               uint32_t* cursor, uint64_t* list, hipStream_t st);
+hipError_t launch_labeled_samples(const uint64_t* list, const uint64_t* scan_off, const uint32_t* cum, uint32_t n_scan,
+                                  uint32_t n_tiles, uint64_t* sample, hipStream_t st);
 // radius[q] = dist[q][k - 1] when cnt[q] >= k (result lists [nq][k]), else +Inf
 hipError_t launch_masked_radius(const float* dist, const uint32_t* cnt, uint32_t nq, uint32_t k, float* radius, hipStream_t st);
 // word w of a bitmap cut at n_bits (bits of the last word beyond n_bits and words beyond it read as 0)

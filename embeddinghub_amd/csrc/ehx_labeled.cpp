@@ -1,0 +1,223 @@
+// Exact kNN under a label column: ehx_knn_labeled (host pointers) and ehx_knn_labeled_device.  One opaque 32-bit label per
+// row, one wanted label per query; row r is allowed for query i iff r < n_eff = min(the call's ONE snapshot of the row count,
+// n_labels) and label_of[r] == want[i].  Row i of the answer is, byte for byte, ehx_knn_masked_device's for query i alone
+// under the bitmap of those rows.  The number of distinct wanted labels is not limited: a call is served in device batches
+// of kSideChunk queries, and per batch
+//   slots        the host sorts and de-duplicates the batch's wanted labels: at most 2048 "slots"
+//   compaction   k_labeled.hip: per-slot row counts (read back: the first wait), every slot's list of row ids back to back in
+//                masked.dList, and — for the slots that scan — the rows before every 256-row tile (read back: the second wait,
+//                taken only where some slot scans), an ascending list and the by-rank sample
+//   answer       the bitmap search's (filtered_answer, ehx_masked.cpp): its routing rule per slot, its grouping, its ONE pass
+//                plan, its first radius and its re-runs, with the row test of the int8 scan's flush "the row's label is the
+//                query's" (kMaskLabel, k_flati8.hip: ONE block, every query's wanted label | a copy of the column)
+// At most 127 slots can scan: a slot scans only with more than masked_exact_cut(n) = max(1024, n / 128) rows, the slots'
+// rows are disjoint, and n / max(1024, n / 128) <= 128 with a strict "more than" — so the tile prefixes are a table of at
+// most 127 x tiles, never slots x tiles.  The cut itself is CARRIED OVER from the bitmap search, where it was measured for a
+// list shared by the whole batch (scripts/bench_masked.py); it was not measured for this call — scripts/bench_labeled.py
+// leg (c) records where the two routes cross here.
+// The list route: a slot that at least kLabeledSharedMin queries of the batch name takes the shared-list tile kernel over
+// their range, as every mask does; all the others — in a batch of 1024 tenants, all of them — go through ONE per-query-list
+// launch (AmongArgs::cand_end lets queries of one slot name the same list), not one launch per label.
+// The device form waits once for d_want (the whole call's), then per device batch at most twice for the compaction — the
+// counts, and the scanning slots' tile prefixes — whatever the number of labels the batch names; the scan route's verdict is
+// radius_knn's one wait per device batch, as under bitmaps.
+// Entry scaffold and host staging are ehx_call.cpp's (search_shared / on_device, HostStage).
+#include "ehx_internal.h"
+
+namespace {
+
+constexpr const char* kLabeledWhy = "filtered search over shards is not built yet";
+constexpr uint32_t kLabeledSharedMin = kAmongTileQ;   // one query tile of the shared-list kernel: a choice, not measured
+static_assert(kSideChunk <= kLabeledMaxSlots, "a device batch names at most one slot per query");
+static_assert(kTabWords == kLabelHead, "the head of the label block is the head filtered_answer rewrites per device batch");
+
+int labeled_check(const ehx_space* s, size_t nq, uint32_t k, const void* q, const void* label_of, uint64_t n_labels,
+                  const void* want, const void* o_ids, const void* o_dist, const void* o_cnt) {
+  if (!s) return fail(EHX_EINVAL, "space is NULL");   // (before the device is looked for)
+  int rc = ehx_init(nullptr, 0);
+  if (rc) return rc;
+  if ((rc = check_batch_call(s, nq, k, "k", false, o_ids && o_dist && o_cnt && (!nq || q)))) return rc;
+  if (n_labels && !label_of) return fail(EHX_EINVAL, "NULL label_of with n_labels = %llu", (unsigned long long)n_labels);
+  if (!want) return fail(EHX_EINVAL, "NULL want");
+  return EHX_OK;
+}
+
+// One device batch of m <= kSideChunk queries under want[0, m) (host memory) over the prefix of n_eff rows of d_label_of.
+// *col_copied: the flush's copy of the column is in place (made once per call, and only where some slot scans).
+int labeled_batch(ehx_space* s, hipStream_t st, uint64_t n_pub, uint64_t n_eff, size_t m, const float* d_queries, uint32_t k,
+                  const uint32_t* d_label_of, const uint32_t* want, bool* col_copied, const ResultBlock& out) {
+  int rc;
+  ehx_space::Labeled& w = s->labeled;
+  ehx_space::Masked& mw = s->masked;
+  const uint32_t n_tiles = (uint32_t)((n_eff + kTileRows16 - 1) / kTileRows16);
+  // the slots: the batch's distinct wanted labels, ascending, and the slot of every query
+  std::vector<uint32_t> table(want, want + m), slot_of(m);
+  std::sort(table.begin(), table.end());
+  table.erase(std::unique(table.begin(), table.end()), table.end());
+  const uint32_t n_slots = (uint32_t)table.size();
+  for (size_t j = 0; j < m; ++j) slot_of[j] = (uint32_t)(std::lower_bound(table.begin(), table.end(), want[j]) - table.begin());
+  uint32_t* d_table = w.dSlots.p;
+  uint32_t* d_count = d_table + kLabeledMaxSlots;
+  uint32_t* d_scan_of = d_count + kLabeledMaxSlots;
+  uint32_t* d_cursor = d_scan_of + kLabeledMaxSlots;
+  // (pageable host memory, here and below: the runtime stages it before the call returns)
+  HIP_TRY(hipMemcpyAsync(d_table, table.data(), n_slots * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  std::vector<uint32_t> count(n_slots, 0u);
+  if (n_tiles) {
+    HIP_TRY(launch_labeled_count(d_label_of, n_eff, d_table, n_slots, w.dSlotOf.p, d_count, st));
+    HIP_TRY(hipMemcpyAsync(count.data(), d_count, n_slots * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));   // the first wait
+  }
+  // routing per slot (the bitmap search's rule), where the lists start, and the scanning slots' indices
+  const bool scan_serves = filter_scan_serves(s, k, n_pub);
+  const uint32_t forced = s->labeled_route.load(std::memory_order_relaxed);   // (test hook: the bench's crossover sweep)
+  const uint64_t cut = forced == 1 ? 0 : forced == 2 ? ~0ull : masked_exact_cut(n_pub);
+  std::vector<uint64_t> n_allowed(n_slots), off(n_slots), scan_off;
+  std::vector<char> scans(n_slots);
+  std::vector<uint32_t> scan_of(n_slots, kLabeledNoScan);
+  uint64_t total = 0;
+  for (uint32_t f = 0; f < n_slots; ++f) {
+    n_allowed[f] = count[f];
+    off[f] = total;
+    total += count[f];
+    scans[f] = scan_serves && n_allowed[f] > cut;
+    if (!scans[f]) continue;
+    scan_of[f] = (uint32_t)scan_off.size();
+    scan_off.push_back(off[f]);
+  }
+  const uint32_t n_scan = (uint32_t)scan_off.size();
+  if (n_scan > kLabeledMaxScan || total > n_eff)   // (disjoint sets of more than max(1024, n / 128) rows each: at most 127)
+    return fail(EHX_EINTERNAL, "label compaction: %u scanning labels, %llu listed rows of %llu", n_scan,
+                (unsigned long long)total, (unsigned long long)n_eff);
+  std::vector<uint32_t> cum((size_t)n_scan * (n_tiles + 1), 0u);
+  if ((rc = mw.dList.ensure(std::max<uint64_t>(total, 1)))) return rc;
+  if (n_tiles) {
+    uint64_t* d_off = w.dOff.p;
+    uint64_t* d_scan_off = d_off + kLabeledMaxSlots;
+    HIP_TRY(hipMemcpyAsync(d_off, off.data(), n_slots * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_scan_of, scan_of.data(), n_slots * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    if (n_scan) {
+      if ((rc = mw.dCum.ensure(cum.size()))) return rc;
+      HIP_TRY(hipMemcpyAsync(d_scan_off, scan_off.data(), n_scan * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+      HIP_TRY(launch_labeled_tiles(w.dSlotOf.p, n_eff, n_tiles, d_scan_of, n_scan, mw.dCum.p, st));
+      HIP_TRY(hipMemcpyAsync(cum.data(), mw.dCum.p, cum.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(launch_labeled_fill(w.dSlotOf.p, n_eff, n_tiles, n_slots, d_off, d_scan_of, n_scan, mw.dCum.p, d_cursor, mw.dList.p, st));
+    if (n_scan) {
+      if (!*col_copied)   // the flush's copy of the column: 4 bytes per row, once per call
+        HIP_TRY(hipMemcpyAsync(w.dBlock.p + kLabelHead, d_label_of, n_eff * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+      *col_copied = true;
+      HIP_TRY(hipStreamSynchronize(st));   // the second wait: the host plans the passes from the tile prefixes
+    }
+  }
+  FilterView v;
+  v.n_pub = n_pub;
+  v.n_eff = n_eff;
+  v.list_rows = total;
+  v.n_tiles = n_tiles;
+  v.n_filters = n_slots;
+  v.n_allowed = n_allowed.data();
+  v.off = off.data();
+  v.filter_of = slot_of.data();
+  v.scans = scans.data();
+  v.cum = cum.data();
+  v.scan_of = scan_of.data();
+  v.d_list = mw.dList.p;
+  v.sample = &mw.dSample;
+  v.samples = [&]() -> int {
+    if (int r = mw.dSample.ensure((size_t)n_scan * 256)) return r;
+    HIP_TRY(launch_labeled_samples(mw.dList.p, w.dOff.p + kLabeledMaxSlots, mw.dCum.p, n_scan, n_tiles, mw.dSample.p, st));
+    return EHX_OK;
+  };
+  v.allow = w.dBlock.p;
+  v.allow_label = true;
+  v.d_head = w.dBlock.p;
+  v.head_of = table.data();   // (the head word of a query is its wanted label itself)
+  v.shared_min = kLabeledSharedMin;
+  v.d_range = &w.dRange;
+  v.ctr = s->labeled_ctr;
+  return filtered_answer(s, st, m, d_queries, k, v, out);
+}
+
+// an unsharded space, locked shared, scratch_mu held, its device current; everything is enqueued on `st`.  want: in host
+// memory; or d_want, read back once (the outputs unwritten until then).
+int labeled_locked(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, const float* d_queries, uint32_t k,
+                   const uint32_t* d_label_of, uint64_t n_labels, const uint32_t* want, const uint32_t* d_want,
+                   const ResultBlock& out) {
+  int rc;
+  if ((rc = check_not_poisoned(s))) return rc;
+  if ((rc = check_rows_fit_lds(s, "filtered search"))) return rc;   // (before anything is enqueued)
+  s->labeled_ctr[4] += 1;
+  ehx_space::Labeled& w = s->labeled;
+  const uint64_t n_eff = std::min<uint64_t>(n_labels, n_pub);   // (row ids are 32 bits wide: n_pub < 2^32)
+  if ((rc = w.dBlock.ensure(kLabelHead + std::max<uint64_t>(n_eff, 1))) || (rc = w.dSlotOf.ensure(std::max<uint64_t>(n_eff, 1))) ||
+      (rc = w.dSlots.ensure(4 * (size_t)kLabeledMaxSlots)) || (rc = w.dOff.ensure((size_t)kLabeledMaxSlots + kLabeledMaxScan + 1)))
+    return rc;
+  // (earlier calls' launches on other streams may still read the block, the lists and the samples)
+  if ((rc = wait_searches_in_flight(s, st))) return rc;
+  std::vector<uint32_t> want_read;
+  if (!want) {
+    want_read.resize(nq);
+    HIP_TRY(hipMemcpyAsync(want_read.data(), d_want, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    want = want_read.data();
+  }
+  bool col_copied = false;
+  for (size_t q0 = 0; q0 < nq; q0 += kSideChunk) {
+    const size_t m = std::min(kSideChunk, nq - q0);
+    if ((rc = labeled_batch(s, st, n_pub, n_eff, m, d_queries + q0 * s->dims, k, d_label_of, want + q0, &col_copied,
+                            out.from(q0, m))))
+      return rc;
+  }
+  return EHX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ehx_knn_labeled_device(ehx_space* s, void* stream, size_t n_queries, const float* d_queries, uint32_t k,
+                           const uint32_t* d_label_of, uint64_t n_labels, const uint32_t* d_want, uint64_t* d_out_ids,
+                           float* d_out_dist, uint32_t* d_out_count) {
+  if (int rc = labeled_check(s, n_queries, k, d_queries, d_label_of, n_labels, d_want, d_out_ids, d_out_dist, d_out_count))
+    return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  return search_on_device(s, "ehx_knn_labeled_device", kLabeledWhy, n_queries, &st, [&] {
+    // the ONE read of the row count: the lists name rows below it only, and every later stage sees at least this prefix
+    const uint64_t n_pub = s->n.load(std::memory_order_acquire);
+    return labeled_locked(s, st, n_pub, n_queries, d_queries, k, d_label_of, n_labels, nullptr, d_want,
+                          ResultBlock{d_out_ids, d_out_dist, d_out_count, nullptr, n_queries, k});
+  });
+}
+
+int ehx_knn_labeled(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, const uint32_t* label_of,
+                    uint64_t n_labels, const uint32_t* want, uint64_t* out_ids, float* out_dist, uint32_t* out_count) {
+  if (int rc = labeled_check(s, n_queries, k, queries, label_of, n_labels, want, out_ids, out_dist, out_count)) return rc;
+  return search_on_device(s, "ehx_knn_labeled", kLabeledWhy, n_queries, nullptr, [&]() -> int {
+    int rc;
+    const uint64_t n_pub = s->n.load(std::memory_order_acquire);   // the ONE read of the row count
+    // (labels at or above it are never looked at: they are not even copied)
+    const uint64_t n_eff = std::min<uint64_t>(n_labels, n_pub);
+    HostStage& h = s->labeled.host;
+    if ((rc = s->labeled.dCol.ensure(std::max<uint64_t>(n_eff, 1))) || (rc = h.up(s->stream, queries, n_queries, s->dims, k, false)))
+      return rc;
+    if (n_eff) HIP_TRY(hipMemcpyAsync(s->labeled.dCol.p, label_of, n_eff * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
+    if ((rc = labeled_locked(s, s->stream, n_pub, n_queries, h.q, k, s->labeled.dCol.p, n_labels, want, nullptr, h.out))) return rc;
+    return h.out.copy_out(s->stream, out_ids, out_dist, out_count, nullptr);
+  });
+}
+
+// test hook, not part of the ABI: queries answered on the scan route, on the list route, queries that overflowed, scan
+// passes launched, calls
+void ehx_test_labeled_counters(ehx_space* s, uint64_t out[5]) {
+  for (int i = 0; i < 5; ++i) out[i] = s ? s->labeled_ctr[i].load(std::memory_order_relaxed) : 0;
+}
+
+// test hook, not part of the ABI: 0 the cut decides the route (the default), 1 the scan route for every non-empty label where
+// the int8 scan serves (more than 127 such labels in one batch: EHX_EINTERNAL), 2 the list route for every label — how
+// scripts/bench_labeled.py finds where they cross
+void ehx_test_labeled_route(ehx_space* s, uint32_t route) {
+  if (s) s->labeled_route.store(route <= 2u ? route : 0u, std::memory_order_relaxed);
+}
+
+}  // extern "C"

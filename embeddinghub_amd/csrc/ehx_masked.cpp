@@ -4,7 +4,9 @@
 // snapshot of the row count and bit r & 31 of word r >> 5 is set; the answer is ehx_knn_among's with the ascending list of
 // allowed rows, byte for byte (k_radius.hip's header has the argument), and row i of a table's answer is the one-bitmap
 // answer for query i alone under its bitmap.  One bitmap is a table of one: ONE plan (masked_plan) and ONE answer over it
-// (masked_answer) serve every entry point, the graph walk's exact route included.
+// (masked_answer) serve every entry point, the graph walk's exact route included.  The answer itself is filtered_answer over
+// a FilterView — "which row test in the flush, which compacted table" — which the search under a label column
+// (ehx_labeled.cpp) shares: masked_answer only states the bitmaps' view.
 //   compaction   every bitmap in one set of launches (k_masked.hip): allowed rows before every 256-row tile per mask, read
 //                back ONCE (the host plans the passes from them) together with mask_of (a table's device form), and the
 //                ascending lists, back to back (one mask: filled in front of that wait; several: behind it, placed by
@@ -168,72 +170,83 @@ int masked_plan(ehx_space* s, hipStream_t st, const MaskTable& tab, uint64_t n_b
 
 }  // namespace ehx_impl
 
-namespace {
+namespace ehx_impl {
 
-// the exact answer over a plan: per mask the scan route where it serves, else the list scan
-int masked_answer(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, const MaskedPlan& p,
-                  const ResultBlock& out) {
+bool filter_scan_serves(const ehx_space* s, uint32_t k, uint64_t n_pub) {
+  return k <= kMaskedScanMaxK && i8_serves_radius(s, n_pub);
+}
+
+// The exact answer over compacted row filters — bitmaps (masked_answer, below) or the labels of a column (ehx_labeled.cpp):
+// per filter the scan route where v.scans says so, else the list scan.  Only the row test in the scan's flush (v.allow*), the
+// table the compaction filled and the counters differ between the two.
+int filtered_answer(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, const FilterView& v,
+                    const ResultBlock& out) {
   ehx_space::Masked& w = s->masked;
-  const uint32_t n_masks = p.n_masks, n_tiles = p.n_tiles;
-  const bool per_query = n_masks > 1;   // one mask: the batch's ONE bitmap in the flush, nothing grouped, no offsets
-  // routing, and the order the queries are answered in: the scan route's first, then by mask
-  const bool scan_serves = k <= kMaskedScanMaxK && i8_serves_radius(s, p.n_pub);
-  std::vector<char> scans(n_masks);
-  for (uint32_t m = 0; m < n_masks; ++m) scans[m] = scan_serves && p.n_allowed[m] > masked_exact_cut(p.n_pub);
+  const uint32_t n_filters = v.n_filters, n_tiles = v.n_tiles;
+  auto filter_at = [&](size_t i) { return v.filter_of ? v.filter_of[i] : 0u; };
+  auto row_of = [&](uint32_t f) { return (size_t)(v.scan_of ? v.scan_of[f] : f); };   // of cum and of the samples
+  // routing, and the order the queries are answered in: the scan route's first, then by filter — with v.shared_min > 1 the
+  // list route's filters that fewer queries name behind the others: they take ONE per-query launch together
+  std::vector<uint32_t> named(v.shared_min > 1 ? n_filters : 0, 0u);
+  for (size_t i = 0; i < nq && !named.empty(); ++i) named[filter_at(i)] += 1;
+  auto tier = [&](uint32_t f) { return v.scans[f] ? 0u : (named.empty() || named[f] >= v.shared_min) ? 1u : 2u; };
   auto place = [&](uint32_t i) {
-    const uint32_t m = p.mask_of ? p.mask_of[i] : 0u;
-    return (scans[m] ? 0u : kMaskedMaxMasks) + m;
+    const uint32_t f = filter_at(i);
+    return (uint64_t)tier(f) * n_filters + f;
   };
-  std::vector<uint32_t> idx(nq), gm(nq);   // gm: the mask of every query in that order
+  std::vector<uint32_t> idx(nq), gm(nq);   // gm: the filter of every query in that order
   for (size_t i = 0; i < nq; ++i) idx[i] = (uint32_t)i;
   auto before = [&](uint32_t a, uint32_t b) { return place(a) < place(b); };
-  const bool in_order = std::is_sorted(idx.begin(), idx.end(), before);   // (one mask: always)
+  const bool in_order = std::is_sorted(idx.begin(), idx.end(), before);   // (one filter: always)
   if (!in_order) std::stable_sort(idx.begin(), idx.end(), before);
-  size_t n_scan = 0;
+  size_t n_scan = 0, n_shared = 0;
   for (size_t i = 0; i < nq; ++i) {
-    gm[i] = p.mask_of ? p.mask_of[idx[i]] : 0u;
-    n_scan += scans[gm[i]];
+    gm[i] = filter_at(idx[i]);
+    n_scan += tier(gm[i]) == 0u;
+    n_shared += tier(gm[i]) == 1u;
   }
-  // [b, e): the next run of queries of one mask in [b, end)
+  // [b, e): the next run of queries of one filter in [b, end)
   auto run_end = [&](size_t b, size_t end) {
     size_t e = b + 1;
     while (e < end && gm[e] == gm[b]) ++e;
     return e;
   };
-  auto exact = [&](uint32_t m, size_t n, const float* q, uint64_t* ids, float* dist, uint32_t* cnt) {
-    return among_locked(s, st, n, q, k, w.dList.p + p.off.off[m], nullptr, p.n_allowed[m], 0, ids, dist, cnt);
+  auto exact = [&](uint32_t f, size_t n, const float* q, uint64_t* ids, float* dist, uint32_t* cnt) {
+    return among_locked(s, st, n, q, k, v.d_list + v.off[f], nullptr, v.n_allowed[f], 0, ids, dist, cnt);
   };
 
   auto answer = [&](size_t, const float* gq, uint64_t* ids, float* dist, uint32_t* cnt) -> int {
     if (n_scan) {
-      // ONE pass plan: the allowed rows seen are, tile by tile, those of whichever scanned mask has seen most
+      // ONE pass plan: the allowed rows seen are, tile by tile, those of whichever scanned filter has seen most
       std::vector<uint32_t> seen((size_t)n_tiles + 1, 0u);
       for (size_t b = 0; b < n_scan; b = run_end(b, n_scan)) {
-        const uint32_t* c = p.cum_of(gm[b]);
+        const uint32_t* c = v.cum + row_of(gm[b]) * ((size_t)n_tiles + 1);
         for (size_t t = 0; t <= n_tiles; ++t) seen[t] = std::max(seen[t], c[t]);
       }
       RadiusKnn c;
       c.passes = masked_passes(seen, n_tiles);
-      c.allow = per_query ? w.dBlock.p : p.d_maps;
-      c.allow_bits = (uint32_t)p.n_eff;
-      c.allow_per_query = per_query;
+      c.allow = v.allow;
+      c.allow_bits = (uint32_t)v.n_eff;
+      c.allow_per_query = v.allow_per_query;
+      c.allow_label = v.allow_label;
       c.out = ResultBlock{ids, dist, cnt, nullptr, n_scan, k};
-      std::vector<uint32_t> offs(per_query ? kTabWords : 0);
-      // stage 0 of a device batch [q0, q0 + m): with several masks its queries' word offsets into the block; per mask the
-      // exact k nearest of the mask's sample by the list scan, into the batch's rows of the output (every query's row is
-      // written again, by the last pass or by the exact route; its queries are not counted there: the verdict counts every
-      // query once): their k-th distance is the first radius, +Inf while the sample gives fewer than k
+      std::vector<uint32_t> head(v.d_head ? kTabWords : 0);
+      // stage 0 of a device batch [q0, q0 + m): where the flush tests per query, the head of its block — every query's word
+      // (its bitmap's offset, or its wanted label); per filter the exact k nearest of the filter's sample by the list scan,
+      // into the batch's rows of the output (every query's row is written again, by the last pass or by the exact route; its
+      // queries are not counted there: the verdict counts every query once): their k-th distance is the first radius, +Inf
+      // while the sample gives fewer than k
       c.first_radius = [&](size_t m, const float* q, const ResultBlock& o, float* d_radius) -> int {
         const size_t q0 = (size_t)(q - gq) / s->dims;
-        if (per_query) {
-          for (size_t j = 0; j < kTabWords; ++j)   // (padding queries: any bitmap, they collect nothing)
-            offs[j] = (uint32_t)(kTabWords + (uint64_t)gm[q0 + std::min(j, m - 1)] * p.words);
-          HIP_TRY(hipMemcpyAsync(w.dBlock.p, offs.data(), kTabWords * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        if (v.d_head) {
+          for (size_t j = 0; j < kTabWords; ++j)   // (padding queries: any word, they collect nothing)
+            head[j] = v.head_of[gm[q0 + std::min(j, m - 1)]];
+          HIP_TRY(hipMemcpyAsync(v.d_head, head.data(), kTabWords * sizeof(uint32_t), hipMemcpyHostToDevice, st));
         }
         for (size_t b = q0; b < q0 + m;) {
           const size_t e = run_end(b, q0 + m), j = b - q0;
-          const uint64_t a = p.n_allowed[gm[b]], stride = (a + kMaskedSample - 1) / kMaskedSample;
-          if (int r = among_locked(s, st, e - b, q + j * s->dims, k, w.dSample.p + (size_t)gm[b] * kMaskedSample, nullptr,
+          const uint64_t a = v.n_allowed[gm[b]], stride = (a + kMaskedSample - 1) / kMaskedSample;
+          if (int r = among_locked(s, st, e - b, q + j * s->dims, k, v.sample->p + row_of(gm[b]) * kMaskedSample, nullptr,
                                    (size_t)((a + stride - 1) / stride), 0, o.ids + j * k, o.dist + j * k, o.cnt + j, false))
             return r;
           b = e;
@@ -241,44 +254,105 @@ int masked_answer(ehx_space* s, hipStream_t st, size_t nq, const float* d_querie
         HIP_TRY(launch_masked_radius(o.dist, o.cnt, (uint32_t)m, k, d_radius, st));
         return EHX_OK;
       };
-      // the flagged queries of a device batch, mask by mask
+      // the flagged queries of a device batch, filter by filter
       c.handed = [&](size_t q0, const std::vector<uint32_t>& todo, const float* q, const ResultBlock& o) -> int {
         for (size_t b = 0; b < todo.size();) {
-          const uint32_t m = gm[q0 + todo[b]];
+          const uint32_t f = gm[q0 + todo[b]];
           size_t e = b + 1;
-          while (e < todo.size() && gm[q0 + todo[e]] == m) ++e;
+          while (e < todo.size() && gm[q0 + todo[e]] == f) ++e;
           const std::vector<uint32_t> part(todo.begin() + b, todo.begin() + e);
           if (int r = w.scan.sub.rerun(
                   s, st, q, part, k,
-                  [&](size_t n, const float* sq, uint64_t* i2, float* d2, uint32_t* c2) { return exact(m, n, sq, i2, d2, c2); },
+                  [&](size_t n, const float* sq, uint64_t* i2, float* d2, uint32_t* c2) { return exact(f, n, sq, i2, d2, c2); },
                   o.ids, o.dist, o.cnt))
             return r;
           b = e;
         }
         return EHX_OK;
       };
-      // (the masks' samples: stage 0 of the scan route alone, so the exact route does not pay for them)
-      if (int r = w.dSample.ensure((size_t)n_masks * kMaskedSample)) return r;
-      HIP_TRY(launch_masked_samples(w.dList.p, p.off, w.dCum.p, n_masks, n_tiles, w.dSample.p, st));
+      // (the filters' samples: stage 0 of the scan route alone, so the exact route does not pay for them)
+      if (int r = v.samples()) return r;
       RadiusKnnTally t;
-      const int r = radius_knn(s, st, w.scan, p.n_pub, gq, c, &t);
+      const int r = radius_knn(s, st, w.scan, v.n_pub, gq, c, &t);
       s->n_queries += t.queries - t.handed;   // (among_locked counts the rest)
-      s->masked_ctr[0] += t.queries - t.handed;
-      s->masked_ctr[1] += t.handed;
-      s->masked_ctr[2] += t.overflowed;
-      s->masked_ctr[3] += t.batches * c.passes.size();
+      v.ctr[0] += t.queries - t.handed;
+      v.ctr[1] += t.handed;
+      v.ctr[2] += t.overflowed;
+      v.ctr[3] += t.batches * c.passes.size();
       if (r) return r;
     }
-    for (size_t b = n_scan; b < nq;) {   // the exact route: one shared list per mask
-      const size_t e = run_end(b, nq);
-      s->masked_ctr[1] += e - b;
+    for (size_t b = n_scan; b < n_scan + n_shared;) {   // the exact route: one shared list per filter
+      const size_t e = run_end(b, n_scan + n_shared);
+      v.ctr[1] += e - b;
       if (int r = exact(gm[b], e - b, gq + b * s->dims, ids + b * k, dist + b * k, cnt + b)) return r;
       b = e;
+    }
+    // ... and the filters that few queries name: ONE launch, a list per query, queries of one filter naming the same list
+    if (const size_t b = n_scan + n_shared; b < nq) {
+      const size_t n = nq - b;
+      std::vector<uint64_t> range(2 * n);   // [n] where every query's list starts | [n] where it ends
+      uint64_t pairs = 0, longest = 0;
+      for (size_t j = 0; j < n; ++j) {
+        const uint32_t f = gm[b + j];
+        range[j] = v.off[f];
+        range[n + j] = v.off[f] + v.n_allowed[f];
+        pairs += v.n_allowed[f];
+        longest = std::max(longest, v.n_allowed[f]);
+      }
+      if (int r = v.d_range->ensure(2 * n)) return r;
+      // (pageable host memory: the runtime stages it before the call returns)
+      HIP_TRY(hipMemcpyAsync(v.d_range->p, range.data(), range.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+      v.ctr[1] += n;
+      if (int r = among_locked(s, st, n, gq + b * s->dims, k, v.d_list, v.d_range->p, (size_t)v.list_rows, (size_t)longest,
+                               ids + b * k, dist + b * k, cnt + b, true, v.d_range->p + n, pairs))
+        return r;
     }
     return EHX_OK;
   };
   if (in_order) return answer(nq, d_queries, out.ids, out.dist, out.cnt);
   return w.group.rerun(s, st, d_queries, idx, k, answer, out.ids, out.dist, out.cnt);
+}
+
+}  // namespace ehx_impl
+
+namespace {
+
+// the exact answer over a plan of bitmaps: filtered_answer with the bitmap — the batch's ONE, or one per query — in the flush
+int masked_answer(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, const MaskedPlan& p,
+                  const ResultBlock& out) {
+  ehx_space::Masked& w = s->masked;
+  const uint32_t n_masks = p.n_masks;
+  const bool per_query = n_masks > 1;   // one mask: the batch's ONE bitmap in the flush, nothing grouped, no offsets
+  const bool scan_serves = filter_scan_serves(s, k, p.n_pub);
+  std::vector<char> scans(n_masks);
+  std::vector<uint32_t> head_of(per_query ? n_masks : 0);   // the word offset of every bitmap in the block
+  for (uint32_t m = 0; m < n_masks; ++m) {
+    scans[m] = scan_serves && p.n_allowed[m] > masked_exact_cut(p.n_pub);
+    if (per_query) head_of[m] = (uint32_t)(kTabWords + (uint64_t)m * p.words);
+  }
+  FilterView v;
+  v.n_pub = p.n_pub;
+  v.n_eff = p.n_eff;
+  v.n_tiles = p.n_tiles;
+  v.n_filters = n_masks;
+  v.n_allowed = p.n_allowed.data();
+  v.off = p.off.off;
+  v.filter_of = p.mask_of;
+  v.scans = scans.data();
+  v.cum = p.cum.data();
+  v.d_list = w.dList.p;
+  v.sample = &w.dSample;
+  v.allow = per_query ? w.dBlock.p : p.d_maps;
+  v.allow_per_query = per_query;
+  v.d_head = per_query ? w.dBlock.p : nullptr;
+  v.head_of = head_of.data();
+  v.samples = [&]() -> int {
+    if (int r = w.dSample.ensure((size_t)n_masks * kMaskedSample)) return r;
+    HIP_TRY(launch_masked_samples(w.dList.p, p.off, w.dCum.p, n_masks, p.n_tiles, w.dSample.p, st));
+    return EHX_OK;
+  };
+  v.ctr = s->masked_ctr;
+  return filtered_answer(s, st, nq, d_queries, k, v, out);
 }
 
 // an unsharded space, locked shared, scratch_mu held, its device current; everything is enqueued on `st` (mask_of /

@@ -2,7 +2,8 @@
 // the best 64 (distance, id) keys per workgroup — out[q][block][64], the layout launch_flat_merge reads — and the page
 // writer that turns a query's merged keys into ids / distances / count.
 //   among_list_kernel   one query per workgroup, the rows read straight from HBM: a gather, bound by what the memory
-//                       system delivers for random whole rows.  Serves the per-query lists.
+//                       system delivers for random whole rows.  Serves the per-query lists; with AmongArgs::cand_end
+//                       (a run-time field: the same nine functions) two queries may name the same list.
 //   among_tile_kernel   ONE list shared by every query: a workgroup stages 8 gathered rows in LDS and applies them to a tile
 //                       of 8 queries before it moves on, so a row makes one trip through the memory system per 8 pairs
 //                       (and the workgroups of the other query tiles, resident together, find it in L2).
@@ -38,7 +39,7 @@ __global__ __launch_bounds__(256) void among_list_kernel(const AmongArgs a) {
   uint64_t lo = 0, hi = a.n_cand;
   if (a.cand_off) {
     lo = a.cand_off[q];
-    hi = a.cand_off[q + 1];
+    hi = a.cand_end ? a.cand_end[q] : a.cand_off[q + 1];   // (cand_end: queries that share a list name the same range)
     hi = hi < a.n_cand ? hi : a.n_cand;   // (the device form cannot check its offsets: never read beyond the id array)
   }
   stage_query_lds<LAYOUT>(qs, a.Q + (size_t)q * a.rows.ld, a.rows.ld, tid, 256);

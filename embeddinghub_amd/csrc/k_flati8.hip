@@ -183,8 +183,11 @@ static_assert(sizeof(I8Ctx) <= 64, "I8Ctx slot");
 // slot.  A flag of the template, so the scans of every other caller run the flush they always ran.  Three forms: kMaskNone,
 // kMaskOne (the batch's ONE bitmap) and kMaskPerQuery (ehx_knn_masked_multi*, several masks): ctx->allow is ONE block, the
 // word offset of every query's bitmap inside it ([q_rows], padding queries included) followed by the bitmaps, and the bit
-// tested is that of the bitmap of the hit's own query.
-constexpr int kMaskNone = 0, kMaskOne = 1, kMaskPerQuery = 2;
+// tested is that of the bitmap of the hit's own query.  A fourth, kMaskLabel (ehx_knn_labeled*): no bitmap at all — ctx->allow
+// is ONE block again, the wanted label of every query (kLabelHead >= q_rows words, padding queries included: they collect
+// nothing) followed by a copy of the label column label_of[0, allow_bits), and a hit survives iff its row's label is its
+// query's: two independent loads.  (The head's length is a constant because I8Ctx has no word left to carry it.)
+constexpr int kMaskNone = 0, kMaskOne = 1, kMaskPerQuery = 2, kMaskLabel = 3;
 template <bool HALF, int MASKED>
 __device__ __attribute__((noinline)) void i8_flush_staging() {
   using L = I8L<HALF>;
@@ -215,6 +218,11 @@ __device__ __attribute__((noinline)) void i8_flush_staging() {
       if (id >= ctx->allow_bits) continue;
       const uint32_t* block = ctx->allow;
       if (!((block[(size_t)block[ctx->q_tile0 + qloc] + (id >> 5)] >> (id & 31u)) & 1u)) continue;
+    }
+    if constexpr (MASKED == kMaskLabel) {
+      if (id >= ctx->allow_bits) continue;
+      const uint32_t* block = ctx->allow;
+      if (block[(size_t)kLabelHead + id] != block[ctx->q_tile0 + qloc]) continue;
     }
     const uint64_t key = ((uint64_t)f32_to_ordered(S) << 32) | (uint64_t)id;
     const uint32_t q = ctx->q_tile0 + qloc;
@@ -1057,6 +1065,12 @@ hipError_t launch_flat_scan_i8(const ScanArgsI8& a, hipStream_t st) {
                        (const void*)flat_scan_i8_kernel<false, false, true, false, false, kMaskPerQuery>,
                        (const void*)flat_scan_i8_kernel<false, false, true, true, false, kMaskPerQuery>,
                        (const void*)flat_scan_i8_kernel<false, false, false, false, true, kMaskPerQuery>,
+                       // ... and for a label column in place of bitmaps (ehx_knn_labeled*)
+                       (const void*)flat_scan_i8_kernel<false, true, false, false, false, kMaskLabel>,
+                       (const void*)flat_scan_i8_kernel<false, false, false, false, false, kMaskLabel>,
+                       (const void*)flat_scan_i8_kernel<false, false, true, false, false, kMaskLabel>,
+                       (const void*)flat_scan_i8_kernel<false, false, true, true, false, kMaskLabel>,
+                       (const void*)flat_scan_i8_kernel<false, false, false, false, true, kMaskLabel>,
                        // the flat chain's long passes: tile ranges from the share planner's table, start / finish stamps
                        (const void*)flat_scan_i8_kernel<false, true, false, false, false, kMaskNone, true>};
   if (hipError_t e = attr.ensure(fns, (int)(sizeof(fns) / sizeof(fns[0])), I8L<false>::kLdsBytes); e != hipSuccess) return e;
@@ -1087,7 +1101,9 @@ hipError_t launch_flat_scan_i8(const ScanArgsI8& a, hipStream_t st) {
       hipLaunchKernelGGL((flat_scan_i8_kernel<false, false, false, false, false, M>), dim3(grid),                            \
                          dim3(I8L<false>::kThreads), I8L<false>::kLdsBytes, st, a);                                          \
   } while (0)
-    if (a.allow_per_query) EHX_LAUNCH_I8_MASKED(kMaskPerQuery);
+    if (a.allow_label && (a.allow_per_query || a.q_tiles * 256u > kLabelHead)) return hipErrorInvalidValue;
+    if (a.allow_label) EHX_LAUNCH_I8_MASKED(kMaskLabel);   // (nothing but this field reaches those instantiations)
+    else if (a.allow_per_query) EHX_LAUNCH_I8_MASKED(kMaskPerQuery);
     else EHX_LAUNCH_I8_MASKED(kMaskOne);
 #undef EHX_LAUNCH_I8_MASKED
   } else if (a.dump) {

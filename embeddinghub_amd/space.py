@@ -516,6 +516,42 @@ class Space:
                                                     _ptr(d_group_of), int(n_labels), _ptr(d_masks), int(n_masks), int(n_bits),
                                                     _ptr(d_mask_of), _ptr(d_ids), _ptr(d_dist), _ptr(d_count)))
 
+    # ---- partitioned kNN: a label per row, a wanted label per query (tenants, namespaces, collections) ----
+    def knn_labeled(self, queries, k, label_of, want, n_labels=None):
+        """The k nearest rows of every query among the rows that carry ITS wanted label, exact (ehx_knn_labeled): query i sees
+        row r iff label_of[r] == want[i].  label_of: one unsigned 32-bit label per row, no value special (0xFFFFFFFF is an
+        ordinary label); rows at or above n_labels (default len(label_of)) or len(self) are not searched.  want: [nq] labels;
+        any number of distinct ones.  Row i of the answer is knn_masked's under the bitmap label_of == want[i].
+        -> ids [nq,k] u64, dist [nq,k] f32, count [nq] u32."""
+        q, pq = _f32(queries)
+        q = q.reshape(-1, self.dims)
+        nq = q.shape[0]
+        labels = np.ascontiguousarray(np.asarray(label_of).reshape(-1), dtype=np.uint32)
+        n_labels = labels.shape[0] if n_labels is None else int(n_labels)
+        if n_labels < 0 or n_labels > labels.shape[0]:
+            raise ValueError("n_labels = %d with %d labels" % (n_labels, labels.shape[0]))
+        w = np.ascontiguousarray(np.asarray(want).reshape(-1), dtype=np.uint32)
+        if w.shape[0] != nq:
+            raise ValueError("expected %d wanted labels, got %d" % (nq, w.shape[0]))
+        (ids, dist, cnt), out = _results(nq, k)
+        check(self._L.ehx_knn_labeled(self._h, nq, pq, k, labels.ctypes.data_as(C.POINTER(C.c_uint32)) if n_labels else None,
+                                      n_labels, w.ctypes.data_as(C.POINTER(C.c_uint32)), *out))
+        return ids[:, :k], dist[:, :k], cnt
+
+    def knn_labeled_device(self, d_queries, k, d_label_of, n_labels, d_want, d_ids, d_dist, d_count, stream=None):
+        """knn_labeled without anything leaving the device (the serving path: the label column stays resident): torch CUDA
+        tensors — d_queries [nq, dims] f32, d_label_of [n_labels] u32 (int32 storage), d_want [nq] u32 (int32 storage),
+        outputs as knn_device's."""
+        nq = d_queries.shape[0] if hasattr(d_queries, "shape") else None
+        if nq is None:
+            raise ValueError("pass torch tensors (queries [nq, dims], row labels, wanted labels)")
+        if hasattr(d_label_of, "numel") and d_label_of.numel() < int(n_labels):
+            raise ValueError("%d row labels are fewer than n_labels = %d" % (d_label_of.numel(), n_labels))
+        if hasattr(d_want, "numel") and d_want.numel() < nq:
+            raise ValueError("%d wanted labels for %d queries" % (d_want.numel(), nq))
+        check(self._L.ehx_knn_labeled_device(self._h, C.c_void_p(stream or 0), nq, _ptr(d_queries), k, _ptr(d_label_of),
+                                             int(n_labels), _ptr(d_want), _ptr(d_ids), _ptr(d_dist), _ptr(d_count)))
+
     # ---- kNN under a row bitmap on the graph path ----
     def graph_knn_masked(self, queries, k, allow, n_bits=None, route=_lib.WALK_AUTO):
         """The k nearest ALLOWED rows the graph walk finds (ehx_graph_knn_masked): approximate when walked, possibly fewer

@@ -327,6 +327,11 @@ int ehx_knn_grouped(ehx_space* s, size_t n_queries, const float* queries, uint32
 int ehx_knn_grouped_masked(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, uint32_t per_group,
                            const uint32_t* group_of, uint64_t n_labels, const uint32_t* masks, uint32_t n_masks,
                            uint64_t n_bits, const uint32_t* mask_of, uint64_t* out_ids, float* out_dist, uint32_t* out_count);
+/* Exact kNN under a label column from host pointers: ehx_knn_labeled_device (below: the contract) plus the H2D / D2H copies.
+ * label_of has n_labels entries, want n_queries.  The labels of the prefix searched are staged on EVERY call — 4 bytes per
+ * row: the device form, with the column resident, is the serving path. */
+int ehx_knn_labeled(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, const uint32_t* label_of,
+                    uint64_t n_labels, const uint32_t* want, uint64_t* out_ids, float* out_dist, uint32_t* out_count);
 /* Exact range search from host pointers: ehx_range_device (below: the contract) plus the H2D / D2H copies.  radius has
  * n_queries entries; out_total may be NULL. */
 int ehx_range(ehx_space* s, size_t n_queries, const float* queries, const float* radius, uint32_t max_results,
@@ -552,6 +557,35 @@ int ehx_knn_grouped_masked_device(ehx_space* s, void* stream, size_t n_queries, 
                                   uint32_t per_group, const uint32_t* d_group_of, uint64_t n_labels, const uint32_t* d_masks,
                                   uint32_t n_masks, uint64_t n_bits, const uint32_t* d_mask_of, uint64_t* d_out_ids,
                                   float* d_out_dist, uint32_t* d_out_count);
+/* Partitioned kNN: exact kNN under a label column — the filter "this request may only see the rows of its own tenant /
+ * namespace / collection", without a bitmap per tenant and without a limit on the tenants of one call.  d_label_of[0, n_labels)
+ * holds one opaque 32-bit label per row, stored once (the column ehx_knn_grouped_device takes as d_group_of will do);
+ * d_want[i] is the label query i is confined to.  NO value is special: 0xFFFFFFFF is an ordinary label here, although
+ * EHX_GROUP_NONE uses that value in the grouped searches.  The call takes ONE acquire-load snapshot of the row count and
+ * searches the prefix n_eff = min(snapshot, n_labels): row r is allowed for query i iff r < n_eff and d_label_of[r] ==
+ * d_want[i].  Row i of the answer is, byte for byte, what ehx_knn_masked_device returns for query i alone under the bitmap
+ * {r < n_eff : d_label_of[r] == d_want[i]}: (canonical distance, id) order, the NaN rule, +-Inf, cosine normalisation, F16
+ * rows as stored, the sentinels beyond d_out_count[i].  A label no row carries gives count 0 for ITS queries only;
+ * n_labels == 0 gives count 0 for every query; n_queries == 0: EHX_OK.  Every space kind ehx_knn_masked serves is served; a
+ * graph space answers from its stored rows, its graph is not walked.
+ * The number of distinct wanted labels is not limited: a call is served in device batches of 2048 queries, each compacting
+ * the column for its own (at most 2048) labels.
+ * Errors as ehx_knn_masked_multi_device: a NULL space: EHX_EINVAL, before the device is looked for; k == 0, NULL outputs or
+ * queries, a NULL d_label_of with n_labels > 0, a NULL d_want: EHX_EINVAL; k > EHX_MAX_K_PAGED, a row-sharded space, rows
+ * longer than the list scan's prepared query: EHX_EUNSUPPORTED; a dropped space: EHX_ENOTFOUND.
+ * Served per wanted label by ehx_knn_masked_multi_device's rule — a label with more than max(1024, rows / 128) rows of the
+ * prefix takes the int8 scan route when k <= 48 and the int8 filter serves the space (at most 127 labels can: they are
+ * disjoint), with the test "the row's label is the query's" where the scan collects its hits; every other label is a short
+ * list, scanned exactly, the labels few queries name all in ONE launch.  That cut was measured for the bitmap search and is
+ * carried over, not measured for this call.  The pass plan is the batch's, as there: a label that clusters late in the id
+ * space behind the others' rows may overflow its queries' pools, and they are then answered from its list — the same answer.
+ * Waits: the device form reads d_want back (one wait for the whole call), then waits at most TWICE per device batch for the
+ * compaction — the per-label row counts, and, only where a label scans, its rows before every tile — however many labels
+ * the batch names; a batch on the scan route reads its verdict as ehx_knn_masked_multi_device does.  A Set that rewrites
+ * rows in place waits for the call like for any search.  DESIGN.md §e.21. */
+int ehx_knn_labeled_device(ehx_space* s, void* stream, size_t n_queries, const float* d_queries, uint32_t k,
+                           const uint32_t* d_label_of, uint64_t n_labels, const uint32_t* d_want, uint64_t* d_out_ids,
+                           float* d_out_dist, uint32_t* d_out_count);
 /* Exact range search: every row closer than a radius.  With D(q, x) the canonical distance ehx_knn reports (cosine, L2^2,
  * inner product as there), row x belongs to query i's answer iff D is not NaN and D <= d_radius[i] as a float comparison
  * (inclusive: a radius that equals a row's distance byte for byte includes that row; -Inf distances under inner product
