@@ -108,6 +108,10 @@ SYMBOLS = {
                                                 C.c_uint32, C.c_uint64, _vp, _vp, _vp, _vp]),
     "ehx_knn_labeled": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_uint32, _u32p, C.c_uint64, _u32p, _u64p, _f32p, _u32p]),
     "ehx_knn_labeled_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint32, _vp, C.c_uint64, _vp, _vp, _vp, _vp]),
+    "ehx_knn_grouped_labeled": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_uint32, C.c_uint32, _u32p, _u32p, C.c_uint64, _u32p, _u64p,
+                                          _f32p, _u32p]),
+    "ehx_knn_grouped_labeled_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint32, C.c_uint32, _vp, _vp, C.c_uint64, _vp,
+                                                 _vp, _vp, _vp]),
     "ehx_graph_knn_masked": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_uint32, _u32p, C.c_uint64, C.c_uint32, _u64p, _f32p, _u32p]),
     "ehx_graph_knn_masked_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint32, _vp, C.c_uint64, C.c_uint32, _vp, _vp,
                                               _vp]),

@@ -587,6 +587,20 @@ struct ehx_space {
   // test hook: queries answered on the scan route, on the list route (by the gate or handed on by the scan), of those the
   // overflowed, scan passes launched, calls
   std::atomic<uint64_t> groupedm_ctr[5] = {};
+  // grouped kNN under a label column (ehx_groupedl.cpp; scratch_mu): the compaction and its scratch are the label search's
+  // (labeled_plan: labeled.dBlock / dSlots / dSlotOf / dOff, masked.dList / dCum), the list route's pools, control words and
+  // carried keys the grouped kNN's (grouped.dPool / dCtl / exact), a host call's staged columns theirs too (grouped.dLabels,
+  // labeled.dCol); its own are the scan route's buffers (its sub-batch: the queries the scan hands on), a device batch's
+  // queries ordered by route, every query's [start | end) in masked.dList, and a host call's staged queries and results
+  struct GroupedLabeled {
+    RadiusKnnBufs scan;
+    SubsetBufs group;
+    DevBuf<uint64_t> dRange;     // [queries of a device batch] start | [queries] end of every query's list
+    HostStage host;
+  } groupedl;
+  // test hook: queries answered on the scan route, on the list route (by the gate or handed on by the scan), of those the
+  // overflowed, scan passes launched, calls
+  std::atomic<uint64_t> groupedl_ctr[5] = {};
   // int8 filter scratch: everything ONE in-flight batch of the int8 pipeline owns — prepared queries, query tiles +
   // parameters, per-pass thresholds, sample scores, pools, running best list, verdict, batch clock.  TWO sets: a host
   // caller's batch can be enqueued behind another caller's on the space's stream while that one still waits for its
@@ -684,6 +698,7 @@ struct ehx_space {
     largek = {};
     grouped = {};
     groupedm = {};
+    groupedl = {};
     one = {};
     xch = {};
     wr = {};
@@ -1030,6 +1045,31 @@ struct FilterView {
 bool filter_scan_serves(const ehx_space* s, uint32_t k, uint64_t n_pub);   // the scan route serves this k on this prefix
 int filtered_answer(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, const FilterView& v,
                     const ResultBlock& out);
+
+// ---- ehx_labeled.cpp ----
+// The label column of one device batch, compacted for the batch's distinct wanted labels ("slots"): the slot of every query,
+// per slot its rows in the prefix and where its list starts in masked.dList, which slots scan, and the scanning slots' rows
+// before every tile.  On the device behind it: the table and the lists (masked.dList: ascending where the slot scans), the
+// scanning slots' prefixes (masked.dCum), their lists' starts by scanning index (labeled.dOff + kLabeledMaxSlots), and —
+// where some slot scans — the column behind the head of labeled.dBlock.
+struct LabeledPlan {
+  uint32_t n_tiles = 0, n_slots = 0, n_scan = 0;
+  uint64_t total = 0;                     // entries of masked.dList the lists hold together
+  std::vector<uint32_t> table, slot_of;   // [n_slots] the wanted labels, ascending | [queries] the slot of every query
+  std::vector<uint64_t> n_allowed, off;   // [n_slots]
+  std::vector<char> scans;                // [n_slots]
+  std::vector<uint32_t> scan_of;          // [n_slots] the slot's row of cum (kLabeledNoScan: it does not scan)
+  std::vector<uint32_t> cum;              // [n_scan][n_tiles + 1]
+};
+// the scratch labeled_plan fills, sized for a prefix of n_eff rows (once per call, before anything is enqueued)
+int labeled_plan_scratch(ehx_space* s, uint64_t n_eff);
+// an unsharded space, locked shared, scratch_mu held, its device current, `st` ordered behind the searches in flight;
+// everything is enqueued on `st`.  m <= kSideChunk queries under want[0, m) (host memory) over d_label_of[0, n_eff).  Waits
+// once for the counts, and a second time — for the tile prefixes — only where some slot scans.  A slot scans iff scan_serves
+// and it has more than `cut` rows — and, with min_scan_queries, only if at least that many queries of the batch name such
+// slots (else none scans).  *col_copied: the column's copy is in place (made once per call, and only where some slot scans).
+int labeled_plan(ehx_space* s, hipStream_t st, uint64_t n_eff, size_t m, const uint32_t* d_label_of, const uint32_t* want,
+                 bool scan_serves, uint64_t cut, size_t min_scan_queries, bool* col_copied, LabeledPlan* p);
 
 // ---- ehx_among.cpp ----
 // exact kNN among row ids on an unsharded space, locked shared, scratch_mu held, its device current (d_off == nullptr: one

@@ -648,6 +648,16 @@ hipError_t launch_grouped_list_slab(const uint64_t* list, const MaskedOffsets& o
                                     const uint32_t* mask_at, uint64_t slab, bool first, uint64_t* pool, uint32_t* pool_cnt,
                                     float* radius, uint32_t* top_cnt, uint32_t* work, uint32_t nq, hipStream_t st);
 
+// grouped kNN under a label column (k_groupedl.hip): the same two fills with query q's list given as the range
+// list[start[q], end[q]) — start, end: device arrays of nq entries, end[q] >= start[q], the range inside the list; queries may
+// name the same range, and any number of ranges fits one launch.  seed: stride = ceil(len / kLargeKSample) over the range by
+// rank; slab: entries [slab * kPoolCap, ...) of the range, possibly none; first: as launch_grouped_list_slab
+hipError_t launch_grouped_range_seed(const uint64_t* list, const uint64_t* start, const uint64_t* end, uint64_t* pool,
+                                     uint32_t* pool_cnt, uint32_t nq, hipStream_t st);
+hipError_t launch_grouped_range_slab(const uint64_t* list, const uint64_t* start, const uint64_t* end, uint64_t slab,
+                                     bool first, uint64_t* pool, uint32_t* pool_cnt, float* radius, uint32_t* top_cnt,
+                                     uint32_t* work, uint32_t nq, hipStream_t st);
+
 // per-row statistics for rows [row0, row0+n): inv_norm (cosine), rowp (a,b) for the scan epilogue;
 // *max_sumsq (optional) is raised to the largest |x|^2 seen (the certification margin's norm bound)
 // perm: the fp32 rows are stored block-permuted (single-copy graph spaces); the sums keep the logical order

@@ -21,6 +21,9 @@
 // The device form waits once for d_want (the whole call's), then per device batch at most twice for the compaction — the
 // counts, and the scanning slots' tile prefixes — whatever the number of labels the batch names; the scan route's verdict is
 // radius_knn's one wait per device batch, as under bitmaps.
+// The compaction is a plan (LabeledPlan, labeled_plan: ehx_internal.h) that the grouped search under a label column
+// (ehx_groupedl.cpp) shares; the two callers' routing differs in what they pass it — whether the scan route serves the call,
+// and how many queries of the batch must name scanning slots (none here).
 // Entry scaffold and host staging are ehx_call.cpp's (search_shared / on_device, HostStage).
 #include "ehx_internal.h"
 
@@ -42,20 +45,35 @@ int labeled_check(const ehx_space* s, size_t nq, uint32_t k, const void* q, cons
   return EHX_OK;
 }
 
-// One device batch of m <= kSideChunk queries under want[0, m) (host memory) over the prefix of n_eff rows of d_label_of.
-// *col_copied: the flush's copy of the column is in place (made once per call, and only where some slot scans).
-int labeled_batch(ehx_space* s, hipStream_t st, uint64_t n_pub, uint64_t n_eff, size_t m, const float* d_queries, uint32_t k,
-                  const uint32_t* d_label_of, const uint32_t* want, bool* col_copied, const ResultBlock& out) {
+}  // namespace
+
+namespace ehx_impl {
+
+int labeled_plan_scratch(ehx_space* s, uint64_t n_eff) {
+  ehx_space::Labeled& w = s->labeled;
+  int rc;
+  if ((rc = w.dBlock.ensure(kLabelHead + std::max<uint64_t>(n_eff, 1))) || (rc = w.dSlotOf.ensure(std::max<uint64_t>(n_eff, 1))) ||
+      (rc = w.dSlots.ensure(4 * (size_t)kLabeledMaxSlots)) || (rc = w.dOff.ensure((size_t)kLabeledMaxSlots + kLabeledMaxScan + 1)))
+    return rc;
+  return EHX_OK;
+}
+
+// The compaction of the column for one device batch (ehx_internal.h has the contract).
+int labeled_plan(ehx_space* s, hipStream_t st, uint64_t n_eff, size_t m, const uint32_t* d_label_of, const uint32_t* want,
+                 bool scan_serves, uint64_t cut, size_t min_scan_queries, bool* col_copied, LabeledPlan* p) {
   int rc;
   ehx_space::Labeled& w = s->labeled;
   ehx_space::Masked& mw = s->masked;
-  const uint32_t n_tiles = (uint32_t)((n_eff + kTileRows16 - 1) / kTileRows16);
+  const uint32_t n_tiles = p->n_tiles = (uint32_t)((n_eff + kTileRows16 - 1) / kTileRows16);
   // the slots: the batch's distinct wanted labels, ascending, and the slot of every query
-  std::vector<uint32_t> table(want, want + m), slot_of(m);
+  std::vector<uint32_t>& table = p->table;
+  table.assign(want, want + m);
+  p->slot_of.resize(m);
   std::sort(table.begin(), table.end());
   table.erase(std::unique(table.begin(), table.end()), table.end());
-  const uint32_t n_slots = (uint32_t)table.size();
-  for (size_t j = 0; j < m; ++j) slot_of[j] = (uint32_t)(std::lower_bound(table.begin(), table.end(), want[j]) - table.begin());
+  const uint32_t n_slots = p->n_slots = (uint32_t)table.size();
+  for (size_t j = 0; j < m; ++j)
+    p->slot_of[j] = (uint32_t)(std::lower_bound(table.begin(), table.end(), want[j]) - table.begin());
   uint32_t* d_table = w.dSlots.p;
   uint32_t* d_count = d_table + kLabeledMaxSlots;
   uint32_t* d_scan_of = d_count + kLabeledMaxSlots;
@@ -68,28 +86,39 @@ int labeled_batch(ehx_space* s, hipStream_t st, uint64_t n_pub, uint64_t n_eff, 
     HIP_TRY(hipMemcpyAsync(count.data(), d_count, n_slots * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));   // the first wait
   }
-  // routing per slot (the bitmap search's rule), where the lists start, and the scanning slots' indices
-  const bool scan_serves = filter_scan_serves(s, k, n_pub);
-  const uint32_t forced = s->labeled_route.load(std::memory_order_relaxed);   // (test hook: the bench's crossover sweep)
-  const uint64_t cut = forced == 1 ? 0 : forced == 2 ? ~0ull : masked_exact_cut(n_pub);
-  std::vector<uint64_t> n_allowed(n_slots), off(n_slots), scan_off;
-  std::vector<char> scans(n_slots);
-  std::vector<uint32_t> scan_of(n_slots, kLabeledNoScan);
+  // routing per slot (the bitmap search's rule; with min_scan_queries the grouped search's gate on top of it), decided
+  // BEFORE the lists are filled: where the lists start, and the scanning slots' indices
+  std::vector<char>& scans = p->scans;
+  scans.assign(n_slots, 0);
+  for (uint32_t f = 0; f < n_slots; ++f) scans[f] = scan_serves && count[f] > cut;
+  if (min_scan_queries) {
+    size_t naming = 0;
+    for (size_t j = 0; j < m; ++j) naming += scans[p->slot_of[j]] != 0;
+    if (naming < min_scan_queries) scans.assign(n_slots, 0);
+  }
+  std::vector<uint64_t>& n_allowed = p->n_allowed;
+  std::vector<uint64_t>& off = p->off;
+  std::vector<uint64_t> scan_off;
+  n_allowed.assign(n_slots, 0);
+  off.assign(n_slots, 0);
+  std::vector<uint32_t>& scan_of = p->scan_of;
+  scan_of.assign(n_slots, kLabeledNoScan);
   uint64_t total = 0;
   for (uint32_t f = 0; f < n_slots; ++f) {
     n_allowed[f] = count[f];
     off[f] = total;
     total += count[f];
-    scans[f] = scan_serves && n_allowed[f] > cut;
     if (!scans[f]) continue;
     scan_of[f] = (uint32_t)scan_off.size();
     scan_off.push_back(off[f]);
   }
-  const uint32_t n_scan = (uint32_t)scan_off.size();
+  p->total = total;
+  const uint32_t n_scan = p->n_scan = (uint32_t)scan_off.size();
   if (n_scan > kLabeledMaxScan || total > n_eff)   // (disjoint sets of more than max(1024, n / 128) rows each: at most 127)
     return fail(EHX_EINTERNAL, "label compaction: %u scanning labels, %llu listed rows of %llu", n_scan,
                 (unsigned long long)total, (unsigned long long)n_eff);
-  std::vector<uint32_t> cum((size_t)n_scan * (n_tiles + 1), 0u);
+  std::vector<uint32_t>& cum = p->cum;
+  cum.assign((size_t)n_scan * (n_tiles + 1), 0u);
   if ((rc = mw.dList.ensure(std::max<uint64_t>(total, 1)))) return rc;
   if (n_tiles) {
     uint64_t* d_off = w.dOff.p;
@@ -110,18 +139,36 @@ int labeled_batch(ehx_space* s, hipStream_t st, uint64_t n_pub, uint64_t n_eff, 
       HIP_TRY(hipStreamSynchronize(st));   // the second wait: the host plans the passes from the tile prefixes
     }
   }
+  return EHX_OK;
+}
+
+}  // namespace ehx_impl
+
+namespace {
+
+// One device batch of m <= kSideChunk queries under want[0, m) (host memory) over the prefix of n_eff rows of d_label_of:
+// the plan, its view, the bitmap search's answer.
+int labeled_batch(ehx_space* s, hipStream_t st, uint64_t n_pub, uint64_t n_eff, size_t m, const float* d_queries, uint32_t k,
+                  const uint32_t* d_label_of, const uint32_t* want, bool* col_copied, const ResultBlock& out) {
+  ehx_space::Labeled& w = s->labeled;
+  ehx_space::Masked& mw = s->masked;
+  const uint32_t forced = s->labeled_route.load(std::memory_order_relaxed);   // (test hook: the bench's crossover sweep)
+  const uint64_t cut = forced == 1 ? 0 : forced == 2 ? ~0ull : masked_exact_cut(n_pub);
+  LabeledPlan p;
+  if (int rc = labeled_plan(s, st, n_eff, m, d_label_of, want, filter_scan_serves(s, k, n_pub), cut, 0, col_copied, &p)) return rc;
+  const uint32_t n_tiles = p.n_tiles, n_scan = p.n_scan;
   FilterView v;
   v.n_pub = n_pub;
   v.n_eff = n_eff;
-  v.list_rows = total;
+  v.list_rows = p.total;
   v.n_tiles = n_tiles;
-  v.n_filters = n_slots;
-  v.n_allowed = n_allowed.data();
-  v.off = off.data();
-  v.filter_of = slot_of.data();
-  v.scans = scans.data();
-  v.cum = cum.data();
-  v.scan_of = scan_of.data();
+  v.n_filters = p.n_slots;
+  v.n_allowed = p.n_allowed.data();
+  v.off = p.off.data();
+  v.filter_of = p.slot_of.data();
+  v.scans = p.scans.data();
+  v.cum = p.cum.data();
+  v.scan_of = p.scan_of.data();
   v.d_list = mw.dList.p;
   v.sample = &mw.dSample;
   v.samples = [&]() -> int {
@@ -132,7 +179,7 @@ int labeled_batch(ehx_space* s, hipStream_t st, uint64_t n_pub, uint64_t n_eff, 
   v.allow = w.dBlock.p;
   v.allow_label = true;
   v.d_head = w.dBlock.p;
-  v.head_of = table.data();   // (the head word of a query is its wanted label itself)
+  v.head_of = p.table.data();   // (the head word of a query is its wanted label itself)
   v.shared_min = kLabeledSharedMin;
   v.d_range = &w.dRange;
   v.ctr = s->labeled_ctr;
@@ -148,11 +195,8 @@ int labeled_locked(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, cons
   if ((rc = check_not_poisoned(s))) return rc;
   if ((rc = check_rows_fit_lds(s, "filtered search"))) return rc;   // (before anything is enqueued)
   s->labeled_ctr[4] += 1;
-  ehx_space::Labeled& w = s->labeled;
   const uint64_t n_eff = std::min<uint64_t>(n_labels, n_pub);   // (row ids are 32 bits wide: n_pub < 2^32)
-  if ((rc = w.dBlock.ensure(kLabelHead + std::max<uint64_t>(n_eff, 1))) || (rc = w.dSlotOf.ensure(std::max<uint64_t>(n_eff, 1))) ||
-      (rc = w.dSlots.ensure(4 * (size_t)kLabeledMaxSlots)) || (rc = w.dOff.ensure((size_t)kLabeledMaxSlots + kLabeledMaxScan + 1)))
-    return rc;
+  if ((rc = labeled_plan_scratch(s, n_eff))) return rc;
   // (earlier calls' launches on other streams may still read the block, the lists and the samples)
   if ((rc = wait_searches_in_flight(s, st))) return rc;
   std::vector<uint32_t> want_read;

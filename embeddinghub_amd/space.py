@@ -552,6 +552,55 @@ class Space:
         check(self._L.ehx_knn_labeled_device(self._h, C.c_void_p(stream or 0), nq, _ptr(d_queries), k, _ptr(d_label_of),
                                              int(n_labels), _ptr(d_want), _ptr(d_ids), _ptr(d_dist), _ptr(d_count)))
 
+    # ---- partitioned grouped kNN: a tenant label per row, a wanted tenant per query, a cap per group ----
+    def knn_grouped_labeled(self, queries, k, group_of, label_of, want, per_group=1, n_labels=None):
+        """knn_grouped over the rows of every query's own tenant alone (ehx_knn_grouped_labeled): query i sees row r iff
+        label_of[r] == want[i]; rows of other tenants neither appear nor count toward a group's cap.  group_of as
+        knn_grouped's (marshal_groups: -1 is GROUP_NONE), label_of and want as knn_labeled's (no value special); the two
+        columns have one length, n_labels (default: that length) may cut both.  Rows at or above n_labels or len(self) are
+        not searched.  Any number of distinct wanted labels.  k <= 256.
+        -> ids [nq,k] u64, dist [nq,k] f32, count [nq] u32."""
+        q, pq = _f32(queries)
+        q = q.reshape(-1, self.dims)
+        nq = q.shape[0]
+        groups, n_groups = marshal_groups(group_of)
+        labels = np.ascontiguousarray(np.asarray(label_of).reshape(-1), dtype=np.uint32)
+        if n_labels is None:
+            if n_groups != labels.shape[0]:
+                raise ValueError("%d group labels but %d row labels" % (n_groups, labels.shape[0]))
+            n_labels = n_groups
+        n_labels = int(n_labels)
+        if n_labels < 0 or n_labels > labels.shape[0] or n_labels > n_groups:
+            raise ValueError("n_labels = %d with %d group labels and %d row labels" % (n_labels, n_groups, labels.shape[0]))
+        w = np.ascontiguousarray(np.asarray(want).reshape(-1), dtype=np.uint32)
+        if w.shape[0] != nq:
+            raise ValueError("expected %d wanted labels, got %d" % (nq, w.shape[0]))
+        (ids, dist, cnt), out = _results(nq, k)
+        u32p = C.POINTER(C.c_uint32)
+        check(self._L.ehx_knn_grouped_labeled(self._h, nq, pq, k, int(per_group),
+                                              groups.ctypes.data_as(u32p) if n_labels else None,
+                                              labels.ctypes.data_as(u32p) if n_labels else None, n_labels,
+                                              w.ctypes.data_as(u32p), *out))
+        return ids[:, :k], dist[:, :k], cnt
+
+    def knn_grouped_labeled_device(self, d_queries, k, d_group_of, d_label_of, n_labels, d_want, d_ids, d_dist, d_count,
+                                   per_group=1, stream=None):
+        """knn_grouped_labeled without anything leaving the device (the serving path: both columns stay resident): torch CUDA
+        tensors — d_queries [nq, dims] f32, d_group_of and d_label_of [n_labels] u32 (int32 storage), d_want [nq] u32 (int32
+        storage), outputs as knn_device's."""
+        nq = d_queries.shape[0] if hasattr(d_queries, "shape") else None
+        if nq is None:
+            raise ValueError("pass torch tensors (queries [nq, dims], group labels, row labels, wanted labels)")
+        if hasattr(d_group_of, "numel") and d_group_of.numel() < int(n_labels):
+            raise ValueError("%d group labels are fewer than n_labels = %d" % (d_group_of.numel(), n_labels))
+        if hasattr(d_label_of, "numel") and d_label_of.numel() < int(n_labels):
+            raise ValueError("%d row labels are fewer than n_labels = %d" % (d_label_of.numel(), n_labels))
+        if hasattr(d_want, "numel") and d_want.numel() < nq:
+            raise ValueError("%d wanted labels for %d queries" % (d_want.numel(), nq))
+        check(self._L.ehx_knn_grouped_labeled_device(self._h, C.c_void_p(stream or 0), nq, _ptr(d_queries), k, int(per_group),
+                                                     _ptr(d_group_of), _ptr(d_label_of), int(n_labels), _ptr(d_want),
+                                                     _ptr(d_ids), _ptr(d_dist), _ptr(d_count)))
+
     # ---- kNN under a row bitmap on the graph path ----
     def graph_knn_masked(self, queries, k, allow, n_bits=None, route=_lib.WALK_AUTO):
         """The k nearest ALLOWED rows the graph walk finds (ehx_graph_knn_masked): approximate when walked, possibly fewer

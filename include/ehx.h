@@ -332,6 +332,12 @@ int ehx_knn_grouped_masked(ehx_space* s, size_t n_queries, const float* queries,
  * row: the device form, with the column resident, is the serving path. */
 int ehx_knn_labeled(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, const uint32_t* label_of,
                     uint64_t n_labels, const uint32_t* want, uint64_t* out_ids, float* out_dist, uint32_t* out_count);
+/* Grouped kNN under a label column from host pointers: ehx_knn_grouped_labeled_device (below: the contract) plus the H2D /
+ * D2H copies.  group_of and label_of have n_labels entries each, want n_queries.  BOTH columns' prefixes searched are staged
+ * on EVERY call — 8 bytes per row, 8 MB at 1 M rows: the device form, with both columns resident, is the serving path. */
+int ehx_knn_grouped_labeled(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, uint32_t per_group,
+                            const uint32_t* group_of, const uint32_t* label_of, uint64_t n_labels, const uint32_t* want,
+                            uint64_t* out_ids, float* out_dist, uint32_t* out_count);
 /* Exact range search from host pointers: ehx_range_device (below: the contract) plus the H2D / D2H copies.  radius has
  * n_queries entries; out_total may be NULL. */
 int ehx_range(ehx_space* s, size_t n_queries, const float* queries, const float* radius, uint32_t max_results,
@@ -586,6 +592,48 @@ int ehx_knn_grouped_masked_device(ehx_space* s, void* stream, size_t n_queries, 
 int ehx_knn_labeled_device(ehx_space* s, void* stream, size_t n_queries, const float* d_queries, uint32_t k,
                            const uint32_t* d_label_of, uint64_t n_labels, const uint32_t* d_want, uint64_t* d_out_ids,
                            float* d_out_dist, uint32_t* d_out_count);
+/* Partitioned grouped kNN: "the k nearest documents OF THIS TENANT, at most per_group chunks each" in one request, for any
+ * number of tenants per call — ehx_knn_grouped_device's cap per group label over the rows ehx_knn_labeled_device's filter
+ * allows.  Two columns of n_labels entries each, under ONE length: d_group_of[r] is the entity row r belongs to
+ * (EHX_GROUP_NONE: a group of its own, as in ehx_knn_grouped_device); d_label_of[r] is the partition — tenant, namespace,
+ * collection — it lies in, where NO value is special (0xFFFFFFFF is an ordinary tenant here).  d_want[i] is the tenant query
+ * i is confined to.
+ * The call takes ONE acquire-load snapshot of the row count and searches the prefix n_eff = min(snapshot, n_labels).  Row r
+ * is ALLOWED for query i iff r < n_eff and d_label_of[r] == d_want[i] (n_labels above the row count is fine; rows appended
+ * after the columns were built are not returned).
+ * The rule is FILTER FIRST, THEN CAP.  Row i of the answer is, byte for byte, what ehx_knn_grouped_masked_device returns for
+ * query i alone under the bitmap {r < n_eff : d_label_of[r] == d_want[i]} with the same d_group_of, n_labels, k and
+ * per_group: the ids, the distance bytes, the count, and the sentinels (id 2^64 - 1, +Inf) behind d_out_count[i].  What that
+ * answer is, is defined there and in ehx_knn_grouped_device: (canonical distance, id) order; NaN is never a neighbour and
+ * never counts toward a cap; +-Inf are ordered; cosine is normalised; F16 rows are read as stored.  Rows of other tenants
+ * neither appear nor count toward a cap: a group whose nearest row belongs to another tenant is represented by its nearest
+ * row OF THE QUERY'S TENANT — which ehx_knn_grouped_device followed by a filter on the host gets wrong.
+ * Consequences, byte for byte: with every d_group_of entry EHX_GROUP_NONE, or per_group at least the size of the largest
+ * group, the call equals ehx_knn_labeled_device; with every row carrying one label and every query wanting it, it equals
+ * ehx_knn_grouped_device.  A label no row carries gives count 0 for ITS queries only; n_labels == 0 gives count 0 for every
+ * query; n_queries == 0: EHX_OK.  The number of distinct wanted labels per call is not limited: a call is served in device
+ * batches of 2048 queries, each compacting the label column for its own (at most 2048) labels.
+ * Errors, the union of the two parents' with their codes and in their order: a NULL space: EHX_EINVAL, before the device is
+ * looked for; k == 0, per_group == 0, NULL outputs, NULL queries with n_queries > 0, a NULL d_group_of or d_label_of with
+ * n_labels > 0, a NULL d_want: EHX_EINVAL; k > EHX_MAX_K_GROUPED, a row-sharded space, rows longer than 21 728 floats:
+ * EHX_EUNSUPPORTED; a dropped space: EHX_ENOTFOUND; no device: EHX_ENODEVICE.
+ * Served per wanted label of a device batch, by ehx_knn_grouped_masked_device's rule: the falling-radius scan of the int8
+ * filter, "the row's label is the query's" tested where the scan collects its hits and a cap per group in its exact re-rank,
+ * on flat spaces whose first engine is the int8 filter, for labels with more than max(1024, rows / 128) rows of the prefix
+ * (at most 127 can: they are disjoint), given at least 64 queries of the batch on such labels; any k here.  Its first radius
+ * comes from a sample of at most 1024 rows of the query's own label.  Everything else — graph spaces (from their stored
+ * rows: the graph is not walked), small spaces, EHX_SCAN_F32 / _F16, small batches, small tenants, and the queries that scan
+ * hands on — by an exact pass over the label's rows in slabs of 4096, every query of the batch in ONE launch per slab
+ * whatever number of labels they name: the cost falls with the tenant's share.  The cut was measured for the bitmap search
+ * and is carried over, not measured for this call.
+ * Waits: the device form reads d_want back (one wait for the whole call, the outputs unwritten until then), then waits at
+ * most TWICE per device batch for the compaction — the per-label row counts, and, only where a label scans, its rows before
+ * every tile; a batch on the scan route reads its verdict once.  A Set that rewrites rows in place waits for the call like
+ * for any search.  Not on the graph walk.  DESIGN.md §e.22. */
+int ehx_knn_grouped_labeled_device(ehx_space* s, void* stream, size_t n_queries, const float* d_queries, uint32_t k,
+                                   uint32_t per_group, const uint32_t* d_group_of, const uint32_t* d_label_of,
+                                   uint64_t n_labels, const uint32_t* d_want, uint64_t* d_out_ids, float* d_out_dist,
+                                   uint32_t* d_out_count);
 /* Exact range search: every row closer than a radius.  With D(q, x) the canonical distance ehx_knn reports (cosine, L2^2,
  * inner product as there), row x belongs to query i's answer iff D is not NaN and D <= d_radius[i] as a float comparison
  * (inclusive: a radius that equals a row's distance byte for byte includes that row; -Inf distances under inner product
