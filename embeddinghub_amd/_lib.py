@@ -20,6 +20,7 @@ MAX_K = 48
 WALK_AUTO, WALK_GRAPH, WALK_EXACT = 0, 1, 2   # route of graph_knn_masked
 WALK_LIST_FACTOR, WALK_LIST_MAX = 12, 4096     # EHX_WALK_LIST_FACTOR / _MAX: the walk list holds max(ef, min(12 ef, 4096))
 GROUP_NONE, MAX_K_GROUPED = 0xFFFFFFFF, 256     # EHX_GROUP_NONE (a row that is a group of its own), EHX_MAX_K_GROUPED
+MAX_COLUMNS = 4                                 # EHX_MAX_COLUMNS: stored label columns of a space
 SEED_CORPUS, SEED_QUERY = 20250211, 20250212
 
 
@@ -112,6 +113,20 @@ SYMBOLS = {
                                           _f32p, _u32p]),
     "ehx_knn_grouped_labeled_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint32, C.c_uint32, _vp, _vp, C.c_uint64, _vp,
                                                  _vp, _vp, _vp]),
+    "ehx_set_batch_cols": (C.c_int, [_vp, C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), _f32p, C.c_uint32, _u32p,
+                                     C.POINTER(_u32p)]),
+    "ehx_column_set": (C.c_int, [_vp, C.c_uint32, C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), _u32p,
+                                 C.POINTER(C.c_size_t)]),
+    "ehx_column_get": (C.c_int, [_vp, C.c_uint32, C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), _u32p,
+                                 C.POINTER(C.c_size_t)]),
+    "ehx_column_load_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint64, C.c_uint64, _vp]),
+    "ehx_column_read_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint64, C.c_uint64, _vp]),
+    "ehx_knn_by_label": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_uint32, C.c_uint32, _u32p, _u64p, _f32p, _u32p]),
+    "ehx_knn_by_label_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp]),
+    "ehx_knn_grouped_by_label": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _u64p,
+                                           _f32p, _u32p]),
+    "ehx_knn_grouped_by_label_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp,
+                                                  _vp, _vp, _vp]),
     "ehx_graph_knn_masked": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_uint32, _u32p, C.c_uint64, C.c_uint32, _u64p, _f32p, _u32p]),
     "ehx_graph_knn_masked_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint32, _vp, C.c_uint64, C.c_uint32, _vp, _vp,
                                               _vp]),

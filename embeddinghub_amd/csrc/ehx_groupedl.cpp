@@ -51,9 +51,20 @@ int groupedl_check(const ehx_space* s, size_t nq, uint32_t k, uint32_t per_group
   return check_batch_size(nq);
 }
 
+// ehx_knn_grouped_by_label*: the same checks with their codes and in their order (the columns are the space's: no pointers,
+// no length), then the column numbers
+int grouped_by_label_check(const ehx_space* s, size_t nq, uint32_t k, uint32_t per_group, const void* q, uint32_t group_col,
+                           uint32_t label_col, const void* want, const void* o_ids, const void* o_dist, const void* o_cnt) {
+  if (int rc = groupedl_check(s, nq, k, per_group, q, nullptr, nullptr, 0, want, o_ids, o_dist, o_cnt)) return rc;
+  if (group_col >= EHX_MAX_COLUMNS || label_col >= EHX_MAX_COLUMNS)
+    return fail(EHX_EINVAL, "group_col = %u, label_col = %u: a space has %u columns", group_col, label_col, (unsigned)EHX_MAX_COLUMNS);
+  return EHX_OK;
+}
+
 // The list route for nq <= kSideChunk queries, query j over masked.dList[start[j], end[j]) (range: [nq] starts | [nq] ends,
-// host memory): any space kind.  count_queries: its queries are not in n_queries yet.
-int groupedl_list(ehx_space* s, hipStream_t st, uint64_t n_eff, const std::vector<uint64_t>& range, size_t nq,
+// host memory; d_list: masked.dList, or a stored column's permutation): any space kind.  count_queries: its queries are not
+// in n_queries yet.
+int groupedl_list(ehx_space* s, hipStream_t st, uint64_t n_eff, const uint64_t* d_list, const std::vector<uint64_t>& range, size_t nq,
                   const float* d_queries, uint32_t k, uint32_t per_group, const uint32_t* d_group_of, uint64_t* d_ids,
                   float* d_dist, uint32_t* d_count, bool count_queries) {
   ehx_space::Grouped& w = s->grouped;
@@ -98,7 +109,7 @@ int groupedl_list(ehx_space* s, hipStream_t st, uint64_t n_eff, const std::vecto
   r.k = k;
   if ((rc = s->clock.scan_begin(st))) return rc;
   for (uint64_t b = 0; b < n_slabs; ++b) {
-    HIP_TRY(launch_grouped_range_slab(s->masked.dList.p, gw.dRange.p, gw.dRange.p + nq, b, b == 0, w.dPool.p, w.dCtl.p, r.radius,
+    HIP_TRY(launch_grouped_range_slab(d_list, gw.dRange.p, gw.dRange.p + nq, b, b == 0, w.dPool.p, w.dCtl.p, r.radius,
                                       r.top_cnt, r.work, (uint32_t)nq, st));
     r.mode = b + 1 == n_slabs ? kRadiusLast : kRadiusPass;
     HIP_TRY(launch_grouped_rerank(g, st));
@@ -111,16 +122,21 @@ int groupedl_list(ehx_space* s, hipStream_t st, uint64_t n_eff, const std::vecto
 
 // One device batch of m <= kSideChunk queries under want[0, m) (host memory) over the prefix of n_eff rows of both columns.
 // *col_copied: the flush's copy of the label column is in place (made once per call, and only where some slot scans).
+// ix: the label column is a stored one — the plan is read from its fresh index (colindex_plan: no launch, no wait), the
+// lists are runs of its permutation and the flush's block is the index's.
 int groupedl_batch(ehx_space* s, hipStream_t st, uint64_t n_pub, uint64_t n_eff, size_t m, const float* d_queries, uint32_t k,
-                   uint32_t per_group, const uint32_t* d_group_of, const uint32_t* d_label_of, const uint32_t* want,
-                   bool* col_copied, const ResultBlock& out) {
+                   uint32_t per_group, const uint32_t* d_group_of, const uint32_t* d_label_of, const ehx_space::ColIndex* ix,
+                   const uint32_t* want, bool* col_copied, const ResultBlock& out) {
   int rc;
   ehx_space::GroupedLabeled& w = s->groupedl;
   // routing: the grouped search's under bitmaps (ehx_groupedm.cpp), applied by the plan before it fills the lists
   const bool scan_serves = s->params.mode != EHX_MODE_GRAPH && !s->x_perm && n_eff > 0 && i8_serves_radius(s, n_eff);
   LabeledPlan p;
-  if ((rc = labeled_plan(s, st, n_eff, m, d_label_of, want, scan_serves, masked_exact_cut(n_pub), kLargeKMinQueries, col_copied, &p)))
+  if (ix) colindex_plan(*ix, m, want, scan_serves, masked_exact_cut(n_pub), kLargeKMinQueries, &p);
+  else if ((rc = labeled_plan(s, st, n_eff, m, d_label_of, want, scan_serves, masked_exact_cut(n_pub), kLargeKMinQueries, col_copied, &p)))
     return rc;
+  const uint64_t* d_list = ix ? ix->dPerm.p : s->masked.dList.p;
+  uint32_t* d_block = ix ? ix->dBlock.p : s->labeled.dBlock.p;
   if ((rc = w.dRange.ensure(2 * m))) return rc;   // (sized once per batch: the seed and the list route upload into it)
   // the order the queries are answered in: the scan route's first (SubsetBufs: gathered, answered, scattered back; skipped
   // when they come in that order — always where no slot scans)
@@ -146,13 +162,13 @@ int groupedl_batch(ehx_space* s, hipStream_t st, uint64_t n_pub, uint64_t n_eff,
     return range;
   };
   auto list = [&](const std::vector<uint64_t>& range, size_t n, const float* q, uint64_t* ids, float* dist, uint32_t* cnt, bool count) {
-    return groupedl_list(s, st, n_eff, range, n, q, k, per_group, d_group_of, ids, dist, cnt, count);
+    return groupedl_list(s, st, n_eff, d_list, range, n, q, k, per_group, d_group_of, ids, dist, cnt, count);
   };
   auto answer = [&](size_t, const float* gq, uint64_t* ids, float* dist, uint32_t* cnt) -> int {
     if (n_scan) {
       RadiusKnn c;
       c.passes = largek_passes(n_eff, env().largek_growth);
-      c.allow = s->labeled.dBlock.p;
+      c.allow = d_block;
       c.allow_label = true;
       c.allow_bits = (uint32_t)n_eff;
       c.out = ResultBlock{ids, dist, cnt, nullptr, n_scan, k};
@@ -163,10 +179,10 @@ int groupedl_batch(ehx_space* s, hipStream_t st, uint64_t n_pub, uint64_t n_eff,
         for (size_t j = 0; j < kLabelHead; ++j)   // (padding queries repeat the last: they collect nothing)
           head[j] = p.table[gs[q0 + std::min(j, mm - 1)]];
         // (pageable host memory: the runtime stages it before the call returns)
-        HIP_TRY(hipMemcpyAsync(s->labeled.dBlock.p, head.data(), kLabelHead * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_block, head.data(), kLabelHead * sizeof(uint32_t), hipMemcpyHostToDevice, st));
         const std::vector<uint64_t> range = ranges_of(nullptr, q0, mm);
         HIP_TRY(hipMemcpyAsync(w.dRange.p, range.data(), 2 * mm * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-        HIP_TRY(launch_grouped_range_seed(s->masked.dList.p, w.dRange.p, w.dRange.p + mm, pool, pool_cnt, (uint32_t)mm, st));
+        HIP_TRY(launch_grouped_range_seed(d_list, w.dRange.p, w.dRange.p + mm, pool, pool_cnt, (uint32_t)mm, st));
         return EHX_OK;
       };
       // The scan runs over the tiles that hold the prefix; the flush drops every row at or above n_eff with the rows of
@@ -212,7 +228,7 @@ int groupedl_batch(ehx_space* s, hipStream_t st, uint64_t n_pub, uint64_t n_eff,
 // labeled.dCol) or on the device; want: in host memory, or d_want, read back once (the outputs unwritten until then)
 int groupedl_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, uint32_t per_group,
                     const uint32_t* group_of, const uint32_t* label_of, bool cols_on_host, uint64_t n_labels,
-                    const uint32_t* want, const uint32_t* d_want, const ResultBlock& out) {
+                    const uint32_t* want, const uint32_t* d_want, const ResultBlock& out, int group_col = -1, int label_col = -1) {
   int rc;
   if ((rc = check_not_poisoned(s))) return rc;
   if (s->ld > grouped_rerank_max_ld())   // (before anything is enqueued)
@@ -221,11 +237,16 @@ int groupedl_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_quer
   s->groupedl_ctr[4] += 1;
   // the ONE read of the row count: the lists name rows below it only, and every later stage sees at least this prefix
   const uint64_t n_pub = s->n.load(std::memory_order_acquire);
-  const uint64_t n_eff = std::min<uint64_t>(n_labels, n_pub);   // (row ids are 32 bits wide: n_pub < 2^32)
-  if ((rc = labeled_plan_scratch(s, n_eff))) return rc;
+  const bool stored = label_col >= 0;   // ehx_knn_grouped_by_label*: both columns are the space's, over the whole prefix
+  const uint64_t n_eff = stored ? n_pub : std::min<uint64_t>(n_labels, n_pub);   // (row ids are 32 bits wide: n_pub < 2^32)
+  if (!stored && (rc = labeled_plan_scratch(s, n_eff))) return rc;
   // (earlier calls' launches on other streams may still read the block, the lists and the staged columns)
   if ((rc = wait_searches_in_flight(s, st))) return rc;
   const uint32_t *d_group_of = group_of, *d_label_of = label_of;
+  const ehx_space::ColIndex* ix = nullptr;   // the label column's index, rebuilt here if a write or an append left it stale
+  if (stored && ((rc = colindex_ensure(s, st, (uint32_t)label_col, n_pub, &ix)) ||
+                 (rc = column_as_groups(s, st, (uint32_t)group_col, n_pub, &d_group_of))))
+    return rc;
   if (cols_on_host) {
     if ((rc = s->grouped.dLabels.ensure(std::max<uint64_t>(n_eff, 1))) || (rc = s->labeled.dCol.ensure(std::max<uint64_t>(n_eff, 1))))
       return rc;
@@ -248,8 +269,8 @@ int groupedl_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_quer
   bool col_copied = false;
   for (size_t q0 = 0; q0 < nq; q0 += kSideChunk) {
     const size_t m = std::min(kSideChunk, nq - q0);
-    if ((rc = groupedl_batch(s, st, n_pub, n_eff, m, d_queries + q0 * s->dims, k, per_group, d_group_of, d_label_of, want + q0,
-                             &col_copied, out.from(q0, m))))
+    if ((rc = groupedl_batch(s, st, n_pub, n_eff, m, d_queries + q0 * s->dims, k, per_group, d_group_of, d_label_of, ix,
+                             want + q0, &col_copied, out.from(q0, m))))
       return rc;
   }
   return EHX_OK;
@@ -285,6 +306,35 @@ int ehx_knn_grouped_labeled(ehx_space* s, size_t n_queries, const float* queries
     if ((rc = h.up(s->stream, queries, n_queries, s->dims, k, false))) return rc;
     if ((rc = groupedl_locked(s, s->stream, n_queries, h.q, k, per_group, group_of, label_of, true, n_labels, want, nullptr,
                               h.out)))
+      return rc;
+    return h.out.copy_out(s->stream, out_ids, out_dist, out_count, nullptr);
+  });
+}
+
+int ehx_knn_grouped_by_label_device(ehx_space* s, void* stream, size_t n_queries, const float* d_queries, uint32_t k,
+                                    uint32_t per_group, uint32_t group_col, uint32_t label_col, const uint32_t* d_want,
+                                    uint64_t* d_out_ids, float* d_out_dist, uint32_t* d_out_count) {
+  if (int rc = grouped_by_label_check(s, n_queries, k, per_group, d_queries, group_col, label_col, d_want, d_out_ids, d_out_dist,
+                                      d_out_count))
+    return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  return search_on_device(s, "ehx_knn_grouped_by_label_device", kGroupedLabeledWhy, n_queries, &st, [&] {
+    return groupedl_locked(s, st, n_queries, d_queries, k, per_group, nullptr, nullptr, false, 0, nullptr, d_want,
+                           ResultBlock{d_out_ids, d_out_dist, d_out_count, nullptr, n_queries, k}, (int)group_col, (int)label_col);
+  });
+}
+
+int ehx_knn_grouped_by_label(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, uint32_t per_group,
+                             uint32_t group_col, uint32_t label_col, const uint32_t* want, uint64_t* out_ids, float* out_dist,
+                             uint32_t* out_count) {
+  if (int rc = grouped_by_label_check(s, n_queries, k, per_group, queries, group_col, label_col, want, out_ids, out_dist, out_count))
+    return rc;
+  return search_on_device(s, "ehx_knn_grouped_by_label", kGroupedLabeledWhy, n_queries, nullptr, [&]() -> int {
+    int rc;
+    HostStage& h = s->groupedl.host;   // (queries up, results down: no column travels)
+    if ((rc = h.up(s->stream, queries, n_queries, s->dims, k, false))) return rc;
+    if ((rc = groupedl_locked(s, s->stream, n_queries, h.q, k, per_group, nullptr, nullptr, false, 0, want, nullptr, h.out,
+                              (int)group_col, (int)label_col)))
       return rc;
     return h.out.copy_out(s->stream, out_ids, out_dist, out_count, nullptr);
   });

@@ -601,6 +601,43 @@ struct ehx_space {
   // test hook: queries answered on the scan route, on the list route (by the gate or handed on by the scan), of those the
   // overflowed, scan passes launched, calls
   std::atomic<uint64_t> groupedl_ctr[5] = {};
+  // Stored label columns (ehx_columns.cpp): column c is one uint32_t per row, written through the write path by key.
+  // dCol[c] is sized to `cap` and moved by grow with the rows; col_live[c] turns true under mu held exclusively, at the
+  // column's first write (readers hold mu at least shared; the writers, serialised by wmu, may read it under wmu alone).  A
+  // column that is not live reads as EHX_GROUP_NONE everywhere.  col_gen[c] counts the writes to entries below the published
+  // row count (mu exclusive) — with the row count it tells a search whether the column's index still describes it.
+  struct Columns {
+    DevBuf<uint32_t> dCol[EHX_MAX_COLUMNS];
+    DevBuf<uint64_t> dDst;       // a write by key (wmu): the row of every entry of the batch (~0: a later entry writes it)
+    DevBuf<uint32_t> dVals;      // ... and its values, a column after the other
+    DevBuf<uint64_t> dGetIds;    // ehx_column_get (scratch_mu): the rows asked for | their values
+    DevBuf<uint32_t> dGetVals;
+    DevBuf<uint32_t> dNone;      // EHX_GROUP_NONE for every row of a prefix: a group column never written (scratch_mu)
+  } cols;
+  bool col_live[EHX_MAX_COLUMNS] = {};
+  std::atomic<uint64_t> col_gen[EHX_MAX_COLUMNS] = {};
+  // The index of a stored column over a prefix of n rows (k_colindex.hip; scratch_mu): valid for a search's snapshot n_pub iff
+  // gen == col_gen[c] and n == n_pub, else rebuilt on the search's stream by the search that finds it stale.
+  struct ColIndex {
+    bool valid = false;
+    uint64_t gen = 0, n = 0;
+    uint32_t n_tiles = 0;
+    DevBuf<uint32_t> dBlock;     // [kLabelHead] the head filtered_answer rewrites per device batch | the column's prefix as
+                                 // the index was built from it: the block of the int8 scan's flush (allow_label)
+    DevBuf<uint32_t> dKey[2], dVal[2];   // the sort's ping-pong arrays
+    DevBuf<uint32_t> dHist;      // [256][tiles of 4096] | [4][256] the column's digit histograms
+    DevBuf<uint32_t> dBounds;    // [n / 256 + 2] labels that begin in every 256-key tile, prefixed
+    DevBuf<uint32_t> dLabels, dStart;    // [L] | [L + 1]
+    DevBuf<uint64_t> dPerm;      // [n] row ids by (label, row id): the lists of every label, back to back
+    DevBuf<uint64_t> dRun;       // [heavy] start | [heavy] end in dPerm of the labels that may scan
+    DevBuf<uint32_t> dCum;       // [heavy][n_tiles + 1]
+    DevBuf<uint64_t> dSample;    // [heavy][256]
+    // the host mirror: planning a search touches the device for nothing that grows with the row count
+    std::vector<uint32_t> labels, start;     // [L] ascending | [L + 1]
+    std::vector<uint32_t> heavy;             // positions in `labels` of the labels with more than masked_exact_cut(n) rows
+    std::vector<uint32_t> cum;               // [heavy][n_tiles + 1]
+    uint64_t builds = 0, served_fresh = 0, last_passes = 0;   // test hook ehx_test_column_counters
+  } colidx[EHX_MAX_COLUMNS];
   // int8 filter scratch: everything ONE in-flight batch of the int8 pipeline owns — prepared queries, query tiles +
   // parameters, per-pass thresholds, sample scores, pools, running best list, verdict, batch clock.  TWO sets: a host
   // caller's batch can be enqueued behind another caller's on the space's stream while that one still waits for its
@@ -699,6 +736,8 @@ struct ehx_space {
     grouped = {};
     groupedm = {};
     groupedl = {};
+    cols = {};
+    for (auto& x : colidx) x = ColIndex{};
     one = {};
     xch = {};
     wr = {};
@@ -1071,6 +1110,46 @@ int labeled_plan_scratch(ehx_space* s, uint64_t n_eff);
 int labeled_plan(ehx_space* s, hipStream_t st, uint64_t n_eff, size_t m, const uint32_t* d_label_of, const uint32_t* want,
                  bool scan_serves, uint64_t cut, size_t min_scan_queries, bool* col_copied, LabeledPlan* p);
 
+// the slots of a device batch: p->table (the distinct wanted labels, ascending), p->n_slots, p->slot_of
+void labeled_slots(const uint32_t* want, size_t m, LabeledPlan* p);
+// ehx_knn_labeled*'s body (label_col < 0) and ehx_knn_by_label*'s (the stored column label_col, d_label_of unused, n_labels the
+// snapshot): an unsharded space, locked shared, scratch_mu held, its device current
+int labeled_locked(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, const float* d_queries, uint32_t k,
+                   const uint32_t* d_label_of, uint64_t n_labels, const uint32_t* want, const uint32_t* d_want,
+                   const ResultBlock& out, int label_col = -1);
+
+// ---- ehx_columns.cpp ----
+struct WriteBatch;
+// The values a Set carries for stored columns: vals[c][i] for column cols[c] of the batch's row i (host memory).
+struct ColumnWrite {
+  uint32_t n_cols = 0;
+  uint32_t cols[EHX_MAX_COLUMNS] = {};
+  const uint32_t* vals[EHX_MAX_COLUMNS] = {};
+  ColumnWrite from(size_t i) const {   // the batch without its first i rows
+    ColumnWrite r = *this;
+    for (uint32_t c = 0; c < n_cols; ++c) r.vals[c] += i;
+    return r;
+  }
+};
+// (wmu held, mu not) the columns cw names exist from here on: the first write of a column takes mu exclusively once
+int columns_create(ehx_space* s, const ColumnWrite& cw);
+// grow()'s group: every live column moved to `want` rows, the first `keep` kept, EHX_GROUP_NONE behind them
+int grow_columns(ehx_space* s, uint64_t want, uint64_t keep, hipStream_t st);
+// write_rows' step, enqueued on the writers' stream in front of the rows: EHX_GROUP_NONE into [old_n, next) of every live
+// column, then cw's values (may be nullptr) by the rows' duplicate rule; a batch that touches committed rows bumps the
+// generation of the columns it writes
+int columns_land(ehx_space* s, hipStream_t ws, const WriteBatch& b, uint64_t old_n, uint64_t next, const ColumnWrite* cw);
+// (scratch_mu held, the space locked shared, `st` ordered behind the searches in flight) the index of column `col` for the
+// prefix of n_pub rows, rebuilt on `st` if it is stale
+int colindex_ensure(ehx_space* s, hipStream_t st, uint32_t col, uint64_t n_pub, const ehx_space::ColIndex** out);
+// labeled_plan's result read from an index instead of compacted: no device work.  p->cum stays empty — the tile prefixes
+// are ix.cum, p->scan_of[f] their row (and the samples') for the slots that scan
+void colindex_plan(const ehx_space::ColIndex& ix, size_t m, const uint32_t* want, bool scan_serves, uint64_t cut,
+                   size_t min_scan_queries, LabeledPlan* p);
+// device pointer to the prefix [0, n_pub) of a stored column as a group column (never written: EHX_GROUP_NONE for every
+// row, made on `st`); scratch_mu held
+int column_as_groups(ehx_space* s, hipStream_t st, uint32_t col, uint64_t n_pub, const uint32_t** out);
+
 // ---- ehx_among.cpp ----
 // exact kNN among row ids on an unsharded space, locked shared, scratch_mu held, its device current (d_off == nullptr: one
 // list shared by every query; max_list: an upper bound of one list's length, 0 = n_cand)
@@ -1102,7 +1181,9 @@ struct RowSource {
   }
 };
 // the body of ehx_set_batch and ehx_set_batch_device: locking, the append-only fast path, graph batches that rewrite keys
-int set_batch_from(ehx_space* s, size_t n, const char* const* keys, const size_t* klens, const RowSource& src);
+// (cw: the values of stored columns the rows carry, ehx_set_batch_cols; nullptr: none)
+int set_batch_from(ehx_space* s, size_t n, const char* const* keys, const size_t* klens, const RowSource& src,
+                   const ColumnWrite* cw = nullptr);
 bool is_dense_run(const uint64_t* ids, size_t n);   // ids[i] == ids[0] + i for every i
 // What a batch of row ids touches, host arithmetic only, computed once per batch by write_batch from the ids and the published
 // row count `old_n` (ids == nullptr: the generator's rows old_n, old_n + 1, ...).
@@ -1117,7 +1198,7 @@ struct WriteBatch {
 WriteBatch write_batch(const uint64_t* ids, size_t n, uint64_t old_n);
 // the write path behind every Set (new_keys == nullptr: a shard's rows, whose parent publishes the keys); invariants at its head
 int write_rows(ehx_space* s, const WriteBatch& b, uint64_t next, const RowSource& src, std::vector<std::string>* new_keys,
-               bool append_only);
+               bool append_only, const ColumnWrite* cw = nullptr);
 // new_keys (moved from) become the keys of rows old_n, old_n + 1, ...; under kmu
 void publish_keys(ehx_space* s, uint64_t old_n, std::vector<std::string>& new_keys);
 // The duplicate rule of a parallel scatter: out[i] = ids[i] for the LAST occurrence of every id, ~0 for the ones before it —

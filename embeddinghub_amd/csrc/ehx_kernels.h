@@ -584,6 +584,29 @@ hipError_t launch_labeled_fill(const uint16_t* slot_of, uint64_t n_rows, uint32_
                                uint32_t* cursor, uint64_t* list, hipStream_t st);
 hipError_t launch_labeled_samples(const uint64_t* list, const uint64_t* scan_off, const uint32_t* cum, uint32_t n_scan,
                                   uint32_t n_tiles, uint64_t* sample, hipStream_t st);
+// stored label columns (k_colindex.hip; ehx_columns.cpp): the index of a column over n < 2^32 rows, by a stable LSD radix
+// sort of (label, row id) with 8-bit digits over tiles of kColIndexTile keys.
+//   launch_colindex_digits  ghist[4][256] = the four digit histograms of keys[0, n) (cleared here)
+//   launch_colindex_pass    ONE digit pass keys_in / vals_in -> keys_out / vals_out (vals_in nullptr: the positions); hist:
+//                           scratch of 256 * colindex_blocks(n) words; ghist: launch_colindex_digits'
+//   launch_colindex_bounds  sorted keys (vals nullptr: the identity) -> labels[L], start[L + 1], perm[n] (64-bit row ids);
+//                           bbase: scratch of n / 256 + 2 words, its entry [ceil(n / 256)] = L when the launches have run
+//   launch_colindex_heavy   run: [n_heavy] starts | [n_heavy] ends in perm of the labels that may scan (ascending row ids
+//                           inside each) -> cum[n_heavy][n_tiles + 1] rows before every 256-row tile (labeled_prefix_kernel's
+//                           layout), sample[n_heavy][256] by rank
+//   launch_column_scatter   col[dst_row[i]] = values[i] where dst_row[i] < cap (~0: skipped); launch_column_gather the reverse
+constexpr uint32_t kColIndexTile = 4096;
+inline uint32_t colindex_blocks(uint64_t n) { return (uint32_t)((n + kColIndexTile - 1) / kColIndexTile); }
+hipError_t launch_colindex_digits(const uint32_t* keys, uint64_t n, uint32_t* ghist, hipStream_t st);
+hipError_t launch_colindex_pass(const uint32_t* keys_in, const uint32_t* vals_in, uint32_t* keys_out, uint32_t* vals_out,
+                                uint64_t n, uint32_t digit, const uint32_t* ghist, uint32_t* hist, hipStream_t st);
+hipError_t launch_colindex_bounds(const uint32_t* keys, const uint32_t* vals, uint64_t n, uint32_t* bbase, uint32_t* labels,
+                                  uint32_t* start, uint64_t* perm, hipStream_t st);
+hipError_t launch_colindex_heavy(const uint64_t* perm, const uint64_t* run, uint32_t n_heavy, uint32_t n_tiles, uint32_t* cum,
+                                 uint64_t* sample, hipStream_t st);
+hipError_t launch_column_scatter(uint32_t* col, uint64_t cap, const uint64_t* dst_row, const uint32_t* values, size_t n,
+                                 hipStream_t st);
+hipError_t launch_column_gather(const uint32_t* col, uint64_t cap, const uint64_t* rows, uint32_t* out, size_t n, hipStream_t st);
 // radius[q] = dist[q][k - 1] when cnt[q] >= k (result lists [nq][k]), else +Inf
 hipError_t launch_masked_radius(const float* dist, const uint32_t* cnt, uint32_t nq, uint32_t k, float* radius, hipStream_t st);
 // word w of a bitmap cut at n_bits (bits of the last word beyond n_bits and words beyond it read as 0)

@@ -45,6 +45,15 @@ int labeled_check(const ehx_space* s, size_t nq, uint32_t k, const void* q, cons
   return EHX_OK;
 }
 
+// ehx_knn_by_label*: ehx_knn_labeled*'s checks with their codes and in their order (the column is the space's: no pointer,
+// no length), then the column number
+int by_label_check(const ehx_space* s, size_t nq, uint32_t k, const void* q, uint32_t label_col, const void* want,
+                   const void* o_ids, const void* o_dist, const void* o_cnt) {
+  if (int rc = labeled_check(s, nq, k, q, nullptr, 0, want, o_ids, o_dist, o_cnt)) return rc;
+  if (label_col >= EHX_MAX_COLUMNS) return fail(EHX_EINVAL, "label_col = %u: a space has %u columns", label_col, (unsigned)EHX_MAX_COLUMNS);
+  return EHX_OK;
+}
+
 }  // namespace
 
 namespace ehx_impl {
@@ -58,6 +67,18 @@ int labeled_plan_scratch(ehx_space* s, uint64_t n_eff) {
   return EHX_OK;
 }
 
+// the slots: the batch's distinct wanted labels, ascending, and the slot of every query
+void labeled_slots(const uint32_t* want, size_t m, LabeledPlan* p) {
+  std::vector<uint32_t>& table = p->table;
+  table.assign(want, want + m);
+  p->slot_of.resize(m);
+  std::sort(table.begin(), table.end());
+  table.erase(std::unique(table.begin(), table.end()), table.end());
+  p->n_slots = (uint32_t)table.size();
+  for (size_t j = 0; j < m; ++j)
+    p->slot_of[j] = (uint32_t)(std::lower_bound(table.begin(), table.end(), want[j]) - table.begin());
+}
+
 // The compaction of the column for one device batch (ehx_internal.h has the contract).
 int labeled_plan(ehx_space* s, hipStream_t st, uint64_t n_eff, size_t m, const uint32_t* d_label_of, const uint32_t* want,
                  bool scan_serves, uint64_t cut, size_t min_scan_queries, bool* col_copied, LabeledPlan* p) {
@@ -65,15 +86,9 @@ int labeled_plan(ehx_space* s, hipStream_t st, uint64_t n_eff, size_t m, const u
   ehx_space::Labeled& w = s->labeled;
   ehx_space::Masked& mw = s->masked;
   const uint32_t n_tiles = p->n_tiles = (uint32_t)((n_eff + kTileRows16 - 1) / kTileRows16);
-  // the slots: the batch's distinct wanted labels, ascending, and the slot of every query
+  labeled_slots(want, m, p);
   std::vector<uint32_t>& table = p->table;
-  table.assign(want, want + m);
-  p->slot_of.resize(m);
-  std::sort(table.begin(), table.end());
-  table.erase(std::unique(table.begin(), table.end()), table.end());
-  const uint32_t n_slots = p->n_slots = (uint32_t)table.size();
-  for (size_t j = 0; j < m; ++j)
-    p->slot_of[j] = (uint32_t)(std::lower_bound(table.begin(), table.end(), want[j]) - table.begin());
+  const uint32_t n_slots = p->n_slots;
   uint32_t* d_table = w.dSlots.p;
   uint32_t* d_count = d_table + kLabeledMaxSlots;
   uint32_t* d_scan_of = d_count + kLabeledMaxSlots;
@@ -147,15 +162,19 @@ int labeled_plan(ehx_space* s, hipStream_t st, uint64_t n_eff, size_t m, const u
 namespace {
 
 // One device batch of m <= kSideChunk queries under want[0, m) (host memory) over the prefix of n_eff rows of d_label_of:
-// the plan, its view, the bitmap search's answer.
+// the plan, its view, the bitmap search's answer.  ix: the plan is read from a stored column's fresh index instead
+// (colindex_plan: no launch, no wait) — its lists are runs of the index's permutation, its tile prefixes, samples and the
+// flush's block the index's own.
 int labeled_batch(ehx_space* s, hipStream_t st, uint64_t n_pub, uint64_t n_eff, size_t m, const float* d_queries, uint32_t k,
-                  const uint32_t* d_label_of, const uint32_t* want, bool* col_copied, const ResultBlock& out) {
+                  const uint32_t* d_label_of, const ehx_space::ColIndex* ix, const uint32_t* want, bool* col_copied,
+                  const ResultBlock& out) {
   ehx_space::Labeled& w = s->labeled;
   ehx_space::Masked& mw = s->masked;
   const uint32_t forced = s->labeled_route.load(std::memory_order_relaxed);   // (test hook: the bench's crossover sweep)
   const uint64_t cut = forced == 1 ? 0 : forced == 2 ? ~0ull : masked_exact_cut(n_pub);
   LabeledPlan p;
-  if (int rc = labeled_plan(s, st, n_eff, m, d_label_of, want, filter_scan_serves(s, k, n_pub), cut, 0, col_copied, &p)) return rc;
+  if (ix) colindex_plan(*ix, m, want, filter_scan_serves(s, k, n_pub), cut, 0, &p);
+  else if (int rc = labeled_plan(s, st, n_eff, m, d_label_of, want, filter_scan_serves(s, k, n_pub), cut, 0, col_copied, &p)) return rc;
   const uint32_t n_tiles = p.n_tiles, n_scan = p.n_scan;
   FilterView v;
   v.n_pub = n_pub;
@@ -167,18 +186,18 @@ int labeled_batch(ehx_space* s, hipStream_t st, uint64_t n_pub, uint64_t n_eff, 
   v.off = p.off.data();
   v.filter_of = p.slot_of.data();
   v.scans = p.scans.data();
-  v.cum = p.cum.data();
+  v.cum = ix ? ix->cum.data() : p.cum.data();
   v.scan_of = p.scan_of.data();
-  v.d_list = mw.dList.p;
-  v.sample = &mw.dSample;
+  v.d_list = ix ? ix->dPerm.p : mw.dList.p;
+  v.sample = ix ? &ix->dSample : &mw.dSample;
   v.samples = [&]() -> int {
+    if (ix) return EHX_OK;   // (prepared when the index was built)
     if (int r = mw.dSample.ensure((size_t)n_scan * 256)) return r;
     HIP_TRY(launch_labeled_samples(mw.dList.p, w.dOff.p + kLabeledMaxSlots, mw.dCum.p, n_scan, n_tiles, mw.dSample.p, st));
     return EHX_OK;
   };
-  v.allow = w.dBlock.p;
+  v.allow = v.d_head = ix ? ix->dBlock.p : w.dBlock.p;
   v.allow_label = true;
-  v.d_head = w.dBlock.p;
   v.head_of = p.table.data();   // (the head word of a query is its wanted label itself)
   v.shared_min = kLabeledSharedMin;
   v.d_range = &w.dRange;
@@ -186,19 +205,23 @@ int labeled_batch(ehx_space* s, hipStream_t st, uint64_t n_pub, uint64_t n_eff, 
   return filtered_answer(s, st, m, d_queries, k, v, out);
 }
 
+}  // namespace
+
 // an unsharded space, locked shared, scratch_mu held, its device current; everything is enqueued on `st`.  want: in host
 // memory; or d_want, read back once (the outputs unwritten until then).
-int labeled_locked(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, const float* d_queries, uint32_t k,
-                   const uint32_t* d_label_of, uint64_t n_labels, const uint32_t* want, const uint32_t* d_want,
-                   const ResultBlock& out) {
+int ehx_impl::labeled_locked(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, const float* d_queries, uint32_t k,
+                             const uint32_t* d_label_of, uint64_t n_labels, const uint32_t* want, const uint32_t* d_want,
+                             const ResultBlock& out, int label_col) {
   int rc;
   if ((rc = check_not_poisoned(s))) return rc;
   if ((rc = check_rows_fit_lds(s, "filtered search"))) return rc;   // (before anything is enqueued)
   s->labeled_ctr[4] += 1;
   const uint64_t n_eff = std::min<uint64_t>(n_labels, n_pub);   // (row ids are 32 bits wide: n_pub < 2^32)
-  if ((rc = labeled_plan_scratch(s, n_eff))) return rc;
+  if (label_col < 0 && (rc = labeled_plan_scratch(s, n_eff))) return rc;
   // (earlier calls' launches on other streams may still read the block, the lists and the samples)
   if ((rc = wait_searches_in_flight(s, st))) return rc;
+  const ehx_space::ColIndex* ix = nullptr;   // a stored column: its index, rebuilt here if a write or an append left it stale
+  if (label_col >= 0 && (rc = colindex_ensure(s, st, (uint32_t)label_col, n_pub, &ix))) return rc;
   std::vector<uint32_t> want_read;
   if (!want) {
     want_read.resize(nq);
@@ -209,14 +232,12 @@ int labeled_locked(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, cons
   bool col_copied = false;
   for (size_t q0 = 0; q0 < nq; q0 += kSideChunk) {
     const size_t m = std::min(kSideChunk, nq - q0);
-    if ((rc = labeled_batch(s, st, n_pub, n_eff, m, d_queries + q0 * s->dims, k, d_label_of, want + q0, &col_copied,
+    if ((rc = labeled_batch(s, st, n_pub, n_eff, m, d_queries + q0 * s->dims, k, d_label_of, ix, want + q0, &col_copied,
                             out.from(q0, m))))
       return rc;
   }
   return EHX_OK;
 }
-
-}  // namespace
 
 extern "C" {
 
@@ -247,6 +268,32 @@ int ehx_knn_labeled(ehx_space* s, size_t n_queries, const float* queries, uint32
       return rc;
     if (n_eff) HIP_TRY(hipMemcpyAsync(s->labeled.dCol.p, label_of, n_eff * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
     if ((rc = labeled_locked(s, s->stream, n_pub, n_queries, h.q, k, s->labeled.dCol.p, n_labels, want, nullptr, h.out))) return rc;
+    return h.out.copy_out(s->stream, out_ids, out_dist, out_count, nullptr);
+  });
+}
+
+int ehx_knn_by_label_device(ehx_space* s, void* stream, size_t n_queries, const float* d_queries, uint32_t k, uint32_t label_col,
+                            const uint32_t* d_want, uint64_t* d_out_ids, float* d_out_dist, uint32_t* d_out_count) {
+  if (int rc = by_label_check(s, n_queries, k, d_queries, label_col, d_want, d_out_ids, d_out_dist, d_out_count)) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  return search_on_device(s, "ehx_knn_by_label_device", kLabeledWhy, n_queries, &st, [&] {
+    const uint64_t n_pub = s->n.load(std::memory_order_acquire);   // the ONE read of the row count
+    test_pause();   // (an append may publish here: the index and every stage describe n_pub rows all the same)
+    return labeled_locked(s, st, n_pub, n_queries, d_queries, k, nullptr, n_pub, nullptr, d_want,
+                          ResultBlock{d_out_ids, d_out_dist, d_out_count, nullptr, n_queries, k}, (int)label_col);
+  });
+}
+
+int ehx_knn_by_label(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, uint32_t label_col, const uint32_t* want,
+                     uint64_t* out_ids, float* out_dist, uint32_t* out_count) {
+  if (int rc = by_label_check(s, n_queries, k, queries, label_col, want, out_ids, out_dist, out_count)) return rc;
+  return search_on_device(s, "ehx_knn_by_label", kLabeledWhy, n_queries, nullptr, [&]() -> int {
+    int rc;
+    const uint64_t n_pub = s->n.load(std::memory_order_acquire);   // the ONE read of the row count
+    test_pause();
+    HostStage& h = s->labeled.host;   // (queries up, results down: no column travels)
+    if ((rc = h.up(s->stream, queries, n_queries, s->dims, k, false))) return rc;
+    if ((rc = labeled_locked(s, s->stream, n_pub, n_queries, h.q, k, nullptr, n_pub, want, nullptr, h.out, (int)label_col))) return rc;
     return h.out.copy_out(s->stream, out_ids, out_dist, out_count, nullptr);
   });
 }

@@ -127,6 +127,7 @@ int grow(ehx_space* s, uint64_t rows) {
   if (s->has16 && (rc = grow_scan16(s, want, keep, st))) return rc;
   if (s->has8 && (rc = grow_scan8(s, want, keep, st))) return rc;
   if (s->params.mode == EHX_MODE_GRAPH && !s->x_perm && (rc = grow_search_copy(s, want, keep, st))) return rc;
+  if ((rc = grow_columns(s, want, keep, st))) return rc;
   s->rows.dX.swap(nx);  // (single-copy graph spaces: the rows ARE the search copy, ehx_space::xs)
   s->rows.dRowp.swap(nr);
   s->rows.dInv.swap(ni);

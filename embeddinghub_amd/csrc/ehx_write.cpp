@@ -306,8 +306,11 @@ static int join_graph(ehx_space* s, const WriteBatch& b, uint64_t old_n, uint64_
 //      lists are uploaded from this frame).
 //   6. tev[0..2] are recorded before the rows, behind the rows, and behind the derived copies; the generator records none.
 //   7. Graph rows join in call order (join_graph), after the row count is published.
+//   8. Stored columns (ehx_columns.cpp) are written on the writers' stream in front of the rows: EHX_GROUP_NONE for every
+//      appended row of every live column, then the batch's own values — both before the stream wait of finish_rows, so before
+//      the keys and the row count are published.  A search that sees a row sees its labels.
 int write_rows(ehx_space* s, const WriteBatch& b, uint64_t next, const RowSource& src, std::vector<std::string>* new_keys,
-               bool append_only) {
+               bool append_only, const ColumnWrite* cw) {
   if (s->frozen) return fail(EHX_EIMMUTABLE, "Cannot write to immutable space");
   HIP_TRY(hipSetDevice(s->device));
   hipStream_t ws = s->wr.wstream ? s->wr.wstream : s->stream;
@@ -329,6 +332,7 @@ int write_rows(ehx_space* s, const WriteBatch& b, uint64_t next, const RowSource
   if (s->wr.timed) HIP_TRY(hipEventRecord(s->wr.tev[0], ws));
   DrainUnlessOk drain{ws, src.host != nullptr};
   if (src.dev && (rc = prepare_device(s, b, src, &dst_rows))) return rc;
+  if ((rc = columns_land(s, ws, b, old_n, next, cw))) return rc;
   {
     RawRowsGuard raw(s, b);
     if ((rc = src.host ? land_host(s, ws, b, src.host) : land_device(s, ws, b, src, dst_rows))) return rc;
@@ -347,18 +351,22 @@ int write_rows(ehx_space* s, const WriteBatch& b, uint64_t next, const RowSource
   return join_graph(s, b, old_n, next);
 }
 
-static int set_batch_locked(ehx_space* s, size_t n, const char* const* keys, const size_t* klens, const RowSource& src) {
+static int set_batch_locked(ehx_space* s, size_t n, const char* const* keys, const size_t* klens, const RowSource& src,
+                            const ColumnWrite* cw) {
   if (is_parent(s)) return sharded_set_batch(s, n, keys, klens, src);
   if (s->frozen) return fail(EHX_EIMMUTABLE, "Cannot write to immutable space");
   std::vector<uint64_t> ids;
   std::vector<std::string> new_keys;
   uint64_t next = 0;
   resolve_keys(s, n, keys, klens, &ids, &next, &new_keys);
-  return write_rows(s, write_batch(ids.data(), n, s->n), next, src, &new_keys, false);
+  return write_rows(s, write_batch(ids.data(), n, s->n), next, src, &new_keys, false, cw);
 }
 
-int set_batch_from(ehx_space* s, size_t n, const char* const* keys, const size_t* klens, const RowSource& src) {
+int set_batch_from(ehx_space* s, size_t n, const char* const* keys, const size_t* klens, const RowSource& src,
+                   const ColumnWrite* cw) {
   std::lock_guard<std::mutex> wg(s->wmu);
+  if (cw)   // (a column's first write takes the exclusive path once; a dropped, row-sharded or frozen space is refused there)
+    if (int rc = columns_create(s, *cw)) return rc;
   std::vector<uint64_t> ids;
   std::vector<std::string> new_keys;
   uint64_t next = 0;
@@ -375,7 +383,7 @@ int set_batch_from(ehx_space* s, size_t n, const char* const* keys, const size_t
         b = write_batch(ids.data(), n, s->n);
       }
     }
-    if (b.all_appended) return write_rows(s, b, next, src, &new_keys, true);
+    if (b.all_appended) return write_rows(s, b, next, src, &new_keys, true, cw);
   }
   s->excl_waiting.fetch_add(1, std::memory_order_release);   // (searches that arrive from here on wait for this batch's turn)
   std::unique_lock<std::shared_mutex> wl(s->mu);
@@ -387,12 +395,14 @@ int set_batch_from(ehx_space* s, size_t n, const char* const* keys, const size_t
     // twice) every row must be in HBM exactly when its turn comes, so such batches go row by row
     resolve_keys(s, n, keys, klens, &ids, &next, &new_keys);
     if (!write_batch(ids.data(), n, s->n).all_appended) {
-      for (size_t i = 0; i < n; ++i)
-        if (int rc = set_batch_locked(s, 1, keys + i, klens + i, src.from(i, s->dims))) return rc;
+      for (size_t i = 0; i < n; ++i) {
+        const ColumnWrite one = cw ? cw->from(i) : ColumnWrite{};
+        if (int rc = set_batch_locked(s, 1, keys + i, klens + i, src.from(i, s->dims), cw ? &one : nullptr)) return rc;
+      }
       return EHX_OK;
     }
   }
-  return set_batch_locked(s, n, keys, klens, src);
+  return set_batch_locked(s, n, keys, klens, src, cw);
 }
 
 // rows row0, row0 + stride, ... of dataset `seed` appended to the space (locked exclusively by the caller) by the tail of
@@ -410,6 +420,7 @@ int fill_synthetic_locked(ehx_space* s, uint64_t seed, uint64_t row0, uint64_t n
   s->implicit_keys = true;
   const WriteBatch b = write_batch(nullptr, n_rows, old_n);
   RawRowsGuard raw(s, b);   // (never armed: nothing committed is touched)
+  if ((rc = columns_land(s, s->stream, b, old_n, next, nullptr))) return rc;
   if ((rc = land_generated(s, s->stream, old_n, n_rows, seed, row0, normalize, stride, latent))) return rc;
   if ((rc = finish_rows(s, s->stream, b, {}, raw, true, next, nullptr))) return rc;
   if ((rc = publish_rows(s, next, false))) return rc;

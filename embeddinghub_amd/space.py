@@ -601,6 +601,118 @@ class Space:
                                                      _ptr(d_group_of), _ptr(d_label_of), int(n_labels), _ptr(d_want),
                                                      _ptr(d_ids), _ptr(d_dist), _ptr(d_count)))
 
+    # ---- stored label columns: labels written with the rows, searched by column number ----
+    def set_batch_cols(self, keys, vecs, columns):
+        """set_batch plus labels (ehx_set_batch_cols): columns maps a column number (< MAX_COLUMNS) to one u32 value per
+        key.  The labels land before the rows are published; a key given twice keeps its last value; an empty mapping is
+        set_batch."""
+        v, pv = _f32(vecs)
+        v = v.reshape(-1, self.dims)
+        n, arr, lens, keep = marshal_keys(keys)
+        if n != v.shape[0]:
+            raise ValueError("keys/vecs length mismatch")
+        cols, vals = marshal_columns(columns, n)
+        u32p = C.POINTER(C.c_uint32)
+        ptrs = (u32p * max(len(vals), 1))(*[a.ctypes.data_as(u32p) for a in vals])
+        check(self._L.ehx_set_batch_cols(self._h, n, arr, lens, pv, len(vals), cols.ctypes.data_as(u32p), ptrs))
+        del keep
+
+    def column_set(self, col, keys, values):
+        """Relabel existing rows by key (ehx_column_set).  An unknown key raises EhxError (ENOTFOUND) whose `bad_index` is its
+        position, and nothing is written."""
+        n, arr, lens, keep = marshal_keys(keys)
+        vals = np.ascontiguousarray(np.asarray(values).reshape(-1), dtype=np.uint32)
+        if vals.shape[0] != n:
+            raise ValueError("expected %d values, got %d" % (n, vals.shape[0]))
+        bad = C.c_size_t(0)
+        rc = self._L.ehx_column_set(self._h, int(col), n, arr, lens, vals.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(bad))
+        del keep
+        _check_bad(rc, bad)
+
+    def column_get(self, col, keys):
+        """The column's values of stored keys (ehx_column_get) -> u32 [n]; GROUP_NONE where none was ever given.  An unknown
+        key raises EhxError (ENOTFOUND) with `bad_index`."""
+        n, arr, lens, keep = marshal_keys(keys)
+        out = np.zeros(n, dtype=np.uint32)
+        bad = C.c_size_t(0)
+        rc = self._L.ehx_column_get(self._h, int(col), n, arr, lens, out.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(bad))
+        del keep
+        _check_bad(rc, bad)
+        return out
+
+    def column_load_device(self, col, row0, d_values, n=None, stream=None):
+        """Rows [row0, row0 + n) of a column from a torch CUDA tensor of u32 (int32 storage) (ehx_column_load_device); n
+        defaults to the tensor's length.  The range must lie below len(self)."""
+        if n is None:
+            if not hasattr(d_values, "numel"):
+                raise ValueError("pass a torch tensor, or n")
+            n = d_values.numel()
+        if hasattr(d_values, "numel") and d_values.numel() < int(n):
+            raise ValueError("%d values are fewer than n = %d" % (d_values.numel(), n))
+        check(self._L.ehx_column_load_device(self._h, C.c_void_p(stream or 0), int(col), int(row0), int(n), _ptr(d_values)))
+
+    def column_read_device(self, col, row0, d_out, n=None, stream=None):
+        """Rows [row0, row0 + n) of a column into a torch CUDA tensor of u32 (int32 storage) (ehx_column_read_device)."""
+        if n is None:
+            if not hasattr(d_out, "numel"):
+                raise ValueError("pass a torch tensor, or n")
+            n = d_out.numel()
+        if hasattr(d_out, "numel") and d_out.numel() < int(n):
+            raise ValueError("%d entries are fewer than n = %d" % (d_out.numel(), n))
+        check(self._L.ehx_column_read_device(self._h, C.c_void_p(stream or 0), int(col), int(row0), int(n), _ptr(d_out)))
+
+    def knn_by_label(self, queries, k, label_col, want):
+        """knn_labeled on the STORED column label_col (ehx_knn_by_label): query i sees the rows whose stored label is
+        want[i]; rows never labelled carry 0xFFFFFFFF.  No column travels: the space indexes it once and reuses the index
+        until the column or the row count changes.  -> ids [nq,k] u64, dist [nq,k] f32, count [nq] u32."""
+        q, pq = _f32(queries)
+        q = q.reshape(-1, self.dims)
+        nq = q.shape[0]
+        w = np.ascontiguousarray(np.asarray(want).reshape(-1), dtype=np.uint32)
+        if w.shape[0] != nq:
+            raise ValueError("expected %d wanted labels, got %d" % (nq, w.shape[0]))
+        (ids, dist, cnt), out = _results(nq, k)
+        check(self._L.ehx_knn_by_label(self._h, nq, pq, k, int(label_col), w.ctypes.data_as(C.POINTER(C.c_uint32)), *out))
+        return ids[:, :k], dist[:, :k], cnt
+
+    def knn_by_label_device(self, d_queries, k, label_col, d_want, d_ids, d_dist, d_count, stream=None):
+        """knn_by_label without anything leaving the device: torch CUDA tensors — d_queries [nq, dims] f32, d_want [nq] u32
+        (int32 storage), outputs as knn_device's."""
+        nq = d_queries.shape[0] if hasattr(d_queries, "shape") else None
+        if nq is None:
+            raise ValueError("pass torch tensors (queries [nq, dims], wanted labels)")
+        if hasattr(d_want, "numel") and d_want.numel() < nq:
+            raise ValueError("%d wanted labels for %d queries" % (d_want.numel(), nq))
+        check(self._L.ehx_knn_by_label_device(self._h, C.c_void_p(stream or 0), nq, _ptr(d_queries), k, int(label_col),
+                                              _ptr(d_want), _ptr(d_ids), _ptr(d_dist), _ptr(d_count)))
+
+    def knn_grouped_by_label(self, queries, k, group_col, label_col, want, per_group=1):
+        """knn_grouped_labeled on STORED columns (ehx_knn_grouped_by_label): group_col holds every row's group (GROUP_NONE: a
+        group of its own, also every row never given one), label_col its tenant.
+        -> ids [nq,k] u64, dist [nq,k] f32, count [nq] u32."""
+        q, pq = _f32(queries)
+        q = q.reshape(-1, self.dims)
+        nq = q.shape[0]
+        w = np.ascontiguousarray(np.asarray(want).reshape(-1), dtype=np.uint32)
+        if w.shape[0] != nq:
+            raise ValueError("expected %d wanted labels, got %d" % (nq, w.shape[0]))
+        (ids, dist, cnt), out = _results(nq, k)
+        check(self._L.ehx_knn_grouped_by_label(self._h, nq, pq, k, int(per_group), int(group_col), int(label_col),
+                                               w.ctypes.data_as(C.POINTER(C.c_uint32)), *out))
+        return ids[:, :k], dist[:, :k], cnt
+
+    def knn_grouped_by_label_device(self, d_queries, k, group_col, label_col, d_want, d_ids, d_dist, d_count, per_group=1,
+                                    stream=None):
+        """knn_grouped_by_label without anything leaving the device: tensors as knn_by_label_device's."""
+        nq = d_queries.shape[0] if hasattr(d_queries, "shape") else None
+        if nq is None:
+            raise ValueError("pass torch tensors (queries [nq, dims], wanted labels)")
+        if hasattr(d_want, "numel") and d_want.numel() < nq:
+            raise ValueError("%d wanted labels for %d queries" % (d_want.numel(), nq))
+        check(self._L.ehx_knn_grouped_by_label_device(self._h, C.c_void_p(stream or 0), nq, _ptr(d_queries), k, int(per_group),
+                                                      int(group_col), int(label_col), _ptr(d_want), _ptr(d_ids), _ptr(d_dist),
+                                                      _ptr(d_count)))
+
     # ---- kNN under a row bitmap on the graph path ----
     def graph_knn_masked(self, queries, k, allow, n_bits=None, route=_lib.WALK_AUTO):
         """The k nearest ALLOWED rows the graph walk finds (ehx_graph_knn_masked): approximate when walked, possibly fewer
@@ -814,6 +926,23 @@ def marshal_mask(allow, n_bits=None):
     if n < 0 or n > a.shape[0] * 32:
         raise ValueError("n_bits = %d outside %d mask words" % (n, a.shape[0]))
     return np.ascontiguousarray(a), n
+
+
+def marshal_columns(columns, n):
+    """The labels of set_batch_cols -> (u32 column numbers [n_cols]; the u32 value arrays, [n] each, C-contiguous).  columns:
+    a mapping column number -> n integer values (0 .. 0xFFFFFFFF)."""
+    cols, vals = [], []
+    for c, v in dict(columns).items():
+        a = np.asarray(v).reshape(-1)
+        if a.dtype.kind not in "ui" and a.size:
+            raise ValueError("column values must be integers, got dtype %s" % a.dtype)
+        if a.shape[0] != n:
+            raise ValueError("column %d: expected %d values, got %d" % (c, n, a.shape[0]))
+        if a.size and (a.min() < 0 or a.max() > 0xFFFFFFFF):
+            raise ValueError("column values must fit 32 bits")
+        cols.append(int(c))
+        vals.append(np.ascontiguousarray(a, dtype=np.uint32))
+    return np.asarray(cols, dtype=np.uint32).reshape(-1), vals
 
 
 def marshal_groups(group_of):

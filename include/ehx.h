@@ -229,6 +229,39 @@ int ehx_set_batch(ehx_space* s, size_t n, const char* const* keys, const size_t*
 int ehx_set_batch_device(ehx_space* s, void* stream, size_t n, const char* const* keys, const size_t* klens,
                          const void* d_vecs /* n x dims, row-major, in HBM */, int src_dtype);
 
+/* ---- stored label columns: labels written with the rows, indexed once ----
+ * A space owns up to EHX_MAX_COLUMNS columns of one uint32_t per row, in device memory, sized and moved with the rows.  A
+ * column exists from its first write (which takes the space's exclusive lock once); a column that was never written reads as
+ * EHX_GROUP_NONE (0xFFFFFFFF) for every row, and searches on it work.  A row whose value was never given holds the default
+ * EHX_GROUP_NONE: rows appended by ehx_set, ehx_set_batch, ehx_set_batch_device and ehx_fill_* after the column exists.
+ * Rewriting a row's vector in place (a Set on a known key) keeps its column values.  Errors common to all of the entry points
+ * below: a NULL space: EHX_EINVAL, before the device is looked for; a column number at or above EHX_MAX_COLUMNS: EHX_EINVAL;
+ * a dropped space: EHX_ENOTFOUND; a row-sharded space: EHX_EUNSUPPORTED; for the writes, a frozen space: EHX_EIMMUTABLE.
+ * n == 0: EHX_OK. */
+#define EHX_MAX_COLUMNS 4
+/* ehx_set_batch plus values[c][i] for column cols[c] of keys[i] (values: n_cols host arrays of n entries).  The labels land
+ * before the row count is published — on the writers' stream, in front of the rows, on the append-only path; inside the same
+ * exclusive section for a batch that touches committed rows — so no search ever sees a new row with a stale or default
+ * label.  A key given twice in one batch keeps its last value, as it keeps its last row.  n_cols == 0 is ehx_set_batch.  A
+ * column named twice, NULL cols / values with n_cols > 0: EHX_EINVAL. */
+int ehx_set_batch_cols(ehx_space* s, size_t n, const char* const* keys, const size_t* klens, const float* vecs, uint32_t n_cols,
+                       const uint32_t* cols, const uint32_t* const* values);
+/* Relabels existing rows by key: column col of keys[i] becomes values[i] (a key given twice keeps its last value).  An unknown
+ * key fails the whole call with EHX_ENOTFOUND, stores its index in *bad_index (may be NULL) as ehx_get_batch does, and
+ * nothing is written.  A rewrite in place: it takes the exclusive lock and waits for the searches in flight, as a Set on
+ * known keys does. */
+int ehx_column_set(ehx_space* s, uint32_t col, size_t n, const char* const* keys, const size_t* klens, const uint32_t* values,
+                   size_t* bad_index /* may be NULL */);
+/* column col of keys[i] -> out_values[i]; an unknown key: EHX_ENOTFOUND, its index in *bad_index, out_values unwritten. */
+int ehx_column_get(ehx_space* s, uint32_t col, size_t n, const char* const* keys, const size_t* klens, uint32_t* out_values,
+                   size_t* bad_index /* may be NULL */);
+/* Bulk load of the contiguous row ids [row0, row0 + n) of a column from device memory (for example after
+ * ehx_fill_synthetic), copied on `stream` (a hipStream_t as void*); the call returns with the values in place.  The range
+ * must lie below the row count: otherwise EHX_EINVAL.  A rewrite in place, as ehx_column_set. */
+int ehx_column_load_device(ehx_space* s, void* stream, uint32_t col, uint64_t row0, uint64_t n, const uint32_t* d_values);
+/* ... and the same range read back into device memory; the call returns with d_out written. */
+int ehx_column_read_device(ehx_space* s, void* stream, uint32_t col, uint64_t row0, uint64_t n, uint32_t* d_out);
+
 /* ---- reads: Get (server.cc:95-111), OnlineStoreTable.Get (online.go:52) ---- */
 int ehx_get(ehx_space* s, const char* key, size_t klen, float* out_vec /* dims floats */);
 int ehx_get_by_id(ehx_space* s, uint64_t id, float* out_vec);
@@ -634,6 +667,40 @@ int ehx_knn_grouped_labeled_device(ehx_space* s, void* stream, size_t n_queries,
                                    uint32_t per_group, const uint32_t* d_group_of, const uint32_t* d_label_of,
                                    uint64_t n_labels, const uint32_t* d_want, uint64_t* d_out_ids, float* d_out_dist,
                                    uint32_t* d_out_count);
+/* Partitioned kNN on a STORED column: "the nearest rows of tenant T" with no side array.  label_col names a column of the
+ * space (above); d_want[i] is the label query i is confined to.  Each call takes ONE acquire-load snapshot n_pub of the row
+ * count and answers, byte for byte, what ehx_knn_labeled_device returns when given the stored column of that prefix with
+ * n_labels = n_pub: ids, distance bytes, counts, sentinels, every error code of that call in its order, every space kind it
+ * serves (a graph space answers from its stored rows).  0xFFFFFFFF is an ordinary label here — the rows never labelled.
+ * label_col at or above EHX_MAX_COLUMNS: EHX_EINVAL.
+ * The column's INDEX — row ids ordered by (label, row id), the table of distinct labels, where each begins, and for the
+ * labels above the scan route's cut their rows before every 256-row tile and a by-rank sample — is built on the device once,
+ * by a radix sort, and reused until the column or the row count changes: any write to an entry below the published row
+ * count, and any append, leaves it stale.  With a fresh index a call makes no pass over the column, compacts nothing and takes
+ * none of ehx_knn_labeled_device's two waits per device batch; the host form uploads queries and wanted labels only.  A stale
+ * index costs one rebuild, on the call's stream, by the first search that finds it stale: one copy of the prefix, a histogram
+ * pass, one sort pass per label byte that varies (one for fewer than 256 small tenant numbers), the boundary passes and four
+ * short waits.  Measured once (scripts/bench_stored_labels.py): the rebuild takes 0.20 ms at 1 M rows and
+ * 0.58 ms at 10 M rows for a column of 16 tenants, 0.79 and 6.8 ms for a column of random 32-bit labels.  A caller that appends
+ * between every two searches pays the rebuild on every search.  Memory: an indexed column keeps 36 bytes per row of the
+ * space's CAPACITY on the device beside the column's own 4 (the index's arrays are sized once, so a rebuild allocates
+ * nothing), and 8 bytes per distinct label on the host. */
+int ehx_knn_by_label_device(ehx_space* s, void* stream, size_t n_queries, const float* d_queries, uint32_t k, uint32_t label_col,
+                            const uint32_t* d_want, uint64_t* d_out_ids, float* d_out_dist, uint32_t* d_out_count);
+/* ... from host pointers: the H2D / D2H copies of queries, wanted labels and results around it. */
+int ehx_knn_by_label(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, uint32_t label_col, const uint32_t* want,
+                     uint64_t* out_ids, float* out_dist, uint32_t* out_count);
+/* Partitioned grouped kNN on STORED columns: group_col holds the entity of every row (EHX_GROUP_NONE: a group of its own —
+ * also every row never given a value), label_col the tenant.  ONE snapshot n_pub of the row count; byte for byte what
+ * ehx_knn_grouped_labeled_device returns when given the two stored columns of that prefix with n_labels = n_pub, with that
+ * call's error codes in its order; a column number at or above EHX_MAX_COLUMNS: EHX_EINVAL.  group_col may equal label_col.
+ * The index is label_col's, as above; group_col is read where it lies. */
+int ehx_knn_grouped_by_label_device(ehx_space* s, void* stream, size_t n_queries, const float* d_queries, uint32_t k,
+                                    uint32_t per_group, uint32_t group_col, uint32_t label_col, const uint32_t* d_want,
+                                    uint64_t* d_out_ids, float* d_out_dist, uint32_t* d_out_count);
+int ehx_knn_grouped_by_label(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, uint32_t per_group,
+                             uint32_t group_col, uint32_t label_col, const uint32_t* want, uint64_t* out_ids, float* out_dist,
+                             uint32_t* out_count);
 /* Exact range search: every row closer than a radius.  With D(q, x) the canonical distance ehx_knn reports (cosine, L2^2,
  * inner product as there), row x belongs to query i's answer iff D is not NaN and D <= d_radius[i] as a float comparison
  * (inclusive: a radius that equals a row's distance byte for byte includes that row; -Inf distances under inner product
