@@ -21,6 +21,7 @@ WALK_AUTO, WALK_GRAPH, WALK_EXACT = 0, 1, 2   # route of graph_knn_masked
 WALK_LIST_FACTOR, WALK_LIST_MAX = 12, 4096     # EHX_WALK_LIST_FACTOR / _MAX: the walk list holds max(ef, min(12 ef, 4096))
 GROUP_NONE, MAX_K_GROUPED = 0xFFFFFFFF, 256     # EHX_GROUP_NONE (a row that is a group of its own), EHX_MAX_K_GROUPED
 MAX_COLUMNS = 4                                 # EHX_MAX_COLUMNS: stored label columns of a space
+PRED_MAX_TERMS, TERM_NOT = 8, 1                 # EHX_PRED_MAX_TERMS, EHX_TERM_NOT: predicates over stored columns
 SEED_CORPUS, SEED_QUERY = 20250211, 20250212
 
 
@@ -48,10 +49,19 @@ class Stats(C.Structure):
                 ("n_exhaustive", C.c_uint64), ("n_i8_queries", C.c_uint64), ("n_i8_fallback", C.c_uint64)]
 
 
+class Term(C.Structure):   # ehx_term: holds iff lo <= value <= hi, unsigned; TERM_NOT in flags inverts
+    _fields_ = [("col", C.c_uint32), ("lo", C.c_uint32), ("hi", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class Pred(C.Structure):   # ehx_pred: a conjunction of n_terms terms
+    _fields_ = [("n_terms", C.c_uint32), ("terms", Term * PRED_MAX_TERMS)]
+
+
 # every symbol include/ehx.h declares: name -> (restype, argtypes)
 _f32p, _u64p, _u32p, _i32p = (C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
                               C.POINTER(C.c_int32))
 _vp = C.c_void_p
+_predp = C.POINTER(Pred)
 SYMBOLS = {
     "ehx_init": (C.c_int, [C.POINTER(C.c_int), C.c_int]),
     "ehx_shutdown": (C.c_int, []),
@@ -142,6 +152,16 @@ SYMBOLS = {
                                    _u32p, _u64p]),
     "ehx_range_masked_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp, C.c_uint32, _vp, C.c_uint32, C.c_uint64, _vp, _vp, _vp,
                                           _vp, _vp]),
+    "ehx_knn_where": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_uint32, _predp, C.c_uint32, _u32p, _u64p, _f32p, _u32p]),
+    "ehx_knn_where_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint32, _predp, C.c_uint32, _vp, _vp, _vp, _vp]),
+    "ehx_knn_grouped_where": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_uint32, C.c_uint32, C.c_uint32, _predp, C.c_uint32, _u32p,
+                                        _u64p, _f32p, _u32p]),
+    "ehx_knn_grouped_where_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _predp, C.c_uint32,
+                                               _vp, _vp, _vp, _vp]),
+    "ehx_range_where": (C.c_int, [_vp, C.c_size_t, _f32p, _f32p, C.c_uint32, _predp, C.c_uint32, _u32p, _u64p, _f32p, _u32p,
+                                  _u64p]),
+    "ehx_range_where_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp, C.c_uint32, _predp, C.c_uint32, _vp, _vp, _vp, _vp,
+                                         _vp]),
     "ehx_knn_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint32, _vp, _vp, _vp]),
     "ehx_merge_topk_device": (C.c_int, [_vp, C.c_size_t, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ehx_merge_topk_strided_device": (C.c_int, [_vp, C.c_size_t, C.c_uint32, C.c_uint32, _vp, C.c_size_t, _vp,

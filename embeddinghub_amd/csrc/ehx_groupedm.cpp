@@ -27,26 +27,6 @@ namespace {
 
 constexpr const char* kGroupedMaskedWhy = "filtered grouped search over shards is not built yet";
 
-int groupedm_check(const ehx_space* s, size_t nq, uint32_t k, uint32_t per_group, const void* q, const void* group_of,
-                   uint64_t n_labels, const void* masks, uint32_t n_masks, uint64_t n_bits, const void* mask_of,
-                   const void* o_ids, const void* o_dist, const void* o_cnt) {
-  if (!s) return fail(EHX_EINVAL, "space is NULL");   // (before the device is looked for)
-  int rc = ehx_init(nullptr, 0);   // (no device: EHX_ENODEVICE, whatever else is wrong with the call)
-  if (rc) return rc;
-  if (k == 0) return fail(EHX_EINVAL, "k is 0");
-  if (per_group == 0) return fail(EHX_EINVAL, "per_group is 0");
-  if (k > EHX_MAX_K_GROUPED) return fail(EHX_EUNSUPPORTED, "k=%u exceeds %u", k, EHX_MAX_K_GROUPED);
-  if (!(o_ids && o_dist && o_cnt && (!nq || q))) return fail(EHX_EINVAL, "NULL argument");
-  if (n_labels && !group_of) return fail(EHX_EINVAL, "NULL group_of with n_labels = %llu", (unsigned long long)n_labels);
-  if (n_bits && !masks) return fail(EHX_EINVAL, "NULL mask with n_bits = %llu", (unsigned long long)n_bits);
-  if ((rc = check_batch_size(nq))) return rc;
-  if (nq == 0) return EHX_OK;
-  if (n_masks == 0) return fail(EHX_EINVAL, "n_masks is 0 with %zu queries", nq);
-  if (n_masks > kMaskedMaxMasks) return fail(EHX_EUNSUPPORTED, "n_masks=%u exceeds %u", n_masks, kMaskedMaxMasks);
-  if (n_masks > 1 && !mask_of) return fail(EHX_EINVAL, "NULL mask_of");
-  return EHX_OK;
-}
-
 // The list route for nq queries, query i under mask gm[i] (host memory) of the plan: any space kind.  count_queries: its
 // queries are not in n_queries yet.
 int groupedm_list(ehx_space* s, hipStream_t st, const MaskedPlan& p, const uint32_t* gm, size_t nq, const float* d_queries,
@@ -109,6 +89,30 @@ int groupedm_list(ehx_space* s, hipStream_t st, const MaskedPlan& p, const uint3
   }
   if (count_queries) s->n_queries += nq;
   s->n_dist += n_listed;
+  return EHX_OK;
+}
+
+}  // namespace
+
+namespace ehx_impl {
+
+int groupedm_check(const ehx_space* s, size_t nq, uint32_t k, uint32_t per_group, const void* q, const void* group_of,
+                   uint64_t n_labels, const void* masks, uint32_t n_masks, uint64_t n_bits, const void* mask_of,
+                   const void* o_ids, const void* o_dist, const void* o_cnt) {
+  if (!s) return fail(EHX_EINVAL, "space is NULL");   // (before the device is looked for)
+  int rc = ehx_init(nullptr, 0);   // (no device: EHX_ENODEVICE, whatever else is wrong with the call)
+  if (rc) return rc;
+  if (k == 0) return fail(EHX_EINVAL, "k is 0");
+  if (per_group == 0) return fail(EHX_EINVAL, "per_group is 0");
+  if (k > EHX_MAX_K_GROUPED) return fail(EHX_EUNSUPPORTED, "k=%u exceeds %u", k, EHX_MAX_K_GROUPED);
+  if (!(o_ids && o_dist && o_cnt && (!nq || q))) return fail(EHX_EINVAL, "NULL argument");
+  if (n_labels && !group_of) return fail(EHX_EINVAL, "NULL group_of with n_labels = %llu", (unsigned long long)n_labels);
+  if (n_bits && !masks) return fail(EHX_EINVAL, "NULL mask with n_bits = %llu", (unsigned long long)n_bits);
+  if ((rc = check_batch_size(nq))) return rc;
+  if (nq == 0) return EHX_OK;
+  if (n_masks == 0) return fail(EHX_EINVAL, "n_masks is 0 with %zu queries", nq);
+  if (n_masks > kMaskedMaxMasks) return fail(EHX_EUNSUPPORTED, "n_masks=%u exceeds %u", n_masks, kMaskedMaxMasks);
+  if (n_masks > 1 && !mask_of) return fail(EHX_EINVAL, "NULL mask_of");
   return EHX_OK;
 }
 
@@ -224,7 +228,7 @@ int groupedm_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_quer
   return w.group.rerun(s, st, d_queries, idx, k, answer, out.ids, out.dist, out.cnt);
 }
 
-}  // namespace
+}  // namespace ehx_impl
 
 extern "C" {
 

@@ -513,6 +513,9 @@ struct ehx_space {
     // `group` and scan.sub)
     DevBuf<uint32_t> dWalkOf;
     SubsetBufs split;
+    // the predicate searches (ehx_where.cpp): [kMaskedMaxMasks] the call's predicates, where the kernel that builds the
+    // bitmaps into dBlock reads them; sized once
+    DevBuf<WherePred> dPreds;
   } masked;
   // test hook: queries answered on the scan route, on the exact route, queries that overflowed, scan passes launched, calls
   // (ehx_knn_masked* and ehx_knn_masked_multi* both count here)
@@ -1029,12 +1032,19 @@ constexpr size_t kTabWords = kSideChunk;    // word offsets in front of the bitm
 // At most this many allowed rows: the exact route of the bitmap searches
 uint64_t masked_exact_cut(uint64_t n_pub);
 int check_mask_of(const uint32_t* mask_of, size_t nq, uint32_t n_masks);   // an entry at or above n_masks: EHX_EINVAL
-// Where a call's bitmaps come from: n_masks >= 1 bitmaps of `stride` words each, in host or device memory.
+// Where a call's bitmaps come from: n_masks >= 1 bitmaps of `stride` words each, in host or device memory — or, with `build`
+// set (p and stride unused), made on the device by build(n_eff, words, dst, st): it enqueues on `st` what writes bitmap m's
+// words of the plan's n_eff rows at dst + m * words, dense.  masked_maps calls it where it would copy the table — after
+// masked.dBlock is ensured and `st` is ordered behind the searches in flight — so a builder sees exactly the plan's snapshot
+// (the predicate searches: ehx_where.cpp).
 struct MaskTable {
   const uint32_t* p;
   uint64_t stride;
   uint32_t n_masks;
   bool host;
+  // (last, with a default: MaskTable stays an aggregate under C++14's rules, so the brace-inits {p, stride, n_masks, host} of
+  // the bitmap forms leave it empty)
+  std::function<int(uint64_t, uint64_t, uint32_t*, hipStream_t)> build = nullptr;
 };
 // The bitmaps of one call, compacted: the call's ONE read of the row count, the rows the bitmaps cover below it, per mask the
 // allowed rows before every tile (read back), their number and where its ascending list of allowed ids starts in
@@ -1055,6 +1065,28 @@ struct MaskedPlan {
 // compaction — and checked then, the outputs unwritten; or neither: every query is mask 0 and nothing is read back for it.
 int masked_plan(ehx_space* s, hipStream_t st, const MaskTable& tab, uint64_t n_bits, size_t nq, const uint32_t* mask_of,
                 const uint32_t* d_mask_of, MaskedPlan* p);
+// The argument checks and the locked bodies of the three exact searches that take a table of bitmaps, as their entry points
+// run them (an unsharded space, locked shared, scratch_mu held, its device current; everything is enqueued on `st`; mask_of /
+// d_mask_of: masked_plan's) — the predicate searches (ehx_where.cpp) enter them with a table that is built, not copied.
+// ehx_knn_masked_multi* (ehx_masked.cpp):
+int masked_table_check(const ehx_space* s, size_t nq, uint32_t k, const void* q, const void* masks, uint32_t n_masks,
+                       uint64_t n_bits, const void* mask_of, const void* o_ids, const void* o_dist, const void* o_cnt);
+int masked_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, const MaskTable& tab,
+                  uint64_t n_bits, const uint32_t* mask_of, const uint32_t* d_mask_of, const ResultBlock& out);
+// ehx_knn_grouped_masked* (ehx_groupedm.cpp):
+int groupedm_check(const ehx_space* s, size_t nq, uint32_t k, uint32_t per_group, const void* q, const void* group_of,
+                   uint64_t n_labels, const void* masks, uint32_t n_masks, uint64_t n_bits, const void* mask_of,
+                   const void* o_ids, const void* o_dist, const void* o_cnt);
+int groupedm_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, uint32_t per_group,
+                    const uint32_t* group_of, bool labels_on_host, uint64_t n_labels, const MaskTable& tab, uint64_t n_bits,
+                    const uint32_t* mask_of, const uint32_t* d_mask_of, const ResultBlock& out);
+// ehx_range_masked* (ehx_rangem.cpp):
+int rangem_check(const ehx_space* s, size_t nq, uint32_t max_results, const void* q, const void* radius, const void* masks,
+                 uint32_t n_masks, uint64_t n_bits, const void* mask_of, const void* o_ids, const void* o_dist,
+                 const void* o_cnt);
+int rangem_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, const float* d_radius, uint32_t max_results,
+                  const MaskTable& tab, uint64_t n_bits, const uint32_t* mask_of, const uint32_t* d_mask_of,
+                  const ResultBlock& out);
 // What the exact answer needs of compacted per-query row filters, whatever they were compacted from: a table of bitmaps
 // (masked_answer, ehx_masked.cpp) or the wanted labels of a label column (ehx_labeled.cpp).  Host arrays unless named d_.
 struct FilterView {

@@ -607,6 +607,27 @@ hipError_t launch_colindex_heavy(const uint64_t* perm, const uint64_t* run, uint
 hipError_t launch_column_scatter(uint32_t* col, uint64_t cap, const uint64_t* dst_row, const uint32_t* values, size_t n,
                                  hipStream_t st);
 hipError_t launch_column_gather(const uint32_t* col, uint64_t cap, const uint64_t* rows, uint32_t* out, size_t n, hipStream_t st);
+// predicate filters on stored columns (k_where.hip; ehx_where.cpp): the bitmaps of n_preds <= kMaskedMaxMasks predicates over
+// the rows [0, n_rows), n_rows < 2^32, bitmap p at dst + p * words, words = ceil(n_rows / 32) — launch_masked_count's dense
+// layout; bits at or above n_rows in the last word are 0, no word at or above `words` is written.  cols.p[c]: column c's values,
+// read iff bit c of cols.named is set (a column some predicate names AND that is live); every other column is the constant
+// 0xFFFFFFFF.  preds: n_preds predicates in DEVICE memory, laid out as include/ehx.h's ehx_pred (ehx_where.cpp asserts it): a
+// term holds iff lo <= value <= hi, unsigned, inverted by flag bit 0.
+constexpr uint32_t kWhereMaxCols = 4, kWhereMaxTerms = 8;   // EHX_MAX_COLUMNS, EHX_PRED_MAX_TERMS
+struct WhereTerm {
+  uint32_t col, lo, hi, flags;
+};
+struct WherePred {
+  uint32_t n_terms;
+  WhereTerm terms[kWhereMaxTerms];
+};
+struct WhereCols {
+  const uint32_t* p[kWhereMaxCols];
+  uint32_t named;
+};
+constexpr uint32_t kWhereSpan = 1024;   // rows of one workgroup: four 256-row tiles, 32 words of every bitmap
+hipError_t launch_where_bitmaps(const WhereCols& cols, const WherePred* preds, uint32_t n_preds, uint64_t n_rows, uint64_t words,
+                                uint32_t* dst, hipStream_t st);
 // radius[q] = dist[q][k - 1] when cnt[q] >= k (result lists [nq][k]), else +Inf
 hipError_t launch_masked_radius(const float* dist, const uint32_t* cnt, uint32_t nq, uint32_t k, float* radius, hipStream_t st);
 // word w of a bitmap cut at n_bits (bits of the last word beyond n_bits and words beyond it read as 0)

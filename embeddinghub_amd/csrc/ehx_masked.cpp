@@ -49,17 +49,6 @@ int masked_check(const ehx_space* s, size_t nq, uint32_t k, const void* q, const
   return EHX_OK;
 }
 
-int masked_table_check(const ehx_space* s, size_t nq, uint32_t k, const void* q, const void* masks, uint32_t n_masks,
-                       uint64_t n_bits, const void* mask_of, const void* o_ids, const void* o_dist, const void* o_cnt) {
-  if (!s) return fail(EHX_EINVAL, "space is NULL");
-  if (int rc = masked_check(s, nq, k, q, masks, n_bits, o_ids, o_dist, o_cnt)) return rc;
-  if (nq == 0) return EHX_OK;
-  if (n_masks == 0) return fail(EHX_EINVAL, "n_masks is 0 with %zu queries", nq);
-  if (n_masks > kMaskedMaxMasks) return fail(EHX_EUNSUPPORTED, "n_masks=%u exceeds %u", n_masks, kMaskedMaxMasks);
-  if (!mask_of) return fail(EHX_EINVAL, "NULL mask_of");
-  return EHX_OK;
-}
-
 // tile ranges of the scan passes: pass j (j = 1, 2, ...; the sample is stage 0) ends at the first tile where the allowed
 // rows seen reach kMaskedSample * 16^j, the last pass takes the rest.  cum[t] = allowed rows in tiles [0, t), non-decreasing.
 std::vector<TileRange> masked_passes(const std::vector<uint32_t>& cum, uint32_t n_tiles) {
@@ -77,11 +66,12 @@ std::vector<TileRange> masked_passes(const std::vector<uint32_t>& cum, uint32_t 
 }
 
 // The bitmaps of a call on the device, bitmap m at *d_maps + m * words (words: those of the n_eff rows below the row count):
-// ONE device bitmap where it lies; host words and every table dense in masked.dBlock behind the offset words.  (Host words
-// are pageable memory: the runtime stages them before the call returns.)
+// ONE device bitmap where it lies; host words and every table dense in masked.dBlock behind the offset words — copied there,
+// or written there by the table's builder (MaskTable::build).  (Host words are pageable memory: the runtime stages them
+// before the call returns.)
 int masked_maps(ehx_space* s, hipStream_t st, const MaskTable& tab, uint64_t n_eff, const uint32_t** d_maps) {
   int rc;
-  const bool in_place = tab.n_masks == 1 && !tab.host;
+  const bool in_place = tab.n_masks == 1 && !tab.host && !tab.build;
   const uint64_t words = (n_eff + 31) / 32;
   if (kTabWords + (uint64_t)tab.n_masks * words > 0xFFFFFFFFull)
     return fail(EHX_EUNSUPPORTED, "%u bitmaps of %llu rows exceed the 2^32 words of one table", tab.n_masks,
@@ -91,6 +81,7 @@ int masked_maps(ehx_space* s, hipStream_t st, const MaskTable& tab, uint64_t n_e
   // (earlier calls' launches on other streams may still read the block, the lists and the samples)
   if ((rc = wait_searches_in_flight(s, st))) return rc;
   *d_maps = in_place ? tab.p : w.dBlock.p + kTabWords;
+  if (tab.build) return words ? tab.build(n_eff, words, w.dBlock.p + kTabWords, st) : (int)EHX_OK;
   for (uint32_t m = 0; !in_place && words && m < tab.n_masks; ++m)
     HIP_TRY(hipMemcpyAsync(w.dBlock.p + kTabWords + (size_t)m * words, tab.p + (size_t)m * tab.stride, words * sizeof(uint32_t),
                            tab.host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
@@ -100,6 +91,17 @@ int masked_maps(ehx_space* s, hipStream_t st, const MaskTable& tab, uint64_t n_e
 }  // namespace
 
 namespace ehx_impl {
+
+int masked_table_check(const ehx_space* s, size_t nq, uint32_t k, const void* q, const void* masks, uint32_t n_masks,
+                       uint64_t n_bits, const void* mask_of, const void* o_ids, const void* o_dist, const void* o_cnt) {
+  if (!s) return fail(EHX_EINVAL, "space is NULL");
+  if (int rc = masked_check(s, nq, k, q, masks, n_bits, o_ids, o_dist, o_cnt)) return rc;
+  if (nq == 0) return EHX_OK;
+  if (n_masks == 0) return fail(EHX_EINVAL, "n_masks is 0 with %zu queries", nq);
+  if (n_masks > kMaskedMaxMasks) return fail(EHX_EUNSUPPORTED, "n_masks=%u exceeds %u", n_masks, kMaskedMaxMasks);
+  if (!mask_of) return fail(EHX_EINVAL, "NULL mask_of");
+  return EHX_OK;
+}
 
 // At most this many allowed rows: the exact route.  max(1024, rows / 128), MEASURED (scripts/bench_masked.py, 1 M x 768
 // cosine, batch 1024, k = 10: the list scan costs what the scan route costs at 7 697 allowed rows, 0.77 % of the space;
@@ -355,6 +357,10 @@ int masked_answer(ehx_space* s, hipStream_t st, size_t nq, const float* d_querie
   return filtered_answer(s, st, nq, d_queries, k, v, out);
 }
 
+}  // namespace
+
+namespace ehx_impl {
+
 // an unsharded space, locked shared, scratch_mu held, its device current; everything is enqueued on `st` (mask_of /
 // d_mask_of: masked_plan's)
 int masked_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, const MaskTable& tab,
@@ -367,6 +373,10 @@ int masked_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_querie
   if ((rc = masked_plan(s, st, tab, n_bits, nq, mask_of, d_mask_of, &p))) return rc;
   return masked_answer(s, st, nq, d_queries, k, p, out);
 }
+
+}  // namespace ehx_impl
+
+namespace {
 
 // host pointers in, host pointers out, on the space's stream (on_device)
 int masked_host_locked(ehx_space* s, size_t nq, const float* queries, uint32_t k, const uint32_t* masks, uint32_t n_masks,

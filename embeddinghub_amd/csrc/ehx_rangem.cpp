@@ -27,21 +27,6 @@ namespace {
 
 constexpr const char* kRangeMaskedWhy = "filtered range search over shards is not built yet";
 
-int rangem_check(const ehx_space* s, size_t nq, uint32_t max_results, const void* q, const void* radius, const void* masks,
-                 uint32_t n_masks, uint64_t n_bits, const void* mask_of, const void* o_ids, const void* o_dist,
-                 const void* o_cnt) {
-  int rc = ehx_init(nullptr, 0);   // (no device: EHX_ENODEVICE, whatever else is wrong with the call)
-  if (rc) return rc;
-  if ((rc = check_batch_call(s, nq, max_results, "max_results", false, o_ids && o_dist && o_cnt && (!nq || (q && radius)))))
-    return rc;
-  if (n_bits && !masks) return fail(EHX_EINVAL, "NULL mask with n_bits = %llu", (unsigned long long)n_bits);
-  if (nq == 0) return EHX_OK;
-  if (n_masks == 0) return fail(EHX_EINVAL, "n_masks is 0 with %zu queries", nq);
-  if (n_masks > kMaskedMaxMasks) return fail(EHX_EUNSUPPORTED, "n_masks=%u exceeds %u", n_masks, kMaskedMaxMasks);
-  if (n_masks > 1 && !mask_of) return fail(EHX_EINVAL, "NULL mask_of");
-  return EHX_OK;
-}
-
 // The list route for the queries sel[0, n) (ascending) of a device batch of m: slot j walks the list of its query's mask.
 // counted[j] != 0: query sel[j]'s overflow is in the counters already.
 int rangem_list_stage(ehx_space* s, hipStream_t st, const MaskedPlan& p, size_t q0, size_t m, const float* d_queries,
@@ -135,6 +120,25 @@ int rangem_list_stage(ehx_space* s, hipStream_t st, const MaskedPlan& p, size_t 
   return EHX_OK;
 }
 
+}  // namespace
+
+namespace ehx_impl {
+
+int rangem_check(const ehx_space* s, size_t nq, uint32_t max_results, const void* q, const void* radius, const void* masks,
+                 uint32_t n_masks, uint64_t n_bits, const void* mask_of, const void* o_ids, const void* o_dist,
+                 const void* o_cnt) {
+  int rc = ehx_init(nullptr, 0);   // (no device: EHX_ENODEVICE, whatever else is wrong with the call)
+  if (rc) return rc;
+  if ((rc = check_batch_call(s, nq, max_results, "max_results", false, o_ids && o_dist && o_cnt && (!nq || (q && radius)))))
+    return rc;
+  if (n_bits && !masks) return fail(EHX_EINVAL, "NULL mask with n_bits = %llu", (unsigned long long)n_bits);
+  if (nq == 0) return EHX_OK;
+  if (n_masks == 0) return fail(EHX_EINVAL, "n_masks is 0 with %zu queries", nq);
+  if (n_masks > kMaskedMaxMasks) return fail(EHX_EUNSUPPORTED, "n_masks=%u exceeds %u", n_masks, kMaskedMaxMasks);
+  if (n_masks > 1 && !mask_of) return fail(EHX_EINVAL, "NULL mask_of");
+  return EHX_OK;
+}
+
 // an unsharded space, locked shared, scratch_mu held, its device current; everything is enqueued on `st` (mask_of /
 // d_mask_of: masked_plan's)
 int rangem_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, const float* d_radius, uint32_t max_results,
@@ -207,7 +211,7 @@ int rangem_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_querie
   return EHX_OK;
 }
 
-}  // namespace
+}  // namespace ehx_impl
 
 extern "C" {
 

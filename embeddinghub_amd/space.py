@@ -713,6 +713,88 @@ class Space:
                                                       int(group_col), int(label_col), _ptr(d_want), _ptr(d_ids), _ptr(d_dist),
                                                       _ptr(d_count)))
 
+    # ---- predicate filters on stored columns: the bitmap searches' answers, the bitmaps built on the device ----
+    def _where_args(self, preds, pred_of, nq):
+        table, n_preds = marshal_preds(preds)
+        if pred_of is None:
+            if n_preds != 1:
+                raise ValueError("a table of %d predicates needs pred_of" % n_preds)
+            of = np.zeros(nq, dtype=np.uint32)
+        else:
+            of = np.ascontiguousarray(np.asarray(pred_of).reshape(-1), dtype=np.uint32)
+            if of.shape[0] != nq:
+                raise ValueError("expected %d pred_of entries, got %d" % (nq, of.shape[0]))
+        return table, n_preds, of
+
+    @staticmethod
+    def _where_device_args(d_queries, preds, d_pred_of):
+        nq = d_queries.shape[0] if hasattr(d_queries, "shape") else None
+        if nq is None:
+            raise ValueError("pass torch tensors (queries [nq, dims], pred_of)")
+        table, n_preds = marshal_preds(preds)
+        if hasattr(d_pred_of, "numel") and d_pred_of.numel() < nq:
+            raise ValueError("%d pred_of entries for %d queries" % (d_pred_of.numel(), nq))
+        return nq, table, n_preds
+
+    def knn_where(self, queries, k, preds, pred_of=None):
+        """knn_masked_multi under the bitmaps the predicates describe (ehx_knn_where): query i sees row r iff every term of
+        preds[pred_of[i]] holds for r's stored column values.  preds: a list of predicates (marshal_preds), at most 64, each a
+        list of (col, lo, hi) or (col, lo, hi, True) for NOT — lo <= value <= hi, unsigned; pred_of: [nq] indices, or None with
+        one predicate (every query under it).  -> ids [nq,k] u64, dist [nq,k] f32, count [nq] u32."""
+        q, pq = _f32(queries)
+        q = q.reshape(-1, self.dims)
+        nq = q.shape[0]
+        table, n_preds, of = self._where_args(preds, pred_of, nq)
+        (ids, dist, cnt), out = _results(nq, k)
+        check(self._L.ehx_knn_where(self._h, nq, pq, k, table, n_preds, of.ctypes.data_as(C.POINTER(C.c_uint32)), *out))
+        return ids[:, :k], dist[:, :k], cnt
+
+    def knn_where_device(self, d_queries, k, preds, d_pred_of, d_ids, d_dist, d_count, stream=None):
+        """knn_where with queries, pred_of ([nq] u32, int32 storage) and results on the device (torch CUDA tensors, as
+        knn_masked_multi_device's); the predicates stay a host list."""
+        nq, table, n_preds = self._where_device_args(d_queries, preds, d_pred_of)
+        check(self._L.ehx_knn_where_device(self._h, C.c_void_p(stream or 0), nq, _ptr(d_queries), k, table, n_preds,
+                                           _ptr(d_pred_of), _ptr(d_ids), _ptr(d_dist), _ptr(d_count)))
+
+    def knn_grouped_where(self, queries, k, group_col, preds, pred_of=None, per_group=1):
+        """knn_grouped_masked under the predicates' bitmaps, the groups read from the stored column group_col
+        (ehx_knn_grouped_where).  -> ids [nq,k] u64, dist [nq,k] f32, count [nq] u32."""
+        q, pq = _f32(queries)
+        q = q.reshape(-1, self.dims)
+        nq = q.shape[0]
+        table, n_preds, of = self._where_args(preds, pred_of, nq)
+        (ids, dist, cnt), out = _results(nq, k)
+        check(self._L.ehx_knn_grouped_where(self._h, nq, pq, k, int(per_group), int(group_col), table, n_preds,
+                                            of.ctypes.data_as(C.POINTER(C.c_uint32)), *out))
+        return ids[:, :k], dist[:, :k], cnt
+
+    def knn_grouped_where_device(self, d_queries, k, group_col, preds, d_pred_of, d_ids, d_dist, d_count, per_group=1, stream=None):
+        """knn_grouped_where without queries or results leaving the device: tensors as knn_where_device's."""
+        nq, table, n_preds = self._where_device_args(d_queries, preds, d_pred_of)
+        check(self._L.ehx_knn_grouped_where_device(self._h, C.c_void_p(stream or 0), nq, _ptr(d_queries), k, int(per_group),
+                                                   int(group_col), table, n_preds, _ptr(d_pred_of), _ptr(d_ids), _ptr(d_dist),
+                                                   _ptr(d_count)))
+
+    def range_where(self, queries, radius, max_results, preds, pred_of=None):
+        """range_masked under the predicates' bitmaps (ehx_range_where).
+        -> ids [nq, max_results] u64, dist [nq, max_results] f32, count [nq] u32, total [nq] u64."""
+        nq, pq, r, (ids, dist, cnt, total), out, keep = self._range_args(queries, radius, max_results)
+        table, n_preds, of = self._where_args(preds, pred_of, nq)
+        check(self._L.ehx_range_where(self._h, nq, pq, r.ctypes.data_as(C.POINTER(C.c_float)), max_results, table, n_preds,
+                                      of.ctypes.data_as(C.POINTER(C.c_uint32)), *out))
+        del keep
+        return ids[:, :max_results], dist[:, :max_results], cnt, total
+
+    def range_where_device(self, d_queries, d_radius, max_results, preds, d_pred_of, d_ids, d_dist, d_count, d_total=None,
+                           stream=None):
+        """range_where without queries, radii or results leaving the device: tensors as range_masked_device's."""
+        nq, table, n_preds = self._where_device_args(d_queries, preds, d_pred_of)
+        if hasattr(d_radius, "shape") and tuple(d_radius.shape) != (nq,):
+            raise ValueError("expected %d radii, got shape %s" % (nq, tuple(d_radius.shape)))
+        check(self._L.ehx_range_where_device(self._h, C.c_void_p(stream or 0), nq, _ptr(d_queries), _ptr(d_radius), max_results,
+                                             table, n_preds, _ptr(d_pred_of), _ptr(d_ids), _ptr(d_dist), _ptr(d_count),
+                                             _ptr(d_total)))
+
     # ---- kNN under a row bitmap on the graph path ----
     def graph_knn_masked(self, queries, k, allow, n_bits=None, route=_lib.WALK_AUTO):
         """The k nearest ALLOWED rows the graph walk finds (ehx_graph_knn_masked): approximate when walked, possibly fewer
@@ -943,6 +1025,33 @@ def marshal_columns(columns, n):
         cols.append(int(c))
         vals.append(np.ascontiguousarray(a, dtype=np.uint32))
     return np.asarray(cols, dtype=np.uint32).reshape(-1), vals
+
+
+def marshal_preds(preds):
+    """The predicates of the *_where searches -> (a ctypes array of ehx_pred, n_preds).  preds: a list of predicates, each a
+    list of terms (col, lo, hi) or (col, lo, hi, negate): the term holds iff lo <= value <= hi as unsigned 32-bit numbers,
+    inverted when negate is true; a predicate is the conjunction of its terms, and one without terms allows every row.
+    ValueError where the C side would say EHX_EINVAL: no predicate, more than PRED_MAX_TERMS terms, a column at or above
+    MAX_COLUMNS, a bound outside 32 bits.  (More than 64 predicates are the C side's EHX_EUNSUPPORTED.)"""
+    preds = list(preds)
+    if not preds:
+        raise ValueError("no predicate")
+    table = (_lib.Pred * len(preds))()
+    for p, terms in enumerate(preds):
+        terms = list(terms)
+        if len(terms) > _lib.PRED_MAX_TERMS:
+            raise ValueError("predicate %d has %d terms: at most %d" % (p, len(terms), _lib.PRED_MAX_TERMS))
+        table[p].n_terms = len(terms)
+        for t, term in enumerate(terms):
+            if len(term) not in (3, 4):
+                raise ValueError("predicate %d, term %d: expected (col, lo, hi) or (col, lo, hi, negate)" % (p, t))
+            col, lo, hi = (int(x) for x in term[:3])
+            if not 0 <= col < _lib.MAX_COLUMNS:
+                raise ValueError("predicate %d, term %d: column %d: a space has %d columns" % (p, t, col, _lib.MAX_COLUMNS))
+            if not (0 <= lo <= 0xFFFFFFFF and 0 <= hi <= 0xFFFFFFFF):
+                raise ValueError("predicate %d, term %d: bounds must fit 32 bits (unsigned)" % (p, t))
+            table[p].terms[t] = _lib.Term(col, lo, hi, _lib.TERM_NOT if len(term) == 4 and term[3] else 0)
+    return table, len(preds)
 
 
 def marshal_groups(group_of):

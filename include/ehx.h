@@ -741,6 +741,63 @@ int ehx_range_masked_device(ehx_space* s, void* stream, size_t n_queries, const 
                             uint32_t max_results, const uint32_t* d_masks, uint32_t n_masks, uint64_t n_bits,
                             const uint32_t* d_mask_of, uint64_t* d_out_ids, float* d_out_dist, uint32_t* d_out_count,
                             uint64_t* d_out_total);
+/* ---- predicate filters on stored columns: the bitmaps of the three exact searches above, built on the device ----
+ * "tenant 7 AND timestamp >= T AND category != 3" without resolving it on the host and uploading n_masks * rows / 8 bytes per
+ * call: a predicate is a CONJUNCTION of at most EHX_PRED_MAX_TERMS terms over the stored columns (above); a call carries up to
+ * 64 predicates and searches query i under predicate pred_of[i].  A term holds for a row iff lo <= value <= hi, compared
+ * UNSIGNED, where value is what column `col` stores for the row; EHX_TERM_NOT in flags inverts the term.
+ * Row r is allowed by predicate P iff r is below the call's ONE acquire-load snapshot n_pub of the row count and every term of
+ * P holds for the value stored in terms[t].col at row r.  A column never written reads as EHX_GROUP_NONE (0xFFFFFFFF) for
+ * every row, a row never given a value reads as EHX_GROUP_NONE, as everywhere else.  lo == hi is equality; lo > hi is an
+ * empty range: it never holds, and always holds under EHX_TERM_NOT; a column may be named by several terms; n_terms == 0
+ * allows every row.  The comparison is unsigned: store signed or float attributes under an order-preserving map (a signed
+ * integer with its sign bit flipped; a float's bits with the sign bit flipped when positive and all bits flipped when
+ * negative).  Disjunctions and IN-lists are out of scope: split them into several predicates — several calls where one query
+ * needs more than one — and merge the answers with ehx_merge_topk_device.
+ * The answers are defined by the bitmap forms: byte for byte what ehx_knn_masked_multi_device, ehx_knn_grouped_masked_device
+ * and ehx_range_masked_device return under the bitmaps the predicates describe with n_bits = n_pub — ids, distance bytes,
+ * counts, totals, sentinels, routes, cuts and waits.  The bitmaps are evaluated by ONE kernel over the columns of the prefix
+ * where they lie (no index, no copy: k_where.hip) into the table those searches compact; every column some
+ * predicate names is read once, 4 bytes per row, and n_preds / 8 bytes per row are written.
+ * preds is a HOST array of n_preds predicates in every form (at most 64 x 132 bytes), validated before anything is enqueued;
+ * pred_of is a host array in the host forms and d_pred_of device memory in the _device forms, read back and checked in the
+ * wait d_mask_of has.  Errors are those of the bitmap form, in its order, and: NULL preds or n_preds == 0 with
+ * n_queries > 0, a term's column at or above EHX_MAX_COLUMNS, n_terms > EHX_PRED_MAX_TERMS, a flag bit other than
+ * EHX_TERM_NOT, an entry of pred_of at or above n_preds: EHX_EINVAL, the outputs unwritten; n_preds > 64: EHX_EUNSUPPORTED,
+ * the bitmap table's limit, for the reason given at ehx_knn_masked_multi_device; a NULL space: EHX_EINVAL before the device
+ * is looked for; a row-sharded space: EHX_EUNSUPPORTED, as for every column call; n_queries == 0: EHX_OK.  A graph space
+ * answers from its stored rows: the graph walk under predicates is NOT built. */
+#define EHX_PRED_MAX_TERMS 8
+#define EHX_TERM_NOT 1u
+typedef struct ehx_term {
+  uint32_t col, lo, hi, flags; /* holds iff lo <= value <= hi, UNSIGNED; EHX_TERM_NOT inverts */
+} ehx_term;
+typedef struct ehx_pred {
+  uint32_t n_terms;
+  ehx_term terms[EHX_PRED_MAX_TERMS]; /* a conjunction */
+} ehx_pred;
+/* ehx_knn_masked_multi_device under the predicates' bitmaps. */
+int ehx_knn_where_device(ehx_space* s, void* stream, size_t n_queries, const float* d_queries, uint32_t k, const ehx_pred* preds,
+                         uint32_t n_preds, const uint32_t* d_pred_of, uint64_t* d_out_ids, float* d_out_dist,
+                         uint32_t* d_out_count);
+int ehx_knn_where(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, const ehx_pred* preds, uint32_t n_preds,
+                  const uint32_t* pred_of, uint64_t* out_ids, float* out_dist, uint32_t* out_count);
+/* ehx_knn_grouped_masked_device under the predicates' bitmaps, given the stored column group_col of the prefix as its labels
+ * (read where it lies, as ehx_knn_grouped_by_label_device reads it; never written: every row a group of its own).  group_col
+ * at or above EHX_MAX_COLUMNS: EHX_EINVAL.  With n_preds == 1, pred_of may be NULL: every query under predicate 0. */
+int ehx_knn_grouped_where_device(ehx_space* s, void* stream, size_t n_queries, const float* d_queries, uint32_t k,
+                                 uint32_t per_group, uint32_t group_col, const ehx_pred* preds, uint32_t n_preds,
+                                 const uint32_t* d_pred_of, uint64_t* d_out_ids, float* d_out_dist, uint32_t* d_out_count);
+int ehx_knn_grouped_where(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, uint32_t per_group,
+                          uint32_t group_col, const ehx_pred* preds, uint32_t n_preds, const uint32_t* pred_of,
+                          uint64_t* out_ids, float* out_dist, uint32_t* out_count);
+/* ehx_range_masked_device under the predicates' bitmaps.  With n_preds == 1, pred_of may be NULL. */
+int ehx_range_where_device(ehx_space* s, void* stream, size_t n_queries, const float* d_queries, const float* d_radius,
+                           uint32_t max_results, const ehx_pred* preds, uint32_t n_preds, const uint32_t* d_pred_of,
+                           uint64_t* d_out_ids, float* d_out_dist, uint32_t* d_out_count, uint64_t* d_out_total);
+int ehx_range_where(ehx_space* s, size_t n_queries, const float* queries, const float* radius, uint32_t max_results,
+                    const ehx_pred* preds, uint32_t n_preds, const uint32_t* pred_of, uint64_t* out_ids, float* out_dist,
+                    uint32_t* out_count, uint64_t* out_total);
 /* k-way merge of per-shard results (RCCL all-gather output): lists laid out
  * [n_lists][n_queries][k]; ids must already be global.  Ordered by (dist, id). */
 int ehx_merge_topk_device(void* stream, size_t n_queries, uint32_t k, uint32_t n_lists,
