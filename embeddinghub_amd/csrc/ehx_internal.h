@@ -563,46 +563,25 @@ struct ehx_space {
   RadiusKnnBufs largek;
   // test hook: queries answered on the route, handed to the exhaustive pass, of those the overflowed, scan passes launched, calls
   std::atomic<uint64_t> largek_ctr[5] = {};
-  // grouped kNN (ehx_grouped.cpp; scratch_mu): the scan route's buffers (RadiusKnnBufs; flagged queries go to the exact
-  // route), the exact route's own — carried keys, radii, every query's slab of row ids and its control words — and a host
-  // call's staged labels, queries and results
+  // grouped kNN in its three forms — unfiltered, under row bitmaps, under a label column (ehx_grouped.cpp's grouped_answer;
+  // scratch_mu): the scan route's buffers (RadiusKnnBufs; its sub-batch: the queries the scan hands on), the list route's own
+  // — carried keys, radii, every query's slab of row ids and its control words — the queries ordered by route and filter,
+  // every query's [start | end) of a device batch, and a host call's staged labels, queries and results.  The compactions
+  // are the bitmap search's and the label search's (masked, labeled).
   struct Grouped {
     RadiusKnnBufs scan;
-    RadiusKnnBufs exact;         // (its sub-batch is not used: the exact route hands nothing on)
+    RadiusKnnBufs exact;         // (its sub-batch is not used: the list route hands nothing on)
+    SubsetBufs group;
     DevBuf<uint64_t> dPool;      // [queries of a device batch][kPoolCap]
     DevBuf<uint32_t> dCtl;       // [queries] pool counts | [queries] flags, all zero
+    DevBuf<uint64_t> dRange;     // [queries of a device batch] start | [queries] end of every query's list
     DevBuf<uint32_t> dLabels;    // host form: the labels of the prefix searched
     HostStage host;
   } grouped;
-  // test hook: queries answered on the scan route, handed to the exact route, of those the overflowed, scan passes launched, calls
+  // test hooks, one per form: queries answered on the scan route, on the list route (by the gate or handed on by the scan),
+  // of those the overflowed, scan passes launched, calls
   std::atomic<uint64_t> grouped_ctr[5] = {};
-  // grouped kNN under row bitmaps (ehx_groupedm.cpp; scratch_mu): the compaction is the bitmap search's (masked), the list
-  // route's pools, control words, carried keys and a host call's staged labels the grouped kNN's (grouped.dPool / dCtl /
-  // exact / dLabels); its own are the scan route's buffers (its sub-batch: the queries the scan hands on), the call's
-  // queries ordered by route and bitmap, the bitmap of every query of a device batch, and a host call's staged queries and
-  // results
-  struct GroupedMasked {
-    RadiusKnnBufs scan;
-    SubsetBufs group;
-    DevBuf<uint32_t> dMaskAt;    // [queries of a device batch]
-    HostStage host;
-  } groupedm;
-  // test hook: queries answered on the scan route, on the list route (by the gate or handed on by the scan), of those the
-  // overflowed, scan passes launched, calls
   std::atomic<uint64_t> groupedm_ctr[5] = {};
-  // grouped kNN under a label column (ehx_groupedl.cpp; scratch_mu): the compaction and its scratch are the label search's
-  // (labeled_plan: labeled.dBlock / dSlots / dSlotOf / dOff, masked.dList / dCum), the list route's pools, control words and
-  // carried keys the grouped kNN's (grouped.dPool / dCtl / exact), a host call's staged columns theirs too (grouped.dLabels,
-  // labeled.dCol); its own are the scan route's buffers (its sub-batch: the queries the scan hands on), a device batch's
-  // queries ordered by route, every query's [start | end) in masked.dList, and a host call's staged queries and results
-  struct GroupedLabeled {
-    RadiusKnnBufs scan;
-    SubsetBufs group;
-    DevBuf<uint64_t> dRange;     // [queries of a device batch] start | [queries] end of every query's list
-    HostStage host;
-  } groupedl;
-  // test hook: queries answered on the scan route, on the list route (by the gate or handed on by the scan), of those the
-  // overflowed, scan passes launched, calls
   std::atomic<uint64_t> groupedl_ctr[5] = {};
   // Stored label columns (ehx_columns.cpp): column c is one uint32_t per row, written through the write path by key.
   // dCol[c] is sized to `cap` and moved by grow with the rows; col_live[c] turns true under mu held exclusively, at the
@@ -737,8 +716,6 @@ struct ehx_space {
     masked = {};
     largek = {};
     grouped = {};
-    groupedm = {};
-    groupedl = {};
     cols = {};
     for (auto& x : colidx) x = ColIndex{};
     one = {};
@@ -1000,12 +977,6 @@ bool largek_serves(const ehx_space* s, size_t nq, uint32_t k, uint64_t n_pub);
 int largek_locked(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, const float* d_queries, uint32_t k,
                   uint64_t* d_ids, float* d_dist, uint32_t* d_count);
 
-// ---- ehx_grouped.cpp ----
-// the exact route of the grouped kNN over the prefix of n_eff rows: every row in slabs of kPoolCap, any space kind
-// (count_queries: its queries are not in n_queries yet)
-int grouped_exact(ehx_space* s, hipStream_t st, uint64_t n_eff, size_t nq, const float* d_queries, uint32_t k, uint32_t per_group,
-                  const uint32_t* d_group_of, uint64_t* d_ids, float* d_dist, uint32_t* d_count, bool count_queries = true);
-
 // ---- ehx_range.cpp ----
 constexpr uint32_t kRangeGridTarget = 4096;   // workgroups an exact range kernel's launch aims for (16 per CU): chosen, not measured
 // The bitmaps of a filtered range search in the int8 scan's flush (RadiusScan's allow fields) and the tiles below their n_bits
@@ -1116,6 +1087,23 @@ struct FilterView {
 bool filter_scan_serves(const ehx_space* s, uint32_t k, uint64_t n_pub);   // the scan route serves this k on this prefix
 int filtered_answer(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, const FilterView& v,
                     const ResultBlock& out);
+
+// ---- ehx_grouped.cpp ----
+// the checks every grouped entry point starts with, with their codes and in their order; the caller appends its own
+int grouped_check_head(const ehx_space* s, size_t nq, uint32_t k, uint32_t per_group, const void* q, const void* group_of,
+                       uint64_t n_labels, const void* o_ids, const void* o_dist, const void* o_cnt);
+int grouped_check_ld(const ehx_space* s);   // rows wider than grouped_rerank_max_ld() floats: EHX_EUNSUPPORTED
+// The grouped list route, any space kind: query j over d_list[range[j], range[nq + j]) (range: host memory; d_list ==
+// nullptr: the identity list, the range is of row ids), in slabs of kPoolCap.  count_queries: its queries are not in
+// n_queries yet.
+int grouped_list(ehx_space* s, hipStream_t st, uint64_t n_eff, const uint64_t* d_list, const uint64_t* range, size_t nq,
+                 const float* d_queries, uint32_t k, uint32_t per_group, const uint32_t* d_group_of, uint64_t* d_ids,
+                 float* d_dist, uint32_t* d_count, bool count_queries);
+// The grouped answer over compacted per-query row filters, whatever they were compacted from — nothing (one filter that
+// allows the prefix, a null d_list), a table of bitmaps, the wanted labels of a column.  Of v it reads n_pub, n_eff,
+// n_filters, n_allowed, off, filter_of, scans, d_list, allow*, d_head, head_of and ctr.
+int grouped_answer(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, uint32_t per_group,
+                   const uint32_t* d_group_of, const FilterView& v, const ResultBlock& out);
 
 // ---- ehx_labeled.cpp ----
 // The label column of one device batch, compacted for the batch's distinct wanted labels ("slots"): the slot of every query,

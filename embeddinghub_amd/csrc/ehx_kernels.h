@@ -676,26 +676,13 @@ struct GroupedRerankArgs {
 };
 uint32_t grouped_rerank_max_ld();   // longest row stride (floats): the pool, the cap's images and the prepared query share the LDS
 hipError_t launch_grouped_rerank(const GroupedRerankArgs& g, hipStream_t st);   // r.k <= kLargeKMax, rows.ld <= grouped_rerank_max_ld()
-// pool[q][i] = row0 + i for i < kPoolCap and pool_cnt[q] = n <= kPoolCap, for every query; first: radius[q] = +Inf,
-// top_cnt[q] = work[q] = 0 besides (the state in front of the first slab)
-hipError_t launch_grouped_slab(uint64_t* pool, uint32_t* pool_cnt, uint32_t nq, uint64_t row0, uint32_t n, bool first,
-                               float* radius, uint32_t* top_cnt, uint32_t* work, hipStream_t st);
-
-// grouped kNN under row bitmaps (k_groupedm.hip): every query's pool filled from the compacted list of ITS OWN bitmap —
-// list, off, cum, n_tiles: launch_masked_fill's (n_tiles >= 1); mask_at[q] < n_masks: the bitmap of query q of the batch.
-// seed: pool[q][i] = mask's list[i * stride] for i * stride < allowed, stride = ceil(allowed / kLargeKSample), pool_cnt[q]
-// the number written.  slab: pool[q][0, n) = entries [slab * kPoolCap, ...) of the mask's list, pool_cnt[q] = n = as many as
-// remain, at most kPoolCap, possibly 0; first: radius[q] = +Inf, top_cnt[q] = work[q] = 0 besides, as launch_grouped_slab
-hipError_t launch_grouped_list_seed(const uint64_t* list, const MaskedOffsets& off, const uint32_t* cum, uint32_t n_tiles,
-                                    const uint32_t* mask_at, uint64_t* pool, uint32_t* pool_cnt, uint32_t nq, hipStream_t st);
-hipError_t launch_grouped_list_slab(const uint64_t* list, const MaskedOffsets& off, const uint32_t* cum, uint32_t n_tiles,
-                                    const uint32_t* mask_at, uint64_t slab, bool first, uint64_t* pool, uint32_t* pool_cnt,
-                                    float* radius, uint32_t* top_cnt, uint32_t* work, uint32_t nq, hipStream_t st);
-
-// grouped kNN under a label column (k_groupedl.hip): the same two fills with query q's list given as the range
-// list[start[q], end[q]) — start, end: device arrays of nq entries, end[q] >= start[q], the range inside the list; queries may
-// name the same range, and any number of ranges fits one launch.  seed: stride = ceil(len / kLargeKSample) over the range by
-// rank; slab: entries [slab * kPoolCap, ...) of the range, possibly none; first: as launch_grouped_list_slab
+// every query's pool filled from ITS OWN rows, query q's given as the range list[start[q], end[q]) — start, end: device
+// arrays of nq entries, end[q] >= start[q], the range inside the list; list == nullptr: the identity list, entry i is row i
+// (an empty range reads nothing, whatever list is).  Queries may name the same range, and any number of ranges fits one
+// launch.  seed: pool[q][i] = entry i * stride of the range for i * stride < len, stride = ceil(len / kLargeKSample),
+// pool_cnt[q] the number written.  slab: pool[q][0, n) = entries [slab * kPoolCap, ...) of the range, pool_cnt[q] = n = as
+// many as remain, at most kPoolCap, possibly 0; first: radius[q] = +Inf, top_cnt[q] = work[q] = 0 besides (the state in front
+// of the first slab)
 hipError_t launch_grouped_range_seed(const uint64_t* list, const uint64_t* start, const uint64_t* end, uint64_t* pool,
                                      uint32_t* pool_cnt, uint32_t nq, hipStream_t st);
 hipError_t launch_grouped_range_slab(const uint64_t* list, const uint64_t* start, const uint64_t* end, uint64_t slab,

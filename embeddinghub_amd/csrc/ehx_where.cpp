@@ -199,7 +199,7 @@ int ehx_knn_grouped_where(ehx_space* s, size_t n_queries, const float* queries, 
     if (int rc = check_mask_of(pred_of, n_queries, n_preds)) return rc;   // (before anything is enqueued)
   return search_on_device(s, "ehx_knn_grouped_where", kWhereWhy, n_queries, nullptr, [&]() -> int {
     int rc;
-    HostStage& h = s->groupedm.host;
+    HostStage& h = s->grouped.host;
     if ((rc = h.up(s->stream, queries, n_queries, s->dims, k, false))) return rc;
     if ((rc = grouped_where_locked(s, s->stream, n_queries, h.q, k, per_group, group_col, preds, n_preds, pred_of, nullptr, h.out)))
       return rc;

@@ -1,7 +1,19 @@
-// Grouped kNN (ehx_knn_grouped*, ehx_grouped.cpp): the first k ELIGIBLE rows of the prefix searched in (canonical distance,
-// id) order, a row being eligible iff its label is kGroupNone or fewer than per_group ("m") rows of its label precede it in
-// that order.  The falling-radius kNN of k_radius.hip with a cap per label in its re-rank:
-//   grouped_slab_kernel     the consecutive ids [row0, row0 + kPoolCap) into every query's pool (the exact route's "pass")
+// Grouped kNN (ehx_knn_grouped*, ehx_grouped.cpp), unfiltered, under row bitmaps and under a label column: the first k
+// ELIGIBLE rows of the rows searched in (canonical distance, id) order, a row being eligible iff its label is kGroupNone or
+// fewer than per_group ("m") rows of its label precede it in that order.  The falling-radius kNN of k_radius.hip with a cap
+// per label in its re-rank.  Whatever names a query's rows — nothing, a bitmap, a wanted label — the host turns it into ONE
+// shape: query q searches list[start[q], end[q]), start and end read from a per-batch device array, so any number of lists
+// fits one launch and queries under one filter name the same range; list == nullptr is the identity list (entry i is row i),
+// which makes the unfiltered search the range [0, n_eff).
+//   grouped_range_seed_kernel   the scan route's sample: every stride-th entry of the range by rank, stride = ceil(len /
+//                               kLargeKSample), at most kLargeKSample of them (a scanning filter's list is ascending, so the
+//                               sample spreads over the id space; the identity list gives rows 0, stride, 2 stride, ...);
+//                               the seed-mode re-rank makes the first radius of it
+//   grouped_range_slab_kernel   the list route's "pass": entries [b kPoolCap, (b + 1) kPoolCap) of the range, as many as
+//                               remain (possibly none: the re-rank keeps its carried keys through an empty pool, and an empty
+//                               range — which reads nothing, whatever list is — still has its page written); in front of the
+//                               first slab the radius +Inf, nothing carried, work 0.  Both are a copy of at most 32 KiB per
+//                               query: nothing to tune.
 //   grouped_rerank_kernel   radius_rerank_kernel's modes and arguments plus the labels: the pool's canonical distances, cut
 //                           at the radius and sorted (pool_rerank_sorted, unchanged), then
 //                             A  the sorted hits capped — at most m per label — and cut at k,
@@ -16,8 +28,11 @@
 // it is kept iff that rank is below m or the label is kGroupNone (such rows are never ranked against one another); a
 // prefix sum over the keep bits in position order compacts the first k kept.
 //
-// Why the answer is exact.  cap(S) below is "S in key order, every row dropped that is not among the first m of its label
-// in S", cap_k(S) its first k entries.
+// Why the answer is exact.  The rows a query may return — the prefix, its allowed rows, the rows of its label — are a FIXED
+// set S: neither a bitmap nor a label column is a function of the search.  cap(S) below is "S in key order, every row
+// dropped that is not among the first m of its label in S", cap_k(S) its first k entries; every step speaks of subsets of S
+// only.  The scan's flush drops every row outside S before it takes a pool slot and the ranges hold S alone, so no row
+// outside S ever reaches a cap: it neither appears nor counts (FILTER FIRST, THEN CAP).
 //   * "At most m per label" is a partition matroid: greedy by ascending key over any set S keeps exactly the rows that are
 //     among the first m of their label in S — cap(S) — and the answer over S is cap_k(S).
 //   * A row that is not among the first m of its label in S is not among them in any superset of S: m nearer rows of its
@@ -26,13 +41,15 @@
 //     below x number min(m, rows of that label below x), which only grows as S grows (kGroupNone rows: each its own label).
 //   * So rows dropped by a cap or by a cut at k never return: cap_k(A u B) = cap_k(cap_k(A) u cap_k(B)).  A is a pass's
 //     hits, B the carried list: step B above computes the right side.
-//   * The k-th key kept over ANY subset of the prefix bounds the true k-th eligible distance from above (third point), so
+//   * The k-th key kept over ANY subset of S bounds the true k-th eligible distance from above (third point), so
 //     every radius is such a bound, the scan under it keeps every member (k_radius.hip's header: the threshold keeps every
 //     row with D <= r), and the cut at the radius drops none.
 //   * The rest is k_radius.hip's induction over passes: a member leaves the carried list only when a cap or a cut drops it,
-//     and then it is no member.  The exact route runs the same kernel over consecutive slabs of ALL rows, radius +Inf first.
+//     and then it is no member.  The list route runs the same kernel over the slabs of ALL of S, radius +Inf first; the
+//     identity above holds for any split of S into slabs, in any order, so its answer does not depend on the order of a
+//     list (a filter that does not scan may be listed in any order).
 //   * Flagged queries (pool overflow, a radius the bound does not serve) write nothing here: the host answers them on the
-//     exact route.
+//     list route.
 #include "ehx_kernels.h"
 
 namespace ehx {
@@ -98,12 +115,36 @@ __device__ __forceinline__ uint32_t cap_sorted(const uint64_t* src, uint32_t n, 
 
 }  // namespace
 
-// one workgroup per query (launch_grouped_slab)
-__global__ __launch_bounds__(256) void grouped_slab_kernel(uint64_t* __restrict__ pool, uint32_t* __restrict__ pool_cnt,
-                                                           uint64_t row0, uint32_t n, uint32_t first, float* __restrict__ radius,
-                                                           uint32_t* __restrict__ top_cnt, uint32_t* __restrict__ work) {
+// entry i of query q's range: list[start + i], or row start + i of the identity list
+__device__ __forceinline__ uint64_t range_entry(const uint64_t* __restrict__ list, uint64_t at) { return list ? list[at] : at; }
+
+// one workgroup per query (launch_grouped_range_seed)
+__global__ __launch_bounds__(256) void grouped_range_seed_kernel(const uint64_t* __restrict__ list,
+                                                                 const uint64_t* __restrict__ start,
+                                                                 const uint64_t* __restrict__ end,
+                                                                 uint64_t* __restrict__ pool, uint32_t* __restrict__ pool_cnt) {
   const uint32_t q = blockIdx.x;
-  for (uint32_t i = threadIdx.x; i < kPoolCap; i += 256u) pool[(size_t)q * kPoolCap + i] = row0 + i;
+  const uint64_t b = start[q], e = end[q];
+  const uint64_t len = e > b ? e - b : 0ull;
+  const uint64_t stride = (len + kLargeKSample - 1u) / kLargeKSample;
+  const uint32_t n_sample = stride ? (uint32_t)((len + stride - 1u) / stride) : 0u;   // (<= kLargeKSample <= kPoolCap)
+  for (uint32_t i = threadIdx.x; i < n_sample; i += 256u) pool[(size_t)q * kPoolCap + i] = range_entry(list, b + (uint64_t)i * stride);
+  if (threadIdx.x == 0) pool_cnt[q] = n_sample;
+}
+
+// one workgroup per query (launch_grouped_range_slab)
+__global__ __launch_bounds__(256) void grouped_range_slab_kernel(const uint64_t* __restrict__ list,
+                                                                 const uint64_t* __restrict__ start,
+                                                                 const uint64_t* __restrict__ end, uint64_t slab,
+                                                                 uint32_t first, uint64_t* __restrict__ pool,
+                                                                 uint32_t* __restrict__ pool_cnt, float* __restrict__ radius,
+                                                                 uint32_t* __restrict__ top_cnt, uint32_t* __restrict__ work) {
+  const uint32_t q = blockIdx.x;
+  const uint64_t b = start[q], e = end[q];
+  const uint64_t len = e > b ? e - b : 0ull, at = slab * kPoolCap;
+  const uint64_t left = at < len ? len - at : 0ull;
+  const uint32_t n = left < kPoolCap ? (uint32_t)left : kPoolCap;
+  for (uint32_t i = threadIdx.x; i < n; i += 256u) pool[(size_t)q * kPoolCap + i] = range_entry(list, b + at + i);
   if (threadIdx.x == 0) {
     pool_cnt[q] = n;
     if (first) {
@@ -198,12 +239,22 @@ DynLdsAttr g_grouped_lds;
 
 uint32_t grouped_rerank_max_ld() { return kGroupedMaxLd; }
 
-hipError_t launch_grouped_slab(uint64_t* pool, uint32_t* pool_cnt, uint32_t nq, uint64_t row0, uint32_t n, bool first,
-                               float* radius, uint32_t* top_cnt, uint32_t* work, hipStream_t st) {
+// (list may be nullptr: the identity list)
+hipError_t launch_grouped_range_seed(const uint64_t* list, const uint64_t* start, const uint64_t* end, uint64_t* pool,
+                                     uint32_t* pool_cnt, uint32_t nq, hipStream_t st) {
   if (nq == 0) return hipSuccess;
-  if (n > kPoolCap || (first && (!radius || !top_cnt || !work))) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(grouped_slab_kernel, dim3(nq), dim3(256), 0, st, pool, pool_cnt, row0, n, first ? 1u : 0u, radius, top_cnt,
-                     work);
+  if (!start || !end || !pool || !pool_cnt) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(grouped_range_seed_kernel, dim3(nq), dim3(256), 0, st, list, start, end, pool, pool_cnt);
+  return hipGetLastError();
+}
+
+hipError_t launch_grouped_range_slab(const uint64_t* list, const uint64_t* start, const uint64_t* end, uint64_t slab,
+                                     bool first, uint64_t* pool, uint32_t* pool_cnt, float* radius, uint32_t* top_cnt,
+                                     uint32_t* work, uint32_t nq, hipStream_t st) {
+  if (nq == 0) return hipSuccess;
+  if (!start || !end || !pool || !pool_cnt || (first && (!radius || !top_cnt || !work))) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(grouped_range_slab_kernel, dim3(nq), dim3(256), 0, st, list, start, end, slab, first ? 1u : 0u, pool,
+                     pool_cnt, radius, top_cnt, work);
   return hipGetLastError();
 }
 

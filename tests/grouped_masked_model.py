@@ -64,7 +64,7 @@ def scan_mask_of(nq=64):
 
 
 def sample_of(allow):
-    """grouped_list_seed_kernel: every stride-th allowed id by rank, stride = ceil(allowed / kLargeKSample)"""
+    """grouped_range_seed_kernel over the mask's list: every stride-th allowed id by rank, stride = ceil(allowed / kLargeKSample)"""
     ids = np.nonzero(allow)[0]
     if len(ids) == 0:
         return ids

@@ -76,16 +76,16 @@ def test_label_marshalling():
 
 
 def test_grouped_kernels_use_no_scratch_and_spill_no_vector_registers(tmp_path):
-    """three layouts x three metrics of the re-rank, and the slab kernel"""
+    """three layouts x three metrics of the re-rank, and the two kernels that fill a query's pool from its range"""
     src = os.path.join(ehx_build.CSRC, "k_grouped.hip")
     flags = [f for f in ehx_build.FLAGS if f != "-shared"]
     r = subprocess.run([ehx_build.HIPCC] + flags + ["-Rpass-analysis=kernel-resource-usage", "-x", "hip", "-c", src, "-o",
                                                     str(tmp_path / "k_grouped.o")], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     names = re.findall(r"Function Name: (\S+)", r.stderr)
-    for kern, count in (("grouped_rerank_kernel", 9), ("grouped_slab_kernel", 1)):
+    for kern, count in (("grouped_rerank_kernel", 9), ("grouped_range_seed_kernel", 1), ("grouped_range_slab_kernel", 1)):
         assert sum(kern in n for n in names) == count, names
-    assert len(names) == 10
+    assert len(names) == 11
     for what in ("ScratchSize \\[bytes/lane\\]", "VGPRs Spill"):
         vals = re.findall(what + r": (\d+)", r.stderr)
         assert len(vals) == len(names) and all(v == "0" for v in vals), (what, vals)

@@ -1,4 +1,4 @@
-"""GPU tests of the grouped kNN under a label column (ehx_knn_grouped_labeled*, ehx_groupedl.cpp, k_groupedl.hip): FILTER
+"""GPU tests of the grouped kNN under a label column (ehx_knn_grouped_labeled*, ehx_groupedl.cpp, k_grouped.hip): FILTER
 FIRST, THEN CAP — the first k eligible rows among the rows of the query's own tenant — on the scan route (the falling-radius
 int8 scan, "the row's label is the query's" in its flush, a cap per group in its re-rank, the first radius from a sample of
 the tenant's rows) and on the list route (the tenant's rows in slabs of 4096 drawn from the compacted lists, any number of

@@ -1,7 +1,8 @@
 """CPU-side checks of the grouped kNN under a label column (ehx_knn_grouped_labeled*): the declarations, the ABI that stays
 as it was, the hook outside it, what both entry points answer without a device, what the header promises, the tenant column
 of the scan cases, the table of the cases the GPU test asserts "none handed on" for — re-derived from the model case by
-case — and the resource usage of k_groupedl.hip built for gfx950 beside the function lists of the two files it stands next to."""
+case — and the resource usage of the two pool-fill kernels (k_grouped.hip) built for gfx950 beside the function lists of the
+two files they stand next to."""
 import ctypes as C
 import inspect
 import os
@@ -31,7 +32,7 @@ def test_entry_points_are_declared_bound_and_exported():
     raw = C.CDLL(_lib.LIB_PATH)
     for name in NEW:
         assert re.search(r"\bint %s\(" % name, header) and name in _lib.SYMBOLS and hasattr(raw, name)
-    assert "k_groupedl.hip" in ehx_build.SOURCES and "ehx_groupedl.cpp" in ehx_build.SOURCES
+    assert "k_grouped.hip" in ehx_build.SOURCES and "ehx_groupedl.cpp" in ehx_build.SOURCES
     assert re.search(r"#define EHX_ABI_VERSION 5\b", header)   # additive: the version stays
     for name in ("knn_grouped_labeled", "knn_grouped_labeled_device"):
         assert callable(getattr(Space, name))
@@ -126,19 +127,21 @@ def _functions(name, tmp_path):
 
 
 def test_groupedl_kernels_use_no_scratch_and_spill_no_vector_registers(tmp_path):
-    """the range seed and the range slab kernel, nothing else"""
-    names, log = _functions("k_groupedl.hip", tmp_path)
+    """the range seed and the range slab kernel, once each in k_grouped.hip: no scratch, no spill, no LDS"""
+    names, log = _functions("k_grouped.hip", tmp_path)
+    blocks = log.split("Function Name: ")[1:]   # one block of remarks per kernel
+    assert len(blocks) == len(names)
     for kern in ("grouped_range_seed_kernel", "grouped_range_slab_kernel"):
-        assert sum(kern in n for n in names) == 1, names
-    assert len(names) == 2
-    for what in ("ScratchSize \\[bytes/lane\\]", "VGPRs Spill", "LDS Size \\[bytes/block\\]"):
-        vals = re.findall(what + r": (\d+)", log)
-        assert len(vals) == len(names) and all(v == "0" for v in vals), (what, vals)
+        mine = [b for b in blocks if kern in b.split()[0]]
+        assert len(mine) == 1, names
+        for what in ("ScratchSize \\[bytes/lane\\]", "VGPRs Spill", "LDS Size \\[bytes/block\\]"):
+            assert re.findall(what + r": (\d+)", mine[0]) == ["0"], (kern, what)
 
 
 def test_the_files_beside_it_hold_the_functions_they_held(tmp_path):
-    names, _ = _functions("k_groupedm.hip", tmp_path)
-    assert len(names) == 2 and all(sum(k in n for n in names) == 1 for k in ("grouped_list_seed_kernel", "grouped_list_slab_kernel"))
+    names, _ = _functions("k_grouped.hip", tmp_path)
+    held = (("grouped_rerank_kernel", 9), ("grouped_range_seed_kernel", 1), ("grouped_range_slab_kernel", 1))
+    assert len(names) == 11 and all(sum(k in n for n in names) == c for k, c in held)
     names, _ = _functions("k_labeled.hip", tmp_path)
     kernels = ("labeled_count_kernel", "labeled_tiles_kernel", "labeled_prefix_kernel", "labeled_fill_kernel",
                "labeled_sample_kernel")

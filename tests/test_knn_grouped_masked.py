@@ -1,4 +1,4 @@
-"""GPU tests of the grouped kNN under row bitmaps (ehx_knn_grouped_masked*, ehx_groupedm.cpp, k_groupedm.hip): FILTER FIRST,
+"""GPU tests of the grouped kNN under row bitmaps (ehx_knn_grouped_masked*, ehx_groupedm.cpp, k_grouped.hip): FILTER FIRST,
 THEN CAP — the first k eligible rows among the rows a query's bitmap allows — on the scan route (the falling-radius int8
 scan, the bitmaps in its flush, a cap per label in its re-rank, the first radius from a sample of the allowed rows) and on
 the list route (every allowed row in slabs of 4096 drawn from the bitmap's compacted list).

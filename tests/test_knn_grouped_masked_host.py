@@ -1,6 +1,6 @@
 """CPU-side checks of the grouped kNN under row bitmaps (ehx_knn_grouped_masked*): the declarations, the ABI that stays as
-it was, the hook outside it, what both entry points answer without a device, and the resource usage of k_groupedm.hip built
-for gfx950."""
+it was, the hook outside it, what both entry points answer without a device, and the resource usage of the two pool-fill
+kernels (k_grouped.hip) built for gfx950."""
 import ctypes as C
 import inspect
 import os
@@ -21,7 +21,7 @@ def test_entry_points_are_declared_bound_and_exported():
     raw = C.CDLL(_lib.LIB_PATH)
     for name in NEW:
         assert re.search(r"\bint %s\(" % name, header) and name in _lib.SYMBOLS and hasattr(raw, name)
-    assert "k_groupedm.hip" in ehx_build.SOURCES and "ehx_groupedm.cpp" in ehx_build.SOURCES
+    assert "k_grouped.hip" in ehx_build.SOURCES and "ehx_groupedm.cpp" in ehx_build.SOURCES
     assert re.search(r"#define EHX_ABI_VERSION 5\b", header)   # additive: the version stays
     for name in ("knn_grouped_masked", "knn_grouped_masked_device"):
         assert callable(getattr(Space, name))
@@ -59,16 +59,15 @@ def test_a_null_space_is_refused_before_the_device_is_looked_for():
 
 
 def test_groupedm_kernels_use_no_scratch_and_spill_no_vector_registers(tmp_path):
-    """the seed and the slab kernel, nothing else"""
-    src = os.path.join(ehx_build.CSRC, "k_groupedm.hip")
+    """the seed and the slab kernel, which the three grouped searches share: once each in k_grouped.hip"""
+    src = os.path.join(ehx_build.CSRC, "k_grouped.hip")
     flags = [f for f in ehx_build.FLAGS if f != "-shared"]
     r = subprocess.run([ehx_build.HIPCC] + flags + ["-Rpass-analysis=kernel-resource-usage", "-x", "hip", "-c", src, "-o",
-                                                    str(tmp_path / "k_groupedm.o")], capture_output=True, text=True)
+                                                    str(tmp_path / "k_grouped.o")], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
-    names = re.findall(r"Function Name: (\S+)", r.stderr)
-    for kern in ("grouped_list_seed_kernel", "grouped_list_slab_kernel"):
-        assert sum(kern in n for n in names) == 1, names
-    assert len(names) == 2
-    for what in ("ScratchSize \\[bytes/lane\\]", "VGPRs Spill"):
-        vals = re.findall(what + r": (\d+)", r.stderr)
-        assert len(vals) == len(names) and all(v == "0" for v in vals), (what, vals)
+    blocks = r.stderr.split("Function Name: ")[1:]   # one block of remarks per kernel
+    for kern in ("grouped_range_seed_kernel", "grouped_range_slab_kernel"):
+        mine = [b for b in blocks if kern in b.split()[0]]
+        assert len(mine) == 1, [b.split()[0] for b in blocks]
+        for what in ("ScratchSize \\[bytes/lane\\]", "VGPRs Spill"):
+            assert re.findall(what + r": (\d+)", mine[0]) == ["0"], (kern, what)
