@@ -227,28 +227,25 @@ void colindex_plan(const ehx_space::ColIndex& ix, size_t m, const uint32_t* want
   p->scan_of.assign(n_slots, kLabeledNoScan);
   p->cum.clear();
   p->n_scan = 0;
+  std::vector<uint32_t> label_at(n_slots, kLabeledNoScan);   // the slot's position in ix.labels
   for (uint32_t f = 0; f < n_slots; ++f) {
     const auto it = std::lower_bound(ix.labels.begin(), ix.labels.end(), p->table[f]);
     if (it == ix.labels.end() || *it != p->table[f]) continue;   // no row carries the label
-    const uint32_t i = (uint32_t)(it - ix.labels.begin());
+    const uint32_t i = label_at[f] = (uint32_t)(it - ix.labels.begin());
     p->off[f] = ix.start[i];
     p->n_allowed[f] = (uint64_t)ix.start[i + 1] - ix.start[i];
-    if (!scan_serves || p->n_allowed[f] <= cut) continue;
-    // (the prefixes were prepared for the labels above masked_exact_cut(n): a cut forced below it leaves the others on lists)
-    const auto h = std::lower_bound(ix.heavy.begin(), ix.heavy.end(), i);
-    if (h == ix.heavy.end() || *h != i) continue;
-    p->scans[f] = 1;
-    p->scan_of[f] = (uint32_t)(h - ix.heavy.begin());
   }
-  if (min_scan_queries) {
-    size_t naming = 0;
-    for (size_t j = 0; j < m; ++j) naming += p->scans[p->slot_of[j]] != 0;
-    if (naming < min_scan_queries) {
-      p->scans.assign(n_slots, 0);
-      p->scan_of.assign(n_slots, kLabeledNoScan);
-    }
+  // the route: the cut; of those only the labels the index prepared prefixes for (above masked_exact_cut(n): a cut forced
+  // below it leaves the others on lists); the gate; then the scanning slots' rows of ix.cum
+  filter_routes_cut(scan_serves, cut, p->n_allowed.data(), n_slots, p->scans.data());
+  for (uint32_t f = 0; f < n_slots; ++f)
+    p->scans[f] = p->scans[f] && std::binary_search(ix.heavy.begin(), ix.heavy.end(), label_at[f]);
+  filter_routes_gate(p->slot_of.data(), m, min_scan_queries, n_slots, p->scans.data());
+  for (uint32_t f = 0; f < n_slots; ++f) {
+    if (!p->scans[f]) continue;
+    p->scan_of[f] = (uint32_t)(std::lower_bound(ix.heavy.begin(), ix.heavy.end(), label_at[f]) - ix.heavy.begin());
+    p->n_scan += 1;
   }
-  for (uint32_t f = 0; f < n_slots; ++f) p->n_scan += p->scans[f] != 0;
 }
 
 int column_as_groups(ehx_space* s, hipStream_t st, uint32_t col, uint64_t n_pub, const uint32_t** out) {

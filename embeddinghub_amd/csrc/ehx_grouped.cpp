@@ -58,6 +58,10 @@ int grouped_check_ld(const ehx_space* s) {
   return EHX_OK;
 }
 
+bool grouped_scan_serves(const ehx_space* s, uint64_t n_eff) {
+  return s->params.mode != EHX_MODE_GRAPH && !s->x_perm && n_eff > 0 && i8_serves_radius(s, n_eff);
+}
+
 int grouped_list(ehx_space* s, hipStream_t st, uint64_t n_eff, const uint64_t* d_list, const uint64_t* range, size_t nq,
                  const float* d_queries, uint32_t k, uint32_t per_group, const uint32_t* d_group_of, uint64_t* d_ids,
                  float* d_dist, uint32_t* d_count, bool count_queries) {
@@ -235,8 +239,7 @@ int grouped_locked(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, cons
   s->grouped_ctr[4] += 1;
   // ONE filter that allows the prefix: rows [0, n_eff) of the identity list, nothing tested in the flush
   const uint64_t n_eff = std::min(n_pub, n_labels), off = 0;
-  const char scans = s->params.mode != EHX_MODE_GRAPH && !s->x_perm && nq >= kLargeKMinQueries && n_eff > 0 &&
-                     i8_serves_radius(s, n_eff);
+  const char scans = nq >= kLargeKMinQueries && grouped_scan_serves(s, n_eff);
   FilterView v;
   v.n_pub = n_pub;
   v.n_eff = n_eff;

@@ -12,11 +12,10 @@
 //   compaction   the label search's (labeled_plan, ehx_labeled.cpp; a stored column: colindex_plan, read from its index): the
 //                batch's distinct wanted labels ("slots"), per slot its rows and its list in masked.dList, for the slots that
 //                scan an ascending list and the column's copy behind the head of labeled.dBlock
-//   routing      the grouped search's under bitmaps, decided by the plan BEFORE the lists are filled: a slot scans iff the
-//                space is flat with plain rows, its int8 scan serves a radius on the prefix, the slot has more than
-//                masked_exact_cut(rows) rows and at least kLargeKMinQueries queries of the batch name such slots — otherwise
-//                none scans, and the batch pays for no tile prefix, no column copy and no second wait.  At most 127 slots
-//                can (ehx_labeled.cpp's argument).  The cut is CARRIED OVER from the bitmap search, not measured for this call.
+//   routing      the one rule (filter_routes_cut / _gate, ehx_masked.cpp) with grouped_scan_serves on the prefix, the cut
+//                masked_exact_cut(rows) — CARRIED OVER from the bitmap search, not measured for this call — and the gate
+//                kLargeKMinQueries, decided by the plan BEFORE the lists are filled: where no slot scans, the batch pays
+//                for no tile prefix, no column copy and no second wait.  At most 127 slots can scan (ehx_labeled.cpp).
 //   the flush    "the row's label is the query's" (allow_label: the head of the block is every query's wanted label)
 // Waits: the device form reads d_want back (one wait for the whole call, the outputs unwritten until then), then per device
 // batch the compaction's — once for the counts, a second time only where some slot scans — and radius_knn's one verdict.
@@ -48,87 +47,36 @@ int grouped_by_label_check(const ehx_space* s, size_t nq, uint32_t k, uint32_t p
   return EHX_OK;
 }
 
-// One device batch of m <= kSideChunk queries under want[0, m) (host memory) over the prefix of n_eff rows of both columns.
-// *col_copied: the flush's copy of the label column is in place (made once per call, and only where some slot scans).
-// ix: the label column is a stored one — the plan is read from its fresh index (colindex_plan: no launch, no wait), the
-// lists are runs of its permutation and the flush's block is the index's.
-int groupedl_batch(ehx_space* s, hipStream_t st, uint64_t n_pub, uint64_t n_eff, size_t m, const float* d_queries, uint32_t k,
-                   uint32_t per_group, const uint32_t* d_group_of, const uint32_t* d_label_of, const ehx_space::ColIndex* ix,
-                   const uint32_t* want, bool* col_copied, const ResultBlock& out) {
-  int rc;
-  // routing: the grouped search's under bitmaps (ehx_groupedm.cpp), applied by the plan before it fills the lists
-  const bool scan_serves = s->params.mode != EHX_MODE_GRAPH && !s->x_perm && n_eff > 0 && i8_serves_radius(s, n_eff);
-  LabeledPlan p;
-  if (ix) colindex_plan(*ix, m, want, scan_serves, masked_exact_cut(n_pub), kLargeKMinQueries, &p);
-  else if ((rc = labeled_plan(s, st, n_eff, m, d_label_of, want, scan_serves, masked_exact_cut(n_pub), kLargeKMinQueries, col_copied, &p)))
-    return rc;
-  uint32_t* d_block = ix ? ix->dBlock.p : s->labeled.dBlock.p;
-  FilterView v;
-  v.n_pub = n_pub;
-  v.n_eff = n_eff;
-  v.n_filters = p.n_slots;
-  v.n_allowed = p.n_allowed.data();
-  v.off = p.off.data();
-  v.filter_of = p.slot_of.data();
-  v.scans = p.scans.data();
-  v.d_list = ix ? ix->dPerm.p : s->masked.dList.p;
-  v.allow = d_block;
-  v.allow_label = true;
-  v.d_head = d_block;
-  v.head_of = p.table.data();
-  v.ctr = s->groupedl_ctr;
-  return grouped_answer(s, st, m, d_queries, k, per_group, d_group_of, v, out);
-}
-
-// an unsharded space, locked shared, scratch_mu held, its device current; everything is enqueued on `st`.  group_of /
-// label_of: at least min(n_labels, row count) entries each, in host memory (cols_on_host: staged in grouped.dLabels and
-// labeled.dCol) or on the device; want: in host memory, or d_want, read back once (the outputs unwritten until then)
+// The label search's body (labeled_call, ehx_labeled.cpp: its contract) with the grouped search's routing inputs, and what a
+// group column adds.  group_of / label_of: at least min(n_labels, row count) entries each, in host memory (cols_on_host:
+// staged in grouped.dLabels and labeled.dCol) or on the device — or, with label_col >= 0, the space's stored columns
+// group_col and label_col over the whole prefix; want / d_want: labeled_call's
 int groupedl_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, uint32_t per_group,
                     const uint32_t* group_of, const uint32_t* label_of, bool cols_on_host, uint64_t n_labels,
                     const uint32_t* want, const uint32_t* d_want, const ResultBlock& out, int group_col = -1, int label_col = -1) {
-  int rc;
-  if ((rc = check_not_poisoned(s))) return rc;
-  if ((rc = grouped_check_ld(s))) return rc;   // (before anything is enqueued)
-  s->groupedl_ctr[4] += 1;
   // the ONE read of the row count: the lists name rows below it only, and every later stage sees at least this prefix
   const uint64_t n_pub = s->n.load(std::memory_order_acquire);
-  const bool stored = label_col >= 0;   // ehx_knn_grouped_by_label*: both columns are the space's, over the whole prefix
-  const uint64_t n_eff = stored ? n_pub : std::min<uint64_t>(n_labels, n_pub);   // (row ids are 32 bits wide: n_pub < 2^32)
-  if (!stored && (rc = labeled_plan_scratch(s, n_eff))) return rc;
-  // (earlier calls' launches on other streams may still read the block, the lists and the staged columns)
-  if ((rc = wait_searches_in_flight(s, st))) return rc;
-  const uint32_t *d_group_of = group_of, *d_label_of = label_of;
-  const ehx_space::ColIndex* ix = nullptr;   // the label column's index, rebuilt here if a write or an append left it stale
-  if (stored && ((rc = colindex_ensure(s, st, (uint32_t)label_col, n_pub, &ix)) ||
-                 (rc = column_as_groups(s, st, (uint32_t)group_col, n_pub, &d_group_of))))
-    return rc;
-  if (cols_on_host) {
-    if ((rc = s->grouped.dLabels.ensure(std::max<uint64_t>(n_eff, 1))) || (rc = s->labeled.dCol.ensure(std::max<uint64_t>(n_eff, 1))))
-      return rc;
-    // (labels at or above the prefix are never looked at: they are not even copied; pageable host memory: the runtime
-    // stages it before the call returns)
-    if (n_eff) {
-      HIP_TRY(hipMemcpyAsync(s->grouped.dLabels.p, group_of, n_eff * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-      HIP_TRY(hipMemcpyAsync(s->labeled.dCol.p, label_of, n_eff * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    }
+  const uint64_t n_eff = label_col >= 0 ? n_pub : std::min<uint64_t>(n_labels, n_pub);
+  LabelCall c = {label_of, cols_on_host, label_col, n_eff, want, d_want};
+  // routing: the grouped search's under bitmaps (ehx_groupedm.cpp), applied by the plan before it fills the lists
+  c.scan_serves = grouped_scan_serves(s, n_eff);
+  c.cut = masked_exact_cut(n_pub);
+  c.min_scan_queries = kLargeKMinQueries;
+  c.fits = grouped_check_ld;
+  c.ctr = s->groupedl_ctr;
+  const uint32_t* d_group_of = group_of;
+  auto stage = [&]() -> int {   // the group column: a stored one resolved, a host one staged
+    if (label_col >= 0) return column_as_groups(s, st, (uint32_t)group_col, n_pub, &d_group_of);
+    if (!cols_on_host) return EHX_OK;
+    if (int rc = s->grouped.dLabels.ensure(std::max<uint64_t>(n_eff, 1))) return rc;
+    // (as labeled_call stages the label column: the prefix alone, pageable host memory)
+    if (n_eff) HIP_TRY(hipMemcpyAsync(s->grouped.dLabels.p, group_of, n_eff * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     d_group_of = s->grouped.dLabels.p;
-    d_label_of = s->labeled.dCol.p;
-  }
-  std::vector<uint32_t> want_read;
-  if (!want) {
-    want_read.resize(nq);
-    HIP_TRY(hipMemcpyAsync(want_read.data(), d_want, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    want = want_read.data();
-  }
-  bool col_copied = false;
-  for (size_t q0 = 0; q0 < nq; q0 += kSideChunk) {
-    const size_t m = std::min(kSideChunk, nq - q0);
-    if ((rc = groupedl_batch(s, st, n_pub, n_eff, m, d_queries + q0 * s->dims, k, per_group, d_group_of, d_label_of, ix,
-                             want + q0, &col_copied, out.from(q0, m))))
-      return rc;
-  }
-  return EHX_OK;
+    return EHX_OK;
+  };
+  return labeled_call(s, st, n_pub, nq, c, stage, [&](size_t q0, size_t m, FilterView& v) {
+    return grouped_answer(s, st, m, d_queries + q0 * s->dims, k, per_group, d_group_of, v, out.from(q0, m));
+  });
 }
 
 }  // namespace

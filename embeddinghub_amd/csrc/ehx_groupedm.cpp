@@ -8,9 +8,8 @@
 //   compaction   the bitmap search's (masked_plan, ehx_masked.cpp) at min(n_bits, n_labels) bits: the row count read once,
 //                the bitmaps on the device, every mask's number of allowed rows and its ascending list, mask_of checked;
 //                bitmaps that cover no row compact to nothing: every query's range is empty, its page still written
-//   routing      per mask: it scans iff it allows more than masked_exact_cut(rows) rows on a flat space with plain rows
-//                whose int8 scan serves a radius on the prefix — and at least kLargeKMinQueries queries name such masks
-//                (fewer than one query tile of the int8 wave tile: the list route for all)
+//   routing      per mask, the one rule (filter_routes_cut / _gate, ehx_masked.cpp): grouped_scan_serves on the prefix, the
+//                cut masked_exact_cut(rows), the gate kLargeKMinQueries (one query tile of the int8 wave tile)
 //   the flush    the batch's one bitmap, or a bitmap per query through the offset words at the head of masked.dBlock
 // Entry scaffold, host staging: ehx_call.cpp's (search_on_device, HostStage).
 #include "ehx_internal.h"
@@ -60,33 +59,12 @@ int groupedm_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_quer
     if (n_eff) HIP_TRY(hipMemcpyAsync(s->grouped.dLabels.p, group_of, n_eff * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     d_group_of = s->grouped.dLabels.p;
   }
-  const uint32_t n_masks = p.n_masks;
-  const bool per_query = n_masks > 1;   // one mask: the batch's ONE bitmap in the flush, no offsets
   // routing per mask; fewer scanning queries than one query tile of the int8 wave tile: the list route for all
-  const bool scan_serves = s->params.mode != EHX_MODE_GRAPH && !s->x_perm && n_eff > 0 && i8_serves_radius(s, n_eff);
   char scans[kMaskedMaxMasks];
-  uint32_t head_of[kMaskedMaxMasks];   // the word offset of every bitmap in the block
-  for (uint32_t m = 0; m < n_masks; ++m) {
-    scans[m] = scan_serves && p.n_allowed[m] > masked_exact_cut(p.n_pub);
-    head_of[m] = (uint32_t)(kTabWords + (uint64_t)m * p.words);
-  }
-  size_t n_scan = 0;
-  for (size_t i = 0; i < nq; ++i) n_scan += scans[p.mask_of ? p.mask_of[i] : 0u];
-  if (n_scan < kLargeKMinQueries)
-    for (uint32_t m = 0; m < n_masks; ++m) scans[m] = 0;
-  FilterView v;
-  v.n_pub = p.n_pub;
-  v.n_eff = n_eff;
-  v.n_filters = n_masks;
-  v.n_allowed = p.n_allowed.data();
-  v.off = p.off.off;
-  v.filter_of = p.mask_of;
-  v.scans = scans;
-  v.d_list = s->masked.dList.p;
-  v.allow = per_query ? s->masked.dBlock.p : p.d_maps;
-  v.allow_per_query = per_query;
-  v.d_head = per_query ? s->masked.dBlock.p : nullptr;
-  v.head_of = head_of;
+  uint32_t head_of[kMaskedMaxMasks];
+  filter_routes_cut(grouped_scan_serves(s, n_eff), masked_exact_cut(p.n_pub), p.n_allowed.data(), p.n_masks, scans);
+  filter_routes_gate(p.mask_of, nq, kLargeKMinQueries, p.n_masks, scans);
+  FilterView v = masked_view(s, st, p, scans, head_of);
   v.ctr = s->groupedm_ctr;
   return grouped_answer(s, st, nq, d_queries, k, per_group, d_group_of, v, out);
 }

@@ -1085,6 +1085,16 @@ struct FilterView {
   std::atomic<uint64_t>* ctr = nullptr;  // [5] scan route, list route, overflowed, scan passes, calls (the caller counts calls)
 };
 bool filter_scan_serves(const ehx_space* s, uint32_t k, uint64_t n_pub);   // the scan route serves this k on this prefix
+// THE route of a filter in every filtered search, in two steps (colindex_plan restricts the scanning filters between them);
+// the caller says which scan_serves, which cut (masked_exact_cut, or a forced 0 / ~0) and which gate (0, kLargeKMinQueries).
+//   cut    scans[f] = scan_serves && n_allowed[f] > cut
+//   gate   min_scan_queries > 0 and fewer queries name scanning filters (all of them together): none scans; filter_of ==
+//          nullptr: every query is filter 0
+void filter_routes_cut(bool scan_serves, uint64_t cut, const uint64_t* n_allowed, uint32_t n_filters, char* scans);
+void filter_routes_gate(const uint32_t* filter_of, size_t nq, size_t min_scan_queries, uint32_t n_filters, char* scans);
+// The view over a plan of bitmaps, every field but ctr.  It BORROWS p, scans[p.n_masks] (the caller's routes) and
+// head_of[p.n_masks] (the caller's storage, filled here): all three outlive it.  st: where v.samples() enqueues.
+FilterView masked_view(ehx_space* s, hipStream_t st, const MaskedPlan& p, const char* scans, uint32_t* head_of);
 int filtered_answer(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, const FilterView& v,
                     const ResultBlock& out);
 
@@ -1093,6 +1103,8 @@ int filtered_answer(ehx_space* s, hipStream_t st, size_t nq, const float* d_quer
 int grouped_check_head(const ehx_space* s, size_t nq, uint32_t k, uint32_t per_group, const void* q, const void* group_of,
                        uint64_t n_labels, const void* o_ids, const void* o_dist, const void* o_cnt);
 int grouped_check_ld(const ehx_space* s);   // rows wider than grouped_rerank_max_ld() floats: EHX_EUNSUPPORTED
+// the grouped scan route serves a prefix of n_eff rows: a flat space with plain rows whose int8 scan serves a radius on it
+bool grouped_scan_serves(const ehx_space* s, uint64_t n_eff);
 // The grouped list route, any space kind: query j over d_list[range[j], range[nq + j]) (range: host memory; d_list ==
 // nullptr: the identity list, the range is of row ids), in slabs of kPoolCap.  count_queries: its queries are not in
 // n_queries yet.
@@ -1120,8 +1132,6 @@ struct LabeledPlan {
   std::vector<uint32_t> scan_of;          // [n_slots] the slot's row of cum (kLabeledNoScan: it does not scan)
   std::vector<uint32_t> cum;              // [n_scan][n_tiles + 1]
 };
-// the scratch labeled_plan fills, sized for a prefix of n_eff rows (once per call, before anything is enqueued)
-int labeled_plan_scratch(ehx_space* s, uint64_t n_eff);
 // an unsharded space, locked shared, scratch_mu held, its device current, `st` ordered behind the searches in flight;
 // everything is enqueued on `st`.  m <= kSideChunk queries under want[0, m) (host memory) over d_label_of[0, n_eff).  Waits
 // once for the counts, and a second time — for the tile prefixes — only where some slot scans.  A slot scans iff scan_serves
@@ -1132,11 +1142,29 @@ int labeled_plan(ehx_space* s, hipStream_t st, uint64_t n_eff, size_t m, const u
 
 // the slots of a device batch: p->table (the distinct wanted labels, ascending), p->n_slots, p->slot_of
 void labeled_slots(const uint32_t* want, size_t m, LabeledPlan* p);
-// ehx_knn_labeled*'s body (label_col < 0) and ehx_knn_by_label*'s (the stored column label_col, d_label_of unused, n_labels the
-// snapshot): an unsharded space, locked shared, scratch_mu held, its device current
-int labeled_locked(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, const float* d_queries, uint32_t k,
-                   const uint32_t* d_label_of, uint64_t n_labels, const uint32_t* want, const uint32_t* d_want,
-                   const ResultBlock& out, int label_col = -1);
+// The view over a device batch's plan, every field but ctr; ix: the plan was read from a stored column's index (lists, tile
+// prefixes, samples and the flush's block are the index's).  It BORROWS p and *ix: both outlive it.  st: as masked_view's.
+FilterView labeled_view(ehx_space* s, hipStream_t st, uint64_t n_pub, uint64_t n_eff, const LabeledPlan& p,
+                        const ehx_space::ColIndex* ix);
+// How a call under a label column names its column and its wanted labels, and what its search passes the plan.
+struct LabelCall {
+  const uint32_t* label_of;   // the column on the device, or with on_host in host memory (staged in labeled.dCol); unused
+  bool on_host;               // with label_col >= 0: the space's stored column of that number
+  int label_col;
+  uint64_t n_labels;          // entries of the column (a stored one: the row count's snapshot)
+  const uint32_t *want, *d_want;   // [queries] host memory; or device memory, read back once (the call's one wait for it)
+  bool scan_serves = false;   // labeled_plan's routing inputs
+  uint64_t cut = 0;
+  size_t min_scan_queries = 0;
+  int (*fits)(const ehx_space*) = nullptr;   // refuses rows the search cannot hold
+  std::atomic<uint64_t>* ctr = nullptr;      // [5] FilterView's
+};
+// The body of every call under a label column (an unsharded space, locked shared, scratch_mu held, its device current;
+// everything is enqueued on `st`; n_pub: the call's ONE read of the row count): poison check, c.fits, the calls counter, the
+// plan's scratch, `st` ordered behind the searches in flight, a stored column's index, stage() (may be empty), a host column
+// staged, d_want read back; then per device batch [q0, q0 + m) the plan, its view (ctr set) and batch(q0, m, view).
+int labeled_call(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, const LabelCall& c, const std::function<int()>& stage,
+                 const std::function<int(size_t, size_t, FilterView&)>& batch);
 
 // ---- ehx_columns.cpp ----
 struct WriteBatch;

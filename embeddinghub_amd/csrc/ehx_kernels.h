@@ -548,8 +548,9 @@ hipError_t launch_range_scan_radii(const float* radius, const uint32_t* scans, u
 // bitmap m starts at maps + m * stride words, stride >= ceil(n_bits / 32); ONE bitmap is used where it lies, the stride
 // never applied.  cum: [n_masks][n_tiles + 1], allowed rows before every tile, the last entry their number.  Counts and
 // prefixes first (the host reads them back and places the lists), then the ascending lists of allowed row ids — mask m's at
-// list + off[m].  launch_masked_samples, for the scan route: every mask's sample of at most 256 ids by rank, stride
-// ceil(allowed / 256), at sample + 256 m.
+// list + off[m].  launch_masked_samples, for the scan route: every mask's sample of at most 256 ids by rank (write_sample,
+// below), at sample + 256 m.  launch_rows_prefix: `rows` rows of n + 1 words, cum[row][0 .. n) counts -> their exclusive prefix
+// in place, cum[row][n] the total (rows or n zero: nothing is launched); launch_labeled_tiles and launch_colindex_bounds use it.
 constexpr uint32_t kMaskedMaxMasks = 64;
 struct MaskedOffsets {
   uint64_t off[kMaskedMaxMasks];
@@ -560,6 +561,7 @@ hipError_t launch_masked_fill(const uint32_t* maps, uint64_t stride, uint32_t n_
                               const uint32_t* cum, const MaskedOffsets& off, uint64_t* list, hipStream_t st);
 hipError_t launch_masked_samples(const uint64_t* list, const MaskedOffsets& off, const uint32_t* cum, uint32_t n_masks,
                                  uint32_t n_tiles, uint64_t* sample, hipStream_t st);
+hipError_t launch_rows_prefix(uint32_t* cum, uint32_t rows, uint32_t n, hipStream_t st);
 // exact kNN under a label column (k_labeled.hip; ehx_knn_labeled*): compaction of the rows [0, n_rows) by label, for the
 // n_slots <= kLabeledMaxSlots distinct wanted labels of one device batch (table: ascending, in device memory).
 //   launch_labeled_count   slot_of[r] = the slot of row r's label (kLabeledNoSlot: nobody wants it), count[slot] += 1
@@ -569,7 +571,7 @@ hipError_t launch_masked_samples(const uint64_t* list, const MaskedOffsets& off,
 //                          (the layout masked_passes reads)
 //   launch_labeled_fill    every slot's list of row ids at list + off[slot]: ascending for the slots that scan (placed by
 //                          cum), in any order for the others (placed by a cursor per slot: cursor[n_slots], cleared here)
-//   launch_labeled_samples sample[256 scan + i] = the i-th of every ceil(rows / 256)-th id of a scanning slot's list by rank
+//   launch_labeled_samples sample[256 scan + i] = the i-th of every sample_stride(rows)-th id of a scanning slot's list by rank
 //                          (scan_off[scan]: where its list starts)
 constexpr uint32_t kLabeledMaxSlots = 2048;   // the queries of one device batch (kSideChunk)
 constexpr uint32_t kLabeledMaxScan = 127;     // labels of more than max(1024, n / 128) rows: n / max(1024, n / 128) <= 128, strictly below
@@ -592,7 +594,7 @@ hipError_t launch_labeled_samples(const uint64_t* list, const uint64_t* scan_off
 //   launch_colindex_bounds  sorted keys (vals nullptr: the identity) -> labels[L], start[L + 1], perm[n] (64-bit row ids);
 //                           bbase: scratch of n / 256 + 2 words, its entry [ceil(n / 256)] = L when the launches have run
 //   launch_colindex_heavy   run: [n_heavy] starts | [n_heavy] ends in perm of the labels that may scan (ascending row ids
-//                           inside each) -> cum[n_heavy][n_tiles + 1] rows before every 256-row tile (labeled_prefix_kernel's
+//                           inside each) -> cum[n_heavy][n_tiles + 1] rows before every 256-row tile (rows_prefix_kernel's
 //                           layout), sample[n_heavy][256] by rank
 //   launch_column_scatter   col[dst_row[i]] = values[i] where dst_row[i] < cap (~0: skipped); launch_column_gather the reverse
 constexpr uint32_t kColIndexTile = 4096;
@@ -638,6 +640,13 @@ __device__ __forceinline__ uint32_t mask_word(const uint32_t* __restrict__ mask,
   const uint64_t left = n_bits - lo;
   if (left < 32) v &= (1u << (uint32_t)left) - 1u;
   return v;
+}
+// The sample of a compacted filter: entry i is list[i * sample_stride(rows)] while that is below rows, at most 256.  Stated
+// ONCE: the three sample kernels write it (256 lanes, one entry each), filtered_answer sizes the list scan over it.
+__host__ __device__ inline uint64_t sample_stride(uint64_t rows) { return (rows + 255u) / 256u; }
+__device__ __forceinline__ void write_sample(const uint64_t* __restrict__ list, uint64_t rows, uint64_t* __restrict__ sample) {
+  const uint64_t i = threadIdx.x * sample_stride(rows);
+  if (i < rows) sample[threadIdx.x] = list[i];
 }
 
 // exact kNN on the int8 radius scan under a radius that falls (k_radius.hip): the bitmap search's scan route (k <= 48) and

@@ -21,9 +21,10 @@
 // The device form waits once for d_want (the whole call's), then per device batch at most twice for the compaction — the
 // counts, and the scanning slots' tile prefixes — whatever the number of labels the batch names; the scan route's verdict is
 // radius_knn's one wait per device batch, as under bitmaps.
-// The compaction is a plan (LabeledPlan, labeled_plan: ehx_internal.h) that the grouped search under a label column
-// (ehx_groupedl.cpp) shares; the two callers' routing differs in what they pass it — whether the scan route serves the call,
-// and how many queries of the batch must name scanning slots (none here).
+// The compaction is a plan (LabeledPlan, labeled_plan), the view over it labeled_view, and the body of a call — checks,
+// scratch, waits, staging, the loop over device batches — labeled_call (all in ehx_internal.h): the grouped search under a
+// label column (ehx_groupedl.cpp) shares the three and differs in what it passes (LabelCall: whether the scan route serves,
+// the cut, the gate — none here) and in what answers a device batch.  A slot's route: filter_routes_cut / _gate (ehx_masked.cpp).
 // Entry scaffold and host staging are ehx_call.cpp's (search_shared / on_device, HostStage).
 #include "ehx_internal.h"
 
@@ -58,7 +59,8 @@ int by_label_check(const ehx_space* s, size_t nq, uint32_t k, const void* q, uin
 
 namespace ehx_impl {
 
-int labeled_plan_scratch(ehx_space* s, uint64_t n_eff) {
+// the scratch labeled_plan fills, sized for a prefix of n_eff rows (once per call, before anything is enqueued)
+static int labeled_plan_scratch(ehx_space* s, uint64_t n_eff) {
   ehx_space::Labeled& w = s->labeled;
   int rc;
   if ((rc = w.dBlock.ensure(kLabelHead + std::max<uint64_t>(n_eff, 1))) || (rc = w.dSlotOf.ensure(std::max<uint64_t>(n_eff, 1))) ||
@@ -101,26 +103,21 @@ int labeled_plan(ehx_space* s, hipStream_t st, uint64_t n_eff, size_t m, const u
     HIP_TRY(hipMemcpyAsync(count.data(), d_count, n_slots * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));   // the first wait
   }
-  // routing per slot (the bitmap search's rule; with min_scan_queries the grouped search's gate on top of it), decided
-  // BEFORE the lists are filled: where the lists start, and the scanning slots' indices
+  // routing per slot (filter_routes: the bitmap search's rule; with min_scan_queries the grouped search's gate on top of it),
+  // decided BEFORE the lists are filled: where the lists start, and the scanning slots' indices
+  std::vector<uint64_t>& n_allowed = p->n_allowed;
+  n_allowed.assign(count.begin(), count.end());
   std::vector<char>& scans = p->scans;
   scans.assign(n_slots, 0);
-  for (uint32_t f = 0; f < n_slots; ++f) scans[f] = scan_serves && count[f] > cut;
-  if (min_scan_queries) {
-    size_t naming = 0;
-    for (size_t j = 0; j < m; ++j) naming += scans[p->slot_of[j]] != 0;
-    if (naming < min_scan_queries) scans.assign(n_slots, 0);
-  }
-  std::vector<uint64_t>& n_allowed = p->n_allowed;
+  filter_routes_cut(scan_serves, cut, n_allowed.data(), n_slots, scans.data());
+  filter_routes_gate(p->slot_of.data(), m, min_scan_queries, n_slots, scans.data());
   std::vector<uint64_t>& off = p->off;
   std::vector<uint64_t> scan_off;
-  n_allowed.assign(n_slots, 0);
   off.assign(n_slots, 0);
   std::vector<uint32_t>& scan_of = p->scan_of;
   scan_of.assign(n_slots, kLabeledNoScan);
   uint64_t total = 0;
   for (uint32_t f = 0; f < n_slots; ++f) {
-    n_allowed[f] = count[f];
     off[f] = total;
     total += count[f];
     if (!scans[f]) continue;
@@ -159,28 +156,17 @@ int labeled_plan(ehx_space* s, hipStream_t st, uint64_t n_eff, size_t m, const u
 
 }  // namespace ehx_impl
 
-namespace {
+namespace ehx_impl {
 
-// One device batch of m <= kSideChunk queries under want[0, m) (host memory) over the prefix of n_eff rows of d_label_of:
-// the plan, its view, the bitmap search's answer.  ix: the plan is read from a stored column's fresh index instead
-// (colindex_plan: no launch, no wait) — its lists are runs of the index's permutation, its tile prefixes, samples and the
-// flush's block the index's own.
-int labeled_batch(ehx_space* s, hipStream_t st, uint64_t n_pub, uint64_t n_eff, size_t m, const float* d_queries, uint32_t k,
-                  const uint32_t* d_label_of, const ehx_space::ColIndex* ix, const uint32_t* want, bool* col_copied,
-                  const ResultBlock& out) {
+FilterView labeled_view(ehx_space* s, hipStream_t st, uint64_t n_pub, uint64_t n_eff, const LabeledPlan& p,
+                        const ehx_space::ColIndex* ix) {
   ehx_space::Labeled& w = s->labeled;
   ehx_space::Masked& mw = s->masked;
-  const uint32_t forced = s->labeled_route.load(std::memory_order_relaxed);   // (test hook: the bench's crossover sweep)
-  const uint64_t cut = forced == 1 ? 0 : forced == 2 ? ~0ull : masked_exact_cut(n_pub);
-  LabeledPlan p;
-  if (ix) colindex_plan(*ix, m, want, filter_scan_serves(s, k, n_pub), cut, 0, &p);
-  else if (int rc = labeled_plan(s, st, n_eff, m, d_label_of, want, filter_scan_serves(s, k, n_pub), cut, 0, col_copied, &p)) return rc;
-  const uint32_t n_tiles = p.n_tiles, n_scan = p.n_scan;
   FilterView v;
   v.n_pub = n_pub;
   v.n_eff = n_eff;
   v.list_rows = p.total;
-  v.n_tiles = n_tiles;
+  v.n_tiles = p.n_tiles;
   v.n_filters = p.n_slots;
   v.n_allowed = p.n_allowed.data();
   v.off = p.off.data();
@@ -190,10 +176,11 @@ int labeled_batch(ehx_space* s, hipStream_t st, uint64_t n_pub, uint64_t n_eff, 
   v.scan_of = p.scan_of.data();
   v.d_list = ix ? ix->dPerm.p : mw.dList.p;
   v.sample = ix ? &ix->dSample : &mw.dSample;
-  v.samples = [&]() -> int {
+  v.samples = [s, st, &p, ix]() -> int {
     if (ix) return EHX_OK;   // (prepared when the index was built)
-    if (int r = mw.dSample.ensure((size_t)n_scan * 256)) return r;
-    HIP_TRY(launch_labeled_samples(mw.dList.p, w.dOff.p + kLabeledMaxSlots, mw.dCum.p, n_scan, n_tiles, mw.dSample.p, st));
+    ehx_space::Masked& m = s->masked;
+    if (int r = m.dSample.ensure((size_t)p.n_scan * 256)) return r;
+    HIP_TRY(launch_labeled_samples(m.dList.p, s->labeled.dOff.p + kLabeledMaxSlots, m.dCum.p, p.n_scan, p.n_tiles, m.dSample.p, st));
     return EHX_OK;
   };
   v.allow = v.d_head = ix ? ix->dBlock.p : w.dBlock.p;
@@ -201,43 +188,71 @@ int labeled_batch(ehx_space* s, hipStream_t st, uint64_t n_pub, uint64_t n_eff, 
   v.head_of = p.table.data();   // (the head word of a query is its wanted label itself)
   v.shared_min = kLabeledSharedMin;
   v.d_range = &w.dRange;
-  v.ctr = s->labeled_ctr;
-  return filtered_answer(s, st, m, d_queries, k, v, out);
+  return v;
 }
 
-}  // namespace
-
-// an unsharded space, locked shared, scratch_mu held, its device current; everything is enqueued on `st`.  want: in host
-// memory; or d_want, read back once (the outputs unwritten until then).
-int ehx_impl::labeled_locked(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, const float* d_queries, uint32_t k,
-                             const uint32_t* d_label_of, uint64_t n_labels, const uint32_t* want, const uint32_t* d_want,
-                             const ResultBlock& out, int label_col) {
+int labeled_call(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, const LabelCall& c, const std::function<int()>& stage,
+                 const std::function<int(size_t, size_t, FilterView&)>& batch) {
   int rc;
   if ((rc = check_not_poisoned(s))) return rc;
-  if ((rc = check_rows_fit_lds(s, "filtered search"))) return rc;   // (before anything is enqueued)
-  s->labeled_ctr[4] += 1;
-  const uint64_t n_eff = std::min<uint64_t>(n_labels, n_pub);   // (row ids are 32 bits wide: n_pub < 2^32)
-  if (label_col < 0 && (rc = labeled_plan_scratch(s, n_eff))) return rc;
-  // (earlier calls' launches on other streams may still read the block, the lists and the samples)
+  if ((rc = c.fits(s))) return rc;   // (before anything is enqueued)
+  c.ctr[4] += 1;
+  const bool stored = c.label_col >= 0;
+  const uint64_t n_eff = std::min<uint64_t>(c.n_labels, n_pub);   // (row ids are 32 bits wide: n_pub < 2^32)
+  if (!stored && (rc = labeled_plan_scratch(s, n_eff))) return rc;
+  // (earlier calls' launches on other streams may still read the block, the lists, the samples and the staged columns)
   if ((rc = wait_searches_in_flight(s, st))) return rc;
   const ehx_space::ColIndex* ix = nullptr;   // a stored column: its index, rebuilt here if a write or an append left it stale
-  if (label_col >= 0 && (rc = colindex_ensure(s, st, (uint32_t)label_col, n_pub, &ix))) return rc;
+  if (stored && (rc = colindex_ensure(s, st, (uint32_t)c.label_col, n_pub, &ix))) return rc;
+  if (stage && (rc = stage())) return rc;
+  const uint32_t* d_label_of = c.label_of;
+  if (c.on_host) {
+    // (labels at or above the prefix are never looked at: they are not even copied; pageable host memory: the runtime stages
+    // it before the call returns)
+    if ((rc = s->labeled.dCol.ensure(std::max<uint64_t>(n_eff, 1)))) return rc;
+    if (n_eff) HIP_TRY(hipMemcpyAsync(s->labeled.dCol.p, c.label_of, n_eff * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    d_label_of = s->labeled.dCol.p;
+  }
+  const uint32_t* want = c.want;
   std::vector<uint32_t> want_read;
   if (!want) {
     want_read.resize(nq);
-    HIP_TRY(hipMemcpyAsync(want_read.data(), d_want, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(want_read.data(), c.d_want, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     want = want_read.data();
   }
   bool col_copied = false;
   for (size_t q0 = 0; q0 < nq; q0 += kSideChunk) {
     const size_t m = std::min(kSideChunk, nq - q0);
-    if ((rc = labeled_batch(s, st, n_pub, n_eff, m, d_queries + q0 * s->dims, k, d_label_of, ix, want + q0, &col_copied,
-                            out.from(q0, m))))
+    LabeledPlan p;
+    if (ix) colindex_plan(*ix, m, want + q0, c.scan_serves, c.cut, c.min_scan_queries, &p);
+    else if ((rc = labeled_plan(s, st, n_eff, m, d_label_of, want + q0, c.scan_serves, c.cut, c.min_scan_queries, &col_copied, &p)))
       return rc;
+    FilterView v = labeled_view(s, st, n_pub, n_eff, p, ix);
+    v.ctr = c.ctr;
+    if ((rc = batch(q0, m, v))) return rc;
   }
   return EHX_OK;
 }
+
+}  // namespace ehx_impl
+
+namespace {
+
+// ehx_knn_labeled* and ehx_knn_by_label* over labeled_call: the kNN's routing inputs, filtered_answer per device batch
+int labeled_locked(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, const float* d_queries, uint32_t k, LabelCall c,
+                   const ResultBlock& out) {
+  const uint32_t forced = s->labeled_route.load(std::memory_order_relaxed);   // (test hook: the bench's crossover sweep)
+  c.scan_serves = filter_scan_serves(s, k, n_pub);
+  c.cut = forced == 1 ? 0 : forced == 2 ? ~0ull : masked_exact_cut(n_pub);
+  c.fits = [](const ehx_space* sp) { return check_rows_fit_lds(sp, "filtered search"); };
+  c.ctr = s->labeled_ctr;
+  return labeled_call(s, st, n_pub, nq, c, nullptr, [&](size_t q0, size_t m, FilterView& v) {
+    return filtered_answer(s, st, m, d_queries + q0 * s->dims, k, v, out.from(q0, m));
+  });
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -250,7 +265,7 @@ int ehx_knn_labeled_device(ehx_space* s, void* stream, size_t n_queries, const f
   return search_on_device(s, "ehx_knn_labeled_device", kLabeledWhy, n_queries, &st, [&] {
     // the ONE read of the row count: the lists name rows below it only, and every later stage sees at least this prefix
     const uint64_t n_pub = s->n.load(std::memory_order_acquire);
-    return labeled_locked(s, st, n_pub, n_queries, d_queries, k, d_label_of, n_labels, nullptr, d_want,
+    return labeled_locked(s, st, n_pub, n_queries, d_queries, k, LabelCall{d_label_of, false, -1, n_labels, nullptr, d_want},
                           ResultBlock{d_out_ids, d_out_dist, d_out_count, nullptr, n_queries, k});
   });
 }
@@ -261,13 +276,11 @@ int ehx_knn_labeled(ehx_space* s, size_t n_queries, const float* queries, uint32
   return search_on_device(s, "ehx_knn_labeled", kLabeledWhy, n_queries, nullptr, [&]() -> int {
     int rc;
     const uint64_t n_pub = s->n.load(std::memory_order_acquire);   // the ONE read of the row count
-    // (labels at or above it are never looked at: they are not even copied)
-    const uint64_t n_eff = std::min<uint64_t>(n_labels, n_pub);
     HostStage& h = s->labeled.host;
-    if ((rc = s->labeled.dCol.ensure(std::max<uint64_t>(n_eff, 1))) || (rc = h.up(s->stream, queries, n_queries, s->dims, k, false)))
+    if ((rc = h.up(s->stream, queries, n_queries, s->dims, k, false))) return rc;
+    // (the column is staged in labeled.dCol by the body, behind its wait for the searches in flight)
+    if ((rc = labeled_locked(s, s->stream, n_pub, n_queries, h.q, k, LabelCall{label_of, true, -1, n_labels, want, nullptr}, h.out)))
       return rc;
-    if (n_eff) HIP_TRY(hipMemcpyAsync(s->labeled.dCol.p, label_of, n_eff * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
-    if ((rc = labeled_locked(s, s->stream, n_pub, n_queries, h.q, k, s->labeled.dCol.p, n_labels, want, nullptr, h.out))) return rc;
     return h.out.copy_out(s->stream, out_ids, out_dist, out_count, nullptr);
   });
 }
@@ -279,8 +292,8 @@ int ehx_knn_by_label_device(ehx_space* s, void* stream, size_t n_queries, const 
   return search_on_device(s, "ehx_knn_by_label_device", kLabeledWhy, n_queries, &st, [&] {
     const uint64_t n_pub = s->n.load(std::memory_order_acquire);   // the ONE read of the row count
     test_pause();   // (an append may publish here: the index and every stage describe n_pub rows all the same)
-    return labeled_locked(s, st, n_pub, n_queries, d_queries, k, nullptr, n_pub, nullptr, d_want,
-                          ResultBlock{d_out_ids, d_out_dist, d_out_count, nullptr, n_queries, k}, (int)label_col);
+    return labeled_locked(s, st, n_pub, n_queries, d_queries, k, LabelCall{nullptr, false, (int)label_col, n_pub, nullptr, d_want},
+                          ResultBlock{d_out_ids, d_out_dist, d_out_count, nullptr, n_queries, k});
   });
 }
 
@@ -293,7 +306,9 @@ int ehx_knn_by_label(ehx_space* s, size_t n_queries, const float* queries, uint3
     test_pause();
     HostStage& h = s->labeled.host;   // (queries up, results down: no column travels)
     if ((rc = h.up(s->stream, queries, n_queries, s->dims, k, false))) return rc;
-    if ((rc = labeled_locked(s, s->stream, n_pub, n_queries, h.q, k, nullptr, n_pub, want, nullptr, h.out, (int)label_col))) return rc;
+    if ((rc = labeled_locked(s, s->stream, n_pub, n_queries, h.q, k, LabelCall{nullptr, false, (int)label_col, n_pub, want, nullptr},
+                             h.out)))
+      return rc;
     return h.out.copy_out(s->stream, out_ids, out_dist, out_count, nullptr);
   });
 }

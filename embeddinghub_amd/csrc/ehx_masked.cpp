@@ -27,7 +27,8 @@
 //                allowed rows in a pass than it would alone.  The queries it hands on — pool overflow, or the bound does
 //                not serve them — take the exact route under their own mask.
 // The plan, the cut between the routes and the check of mask_of are declared in ehx_internal.h: the range search under row
-// bitmaps (ehx_rangem.cpp) compacts its table with the same masked_plan.
+// bitmaps (ehx_rangem.cpp) compacts its table with the same masked_plan.  So are THE routing rule of every filtered
+// search (filter_routes_cut / _gate) and the view over a plan of bitmaps (masked_view: ehx_groupedm.cpp's too).
 // n_masks <= kMaskedMaxMasks = 64: a choice (include/ehx.h says why), not a knob.
 // Entry scaffold and host staging are ehx_call.cpp's (search_shared / on_device, HostStage).
 #include "ehx_internal.h"
@@ -35,7 +36,7 @@
 namespace {
 
 constexpr uint32_t kMaskedScanMaxK = 48;    // the scan route carries <= k keys per query between passes: the certified engines' k
-constexpr uint64_t kMaskedSample = 256;     // allowed rows in the sample, at most
+constexpr uint64_t kMaskedSample = 256;     // allowed rows in the sample, at most (sample_stride, ehx_kernels.h)
 constexpr uint64_t kMaskedPassGrowth = 16;  // pass j ends where kMaskedSample * 16^j allowed rows have been seen
 constexpr const char* kMaskedWhy = "filtered search over shards is not built yet";
 static_assert(kSideChunk % 256 == 0, "the offset table covers the padded query rows of one device batch");
@@ -178,6 +179,46 @@ bool filter_scan_serves(const ehx_space* s, uint32_t k, uint64_t n_pub) {
   return k <= kMaskedScanMaxK && i8_serves_radius(s, n_pub);
 }
 
+void filter_routes_cut(bool scan_serves, uint64_t cut, const uint64_t* n_allowed, uint32_t n_filters, char* scans) {
+  for (uint32_t f = 0; f < n_filters; ++f) scans[f] = scan_serves && n_allowed[f] > cut;
+}
+
+void filter_routes_gate(const uint32_t* filter_of, size_t nq, size_t min_scan_queries, uint32_t n_filters, char* scans) {
+  if (!min_scan_queries || !n_filters) return;
+  size_t naming = 0;
+  for (size_t i = 0; i < nq; ++i) naming += scans[filter_of ? filter_of[i] : 0u] != 0;
+  if (naming < min_scan_queries) std::fill(scans, scans + n_filters, (char)0);
+}
+
+FilterView masked_view(ehx_space* s, hipStream_t st, const MaskedPlan& p, const char* scans, uint32_t* head_of) {
+  ehx_space::Masked& w = s->masked;
+  const bool per_query = p.n_masks > 1;   // one mask: the batch's ONE bitmap in the flush, nothing grouped, no offsets
+  for (uint32_t m = 0; m < p.n_masks; ++m) head_of[m] = (uint32_t)(kTabWords + (uint64_t)m * p.words);
+  FilterView v;
+  v.n_pub = p.n_pub;
+  v.n_eff = p.n_eff;
+  v.n_tiles = p.n_tiles;
+  v.n_filters = p.n_masks;
+  v.n_allowed = p.n_allowed.data();
+  v.off = p.off.off;
+  v.filter_of = p.mask_of;
+  v.scans = scans;
+  v.cum = p.cum.data();
+  v.d_list = w.dList.p;
+  v.sample = &w.dSample;
+  v.allow = per_query ? w.dBlock.p : p.d_maps;
+  v.allow_per_query = per_query;
+  v.d_head = per_query ? w.dBlock.p : nullptr;
+  v.head_of = head_of;
+  v.samples = [s, st, &p]() -> int {
+    ehx_space::Masked& m = s->masked;
+    if (int r = m.dSample.ensure((size_t)p.n_masks * kMaskedSample)) return r;
+    HIP_TRY(launch_masked_samples(m.dList.p, p.off, m.dCum.p, p.n_masks, p.n_tiles, m.dSample.p, st));
+    return EHX_OK;
+  };
+  return v;
+}
+
 // The exact answer over compacted row filters — bitmaps (masked_answer, below) or the labels of a column (ehx_labeled.cpp):
 // per filter the scan route where v.scans says so, else the list scan.  Only the row test in the scan's flush (v.allow*), the
 // table the compaction filled and the counters differ between the two.
@@ -247,7 +288,7 @@ int filtered_answer(ehx_space* s, hipStream_t st, size_t nq, const float* d_quer
         }
         for (size_t b = q0; b < q0 + m;) {
           const size_t e = run_end(b, q0 + m), j = b - q0;
-          const uint64_t a = v.n_allowed[gm[b]], stride = (a + kMaskedSample - 1) / kMaskedSample;
+          const uint64_t a = v.n_allowed[gm[b]], stride = sample_stride(a);
           if (int r = among_locked(s, st, e - b, q + j * s->dims, k, v.sample->p + row_of(gm[b]) * kMaskedSample, nullptr,
                                    (size_t)((a + stride - 1) / stride), 0, o.ids + j * k, o.dist + j * k, o.cnt + j, false))
             return r;
@@ -322,37 +363,10 @@ namespace {
 // the exact answer over a plan of bitmaps: filtered_answer with the bitmap — the batch's ONE, or one per query — in the flush
 int masked_answer(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, const MaskedPlan& p,
                   const ResultBlock& out) {
-  ehx_space::Masked& w = s->masked;
-  const uint32_t n_masks = p.n_masks;
-  const bool per_query = n_masks > 1;   // one mask: the batch's ONE bitmap in the flush, nothing grouped, no offsets
-  const bool scan_serves = filter_scan_serves(s, k, p.n_pub);
-  std::vector<char> scans(n_masks);
-  std::vector<uint32_t> head_of(per_query ? n_masks : 0);   // the word offset of every bitmap in the block
-  for (uint32_t m = 0; m < n_masks; ++m) {
-    scans[m] = scan_serves && p.n_allowed[m] > masked_exact_cut(p.n_pub);
-    if (per_query) head_of[m] = (uint32_t)(kTabWords + (uint64_t)m * p.words);
-  }
-  FilterView v;
-  v.n_pub = p.n_pub;
-  v.n_eff = p.n_eff;
-  v.n_tiles = p.n_tiles;
-  v.n_filters = n_masks;
-  v.n_allowed = p.n_allowed.data();
-  v.off = p.off.off;
-  v.filter_of = p.mask_of;
-  v.scans = scans.data();
-  v.cum = p.cum.data();
-  v.d_list = w.dList.p;
-  v.sample = &w.dSample;
-  v.allow = per_query ? w.dBlock.p : p.d_maps;
-  v.allow_per_query = per_query;
-  v.d_head = per_query ? w.dBlock.p : nullptr;
-  v.head_of = head_of.data();
-  v.samples = [&]() -> int {
-    if (int r = w.dSample.ensure((size_t)n_masks * kMaskedSample)) return r;
-    HIP_TRY(launch_masked_samples(w.dList.p, p.off, w.dCum.p, n_masks, p.n_tiles, w.dSample.p, st));
-    return EHX_OK;
-  };
+  char scans[kMaskedMaxMasks];
+  uint32_t head_of[kMaskedMaxMasks];
+  filter_routes_cut(filter_scan_serves(s, k, p.n_pub), masked_exact_cut(p.n_pub), p.n_allowed.data(), p.n_masks, scans);
+  FilterView v = masked_view(s, st, p, scans, head_of);
   v.ctr = s->masked_ctr;
   return filtered_answer(s, st, nq, d_queries, k, v, out);
 }

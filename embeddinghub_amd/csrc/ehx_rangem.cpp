@@ -154,11 +154,10 @@ int rangem_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_querie
   const bool per_query = p.n_masks > 1;   // one mask: the batch's ONE bitmap in the flush, no offsets
   // The cut is the bitmap kNN's (masked_exact_cut: measured for a k-th distance, profiles/masked_bench.jsonl) — for a radius
   // a CARRIED-OVER choice (the file header has what scripts/bench_range_masked.py measured).
-  const bool i8 = i8_serves_radius(s, p.n_pub);
   const uint32_t forced = s->rangem_route.load(std::memory_order_relaxed);   // (test hook: the bench's crossover sweep)
-  const uint64_t cut = forced == 1u ? 0 : masked_exact_cut(p.n_pub);
-  bool scans[kMaskedMaxMasks];
-  for (uint32_t mk = 0; mk < p.n_masks; ++mk) scans[mk] = i8 && forced != 2u && p.n_allowed[mk] > cut;
+  const uint64_t cut = forced == 1u ? 0 : forced == 2u ? ~0ull : masked_exact_cut(p.n_pub);
+  char scans[kMaskedMaxMasks];
+  filter_routes_cut(i8_serves_radius(s, p.n_pub), cut, p.n_allowed.data(), p.n_masks, scans);
   std::vector<uint32_t> route, list, offs(per_query ? kTabWords : 0);
   std::vector<uint8_t> counted;
   for (size_t q0 = 0; q0 < nq; q0 += kSideChunk) {

@@ -21,6 +21,9 @@
 //   ehx_test_write_batch       what a batch of row ids touches (WriteBatch), host arithmetic only (no device, no space)
 //   ehx_test_write_times       device time of the last write's upload (or scatter) and of its derived copies (scripts/bench_rowio.py)
 //   ehx_test_shard             the handle of one shard of a row-sharded space (what a caller that kept one would hold)
+// ... and of the filtered searches (ehx_masked.cpp, k_masked.hip):
+//   ehx_test_filter_routes     the routing rule (filter_routes_cut, then _gate), host arithmetic only (no device, no space)
+//   ehx_test_rows_prefix       launch_rows_prefix on host arrays (a device, no space)
 // No production path calls in here.
 #include "ehx_internal.h"
 
@@ -476,6 +479,31 @@ int ehx_test_write_times(ehx_space* s, float out[2]) {
     (void)hipGetLastError();
     return fail(EHX_ENOTFOUND, "no write timed yet");
   }
+  return EHX_OK;
+}
+
+// filter_routes_cut, then filter_routes_gate: scans[0, n_filters) as every filtered search decides them (host arithmetic)
+void ehx_test_filter_routes(int scan_serves, uint64_t cut, const uint64_t* n_allowed, uint32_t n_filters, const uint32_t* filter_of,
+                            size_t nq, size_t min_scan_queries, char* scans) {
+  filter_routes_cut(scan_serves != 0, cut, n_allowed, n_filters, scans);
+  filter_routes_gate(filter_of, nq, min_scan_queries, n_filters, scans);
+}
+
+// launch_rows_prefix on host arrays, no space: out[rows][n + 1] and ONE word behind go up as they are, counts[rows][n] into
+// the first n words of every row; all rows * (n + 1) + 1 words come back
+int ehx_test_rows_prefix(const uint32_t* counts, uint32_t rows, uint32_t n, uint32_t* out) {
+  int rc = ehx_init(nullptr, 0);
+  if (rc) return rc;
+  if (!out || (!counts && rows && n)) return fail(EHX_EINVAL, "NULL argument");
+  const size_t words = (size_t)rows * ((size_t)n + 1) + 1;
+  DevBuf<uint32_t> d;
+  if ((rc = d.ensure(words))) return rc;
+  HIP_TRY(hipMemcpy(d.p, out, words * sizeof(uint32_t), hipMemcpyHostToDevice));
+  for (uint32_t r = 0; n && r < rows; ++r)
+    HIP_TRY(hipMemcpy(d.p + (size_t)r * (n + 1), counts + (size_t)r * n, n * sizeof(uint32_t), hipMemcpyHostToDevice));
+  HIP_TRY(launch_rows_prefix(d.p, rows, n, nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(out, d.p, words * sizeof(uint32_t), hipMemcpyDeviceToHost));
   return EHX_OK;
 }
 

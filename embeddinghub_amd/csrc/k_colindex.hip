@@ -10,7 +10,8 @@
 //                             bucket needs no pass (the host skips it): a column of fewer than 256 small tenant numbers sorts
 //                             in one pass, a column of one label in none.
 //   colindex_tilehist_kernel  per pass: the digit counts of every 4096-key tile, hist[digit][tile]
-//   colindex_scan_kernel      per pass: a workgroup per digit, exclusive prefix along its tiles on top of the digit's base
+//   colindex_scan_kernel      per pass: a workgroup per digit, exclusive prefix (block_prefix, k_prefix.h) along its tiles on
+//                             top of the digit's base
 //                             (the sum of the smaller digits' totals, from the column's histogram): where every (digit, tile)
 //                             begins in the output
 //   colindex_scatter_kernel   per pass: the stable scatter.  A tile is 4 waves x 16 rounds x 64 keys, wave w's keys
@@ -20,17 +21,17 @@
 //                             the same digit (eight ballots, one per bit of the digit).  Equal digits keep their order by
 //                             construction: row ids ascend inside a label.
 //   colindex_bcount_kernel    sorted labels -> boundaries per 256-key tile (a key differs from the one before it)
-//   colindex_prefix_kernel    ONE workgroup: exclusive prefix of those counts, the total behind them
+//   (rows_prefix_kernel)      k_masked.hip's, ONE row: exclusive prefix of those counts, the total behind them
 //   colindex_bfill_kernel     labels, start (boundary rank = tile prefix + waves before + ballot), perm widened to 64 bits
 //   colindex_tiles_kernel     for every label with more than the cut's rows ("heavy", at most 127): its rows before every
 //                             256-row tile of the id space — a lower bound in its ascending run of perm —
-//                             labeled_prefix_kernel's layout, cum[heavy][0 .. n_tiles]
-//   colindex_sample_kernel    sample[heavy][i] = its run[i * ceil(rows / 256)]
+//                             rows_prefix_kernel's layout, cum[heavy][0 .. n_tiles]
+//   colindex_sample_kernel    sample[heavy][i] = its run[i * sample_stride(rows)]
 //   column_scatter_kernel / column_gather_kernel   values by row id (ehx_set_batch_cols, ehx_column_set / _get)
 // Workgroup shape: 256 lanes (4 waves).  LDS: digits 4 KB, tilehist 1 KB, scatter 4 KB (the four waves' digit rows, turned in
 // place into their output bases), nothing else; 16 keys and 16 ranks per lane stay in registers, no scratch.  Stores of the
 // scatter are per-lane (up to 256 runs per tile): a pass is supposed to be bound by them (not measured).
-#include "ehx_kernels.h"
+#include "k_prefix.h"
 
 namespace ehx {
 
@@ -78,33 +79,10 @@ __global__ __launch_bounds__(256) void colindex_tilehist_kernel(const uint32_t* 
 // workgroup d: hist[d][0 .. n_blocks) counts -> where (d, tile) begins in the output
 __global__ __launch_bounds__(256) void colindex_scan_kernel(uint32_t* __restrict__ hist, uint32_t n_blocks,
                                                             const uint32_t* __restrict__ ghist) {
-  __shared__ uint32_t wave_sum[4];
-  __shared__ uint32_t carry_s;
-  const uint32_t d = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
-  uint32_t* row = hist + (size_t)d * n_blocks;
-  if (tid == 0) {
-    uint32_t base = 0;
-    for (uint32_t i = 0; i < d; ++i) base += ghist[i];
-    carry_s = base;
-  }
-  __syncthreads();
-  for (uint32_t t0 = 0; t0 < n_blocks; t0 += kCiThreads) {
-    const uint32_t t = t0 + tid;
-    const uint32_t c = t < n_blocks ? row[t] : 0u;
-    uint32_t incl = c;
-    for (int s = 1; s < 64; s <<= 1) {
-      const uint32_t o = (uint32_t)__shfl_up((int)incl, s, 64);
-      if ((int)lane >= s) incl += o;
-    }
-    if (lane == 63u) wave_sum[w] = incl;
-    __syncthreads();
-    uint32_t before = carry_s;
-    for (uint32_t i = 0; i < w; ++i) before += wave_sum[i];
-    if (t < n_blocks) row[t] = before + incl - c;
-    __syncthreads();
-    if (tid == kCiThreads - 1u) carry_s = before + incl;
-    __syncthreads();
-  }
+  const uint32_t d = blockIdx.x;
+  uint32_t base = 0;   // (lane 0's counts alone)
+  for (uint32_t i = 0; threadIdx.x == 0 && i < d; ++i) base += ghist[i];
+  block_prefix<kCiThreads>(hist + (size_t)d * n_blocks, n_blocks, base, false);
 }
 
 // one workgroup per tile; vals_in == nullptr: the values are the positions themselves (the first pass: row ids)
@@ -178,33 +156,6 @@ __global__ __launch_bounds__(256) void colindex_bcount_kernel(const uint32_t* __
   if (tid == 0) bcount[blockIdx.x] = wc[0] + wc[1] + wc[2] + wc[3];
 }
 
-// ONE workgroup: c[0 .. m) counts -> exclusive prefix in place, c[m] = the total
-__global__ __launch_bounds__(1024) void colindex_prefix_kernel(uint32_t* __restrict__ c, uint32_t m) {
-  __shared__ uint32_t wave_sum[16];
-  __shared__ uint32_t carry_s;
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
-  if (tid == 0) carry_s = 0;
-  __syncthreads();
-  for (uint32_t t0 = 0; t0 < m; t0 += 1024u) {
-    const uint32_t t = t0 + tid;
-    const uint32_t v = t < m ? c[t] : 0u;
-    uint32_t incl = v;
-    for (int s = 1; s < 64; s <<= 1) {
-      const uint32_t o = (uint32_t)__shfl_up((int)incl, s, 64);
-      if ((int)lane >= s) incl += o;
-    }
-    if (lane == 63u) wave_sum[w] = incl;
-    __syncthreads();
-    uint32_t before = carry_s;
-    for (uint32_t i = 0; i < w; ++i) before += wave_sum[i];
-    if (t < m) c[t] = before + incl - v;
-    __syncthreads();
-    if (tid == 1023u) carry_s = before + incl;
-    __syncthreads();
-  }
-  if (tid == 0) c[m] = carry_s;
-}
-
 // one workgroup per 256-key tile; vals == nullptr: no pass ran, perm is the identity
 __global__ __launch_bounds__(256) void colindex_bfill_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals,
                                                              uint64_t n, uint32_t n_tiles, const uint32_t* __restrict__ bbase,
@@ -251,9 +202,7 @@ __global__ __launch_bounds__(256) void colindex_tiles_kernel(const uint64_t* __r
 __global__ __launch_bounds__(256) void colindex_sample_kernel(const uint64_t* __restrict__ perm, const uint64_t* __restrict__ run,
                                                               uint32_t n_heavy, uint64_t* __restrict__ sample) {
   const uint32_t h = blockIdx.x;
-  const uint64_t b = run[h], rows = run[n_heavy + h] - b;
-  const uint64_t stride = (rows + 255u) / 256u, i = threadIdx.x;
-  if (i * stride < rows) sample[(size_t)h * 256u + i] = perm[b + i * stride];
+  write_sample(perm + run[h], run[n_heavy + h] - run[h], sample + (size_t)h * 256u);
 }
 
 __global__ __launch_bounds__(256) void column_scatter_kernel(uint32_t* __restrict__ col, uint64_t cap,
@@ -302,7 +251,7 @@ hipError_t launch_colindex_bounds(const uint32_t* keys, const uint32_t* vals, ui
   if (n > 0xFFFFFFFFull) return hipErrorInvalidValue;
   const uint32_t n_tiles = (uint32_t)((n + 255u) / 256u);
   hipLaunchKernelGGL(colindex_bcount_kernel, dim3(n_tiles), dim3(256), 0, st, keys, n, bbase);
-  hipLaunchKernelGGL(colindex_prefix_kernel, dim3(1), dim3(1024), 0, st, bbase, n_tiles);
+  if (hipError_t e = launch_rows_prefix(bbase, 1, n_tiles, st); e != hipSuccess) return e;
   hipLaunchKernelGGL(colindex_bfill_kernel, dim3(n_tiles), dim3(256), 0, st, keys, vals, n, n_tiles, bbase, labels, start, perm);
   return hipGetLastError();
 }

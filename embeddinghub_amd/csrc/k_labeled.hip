@@ -8,14 +8,14 @@
 //                           reduced per workgroup in LDS: one global add per slot and workgroup, not one per row
 //   labeled_tiles_kernel    the scanning slots' rows in every tile, cum[scan][tile] (a workgroup per tile, 127 LDS counters:
 //                           never a slots x tiles table)
-//   labeled_prefix_kernel   their exclusive prefix per scanning slot, cum[scan][0 .. n_tiles]: masked_prefix_kernel's
-//                           layout, which masked_passes reads
+//   (rows_prefix_kernel)    k_masked.hip's: their exclusive prefix per scanning slot, cum[scan][0 .. n_tiles], the layout
+//                           masked_passes reads
 //   labeled_fill_kernel     the lists.  A scanning slot's row lands at off + cum[scan][tile] + its rank inside the tile (a
 //                           ballot per distinct scanning slot of the wave, the waves' counts through LDS): ascending.  Every
 //                           other slot's row takes the next free entry of its list from a cursor: any order, which
 //                           ehx_knn_among_device's contract allows — the list scan orders by (distance, id), no answer
 //                           depends on it.
-//   labeled_sample_kernel   sample[scan][i] = the scanning slot's list[i * ceil(rows / 256)]
+//   labeled_sample_kernel   sample[scan][i] = the scanning slot's list[i * sample_stride(rows)]
 // The offsets come from device arrays (2048 slots do not fit a kernel argument as MaskedOffsets' 64 do).
 #include "ehx_kernels.h"
 
@@ -79,35 +79,6 @@ __global__ __launch_bounds__(256) void labeled_tiles_kernel(const uint16_t* __re
   }
 }
 
-// ONE workgroup per scanning slot: cum[scan][0 .. n_tiles) counts -> exclusive prefix in place, cum[scan][n_tiles] = the
-// total.  Blocks of 1024 tiles with a running carry, as masked_prefix_kernel (k_masked.hip) does per mask.
-__global__ __launch_bounds__(1024) void labeled_prefix_kernel(uint32_t* __restrict__ cum_all, uint32_t n_tiles) {
-  __shared__ uint32_t wave_sum[16];
-  __shared__ uint32_t carry_s;
-  uint32_t* cum = cum_all + (size_t)blockIdx.x * (n_tiles + 1u);
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
-  if (tid == 0) carry_s = 0;
-  __syncthreads();
-  for (uint32_t t0 = 0; t0 < n_tiles; t0 += 1024u) {
-    const uint32_t t = t0 + tid;
-    const uint32_t c = t < n_tiles ? cum[t] : 0u;
-    uint32_t incl = c;   // inclusive scan across the wave
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t o = (uint32_t)__shfl_up((int)incl, d, 64);
-      if ((int)lane >= d) incl += o;
-    }
-    if (lane == 63u) wave_sum[w] = incl;
-    __syncthreads();
-    uint32_t before = carry_s;
-    for (uint32_t i = 0; i < w; ++i) before += wave_sum[i];
-    if (t < n_tiles) cum[t] = before + incl - c;
-    __syncthreads();
-    if (tid == 1023u) carry_s = before + incl;
-    __syncthreads();
-  }
-  if (tid == 0) cum[n_tiles] = carry_s;
-}
-
 // one workgroup per tile, one lane per row
 __global__ __launch_bounds__(256) void labeled_fill_kernel(const uint16_t* __restrict__ slot_of, uint64_t n_rows,
                                                            uint32_t n_tiles, const uint64_t* __restrict__ off,
@@ -139,15 +110,13 @@ __global__ __launch_bounds__(256) void labeled_fill_kernel(const uint16_t* __res
   list[off[slot] + cum[(size_t)sc * (n_tiles + 1u) + tile] + before + rank] = r;
 }
 
-// one workgroup per scanning slot: sample[256 scan + i] = its list[i * stride] while i * stride < rows, stride = ceil(rows / 256)
+// one workgroup per scanning slot: its sample (write_sample, ehx_kernels.h) at sample + 256 scan
 __global__ __launch_bounds__(256) void labeled_sample_kernel(const uint64_t* __restrict__ list,
                                                              const uint64_t* __restrict__ scan_off,
                                                              const uint32_t* __restrict__ cum, uint32_t n_tiles,
                                                              uint64_t* __restrict__ sample) {
   const uint32_t sc = blockIdx.x;
-  const uint64_t n_allowed = cum[(size_t)sc * (n_tiles + 1u) + n_tiles];
-  const uint64_t stride = (n_allowed + 255u) / 256u, i = threadIdx.x;
-  if (i * stride < n_allowed) sample[(size_t)sc * 256u + i] = list[scan_off[sc] + i * stride];
+  write_sample(list + scan_off[sc], cum[(size_t)sc * (n_tiles + 1u) + n_tiles], sample + (size_t)sc * 256u);
 }
 
 namespace {
@@ -172,8 +141,7 @@ hipError_t launch_labeled_tiles(const uint16_t* slot_of, uint64_t n_rows, uint32
   if (n_scan > kLabeledMaxScan || (uint64_t)n_tiles * 256u < n_rows) return hipErrorInvalidValue;
   hipLaunchKernelGGL(labeled_tiles_kernel, dim3(std::min(n_tiles, kLabeledGrid)), dim3(256), 0, st, slot_of, n_rows, n_tiles,
                      scan_of, n_scan, cum);
-  hipLaunchKernelGGL(labeled_prefix_kernel, dim3(n_scan), dim3(1024), 0, st, cum, n_tiles);
-  return hipGetLastError();
+  return launch_rows_prefix(cum, n_scan, n_tiles, st);
 }
 
 hipError_t launch_labeled_fill(const uint16_t* slot_of, uint64_t n_rows, uint32_t n_tiles, uint32_t n_slots,

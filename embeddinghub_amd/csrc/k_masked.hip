@@ -3,10 +3,11 @@
 // byte for byte.  This file compacts the bitmaps, every one of a table in one set of launches, the mask a grid dimension
 // (one bitmap: a table of one, used where it lies — the row stride is never applied):
 //   masked_count_kernel    allowed rows of every 256-row tile (8 words of the bitmap) of every mask
-//   masked_prefix_kernel   their exclusive prefix per mask, cum[m][0 .. n_tiles] (cum[m][n_tiles] = mask m's allowed rows)
+//   rows_prefix_kernel     their exclusive prefix per mask, cum[m][0 .. n_tiles] (cum[m][n_tiles] = mask m's allowed rows);
+//                          the label compaction (k_labeled.hip) and the column index (k_colindex.hip) launch it too
 //   masked_fill_kernel     the ascending lists of allowed row ids, mask m's at list + off[m] (the host places them back to
 //                          back from the counts it read)
-//   masked_sample_kernel   every mask's sample, every ceil(allowed / 256)-th allowed id by rank: its exact k-th distance is
+//   masked_sample_kernel   every mask's sample, every sample_stride(allowed)-th allowed id by rank: its exact k-th distance is
 //                          the first radius (launched for the scan route only)
 //   masked_radius_kernel   radius[q] = that distance, from the list scan's answer over the sample of the query's own mask
 //                          (+Inf while it gave fewer than k)
@@ -14,7 +15,7 @@
 // radius kNN of k_radius.hip with the bitmap in the int8 scan's flush (one for the batch, or one per query: k_flati8.hip)
 // and this first radius — that file's header has the re-rank kernel and the argument why the answer is exact, "allowed
 // rows" being its rows.
-#include "ehx_kernels.h"
+#include "k_prefix.h"
 
 namespace ehx {
 
@@ -29,33 +30,10 @@ __global__ __launch_bounds__(256) void masked_count_kernel(const uint32_t* __res
   cum[(size_t)m * (n_tiles + 1u) + t] = c;
 }
 
-// ONE workgroup per mask: cum[m][0 .. n_tiles) counts -> exclusive prefix in place, cum[m][n_tiles] = the total.  Blocks of
-// 1024 tiles, a running carry between them (n_tiles <= 2^24: at most 16 384 steps of a kernel that runs once per call).
-__global__ __launch_bounds__(1024) void masked_prefix_kernel(uint32_t* __restrict__ cum_all, uint32_t n_tiles) {
-  __shared__ uint32_t wave_sum[16];
-  __shared__ uint32_t carry_s;
-  uint32_t* cum = cum_all + (size_t)blockIdx.x * (n_tiles + 1u);
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
-  if (tid == 0) carry_s = 0;
-  __syncthreads();
-  for (uint32_t t0 = 0; t0 < n_tiles; t0 += 1024u) {
-    const uint32_t t = t0 + tid;
-    const uint32_t c = t < n_tiles ? cum[t] : 0u;
-    uint32_t incl = c;   // inclusive scan across the wave
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t o = (uint32_t)__shfl_up((int)incl, d, 64);
-      if ((int)lane >= d) incl += o;
-    }
-    if (lane == 63u) wave_sum[w] = incl;
-    __syncthreads();
-    uint32_t before = carry_s;
-    for (uint32_t i = 0; i < w; ++i) before += wave_sum[i];
-    if (t < n_tiles) cum[t] = before + incl - c;
-    __syncthreads();
-    if (tid == 1023u) carry_s = before + incl;
-    __syncthreads();
-  }
-  if (tid == 0) cum[n_tiles] = carry_s;
+// ONE workgroup per row of counts: cum[row][0 .. n) -> exclusive prefix in place, cum[row][n] = the total (block_prefix,
+// k_prefix.h).  Every compaction's: the tiles of a bitmap, of a scanning label, the label boundaries of a column index.
+__global__ __launch_bounds__(1024) void rows_prefix_kernel(uint32_t* __restrict__ cum_all, uint32_t n) {
+  block_prefix<1024>(cum_all + (size_t)blockIdx.x * (n + 1u), n, 0u, true);
 }
 
 // one workgroup per (tile, mask), one lane per row: list[off[mask] + cum[mask][tile] + rank inside the tile] = row id
@@ -76,14 +54,12 @@ __global__ __launch_bounds__(256) void masked_fill_kernel(const uint32_t* __rest
   list[off.off[m] + cum[(size_t)m * (n_tiles + 1u) + tile] + rank] = (uint64_t)tile * 256u + tid;
 }
 
-// one workgroup per mask: sample[256 m + i] = mask m's list[i * stride] while i * stride < allowed, stride = ceil(allowed / 256)
+// one workgroup per mask: mask m's sample (write_sample, ehx_kernels.h) at sample + 256 m
 __global__ __launch_bounds__(256) void masked_sample_kernel(const uint64_t* __restrict__ list, const MaskedOffsets off,
                                                             const uint32_t* __restrict__ cum, uint32_t n_tiles,
                                                             uint64_t* __restrict__ sample) {
   const uint32_t m = blockIdx.x;
-  const uint64_t n_allowed = cum[(size_t)m * (n_tiles + 1u) + n_tiles];
-  const uint64_t stride = (n_allowed + 255u) / 256u, i = threadIdx.x;
-  if (i * stride < n_allowed) sample[(size_t)m * 256u + i] = list[off.off[m] + i * stride];
+  write_sample(list + off.off[m], cum[(size_t)m * (n_tiles + 1u) + n_tiles], sample + (size_t)m * 256u);
 }
 
 __global__ __launch_bounds__(256) void masked_radius_kernel(const float* __restrict__ dist, const uint32_t* __restrict__ cnt,
@@ -99,7 +75,12 @@ hipError_t launch_masked_count(const uint32_t* maps, uint64_t stride, uint32_t n
   if (n_masks > kMaskedMaxMasks || (n_masks > 1 && stride < (n_bits + 31) / 32)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(masked_count_kernel, dim3((n_tiles + 255u) / 256u, n_masks), dim3(256), 0, st, maps, stride, n_bits,
                      n_tiles, cum);
-  hipLaunchKernelGGL(masked_prefix_kernel, dim3(n_masks), dim3(1024), 0, st, cum, n_tiles);
+  return launch_rows_prefix(cum, n_masks, n_tiles, st);
+}
+
+hipError_t launch_rows_prefix(uint32_t* cum, uint32_t rows, uint32_t n, hipStream_t st) {
+  if (rows == 0 || n == 0) return hipSuccess;
+  hipLaunchKernelGGL(rows_prefix_kernel, dim3(rows), dim3(1024), 0, st, cum, n);
   return hipGetLastError();
 }
 

@@ -83,6 +83,20 @@ def two_batches():
     return want
 
 
+def both_routes_batch():
+    """uint32 [134]: 66 queries on the three dense labels (above the cut: they scan) and 68 on labels at or below it (FEW,
+    ABSENT, ALL_ONES and 40 small ones: listed) — at least 64 on either side, so the grouped searches' 64-query gate lets
+    the dense labels scan; shuffled.  -> (want, scans: bool per query, by the rule in numpy over column())"""
+    want = _shuffled(list(DENSE) * 22 + [FEW] * 20 + [ABSENT, ALL_ONES] * 4 + [SMALL0 + i for i in range(40)], 5)
+    col, cut = column(), mc.exact_cut(rc.I8_ROWS)
+    assert cut == 1024
+    rows = np.array([int((col == lab).sum()) for lab in want])
+    scans = rows > cut
+    assert sorted(set(want[scans].tolist())) == sorted(DENSE) and rows[~scans].max() <= 300 < cut
+    assert int(scans.sum()) == 66 >= 64 and int((~scans).sum()) == 68 >= 64
+    return want, scans
+
+
 def as_table(col, want):
     """-> (bool [labels, rows], mask_of): the bitmaps that allow what the wanted labels allow, in ascending label order"""
     labs = np.unique(want)

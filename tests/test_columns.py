@@ -131,7 +131,7 @@ def test_index_against_numpy(kind, n):
 @pytest.mark.parametrize("kind", ["random32", "tenants16"])
 def test_index_against_numpy_past_the_carry_loops(kind):
     """cc.BIG_ROWS rows: more than 256 sort tiles (colindex_scan_kernel carries between chunks of 256 tiles) and more than
-    1024 boundary tiles (colindex_prefix_kernel carries between chunks of 1024).  Rows by the generator, the column loaded
+    1024 boundary tiles (rows_prefix_kernel carries between chunks of 1024).  Rows by the generator, the column loaded
     from device memory: no key is marshalled."""
     import torch
     n, d, c = cc.BIG_ROWS, 4, 0

@@ -22,7 +22,7 @@ METHODS = ("set_batch_cols", "column_set", "column_get", "column_load_device", "
            "knn_by_label_device", "knn_grouped_by_label", "knn_grouped_by_label_device")
 # kernel -> LDS bytes per workgroup, as designed (k_colindex.hip's header)
 KERNELS = {"colindex_digits_kernel": 4096, "colindex_tilehist_kernel": 1024, "colindex_scan_kernel": 20,
-           "colindex_scatter_kernel": 4096, "colindex_bcount_kernel": 16, "colindex_prefix_kernel": 68,
+           "colindex_scatter_kernel": 4096, "colindex_bcount_kernel": 16,
            "colindex_bfill_kernel": 16, "colindex_tiles_kernel": 0, "colindex_sample_kernel": 0,
            "column_scatter_kernel": 0, "column_gather_kernel": 0}
 

@@ -143,6 +143,5 @@ def test_the_files_beside_it_hold_the_functions_they_held(tmp_path):
     held = (("grouped_rerank_kernel", 9), ("grouped_range_seed_kernel", 1), ("grouped_range_slab_kernel", 1))
     assert len(names) == 11 and all(sum(k in n for n in names) == c for k, c in held)
     names, _ = _functions("k_labeled.hip", tmp_path)
-    kernels = ("labeled_count_kernel", "labeled_tiles_kernel", "labeled_prefix_kernel", "labeled_fill_kernel",
-               "labeled_sample_kernel")
-    assert len(names) == 5 and all(sum(k in n for n in names) == 1 for k in kernels)
+    kernels = ("labeled_count_kernel", "labeled_tiles_kernel", "labeled_fill_kernel", "labeled_sample_kernel")
+    assert len(names) == len(kernels) and all(sum(k in n for n in names) == 1 for k in kernels)

@@ -125,6 +125,58 @@ def test_equals_knn_masked_multi_byte_for_byte_and_counter_for_counter(d):
     s.drop()
 
 
+# ---- 2b. the same wanted labels asked four ways: from the call and from a stored column, ungrouped and grouped ----
+
+def _hook(s, name):
+    out = (C.c_uint64 * 5)()
+    getattr(_raw(), name)(s._h, out)
+    return np.array(list(out), dtype=np.int64)
+
+
+def test_one_batch_asked_four_ways_scans_and_lists_alike():
+    """knn_labeled_device, knn_by_label_device on a stored copy of the column, and their grouped counterparts with every
+    group EHX_GROUP_NONE and per_group 1 (a cap that caps nothing): one body (labeled_call), two views' users.  66 queries
+    name scanning labels and 68 listed ones, so the grouped forms' 64-query gate opens."""
+    import torch
+    d, k, label_col, group_col = 64, 10, 1, 2   # (column 2 is never written: EHX_GROUP_NONE for every row)
+    X, Q = rc.i8_data(d)
+    col = lbc.column()
+    want, scans = lbc.both_routes_batch()
+    nq, n = len(want), len(X)
+    Q = np.ascontiguousarray(Q[:nq])
+    s = ehx.Space.unique("labeled-four-ways", d, metric=METRICS["cosine"][0], initial_capacity=n)
+    s.set_batch_cols(_keys(n), X, {label_col: col})
+    assert s.scan_engine() == "i8"
+    dq = torch.tensor(Q, device="cuda")
+    dc = torch.tensor(np.ascontiguousarray(col).view(np.int32), device="cuda")
+    dg = torch.full((n,), -1, dtype=torch.int32, device="cuda")   # EHX_GROUP_NONE
+    dw = torch.tensor(want.view(np.int32), device="cuda")
+    assert ehx.GROUP_NONE == 0xFFFFFFFF
+    forms = (("ehx_test_labeled_counters", lambda o: s.knn_labeled_device(dq, k, dc, n, dw, *o)),
+             ("ehx_test_labeled_counters", lambda o: s.knn_by_label_device(dq, k, label_col, dw, *o)),
+             ("ehx_test_grouped_labeled_counters", lambda o: s.knn_grouped_labeled_device(dq, k, dg, dc, n, dw, *o, per_group=1)),
+             ("ehx_test_grouped_labeled_counters",
+              lambda o: s.knn_grouped_by_label_device(dq, k, group_col, label_col, dw, *o, per_group=1)))
+    answers, splits = [], []
+    for hook, call in forms:
+        o = (torch.full((nq, k), -7, dtype=torch.int64, device="cuda"), torch.full((nq, k), -7.0, dtype=torch.float32, device="cuda"),
+             torch.full((nq,), 77, dtype=torch.int32, device="cuda"))
+        c0 = _hook(s, hook)
+        call(o)
+        torch.cuda.synchronize()
+        dcnt = (_hook(s, hook) - c0).tolist()
+        print(hook, dcnt)
+        answers.append((o[0].cpu().numpy().view(np.uint64), o[1].cpu().numpy(), o[2].cpu().numpy().view(np.uint32)))
+        splits.append(dcnt[:2])
+        assert dcnt[4] == 1, (hook, dcnt)
+    _assert_rows(answers[0], _want(X, Q, k, METRICS["cosine"][1], col, want), "four ways")
+    assert _same_bytes(answers[0], answers[1]), "knn_labeled_device and knn_by_label_device differ"
+    assert _same_bytes(answers[2], answers[3]), "the grouped forms differ"
+    assert _same_bytes(answers[0], answers[2]), "the grouped answer differs from the kNN's"
+    assert splits == [[int(scans.sum()), int((~scans).sum())]] * 4, splits   # 66 on the scan route, 68 on the lists
+    s.drop()
+
+
 # ---- 3. no query is judged by another query's label ----
 
 @pytest.mark.parametrize("metric", ["l2", "cosine"])

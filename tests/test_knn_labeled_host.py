@@ -16,8 +16,7 @@ from embeddinghub_amd.space import Space
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("ehx_knn_labeled", "ehx_knn_labeled_device")
 HOOK = "ehx_test_labeled_counters"
-KERNELS = ("labeled_count_kernel", "labeled_tiles_kernel", "labeled_prefix_kernel", "labeled_fill_kernel",
-           "labeled_sample_kernel")
+KERNELS = ("labeled_count_kernel", "labeled_tiles_kernel", "labeled_fill_kernel", "labeled_sample_kernel")
 
 
 def _header():
@@ -87,3 +86,11 @@ def test_labeled_kernels_use_no_scratch_and_spill_no_vector_registers(tmp_path):
         assert len(vals) == len(names) and all(v == "0" for v in vals), (what, vals)
     lds = [int(v) for v in re.findall(r"LDS Size \[bytes/block\]: (\d+)", r.stderr)]
     assert max(lds) == 16384   # the table of 2048 labels and its counters: 8 KB each
+
+
+def test_the_batch_asked_four_ways_names_labels_on_both_sides_of_the_cut():
+    """tests/test_knn_labeled.py's four-ways batch, by the routing rule in numpy: at least 64 queries on scanning labels and at
+    least 64 on listed ones (labeled_cases.both_routes_batch asserts the sizes where it makes the batch)"""
+    want, scans = lbc.both_routes_batch()
+    assert len(want) == len(scans) == 134 and scans.sum() >= 64 and (~scans).sum() >= 64
+    assert set(want[scans].tolist()) == set(lbc.DENSE)

@@ -87,10 +87,13 @@ def test_masked_kernels_use_no_scratch_and_spill_no_vector_registers(tmp_path):
                                                     str(tmp_path / "k_masked.o")], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     names = re.findall(r"Function Name: (\S+)", r.stderr)
-    for kern in ("masked_count_kernel", "masked_prefix_kernel", "masked_fill_kernel", "masked_sample_kernel",
+    for kern in ("masked_count_kernel", "rows_prefix_kernel", "masked_fill_kernel", "masked_sample_kernel",
                  "masked_radius_kernel"):
         assert sum(kern in n for n in names) == 1, names
     assert len(names) == 5
     for what in ("ScratchSize \\[bytes/lane\\]", "VGPRs Spill"):
         vals = re.findall(what + r": (\d+)", r.stderr)
         assert len(vals) == len(names) and all(v == "0" for v in vals), (what, vals)
+    # the ONE tile prefix of every compaction (block_prefix<1024>): 16 wave sums and the carry
+    lds = dict(zip(names, re.findall(r"LDS Size \[bytes/block\]: (\d+)", r.stderr)))
+    assert len(lds) == 5 and [v for n, v in lds.items() if "rows_prefix_kernel" in n] == ["68"], lds
