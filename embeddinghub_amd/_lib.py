@@ -22,6 +22,7 @@ WALK_LIST_FACTOR, WALK_LIST_MAX = 12, 4096     # EHX_WALK_LIST_FACTOR / _MAX: th
 GROUP_NONE, MAX_K_GROUPED = 0xFFFFFFFF, 256     # EHX_GROUP_NONE (a row that is a group of its own), EHX_MAX_K_GROUPED
 MAX_COLUMNS = 4                                 # EHX_MAX_COLUMNS: stored label columns of a space
 PRED_MAX_TERMS, TERM_NOT = 8, 1                 # EHX_PRED_MAX_TERMS, EHX_TERM_NOT: predicates over stored columns
+TERM_IN, FILTER_MAX_CLAUSES, FILTER_MAX_VALUES = 2, 128, 4096   # EHX_TERM_IN, EHX_FILTER_MAX_*: Boolean filters over them
 SEED_CORPUS, SEED_QUERY = 20250211, 20250212
 
 
@@ -57,11 +58,21 @@ class Pred(C.Structure):   # ehx_pred: a conjunction of n_terms terms
     _fields_ = [("n_terms", C.c_uint32), ("terms", Term * PRED_MAX_TERMS)]
 
 
+class Filter(C.Structure):   # ehx_filter: the OR of clauses[first_clause, first_clause + n_clauses)
+    _fields_ = [("first_clause", C.c_uint32), ("n_clauses", C.c_uint32)]
+
+
+class Filters(C.Structure):   # ehx_filters: the table of one call, host memory
+    _fields_ = [("clauses", C.POINTER(Pred)), ("n_clauses", C.c_uint32), ("values", C.POINTER(C.c_uint32)),
+                ("n_values", C.c_uint32), ("filters", C.POINTER(Filter)), ("n_filters", C.c_uint32)]
+
+
 # every symbol include/ehx.h declares: name -> (restype, argtypes)
 _f32p, _u64p, _u32p, _i32p = (C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
                               C.POINTER(C.c_int32))
 _vp = C.c_void_p
 _predp = C.POINTER(Pred)
+_filtp = C.POINTER(Filters)
 SYMBOLS = {
     "ehx_init": (C.c_int, [C.POINTER(C.c_int), C.c_int]),
     "ehx_shutdown": (C.c_int, []),
@@ -162,6 +173,16 @@ SYMBOLS = {
                                   _u64p]),
     "ehx_range_where_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp, C.c_uint32, _predp, C.c_uint32, _vp, _vp, _vp, _vp,
                                          _vp]),
+    "ehx_knn_filter": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_uint32, _filtp, _u32p, _u64p, _f32p, _u32p]),
+    "ehx_knn_filter_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint32, _filtp, _vp, _vp, _vp, _vp]),
+    "ehx_knn_grouped_filter": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_uint32, C.c_uint32, C.c_uint32, _filtp, _u32p, _u64p, _f32p,
+                                         _u32p]),
+    "ehx_knn_grouped_filter_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _filtp, _vp, _vp,
+                                                _vp, _vp]),
+    "ehx_range_filter": (C.c_int, [_vp, C.c_size_t, _f32p, _f32p, C.c_uint32, _filtp, _u32p, _u64p, _f32p, _u32p, _u64p]),
+    "ehx_range_filter_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp, C.c_uint32, _filtp, _vp, _vp, _vp, _vp, _vp]),
+    "ehx_graph_knn_filter": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_uint32, _filtp, _u32p, C.c_uint32, _u64p, _f32p, _u32p]),
+    "ehx_graph_knn_filter_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint32, _filtp, _vp, C.c_uint32, _vp, _vp, _vp]),
     "ehx_knn_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint32, _vp, _vp, _vp]),
     "ehx_merge_topk_device": (C.c_int, [_vp, C.c_size_t, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ehx_merge_topk_strided_device": (C.c_int, [_vp, C.c_size_t, C.c_uint32, C.c_uint32, _vp, C.c_size_t, _vp,

@@ -10,10 +10,10 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIB_DIR, "libehx%s.so" % os.environ.get("EHX_LIB_SUFFIX", ""))  # suffix: ablation builds
 SOURCES = ["ehx_api.cpp", "ehx_space.cpp", "ehx_flat.cpp", "ehx_graph.cpp", "ehx_shards.cpp", "ehx_write.cpp", "ehx_search.cpp", "ehx_among.cpp",
-           "ehx_range.cpp", "ehx_rangem.cpp", "ehx_masked.cpp", "ehx_largek.cpp", "ehx_grouped.cpp", "ehx_groupedm.cpp", "ehx_labeled.cpp", "ehx_groupedl.cpp", "ehx_call.cpp", "ehx_rowio.cpp", "ehx_testhooks.cpp", "ehx_columns.cpp", "ehx_where.cpp",
+           "ehx_range.cpp", "ehx_rangem.cpp", "ehx_masked.cpp", "ehx_largek.cpp", "ehx_grouped.cpp", "ehx_groupedm.cpp", "ehx_labeled.cpp", "ehx_groupedl.cpp", "ehx_call.cpp", "ehx_rowio.cpp", "ehx_testhooks.cpp", "ehx_columns.cpp", "ehx_where.cpp", "ehx_filter.cpp",
            "k_flat.hip", "k_flat8.hip", "k_flat16.hip", "k_flati8.hip", "k_select.hip", "k_misc.hip",
            "k_graph.hip", "k_graphw.hip", "k_insert.hip", "k_bykey.hip", "k_among.hip", "k_range.hip", "k_rangem.hip", "k_masked.hip",
-           "k_radius.hip", "k_rowio.hip", "k_graphm.hip", "k_grouped.hip", "k_labeled.hip", "k_colindex.hip", "k_where.hip"]
+           "k_radius.hip", "k_rowio.hip", "k_graphm.hip", "k_grouped.hip", "k_labeled.hip", "k_colindex.hip", "k_where.hip", "k_filter.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-function",
          "-fno-gpu-rdc", "-ffp-contract=off", "-I", os.path.join(ROOT, "include"),

@@ -516,6 +516,9 @@ struct ehx_space {
     // the predicate searches (ehx_where.cpp): [kMaskedMaxMasks] the call's predicates, where the kernel that builds the
     // bitmaps into dBlock reads them; sized once
     DevBuf<WherePred> dPreds;
+    // the Boolean filter searches (ehx_filter.cpp): [kFilterExprWords] the call's packed expression — clauses | values |
+    // filter runs — where k_filter.hip's kernel reads it; sized once
+    DevBuf<uint32_t> dFilter;
   } masked;
   // test hook: queries answered on the scan route, on the exact route, queries that overflowed, scan passes launched, calls
   // (ehx_knn_masked* and ehx_knn_masked_multi* both count here)
@@ -1058,6 +1061,27 @@ int rangem_check(const ehx_space* s, size_t nq, uint32_t max_results, const void
 int rangem_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, const float* d_radius, uint32_t max_results,
                   const MaskTable& tab, uint64_t n_bits, const uint32_t* mask_of, const uint32_t* d_mask_of,
                   const ResultBlock& out);
+// ehx_graph_knn_masked_multi* (ehx_masked.cpp): the walk, the exact answer or both, by `route` and per mask
+int graphm_table_check(const ehx_space* s, size_t nq, uint32_t k, const void* q, const void* masks, uint32_t n_masks,
+                       uint64_t n_bits, const void* mask_of, uint32_t route, const void* o_ids, const void* o_dist,
+                       const void* o_cnt);
+int graphm_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, const MaskTable& tab,
+                  uint64_t n_bits, const uint32_t* mask_of, const uint32_t* d_mask_of, uint32_t route, const ResultBlock& out);
+// ---- ehx_where.cpp: what the searches under BUILT tables share (predicates; Boolean filters, ehx_filter.cpp) ----
+constexpr uint64_t kAllRows = ~0ull;   // n_bits (and n_labels) of a built table: the call's snapshot alone bounds the rows
+constexpr const char* kWhereWhy = "stored columns over shards are not built yet";
+// the columns a build kernel reads: those SOME of the n_preds conjunctions names and that are live (the space locked at least
+// shared)
+WhereCols where_cols(const ehx_space* s, const ehx_pred* preds, uint32_t n_preds);
+int check_group_col(uint32_t col);   // at or above EHX_MAX_COLUMNS: EHX_EINVAL
+// groupedm_locked under a built table, the stored column group_col of the whole prefix as its labels, read where it lies
+int grouped_built_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, uint32_t per_group,
+                         uint32_t group_col, const MaskTable& tab, const uint32_t* mask_of, const uint32_t* d_mask_of,
+                         const ResultBlock& out);
+// what the builders' test hooks share: the builder alone under the search's locks, as masked_maps runs it — the snapshot
+// into *out_n, the table built behind masked.dBlock's head — then then(n_pub, words, table, stream), unless the space is empty
+int built_table_hook(ehx_space* s, const char* what, const MaskTable& tab, uint64_t* out_n,
+                     const std::function<int(uint64_t, uint64_t, uint32_t*, hipStream_t)>& then);
 // What the exact answer needs of compacted per-query row filters, whatever they were compacted from: a table of bitmaps
 // (masked_answer, ehx_masked.cpp) or the wanted labels of a label column (ehx_labeled.cpp).  Host arrays unless named d_.
 struct FilterView {

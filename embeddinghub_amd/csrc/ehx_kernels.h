@@ -630,6 +630,16 @@ struct WhereCols {
 constexpr uint32_t kWhereSpan = 1024;   // rows of one workgroup: four 256-row tiles, 32 words of every bitmap
 hipError_t launch_where_bitmaps(const WhereCols& cols, const WherePred* preds, uint32_t n_preds, uint64_t n_rows, uint64_t words,
                                 uint32_t* dst, hipStream_t st);
+// Boolean filters on stored columns (k_filter.hip; ehx_filter.cpp): the same dense table for n_filters <= kMaskedMaxMasks
+// filters, filter f the OR of the clauses [first, first + n) its run names, a clause a WherePred whose terms may carry
+// kFilterTermIn: then lo is where the term's sorted, de-duplicated set starts among the values and hi how many it holds.
+// expr, DEVICE memory, packed: n_clauses WherePreds | n_values values | n_filters x (first, n); every run lies inside the
+// clauses and every set inside the values (ehx_filter.cpp checks and packs).  cols: as above, over every clause's terms.
+constexpr uint32_t kFilterMaxClauses = 128, kFilterMaxValues = 4096, kFilterTermIn = 2u;   // EHX_FILTER_MAX_*, EHX_TERM_IN
+constexpr uint32_t kFilterExprWords =
+    kFilterMaxClauses * (uint32_t)(sizeof(WherePred) / sizeof(uint32_t)) + kFilterMaxValues + 2u * kMaskedMaxMasks;
+hipError_t launch_filter_bitmaps(const WhereCols& cols, const uint32_t* expr, uint32_t n_clauses, uint32_t n_values,
+                                 uint32_t n_filters, uint64_t n_rows, uint64_t words, uint32_t* dst, hipStream_t st);
 // radius[q] = dist[q][k - 1] when cnt[q] >= k (result lists [nq][k]), else +Inf
 hipError_t launch_masked_radius(const float* dist, const uint32_t* cnt, uint32_t nq, uint32_t k, float* radius, hipStream_t st);
 // word w of a bitmap cut at n_bits (bits of the last word beyond n_bits and words beyond it read as 0)

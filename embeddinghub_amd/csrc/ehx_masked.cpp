@@ -426,6 +426,10 @@ int graphm_check(const ehx_space* s, size_t nq, uint32_t k, const void* q, const
   return check_route(route);
 }
 
+}  // namespace
+
+namespace ehx_impl {
+
 int graphm_table_check(const ehx_space* s, size_t nq, uint32_t k, const void* q, const void* masks, uint32_t n_masks,
                        uint64_t n_bits, const void* mask_of, uint32_t route, const void* o_ids, const void* o_dist,
                        const void* o_cnt) {
@@ -456,7 +460,8 @@ int graphm_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_querie
     p.n_masks = tab.n_masks;
     p.mask_of = mask_of;
     p.d_maps = tab.p;
-    if ((tab.host || tab.n_masks > 1) && (rc = masked_maps(s, st, tab, p.n_eff, &p.d_maps))) return rc;
+    // (a table that is BUILT has no words anywhere yet, whatever its size: masked_maps has them written)
+    if ((tab.host || tab.build || tab.n_masks > 1) && (rc = masked_maps(s, st, tab, p.n_eff, &p.d_maps))) return rc;
     if (d_mask_of) {
       p.mask_of_read.resize(nq);
       HIP_TRY(hipMemcpyAsync(p.mask_of_read.data(), d_mask_of, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -514,6 +519,10 @@ int graphm_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_querie
   p.mask_of = mx.data();
   return w.split.rerun(s, st, d_queries, ix, k, exact, out.ids, out.dist, out.cnt);
 }
+
+}  // namespace ehx_impl
+
+namespace {
 
 // host pointers in, host pointers out, on the space's stream: the bitmaps' words below the row count are staged by whichever
 // route is taken (bits at or above the call's snapshot of the row count are never looked at: they are not even copied)

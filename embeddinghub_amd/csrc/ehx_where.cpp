@@ -18,15 +18,14 @@
 //     valid, and a column that is not live is not read at all — it is the constant EHX_GROUP_NONE.
 // The predicates travel as a small device buffer (masked.dPreds: 64 x 132 bytes do not fit a kernel argument), uploaded behind
 // wait_searches_in_flight like the table itself, so an earlier call's kernel has read its own predicates by then.
-// Not built here: the graph walk under predicates, disjunctions, shards, the per-tile counts fused into the
+// Disjunctions, IN-lists and the graph walk under them are ehx_filter.cpp's, which enters the same bodies and
+// shares the pieces below that ehx_internal.h names.  Not built: shards, the per-tile counts fused into the
 // build kernel, the column index for very selective equality terms.
 // Entry scaffold and host staging are ehx_call.cpp's (search_on_device, HostStage).
 #include "ehx_internal.h"
 
 namespace {
 
-constexpr const char* kWhereWhy = "stored columns over shards are not built yet";
-constexpr uint64_t kAllRows = ~0ull;   // n_bits (and n_labels) of a built table: the call's snapshot alone bounds the rows
 static_assert(sizeof(ehx_pred) == sizeof(WherePred) && sizeof(ehx_pred) == 132 && sizeof(ehx_term) == sizeof(WhereTerm) &&
                   offsetof(ehx_pred, terms) == offsetof(WherePred, terms) && offsetof(ehx_term, flags) == offsetof(WhereTerm, flags),
               "the kernel reads the ABI's predicates as they are");
@@ -51,7 +50,10 @@ int where_check(const ehx_pred* preds, uint32_t n_preds) {
   return EHX_OK;
 }
 
-// the columns the kernel reads: those SOME predicate of the call names and that are live (the space locked at least shared)
+}  // namespace
+
+namespace ehx_impl {
+
 WhereCols where_cols(const ehx_space* s, const ehx_pred* preds, uint32_t n_preds) {
   WhereCols cols = {};
   for (uint32_t p = 0; p < n_preds; ++p)
@@ -62,6 +64,46 @@ WhereCols where_cols(const ehx_space* s, const ehx_pred* preds, uint32_t n_preds
   }
   return cols;
 }
+
+int check_group_col(uint32_t col) {
+  return col < EHX_MAX_COLUMNS ? (int)EHX_OK
+                               : fail(EHX_EINVAL, "group_col = %u: a space has %u columns", col, (unsigned)EHX_MAX_COLUMNS);
+}
+
+// the stored column as the labels of the whole prefix, read where it lies
+int grouped_built_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, uint32_t per_group,
+                         uint32_t group_col, const MaskTable& tab, const uint32_t* mask_of, const uint32_t* d_mask_of,
+                         const ResultBlock& out) {
+  int rc;
+  const uint32_t* d_group_of = nullptr;
+  // A column never written is cols.dNone, which column_as_groups allocates again where it holds fewer entries than it is
+  // asked for — behind the searches in flight that read it, as ehx_knn_grouped_by_label* does.  It is asked for the CAPACITY,
+  // not for a row count read here: the plan takes the call's snapshot later, an append may publish rows in between, and an
+  // array an earlier call sized for a smaller capacity would be read past its end.  The capacity changes only under `mu`
+  // held exclusively, so it bounds every row count this shared hold can see.
+  if ((rc = wait_searches_in_flight(s, st)) || (rc = column_as_groups(s, st, group_col, s->cap, &d_group_of))) return rc;
+  return groupedm_locked(s, st, nq, d_queries, k, per_group, d_group_of, false, kAllRows, tab, kAllRows, mask_of, d_mask_of, out);
+}
+
+int built_table_hook(ehx_space* s, const char* what, const MaskTable& tab, uint64_t* out_n,
+                     const std::function<int(uint64_t, uint64_t, uint32_t*, hipStream_t)>& then) {
+  return search_on_device(s, what, kWhereWhy, 1, nullptr, [&]() -> int {
+    int rc;
+    const hipStream_t st = s->stream;
+    const uint64_t n_pub = s->n.load(std::memory_order_acquire), words = (n_pub + 31) / 32;
+    *out_n = n_pub;
+    if ((rc = s->masked.dBlock.ensure(kTabWords + std::max<size_t>((size_t)tab.n_masks * words, 1)))) return rc;
+    if ((rc = wait_searches_in_flight(s, st))) return rc;
+    if (!words) return EHX_OK;
+    uint32_t* dst = s->masked.dBlock.p + kTabWords;
+    if ((rc = tab.build(n_pub, words, dst, st))) return rc;
+    return then(n_pub, words, dst, st);
+  });
+}
+
+}  // namespace ehx_impl
+
+namespace {
 
 // MaskTable::build of a predicate search: the space locked shared, scratch_mu held, masked.dBlock ensured, `st` ordered behind
 // the searches in flight; n_eff is the plan's snapshot of the row count
@@ -81,11 +123,6 @@ MaskTable where_table(ehx_space* s, const ehx_pred* preds, uint32_t n_preds) {
     return where_build(s, preds, n_preds, n_eff, words, dst, st);
   };
   return tab;
-}
-
-int check_group_col(uint32_t col) {
-  return col < EHX_MAX_COLUMNS ? (int)EHX_OK
-                               : fail(EHX_EINVAL, "group_col = %u: a space has %u columns", col, (unsigned)EHX_MAX_COLUMNS);
 }
 
 int knn_where_check(const ehx_space* s, size_t nq, uint32_t k, const void* q, const ehx_pred* preds, uint32_t n_preds,
@@ -110,41 +147,13 @@ int range_where_check(const ehx_space* s, size_t nq, uint32_t max_results, const
   return nq ? where_check(preds, n_preds) : (int)EHX_OK;
 }
 
-// ehx_knn_grouped_where*'s locked body: the stored column as the labels of the whole prefix, read where it lies
-int grouped_where_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, uint32_t per_group,
-                         uint32_t group_col, const ehx_pred* preds, uint32_t n_preds, const uint32_t* pred_of,
-                         const uint32_t* d_pred_of, const ResultBlock& out) {
-  int rc;
-  const uint32_t* d_group_of = nullptr;
-  // A column never written is cols.dNone, which column_as_groups allocates again where it holds fewer entries than it is
-  // asked for — behind the searches in flight that read it, as ehx_knn_grouped_by_label* does.  It is asked for the CAPACITY,
-  // not for a row count read here: the plan takes the call's snapshot later, an append may publish rows in between, and an
-  // array an earlier call sized for a smaller capacity would be read past its end.  The capacity changes only under `mu`
-  // held exclusively, so it bounds every row count this shared hold can see.
-  if ((rc = wait_searches_in_flight(s, st)) || (rc = column_as_groups(s, st, group_col, s->cap, &d_group_of))) return rc;
-  return groupedm_locked(s, st, nq, d_queries, k, per_group, d_group_of, false, kAllRows, where_table(s, preds, n_preds), kAllRows,
-                         pred_of, d_pred_of, out);
-}
-
-// what the two test hooks below share: the builder alone under the search's locks, as masked_maps runs it — the snapshot into
-// *out_n, the table built behind masked.dBlock's head — then then(n_pub, words, table, stream), unless the space is empty
+// what the two test hooks below share: built_table_hook behind the hooks' own checks
 template <class Then>
 int where_hook(ehx_space* s, const char* what, const ehx_pred* preds, uint32_t n_preds, uint64_t* out_n, Then&& then) {
   if (!s || !out_n) return fail(EHX_EINVAL, "NULL argument");
   if (int rc = ehx_init(nullptr, 0)) return rc;
   if (int rc = where_check(preds, n_preds)) return rc;
-  return search_on_device(s, what, kWhereWhy, 1, nullptr, [&]() -> int {
-    int rc;
-    const hipStream_t st = s->stream;
-    const uint64_t n_pub = s->n.load(std::memory_order_acquire), words = (n_pub + 31) / 32;
-    *out_n = n_pub;
-    if ((rc = s->masked.dBlock.ensure(kTabWords + std::max<size_t>((size_t)n_preds * words, 1)))) return rc;
-    if ((rc = wait_searches_in_flight(s, st))) return rc;
-    if (!words) return EHX_OK;
-    uint32_t* dst = s->masked.dBlock.p + kTabWords;
-    if ((rc = where_build(s, preds, n_preds, n_pub, words, dst, st))) return rc;
-    return then(n_pub, words, dst, st);
-  });
+  return built_table_hook(s, what, where_table(s, preds, n_preds), out_n, then);
 }
 
 }  // namespace
@@ -184,7 +193,7 @@ int ehx_knn_grouped_where_device(ehx_space* s, void* stream, size_t n_queries, c
     return rc;
   const hipStream_t st = (hipStream_t)stream;
   return search_on_device(s, "ehx_knn_grouped_where_device", kWhereWhy, n_queries, &st, [&] {
-    return grouped_where_locked(s, st, n_queries, d_queries, k, per_group, group_col, preds, n_preds, nullptr, d_pred_of,
+    return grouped_built_locked(s, st, n_queries, d_queries, k, per_group, group_col, where_table(s, preds, n_preds), nullptr, d_pred_of,
                                 ResultBlock{d_out_ids, d_out_dist, d_out_count, nullptr, n_queries, k});
   });
 }
@@ -201,7 +210,8 @@ int ehx_knn_grouped_where(ehx_space* s, size_t n_queries, const float* queries, 
     int rc;
     HostStage& h = s->grouped.host;
     if ((rc = h.up(s->stream, queries, n_queries, s->dims, k, false))) return rc;
-    if ((rc = grouped_where_locked(s, s->stream, n_queries, h.q, k, per_group, group_col, preds, n_preds, pred_of, nullptr, h.out)))
+    if ((rc = grouped_built_locked(s, s->stream, n_queries, h.q, k, per_group, group_col, where_table(s, preds, n_preds), pred_of,
+                                   nullptr, h.out)))
       return rc;
     return h.out.copy_out(s->stream, out_ids, out_dist, out_count, nullptr);
   });

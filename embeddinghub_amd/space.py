@@ -795,6 +795,110 @@ class Space:
                                              table, n_preds, _ptr(d_pred_of), _ptr(d_ids), _ptr(d_dist), _ptr(d_count),
                                              _ptr(d_total)))
 
+    # ---- Boolean filters on stored columns: OR of clauses, IN-lists; the bitmap searches' answers, the graph walk included ----
+    @staticmethod
+    def _filter_args(filters, filter_of, nq):
+        ft = filters if isinstance(filters, FilterTable) else marshal_filters(filters)
+        if filter_of is None:
+            if ft.n_filters != 1:
+                raise ValueError("a table of %d filters needs filter_of" % ft.n_filters)
+            of = np.zeros(nq, dtype=np.uint32)
+        else:
+            of = np.ascontiguousarray(np.asarray(filter_of).reshape(-1), dtype=np.uint32)
+            if of.shape[0] != nq:
+                raise ValueError("expected %d filter_of entries, got %d" % (nq, of.shape[0]))
+        return ft, of
+
+    @staticmethod
+    def _filter_device_args(d_queries, filters, d_filter_of):
+        nq = d_queries.shape[0] if hasattr(d_queries, "shape") else None
+        if nq is None:
+            raise ValueError("pass torch tensors (queries [nq, dims], filter_of)")
+        ft = filters if isinstance(filters, FilterTable) else marshal_filters(filters)
+        if hasattr(d_filter_of, "numel") and d_filter_of.numel() < nq:
+            raise ValueError("%d filter_of entries for %d queries" % (d_filter_of.numel(), nq))
+        return nq, ft
+
+    def knn_filter(self, queries, k, filters, filter_of=None):
+        """knn_masked_multi under the bitmaps the filters describe (ehx_knn_filter): query i sees row r iff SOME clause of
+        filters[filter_of[i]] holds for r's stored column values — a row several clauses allow is returned once.  filters: a
+        list of filters (marshal_filters) or a FilterTable, at most 64; filter_of: [nq] indices, or None with one filter.
+        -> ids [nq,k] u64, dist [nq,k] f32, count [nq] u32."""
+        q, pq = _f32(queries)
+        q = q.reshape(-1, self.dims)
+        nq = q.shape[0]
+        ft, of = self._filter_args(filters, filter_of, nq)
+        (ids, dist, cnt), out = _results(nq, k)
+        check(self._L.ehx_knn_filter(self._h, nq, pq, k, C.byref(ft.struct), of.ctypes.data_as(C.POINTER(C.c_uint32)), *out))
+        return ids[:, :k], dist[:, :k], cnt
+
+    def knn_filter_device(self, d_queries, k, filters, d_filter_of, d_ids, d_dist, d_count, stream=None):
+        """knn_filter with queries, filter_of ([nq] u32, int32 storage) and results on the device (torch CUDA tensors, as
+        knn_masked_multi_device's); the filters stay on the host."""
+        nq, ft = self._filter_device_args(d_queries, filters, d_filter_of)
+        check(self._L.ehx_knn_filter_device(self._h, C.c_void_p(stream or 0), nq, _ptr(d_queries), k, C.byref(ft.struct),
+                                            _ptr(d_filter_of), _ptr(d_ids), _ptr(d_dist), _ptr(d_count)))
+
+    def knn_grouped_filter(self, queries, k, group_col, filters, filter_of=None, per_group=1):
+        """knn_grouped_masked under the filters' bitmaps, the groups read from the stored column group_col
+        (ehx_knn_grouped_filter).  -> ids [nq,k] u64, dist [nq,k] f32, count [nq] u32."""
+        q, pq = _f32(queries)
+        q = q.reshape(-1, self.dims)
+        nq = q.shape[0]
+        ft, of = self._filter_args(filters, filter_of, nq)
+        (ids, dist, cnt), out = _results(nq, k)
+        check(self._L.ehx_knn_grouped_filter(self._h, nq, pq, k, int(per_group), int(group_col), C.byref(ft.struct),
+                                             of.ctypes.data_as(C.POINTER(C.c_uint32)), *out))
+        return ids[:, :k], dist[:, :k], cnt
+
+    def knn_grouped_filter_device(self, d_queries, k, group_col, filters, d_filter_of, d_ids, d_dist, d_count, per_group=1,
+                                  stream=None):
+        """knn_grouped_filter without queries or results leaving the device: tensors as knn_filter_device's."""
+        nq, ft = self._filter_device_args(d_queries, filters, d_filter_of)
+        check(self._L.ehx_knn_grouped_filter_device(self._h, C.c_void_p(stream or 0), nq, _ptr(d_queries), k, int(per_group),
+                                                    int(group_col), C.byref(ft.struct), _ptr(d_filter_of), _ptr(d_ids),
+                                                    _ptr(d_dist), _ptr(d_count)))
+
+    def range_filter(self, queries, radius, max_results, filters, filter_of=None):
+        """range_masked under the filters' bitmaps (ehx_range_filter).
+        -> ids [nq, max_results] u64, dist [nq, max_results] f32, count [nq] u32, total [nq] u64."""
+        nq, pq, r, (ids, dist, cnt, total), out, keep = self._range_args(queries, radius, max_results)
+        ft, of = self._filter_args(filters, filter_of, nq)
+        check(self._L.ehx_range_filter(self._h, nq, pq, r.ctypes.data_as(C.POINTER(C.c_float)), max_results, C.byref(ft.struct),
+                                       of.ctypes.data_as(C.POINTER(C.c_uint32)), *out))
+        del keep
+        return ids[:, :max_results], dist[:, :max_results], cnt, total
+
+    def range_filter_device(self, d_queries, d_radius, max_results, filters, d_filter_of, d_ids, d_dist, d_count, d_total=None,
+                            stream=None):
+        """range_filter without queries, radii or results leaving the device: tensors as range_masked_device's."""
+        nq, ft = self._filter_device_args(d_queries, filters, d_filter_of)
+        if hasattr(d_radius, "shape") and tuple(d_radius.shape) != (nq,):
+            raise ValueError("expected %d radii, got shape %s" % (nq, tuple(d_radius.shape)))
+        check(self._L.ehx_range_filter_device(self._h, C.c_void_p(stream or 0), nq, _ptr(d_queries), _ptr(d_radius), max_results,
+                                              C.byref(ft.struct), _ptr(d_filter_of), _ptr(d_ids), _ptr(d_dist), _ptr(d_count),
+                                              _ptr(d_total)))
+
+    def graph_knn_filter(self, queries, k, filters, filter_of=None, route=_lib.WALK_AUTO):
+        """graph_knn_masked_multi under the filters' bitmaps (ehx_graph_knn_filter): the graph WALK under Boolean filters,
+        the exact answer, or both by filter — route as graph_knn_masked_multi's.
+        -> ids [nq,k] u64, dist [nq,k] f32, count [nq] u32."""
+        q, pq = _f32(queries)
+        q = q.reshape(-1, self.dims)
+        nq = q.shape[0]
+        ft, of = self._filter_args(filters, filter_of, nq)
+        (ids, dist, cnt), out = _results(nq, k)
+        check(self._L.ehx_graph_knn_filter(self._h, nq, pq, k, C.byref(ft.struct), of.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                           int(route), *out))
+        return ids[:, :k], dist[:, :k], cnt
+
+    def graph_knn_filter_device(self, d_queries, k, filters, d_filter_of, d_ids, d_dist, d_count, route=_lib.WALK_AUTO,
+                                stream=None):
+        """graph_knn_filter without queries or results leaving the device: tensors as knn_filter_device's."""
+        nq, ft = self._filter_device_args(d_queries, filters, d_filter_of)
+        check(self._L.ehx_graph_knn_filter_device(self._h, C.c_void_p(stream or 0), nq, _ptr(d_queries), k, C.byref(ft.struct),
+                                                  _ptr(d_filter_of), int(route), _ptr(d_ids), _ptr(d_dist), _ptr(d_count)))
+
     # ---- kNN under a row bitmap on the graph path ----
     def graph_knn_masked(self, queries, k, allow, n_bits=None, route=_lib.WALK_AUTO):
         """The k nearest ALLOWED rows the graph walk finds (ehx_graph_knn_masked): approximate when walked, possibly fewer
@@ -1052,6 +1156,83 @@ def marshal_preds(preds):
                 raise ValueError("predicate %d, term %d: bounds must fit 32 bits (unsigned)" % (p, t))
             table[p].terms[t] = _lib.Term(col, lo, hi, _lib.TERM_NOT if len(term) == 4 and term[3] else 0)
     return table, len(preds)
+
+
+class FilterTable:
+    """A marshalled table of Boolean filters (marshal_filter_table): .struct is the ehx_filters the *_filter calls take; the
+    arrays it points into live as long as this object."""
+
+    def __init__(self, clauses, values, runs):
+        self.clauses, self.values, self.runs = clauses, values, runs
+        self.n_clauses, self.n_values, self.n_filters = len(clauses), len(values), len(runs)
+        self.struct = _lib.Filters(clauses if len(clauses) else None, len(clauses),
+                                   values.ctypes.data_as(C.POINTER(C.c_uint32)) if len(values) else None, len(values),
+                                   runs if len(runs) else None, len(runs))
+
+
+def marshal_filter_table(clauses, runs, pack=True):
+    """Clauses and the filters' runs over them -> FilterTable.  clauses: a list of clauses, each a list of terms
+    (col, lo, hi[, negate]) — marshal_preds' range term — or (col, "in", values[, negate]): the term holds iff the stored value
+    is one of `values` (none: never; under negate: always).  runs: a list of (first_clause, n_clauses), filter f the OR of that
+    run; runs may overlap, and n_clauses == 0 is the empty disjunction, which allows no row.  pack: every IN term's set is
+    sorted and de-duplicated here, as the library would do with its private copy; False passes the values as given.
+    ValueError where the C side would say EHX_EINVAL: no filter, a run past the clauses, more than PRED_MAX_TERMS terms, a
+    column at or above MAX_COLUMNS, a bound or value outside 32 bits, a malformed term.  (More than 64 filters,
+    FILTER_MAX_CLAUSES clauses or FILTER_MAX_VALUES values are the C side's EHX_EUNSUPPORTED.)"""
+    clauses, runs = list(clauses), list(runs)
+    if not runs:
+        raise ValueError("no filter")
+    table = (_lib.Pred * len(clauses))()
+    values = []
+    for c, terms in enumerate(clauses):
+        terms = list(terms)
+        if len(terms) > _lib.PRED_MAX_TERMS:
+            raise ValueError("clause %d has %d terms: at most %d" % (c, len(terms), _lib.PRED_MAX_TERMS))
+        table[c].n_terms = len(terms)
+        for t, term in enumerate(terms):
+            if len(term) not in (3, 4):
+                raise ValueError("clause %d, term %d: expected (col, lo, hi[, negate]) or (col, 'in', values[, negate])" % (c, t))
+            col = int(term[0])
+            if not 0 <= col < _lib.MAX_COLUMNS:
+                raise ValueError("clause %d, term %d: column %d: a space has %d columns" % (c, t, col, _lib.MAX_COLUMNS))
+            flags = _lib.TERM_NOT if len(term) == 4 and term[3] else 0
+            if isinstance(term[1], str):
+                if term[1].lower() != "in":
+                    raise ValueError("clause %d, term %d: %r is not 'in'" % (c, t, term[1]))
+                vals = [int(v) for v in term[2]]
+                if any(not 0 <= v <= 0xFFFFFFFF for v in vals):
+                    raise ValueError("clause %d, term %d: values must fit 32 bits (unsigned)" % (c, t))
+                if pack:
+                    vals = sorted(set(vals))
+                table[c].terms[t] = _lib.Term(col, len(values), len(vals), flags | _lib.TERM_IN)
+                values.extend(vals)
+            else:
+                lo, hi = int(term[1]), int(term[2])
+                if not (0 <= lo <= 0xFFFFFFFF and 0 <= hi <= 0xFFFFFFFF):
+                    raise ValueError("clause %d, term %d: bounds must fit 32 bits (unsigned)" % (c, t))
+                table[c].terms[t] = _lib.Term(col, lo, hi, flags)
+    if len(values) > 0xFFFFFFFF:
+        raise ValueError("too many values")
+    fl = (_lib.Filter * len(runs))()
+    for f, (first, n) in enumerate(runs):
+        first, n = int(first), int(n)
+        if first < 0 or n < 0 or first + n > len(clauses):
+            raise ValueError("filter %d: clauses [%d, %d + %d) of %d" % (f, first, first, n, len(clauses)))
+        fl[f] = _lib.Filter(first, n)
+    return FilterTable(table, np.asarray(values, dtype=np.uint32), fl)
+
+
+def marshal_filters(filters, pack=True):
+    """The filters of the *_filter searches -> FilterTable.  filters: a list of filters, each a list of clauses (ORed), each
+    clause a list of terms (ANDed) as marshal_filter_table takes them; a filter without clauses allows no row, a clause
+    without terms every row.  Every filter gets a run of its own (marshal_filter_table shares clauses between filters).
+    ValueError as marshal_filter_table."""
+    clauses, runs = [], []
+    for f in list(filters):
+        f = list(f)
+        runs.append((len(clauses), len(f)))
+        clauses.extend(f)
+    return marshal_filter_table(clauses, runs, pack)
 
 
 def marshal_groups(group_of):

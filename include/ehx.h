@@ -766,7 +766,8 @@ int ehx_range_masked_device(ehx_space* s, void* stream, size_t n_queries, const 
  * EHX_TERM_NOT, an entry of pred_of at or above n_preds: EHX_EINVAL, the outputs unwritten; n_preds > 64: EHX_EUNSUPPORTED,
  * the bitmap table's limit, for the reason given at ehx_knn_masked_multi_device; a NULL space: EHX_EINVAL before the device
  * is looked for; a row-sharded space: EHX_EUNSUPPORTED, as for every column call; n_queries == 0: EHX_OK.  A graph space
- * answers from its stored rows: the graph walk under predicates is NOT built. */
+ * answers from its stored rows: the graph walk under predicates is NOT built.  (ORs of such predicates, IN-lists and the
+ * graph walk under them are the Boolean filters' — ehx_knn_filter* and the block behind ehx_range_where.) */
 #define EHX_PRED_MAX_TERMS 8
 #define EHX_TERM_NOT 1u
 typedef struct ehx_term {
@@ -798,6 +799,76 @@ int ehx_range_where_device(ehx_space* s, void* stream, size_t n_queries, const f
 int ehx_range_where(ehx_space* s, size_t n_queries, const float* queries, const float* radius, uint32_t max_results,
                     const ehx_pred* preds, uint32_t n_preds, const uint32_t* pred_of, uint64_t* out_ids, float* out_dist,
                     uint32_t* out_count, uint64_t* out_total);
+/* ---- Boolean filters on stored columns: OR of clauses, IN-lists, and the graph walk under them ----
+ * "tenant = 3 OR timestamp >= T", "group IN (the 30 groups of this user)": a call carries a table of FILTERS and searches
+ * query i under filter filter_of[i].  A filter is a DISJUNCTION of clauses: the run clauses[first_clause, first_clause +
+ * n_clauses) of the call's clause array; runs of different filters may overlap, so clauses can be shared.  A clause is an
+ * ehx_pred as above, unchanged: at most EHX_PRED_MAX_TERMS terms, ANDed.  In THIS form only, a term may carry EHX_TERM_IN:
+ * then lo is the first index into values[] and hi the number of values, and the term holds iff the stored value equals one of
+ * values[lo, lo + hi); EHX_TERM_NOT inverts it (NOT IN).  hi == 0 is the empty set: it never holds, and always holds under
+ * EHX_TERM_NOT.  The values need not be sorted or distinct: the library packs a private, sorted, de-duplicated copy of every
+ * term's set.  (ehx_knn_where* keep refusing every flag bit but EHX_TERM_NOT.)
+ * Filter F allows row r iff r is below the call's ONE acquire-load snapshot n_pub of the row count and some clause of F's run
+ * allows r; a clause allows r iff every one of its terms holds, range terms exactly as above (unsigned, a column never written
+ * reading as EHX_GROUP_NONE, lo > hi the empty range).  A filter with n_clauses == 0 is the empty disjunction: it allows no
+ * row and its queries get count 0.  A row that several clauses of a filter allow is ONE allowed row: it is returned once.
+ * The answers are defined by the bitmap forms: byte for byte what ehx_knn_masked_multi_device, ehx_knn_grouped_masked_device,
+ * ehx_range_masked_device and ehx_graph_knn_masked_multi_device return under the bitmaps the filters describe with n_bits =
+ * n_pub — ids, distance bytes, counts, totals, sentinels, routes, cuts, counters and waits.  The bitmaps are evaluated by ONE
+ * kernel over the columns of the prefix where they lie (k_filter.hip), every clause once however many filters
+ * share it.  A graph space WALKS under the filters through ehx_graph_knn_filter* (ehx_knn_filter* answers from its stored
+ * rows, like every exact search).
+ * The table, its clauses, values and filters are HOST memory in every form, validated before anything is enqueued; filter_of
+ * is a host array in the host forms and d_filter_of device memory in the _device forms, read back and checked in the wait
+ * d_mask_of has.  Errors are those of the bitmap form, in its order (n_filters in the place of n_masks), and: a NULL table, NULL
+ * clauses, filters or values where a count says there are some, n_filters == 0 with n_queries > 0, a filter's run past
+ * n_clauses, an IN term with lo + hi > n_values, a term's column at or above EHX_MAX_COLUMNS, n_terms > EHX_PRED_MAX_TERMS,
+ * a flag bit other than EHX_TERM_NOT | EHX_TERM_IN, an entry of filter_of at or above n_filters: EHX_EINVAL, the outputs
+ * unwritten; n_filters > 64, n_clauses > EHX_FILTER_MAX_CLAUSES, more than EHX_FILTER_MAX_VALUES values summed over the IN
+ * terms, a row-sharded space: EHX_EUNSUPPORTED; a NULL space: EHX_EINVAL before the device is looked for; n_queries == 0:
+ * EHX_OK.  Not built: nesting beyond OR-of-AND, larger sets (a job for the column index), shards. */
+#define EHX_TERM_IN 2u             /* lo = first index into values[], hi = number of values: holds iff the stored value equals one of them */
+#define EHX_FILTER_MAX_CLAUSES 128 /* per call */
+#define EHX_FILTER_MAX_VALUES 4096 /* per call: the sum of hi over the IN terms */
+typedef struct ehx_filter {
+  uint32_t first_clause, n_clauses; /* OR of clauses[first_clause .. first_clause + n_clauses) */
+} ehx_filter;
+typedef struct ehx_filters {
+  const ehx_pred* clauses;
+  uint32_t n_clauses;
+  const uint32_t* values;
+  uint32_t n_values;
+  const ehx_filter* filters;
+  uint32_t n_filters; /* <= 64, the bitmap table's limit */
+} ehx_filters;        /* host memory in every form */
+/* ehx_knn_masked_multi_device under the filters' bitmaps. */
+int ehx_knn_filter_device(ehx_space* s, void* stream, size_t n_queries, const float* d_queries, uint32_t k,
+                          const ehx_filters* filters, const uint32_t* d_filter_of, uint64_t* d_out_ids, float* d_out_dist,
+                          uint32_t* d_out_count);
+int ehx_knn_filter(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, const ehx_filters* filters,
+                   const uint32_t* filter_of, uint64_t* out_ids, float* out_dist, uint32_t* out_count);
+/* ehx_knn_grouped_masked_device under the filters' bitmaps, the stored column group_col as its labels (as
+ * ehx_knn_grouped_where*).  With n_filters == 1, filter_of may be NULL: every query under filter 0. */
+int ehx_knn_grouped_filter_device(ehx_space* s, void* stream, size_t n_queries, const float* d_queries, uint32_t k,
+                                  uint32_t per_group, uint32_t group_col, const ehx_filters* filters,
+                                  const uint32_t* d_filter_of, uint64_t* d_out_ids, float* d_out_dist, uint32_t* d_out_count);
+int ehx_knn_grouped_filter(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, uint32_t per_group,
+                           uint32_t group_col, const ehx_filters* filters, const uint32_t* filter_of, uint64_t* out_ids,
+                           float* out_dist, uint32_t* out_count);
+/* ehx_range_masked_device under the filters' bitmaps.  With n_filters == 1, filter_of may be NULL. */
+int ehx_range_filter_device(ehx_space* s, void* stream, size_t n_queries, const float* d_queries, const float* d_radius,
+                            uint32_t max_results, const ehx_filters* filters, const uint32_t* d_filter_of, uint64_t* d_out_ids,
+                            float* d_out_dist, uint32_t* d_out_count, uint64_t* d_out_total);
+int ehx_range_filter(ehx_space* s, size_t n_queries, const float* queries, const float* radius, uint32_t max_results,
+                     const ehx_filters* filters, const uint32_t* filter_of, uint64_t* out_ids, float* out_dist,
+                     uint32_t* out_count, uint64_t* out_total);
+/* ehx_graph_knn_masked_multi_device under the filters' bitmaps: route is EHX_WALK_AUTO, EHX_WALK_GRAPH or EHX_WALK_EXACT,
+ * with that call's meaning (EHX_WALK_AUTO decides per filter from its allowed rows; a flat space takes the exact route). */
+int ehx_graph_knn_filter_device(ehx_space* s, void* stream, size_t n_queries, const float* d_queries, uint32_t k,
+                                const ehx_filters* filters, const uint32_t* d_filter_of, uint32_t route, uint64_t* d_out_ids,
+                                float* d_out_dist, uint32_t* d_out_count);
+int ehx_graph_knn_filter(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, const ehx_filters* filters,
+                         const uint32_t* filter_of, uint32_t route, uint64_t* out_ids, float* out_dist, uint32_t* out_count);
 /* k-way merge of per-shard results (RCCL all-gather output): lists laid out
  * [n_lists][n_queries][k]; ids must already be global.  Ordered by (dist, id). */
 int ehx_merge_topk_device(void* stream, size_t n_queries, uint32_t k, uint32_t n_lists,
