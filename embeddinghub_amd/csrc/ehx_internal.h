@@ -586,6 +586,13 @@ struct ehx_space {
   std::atomic<uint64_t> grouped_ctr[5] = {};
   std::atomic<uint64_t> groupedm_ctr[5] = {};
   std::atomic<uint64_t> groupedl_ctr[5] = {};
+  // MMR search (ehx_mmr.cpp; scratch_mu): the candidate block of ehx_knn_mmr* — ids | distances | counts at fetch_k, what the
+  // space's own kNN writes and the selection kernel reads; the space's clock fences it across streams — and a host call's
+  // staged queries and results.
+  struct Mmr {
+    DevBuf<unsigned char> dCand;
+    HostStage host;
+  } mmr;
   // Stored label columns (ehx_columns.cpp): column c is one uint32_t per row, written through the write path by key.
   // dCol[c] is sized to `cap` and moved by grow with the rows; col_live[c] turns true under mu held exclusively, at the
   // column's first write (readers hold mu at least shared; the writers, serialised by wmu, may read it under wmu alone).  A
@@ -719,6 +726,7 @@ struct ehx_space {
     masked = {};
     largek = {};
     grouped = {};
+    mmr = {};
     cols = {};
     for (auto& x : colidx) x = ColIndex{};
     one = {};

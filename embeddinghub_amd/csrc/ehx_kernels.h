@@ -481,6 +481,23 @@ hipError_t launch_among(const AmongArgs& a, hipStream_t st);
 hipError_t launch_among_emit(const uint64_t* merged, uint32_t nq, uint32_t k, uint32_t out_stride, uint32_t out_offset,
                              uint64_t* out_ids, float* out_dist, uint32_t* out_count, hipStream_t st);
 
+// MMR re-ranking of candidate lists (k_mmr.hip): per query, from the first min(cand_count[q], fetch_k) entries of its list,
+// greedily the k least by lambda * dq - (1 - lambda) * (distance to the nearest pick so far); include/ehx.h has the contract
+constexpr uint32_t kMmrMaxFetch = 256;   // candidates per query: one thread of the workgroup each
+struct MmrArgs {
+  RowsView rows;               // stored rows, any layout; an id at or above rows.n_rows is no candidate
+  const uint64_t* cand_ids;    // [nq][fetch_k] as every *_device search writes its lists
+  const float* cand_dist;      // [nq][fetch_k]
+  const uint32_t* cand_count;  // [nq]
+  uint64_t* out_ids;           // [nq][k] in pick order, sentinels behind the count; must not overlap the candidates
+  float* out_dist;             // [nq][k]
+  uint32_t* out_count;         // [nq]
+  uint32_t nq, fetch_k, k;     // 1 <= k <= fetch_k <= kMmrMaxFetch
+  float lambda;                // in [0, 1]
+};
+uint32_t mmr_max_ld();   // longest row stride (floats): the prepared pivot and the kernel's tables share one CU's LDS
+hipError_t launch_mmr_select(const MmrArgs& a, hipStream_t st);
+
 // exact range search (k_range.hip): every row with canonical distance <= radius[q].  The control words are per query
 // SLOT j (slot j answers query sel[j], or j when sel == nullptr): pool_cnt[j] counts every member — stored in
 // pool[j][kPoolCap] only while a slot is free — so it is the exact total, and pool_cnt[j] > kPoolCap is the overflow verdict.

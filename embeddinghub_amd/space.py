@@ -466,6 +466,42 @@ class Space:
         check(self._L.ehx_knn_grouped_device(self._h, C.c_void_p(stream or 0), nq, _ptr(d_queries), k, int(per_group),
                                              _ptr(d_group_of), int(n_labels), _ptr(d_ids), _ptr(d_dist), _ptr(d_count)))
 
+    # ---- MMR search: k of fetch_k candidates, near the query and not near each other ----
+    def knn_mmr(self, queries, k, fetch_k=None, lam=0.5):
+        """Maximal marginal relevance (ehx_knn_mmr): the fetch_k nearest rows of every query (knn's answer at fetch_k),
+        then greedily the k least by lam * distance - (1 - lam) * (distance to the nearest pick so far), selected on the
+        device.  fetch_k defaults to min(256, 4 k); 1 <= k <= fetch_k <= 256.  lam = 1 is knn at k.  Rows in PICK order.
+        -> ids [nq,k] u64, dist [nq,k] f32 (to the query), count [nq] u32."""
+        q, pq = _f32(queries)
+        q = q.reshape(-1, self.dims)
+        nq = q.shape[0]
+        fetch_k = min(_lib.MMR_MAX_FETCH, 4 * k) if fetch_k is None else int(fetch_k)
+        (ids, dist, cnt), out = _results(nq, k)
+        check(self._L.ehx_knn_mmr(self._h, nq, pq, k, fetch_k, float(lam), *out))
+        return ids[:, :k], dist[:, :k], cnt
+
+    def knn_mmr_device(self, d_queries, k, fetch_k, lam, d_ids, d_dist, d_count, stream=None):
+        """knn_mmr without anything leaving the device: torch CUDA tensors, d_queries [nq, dims] f32, outputs [nq, k] as
+        knn_device's."""
+        nq = d_queries.shape[0] if hasattr(d_queries, "shape") else None
+        if nq is None:
+            raise ValueError("pass torch tensors (queries [nq, dims])")
+        check(self._L.ehx_knn_mmr_device(self._h, C.c_void_p(stream or 0), nq, _ptr(d_queries), k, int(fetch_k), float(lam),
+                                         _ptr(d_ids), _ptr(d_dist), _ptr(d_count)))
+
+    def mmr_select_device(self, d_cand_ids, d_cand_dist, d_cand_count, k, lam, d_ids, d_dist, d_count, stream=None):
+        """The selection alone (ehx_mmr_select_device) over candidate lists already on the device, laid out as every *_device
+        search writes them: d_cand_ids [nq, fetch_k] u64 (int64 storage), d_cand_dist [nq, fetch_k] f32, d_cand_count [nq]
+        u32 (int32 storage); outputs [nq, k], distinct from the candidates."""
+        if not hasattr(d_cand_ids, "shape") or len(d_cand_ids.shape) != 2:
+            raise ValueError("pass torch tensors (candidate ids [nq, fetch_k], distances, counts)")
+        nq, fetch_k = d_cand_ids.shape
+        if tuple(d_cand_dist.shape) != (nq, fetch_k) or d_cand_count.numel() < nq:
+            raise ValueError("candidate distances %s / counts %d do not match ids [%d, %d]"
+                             % (tuple(d_cand_dist.shape), d_cand_count.numel(), nq, fetch_k))
+        check(self._L.ehx_mmr_select_device(self._h, C.c_void_p(stream or 0), nq, fetch_k, _ptr(d_cand_ids), _ptr(d_cand_dist),
+                                            _ptr(d_cand_count), k, float(lam), _ptr(d_ids), _ptr(d_dist), _ptr(d_count)))
+
     # ---- grouped kNN under row bitmaps: filter first, then at most per_group rows per group label ----
     def knn_grouped_masked(self, queries, k, group_of, allows, mask_of=None, per_group=1, n_bits=None):
         """knn_grouped over the allowed rows alone (ehx_knn_grouped_masked): query i is answered under allows[mask_of[i]];

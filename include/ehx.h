@@ -869,6 +869,51 @@ int ehx_graph_knn_filter_device(ehx_space* s, void* stream, size_t n_queries, co
                                 float* d_out_dist, uint32_t* d_out_count);
 int ehx_graph_knn_filter(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, const ehx_filters* filters,
                          const uint32_t* filter_of, uint32_t route, uint64_t* out_ids, float* out_dist, uint32_t* out_count);
+/* MMR (maximal marginal relevance) re-ranking on the device: from a query's candidate list, greedily the k entries that are
+ * near the query and not near each other — max_marginal_relevance_search(k, fetch_k, lambda) of the vector-store clients,
+ * without fetch_k rows per query leaving HBM.  The candidate lists are laid out exactly as every *_device search writes its
+ * results — d_cand_ids / d_cand_dist [n_queries][fetch_k], d_cand_count [n_queries] — so the call composes with the plain,
+ * masked, filter, labeled, grouped and graph searches; entries behind a query's count are ignored.
+ * The contract, for one query with the c = min(count, fetch_k) candidates (id_j, dq_j), j = 0 .. c - 1 the RANK:
+ *   pair(a, b)  the canonical distance of stored row a to stored row b taken as the query: row b as ehx_get_by_id returns it,
+ *               prepared as any query is (padded; cosine: normalised with the canonical sequential norm) — byte for byte
+ *               the distance ehx_knn_by_ids_device reports for row a in the list of row b.
+ *   near_j      starts at +Inf.  The first pick is rank 0.  After each pick p, for every unpicked j: d = pair(id_j, id_p),
+ *               and near_j = d iff d < near_j (a NaN never lowers it).
+ *   cost_j      a_j - b_j in fp32, every operation rounded on its own: a_j = lambda * dq_j, or 0 where lambda == 0;
+ *               b_j = mu * near_j with mu = 1.0f - lambda, or 0 where mu == 0 (the two rules keep 0 * Inf out).
+ *   next pick   the unpicked j least by (cost, rank): costs compared as IEEE values (-0 equals +0), a NaN cost behind +Inf.
+ *   stop        after min(k, c) picks.  Output in PICK order: the id and dq of each pick, the number of picks in
+ *               d_out_count, sentinels (id 2^64 - 1, +Inf) behind it.
+ * In distance space this is MMR for all three metrics: for inner product and cosine the "1 -" of the distance adds the same
+ * constant to every candidate's cost.  The result is defined in fp32, so two implementations agree to the byte.
+ * The call takes ONE acquire-load snapshot of the row count; a candidate whose id is at or above it is skipped as if it were
+ * not in the list: never picked, never a pivot (the first pick is then the lowest rank that is a row, and the picks stop
+ * after min(k, rows among the c)).
+ * Consequences: k == 1 gives rank 0; lambda == 1 gives the first min(k, c) candidates of a list in ascending distance order
+ * — as every search writes it — unchanged, byte for byte.  lambda == 1, k == 1 and c <= 1 read no row.
+ * The outputs must not overlap the candidate arrays.
+ * Errors: a NULL space, k == 0, k > fetch_k, lambda NaN or outside [0, 1], NULL outputs or inputs: EHX_EINVAL, all decided
+ * before the device is looked for; fetch_k > EHX_MMR_MAX_FETCH, a row-sharded space, rows longer than 38 624 floats (the
+ * prepared pivot and the kernel's tables share one CU's LDS): EHX_EUNSUPPORTED; a dropped space: EHX_ENOTFOUND;
+ * n_queries == 0: EHX_OK.  Asynchronous on `stream`; a Set that rewrites rows in place waits for the call like for any
+ * search.  DESIGN.md §e.28. */
+#define EHX_MMR_MAX_FETCH 256u
+int ehx_mmr_select_device(ehx_space* s, void* stream, size_t n_queries, uint32_t fetch_k, const uint64_t* d_cand_ids,
+                          const float* d_cand_dist, const uint32_t* d_cand_count, uint32_t k, float lambda,
+                          uint64_t* d_out_ids, float* d_out_dist, uint32_t* d_out_count);
+/* MMR search: the candidates are what ehx_knn_device returns for d_queries at k = fetch_k on this space, whatever route
+ * serves it (the engine chain, the large-k route for 48 < fetch_k <= 256, a graph space's walk); ehx_mmr_select_device's
+ * selection follows.  One shared hold of the space covers both steps, and on a flat space ONE snapshot of the row count (a
+ * graph space's walk takes its own; the selection's is read behind it, so every id the walk returned is a row of it).  The
+ * candidate block is the space's own scratch.  Outputs [n_queries][k]; 1 <= k <= fetch_k <= EHX_MMR_MAX_FETCH.  Errors as
+ * ehx_mmr_select_device.  The kNN step waits for its verdicts as ehx_knn_device does; the selection is asynchronous on
+ * `stream`. */
+int ehx_knn_mmr_device(ehx_space* s, void* stream, size_t n_queries, const float* d_queries, uint32_t k, uint32_t fetch_k,
+                       float lambda, uint64_t* d_out_ids, float* d_out_dist, uint32_t* d_out_count);
+/* MMR search from host pointers: ehx_knn_mmr_device plus the H2D / D2H copies, on the space's own stream. */
+int ehx_knn_mmr(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, uint32_t fetch_k, float lambda,
+                uint64_t* out_ids, float* out_dist, uint32_t* out_count);
 /* k-way merge of per-shard results (RCCL all-gather output): lists laid out
  * [n_lists][n_queries][k]; ids must already be global.  Ordered by (dist, id). */
 int ehx_merge_topk_device(void* stream, size_t n_queries, uint32_t k, uint32_t n_lists,
