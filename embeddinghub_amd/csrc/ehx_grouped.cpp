@@ -225,12 +225,7 @@ int grouped_answer(ehx_space* s, hipStream_t st, size_t nq, const float* d_queri
   return w.group.rerun(s, st, d_queries, idx, k, answer, out.ids, out.dist, out.cnt);
 }
 
-}  // namespace ehx_impl
-
-namespace {
-
-// an unsharded space, locked shared, scratch_mu held, its device current; everything is enqueued on `st`.  n_pub: the call's
-// ONE read of the row count; d_group_of: at least min(n_pub, n_labels) labels on the device
+// (ehx_internal.h has its contract; the MaxSim search enters here too, ehx_maxsim.cpp)
 int grouped_locked(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, const float* d_queries, uint32_t k,
                    uint32_t per_group, const uint32_t* d_group_of, uint64_t n_labels, const ResultBlock& out) {
   int rc;
@@ -250,6 +245,10 @@ int grouped_locked(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, cons
   v.ctr = s->grouped_ctr;
   return grouped_answer(s, st, nq, d_queries, k, per_group, d_group_of, v, out);
 }
+
+}  // namespace ehx_impl
+
+namespace {
 
 // host pointers in, host pointers out, on the space's stream (on_device): the labels of the prefix staged in grouped.dLabels
 int grouped_host_locked(ehx_space* s, size_t nq, const float* queries, uint32_t k, uint32_t per_group, const uint32_t* group_of,

@@ -593,6 +593,19 @@ struct ehx_space {
     DevBuf<unsigned char> dCand;
     HostStage host;
   } mmr;
+  // MaxSim search (ehx_maxsim.cpp; scratch_mu): the prepared query vectors of a call; for ehx_knn_maxsim* the live query
+  // vectors compacted (dLive; dIdx: their positions | every query's first live vector), the grouped search's answer for them
+  // at fetch_k (dFetch: a result block) and the candidate block made of it (dCand: labels | counts); a host call's staged
+  // vectors, token counts and results.  The space's clock fences all of it across streams.  dWork: candidates scored, rows
+  // walked (the kernel adds to them); calls and rebuilds (index rebuilds a call caused): test hook ehx_test_maxsim_counters.
+  struct Maxsim {
+    DevBuf<float> dQ, dLive;
+    DevBuf<uint32_t> dIdx, dCand, dTok;
+    DevBuf<unsigned char> dFetch;
+    DevBuf<unsigned long long> dWork;
+    HostStage host;
+    uint64_t calls = 0, rebuilds = 0;
+  } maxsim;
   // Stored label columns (ehx_columns.cpp): column c is one uint32_t per row, written through the write path by key.
   // dCol[c] is sized to `cap` and moved by grow with the rows; col_live[c] turns true under mu held exclusively, at the
   // column's first write (readers hold mu at least shared; the writers, serialised by wmu, may read it under wmu alone).  A
@@ -727,6 +740,7 @@ struct ehx_space {
     largek = {};
     grouped = {};
     mmr = {};
+    maxsim = {};
     cols = {};
     for (auto& x : colidx) x = ColIndex{};
     one = {};
@@ -1148,6 +1162,10 @@ int grouped_list(ehx_space* s, hipStream_t st, uint64_t n_eff, const uint64_t* d
 // n_filters, n_allowed, off, filter_of, scans, d_list, allow*, d_head, head_of and ctr.
 int grouped_answer(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, uint32_t per_group,
                    const uint32_t* d_group_of, const FilterView& v, const ResultBlock& out);
+// ehx_knn_grouped_device's body: an unsharded space, locked shared, scratch_mu held, its device current; everything is
+// enqueued on `st`.  n_pub: the call's ONE read of the row count; d_group_of: at least min(n_pub, n_labels) labels on the device
+int grouped_locked(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, const float* d_queries, uint32_t k,
+                   uint32_t per_group, const uint32_t* d_group_of, uint64_t n_labels, const ResultBlock& out);
 
 // ---- ehx_labeled.cpp ----
 // The label column of one device batch, compacted for the batch's distinct wanted labels ("slots"): the slot of every query,

@@ -498,6 +498,36 @@ struct MmrArgs {
 uint32_t mmr_max_ld();   // longest row stride (floats): the prepared pivot and the kernel's tables share one CU's LDS
 hipError_t launch_mmr_select(const MmrArgs& a, hipStream_t st);
 
+// MaxSim scoring of candidate entities (k_maxsim.hip): per query, every distinct candidate label that the column index knows
+// is scored against the query's vectors — the sum over the vectors of the least distance among the label's rows — and the
+// first k by (score, label) are written; include/ehx.h has the contract
+constexpr uint32_t kMaxsimMaxTokens = 32;   // query vectors per query: the width of a slab's table of minima
+constexpr uint32_t kMaxsimMaxCand = 1024;   // candidate labels per query: the keys the epilogue sorts in LDS
+struct MaxsimArgs {
+  RowsView rows;                // stored rows, any layout; the index names rows below rows.n_rows only
+  const float* Q;               // prepared query vectors [nq][n_tokens][ld] (launch_prep_queries)
+  const uint32_t* token_count;  // [nq] or nullptr: n_tokens; a value above n_tokens is clamped
+  const uint32_t* cand;         // [nq][n_cand] candidate labels
+  const uint32_t* cand_count;   // [nq]; a value above n_cand is clamped
+  const uint32_t* labels;       // the column's index (ehx_space::ColIndex): [n_labels] ascending |
+  const uint32_t* start;        // [n_labels + 1] where every label's run begins in perm |
+  const uint64_t* perm;         // the row ids by (label, row id)
+  uint64_t* out_ids;            // [nq][k] labels zero-extended, sentinels behind the count
+  float* out_score;             // [nq][k]
+  uint32_t* out_count;          // [nq]
+  unsigned long long* work;     // [2] candidates scored, rows walked: added to (test hook)
+  uint32_t nq, n_tokens, n_cand, n_labels, k;   // n_tokens <= kMaxsimMaxTokens; n_cand, k <= kMaxsimMaxCand
+};
+uint32_t maxsim_max_ld();   // longest row stride (floats): a block of prepared query vectors and the kernel's tables share one CU's LDS
+hipError_t launch_maxsim_score(const MaxsimArgs& a, hipStream_t st);
+// the candidate block of ehx_knn_maxsim*: the rows the grouped search returned for the live query vectors (ids [*][fetch_k],
+// cnt [*]; cnt == nullptr: none), turned into their labels col[id] (ids at or above n_rows and entries behind a count:
+// kGroupNone).  Query i owns the live vectors [base[i], base[i] + T_i) (base == nullptr: i * n_tokens), T_i as MaxsimArgs';
+// cand[i][t * fetch_k + j] and cand_count[i] = T_i * fetch_k are written, n_cand = n_tokens * fetch_k.
+hipError_t launch_maxsim_labels(const uint64_t* ids, const uint32_t* cnt, const uint32_t* col, uint64_t n_rows,
+                                const uint32_t* base, const uint32_t* token_count, uint32_t nq, uint32_t n_tokens,
+                                uint32_t fetch_k, uint32_t* cand, uint32_t* cand_count, hipStream_t st);
+
 // exact range search (k_range.hip): every row with canonical distance <= radius[q].  The control words are per query
 // SLOT j (slot j answers query sel[j], or j when sel == nullptr): pool_cnt[j] counts every member — stored in
 // pool[j][kPoolCap] only while a slot is free — so it is the exact total, and pool_cnt[j] > kPoolCap is the overflow verdict.

@@ -24,6 +24,8 @@
 // ... and of the filtered searches (ehx_masked.cpp, k_masked.hip):
 //   ehx_test_filter_routes     the routing rule (filter_routes_cut, then _gate), host arithmetic only (no device, no space)
 //   ehx_test_rows_prefix       launch_rows_prefix on host arrays (a device, no space)
+// ... and of the MaxSim search (ehx_maxsim.cpp, k_maxsim.hip):
+//   ehx_test_maxsim_counters   calls, candidates scored, rows walked, index rebuilds the calls caused
 // No production path calls in here.
 #include "ehx_internal.h"
 
@@ -504,6 +506,29 @@ int ehx_test_rows_prefix(const uint32_t* counts, uint32_t rows, uint32_t n, uint
   HIP_TRY(launch_rows_prefix(d.p, rows, n, nullptr));
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(out, d.p, words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return EHX_OK;
+}
+
+// MaxSim search (ehx_maxsim.cpp): calls, candidates scored, rows walked, index rebuilds the calls caused.  Waits for the
+// space's searches in flight (the kernels add to the middle two).
+int ehx_test_maxsim_counters(ehx_space* s, uint64_t out[4]) {
+  int rc = hook_space(s, "ehx_test_maxsim_counters", 0);
+  if (rc) return rc;
+  if (!out) return fail(EHX_EINVAL, "NULL argument");
+  std::shared_lock<std::shared_mutex> rl(s->mu);
+  std::lock_guard<std::mutex> sl(s->scratch_mu);
+  HIP_TRY(hipSetDevice(s->device));
+  unsigned long long work[2] = {0, 0};
+  if (s->maxsim.dWork.p) {
+    const hipStream_t st = s->stream;
+    if ((rc = wait_searches_in_flight(s, st))) return rc;
+    HIP_TRY(hipMemcpyAsync(work, s->maxsim.dWork.p, sizeof(work), hipMemcpyDeviceToHost, st));
+    if ((rc = sync_stream(s, st))) return rc;
+  }
+  out[0] = s->maxsim.calls;
+  out[1] = work[0];
+  out[2] = work[1];
+  out[3] = s->maxsim.rebuilds;
   return EHX_OK;
 }
 

@@ -12,7 +12,8 @@
 // metric01: 0 = L2^2, 1 = 1 - inner product.  For cosine the stored row is normalised on the fly (x * inv_norm, one
 // rounding — hnswlib-python's normalize_vector) and the query arrives normalised.
 // The walkers differ only in who plays the four SSE lanes and how the row reaches them: a 4-lane group over plain fp32 or
-// binary16 rows (canon_dist), one lane with 16-byte loads (canon_dist_lane_t), a 4-lane group over the block-permuted
+// binary16 rows (canon_dist), one lane with 16-byte loads (canon_dist_lane_t; canon_dist_lane_multi: the same lane against
+// several queries at once), a 4-lane group over the block-permuted
 // search copy (canon_dist_group_t, _pair, _quad; wave_group_dists hands a wave's rows to them), one lane over two rows of
 // the search copy (row_row_dist).
 #pragma once
@@ -250,6 +251,56 @@ __device__ __forceinline__ float canon_dist_lane_t(const float* __restrict__ q, 
 #undef EHX_LANE_STEP
   float res = canon_hsum(p0, p1, p2, p3);
   EHX_CANON_FINISH(METRIC01, res, body, dims, EHX_CANON_RUN(METRIC01, false, tail, q, 1.0f, false, x, xscale, SCALE, true, body, dims, 1))
+}
+
+// ONE lane, one plain fp32 row against NQ prepared queries q, q + qld, ..., q + (NQ - 1) qld (the MaxSim scoring,
+// k_maxsim.hip: the query vectors of a block are staged in LDS, and every lane of a wave reads the same piece of them — a
+// broadcast).  The row's 16-byte pieces are loaded ONCE, four at a time with the next four requested ahead of the
+// products, and each piece is run against all NQ queries: NQ x 4 partial sums.  Per query the additions and their order are
+// canon_dist_lane_t's — piece after piece, element j of a piece into partial sum j, the same join — so res[j] is the byte
+// that walker returns for query j.  Requires 16-byte aligned q, qld % 4 == 0 and x.
+template <int METRIC01, bool SCALE>
+__device__ __forceinline__ float canon_lane_join(float res, const float* __restrict__ q, const float* __restrict__ x,
+                                                 float xscale, uint32_t body, uint32_t dims) {
+  EHX_CANON_FINISH(METRIC01, res, body, dims, EHX_CANON_RUN(METRIC01, false, tail, q, 1.0f, false, x, xscale, SCALE, true, body, dims, 1))
+}
+template <int METRIC01, bool SCALE, int NQ>
+__device__ __forceinline__ void canon_dist_lane_multi(const float* __restrict__ q, uint32_t qld, const float* __restrict__ x,
+                                                      float xscale, uint32_t dims, float (&res)[NQ]) {
+  const uint32_t body = canon_body(dims);
+  const uint32_t n4 = body / 4u;
+  float p[NQ][4];
+#pragma unroll
+  for (int j = 0; j < NQ; ++j) p[j][0] = p[j][1] = p[j][2] = p[j][3] = 0.0f;
+  const float4* x4 = (const float4*)x;
+#define EHX_MULTI_STEP(XV, M)                                                                                          \
+  _Pragma("unroll") for (int j_ = 0; j_ < NQ; ++j_)                                                                    \
+      canon_lane_step<METRIC01, SCALE>(XV, ((const float4*)(q + (size_t)j_ * qld))[M], xscale, p[j_][0], p[j_][1], p[j_][2], p[j_][3]);
+  uint32_t m = 0;
+  if (n4 >= 4u) {
+    float4 c0 = x4[0], c1 = x4[1], c2 = x4[2], c3 = x4[3];
+    for (; m + 4u <= n4; m += 4u) {
+      const bool more = m + 8u <= n4;   // (the last group asks for nothing: a row ends where its stride does)
+      const uint32_t a = more ? m + 4u : m;
+      const float4 n0 = x4[a], n1 = x4[a + 1u], n2 = x4[a + 2u], n3 = x4[a + 3u];
+      EHX_MULTI_STEP(c0, m)
+      EHX_MULTI_STEP(c1, m + 1u)
+      EHX_MULTI_STEP(c2, m + 2u)
+      EHX_MULTI_STEP(c3, m + 3u)
+      c0 = n0;
+      c1 = n1;
+      c2 = n2;
+      c3 = n3;
+    }
+  }
+  for (; m < n4; ++m) {
+    const float4 xv = x4[m];
+    EHX_MULTI_STEP(xv, m)
+  }
+#undef EHX_MULTI_STEP
+#pragma unroll
+  for (int j = 0; j < NQ; ++j)
+    res[j] = canon_lane_join<METRIC01, SCALE>(canon_hsum(p[j][0], p[j][1], p[j][2], p[j][3]), q + (size_t)j * qld, x, xscale, body, dims);
 }
 
 // A 4-LANE GROUP over a row of the graph-mode SEARCH COPY (launch_make_search_copy: inside every 16-float block the four

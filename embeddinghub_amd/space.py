@@ -502,6 +502,51 @@ class Space:
         check(self._L.ehx_mmr_select_device(self._h, C.c_void_p(stream or 0), nq, fetch_k, _ptr(d_cand_ids), _ptr(d_cand_dist),
                                             _ptr(d_cand_count), k, float(lam), _ptr(d_ids), _ptr(d_dist), _ptr(d_count)))
 
+    # ---- MaxSim search: a bag of vectors per query, scored per entity of a stored column ----
+    def knn_maxsim(self, tokens, k, entity_col, fetch_k=None, token_count=None):
+        """Late interaction (ehx_knn_maxsim): tokens [nq, n_tokens, dims], at most 32 vectors per query (token_count [nq]: only
+        the first token_count[i] of query i count).  An entity is a value of stored column entity_col; its score is the sum
+        over the query's vectors of the least distance among its rows.  The candidates are the entities of the fetch_k
+        nearest rows (one per entity) of every vector; fetch_k defaults to min(256, 1024 // n_tokens, 4 k), and n_tokens *
+        fetch_k <= 1024.  -> ids [nq,k] u64 (entity labels), score [nq,k] f32 ascending, count [nq] u32."""
+        q, pq = _f32(tokens)
+        if q.ndim != 3 or q.shape[2] != self.dims:
+            raise ValueError("expected tokens [nq, n_tokens, %d], got %s" % (self.dims, q.shape))
+        nq, n_tokens = q.shape[:2]
+        if fetch_k is None:
+            fetch_k = max(1, min(_lib.MAX_K_GROUPED, _lib.MAXSIM_MAX_CAND // max(n_tokens, 1), 4 * k))
+        tc = None
+        if token_count is not None:
+            tc = np.ascontiguousarray(np.asarray(token_count).reshape(-1), dtype=np.uint32)
+            if tc.shape[0] != nq:
+                raise ValueError("expected %d token counts, got %d" % (nq, tc.shape[0]))
+        (ids, score, cnt), out = _results(nq, k)
+        check(self._L.ehx_knn_maxsim(self._h, nq, n_tokens, pq, None if tc is None else tc.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                     int(entity_col), k, int(fetch_k), *out))
+        return ids[:, :k], score[:, :k], cnt
+
+    def knn_maxsim_device(self, d_tokens, d_token_count, entity_col, k, fetch_k, d_ids, d_score, d_count, stream=None):
+        """knn_maxsim without anything leaving the device: torch CUDA tensors, d_tokens [nq, n_tokens, dims] f32,
+        d_token_count [nq] u32 (int32 storage) or None, outputs [nq, k] as knn_device's."""
+        if not hasattr(d_tokens, "shape") or len(d_tokens.shape) != 3:
+            raise ValueError("pass torch tensors (tokens [nq, n_tokens, dims])")
+        nq, n_tokens = d_tokens.shape[:2]
+        check(self._L.ehx_knn_maxsim_device(self._h, C.c_void_p(stream or 0), nq, n_tokens, _ptr(d_tokens), _ptr(d_token_count),
+                                            int(entity_col), k, int(fetch_k), _ptr(d_ids), _ptr(d_score), _ptr(d_count)))
+
+    def maxsim_select_device(self, d_tokens, d_token_count, entity_col, d_cand, d_cand_count, k, d_ids, d_score, d_count,
+                             stream=None):
+        """The scoring alone (ehx_maxsim_select_device) over candidate entity labels already on the device: d_cand [nq,
+        n_cand] u32 (int32 storage), d_cand_count [nq] u32 (int32 storage); the rest as knn_maxsim_device's."""
+        if not hasattr(d_tokens, "shape") or len(d_tokens.shape) != 3 or len(d_cand.shape) != 2:
+            raise ValueError("pass torch tensors (tokens [nq, n_tokens, dims], candidate labels [nq, n_cand], counts)")
+        nq, n_tokens = d_tokens.shape[:2]
+        if d_cand.shape[0] != nq or d_cand_count.numel() < nq:
+            raise ValueError("candidate labels %s / counts %d do not match %d queries" % (tuple(d_cand.shape), d_cand_count.numel(), nq))
+        check(self._L.ehx_maxsim_select_device(self._h, C.c_void_p(stream or 0), nq, n_tokens, _ptr(d_tokens), _ptr(d_token_count),
+                                               int(entity_col), d_cand.shape[1], _ptr(d_cand), _ptr(d_cand_count), k, _ptr(d_ids),
+                                               _ptr(d_score), _ptr(d_count)))
+
     # ---- grouped kNN under row bitmaps: filter first, then at most per_group rows per group label ----
     def knn_grouped_masked(self, queries, k, group_of, allows, mask_of=None, per_group=1, n_bits=None):
         """knn_grouped over the allowed rows alone (ehx_knn_grouped_masked): query i is answered under allows[mask_of[i]];

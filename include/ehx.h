@@ -914,6 +914,61 @@ int ehx_knn_mmr_device(ehx_space* s, void* stream, size_t n_queries, const float
 /* MMR search from host pointers: ehx_knn_mmr_device plus the H2D / D2H copies, on the space's own stream. */
 int ehx_knn_mmr(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, uint32_t fetch_k, float lambda,
                 uint64_t* out_ids, float* out_dist, uint32_t* out_count);
+/* MaxSim ("late interaction") scoring on the device: a query is a bag of up to EHX_MAXSIM_MAX_TOKENS vectors (ColBERT token
+ * vectors, ColPali patch vectors, a document's chunk embeddings, a clip's frames), an entity the rows that carry one value
+ * of a stored column, and an entity's score the sum over the query's vectors of the best match among its rows — without a
+ * row of a candidate entity leaving HBM.  d_tokens [n_queries][n_tokens][dims]; d_token_count [n_queries] or NULL; the
+ * candidate lists d_cand [n_queries][n_cand] are entity labels, d_cand_count [n_queries] their numbers, so the call composes
+ * with any search whose rows are turned into labels of the column.
+ * The contract, for one query i, defined in fp32 so that two implementations agree to the byte:
+ *   vectors     the first T_i = d_token_count[i] vectors of the query (NULL: n_tokens; a value above n_tokens is clamped;
+ *               T_i == 0: count 0), each prepared as any query is (padded; cosine: normalised with the canonical sequential
+ *               norm).
+ *   snapshot    the call takes ONE acquire-load snapshot n_pub of the row count.
+ *   entities    an entity e is a value of stored column entity_col other than EHX_GROUP_NONE; its rows are the rows below
+ *               n_pub that carry e.  EHX_GROUP_NONE is no entity: every row never labelled, a column never written.
+ *   D(t, r)     the canonical distance ehx_knn reports for query vector t and row r (binary16 rows as stored, cosine rows
+ *               scaled by their inverse norm).
+ *   m_t(e)      starts at +Inf; for each row r of e, m_t = D(t, r) iff D(t, r) < m_t (a NaN never lowers it).
+ *   score(e)    ((m_0 + m_1) + m_2) + ... over t < T_i in vector order, every add rounded on its own.  For inner product and
+ *               cosine this is T_i - sum_t max_r sim(t, r): ascending score is descending MaxSim; for L2^2 it is the summed
+ *               least distance (Chamfer).
+ *   candidates  the first min(d_cand_count[i], n_cand) labels of row i of d_cand; a label given twice is scored once; a
+ *               label that no row below n_pub carries is skipped, as is EHX_GROUP_NONE.
+ *   answer      the scored candidates in (score, label) order — scores compared as IEEE values, -0 equal to +0; a NaN score
+ *               (+Inf + -Inf under inner product) is never an answer — and of them the first k: d_out_ids the label
+ *               zero-extended to 64 bits, d_out_score the score, d_out_count how many; sentinels (2^64 - 1, +Inf) behind.
+ * Errors: a NULL space, k == 0, n_tokens == 0, NULL tokens, outputs or candidate arrays, entity_col >= EHX_MAX_COLUMNS:
+ * EHX_EINVAL; n_tokens > EHX_MAXSIM_MAX_TOKENS, n_cand > EHX_MAXSIM_MAX_CAND, k > EHX_MAXSIM_MAX_CAND: EHX_EUNSUPPORTED — all
+ * of these decided before the device is looked for; a row-sharded space, rows longer than 4 192 floats (a block of eight
+ * prepared query vectors and the kernel's tables share one CU's LDS): EHX_EUNSUPPORTED; a dropped space: EHX_ENOTFOUND;
+ * n_queries == 0: EHX_OK.  Asynchronous on `stream` once the column's index is fresh; a stale index (an append, a write to the
+ * column) is rebuilt by the call, which waits for that, exactly as ehx_knn_by_label_device does.  A Set that rewrites rows
+ * in place waits for the call like for any search.  The query vectors are prepared in the space's own scratch.
+ * DESIGN.md §e.29. */
+#define EHX_MAXSIM_MAX_TOKENS 32u
+#define EHX_MAXSIM_MAX_CAND 1024u
+int ehx_maxsim_select_device(ehx_space* s, void* stream, size_t n_queries, uint32_t n_tokens, const float* d_tokens,
+                             const uint32_t* d_token_count, uint32_t entity_col, uint32_t n_cand, const uint32_t* d_cand,
+                             const uint32_t* d_cand_count, uint32_t k, uint64_t* d_out_ids, float* d_out_score,
+                             uint32_t* d_out_count);
+/* MaxSim search: the candidates of query i are the distinct entities of the rows that ehx_knn_grouped_device returns at
+ * per_group = 1, k = fetch_k with the stored column itself as d_group_of (read where it lies, as ehx_knn_grouped_by_label*
+ * reads its group column) for the sum of T_i live query vectors of the batch, whatever route serves them; rows labelled
+ * EHX_GROUP_NONE that it returns are dropped; ehx_maxsim_select_device's scoring follows.  One shared hold of the space and
+ * ONE snapshot of the row count cover both steps: the answer is byte for byte the composition of the two public calls.
+ * Requires n_tokens * fetch_k <= EHX_MAXSIM_MAX_CAND (the union of the vectors' candidates is never cut) and fetch_k <=
+ * EHX_MAX_K_GROUPED, else EHX_EUNSUPPORTED; fetch_k == 0: EHX_EINVAL; rows wider than the grouped search takes:
+ * EHX_EUNSUPPORTED; other errors as ehx_maxsim_select_device.  The scoring is exact for the candidates; like MMR's fetch_k,
+ * the retrieval is as good as the candidate set, and with fetch_k at least the number of entities (plus the rows labelled
+ * EHX_GROUP_NONE, each a group of its own in the grouped step) the answer is the exact MaxSim ranking of the whole space.  A d_token_count is read back by the call (one wait); the grouped step waits as
+ * ehx_knn_grouped_device does; the scoring is asynchronous on `stream`. */
+int ehx_knn_maxsim_device(ehx_space* s, void* stream, size_t n_queries, uint32_t n_tokens, const float* d_tokens,
+                          const uint32_t* d_token_count, uint32_t entity_col, uint32_t k, uint32_t fetch_k, uint64_t* d_out_ids,
+                          float* d_out_score, uint32_t* d_out_count);
+/* MaxSim search from host pointers: ehx_knn_maxsim_device plus the H2D / D2H copies, on the space's own stream. */
+int ehx_knn_maxsim(ehx_space* s, size_t n_queries, uint32_t n_tokens, const float* tokens, const uint32_t* token_count,
+                   uint32_t entity_col, uint32_t k, uint32_t fetch_k, uint64_t* out_ids, float* out_score, uint32_t* out_count);
 /* k-way merge of per-shard results (RCCL all-gather output): lists laid out
  * [n_lists][n_queries][k]; ids must already be global.  Ordered by (dist, id). */
 int ehx_merge_topk_device(void* stream, size_t n_queries, uint32_t k, uint32_t n_lists,
