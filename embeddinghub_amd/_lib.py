@@ -21,6 +21,7 @@ WALK_AUTO, WALK_GRAPH, WALK_EXACT = 0, 1, 2   # route of graph_knn_masked
 WALK_LIST_FACTOR, WALK_LIST_MAX = 12, 4096     # EHX_WALK_LIST_FACTOR / _MAX: the walk list holds max(ef, min(12 ef, 4096))
 GROUP_NONE, MAX_K_GROUPED = 0xFFFFFFFF, 256     # EHX_GROUP_NONE (a row that is a group of its own), EHX_MAX_K_GROUPED
 MMR_MAX_FETCH = 256                             # EHX_MMR_MAX_FETCH
+EXCEPT_MAX_LIST = 4096                          # EHX_EXCEPT_MAX_LIST: entries of one query's exclusion list
 MAXSIM_MAX_TOKENS, MAXSIM_MAX_CAND = 32, 1024   # EHX_MAXSIM_MAX_TOKENS, EHX_MAXSIM_MAX_CAND
 MAX_COLUMNS = 4                                 # EHX_MAX_COLUMNS: stored label columns of a space
 PRED_MAX_TERMS, TERM_NOT = 8, 1                 # EHX_PRED_MAX_TERMS, EHX_TERM_NOT: predicates over stored columns
@@ -129,6 +130,10 @@ SYMBOLS = {
     "ehx_mmr_select_device": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint32, _vp, _vp, _vp, C.c_uint32, C.c_float, _vp, _vp, _vp]),
     "ehx_knn_mmr_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint32, C.c_uint32, C.c_float, _vp, _vp, _vp]),
     "ehx_knn_mmr": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_uint32, C.c_uint32, C.c_float, _u64p, _f32p, _u32p]),
+    "ehx_knn_except_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint32, _vp, _vp, C.c_size_t, _vp, _vp, _vp]),
+    "ehx_knn_except": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_uint32, _u64p, _u64p, C.c_size_t, _u64p, _f32p, _u32p]),
+    "ehx_knn_except_keys": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), _u64p,
+                                      C.c_size_t, _u64p, _f32p, _u32p]),
     "ehx_maxsim_select_device": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint32, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp,
                                            C.c_uint32, _vp, _vp, _vp]),
     "ehx_knn_maxsim_device": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint32, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp,

@@ -586,6 +586,24 @@ struct ehx_space {
   std::atomic<uint64_t> grouped_ctr[5] = {};
   std::atomic<uint64_t> groupedm_ctr[5] = {};
   std::atomic<uint64_t> groupedl_ctr[5] = {};
+  // kNN with per-query exclusion lists (ehx_except.cpp; scratch_mu): the scan route's buffers (RadiusKnnBufs; its sub-batch: the
+  // queries the scan hands on), the exact route's own — carried keys, radii, every query's slab of row ids and its control
+  // words, the slabs' [start | end) — the sorted unique lists of a device batch and their lengths (k_except.hip), and a host
+  // call's staged lists, queries and results.
+  struct Except {
+    RadiusKnnBufs scan;
+    RadiusKnnBufs exact;         // (its sub-batch is not used: the exact route hands nothing on)
+    DevBuf<uint64_t> dPool;      // [queries of a device batch][kPoolCap]
+    DevBuf<uint32_t> dCtl;       // [queries] pool counts | [queries] flags, all zero
+    DevBuf<uint64_t> dRange;     // [queries] 0 | [queries] the prefix: every query's slabs cover all rows
+    DevBuf<uint32_t> dSorted;    // [queries of a device batch][kExceptMaxList] ascending unique row ids
+    DevBuf<uint32_t> dSortedCnt; // [queries]
+    DevBuf<uint64_t> dLists;     // host form: ids | offsets
+    HostStage host;
+  } except;
+  // test hook: queries answered on the scan route, handed to the exact route (by the gate or by the scan route), of those the
+  // ones whose pool overflowed, scan passes launched, calls
+  std::atomic<uint64_t> except_ctr[5] = {};
   // MMR search (ehx_mmr.cpp; scratch_mu): the candidate block of ehx_knn_mmr* — ids | distances | counts at fetch_k, what the
   // space's own kNN writes and the selection kernel reads; the space's clock fences it across streams — and a host call's
   // staged queries and results.
@@ -739,6 +757,7 @@ struct ehx_space {
     masked = {};
     largek = {};
     grouped = {};
+    except = {};
     mmr = {};
     maxsim = {};
     cols = {};

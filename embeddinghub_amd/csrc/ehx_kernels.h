@@ -731,6 +731,80 @@ struct RadiusRerankArgs {
   uint32_t mode;             // kRadiusPass | kRadiusLast (write the page instead of carrying) | kRadiusSeed (the radius only)
 };
 hipError_t launch_radius_rerank(const RadiusRerankArgs& a, hipStream_t st);   // k <= kLargeKMax, rows.ld <= range_rerank_max_ld()
+// What a falling-radius re-rank (radius_rerank_kernel, except_rerank_kernel) does for query q behind its sorted hits: keys,
+// the pool image in LDS, holds `total` (distance, id) keys within the radius, ascending; `walked` rows gave them.  Seed mode:
+// the k-th of them is the first radius (+Inf while there are fewer), nothing is carried.  Otherwise the first k hits are
+// merged by rank with the carried keys (k_radius.hip's header) — the carried keys go to keys[kLargeKMax, 2 kLargeKMax), the
+// merged list to [2 kLargeKMax, 3 kLargeKMax): later hits than the k-th are no members and may be overwritten — and the
+// best k are carried on under the lowered radius, or, in last mode, written as the page.  A workgroup of T >= kLargeKMax
+// threads, all of them behind the barrier that ended the sort.
+template <uint32_t T>
+__device__ __forceinline__ void radius_carry_or_emit(const RadiusRerankArgs& a, uint64_t* keys, uint32_t total, uint32_t walked,
+                                                     uint32_t q, uint32_t tid) {
+  static_assert(kLargeKMax <= T && 3u * kLargeKMax <= kPoolCap, "one thread per key; hits | carried | merged share the image");
+  if (a.mode == kRadiusSeed) {
+    // the sample gives the first radius and nothing else
+    if (tid == 0) {
+      a.radius[q] = total >= a.k ? ordered_to_f32((uint32_t)(keys[a.k - 1] >> 32)) : __builtin_inff();
+      a.pool_cnt[q] = 0;
+      a.top_cnt[q] = 0;
+      a.work[q] = walked;
+    }
+    return;
+  }
+  const uint32_t nh = total < a.k ? total : a.k;   // hits that can still be members: keys[0, nh)
+  const uint32_t have = a.top_cnt[q];
+  const uint32_t nc = have < a.k ? have : a.k;     // (never more than k: this function wrote it)
+  uint64_t* carried = keys + kLargeKMax;
+  uint64_t* merged = keys + 2u * kLargeKMax;
+  uint64_t* tq = a.top + (size_t)q * kLargeKMax;
+  uint64_t c = kKeyInf;
+  if (tid < nc) {
+    c = tq[tid];
+    carried[tid] = c;
+  }
+  __syncthreads();
+  const uint32_t n_out = nh + nc < a.k ? nh + nc : a.k;
+  if (tid < nh) {
+    const uint64_t h = keys[tid];
+    const uint32_t at = tid + lower_bound_lds(carried, nc, h);
+    if (at < n_out) merged[at] = h;
+  }
+  if (tid < nc) {
+    const uint32_t at = tid + lower_bound_lds(keys, nh, c);
+    if (at < n_out) merged[at] = c;
+  }
+  __syncthreads();
+  if (a.mode == kRadiusLast) {
+    emit_page([&](uint32_t i) { return merged[i]; }, n_out, a.k, a.out_ids + (size_t)q * a.k, a.out_dist + (size_t)q * a.k,
+              a.out_count + q, 0, tid, T);
+  } else {
+    if (tid < n_out) tq[tid] = merged[tid];
+    if (tid == 0) {
+      a.top_cnt[q] = n_out;
+      a.pool_cnt[q] = 0;
+      // (every key held is <= r: the k-th of them is the new, smaller or equal, radius)
+      if (n_out >= a.k) a.radius[q] = ordered_to_f32((uint32_t)(merged[a.k - 1] >> 32));
+    }
+  }
+  if (tid == 0) a.work[q] += walked;
+}
+
+// kNN with per-query exclusion lists (k_except.hip): the falling-radius re-rank with the listed rows dropped from the pool
+// BEFORE their rows are walked; every layout of stored rows
+constexpr uint32_t kExceptMaxList = 4096;   // EHX_EXCEPT_MAX_LIST: entries of one query's list (sorted 32-bit ids: 16 KiB of LDS)
+// sorted[j][0, sorted_cnt[j]) = the ids below n_rows of excl_ids[excl_off[j], excl_off[j + 1]), ascending, each once; the
+// lists may be unsorted and repeat ids; one longer than kExceptMaxList is cut there (the host refuses it first)
+hipError_t launch_except_lists(const uint64_t* excl_ids, const uint64_t* excl_off, uint32_t nq, uint64_t n_rows,
+                               uint32_t* sorted, uint32_t* sorted_cnt, hipStream_t st);
+struct ExceptRerankArgs {
+  RadiusRerankArgs r;           // (rows: any layout)
+  const uint32_t* sorted;       // [*][kExceptMaxList] launch_except_lists' lists
+  const uint32_t* sorted_cnt;   // [*]
+  const uint32_t* list_of;      // [r.nq] the list of query q, or nullptr: list q
+};
+uint32_t except_rerank_max_ld();   // longest row stride (floats): the pool image, the list and the prepared query share the LDS
+hipError_t launch_except_rerank(const ExceptRerankArgs& e, hipStream_t st);   // r.k <= kLargeKMax, rows.ld <= except_rerank_max_ld()
 
 // grouped kNN (k_grouped.hip): the falling-radius re-rank with at most per_group rows of one label among the keys it carries,
 // hands on and writes; every layout of stored rows

@@ -99,17 +99,19 @@ __device__ __forceinline__ uint64_t keep_best64(uint64_t best, uint64_t key, int
 }
 
 // ---- a pool of candidates, re-ranked (k_range.hip, k_radius.hip) ----
-// Canonical distances of the pool's rows for a workgroup of T threads: pool[0, cnt) are keys whose low halves are row ids
-// (each row at most once), qs the prepared query in LDS; keys[i] = the (distance, id) key of entry i, kKeyInf where the
-// distance lies above r or is NaN.  Returns, in every lane of a wave, how many entries that wave's lanes kept.
-template <int LAYOUT, int METRIC, uint32_t T>
-__device__ __forceinline__ uint32_t rerank_pool_cut(const RowsView& rows, const float* qs, const uint64_t* __restrict__ pool,
-                                                    uint32_t cnt, float r, uint64_t* keys, uint32_t tid) {
+// Canonical distances of the pool's rows for a workgroup of T threads: id_at(i), i < cnt, is entry i's row id (each row at
+// most once; the same in the four lanes of a group), qs the prepared query in LDS; keys[i] = the (distance, id) key of entry
+// i, kKeyInf where the distance lies above r or is NaN.  id_at may read keys[i] itself — a pool staged in the image: an
+// entry is read by the lanes that walk it, in front of the walk, and written behind it.  Returns, in every lane of a wave,
+// how many entries that wave's lanes kept.
+template <int LAYOUT, int METRIC, uint32_t T, class IdAt>
+__device__ __forceinline__ uint32_t rerank_ids_cut(const RowsView& rows, const float* qs, IdAt id_at, uint32_t cnt, float r,
+                                                   uint64_t* keys, uint32_t tid) {
   const bool writer = walk_by_lane<LAYOUT, true>() || (tid & 3u) == 0;   // this lane files its slot's key
   uint32_t kept = 0;
   for (uint32_t i0 = 0; i0 < cnt; i0 += walk_rows<LAYOUT, true>(T)) {
     const uint32_t i = i0 + walk_slot<LAYOUT, true>(tid);
-    const uint32_t id = i < cnt ? (uint32_t)pool[i] : ~0u;   // (the same in the four lanes of a group)
+    const uint32_t id = i < cnt ? id_at(i) : ~0u;   // (the same in the four lanes of a group)
     bool mine;
     const float d = walk_row<LAYOUT, METRIC, true>(rows, qs, id, id < rows.n_rows, tid, &mine);
     const bool in = mine && d <= r;   // (a NaN distance compares false: never a member)
@@ -118,15 +120,21 @@ __device__ __forceinline__ uint32_t rerank_pool_cut(const RowsView& rows, const 
   }
   return kept;
 }
+// ... of a pool in global memory: pool[0, cnt) are keys whose low halves are the row ids
+template <int LAYOUT, int METRIC, uint32_t T>
+__device__ __forceinline__ uint32_t rerank_pool_cut(const RowsView& rows, const float* qs, const uint64_t* __restrict__ pool,
+                                                    uint32_t cnt, float r, uint64_t* keys, uint32_t tid) {
+  return rerank_ids_cut<LAYOUT, METRIC, T>(rows, qs, [&](uint32_t i) { return (uint32_t)pool[i]; }, cnt, r, keys, tid);
+}
 
 // ascending bitonic sort of keys[0, m) in LDS, m a power of two >= 2, by a whole workgroup of T threads
-template <uint32_t T>
-__device__ __forceinline__ void block_sort_lds(uint64_t* keys, uint32_t m, uint32_t tid) {
+template <uint32_t T, class Key = uint64_t>
+__device__ __forceinline__ void block_sort_lds(Key* keys, uint32_t m, uint32_t tid) {
   for (uint32_t k = 2; k <= m; k <<= 1) {
     for (uint32_t j = k >> 1; j > 0; j >>= 1) {
       for (uint32_t t = tid; t < (m >> 1); t += T) {
         const uint32_t i = ((t & ~(j - 1)) << 1) | (t & (j - 1));   // the pair (i, i + j)
-        const uint64_t a = keys[i], b = keys[i + j];
+        const Key a = keys[i], b = keys[i + j];
         const bool up = (i & k) == 0;
         if ((a > b) == up) {
           keys[i] = b;
@@ -138,14 +146,14 @@ __device__ __forceinline__ void block_sort_lds(uint64_t* keys, uint32_t m, uint3
   }
 }
 
-// keys[0, n) padded with kKeyInf to the power of two the sort runs over, and sorted
-template <uint32_t T>
-__device__ __forceinline__ void pad_and_sort_lds(uint64_t* keys, uint32_t n, uint32_t tid) {
+// keys[0, n) padded with kKeyInf (all ones, whatever the keys' width) to the power of two the sort runs over, and sorted
+template <uint32_t T, class Key = uint64_t>
+__device__ __forceinline__ void pad_and_sort_lds(Key* keys, uint32_t n, uint32_t tid) {
   uint32_t m = 2;
   while (m < n) m <<= 1;
-  for (uint32_t i = n + tid; i < m; i += T) keys[i] = kKeyInf;
+  for (uint32_t i = n + tid; i < m; i += T) keys[i] = (Key)kKeyInf;
   __syncthreads();
-  block_sort_lds<T>(keys, m, tid);
+  block_sort_lds<T, Key>(keys, m, tid);
 }
 
 // One query's pool re-ranked by its workgroup of T threads, whose whole LDS is the launch's pool_rerank_lds_bytes(rows.ld):
@@ -164,6 +172,19 @@ __device__ __forceinline__ uint32_t pool_rerank_sorted(float4* lds, const RowsVi
   if (tid == 0) kept_s = 0;
   __syncthreads();
   const uint32_t kept = rerank_pool_cut<LAYOUT, METRIC, T>(rows, qs, pool, cnt, r, keys, tid);
+  if ((tid & 63u) == 0 && kept) atomicAdd(&kept_s, kept);
+  pad_and_sort_lds<T>(keys, cnt, tid);   // (at least one barrier: every wave's count has landed)
+  return kept_s;
+}
+// The form for a pool the caller has ALREADY staged and compacted in the image (k_except.hip: the rows its list names are
+// dropped before any row is read): the low halves of keys[0, cnt) are the row ids to walk, the prepared query is staged, the
+// counter behind it zero, all of it behind a barrier.  Result as above.
+template <int LAYOUT, int METRIC, uint32_t T>
+__device__ __forceinline__ uint32_t staged_rerank_sorted(float4* lds, const RowsView& rows, uint32_t cnt, float r, uint32_t tid) {
+  uint64_t* keys = (uint64_t*)lds;
+  const float* qs = (const float*)(keys + kPoolCap);
+  uint32_t& kept_s = *(uint32_t*)(qs + rows.ld);
+  const uint32_t kept = rerank_ids_cut<LAYOUT, METRIC, T>(rows, qs, [&](uint32_t i) { return (uint32_t)keys[i]; }, cnt, r, keys, tid);
   if ((tid & 63u) == 0 && kept) atomicAdd(&kept_s, kept);
   pad_and_sort_lds<T>(keys, cnt, tid);   // (at least one barrier: every wave's count has landed)
   return kept_s;

@@ -40,8 +40,6 @@ namespace ehx {
 namespace {
 
 constexpr uint32_t kRadiusThreads = 256;
-static_assert(kLargeKMax <= kRadiusThreads, "one thread per carried key and per surviving hit");
-static_assert(3u * kLargeKMax <= kPoolCap, "hits | carried | merged share the pool's LDS image");
 
 }  // namespace
 
@@ -53,9 +51,8 @@ __global__ __launch_bounds__(256) void radius_seed_kernel(uint64_t* __restrict__
   if (threadIdx.x == 0) pool_cnt[q] = n_sample;
 }
 
-// One workgroup per query (file header).  LDS: the pool's 32 KiB of keys and the prepared query; behind the sort the first
-// <= k hits stay at keys[0, kLargeKMax), the carried keys go to [kLargeKMax, 2 kLargeKMax), the merged list to
-// [2 kLargeKMax, 3 kLargeKMax) — later hits than the k-th are no members and may be overwritten.
+// One workgroup per query (file header).  LDS: the pool's 32 KiB of keys and the prepared query; what happens behind the sort
+// is radius_carry_or_emit's (ehx_kernels.h), shared with the exclusion-list re-rank (k_except.hip).
 template <bool HALFX, int METRIC>
 __global__ __launch_bounds__(kRadiusThreads) void radius_rerank_kernel(const RadiusRerankArgs a) {
   extern __shared__ float4 radius_lds[];
@@ -73,52 +70,7 @@ __global__ __launch_bounds__(kRadiusThreads) void radius_rerank_kernel(const Rad
   const float r = seed ? __builtin_inff() : a.radius[q];
   const uint32_t total = pool_rerank_sorted<HALFX ? kLayoutF16 : kLayoutF32, METRIC, kRadiusThreads>(
       radius_lds, a.rows, a.Q + (size_t)q * a.rows.ld, a.pool + (size_t)q * kPoolCap, cnt, r, tid);
-  if (seed) {
-    // the sample gives the first radius and nothing else
-    if (tid == 0) {
-      a.radius[q] = total >= a.k ? ordered_to_f32((uint32_t)(keys[a.k - 1] >> 32)) : __builtin_inff();
-      a.pool_cnt[q] = 0;
-      a.top_cnt[q] = 0;
-      a.work[q] = cnt;
-    }
-    return;
-  }
-  const uint32_t nh = total < a.k ? total : a.k;   // hits that can still be members: keys[0, nh)
-  const uint32_t have = a.top_cnt[q];
-  const uint32_t nc = have < a.k ? have : a.k;     // (never more than k: this kernel wrote it)
-  uint64_t* carried = keys + kLargeKMax;
-  uint64_t* merged = keys + 2u * kLargeKMax;
-  uint64_t* tq = a.top + (size_t)q * kLargeKMax;
-  uint64_t c = kKeyInf;
-  if (tid < nc) {
-    c = tq[tid];
-    carried[tid] = c;
-  }
-  __syncthreads();
-  const uint32_t n_out = nh + nc < a.k ? nh + nc : a.k;
-  if (tid < nh) {
-    const uint64_t h = keys[tid];
-    const uint32_t at = tid + lower_bound_lds(carried, nc, h);
-    if (at < n_out) merged[at] = h;
-  }
-  if (tid < nc) {
-    const uint32_t at = tid + lower_bound_lds(keys, nh, c);
-    if (at < n_out) merged[at] = c;
-  }
-  __syncthreads();
-  if (a.mode == kRadiusLast) {
-    emit_page([&](uint32_t i) { return merged[i]; }, n_out, a.k, a.out_ids + (size_t)q * a.k, a.out_dist + (size_t)q * a.k,
-              a.out_count + q, 0, tid, kRadiusThreads);
-  } else {
-    if (tid < n_out) tq[tid] = merged[tid];
-    if (tid == 0) {
-      a.top_cnt[q] = n_out;
-      a.pool_cnt[q] = 0;
-      // (every key held is <= r: the k-th of them is the new, smaller or equal, radius)
-      if (n_out >= a.k) a.radius[q] = ordered_to_f32((uint32_t)(merged[a.k - 1] >> 32));
-    }
-  }
-  if (tid == 0) a.work[q] += cnt;
+  radius_carry_or_emit<kRadiusThreads>(a, keys, total, cnt, q, tid);
 }
 
 namespace {

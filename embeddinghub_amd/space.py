@@ -466,6 +466,57 @@ class Space:
         check(self._L.ehx_knn_grouped_device(self._h, C.c_void_p(stream or 0), nq, _ptr(d_queries), k, int(per_group),
                                              _ptr(d_group_of), int(n_labels), _ptr(d_ids), _ptr(d_dist), _ptr(d_count)))
 
+    # ---- kNN with per-query exclusion lists: the nearest rows a query has NOT seen ----
+    def knn_except(self, queries, k, seen, seen_off=None):
+        """The k nearest rows of every query that ITS list does not name, exact (ehx_knn_except): knn_masked's answer under
+        the complement bitmap of the list.  seen: a list of per-query id sequences, or a flat id sequence cut by seen_off
+        [nq + 1] (marshal_id_lists).  Lists may be unsorted, repeat ids and name ids at or beyond len(self) (ignored); at
+        most EXCEPT_MAX_LIST entries each.  k <= 256.  -> ids [nq,k] u64, dist [nq,k] f32, count [nq] u32."""
+        q, pq = _f32(queries)
+        q = q.reshape(-1, self.dims)
+        nq = q.shape[0]
+        ids_in, off_in = marshal_id_lists(seen, seen_off)
+        if off_in is None or off_in.shape[0] != nq + 1:
+            raise ValueError("expected %d per-query lists, got %s" % (nq, "one flat list" if off_in is None else off_in.shape[0] - 1))
+        (ids, dist, cnt), out = _results(nq, k)
+        u64p = C.POINTER(C.c_uint64)
+        check(self._L.ehx_knn_except(self._h, nq, pq, k, ids_in.ctypes.data_as(u64p), off_in.ctypes.data_as(u64p),
+                                     ids_in.shape[0], *out))
+        return ids[:, :k], dist[:, :k], cnt
+
+    def knn_except_keys(self, queries, k, seen_keys):
+        """knn_except with the lists given as stored keys (a list of key lists), looked up under the same state of the space
+        the search sees.  A key that is not stored is ignored: it names no row."""
+        q, pq = _f32(queries)
+        q = q.reshape(-1, self.dims)
+        nq = q.shape[0]
+        lists = [list(ks) for ks in seen_keys]
+        if len(lists) != nq:
+            raise ValueError("expected %d per-query key lists, got %d" % (nq, len(lists)))
+        off = np.zeros(nq + 1, dtype=np.uint64)
+        if nq:
+            np.cumsum([len(ks) for ks in lists], out=off[1:])
+        n, arr, lens, keep = marshal_keys([key for ks in lists for key in ks])
+        (ids, dist, cnt), out = _results(nq, k)
+        rc = self._L.ehx_knn_except_keys(self._h, nq, pq, k, arr, lens, off.ctypes.data_as(C.POINTER(C.c_uint64)), n, *out)
+        del keep
+        check(rc)
+        return ids[:, :k], dist[:, :k], cnt
+
+    def knn_except_device(self, d_queries, k, d_seen_ids, d_seen_off, d_ids, d_dist, d_count, stream=None):
+        """knn_except without queries, lists or results leaving the device: torch CUDA tensors — d_queries [nq, dims] f32,
+        d_seen_ids [n] u64 (int64 storage; may be empty), d_seen_off [nq + 1] u64 (int64 storage), outputs as knn_device's.
+        The offsets are read back and checked before the search starts."""
+        nq = d_queries.shape[0] if hasattr(d_queries, "shape") else None
+        n = d_seen_ids.shape[0] if hasattr(d_seen_ids, "shape") else None
+        if nq is None or n is None:
+            raise ValueError("pass torch tensors (queries [nq, dims], seen ids [n], offsets [nq + 1])")
+        if hasattr(d_seen_off, "numel") and d_seen_off.numel() != nq + 1:
+            raise ValueError("%d offsets for %d queries" % (d_seen_off.numel(), nq))
+        check(self._L.ehx_knn_except_device(self._h, C.c_void_p(stream or 0), nq, _ptr(d_queries), k,
+                                            _ptr(d_seen_ids) if n else None, _ptr(d_seen_off), n, _ptr(d_ids), _ptr(d_dist),
+                                            _ptr(d_count)))
+
     # ---- MMR search: k of fetch_k candidates, near the query and not near each other ----
     def knn_mmr(self, queries, k, fetch_k=None, lam=0.5):
         """Maximal marginal relevance (ehx_knn_mmr): the fetch_k nearest rows of every query (knn's answer at fetch_k),

@@ -914,6 +914,48 @@ int ehx_knn_mmr_device(ehx_space* s, void* stream, size_t n_queries, const float
 /* MMR search from host pointers: ehx_knn_mmr_device plus the H2D / D2H copies, on the space's own stream. */
 int ehx_knn_mmr(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, uint32_t fetch_k, float lambda,
                 uint64_t* out_ids, float* out_dist, uint32_t* out_count);
+/* kNN with per-query exclusion lists: "the k nearest items this user has not seen yet", a different short list of rows that
+ * may NOT come back for every query of the batch.  Query i's list is d_excl_ids[d_excl_off[i], d_excl_off[i + 1]): 64-bit row
+ * ids in the CSR form of ehx_knn_among_device, d_excl_off of n_queries + 1 entries that ends at n_excl.
+ * The call takes ONE acquire-load snapshot of the row count.  Row i of the answer is the first k rows in (canonical distance,
+ * id) order among the rows of that prefix which query i's list does NOT name, under ehx_knn's rules (NaN is never a
+ * neighbour, +-Inf are ordered, cosine is normalised, F16 rows are read as stored), with sentinels (id 2^64 - 1, +Inf) behind
+ * d_out_count[i]: byte for byte what ehx_knn_masked_device returns for query i under the complement bitmap of its list —
+ * ids, distance bytes, count and sentinels.
+ * Lists may be unsorted and may repeat ids.  An id at or beyond the prefix (a seen-list compiled against a later state) is
+ * ignored, it is no error.  An empty list gives ehx_knn's answer.  At most EHX_EXCEPT_MAX_LIST entries per query, counted
+ * before de-duplication: the sorted list shares the re-rank's LDS with one pool, and excluded rows alone can then never need
+ * more than one pool.  For longer lists there is ehx_knn_masked_multi_device with a bitmap per query.
+ * Outputs [n_queries][k], 1 <= k <= EHX_MAX_K_GROUPED.
+ * Errors: a NULL space, k == 0, NULL outputs, NULL queries or offsets with n_queries > 0, NULL ids with n_excl > 0, offsets
+ * that are not non-decreasing or do not end at n_excl, a list longer than EHX_EXCEPT_MAX_LIST (the message names the query):
+ * EHX_EINVAL; k > EHX_MAX_K_GROUPED, a row-sharded space, rows longer than 28 640 floats (the pool, the list and the prepared
+ * query share one CU's LDS): EHX_EUNSUPPORTED; a dropped space: EHX_ENOTFOUND; n_queries == 0: EHX_OK.  The host forms decide
+ * every EHX_EINVAL above before the device is looked for; the device form reads d_excl_off back first (one small copy and a
+ * wait on `stream`) and checks it then.
+ * Served by the falling-radius scan of the int8 filter where ehx_knn_device's large-k route would serve the prefix (flat
+ * spaces whose first engine is the int8 filter, device batches of at least 64 queries; every k here, k <= EHX_MAX_K included)
+ * with the listed rows dropped in its exact re-rank BEFORE their rows are read — the scan itself is ehx_knn's; everything
+ * else — graph spaces (from their stored rows: the graph is not walked), small spaces, EHX_SCAN_F32 / _F16, small batches and
+ * the queries the scan hands on, each with its own list — by an exact pass over every prefix row in slabs of 4096.  The call
+ * waits for its verdicts as ehx_knn_device does; a Set that rewrites rows in place waits for it like for any search.
+ * DESIGN.md §e.30. */
+#define EHX_EXCEPT_MAX_LIST 4096u
+int ehx_knn_except_device(ehx_space* s, void* stream, size_t n_queries, const float* d_queries, uint32_t k,
+                          const uint64_t* d_excl_ids, const uint64_t* d_excl_off, size_t n_excl, uint64_t* d_out_ids,
+                          float* d_out_dist, uint32_t* d_out_count);
+/* ... from host pointers: ehx_knn_except_device plus the H2D / D2H copies, on the space's own stream. */
+int ehx_knn_except(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, const uint64_t* excl_ids,
+                   const uint64_t* excl_off, size_t n_excl, uint64_t* out_ids, float* out_dist, uint32_t* out_count);
+/* ... with the lists given as stored keys: query i excludes the rows of keys[key_off[i], key_off[i + 1]) (klens: their
+ * lengths; key_off of n_queries + 1 entries that ends at n_keys; limits and checks as for excl_off).  The keys are resolved
+ * under the same hold of the space's lock as the search, so the answer describes one state of the space.  A key that is NOT
+ * stored is ignored: it can name no row, so it excludes nothing.  This differs from ehx_knn_among_keys on purpose — there an
+ * unknown key is EHX_ENOTFOUND, because a caller who ALLOWS a row that does not exist has made a mistake, while a seen-list
+ * may well outlive an item. */
+int ehx_knn_except_keys(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, const char* const* keys,
+                        const size_t* klens, const uint64_t* key_off, size_t n_keys, uint64_t* out_ids, float* out_dist,
+                        uint32_t* out_count);
 /* MaxSim ("late interaction") scoring on the device: a query is a bag of up to EHX_MAXSIM_MAX_TOKENS vectors (ColBERT token
  * vectors, ColPali patch vectors, a document's chunk embeddings, a clip's frames), an entity the rows that carry one value
  * of a stored column, and an entity's score the sum over the query's vectors of the best match among its rows — without a
