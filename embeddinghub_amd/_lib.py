@@ -22,6 +22,7 @@ WALK_LIST_FACTOR, WALK_LIST_MAX = 12, 4096     # EHX_WALK_LIST_FACTOR / _MAX: th
 GROUP_NONE, MAX_K_GROUPED = 0xFFFFFFFF, 256     # EHX_GROUP_NONE (a row that is a group of its own), EHX_MAX_K_GROUPED
 MMR_MAX_FETCH = 256                             # EHX_MMR_MAX_FETCH
 EXCEPT_MAX_LIST = 4096                          # EHX_EXCEPT_MAX_LIST: entries of one query's exclusion list
+PROFILE_MAX_LIST = 4096                         # EHX_PROFILE_MAX_LIST: entries of one query's profile (rows and weights)
 MAXSIM_MAX_TOKENS, MAXSIM_MAX_CAND = 32, 1024   # EHX_MAXSIM_MAX_TOKENS, EHX_MAXSIM_MAX_CAND
 MAX_COLUMNS = 4                                 # EHX_MAX_COLUMNS: stored label columns of a space
 PRED_MAX_TERMS, TERM_NOT = 8, 1                 # EHX_PRED_MAX_TERMS, EHX_TERM_NOT: predicates over stored columns
@@ -134,6 +135,11 @@ SYMBOLS = {
     "ehx_knn_except": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_uint32, _u64p, _u64p, C.c_size_t, _u64p, _f32p, _u32p]),
     "ehx_knn_except_keys": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), _u64p,
                                       C.c_size_t, _u64p, _f32p, _u32p]),
+    "ehx_combine_rows_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t, _vp, _vp]),
+    "ehx_knn_profile_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t, C.c_uint32, _vp, _vp, _vp]),
+    "ehx_knn_profile": (C.c_int, [_vp, C.c_size_t, _u64p, _u64p, _f32p, C.c_size_t, C.c_uint32, _u64p, _f32p, _u32p]),
+    "ehx_knn_profile_keys": (C.c_int, [_vp, C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), _u64p, _f32p, C.c_size_t,
+                                       C.c_uint32, _u64p, _f32p, _u32p]),
     "ehx_maxsim_select_device": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint32, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp,
                                            C.c_uint32, _vp, _vp, _vp]),
     "ehx_knn_maxsim_device": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint32, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp,

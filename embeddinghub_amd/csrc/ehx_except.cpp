@@ -25,6 +25,10 @@ constexpr const char* kExceptWhy = "search with exclusion lists over shards is n
 static_assert(EHX_EXCEPT_MAX_LIST == kExceptMaxList, "the header's limit is the kernel's LDS list");
 static_assert(EHX_MAX_K_GROUPED == kLargeKMax, "the re-rank carries one key per thread");
 
+}  // namespace
+
+namespace ehx_impl {
+
 // what is decided before the device is looked for, with its codes and in this order (s is not read)
 int except_check(const ehx_space* s, size_t nq, uint32_t k, bool ptrs_ok) {
   if (!s) return fail(EHX_EINVAL, "space is NULL");
@@ -33,6 +37,18 @@ int except_check(const ehx_space* s, size_t nq, uint32_t k, bool ptrs_ok) {
   if (!ptrs_ok) return fail(EHX_EINVAL, "NULL argument");
   return check_batch_size(nq);
 }
+
+int except_check_ld(const ehx_space* s) {
+  if (int rc = check_rows_fit_lds(s, "search with exclusion lists")) return rc;
+  if (s->ld > except_rerank_max_ld())
+    return fail(EHX_EUNSUPPORTED, "search with exclusion lists keeps a pool, a list and a prepared query in LDS: rows of %u floats exceed %u",
+                s->ld, except_rerank_max_ld());
+  return EHX_OK;
+}
+
+}  // namespace ehx_impl
+
+namespace {
 
 // the offsets of a call, host memory: non-decreasing, ending at n_excl, no list longer than the kernel's
 int except_check_off(const uint64_t* off, size_t nq, size_t n_excl, const char* name, const char* n_name) {
@@ -44,14 +60,6 @@ int except_check_off(const uint64_t* off, size_t nq, size_t n_excl, const char* 
   }
   if (off[nq] != n_excl)
     return fail(EHX_EINVAL, "%s ends at %llu, not at %s = %zu", name, (unsigned long long)off[nq], n_name, n_excl);
-  return EHX_OK;
-}
-
-int except_check_ld(const ehx_space* s) {
-  if (int rc = check_rows_fit_lds(s, "search with exclusion lists")) return rc;
-  if (s->ld > except_rerank_max_ld())
-    return fail(EHX_EUNSUPPORTED, "search with exclusion lists keeps a pool, a list and a prepared query in LDS: rows of %u floats exceed %u",
-                s->ld, except_rerank_max_ld());
   return EHX_OK;
 }
 
@@ -117,15 +125,15 @@ int except_exact(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, const 
   return EHX_OK;
 }
 
-// an unsharded space, locked shared, scratch_mu held, its device current; everything is enqueued on `st`.  The lists are on
-// the device and their offsets checked (except_check_off).
-int except_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, const uint64_t* d_excl_ids,
-                  const uint64_t* d_excl_off, const ResultBlock& out) {
+}  // namespace
+
+// an unsharded space, locked shared, scratch_mu held, its device current, not poisoned, its rows within except_check_ld;
+// everything is enqueued on `st`.  The lists are on the device and their offsets checked (except_check_off).  n_pub: the
+// call's ONE read of the row count — except_locked's own, or the profile search's, whose targets were summed under it.
+int ehx_impl::except_locked_at(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, const float* d_queries, uint32_t k,
+                               const uint64_t* d_excl_ids, const uint64_t* d_excl_off, const ResultBlock& out) {
   int rc;
-  if ((rc = check_not_poisoned(s))) return rc;
-  if ((rc = except_check_ld(s))) return rc;   // (before anything is enqueued)
   ehx_space::Except& w = s->except;
-  const uint64_t n_pub = s->n.load(std::memory_order_acquire);   // the ONE read of the row count
   s->except_ctr[4] += 1;
   const bool scans = s->params.mode != EHX_MODE_GRAPH && !s->x_perm && n_pub > 0 && i8_serves_radius(s, n_pub);
   // (a last device batch below the gate goes with the exact route's queries)
@@ -176,6 +184,17 @@ int except_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_querie
   s->except_ctr[1] += nq - n_scan;
   return except_exact(s, st, n_pub, nq - n_scan, d_queries + n_scan * s->dims, k, d_excl_ids, d_excl_off + n_scan, nullptr,
                       out.ids + n_scan * k, out.dist + n_scan * k, out.cnt + n_scan, true);
+}
+
+namespace {
+
+int except_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, uint32_t k, const uint64_t* d_excl_ids,
+                  const uint64_t* d_excl_off, const ResultBlock& out) {
+  int rc;
+  if ((rc = check_not_poisoned(s))) return rc;
+  if ((rc = except_check_ld(s))) return rc;   // (before anything is enqueued)
+  const uint64_t n_pub = s->n.load(std::memory_order_acquire);   // the ONE read of the row count
+  return except_locked_at(s, st, n_pub, nq, d_queries, k, d_excl_ids, d_excl_off, out);
 }
 
 // host pointers in, host pointers out, on the space's stream (on_device): ids | offsets staged in except.dLists

@@ -604,6 +604,17 @@ struct ehx_space {
   // test hook: queries answered on the scan route, handed to the exact route (by the gate or by the scan route), of those the
   // ones whose pool overflowed, scan passes launched, calls
   std::atomic<uint64_t> except_ctr[5] = {};
+  // profile search (ehx_profile.cpp; scratch_mu): the targets combine_rows_kernel sums for a call and their validity flags —
+  // what the except route then reads as its queries — and a host call's staged ids | offsets, weights and results.  by.by_ev
+  // orders a call behind the last one that used them, on whatever stream, and is what a Set that rewrites rows in place waits
+  // for: the combine reads rows outside the batch clock.
+  struct Profile {
+    DevBuf<float> dTarget;       // [queries][dims]
+    DevBuf<uint32_t> dValid;     // [queries]
+    DevBuf<uint64_t> dLists;     // host form: ids | offsets
+    DevBuf<float> dWeights;      // host form
+    DevBuf<unsigned char> dOut;  // host form: a ResultBlock
+  } profile;
   // MMR search (ehx_mmr.cpp; scratch_mu): the candidate block of ehx_knn_mmr* — ids | distances | counts at fetch_k, what the
   // space's own kNN writes and the selection kernel reads; the space's clock fences it across streams — and a host call's
   // staged queries and results.
@@ -758,6 +769,7 @@ struct ehx_space {
     largek = {};
     grouped = {};
     except = {};
+    profile = {};
     mmr = {};
     maxsim = {};
     cols = {};
@@ -1020,6 +1032,16 @@ bool largek_serves(const ehx_space* s, size_t nq, uint32_t k, uint64_t n_pub);
 // returns with the stream drained
 int largek_locked(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, const float* d_queries, uint32_t k,
                   uint64_t* d_ids, float* d_dist, uint32_t* d_count);
+
+// ---- ehx_except.cpp ----
+// what ehx_knn_except* decide before the device is looked for, with their codes and in this order (s is not read)
+int except_check(const ehx_space* s, size_t nq, uint32_t k, bool ptrs_ok);
+int except_check_ld(const ehx_space* s);   // rows wider than the except re-rank takes: EHX_EUNSUPPORTED
+// ehx_knn_except_device's body under a row count the CALLER read: an unsharded space, locked shared, scratch_mu held, its
+// device current, not poisoned, within except_check_ld; the lists on the device, their offsets checked; everything is enqueued
+// on `st`.  n_pub: the call's ONE read of the row count (the profile search sums its targets under the same one).
+int except_locked_at(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, const float* d_queries, uint32_t k,
+                     const uint64_t* d_excl_ids, const uint64_t* d_excl_off, const ResultBlock& out);
 
 // ---- ehx_range.cpp ----
 constexpr uint32_t kRangeGridTarget = 4096;   // workgroups an exact range kernel's launch aims for (16 per CU): chosen, not measured

@@ -806,6 +806,24 @@ struct ExceptRerankArgs {
 uint32_t except_rerank_max_ld();   // longest row stride (floats): the pool image, the list and the prepared query share the LDS
 hipError_t launch_except_rerank(const ExceptRerankArgs& e, hipStream_t st);   // r.k <= kLargeKMax, rows.ld <= except_rerank_max_ld()
 
+// profile search (k_profile.hip): every query's target, the 8-strand weighted sum of the stored rows its list names
+// (include/ehx.h has the definition), streamed through registers; every layout of stored rows
+constexpr uint32_t kProfileMaxList = 4096;   // EHX_PROFILE_MAX_LIST: entries of one query's list (row | weight: 32 KiB of LDS)
+constexpr uint32_t kProfileStrands = 8;      // the definition's strands: one wave each
+struct CombineRowsArgs {
+  const uint64_t* ids;      // the lists' row ids; an id at or above rows.n_rows names no row: it is skipped, not read
+  const uint64_t* off;      // [nq + 1] checked by the host: non-decreasing, no list longer than kProfileMaxList
+  const float* weights;     // parallel to ids, or nullptr: every weight is 1
+  RowsView rows;            // stored rows, any layout (inv_norm and metric are not read: the rows as ehx_get_by_id returns them)
+  float* out;               // [nq][dims] the targets
+  uint32_t* valid;          // [nq] 0: no entry of the list names a row (the target is +0 everywhere)
+  uint32_t nq;
+};
+hipError_t launch_combine_rows(const CombineRowsArgs& a, int n_cus, hipStream_t st);
+// the rows of the queries with valid[q] == 0: count 0, sentinels (id ~0, +Inf) in all k places
+hipError_t launch_blank_invalid(const uint32_t* valid, uint32_t nq, uint32_t k, uint64_t* out_ids, float* out_dist,
+                                uint32_t* out_count, hipStream_t st);
+
 // grouped kNN (k_grouped.hip): the falling-radius re-rank with at most per_group rows of one label among the keys it carries,
 // hands on and writes; every layout of stored rows
 constexpr uint32_t kGroupNone = 0xFFFFFFFFu;   // EHX_GROUP_NONE: a row that is a group of its own

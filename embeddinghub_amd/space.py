@@ -517,6 +517,81 @@ class Space:
                                             _ptr(d_seen_ids) if n else None, _ptr(d_seen_off), n, _ptr(d_ids), _ptr(d_dist),
                                             _ptr(d_count)))
 
+    # ---- profile search: the query is a weighted sum of stored rows, and its list is its exclusion list ----
+    @staticmethod
+    def _profile_weights(weights, n):
+        """the weights of n list entries for the C call: None (NULL: every weight is 1) or a flat f32 array of n"""
+        if weights is None:
+            return None, None
+        parts = [np.asarray(p, dtype=np.float32).reshape(-1) for p in weights] if isinstance(weights, (list, tuple)) else [
+            np.asarray(weights, dtype=np.float32).reshape(-1)]
+        w = np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros(0, dtype=np.float32))
+        if w.shape[0] != n:
+            raise ValueError("%d weights for %d list entries" % (w.shape[0], n))
+        return w, w.ctypes.data_as(C.POINTER(C.c_float))
+
+    def knn_profile(self, k, liked, weights=None, liked_off=None):
+        """The k nearest rows of every query's TARGET that its list does not name (ehx_knn_profile): the target is the
+        weighted sum of the stored rows the list names, summed on the device in the 8-strand order include/ehx.h defines,
+        and every listed row is excluded whatever its weight.  liked: a list of per-query id sequences, or a flat id
+        sequence cut by liked_off [nq + 1] (marshal_id_lists); weights: None (all 1) or shaped like liked.  Lists may be
+        unsorted, repeat ids (a repeat counts every time) and name ids at or beyond len(self) (ignored); at most
+        PROFILE_MAX_LIST entries each; a query whose list names no row gets count 0.  k <= 256.
+        -> ids [nq,k] u64, dist [nq,k] f32, count [nq] u32."""
+        ids_in, off_in = marshal_id_lists(liked, liked_off)
+        if off_in is None:
+            raise ValueError("expected per-query lists, got one flat list without offsets")
+        nq = off_in.shape[0] - 1
+        w, pw = self._profile_weights(weights, ids_in.shape[0])
+        (ids, dist, cnt), out = _results(nq, k)
+        u64p = C.POINTER(C.c_uint64)
+        check(self._L.ehx_knn_profile(self._h, nq, ids_in.ctypes.data_as(u64p), off_in.ctypes.data_as(u64p), pw,
+                                      ids_in.shape[0], k, *out))
+        return ids[:, :k], dist[:, :k], cnt
+
+    def knn_profile_keys(self, k, liked_keys, weights=None):
+        """knn_profile with the lists given as stored keys (a list of key lists) and weights shaped like them, looked up
+        under the same state of the space the search sees.  A key that is not stored keeps its place in the list,
+        contributes nothing and excludes nothing."""
+        lists = [list(ks) for ks in liked_keys]
+        nq = len(lists)
+        off = np.zeros(nq + 1, dtype=np.uint64)
+        if nq:
+            np.cumsum([len(ks) for ks in lists], out=off[1:])
+        n, arr, lens, keep = marshal_keys([key for ks in lists for key in ks])
+        w, pw = self._profile_weights(weights, n)
+        (ids, dist, cnt), out = _results(nq, k)
+        rc = self._L.ehx_knn_profile_keys(self._h, nq, arr, lens, off.ctypes.data_as(C.POINTER(C.c_uint64)), pw, n, k, *out)
+        del keep
+        check(rc)
+        return ids[:, :k], dist[:, :k], cnt
+
+    @staticmethod
+    def _profile_lists(d_ids, d_off, d_weights):
+        """(nq, n) of a device call's lists: d_ids [n] u64, d_off [nq + 1] u64 (int64 storage), d_weights [n] f32 or None"""
+        if not hasattr(d_ids, "shape") or not hasattr(d_off, "numel") or d_off.numel() < 1:
+            raise ValueError("pass torch tensors (ids [n], offsets [nq + 1], weights [n] or None)")
+        n = d_ids.shape[0]
+        if d_weights is not None and d_weights.numel() != n:
+            raise ValueError("%d weights for %d list entries" % (d_weights.numel(), n))
+        return d_off.numel() - 1, n
+
+    def combine_rows_device(self, d_ids, d_off, d_weights, d_out, d_valid, stream=None):
+        """The targets alone (ehx_combine_rows_device): d_out [nq, dims] f32 = every query's weighted sum of the stored rows
+        its list names, d_valid [nq] u32 (int32 storage) = 0 where the list names no row.  Torch CUDA tensors; d_weights
+        may be None.  The offsets are read back and checked before the kernel starts."""
+        nq, n = self._profile_lists(d_ids, d_off, d_weights)
+        check(self._L.ehx_combine_rows_device(self._h, C.c_void_p(stream or 0), nq, _ptr(d_ids) if n else None, _ptr(d_off),
+                                              _ptr(d_weights) if n else None, n, _ptr(d_out), _ptr(d_valid)))
+
+    def knn_profile_device(self, k, d_ids, d_off, d_weights, d_out_ids, d_out_dist, d_out_count, stream=None):
+        """knn_profile without lists, targets or results leaving the device: torch CUDA tensors, the lists as
+        combine_rows_device's, outputs as knn_device's."""
+        nq, n = self._profile_lists(d_ids, d_off, d_weights)
+        check(self._L.ehx_knn_profile_device(self._h, C.c_void_p(stream or 0), nq, _ptr(d_ids) if n else None, _ptr(d_off),
+                                             _ptr(d_weights) if n else None, n, k, _ptr(d_out_ids), _ptr(d_out_dist),
+                                             _ptr(d_out_count)))
+
     # ---- MMR search: k of fetch_k candidates, near the query and not near each other ----
     def knn_mmr(self, queries, k, fetch_k=None, lam=0.5):
         """Maximal marginal relevance (ehx_knn_mmr): the fetch_k nearest rows of every query (knn's answer at fetch_k),

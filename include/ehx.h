@@ -956,6 +956,54 @@ int ehx_knn_except(ehx_space* s, size_t n_queries, const float* queries, uint32_
 int ehx_knn_except_keys(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, const char* const* keys,
                         const size_t* klens, const uint64_t* key_off, size_t n_keys, uint64_t* out_ids, float* out_dist,
                         uint32_t* out_count);
+/* Profile search ("recommend by examples"): the query is not a vector the caller holds but a weighted sum of rows the space
+ * already holds — "items near what this user liked, weighted by recency, minus what they disliked, and none of the items
+ * already in their history" — and the same list is the query's exclusion list.  The lists come in the CSR form of
+ * ehx_knn_except_device: query i's entries e = 0 .. L_i - 1 are (d_ids[d_off[i] + e], d_weights[d_off[i] + e]), d_off of
+ * n_queries + 1 entries that ends at n_entries; d_weights == NULL: every weight is 1.  L_i <= EHX_PROFILE_MAX_LIST.  A list
+ * may be unsorted and may repeat ids; a repeat counts every time it occurs.  The call takes ONE acquire-load snapshot of the
+ * row count; an id at or beyond it contributes nothing and excludes nothing.
+ * The target t_i, defined in fp32 so that two implementations agree to the byte.  x_e is row id_e exactly as ehx_get_by_id
+ * returns it: fp32 as stored, binary16 widened, cosine rows as they were Set (they are not re-normalised), single-copy graph
+ * rows with the block permutation undone.  Per component c, over 8 STRANDS, every multiply and every add rounded on its own
+ * (no fused multiply-add):
+ *   strand s = 0 .. 7   acc_s = +0; then for e = s, s + 8, s + 16, ... in list order, skipping the entries whose id names no
+ *                       row:  acc_s = fl(acc_s + fl(w_e * x_e[c]))
+ *   t_i[c]              fl(... fl(fl(acc_0 + acc_1) + acc_2) ... + acc_7)
+ * The strand of an entry is its position in the list AS GIVEN, mod 8: skipped entries do not shift the ones behind them.
+ * Eight independent row streams per query, no data-dependent order: that is what lets the rows stream through registers
+ * once (k_profile.hip).  Eight is a choice, not a measurement.
+ * ehx_combine_rows_device writes the targets alone — d_out [n_queries][dims], d_valid [n_queries]: 0 iff no entry of the list
+ * names a row (the target is then +0 everywhere) — for callers who want no exclusion, or who store the profiles in another
+ * space through ehx_set_batch_device.  Asynchronous on `stream` behind the read-back of d_off.
+ * Errors: a NULL space, NULL outputs, NULL offsets with n_queries > 0, NULL ids with n_entries > 0, offsets that are not
+ * non-decreasing or do not end at n_entries, a list longer than EHX_PROFILE_MAX_LIST (the message names the query): EHX_EINVAL;
+ * a row-sharded space: EHX_EUNSUPPORTED; a dropped space: EHX_ENOTFOUND; n_queries == 0: EHX_OK.  The device forms read d_off
+ * back first (one small copy and a wait on `stream`) and check it then; the host forms decide every EHX_EINVAL before the
+ * device is looked for.  DESIGN.md §e.31. */
+#define EHX_PROFILE_MAX_LIST 4096u
+int ehx_combine_rows_device(ehx_space* s, void* stream, size_t n_queries, const uint64_t* d_ids, const uint64_t* d_off,
+                            const float* d_weights /* NULL ok */, size_t n_entries, float* d_out, uint32_t* d_valid);
+/* ... and the search: row i of the answer is byte for byte ehx_knn_except_device's for the query vector t_i and the exclusion
+ * list d_ids[d_off[i], d_off[i + 1]) — every listed row is excluded whatever its weight, a zero included — under the SAME
+ * snapshot of the row count the targets were summed under.  The targets are prepared like any query (padded; cosine:
+ * normalised by the canonical sequential norm; ehx_knn's NaN rule holds, so a target with a NaN component finds nothing),
+ * in a scratch buffer the space owns.  A query none of whose entries names a row — an empty list too — gets count 0 and
+ * sentinels.  Outputs [n_queries][k], 1 <= k <= EHX_MAX_K_GROUPED; checks, codes and their order are ehx_knn_except_device's
+ * (k == 0: EHX_EINVAL; k > EHX_MAX_K_GROUPED: EHX_EUNSUPPORTED; then the pointers), routes and waits as well: graph spaces
+ * answer from their stored rows. */
+int ehx_knn_profile_device(ehx_space* s, void* stream, size_t n_queries, const uint64_t* d_ids, const uint64_t* d_off,
+                           const float* d_weights /* NULL ok */, size_t n_entries, uint32_t k, uint64_t* d_out_ids,
+                           float* d_out_dist, uint32_t* d_out_count);
+/* ... from host pointers: ehx_knn_profile_device plus the H2D / D2H copies, on the space's own stream. */
+int ehx_knn_profile(ehx_space* s, size_t n_queries, const uint64_t* ids, const uint64_t* off, const float* weights /* NULL ok */,
+                    size_t n_entries, uint32_t k, uint64_t* out_ids, float* out_dist, uint32_t* out_count);
+/* ... with the lists given as stored keys and a parallel array of weights (NULL: all 1), resolved under the same hold of the
+ * space's lock as the search.  A key that is NOT stored keeps its place in the list (the strands behind it do not move),
+ * contributes nothing and excludes nothing, as in ehx_knn_except_keys. */
+int ehx_knn_profile_keys(ehx_space* s, size_t n_queries, const char* const* keys, const size_t* klens, const uint64_t* key_off,
+                         const float* weights /* NULL ok */, size_t n_keys, uint32_t k, uint64_t* out_ids, float* out_dist,
+                         uint32_t* out_count);
 /* MaxSim ("late interaction") scoring on the device: a query is a bag of up to EHX_MAXSIM_MAX_TOKENS vectors (ColBERT token
  * vectors, ColPali patch vectors, a document's chunk embeddings, a clip's frames), an entity the rows that carry one value
  * of a stored column, and an entity's score the sum over the query's vectors of the best match among its rows — without a
