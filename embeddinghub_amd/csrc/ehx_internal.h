@@ -604,6 +604,25 @@ struct ehx_space {
   // test hook: queries answered on the scan route, handed to the exact route (by the gate or by the scan route), of those the
   // ones whose pool overflowed, scan passes launched, calls
   std::atomic<uint64_t> except_ctr[5] = {};
+  // boosted kNN (ehx_boost.cpp; scratch_mu): the scan route's buffers (RadiusKnnBufs — its radii are the DISTANCE radii the
+  // scan's thresholds are mapped from; its sub-batch: the queries the scan hands on) and score radii, the exact route's own —
+  // carried keys, score radii, every query's slab of row ids and its control words, the slabs' [start | end) — the state of
+  // the array form's floor (k_boost.hip), and a host call's staged penalties | weights, queries and results.
+  struct Boost {
+    RadiusKnnBufs scan;
+    RadiusKnnBufs exact;         // (its sub-batch is not used: the exact route hands nothing on; its radii are never read)
+    DevBuf<uint64_t> dPool;      // [queries of a device batch][kPoolCap]
+    DevBuf<uint32_t> dCtl;       // [queries] pool counts | [queries] flags, all zero
+    DevBuf<uint64_t> dRange;     // [queries] 0 | [queries] the prefix: every query's slabs cover all rows
+    DevBuf<float> dScoreScan;    // [queries of a device batch] the scan route's score radii
+    DevBuf<float> dScoreExact;   // ... the exact route's
+    DevBuf<uint32_t> dFloor;     // [kBoostFloorWords]
+    DevBuf<float> dStage;        // host form: penalties | weights
+    HostStage host;
+  } boost;
+  // test hook: queries answered on the scan route, handed to the exact route (by the gate, the floor flag or the scan route),
+  // of those the ones whose pool overflowed, scan passes launched, calls
+  std::atomic<uint64_t> boost_ctr[5] = {};
   // profile search (ehx_profile.cpp; scratch_mu): the targets combine_rows_kernel sums for a call and their validity flags —
   // what the except route then reads as its queries — and a host call's staged ids | offsets, weights and results.  by.by_ev
   // orders a call behind the last one that used them, on whatever stream, and is what a Set that rewrites rows in place waits
@@ -769,6 +788,7 @@ struct ehx_space {
     largek = {};
     grouped = {};
     except = {};
+    boost = {};
     profile = {};
     mmr = {};
     maxsim = {};

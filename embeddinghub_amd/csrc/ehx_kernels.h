@@ -806,6 +806,30 @@ struct ExceptRerankArgs {
 uint32_t except_rerank_max_ld();   // longest row stride (floats): the pool image, the list and the prepared query share the LDS
 hipError_t launch_except_rerank(const ExceptRerankArgs& e, hipStream_t st);   // r.k <= kLargeKMax, rows.ld <= except_rerank_max_ld()
 
+// boosted kNN (k_boost.hip): the falling-radius re-rank on SCORES, score = fl(D + fl(w p)) with p a number stored beside the
+// row; every layout of stored rows
+enum { kBoostArray = 0, kBoostColumn = 1 };   // where p comes from: a caller's float array | min(|col - origin|, span) of a column
+constexpr uint32_t kBoostFloorWords = 4;      // launch_boost_floor's state: ordered minimum | blocks done | flag | the minimum's bits
+// state[3] = the least non-NaN value of p[0, n) as float bits, state[2] = 1 if that is -Inf or no finite value exists (then
+// +Inf), else 0.  state[0, 4) must hold {0xFFFFFFFF, 0, 0, 0} when the kernel starts.
+hipError_t launch_boost_floor(const float* p, uint64_t n, uint32_t* state, int n_cus, hipStream_t st);
+struct BoostRerankArgs {
+  RadiusRerankArgs r;        // (rows: any layout.  r.radius: the DISTANCE radius)
+  uint64_t n_penalty;        // rows [0, n_penalty) are searched, n_penalty <= r.rows.n_rows: a pool entry at or beyond is dropped
+  const float* penalty;      // kBoostArray: [>= n_penalty]
+  const uint32_t* col;       // kBoostColumn: [>= n_penalty]
+  uint32_t origin, span;     // kBoostColumn
+  const float* weight;       // [*] one weight >= 0 per query, or nullptr: 1
+  const uint32_t* weight_of; // [r.nq] the weight of query q, or nullptr: weight q
+  float* score_r;            // [r.nq] the SCORE radius: the exact k-th score held (the seed writes it, a pass lowers it)
+  const float* floor;        // the least penalty p_min (launch_boost_floor's state + 3), or nullptr: 0
+  uint32_t* flag;            // r.ovf, writable: a query whose distance radius is not finite is marked 2 there; nullptr (the
+                             // exact route, which bounds nothing): no distance radius is written at all
+  int form;                  // kBoostArray | kBoostColumn
+};
+uint32_t boost_rerank_max_ld();   // longest row stride (floats): the pool image and the prepared query share the LDS
+hipError_t launch_boost_rerank(const BoostRerankArgs& e, hipStream_t st);   // r.k <= kLargeKMax, rows.ld <= boost_rerank_max_ld()
+
 // profile search (k_profile.hip): every query's target, the 8-strand weighted sum of the stored rows its list names
 // (include/ehx.h has the definition), streamed through registers; every layout of stored rows
 constexpr uint32_t kProfileMaxList = 4096;   // EHX_PROFILE_MAX_LIST: entries of one query's list (row | weight: 32 KiB of LDS)

@@ -18,6 +18,8 @@
 //   ehx_test_largek_plan       the route's pass planner, host arithmetic only (no device, no space)
 // ... and of the kNN with per-query exclusion lists (ehx_except.cpp):
 //   ehx_test_except_counters   what its two routes did so far on a space
+// ... and of the boosted kNN (ehx_boost.cpp):
+//   ehx_test_boost_counters    what its two routes did so far on a space
 // ... and of the Set from device memory (ehx_rowio.cpp, ehx_write.cpp):
 //   ehx_test_last_writers      the duplicate rule of its scatter, host arithmetic only (no device, no space)
 //   ehx_test_write_batch       what a batch of row ids touches (WriteBatch), host arithmetic only (no device, no space)
@@ -440,6 +442,12 @@ void ehx_test_largek_counters(ehx_space* s, uint64_t out[5]) {
 // route), of those the ones whose pool overflowed, scan passes launched, calls
 void ehx_test_except_counters(ehx_space* s, uint64_t out[5]) {
   for (int i = 0; i < 5; ++i) out[i] = s ? s->except_ctr[i].load(std::memory_order_relaxed) : 0;
+}
+
+// boosted kNN: queries answered on the scan route, queries handed to the exact route (by the gate, the floor flag or the scan
+// route), of those the ones whose pool overflowed, scan passes launched, calls
+void ehx_test_boost_counters(ehx_space* s, uint64_t out[5]) {
+  for (int i = 0; i < 5; ++i) out[i] = s ? s->boost_ctr[i].load(std::memory_order_relaxed) : 0;
 }
 
 // largek_passes(n_rows, growth) as (tile0, n_tiles) pairs into out_pairs[2 * cap]; returns the number of passes (the first

@@ -517,6 +517,65 @@ class Space:
                                             _ptr(d_seen_ids) if n else None, _ptr(d_seen_off), n, _ptr(d_ids), _ptr(d_dist),
                                             _ptr(d_count)))
 
+    # ---- boosted kNN: ranked on distance + weight * a number stored beside the row ----
+    @staticmethod
+    def _boost_weights(weight, nq):
+        """the weights of nq queries for the C call: None (NULL: every weight is 1) or a flat f32 array of nq"""
+        if weight is None:
+            return None, None
+        w = np.ascontiguousarray(np.broadcast_to(np.asarray(weight, dtype=np.float32).reshape(-1), (nq,)))
+        return w, w.ctypes.data_as(C.POINTER(C.c_float))
+
+    def knn_boosted(self, queries, k, penalty, weight=None):
+        """The k rows of least SCORE for every query, exact (ehx_knn_boosted): score = fl32(distance + fl32(weight[q] *
+        penalty[row])), rows in (score, id) order.  penalty: one float per row — rows at or above len(penalty) or len(self)
+        are not searched; any value, a NaN never comes back.  weight: None (1), a number or one per query, finite and >= 0.
+        k <= 256.  -> ids [nq,k] u64, score [nq,k] f32, count [nq] u32."""
+        q, pq = _f32(queries)
+        q = q.reshape(-1, self.dims)
+        nq = q.shape[0]
+        p, pp = _f32(np.asarray(penalty).reshape(-1))
+        w, pw = self._boost_weights(weight, nq)
+        (ids, score, cnt), out = _results(nq, k)
+        check(self._L.ehx_knn_boosted(self._h, nq, pq, k, pp if p.shape[0] else None, p.shape[0], pw, *out))
+        return ids[:, :k], score[:, :k], cnt
+
+    def knn_boosted_device(self, d_queries, k, d_penalty, n_penalty, d_ids, d_score, d_count, d_weight=None, stream=None):
+        """knn_boosted without anything leaving the device: torch CUDA tensors — d_queries [nq, dims] f32, d_penalty
+        [n_penalty] f32, d_weight [nq] f32 or None, outputs as knn_device's (d_score in the place of the distances).  The
+        weights are read back and checked before the search starts."""
+        nq = d_queries.shape[0] if hasattr(d_queries, "shape") else None
+        if nq is None:
+            raise ValueError("pass torch tensors (queries [nq, dims], penalties [n_penalty])")
+        if hasattr(d_penalty, "numel") and d_penalty.numel() < int(n_penalty):
+            raise ValueError("%d penalties are fewer than n_penalty = %d" % (d_penalty.numel(), n_penalty))
+        if hasattr(d_weight, "numel") and d_weight.numel() != nq:
+            raise ValueError("%d weights for %d queries" % (d_weight.numel(), nq))
+        check(self._L.ehx_knn_boosted_device(self._h, C.c_void_p(stream or 0), nq, _ptr(d_queries), k,
+                                             _ptr(d_penalty) if n_penalty else None, int(n_penalty), _ptr(d_weight), _ptr(d_ids),
+                                             _ptr(d_score), _ptr(d_count)))
+
+    def knn_decay(self, queries, k, col, origin, span, weight=None):
+        """knn_boosted with penalty[row] = float(min(|column col of the row - origin|, span)) taken from the STORED column
+        (ehx_knn_decay): a linear decay by a stored timestamp, price or counter; no array travels.  origin, span: u32."""
+        q, pq = _f32(queries)
+        q = q.reshape(-1, self.dims)
+        nq = q.shape[0]
+        w, pw = self._boost_weights(weight, nq)
+        (ids, score, cnt), out = _results(nq, k)
+        check(self._L.ehx_knn_decay(self._h, nq, pq, k, int(col), int(origin), int(span), pw, *out))
+        return ids[:, :k], score[:, :k], cnt
+
+    def knn_decay_device(self, d_queries, k, col, origin, span, d_ids, d_score, d_count, d_weight=None, stream=None):
+        """knn_decay without queries, weights or results leaving the device (torch CUDA tensors, as knn_boosted_device's)."""
+        nq = d_queries.shape[0] if hasattr(d_queries, "shape") else None
+        if nq is None:
+            raise ValueError("pass torch tensors (queries [nq, dims])")
+        if hasattr(d_weight, "numel") and d_weight.numel() != nq:
+            raise ValueError("%d weights for %d queries" % (d_weight.numel(), nq))
+        check(self._L.ehx_knn_decay_device(self._h, C.c_void_p(stream or 0), nq, _ptr(d_queries), k, int(col), int(origin),
+                                           int(span), _ptr(d_weight), _ptr(d_ids), _ptr(d_score), _ptr(d_count)))
+
     # ---- profile search: the query is a weighted sum of stored rows, and its list is its exclusion list ----
     @staticmethod
     def _profile_weights(weights, n):

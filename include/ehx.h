@@ -956,6 +956,50 @@ int ehx_knn_except(ehx_space* s, size_t n_queries, const float* queries, uint32_
 int ehx_knn_except_keys(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, const char* const* keys,
                         const size_t* klens, const uint64_t* key_off, size_t n_keys, uint64_t* out_ids, float* out_dist,
                         uint32_t* out_count);
+/* Boosted kNN: a ranking that MIXES the vector distance with a number stored beside the row — a recency decay, a popularity
+ * or quality prior, a price distance, the item bias of a matrix-factorisation recommender (Elastic's function_score, Qdrant's
+ * score boosting, a Vespa rank profile).  Over-fetching ehx_knn and re-scoring is inexact: a row at distance rank 5000 with
+ * the best prior never enters the candidates.  This is exact.  For query q and row i of the searched prefix
+ *     score(q, i) = fl32( D(q, i) + fl32( w[q] * p[i] ) )
+ * with D the canonical distance ehx_knn returns, the multiply and the add each rounded to fp32 on their own (no fused
+ * multiply-add).  The call takes ONE acquire-load snapshot of the row count.  Row q of the answer is the first k rows of the
+ * prefix in ascending (score, id) order; a row whose score is NaN (a NaN distance, a NaN penalty, Inf - Inf, 0 * Inf) is never
+ * a neighbour, exactly as ehx_knn treats a NaN distance; +-Inf scores are ordered; sentinels (id 2^64 - 1, +Inf) stand behind
+ * d_out_count[q].  d_out_score takes the place of ehx_knn's distances: it holds the score bytes.
+ * The penalties p: a device array float[n_penalty], any value allowed, negative ones included.  The searched prefix is
+ * min(snapshot, n_penalty): rows without a penalty are not returned (the convention of n_bits in ehx_knn_masked).
+ * The weights w: one per query, finite and >= 0; d_weight == NULL: 1 for every query.  The device form reads them back first
+ * (one small copy and a wait on `stream`) and checks them before anything is enqueued.
+ * Outputs [n_queries][k], 1 <= k <= EHX_MAX_K_GROUPED.
+ * Errors: a NULL space, k == 0, NULL outputs, NULL queries with n_queries > 0, NULL penalties with n_penalty > 0, a negative,
+ * NaN or infinite weight: EHX_EINVAL; k > EHX_MAX_K_GROUPED, a row-sharded space, rows longer than 32 736 floats (the pool and
+ * the prepared query share one CU's LDS): EHX_EUNSUPPORTED; a dropped space: EHX_ENOTFOUND; n_queries == 0: EHX_OK.  A call
+ * that fails writes no output.
+ * Served by the falling-radius scan of the int8 filter where ehx_knn_device's large-k route would serve the prefix (flat spaces
+ * whose first engine is the int8 filter, device batches of at least 64 queries; every k here): the scan bounds the DISTANCE
+ * under a radius derived from the k-th SCORE held and the least penalty, the exact re-rank behind it gathers the penalties
+ * BEFORE it reads a row and ranks on the score.  The filter is only as tight as w (p - p_min) is small against the spread of
+ * the distances: a large weight makes the distance radius loose, more rows are re-ranked and more queries are handed to the
+ * exact route.  Everything else — graph spaces (from their stored rows: the graph is not walked), small spaces, EHX_SCAN_F32 /
+ * _F16, small batches, the queries the scan hands on, and every call whose penalties hold -Inf or no finite value — by an
+ * exact pass over every prefix row in slabs of 4096.  DESIGN.md §e.32. */
+int ehx_knn_boosted_device(ehx_space* s, void* stream, size_t n_queries, const float* d_queries, uint32_t k, const float* d_penalty,
+                           uint64_t n_penalty, const float* d_weight, uint64_t* d_out_ids, float* d_out_score,
+                           uint32_t* d_out_count);
+/* ... from host pointers: ehx_knn_boosted_device plus the H2D / D2H copies, on the space's own stream; every EHX_EINVAL above is
+ * decided before the device is looked for. */
+int ehx_knn_boosted(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, const float* penalty, uint64_t n_penalty,
+                    const float* weight, uint64_t* out_ids, float* out_score, uint32_t* out_count);
+/* ... with the penalty a linear decay of a stored column (ehx_set_batch_cols): p[i] = (float) min(|col[i] - origin|, span), the
+ * absolute difference in unsigned arithmetic, the conversion to float round-to-nearest — a decay by a stored timestamp, price
+ * or counter; nothing is uploaded per call.  Every row of the snapshot is searched; p >= 0.  A column never written reads as
+ * EHX_GROUP_NONE for every row, as in the label searches (no error); col >= EHX_MAX_COLUMNS: EHX_EINVAL.  Everything else as
+ * ehx_knn_boosted_device: byte for byte its answer for the same penalties given as an array. */
+int ehx_knn_decay_device(ehx_space* s, void* stream, size_t n_queries, const float* d_queries, uint32_t k, uint32_t col,
+                         uint32_t origin, uint32_t span, const float* d_weight, uint64_t* d_out_ids, float* d_out_score,
+                         uint32_t* d_out_count);
+int ehx_knn_decay(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, uint32_t col, uint32_t origin, uint32_t span,
+                  const float* weight, uint64_t* out_ids, float* out_score, uint32_t* out_count);
 /* Profile search ("recommend by examples"): the query is not a vector the caller holds but a weighted sum of rows the space
  * already holds — "items near what this user liked, weighted by recency, minus what they disliked, and none of the items
  * already in their history" — and the same list is the query's exclusion list.  The lists come in the CSR form of
