@@ -142,6 +142,9 @@ SYMBOLS = {
     "ehx_knn_decay": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _f32p, _u64p, _f32p,
                                 _u32p]),
     "ehx_combine_rows_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t, _vp, _vp]),
+    "ehx_assign_device": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint32, _vp, _vp]),
+    "ehx_centroid_sums_device": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint32, _vp, _vp]),
+    "ehx_kmeans_device": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _u32p]),
     "ehx_knn_profile_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t, C.c_uint32, _vp, _vp, _vp]),
     "ehx_knn_profile": (C.c_int, [_vp, C.c_size_t, _u64p, _u64p, _f32p, C.c_size_t, C.c_uint32, _u64p, _f32p, _u32p]),
     "ehx_knn_profile_keys": (C.c_int, [_vp, C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), _u64p, _f32p, C.c_size_t,

@@ -654,6 +654,18 @@ struct ehx_space {
     HostStage host;
     uint64_t calls = 0, rebuilds = 0;
   } maxsim;
+  // Assignment and Lloyd steps (ehx_assign.cpp; scratch_mu): the prepared centroids (padded to whole tiles of the filter), their
+  // |c|^2, the list of rows the filter hands to the exact kernel, the control words [rows handed on | rows certified | a
+  // centroid is not finite | rows moved] and where they land; the sums' sort (keys and positions, ping-pong, and the digit
+  // histograms); a k-means call's sums, counts and previous labels.  by.by_ev orders a call behind the last one that used
+  // them and is what a Set that rewrites rows in place waits for.  assign_ctr: rows the filter certified, rows the exact
+  // kernel answered (test hook ehx_test_assign_counts).
+  struct Assign {
+    DevBuf<float> dQ, dCn2, dSums;
+    DevBuf<uint32_t> dList, dCtl, dKey[2], dVal[2], dHist, dCount, dPrev;
+    PinBuf<uint32_t> hCtl;
+  } assign;
+  std::atomic<uint64_t> assign_ctr[2] = {};
   // Stored label columns (ehx_columns.cpp): column c is one uint32_t per row, written through the write path by key.
   // dCol[c] is sized to `cap` and moved by grow with the rows; col_live[c] turns true under mu held exclusively, at the
   // column's first write (readers hold mu at least shared; the writers, serialised by wmu, may read it under wmu alone).  A
@@ -792,6 +804,7 @@ struct ehx_space {
     profile = {};
     mmr = {};
     maxsim = {};
+    assign = {};
     cols = {};
     for (auto& x : colidx) x = ColIndex{};
     one = {};

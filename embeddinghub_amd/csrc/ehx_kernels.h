@@ -842,8 +842,46 @@ struct CombineRowsArgs {
   float* out;               // [nq][dims] the targets
   uint32_t* valid;          // [nq] 0: no entry of the list names a row (the target is +0 everywhere)
   uint32_t nq;
+  // The centroid sums (ehx_centroid_sums_device) only: sorted_key != nullptr — "query" c's list is not ids[off[c], off[c + 1])
+  // but the rows row0 + sorted_pos[e] of the entries e with sorted_key[e] == c, of ANY length (the kernel takes it through
+  // LDS in pieces of kProfileMaxList); the keys ascending, the positions ascending inside a key; count[c] = the list's
+  // length is written instead of valid.  ids, off, weights and valid are then not read.
+  const uint32_t* sorted_key = nullptr;   // [n_sorted]
+  const uint32_t* sorted_pos = nullptr;   // [n_sorted]
+  uint64_t row0 = 0;
+  uint32_t n_sorted = 0;
+  uint32_t* count = nullptr;              // [nq]
 };
 hipError_t launch_combine_rows(const CombineRowsArgs& a, int n_cus, hipStream_t st);
+
+// nearest-centroid assignment and Lloyd steps (k_assign.hip; ehx_assign.cpp): include/ehx.h has the contract
+constexpr uint32_t kAssignMaxCentroids = 4096;   // EHX_ASSIGN_MAX_CENTROIDS
+constexpr uint32_t kAssignTileC = 128;           // the prepared centroids are padded to whole tiles of the filter (zero rows)
+struct AssignArgs {
+  RowsView rows;         // stored rows, any layout (the filter: plain fp32 or binary16 only)
+  const float* cent;     // prepared centroids [c_rows][ld] (launch_prep_queries with q_rows = c_rows, c_rows % kAssignTileC == 0)
+  const float* cn2;      // [c_rows] launch_centroid_stats
+  const uint32_t* bad;   // launch_centroid_stats' flag: a centroid is not finite, the filter certifies nothing
+  uint64_t row0;         // the call's range [row0, row0 + n_rows), inside rows.n_rows
+  uint32_t n_rows, n_cent;
+  uint32_t* label;       // [n_rows]
+  float* dist;           // [n_rows] or nullptr
+  uint32_t* list;        // [n_rows] the rows (relative to row0) the filter hands on, in any order
+  uint32_t* ctl;         // [0] += rows handed on (the list's length; zero before the filter), [1] += rows certified
+};
+uint32_t assign_max_ld();         // longest row stride (floats) the filter takes: its smallest row tile and the slabs share one CU's LDS
+uint32_t assign_exact_max_ld();   // ... the exact kernel: a block of prepared centroids in LDS
+// cn2[c] = |c|^2 of every prepared centroid; *bad |= 1 if one of the first n_cent is not finite (*bad: zero before)
+hipError_t launch_centroid_stats(const float* cent, uint32_t c_rows, uint32_t n_cent, uint32_t ld, float* cn2, uint32_t* bad,
+                                 hipStream_t st);
+hipError_t launch_assign_filter(const AssignArgs& a, hipStream_t st);
+// listed: the rows list[0, n_work); else the rows [0, n_work) of the range
+hipError_t launch_assign_exact(const AssignArgs& a, uint32_t n_work, bool listed, int n_cus, hipStream_t st);
+// keys[i] = label[i] < n_cent ? label[i] : n_cent — what the sums' sort orders the range by
+hipError_t launch_label_keys(const uint32_t* label, uint32_t n, uint32_t n_cent, uint32_t* keys, hipStream_t st);
+// cent[c][j] = sums[c][j] / (float)count[c] where count[c] > 0 (cent: [n_cent][dims], the caller's layout)
+hipError_t launch_lloyd_divide(const float* sums, const uint32_t* count, uint32_t n_cent, uint32_t dims, float* cent, hipStream_t st);
+hipError_t launch_count_moved(const uint32_t* was, const uint32_t* is, uint32_t n, uint32_t* moved, hipStream_t st);
 // the rows of the queries with valid[q] == 0: count 0, sentinels (id ~0, +Inf) in all k places
 hipError_t launch_blank_invalid(const uint32_t* valid, uint32_t nq, uint32_t k, uint64_t* out_ids, float* out_dist,
                                 uint32_t* out_count, hipStream_t st);

@@ -30,6 +30,7 @@
 //   ehx_test_rows_prefix       launch_rows_prefix on host arrays (a device, no space)
 // ... and of the MaxSim search (ehx_maxsim.cpp, k_maxsim.hip):
 //   ehx_test_maxsim_counters   calls, candidates scored, rows walked, index rebuilds the calls caused
+//   ehx_test_assign_counts     rows the assignment's filter certified, rows its exact kernel answered
 // No production path calls in here.
 #include "ehx_internal.h"
 
@@ -552,6 +553,13 @@ int ehx_test_maxsim_counters(ehx_space* s, uint64_t out[4]) {
 ehx_space* ehx_test_shard(ehx_space* s, uint32_t i) { return s && i < s->shards.size() ? s->shards[i] : nullptr; }
 
 // how many ehx_knn calls the one-launch kernels answered (single_query_kernel, the graph search's one-launch form)
+int ehx_test_assign_counts(ehx_space* s, uint64_t out[2]) {
+  if (!s || !out) return fail(EHX_EINVAL, "NULL argument");
+  out[0] = s->assign_ctr[0].load(std::memory_order_relaxed);
+  out[1] = s->assign_ctr[1].load(std::memory_order_relaxed);
+  return EHX_OK;
+}
+
 uint64_t ehx_test_one_launch_count(ehx_space* s) { return s ? s->n_one_launch.load(std::memory_order_relaxed) : 0; }
 
 }  // extern "C"

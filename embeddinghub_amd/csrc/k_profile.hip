@@ -65,27 +65,41 @@ __device__ __forceinline__ void unit_madd(float4* acc, float w, const float4& ra
     acc[0] = madd4(acc[0], w, raw);
   }
 }
+
+// number of entries of the ascending global array a[0, n) that are < key
+__device__ __forceinline__ uint32_t lower_bound_u32(const uint32_t* __restrict__ a, uint32_t n, uint32_t key) {
+  uint32_t lo = 0, hi = n;
+  while (lo < hi) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if (a[mid] < key) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
 }  // namespace
 
-template <bool HALFX, bool PERM>
+// SORTED (the centroid sums, ehx_assign.cpp): the list is a run of a label-sorted range and may have ANY length — it goes
+// through LDS in pieces of kProfileMaxList entries, the lane accumulators staying in registers across the pieces (a piece is a
+// multiple of 8 entries: an entry's strand by its place in the piece is its strand in the list); every weight is 1, and the
+// run's length is written where the other form writes valid[q].  !SORTED runs the piece loop once: the code it always was.
+template <bool HALFX, bool PERM, bool SORTED>
 __global__ __launch_bounds__(kThreads) void combine_rows_kernel(CombineRowsArgs a, uint32_t n_units, uint32_t slab_units) {
   constexpr uint32_t kF = HALFX ? 8 : 4, kU = HALFX ? 2 : 3, kV = kF / 4;   // floats of a unit, units per lane at most, float4 of a unit
   // the list as (row, weight bits) pairs; behind the walk, the strands' partials [8][slab_units * kF]
   __shared__ uint2 lds[kProfileMaxList];
   static_assert(sizeof(uint2) * kProfileMaxList >= sizeof(float) * kProfileStrands * 64 * kU * kF, "the partials re-use the list's LDS");
+  static_assert(kProfileMaxList % kProfileStrands == 0, "a piece keeps every entry's strand");
   const uint32_t tid = threadIdx.x, lane = tid & 63u, strand = tid >> 6, q = blockIdx.x;
-  const uint64_t e0 = a.off[q];
-  const uint64_t len = a.off[q + 1] - e0;
-  const uint32_t L = len < kProfileMaxList ? (uint32_t)len : kProfileMaxList;
-  bool names = false;
-  for (uint32_t e = tid; e < L; e += kThreads) {
-    const uint64_t id = a.ids[e0 + e];
-    const bool ok = id < a.rows.n_rows;
-    names |= ok;
-    lds[e] = make_uint2(ok ? (uint32_t)id : kNoRow, a.weights ? __float_as_uint(a.weights[e0 + e]) : 0x3F800000u);
+  uint64_t e0, len;
+  if (SORTED) {
+    e0 = lower_bound_u32(a.sorted_key, a.n_sorted, q);
+    len = lower_bound_u32(a.sorted_key, a.n_sorted, q + 1u) - e0;
+    if (blockIdx.y == 0 && tid == 0) a.count[q] = (uint32_t)len;
+  } else {
+    e0 = a.off[q];
+    len = a.off[q + 1] - e0;
+    if (len > kProfileMaxList) len = kProfileMaxList;
   }
-  const int any = __syncthreads_or(names ? 1 : 0);
-  if (blockIdx.y == 0 && tid == 0) a.valid[q] = any ? 1u : 0u;
 
   // this lane's units of the slab (one beyond the row is clamped into it: read, summed, never stored)
   const uint32_t u0 = blockIdx.y * slab_units;
@@ -102,41 +116,65 @@ __global__ __launch_bounds__(kThreads) void combine_rows_kernel(CombineRowsArgs 
 #pragma unroll
     for (uint32_t v = 0; v < kV; ++v) acc[j][v] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 
-  // strand `strand`: entries strand, strand + 8, ... in groups of kGroup; entry i of a group is list entry e + 8 i
-  uint2 ent[kGroup], ent_next[kGroup];
-  float4 raw[kGroup][kU], raw_next[kGroup][kU];
-  auto fetch = [&](uint32_t e, uint2* en, float4 (*rw)[kU]) {
+  uint64_t p0 = 0;   // where the piece begins in the list
+  do {
+    const uint32_t L = len - p0 < kProfileMaxList ? (uint32_t)(len - p0) : kProfileMaxList;
+    if (SORTED) {
+      if (p0) __syncthreads();   // (every wave is done with the last piece)
+      for (uint32_t e = tid; e < L; e += kThreads) {
+        const uint64_t id = a.row0 + a.sorted_pos[e0 + p0 + e];
+        lds[e] = make_uint2(id < a.rows.n_rows ? (uint32_t)id : kNoRow, 0x3F800000u);
+      }
+      __syncthreads();
+    } else {
+      bool names = false;
+      for (uint32_t e = tid; e < L; e += kThreads) {
+        const uint64_t id = a.ids[e0 + e];
+        const bool ok = id < a.rows.n_rows;
+        names |= ok;
+        lds[e] = make_uint2(ok ? (uint32_t)id : kNoRow, a.weights ? __float_as_uint(a.weights[e0 + e]) : 0x3F800000u);
+      }
+      const int any = __syncthreads_or(names ? 1 : 0);
+      if (blockIdx.y == 0 && tid == 0) a.valid[q] = any ? 1u : 0u;
+    }
+
+    // strand `strand`: entries strand, strand + 8, ... in groups of kGroup; entry i of a group is list entry e + 8 i
+    uint2 ent[kGroup], ent_next[kGroup];
+    float4 raw[kGroup][kU], raw_next[kGroup][kU];
+    auto fetch = [&](uint32_t e, uint2* en, float4 (*rw)[kU]) {
 #pragma unroll
-    for (uint32_t i = 0; i < kGroup; ++i) {
-      const uint32_t ei = e + kProfileStrands * i;
-      en[i] = ei < L ? lds[ei] : make_uint2(kNoRow, 0u);   // (wave-uniform: every lane reads the same entry)
-      if (en[i].x != kNoRow) {
-        const char* __restrict__ row = X + (size_t)en[i].x * row_bytes;
+      for (uint32_t i = 0; i < kGroup; ++i) {
+        const uint32_t ei = e + kProfileStrands * i;
+        en[i] = ei < L ? lds[ei] : make_uint2(kNoRow, 0u);   // (wave-uniform: every lane reads the same entry)
+        if (en[i].x != kNoRow) {
+          const char* __restrict__ row = X + (size_t)en[i].x * row_bytes;
+#pragma unroll
+          for (uint32_t j = 0; j < kU; ++j)
+            if (j < upl) rw[i][j] = *(const float4*)(row + (size_t)unit[j] * 16);
+        }
+      }
+    };
+    if (strand < L) fetch(strand, ent, raw);
+    for (uint32_t e = strand; e < L; e += kProfileStrands * kGroup) {
+      const uint32_t en = e + kProfileStrands * kGroup;
+      if (en < L) fetch(en, ent_next, raw_next);
+#pragma unroll
+      for (uint32_t i = 0; i < kGroup; ++i) {
+        if (ent[i].x == kNoRow) continue;
+        const float w = __uint_as_float(ent[i].y);
 #pragma unroll
         for (uint32_t j = 0; j < kU; ++j)
-          if (j < upl) rw[i][j] = *(const float4*)(row + (size_t)unit[j] * 16);
+          if (j < upl) unit_madd<HALFX>(acc[j], w, raw[i][j]);
+      }
+#pragma unroll
+      for (uint32_t i = 0; i < kGroup; ++i) {
+        ent[i] = ent_next[i];
+#pragma unroll
+        for (uint32_t j = 0; j < kU; ++j) raw[i][j] = raw_next[i][j];
       }
     }
-  };
-  if (strand < L) fetch(strand, ent, raw);
-  for (uint32_t e = strand; e < L; e += kProfileStrands * kGroup) {
-    const uint32_t en = e + kProfileStrands * kGroup;
-    if (en < L) fetch(en, ent_next, raw_next);
-#pragma unroll
-    for (uint32_t i = 0; i < kGroup; ++i) {
-      if (ent[i].x == kNoRow) continue;
-      const float w = __uint_as_float(ent[i].y);
-#pragma unroll
-      for (uint32_t j = 0; j < kU; ++j)
-        if (j < upl) unit_madd<HALFX>(acc[j], w, raw[i][j]);
-    }
-#pragma unroll
-    for (uint32_t i = 0; i < kGroup; ++i) {
-      ent[i] = ent_next[i];
-#pragma unroll
-      for (uint32_t j = 0; j < kU; ++j) raw[i][j] = raw_next[i][j];
-    }
-  }
+    p0 += kProfileMaxList;
+  } while (SORTED && p0 < len);
 
   // the partials meet: part[strand][position in the slab, stored order]
   __syncthreads();   // (every wave is done with the list)
@@ -178,9 +216,16 @@ hipError_t launch_combine_rows(const CombineRowsArgs& a, int n_cus, hipStream_t 
   while (upl > 1 && (uint64_t)a.nq * ((n_units + 64 * upl - 1) / (64 * upl)) < (uint64_t)n_cus) --upl;
   const uint32_t whole = (n_units + 3u) / 4u * 4u, slab_units = 64 * upl < whole ? 64 * upl : whole;   // (a short row: one partial slab, whole blocks)
   const dim3 grid(a.nq, (n_units + slab_units - 1) / slab_units), block(kThreads);
-  if (half) hipLaunchKernelGGL((combine_rows_kernel<true, false>), grid, block, 0, st, a, n_units, slab_units);
-  else if (perm) hipLaunchKernelGGL((combine_rows_kernel<false, true>), grid, block, 0, st, a, n_units, slab_units);
-  else hipLaunchKernelGGL((combine_rows_kernel<false, false>), grid, block, 0, st, a, n_units, slab_units);
+  if (a.sorted_key) {   // the centroid sums
+    if (!a.sorted_pos || !a.count) return hipErrorInvalidValue;
+    if (half) hipLaunchKernelGGL((combine_rows_kernel<true, false, true>), grid, block, 0, st, a, n_units, slab_units);
+    else if (perm) hipLaunchKernelGGL((combine_rows_kernel<false, true, true>), grid, block, 0, st, a, n_units, slab_units);
+    else hipLaunchKernelGGL((combine_rows_kernel<false, false, true>), grid, block, 0, st, a, n_units, slab_units);
+    return hipGetLastError();
+  }
+  if (half) hipLaunchKernelGGL((combine_rows_kernel<true, false, false>), grid, block, 0, st, a, n_units, slab_units);
+  else if (perm) hipLaunchKernelGGL((combine_rows_kernel<false, true, false>), grid, block, 0, st, a, n_units, slab_units);
+  else hipLaunchKernelGGL((combine_rows_kernel<false, false, false>), grid, block, 0, st, a, n_units, slab_units);
   return hipGetLastError();
 }
 

@@ -651,6 +651,33 @@ class Space:
                                              _ptr(d_weights) if n else None, n, k, _ptr(d_out_ids), _ptr(d_out_dist),
                                              _ptr(d_out_count)))
 
+    # ---- clustering: labels made from the vectors themselves ----
+    def assign_device(self, d_centroids, d_label, d_dist=None, row0=0, n_rows=None, stream=None):
+        """Nearest centroid of every row of [row0, row0 + n_rows) (ehx_assign_device; n_rows None: up to the row count):
+        d_centroids [C, dims] f32, d_label [n_rows] u32 (int32 storage), d_dist [n_rows] f32 or None.  Torch CUDA tensors.
+        The label is the canonical argmin, ties to the lower centroid; 0xFFFFFFFF and NaN where no pair is a candidate."""
+        n_rows = len(self) - row0 if n_rows is None else int(n_rows)
+        check(self._L.ehx_assign_device(self._h, C.c_void_p(stream or 0), int(row0), n_rows, _ptr(d_centroids),
+                                        d_centroids.shape[0], _ptr(d_label), None if d_dist is None else _ptr(d_dist)))
+
+    def centroid_sums_device(self, d_label, n_centroids, d_sums, d_count, row0=0, n_rows=None, stream=None):
+        """Per centroid the 8-strand fp32 sum (combine_rows_device's definition, weights 1) of the rows of the range that
+        carry its label, in ascending row id, and their number (ehx_centroid_sums_device): d_label [n_rows] u32, d_sums
+        [n_centroids, dims] f32, d_count [n_centroids] u32 (int32 storage).  Torch CUDA tensors."""
+        n_rows = len(self) - row0 if n_rows is None else int(n_rows)
+        check(self._L.ehx_centroid_sums_device(self._h, C.c_void_p(stream or 0), int(row0), n_rows, _ptr(d_label),
+                                               int(n_centroids), _ptr(d_sums), _ptr(d_count)))
+
+    def kmeans_device(self, d_centroids, iters, d_label, d_dist=None, row0=0, n_rows=None, stream=None):
+        """`iters` Lloyd steps from d_centroids [C, dims] f32 (updated in place), then one last assignment against them into
+        d_label / d_dist (ehx_kmeans_device).  -> the number of rows whose entry of d_label that last assignment changed."""
+        n_rows = len(self) - row0 if n_rows is None else int(n_rows)
+        moved = C.c_uint32(0)
+        check(self._L.ehx_kmeans_device(self._h, C.c_void_p(stream or 0), int(row0), n_rows, d_centroids.shape[0], int(iters),
+                                        _ptr(d_centroids), _ptr(d_label), None if d_dist is None else _ptr(d_dist),
+                                        C.byref(moved)))
+        return int(moved.value)
+
     # ---- MMR search: k of fetch_k candidates, near the query and not near each other ----
     def knn_mmr(self, queries, k, fetch_k=None, lam=0.5):
         """Maximal marginal relevance (ehx_knn_mmr): the fetch_k nearest rows of every query (knn's answer at fetch_k),

@@ -1146,6 +1146,42 @@ int ehx_graph_import(ehx_space* s, uint64_t n, const uint32_t* level0, const int
 int ehx_graph_export(ehx_space* s, uint32_t* level0, int32_t* levels, uint32_t* up_start, uint32_t* up_lists,
                      uint64_t up_lists_cap, uint64_t* n_lists, uint32_t* entry_point, int32_t* max_level);
 
+/* ---- clustering: nearest-centroid assignment, centroid sums, k-means ----
+ * Labels made from the vectors themselves: what ehx_column_load_device stores and the labelled, grouped and filtered searches
+ * then read.  All three calls work on the rows [row0, row0 + n_rows), which must lie inside ONE acquire-load snapshot of the
+ * row count, hold the space's lock shared like ehx_knn_device, and run on `stream`.
+ * Assignment.  Centroid c plays the QUERY and a stored row the ROW of the canonical distance: the centroids go through the
+ * query preparation (padded; cosine: normalised by the canonical sequential norm) and a cosine row is normalised on the fly.
+ *   label[i]  the c that minimises the canonical distance to row row0 + i; ties go to the LOWER c.  A pair whose distance is
+ *             NaN is no candidate (ehx_knn's rule); +-Inf distances are ordinary keys.
+ *   dist[i]   that distance, to the byte.  A row with no candidate: label EHX_ASSIGN_NONE and a NaN.
+ * That is the first entry of every row's list when the exhaustive search of the rows, as queries' targets, is transposed.  A
+ * matrix-core pass answers the rows whose winner it can PROVE (second-best minus best score above a worst-case bound of both
+ * computations' error); every other row is walked canonically against all centroids.  The answer never depends on the route.
+ * Centroid sums.  Per centroid c < n_centroids: the rows of the range whose label is c, in ascending row id, are a list;
+ * d_out_sums[c] is ehx_combine_rows_device's target for that list with every weight 1 — eight strands, strand s adding the
+ * entries at list positions s, s + 8, ... in order from +0, the strands joined in strand order — over a list of ANY length,
+ * and d_out_count[c] its length.  A row labelled EHX_ASSIGN_NONE, or at or above n_centroids, belongs to no list.
+ * One Lloyd step: new_c = fl(sum_c / fl32(count_c)) per component where count_c > 0; a centroid with no rows keeps its
+ * bytes.  Centroids are not re-normalised for cosine: the next assignment's preparation does that.
+ * ehx_kmeans_device runs `iters` steps from the centroids it is given, then ONE last assignment against the centroids it
+ * returns: d_out_label and d_out_dist describe those.  *out_moved = the rows whose entry of d_out_label that last assignment
+ * changed (with iters == 0: against what the caller passed in), one 4-byte read-back.  The start centroids are the caller's
+ * business (ehx_get_by_ids_device of sampled ids, say).
+ * Errors: a NULL space, n_centroids == 0 or > EHX_ASSIGN_MAX_CENTROIDS, a NULL pointer that is not marked optional, a range
+ * that does not lie inside the row count: EHX_EINVAL; a row-sharded space, n_rows >= 2^32: EHX_EUNSUPPORTED; n_rows == 0:
+ * EHX_OK, nothing is written.  The assignment waits once on `stream`, for the number of rows handed to the canonical walk. */
+#define EHX_ASSIGN_MAX_CENTROIDS 4096u
+#define EHX_ASSIGN_NONE 0xFFFFFFFFu
+int ehx_assign_device(ehx_space* s, void* stream, uint64_t row0, uint64_t n_rows,
+                      const float* d_centroids /* [n_centroids, dims] fp32, row-major */, uint32_t n_centroids,
+                      uint32_t* d_out_label /* [n_rows] */, float* d_out_dist /* [n_rows], NULL ok */);
+int ehx_centroid_sums_device(ehx_space* s, void* stream, uint64_t row0, uint64_t n_rows, const uint32_t* d_label,
+                             uint32_t n_centroids, float* d_out_sums /* [n_centroids, dims] */, uint32_t* d_out_count);
+int ehx_kmeans_device(ehx_space* s, void* stream, uint64_t row0, uint64_t n_rows, uint32_t n_centroids, uint32_t iters,
+                      float* d_centroids /* in: the start; out: after `iters` steps */, uint32_t* d_out_label,
+                      float* d_out_dist /* NULL ok */, uint32_t* out_moved /* host; NULL ok */);
+
 /* ---- stats ---- */
 int ehx_stats(ehx_space* s, ehx_stats_t* out);
 int ehx_stats_reset(ehx_space* s);
