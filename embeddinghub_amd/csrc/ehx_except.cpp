@@ -46,17 +46,14 @@ int except_check_ld(const ehx_space* s) {
   return EHX_OK;
 }
 
-}  // namespace ehx_impl
-
-namespace {
-
-// the offsets of a call, host memory: non-decreasing, ending at n_excl, no list longer than the kernel's
-int except_check_off(const uint64_t* off, size_t nq, size_t n_excl, const char* name, const char* n_name) {
+// the offsets of a call, host memory: non-decreasing, ending at n_excl, no list longer than the kernel's (instead: the entry
+// point the message names for longer lists)
+int except_check_off(const uint64_t* off, size_t nq, size_t n_excl, const char* name, const char* n_name, const char* instead) {
   for (size_t i = 0; i < nq; ++i) {
     if (off[i] > off[i + 1]) return fail(EHX_EINVAL, "%s is not non-decreasing at query %zu", name, i);
     if (off[i + 1] - off[i] > EHX_EXCEPT_MAX_LIST)
-      return fail(EHX_EINVAL, "query %zu excludes %llu entries, more than EHX_EXCEPT_MAX_LIST = %u: use ehx_knn_masked_multi with a bitmap per query",
-                  i, (unsigned long long)(off[i + 1] - off[i]), EHX_EXCEPT_MAX_LIST);
+      return fail(EHX_EINVAL, "query %zu excludes %llu entries, more than EHX_EXCEPT_MAX_LIST = %u: use %s with a bitmap per query",
+                  i, (unsigned long long)(off[i + 1] - off[i]), EHX_EXCEPT_MAX_LIST, instead);
   }
   if (off[nq] != n_excl)
     return fail(EHX_EINVAL, "%s ends at %llu, not at %s = %zu", name, (unsigned long long)off[nq], n_name, n_excl);
@@ -125,7 +122,21 @@ int except_exact(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, const 
   return EHX_OK;
 }
 
-}  // namespace
+// the row ids of a call's stored keys (space locked shared; takes kmu shared).  A key that is not stored names no row: an id
+// no prefix holds, which the list preparation drops
+int except_key_ids(ehx_space* s, const char* const* keys, const size_t* klens, size_t n_keys, std::vector<uint64_t>* ids) {
+  ids->assign(n_keys, ~0ull);
+  std::shared_lock<std::shared_mutex> kl(s->kmu);
+  for (size_t i = 0; i < n_keys; ++i) {
+    if (!keys[i]) return fail(EHX_EINVAL, "NULL argument");
+    if (implicit_id(s, keys[i], klens[i], &(*ids)[i])) continue;
+    auto it = s->key_to_id.find(std::string(keys[i], klens[i]));
+    if (it != s->key_to_id.end()) (*ids)[i] = it->second;
+  }
+  return EHX_OK;
+}
+
+}  // namespace ehx_impl
 
 // an unsharded space, locked shared, scratch_mu held, its device current, not poisoned, its rows within except_check_ld;
 // everything is enqueued on `st`.  The lists are on the device and their offsets checked (except_check_off).  n_pub: the
@@ -262,17 +273,8 @@ int ehx_knn_except_keys(ehx_space* s, size_t n_queries, const float* queries, ui
   if (int rc = ehx_init(nullptr, 0)) return rc;
   // ONE shared hold for key lookup and search: the answer describes one state of the space
   return search_shared(s, "ehx_knn_except_keys", kExceptWhy, [&]() -> int {
-    // (a key that is not stored names no row: an id no prefix holds, which the list preparation drops)
-    std::vector<uint64_t> ids(n_keys, ~0ull);
-    {
-      std::shared_lock<std::shared_mutex> kl(s->kmu);
-      for (size_t i = 0; i < n_keys; ++i) {
-        if (!keys[i]) return fail(EHX_EINVAL, "NULL argument");
-        if (implicit_id(s, keys[i], klens[i], &ids[i])) continue;
-        auto it = s->key_to_id.find(std::string(keys[i], klens[i]));
-        if (it != s->key_to_id.end()) ids[i] = it->second;
-      }
-    }
+    std::vector<uint64_t> ids;
+    if (int rc = except_key_ids(s, keys, klens, n_keys, &ids)) return rc;
     return on_device(s, n_queries, s->stream, [&] {
       return except_host_locked(s, n_queries, queries, k, ids.data(), key_off, n_keys, out_ids, out_dist, out_count);
     });

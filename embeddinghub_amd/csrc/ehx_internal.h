@@ -600,6 +600,7 @@ struct ehx_space {
     DevBuf<uint32_t> dSortedCnt; // [queries]
     DevBuf<uint64_t> dLists;     // host form: ids | offsets
     HostStage host;
+    SubsetBufs split;            // ehx_graph_knn_except*: the walked and the exact part of a device batch EHX_WALK_AUTO splits
   } except;
   // test hook: queries answered on the scan route, handed to the exact route (by the gate or by the scan route), of those the
   // ones whose pool overflowed, scan passes launched, calls
@@ -857,6 +858,12 @@ struct GraphMask {        // the walk under a row bitmap (k_graphm.hip): always 
   uint64_t n_bits;         // already cut at the call's snapshot of the row count
   unsigned long long* cap_hits;   // device counter: queries whose list reached its cap
   const uint32_t* allow_of;       // nullptr: ONE bitmap; else device [nq]: query i's bitmap begins allow_of[i] words into allow
+  // excl != nullptr: an exclusion list per query in the bitmap's place (k_graphx.hip; allow unused, n_bits the call's row
+  // count) — GraphArgs' excl, excl_cnt, excl_of and excl_lds
+  const uint32_t* excl = nullptr;
+  const uint32_t* excl_cnt = nullptr;
+  const uint32_t* excl_of = nullptr;
+  uint32_t excl_lds = 0;
 };
 // the walk list's length under a bitmap, a function of ef alone: max(ef, min(EHX_WALK_LIST_FACTOR * ef, EHX_WALK_LIST_MAX))
 inline uint32_t graph_walk_cap(uint32_t ef) {
@@ -1075,6 +1082,15 @@ int except_check_ld(const ehx_space* s);   // rows wider than the except re-rank
 // on `st`.  n_pub: the call's ONE read of the row count (the profile search sums its targets under the same one).
 int except_locked_at(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, const float* d_queries, uint32_t k,
                      const uint64_t* d_excl_ids, const uint64_t* d_excl_off, const ResultBlock& out);
+// what ehx_graph_knn_except* (ehx_graphx.cpp) share with these entry points: the check of a call's offsets in host memory, the
+// exact route for nq queries (their lists given, or — d_excl_off == nullptr, nq <= kSideChunk — query j's being list d_list_of[j],
+// nullptr: list j, of the lists a device batch left sorted in except.dSorted), and the ids of a call's stored keys
+int except_check_off(const uint64_t* off, size_t nq, size_t n_excl, const char* name, const char* n_name,
+                     const char* instead = "ehx_knn_masked_multi");
+int except_exact(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, const float* d_queries, uint32_t k,
+                 const uint64_t* d_excl_ids, const uint64_t* d_excl_off, const uint32_t* d_list_of, uint64_t* d_ids, float* d_dist,
+                 uint32_t* d_count, bool count_queries);
+int except_key_ids(ehx_space* s, const char* const* keys, const size_t* klens, size_t n_keys, std::vector<uint64_t>* ids);
 
 // ---- ehx_range.cpp ----
 constexpr uint32_t kRangeGridTarget = 4096;   // workgroups an exact range kernel's launch aims for (16 per CU): chosen, not measured
@@ -1157,6 +1173,7 @@ int rangem_check(const ehx_space* s, size_t nq, uint32_t max_results, const void
 int rangem_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_queries, const float* d_radius, uint32_t max_results,
                   const MaskTable& tab, uint64_t n_bits, const uint32_t* mask_of, const uint32_t* d_mask_of,
                   const ResultBlock& out);
+int check_route(uint32_t route);   // none of EHX_WALK_AUTO / _GRAPH / _EXACT: EHX_EINVAL
 // ehx_graph_knn_masked_multi* (ehx_masked.cpp): the walk, the exact answer or both, by `route` and per mask
 int graphm_table_check(const ehx_space* s, size_t nq, uint32_t k, const void* q, const void* masks, uint32_t n_masks,
                        uint64_t n_bits, const void* mask_of, uint32_t route, const void* o_ids, const void* o_dist,

@@ -970,12 +970,22 @@ struct GraphArgs {
   uint32_t allow_bits = 0;
   unsigned long long* cap_hits = nullptr;
   const uint32_t* allow_of = nullptr;   // [nq] word offsets, or nullptr: ONE bitmap for the batch
+  // The walk under an exclusion list PER QUERY (k_graphx.hip; launch_graph_search_except only): row r is allowed iff
+  // r < allow_bits and query i's list does not hold r.  The lists are launch_except_lists' — ascending unique 32-bit ids,
+  // kExceptMaxList apart, their lengths in excl_cnt — and query i's is list excl_of[i] (nullptr: list i).  excl_lds: the
+  // entries the kernel's LDS has room for, a multiple of 64 that no list of the launch exceeds.  allow is unused.
+  const uint32_t* excl = nullptr;
+  const uint32_t* excl_cnt = nullptr;
+  const uint32_t* excl_of = nullptr;
+  uint32_t excl_lds = 0;
 };
 size_t graph_lds_bytes(uint32_t ld, uint32_t ef_cap, uint32_t width = 1);
 hipError_t launch_graph_search(const GraphArgs& a, hipStream_t st);
 // the strict walk that carries a row bitmap, or with a.allow_of one per query: keys hold the row id in 30 bits
 // (a.n <= 2^30), width is ignored
 hipError_t launch_graph_search_masked(const GraphArgs& a, hipStream_t st);
+// the same walk with a.excl, a sorted exclusion list per query held in LDS, in the bitmap's place
+hipError_t launch_graph_search_except(const GraphArgs& a, hipStream_t st);
 
 // graph-mode insertion (k_insert.hip)
 // hipFuncAttributeMaxDynamicSharedMemorySize is set per function AND per device (every device has its own loaded code

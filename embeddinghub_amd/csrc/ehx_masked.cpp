@@ -414,12 +414,6 @@ int masked_host_locked(ehx_space* s, size_t nq, const float* queries, uint32_t k
 // A batch of a table may therefore be mixed: its walked queries take ONE walk launch, the others ONE masked_answer over the
 // same plan, each part gathered and scattered back (masked.split); a batch that is all walk or all exact is answered in
 // place.  A flat space has no graph: the exact route. ----
-int check_route(uint32_t route) {
-  if (route != EHX_WALK_AUTO && route != EHX_WALK_GRAPH && route != EHX_WALK_EXACT)
-    return fail(EHX_EINVAL, "route %u is none of EHX_WALK_AUTO, EHX_WALK_GRAPH, EHX_WALK_EXACT", route);
-  return EHX_OK;
-}
-
 int graphm_check(const ehx_space* s, size_t nq, uint32_t k, const void* q, const void* mask, uint64_t n_bits, uint32_t route,
                  const void* o_ids, const void* o_dist, const void* o_cnt) {
   if (int rc = masked_check(s, nq, k, q, mask, n_bits, o_ids, o_dist, o_cnt)) return rc;
@@ -429,6 +423,12 @@ int graphm_check(const ehx_space* s, size_t nq, uint32_t k, const void* q, const
 }  // namespace
 
 namespace ehx_impl {
+
+int check_route(uint32_t route) {
+  if (route != EHX_WALK_AUTO && route != EHX_WALK_GRAPH && route != EHX_WALK_EXACT)
+    return fail(EHX_EINVAL, "route %u is none of EHX_WALK_AUTO, EHX_WALK_GRAPH, EHX_WALK_EXACT", route);
+  return EHX_OK;
+}
 
 int graphm_table_check(const ehx_space* s, size_t nq, uint32_t k, const void* q, const void* masks, uint32_t n_masks,
                        uint64_t n_bits, const void* mask_of, uint32_t route, const void* o_ids, const void* o_dist,

@@ -25,28 +25,9 @@
 // descent, ranking, merge, the visited bitmap's log and clear — is k_graph_common.h's.
 // The walk is written once (k_graphm_walk.h, the body of both kernel templates below); the kernels of a table differ in
 // the two places a bit is tested: the word is allow[allow_of[qi] + (id >> 5)].
-#include "k_graph_common.h"
+#include "k_graphm_keys.h"
 
 namespace ehx {
-
-namespace {
-
-constexpr uint64_t kKeyExpanded = 1ull, kKeyAllowed = 2ull;
-__device__ __forceinline__ uint32_t mkey_id(uint64_t key) { return (uint32_t)(key & 0xFFFFFFFFull) >> 2; }
-
-// the kernel's argument block where it lies in memory (scalar loads at the point of use; the empty asm keeps them there)
-typedef const GraphArgs __attribute__((address_space(4)))* KernArgs;
-__device__ __forceinline__ KernArgs late_args() {
-  KernArgs p = (KernArgs)__builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(p));
-  return p;
-}
-// query qi's entry of a [nq] argument array the host wrote before the launch: wave-uniform and constant while the kernel
-// runs, so it is read with a scalar load (no vector-memory round trip in front of the load that depends on it)
-typedef const uint32_t __attribute__((address_space(4)))* ConstWords;
-__device__ __forceinline__ uint32_t uniform_word(const uint32_t* p, uint32_t qi) { return ((ConstWords)p)[qi]; }
-
-}  // namespace
 
 // ONE bitmap for the batch
 template <int METRIC01>

@@ -1,8 +1,13 @@
-// The body of the walk kernels of k_graphm.hip — included INSIDE each of them, not a header of declarations: with
+// The body of the walk kernels of k_graphm.hip and k_graphx.hip — included INSIDE each of them, not a header of declarations: with
 //   METRIC01   0: L2, 1: the dot-product metrics
-//   TABLE      0: ONE bitmap for the batch; 1: a bitmap PER QUERY (ehx_graph_knn_masked_multi*) — a.allow is a table of bitmaps
+//   TABLE      how a row's allowed bit is found.  0: ONE bitmap for the batch; 1: a bitmap PER QUERY (ehx_graph_knn_masked_multi*) — a.allow is a table of bitmaps
 //              and query qi's begins a.allow_of[qi] words into it.  The offset is wave-uniform and is read where a bit is
 //              tested (one scalar load beside the ones late_args() already issues there), never held across the level-0 loop
+//              2: an EXCLUSION LIST per query (k_graphx.hip, ehx_graph_knn_except*) — no bitmap: the query's ascending list of
+//              excluded ids (a.excl) is copied into LDS behind the walk's own carve, sixteen bytes a lane and four such loads
+//              in flight, in front of the query row's loads: the descent's first row fetch queues behind it.  A row is allowed
+//              iff it lies below a.allow_bits and the list does not hold it: every lane searches its own id (lds_list_holds),
+//              in the same two places.  The list's LDS address and its length are wave-uniform and held across the loop
 //   a          the kernel's GraphArgs
 // in scope.  Text, not a __device__ function: a function inlined into the kernels is optimised on its own first (without
 // the kernel's launch bounds) and came out as other code for the one-bitmap pair than the kernel written out — 2 % or so
@@ -17,6 +22,31 @@
   uint32_t* ids_l = L.ids;
   uint32_t n_logged = 0;  // rows marked visited so far (wave-uniform)
   for (uint32_t i = lane; i < a.ef_cap; i += 64) L.F[i] = 0;
+  uint32_t* xl = nullptr;  // TABLE == 2: the query's list in LDS and its length
+  uint32_t xn = 0;
+  if (TABLE == 2) {
+    xl = (uint32_t*)(smem + graph_list_lds_offset(a.ld, a.ef_cap));
+    const uint32_t slot = a.excl_of ? uniform_word(a.excl_of, qi) : qi;
+    const uint32_t have = uniform_word(a.excl_cnt, slot);
+    xn = have < a.excl_lds ? have : a.excl_lds;
+    // (whole 16-byte pieces: up to three entries behind the list are copied with it — they lie inside the list's
+    // kExceptMaxList entries of the scratch and inside the LDS region, a multiple of 64 entries — and are never searched)
+    const uint4* src = (const uint4*)(a.excl + (size_t)slot * kExceptMaxList);
+    uint4* dst = (uint4*)xl;
+    const uint32_t n4 = (xn + 3u) >> 2;
+    for (uint32_t i = lane; i < n4; i += 256) {
+      const uint32_t i1 = i + 64u, i2 = i + 128u, i3 = i + 192u;
+      const uint4 none = {0u, 0u, 0u, 0u};
+      const uint4 v0 = src[i];
+      const uint4 v1 = i1 < n4 ? src[i1] : none;
+      const uint4 v2 = i2 < n4 ? src[i2] : none;
+      const uint4 v3 = i3 < n4 ? src[i3] : none;
+      dst[i] = v0;
+      if (i1 < n4) dst[i1] = v1;
+      if (i2 < n4) dst[i2] = v2;
+      if (i3 < n4) dst[i3] = v3;
+    }
+  }
   load_query<1>(a, L.qs, qi, 0, lane);
 
   WalkCounters ctr;
@@ -41,7 +71,9 @@
   const uint64_t lt_lane = (1ull << lane) - 1ull;
   // allowed entries of R: exact behind every trim, an upper bound in between (entries the merge dropped behind cap are
   // not taken off); trimmed: R holds exactly ef of them and ends with one
-  uint32_t n_allow = cur < al->allow_bits && ((al->allow[(TABLE ? uniform_word(al->allow_of, qi) : 0u) + (cur >> 5)] >> (cur & 31)) & 1u) ? 1u : 0u;
+  uint32_t n_allow;
+  if (TABLE == 2) n_allow = cur < al->allow_bits && !lds_list_holds(xl, xn, cur) ? 1u : 0u;
+  else n_allow = cur < al->allow_bits && ((al->allow[(TABLE ? uniform_word(al->allow_of, qi) : 0u) + (cur >> 5)] >> (cur & 31)) & 1u) ? 1u : 0u;
   n_allow = wave_uniform(n_allow);   // (>= ef at the head of a step: R is trimmed, and then it is ef exactly)
   uint32_t nR = 1;
   if (lane == 0) {
@@ -108,10 +140,12 @@
     }
     const bool fresh = nb != kNoNode && !(word & (1u << (nb & 31)));
     if (fresh) (void)__hip_atomic_fetch_or(&vis[nb >> 5], 1u << (nb & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    // the allowed bit of a fresh id: its word of the bitmap, in flight beside the row fetches
+    // the allowed bit of a fresh id: its word of the bitmap, in flight beside the row fetches (TABLE == 2: all ones or none,
+    // by the search of the list in LDS — every lane takes the same number of steps, whatever it holds)
     const KernArgs ap = late_args();
     uint32_t aword = 0;
-    if (fresh && nb < ap->allow_bits) aword = ap->allow[(TABLE ? uniform_word(ap->allow_of, qi) : 0u) + (nb >> 5)];
+    if (TABLE == 2) aword = nb < ap->allow_bits && !lds_list_holds(xl, xn, nb) ? ~0u : 0u;
+    else if (fresh && nb < ap->allow_bits) aword = ap->allow[(TABLE ? uniform_word(ap->allow_of, qi) : 0u) + (nb >> 5)];
     pf_node = c2;
     pf_nb = kNoNode;
     if (c2 != kNoNode && lane < (int)M0) pf_nb = load_here(adj0 + (size_t)c2 * M0 + lane);

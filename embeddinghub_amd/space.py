@@ -1249,6 +1249,58 @@ class Space:
                                                         int(n_masks), int(n_bits), _ptr(d_mask_of), int(route), _ptr(d_ids),
                                                         _ptr(d_dist), _ptr(d_count)))
 
+    # ---- the graph walk under per-query exclusion lists: the nearest rows a query has NOT seen, at the graph's rate ----
+    def graph_knn_except(self, queries, k, seen, seen_off=None, route=_lib.WALK_AUTO):
+        """knn_except's question answered by the graph walk (ehx_graph_knn_except): row i is graph_knn_masked_multi's answer
+        for query i alone under the complement bitmap of ITS list, with the same route — approximate where it walks.  seen /
+        seen_off as knn_except: unsorted, repeats and ids at or beyond len(self) allowed, at most EXCEPT_MAX_LIST entries
+        each.  k <= 256.  -> ids [nq,k] u64, dist [nq,k] f32, count [nq] u32."""
+        q, pq = _f32(queries)
+        q = q.reshape(-1, self.dims)
+        nq = q.shape[0]
+        ids_in, off_in = marshal_id_lists(seen, seen_off)
+        if off_in is None or off_in.shape[0] != nq + 1:
+            raise ValueError("expected %d per-query lists, got %s" % (nq, "one flat list" if off_in is None else off_in.shape[0] - 1))
+        (ids, dist, cnt), out = _results(nq, k)
+        u64p = C.POINTER(C.c_uint64)
+        check(self._L.ehx_graph_knn_except(self._h, nq, pq, k, ids_in.ctypes.data_as(u64p), off_in.ctypes.data_as(u64p),
+                                           ids_in.shape[0], int(route), *out))
+        return ids[:, :k], dist[:, :k], cnt
+
+    def graph_knn_except_keys(self, queries, k, seen_keys, route=_lib.WALK_AUTO):
+        """graph_knn_except with the lists given as stored keys (a list of key lists), as knn_except_keys takes them: a key
+        that is not stored is ignored."""
+        q, pq = _f32(queries)
+        q = q.reshape(-1, self.dims)
+        nq = q.shape[0]
+        lists = [list(ks) for ks in seen_keys]
+        if len(lists) != nq:
+            raise ValueError("expected %d per-query key lists, got %d" % (nq, len(lists)))
+        off = np.zeros(nq + 1, dtype=np.uint64)
+        if nq:
+            np.cumsum([len(ks) for ks in lists], out=off[1:])
+        n, arr, lens, keep = marshal_keys([key for ks in lists for key in ks])
+        (ids, dist, cnt), out = _results(nq, k)
+        rc = self._L.ehx_graph_knn_except_keys(self._h, nq, pq, k, arr, lens, off.ctypes.data_as(C.POINTER(C.c_uint64)), n,
+                                               int(route), *out)
+        del keep
+        check(rc)
+        return ids[:, :k], dist[:, :k], cnt
+
+    def graph_knn_except_device(self, d_queries, k, d_seen_ids, d_seen_off, d_ids, d_dist, d_count, route=_lib.WALK_AUTO,
+                                stream=None):
+        """graph_knn_except without queries, lists or results leaving the device: tensors as knn_except_device's.  The
+        offsets are read back and checked before the search starts."""
+        nq = d_queries.shape[0] if hasattr(d_queries, "shape") else None
+        n = d_seen_ids.shape[0] if hasattr(d_seen_ids, "shape") else None
+        if nq is None or n is None:
+            raise ValueError("pass torch tensors (queries [nq, dims], seen ids [n], offsets [nq + 1])")
+        if hasattr(d_seen_off, "numel") and d_seen_off.numel() != nq + 1:
+            raise ValueError("%d offsets for %d queries" % (d_seen_off.numel(), nq))
+        check(self._L.ehx_graph_knn_except_device(self._h, C.c_void_p(stream or 0), nq, _ptr(d_queries), k,
+                                                  _ptr(d_seen_ids) if n else None, _ptr(d_seen_off), n, int(route),
+                                                  _ptr(d_ids), _ptr(d_dist), _ptr(d_count)))
+
     # ---- range search (every row within a radius) ----
     def _range_args(self, queries, radius, max_results):
         q, pq = _f32(queries)

@@ -956,6 +956,38 @@ int ehx_knn_except(ehx_space* s, size_t n_queries, const float* queries, uint32_
 int ehx_knn_except_keys(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, const char* const* keys,
                         const size_t* klens, const uint64_t* key_off, size_t n_keys, uint64_t* out_ids, float* out_dist,
                         uint32_t* out_count);
+/* The GRAPH WALK under per-query exclusion lists: "the k nearest rows this user has not seen", approximate, at the graph's
+ * rate.  ehx_knn_except* stays exact on a graph space (every row's distance for every query); ehx_graph_knn_masked_multi*
+ * walks under at most 64 bitmaps a call, n / 8 bytes each.  Here every query brings its own list, and the walk keeps it
+ * sorted in LDS.
+ * Query i is answered as ehx_graph_knn_masked_multi_device answers query i ALONE with the same `route`, under a bitmap with
+ * n_bits = this call's ONE snapshot of the row count whose bit r is clear iff r occurs in query i's list — ids, distance
+ * bytes and count, byte for byte.  So: every node is a candidate and is walked through, only rows NOT in the list enter the
+ * results and set the bound, the walk's list is at most max(ef, min(EHX_WALK_LIST_FACTOR * ef, EHX_WALK_LIST_MAX)) long,
+ * ef = max(params.ef, k), and fewer than k rows may come back.  An empty list gives the plain strict walk's answer.
+ * The lists: ehx_knn_except's in form and rules — CSR (excl_ids, excl_off of n_queries + 1 entries ending at n_excl), at most
+ * EHX_EXCEPT_MAX_LIST entries per query, unsorted, repeats allowed, ids at or beyond the row count exclude nothing.
+ * route: EHX_WALK_GRAPH always walks; EHX_WALK_EXACT gives ehx_knn_except's answer; EHX_WALK_AUTO decides per query by the
+ * masked graph search's rule — walked iff (rows - distinct listed rows) * EHX_WALK_LIST_FACTOR >= rows, which a list of at
+ * most 4096 ids can miss only on a space of a few thousand rows.  A flat space has no graph: ehx_knn_except's answer.
+ * Outputs [n_queries][k], 1 <= k <= EHX_MAX_K_GROUPED, sentinels (id 2^64 - 1, +Inf) behind the count.
+ * Checked in this order: a NULL space: EHX_EINVAL "space is NULL"; no device: EHX_ENODEVICE; then ehx_knn_except's checks of
+ * k, the pointers and the offsets with their codes (a list longer than EHX_EXCEPT_MAX_LIST: EHX_EINVAL, pointing at
+ * ehx_graph_knn_masked_multi), a route that is none of the three: EHX_EINVAL; a row-sharded space, more than 2^30 rows,
+ * ef > 4096, a graph that does not cover the rows: EHX_EUNSUPPORTED; a dropped space: EHX_ENOTFOUND.  The device form reads
+ * the offsets back first (one small copy and a wait on `stream`). */
+int ehx_graph_knn_except_device(ehx_space* s, void* stream, size_t n_queries, const float* d_queries, uint32_t k,
+                                const uint64_t* d_excl_ids, const uint64_t* d_excl_off, size_t n_excl, uint32_t route,
+                                uint64_t* d_out_ids, float* d_out_dist, uint32_t* d_out_count);
+/* ... from host pointers: ehx_graph_knn_except_device plus the H2D / D2H copies, on the space's own stream. */
+int ehx_graph_knn_except(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, const uint64_t* excl_ids,
+                         const uint64_t* excl_off, size_t n_excl, uint32_t route, uint64_t* out_ids, float* out_dist,
+                         uint32_t* out_count);
+/* ... with the lists given as stored keys, as ehx_knn_except_keys takes them: resolved under the same hold of the space's
+ * lock as the search; a key that is NOT stored excludes nothing. */
+int ehx_graph_knn_except_keys(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, const char* const* keys,
+                              const size_t* klens, const uint64_t* key_off, size_t n_keys, uint32_t route, uint64_t* out_ids,
+                              float* out_dist, uint32_t* out_count);
 /* Boosted kNN: a ranking that MIXES the vector distance with a number stored beside the row — a recency decay, a popularity
  * or quality prior, a price distance, the item bias of a matrix-factorisation recommender (Elastic's function_score, Qdrant's
  * score boosting, a Vespa rank profile).  Over-fetching ehx_knn and re-scoring is inexact: a row at distance rank 5000 with
