@@ -141,6 +141,10 @@ SYMBOLS = {
                                        _u32p]),
     "ehx_graph_knn_except_keys": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t),
                                             _u64p, C.c_size_t, C.c_uint32, _u64p, _f32p, _u32p]),
+    "ehx_graph_knn_grouped_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint32, C.c_uint32, _vp, C.c_uint64, C.c_uint32,
+                                               _vp, _vp, _vp]),
+    "ehx_graph_knn_grouped": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_uint32, C.c_uint32, _u32p, C.c_uint64, C.c_uint32, _u64p,
+                                        _f32p, _u32p]),
     "ehx_knn_boosted_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint32, _vp, C.c_uint64, _vp, _vp, _vp, _vp]),
     "ehx_knn_boosted": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_uint32, _f32p, C.c_uint64, _f32p, _u64p, _f32p, _u32p]),
     "ehx_knn_decay_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp,

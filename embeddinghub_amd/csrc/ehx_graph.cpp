@@ -370,7 +370,7 @@ int graph_update(ehx_space* s, uint32_t id) {
 
 // graph pipeline: prepared queries -> zero visited bitmaps -> one-wave-per-query search
 // `mask` (optional, batch form only): the strict walk under a row bitmap, or under one per query (k_graphm.hip), or under an
-// exclusion list per query (k_graphx.hip) — the same
+// exclusion list per query (k_graphx.hip), or with a cap per group label (k_graphg.hip) — the same
 // arguments, the same wait, clock and refusals; its list is graph_walk_cap(ef) long and the visit log is sized from that.
 // `one` (optional): ONE query per call in ONE launch — the raw query sits in host-visible memory (one->q_host), the
 // kernel prepares it itself, writes ids / distances / count into host-visible memory (d_ids / d_dist / d_count then point
@@ -466,6 +466,8 @@ int knn_graph_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_que
     a.excl_cnt = mask->excl_cnt;
     a.excl_of = mask->excl_of;
     a.excl_lds = mask->excl_lds;
+    a.group_of = mask->group_of;
+    a.per_group = std::min(mask->per_group, ef_cap);   // (a list of ef_cap entries holds no more of a group)
   }
   if (one) {
     a.q_raw = one->q_host;
@@ -484,7 +486,10 @@ int knn_graph_locked(ehx_space* s, hipStream_t st, size_t nq, const float* d_que
   else if (!log_now)
     HIP_TRY(hipMemsetAsync(s->graph.dVisited.p, 0, (size_t)nq * vis_words * sizeof(uint32_t), st));
   s->vis_dirty = !log_now;
-  HIP_TRY(!mask ? launch_graph_search(a, st) : mask->excl ? launch_graph_search_except(a, st) : launch_graph_search_masked(a, st));
+  HIP_TRY(!mask             ? launch_graph_search(a, st)
+          : mask->per_group ? launch_graph_search_grouped(a, st)
+          : mask->excl      ? launch_graph_search_except(a, st)
+                            : launch_graph_search_masked(a, st));
   if ((rc = s->clock.scan_end(st)) || (rc = s->clock.finish(st))) return rc;
   s->n_queries += nq;
   return EHX_OK;

@@ -864,6 +864,10 @@ struct GraphMask {        // the walk under a row bitmap (k_graphm.hip): always 
   const uint32_t* excl_cnt = nullptr;
   const uint32_t* excl_of = nullptr;
   uint32_t excl_lds = 0;
+  // per_group != 0: the grouped walk (k_graphg.hip; allow and the lists unused, n_bits the labelled
+  // prefix min(row count, n_labels)) — device labels of that prefix, and the cap per label
+  const uint32_t* group_of = nullptr;
+  uint32_t per_group = 0;
 };
 // the walk list's length under a bitmap, a function of ef alone: max(ef, min(EHX_WALK_LIST_FACTOR * ef, EHX_WALK_LIST_MAX))
 inline uint32_t graph_walk_cap(uint32_t ef) {

@@ -978,6 +978,11 @@ struct GraphArgs {
   const uint32_t* excl_cnt = nullptr;
   const uint32_t* excl_of = nullptr;
   uint32_t excl_lds = 0;
+  // The GROUPED walk (k_graphg.hip; launch_graph_search_grouped only): row r is labelled iff r < allow_bits, its label is
+  // group_of[r] (kGroupNone: a group of its own), and at most per_group (1 .. ef_cap) rows of a label are returned and
+  // counted toward ef.  allow and the lists are unused.
+  const uint32_t* group_of = nullptr;
+  uint32_t per_group = 0;
 };
 size_t graph_lds_bytes(uint32_t ld, uint32_t ef_cap, uint32_t width = 1);
 hipError_t launch_graph_search(const GraphArgs& a, hipStream_t st);
@@ -986,6 +991,9 @@ hipError_t launch_graph_search(const GraphArgs& a, hipStream_t st);
 hipError_t launch_graph_search_masked(const GraphArgs& a, hipStream_t st);
 // the same walk with a.excl, a sorted exclusion list per query held in LDS, in the bitmap's place
 hipError_t launch_graph_search_except(const GraphArgs& a, hipStream_t st);
+// the walk with a cap per group label: a.group_of and a.per_group, label and eligibility of every list slot held in LDS
+hipError_t launch_graph_search_grouped(const GraphArgs& a, hipStream_t st);
+size_t graph_grouped_lds_bytes(uint32_t ld, uint32_t ef_cap);   // its dynamic LDS
 
 // graph-mode insertion (k_insert.hip)
 // hipFuncAttributeMaxDynamicSharedMemorySize is set per function AND per device (every device has its own loaded code

@@ -193,17 +193,27 @@ __device__ __forceinline__ uint32_t rank_by_counting(const uint64_t* batch, uint
 // slots, so per 64 slots that number is one ballot + a lane-prefix popcount — no per-entry search.  Top down: a chunk
 // reads only slots at or below its own, which are still untouched.  Only [first insertion point, nR) is touched.
 // PROF_POINTS / PROF_MOVED: the caller's profile slots for "insertion points found" and "R moved".
-template <int PROF_POINTS, int PROF_MOVED>
+// Payload (k_graphg.hip): every slot of R carries a 32-bit tag (pay.tag[ef], the lane's fresh one in pay.mine, sorted through
+// pay.stage[64]) and one flag, bit 1 of the slot's byte of F — bit 0 stays the landing mark, so the flag of an old entry
+// survives a fresh key landing on its slot until the entry has moved up; a fresh key's flag is pay.first(key, tag).  Tag and
+// flag move with their key.  NoPayload: none of that text exists, the merge is the one the other walks have always had.
+struct NoPayload {
+  static constexpr bool kHas = false;
+};
+template <int PROF_POINTS, int PROF_MOVED, class Payload = NoPayload>
 __device__ __forceinline__ void merge_sorted_into_R(const GraphLds& L, uint32_t ef, uint64_t mykey, bool has, uint32_t rank,
                                                     uint32_t n, uint32_t& nR, uint32_t& scan_from, int lane,
-                                                    GraphProf& prof) {
+                                                    GraphProf& prof, const Payload pay = Payload()) {
   uint64_t* R = L.R;
   if (has) L.S[rank] = mykey;
+  if constexpr (Payload::kHas)
+    if (has) pay.stage[rank] = pay.mine;
   wave_lds_sync();
   uint64_t skey = kKeyInf;
-  uint32_t ps = kNoNode;
+  uint32_t ps = kNoNode, stag = 0;
   if ((uint32_t)lane < n) {
     skey = L.S[lane];  // the lane-th smallest fresh key
+    if constexpr (Payload::kHas) stag = pay.stage[lane];
     ps = lower_bound_lds(R, nR, skey);
   }
   // insertion point of the smallest fresh key (lane 0).  readfirstlane, not a shuffle: the value is wave-uniform
@@ -214,27 +224,52 @@ __device__ __forceinline__ void merge_sorted_into_R(const GraphLds& L, uint32_t 
     const uint32_t new_nR = nR + n < ef ? nR + n : ef;
     const uint32_t fpos = ps + (uint32_t)lane;
     const bool lands = (uint32_t)lane < n && fpos < ef;
-    if (lands) L.F[fpos] = 1;
+    if constexpr (Payload::kHas) {
+      if (lands) L.F[fpos] |= 1;
+    } else {
+      if (lands) L.F[fpos] = 1;
+    }
     wave_lds_sync();
     for (uint32_t dhi = new_nR; dhi > p0;) {
       const uint32_t dlo = dhi - p0 > 64 ? dhi - 64 : p0;
       const uint32_t dpos = dlo + (uint32_t)lane;
       const bool in = dpos < dhi;
-      const bool taken = in && L.F[dpos] != 0;
+      bool taken;
+      if constexpr (Payload::kHas) taken = in && (L.F[dpos] & 1) != 0;
+      else taken = in && L.F[dpos] != 0;
       const uint64_t occ = __ballot(taken);
       const uint32_t below = (uint32_t)__builtin_popcountll(__ballot(lands && fpos < dlo));
       const uint32_t cnt = below + (uint32_t)__builtin_popcountll(occ & ((1ull << lane) - 1ull));
       const bool mv = in && !taken;
       uint64_t kj = 0;
+      uint32_t tj = 0;
+      uint8_t fj = 0;
       if (mv) kj = R[dpos - cnt];
+      if constexpr (Payload::kHas) {
+        if (mv) {
+          tj = pay.tag[dpos - cnt];
+          fj = L.F[dpos - cnt] & 2;
+        }
+      }
       wave_lds_sync();
       if (mv) R[dpos] = kj;
+      if constexpr (Payload::kHas) {
+        if (mv) {
+          pay.tag[dpos] = tj;
+          L.F[dpos] = fj;
+        }
+      }
       wave_lds_sync();
       dhi = dlo;
     }
     if (lands) {
       R[fpos] = skey;
-      L.F[fpos] = 0;
+      if constexpr (Payload::kHas) {
+        pay.tag[fpos] = stag;
+        L.F[fpos] = pay.first(skey, stag);
+      } else {
+        L.F[fpos] = 0;
+      }
     }
     wave_lds_sync();
     nR = new_nR;

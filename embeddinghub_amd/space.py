@@ -1301,6 +1301,36 @@ class Space:
                                                   _ptr(d_seen_ids) if n else None, _ptr(d_seen_off), n, int(route),
                                                   _ptr(d_ids), _ptr(d_dist), _ptr(d_count)))
 
+    # ---- the graph walk with a cap per group label: the nearest documents, at most per_group chunks each ----
+    def graph_knn_grouped(self, queries, k, per_group, group_of, route=_lib.WALK_AUTO):
+        """knn_grouped's question answered by the graph walk (ehx_graph_knn_grouped): the walk's list is cut at its ef-th
+        ELIGIBLE entry and its first k eligible entries come back — approximate where it walks.  group_of as knn_grouped's
+        (one label per row, -1 is GROUP_NONE); rows at or above len(group_of) are walked through and never returned.
+        WALK_EXACT, and a flat space, give knn_grouped's answer.  k <= 256.  -> ids [nq,k] u64, dist [nq,k] f32,
+        count [nq] u32."""
+        q, pq = _f32(queries)
+        q = q.reshape(-1, self.dims)
+        nq = q.shape[0]
+        labels, n_labels = marshal_groups(group_of)
+        (ids, dist, cnt), out = _results(nq, k)
+        check(self._L.ehx_graph_knn_grouped(self._h, nq, pq, k, int(per_group),
+                                            labels.ctypes.data_as(C.POINTER(C.c_uint32)) if n_labels else None, n_labels,
+                                            int(route), *out))
+        return ids[:, :k], dist[:, :k], cnt
+
+    def graph_knn_grouped_device(self, d_queries, k, per_group, d_group_of, n_labels, d_ids, d_dist, d_count,
+                                 route=_lib.WALK_AUTO, stream=None):
+        """graph_knn_grouped without anything leaving the device: tensors as knn_grouped_device's (a stored column: what
+        column_read_device filled).  The walked route does not wait for the device."""
+        nq = d_queries.shape[0] if hasattr(d_queries, "shape") else None
+        if nq is None:
+            raise ValueError("pass torch tensors (queries [nq, dims], group labels)")
+        if hasattr(d_group_of, "numel") and d_group_of.numel() < int(n_labels):
+            raise ValueError("%d group labels are fewer than n_labels = %d" % (d_group_of.numel(), n_labels))
+        check(self._L.ehx_graph_knn_grouped_device(self._h, C.c_void_p(stream or 0), nq, _ptr(d_queries), k, int(per_group),
+                                                   _ptr(d_group_of) if int(n_labels) else None, int(n_labels), int(route),
+                                                   _ptr(d_ids), _ptr(d_dist), _ptr(d_count)))
+
     # ---- range search (every row within a radius) ----
     def _range_args(self, queries, radius, max_results):
         q, pq = _f32(queries)

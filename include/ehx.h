@@ -551,10 +551,12 @@ int ehx_graph_knn_masked_multi_device(ehx_space* s, void* stream, size_t n_queri
  * EHX_EUNSUPPORTED; a dropped space: EHX_ENOTFOUND.  n_labels == 0: count 0 for every query; n_queries == 0: EHX_OK.
  * Served by the falling-radius scan of the int8 filter where ehx_knn_device's large-k route would serve the prefix (flat
  * spaces whose first engine is the int8 filter, at least 64 queries; any k here) with a cap per label in its exact re-rank;
- * everything else — graph spaces (from their stored rows: the graph is not walked), small spaces, EHX_SCAN_F32 / _F16, small
+ * everything else — graph spaces (from their stored rows: THIS call does not walk the graph; ehx_graph_knn_grouped_device
+ * does), small spaces, EHX_SCAN_F32 / _F16, small
  * batches, and the queries that scan hands on — by an exact pass over every prefix row in slabs of 4096, which costs what
  * the exhaustive pass costs plus a sort per slab.  A Set that rewrites rows in place waits for the call like for any
- * search.  Under row bitmaps: ehx_knn_grouped_masked_device; not on the graph walk.  DESIGN.md §e.19. */
+ * search.  Under row bitmaps: ehx_knn_grouped_masked_device; on the graph walk, approximate: ehx_graph_knn_grouped_device.
+ * DESIGN.md §e.19. */
 #define EHX_GROUP_NONE 0xFFFFFFFFu
 #define EHX_MAX_K_GROUPED 256u
 int ehx_knn_grouped_device(ehx_space* s, void* stream, size_t n_queries, const float* d_queries, uint32_t k,
@@ -988,6 +990,38 @@ int ehx_graph_knn_except(ehx_space* s, size_t n_queries, const float* queries, u
 int ehx_graph_knn_except_keys(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, const char* const* keys,
                               const size_t* klens, const uint64_t* key_off, size_t n_keys, uint32_t route, uint64_t* out_ids,
                               float* out_dist, uint32_t* out_count);
+/* The GRAPH WALK with a cap per group label: "the k nearest documents, at most per_group chunks each", approximate, at the
+ * graph's rate.  ehx_knn_grouped* stays exact on a graph space (every prefix row's distance for every query); here the walk
+ * itself carries the cap, as it carries a bitmap or an exclusion list.  Labels as ehx_knn_grouped_device's: d_group_of[r]
+ * for r < n_eff = min(this call's ONE snapshot of the row count, n_labels), EHX_GROUP_NONE a group of its own.
+ * The walk is ehx_graph_knn_masked_device's with "allowed" replaced by ELIGIBLE, a fact about the walk's list R and not
+ * about a row alone.  A row r is LABELLED iff r < n_eff; other rows are walked through and never returned, never eligible,
+ * and count toward no cap.  An entry of R is eligible iff its row is labelled and its label is EHX_GROUP_NONE or fewer than
+ * per_group labelled entries of R with the same label lie in front of it in (distance, id) order.  After every merge of
+ * fresh neighbours (NaN distances dropped) eligibility is evaluated anew — a closer row of a group makes a farther one
+ * ineligible —, then R is cut behind its ef-th eligible entry if it has one, then behind position
+ * max(ef, min(EHX_WALK_LIST_FACTOR * ef, EHX_WALK_LIST_MAX)).  The answer is the first k eligible entries of R, never the NaN
+ * seed; fewer than k may come back.  ef = max(params.ef, k); params.search_width is ignored (one node per step).
+ * So, byte for byte: with every label EHX_GROUP_NONE, or per_group at least the largest group, and n_labels at least the
+ * row count, the answer is ehx_knn_device's strict walk; with ef at least the row count on a connected graph (R is never
+ * cut), it is ehx_knn_grouped_device's exact answer.
+ * route: EHX_WALK_GRAPH walks; EHX_WALK_EXACT, and any valid route on a flat space, give ehx_knn_grouped_device's answer;
+ * EHX_WALK_AUTO walks on a graph space — there is no selectivity to decide on: a cap thins the list by the groups' sizes
+ * near the query, which no count known before the walk tells.
+ * Outputs [n_queries][k], sentinels (id 2^64 - 1, +Inf) behind the count.  Checked in this order: a NULL space: EHX_EINVAL
+ * "space is NULL"; no device: EHX_ENODEVICE; k == 0, per_group == 0: EHX_EINVAL; k > EHX_MAX_K_GROUPED: EHX_EUNSUPPORTED;
+ * NULL outputs, NULL queries with n_queries > 0, NULL d_group_of with n_labels > 0, a route that is none of the three:
+ * EHX_EINVAL; a row-sharded space, more than 2^30 rows, ef > 4096, a graph that does not cover the rows: EHX_EUNSUPPORTED;
+ * a dropped space: EHX_ENOTFOUND.  n_labels == 0: count 0 for every query; n_queries == 0: EHX_OK.  The walked route does
+ * not wait for the device.  Counted in ehx_stats (queries) and ehx_graph_counters (rows fetched, expansions).
+ * DESIGN.md §e.35. */
+int ehx_graph_knn_grouped_device(ehx_space* s, void* stream, size_t n_queries, const float* d_queries, uint32_t k,
+                                 uint32_t per_group, const uint32_t* d_group_of, uint64_t n_labels, uint32_t route,
+                                 uint64_t* d_out_ids, float* d_out_dist, uint32_t* d_out_count);
+/* ... from host pointers: ehx_graph_knn_grouped_device plus the H2D / D2H copies, on the space's own stream. */
+int ehx_graph_knn_grouped(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, uint32_t per_group,
+                          const uint32_t* group_of, uint64_t n_labels, uint32_t route, uint64_t* out_ids, float* out_dist,
+                          uint32_t* out_count);
 /* Boosted kNN: a ranking that MIXES the vector distance with a number stored beside the row — a recency decay, a popularity
  * or quality prior, a price distance, the item bias of a matrix-factorisation recommender (Elastic's function_score, Qdrant's
  * score boosting, a Vespa rank profile).  Over-fetching ehx_knn and re-scoring is inexact: a row at distance rank 5000 with
