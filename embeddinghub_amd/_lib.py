@@ -25,6 +25,7 @@ EXCEPT_MAX_LIST = 4096                          # EHX_EXCEPT_MAX_LIST: entries o
 PROFILE_MAX_LIST = 4096                         # EHX_PROFILE_MAX_LIST: entries of one query's profile (rows and weights)
 MAXSIM_MAX_TOKENS, MAXSIM_MAX_CAND = 32, 1024   # EHX_MAXSIM_MAX_TOKENS, EHX_MAXSIM_MAX_CAND
 MAX_COLUMNS = 4                                 # EHX_MAX_COLUMNS: stored label columns of a space
+MAX_WANT = 64                                   # EHX_MAX_WANT: labels per query of knn_by_labels
 PRED_MAX_TERMS, TERM_NOT = 8, 1                 # EHX_PRED_MAX_TERMS, EHX_TERM_NOT: predicates over stored columns
 TERM_IN, FILTER_MAX_CLAUSES, FILTER_MAX_VALUES = 2, 128, 4096   # EHX_TERM_IN, EHX_FILTER_MAX_*: Boolean filters over them
 SEED_CORPUS, SEED_QUERY = 20250211, 20250212
@@ -185,6 +186,8 @@ SYMBOLS = {
     "ehx_column_read_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint64, C.c_uint64, _vp]),
     "ehx_knn_by_label": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_uint32, C.c_uint32, _u32p, _u64p, _f32p, _u32p]),
     "ehx_knn_by_label_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp]),
+    "ehx_knn_by_labels": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _u32p, _u64p, _f32p, _u32p]),
+    "ehx_knn_by_labels_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
     "ehx_knn_grouped_by_label": (C.c_int, [_vp, C.c_size_t, _f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _u64p,
                                            _f32p, _u32p]),
     "ehx_knn_grouped_by_label_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp,

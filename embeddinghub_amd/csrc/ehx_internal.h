@@ -541,6 +541,22 @@ struct ehx_space {
   // test hook (scripts/bench_labeled.py's crossover sweep): 0 the cut decides; 1 every non-empty label takes the scan route
   // where the int8 scan serves (a batch may then name at most 127 of them); 2 every label takes the list route
   std::atomic<uint32_t> labeled_route{0};
+  // exact kNN under a set of stored labels per query (ehx_probe.cpp; scratch_mu): the work list of a device batch on the
+  // device and the pinned blocks it is planned in — two, taken in turn: up_ev[i] says that the copy out of block i has run,
+  // which is all the next plan but one waits for — and a host call's staged queries and results.  The prepared queries, the
+  // key lists, the merged keys and the page floor are the exhaustive pass's (scr.dQ / dPart / dMerged / dGthr), fenced by
+  // the space's clock.
+  struct Probe {
+    DevBuf<ProbeItem> dItems;
+    PinBuf<ProbeItem> hItems[2];
+    Event up_ev[2];
+    bool up_pending[2] = {false, false};
+    uint32_t turn = 0;
+    std::vector<uint32_t> head;  // [labels of the index + 1] the counting sort's cursors, all zero between plans
+    HostStage host;
+  } probe;
+  // test hook: calls, work items launched, rows staged, (row, query) pairs evaluated
+  std::atomic<uint64_t> probe_ctr[4] = {};
   // exact range search under row bitmaps (ehx_rangem.cpp; scratch_mu): the compaction is the bitmap search's (masked), the
   // pools, control words and slot queries the range search's (range.dPool / dCtl / dSel); its own are the scan route's radii
   // (NaN for the queries of a device batch the scan does not answer), every list-route slot's list, the sub-batch of the
@@ -798,6 +814,7 @@ struct ehx_space {
     among = {};
     range = {};
     masked = {};
+    probe = {};
     largek = {};
     grouped = {};
     except = {};
@@ -1310,6 +1327,9 @@ struct LabelCall {
 // staged, d_want read back; then per device batch [q0, q0 + m) the plan, its view (ctr set) and batch(q0, m, view).
 int labeled_call(ehx_space* s, hipStream_t st, uint64_t n_pub, size_t nq, const LabelCall& c, const std::function<int()>& stage,
                  const std::function<int(size_t, size_t, FilterView&)>& batch);
+// what ehx_knn_by_label* and ehx_knn_by_labels* (ehx_probe.cpp) decide first, with their codes and in this order
+int by_label_check(const ehx_space* s, size_t nq, uint32_t k, const void* q, uint32_t label_col, const void* want,
+                   const void* o_ids, const void* o_dist, const void* o_cnt);
 
 // ---- ehx_columns.cpp ----
 struct WriteBatch;

@@ -481,6 +481,33 @@ hipError_t launch_among(const AmongArgs& a, hipStream_t st);
 hipError_t launch_among_emit(const uint64_t* merged, uint32_t nq, uint32_t k, uint32_t out_stride, uint32_t out_offset,
                              uint64_t* out_ids, float* out_dist, uint32_t* out_count, hipStream_t st);
 
+// exact kNN under a SET of stored labels per query (k_probe.hip): the list-major scan.  The batch's (query, want-slot) pairs
+// are grouped by the label they name; a work item is one workgroup that walks a range of the column index's permutation
+// (one label's list, or one chunk of a long one), stages every row ONCE and applies it to the item's up to 8 pairs.
+constexpr uint32_t kProbeTilePairs = 8;   // pairs per work item: among_tile_kernel's tile, a (row, pair) per 4-lane group
+constexpr uint32_t kProbeChunk = 4096;    // rows of a list one work item walks at most while the launch has chunks to
+                                          // spare (kProbeMaxChunks): a choice, not measured
+constexpr uint32_t kProbeMaxChunks = 16;  // key lists a (query, want-slot) pair may leave for the merge
+struct ProbeItem {
+  uint32_t lo, hi;                   // the rows perm[lo, hi)
+  uint32_t n_pairs, chunk;           // pairs in use; which of the pair's key lists this item writes
+  uint32_t q[kProbeTilePairs];       // the pair's query (of the device batch) ...
+  uint32_t slot[kProbeTilePairs];    // ... and its slot in the query's set
+};
+struct ProbeArgs {
+  const float* Q;            // prepared queries [nq][ld] (launch_prep_queries)
+  RowsView rows;             // stored rows, any layout
+  const uint64_t* perm;      // [n_perm] row ids by (label, row id): ColIndex::dPerm; an id at or above rows.n_rows is ignored
+  const ProbeItem* items;    // [n_items]
+  const uint64_t* floor;     // optional, per QUERY: only keys strictly above floor[q] are kept (paging for k > 64)
+  uint64_t* out;             // [nq][n_want * n_chunks][64]; the blocks no item names keep what the caller filled them with
+  uint64_t n_perm;
+  uint32_t n_items, nq, n_want, n_chunks;
+};
+uint32_t probe_max_ld();     // longest row stride (floats): 8 prepared queries, 8 staged rows and the key area share the LDS
+hipError_t launch_probe(const ProbeArgs& a, hipStream_t st);
+hipError_t launch_probe_fill(uint64_t* out, size_t n_keys, hipStream_t st);   // kKeyInf into out[0, n_keys)
+
 // MMR re-ranking of candidate lists (k_mmr.hip): per query, from the first min(cand_count[q], fetch_k) entries of its list,
 // greedily the k least by lambda * dq - (1 - lambda) * (distance to the nearest pick so far); include/ehx.h has the contract
 constexpr uint32_t kMmrMaxFetch = 256;   // candidates per query: one thread of the workgroup each

@@ -46,18 +46,18 @@ int labeled_check(const ehx_space* s, size_t nq, uint32_t k, const void* q, cons
   return EHX_OK;
 }
 
-// ehx_knn_by_label*: ehx_knn_labeled*'s checks with their codes and in their order (the column is the space's: no pointer,
-// no length), then the column number
+}  // namespace
+
+namespace ehx_impl {
+
+// ehx_knn_by_label* (and ehx_knn_by_labels*, ehx_probe.cpp): ehx_knn_labeled*'s checks with their codes and in their order
+// (the column is the space's: no pointer, no length), then the column number
 int by_label_check(const ehx_space* s, size_t nq, uint32_t k, const void* q, uint32_t label_col, const void* want,
                    const void* o_ids, const void* o_dist, const void* o_cnt) {
   if (int rc = labeled_check(s, nq, k, q, nullptr, 0, want, o_ids, o_dist, o_cnt)) return rc;
   if (label_col >= EHX_MAX_COLUMNS) return fail(EHX_EINVAL, "label_col = %u: a space has %u columns", label_col, (unsigned)EHX_MAX_COLUMNS);
   return EHX_OK;
 }
-
-}  // namespace
-
-namespace ehx_impl {
 
 // the scratch labeled_plan fills, sized for a prefix of n_eff rows (once per call, before anything is enqueued)
 static int labeled_plan_scratch(ehx_space* s, uint64_t n_eff) {

@@ -18,8 +18,6 @@ namespace ehx {
 
 namespace {
 
-typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
-
 constexpr uint32_t kLdsPad = 4;   // floats behind every LDS row: the 8 rows a 32-lane group reads fall into 32 banks
 
 }  // namespace
@@ -114,43 +112,8 @@ __global__ __launch_bounds__(256) void among_tile_kernel(const AmongArgs a) {
         row_id[sr] = (uint32_t)id;
         row_ok[sr] = ok ? 1u : 0u;
       }
-      if (ok) {   // (a row that is not staged leaves stale floats behind: its pairs' keys are dropped)
-        const float inv = scale ? a.rows.inv_norm[id] : 1.0f;
-        float4* dst = (float4*)xs + sr * lds4;
-        if (LAYOUT == kLayoutF16) {
-          const half8_t* x = (const half8_t*)((const _Float16*)a.rows.X + (size_t)id * a.rows.ld);
-          for (uint32_t c = sl; c < (a.rows.dims + 7u) >> 3; c += 32) {
-            const half8_t h = x[c];
-            float4 v0 = make_float4((float)h[0], (float)h[1], (float)h[2], (float)h[3]);
-            float4 v1 = make_float4((float)h[4], (float)h[5], (float)h[6], (float)h[7]);
-            if (scale) {
-              v0 = scale_f4(v0, inv);
-              v1 = scale_f4(v1, inv);
-            }
-            dst[2 * c] = v0;
-            dst[2 * c + 1] = v1;
-          }
-        } else if (LAYOUT == kLayoutPerm) {
-          // a 16-float block of the search copy's order: four 16-byte loads, the 4 x 4 transpose undone (search_copy_pos)
-          const float4* x = (const float4*)((const float*)a.rows.X + (size_t)id * a.rows.ld);
-          for (uint32_t b = sl; b < (a.rows.dims + 15u) >> 4; b += 32) {
-            float4 v0 = x[4 * b], v1 = x[4 * b + 1], v2 = x[4 * b + 2], v3 = x[4 * b + 3];
-            if (scale) {
-              v0 = scale_f4(v0, inv);
-              v1 = scale_f4(v1, inv);
-              v2 = scale_f4(v2, inv);
-              v3 = scale_f4(v3, inv);
-            }
-            dst[4 * b] = make_float4(v0.x, v1.x, v2.x, v3.x);
-            dst[4 * b + 1] = make_float4(v0.y, v1.y, v2.y, v3.y);
-            dst[4 * b + 2] = make_float4(v0.z, v1.z, v2.z, v3.z);
-            dst[4 * b + 3] = make_float4(v0.w, v1.w, v2.w, v3.w);
-          }
-        } else {
-          const float4* x = (const float4*)((const float*)a.rows.X + (size_t)id * a.rows.ld);
-          for (uint32_t c = sl; c < (a.rows.dims + 3u) >> 2; c += 32) dst[c] = scale ? scale_f4(x[c], inv) : x[c];
-        }
-      }
+      // (a row that is not staged leaves stale floats behind: its pairs' keys are dropped)
+      if (ok) stage_row_lds<LAYOUT, scale>((float4*)xs + sr * lds4, a.rows, id, sl, 32);
       __syncthreads();
       const float d = canon_dist(metric01, qs + (size_t)pq * lds, xs + (size_t)pr * lds, 1.0f, false, a.rows.dims, sub);
       if (sub == 0) keys[pq * 64 + st * R + pr] = dist_key_paged(d, row_id[pr], row_ok[pr] != 0 && pq < nqt, paged, fl);

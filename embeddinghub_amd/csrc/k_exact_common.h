@@ -36,6 +36,49 @@ __device__ __forceinline__ void stage_query_lds(float* qs, const float* __restri
   for (uint32_t m = tid; m < ld; m += nthreads) qs[LAYOUT == kLayoutPerm ? search_copy_pos(m) : m] = qv[m];
 }
 
+// Stored row `id` into LDS as a plain fp32 row, whatever the stored layout, by the nl lanes sl = 0 .. nl - 1 with 16-byte
+// loads: binary16 widened exactly, the search copy's block permutation undone (search_copy_pos), and with SCALE every
+// element times inv_norm[id] — one rounding per element, hnswlib-python's stored normalised row.  What the kernels that
+// apply one staged row to several queries read with canon_dist (k_among.hip's tile kernel, k_probe.hip).
+template <int LAYOUT, bool SCALE>
+__device__ __forceinline__ void stage_row_lds(float4* dst, const RowsView& v, uint64_t id, uint32_t sl, uint32_t nl) {
+  typedef _Float16 half8 __attribute__((ext_vector_type(8)));
+  const float inv = SCALE ? v.inv_norm[id] : 1.0f;
+  if (LAYOUT == kLayoutF16) {
+    const half8* x = (const half8*)((const _Float16*)v.X + (size_t)id * v.ld);
+    for (uint32_t c = sl; c < (v.dims + 7u) >> 3; c += nl) {
+      const half8 h = x[c];
+      float4 v0 = make_float4((float)h[0], (float)h[1], (float)h[2], (float)h[3]);
+      float4 v1 = make_float4((float)h[4], (float)h[5], (float)h[6], (float)h[7]);
+      if (SCALE) {
+        v0 = scale_f4(v0, inv);
+        v1 = scale_f4(v1, inv);
+      }
+      dst[2 * c] = v0;
+      dst[2 * c + 1] = v1;
+    }
+  } else if (LAYOUT == kLayoutPerm) {
+    // a 16-float block of the search copy's order: four 16-byte loads, the 4 x 4 transpose undone
+    const float4* x = (const float4*)((const float*)v.X + (size_t)id * v.ld);
+    for (uint32_t b = sl; b < (v.dims + 15u) >> 4; b += nl) {
+      float4 v0 = x[4 * b], v1 = x[4 * b + 1], v2 = x[4 * b + 2], v3 = x[4 * b + 3];
+      if (SCALE) {
+        v0 = scale_f4(v0, inv);
+        v1 = scale_f4(v1, inv);
+        v2 = scale_f4(v2, inv);
+        v3 = scale_f4(v3, inv);
+      }
+      dst[4 * b] = make_float4(v0.x, v1.x, v2.x, v3.x);
+      dst[4 * b + 1] = make_float4(v0.y, v1.y, v2.y, v3.y);
+      dst[4 * b + 2] = make_float4(v0.z, v1.z, v2.z, v3.z);
+      dst[4 * b + 3] = make_float4(v0.w, v1.w, v2.w, v3.w);
+    }
+  } else {
+    const float4* x = (const float4*)((const float*)v.X + (size_t)id * v.ld);
+    for (uint32_t c = sl; c < (v.dims + 3u) >> 2; c += nl) dst[c] = SCALE ? scale_f4(x[c], inv) : x[c];
+  }
+}
+
 // ---- the row walk ----
 // LANE: one lane per row where the layout has such a walk (fp32 rows: canon_dist_lane_t, 16-byte loads through its register
 // ring); otherwise, and always with !LANE, a 4-lane group per row (fp32 / binary16: canon_dist; block-permuted:

@@ -979,6 +979,42 @@ class Space:
         check(self._L.ehx_knn_by_label_device(self._h, C.c_void_p(stream or 0), nq, _ptr(d_queries), k, int(label_col),
                                               _ptr(d_want), _ptr(d_ids), _ptr(d_dist), _ptr(d_count)))
 
+    def knn_by_labels(self, queries, k, label_col, want, want_count=None):
+        """kNN under a SET of stored labels per query (ehx_knn_by_labels): want is [nq, n_want] u32, query i sees the rows
+        whose stored label is among the first want_count[i] entries of its row (None: all n_want).  A repeated label counts
+        once, a label no row carries contributes nothing, want_count[i] == 0 gives count 0.  With the labels of
+        kmeans_device as the column and every query's nearest centroids as its set this is an IVF probe.
+        -> ids [nq,k] u64, dist [nq,k] f32, count [nq] u32."""
+        q, pq = _f32(queries)
+        q = q.reshape(-1, self.dims)
+        nq = q.shape[0]
+        w = np.ascontiguousarray(np.asarray(want), dtype=np.uint32)
+        if w.ndim != 2 or w.shape[0] != nq:
+            raise ValueError("expected wanted labels of shape [%d, n_want], got %s" % (nq, (w.shape,)))
+        wc = None
+        if want_count is not None:
+            wc = np.ascontiguousarray(np.asarray(want_count).reshape(-1), dtype=np.uint32)
+            if wc.shape[0] != nq:
+                raise ValueError("expected %d counts, got %d" % (nq, wc.shape[0]))
+        (ids, dist, cnt), out = _results(nq, k)
+        u32p = C.POINTER(C.c_uint32)
+        check(self._L.ehx_knn_by_labels(self._h, nq, pq, k, int(label_col), w.shape[1], w.ctypes.data_as(u32p),
+                                        wc.ctypes.data_as(u32p) if wc is not None else None, *out))
+        return ids[:, :k], dist[:, :k], cnt
+
+    def knn_by_labels_device(self, d_queries, k, label_col, d_want, d_ids, d_dist, d_count, d_want_count=None, stream=None):
+        """knn_by_labels without anything leaving the device: torch CUDA tensors — d_queries [nq, dims] f32, d_want
+        [nq, n_want] u32 (int32 storage, contiguous), d_want_count [nq] u32 or None, outputs as knn_device's."""
+        nq = d_queries.shape[0] if hasattr(d_queries, "shape") else None
+        if nq is None or not hasattr(d_want, "shape") or len(d_want.shape) != 2 or d_want.shape[0] != nq:
+            raise ValueError("pass torch tensors (queries [nq, dims], wanted labels [nq, n_want])")
+        if d_want_count is not None and d_want_count.numel() < nq:
+            raise ValueError("%d counts for %d queries" % (d_want_count.numel(), nq))
+        check(self._L.ehx_knn_by_labels_device(self._h, C.c_void_p(stream or 0), nq, _ptr(d_queries), k, int(label_col),
+                                               int(d_want.shape[1]), _ptr(d_want),
+                                               _ptr(d_want_count) if d_want_count is not None else None, _ptr(d_ids),
+                                               _ptr(d_dist), _ptr(d_count)))
+
     def knn_grouped_by_label(self, queries, k, group_col, label_col, want, per_group=1):
         """knn_grouped_labeled on STORED columns (ehx_knn_grouped_by_label): group_col holds every row's group (GROUP_NONE: a
         group of its own, also every row never given one), label_col its tenant.

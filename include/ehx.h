@@ -692,6 +692,34 @@ int ehx_knn_by_label_device(ehx_space* s, void* stream, size_t n_queries, const 
 /* ... from host pointers: the H2D / D2H copies of queries, wanted labels and results around it. */
 int ehx_knn_by_label(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, uint32_t label_col, const uint32_t* want,
                      uint64_t* out_ids, float* out_dist, uint32_t* out_count);
+/* Multi-probe label search: kNN under a per-query SET of stored labels — "the k nearest rows among the lists of this
+ * query's n_probe nearest centroids" (an IVF search over the library's own k-means labels), or "rows whose group is one of
+ * the groups this user belongs to".  d_want is [n_queries][n_want]; query i names the first min(d_want_count[i], n_want)
+ * entries of its row (d_want_count == NULL: n_want each).  The call takes ONE acquire-load snapshot n_pub of the row count;
+ * row r is allowed for query i iff r < n_pub and the stored column's value at r is among those entries.  Row i of the answer
+ * is, byte for byte, what ehx_knn_masked_device returns for query i alone under the bitmap of its allowed rows: (canonical
+ * distance, id) order, the NaN rule, +-Inf and cosine normalisation, F16 rows as stored, counts, and the sentinels (id ~0,
+ * +Inf) behind the count.  No label value is special (0xFFFFFFFF: the rows never labelled); a label repeated inside a set
+ * counts once; a label no row carries contributes nothing; a count of 0 gives count 0 for that query only.  With
+ * n_want == 1 the call equals ehx_knn_by_label_device byte for byte.  Every space kind ehx_knn_by_label serves is served (a
+ * graph space answers from its stored rows).  1 <= k <= EHX_MAX_K_PAGED, served in pages of 64.
+ * Errors: ehx_knn_by_label_device's, with their codes in their order; then n_want == 0 or n_want > EHX_MAX_WANT: EHX_EINVAL;
+ * a row-sharded space: EHX_EUNSUPPORTED; rows longer than 2464 floats (8 prepared queries and 8 staged rows share the 160 KB
+ * of LDS of a compute unit with 4 KB of keys): EHX_EUNSUPPORTED.
+ * Always the LIST route, list-major: the batch's (query, label) pairs are grouped by label on the host against the column
+ * index's mirror (the index is ehx_knn_by_label's, rebuilt by the call if stale), and a label's rows go through the memory
+ * system once per 8 pairs that name it, not once per pair.  A very large label is served correctly, but not at the int8
+ * scan's rate — ehx_knn_by_label routes such labels to the scan, this call does not.  The device form waits once, for
+ * d_want and d_want_count (the outputs unwritten until then); the host form plans from the caller's arrays where they lie.
+ * DESIGN.md §e.36. */
+#define EHX_MAX_WANT 64u
+int ehx_knn_by_labels_device(ehx_space* s, void* stream, size_t n_queries, const float* d_queries, uint32_t k, uint32_t label_col,
+                             uint32_t n_want, const uint32_t* d_want /* [n_queries][n_want] */,
+                             const uint32_t* d_want_count /* [n_queries] or NULL = n_want each */, uint64_t* d_out_ids,
+                             float* d_out_dist, uint32_t* d_out_count);
+/* ... from host pointers: the H2D / D2H copies of queries and results around it. */
+int ehx_knn_by_labels(ehx_space* s, size_t n_queries, const float* queries, uint32_t k, uint32_t label_col, uint32_t n_want,
+                      const uint32_t* want, const uint32_t* want_count, uint64_t* out_ids, float* out_dist, uint32_t* out_count);
 /* Partitioned grouped kNN on STORED columns: group_col holds the entity of every row (EHX_GROUP_NONE: a group of its own —
  * also every row never given a value), label_col the tenant.  ONE snapshot n_pub of the row count; byte for byte what
  * ehx_knn_grouped_labeled_device returns when given the two stored columns of that prefix with n_labels = n_pub, with that
